@@ -8,7 +8,10 @@ Workload (BASELINE.json configs[1]): synthetic 4-ch 24 kHz 60 s clips, batch 64 
 12 classes, random-init weights (seed 100), fp32 arithmetic (exact-fp32 MFMA).  Weak scaling: every rank
 processes its own 64 clips.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--seconds S]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--seconds S] [--dump-outputs DIR]
+
+--dump-outputs DIR writes what the last timed step computed (loss, parameters, gradients, BatchNorm statistics) as
+DIR/<name>.npy; inputs and initial weights are seeded, so two builds run with the same arguments compare output for output.
 
 With --gpus N > 1 and no RANK in the environment this process only LAUNCHES: it starts N fresh worker processes
 (one per GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 / a free MASTER_PORT), relays rank 0's JSON line
@@ -503,6 +506,35 @@ def _run_extra_config(name, cfg, torch, modes):
     return ent
 
 
+# ---------------------------------------------------------------------------------------------- --dump-outputs
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(out_dir, torch, model, loss):
+    """What a caller of the timed step holds after its last call: the loss it returned (float64) and the model it updated
+    -- parameters and their gradients in ``model.parameters()`` order, floating-point buffers (BatchNorm running statistics)
+    in ``model.buffers()`` order, each flattened and concatenated (float32).  Independent of the flat-buffer layout the
+    step uses internally.  If the whole exceeds 64 MB, every array larger than its share keeps a fixed, seeded, sorted
+    sample of its elements (the same for the same sizes)."""
+    import numpy as np
+    flat = lambda ts: torch.cat([t.detach().reshape(-1).float() for t in ts]).cpu().numpy() if ts else np.zeros(0, np.float32)  # noqa: E731
+    params = [p for p in model.parameters() if p.requires_grad]
+    arrays = {"loss": loss.detach().double().reshape(-1).cpu().numpy(),
+              "parameters": flat(params),
+              "gradients": flat([p.grad if p.grad is not None else torch.zeros_like(p) for p in params]),
+              "buffers": flat([b for b in model.buffers() if b.is_floating_point()])}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        share = DUMP_LIMIT_BYTES // len(arrays)
+        for name, a in arrays.items():
+            if a.nbytes > share:
+                idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+                arrays[name] = a[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 # ---------------------------------------------------------------------------------------------- worker
 def main():
     ap = argparse.ArgumentParser()
@@ -530,7 +562,12 @@ def main():
                          "`roofline`) or also around the weight gradients and K1 (`all`: +~100 launches x 2 events x ~6.5 us of GPU idle per step)")
     ap.add_argument("--encoder", default="se-resnet34", choices=["se-resnet34", "resnet-conformer"],
                     help="se-resnet34 = the headline workload (BASELINE configs[1]); resnet-conformer = config 4")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last of them computed (loss, parameters, gradients, BatchNorm "
+                         "statistics) as DIR/<name>.npy: the same arguments give the same inputs, so two builds compare output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(self_launch(args.gpus, sys.argv[1:]))
@@ -688,6 +725,8 @@ def main():
         dt = float(tmax)
     loss_val = float(loss.detach())
     step_ms = dt / args.steps * 1e3
+    if args.dump_outputs and rank == 0:            # (before the extra steps below move the parameters on)
+        dump_outputs(args.dump_outputs, torch, trainer.model, loss)
 
     def timed_steps(step_fn, k, w):
         """w untimed + k timed calls, barrier + synchronize on both sides, max over ranks -> ms per step"""

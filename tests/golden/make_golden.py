@@ -192,6 +192,55 @@ def gen_encoder():
     print("head.npz", tuple(hy.shape))
 
 
+def gen_encoder_f64():
+    """``encoder.npz``'s cases with the same filled modules cast to float64.  A float32 run's round-off depends on the CPU and
+    its BLAS / oneDNN kernels (the reference's own float32 outputs sit 3e-4 from float64 on these inputs, the float32 gradients up to
+    7e-3 of their absmax), so the oracle is pinned to the reference in float64, where both agree far below any float32 noise.
+    Inputs come from ``encoder.npz`` (x, probe).  Every array is stored flattened, as the ``strided_sample(numel, 2048)``
+    elements of the whole tensor (gradients: of the whole gradient), to keep the fixture small."""
+    from models.backbones.resnet import SEResnet34
+    from models.linearheads import ADYOLOhead
+    g32 = np.load(os.path.join(HERE, "encoder.npz"))
+    enc = SEResnet34((1, 7, 64, 64), (), make_params())
+    head = ADYOLOhead(256, 256, 12, [45, 45], 5)
+    fill_module_(_Wrap(enc, head))
+    enc.double()
+    head.double()
+    x = torch.from_numpy(g32["x"]).double()
+    probe = torch.from_numpy(g32["probe"]).double()
+    out = {}
+    enc.eval()
+    with torch.no_grad():
+        taps = {}
+        h = enc.conv1(x); h = enc.relu(h); h = enc.bn1(h); taps["stem"] = h
+        h = enc.layer1(h); taps["layer1"] = h
+        h = enc.layer2(h); h = enc.layer3(h); h = enc.layer4(h); taps["layer4"] = h
+        y_eval = enc(x)
+        out["y_eval"] = y_eval.numpy()
+        out["y_eval_b1"] = enc(x[:1]).numpy()
+        out["head_eval"] = head(y_eval).numpy()
+    for k in ("stem", "layer1", "layer4"):
+        out["tap_eval_" + k] = taps[k].numpy()[:, :4]
+    enc.train()
+    enc.lstm.dropout = 0.0
+    xg = x.clone().requires_grad_(True)
+    y_tr = enc(xg)
+    (y_tr * probe).sum().backward()
+    out["y_train"] = y_tr.detach().numpy()
+    out["dx_train"] = xg.grad.numpy()
+    sd = enc.state_dict()
+    named = dict(enc.named_parameters())
+    for key in g32.files:
+        if key.startswith("stat_"):
+            out[key] = sd[key[5:]].numpy()
+        if key.startswith("grad_"):
+            out[key] = named[key[5:]].grad.numpy()
+    print("encoder_f64.npz y_eval dev of float32 %.2e, dx dev %.2e" % (float(np.abs(out["y_eval"] - g32["y_eval"]).max()),
+                                                                     float(np.abs(out["dx_train"] - g32["dx_train"]).max())))
+    out = {k: v.reshape(-1)[strided_sample(v.size, 2048)] for k, v in out.items()}
+    np.savez_compressed(os.path.join(HERE, "encoder_f64.npz"), **out)
+
+
 class _Wrap(torch.nn.Module):
     """Same key prefixes ('encoder.', 'head.') as the reference WrapperModel (wrapper.py:26-47)."""
 
@@ -821,6 +870,7 @@ if __name__ == "__main__":
     flp = gen_labels()
     gen_loss(flp)
     gen_encoder()
+    gen_encoder_f64()
     gen_init()
     gen_seed100_train()
     gen_other_losses()

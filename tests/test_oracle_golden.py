@@ -88,40 +88,87 @@ def test_state_dict_spec_counts():
     assert n_param == 6682093        # 5 999 501 + 682 592
 
 
-def test_encoder_eval_matches_reference():
-    g = np.load(os.path.join(G, "encoder.npz"))
+def _filled_sd_as(dtype):
     enc, head = _filled_sd()
-    x = torch.from_numpy(g["x"])
+    cast = lambda sd: {k: v.to(dtype) if v.is_floating_point() else v for k, v in sd.items()}   # noqa: E731
+    return cast(enc), cast(head)
+
+
+# encoder.npz holds the reference's float32 outputs; encoder_f64.npz the same modules and inputs in float64.  The float32
+# outputs carry the round-off of the CPU and the BLAS / oneDNN kernels they were made with (3e-4 on y_eval, up to 7e-3 of
+# absmax on the gradients, where a few ReLU masks flip), which no other machine reproduces element for element.  So the
+# oracle is pinned to the reference in float64, where the two agree to 1e-14, and its float32 run must stay within
+# float32 round-off of that: the bounds smoke() and the GPU tests hold against the oracle (1e-3 of absmax on outputs,
+# 1e-2 on gradients).  encoder_f64.npz keeps 2048 evenly strided elements of every flattened tensor
+# (make_golden.strided_sample): the same elements are picked here from the oracle's whole tensor.
+F64_RTOL = 1e-9
+F64_SAMPLE = 2048
+
+
+def _sampled(got):
+    flat = np.asarray(got, dtype=np.float64).reshape(-1)
+    return flat[np.arange(0, flat.size, max(1, flat.size // F64_SAMPLE))[:F64_SAMPLE]]
+
+
+def _assert_f64(got, ref, what):
+    np.testing.assert_allclose(_sampled(got), ref, rtol=F64_RTOL, atol=F64_RTOL * max(1.0, float(np.abs(ref).max())),
+                               err_msg=what + " (float64)")
+
+
+def _assert_f32(got, ref, bound, what):
+    dev = float(np.abs(_sampled(got) - ref).max())
+    assert dev <= bound * max(1.0, float(np.abs(ref).max())), "%s (float32): %.3e from float64" % (what, dev)
+
+
+def _encoder_eval(dtype, x):
+    enc, head = _filled_sd_as(dtype)
+    x = x.to(dtype)
     taps = {}
     with torch.no_grad():
-        y = onet.encoder_forward(enc, x, training=False, taps=taps)
-        y1 = onet.encoder_forward(enc, x[:1], training=False)
-        hy = onet.adyolo_head(head, y)
-    np.testing.assert_allclose(y.numpy(), g["y_eval"], rtol=1e-4, atol=2e-5)
-    np.testing.assert_allclose(y1.numpy(), g["y_eval_b1"], rtol=1e-4, atol=2e-5)
-    np.testing.assert_allclose(hy.numpy(), g["head_eval"], rtol=1e-4, atol=1e-4)
+        out = {"y_eval": onet.encoder_forward(enc, x, training=False, taps=taps),
+               "y_eval_b1": onet.encoder_forward(enc, x[:1], training=False)}
+        out["head_eval"] = onet.adyolo_head(head, out["y_eval"])
     for k in ("stem", "layer1", "layer4"):
-        np.testing.assert_allclose(taps[k].numpy()[:, :4], g["tap_eval_" + k], rtol=1e-4, atol=2e-5)
+        out["tap_eval_" + k] = taps[k][:, :4]
+    return {k: v.numpy() for k, v in out.items()}
 
 
-def test_encoder_train_and_grads_match_reference():
-    g = np.load(os.path.join(G, "encoder.npz"))
-    enc, _ = _filled_sd()
+def test_encoder_eval_matches_reference():
+    g32 = np.load(os.path.join(G, "encoder.npz"))
+    g = np.load(os.path.join(G, "encoder_f64.npz"))
+    x = torch.from_numpy(g32["x"])
+    for k, v in _encoder_eval(torch.float64, x).items():
+        _assert_f64(v, g[k], k)
+    for k, v in _encoder_eval(torch.float32, x).items():
+        _assert_f32(v, g[k], 1e-3, k)
+
+
+def _encoder_train(dtype, g32):
+    enc, _ = _filled_sd_as(dtype)
     for k, v in enc.items():
         if v.is_floating_point() and not k.endswith(("running_mean", "running_var")):
             v.requires_grad_(True)
-    x = torch.from_numpy(g["x"]).requires_grad_(True)
+    x = torch.from_numpy(g32["x"]).to(dtype).requires_grad_(True)
     y = onet.encoder_forward(enc, x, training=True, update_stats=True)
-    (y * torch.from_numpy(g["probe"])).sum().backward()
-    np.testing.assert_allclose(y.detach().numpy(), g["y_train"], rtol=1e-4, atol=2e-5)
-    np.testing.assert_allclose(x.grad.numpy(), g["dx_train"], rtol=2e-3, atol=2e-4)
-    for key in g.files:
+    (y * torch.from_numpy(g32["probe"]).to(dtype)).sum().backward()
+    out = {"y_train": y.detach().numpy(), "dx_train": x.grad.numpy()}
+    for key in g32.files:
         if key.startswith("grad_"):
-            got = enc[key[5:]].grad.numpy().reshape(-1)[:g[key].size]
-            ref = g[key].reshape(-1)
-            np.testing.assert_allclose(got, ref, rtol=2e-3, atol=2e-4 * max(1.0, float(np.abs(ref).max())))
+            out[key] = enc[key[5:]].grad.numpy()
         if key.startswith("stat_") and not key.endswith("num_batches_tracked"):
-            np.testing.assert_allclose(enc[key[5:]].detach().numpy(), g[key], rtol=1e-4, atol=1e-5)
+            out[key] = enc[key[5:]].detach().numpy()
+    return out
+
+
+def test_encoder_train_and_grads_match_reference():
+    g32 = np.load(os.path.join(G, "encoder.npz"))
+    g = np.load(os.path.join(G, "encoder_f64.npz"))
+    got64 = _encoder_train(torch.float64, g32)
+    assert len(got64) == 2 + sum(k.startswith(("grad_", "stat_")) and not k.endswith("num_batches_tracked") for k in g32.files)
+    for k, v in got64.items():
+        _assert_f64(v, g[k], k)
+    for k, v in _encoder_train(torch.float32, g32).items():
+        _assert_f32(v, g[k], 1e-2 if k.startswith(("grad_", "dx_")) else 1e-3, k)
 
 
 def test_head_grads_match_reference():

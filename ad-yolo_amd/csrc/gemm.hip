@@ -36,9 +36,9 @@ struct ConvGather {
 };
 
 // Tile shape (round 4): WM x WN waves, each SM x SN accumulator tiles of 32 x 32: BM = 32 WM SM rows x BN = 32 WN SN columns.
-//   4 x 1 x 1 x 2 = 128 x 64 on 256 threads (the form of rounds 1-3; skinny and split-K calls),
-//   4 x 2 x 2 x 2 = 256 x 128 on 512 threads: per MFMA half the global loads (each costs 12-20 ns of the issue port the fp32
-//   MFMA shares) and two thirds of the LDS reads.  Every thread stages 4 + 2 float4 per K tile in both.
+//   4 x 1 x 1 x 2 = 128 x 64 on 256 threads: the form every launch uses.
+//   4 x 2 x 2 x 2 = 256 x 128 on 512 threads was measured in round 4 and is not launched (not faster: see above adyolo_gemm).
+//   Every thread stages 4 + 2 float4 per K tile in both.
 template <bool TA, bool TB, int G = 0, int WM = 4, int WN = 1, int SM = 1, int SN = 2>
 __global__ __launch_bounds__(64 * WM * WN, (WM * WN > 4 ? 1 : 2)) void gemm_kernel(const float *__restrict__ A, const float *__restrict__ B,
                                                       const float *__restrict__ bias, float *__restrict__ C,
@@ -540,28 +540,17 @@ __global__ void scale_dev_kernel(const float4 *__restrict__ a, const float *__re
 
 using namespace adyolo;
 
-// 256 x 128 tiles: built and measured in round 4 -- NOT faster: plain GEMMs 0.85-1.04 x of the
+// 256 x 128 tiles were built and measured in round 4 -- NOT faster: plain GEMMs 0.85-1.04 x of the
 // 128 x 64 form (head dX 0.72 x), implicit-GEMM convolutions 0.89-1.0 x, only the split-K weight-gradient shapes gain 2-4 %
 // (profiles/r04_gemm_tile_ab.txt).  One 8-wave workgroup per CU is the same two waves per SIMD as two 4-wave workgroups, but
-// all eight meet at every barrier.  Kept as an opt-in for that A/B: ADYOLO_GEMM_TILE=big (auto = where >= 256 such tiles
-// exist); the default is the 128 x 64 form everywhere.
+// all eight meet at every barrier.  Every launch uses the 128 x 64 form.
 // plain operands through buffer descriptors: whole K tiles per split and both operands addressable with 31-bit byte offsets
 static int gemm_fast_fetch(int M, int N, int K, int lda, int ldb, int transA, int transB, int klen) {
-    static const char *env = getenv("ADYOLO_GEMM_FETCH");             // "old": the round-3 fetch (A/B measurements)
-    if (env && env[0] == 'o') return 0;
     if (K % GBK != 0 || klen % GBK != 0) return 0;
     const long ea = transA ? ((long)(K - 1) * lda + M) : ((long)(M - 1) * lda + K);
     const long eb = transB ? ((long)(K - 1) * ldb + N) : ((long)(N - 1) * ldb + K);
     const long lim = ((long)1 << 29) - 64;                            // floats: byte offsets (and scalar K offsets) stay below 2^31
     return ea < lim && eb < lim ? 3 : 0;                              // bit 0: operand A, bit 1: operand B
-}
-
-static bool gemm_big_tile(int M, int N, int splits, int batch) {
-    static const char *env = getenv("ADYOLO_GEMM_TILE");
-    if (!env || env[0] == 's') return false;
-    if (env[0] == 'b') return M >= 32 && N >= 32;
-    if (M < 256 || N < 128) return false;
-    return (long)cdiv(M, 256) * cdiv(N, 128) * splits * batch >= 256;
 }
 
 extern "C" int adyolo_scale_dev(const float *a, const float *scalar_dev, float *y, long n, void *stream) {
@@ -587,22 +576,15 @@ extern "C" int adyolo_gemm(const float *A, const float *B, const float *bias, fl
     hipStream_t st = as_stream(stream);
     int klen = cdiv(cdiv(K, splits), GBK) * GBK;
     splits = cdiv(K, klen);
-    const bool big = gemm_big_tile(M, N, splits, 1);
     const int fastg = gemm_fast_fetch(M, N, K, lda, ldb, transA, transB, klen);
-    dim3 grid((unsigned)cdiv(N, big ? 128 : GBN), (unsigned)cdiv(M, big ? 256 : GBM), (unsigned)splits);
+    dim3 grid((unsigned)cdiv(N, GBN), (unsigned)cdiv(M, GBM), (unsigned)splits);
     const size_t slab_stride = splits > 1 ? (size_t)M * N : 0;
     float *out = splits > 1 ? slabs : C;
     GemmBatch bt{0, 0, 0, 0, 0, 0, 0, 1.0f};
     ConvGather cg{};
-#define LAUNCH(TA_, TB_)                                                                                                     \
-    do {                                                                                                                     \
-        if (big)                                                                                                             \
-            hipLaunchKernelGGL((gemm_kernel<TA_, TB_, 0, 4, 2, 2, 2>), grid, dim3(512), 0, st, A, B, bias, out, M, N, K, lda, ldb, \
-                               ldc, klen, slab_stride, N, accumulate, bt, cg, fastg);                                        \
-        else                                                                                                                 \
-            hipLaunchKernelGGL((gemm_kernel<TA_, TB_>), grid, dim3(256), 0, st, A, B, bias, out, M, N, K, lda, ldb, ldc,       \
-                               klen, slab_stride, N, accumulate, bt, cg, fastg);                                             \
-    } while (0)
+#define LAUNCH(TA_, TB_)                                                                                              \
+    hipLaunchKernelGGL((gemm_kernel<TA_, TB_>), grid, dim3(256), 0, st, A, B, bias, out, M, N, K, lda, ldb, ldc, klen, \
+                       slab_stride, N, accumulate, bt, cg, fastg)
     if (transA && transB) LAUNCH(true, true);
     else if (transA) LAUNCH(true, false);
     else if (transB) LAUNCH(false, true);
@@ -681,7 +663,6 @@ extern "C" int adyolo_conv_gemm(const float *src, const float *other, float *out
     ADYOLO_REQUIRE(splits == 1 || slabs, ADYOLO_EINVAL, "conv_gemm: splits > 1 needs a slab workspace");
     const int klen = cdiv(cdiv(K, splits), GBK) * GBK;
     splits = cdiv(K, klen);
-    const bool big = gemm_big_tile(M, Nn, splits, 1);
     // the operand that is NOT gathered goes through the buffer-descriptor fetch: mode 2: A = dy [pixels][Cout] (transposed,
     // lda = Cout); modes 0 / 1: B = the packed filter [Nn][K] (k-major, ldb = K)
     int fastg = mode == 2 ? (gemm_fast_fetch(M, 4, K, Cout, 4, 1, 1, klen) & 1)
@@ -691,24 +672,15 @@ extern "C" int adyolo_conv_gemm(const float *src, const float *other, float *out
     if (fastg && mode != 2 && cg.Cs % GBK == 0 && (mode == 0 || (SH == 1 && SW == 1)) &&
         (long)N * cg.Hs * cg.Ws * cg.Cs + (long)(KH * cg.Ws + KW) * cg.Cs < ((long)1 << 29))
         fastg |= 4;
-    dim3 grid((unsigned)cdiv(Nn, big ? 128 : GBN), (unsigned)cdiv(M, big ? 256 : GBM), (unsigned)splits);
+    dim3 grid((unsigned)cdiv(Nn, GBN), (unsigned)cdiv(M, GBM), (unsigned)splits);
     const size_t slab_stride = splits > 1 ? (size_t)M * Nn : 0;
     float *dst = splits > 1 ? slabs : out;
-    if (mode == 2) {
-        if (big)
-            hipLaunchKernelGGL((gemm_kernel<true, true, 2, 4, 2, 2, 2>), grid, dim3(512), 0, st, other, src, bias, dst, M, Nn, K,
-                               Cout, 0, Nn, klen, slab_stride, Nn, 0, bt, cg, fastg);
-        else
-            hipLaunchKernelGGL((gemm_kernel<true, true, 2>), grid, dim3(256), 0, st, other, src, bias, dst, M, Nn, K, Cout, 0,
-                               Nn, klen, slab_stride, Nn, 0, bt, cg, fastg);
-    } else {
-        if (big)
-            hipLaunchKernelGGL((gemm_kernel<false, false, 1, 4, 2, 2, 2>), grid, dim3(512), 0, st, src, other, bias, dst, M, Nn, K,
-                               0, mode == 0 ? Kp : Kq, Nn, klen, slab_stride, Nn, 0, bt, cg, fastg);
-        else
-            hipLaunchKernelGGL((gemm_kernel<false, false, 1>), grid, dim3(256), 0, st, src, other, bias, dst, M, Nn, K, 0,
-                               mode == 0 ? Kp : Kq, Nn, klen, slab_stride, Nn, 0, bt, cg, fastg);
-    }
+    if (mode == 2)
+        hipLaunchKernelGGL((gemm_kernel<true, true, 2>), grid, dim3(256), 0, st, other, src, bias, dst, M, Nn, K, Cout, 0,
+                           Nn, klen, slab_stride, Nn, 0, bt, cg, fastg);
+    else
+        hipLaunchKernelGGL((gemm_kernel<false, false, 1>), grid, dim3(256), 0, st, src, other, bias, dst, M, Nn, K, 0,
+                           mode == 0 ? Kp : Kq, Nn, klen, slab_stride, Nn, 0, bt, cg, fastg);
     int rc = check_launch("conv_gemm");
     if (rc || splits == 1) return rc;
     const size_t total = (size_t)M * Nn;

@@ -6,33 +6,30 @@ parameter gradients, so ``loss.backward()`` works exactly as in the reference's 
 Activations are channels-last float32: [N][T][F][C].
 """
 import os
+from typing import NamedTuple
 
 import torch
 
 from . import ops
 
-# Fusion switches (all on by default; the env override exists so that A/B timings can be taken in one process)
-FUSE_AFFINE = os.environ.get("ADYOLO_FUSE_AFFINE", "1") != "0"   # BN1 affine applied while conv2 stages its input
-FUSE_STATS = os.environ.get("ADYOLO_FUSE_STATS", "1") != "0"     # BN statistics from the conv epilogue
-FUSE_DR = os.environ.get("ADYOLO_FUSE_DR", "1") != "0"           # identity-shortcut gradient formed in the dgrad epilogue
+# Fusions of the SE-ResNet block, all taken unconditionally (measured reasons in DESIGN.md):
+#  * BN1's affine is applied while conv2 stages its input: bn1(a) is never written;
+#  * BatchNorm statistics come from the convolution epilogues (per-patch sums), not from a separate read pass;
+#  * the identity-shortcut gradient de * (e > 0) is formed in the data-gradient epilogue of conv1;
+#  * the block's final ReLU mask (e > 0) is written as bits by se_tail_fwd (1/32 of the bytes of e), and the two backward passes
+#    of the SE tail read the bits instead of e: 7 -> 5.06 tensor passes for se_tail_bwd;
+#  * SE / BN2 backward sums of block A come from the dgrad(conv1) epilogue of the identity-shortcut block B that follows it: the
+#    launch that produces dA = conv1_dgrad(da_B) + de_B * (e_B > 0) also sums dA * (e_A > 0) and dA * (e_A > 0) * xhat(c_A) per
+#    patch (stat_mask = the bits of e_A, stat_aux = c_A), so A's backward skips its three-tensor reduction pass (BlockLink).
+#    Round 1, with e_A read as floats, this cost what it saved (168.5 vs 168.3 ms per step); round 2, with the masks read as
+#    bits, it wins 0.3-0.5 ms per step (160.45 / 160.72 -> 160.18 ms in one session);
+#  * the stem's BatchNorm output is never written: the stem hands relu(conv(x)) and (scale, shift) to the first block, which
+#    applies the affine while conv1 / its weight-gradient stage the tensor and while the SE tail reads the identity shortcut.
+# The switches below stay because tests use their off side as a reference (the env override takes A/B timings in one process).
 # BN1 backward sums from the dgrad(conv2) epilogue (no separate read pass over dy and the BatchNorm input).  With the direct
 # kernel's scalar epilogue and a one-stage tile reduction this was 7 % slower; with the Winograd kernel's float4 epilogue and
 # the two-stage adyolo_bn_bwd_tiles it measures 173.5 -> 171.0 ms per step, so it is on (ADYOLO_FUSE_BNBWD=0 switches it off)
 FUSE_BNBWD = os.environ.get("ADYOLO_FUSE_BNBWD", "1") != "0"
-# SE / BN2 backward sums of block A from the dgrad(conv1) epilogue of the identity-shortcut block B that follows it: the
-# launch that produces dA = conv1_dgrad(da_B) + de_B * (e_B > 0) also sums dA * (e_A > 0) and dA * (e_A > 0) * xhat(c_A) per
-# patch (stat_mask = e_A = B's input, stat_aux = c_A), so A's backward skips its three-tensor reduction pass.  Active for 12
-# of the 16 blocks, bit-compatible with the unfused path in the golden tests, but the two extra tensors the epilogue
-# reads cost what the removed pass saved (168.5 vs 168.3 ms per step) in round 1.  Round 2: with the ReLU masks read as
-# BITS (stat_mask and addend_mask of the epilogue move 1/32 of the bytes) the fusion wins 0.3-0.5 ms per step
-# (160.45 / 160.72 -> 160.18 ms in one session) and is on; ADYOLO_FUSE_SEBWD=0 switches it off.
-FUSE_SEBWD = os.environ.get("ADYOLO_FUSE_SEBWD", "1") != "0"
-# The block's final ReLU mask (e > 0) is written as bits by se_tail_fwd (1/32 of the bytes of e) and the two backward passes
-# of the SE tail read the bits instead of e: 7 -> 5.06 tensor passes for se_tail_bwd.
-FUSE_MASKBITS = os.environ.get("ADYOLO_FUSE_MASKBITS", "1") != "0"
-# The stem's BatchNorm output is never written: the stem hands relu(conv(x)) and (scale, shift) to the first block, which
-# applies the affine while conv1 / its weight-gradient stage the tensor and while the SE tail reads the identity shortcut.
-FUSE_STEM_AFFINE = os.environ.get("ADYOLO_FUSE_STEM_AFFINE", "1") != "0"
 # the tail of the last block in front of a pooled stage boundary writes avgpool2(e) + the mask bits of e, never e (round 6)
 FUSE_POOL = os.environ.get("ADYOLO_FUSE_POOL", "1") != "0"
 FUSE_POOL_BWD = os.environ.get("ADYOLO_FUSE_POOL_BWD", "1") != "0"      # ... and its backward never reads a full-size de
@@ -44,8 +41,21 @@ class BlockLink:
 
     def __init__(self):
         self.cc = self.mean2 = self.invstd2 = self.tiles = self.ebits = None
-        self.affine = self.stem_bn = None        # (stem hand-over: see StemFn / FUSE_STEM_AFFINE)
-        self.prepooled = False                   # A wrote avgpool2(e) instead of e (FUSE_POOL): B must not pool again
+        self.affine = self.stem_bn = None        # (stem hand-over: see StemFn)
+        self.prepooled = None                    # (H, W) of avgpool2(e) when A wrote that instead of e (FUSE_POOL): B must not pool again
+
+
+class BlockArgs(NamedTuple):
+    """The non-tensor operands of ``SEBlockFn.forward`` (``SEBasicBlock.forward`` builds them)."""
+    bn1: object
+    bn2: object
+    bnd: object = None              # BatchNorm of the projection shortcut, or None
+    link_in: object = None          # BlockLink shared with the block below / above
+    link_out: object = None
+    in_affine: tuple = None         # (scale, shift): the input is seen through this per-channel affine (the stem's BatchNorm)
+    stem_holder: object = None      # BlockLink of the stem: its BatchNorm backward sums come from our dgrad
+    packs: tuple = None             # (u_fwd1, u_dgrad1, u_fwd2, u_dgrad2) from ops.WinoPackSet, or None
+    pool_next: bool = False         # the NEXT block starts with AvgPool2d(2, 2): see FUSE_POOL
 
 
 def _c(t):
@@ -229,16 +239,12 @@ class StemFn(torch.autograd.Function):
         holder.affine = (scale, shift) for the consumer (SEBlockFn's ``p_affine``); the incoming gradient is then the
         gradient w.r.t. the affine's output, exactly what the consumer returns for its input."""
         wpk, _ = ops.pack_w3x3(w, x8.shape[-1], want_dgrad=False)      # 8-channel pixels (FOA: 7 features) or 32 (MIC: 10)
-        if training and FUSE_STATS:
+        if training:
             a, st = ops.conv3x3(x8, wpk, w.shape[0], bias=b, relu=True, want_stats=True)
             _, mean, invstd, scale, shift = _BNState(bn).stats_tiles(st, a, affine=(gamma, beta))
         else:
             a = ops.conv3x3(x8, wpk, w.shape[0], bias=b, relu=True)
-            if training:
-                _, mean, invstd = _BNState(bn).stats(a, True)
-                scale, shift = ops.bn_scale_shift(gamma, beta, mean, invstd)
-            else:
-                mean, invstd, scale, shift = _BNState(bn).eval_affine(gamma, beta)
+            mean, invstd, scale, shift = _BNState(bn).eval_affine(gamma, beta)
         ctx.holder = None
         if holder is not None:
             holder.affine = (scale, shift)
@@ -288,127 +294,83 @@ class SEBlockFn(torch.autograd.Function):
     """
 
     @staticmethod
-    def forward(ctx, x, training, pool, bns, w1, g1, b1, w2, g2, b2, fw1, fb1, fw2, fb2, wd=None, gd=None, bd=None):
-        bn1, bn2, bnd, link_in, link_out = bns[:5]
-        p_aff = bns[5] if len(bns) > 5 else None      # (scale, shift): the input is seen through this per-channel affine
-        ctx.stem_holder = bns[6] if len(bns) > 6 else None    # BlockLink of the stem: its BatchNorm backward sums come from our dgrad
-        packs = bns[7] if len(bns) > 7 else None              # (u_fwd1, u_dgrad1, u_fwd2, u_dgrad2) from ops.WinoPackSet, or None
-        pool_next = bool(bns[8]) if len(bns) > 8 else False   # the NEXT block starts with AvgPool2d(2, 2): see FUSE_POOL below
-        prepooled = pool and link_in is not None and link_in.prepooled   # ... and the block BELOW handed us avgpool2(its output)
+    def forward(ctx, x, training, pool, args, w1, g1, b1, w2, g2, b2, fw1, fb1, fw2, fb2, wd=None, gd=None, bd=None):
+        link_in, link_out, p_aff = args.link_in, args.link_out, args.in_affine
+        prepooled = pool and link_in is not None and link_in.prepooled is not None   # the block BELOW handed us avgpool2(its output)
+        if prepooled and tuple(x.shape[1:3]) != link_in.prepooled:
+            raise ValueError("SEBlockFn: link_in.prepooled says the block below wrote a %d x %d map, but the input is %d x %d"
+                             % (link_in.prepooled + tuple(x.shape[1:3])))
         if p_aff is not None and (pool or wd is not None):
             raise NotImplementedError("p_affine is only supported for identity-shortcut blocks without pooling")
         p = ops.avgpool2(x) if (pool and not prepooled) else x
         n, h, w_, cin = p.shape
         c = w1.shape[0]
-        if packs is not None:
-            # (ops.DualPack -> the form this launch size runs on: F(4x4) when the grid fills the chip, else F(2x2))
-            # (the data-gradient of conv1 always carries an addend -- the shortcut's gradient -- in its epilogue)
-            # (conv1's data-gradient pack is picked at the end of this forward pass, when its operand combination is known: with
-            #  32-channel output blocks only the persistent F(4x4) kernel exists, and it is built for certain combinations)
-            wpk1, wpk1d, wpk2, wpk2d = [pk.pick(n, h, w_, co, ad) if (isinstance(pk, ops.DualPack) and i != 1) else pk
-                                        for i, (pk, co, ad) in enumerate(zip(packs, (c, cin, c, c), (False, True, False, False)))]
+        if args.packs is not None:
+            # ops.DualPack or a plain pack: ops.conv3x3 picks the form each launch runs on from its size and its operands (F(4x4)
+            # when the grid fills the chip, else F(2x2); with 32-channel output blocks only the persistent F(4x4) kernel exists,
+            # and it is built for certain operand combinations)
+            wpk1, wpk1d, wpk2, wpk2d = args.packs
         else:
             wpk1, wpk1d = ops.pack_w3x3(w1, cin)
             wpk2, wpk2d = ops.pack_w3x3(w2, c)
-        if training and FUSE_STATS:
+        if training:
             a, st1 = ops.conv3x3(p, wpk1, c, relu=True, want_stats=True, in_affine=p_aff)
-            _, mean1, invstd1, scale1, shift1 = _BNState(bn1).stats_tiles(st1, a, affine=(g1, b1))
+            _, mean1, invstd1, scale1, shift1 = _BNState(args.bn1).stats_tiles(st1, a, affine=(g1, b1))
         else:
             a = ops.conv3x3(p, wpk1, c, relu=True, in_affine=p_aff)
-            if training:
-                _, mean1, invstd1 = _BNState(bn1).stats(a, True)
-                scale1, shift1 = ops.bn_scale_shift(g1, b1, mean1, invstd1)
-            else:
-                mean1, invstd1, scale1, shift1 = _BNState(bn1).eval_affine(g1, b1)
-        if FUSE_AFFINE:
-            # BN1's affine is applied while conv2 stages its input: bn1(a) is never written to HBM
-            src, aff = a, (scale1, shift1)
+            mean1, invstd1, scale1, shift1 = _BNState(args.bn1).eval_affine(g1, b1)
+        # BN1's affine is applied while conv2 stages its input: bn1(a) is never written to HBM
+        cc, st2 = ops.conv3x3(a, wpk2, c, in_affine=(scale1, shift1), want_stats=True)
+        if training:
+            ssum2, mean2, invstd2, scale2, shift2 = _BNState(args.bn2).stats_tiles(st2, cc, affine=(g2, b2))
         else:
-            src, aff = ops.affine(a, scale1, shift1), None
-        if FUSE_STATS:
-            cc, st2 = ops.conv3x3(src, wpk2, c, in_affine=aff, want_stats=True)
-            scale2 = None
-            if training:
-                ssum2, mean2, invstd2, scale2, shift2 = _BNState(bn2).stats_tiles(st2, cc, affine=(g2, b2))
-            else:
-                ssum2, _, _ = _BNState(bn2).stats_tiles(st2, cc, update=False)
-                mean2, invstd2, scale2, shift2 = _BNState(bn2).eval_affine(g2, b2)
-        else:
-            scale2 = None
-            cc = ops.conv3x3(src, wpk2, c, in_affine=aff)
-            if training:
-                ssum2, mean2, invstd2 = _BNState(bn2).stats(cc, True)
-            else:
-                ssum2, _, _ = ops.bn_stats(cc, None, None)
-                mean2, invstd2, scale2, shift2 = _BNState(bn2).eval_affine(g2, b2)
-        if scale2 is None:
-            scale2, shift2 = ops.bn_scale_shift(g2, b2, mean2, invstd2)
+            ssum2, _, _ = _BNState(args.bn2).stats_tiles(st2, cc, update=False)
+            mean2, invstd2, scale2, shift2 = _BNState(args.bn2).eval_affine(g2, b2)
         pooled, hid, s = ops.se_fc_fwd(ssum2, scale2, shift2, fw1, fb1, fw2, fb2, h * w_)
         q = None
         meand = invstdd = None
         if wd is not None:
             q = ops.gemm(p, wd, n * h * w_, c, cin, cin, cin).view(n, h, w_, c)
             if training:
-                _, meand, invstdd = _BNState(bnd).stats(q, True)
+                _, meand, invstdd = _BNState(args.bnd).stats(q, True)
                 scaled, shiftd = ops.bn_scale_shift(gd, bd, meand, invstdd)
             else:
-                meand, invstdd, scaled, shiftd = _BNState(bnd).eval_affine(gd, bd)
+                meand, invstdd, scaled, shiftd = _BNState(args.bnd).eval_affine(gd, bd)
             r, raff = q, (scaled, shiftd)            # the downsample BatchNorm is applied while the tail reads q
         else:
             r, raff = p, p_aff
         # FUSE_POOL: in front of a pooled stage boundary the tail writes avgpool2(e) and the ReLU-mask bits of e; e itself -- read
         # only by that pooling in the forward pass, through its bits in the backward pass -- never goes to HBM (round 6)
-        pool_out = FUSE_POOL and pool_next and link_out is not None and ops.se_tail_pool_ok(h, w_, c) and \
-            (FUSE_MASKBITS or not training)
+        pool_out = FUSE_POOL and args.pool_next and link_out is not None and ops.se_tail_pool_ok(h, w_, c)
         if pool_out:
             e, ebits = ops.se_tail_fwd(cc, r, scale2, shift2, s, want_mask=training, r_affine=raff, pool_hw=(h, w_))
-            link_out.prepooled = True
-        elif training and FUSE_MASKBITS:
+            link_out.prepooled = (e.shape[1], e.shape[2])
+        elif training:
+            # the ReLU mask (e > 0) as bits for the backward passes (None when the shape has none: HW * C / 4 % 64 != 0)
             e, ebits = ops.se_tail_fwd(cc, r, scale2, shift2, s, want_mask=True, r_affine=raff)
         else:
             e, ebits = ops.se_tail_fwd(cc, r, scale2, shift2, s, r_affine=raff), None
-        ctx.link_in = link_in if (FUSE_SEBWD and FUSE_DR and training and link_in is not None and not pool
-                                  and link_in.cc is not None) else None
-        ctx.link_out = link_out if (FUSE_SEBWD and training) else None
+        ctx.link_in = link_in if (training and link_in is not None and not pool and link_in.cc is not None) else None
+        ctx.link_out = link_out if training else None
         if ctx.link_out is not None:
             link_out.cc, link_out.mean2, link_out.invstd2, link_out.tiles = cc, mean2, invstd2, None
             link_out.ebits = ebits
         ctx.training, ctx.pool, ctx.has_down = training, pool and not prepooled, wd is not None
         ctx.pool_out = (h, w_) if pool_out else None
         ctx.in_hw = (x.shape[1], x.shape[2])
-        ctx.fused_affine = aff is not None
-        ctx.a_unfused = None if aff is not None else a      # (A/B switch only; keeps `a` alive for BN1's backward)
-        ctx.has_bits = ebits is not None
         ctx.p_aff = p_aff
+        ctx.stem_holder = args.stem_holder
+        ctx.dgrad_packs = (wpk1d, wpk2d)       # (not saved tensors: a DualPack is picked by ops.conv3x3 in backward)
         # storage addresses of the parameters whose gradients can be written straight into the flat buffer (GradSink)
         ctx.ptrs = (w1.data_ptr(), g1.data_ptr(), b1.data_ptr(), w2.data_ptr(),
                     (fb2.data_ptr(), fw2.data_ptr(), fb1.data_ptr(), fw1.data_ptr(), b2.data_ptr(), g2.data_ptr()))
         ctx.wshapes = (tuple(w1.shape), tuple(w2.shape))
         # ... and of the shortcut projection (1x1 convolution + BatchNorm; round 6: three AccumulateGrad adds fewer per such block)
         ctx.down_ptrs = (wd.data_ptr(), gd.data_ptr(), bd.data_ptr(), tuple(wd.shape)) if wd is not None else None
-        if isinstance(wpk1d, ops.DualPack):
-            # the operand combination backward() will launch conv1's data-gradient with (see there): projection shortcut -> addend
-            # (+ statistics against the block above's BatchNorm input with its ReLU-mask bits); identity -> addend + mask bits +
-            # statistics / mask bits of the block above; the very first block -> addend + mask bits + statistics against the stem's
-            # BatchNorm input (combination 15, persistent since round 6); the other combinations (the unfused ones) have no
-            # persistent F(4x4) form
-            lk = ctx.link_in
-            if wd is not None:
-                p_ok = lk is None or lk.ebits is not None
-            elif lk is not None:
-                p_ok = ebits is not None and lk.ebits is not None
-            else:
-                stem15 = FUSE_DR and ebits is not None and ctx.stem_holder is not None and \
-                    getattr(ctx.stem_holder, "stem_bn", None) is not None
-                p_ok = (not FUSE_DR) or stem15
-            wpk1d = wpk1d.pick(n, h, w_, cin, True, p_ok)
-        tensors = [p, src, scale1, cc, None if pool_out else e, g1, mean1, invstd1, g2, b2, mean2, invstd2, ssum2, pooled, hid, s, fw1, fw2,
-                   wpk1d, wpk2d, shift1]
-        names = ["p", "a", "scale1", "cc", "e", "g1", "mean1", "invstd1", "g2", "b2", "mean2", "invstd2", "ssum2", "pooled",
-                 "hid", "s", "fw1", "fw2", "wpk1d", "wpk2d", "shift1"]
-        if ebits is not None:
-            tensors.append(ebits)
-            names.append("ebits")
+        tensors = [p, a, scale1, shift1, cc, None if pool_out else e, ebits, g1, mean1, invstd1, g2, b2, mean2, invstd2, ssum2,
+                   pooled, hid, s, fw1, fw2]
+        names = ["p", "a", "scale1", "shift1", "cc", "e", "ebits", "g1", "mean1", "invstd1", "g2", "b2", "mean2", "invstd2",
+                 "ssum2", "pooled", "hid", "s", "fw1", "fw2"]
         if wd is not None:
             tensors += [q, wd, gd, meand, invstdd]
             names += ["q", "wd", "gd", "meand", "invstdd"]
@@ -421,14 +383,14 @@ class SEBlockFn(torch.autograd.Function):
         if not ctx.training:
             raise NotImplementedError("backward through eval-mode BatchNorm is not part of the hot path")
         t = ctx.saved_tensors
-        (p, src, scale1, cc, e, g1, mean1, invstd1, g2, b2, mean2, invstd2, ssum2, pooled, hid, s, fw1, fw2, wpk1d,
-         wpk2d, shift1) = t[:21]
+        (p, a, scale1, shift1, cc, e, ebits, g1, mean1, invstd1, g2, b2, mean2, invstd2, ssum2, pooled, hid, s, fw1,
+         fw2) = t[:20]
+        wpk1d, wpk2d = ctx.dgrad_packs
         n, h, w_, cin = p.shape
         c = cc.shape[-1]
         de = _c(de)
-        ebits_early = t[21] if ctx.has_bits else None
         pooled_hw = None
-        if ctx.pool_out is not None and ebits_early is not None and FUSE_POOL_BWD:
+        if ctx.pool_out is not None and FUSE_POOL_BWD:
             # our output was avgpool2(e): both passes of the tail's backward spread the pooled gradient on the fly, and the
             # apply pass writes the gradient of e itself where the identity shortcut needs it (conv1's data-gradient addend)
             pooled_hw = ctx.pool_out
@@ -437,10 +399,6 @@ class SEBlockFn(torch.autograd.Function):
         tiles = None
         if ctx.link_out is not None and ctx.link_out.tiles is not None:
             tiles, ctx.link_out.tiles = ctx.link_out.tiles, None      # left by the block above (its dgrad produced `de`)
-        nb = 21
-        ebits = None
-        if ctx.has_bits:
-            ebits, nb = t[21], 22
         pw1, pg1, pb1, pw2, pse = ctx.ptrs
         vse = SINK.span(pse)                  # [fc.2.bias | fc.2.weight | fc.0.bias | fc.0.weight | bn2.bias | bn2.weight] or None
         vw1, vw2 = SINK.view(pw1, ctx.wshapes[0]), SINK.view(pw2, ctx.wshapes[1])
@@ -449,21 +407,16 @@ class SEBlockFn(torch.autograd.Function):
         if not sunk:
             vse = vw1 = vw2 = vg1 = vb1 = None
         de_full = None
-        if pooled_hw is not None and not ctx.has_down and FUSE_DR:
+        if pooled_hw is not None and not ctx.has_down:
             de_full = torch.empty(n, pooled_hw[0], pooled_hw[1], c, dtype=torch.float32, device=de.device)
         dc, dr, dg2, db2, dfw1, dfb1, dfw2, dfb2 = ops.se_tail_bwd(de, e, cc, g2, b2, mean2, invstd2, ssum2, pooled,
                                                                    hid, s, fw1, fw2,
-                                                                   want_dr=ctx.has_down or not FUSE_DR, tile_stats=tiles,
+                                                                   want_dr=ctx.has_down, tile_stats=tiles,
                                                                    mask=ebits, packed_out=vse, pooled_hw=pooled_hw,
                                                                    de_out=de_full)
         if pooled_hw is not None:
             de = de_full                          # (None when nothing below reads it)
-        if ctx.fused_affine:
-            a = src
-            dw2 = ops.conv3x3_wgrad(a, dc, c, in_affine=(scale1, shift1), out=vw2)
-        else:
-            dw2 = ops.conv3x3_wgrad(src, dc, c, out=vw2)
-            a = ctx.a_unfused
+        dw2 = ops.conv3x3_wgrad(a, dc, c, in_affine=(scale1, shift1), out=vw2)
         if FUSE_BNBWD:
             dbb, st = ops.conv3x3(dc, wpk2d, c, want_stats=True, stat_bn=(a, mean1, invstd1))
             da, dg1, db1 = ops.bn_bwd(dbb, a, g1, mean1, invstd1, relu_mask=True, tile_stats=st, out_dgamma=vg1,
@@ -478,7 +431,7 @@ class SEBlockFn(torch.autograd.Function):
             dw1 = dg1 = db1 = dw2 = dg2 = db2 = dfw1 = dfb1 = dfw2 = dfb2 = None
         dwd = dgd = dbd = None
         if ctx.has_down:
-            q, wd, gd, meand, invstdd = t[nb:nb + 5]
+            q, wd, gd, meand, invstdd = t[20:25]
             pwd, pgd, pbd, wdshape = ctx.down_ptrs
             vwd, vgd, vbd = SINK.view(pwd, (wdshape[0], wdshape[1])), SINK.view(pgd), SINK.view(pbd)
             dsunk = sunk and vwd is not None and vgd is not None and vbd is not None
@@ -491,31 +444,24 @@ class SEBlockFn(torch.autograd.Function):
             if dsunk:
                 SINK.done(pwd, pgd, pbd)
                 dwd = dgd = dbd = None
-            dp_res = ops.gemm(dq, wd, rows, cin, c, c, cin, trans_b=True).view(n, h, w_, cin)
-            if ctx.link_in is not None:       # un-pooled stage boundary (stage 4): dp is the gradient of the block above
-                lk = ctx.link_in
-                dp, lk.tiles = ops.conv3x3(da, wpk1d, cin, addend=dp_res, want_stats=True,
-                                           stat_bn=(lk.cc, lk.mean2, lk.invstd2),
-                                           stat_mask=lk.ebits if lk.ebits is not None else p)
-            else:
-                dp = ops.conv3x3(da, wpk1d, cin, addend=dp_res)
+            addend = ops.gemm(dq, wd, rows, cin, c, c, cin, trans_b=True).view(n, h, w_, cin)
+            amask = None
         else:
-            # identity shortcut: its gradient de * (e > 0) is formed inside the dgrad epilogue
-            emask = ebits if ebits is not None else e          # this block's ReLU mask: bits when the forward stored them
-            if ctx.link_in is not None:
-                lk = ctx.link_in
-                dp, lk.tiles = ops.conv3x3(da, wpk1d, cin, addend=de, addend_mask=emask, want_stats=True,
-                                           stat_bn=(lk.cc, lk.mean2, lk.invstd2),
-                                           stat_mask=lk.ebits if lk.ebits is not None else p)
-            elif FUSE_DR and ctx.stem_holder is not None and getattr(ctx.stem_holder, "stem_bn", None) is not None:
-                # first block: dp is the gradient w.r.t. the stem's BatchNorm output -- sum dp and dp * xhat(a_stem) per patch
-                # here, so the stem's backward skips its 2.5 GB reduction pass
-                dp, ctx.stem_holder.tiles = ops.conv3x3(da, wpk1d, cin, addend=de, addend_mask=emask, want_stats=True,
-                                                        stat_bn=ctx.stem_holder.stem_bn)
-            elif FUSE_DR:
-                dp = ops.conv3x3(da, wpk1d, cin, addend=de, addend_mask=emask)
-            else:
-                dp = ops.conv3x3(da, wpk1d, cin, addend=dr)
+            # identity shortcut: its gradient de * (e > 0) is formed inside the dgrad epilogue (the ReLU mask as bits where the
+            # shape has them)
+            addend, amask = de, (ebits if ebits is not None else e)
+        lk, holder = ctx.link_in, ctx.stem_holder
+        if lk is not None:
+            # the block below feeds only us: the same launch sums its SE / BN2 backward statistics (stage 4's projection block
+            # included: an un-pooled stage boundary)
+            dp, lk.tiles = ops.conv3x3(da, wpk1d, cin, addend=addend, addend_mask=amask, want_stats=True,
+                                       stat_bn=(lk.cc, lk.mean2, lk.invstd2), stat_mask=lk.ebits if lk.ebits is not None else p)
+        elif not ctx.has_down and holder is not None and holder.stem_bn is not None:
+            # first block: dp is the gradient w.r.t. the stem's BatchNorm output -- sum dp and dp * xhat(a_stem) per patch
+            # here, so the stem's backward skips its 2.5 GB reduction pass
+            dp, holder.tiles = ops.conv3x3(da, wpk1d, cin, addend=addend, addend_mask=amask, want_stats=True, stat_bn=holder.stem_bn)
+        else:
+            dp = ops.conv3x3(da, wpk1d, cin, addend=addend, addend_mask=amask)
         dx = ops.avgpool2_bwd(dp, ctx.in_hw[0], ctx.in_hw[1]) if ctx.pool else dp
         return (dx, None, None, None, dw1, dg1, db1, dw2, dg2, db2, dfw1, dfb1, dfw2, dfb2, dwd, dgd, dbd)
 

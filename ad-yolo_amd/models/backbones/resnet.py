@@ -83,15 +83,16 @@ class SEBasicBlock(nn.Module):
             self.downsample = None
 
     def forward(self, x, link_in=None, link_out=None, in_affine=None, stem_holder=None, packs=None, pool_next=False):
-        """link_in / link_out: ``functional.BlockLink`` shared with the block below / above (see FUSE_SEBWD);
+        """link_in / link_out: ``functional.BlockLink`` shared with the block below / above (the SE / BN2 backward sums of
+        the block below come from our conv1 data-gradient epilogue);
         in_affine = (scale, shift): x is seen through this per-channel affine (the stem's un-materialised BatchNorm);
         packs = the Winograd-packed filters of conv1 / conv2 from the encoder's ``ops.WinoPackSet`` (one launch for all);
         pool_next: the block that consumes our output starts with AvgPool2d(2, 2) -- we may hand it the pooled tensor
         (``functional.FUSE_POOL``; ``link_out.prepooled`` tells it)."""
         fc0, fc2 = self.se.fc["0"], self.se.fc["2"]
-        args = [x, self.training, self.pool,
-                (self.bn1, self.bn2, self.downsample["1"] if self.downsample is not None else None, link_in, link_out,
-                 in_affine, stem_holder, packs, pool_next),
+        bargs = Fn.BlockArgs(self.bn1, self.bn2, self.downsample["1"] if self.downsample is not None else None, link_in,
+                             link_out, in_affine, stem_holder, packs, bool(pool_next))
+        args = [x, self.training, self.pool, bargs,
                 self.conv1.weight, self.bn1.weight, self.bn1.bias, self.conv2.weight, self.bn2.weight, self.bn2.bias,
                 fc0.weight, fc0.bias, fc2.weight, fc2.bias]
         if self.downsample is not None:
@@ -193,11 +194,11 @@ class SEResnet34(nn.Module):
             raise RuntimeError("SEResnet34: %d input features need %d-channel pixels (got %d)"
                                % (self.in_channels, 8 if self.in_channels <= 8 else 32, x8.shape[-1]))
         first = self.layer1[0]
-        holder = Fn.BlockLink() if (Fn.FUSE_STEM_AFFINE and not first.pool and first.downsample is None) else None
+        holder = Fn.BlockLink() if (not first.pool and first.downsample is None) else None
         y = Fn.StemFn.apply(x8, self.conv1.weight, self.conv1.bias, self.bn1.weight, self.bn1.bias, self.bn1,
                             self.training, holder)
         stem_affine = holder.affine if holder is not None else None     # the stem's BatchNorm is applied by its consumer
-        link = None                              # BlockLink between consecutive blocks (functional.FUSE_SEBWD)
+        link = None                              # BlockLink between consecutive blocks (functional.BlockLink)
         blocks = [blk for li in range(1, 5) for blk in getattr(self, "layer%d" % li)]
         packs = None
         if ops.conv_algo() in ("winograd", "winograd4"):     # every block filter packed by ONE launch (two with winograd4)

@@ -437,6 +437,13 @@ def test_se_basic_block_matches_oracle(ops, cin, c, pool, n, h, w, training):
         for name, buf in blk.named_buffers():
             if "running" in name:
                 assert_close(buf, osd["blk." + name], 1e-4, "block buffer " + name)
+    if pool:
+        # a link saying the block below already pooled to H/2 x W/2 (functional.FUSE_POOL) does not match a full-size input
+        from adyolo_amd import functional as Fn
+        lk = Fn.BlockLink()
+        lk.prepooled = (h // 2, w // 2)
+        with pytest.raises(ValueError, match="prepooled"):
+            blk(xg, link_in=lk)
 
 
 def test_sap_gru_ln_linear_match_oracle(ops):

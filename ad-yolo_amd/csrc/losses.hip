@@ -3,6 +3,7 @@
 //   * ACCDOA   MSE                                               loss.py:57-67
 //   * SEDDOA   BCE + 1000 * (masked) MSE                         loss.py:32-54
 //   * ADPIT    13-permutation min-MSE (multi-ACCDOA)             loss.py:70-153
+//   * SEDDOA / ACCDOA / ADPIT inference decode                   datasets.py:536-739 (thresholds + unify stay on the host)
 // Each loss is ONE pass over the network output that also writes d(loss)/d(output) (HBM-bound: read output +
 // target, write gradient), per-workgroup partial sums combined in double by a one-workgroup finishing kernel.
 #include "common.hpp"
@@ -151,6 +152,71 @@ __global__ __launch_bounds__(256) void sum_final_kernel(const float *__restrict_
     if (threadIdx.x == 0) loss[0] = (float)(s / denom);
 }
 
+// Class-wise inference decode: one thread per (frame, class) record, threshold-free (the conf threshold and the ADPIT
+// unify decision run on the host, postprocess.py).  Records, CLASSWISE_REC(mode) floats each:
+//   seddoa  [act, x, y, z]   act = out[c]; xyz = out[C+c], out[2C+c], out[3C+c]
+//   accdoa  [act, x, y, z]   act = sqrt(x*x + y*y + z*z); xyz = out[c], out[C+c], out[2C+c]
+//   adpit   [act0, act1, act2, x0, y0, z0, x1, y1, z1, x2, y2, z2, d01, d12, d20, 0]; track k at out[3kC]
+// Activities are rounded step by step in that order (no contraction), so they equal numpy's float32
+// np.sqrt(x**2 + y**2 + z**2) bit for bit; the distances follow distance_between_cartesian_coordinates
+// (utils/seld_metrics.py:97-114) in fp32.  Lanes of a wave read consecutive classes of one column (coalesced) and write
+// consecutive records.
+// Bit-exact pieces.  Without OCML's rounded operations HIP's __fmul_rn / __fadd_rn are plain operators (the compiler fuses
+// x*x + y*y into one FMA) and __fsqrt_rn is the hardware v_sqrt_f32 (within 1 ulp): a product is taken as fma(x, y, +0)
+// (rounded once, never contracted further) and the square root is corrected to the rounded-to-nearest neighbour by the
+// sign of its exact residual, as LLVM lowers a correctly rounded f32 sqrt for gfx9.
+__device__ __forceinline__ float mul_rn(float x, float y) { return __builtin_fmaf(x, y, 0.f); }
+__device__ __forceinline__ float sqrt_rn(float a) {
+    const bool tiny = a < 0x1p-96f;
+    const float x = tiny ? a * 0x1p+32f : a;
+    const float s = __builtin_amdgcn_sqrtf(x);
+    const float dn = __int_as_float(__float_as_int(s) - 1), up = __int_as_float(__float_as_int(s) + 1);
+    float r = s;
+    if (__builtin_fmaf(-dn, s, x) <= 0.f) r = dn;
+    if (__builtin_fmaf(-up, s, x) > 0.f) r = up;
+    r = tiny ? r * 0x1p-16f : r;
+    return (x == 0.f || __builtin_isinf(x)) ? a : r;
+}
+__device__ __forceinline__ float norm3_rn(float x, float y, float z) {
+    return sqrt_rn((mul_rn(x, x) + mul_rn(y, y)) + mul_rn(z, z));
+}
+__device__ __forceinline__ float cart_dist_deg(float x1, float y1, float z1, float x2, float y2, float z2) {
+    const float n1 = sqrt_rn(((mul_rn(x1, x1) + mul_rn(y1, y1)) + mul_rn(z1, z1)) + 1e-10f);
+    const float n2 = sqrt_rn(((mul_rn(x2, x2) + mul_rn(y2, y2)) + mul_rn(z2, z2)) + 1e-10f);
+    x1 /= n1, y1 /= n1, z1 /= n1, x2 /= n2, y2 /= n2, z2 /= n2;
+    float d = (mul_rn(x1, x2) + mul_rn(y1, y2)) + mul_rn(z1, z2);
+    d = fminf(fmaxf(d, -1.f), 1.f);
+    return acosf(d) * 180.f / 3.14159265358979f;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void classwise_decode_kernel(const float *__restrict__ out, float *__restrict__ dec,
+                                                               long n_frames, int C) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_frames * C) return;
+    const long f = i / C;
+    const int c = (int)(i - f * C);
+    if (MODE == ADYOLO_CLASSWISE_ADPIT) {
+        const float *o = out + f * 9 * C + c;
+        float v[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) v[k] = o[(long)k * C];
+        f32x4 *d = reinterpret_cast<f32x4 *>(dec + i * 16);
+        d[0] = f32x4{norm3_rn(v[0], v[1], v[2]), norm3_rn(v[3], v[4], v[5]), norm3_rn(v[6], v[7], v[8]), v[0]};
+        d[1] = f32x4{v[1], v[2], v[3], v[4]};
+        d[2] = f32x4{v[5], v[6], v[7], v[8]};
+        d[3] = f32x4{cart_dist_deg(v[0], v[1], v[2], v[3], v[4], v[5]), cart_dist_deg(v[3], v[4], v[5], v[6], v[7], v[8]),
+                     cart_dist_deg(v[6], v[7], v[8], v[0], v[1], v[2]), 0.f};
+    } else if (MODE == ADYOLO_CLASSWISE_ACCDOA) {
+        const float *o = out + f * 3 * C + c;
+        const float x = o[0], y = o[C], z = o[2 * C];
+        reinterpret_cast<f32x4 *>(dec)[i] = f32x4{norm3_rn(x, y, z), x, y, z};
+    } else {
+        const float *o = out + f * 4 * C + c;
+        reinterpret_cast<f32x4 *>(dec)[i] = f32x4{o[0], o[C], o[2 * C], o[3 * C]};
+    }
+}
+
 static inline int loss_grid(long n) {
     long g = (n + 255) / 256;
     return (int)(g > LOSSES_BLOCKS ? LOSSES_BLOCKS : (g < 1 ? 1 : g));
@@ -206,4 +272,21 @@ extern "C" int adyolo_adpit_loss(const float *out, const float *tgt, float *loss
     if (rc) return rc;
     hipLaunchKernelGGL(sum_final_kernel, dim3(1), dim3(256), 0, st, partial, g, (double)total, loss);
     return check_launch("adpit_final");
+}
+
+extern "C" int adyolo_classwise_decode(const float *out, float *dec, long n_frames, int C, int mode, void *stream) {
+    ADYOLO_REQUIRE(out && dec && n_frames > 0 && C > 0 && ((uintptr_t)dec & 15) == 0, ADYOLO_EINVAL,
+                   "classwise_decode: bad arguments");
+    ADYOLO_REQUIRE(mode == ADYOLO_CLASSWISE_SEDDOA || mode == ADYOLO_CLASSWISE_ACCDOA || mode == ADYOLO_CLASSWISE_ADPIT,
+                   ADYOLO_ENOSUP, "classwise_decode: unknown mode %d", mode);
+    const long total = n_frames * C;
+    const dim3 grid(cdiv(total, 256)), block(256);
+    hipStream_t st = as_stream(stream);
+    if (mode == ADYOLO_CLASSWISE_ADPIT)
+        hipLaunchKernelGGL(classwise_decode_kernel<ADYOLO_CLASSWISE_ADPIT>, grid, block, 0, st, out, dec, n_frames, C);
+    else if (mode == ADYOLO_CLASSWISE_ACCDOA)
+        hipLaunchKernelGGL(classwise_decode_kernel<ADYOLO_CLASSWISE_ACCDOA>, grid, block, 0, st, out, dec, n_frames, C);
+    else
+        hipLaunchKernelGGL(classwise_decode_kernel<ADYOLO_CLASSWISE_SEDDOA>, grid, block, 0, st, out, dec, n_frames, C);
+    return check_launch("classwise_decode");
 }

@@ -248,7 +248,8 @@ class FoaDataset(torch.utils.data.Dataset):
     ``init_remaining_file_from_list`` for resume) and the same CSV label reader -- but ``__getitem__`` stops before the
     arithmetic: it returns ``(pcm int16 (T, 4), comb_no, label_rows)``.  Normalisation, rotation of the audio and the
     features run on the GPU (``AudioStager`` -> ``rotate_audio`` -> ``FeatureExtractor``); the label half of the rotation
-    and the AD-YOLO label encoding stay here on the host, as in the reference's DataLoader workers."""
+    and the label encoding stay here on the host, as in the reference's DataLoader workers.  ``label_rows``: the AD-YOLO row
+    list, or for ``seddoa | masked-seddoa | accdoa | adpit`` the dense ``ClasswiseLabelEncoder`` tensor (T', ...)."""
 
     def __init__(self, params: dict, set_type: str, is_valid=False, rank=None, world=None):
         """rank / world: data-parallel shard (default: torch.distributed if initialised, else RANK / WORLD_SIZE, else 0 / 1).
@@ -292,9 +293,12 @@ class FoaDataset(torch.utils.data.Dataset):
                 self.filelist = sorted(self.filelist)[self.rank::self.world]
         self.hop_label = int(dc.get("sr", 24000) * dc.get("label_hop_len_s", 0.1))
         self.rotate = bool(params.get("aug_config", {}).get("rotation_augment", False)) and not is_valid
-        if self.loss_nm != "adyolo":
-            raise NotImplementedError("FoaDataset encodes AD-YOLO labels; use ClasswiseLabelEncoder for %s" % self.loss_nm)
-        self.encoder = YoloLabelEncoder(params)
+        if self.loss_nm == "adyolo":
+            self.encoder = YoloLabelEncoder(params)
+        elif self.loss_nm in CLASSWISE_LABELS:
+            self.encoder = ClasswiseLabelEncoder(dc["nb_classes"])
+        else:
+            raise NotImplementedError("FoaDataset: loss %s" % self.loss_nm)
 
     def sample_filelist_for_train_iter(self):
         """datasets.py:67-91, statement for statement (so that a seeded ``random`` draws the same files)."""
@@ -356,12 +360,24 @@ class FoaDataset(torch.utils.data.Dataset):
             comb_no = int(self._random.uniform(0, 16))                                    # augmentations.py:76
             label = rotate_labels(label, comb_no)
         nb_label_frames = pcm.shape[0] // self.hop_label
-        return np.ascontiguousarray(pcm, dtype=np.int16), comb_no, self.encoder.get_yolo_label(label, nb_label_frames)
+        if self.loss_nm == "adyolo":
+            target = self.encoder.get_yolo_label(label, nb_label_frames)
+        else:                                   # dense (T', ...) float32 tensor, datasets.py:210-219
+            target = getattr(self.encoder, CLASSWISE_LABELS[self.loss_nm])(label, nb_label_frames)
+        return np.ascontiguousarray(pcm, dtype=np.int16), comb_no, target
+
+
+CLASSWISE_LABELS = {"seddoa": "get_seddoa_label", "masked-seddoa": "get_seddoa_label", "accdoa": "get_accdoa_label",
+                    "adpit": "get_adpit_label"}
 
 
 def audio_collate_fn(batch):
-    """list of FoaDataset items -> (pcm int16 (B, T, 4) host tensor, comb_nos list, target (M, 7) float32); the target
-    rows are built exactly like ``collate_fn`` (datasets.py:164-184)."""
+    """list of FoaDataset items -> (pcm int16 (B, T, 4) host tensor, comb_nos list, target).  AD-YOLO: target (M, 7) float32
+    rows built exactly like ``collate_fn`` (datasets.py:164-184); class-wise losses: the dense labels stacked to (B, T', ...),
+    like the default collate the reference uses for them."""
     pcms, combs, labels = zip(*batch)
-    _, target = collate_fn([(np.zeros(1, dtype=np.float32), rows) for rows in labels])
+    if isinstance(labels[0], torch.Tensor):
+        target = torch.stack(labels, 0)
+    else:
+        _, target = collate_fn([(np.zeros(1, dtype=np.float32), rows) for rows in labels])
     return torch.stack([torch.from_numpy(p) for p in pcms], 0), list(combs), target

@@ -239,8 +239,8 @@ class StepGraphs:
 
 class ForwardGraphs:
     """Evaluation forward (``test_epoch``, reference src/test.py:33-60: one clip at a time) as one hipGraph per clip length:
-    K1 features -> encoder + head (eval mode) -> AD-YOLO decode.  ``__call__(audio (B, n, 4))`` -> (logits, decoded or
-    None); both are the graph's static outputs, valid until the next call with the same shape."""
+    K1 features -> encoder + head (eval mode) -> decode (``LabelPostProcessor.decode_device``).  ``__call__(audio (B, n, 4))``
+    -> (logits, decoded or None); both are the graph's static outputs, valid until the next call with the same shape."""
 
     def __init__(self, model, features, postprocessor=None, warm_calls=1):
         self.model, self.features, self.post = model, features, postprocessor
@@ -280,8 +280,7 @@ class ForwardGraphs:
         out = self.model(self.features(audio, channels_last8=True), channels_last8=True)
         dec = None
         if self.post is not None:
-            p = self.post
-            dec = ops.yolo_decode(out.contiguous(), p.nb_classes, p.nb_grids, p.nb_anchors, p.grid_size, p.g_overlap)
+            dec = self.post.decode_device(out)         # the post-processor owns the decode format (AD-YOLO or class-wise)
         return out, dec
 
     def __call__(self, audio):

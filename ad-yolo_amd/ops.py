@@ -888,6 +888,25 @@ def adpit_loss(out2d, tgt, nb_classes, need_grad=True):
     return loss, dout
 
 
+CLASSWISE_MODES = {"seddoa": 0, "masked-seddoa": 0, "accdoa": 1, "adpit": 2}     # ADYOLO_CLASSWISE_* in adyolo_hip.h
+CLASSWISE_WIDTH = {0: 4, 1: 3, 2: 9}                                               # output columns per class
+CLASSWISE_REC = {0: 4, 1: 4, 2: 16}                                                # decoded floats per (frame, class)
+
+
+def classwise_decode(output, nb_classes, mode):
+    """output [...][W*C] of a seddoa / accdoa / adpit head -> decoded [frames][C][rec] (adyolo_hip.h, ``adyolo_classwise_decode``:
+    activities, copied xyz and, for adpit, the angular distances of the track pairs).  mode: a loss name or its integer code."""
+    _chk(output)
+    m = CLASSWISE_MODES[mode] if isinstance(mode, str) else int(mode)
+    k = CLASSWISE_WIDTH.get(m, 1) * int(nb_classes)
+    frames = output.numel() // k if k > 0 else 0
+    if k <= 0 or output.numel() != frames * k:
+        raise _lib.AdyoloHipError("classwise_decode: %d output values are not a whole number of frames of %d" % (output.numel(), k))
+    dec = _new(output, frames, int(nb_classes), CLASSWISE_REC.get(m, 4))
+    _c("adyolo_classwise_decode", _p(output), _p(dec), frames, int(nb_classes), m, _stream())
+    return dec
+
+
 def yolo_decode(logit, nb_classes, grid=(8, 4), anchors=5, grid_size=(45.0, 45.0), g_overlap=0.5):
     """logit [...][G*A*(C+3)] -> decoded [frames][Gaz][Gel][A][C+3] (conf, class-confidence scores, U, V)."""
     _chk(logit)

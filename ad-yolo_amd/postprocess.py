@@ -6,6 +6,11 @@ Mirror of ``LabelPostProcessor`` for ``--loss adyolo`` (/root/reference/src/data
 arithmetic as the loss (csrc/loss.hip ``yolo_decode_kernel``); the NMS is tiny, data dependent and stays on the host
 (NumPy float32), exactly where the reference runs it (``postprocessor.postprocess(output.detach().cpu())``, test.py:52).
 Like the reference it handles one clip at a time (B = 1, datasets.py:752-753).
+
+The class-wise heads (``--loss seddoa | masked-seddoa | accdoa | adpit``, ``get_seddoa_output`` / ``get_accdoa_output`` /
+``get_adpit_output``, datasets.py:536-739) follow the same split: a threshold-free GPU decode (csrc/losses.hip
+``adyolo_classwise_decode``: per (frame, class) the track activities, their xyz and, for adpit, the pair distances), then a
+vectorised host ``select`` per threshold (``classwise_select``).
 """
 import math
 
@@ -101,15 +106,84 @@ def nms_decoded(decoded, nb_classes, conf_thresh, clss_thresh, unify_thresh, nms
     return out
 
 
+CLASSWISE = ("seddoa", "masked-seddoa", "accdoa", "adpit")
+
+
+def _above(act, thresh):
+    """The reference's double test: ``sed = act > thresh`` and then ``sed[f][c] > thresh`` on the BOOLEAN (True counts as 1),
+    so a threshold >= 1 keeps nothing that passes through it."""
+    return (act > thresh).astype(F32) > thresh
+
+
+def classwise_select(decoded, loss, conf_thresh, unify_thresh=None):
+    """Host half of the class-wise post-processing on a decode [T][C][rec] (``adyolo_classwise_decode``) ->
+    {frame: [[class, x, y, z], ...]}: frames ascending, classes ascending, and for adpit within one class the case order of
+    ``get_adpit_output`` (datasets.py:661-739).  Two tracks are one event when both are active (activity > conf_thresh) and
+    their angular distance is below unify_thresh; per class:
+      * no such pair: every active track (double test), in track order;
+      * exactly one pair: the third track (double test), then the mean of the pair, (a + b) / 2;
+      * two or three pairs: the mean of all three, ((a + b) + c) / 3.
+    The means are float32, like the reference's arithmetic on the float32 output."""
+    dec = np.asarray(decoded, dtype=F32)
+    t, c = dec.shape[0], dec.shape[1]
+    if loss != "adpit":
+        keep = _above(dec[..., 0], conf_thresh)
+        rows = np.concatenate([np.broadcast_to(np.arange(c, dtype=F32)[None, :, None], (t, c, 1)), dec[..., 1:4]], axis=-1)
+        fr, cl = np.nonzero(keep)
+        return _group(fr, rows[fr, cl])
+    act, xyz, dist = dec[..., 0:3], dec[..., 3:12].reshape(t, c, 3, 3), dec[..., 12:15]
+    sed = act > conf_thresh
+    q = _above(act, conf_thresh)
+    pair = np.stack([sed[..., 0] & sed[..., 1], sed[..., 1] & sed[..., 2], sed[..., 2] & sed[..., 0]], -1) & (dist < unify_thresh)
+    n = pair.sum(-1)
+    one = n == 1
+    p01, p12, p20 = (pair[..., k] & one for k in range(3))
+    a, b, d = xyz[..., 0, :], xyz[..., 1, :], xyz[..., 2, :]
+    # up to three rows per (frame, class), in the reference's order: slot 0, slot 1, slot 2
+    slot_ok = np.zeros((t, c, 3), dtype=bool)
+    slot_xyz = np.zeros((t, c, 3, 3), dtype=F32)
+    zero = n == 0
+    slot_ok[..., 0] = (zero & q[..., 0]) | (p01 & q[..., 2]) | (p12 & q[..., 0]) | (p20 & q[..., 1]) | (n >= 2)
+    slot_xyz[..., 0, :] = np.select([zero[..., None] | p12[..., None], p01[..., None], p20[..., None]], [a, d, b],
+                                    ((a + b) + d) / F32(3))
+    slot_ok[..., 1] = (zero & q[..., 1]) | one
+    slot_xyz[..., 1, :] = np.select([zero[..., None], p01[..., None], p12[..., None]], [b, (a + b) / F32(2), (b + d) / F32(2)],
+                                    (d + a) / F32(2))
+    slot_ok[..., 2] = zero & q[..., 2]
+    slot_xyz[..., 2, :] = d
+    fr, cl, sl = np.nonzero(slot_ok)
+    rows = np.concatenate([cl.astype(F32)[:, None], slot_xyz[fr, cl, sl]], axis=1)
+    return _group(fr, rows)
+
+
+def _group(frames, rows):
+    """rows (N, 4) float32 with ascending ``frames`` (N,) -> {frame: [[class, x, y, z], ...]}."""
+    out = {}
+    if len(frames) == 0:
+        return out
+    starts = np.flatnonzero(np.r_[True, frames[1:] != frames[:-1]])
+    ends = np.r_[starts[1:], len(frames)]
+    vals = rows.tolist()
+    for s, e in zip(starts.tolist(), ends.tolist()):
+        out[int(frames[s])] = vals[s:e]
+    return out
+
+
 class LabelPostProcessor:
-    """``LabelPostProcessor(params).postprocess(output)`` for the adyolo head; ``output`` (1, T', K) logits on the GPU."""
+    """``LabelPostProcessor(params).postprocess(output)`` for the adyolo head (decode + NMS) and the class-wise heads
+    (``--loss seddoa | masked-seddoa | accdoa | adpit``); ``output`` (1, T', K) on the GPU."""
 
     def __init__(self, params):
         tc = params["train_config"]
         self.nb_classes = params["data_config"]["nb_classes"]
         self.loss = params["args"]["loss"]
+        self.conf_thresh = tc["conf_thresh"]
+        if self.loss in CLASSWISE:
+            # unify_thresh: read at select time (the reference's test.py:96-98 sets it on the object between runs)
+            self.unify_thresh = tc.get("unify_thresh") if self.loss == "adpit" else None
+            return
         if self.loss != "adyolo":
-            raise NotImplementedError("postprocess: {} (only the adyolo decode + NMS is built)".format(self.loss))
+            raise NotImplementedError("postprocess: {}".format(self.loss))
         self.grid_size = [float(v) for v in tc["grid_size"]]
         self.nb_anchors = int(tc["nb_anchors"])
         self.nb_grids = (int(math.ceil(360.0 / self.grid_size[0])), int(math.ceil(180.0 / self.grid_size[1])))
@@ -126,19 +200,30 @@ class LabelPostProcessor:
         self.conf_thresh = thresh
         self.clss_thresh = thresh
 
+    def decode_device(self, output):
+        """The GPU decode of (B, T', K) network outputs as a device tensor, clip after clip along its first axis (B * T'
+        frames): adyolo [frames][Gaz][Gel][A][C+3], class-wise [frames][C][rec] (``adyolo_classwise_decode``).  What ``select``
+        reads; ``graph.ForwardGraphs`` records it with the forward pass."""
+        from . import ops
+        if self.loss in CLASSWISE:
+            return ops.classwise_decode(output.contiguous(), self.nb_classes, self.loss)
+        return ops.yolo_decode(output.contiguous(), self.nb_classes, self.nb_grids, self.nb_anchors, self.grid_size,
+                               self.g_overlap)
+
     def decode(self, output, borrow=False):
         """GPU half of ``postprocess`` (threshold-free): logits (1, T', K) -> decoded predictions as a host array.
         borrow: return a view of the page-locked staging buffer (valid until the next decode of that shape) instead of a copy."""
         from . import ops
         if output.shape[0] != 1:
             raise ValueError("postprocess handles one clip at a time (B = 1), like the reference (datasets.py:752-753)")
-        dec = ops.yolo_decode(output.contiguous(), self.nb_classes, self.nb_grids, self.nb_anchors, self.grid_size,
-                              self.g_overlap)
-        host = ops.to_host(dec).numpy()
+        host = ops.to_host(self.decode_device(output)).numpy()
         return host if borrow else host.copy()
 
     def select(self, decoded):
-        """Host half: confidence / class thresholds + conn-merge NMS on a ``decode`` result."""
+        """Host half on a ``decode`` result: adyolo -- confidence / class thresholds + NMS; class-wise -- ``classwise_select``
+        with the current conf_thresh and unify_thresh."""
+        if self.loss in CLASSWISE:
+            return classwise_select(decoded, self.loss, self.conf_thresh, self.unify_thresh)
         return nms_decoded(decoded, self.nb_classes, self.conf_thresh, self.clss_thresh, self.unify_thresh, self.nms)
 
     def postprocess(self, output):

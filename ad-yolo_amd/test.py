@@ -104,12 +104,13 @@ def test_epoch_audio(dataset, model, features, criterion, postprocessor, device,
                 output = model(features(audio, channels_last8=True), channels_last8=True)
             for b, (pcm, _, rows) in enumerate(items):
                 out_b = output[b:b + 1]
-                if rows:
-                    target = audio_collate_fn([(pcm, 0, rows)])[2]
+                dense = isinstance(rows, torch.Tensor)          # class-wise losses: (T', ...) label, all zeros for 'infer'
+                if (not getattr(dataset, "is_infer", False)) if dense else rows:
+                    target = rows.unsqueeze(0) if dense else audio_collate_fn([(pcm, 0, rows)])[2]
                     loss = criterion(out_b, target)
                     total = loss.reshape(-1)[:1].clone() if total is None else total + loss.reshape(-1)[:1]
                     n += 1
-                tp = output.shape[1]                          # decoded: [B * T'][Gaz][Gel][A][C+3], clip after clip
+                tp = output.shape[1]                          # decoded: [B * T'][...], clip after clip
                 rows_out = postprocessor.select(decoded[b * tp:(b + 1) * tp]) if decoded is not None else postprocessor.postprocess(out_b)
                 write_seld_output_file(os.path.join(output_pth, names[i + b] + ".csv"), rows_out)
             i += len(items)

@@ -402,6 +402,21 @@ int adyolo_seddoa_loss(const float *out, const float *tgt, float *loss, float *d
 int adyolo_adpit_loss(const float *out, const float *tgt, float *loss, float *dout, float *partial, long rows,
                       int C, void *stream);
 
+/* Class-wise inference decode (LabelPostProcessor.get_seddoa_output / get_accdoa_output / get_adpit_output,
+ * src/datasets.py:536-739), threshold-free: one record of ADYOLO_CLASSWISE_REC(mode) floats per (frame, class),
+ * dec [n_frames][C][rec]; the conf threshold and the ADPIT unify decision stay on the host (ad-yolo_amd/postprocess.py).
+ *   SEDDOA  out [n_frames][4C]: [act = out[c], x, y, z = out[C+c], out[2C+c], out[3C+c]]
+ *   ACCDOA  out [n_frames][3C]: [act = sqrt(x*x + y*y + z*z), x, y, z = out[c], out[C+c], out[2C+c]]
+ *   ADPIT   out [n_frames][9C] (track k at 3kC): [act0, act1, act2, x0, y0, z0, x1, y1, z1, x2, y2, z2, d01, d12, d20, 0],
+ *           d = angular distance in degrees between two tracks (utils/seld_metrics.py:97-114, fp32)
+ * Activities are evaluated in that order without contraction (bit-equal to numpy's float32); xyz are copied.
+ * dec must be 16-byte aligned.  EINVAL: bad arguments; ENOSUP: unknown mode. */
+#define ADYOLO_CLASSWISE_SEDDOA 0
+#define ADYOLO_CLASSWISE_ACCDOA 1
+#define ADYOLO_CLASSWISE_ADPIT  2
+#define ADYOLO_CLASSWISE_REC(mode) ((mode) == ADYOLO_CLASSWISE_ADPIT ? 16 : 4)
+int adyolo_classwise_decode(const float *out, float *dec, long n_frames, int C, int mode, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Input pipeline around K1.
  *   adyolo_pcm16_to_f32: staged WAV samples int16 -> float, x / 32768 + 1e-8 (src/datasets.py:105, src/preprocess.py:104)

@@ -86,6 +86,8 @@ SIGNATURES = {
     "adyolo_loss_fwd_bwd": (I, [P] * 6 + [I] * 7 + [P, P, F, F, F, F, P]),
     "adyolo_loss_phase": (I, [P] * 6 + [I] * 7 + [P, P, F, F, F, F, I, L, P]),
     "adyolo_yolo_decode": (I, [P, P, L, I, I, I, I, F, F, F, P]),
+    "adyolo_yolo_select_workspace_words": (L, [L, I, I]),
+    "adyolo_yolo_select": (I, [P] * 4 + [L, I, I, F, F, F, F, I, P]),
     "adyolo_act_fwd": (I, [P, P, L, I, I, P]),
     "adyolo_act_bwd": (I, [P, P, P, L, I, I, P]),
     "adyolo_seddoa_loss": (I, [P] * 5 + [L, I, I, I, F, F, P]),

@@ -1,0 +1,311 @@
+// AD-YOLO detection selection on the GPU: the confidence / class thresholds and the per-class NMS of
+// LabelPostProcessor.get_yolo_output (src/datasets.py:773-855, helpers :858-919), i.e. postprocess.nms_decoded, on a
+// decoded tensor [frames][N = Gaz*Gel*A][C+3] (csrc/loss.hip yolo_decode_kernel).
+//
+// Three launches:
+//   1. yolo_select_kernel, one wave per (frame, class): filter conf > conf_t and class_conf > clss_t; stable rank by
+//      descending class_conf (ties: anchor order, what argsort(kind="stable") does on the np.nonzero order); the sorted
+//      rows' angles, xyz and vote exponents go to LDS; then the clusters, seeded in rank order:
+//        conn-merge  connected components of dist < unify, grown breadth first from the lowest unassigned rank
+//        soft-merge  greedy: the seed's cluster is every row of the class with dist <= unify (removed ones too); the
+//                    rows within dist <= unify of the seed leave the remaining set
+//        plain       the same greedy suppression, each seed written alone, xyz not normalised
+//      and the vote of each cluster (postprocess._voted: softmax of exp(conf^2 / t), weighted xyz, normalised).  A class
+//      with one surviving row is written alone (postprocess._single).  Rows go to a per-(frame, class) slot of the workspace.
+//      Every pair distance is evaluated at most once per seed (greedy) or once per frontier row (components), so the cost
+//      grows with the surviving candidates K (K^2 at worst), not with N^2.
+//   2. select_scan_kernel (one workgroup): exclusive scan of the slot counts, per-frame row counts and the total.
+//   3. select_compact_kernel: slot rows -> compacted [frame, class, x, y, z].
+// Angular distances use the float32 formula of postprocess._ang_dist_deg evaluated in its order without contraction.
+#include "common.hpp"
+
+namespace adyolo {
+
+constexpr int SEL_WAVE = 64;
+constexpr int SEL_WORDS = ADYOLO_SELECT_MAX_N / SEL_WAVE;   // rows per lane: row j = lane + 64 k, bit k of a lane mask
+static_assert(SEL_WORDS <= 32, "lane masks are 32-bit");
+
+// numpy's float32 constants: np.deg2rad multiplies by (float)(pi / 180), np.rad2deg by 180.f / (float)pi
+#define SEL_D2R 0.017453292f
+#define SEL_R2D 57.295776f
+
+__device__ __forceinline__ float sel_dist(float ru_a, float sv_a, float cv_a, float ru_b, float sv_b, float cv_b) {
+#pragma clang fp contract(off)
+    float d = sv_a * sv_b + cv_a * cv_b * cosf(fabsf(ru_a - ru_b));
+    d = fminf(fmaxf(d, -1.f), 1.f);
+    return acosf(d) * SEL_R2D;
+}
+
+// lowest row index whose bit is set in some lane's mask, or -1 (wave-uniform)
+__device__ __forceinline__ int sel_first(uint32_t bits, int kw) {
+    for (int k = 0; k < kw; ++k) {
+        const unsigned long long b = __ballot((bits >> k) & 1u);
+        if (b) return k * SEL_WAVE + (int)__builtin_ctzll(b);
+    }
+    return -1;
+}
+
+struct SelRows {
+    float *ru, *sv, *cv, *x, *y, *z, *e;   // sorted by rank: u (rad), sin v, cos v, unit vector, exp(conf^2 / t)
+};
+
+// postprocess._voted over the rows whose bits are set in `memb` (wave-wide; every lane returns the result)
+__device__ void sel_vote(const SelRows &r, uint32_t memb, int kw, int lane, float &ox, float &oy, float &oz) {
+#pragma clang fp contract(off)
+    float m = -INFINITY;
+    for (int k = 0; k < kw; ++k)
+        if ((memb >> k) & 1u) m = fmaxf(m, r.e[lane + k * SEL_WAVE]);
+    m = wave_max(m);
+    float sw = 0.f;
+    for (int k = 0; k < kw; ++k)
+        if ((memb >> k) & 1u) sw += expf(r.e[lane + k * SEL_WAVE] - m);
+    sw = wave_sum(sw);
+    float vx = 0.f, vy = 0.f, vz = 0.f;
+    for (int k = 0; k < kw; ++k)
+        if ((memb >> k) & 1u) {
+            const int j = lane + k * SEL_WAVE;
+            const float w = expf(r.e[j] - m) / sw;
+            vx += r.x[j] * w;
+            vy += r.y[j] * w;
+            vz += r.z[j] * w;
+        }
+    vx = wave_sum(vx);
+    vy = wave_sum(vy);
+    vz = wave_sum(vz);
+    const float n = sqrtf(vx * vx + vy * vy + vz * vz);
+    ox = vx / n;
+    oy = vy / n;
+    oz = vz / n;
+}
+
+// grid: one 64-lane workgroup per (frame, class) slot; dynamic LDS: 9 arrays of npad = N rounded up to 64 words
+__global__ __launch_bounds__(64) void yolo_select_kernel(const float *__restrict__ dec, float *__restrict__ slot_xyz,
+                                                         int *__restrict__ slot_count, int N, int C, float conf_t,
+                                                         float clss_t, float unify_t, float vote_t, int mode) {
+#pragma clang fp contract(off)
+    extern __shared__ float sel_lds[];
+    const int npad = (N + SEL_WAVE - 1) / SEL_WAVE * SEL_WAVE;
+    float *s_key = sel_lds;                                       // class conf of the survivors, anchor order
+    int *s_anchor = reinterpret_cast<int *>(sel_lds + npad);      // their anchor index
+    int *s_front[2] = {reinterpret_cast<int *>(s_key), s_anchor}; // conn-merge frontier lists (after the sort)
+    SelRows r{sel_lds + 2 * npad, sel_lds + 3 * npad, sel_lds + 4 * npad, sel_lds + 5 * npad,
+              sel_lds + 6 * npad, sel_lds + 7 * npad, sel_lds + 8 * npad};
+    const long slot = blockIdx.x;
+    const long frame = slot / C;
+    const int cls = (int)(slot - frame * C);
+    const int lane = threadIdx.x;
+    const int CH = C + 3;
+    const float *fd = dec + (size_t)frame * N * CH;
+    float *out = slot_xyz + (size_t)slot * N * 3;
+
+    // 1. filter, compacted in anchor order
+    int K = 0;
+    for (int n0 = 0; n0 < N; n0 += SEL_WAVE) {
+        const int n = n0 + lane;
+        float cc = 0.f;
+        bool pass = false;
+        if (n < N) {
+            const float *p = fd + (size_t)n * CH;
+            cc = p[1 + cls];
+            pass = p[0] > conf_t && cc > clss_t;
+        }
+        const unsigned long long b = __ballot(pass);
+        if (pass) {
+            const int at = K + __popcll(b & ((1ull << lane) - 1ull));
+            s_key[at] = cc;
+            s_anchor[at] = n;
+        }
+        K += __popcll(b);
+    }
+    if (K == 0) {
+        if (lane == 0) slot_count[slot] = 0;
+        return;
+    }
+    __syncthreads();
+    // 2. stable rank by descending class conf; the sorted rows' angles, unit vectors and vote exponents
+    for (int i = lane; i < K; i += SEL_WAVE) {
+        const float ki = s_key[i];
+        int rank = 0;
+        for (int j = 0; j < K; ++j) {
+            const float kj = s_key[j];
+            rank += (kj > ki) || (kj == ki && j < i);
+        }
+        const float *p = fd + (size_t)s_anchor[i] * CH;
+        const float ru = p[C + 1] * SEL_D2R, rv = p[C + 2] * SEL_D2R;
+        const float sv = sinf(rv), cv = cosf(rv);
+        r.ru[rank] = ru;
+        r.sv[rank] = sv;
+        r.cv[rank] = cv;
+        r.x[rank] = cosf(ru) * cv;
+        r.y[rank] = sinf(ru) * cv;
+        r.z[rank] = sv;
+        r.e[rank] = expf(ki * ki / vote_t);
+    }
+    __syncthreads();
+    if (K == 1) {                                                 // _single: not normalised
+        if (lane == 0) {
+            out[0] = r.x[0];
+            out[1] = r.y[0];
+            out[2] = r.z[0];
+            slot_count[slot] = 1;
+        }
+        return;
+    }
+    const int kw = (K + SEL_WAVE - 1) / SEL_WAVE;
+    uint32_t left = 0;                                            // rows not yet removed / assigned
+    for (int k = 0; k < kw; ++k)
+        if (lane + k * SEL_WAVE < K) left |= 1u << k;
+    int S = 0;
+    for (int seed = sel_first(left, kw); seed >= 0; seed = sel_first(left, kw), ++S) {
+        if (lane == (seed & (SEL_WAVE - 1))) left &= ~(1u << (seed / SEL_WAVE));
+        float ox, oy, oz;
+        if (mode == ADYOLO_SELECT_CONN) {
+            uint32_t memb = lane == (seed & (SEL_WAVE - 1)) ? 1u << (seed / SEL_WAVE) : 0u;
+            int cur = 0, fsz = 1;
+            if (lane == 0) s_front[0][0] = seed;
+            __syncthreads();
+            while (fsz > 0) {
+                uint32_t fresh = 0;
+                for (int k = 0; k < kw; ++k) {
+                    if (!((left >> k) & 1u)) continue;
+                    const int j = lane + k * SEL_WAVE;
+                    const float ru = r.ru[j], sv = r.sv[j], cv = r.cv[j];
+                    for (int q = 0; q < fsz; ++q) {
+                        const int f = s_front[cur][q];
+                        if (sel_dist(r.ru[f], r.sv[f], r.cv[f], ru, sv, cv) < unify_t) {
+                            fresh |= 1u << k;
+                            break;
+                        }
+                    }
+                }
+                int n = 0;
+                for (int k = 0; k < kw; ++k) {
+                    const unsigned long long b = __ballot((fresh >> k) & 1u);
+                    if ((fresh >> k) & 1u) s_front[cur ^ 1][n + __popcll(b & ((1ull << lane) - 1ull))] = lane + k * SEL_WAVE;
+                    n += __popcll(b);
+                }
+                left &= ~fresh;
+                memb |= fresh;
+                __syncthreads();
+                cur ^= 1;
+                fsz = n;
+            }
+            sel_vote(r, memb, kw, lane, ox, oy, oz);
+        } else {
+            const float ru = r.ru[seed], sv = r.sv[seed], cv = r.cv[seed];
+            uint32_t memb = 0;
+            for (int k = 0; k < kw; ++k) {
+                const int j = lane + k * SEL_WAVE;
+                if (j >= K || (mode != ADYOLO_SELECT_SOFT && !((left >> k) & 1u))) continue;
+                const bool near = !(sel_dist(ru, sv, cv, r.ru[j], r.sv[j], r.cv[j]) > unify_t);
+                if (near) {
+                    memb |= 1u << k;
+                    left &= ~(1u << k);
+                }
+            }
+            if (mode == ADYOLO_SELECT_SOFT) {
+                sel_vote(r, memb, kw, lane, ox, oy, oz);
+            } else {
+                ox = r.x[seed];
+                oy = r.y[seed];
+                oz = r.z[seed];
+            }
+        }
+        if (lane == 0) {
+            out[3 * S + 0] = ox;
+            out[3 * S + 1] = oy;
+            out[3 * S + 2] = oz;
+        }
+    }
+    if (lane == 0) slot_count[slot] = S;
+}
+
+constexpr int SCAN_THREADS = 1024;
+
+// counts [n_slots] -> offsets [n_slots] (exclusive), frame_counts [n_frames] (+ the total at [n_frames])
+__global__ __launch_bounds__(SCAN_THREADS) void select_scan_kernel(const int *__restrict__ count, int *__restrict__ offs,
+                                                                   int *__restrict__ frame_counts, long n_frames, int C) {
+    __shared__ int part[SCAN_THREADS];
+    const int t = threadIdx.x;
+    const long n_slots = n_frames * C;
+    const long chunk = (n_slots + SCAN_THREADS - 1) / SCAN_THREADS;
+    const long s0 = t * chunk, s1 = s0 + chunk < n_slots ? s0 + chunk : n_slots;
+    int sum = 0;
+    for (long s = s0; s < s1; ++s) sum += count[s];
+    part[t] = sum;
+    __syncthreads();
+    for (int o = 1; o < SCAN_THREADS; o <<= 1) {                 // inclusive Hillis-Steele scan of the chunk sums
+        const int v = t >= o ? part[t - o] : 0;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    int run = part[t] - sum;
+    for (long s = s0; s < s1; ++s) {
+        offs[s] = run;
+        run += count[s];
+    }
+    for (long f = t; f < n_frames; f += SCAN_THREADS) {
+        int c = 0;
+        for (int k = 0; k < C; ++k) c += count[f * C + k];
+        frame_counts[f] = c;
+    }
+    if (t == SCAN_THREADS - 1) frame_counts[n_frames] = part[t];
+}
+
+__global__ __launch_bounds__(64) void select_compact_kernel(const float *__restrict__ slot_xyz, const int *__restrict__ count,
+                                                            const int *__restrict__ offs, float *__restrict__ rows,
+                                                            long n_slots, int N, int C) {
+    for (long slot = blockIdx.x; slot < n_slots; slot += gridDim.x) {
+        const int cnt = count[slot];
+        const float *src = slot_xyz + (size_t)slot * N * 3;
+        float *dst = rows + (size_t)offs[slot] * 5;
+        const float fr = (float)(slot / C), cl = (float)(slot % C);
+        for (int i = threadIdx.x; i < cnt; i += blockDim.x) {
+            dst[5 * i + 0] = fr;
+            dst[5 * i + 1] = cl;
+            dst[5 * i + 2] = src[3 * i + 0];
+            dst[5 * i + 3] = src[3 * i + 1];
+            dst[5 * i + 4] = src[3 * i + 2];
+        }
+    }
+}
+
+}  // namespace adyolo
+
+using namespace adyolo;
+
+extern "C" long adyolo_yolo_select_workspace_words(long n_frames, int n_anchor, int C) {
+    if (n_frames <= 0 || n_anchor <= 0 || C <= 0) return 0;
+    return n_frames * C * (3L * n_anchor + 2);
+}
+
+extern "C" int adyolo_yolo_select(const float *dec, float *ws, float *rows, int *frame_counts, long n_frames, int n_anchor,
+                                  int C, float conf_thresh, float clss_thresh, float unify_thresh, float vote_thresh,
+                                  int mode, void *stream) {
+    ADYOLO_REQUIRE(dec && ws && rows && frame_counts && n_frames > 0 && n_anchor > 0 && C > 0, ADYOLO_EINVAL,
+                   "yolo_select: bad arguments");
+    ADYOLO_REQUIRE(mode == ADYOLO_SELECT_PLAIN || mode == ADYOLO_SELECT_CONN || mode == ADYOLO_SELECT_SOFT, ADYOLO_EINVAL,
+                   "yolo_select: unknown mode %d", mode);
+    ADYOLO_REQUIRE(n_anchor <= ADYOLO_SELECT_MAX_N, ADYOLO_ENOSUP, "yolo_select: %d candidates per frame and class, at most %d",
+                   n_anchor, ADYOLO_SELECT_MAX_N);
+    const long n_slots = n_frames * C;
+    ADYOLO_REQUIRE(n_slots * n_anchor < (1L << 31) && n_slots < (1L << 31), ADYOLO_ENOSUP,
+                   "yolo_select: %ld frames x %d classes x %d candidates do not fit 32-bit row counts", n_frames, C, n_anchor);
+    float *slot_xyz = ws;
+    int *count = reinterpret_cast<int *>(ws + (size_t)n_slots * n_anchor * 3);
+    int *offs = count + n_slots;
+    hipStream_t st = as_stream(stream);
+    const int npad = (n_anchor + SEL_WAVE - 1) / SEL_WAVE * SEL_WAVE;
+    hipLaunchKernelGGL(yolo_select_kernel, dim3((unsigned)n_slots), dim3(SEL_WAVE), (size_t)9 * npad * sizeof(float), st,
+                       dec, slot_xyz, count, n_anchor, C, conf_thresh, clss_thresh, unify_thresh, vote_thresh, mode);
+    int rc = check_launch("yolo_select");
+    if (rc) return rc;
+    hipLaunchKernelGGL(select_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, st, count, offs, frame_counts, n_frames, C);
+    rc = check_launch("yolo_select_scan");
+    if (rc) return rc;
+    const long g = n_slots < 4096 ? n_slots : 4096;
+    hipLaunchKernelGGL(select_compact_kernel, dim3((unsigned)g), dim3(64), 0, st, slot_xyz, count, offs, rows, n_slots,
+                       n_anchor, C);
+    return check_launch("yolo_select_compact");
+}

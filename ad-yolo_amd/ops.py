@@ -7,6 +7,7 @@ in ``dist.py``, torch.distributed/RCCL.  Every function launches hand-written gf
 import ctypes
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -114,6 +115,28 @@ def to_host(t):
     buf.copy_(t, non_blocking=True)
     torch.cuda.current_stream(t.device).synchronize()
     return buf
+
+
+# Results whose size the device decides (the selected detection rows): page-locked buffers that grow to the largest request.
+_PINNED_GROW = {}
+
+
+def to_host_many(*ts):
+    """Device tensors of any shape copied into reused, growing page-locked host tensors (one per argument position and
+    dtype) with ONE synchronisation; the returned views are valid until the next ``to_host_many``."""
+    outs = []
+    for i, t in enumerate(ts):
+        key = (i, t.dtype)
+        buf = _PINNED_GROW.get(key)
+        if buf is None or buf.numel() < t.numel():
+            buf = torch.empty(1 << max(16, (t.numel() - 1).bit_length()), dtype=t.dtype, pin_memory=True)
+            _PINNED_GROW[key] = buf
+        view = buf[:t.numel()].view(t.shape)
+        view.copy_(t, non_blocking=True)
+        outs.append(view)
+    if ts:
+        torch.cuda.current_stream(ts[0].device).synchronize()
+    return outs
 
 
 # Parameter / buffer epoch: bumped by everything that writes parameters or BatchNorm buffers IN PLACE through a kernel (no
@@ -916,6 +939,46 @@ def yolo_decode(logit, nb_classes, grid=(8, 4), anchors=5, grid_size=(45.0, 45.0
     _c("adyolo_yolo_decode", _p(logit), _p(out), frames, grid[0], grid[1], anchors, nb_classes, float(grid_size[0]),
        float(grid_size[1]), float(g_overlap), _stream())
     return out
+
+
+SELECT_MODES = {"conn-merge": 1, "soft-merge": 2}                                   # ADYOLO_SELECT_* in adyolo_hip.h; else 0
+
+
+def np_f32_threshold(t, op):
+    """The float32 value t32 with ``(x op t32) == (x op t)`` for every float32 array x under NumPy's promotion rules, op one of
+    '>', '<', '<='.  A Python float (NumPy 2: a weak scalar) is rounded to float32 before the compare, so 0.1 * 3 acts as
+    float32(0.3); a float64 NumPy scalar such as an ``np.arange`` threshold is compared in float64, which float32 reproduces
+    with the threshold rounded down ('>', '<=') or up ('<')."""
+    if np.result_type(np.float32, t) == np.float32:
+        return float(np.float32(t))
+    t = float(t)
+    lo = np.float32(t)
+    if float(lo) > t:
+        lo = np.nextafter(lo, np.float32(-np.inf))
+    hi = lo if float(lo) == t else np.nextafter(lo, np.float32(np.inf))
+    return float(lo if op in (">", "<=") else hi)
+
+
+def yolo_select(decoded, nb_classes, conf, clss, unify, nms="conn-merge"):
+    """decoded [frames][Gaz][Gel][A][C+3] (``yolo_decode``) -> (rows (N, 5) [frame, class, x, y, z], counts (frames,) int32),
+    both on the device (adyolo_hip.h, ``adyolo_yolo_select``): the thresholds and the per-class NMS of
+    ``postprocess.nms_decoded`` with the same rows in the same order.  The thresholds are compared as NumPy compares them
+    with the host path's float32 arrays (``np_f32_threshold``).  One 4-byte read of the row total synchronises the stream."""
+    _chk(decoded)
+    ch = int(nb_classes) + 3
+    frames = decoded.shape[0] if decoded.dim() > 0 else 0
+    if frames <= 0 or decoded.numel() % (frames * ch) != 0 or decoded.shape[-1] != ch:
+        raise _lib.AdyoloHipError("yolo_select: decoded %s is not [frames][...][%d]" % (tuple(decoded.shape), ch))
+    n_anchor = decoded.numel() // (frames * ch)               # above ADYOLO_SELECT_MAX_N the C call refuses it (ENOSUP)
+    mode = SELECT_MODES.get(nms, 0)
+    ws = _new(decoded, max(1, _lib.load().adyolo_yolo_select_workspace_words(frames, n_anchor, int(nb_classes))))
+    rows = _new(decoded, frames * int(nb_classes) * n_anchor, 5)
+    counts = torch.empty(frames + 1, dtype=torch.int32, device=decoded.device)
+    _c("adyolo_yolo_select", _p(decoded), _p(ws), _p(rows), _p(counts), frames, n_anchor, int(nb_classes),
+       np_f32_threshold(conf, ">"), np_f32_threshold(clss, ">"), np_f32_threshold(unify, "<" if mode == 1 else "<="),
+       float(np.float32(clss)), mode, _stream())
+    total = int(to_host(counts[frames:])[0])
+    return rows[:total], counts[:frames]
 
 
 def adam_step(param, grad, exp_avg, exp_avg_sq, step, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,

@@ -5,7 +5,9 @@ Mirror of ``LabelPostProcessor`` for ``--loss adyolo`` (/root/reference/src/data
 :741-855, helpers :858-919) and ``write_seld_output_file`` (/root/reference/src/test.py:26-30).  The decode is the same
 arithmetic as the loss (csrc/loss.hip ``yolo_decode_kernel``); the NMS is tiny, data dependent and stays on the host
 (NumPy float32), exactly where the reference runs it (``postprocessor.postprocess(output.detach().cpu())``, test.py:52).
-Like the reference it handles one clip at a time (B = 1, datasets.py:752-753).
+Like the reference it handles one clip at a time (B = 1, datasets.py:752-753).  Opt-in, ``select_device`` /
+``postprocess(on_device=True)`` run the thresholds and the NMS on the GPU too (csrc/select.hip ``adyolo_yolo_select``, the same
+rows in the same order) and copy only the selected rows to the host.
 
 The class-wise heads (``--loss seddoa | masked-seddoa | accdoa | adpit``, ``get_seddoa_output`` / ``get_accdoa_output`` /
 ``get_adpit_output``, datasets.py:536-739) follow the same split: a threshold-free GPU decode (csrc/losses.hip
@@ -169,6 +171,26 @@ def _group(frames, rows):
     return out
 
 
+def group_rows(rows, counts, n_clips=1):
+    """Host half of ``LabelPostProcessor.select_device``: rows (N, 5) [frame, class, x, y, z] in frame order and counts
+    (frames,) rows per frame, frames = n_clips * T' clip after clip -> one {frame of the clip: [[class, x, y, z], ...]} per
+    clip, the shape ``select`` returns."""
+    counts = np.asarray(counts, dtype=np.int64).reshape(-1)
+    rows = np.asarray(rows, dtype=F32).reshape(-1, 5)
+    if n_clips < 1 or len(counts) % n_clips or int(counts.sum()) != len(rows):
+        raise ValueError("group_rows: %d rows, %d frame counts summing to %d, %d clips"
+                         % (len(rows), len(counts), int(counts.sum()), n_clips))
+    t = len(counts) // n_clips
+    ends = np.cumsum(counts)
+    frames = np.flatnonzero(counts)
+    clip, local = np.divmod(frames, max(t, 1))
+    vals = rows[:, 1:].tolist()
+    outs = [{} for _ in range(n_clips)]
+    for c, f, s, e in zip(clip.tolist(), local.tolist(), (ends[frames] - counts[frames]).tolist(), ends[frames].tolist()):
+        outs[c][f] = vals[s:e]
+    return outs
+
+
 class LabelPostProcessor:
     """``LabelPostProcessor(params).postprocess(output)`` for the adyolo head (decode + NMS) and the class-wise heads
     (``--loss seddoa | masked-seddoa | accdoa | adpit``); ``output`` (1, T', K) on the GPU."""
@@ -226,7 +248,24 @@ class LabelPostProcessor:
             return classwise_select(decoded, self.loss, self.conf_thresh, self.unify_thresh)
         return nms_decoded(decoded, self.nb_classes, self.conf_thresh, self.clss_thresh, self.unify_thresh, self.nms)
 
-    def postprocess(self, output):
+    def select_device(self, decoded_dev, n_clips=1):
+        """``select`` on the device for the adyolo head (``ops.yolo_select``: the same rows in the same order) on a
+        ``decode_device`` result of n_clips clips -> one {frame: [[class, x, y, z], ...]} per clip.  Only the selected rows
+        and the per-frame counts are copied to the host."""
+        from . import ops
+        if self.loss != "adyolo":
+            raise NotImplementedError("select_device: adyolo only (the class-wise heads select with classwise_select)")
+        rows, counts = ops.yolo_select(decoded_dev, self.nb_classes, self.conf_thresh, self.clss_thresh, self.unify_thresh,
+                                       self.nms)
+        rows_h, counts_h = ops.to_host_many(rows, counts)
+        return group_rows(rows_h.numpy(), counts_h.numpy(), n_clips)
+
+    def postprocess(self, output, on_device=False):
+        """on_device: the selection too runs on the GPU (``select_device``); default: ``select`` on the host."""
+        if on_device:
+            if output.shape[0] != 1:
+                raise ValueError("postprocess handles one clip at a time (B = 1), like the reference (datasets.py:752-753)")
+            return self.select_device(self.decode_device(output))[0]
         return self.select(self.decode(output, borrow=True))       # consumed at once: no second host copy
 
 

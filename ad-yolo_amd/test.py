@@ -32,12 +32,14 @@ def test_epoch(dataloader, filelist, model, criterion, postprocessor, device, ou
 
 
 def sweep_conf_thresh(dataloader, filelist, model, criterion, postprocessor, scorer, device, output_pth,
-                      thresholds=None):
+                      thresholds=None, device_select=False):
     """The reference's periodic threshold reset (src/train.py:178-203): try conf_thresh 0.1 .. 0.9, keep the first one
     with the lowest validation SELD score, leave it set on the post-processor (which rewrites conf AND class threshold,
     datasets.py:532-534).  The reference re-runs the whole validation epoch for each of the nine thresholds; the network
     output does not depend on the threshold, so here the model runs ONCE per file and only the host-side selection/NMS,
     the CSV files and the metrics are redone per threshold -- same files, same scores, a ninth of the forward passes.
+    device_select: every file's decode stays on the device (~6 MB per 60 s clip) and the nine selections run there
+    (``postprocessor.select_device``); only the selected rows come back to the host.
     -> (new_thresh, [[ER, F, LE, LR, SELD] per threshold], mean validation loss)"""
     import numpy as np
     if thresholds is None:
@@ -49,14 +51,20 @@ def sweep_conf_thresh(dataloader, filelist, model, criterion, postprocessor, sco
             output = model(feat.to(device).float())
             loss = criterion(output, label)
             total = loss.reshape(-1)[:1].clone() if total is None else total + loss.reshape(-1)[:1]
-            decoded.append(postprocessor.decode(output))
+            if device_select:
+                if output.shape[0] != 1:
+                    raise ValueError("sweep_conf_thresh: one file per batch (B = 1)")
+                decoded.append(postprocessor.decode_device(output))
+            else:
+                decoded.append(postprocessor.decode(output))
             n = i + 1
     new_thresh, best, table = postprocessor.get_conf_thresh(), 9999.0, []
     for th in thresholds:
         postprocessor.set_conf_thresh(th)
         delete_and_create_folder(output_pth)
         for i, dec in enumerate(decoded):
-            write_seld_output_file(os.path.join(output_pth, filelist[i] + ".csv"), postprocessor.select(dec))
+            rows = postprocessor.select_device(dec)[0] if device_select else postprocessor.select(dec)
+            write_seld_output_file(os.path.join(output_pth, filelist[i] + ".csv"), rows)
         er, f, le, lr, seld = scorer.get_SELD_Results(output_pth)[:5]
         table.append([er, f, le, lr, seld])
         if seld < best:
@@ -65,7 +73,8 @@ def sweep_conf_thresh(dataloader, filelist, model, criterion, postprocessor, sco
     return new_thresh, table, (float(total) / max(n, 1) if total is not None else 0.0)
 
 
-def test_epoch_audio(dataset, model, features, criterion, postprocessor, device, output_pth, batch_size=1, forward=None):
+def test_epoch_audio(dataset, model, features, criterion, postprocessor, device, output_pth, batch_size=1, forward=None,
+                     device_select=False):
     """``test_epoch`` for a raw-audio ``FoaDataset`` split ('valid' / 'test' / 'infer'): int16 audio normalised on the GPU, K1
     features, encoder + head, loss, decode + NMS, one CSV per clip named after the file.  Returns the mean loss (0 for
     'infer', which has no labels).
@@ -75,7 +84,8 @@ def test_epoch_audio(dataset, model, features, criterion, postprocessor, device,
     EQUAL length may share one forward pass (batch_size > 1: same CSV files; the 60 s clips of a DCASE split all qualify) --
     3 ms per clip at B = 1 against ~1 ms at B = 8 on MI355X.  The loss stays per clip (its normalisers are per call), averaged
     over the clips like the reference's.  forward: optional ``graph.ForwardGraphs`` (K1 + model + decode replayed from a
-    hipGraph per clip length); default: eager calls."""
+    hipGraph per clip length); default: eager calls.  device_select: the decoded batch is selected on the device
+    (``postprocessor.select_device``, launched after the graph replay, not recorded in it) and only the rows come back."""
     from . import ops
     from .datasets import audio_collate_fn
     model.eval()
@@ -95,13 +105,17 @@ def test_epoch_audio(dataset, model, features, criterion, postprocessor, device,
             t = items[0][1]
             pcm_b = torch.from_numpy(__import__("numpy").stack([it[0][:t] for it in items])).to(device).contiguous()
             audio = ops.pcm16_to_f32(pcm_b).view(len(items), t, 4)
-            decoded = None
+            decoded = selected = None
             if forward is not None:
                 output, dec = forward(audio)
-                if dec is not None:                           # the graph decoded the whole batch: ONE page-locked copy to the host
+                if dec is not None and device_select:
+                    selected = postprocessor.select_device(dec, len(items))
+                elif dec is not None:                         # the graph decoded the whole batch: ONE page-locked copy to the host
                     decoded = ops.to_host(dec).numpy()
             else:
                 output = model(features(audio, channels_last8=True), channels_last8=True)
+            if device_select and selected is None:
+                selected = postprocessor.select_device(postprocessor.decode_device(output), len(items))
             for b, (pcm, _, rows) in enumerate(items):
                 out_b = output[b:b + 1]
                 dense = isinstance(rows, torch.Tensor)          # class-wise losses: (T', ...) label, all zeros for 'infer'
@@ -111,7 +125,12 @@ def test_epoch_audio(dataset, model, features, criterion, postprocessor, device,
                     total = loss.reshape(-1)[:1].clone() if total is None else total + loss.reshape(-1)[:1]
                     n += 1
                 tp = output.shape[1]                          # decoded: [B * T'][...], clip after clip
-                rows_out = postprocessor.select(decoded[b * tp:(b + 1) * tp]) if decoded is not None else postprocessor.postprocess(out_b)
+                if selected is not None:
+                    rows_out = selected[b]
+                elif decoded is not None:
+                    rows_out = postprocessor.select(decoded[b * tp:(b + 1) * tp])
+                else:
+                    rows_out = postprocessor.postprocess(out_b)
                 write_seld_output_file(os.path.join(output_pth, names[i + b] + ".csv"), rows_out)
             i += len(items)
     return float(total) / max(n, 1) if total is not None else 0.0

@@ -381,9 +381,31 @@ int  adyolo_loss_phase(const float *logit, const float *target, float *ws, float
 
 /* K8b inference decode (LabelPostProcessor.get_yolo_output, src/datasets.py:752-771): per anchor
  *   out = [sigmoid(obj), sigmoid(cls_c)*sigmoid(obj) x C, U deg in [-180,180), V deg in [-90, 90-1e-7]];
- *   thresholding and the (tiny, data-dependent) NMS stay on the host (ad-yolo_amd/postprocess.py). */
+ *   by default thresholding and the (tiny, data-dependent) NMS stay on the host (ad-yolo_amd/postprocess.py);
+ *   adyolo_yolo_select below runs them on the device. */
 int adyolo_yolo_decode(const float *logit, float *out, long n_frames, int Gaz, int Gel, int A, int C,
                        float grid_az, float grid_el, float g_overlap, void *stream);
+
+/* K8c inference selection (csrc/select.hip), opt-in: what postprocess.nms_decoded does on the host
+ * (get_yolo_output thresholds + per-class NMS, src/datasets.py:773-855, helpers :858-919), on the decode above.
+ *   dec   [n_frames][n_anchor = Gaz*Gel*A][C+3] from adyolo_yolo_decode; n_anchor <= ADYOLO_SELECT_MAX_N, else ENOSUP
+ *   ws    adyolo_yolo_select_workspace_words(n_frames, n_anchor, C) words
+ *   rows  capacity n_frames * C * n_anchor rows of [frame, class, x, y, z] float32; the first total rows are written:
+ *         frames ascending, classes ascending, within a class the clusters in the order of their seeds
+ *   frame_counts  [n_frames + 1] int32: rows per frame, then the total at [n_frames]
+ *   a row passes with conf > conf_thresh and class_conf > clss_thresh (float32 compares: the caller rounds the
+ *   thresholds the way its host comparison would); mode: ADYOLO_SELECT_CONN (connected components of
+ *   dist < unify_thresh), ADYOLO_SELECT_SOFT (greedy, clusters of dist <= unify_thresh over all rows of the class) or
+ *   ADYOLO_SELECT_PLAIN (greedy suppression, the seed alone).  Cluster vote: softmax(exp(conf^2 / vote_thresh)) weighted
+ *   xyz, normalised; a class with one row and every PLAIN row keeps its unnormalised xyz. */
+#define ADYOLO_SELECT_PLAIN 0
+#define ADYOLO_SELECT_CONN  1
+#define ADYOLO_SELECT_SOFT  2
+#define ADYOLO_SELECT_MAX_N 1024
+long adyolo_yolo_select_workspace_words(long n_frames, int n_anchor, int C);
+int  adyolo_yolo_select(const float *dec, float *ws, float *rows, int *frame_counts, long n_frames, int n_anchor, int C,
+                        float conf_thresh, float clss_thresh, float unify_thresh, float vote_thresh, int mode,
+                        void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * K10 the other heads / losses behind the reference's --loss switch (src/main.py:43)

@@ -959,11 +959,13 @@ def np_f32_threshold(t, op):
     return float(lo if op in (">", "<=") else hi)
 
 
-def yolo_select(decoded, nb_classes, conf, clss, unify, nms="conn-merge"):
+def yolo_select(decoded, nb_classes, conf, clss, unify, nms="conn-merge", trim=True):
     """decoded [frames][Gaz][Gel][A][C+3] (``yolo_decode``) -> (rows (N, 5) [frame, class, x, y, z], counts (frames,) int32),
     both on the device (adyolo_hip.h, ``adyolo_yolo_select``): the thresholds and the per-class NMS of
     ``postprocess.nms_decoded`` with the same rows in the same order.  The thresholds are compared as NumPy compares them
-    with the host path's float32 arrays (``np_f32_threshold``).  One 4-byte read of the row total synchronises the stream."""
+    with the host path's float32 arrays (``np_f32_threshold``).  One 4-byte read of the row total synchronises the stream.
+    trim=False: no read and no synchronisation; rows is the whole capacity buffer, of which the first counts.sum() rows are
+    written (what ``seld_score`` takes)."""
     _chk(decoded)
     ch = int(nb_classes) + 3
     frames = decoded.shape[0] if decoded.dim() > 0 else 0
@@ -977,8 +979,62 @@ def yolo_select(decoded, nb_classes, conf, clss, unify, nms="conn-merge"):
     _c("adyolo_yolo_select", _p(decoded), _p(ws), _p(rows), _p(counts), frames, n_anchor, int(nb_classes),
        np_f32_threshold(conf, ">"), np_f32_threshold(clss, ">"), np_f32_threshold(unify, "<" if mode == 1 else "<="),
        float(np.float32(clss)), mode, _stream())
+    if not trim:
+        return rows, counts[:frames]
     total = int(to_host(counts[frames:])[0])
     return rows[:total], counts[:frames]
+
+
+SELD_STATUS = ((1, "more than 1024 predictions in one frame and class"),      # ADYOLO_SELD_* in adyolo_hip.h
+               (2, "more than 8 reference events in one frame and class"),
+               (4, "frame counts negative or summing past the rows given"),
+               (8, "a file index outside the reference table"),
+               (16, "no finite assignment (NaN coordinates)"))
+SELD_ENOSUP_BITS = 1 | 2                                      # ADYOLO_SELD_PRED_OVERFLOW | ADYOLO_SELD_REF_OVERFLOW
+
+
+def seld_status_check(status):
+    """Raise ``AdyoloHipError`` for the ADYOLO_SELD_* bits of a ``seld_score`` status word (one 4-byte copy, synchronises)."""
+    word = int(to_host(status.reshape(-1)[:1])[0])
+    if word:
+        why = "; ".join(msg for bit, msg in SELD_STATUS if word & bit)
+        code = -2 if word & SELD_ENOSUP_BITS else -1
+        raise _lib.AdyoloHipError("adyolo_seld_score failed (rc=%d, status 0x%x): %s" % (code, word, why))
+
+
+def seld_score(rows, counts, table, file_ids, t_clip, out, status=None):
+    """Adds the SELD accumulators of n_clips = counts.numel() // t_clip clips into out [files][9 C + 3] float64
+    (adyolo_hip.h, ``adyolo_seld_score``).  rows (N, 5) float32 or float64 [frame, class, x, y, z] with per-frame counts
+    (int32, clip after clip: what ``yolo_select(..., trim=False)`` returns; rows beyond counts.sum() are not read), table a
+    ``seld_metrics.SELDRefTable`` on the same device, file_ids (n_clips,) int32 on the device.  status: an int32 word on the
+    device that collects errors across calls (the caller checks it with ``seld_status_check``; while it is set nothing is
+    added); None: a fresh word, checked before returning (synchronises)."""
+    if not rows.is_cuda or rows.dtype not in (torch.float32, torch.float64) or not rows.is_contiguous():
+        raise _lib.AdyoloHipError("seld_score: rows must be a contiguous float32 or float64 tensor on the device")
+    if rows.numel() % 5 or (rows.dim() == 2 and rows.shape[1] != 5):
+        raise _lib.AdyoloHipError("seld_score: rows %s are not (N, 5)" % (tuple(rows.shape),))
+    for name, t, dt in (("counts", counts, torch.int32), ("file_ids", file_ids, torch.int32), ("out", out, torch.float64)):
+        if not t.is_cuda or t.dtype != dt or not t.is_contiguous() or t.device != rows.device:
+            raise _lib.AdyoloHipError("seld_score: %s must be a contiguous %s tensor on %s" % (name, dt, rows.device))
+    t_clip = int(t_clip)
+    n_clips = file_ids.numel()
+    if t_clip <= 0 or counts.numel() != n_clips * t_clip:
+        raise _lib.AdyoloHipError("seld_score: %d frame counts for %d clips of %d frames" % (counts.numel(), n_clips, t_clip))
+    if out.shape != (table.n_files, 9 * table.nb_classes + 3):
+        raise _lib.AdyoloHipError("seld_score: out %s is not [%d][%d]" % (tuple(out.shape), table.n_files,
+                                                                          9 * table.nb_classes + 3))
+    own = status is None
+    if own:
+        status = torch.zeros(1, dtype=torch.int32, device=rows.device)
+    words = _lib.load().adyolo_seld_score_workspace_words(n_clips, t_clip, table.max_blocks, table.nb_classes)
+    ws = torch.empty(max(1, words), dtype=torch.float32, device=rows.device)
+    _c("adyolo_seld_score", _p(rows) if rows.numel() else NULL, int(rows.dtype == torch.float64), rows.numel() // 5,
+       _p(counts), n_clips, t_clip, _p(file_ids), _p(table.file_info), _p(table.ref_off), _p(table.ref_ev),
+       _p(table.keep), table.n_files, table.nb_classes, table.frames_per_block, table.max_blocks, float(table.doa_threshold),
+       _p(ws), _p(out), _p(status), _stream())
+    if own:
+        seld_status_check(status)
+    return status
 
 
 def adam_step(param, grad, exp_avg, exp_avg_sq, step, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,

@@ -248,15 +248,24 @@ class LabelPostProcessor:
             return classwise_select(decoded, self.loss, self.conf_thresh, self.unify_thresh)
         return nms_decoded(decoded, self.nb_classes, self.conf_thresh, self.clss_thresh, self.unify_thresh, self.nms)
 
-    def select_device(self, decoded_dev, n_clips=1):
+    def select_device_rows(self, decoded_dev, n_clips=1, trim=True):
         """``select`` on the device for the adyolo head (``ops.yolo_select``: the same rows in the same order) on a
-        ``decode_device`` result of n_clips clips -> one {frame: [[class, x, y, z], ...]} per clip.  Only the selected rows
-        and the per-frame counts are copied to the host."""
+        ``decode_device`` result of n_clips clips -> (rows (N, 5) [frame, class, x, y, z], counts (n_clips * T',) int32, clip
+        after clip), both on the device.  trim=False: no synchronisation, rows is the capacity buffer of which the first counts.sum() are
+        written (what ``seld_metrics.DeviceSELDScorer.add_rows`` takes)."""
         from . import ops
         if self.loss != "adyolo":
             raise NotImplementedError("select_device: adyolo only (the class-wise heads select with classwise_select)")
-        rows, counts = ops.yolo_select(decoded_dev, self.nb_classes, self.conf_thresh, self.clss_thresh, self.unify_thresh,
-                                       self.nms)
+        if n_clips < 1 or decoded_dev.shape[0] % n_clips:
+            raise ValueError("select_device_rows: %d frames for %d clips" % (decoded_dev.shape[0], n_clips))
+        return ops.yolo_select(decoded_dev, self.nb_classes, self.conf_thresh, self.clss_thresh, self.unify_thresh, self.nms,
+                               trim=trim)
+
+    def select_device(self, decoded_dev, n_clips=1):
+        """``select_device_rows`` -> one {frame: [[class, x, y, z], ...]} per clip.  Only the selected rows and the per-frame
+        counts are copied to the host."""
+        from . import ops
+        rows, counts = self.select_device_rows(decoded_dev, n_clips)
         rows_h, counts_h = ops.to_host_many(rows, counts)
         return group_rows(rows_h.numpy(), counts_h.numpy(), n_clips)
 

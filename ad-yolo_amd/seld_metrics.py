@@ -119,17 +119,49 @@ class SELDScorer:
             self.D += max(0, loc_fn - loc_fp)
             self.I += max(0, loc_fp - loc_fn)
 
+    def accumulator(self):
+        """The counts as one vector [9 * C + 3]: TP, FP, FP_spatial, FN, Nref, total_DE, DE_TP, DE_FP, DE_FN (C each), S, D, I
+        -- the layout of ``DeviceSELDScorer``'s per-file accumulators."""
+        return np.concatenate([self.TP, self.FP, self.FP_spatial, self.FN, self.Nref, self.total_DE, self.DE_TP, self.DE_FP,
+                               self.DE_FN, np.asarray([self.S, self.D, self.I], dtype=float)])
+
     def scores(self):
         """Macro average (seld_metrics.py:260-287) -> ER, F, LE, LR, SELD, classwise (5, C)."""
-        er = (self.S + self.D + self.I) / (self.Nref.sum() + EPS)
-        f = self.TP / (EPS + self.TP + self.FP_spatial + 0.5 * (self.FP + self.FN))
-        le = self.total_DE / (self.DE_TP + EPS)
-        le[self.DE_TP == 0] = 180.0
-        lr = self.DE_TP / (EPS + self.DE_TP + self.DE_FN)
-        er_c = np.repeat(er, self.nb_classes)
-        seld = np.mean([er_c, 1 - f, le / 180, 1 - lr], 0)
-        classwise = np.array([er_c, f, le, lr, seld])
-        return er, f.mean(), le.mean(), lr.mean(), seld.mean(), classwise
+        return macro_average(self.accumulator(), self.nb_classes)
+
+
+def macro_average(acc, nb_classes):
+    """ER, F, LE, LR, SELD (class macro averages) and the classwise table (5, C) of one accumulator vector
+    (``SELDScorer.accumulator`` layout; seld_metrics.py:260-287)."""
+    a = np.asarray(acc, dtype=np.float64)
+    tp, fp, fp_spatial, fn, nref, total_de, de_tp, de_fp, de_fn = a[:9 * nb_classes].reshape(9, nb_classes)
+    s, d, i = a[9 * nb_classes:9 * nb_classes + 3]
+    er = (s + d + i) / (nref.sum() + EPS)
+    f = tp / (EPS + tp + fp_spatial + 0.5 * (fp + fn))
+    le = total_de / (de_tp + EPS)
+    le[de_tp == 0] = 180.0
+    lr = de_tp / (EPS + de_tp + de_fn)
+    er_c = np.repeat(er, nb_classes)
+    seld = np.mean([er_c, 1 - f, le / 180, 1 - lr], 0)
+    classwise = np.array([er_c, f, le, lr, seld])
+    return er, f.mean(), le.mean(), lr.mean(), seld.mean(), classwise
+
+
+def jackknife_from_accumulators(acc, nb_classes):
+    """``get_SELD_Results(..., is_jackknife=True)`` from per-file accumulators (n_files, 9 C + 3), one row per file in the
+    order the host would visit the files: leave-one-file-out sums, the same intervals, and the reference quirk of
+    ``ComputeSELDResults._jackknife`` (the point values are those of the LAST leave-one-out pass)."""
+    acc = np.asarray(acc, dtype=np.float64)
+    er, f, le, lr, seld, cw = macro_average(acc.sum(0), nb_classes)
+    global_values = [er, f, le, lr, seld] + cw.reshape(-1).tolist()
+    partial, last = [], None
+    for k in range(len(acc)):
+        last = macro_average(np.delete(acc, k, 0).sum(0), nb_classes)
+        partial.append([last[0], last[1], last[2], last[3], last[4]] + last[5].reshape(-1).tolist())
+    partial = np.asarray(partial)
+    conf = [jackknife_estimation(global_values[i], partial[:, i], 0.05)[3] for i in range(len(global_values))]
+    return ([last[0], conf[0]], [last[1], conf[1]], [last[2], conf[2]], [last[3], conf[3]], [last[4], conf[4]],
+            [last[5], np.array(conf)[5:].reshape(5, nb_classes, 2)])
 
 
 def jackknife_estimation(global_value, partial_estimates, significance_level=0.05):
@@ -242,3 +274,206 @@ class ComputeSELDResultsFromEventOverlap(ComputeSELDResults):
         pred = cartesian_to_polar(load_output_format_file(os.path.join(pred_files_path, name)))
         pred = {fr: pred[fr] for fr in self._ov_frames[name] if fr in pred}
         return segment(pred, self._ref[name][1], self._fpb)
+
+
+def overlap_frames(gt, nb_classes, classwise_overlap_test=False):
+    """The frames of a reference {frame: events} that ``ComputeSELDResultsFromEventOverlap`` keeps, in dict order: more than
+    one event, or (classwise_overlap_test) more than one event of the same class."""
+    keep = []
+    for frame, events in gt.items():
+        if classwise_overlap_test:
+            cnt = np.zeros(nb_classes)
+            for ev in events:
+                cnt[ev[0]] += 1
+            hit = cnt.max() > 1
+        else:
+            hit = len(events) > 1
+        if hit:
+            keep.append(frame)
+    return keep
+
+
+MAX_REF_PER_FRAME_CLASS = 8                       # ADYOLO_SELD_MAX_REF
+
+
+def pack_reference(refs, nb_classes, frames_per_block, keep_frames=None):
+    """Reference files -> the host arrays of the device table (adyolo_hip.h, ``adyolo_seld_score``).
+    refs: [(gt {frame: [[class, source, az, el], ...]}, length)], length = max(frame index) of the full file.
+    keep_frames: None, or per file the frames whose events (and predictions) are scored.
+    -> dict of file_info (n_files, 2) int32 [first table frame, blocks], ref_off (frames * C + 1,) int32, ref_ev (n, 3)
+    float64 [az rad, sin el, cos el], keep (frames,) int32 or None.  Only frames < blocks * frames_per_block are held, blocks =
+    ceil(length / frames_per_block): the last started block is complete, later frames are not scored (``segment``).  Raises
+    ValueError for more than MAX_REF_PER_FRAME_CLASS events of one class in one scored frame."""
+    c = nb_classes
+    info, keys, ang, keep = [], [], [], []
+    base = 0
+    for k, (gt, length) in enumerate(refs):
+        blocks = int(math.ceil(length / float(frames_per_block)))
+        n = blocks * frames_per_block
+        kept = None if keep_frames is None else set(keep_frames[k])
+        if keep_frames is not None:
+            m = np.zeros(n, dtype=np.int32)
+            for fr in kept:
+                if 0 <= fr < n:
+                    m[fr] = 1
+            keep.append(m)
+        for fr in range(n):
+            if kept is not None and fr not in kept:
+                continue
+            for ev in gt.get(fr, ()):
+                if 0 <= int(ev[0]) < c:
+                    keys.append((base + fr) * c + int(ev[0]))
+                    ang.append(ev[-2:])
+        info.append((base, blocks))
+        base += n
+    keys = np.asarray(keys, dtype=np.int64)
+    cnt = np.bincount(keys, minlength=base * c) if len(keys) else np.zeros(base * c, dtype=np.int64)
+    if len(cnt) and cnt.max() > MAX_REF_PER_FRAME_CLASS:
+        cell = int(np.argmax(cnt))
+        raise ValueError("device SELD scoring: %d reference events of class %d in one frame, at most %d"
+                         % (int(cnt.max()), cell % c, MAX_REF_PER_FRAME_CLASS))
+    order = np.argsort(keys, kind="stable")                         # frame, class; reference order within them
+    deg = np.asarray(ang, dtype=np.float64).reshape(-1, 2)[order]
+    rad = deg * np.pi / 180.0                                       # what SELDScorer.update does to the reference angles
+    ev = np.stack([rad[:, 0], np.sin(rad[:, 1]), np.cos(rad[:, 1])], axis=1) if len(rad) else np.zeros((0, 3))
+    off = np.zeros(base * c + 1, dtype=np.int64)
+    off[1:] = np.cumsum(cnt)
+    if keep_frames is not None:
+        keep = np.concatenate(keep).astype(np.int32) if keep else np.zeros(0, dtype=np.int32)
+    return {"file_info": np.asarray(info, dtype=np.int32).reshape(-1, 2), "ref_off": off.astype(np.int32),
+            "ref_ev": np.ascontiguousarray(ev, dtype=np.float64), "keep": keep if keep_frames is not None else None}
+
+
+class SELDRefTable:
+    """A packed reference table (``pack_reference``) on a device, the ``table`` argument of ``ops.seld_score``."""
+
+    def __init__(self, packed, nb_classes, frames_per_block, device, doa_threshold=20.0):
+        import torch
+        self.nb_classes, self.frames_per_block, self.doa_threshold = nb_classes, frames_per_block, doa_threshold
+        self.n_files = len(packed["file_info"])
+        self.max_blocks = max(1, int(packed["file_info"][:, 1].max()) if self.n_files else 1)
+
+        def up(a, dtype):
+            a = np.ascontiguousarray(a)
+            return torch.from_numpy(a if a.size else np.zeros(1, dtype=a.dtype)).to(device=device, dtype=dtype)
+        self.file_info = up(packed["file_info"], torch.int32)
+        self.ref_off = up(packed["ref_off"], torch.int32)
+        self.ref_ev = up(packed["ref_ev"], torch.float64)
+        self.keep = None if packed["keep"] is None else up(packed["keep"], torch.int32)
+
+
+class DeviceSELDScorer:
+    """``ComputeSELDResults`` (overlap=None) or ``ComputeSELDResultsFromEventOverlap`` (overlap="polyphony": frames with more
+    than one event; "homogenous": more than one event of one class) on the device (csrc/seld.hip, ``ops.seld_score``): the
+    reference CSVs are parsed and uploaded once; predictions are added as device rows (``add_rows``, what
+    ``LabelPostProcessor.select_device_rows`` returns) or host dicts (``add_dict``) into per-file float64 accumulators on the
+    device; ``scores()`` copies them once and returns what ``get_SELD_Results`` returns on the CSV files of the same rows.
+    Every added file counts, rows or not (an empty CSV file); a file added twice counts twice.  Names without a reference
+    raise KeyError (overlap=None) or are skipped (the overlap variants), like the host; the overlap variants also skip the
+    files without overlapping frames.  A skipped clip of an ``add_rows`` batch is scored against an empty table entry that
+    nothing reads."""
+
+    def __init__(self, params, ref_files_folder, device="cuda:0", overlap=None):
+        if overlap not in (None, "polyphony", "homogenous"):
+            raise ValueError("overlap must be None, 'polyphony' or 'homogenous' (got %r)" % (overlap,))
+        dc = params["data_config"]
+        self.nb_classes = c = dc["nb_classes"]
+        self._fpb = int(dc["sr"] / float(int(dc["sr"] * dc["label_hop_len_s"])))
+        self.overlap, self.device = overlap, device
+        refs, keeps, self.names = [], [], []
+        n_ov_frames = 0
+        for name in os.listdir(ref_files_folder):
+            gt = load_output_format_file(os.path.join(ref_files_folder, name))
+            nb = max(list(gt.keys()))
+            if overlap is not None:
+                kept = overlap_frames(gt, c, overlap == "homogenous")
+                n_ov_frames += len(kept)
+                if not kept:
+                    continue
+                keeps.append(kept)
+            refs.append((gt, nb))
+            self.names.append(name)
+        if overlap is not None:
+            self.nb_overlap_files, self.nb_overlap_frames = len(self.names), n_ov_frames
+        self._index = {name: k for k, name in enumerate(self.names)}
+        self._skip = len(self.names)                               # the empty entry: no blocks, never counted
+        refs.append(({}, 0))
+        keeps.append([])
+        packed = pack_reference(refs, c, self._fpb, keeps if overlap is not None else None)
+        self._frames = (packed["file_info"][:, 1].astype(np.int64) * self._fpb).tolist()
+        self.table = SELDRefTable(packed, c, self._fpb, device)
+        self._ids = {}
+        self.reset()
+
+    def reset(self):
+        """Forget every added file."""
+        import torch
+        self._acc = torch.zeros(self.table.n_files, 9 * self.nb_classes + 3, dtype=torch.float64, device=self.device)
+        self._status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._order = []                                           # file indices, each once, in the order first added
+
+    def _lookup(self, name):
+        """Table index of a prediction file name (with or without .csv); the empty entry for a file the overlap variants skip."""
+        key = name if name.endswith(".csv") else name + ".csv"
+        if key not in self._index:
+            if self.overlap is None:
+                raise KeyError(key)
+            return self._skip
+        return self._index[key]
+
+    def _score(self, rows, counts, ids, t_clip):
+        import torch
+        from . import ops
+        key = tuple(ids)
+        dev = self._ids.get(key)
+        if dev is None:
+            if len(self._ids) >= 64:
+                self._ids.clear()
+            dev = self._ids[key] = torch.tensor(ids, dtype=torch.int32).to(self.device, non_blocking=True)
+        ops.seld_score(rows, counts, self.table, dev, t_clip, self._acc, self._status)
+        seen = set(self._order)
+        for k in ids:
+            if k != self._skip and k not in seen:
+                self._order.append(k)
+                seen.add(k)
+
+    def add_rows(self, rows, counts, names):
+        """rows (N, 5) [frame, class, x, y, z] and counts (len(names) * T',) int32 on the device for len(names) clips of T'
+        frames (names as ``FoaDataset.get_filelist()`` gives them); rows past counts.sum() are not read.  No synchronisation."""
+        ids = [self._lookup(n) for n in names]
+        if not names or counts.numel() % len(names):
+            raise ValueError("add_rows: %d frame counts for %d clips" % (counts.numel(), len(names)))
+        self._score(rows, counts.reshape(-1), ids, counts.numel() // len(names))
+
+    def add_dict(self, name, labels):
+        """Host rows {frame: [[class, x, y, z], ...]} of one file (what ``LabelPostProcessor.select`` returns); uploaded in
+        float64, so they score exactly as the CSV file of the same rows would."""
+        import torch
+        k = self._lookup(name)
+        if k == self._skip:
+            return
+        t = max(1, self._frames[k])
+        frames = sorted(int(fr) for fr in labels if 0 <= int(fr) < t)
+        counts = np.zeros(t, dtype=np.int32)
+        vals = []
+        for fr in frames:
+            counts[fr] = len(labels[fr])
+            vals.extend([float(fr)] + [float(v) for v in r[:4]] for r in labels[fr])
+        rows = torch.from_numpy(np.asarray(vals, dtype=np.float64).reshape(-1, 5)).to(self.device)
+        self._score(rows, torch.from_numpy(counts).to(self.device), [k], t)
+
+    def accumulators(self):
+        """(files added, 9 C + 3) float64 on the host, one row per file in the order first added, and their names.  Raises
+        ``AdyoloHipError`` when a call has failed on the device (e.g. more than 1024 predictions of one frame and class)."""
+        from . import ops
+        ops.seld_status_check(self._status)
+        acc = ops.to_host(self._acc).numpy()
+        return acc[self._order].copy(), [self.names[k] for k in self._order]
+
+    def scores(self, is_jackknife=False):
+        """What ``get_SELD_Results(pred_folder, is_jackknife)`` returns for the added files (jackknife: files left out in the
+        order they were first added)."""
+        acc, _ = self.accumulators()
+        if is_jackknife:
+            return jackknife_from_accumulators(acc, self.nb_classes)
+        return macro_average(acc.sum(0), self.nb_classes)

@@ -6,7 +6,7 @@ import shutil
 
 import torch
 
-from .postprocess import write_seld_output_file
+from .postprocess import group_rows, write_seld_output_file
 
 
 def delete_and_create_folder(dir_pth):
@@ -32,7 +32,7 @@ def test_epoch(dataloader, filelist, model, criterion, postprocessor, device, ou
 
 
 def sweep_conf_thresh(dataloader, filelist, model, criterion, postprocessor, scorer, device, output_pth,
-                      thresholds=None, device_select=False):
+                      thresholds=None, device_select=False, device_score=False):
     """The reference's periodic threshold reset (src/train.py:178-203): try conf_thresh 0.1 .. 0.9, keep the first one
     with the lowest validation SELD score, leave it set on the post-processor (which rewrites conf AND class threshold,
     datasets.py:532-534).  The reference re-runs the whole validation epoch for each of the nine thresholds; the network
@@ -40,8 +40,16 @@ def sweep_conf_thresh(dataloader, filelist, model, criterion, postprocessor, sco
     the CSV files and the metrics are redone per threshold -- same files, same scores, a ninth of the forward passes.
     device_select: every file's decode stays on the device (~6 MB per 60 s clip) and the nine selections run there
     (``postprocessor.select_device``); only the selected rows come back to the host.
+    device_score: ``scorer`` is a ``seld_metrics.DeviceSELDScorer``; every threshold's rows are scored on the device (device
+    rows with device_select, ``add_rows``; host rows otherwise, ``add_dict``) without CSV files, and only the last threshold's
+    CSV files are written, so ``output_pth`` ends up as the host sweep leaves it.
     -> (new_thresh, [[ER, F, LE, LR, SELD] per threshold], mean validation loss)"""
     import numpy as np
+    from . import ops
+    from .seld_metrics import DeviceSELDScorer
+    if device_score and not isinstance(scorer, DeviceSELDScorer):
+        raise ValueError("sweep_conf_thresh: device_score=True needs a seld_metrics.DeviceSELDScorer (got %s)"
+                         % type(scorer).__name__)
     if thresholds is None:
         thresholds = np.arange(0.1, 1.0, 0.1)
     model.eval()
@@ -59,13 +67,26 @@ def sweep_conf_thresh(dataloader, filelist, model, criterion, postprocessor, sco
                 decoded.append(postprocessor.decode(output))
             n = i + 1
     new_thresh, best, table = postprocessor.get_conf_thresh(), 9999.0, []
-    for th in thresholds:
+    for k, th in enumerate(thresholds):
         postprocessor.set_conf_thresh(th)
-        delete_and_create_folder(output_pth)
+        write = not device_score or k == len(thresholds) - 1
+        if write:
+            delete_and_create_folder(output_pth)
+        if device_score:
+            scorer.reset()
         for i, dec in enumerate(decoded):
-            rows = postprocessor.select_device(dec)[0] if device_select else postprocessor.select(dec)
-            write_seld_output_file(os.path.join(output_pth, filelist[i] + ".csv"), rows)
-        er, f, le, lr, seld = scorer.get_SELD_Results(output_pth)[:5]
+            if device_score and device_select:                  # rows stay on the device; the row total is read to write
+                rows, counts = postprocessor.select_device_rows(dec, trim=write)
+                scorer.add_rows(rows, counts, [filelist[i]])
+                if write:
+                    rows = group_rows(*[t.numpy() for t in ops.to_host_many(rows, counts)])[0]
+            else:
+                rows = postprocessor.select_device(dec)[0] if device_select else postprocessor.select(dec)
+                if device_score:
+                    scorer.add_dict(filelist[i], rows)
+            if write:
+                write_seld_output_file(os.path.join(output_pth, filelist[i] + ".csv"), rows)
+        er, f, le, lr, seld = (scorer.scores() if device_score else scorer.get_SELD_Results(output_pth))[:5]
         table.append([er, f, le, lr, seld])
         if seld < best:
             new_thresh, best = th, seld
@@ -74,7 +95,7 @@ def sweep_conf_thresh(dataloader, filelist, model, criterion, postprocessor, sco
 
 
 def test_epoch_audio(dataset, model, features, criterion, postprocessor, device, output_pth, batch_size=1, forward=None,
-                     device_select=False):
+                     device_select=False, device_scorer=None):
     """``test_epoch`` for a raw-audio ``FoaDataset`` split ('valid' / 'test' / 'infer'): int16 audio normalised on the GPU, K1
     features, encoder + head, loss, decode + NMS, one CSV per clip named after the file.  Returns the mean loss (0 for
     'infer', which has no labels).
@@ -85,9 +106,18 @@ def test_epoch_audio(dataset, model, features, criterion, postprocessor, device,
     3 ms per clip at B = 1 against ~1 ms at B = 8 on MI355X.  The loss stays per clip (its normalisers are per call), averaged
     over the clips like the reference's.  forward: optional ``graph.ForwardGraphs`` (K1 + model + decode replayed from a
     hipGraph per clip length); default: eager calls.  device_select: the decoded batch is selected on the device
-    (``postprocessor.select_device``, launched after the graph replay, not recorded in it) and only the rows come back."""
+    (``postprocessor.select_device``, launched after the graph replay, not recorded in it) and only the rows come back.
+    device_scorer: a ``seld_metrics.DeviceSELDScorer`` the selected rows of every batch are also added to (the device rows
+    with device_select); the CSV files are written all the same, and the caller reads ``device_scorer.scores()``."""
     from . import ops
     from .datasets import audio_collate_fn
+
+    def select_on_device(dec, clips):
+        rows, counts = postprocessor.select_device_rows(dec, len(clips))
+        if device_scorer is not None:
+            device_scorer.add_rows(rows, counts, clips)
+        return group_rows(*[t.numpy() for t in ops.to_host_many(rows, counts)], len(clips))
+
     model.eval()
     delete_and_create_folder(output_pth)
     total, n = None, 0
@@ -109,13 +139,13 @@ def test_epoch_audio(dataset, model, features, criterion, postprocessor, device,
             if forward is not None:
                 output, dec = forward(audio)
                 if dec is not None and device_select:
-                    selected = postprocessor.select_device(dec, len(items))
+                    selected = select_on_device(dec, names[i:i + len(items)])
                 elif dec is not None:                         # the graph decoded the whole batch: ONE page-locked copy to the host
                     decoded = ops.to_host(dec).numpy()
             else:
                 output = model(features(audio, channels_last8=True), channels_last8=True)
             if device_select and selected is None:
-                selected = postprocessor.select_device(postprocessor.decode_device(output), len(items))
+                selected = select_on_device(postprocessor.decode_device(output), names[i:i + len(items)])
             for b, (pcm, _, rows) in enumerate(items):
                 out_b = output[b:b + 1]
                 dense = isinstance(rows, torch.Tensor)          # class-wise losses: (T', ...) label, all zeros for 'infer'
@@ -131,6 +161,8 @@ def test_epoch_audio(dataset, model, features, criterion, postprocessor, device,
                     rows_out = postprocessor.select(decoded[b * tp:(b + 1) * tp])
                 else:
                     rows_out = postprocessor.postprocess(out_b)
+                if device_scorer is not None and selected is None:
+                    device_scorer.add_dict(names[i + b], rows_out)
                 write_seld_output_file(os.path.join(output_pth, names[i + b] + ".csv"), rows_out)
             i += len(items)
     return float(total) / max(n, 1) if total is not None else 0.0

@@ -407,6 +407,39 @@ int  adyolo_yolo_select(const float *dec, float *ws, float *rows, int *frame_cou
                         float conf_thresh, float clss_thresh, float unify_thresh, float vote_thresh, int mode,
                         void *stream);
 
+/* K8d SELD scoring (csrc/seld.hip), opt-in: what seld_metrics.SELDScorer.update adds for one recording (DCASE
+ * location-sensitive detection and class-sensitive localisation over blocks of fpb frames, Hungarian association of the
+ * predictions with the reference events per frame and class, 20-degree tracks), for rows already on the device.
+ *   rows    [n_rows][5] [frame, class, x, y, z], float32 (rows_f64 = 0: what adyolo_yolo_select writes) or float64 (1); the
+ *           frame column is not read: counts [n_clips * t_clip] int32 gives the rows of each frame, clip after clip, frames
+ *           in order (a capacity n_rows beyond their sum is allowed).  Within a frame classes may come in any order; the
+ *           order within a (frame, class) is kept (it decides the assignment under ties, as in scipy).
+ *   file_ids [n_clips] int32: the reference file of each clip
+ *   reference table, uploaded once (seld_metrics.DeviceSELDScorer):
+ *     file_info [n_files][2] int32: first frame of the file in the table, number of blocks ceil(len / fpb), len = the
+ *               largest frame index of its reference; frames >= blocks * fpb are not scored
+ *     ref_off   [table frames * C + 1] int32: events of (frame, class) are ref_ev[ref_off[f * C + c] .. ref_off[f * C + c + 1])
+ *               in reference order, at most ADYOLO_SELD_MAX_REF per (frame, class)
+ *     ref_ev    [n_events][3] float64: azimuth in rad, sin and cos of the elevation
+ *     keep      NULL, or [table frames] int32: only predictions of frames with keep != 0 are scored (overlap variants)
+ *   acc     [n_files][9 * C + 3] float64, ADDED to: TP, FP, FP_spatial, FN, Nref, total_DE, DE_TP, DE_FP, DE_FN (each C
+ *           classes wide), then S, D, I
+ *   ws      adyolo_seld_score_workspace_words(n_clips, t_clip, max_blocks, C) words; max_blocks >= every blocks of file_info
+ *   status  one int32 the kernels OR ADYOLO_SELD_* bits into; while it is nonzero (an error of this or an earlier call) acc
+ *           is left as it is.  n_pred is only known on the device: more than ADYOLO_SELECT_MAX_N predictions of one
+ *           (frame, class) set ADYOLO_SELD_PRED_OVERFLOW, which the caller reports as ENOSUP. */
+#define ADYOLO_SELD_MAX_REF 8
+#define ADYOLO_SELD_PRED_OVERFLOW 1   /* more than ADYOLO_SELECT_MAX_N predictions in one (frame, class) */
+#define ADYOLO_SELD_REF_OVERFLOW  2   /* more than ADYOLO_SELD_MAX_REF reference events in one (frame, class) */
+#define ADYOLO_SELD_BAD_ROWS      4   /* a negative count, or counts summing past n_rows */
+#define ADYOLO_SELD_BAD_FILE      8   /* a file id outside [0, n_files) */
+#define ADYOLO_SELD_NO_ASSIGNMENT 16  /* no finite assignment (a NaN coordinate) */
+long adyolo_seld_score_workspace_words(long n_clips, int t_clip, int max_blocks, int C);
+int  adyolo_seld_score(const void *rows, int rows_f64, long n_rows, const int *counts, long n_clips, int t_clip,
+                       const int *file_ids, const int *file_info, const int *ref_off, const double *ref_ev, const int *keep,
+                       int n_files, int C, int fpb, int max_blocks, double doa_thresh, float *ws, double *acc, int *status,
+                       void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * K10 the other heads / losses behind the reference's --loss switch (src/main.py:43)
  *   adyolo_act_fwd/bwd : y[r][c] = c < n_sigmoid_cols ? sigmoid(x) : tanh(x)   (linearheads.py:44-47,65,83)

@@ -8,7 +8,14 @@ Workload (BASELINE.json configs[1]): synthetic 4-ch 24 kHz 60 s clips, batch 64 
 12 classes, random-init weights (seed 100), fp32 arithmetic (exact-fp32 MFMA).  Weak scaling: every rank
 processes its own 64 clips.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--seconds S] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--seconds S] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: it sets up, runs W warm-up and K timed steps, writes its outputs
+(--dump-outputs) and prints the line -- the headline plus what the timed steps themselves recorded (`roofline`,
+`stages.conv3x3_fwd_dgrad`).  --full adds every other measurement and check, in this order: the parity gate (before the
+warm-up), then after the timed steps the host-fed `pipeline`, the `dispatch` step, `stages.encoder_fwd`, the instrumented
+`stages` steps (with `conv3x3_wgrad` and `k1_features`), the `rccl` block and its reducer-off run (N > 1), `extra_configs`
+and `cpu_baseline`.  The --no-* switches leave parts of a --full run out.
 
 --dump-outputs DIR writes what the last timed step computed (loss, parameters, gradients, BatchNorm statistics) as
 DIR/<name>.npy; inputs and initial weights are seeded, so two builds run with the same arguments compare output for output.
@@ -22,9 +29,9 @@ Rank 0 prints ONE JSON line.  `roofline` is measured live with HIP events (torch
 kernels are launched on) around every launch of the dominant kernel family (conv3x3 forward / data-gradient)
 inside the timed region: `achieved` = matrix FLOPs ISSUED per second (Winograd issues 16/36 of the algorithmic
 convolution FLOPs), `frac` = achieved / the exact-fp32 MFMA peak, `algorithmic_tflops` = the direct-convolution FLOPs
-per second the same launches stand for.  `stages` (HBM-bound passes: GB/s against 8 TB/s) are timed with HIP events in
-two extra, separately instrumented steps AFTER the timed region, so their events do not perturb `value`.
-`cpu_baseline` times the CPU oracle (a port of the reference path, `oracle/`) on the host cores on a bounded sample
+per second the same launches stand for.  `stages` (HBM-bound passes: GB/s against 8 TB/s; --full) are timed with HIP events
+in two extra, separately instrumented steps AFTER the timed region, so their events do not perturb `value`.
+`cpu_baseline` (--full) times the CPU oracle (a port of the reference path, `oracle/`) on the host cores on a bounded sample
 (8 x 20 s clips, 3 warm-ups, median of 5 steps; N = 1, rank 0 only).
 """
 import argparse
@@ -543,16 +550,19 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=64, help="clips per GPU")
     ap.add_argument("--seconds", type=int, default=60, help="clip length")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-stages", action="store_true", help="skip the two extra instrumented steps")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra_configs block (the reference's own shapes)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run every other measurement and check: parity gate, pipeline, dispatch step, "
+                         "encoder forward, instrumented stage steps, reducer-off run (N > 1), extra_configs, cpu_baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-stages", action="store_true", help="with --full: skip the two extra instrumented steps")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the extra_configs block (the reference's own shapes)")
     ap.add_argument("--only-extra", default=None, help="run ONE extra config by name and print its entry (profiling)")
     ap.add_argument("--extra-mode", default="both", choices=["both", "hipgraph", "eager"],
                     help="with --only-extra: run only the graph or only the eager variant (profiling: a known step count)")
     ap.add_argument("--no-parity", action="store_true",
-                    help="skip the parity gate (profiling: its 8-clip launches would enter the per-kernel averages of the trace)")
+                    help="with --full: skip the parity gate (profiling: its 8-clip launches would enter the per-kernel averages of the trace)")
     ap.add_argument("--no-pipeline", dest="pipeline", action="store_false",
-                    help="skip the host-fed variant of the step (int16 clips through AudioStager), reported as `pipeline`")
+                    help="with --full: skip the host-fed variant of the step (int16 clips through AudioStager), reported as `pipeline`")
     ap.add_argument("--graph", action="store_true", help="replay the headline step from a hipGraph too (no per-kernel events)")
     ap.add_argument("--event-kind", default="timing", choices=["timing", "torch"],
                     help="timing: HIP events created with hipEventDisableSystemFence (no L2 write-back / invalidate "
@@ -610,12 +620,12 @@ def main():
     conv_algo = ops.conv_algo()
     wino = conv_algo in ("winograd", "winograd4")
 
-    # parity gate at the benchmark's clip shape on a SLICE of the batch (12 clips: every layer still takes the kernel the full
+    # (--full) parity gate at the benchmark's clip shape on a SLICE of the batch (12 clips: every layer still takes the kernel the full
     # batch takes -- ops.DualPack picks by launch size, the 128 -> 64 data-gradient needs 11 clips; round 3 ran it on all 64
     # clips, 40 GB of allocator churn before the timed region): the first forward loss with the benchmarked (Winograd) convolutions must equal
     # the direct implicit-GEMM path within 1e-3 (both are checked against torch / the oracle in tests/)
     parity = None
-    if args.encoder == "se-resnet34" and wino and world == 1 and not args.no_parity:      # (N > 1: a rank-0-only assert would strand the other ranks)
+    if args.full and args.encoder == "se-resnet34" and wino and world == 1 and not args.no_parity:      # (N > 1: a rank-0-only assert would strand the other ranks)
         model.train()
         vals, outs = {}, {}
         nb = min(B, 12)
@@ -749,7 +759,7 @@ def main():
     # how many bucket all-reduces per step were issued from gradient hooks (overlapped with the backward pass) against from
     # finish() (exposed), and the same step with the reducer switched off (its difference to ms_per_step = exposed all-reduce)
     rccl = None
-    if world > 1:
+    if world > 1 and args.full:
         red = trainer.reducer
         ones = torch.ones(1, device=device)
         dist.all_reduce(ones)
@@ -770,7 +780,7 @@ def main():
     # AudioStager's page-locked buffer (a worker thread, as DataLoader workers would) -> PCIe copy on a side stream, overlapped
     # with the step on the previous batch -> int16 -> float32 on the device -> the step.  `value` stays the resident-input rate.
     pipeline = None
-    if args.pipeline:
+    if args.full and args.pipeline:
         from adyolo_amd.datasets import AudioStager
         host = [torch.clamp(torch.round((audio.double() - 1e-8) * 32768.0), -32768, 32767).to(torch.int16).cpu()]   # the int16 the clips came from
         host.append(torch.flip(host[0], dims=[0]).contiguous())                    # a second batch: the same clips in reverse order
@@ -806,7 +816,7 @@ def main():
     # ---- which kernel every 3x3 convolution of one step launches: counted in one extra step
     # (every rank runs these extra steps -- with N > 1 the reducer's all-reduces need all of them; rank 0 keeps the books)
     dispatch = None
-    if not args.graph:
+    if args.full and not args.graph:
         ops.DISPATCH_LOG = {}
         trainer.step(audio, target)
         torch.cuda.synchronize()
@@ -826,7 +836,7 @@ def main():
     # ---- the encoder + head FORWARD alone, training mode (north_star: ">= 40 % MFMA utilisation on the SE-ResNet forward";
     # 2.269 GFLOP per audio-second algorithmic): HIP events around model(feat) on precomputed features
     encoder_fwd = None
-    if not args.graph and args.encoder == "se-resnet34":
+    if args.full and not args.graph and args.encoder == "se-resnet34":
         model.train()
         feat = fx(audio, channels_last8=True)
         n_f0 = len(timer.records.get("conv3x3_fwd_dgrad", []))
@@ -863,7 +873,7 @@ def main():
         torch.cuda.empty_cache()
 
     stages = {}
-    if not args.no_stages and not args.graph:
+    if args.full and not args.no_stages and not args.graph:
         n_inst = 2
         trainer.step(audio, target)            # (untimed: the allocator refills its pool after the empty_cache() above)
         torch.cuda.synchronize()
@@ -895,7 +905,7 @@ def main():
         stages["_elementwise_total"] = {"ms_per_step": round(ew_ms, 3), "share_of_step": round(ew_ms / step_ms, 4),
                                         "instrumented_step_ms": round(inst_ms, 3)}
 
-    if world > 1:
+    if rccl is not None:
         # "reducer off": the same step without the gradient all-reduce (its difference to ms_per_step = exposed all-reduce).  LAST
         # measurement of the run: the replicas (parameters AND Adam moments) drift apart while nothing is averaged, and nothing
         # that assumes identical replicas follows (round 4 ran it before the pipeline / stage passes; ADVICE)
@@ -969,6 +979,8 @@ def main():
             "timing": {"events_in_timed_steps": args.events, "event_kind": EVENT_KIND_USED["kind"],
                        "event_fallback": EVENT_KIND_USED["fallback"]},
         }
+        if not (args.full or ev_all):                   # (recorded only in the instrumented steps of --full: nothing to report)
+            del line["stages"]["conv3x3_wgrad"], line["stages"]["k1_features"]
         line["stages"].update(stages)
         if encoder_fwd is not None:
             line["stages"]["encoder_fwd"] = encoder_fwd
@@ -980,11 +992,11 @@ def main():
             line["rccl"] = rccl
         if pipeline is not None:
             line["pipeline"] = pipeline
-        if world == 1 and not args.no_extra and args.encoder == "se-resnet34":
+        if args.full and world == 1 and not args.no_extra and args.encoder == "se-resnet34":
             del trainer, model                          # the headline model's 40 GB of cached activations go back first
             torch.cuda.empty_cache()
             line["extra_configs"] = {name: run_extra_config(name, torch) for name in EXTRA_CONFIGS}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline()
         print(json.dumps(line), flush=True)
     if dist.is_initialized():

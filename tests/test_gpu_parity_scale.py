@@ -1148,7 +1148,7 @@ def test_exact_data_parallel_equals_one_device_on_the_concatenated_batch(ops, tm
 
 
 def test_bench_two_ranks_functional_run_on_one_device(ops):
-    """``bench.py --gpus 2`` end to end on this single-GPU box: the launcher starts two workers, both on cuda:0 over gloo
+    """``bench.py --gpus 2 --full`` end to end on this single-GPU box: the launcher starts two workers, both on cuda:0 over gloo
     (ADYOLO_DIST_BACKEND / ADYOLO_BENCH_ONE_DEVICE: RCCL refuses two ranks on one device), barrier + max-over-ranks timing,
     rank 0 prints ONE JSON line with n_gpus = 2 and the whole-job aggregate.  A functional check of the N > 1 path of the
     benchmark (launcher, rank env, collectives, JSON contract) -- its numbers mean nothing."""
@@ -1160,7 +1160,7 @@ def test_bench_two_ranks_functional_run_on_one_device(ops):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "ADYOLO_FORCE_DP_HOOKS"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2",
-                        "--seconds", "4", "--no-cpu-baseline", "--no-stages", "--no-extra"], env=env, capture_output=True, text=True,
+                        "--seconds", "4", "--full", "--no-cpu-baseline", "--no-stages", "--no-extra"], env=env, capture_output=True, text=True,
                        timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]
@@ -1181,3 +1181,43 @@ def test_bench_two_ranks_functional_run_on_one_device(ops):
     pl = d["pipeline"]
     assert pl["ms_per_step"] > 0 and abs(pl["value"] - 2 * 2 * 4 / (pl["ms_per_step"] * 1e-3)) <= 0.01 * pl["value"]
     assert abs(pl["h2d_MB_per_step_per_gpu"] - 2 * 96000 * 4 * 2 / 1e6) < 0.11
+
+
+def test_bench_plain_run_is_the_headline_alone_and_full_computes_the_same(ops, tmp_path):
+    """A plain ``bench.py`` run times its steps and prints the headline with what those steps recorded, nothing else; ``--full``
+    adds the parity gate, the pipeline, the dispatch step, the encoder forward and the instrumented stage steps -- and its
+    timed steps compute exactly what the plain run's compute (the parity gate runs before them on a model that is rebuilt
+    from the same seed; every other extra runs after the outputs are written)."""
+    import json
+    import subprocess
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "ADYOLO_BENCH_ONE_DEVICE"):
+        env.pop(k, None)
+    lines = {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline", "--no-extra"])):
+        r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "2",
+                            "--seconds", "4", "--dump-outputs", str(tmp_path / mode)] + extra, env=env, capture_output=True,
+                           text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]
+        assert len(out) == 1, r.stdout[-2000:]
+        lines[mode] = json.loads(out[0])
+    p, f = lines["plain"], lines["full"]
+    for d in (p, f):
+        assert d["unit"] == "audio-s/s" and d["higher_is_better"] is True and d["dtype"] == "f32" and d["n_gpus"] == 1
+        assert d["steps"] == 2 and d["warmup"] == 1 and abs(d["value"] - 2 * 4 / (d["ms_per_step"] * 1e-3)) <= 0.01 * d["value"]
+        assert d["roofline"]["launches"] > 0 and d["stages"]["conv3x3_fwd_dgrad"]["launches"] > 0
+    for key in ("parity_check", "pipeline", "dispatch", "rccl", "extra_configs", "cpu_baseline"):
+        assert key not in p, key
+    assert set(p["stages"]) == {"conv3x3_fwd_dgrad"}
+    for key in ("parity_check", "pipeline", "dispatch"):
+        assert key in f, key
+    for key in ("conv3x3_wgrad", "k1_features", "encoder_fwd", "_elementwise_total"):
+        assert key in f["stages"], key
+    assert f["stages"]["conv3x3_wgrad"]["launches"] > 0 and f["stages"]["k1_features"]["ms"] > 0
+    assert p["final_loss"] == f["final_loss"]
+    for name in ("loss", "parameters", "gradients", "buffers"):
+        a, b = np.load(tmp_path / "plain" / (name + ".npy")), np.load(tmp_path / "full" / (name + ".npy"))
+        assert a.shape == b.shape and np.array_equal(a, b), name

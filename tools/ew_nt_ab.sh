@@ -3,7 +3,7 @@ a=${1:--}; b=$2
 for lib in $a $b $a $b; do
   [ "$lib" = "-" ] && lib=""
   echo "== lib: ${lib:-in-tree}"
-  ADYOLO_LIB=$lib python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extra --no-pipeline --no-parity 2>/dev/null | python3 -c "
+  ADYOLO_LIB=$lib python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-extra --no-pipeline --no-parity 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.readline())
 st=d['stages']

@@ -338,6 +338,71 @@ __global__ __launch_bounds__(GTH) void gru_bwd_kernel(const float *__restrict__ 
 }
 
 // ---------------------------------------------------------------------------------- LayerNorm + tanh (C = 256)
+// Rows far from zero mean.  The fp32 sum of a row misses by up to ~ulp(|sum|), and that miss shifts every x - mean of the
+// row alike, by ~(|mean| / std) x 1e-7 of the row's std (mean 1e3, std 1e-2: x_hat off by 2e-3).  The kernels below keep
+// the plain two-pass form for rows with |mean| <= 4 std and hand every other row to these functions, which centre it once
+// more by the mean of its deviations (corrected two-pass).  They are not inlined, so the plain path compiles as it did
+// without them.  mean and var are wave-uniform (every lane of the butterfly holds the same sums): the whole wave takes the
+// same branch.
+__device__ __forceinline__ float4 ln_row_centred(const float4 v, float &is, float eps) {
+    const float mean = wave_sum(v.x + v.y + v.z + v.w) * (1.0f / 256.f);
+    float4 d = make_float4(v.x - mean, v.y - mean, v.z - mean, v.w - mean);
+    const float miss = wave_sum(d.x + d.y + d.z + d.w) * (1.0f / 256.f);
+    d = make_float4(d.x - miss, d.y - miss, d.z - miss, d.w - miss);
+    const float var = wave_sum(d.x * d.x + d.y * d.y + d.z * d.z + d.w * d.w) * (1.0f / 256.f);
+    is = 1.0f / sqrtf(var + eps);
+    return d;
+}
+
+// |mean| > 4 std?  Computed apart from the kernels' own statistics (so that their arithmetic is unchanged).
+__device__ __noinline__ bool ln_row_far(const float *__restrict__ x, long row) {
+    const float4 v = reinterpret_cast<const float4 *>(x + (size_t)row * 256)[threadIdx.x & 63];
+    const float mean = wave_sum(v.x + v.y + v.z + v.w) * (1.0f / 256.f);
+    const float4 d = make_float4(v.x - mean, v.y - mean, v.z - mean, v.w - mean);
+    const float var = wave_sum(d.x * d.x + d.y * d.y + d.z * d.z + d.w * d.w) * (1.0f / 256.f);
+    return mean * mean > 16.f * var;
+}
+
+template <bool TANH>
+__device__ __noinline__ void ln_fwd_row_centred(const float *__restrict__ x, const float *__restrict__ gamma,
+                                                const float *__restrict__ beta, float *__restrict__ y, long row, float eps) {
+    const int lane = threadIdx.x & 63;
+    float is;
+    const float4 d = ln_row_centred(reinterpret_cast<const float4 *>(x + (size_t)row * 256)[lane], is, eps);
+    const float4 g = reinterpret_cast<const float4 *>(gamma)[lane];
+    const float4 bt = reinterpret_cast<const float4 *>(beta)[lane];
+    float4 o = make_float4(d.x * is * g.x + bt.x, d.y * is * g.y + bt.y, d.z * is * g.z + bt.z, d.w * is * g.w + bt.w);
+    if (TANH) o = make_float4(tanhf(o.x), tanhf(o.y), tanhf(o.z), tanhf(o.w));
+    reinterpret_cast<float4 *>(y + (size_t)row * 256)[lane] = o;
+}
+
+struct LnRowGrad {
+    float4 dg, db;        // this lane's dgamma / dbeta terms of the row
+};
+
+template <bool TANH>
+__device__ __noinline__ LnRowGrad ln_bwd_row_centred(const float *__restrict__ dy, const float *__restrict__ x,
+                                                     const float *__restrict__ y, const float *__restrict__ gamma,
+                                                     float *__restrict__ dx, long row, float eps) {
+    const int lane = threadIdx.x & 63;
+    float is;
+    const float4 d = ln_row_centred(reinterpret_cast<const float4 *>(x + (size_t)row * 256)[lane], is, eps);
+    const float4 go = reinterpret_cast<const float4 *>(dy + (size_t)row * 256)[lane];
+    const float4 g = reinterpret_cast<const float4 *>(gamma)[lane];
+    float4 yo = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (TANH) yo = reinterpret_cast<const float4 *>(y + (size_t)row * 256)[lane];
+    const float4 xh = make_float4(d.x * is, d.y * is, d.z * is, d.w * is);
+    const float4 dp = make_float4(go.x * (1.f - yo.x * yo.x), go.y * (1.f - yo.y * yo.y),
+                                  go.z * (1.f - yo.z * yo.z), go.w * (1.f - yo.w * yo.w));
+    const float4 dxh = make_float4(dp.x * g.x, dp.y * g.y, dp.z * g.z, dp.w * g.w);
+    const float m1 = wave_sum(dxh.x + dxh.y + dxh.z + dxh.w) * (1.0f / 256.f);
+    const float m2 = wave_sum(dxh.x * xh.x + dxh.y * xh.y + dxh.z * xh.z + dxh.w * xh.w) * (1.0f / 256.f);
+    reinterpret_cast<float4 *>(dx + (size_t)row * 256)[lane] =
+        make_float4(is * (dxh.x - m1 - xh.x * m2), is * (dxh.y - m1 - xh.y * m2), is * (dxh.z - m1 - xh.z * m2),
+                    is * (dxh.w - m1 - xh.w * m2));
+    return {make_float4(dp.x * xh.x, dp.y * xh.y, dp.z * xh.z, dp.w * xh.w), dp};
+}
+
 template <bool TANH>
 __global__ __launch_bounds__(256) void ln_tanh_fwd_kernel(const float *__restrict__ x, const float *__restrict__ gamma,
                                                           const float *__restrict__ beta, float *__restrict__ y,
@@ -345,6 +410,10 @@ __global__ __launch_bounds__(256) void ln_tanh_fwd_kernel(const float *__restric
     const int lane = threadIdx.x & 63;
     const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= R) return;
+    if (ln_row_far(x, row)) {                  // far from zero mean: corrected centring (ln_row_centred)
+        ln_fwd_row_centred<TANH>(x, gamma, beta, y, row, eps);
+        return;
+    }
     const float4 v = reinterpret_cast<const float4 *>(x + (size_t)row * 256)[lane];
     const float mean = wave_sum(v.x + v.y + v.z + v.w) * (1.0f / 256.f);
     const float4 d = make_float4(v.x - mean, v.y - mean, v.z - mean, v.w - mean);
@@ -370,9 +439,16 @@ __global__ __launch_bounds__(256) void ln_tanh_bwd_kernel(const float *__restric
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const float4 g = reinterpret_cast<const float4 *>(gamma)[lane];
     float4 dga = make_float4(0.f, 0.f, 0.f, 0.f), dba = dga;
+    float4 fga = dga, fba = dga;                  // the same from rows far from zero mean (kept apart)
     const long rbeg = (long)blockIdx.x * rows_per_block;
     const long rend = rbeg + rows_per_block < R ? rbeg + rows_per_block : R;
     for (long row = rbeg + wave; row < rend; row += 4) {
+        if (ln_row_far(x, row)) {              // far from zero mean: corrected centring (ln_row_centred)
+            const LnRowGrad c = ln_bwd_row_centred<TANH>(dy, x, y, gamma, dx, row, eps);
+            fga.x += c.dg.x; fga.y += c.dg.y; fga.z += c.dg.z; fga.w += c.dg.w;
+            fba.x += c.db.x; fba.y += c.db.y; fba.z += c.db.z; fba.w += c.db.w;
+            continue;
+        }
         const float4 v = reinterpret_cast<const float4 *>(x + (size_t)row * 256)[lane];
         const float4 go = reinterpret_cast<const float4 *>(dy + (size_t)row * 256)[lane];
         float4 yo = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -396,6 +472,8 @@ __global__ __launch_bounds__(256) void ln_tanh_bwd_kernel(const float *__restric
         o.w = is * (dxh.w - m1 - xh.w * m2);
         reinterpret_cast<float4 *>(dx + (size_t)row * 256)[lane] = o;
     }
+    dga.x += fga.x; dga.y += fga.y; dga.z += fga.z; dga.w += fga.w;
+    dba.x += fba.x; dba.y += fba.y; dba.z += fba.z; dba.w += fba.w;
     float *p = red[wave];
     p[lane * 4 + 0] = dga.x; p[lane * 4 + 1] = dga.y; p[lane * 4 + 2] = dga.z; p[lane * 4 + 3] = dga.w;
     p[256 + lane * 4 + 0] = dba.x; p[256 + lane * 4 + 1] = dba.y; p[256 + lane * 4 + 2] = dba.z;

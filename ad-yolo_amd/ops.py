@@ -767,8 +767,8 @@ def sap_fwd(x, w, b):
 
 
 def sap_bwd(dy, x, w, attn, out_dw=None, out_db=None):
-    """out_dw [C] / out_db [1]: ZEROED accumulators to sum into instead of fresh ones (``functional.GradSink``: the parameters' slices
-    of the flat gradient buffer, zero since ``zero_grad``)."""
+    """out_dw [C] / out_db [1]: accumulators the kernel ADDS the two gradients into instead of fresh zeros (``functional.GradSink``:
+    the parameters' slices of the flat gradient buffer, zero since ``zero_grad``)."""
     _chk(dy, x, w, attn)
     r, f, c = x.shape
     dx = torch.empty_like(x)
@@ -807,7 +807,7 @@ def ln_tanh_fwd(x2d, gamma, beta, eps=1e-5):
 
 
 def ln_tanh_bwd(dy2d, x2d, y2d, gamma, eps=1e-5, out_dgamma=None, out_dbeta=None):
-    """out_dgamma / out_dbeta [C]: ZEROED accumulators to sum into instead of fresh ones (see ``sap_bwd``)."""
+    """out_dgamma / out_dbeta [C]: accumulators the kernel ADDS the two gradients into instead of fresh zeros (see ``sap_bwd``)."""
     _chk(dy2d, x2d, y2d, gamma)
     r, c = x2d.shape
     dx = torch.empty_like(x2d)

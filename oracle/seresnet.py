@@ -82,6 +82,32 @@ def gru_cell_steps(x, w_ih, w_hh, b_ih, b_hh, reverse=False):
     return torch.stack(hs, dim=1)
 
 
+def gru_gate_steps(gx, w_hh, b_hh, reverse=False):
+    """``gru_cell_steps`` from the input projections ``gx`` (B,T,3H) = x W_ih^T + b_ih, keeping what the GPU recurrence
+    saves: dict of h, r, z, n, hn (= the n rows of h_prev W_hh^T + b_hh), hprev, each (B,T,H) in time order, and the
+    per-step pre-activations ``gh`` (B,3H each, in step order) for gradient checks (``retain_grad``)."""
+    b, t, _ = gx.shape
+    h = gx.new_zeros(b, w_hh.shape[1])
+    keep = {k: [None] * t for k in ("h", "r", "z", "n", "hn", "hprev")}
+    gh_steps = []
+    order = range(t - 1, -1, -1) if reverse else range(t)
+    for i in order:
+        gh = F.linear(h, w_hh, b_hh)
+        gh_steps.append(gh)
+        xr, xz, xn = gx[:, i].chunk(3, dim=1)
+        hr, hz, hn = gh.chunk(3, dim=1)
+        r = torch.sigmoid(xr + hr)
+        z = torch.sigmoid(xz + hz)
+        n = torch.tanh(xn + r * hn)
+        keep["hprev"][i] = h
+        h = (1.0 - z) * n + z * h
+        for k, v in (("h", h), ("r", r), ("z", z), ("n", n), ("hn", hn)):
+            keep[k][i] = v
+    out = {k: torch.stack(v, dim=1) for k, v in keep.items()}
+    out["gh"] = gh_steps
+    return out
+
+
 def _bigru_layer(sd, layer, x):
     names = ["lstm.weight_ih_l%d", "lstm.weight_hh_l%d", "lstm.bias_ih_l%d", "lstm.bias_hh_l%d"]
     flat = [sd[n % layer] for n in names] + [sd[(n % layer) + "_reverse"] for n in names]

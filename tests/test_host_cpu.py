@@ -434,3 +434,27 @@ def test_dispatch_thresholds_and_parameter_epoch(monkeypatch):
     e1 = ops.PARAMS_EPOCH[0]
     model.load_state_dict(model.state_dict())
     assert ops.PARAMS_EPOCH[0] == e1 + 1
+
+
+def test_float64_gru_references_match_torch_gru():
+    """The float64 references the GPU sequence-stage tests compare against: the explicit ``gru_cell_steps`` pair (both
+    directions) equals ``torch.nn.GRU(bidirectional=True)`` in float64, and ``gru_gate_steps`` (the same recurrence from the
+    input projections, keeping the gates) equals ``gru_cell_steps``, over several 16-step chunks."""
+    g = torch.Generator().manual_seed(7)
+    gru = torch.nn.GRU(256, 128, batch_first=True, bidirectional=True).double()
+    with torch.no_grad():
+        for p in gru.parameters():
+            p.uniform_(-1.0 / 128 ** 0.5, 1.0 / 128 ** 0.5, generator=g)
+    x = torch.randn(3, 37, 256, generator=g, dtype=torch.float64)
+    with torch.no_grad():
+        ref, _ = gru(x)
+        halves = []
+        for sfx, rev in (("", False), ("_reverse", True)):
+            w_ih, w_hh, b_ih, b_hh = (getattr(gru, "%s_l0%s" % (n, sfx)) for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"))
+            h = onet.gru_cell_steps(x, w_ih, w_hh, b_ih, b_hh, reverse=rev)
+            st = onet.gru_gate_steps(torch.nn.functional.linear(x, w_ih, b_ih), w_hh, b_hh, reverse=rev)
+            assert float((st["h"] - h).abs().max()) <= 1e-12
+            first = -1 if rev else 0
+            assert torch.equal(st["hprev"][:, first], torch.zeros_like(st["hprev"][:, first]))
+            halves.append(h)
+    assert float((torch.cat(halves, dim=-1) - ref).abs().max()) <= 1e-12

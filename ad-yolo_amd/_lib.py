@@ -126,6 +126,7 @@ SIGNATURES = {
     "adyolo_foa_rotate": (I, [P, P, P, I, L, P]),
     "adyolo_pcm16_to_f32": (I, [P, P, L, P]),
     "adyolo_mask_ranges": (I, [P, P, I, I, I, I, P]),
+    "adyolo_mask_groups": (I, [P, P, I, I, I, I, I, P, P]),
     "adyolo_colstats": (I, [P, P, P, L, I, P]),
     "adyolo_adam_step": (I, [P] * 4 + [L, F, F, F, F, F, I, F, P]),
     "adyolo_adam_step_dev": (I, [P] * 4 + [L, F, F, F, F, F, P, P, F, P]),

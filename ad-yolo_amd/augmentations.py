@@ -91,15 +91,25 @@ class SpecAug:
         start = random.random() * (size - value)
         return int(start), int(start + value)
 
+    def _draw_one(self, t, f):
+        """One mask pair, drawn as the reference's ``_mask`` draws it for one spectrogram -> [t0, t1, f0, f1]."""
+        r = [0, 0, 0, 0]
+        if random.random() <= self.thresh:                           # reference "time_masking": last axis = mel bins
+            r[2], r[3] = self._range(self.time_mask_param, f)
+        if random.random() <= self.thresh:                           # reference "frequency_masking": axis 1 = frames
+            r[0], r[1] = self._range(self.freq_mask_param, t)
+        return r
+
     def draw(self, batch, t, f):
         """-> int32 (batch, 4) host tensor {t0, t1, f0, f1}; empty ranges where a mask is not applied."""
-        rng = torch.zeros((batch, 4), dtype=torch.int32)
-        for b in range(batch):
-            if random.random() <= self.thresh:                       # reference "time_masking": last axis = mel bins
-                rng[b, 2], rng[b, 3] = self._range(self.time_mask_param, f)
-            if random.random() <= self.thresh:                       # reference "frequency_masking": axis 1 = frames
-                rng[b, 0], rng[b, 1] = self._range(self.freq_mask_param, t)
-        return rng
+        return torch.tensor([self._draw_one(t, f) for _ in range(batch)], dtype=torch.int32).reshape(batch, 4)
+
+    def draw_groups(self, batch, t, f, groups=2):
+        """-> int32 (batch, groups, 4) host tensor: one independent ``draw`` per sample and feature group, sample after sample
+        and group after group -- the reference masks each element of ``feature_stack = [MEL, IV]`` with its own draw
+        (datasets.py:158-159).  ``draw_groups(b, t, f, 1)[:, 0]`` == ``draw(b, t, f)`` from the same ``random`` state."""
+        return torch.tensor([[self._draw_one(t, f) for _ in range(groups)] for _ in range(batch)],
+                            dtype=torch.int32).reshape(batch, groups, 4)
 
     def augment(self, feat, ranges=None):
         if not self.apply_augment:

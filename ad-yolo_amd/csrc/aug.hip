@@ -29,18 +29,42 @@ __global__ __launch_bounds__(256) void pcm16_to_f32_kernel(const int16_t *__rest
     }
 }
 
-// SpecAug on feat [B][T][F][C]: per sample b zero frames [t0,t1) and mel bins [f0,f1) (ranges in `rng` [B][4], an
-// empty range = no mask); mask value 0 like torchaudio's default
-__global__ __launch_bounds__(256) void mask_ranges_kernel(float *__restrict__ feat, const int *__restrict__ rng, int T,
-                                                          int F, int C4) {
-    const int b = blockIdx.y;
-    const int t0 = rng[b * 4 + 0], t1 = rng[b * 4 + 1], f0 = rng[b * 4 + 2], f1 = rng[b * 4 + 3];
-    if (t0 >= t1 && f0 >= f1) return;
-    float4 *base = reinterpret_cast<float4 *>(feat) + (size_t)b * T * F * C4;
-    const long total = (long)T * F * C4;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const int f = (int)((i / C4) % F), t = (int)(i / ((long)C4 * F));
-        if ((t >= t0 && t < t1) || (f >= f0 && f < f1)) base[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+// SpecAug on feat [B][T][F][C] (C4 = C / 4 float4 quads per pixel), per sample b and channel group g: zero frames [t0,t1) x
+// all bins and bins [f0,f1) x all frames of the group's quads [q0,q1).  ranges int32 [B][G][4] = {t0, t1, f0, f1} (an empty
+// range = no mask; every range clamped to [0,T] / [0,F] here, so no table value writes outside the tensor); mask value 0
+// like torchaudio's default.  Write-only: one float4 store per masked element, nothing else is touched.  Work items of one
+// (b, g) = the frame stripe (nt frames x F bins x nq quads) followed by the bin stripe without the frames already masked
+// ((T - nt) frames x nf bins x nq quads); grid (blocks per group, B * G), grid-stride over the items.
+struct MaskGroups {
+    int q[ADYOLO_MASK_MAX_GROUPS][2];
+};
+
+__global__ __launch_bounds__(256) void mask_groups_kernel(float *__restrict__ feat, const int *__restrict__ rng,
+                                                          MaskGroups groups, int G, int T, int F, int C4) {
+    const int b = blockIdx.y / G, g = blockIdx.y - b * G;
+    const int *r = rng + (size_t)blockIdx.y * 4;
+    const int t0 = min(max(r[0], 0), T), t1 = min(max(r[1], t0), T);
+    const int f0 = min(max(r[2], 0), F), f1 = min(max(r[3], f0), F);
+    const int q0 = groups.q[g][0], nq = groups.q[g][1] - q0;
+    const unsigned nt = t1 - t0, nf = f1 - f0;
+    if ((nt == 0 && nf == 0) || nq <= 0) return;
+    float4 *base = reinterpret_cast<float4 *>(feat) + (size_t)b * T * F * C4 + q0;
+    const unsigned n_t = nt * F * nq, n_all = n_t + (T - nt) * nf * nq;
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < n_all; i += gridDim.x * blockDim.x) {
+        unsigned t, f;
+        const unsigned q = i % nq;
+        if (i < n_t) {
+            const unsigned k = i / nq;
+            f = k % F;
+            t = t0 + k / F;
+        } else {
+            const unsigned k = (i - n_t) / nq;
+            f = f0 + k % nf;
+            t = k / nf;
+            t += t < (unsigned)t0 ? 0u : nt;
+        }
+        base[((size_t)t * F + f) * C4 + q] = z;
     }
 }
 
@@ -98,12 +122,37 @@ extern "C" int adyolo_pcm16_to_f32(const int16_t *pcm, float *out, long n, void 
     return check_launch("pcm16_to_f32");
 }
 
+extern "C" int adyolo_mask_groups(float *feat, const int *ranges, int B, int G, int T, int F, int C, const int *group_quads,
+                                  void *stream) {
+    ADYOLO_REQUIRE(feat && ranges && group_quads && B > 0 && G > 0 && G <= ADYOLO_MASK_MAX_GROUPS && T > 0 && F > 0 && C > 0 &&
+                   C % 4 == 0 && (long)T * F * (C / 4) < (1L << 31) && (long)B * G < 65536, ADYOLO_EINVAL,
+                   "mask_groups: bad arguments");
+    ADYOLO_REQUIRE(((uintptr_t)feat & 15) == 0 && ((uintptr_t)ranges & 3) == 0, ADYOLO_EINVAL, "mask_groups: misaligned buffers");
+    const int C4 = C / 4;
+    MaskGroups groups{};
+    int nq_max = 0;
+    for (int g = 0; g < G; ++g) {
+        const int q0 = group_quads[2 * g], q1 = group_quads[2 * g + 1];
+        ADYOLO_REQUIRE(0 <= q0 && q0 <= q1 && q1 <= C4, ADYOLO_EINVAL, "mask_groups: group %d quads [%d,%d) outside [0,%d]", g, q0,
+                       q1, C4);
+        groups.q[g][0] = q0;
+        groups.q[g][1] = q1;
+        nq_max = q1 - q0 > nq_max ? q1 - q0 : nq_max;
+    }
+    if (nq_max == 0) return 0;
+    // the stripes of one group are at most ~T * 64 float4 at the usual mask widths: ~16 per thread, at most 32 blocks
+    int gx = cdiv((long)T * F * nq_max, 256L * 16);
+    gx = gx < 1 ? 1 : (gx > 32 ? 32 : gx);
+    hipLaunchKernelGGL(mask_groups_kernel, dim3((unsigned)gx, (unsigned)(B * G)), dim3(256), 0, as_stream(stream), feat, ranges,
+                       groups, G, T, F, C4);
+    return check_launch("mask_groups");
+}
+
+// one group over all quads: ranges [B][4] is the table [B][1][4]
 extern "C" int adyolo_mask_ranges(float *feat, const int *ranges, int B, int T, int F, int C, void *stream) {
     ADYOLO_REQUIRE(feat && ranges && B > 0 && T > 0 && F > 0 && C > 0 && C % 4 == 0, ADYOLO_EINVAL, "mask_ranges: bad arguments");
-    long g = ((long)T * F * (C / 4) + 255) / 256;
-    if (g > 1024) g = 1024;
-    hipLaunchKernelGGL(mask_ranges_kernel, dim3((unsigned)g, B), dim3(256), 0, as_stream(stream), feat, ranges, T, F, C / 4);
-    return check_launch("mask_ranges");
+    const int all[2] = {0, C / 4};
+    return adyolo_mask_groups(feat, ranges, B, 1, T, F, C, all, stream);
 }
 
 extern "C" int adyolo_colstats(const float *a, float *partial, double *out, long rows, int cols, void *stream) {

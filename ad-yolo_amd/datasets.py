@@ -246,7 +246,9 @@ class FoaDataset(torch.utils.data.Dataset):
     (``foa_dev/dev-train-chunked_<w>s_<s>s``, ``metadata_dev/...``, ``dev-valid`` / ``dev-test``, ``infer_pth``), the
     same per-epoch file sampling without replacement (``sample_filelist_for_train_iter``, ``get_remaining_file`` /
     ``init_remaining_file_from_list`` for resume) and the same CSV label reader -- but ``__getitem__`` stops before the
-    arithmetic: it returns ``(pcm int16 (T, 4), comb_no, label_rows)``.  Normalisation, rotation of the audio and the
+    arithmetic: it returns ``(pcm int16 (T, 4), comb_no, label_rows)``, and with ``aug_config.spec_augment`` on a training split a
+    4th element, the item's SpecAug table int32 (2, 4) (``SpecAug.draw_groups``: log-mel, then intensity vector; masked on the
+    GPU by ``FeatureExtractor(.., spec_ranges=)`` inside ``TrainStep.step``).  Normalisation, rotation of the audio and the
     features run on the GPU (``AudioStager`` -> ``rotate_audio`` -> ``FeatureExtractor``); the label half of the rotation
     and the label encoding stay here on the host, as in the reference's DataLoader workers.  ``label_rows``: the AD-YOLO row
     list, or for ``seddoa | masked-seddoa | accdoa | adpit`` the dense ``ClasswiseLabelEncoder`` tensor (T', ...)."""
@@ -293,6 +295,8 @@ class FoaDataset(torch.utils.data.Dataset):
                 self.filelist = sorted(self.filelist)[self.rank::self.world]
         self.hop_label = int(dc.get("sr", 24000) * dc.get("label_hop_len_s", 0.1))
         self.rotate = bool(params.get("aug_config", {}).get("rotation_augment", False)) and not is_valid
+        from .augmentations import SpecAug
+        self.specaug = SpecAug(params, is_valid)            # spec_augment on and not a validation split: a mask table per item
         if self.loss_nm == "adyolo":
             self.encoder = YoloLabelEncoder(params)
         elif self.loss_nm in CLASSWISE_LABELS:
@@ -359,11 +363,17 @@ class FoaDataset(torch.utils.data.Dataset):
         if self.rotate:
             comb_no = int(self._random.uniform(0, 16))                                    # augmentations.py:76
             label = rotate_labels(label, comb_no)
+        spec = None
+        if self.specaug.apply_augment:          # datasets.py:158-159: MEL, then IV, each its own draw, right after the rotation
+            from .features import HOP, N_MELS
+            spec = self.specaug.draw_groups(1, pcm.shape[0] // HOP, N_MELS, 2)[0]
         nb_label_frames = pcm.shape[0] // self.hop_label
         if self.loss_nm == "adyolo":
             target = self.encoder.get_yolo_label(label, nb_label_frames)
         else:                                   # dense (T', ...) float32 tensor, datasets.py:210-219
             target = getattr(self.encoder, CLASSWISE_LABELS[self.loss_nm])(label, nb_label_frames)
+        if spec is not None:
+            return np.ascontiguousarray(pcm, dtype=np.int16), comb_no, target, spec
         return np.ascontiguousarray(pcm, dtype=np.int16), comb_no, target
 
 
@@ -374,10 +384,14 @@ CLASSWISE_LABELS = {"seddoa": "get_seddoa_label", "masked-seddoa": "get_seddoa_l
 def audio_collate_fn(batch):
     """list of FoaDataset items -> (pcm int16 (B, T, 4) host tensor, comb_nos list, target).  AD-YOLO: target (M, 7) float32
     rows built exactly like ``collate_fn`` (datasets.py:164-184); class-wise losses: the dense labels stacked to (B, T', ...),
-    like the default collate the reference uses for them."""
-    pcms, combs, labels = zip(*batch)
+    like the default collate the reference uses for them.  Items with SpecAug tables (4-tuples) -> a 4th element, the tables
+    stacked to int32 (B, 2, 4)."""
+    pcms, combs, labels = list(zip(*batch))[:3]
     if isinstance(labels[0], torch.Tensor):
         target = torch.stack(labels, 0)
     else:
         _, target = collate_fn([(np.zeros(1, dtype=np.float32), rows) for rows in labels])
-    return torch.stack([torch.from_numpy(p) for p in pcms], 0), list(combs), target
+    out = torch.stack([torch.from_numpy(p) for p in pcms], 0), list(combs), target
+    if len(batch[0]) == 4:
+        out += (torch.stack([item[3] for item in batch], 0).to(torch.int32),)
+    return out

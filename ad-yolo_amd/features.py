@@ -14,7 +14,7 @@ import math
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ops
 from .ops import _p, _stream
 
 SR = 24000
@@ -94,9 +94,18 @@ class FeatureExtractor:
         self.sc_mean, self.sc_rstd = f32(mean), f32(1.0 / std)
         self.mel_nnz = len(weights)
 
-    def __call__(self, audio, channels_last8=True, chunk_offsets=None, chunk_samples=None, validate_offsets=True):
+    # SpecAug groups of the 8-channel pixel, in float4 quads: log-mel W,Y,Z,X | intensity vector y,z,x + the zero channel 7
+    SPEC_GROUPS = ((0, 1), (1, 2))
+
+    def __call__(self, audio, channels_last8=True, chunk_offsets=None, chunk_samples=None, validate_offsets=True,
+                 spec_ranges=None):
         """-> (B, T, 64, 8) float32 channels-last (8th channel zero) when ``channels_last8`` (what the
         encoder consumes), else (B, 7, T, 64) in the reference's layout (datasets.py:158-160).
+
+        spec_ranges: None, or an int32 (B, 2, 4) tensor (host or device) of SpecAug ranges {t0, t1, f0, f1} per sample for
+        the log-mel group (channels 0-3) and the intensity-vector group (4-6), e.g. ``SpecAug.draw_groups(B, T, 64, 2)``:
+        the normalised features are masked with 0 in the same call (``ops.mask_groups_``, one more launch on the stream),
+        as the reference masks MEL and IV each with its own draw (datasets.py:158-159).  Channels-last only.
 
         chunk_offsets (int64 tensor on the device, sample offsets into the flattened (B * n_samples) audio) with
         chunk_samples: features of the CHUNKS ``audio.view(-1, 4)[off : off + chunk_samples]`` instead (one output row
@@ -122,6 +131,9 @@ class FeatureExtractor:
                     raise _lib.AdyoloHipError("chunk_offsets must satisfy 0 <= off <= %d - chunk_samples (got min %d, max %d)"
                                               % (b * n, lo, hi))
             offs, b, n = chunk_offsets, chunk_offsets.numel(), int(chunk_samples)
+        if spec_ranges is not None and not channels_last8:
+            raise _lib.AdyoloHipError("FeatureExtractor: spec_ranges needs channels_last8=True (the masks are applied to the "
+                                      "channels-last (B, T, 64, 8) features)")
         t = n // HOP
         layout = 1 if channels_last8 else 0
         out = torch.empty((b, t, N_MELS, 8) if channels_last8 else (b, 7, t, N_MELS), dtype=torch.float32,
@@ -132,6 +144,8 @@ class FeatureExtractor:
                   _p(self.ck_start), _p(self.ck_len), _p(self.ck_off), _p(self.mel_w), self.n_chunks, self.mel_nnz,
                   _p(self.sc_mean), _p(self.sc_rstd), _p(out), _p(chan_max), b, n, layout, st)
         _lib.call("adyolo_feat_finish", _p(out), _p(chan_max), _p(self.sc_mean), _p(self.sc_rstd), b, t, layout, st)
+        if spec_ranges is not None:
+            _mask(out, spec_ranges, self.SPEC_GROUPS)
         return out
 
     @staticmethod
@@ -148,9 +162,14 @@ class MicFeatureExtractor:
 
     scaler: {'MEL': {'mean','std'} (1,64,4), 'GCC': {'mean','std'} (1,64,6)} or None.
     ``__call__(audio (B, n, 4))`` -> (B, T, 64, 32) channels-last float32 (features 0-9, zeros above: the 32-channel pixel the
-    Winograd stem convolution consumes) or, with ``channels_last=False``, (B, 10, T, 64)."""
+    Winograd stem convolution consumes) or, with ``channels_last=False``, (B, 10, T, 64).
+
+    ``spec_ranges`` (int32 (B, 2, 4), host or device): SpecAug as in ``FeatureExtractor``, one mask per feature family -- group 0
+    the log-mel channels 0-3, group 1 the GCC-PHAT channels 4-9 (with the zero channels 10-11 of its quads).  The reference has no
+    MIC format; this grouping restates its one-draw-per-feature-family rule (datasets.py:158-159) for the MIC feature set."""
 
     N_FEATURES = 10
+    SPEC_GROUPS = ((0, 1), (1, 3))
 
     def __init__(self, scaler=None, device="cuda:0"):
         mel_scaler = None
@@ -164,9 +183,12 @@ class MicFeatureExtractor:
         self.gcc_mean = torch.tensor(np.asarray(mean, dtype=np.float32), device=dev).contiguous()
         self.gcc_rstd = torch.tensor(np.asarray(1.0 / std, dtype=np.float32), device=dev).contiguous()
 
-    def __call__(self, audio, channels_last=True):
+    def __call__(self, audio, channels_last=True, spec_ranges=None):
         if not audio.is_cuda or audio.dtype != torch.float32 or not audio.is_contiguous():
             raise _lib.AdyoloHipError("MicFeatureExtractor needs contiguous float32 audio (B, n_samples, 4) on the GPU")
+        if spec_ranges is not None and not channels_last:
+            raise _lib.AdyoloHipError("MicFeatureExtractor: spec_ranges needs channels_last=True (the masks are applied to the "
+                                      "channels-last (B, T, 64, 32) features)")
         b, n, ch = audio.shape
         if ch != 4 or n % HOP != 0:
             raise _lib.AdyoloHipError("audio must be (B, n_samples, 4) with n_samples %% 600 == 0")
@@ -176,9 +198,18 @@ class MicFeatureExtractor:
         out[..., :4] = mel8[..., :4]                                  # (plumbing copy; the intensity-vector channels are not used)
         _lib.call("adyolo_feat_gcc_phat", _p(audio), _p(None), _p(self.k1.twiddle), _p(self.gcc_mean), _p(self.gcc_rstd),
                   _p(out), b, n, 32, 4, _stream())
+        if spec_ranges is not None:
+            _mask(out, spec_ranges, self.SPEC_GROUPS)
         if channels_last:
             return out
         return out[..., :10].permute(0, 3, 1, 2).contiguous()
+
+
+def _mask(out, spec_ranges, groups):
+    """SpecAug masks of (B, 2, 4) int32 ranges (host or device) on the channels-last features ``out``, stream-ordered."""
+    if not isinstance(spec_ranges, torch.Tensor) or spec_ranges.dtype != torch.int32:
+        raise _lib.AdyoloHipError("spec_ranges must be an int32 tensor (B, %d, 4)" % len(groups))
+    ops.mask_groups_(out, spec_ranges.to(out.device, non_blocking=True).contiguous(), groups)
 
 
 def load_scaler_npz(path):

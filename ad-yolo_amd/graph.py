@@ -22,6 +22,7 @@ import os
 
 import torch
 
+from . import _lib
 from . import functional as Fn
 from . import ops
 from . import rng as _rng
@@ -60,14 +61,16 @@ def _quiet_collector():
 
 
 class _Entry:
-    __slots__ = ("graph", "audio", "target", "loss", "deltas", "n_replays")
+    __slots__ = ("graph", "audio", "target", "spec", "loss", "deltas", "n_replays")
 
 
 class StepGraphs:
-    """The captured steps of one ``train.TrainStep`` (single process).  ``step(audio, target)``: the first call at a new
-    (audio shape, target capacity) runs eagerly (lazy initialisations, allocator warm-up -- and it IS a real step, nothing
-    is discarded), the second records the graph, every call from then on copies the inputs into the graph's static
-    buffers (skipped when the caller already works in them: ``static_inputs``) and replays it."""
+    """The captured steps of one ``train.TrainStep`` (single process).  ``step(audio, target, spec_ranges=None)``: the first
+    call at a new (audio shape, target capacity[, masked]) runs eagerly (lazy initialisations, allocator warm-up -- and it IS a
+    real step, nothing is discarded), the second records the graph, every call from then on copies the inputs into the graph's
+    static buffers (skipped when the caller already works in them: ``static_inputs``) and replays it.  A step with SpecAug
+    tables (int32 (B, 2, 4)) is recorded with a static device buffer for them, refreshed before every replay like the audio:
+    the masks change from step to step without a new capture."""
 
     def __init__(self, trainer, warm_calls=1):
         self.trainer = trainer
@@ -87,9 +90,10 @@ class StepGraphs:
             return ((target.shape[0] + TARGET_QUANTUM - 1) // TARGET_QUANTUM) * TARGET_QUANTUM
         return None
 
-    def _key(self, audio, target):
+    def _key(self, audio, target, spec=None):
         cap = self._capacity(target)
-        return (tuple(audio.shape), cap if cap is not None else tuple(target.shape))
+        key = (tuple(audio.shape), cap if cap is not None else tuple(target.shape))
+        return key if spec is None else key + ("masked", tuple(spec.shape))
 
     def static_inputs(self, audio_shape, target_like):
         """(audio, target) buffers of the graph for this shape once it exists (else None): a producer may write the next
@@ -98,9 +102,11 @@ class StepGraphs:
         ent = self.entries.get((tuple(audio_shape), cap if cap is not None else tuple(target_like.shape)))
         return (ent.audio, ent.target) if ent is not None else None
 
-    def _load(self, ent, audio, target):
+    def _load(self, ent, audio, target, spec=None):
         if audio.data_ptr() != ent.audio.data_ptr():
             ent.audio.copy_(audio, non_blocking=True)
+        if spec is not None:
+            ent.spec.copy_(spec, non_blocking=True)
         if target.data_ptr() != ent.target.data_ptr():
             if self._capacity(target) is not None:
                 m = target.shape[0]
@@ -111,18 +117,19 @@ class StepGraphs:
                 ent.target.copy_(target, non_blocking=True)
 
     # ---------------------------------------------------------------------------------------- capture / replay
-    def _capture(self, key, audio, target):
+    def _capture(self, key, audio, target, spec=None):
         tr = self.trainer
         dev = audio.device
         ent = _Entry()
         ent.audio = torch.empty_like(audio)
+        ent.spec = None if spec is None else torch.zeros(tuple(spec.shape), dtype=torch.int32, device=dev)
         cap = self._capacity(target)
         if cap is not None:
             ent.target = torch.full((cap, 7), -1.0, dtype=torch.float32, device=dev)
         else:
             ent.target = torch.empty(tuple(target.shape), dtype=torch.float32, device=dev)
         ent.n_replays = 0
-        self._load(ent, audio, target)
+        self._load(ent, audio, target, spec)
         # host-side state the captured step advances: put back afterwards (recording runs nothing), re-applied per replay
         step0 = tr.optimizer.step_count
         tr.optimizer.sync_device_step()
@@ -133,7 +140,7 @@ class StepGraphs:
         graph = torch.cuda.CUDAGraph()
         try:
             with _quiet_collector(), torch.cuda.graph(graph):
-                loss = tr.step_eager(ent.audio, ent.target)
+                loss = tr.step_eager(ent.audio, ent.target, ent.spec)
                 for s in self.streams:
                     ops.counter_add_(s.dev, s.offset - s.capture_base)
         except BaseException:
@@ -183,10 +190,12 @@ class StepGraphs:
         if red is not None and getattr(red, "active", False):
             red.reset()
 
-    def step(self, audio, target):
+    def step(self, audio, target, spec_ranges=None):
         tr = self.trainer
         target = target.to(torch.float32)
-        key = self._key(audio, target)
+        if spec_ranges is not None and spec_ranges.dtype != torch.int32:
+            raise _lib.AdyoloHipError("spec_ranges must be an int32 tensor (B, 2, 4)")
+        key = self._key(audio, target, spec_ranges)
         sw = ops.switch_stamp()
         if sw != self.switches:                # ``ops.reload_thresholds()`` / ADYOLO_CONV_ALGO moved the dispatch: record again
             self.entries.clear()
@@ -194,7 +203,7 @@ class StepGraphs:
             self.switches = sw
         if key in self.eager_only:
             self.eager_steps += 1
-            return tr.step_eager(audio, target)
+            return tr.step_eager(audio, target, spec_ranges)
         ent = self.entries.get(key)
         if ent is None:
             n = self.seen.get(key, 0)
@@ -202,14 +211,14 @@ class StepGraphs:
             if n < self.warm_calls:
                 self.eager_steps += 1
                 before = sum(s.host_draws for s in self.streams)
-                loss = tr.step_eager(audio, target)
+                loss = tr.step_eager(audio, target, spec_ranges)
                 if sum(s.host_draws for s in self.streams) != before:
                     # the step drew host-computed values (the ResNet-Conformer's attention-dropout seeds, a dropout mask
                     # override): it cannot be replayed -- decided here, on the warm-up step, without attempting a capture
                     self._mark_eager(key, "its dropout draws host-computed values")
                 return loss
             try:
-                ent = self._capture(key, audio, target)
+                ent = self._capture(key, audio, target, spec_ranges)
             except Exception as e:                                               # noqa: BLE001
                 # second line of defence.  ``_capture`` has ended the capture and put the RNG offsets / step count back; whatever
                 # else the half-recorded step touched on the host is reset here.  Only an error CAUSED by recording makes the
@@ -221,9 +230,9 @@ class StepGraphs:
                     raise
                 self._mark_eager(key, "%s: %s" % (type(e).__name__, e))
                 self.eager_steps += 1
-                return tr.step_eager(audio, target)
+                return tr.step_eager(audio, target, spec_ranges)
         else:
-            self._load(ent, audio, target)
+            self._load(ent, audio, target, spec_ranges)
             self.entries.move_to_end(key)
         tr.optimizer.sync_device_step()
         for s in self.streams:

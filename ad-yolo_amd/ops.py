@@ -1371,6 +1371,26 @@ def mask_ranges_(feat, ranges):
     return feat
 
 
+def mask_groups_(feat, ranges, group_quads):
+    """In-place SpecAug masking of feat [B][T][F][C] per channel group: ranges int32 [B][G][4] = {t0, t1, f0, f1} on the device
+    (clamped to the tensor by the kernel), group_quads G pairs (q0, q1) of float4 quads (channels 4 q0 .. 4 q1 - 1)."""
+    _chk(feat)
+    if feat.dim() != 4 or feat.shape[3] % 4 != 0:
+        raise _lib.AdyoloHipError("mask_groups_ needs feat (B, T, F, C) with C %% 4 == 0 (got %s)" % (tuple(feat.shape),))
+    b, t, f, c = feat.shape
+    gq = [(int(q0), int(q1)) for q0, q1 in group_quads]
+    g = len(gq)
+    if ranges.dtype != torch.int32 or not ranges.is_contiguous() or ranges.device != feat.device:
+        raise _lib.AdyoloHipError("mask_groups_ needs contiguous int32 ranges on the device of feat")
+    if tuple(ranges.shape) != (b, g, 4):
+        raise _lib.AdyoloHipError("mask_groups_: ranges must be (%d, %d, 4) (got %s)" % (b, g, tuple(ranges.shape)))
+    if not 0 < g <= 8 or any(not 0 <= q0 <= q1 <= c // 4 for q0, q1 in gq):
+        raise _lib.AdyoloHipError("mask_groups_: 1..8 groups of quads within [0, %d] (got %s)" % (c // 4, gq))
+    quads = (ctypes.c_int32 * (2 * g))(*[q for pair in gq for q in pair])
+    _c("adyolo_mask_groups", _p(feat), _p(ranges), b, g, t, f, c, ctypes.cast(quads, ctypes.c_void_p), _stream())
+    return feat
+
+
 def colstats(a2d):
     """[rows][cols] fp32 -> float64 [4][cols]: column sum, sum of squares, max, min."""
     _chk(a2d)

@@ -84,8 +84,10 @@ def get_optimizers(params: dict, flat: FlatParameters):
 class TrainStep:
     """One data-parallel optimisation step on raw audio.
 
-    step(audio (B, n_samples, 4) float32 on the GPU, target (M,7)) -> loss tensor (1,) on the device (no host sync).
-
+    step(audio (B, n_samples, 4) float32 on the GPU, target (M,7), spec_ranges=None) -> loss tensor (1,) on the device (no
+    host sync).  spec_ranges: SpecAug tables int32 (B, 2, 4) (``FoaDataset`` items with ``spec_augment`` on), handed to the
+    feature extractor, which masks its output in the same call; None leaves the step exactly as without SpecAug (the
+    feature callable is then called without the keyword).
 
     graph=True (default: the ADYOLO_GRAPH environment variable, off when unset): the whole step is recorded ONCE per input
     shape in a hipGraph and replayed (``graph.StepGraphs``) -- ~770 kernel launches per step leave the Python / ctypes /
@@ -110,16 +112,19 @@ class TrainStep:
             from .graph import StepGraphs
             self.graphs = StepGraphs(self)
 
-    def step(self, audio, target):
+    def step(self, audio, target, spec_ranges=None):
         if self.graphs is not None:
-            return self.graphs.step(audio, target)
-        return self.step_eager(audio, target)
+            return self.graphs.step(audio, target, spec_ranges)
+        return self.step_eager(audio, target, spec_ranges)
 
-    def step_eager(self, audio, target):
+    def step_eager(self, audio, target, spec_ranges=None):
         self.model.train()
         exact = self.exact and ops.EXACT.enable(self.reducer.group)
         try:
-            feat = self.features(audio, channels_last8=True)
+            if spec_ranges is None:
+                feat = self.features(audio, channels_last8=True)
+            else:
+                feat = self.features(audio, channels_last8=True, spec_ranges=spec_ranges)
             output = self.model(feat, channels_last8=True)
             self.optimizer.zero_grad()
             loss = self.criterion(output, target)
@@ -166,16 +171,17 @@ def train_one_epoch(params: dict, dataloader, model, optimizer, criterion, devic
 
 
 def train_one_epoch_audio(params: dict, dataloader, trainer, stager=None, rotate=True):
-    """The raw-audio epoch: ``dataloader`` yields ``audio_collate_fn`` batches (pcm int16 (B,T,4), comb_nos, target); each is
-    staged to the GPU (int16 over PCIe on a side stream, double-buffered), converted, rotated and handed to
-    ``TrainStep.step`` (features + forward + loss + backward [+ all-reduce] + Adam).  Returns the mean loss with ONE
-    device sync at the end of the epoch (the reference syncs every iteration, train.py:57)."""
+    """The raw-audio epoch: ``dataloader`` yields ``audio_collate_fn`` batches (pcm int16 (B,T,4), comb_nos, target[, SpecAug
+    tables (B,2,4)]); each is staged to the GPU (int16 over PCIe on a side stream, double-buffered), converted, rotated and
+    handed with its tables to ``TrainStep.step`` (features [+ SpecAug masks] + forward + loss + backward [+ all-reduce] +
+    Adam).  Returns the mean loss with ONE device sync at the end of the epoch (the reference syncs every iteration,
+    train.py:57)."""
     from .augmentations import rotate_audio
     from .datasets import AudioStager
     total, n = None, 0
     it = iter(dataloader)
     try:
-        pcm, combs, target = next(it)
+        pcm, combs, target, *spec = next(it)
     except StopIteration:
         return 0.0
     if stager is None:
@@ -183,14 +189,14 @@ def train_one_epoch_audio(params: dict, dataloader, trainer, stager=None, rotate
     stager.stage(pcm)
     while True:
         audio = stager.get()
-        cur_combs, cur_target = combs, target
+        cur_combs, cur_target, cur_spec = combs, target, (spec[0] if spec else None)
         nxt = next(it, None)
         if nxt is not None:                       # the next batch crosses PCIe while this step runs
-            pcm, combs, target = nxt
+            pcm, combs, target, *spec = nxt
             stager.stage(pcm)
         if rotate and any(int(c) != 0 for c in cur_combs):
             audio = rotate_audio(audio, cur_combs)
-        loss = trainer.step(audio, cur_target)
+        loss = trainer.step(audio, cur_target, cur_spec)
         total = loss.detach().reshape(-1)[:1].clone() if total is None else total + loss.detach().reshape(-1)[:1]
         n += 1
         if nxt is None or (params.get("args", {}).get("quick_test") and n == 5):

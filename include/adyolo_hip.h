@@ -477,11 +477,21 @@ int adyolo_classwise_decode(const float *out, float *dec, long n_frames, int C, 
  *   adyolo_pcm16_to_f32: staged WAV samples int16 -> float, x / 32768 + 1e-8 (src/datasets.py:105, src/preprocess.py:104)
  *   adyolo_mask_ranges:  SpecAug (src/utils/augmentations.py:6-33) on feat [B][T][F][C]: per sample zero frames [t0,t1) and
  *                        mel bins [f0,f1); ranges [B][4] int32 = {t0, t1, f0, f1}, an empty range masks nothing
+ *   adyolo_mask_groups:  SpecAug per channel group (the reference masks MEL and IV each with its own draw, src/datasets.py:
+ *                        158-159) on feat [B][T][F][C], C % 4 == 0: per sample b and group g zero frames [t0,t1) x all bins
+ *                        and bins [f0,f1) x all frames of the group's float4 quads [q0,q1) (channels 4 q0 .. 4 q1 - 1).
+ *                        ranges: DEVICE int32 [B][G][4] = {t0, t1, f0, f1}, clamped to [0,T] / [0,F] on the device (any value is
+ *                        safe); group_quads: HOST int32 [G][2] = {q0, q1}, 0 <= q0 <= q1 <= C/4, G <= ADYOLO_MASK_MAX_GROUPS
+ *                        (passed by value: capturable in a hipGraph).  Writes only the masked elements; no sync, no memset.
+ *                        adyolo_mask_ranges is its one-group case (group_quads {0, C/4}).
  *   adyolo_colstats:     per-column sum, sum of squares, max, min of a [rows][cols] fp32 matrix -> out [4][cols] float64
  *                        (train-set scaler statistics, src/preprocess.py:86-130); partial = [4][1024][cols] fp32 scratch
  * ---------------------------------------------------------------------------------------------- */
 int adyolo_pcm16_to_f32(const int16_t *pcm, float *out, long n, void *stream);
 int adyolo_mask_ranges(float *feat, const int32_t *ranges, int B, int T, int F, int C, void *stream);
+#define ADYOLO_MASK_MAX_GROUPS 8
+int adyolo_mask_groups(float *feat, const int32_t *ranges, int B, int G, int T, int F, int C, const int32_t *group_quads,
+                       void *stream);
 int adyolo_colstats(const float *a, float *partial, double *out, long rows, int cols, void *stream);
 
 /* General strided convolution (channels-last) as an implicit GEMM on the fp32 MFMA, no column buffer (replaces nn.Conv2d

@@ -1,0 +1,354 @@
+"""Training from an HBM-resident corpus: the chunked training split held on the device, batches made there.
+
+The host path (``datasets.FoaDataset`` -> ``audio_collate_fn`` -> ``AudioStager``) reads one 20 s int16 WAV and one CSV per item,
+rotates and encodes the labels on the host and stages every batch over PCIe.  Here the split is read once:
+
+* ``load_chunked_split`` (host half, NumPy): the directory ``FoaDataset`` reads (``<data_pth>/<foa_dev|mic_dev>/dev-train-chunked_
+  <w>s_<s>s`` + ``metadata_dev/...``), grouped by recording (``<rec>_chunkNNN``, parsed at the last ``_chunk``).  Each recording
+  is rebuilt as ONE int16 stream -- chunk 001 whole, then the last ``stride`` samples of every later chunk -- so chunk k is
+  ``stream[(k-1) stride : (k-1) stride + window]`` bit for bit, the zero padding of the last window included; and one event
+  table -- chunk 001's rows, then the last ``stride / label_hop`` frames of every later chunk on the recording's frame axis.
+  Every chunk CSV is checked against the table, and (``verify``) chunk audio against the stream.
+* ``DeviceCorpus`` (device half): the streams as one int16 buffer and the events as one float64 table in HBM (0.69 GB per hour
+  of 4-channel 24 kHz audio), ``FoaDataset``'s sampling surface (the same functions), and ``batch(indices)``: the same ``random``
+  draws as ``FoaDataset.__getitem__`` item by item, one small H2D copy of the item table, then ``adyolo_corpus_gather`` (audio,
+  rotated) and ``adyolo_corpus_yolo_labels`` (the AD-YOLO rows into a fixed-capacity target, padding b = -1).  No host sync.
+
+Parity: the same audio bit for bit and the same rows in the same order as the host path iterated in the main process
+(``num_workers=0``); with DataLoader workers the host path's draws happen in per-worker streams.
+"""
+import copy
+import os
+import random
+
+import numpy as np
+import torch
+
+from . import ops
+from .datasets import FoaDataset, YoloLabelEncoder
+
+# event table columns (host): recording frame, class, source, azimuth, elevation
+_EV_COLS = 5
+
+
+def _split_dirs(params, set_type):
+    dc = params["data_config"]
+    if set_type != "train":
+        raise ValueError("load_chunked_split: only the chunked training split is supported (got set_type=%r)" % (set_type,))
+    adir = {"foa": "foa_dev", "mic": "mic_dev"}[str(dc.get("audio_format", "foa")).lower()]     # FoaDataset's rule
+    sub = "dev-train-chunked_{}s_{}s".format(dc["chunk_window_s"], dc["chunk_stride_s"])
+    return os.path.join(dc["data_pth"], adir, sub), os.path.join(dc["data_pth"], "metadata_dev", sub)
+
+
+def _parse_chunk(name):
+    i = name.rfind("_chunk")
+    if i < 0 or not name[i + 6:].isdigit():
+        raise ValueError("load_chunked_split: %s is not named <recording>_chunkNNN" % name)
+    return name[:i], int(name[i + 6:])
+
+
+def _csv_rows(path):
+    """A chunk CSV as ``FoaDataset`` sees it: ``load_csv2dict`` iterated -> [(frame, cls, src, az, el)] (polar rows only)."""
+    if not os.path.exists(path):
+        raise ValueError("load_chunked_split: label file %s is missing" % path)
+    rows = []
+    for frame, events in FoaDataset.load_csv2dict(path).items():
+        for ev in events:
+            if len(ev) != 4:
+                raise ValueError("load_chunked_split: %s has a row that is not [frame, class, source, azimuth, elevation]" % path)
+            rows.append((frame, ev[0], ev[1], ev[2], ev[3]))
+    return rows
+
+
+class HostCorpus:
+    """What ``load_chunked_split`` returns (NumPy, host memory).
+
+    audio      int16 (S, 4): the recordings' streams, each starting on a 16-frame boundary
+    rec_names  recording names; rec_start int64 (R + 1,): first frame of each stream in ``audio`` (end of the last at R)
+    events     float64 (E, 5) [frame on the recording's axis, class, source, azimuth, elevation], recording after recording,
+               frames ascending, file order within a frame; ev_start int64 (R + 1,)
+    chunks     name -> (recording, sample offset into ``audio``, frame offset on the recording's axis)
+    chunk_events  name -> (first event, number of events) of its label window
+    total_filelist  the chunk names in ``os.listdir`` order, exactly as ``FoaDataset`` builds it
+    window, stride (samples), hop_label (samples per label frame), window_frames, max_events (largest event count of a window)
+    """
+
+    def nbytes(self):
+        return int(self.audio.nbytes + self.events.nbytes)
+
+
+def load_chunked_split(params, set_type="train", verify="sample"):
+    """The chunked training split -> ``HostCorpus`` (see the module docstring).  verify: "sample" (default) reads the first,
+    middle and last chunk of every recording in full and compares them with their rebuilt windows, "all" every chunk, "none"
+    nothing; every header is checked (int16, 4 channels, ``window`` samples) and every CSV is compared with the event table.
+    Anything else raises ``ValueError`` naming the file."""
+    from scipy.io import wavfile
+    if verify not in ("sample", "all", "none"):
+        raise ValueError("load_chunked_split: verify must be 'sample', 'all' or 'none' (got %r)" % (verify,))
+    dc = params["data_config"]
+    wav_pth, csv_pth = _split_dirs(params, set_type)
+    sr = int(dc.get("sr", 24000))
+    window, stride = int(round(sr * dc["chunk_window_s"])), int(round(sr * dc["chunk_stride_s"]))
+    hop = int(sr * dc.get("label_hop_len_s", 0.1))                    # FoaDataset.hop_label
+    if stride <= 0 or window < stride or stride % hop:
+        raise ValueError("load_chunked_split: window %d / stride %d samples with a label hop of %d" % (window, stride, hop))
+    window_frames, stride_frames = window // hop, stride // hop
+
+    total_filelist = [i.replace(".wav", "") for i in os.listdir(wav_pth)]          # FoaDataset.total_filelist
+    groups = {}
+    for name in total_filelist:
+        rec, k = _parse_chunk(name)
+        groups.setdefault(rec, {})[k] = name
+    rec_names = sorted(groups)
+    for rec in rec_names:
+        ks = sorted(groups[rec])
+        if ks != list(range(1, len(ks) + 1)):
+            raise ValueError("load_chunked_split: recording %s has chunks %s (expected 1..%d without gaps)" % (rec, ks, len(ks)))
+
+    def wav_of(name):
+        path = os.path.join(wav_pth, name + ".wav")
+        _, data = wavfile.read(path, mmap=True)
+        if data.dtype != np.int16 or data.ndim != 2 or data.shape != (window, 4):
+            raise ValueError("load_chunked_split: %s holds %s %s, expected int16 (%d, 4)"
+                             % (path, data.dtype, tuple(data.shape), window))
+        return path, data
+
+    # stream layout: each recording starts on a 16-frame boundary (aligned 16-byte loads in the gather)
+    lengths = [window + (len(groups[r]) - 1) * stride for r in rec_names]
+    rec_start = np.zeros(len(rec_names) + 1, dtype=np.int64)
+    pos = 0
+    for i, n in enumerate(lengths):
+        rec_start[i] = pos
+        pos += (n + 15) // 16 * 16
+    rec_start[-1] = pos
+    audio = np.zeros((max(pos, 16), 4), dtype=np.int16)
+    ev_parts, ev_start = [], [0]
+    chunks, chunk_events = {}, {}
+    max_events = 0
+    for r, rec in enumerate(rec_names):
+        names = groups[rec]
+        nk = len(names)
+        s0 = int(rec_start[r])
+        # audio: chunk 1 whole, the last `stride` samples of every later chunk
+        for k in range(1, nk + 1):
+            path, data = wav_of(names[k])
+            if k == 1:
+                audio[s0:s0 + window] = data
+            else:
+                lo = s0 + window + (k - 2) * stride
+                audio[lo:lo + stride] = data[window - stride:]
+            del data
+        checks = range(1, nk + 1) if verify == "all" else (sorted({1, (nk + 1) // 2, nk}) if verify == "sample" else ())
+        for k in checks:
+            path, data = wav_of(names[k])
+            lo = s0 + (k - 1) * stride
+            if not np.array_equal(np.asarray(data), audio[lo:lo + window]):
+                raise ValueError("load_chunked_split: %s differs from the window rebuilt from its neighbours (overlapping chunks "
+                                 "of %s disagree)" % (path, rec))
+            del data
+        # labels: chunk 1's rows, then the last stride_frames frames of every later chunk, on the recording's frame axis
+        csv = {k: _csv_rows(os.path.join(csv_pth, names[k] + ".csv")) for k in range(1, nk + 1)}
+        rows = []
+        for k in range(1, nk + 1):
+            f_off = (k - 1) * stride_frames
+            keep = [e for e in csv[k] if k == 1 or e[0] >= window_frames - stride_frames]
+            keep.sort(key=lambda e: e[0])                                   # stable: file order within a frame
+            rows += [(e[0] + f_off,) + tuple(e[1:]) for e in keep]
+        ev = np.asarray(rows, dtype=np.float64).reshape(-1, _EV_COLS)
+        frames = ev[:, 0]
+        for k in range(1, nk + 1):
+            f_off = (k - 1) * stride_frames
+            lo, hi = np.searchsorted(frames, f_off, "left"), np.searchsorted(frames, f_off + window_frames, "left")
+            want = [(float(e[0] - f_off),) + tuple(float(v) for v in e[1:]) for e in ev[lo:hi].tolist()]
+            got = [tuple(float(v) for v in e) for e in csv[k]]
+            if got != want:
+                raise ValueError("load_chunked_split: %s disagrees with the event table of %s rebuilt from its chunks (rows "
+                                 "outside [0, %d) frames, out of frame order, or overlaps that differ)"
+                                 % (os.path.join(csv_pth, names[k] + ".csv"), rec, window_frames))
+            chunks[names[k]] = (r, s0 + (k - 1) * stride, f_off)
+            chunk_events[names[k]] = (ev_start[-1] + int(lo), int(hi - lo))
+            max_events = max(max_events, int(hi - lo))
+        ev_parts.append(ev)
+        ev_start.append(ev_start[-1] + ev.shape[0])
+
+    hc = HostCorpus()
+    hc.wav_pth, hc.csv_pth, hc.set_type = wav_pth, csv_pth, set_type
+    hc.audio = audio
+    hc.rec_names, hc.rec_start = rec_names, rec_start
+    hc.events = np.concatenate(ev_parts, 0) if ev_parts else np.zeros((0, _EV_COLS))
+    hc.ev_start = np.asarray(ev_start, dtype=np.int64)
+    hc.chunks, hc.chunk_events = chunks, chunk_events
+    hc.total_filelist = total_filelist
+    hc.window, hc.stride, hc.hop_label = window, stride, hop
+    hc.window_frames, hc.max_events = window_frames, max_events
+    return hc
+
+
+def max_cells_per_event(encoder):
+    """The largest number of grid cells one event can occupy (``YoloLabelEncoder.encode_events``): the cells are the product
+    of an azimuth and an elevation set, each piecewise constant between the cell bounds -- evaluated on every bound and every
+    midpoint between neighbouring bounds."""
+    def most(points, count):
+        p = np.unique(np.asarray(points, dtype=np.float64))
+        cand = np.concatenate([p, (p[1:] + p[:-1]) * 0.5])
+        return max(int(count(c)) for c in cand)
+    az_pts = [v for b in (encoder.az_lb, encoder.az_ub) for x in b for v in (x, x - 360.0, x + 360.0) if -180.0 <= v <= 180.0]
+    el_pts = [v for b in (encoder.el_lb, encoder.el_ub) for v in b] + [-90.0, 90.0]
+
+    def n_az(a):
+        a = -180.0 if a == 180.0 else a
+        return (((encoder.az_lb <= a) & (a < encoder.az_ub)) | (a + 360 < encoder.az_ub) | (encoder.az_lb < a - 360)).sum()
+
+    def n_el(e):
+        return ((encoder.el_lb <= e) & (e < encoder.el_ub)).sum()
+    return most(az_pts + [-180.0, 180.0], n_az) * most(el_pts, n_el)
+
+
+def _rank_world(rank, world):
+    """FoaDataset's default: torch.distributed if initialised, else RANK / WORLD_SIZE, else 0 / 1."""
+    if world is None:
+        import torch.distributed as tdist
+        if tdist.is_available() and tdist.is_initialized():
+            rank, world = tdist.get_rank(), tdist.get_world_size()
+        else:
+            rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
+    return int(rank or 0), int(world)
+
+
+class DeviceCorpus:
+    """A ``HostCorpus`` in HBM with ``FoaDataset``'s sampling surface and a device-side ``batch``.
+
+        corpus = DeviceCorpus(load_chunked_split(params), params, "cuda:0")
+        audio, target, spec = corpus.batch(range(16))    # (16, n, 4) f32, (cap, 7) f32, (16, 2, 4) int32 or None: all on the device
+
+    ``cap`` (the target rows) is fixed here: batch_size x (largest event count of a window) x (largest cell count of an event),
+    rounded up to ``graph.TARGET_QUANTUM`` -- one input shape, one recorded graph.  More rows than that in a batch (a smaller
+    ``cap`` forced by the caller) set the status word; ``check()`` raises then.  AD-YOLO labels only."""
+
+    # the same functions as the host dataset: checkpoints (remaining_file) and the rank shards interchange with it
+    sample_filelist_for_train_iter = FoaDataset.sample_filelist_for_train_iter
+    init_remaining_file_from_list = FoaDataset.init_remaining_file_from_list
+    get_remaining_file = FoaDataset.get_remaining_file
+    get_filelist = FoaDataset.get_filelist
+    __len__ = FoaDataset.__len__
+
+    def __init__(self, host_corpus, params, device="cuda:0", rank=None, world=None, cap=None):
+        from . import graph
+        from .augmentations import COMBINATIONS, SpecAug
+        self.loss_nm = params["args"]["loss"]
+        if self.loss_nm != "adyolo":
+            raise NotImplementedError("DeviceCorpus: loss %s -- only the AD-YOLO label encoding runs on the device; the class-wise "
+                                      "losses need FoaDataset" % self.loss_nm)
+        self.host = hc = host_corpus
+        self.device = torch.device(device)
+        self._copy, self._os, self._random = copy, os, random
+        self.rank, self.world = _rank_world(rank, world)
+        self.is_valid, self.is_infer, self.set_type = False, False, hc.set_type
+        self.wav_pth, self.csv_pth = hc.wav_pth, hc.csv_pth
+        self.hop_label = hc.hop_label
+        self.rotate = bool(params.get("aug_config", {}).get("rotation_augment", False))
+        self.specaug = SpecAug(params, False)
+        self.encoder = YoloLabelEncoder(params)
+        self.batch_size = int(params["train_config"]["batch_size"])
+        self.n_samples, self.n_label_frames = hc.window, hc.window // hc.hop_label
+        self.max_events = hc.max_events
+        self.cells = max_cells_per_event(self.encoder)
+        if cap is None:
+            need = max(1, self.batch_size * self.max_events * self.cells)
+            cap = (need + graph.TARGET_QUANTUM - 1) // graph.TARGET_QUANTUM * graph.TARGET_QUANTUM
+        self.cap = int(cap)
+        # the corpus in HBM
+        self.pcm = torch.from_numpy(hc.audio).to(self.device)
+        ev = hc.events[:, [0, 1, 3, 4]] if hc.events.shape[0] else np.zeros((1, 4))
+        self.events = torch.from_numpy(np.ascontiguousarray(ev, dtype=np.float64)).to(self.device)
+        self.n_events = int(hc.events.shape[0])
+        enc = self.encoder
+        self.bounds = torch.from_numpy(np.concatenate([enc.az_lb, enc.az_ub, enc.el_lb, enc.el_ub]).astype(np.float64)).to(self.device)
+        self.grid = (len(enc.az_lb), len(enc.el_lb))
+        self.rot = ops.corpus_rot_table(COMBINATIONS)
+        self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.rows = None                 # int32 word on the device: the row count of the last batch
+        self._pinned, self._copied, self._slot = {}, [None, None], 0
+        # sampling: FoaDataset.__init__ for a training split
+        self.total_filelist = list(hc.total_filelist)
+        self.remaining_file = copy.deepcopy(self.total_filelist)
+        self.nb_samples = self.batch_size * params["train_config"]["nb_iters"] * self.world
+        self.filelist = []
+        self.sample_filelist_for_train_iter()
+
+    def nbytes(self):
+        return int(self.pcm.numel() * 2 + self.events.numel() * 8)
+
+    # ---------------------------------------------------------------------------------------------------------- batches
+    def draw(self, indices):
+        """The host half of a batch: ``FoaDataset.__getitem__``'s ``random`` draws item by item (rotation, then SpecAug) and the
+        item table -> (items int64 (B, 8), spec int32 (B, 2, 4) or None), host arrays."""
+        from .features import HOP, N_MELS
+        names = [self.filelist[i] for i in indices]
+        b = len(names)
+        items = np.zeros((b, ops.CORPUS_ITEM_WORDS), dtype=np.int64)
+        spec = np.zeros((b, 2, 4), dtype=np.int32) if self.specaug.apply_augment else None
+        for j, name in enumerate(names):
+            rec, off, f_off = self.host.chunks[name]
+            ev_lo, ev_n = self.host.chunk_events[name]
+            comb = -1
+            if self.rotate:
+                comb = int(self._random.uniform(0, 16))                       # augmentations.py:76, as in __getitem__
+            if spec is not None:
+                spec[j] = self.specaug.draw_groups(1, self.n_samples // HOP, N_MELS, 2)[0].numpy()
+            items[j] = (off, f_off, ev_lo, ev_n, comb, rec, 0, 0)
+        return items, spec
+
+    def launch(self, drawn, audio_out=None, target_out=None):
+        """The device half: one H2D copy of the item table (+ SpecAug tables), the gather and the label kernels.
+        -> (audio (B, n, 4) f32, target (cap, 7) f32, spec (B, 2, 4) int32 or None) on the device; no host sync."""
+        items, spec = drawn
+        b = items.shape[0]
+        n_i = b * ops.CORPUS_ITEM_WORDS
+        n_words = n_i + (b * 4 if spec is not None else 0)              # 8 int32 of SpecAug per item = 4 int64 words
+        slot = self._slot
+        self._slot ^= 1
+        key = (slot, n_words)
+        host = self._pinned.get(key)
+        if host is None:
+            host = self._pinned[key] = torch.empty(n_words, dtype=torch.int64).pin_memory()
+        if self._copied[slot] is not None:
+            self._copied[slot].synchronize()          # the copy out of this page-locked buffer two batches ago has landed
+        hv = host.numpy()
+        hv[:n_i] = items.reshape(-1)
+        if spec is not None:
+            hv[n_i:].view(np.int32)[:] = spec.reshape(-1)
+        dev = torch.empty(n_words, dtype=torch.int64, device=self.device)
+        dev.copy_(host, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.device))
+        self._copied[slot] = ev
+        dev_items = dev[:n_i].view(b, ops.CORPUS_ITEM_WORDS)
+        dev_spec = dev[n_i:].view(torch.int32).view(b, 2, 4) if spec is not None else None
+        audio = audio_out if audio_out is not None else \
+            torch.empty((b, self.n_samples, 4), dtype=torch.float32, device=self.device)
+        target = target_out if target_out is not None else torch.empty((self.cap, 7), dtype=torch.float32, device=self.device)
+        if tuple(audio.shape) != (b, self.n_samples, 4) or tuple(target.shape) != (self.cap, 7):
+            raise ValueError("DeviceCorpus.launch: output buffers %s / %s, expected (%d, %d, 4) / (%d, 7)"
+                             % (tuple(audio.shape), tuple(target.shape), b, self.n_samples, self.cap))
+        ws = torch.empty(max(1, ops.corpus_labels_workspace_words(b, self.max_events)), dtype=torch.int32, device=self.device)
+        self.rows = torch.empty(1, dtype=torch.int32, device=self.device)
+        ops.corpus_gather(self.pcm, dev_items, self.rot, audio, self.status)
+        ops.corpus_yolo_labels(self.events, dev_items, self.max_events, self.n_label_frames, self.bounds, self.grid, self.rot, ws,
+                               target, self.rows, self.status)
+        return audio, target, dev_spec
+
+    def batch(self, indices, audio_out=None, target_out=None):
+        """Items ``indices`` of ``get_filelist()`` -> (audio (B, n, 4) f32, target (cap, 7) f32, spec (B, 2, 4) int32 or None), on
+        the device, with no host synchronisation.  audio_out / target_out: write into these buffers (a recorded step's)."""
+        return self.launch(self.draw(indices), audio_out, target_out)
+
+    def reset_status(self):
+        self.status.zero_()
+
+    def check(self, word=None):
+        """Raise if a batch overflowed its capacity or had an item outside the corpus (reads the status word: synchronises,
+        unless the caller passes the word it already read)."""
+        if word is None:
+            word = int(ops.to_host(self.status)[0])
+        ops.corpus_status_check(word)

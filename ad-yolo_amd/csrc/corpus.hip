@@ -1,0 +1,271 @@
+// Training batches from an HBM-resident corpus (ad-yolo_amd/corpus.py DeviceCorpus): the chunk gather of the audio and the
+// AD-YOLO label encoding, both from a per-batch item table, so that no training chunk crosses PCIe.  What they replace is the
+// host half of FoaDataset.__getitem__ + audio_collate_fn (reference src/datasets.py:93-184: the WAV read, ``audio / 32768 +
+// 1e-8``, RotationAug, get_yolo_label, collate_fn) followed by AudioStager, adyolo_pcm16_to_f32 and adyolo_foa_rotate.
+//
+//   corpus_gather_kernel     one pass int16 window -> float32 ``x / 32768 + 1e-8``, FOA channels rotated; 16-byte loads of
+//                            two int16 frames, two 16-byte stores (8-byte loads when the window starts on an odd frame)
+//   corpus_count_scan_kernel one workgroup: rows per (item, event) lane, exclusive scan, the total and the overflow bit
+//   corpus_rows_kernel       the rows [b, t, gi, gj, cls, U, V] at their scanned offsets, b = -1 in the rest of the capacity
+// The label arithmetic is done in double, as the host does it (augmentations.rotate_labels on Python floats,
+// datasets.YoloLabelEncoder.encode_events in float64); only the written row is rounded to float32.
+#include "common.hpp"
+
+namespace adyolo {
+
+struct CorpusRot {                     // ADYOLO_CORPUS_ROT_WORDS floats per combination, passed by value (capturable)
+    float c[16][ADYOLO_CORPUS_ROT_WORDS];
+};
+
+__device__ __forceinline__ float4 pcm_rot(int lo, int hi, float sy, float sz, float sx, bool swap) {
+    // the arithmetic of pcm16_to_f32_kernel (csrc/aug.hip) then foa_rotate_kernel (csrc/optim.hip), element for element
+    const float w = (float)(short)(lo & 0xffff) / 32768.0f + 1e-8f;
+    const float y = (float)(short)(lo >> 16) / 32768.0f + 1e-8f;
+    const float z = (float)(short)(hi & 0xffff) / 32768.0f + 1e-8f;
+    const float x = (float)(short)(hi >> 16) / 32768.0f + 1e-8f;
+    const float yy = y * sy, zz = z * sz, xx = x * sx;
+    return swap ? make_float4(w, xx, zz, yy) : make_float4(w, yy, zz, xx);
+}
+
+// grid (blocks per item, B).  An item whose offset or combination is outside the corpus gets zeros and sets status bit 2.
+__global__ __launch_bounds__(256) void corpus_gather_kernel(const int16_t *__restrict__ pcm, long n_total,
+                                                            const int64_t *__restrict__ items, long n, CorpusRot rot,
+                                                            float4 *__restrict__ out, int *__restrict__ status) {
+    const int b = blockIdx.y;
+    const int64_t off = items[(size_t)b * ADYOLO_CORPUS_ITEM_WORDS + 0];
+    const int64_t comb = items[(size_t)b * ADYOLO_CORPUS_ITEM_WORDS + 4];
+    float4 *dst = out + (size_t)b * n;
+    const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, nth = (long)gridDim.x * blockDim.x;
+    if (off < 0 || off > n_total - n || comb >= 16) {
+        if (tid == 0 && status) atomicOr(status, ADYOLO_CORPUS_BAD_ITEM);
+        for (long i = tid; i < n; i += nth) dst[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        return;
+    }
+    float sy = 1.f, sz = 1.f, sx = 1.f;
+    bool swap = false;
+    if (comb >= 0) {
+        sy = rot.c[comb][0]; sz = rot.c[comb][1]; sx = rot.c[comb][2]; swap = rot.c[comb][3] != 0.f;
+    }
+    const int16_t *src = pcm + (size_t)off * 4;
+    if ((off & 1) == 0) {                                   // two frames per 16-byte load
+        const long n2 = n >> 1;
+        const int4 *s4 = reinterpret_cast<const int4 *>(src);
+        for (long i = tid; i < n2; i += nth) {
+            const int4 v = s4[i];
+            dst[2 * i] = pcm_rot(v.x, v.y, sy, sz, sx, swap);
+            dst[2 * i + 1] = pcm_rot(v.z, v.w, sy, sz, sx, swap);
+        }
+        if ((n & 1) && tid == 0) {
+            const int2 v = reinterpret_cast<const int2 *>(src)[n - 1];
+            dst[n - 1] = pcm_rot(v.x, v.y, sy, sz, sx, swap);
+        }
+    } else {
+        const int2 *s2 = reinterpret_cast<const int2 *>(src);
+        for (long i = tid; i < n; i += nth) {
+            const int2 v = s2[i];
+            dst[i] = pcm_rot(v.x, v.y, sy, sz, sx, swap);
+        }
+    }
+}
+
+struct CorpusLabelGeom {
+    int B, max_events, n_label_frames, Gaz, Gel;
+    long n_events, cap;
+};
+
+// The label window of lane (b, e): event ev_lo + e of the item's range, its frame relative to the window, the rotated angles
+// and its az / el cell masks.  Returns the number of rows it produces (0: no event, or its frame is past the label frames).
+__device__ int corpus_event(const double *__restrict__ events, const int64_t *__restrict__ items,
+                            const double *__restrict__ bounds, const CorpusRot &rot, const CorpusLabelGeom &g, long lane,
+                            int &frame, int &cls, double &az, double &el, unsigned long long &az_bits,
+                            unsigned long long &el_bits, bool &bad) {
+    const int b = (int)(lane / g.max_events), e = (int)(lane % g.max_events);
+    const int64_t *it = items + (size_t)b * ADYOLO_CORPUS_ITEM_WORDS;
+    const int64_t frame_off = it[1], ev_lo = it[2], ev_n = it[3], comb = it[4];
+    bad = ev_lo < 0 || ev_n < 0 || ev_n > g.max_events || ev_lo > g.n_events - ev_n || comb >= 16;
+    if (bad || e >= ev_n) return 0;
+    const double *ev = events + (size_t)(ev_lo + e) * 4;
+    const int64_t fr = (int64_t)ev[0] - frame_off;
+    if (fr < 0 || fr >= g.n_label_frames) return 0;              // get_yolo_label: frame_idx < nb_label_frames
+    frame = (int)fr;
+    cls = (int)ev[1];
+    double a = ev[2], v = ev[3];
+    if (comb >= 0) {                                              // augmentations.rotate_labels
+#pragma clang fp contract(off)
+        a = a * (double)rot.c[comb][4] + (double)rot.c[comb][5];
+        if (a < -180.0)
+            a += 360.0;
+        else if (a > 180.0)
+            a -= 360.0;
+        v = v * (double)rot.c[comb][6];
+    }
+    if (a == 180.0) a = -180.0;                                  // YoloLabelEncoder.encode_events
+    const double *az_lb = bounds, *az_ub = bounds + g.Gaz, *el_lb = bounds + 2 * g.Gaz, *el_ub = el_lb + g.Gel;
+    az_bits = 0ull;
+    el_bits = 0ull;
+    int naz = 0, nel = 0;
+    for (int i = 0; i < g.Gaz; ++i) {
+        const bool ok = (az_lb[i] <= a && a < az_ub[i]) || (a + 360.0 < az_ub[i]) || (az_lb[i] < a - 360.0);
+        if (ok) { az_bits |= 1ull << i; ++naz; }
+    }
+    for (int j = 0; j < g.Gel; ++j) {
+        const bool ok = el_lb[j] <= v && v < el_ub[j];
+        if (ok) { el_bits |= 1ull << j; ++nel; }
+    }
+    az = a;
+    el = v;
+    return naz * nel;
+}
+
+constexpr int CORPUS_SCAN_THREADS = 1024;
+
+// one workgroup: ws[lane] = exclusive offset of lane's rows; count[0] = total rows; status |= overflow / bad item
+__global__ __launch_bounds__(CORPUS_SCAN_THREADS) void corpus_count_scan_kernel(const double *__restrict__ events,
+                                                                               const int64_t *__restrict__ items,
+                                                                               const double *__restrict__ bounds, CorpusRot rot,
+                                                                               CorpusLabelGeom g, int *__restrict__ ws,
+                                                                               int *__restrict__ count,
+                                                                               int *__restrict__ status) {
+    __shared__ int part[CORPUS_SCAN_THREADS];
+    __shared__ int any_bad;
+    const int t = threadIdx.x;
+    if (t == 0) any_bad = 0;
+    __syncthreads();
+    const long lanes = (long)g.B * g.max_events;
+    const long chunk = (lanes + CORPUS_SCAN_THREADS - 1) / CORPUS_SCAN_THREADS;
+    const long s0 = t * chunk, s1 = s0 + chunk < lanes ? s0 + chunk : lanes;
+    int sum = 0;
+    bool bad_here = false;
+    for (long s = s0; s < s1; ++s) {
+        int frame, cls;
+        double az, el;
+        unsigned long long ab, eb;
+        bool bad;
+        const int c = corpus_event(events, items, bounds, rot, g, s, frame, cls, az, el, ab, eb, bad);
+        bad_here |= bad;
+        ws[s] = c;
+        sum += c;
+    }
+    if (bad_here) any_bad = 1;
+    part[t] = sum;
+    __syncthreads();
+    for (int o = 1; o < CORPUS_SCAN_THREADS; o <<= 1) {          // inclusive Hillis-Steele scan of the chunk sums
+        const int v = t >= o ? part[t - o] : 0;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    int run = part[t] - sum;
+    for (long s = s0; s < s1; ++s) {
+        const int c = ws[s];
+        ws[s] = run;
+        run += c;
+    }
+    if (t == CORPUS_SCAN_THREADS - 1) {
+        const int total = part[t];
+        count[0] = total;
+        int bits = any_bad ? ADYOLO_CORPUS_BAD_ITEM : 0;
+        if ((long)total > g.cap) bits |= ADYOLO_CORPUS_OVERFLOW;
+        if (bits && status) atomicOr(status, bits);
+    }
+}
+
+// grid-stride over the lanes (rows of each event, cells in (gi, gj) order) and over the capacity (b = -1 past the total)
+__global__ __launch_bounds__(256) void corpus_rows_kernel(const double *__restrict__ events, const int64_t *__restrict__ items,
+                                                          const double *__restrict__ bounds, CorpusRot rot, CorpusLabelGeom g,
+                                                          const int *__restrict__ ws, const int *__restrict__ count,
+                                                          float *__restrict__ target) {
+    const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, nth = (long)gridDim.x * blockDim.x;
+    const long lanes = (long)g.B * g.max_events;
+    for (long s = tid; s < lanes; s += nth) {
+        int frame, cls;
+        double az, el;
+        unsigned long long ab, eb;
+        bool bad;
+        const int c = corpus_event(events, items, bounds, rot, g, s, frame, cls, az, el, ab, eb, bad);
+        if (c == 0) continue;
+        long r = ws[s];
+        const float fb = (float)(s / g.max_events), ft = (float)frame, fc = (float)cls, fu = (float)az, fv = (float)el;
+        for (int i = 0; i < g.Gaz; ++i) {
+            if (!((ab >> i) & 1ull)) continue;
+            for (int j = 0; j < g.Gel; ++j) {
+                if (!((eb >> j) & 1ull)) continue;
+                if (r < g.cap) {
+                    float *row = target + (size_t)r * 7;
+                    row[0] = fb; row[1] = ft; row[2] = (float)i; row[3] = (float)j; row[4] = fc; row[5] = fu; row[6] = fv;
+                }
+                ++r;
+            }
+        }
+    }
+    const long total = count[0];
+    for (long r = total + tid; r < g.cap; r += nth) {
+        float *row = target + (size_t)r * 7;
+        row[0] = -1.f; row[1] = 0.f; row[2] = 0.f; row[3] = 0.f; row[4] = 0.f; row[5] = 0.f; row[6] = 0.f;
+    }
+}
+
+static int corpus_rot(const float *rot_host, CorpusRot &rot) {
+    if (!rot_host) return ADYOLO_EINVAL;
+    for (int c = 0; c < 16; ++c)
+        for (int k = 0; k < ADYOLO_CORPUS_ROT_WORDS; ++k) rot.c[c][k] = rot_host[c * ADYOLO_CORPUS_ROT_WORDS + k];
+    return 0;
+}
+
+}  // namespace adyolo
+
+using namespace adyolo;
+
+extern "C" int adyolo_corpus_gather(const int16_t *pcm, long n_total, const int64_t *items, int B, long n,
+                                    const float *rot_host, float *audio, int *status, void *stream) {
+    ADYOLO_REQUIRE(pcm && items && audio && rot_host, ADYOLO_EINVAL, "corpus_gather: null pointer");
+    ADYOLO_REQUIRE(B > 0 && B < 65536 && n > 0 && n_total >= n, ADYOLO_EINVAL,
+                   "corpus_gather: bad shape B=%d n=%ld n_total=%ld", B, n, n_total);
+    ADYOLO_REQUIRE(((uintptr_t)pcm & 15) == 0 && ((uintptr_t)audio & 15) == 0 && ((uintptr_t)items & 7) == 0, ADYOLO_EINVAL,
+                   "corpus_gather: misaligned buffers (pcm / audio 16 bytes, items 8 bytes)");
+    CorpusRot rot;
+    corpus_rot(rot_host, rot);
+    // ~16 frames per thread: at 20 s (480000 frames) 118 blocks per item, 1888 for a batch of 16
+    int gx = cdiv(n, 256L * 16);
+    gx = gx < 1 ? 1 : (gx > 4096 ? 4096 : gx);
+    hipLaunchKernelGGL(corpus_gather_kernel, dim3((unsigned)gx, (unsigned)B), dim3(256), 0, as_stream(stream), pcm, n_total,
+                       items, n, rot, (float4 *)audio, status);
+    return check_launch("corpus_gather");
+}
+
+extern "C" long adyolo_corpus_yolo_labels_workspace_words(int B, int max_events) {
+    if (B <= 0 || max_events < 0) return -1;
+    return (long)B * (max_events > 0 ? max_events : 1);
+}
+
+extern "C" int adyolo_corpus_yolo_labels(const double *events, long n_events, const int64_t *items, int B, int max_events,
+                                         int n_label_frames, const double *grid_bounds, int Gaz, int Gel,
+                                         const float *rot_host, int *ws, float *target, long cap, int *count, int *status,
+                                         void *stream) {
+    ADYOLO_REQUIRE(events && items && grid_bounds && rot_host && ws && target && count && status, ADYOLO_EINVAL,
+                   "corpus_yolo_labels: null pointer");
+    ADYOLO_REQUIRE(B > 0 && max_events >= 0 && n_events >= 0 && n_label_frames > 0 && cap > 0 && cap < (1L << 31) &&
+                       (long)B * max_events < (1L << 31),
+                   ADYOLO_EINVAL, "corpus_yolo_labels: bad shape B=%d max_events=%d cap=%ld", B, max_events, cap);
+    ADYOLO_REQUIRE(Gaz > 0 && Gaz <= 64 && Gel > 0 && Gel <= 64, ADYOLO_ENOSUP,
+                   "corpus_yolo_labels: grid %d x %d (at most 64 x 64 cells)", Gaz, Gel);
+    ADYOLO_REQUIRE(((uintptr_t)events & 7) == 0 && ((uintptr_t)items & 7) == 0 && ((uintptr_t)grid_bounds & 7) == 0 &&
+                       ((uintptr_t)target & 3) == 0,
+                   ADYOLO_EINVAL, "corpus_yolo_labels: misaligned buffers");
+    CorpusRot rot;
+    corpus_rot(rot_host, rot);
+    CorpusLabelGeom g;
+    g.B = B; g.max_events = max_events; g.n_label_frames = n_label_frames; g.Gaz = Gaz; g.Gel = Gel;
+    g.n_events = n_events; g.cap = cap;
+    hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(corpus_count_scan_kernel, dim3(1), dim3(CORPUS_SCAN_THREADS), 0, st, events, items, grid_bounds, rot, g,
+                       ws, count, status);
+    int rc = check_launch("corpus_count_scan");
+    if (rc) return rc;
+    long work = cap > (long)B * max_events ? cap : (long)B * max_events;
+    int gx = cdiv(work, 256L * 4);
+    gx = gx < 1 ? 1 : (gx > 1024 ? 1024 : gx);
+    hipLaunchKernelGGL(corpus_rows_kernel, dim3((unsigned)gx), dim3(256), 0, st, events, items, grid_bounds, rot, g, ws, count,
+                       target);
+    return check_launch("corpus_rows");
+}

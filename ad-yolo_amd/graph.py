@@ -95,11 +95,15 @@ class StepGraphs:
         key = (tuple(audio.shape), cap if cap is not None else tuple(target.shape))
         return key if spec is None else key + ("masked", tuple(spec.shape))
 
-    def static_inputs(self, audio_shape, target_like):
+    def static_inputs(self, audio_shape, target_like, spec_shape=None):
         """(audio, target) buffers of the graph for this shape once it exists (else None): a producer may write the next
-        batch straight into them and pass them to ``step`` (no copy then)."""
+        batch straight into them and pass them to ``step`` (no copy then).  spec_shape: the graph recorded with SpecAug
+        tables of that shape."""
         cap = self._capacity(target_like)
-        ent = self.entries.get((tuple(audio_shape), cap if cap is not None else tuple(target_like.shape)))
+        key = (tuple(audio_shape), cap if cap is not None else tuple(target_like.shape))
+        if spec_shape is not None:
+            key += ("masked", tuple(spec_shape))
+        ent = self.entries.get(key)
         return (ent.audio, ent.target) if ent is not None else None
 
     def _load(self, ent, audio, target, spec=None):

@@ -1361,6 +1361,81 @@ def pcm16_to_f32(pcm, out=None):
     return out
 
 
+CORPUS_ITEM_WORDS = 8                                     # ADYOLO_CORPUS_ITEM_WORDS / _ROT_WORDS in adyolo_hip.h
+CORPUS_STATUS = ((1, "more AD-YOLO rows than the target capacity"), (2, "an item outside the corpus"))
+
+
+def corpus_rot_table(combinations):
+    """augmentations.COMBINATIONS -> the host table [16][8] float {sy, sz, sx, swap, az weight, az offset, el weight, 0}."""
+    vals = []
+    for (sy, sz, sx), swap, pw, dpi, tw in combinations:
+        vals += [float(sy), float(sz), float(sx), float(swap), float(pw), float(dpi), float(tw), 0.0]
+    return (ctypes.c_float * len(vals))(*vals)
+
+
+def _corpus_i64(name, t, device):
+    if not t.is_cuda or t.dtype != torch.int64 or not t.is_contiguous() or t.device != device:
+        raise _lib.AdyoloHipError("%s must be a contiguous int64 tensor on %s" % (name, device))
+
+
+def corpus_gather(pcm, items, rot, out, status):
+    """pcm int16 (S, 4) and items int64 (B, 8) on the device -> out (B, n, 4) float32: the int16 windows at the items' sample
+    offsets as ``x / 32768 + 1e-8``, FOA-rotated by their combinations (adyolo_hip.h ``adyolo_corpus_gather``).  rot:
+    ``corpus_rot_table``; status: int32 word on the device the call ORs its bits into.  No allocation, no sync."""
+    dev = pcm.device
+    if not pcm.is_cuda or pcm.dtype != torch.int16 or not pcm.is_contiguous() or pcm.dim() != 2 or pcm.shape[1] != 4:
+        raise _lib.AdyoloHipError("corpus_gather: pcm must be a contiguous int16 tensor (S, 4) on the device")
+    _corpus_i64("corpus_gather: items", items, dev)
+    _chk(out)
+    b = items.shape[0] if items.dim() == 2 else 0
+    if items.dim() != 2 or items.shape[1] != CORPUS_ITEM_WORDS or out.dim() != 3 or out.shape[0] != b or out.shape[2] != 4:
+        raise _lib.AdyoloHipError("corpus_gather: items %s / out %s are not (B, %d) / (B, n, 4)"
+                                  % (tuple(items.shape), tuple(out.shape), CORPUS_ITEM_WORDS))
+    if status.dtype != torch.int32 or status.device != dev:
+        raise _lib.AdyoloHipError("corpus_gather: status must be an int32 word on %s" % dev)
+    _c("adyolo_corpus_gather", _p(pcm), pcm.shape[0], _p(items), b, out.shape[1], ctypes.cast(rot, ctypes.c_void_p), _p(out),
+       _p(status), _stream())
+    return out
+
+
+def corpus_labels_workspace_words(batch, max_events):
+    return int(_lib.load().adyolo_corpus_yolo_labels_workspace_words(int(batch), int(max_events)))
+
+
+def corpus_yolo_labels(events, items, max_events, n_label_frames, bounds, grid, rot, ws, target, count, status):
+    """The AD-YOLO rows of a batch on the device (adyolo_hip.h ``adyolo_corpus_yolo_labels``): events float64 (E, 4) {frame,
+    class, az, el}, items int64 (B, 8), bounds float64 (2 Gaz + 2 Gel,), grid (Gaz, Gel), ws int32 of
+    ``corpus_labels_workspace_words`` words -> target (cap, 7) float32 (b = -1 past the total), count int32 word = total rows.
+    status: int32 word the call ORs its bits into.  No allocation, no sync."""
+    dev = items.device
+    _corpus_i64("corpus_yolo_labels: items", items, dev)
+    if not events.is_cuda or events.dtype != torch.float64 or not events.is_contiguous() or events.dim() != 2 \
+            or events.shape[1] != 4 or events.device != dev:
+        raise _lib.AdyoloHipError("corpus_yolo_labels: events must be a contiguous float64 tensor (E, 4) on %s" % dev)
+    gaz, gel = int(grid[0]), int(grid[1])
+    if bounds.dtype != torch.float64 or bounds.device != dev or not bounds.is_contiguous() or bounds.numel() != 2 * (gaz + gel):
+        raise _lib.AdyoloHipError("corpus_yolo_labels: bounds must be float64 (2 Gaz + 2 Gel,) on %s" % dev)
+    _chk(target)
+    if target.dim() != 2 or target.shape[1] != 7:
+        raise _lib.AdyoloHipError("corpus_yolo_labels: target %s is not (cap, 7)" % (tuple(target.shape),))
+    b = items.shape[0]
+    for name, t, words in (("ws", ws, corpus_labels_workspace_words(b, max_events)), ("count", count, 1), ("status", status, 1)):
+        if t.dtype != torch.int32 or t.device != dev or not t.is_contiguous() or t.numel() < words:
+            raise _lib.AdyoloHipError("corpus_yolo_labels: %s must be at least %d int32 words on %s" % (name, words, dev))
+    n_ev = events.shape[0]
+    _c("adyolo_corpus_yolo_labels", _p(events), n_ev, _p(items), b, int(max_events), int(n_label_frames), _p(bounds), gaz, gel,
+       ctypes.cast(rot, ctypes.c_void_p), _p(ws), _p(target), target.shape[0], _p(count), _p(status), _stream())
+    return target
+
+
+def corpus_status_check(word):
+    """Raise ``AdyoloHipError`` for the ADYOLO_CORPUS_* bits of a status word already read to the host."""
+    word = int(word)
+    if word:
+        raise _lib.AdyoloHipError("adyolo corpus batch failed (status 0x%x): %s"
+                                  % (word, "; ".join(msg for bit, msg in CORPUS_STATUS if word & bit)))
+
+
 def mask_ranges_(feat, ranges):
     """In-place SpecAug masking of feat [B][T][F][C]: ranges int32 [B][4] = {t0, t1, f0, f1} per sample."""
     _chk(feat)

@@ -202,3 +202,41 @@ def train_one_epoch_audio(params: dict, dataloader, trainer, stager=None, rotate
         if nxt is None or (params.get("args", {}).get("quick_test") and n == 5):
             break
     return float(total) / max(n, 1)
+
+
+def train_one_epoch_corpus(params: dict, corpus, trainer):
+    """``train_one_epoch_audio`` on a ``corpus.DeviceCorpus``: batches of ``batch_size`` over ``corpus.get_filelist()`` in order,
+    each made on the device (gather + rotation of the audio, AD-YOLO rows into the fixed-capacity target) and handed with its
+    SpecAug tables to ``TrainStep.step``.  With ``trainer.graphs`` the two kernels write straight into the recorded step's input
+    buffers once it exists (eager launches before the replay, no copy).  The host draws of batch k+1 (rotation, SpecAug) happen
+    while step k runs, in the order the host path draws them.  Returns the mean loss with ONE device sync at the end, where the
+    corpus' status word is read too: a batch with more rows than the capacity (or an item outside the corpus) raises."""
+    bs = int(params["train_config"]["batch_size"])
+    files = corpus.get_filelist()
+    starts = list(range(0, len(files), bs))
+    if not starts:
+        return 0.0
+    graphs = trainer.graphs
+    target_like = torch.empty((corpus.cap, 7), dtype=torch.float32, device="meta")
+    corpus.reset_status()
+    total, n = None, 0
+    nxt = corpus.draw(range(starts[0], min(len(files), starts[0] + bs)))
+    for k in range(len(starts)):
+        drawn = nxt
+        items, spec = drawn
+        bufs = None
+        if graphs is not None:
+            bufs = graphs.static_inputs((items.shape[0], corpus.n_samples, 4), target_like,
+                                        None if spec is None else tuple(spec.shape))
+        audio, target, spec_dev = corpus.launch(drawn, *(bufs or ()))
+        loss = trainer.step(audio, target, spec_dev)
+        total = loss.detach().reshape(-1)[:1].clone() if total is None else total + loss.detach().reshape(-1)[:1]
+        n += 1
+        nxt = None
+        if k + 1 < len(starts):                   # the next batch's host draws while this step runs
+            nxt = corpus.draw(range(starts[k + 1], min(len(files), starts[k + 1] + bs)))
+        if nxt is None or (params.get("args", {}).get("quick_test") and n == 5):
+            break
+    loss_sum, status = ops.to_host_many(total, corpus.status)
+    corpus.check(int(status[0]))
+    return float(loss_sum[0]) / max(n, 1)

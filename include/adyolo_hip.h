@@ -566,6 +566,38 @@ int adyolo_ln_bwd(const float *dy, const float *x, const float *gamma, float *dx
  * cfg [B][4] = {sign_y, sign_z, sign_x, swap_xy}.  Label angles are remapped on the host (augmentations.RotationAug). */
 int adyolo_foa_rotate(const float *audio, float *out, const float *cfg, int B, long n_samples, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Training batches from an HBM-resident corpus (csrc/corpus.hip, ad-yolo_amd/corpus.py DeviceCorpus), opt-in: the host half of
+ * FoaDataset.__getitem__ + audio_collate_fn (src/datasets.py:93-184) on the device, from one small per-batch item table.
+ *   items    DEVICE int64 [B][ADYOLO_CORPUS_ITEM_WORDS] = {sample offset into pcm (frames), frame offset of the label window on
+ *            its recording's frame axis, first event of the window in `events`, number of events, FOA combination (0..15, or -1:
+ *            no rotation -- labels are then not wrapped either), recording, 0, 0}
+ *   rot_host HOST float [16][ADYOLO_CORPUS_ROT_WORDS] = {sign_y, sign_z, sign_x, swap_xy, azimuth weight, azimuth offset,
+ *            elevation weight, 0} per combination (augmentations.COMBINATIONS; passed by value: capturable)
+ *   status   DEVICE int32 word the calls OR their ADYOLO_CORPUS_* bits into (never cleared by them)
+ * adyolo_corpus_gather: audio [B][n][4] float32 = the int16 frames pcm[off .. off + n) (W,Y,Z,X) as x / 32768 + 1e-8, rotated
+ *   like adyolo_foa_rotate -- bit for bit adyolo_pcm16_to_f32 followed by adyolo_foa_rotate.  pcm [n_total][4] int16, 16-byte
+ *   aligned; an item outside it gets zeros and sets ADYOLO_CORPUS_BAD_ITEM.
+ * adyolo_corpus_yolo_labels: the AD-YOLO rows of the batch (datasets.get_yolo_label + collate_fn): per item, per event
+ *   [b, frame - frame offset, gi, gj, cls, U, V] for every responsible cell in (gi, gj) order, the rotation of
+ *   augmentations.rotate_labels and the cell test of YoloLabelEncoder.encode_events in double, events whose relative frame is
+ *   >= n_label_frames dropped.  events DEVICE double [n_events][4] = {frame, class, azimuth, elevation}; grid_bounds DEVICE
+ *   double [2 Gaz + 2 Gel] = az_lb, az_ub, el_lb, el_ub (YoloLabelEncoder); target [cap][7] float32: the first count[0] rows
+ *   written (at most cap; more sets ADYOLO_CORPUS_OVERFLOW, the rows past cap are dropped), b = -1 in the others (the loss
+ *   skips them); ws adyolo_corpus_yolo_labels_workspace_words(B, max_events) int32 words; max_events >= every item's event
+ *   count (a larger count sets ADYOLO_CORPUS_BAD_ITEM and the item gets no rows).  Gaz, Gel <= 64, else ENOSUP.
+ * ---------------------------------------------------------------------------------------------- */
+#define ADYOLO_CORPUS_ITEM_WORDS 8
+#define ADYOLO_CORPUS_ROT_WORDS  8
+#define ADYOLO_CORPUS_OVERFLOW   1   /* more rows than the target capacity */
+#define ADYOLO_CORPUS_BAD_ITEM   2   /* an item table entry outside the corpus */
+int  adyolo_corpus_gather(const int16_t *pcm, long n_total, const int64_t *items, int B, long n, const float *rot_host,
+                          float *audio, int *status, void *stream);
+long adyolo_corpus_yolo_labels_workspace_words(int B, int max_events);
+int  adyolo_corpus_yolo_labels(const double *events, long n_events, const int64_t *items, int B, int max_events,
+                               int n_label_frames, const double *grid_bounds, int Gaz, int Gel, const float *rot_host,
+                               int *ws, float *target, long cap, int *count, int *status, void *stream);
+
 /* K11 fused Adam over one flat parameter buffer (torch.optim.Adam at src/train.py:31,55; no amsgrad) */
 int adyolo_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, long n,
                      float lr, float beta1, float beta2, float eps, float weight_decay, int step,

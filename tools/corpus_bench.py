@@ -1,0 +1,221 @@
+"""Training from the HBM-resident corpus against the host loader, on a synthetic chunked split written to local disk.
+
+A split in the reference's chunked layout (``foa_dev/dev-train-chunked_20s_1s`` + ``metadata_dev/...``: 60 s recordings of int16
+noise cut into 41 overlapping 20 s chunks, chunk CSVs with ~1 event per label frame, 12 classes) is written to --dir.  Then, per
+batch size (16 and 64 x 20 s, hipGraph-replayed steps):
+
+  load          load_chunked_split (verify="sample") + DeviceCorpus upload: seconds and bytes held on the device
+  batch         gather + label kernels of one batch (DeviceCorpus.launch), device time per batch (events around --iters batches)
+  replay        the recorded train step alone on fixed inputs (the rate a loader has to keep up with)
+  corpus        train_one_epoch_corpus
+  host          train_one_epoch_audio over DataLoader(FoaDataset, num_workers=--workers, audio_collate_fn)
+For both epochs: the wall time per step over the whole epoch (synchronised at its end; DataLoader start-up included), the
+steady interval between step launches from the third step on (both paths keep at most two batches in flight, so this is the
+rate the GPU is fed at), and the host CPU seconds per step (resource.getrusage of this process -- the launching thread's waits
+on the GPU included -- and of its reaped children, i.e. the DataLoader workers).  Each path runs one warm epoch first (eager
+step, capture; page cache).
+
+  python tools/corpus_bench.py [--dir /tmp/adyolo_corpus] [--batches 16,64] [--steps 32,8] [--workers 16] [--json out.json]
+"""
+import argparse
+import csv
+import json
+import os
+import random
+import resource
+import shutil
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+SR, WINDOW_S, STRIDE_S, REC_S = 24000, 20, 1, 60
+
+
+def write_split(root, n_recordings, seed=0):
+    """n_recordings x 60 s, chunked as the reference's preprocess.chunk_instance cuts them (60 s: no padding)."""
+    from scipy.io import wavfile
+    rs = np.random.RandomState(seed)
+    sub = "dev-train-chunked_%ds_%ds" % (WINDOW_S, STRIDE_S)
+    wdir, cdir = os.path.join(root, "foa_dev", sub), os.path.join(root, "metadata_dev", sub)
+    os.makedirs(wdir, exist_ok=True)
+    os.makedirs(cdir, exist_ok=True)
+    win, st, wf, sf = SR * WINDOW_S, SR * STRIDE_S, WINDOW_S * 10, STRIDE_S * 10
+    nbytes = 0
+    for r in range(n_recordings):
+        audio = np.clip(rs.normal(0, 3000, size=(SR * REC_S, 4)), -32768, 32767).astype(np.int16)
+        label = {}
+        for f in range(REC_S * 10):
+            k = rs.choice(3, p=[0.35, 0.45, 0.2])
+            if k:
+                label[f] = [[int(rs.randint(12)), s, round(float(rs.uniform(-180, 180)), 1), round(float(rs.uniform(-60, 60)), 1)]
+                            for s in range(k)]
+        for i in range((len(audio) - win) // st + 1):
+            name = "fold1_room%d_mix%03d_chunk%03d" % (r % 10, r, i + 1)
+            wavfile.write(os.path.join(wdir, name + ".wav"), SR, audio[i * st:i * st + win])
+            nbytes += win * 8
+            with open(os.path.join(cdir, name + ".csv"), "w", newline="") as fid:
+                w = csv.writer(fid)
+                for f in range(wf):
+                    for ev in label.get(i * sf + f, ()):
+                        w.writerow([f] + ev)
+    return nbytes
+
+
+def params(root, batch, steps):
+    from __graft_entry__ import _params
+    prm = _params()
+    prm["data_config"].update({"data_pth": root, "chunk_window_s": WINDOW_S, "chunk_stride_s": STRIDE_S, "sr": SR,
+                               "label_hop_len_s": 0.1})
+    prm["train_config"].update({"batch_size": batch, "nb_iters": steps})
+    prm["aug_config"] = {"rotation_augment": True, "spec_augment": True, "spec_augment_thresh": 0.5,
+                         "spec_augment_time_mask_param": 40, "spec_augment_freq_mask_param": 40}
+    return prm
+
+
+def trainer(prm):
+    from adyolo_amd.features import FeatureExtractor
+    from adyolo_amd.train import TrainStep
+    from adyolo_amd.wrapper import WrapperCriterion, WrapperModel
+    torch.manual_seed(0)
+    model = WrapperModel((1, 7, SR * WINDOW_S // 600, 64), (), prm).to("cuda:0")
+    tr = TrainStep(model, WrapperCriterion(prm), FeatureExtractor(None, "cuda:0"), prm, graph=True)
+    tr.stamps = []
+    inner = tr.step
+
+    def step(audio, target, spec=None):
+        loss = inner(audio, target, spec)
+        tr.stamps.append(time.perf_counter())
+        return loss
+    tr.step = step
+    return tr
+
+
+def cpu_seconds():
+    s, c = resource.getrusage(resource.RUSAGE_SELF), resource.getrusage(resource.RUSAGE_CHILDREN)
+    return s.ru_utime + s.ru_stime + c.ru_utime + c.ru_stime
+
+
+def timed_epoch(run, tr):
+    """run() -> one epoch.  -> steps, wall s, steady steps/s, CPU s per step."""
+    torch.cuda.synchronize()
+    tr.stamps = []
+    c0, t0 = cpu_seconds(), time.perf_counter()
+    run()
+    torch.cuda.synchronize()
+    t1, c1 = time.perf_counter(), cpu_seconds()
+    n = len(tr.stamps)
+    steady = (tr.stamps[-1] - tr.stamps[2]) / (n - 3) if n > 3 else float("nan")
+    return {"steps": n, "wall_s": round(t1 - t0, 4), "wall_ms_per_step": round(1e3 * (t1 - t0) / max(n, 1), 3),
+            "steady_ms_per_step": round(1e3 * steady, 3), "steady_steps_per_s": round(1.0 / steady, 2),
+            "cpu_s_per_step": round((c1 - c0) / max(n, 1), 4)}
+
+
+def bench_batch(root, batch, steps, workers, iters):
+    from adyolo_amd.corpus import DeviceCorpus, load_chunked_split
+    from adyolo_amd.datasets import FoaDataset, audio_collate_fn
+    from adyolo_amd.train import train_one_epoch_audio, train_one_epoch_corpus
+    prm = params(root, batch, steps)
+    out = {"batch": batch, "steps_per_epoch": steps}
+    t0 = time.perf_counter()
+    hc = load_chunked_split(prm, verify="sample")
+    t1 = time.perf_counter()
+    random.seed(0)
+    corpus = DeviceCorpus(hc, prm, "cuda:0")
+    torch.cuda.synchronize()
+    t2 = time.perf_counter()
+    out["load"] = {"host_s": round(t1 - t0, 3), "upload_s": round(t2 - t1, 3), "device_bytes": corpus.nbytes(),
+                   "files": len(hc.total_filelist), "recordings": len(hc.rec_names), "cap_rows": corpus.cap}
+    # gather + labels of one batch
+    drawn = [corpus.draw(range(i * batch % len(corpus), i * batch % len(corpus) + batch)) for i in range(4)]
+    for d in drawn:
+        corpus.launch(d)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for i in range(iters):
+        corpus.launch(drawn[i % 4])
+    e1.record()
+    torch.cuda.synchronize()
+    out["batch_ms"] = round(e0.elapsed_time(e1) / iters, 4)
+
+    tc = trainer(prm)
+    for ep in range(2):
+        if ep:
+            corpus.sample_filelist_for_train_iter()
+        r = timed_epoch(lambda: train_one_epoch_corpus(prm, corpus, tc), tc)
+    out["corpus"] = r
+    out["corpus"]["captures"] = tc.graphs.captures
+    # the replayed step alone, on fixed inputs
+    audio, target, spec = corpus.batch(range(batch))
+    for _ in range(3):
+        tc.step(audio, target, spec)
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(iters):
+        tc.step(audio, target, spec)
+    e1.record()
+    torch.cuda.synchronize()
+    out["replay_ms"] = round(e0.elapsed_time(e1) / iters, 3)
+    del tc, corpus
+    torch.cuda.empty_cache()
+
+    th = trainer(prm)
+    random.seed(0)
+    ds = FoaDataset(prm, "train")
+    for ep in range(2):
+        if ep:
+            ds.sample_filelist_for_train_iter()
+        loader = torch.utils.data.DataLoader(ds, batch_size=batch, shuffle=False, collate_fn=audio_collate_fn,
+                                             num_workers=workers, pin_memory=False)
+        r = timed_epoch(lambda: train_one_epoch_audio(prm, loader, th), th)
+        del loader
+    out["host"] = r
+    out["host"]["workers"] = workers
+    out["host"]["captures"] = th.graphs.captures
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--dir", default=os.path.join("/tmp", "adyolo_corpus_bench"))
+    ap.add_argument("--batches", default="16,64")
+    ap.add_argument("--steps", default="32,8", help="steps per epoch, one per batch size")
+    ap.add_argument("--workers", type=int, default=16)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--keep", action="store_true", help="keep the split on disk afterwards")
+    ap.add_argument("--json")
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "corpus_bench needs the GPU"
+    import adyolo_amd  # noqa: F401
+    batches = [int(b) for b in a.batches.split(",")]
+    steps = [int(s) for s in a.steps.split(",")]
+    steps = (steps * len(batches))[:len(batches)] if len(steps) == 1 else steps
+    files = max(b * s for b, s in zip(batches, steps))
+    n_rec = -(-files // (REC_S - WINDOW_S + 1))
+    shutil.rmtree(a.dir, ignore_errors=True)
+    t0 = time.perf_counter()
+    nbytes = write_split(a.dir, n_rec)
+    res = {"split": {"recordings": n_rec, "wav_bytes": nbytes, "write_s": round(time.perf_counter() - t0, 2)},
+           "cpus": len(os.sched_getaffinity(0))}
+    print(json.dumps(res), flush=True)
+    try:
+        for b, s in zip(batches, steps):
+            r = bench_batch(a.dir, b, s, a.workers, a.iters)
+            res["b%d" % b] = r
+            print(json.dumps(r), flush=True)
+    finally:
+        if not a.keep:
+            shutil.rmtree(a.dir, ignore_errors=True)
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()

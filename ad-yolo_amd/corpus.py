@@ -9,23 +9,29 @@ rotates and encodes the labels on the host and stages every batch over PCIe.  He
   ``stream[(k-1) stride : (k-1) stride + window]`` bit for bit, the zero padding of the last window included; and one event
   table -- chunk 001's rows, then the last ``stride / label_hop`` frames of every later chunk on the recording's frame axis.
   Every chunk CSV is checked against the table, and (``verify``) chunk audio against the stream.
-* ``DeviceCorpus`` (device half): the streams as one int16 buffer and the events as one float64 table in HBM (0.69 GB per hour
-  of 4-channel 24 kHz audio), ``FoaDataset``'s sampling surface (the same functions), and ``batch(indices)``: the same ``random``
-  draws as ``FoaDataset.__getitem__`` item by item, one small H2D copy of the item table, then ``adyolo_corpus_gather`` (audio,
-  rotated) and ``adyolo_corpus_yolo_labels`` (the AD-YOLO rows into a fixed-capacity target, padding b = -1).  No host sync.
+* ``DeviceCorpus`` (device half, AD-YOLO): the streams as one int16 buffer and the events as one float64 table in HBM (0.69 GB
+  per hour of 4-channel 24 kHz audio), ``FoaDataset``'s sampling surface (the same functions), and ``batch(indices)``: the same
+  ``random`` draws as ``FoaDataset.__getitem__`` item by item, one small H2D copy of the item table, then ``adyolo_corpus_gather``
+  (audio, rotated) and ``adyolo_corpus_yolo_labels`` (the AD-YOLO rows into a fixed-capacity target, padding b = -1).  No host
+  sync.
+* ``ClasswiseDeviceCorpus`` (device half, ``seddoa | masked-seddoa | accdoa | adpit``): the same split, sampling, draws and
+  gather; the labels are ``adyolo_corpus_classwise_labels``, the dense ``ClasswiseLabelEncoder`` targets of the batch written
+  whole, from a float32 table of every event's direction vector under no rotation and the 16 FOA combinations (``xyz_table``,
+  built once on the host with the host's own functions: 204 bytes per event).
 
-Parity: the same audio bit for bit and the same rows in the same order as the host path iterated in the main process
-(``num_workers=0``); with DataLoader workers the host path's draws happen in per-worker streams.
+Parity: the same audio bit for bit and the same rows in the same order (or the same dense targets bit for bit) as the host
+path iterated in the main process (``num_workers=0``); with DataLoader workers the host path's draws happen in per-worker streams.
 """
 import copy
 import os
 import random
+import struct
 
 import numpy as np
 import torch
 
 from . import ops
-from .datasets import FoaDataset, YoloLabelEncoder
+from .datasets import CLASSWISE_LABELS, FoaDataset, YoloLabelEncoder
 
 # event table columns (host): recording frame, class, source, azimuth, elevation
 _EV_COLS = 5
@@ -215,15 +221,41 @@ def _rank_world(rank, world):
     return int(rank or 0), int(world)
 
 
-class DeviceCorpus:
-    """A ``HostCorpus`` in HBM with ``FoaDataset``'s sampling surface and a device-side ``batch``.
+def xyz_table(az, el):
+    """float32 (E, 17, 3): the direction vector ``ClasswiseLabelEncoder`` writes for each event (azimuth / elevation in degrees)
+    -- slot 0 without rotation (the host path does not call ``rotate_labels`` then), slot 1 + k after ``rotate_labels`` with
+    combination k -- computed by the host's own functions on scalars and rounded to float32 as the encoder's output is.  Memoised
+    on the bit patterns of the angles (``-0.0 == 0.0`` as a dict key, but ``sin(-0.0)`` is ``-0.0``)."""
+    from .augmentations import COMBINATIONS, rotate_labels
+    from .datasets import _polar_to_xyz
+    az = np.asarray(az, dtype=np.float64).reshape(-1)
+    el = np.asarray(el, dtype=np.float64).reshape(-1)
+    n_slots = 1 + len(COMBINATIONS)
+    if az.shape[0] == 0:
+        return np.zeros((0, n_slots, 3), dtype=np.float32)
+    keys, inv = np.unique(np.stack([az, el], 1).view(np.int64), axis=0, return_inverse=True)
+    pairs = keys.view(np.float64).tolist()                       # Python floats, as load_csv2dict reads them
+    memo = {}
 
-        corpus = DeviceCorpus(load_chunked_split(params), params, "cuda:0")
-        audio, target, spec = corpus.batch(range(16))    # (16, n, 4) f32, (cap, 7) f32, (16, 2, 4) int32 or None: all on the device
+    def xyz(a, e):
+        k = struct.pack("<dd", a, e)
+        v = memo.get(k)
+        if v is None:
+            v = memo[k] = _polar_to_xyz(a, e)
+        return v
+    uniq = np.empty((len(pairs), n_slots, 3), dtype=np.float64)
+    for i, (a, e) in enumerate(pairs):
+        uniq[i, 0] = xyz(a, e)
+    rows = [[0, 0, a, e] for a, e in pairs]
+    for k in range(len(COMBINATIONS)):
+        for i, ev in enumerate(rotate_labels({0: rows}, k)[0]):
+            uniq[i, 1 + k] = xyz(ev[2], ev[3])
+    return uniq.astype(np.float32)[inv.reshape(-1)]
 
-    ``cap`` (the target rows) is fixed here: batch_size x (largest event count of a window) x (largest cell count of an event),
-    rounded up to ``graph.TARGET_QUANTUM`` -- one input shape, one recorded graph.  More rows than that in a batch (a smaller
-    ``cap`` forced by the caller) set the status word; ``check()`` raises then.  AD-YOLO labels only."""
+
+class _CorpusBase:
+    """What both device corpora share: the split in HBM, ``FoaDataset``'s sampling surface, the host draws of a batch, the upload
+    of its item table and the audio gather.  Subclasses add the label encoding."""
 
     # the same functions as the host dataset: checkpoints (remaining_file) and the rank shards interchange with it
     sample_filelist_for_train_iter = FoaDataset.sample_filelist_for_train_iter
@@ -232,13 +264,8 @@ class DeviceCorpus:
     get_filelist = FoaDataset.get_filelist
     __len__ = FoaDataset.__len__
 
-    def __init__(self, host_corpus, params, device="cuda:0", rank=None, world=None, cap=None):
-        from . import graph
+    def _setup(self, host_corpus, params, device, rank, world):
         from .augmentations import COMBINATIONS, SpecAug
-        self.loss_nm = params["args"]["loss"]
-        if self.loss_nm != "adyolo":
-            raise NotImplementedError("DeviceCorpus: loss %s -- only the AD-YOLO label encoding runs on the device; the class-wise "
-                                      "losses need FoaDataset" % self.loss_nm)
         self.host = hc = host_corpus
         self.device = torch.device(device)
         self._copy, self._os, self._random = copy, os, random
@@ -248,29 +275,21 @@ class DeviceCorpus:
         self.hop_label = hc.hop_label
         self.rotate = bool(params.get("aug_config", {}).get("rotation_augment", False))
         self.specaug = SpecAug(params, False)
-        self.encoder = YoloLabelEncoder(params)
         self.batch_size = int(params["train_config"]["batch_size"])
         self.n_samples, self.n_label_frames = hc.window, hc.window // hc.hop_label
         self.max_events = hc.max_events
-        self.cells = max_cells_per_event(self.encoder)
-        if cap is None:
-            need = max(1, self.batch_size * self.max_events * self.cells)
-            cap = (need + graph.TARGET_QUANTUM - 1) // graph.TARGET_QUANTUM * graph.TARGET_QUANTUM
-        self.cap = int(cap)
         # the corpus in HBM
         self.pcm = torch.from_numpy(hc.audio).to(self.device)
         ev = hc.events[:, [0, 1, 3, 4]] if hc.events.shape[0] else np.zeros((1, 4))
         self.events = torch.from_numpy(np.ascontiguousarray(ev, dtype=np.float64)).to(self.device)
         self.n_events = int(hc.events.shape[0])
-        enc = self.encoder
-        self.bounds = torch.from_numpy(np.concatenate([enc.az_lb, enc.az_ub, enc.el_lb, enc.el_ub]).astype(np.float64)).to(self.device)
-        self.grid = (len(enc.az_lb), len(enc.el_lb))
         self.rot = ops.corpus_rot_table(COMBINATIONS)
         self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
-        self.rows = None                 # int32 word on the device: the row count of the last batch
         self._pinned, self._copied, self._slot = {}, [None, None], 0
-        # sampling: FoaDataset.__init__ for a training split
-        self.total_filelist = list(hc.total_filelist)
+
+    def _start_sampling(self, params):
+        """FoaDataset.__init__ for a training split: the first draw of files."""
+        self.total_filelist = list(self.host.total_filelist)
         self.remaining_file = copy.deepcopy(self.total_filelist)
         self.nb_samples = self.batch_size * params["train_config"]["nb_iters"] * self.world
         self.filelist = []
@@ -299,9 +318,9 @@ class DeviceCorpus:
             items[j] = (off, f_off, ev_lo, ev_n, comb, rec, 0, 0)
         return items, spec
 
-    def launch(self, drawn, audio_out=None, target_out=None):
-        """The device half: one H2D copy of the item table (+ SpecAug tables), the gather and the label kernels.
-        -> (audio (B, n, 4) f32, target (cap, 7) f32, spec (B, 2, 4) int32 or None) on the device; no host sync."""
+    def _upload(self, drawn):
+        """One H2D copy of the item table (+ SpecAug tables) through a double-buffered page-locked buffer
+        -> (items int64 (B, 8), spec int32 (B, 2, 4) or None) on the device."""
         items, spec = drawn
         b = items.shape[0]
         n_i = b * ops.CORPUS_ITEM_WORDS
@@ -325,6 +344,63 @@ class DeviceCorpus:
         self._copied[slot] = ev
         dev_items = dev[:n_i].view(b, ops.CORPUS_ITEM_WORDS)
         dev_spec = dev[n_i:].view(torch.int32).view(b, 2, 4) if spec is not None else None
+        return dev_items, dev_spec
+
+    def batch(self, indices, audio_out=None, target_out=None):
+        """Items ``indices`` of ``get_filelist()`` -> (audio (B, n, 4) f32, target, spec (B, 2, 4) int32 or None), on the device,
+        with no host synchronisation.  audio_out / target_out: write into these buffers (a recorded step's)."""
+        return self.launch(self.draw(indices), audio_out, target_out)
+
+    def reset_status(self):
+        self.status.zero_()
+
+    def check(self, word=None):
+        """Raise if a batch overflowed its capacity, had an item outside the corpus or an event class outside the model's (reads
+        the status word: synchronises, unless the caller passes the word it already read)."""
+        if word is None:
+            word = int(ops.to_host(self.status)[0])
+        ops.corpus_status_check(word)
+
+
+class DeviceCorpus(_CorpusBase):
+    """A ``HostCorpus`` in HBM with ``FoaDataset``'s sampling surface and a device-side ``batch``.
+
+        corpus = DeviceCorpus(load_chunked_split(params), params, "cuda:0")
+        audio, target, spec = corpus.batch(range(16))    # (16, n, 4) f32, (cap, 7) f32, (16, 2, 4) int32 or None: all on the device
+
+    ``cap`` (the target rows) is fixed here: batch_size x (largest event count of a window) x (largest cell count of an event),
+    rounded up to ``graph.TARGET_QUANTUM`` -- one input shape, one recorded graph.  More rows than that in a batch (a smaller
+    ``cap`` forced by the caller) set the status word; ``check()`` raises then.  AD-YOLO labels only: the class-wise losses
+    train from ``ClasswiseDeviceCorpus``."""
+
+    def __init__(self, host_corpus, params, device="cuda:0", rank=None, world=None, cap=None):
+        from . import graph
+        self.loss_nm = params["args"]["loss"]
+        if self.loss_nm != "adyolo":
+            raise NotImplementedError("DeviceCorpus: loss %s -- AD-YOLO labels only; the class-wise losses train from "
+                                      "ClasswiseDeviceCorpus" % self.loss_nm)
+        self._setup(host_corpus, params, device, rank, world)
+        self.encoder = YoloLabelEncoder(params)
+        self.cells = max_cells_per_event(self.encoder)
+        if cap is None:
+            need = max(1, self.batch_size * self.max_events * self.cells)
+            cap = (need + graph.TARGET_QUANTUM - 1) // graph.TARGET_QUANTUM * graph.TARGET_QUANTUM
+        self.cap = int(cap)
+        enc = self.encoder
+        self.bounds = torch.from_numpy(np.concatenate([enc.az_lb, enc.az_ub, enc.el_lb, enc.el_ub]).astype(np.float64)).to(self.device)
+        self.grid = (len(enc.az_lb), len(enc.el_lb))
+        self.rows = None                 # int32 word on the device: the row count of the last batch
+        self._start_sampling(params)
+
+    def target_shape(self, batch):
+        """The target of every batch: (cap, 7) rows, whatever the batch size."""
+        return (self.cap, 7)
+
+    def launch(self, drawn, audio_out=None, target_out=None):
+        """The device half: one H2D copy of the item table (+ SpecAug tables), the gather and the label kernels.
+        -> (audio (B, n, 4) f32, target (cap, 7) f32, spec (B, 2, 4) int32 or None) on the device; no host sync."""
+        dev_items, dev_spec = self._upload(drawn)
+        b = dev_items.shape[0]
         audio = audio_out if audio_out is not None else \
             torch.empty((b, self.n_samples, 4), dtype=torch.float32, device=self.device)
         target = target_out if target_out is not None else torch.empty((self.cap, 7), dtype=torch.float32, device=self.device)
@@ -338,17 +414,58 @@ class DeviceCorpus:
                                target, self.rows, self.status)
         return audio, target, dev_spec
 
-    def batch(self, indices, audio_out=None, target_out=None):
-        """Items ``indices`` of ``get_filelist()`` -> (audio (B, n, 4) f32, target (cap, 7) f32, spec (B, 2, 4) int32 or None), on
-        the device, with no host synchronisation.  audio_out / target_out: write into these buffers (a recorded step's)."""
-        return self.launch(self.draw(indices), audio_out, target_out)
 
-    def reset_status(self):
-        self.status.zero_()
+class ClasswiseDeviceCorpus(_CorpusBase):
+    """``DeviceCorpus`` for the class-wise losses (``seddoa | masked-seddoa | accdoa | adpit``): the same split in HBM, sampling
+    surface, ``random`` draws and audio gather; the target is the dense tensor ``FoaDataset`` + ``audio_collate_fn`` make
+    (``ClasswiseLabelEncoder`` on the rotated labels, stacked), written whole on the device by ``adyolo_corpus_classwise_labels``
+    from ``xyz`` (``xyz_table`` of every event, float32 (E, 17, 3) in HBM).
 
-    def check(self, word=None):
-        """Raise if a batch overflowed its capacity or had an item outside the corpus (reads the status word: synchronises,
-        unless the caller passes the word it already read)."""
-        if word is None:
-            word = int(ops.to_host(self.status)[0])
-        ops.corpus_status_check(word)
+        corpus = ClasswiseDeviceCorpus(load_chunked_split(params), params, "cuda:0")
+        audio, target, spec = corpus.batch(range(64))    # target: corpus.target_shape(64), e.g. (64, T', 6, 4, C) for adpit
+
+    Every event class must be in [0, nb_classes) (``ValueError`` naming the recording otherwise: the host encoders would fail on
+    it).  No host sync in ``batch`` / ``launch``; ``check()`` reads the status word."""
+
+    def __init__(self, host_corpus, params, device="cuda:0", rank=None, world=None):
+        self.loss_nm = params["args"]["loss"]
+        if self.loss_nm not in CLASSWISE_LABELS:
+            raise ValueError("ClasswiseDeviceCorpus: loss %s -- the class-wise losses are %s (AD-YOLO trains from DeviceCorpus)"
+                             % (self.loss_nm, ", ".join(sorted(CLASSWISE_LABELS))))
+        self.nb_classes = c = int(params["data_config"]["nb_classes"])
+        hc = host_corpus
+        cls = hc.events[:, 1]
+        bad = np.flatnonzero(~((cls >= 0) & (cls < c)))
+        if bad.size:
+            r = int(np.searchsorted(hc.ev_start, bad[0], "right")) - 1
+            raise ValueError("ClasswiseDeviceCorpus: recording %s has an event of class %g, outside [0, %d) (nb_classes)"
+                             % (hc.rec_names[r], cls[bad[0]], c))
+        self._setup(host_corpus, params, device, rank, world)
+        xyz = xyz_table(hc.events[:, 3], hc.events[:, 4]) if hc.events.shape[0] else \
+            np.zeros((1, ops.CORPUS_XYZ_SLOTS, 3), dtype=np.float32)
+        self.xyz = torch.from_numpy(xyz).to(self.device)
+        self._start_sampling(params)
+
+    def nbytes(self):
+        return super().nbytes() + int(self.xyz.numel() * 4)
+
+    def target_shape(self, batch):
+        """(B, T', 4C) seddoa / masked-seddoa, (B, T', 3C) accdoa, (B, T', 6, 4, C) adpit."""
+        return ops.corpus_classwise_shape(self.loss_nm, batch, self.n_label_frames, self.nb_classes)
+
+    def launch(self, drawn, audio_out=None, target_out=None):
+        """The device half: one H2D copy of the item table (+ SpecAug tables), the gather and the label kernel.
+        -> (audio (B, n, 4) f32, target ``target_shape(B)`` f32, spec (B, 2, 4) int32 or None) on the device; no host sync."""
+        dev_items, dev_spec = self._upload(drawn)
+        b = dev_items.shape[0]
+        shape = self.target_shape(b)
+        audio = audio_out if audio_out is not None else \
+            torch.empty((b, self.n_samples, 4), dtype=torch.float32, device=self.device)
+        target = target_out if target_out is not None else torch.empty(shape, dtype=torch.float32, device=self.device)
+        if tuple(audio.shape) != (b, self.n_samples, 4) or tuple(target.shape) != shape:
+            raise ValueError("ClasswiseDeviceCorpus.launch: output buffers %s / %s, expected (%d, %d, 4) / %s"
+                             % (tuple(audio.shape), tuple(target.shape), b, self.n_samples, shape))
+        ops.corpus_gather(self.pcm, dev_items, self.rot, audio, self.status)
+        ops.corpus_classwise_labels(self.events, dev_items, self.xyz, self.max_events, self.n_label_frames, self.nb_classes,
+                                    self.loss_nm, target, self.status)
+        return audio, target, dev_spec

@@ -1,14 +1,19 @@
-// Training batches from an HBM-resident corpus (ad-yolo_amd/corpus.py DeviceCorpus): the chunk gather of the audio and the
-// AD-YOLO label encoding, both from a per-batch item table, so that no training chunk crosses PCIe.  What they replace is the
-// host half of FoaDataset.__getitem__ + audio_collate_fn (reference src/datasets.py:93-184: the WAV read, ``audio / 32768 +
-// 1e-8``, RotationAug, get_yolo_label, collate_fn) followed by AudioStager, adyolo_pcm16_to_f32 and adyolo_foa_rotate.
+// Training batches from an HBM-resident corpus (ad-yolo_amd/corpus.py DeviceCorpus, ClasswiseDeviceCorpus): the chunk gather of
+// the audio and the label encoding (AD-YOLO rows or dense class-wise targets), both from a per-batch item table, so that no
+// training chunk crosses PCIe.  What they replace is the host half of FoaDataset.__getitem__ + audio_collate_fn (reference
+// src/datasets.py:93-184: the WAV read, ``audio / 32768 + 1e-8``, RotationAug, get_yolo_label or the class-wise encoders,
+// collate_fn) followed by AudioStager, adyolo_pcm16_to_f32 and adyolo_foa_rotate.
 //
 //   corpus_gather_kernel     one pass int16 window -> float32 ``x / 32768 + 1e-8``, FOA channels rotated; 16-byte loads of
 //                            two int16 frames, two 16-byte stores (8-byte loads when the window starts on an odd frame)
 //   corpus_count_scan_kernel one workgroup: rows per (item, event) lane, exclusive scan, the total and the overflow bit
 //   corpus_rows_kernel       the rows [b, t, gi, gj, cls, U, V] at their scanned offsets, b = -1 in the rest of the capacity
-// The label arithmetic is done in double, as the host does it (augmentations.rotate_labels on Python floats,
-// datasets.YoloLabelEncoder.encode_events in float64); only the written row is rounded to float32.
+//   corpus_classwise_kernel  the dense SEDDOA / ACCDOA / ADPIT targets (datasets.ClasswiseLabelEncoder): per tile of label
+//                            frames, each frame's event range, the event each (frame, class) output takes, then every output
+//                            element written once
+// The AD-YOLO label arithmetic is done in double, as the host does it (augmentations.rotate_labels on Python floats,
+// datasets.YoloLabelEncoder.encode_events in float64); only the written row is rounded to float32.  The class-wise kernel does
+// no arithmetic at all: the direction vectors come from a table the host builds with its own functions (corpus.xyz_table).
 #include "common.hpp"
 
 namespace adyolo {
@@ -205,6 +210,113 @@ __global__ __launch_bounds__(256) void corpus_rows_kernel(const double *__restri
     }
 }
 
+constexpr int CW_THREADS = 256;
+constexpr int CW_FRAMES = 8;                   // label frames per workgroup
+constexpr int CW_MAX_CLASSES = 256;
+constexpr int CW_EV_CACHE = 512;               // classes of a tile's events held in LDS (the rest are read from memory)
+
+struct CorpusClasswiseGeom {
+    int B, max_events, n_label_frames, C, format, row;   // row: floats per label frame (4 C, 3 C or 24 C)
+    long n_events;
+};
+
+// grid (label-frame tiles, B).  LDS: lb[i] = the first event of the item at or after frame t0 + i; cls[] = the classes of the
+// tile's events (-1: outside [0, C)); pick[i][c] = {count of class c in frame t0 + i, its first three events} (ADPIT) or {its
+// last event, ...} (SEDDOA / ACCDOA), -1 where there is none.
+__global__ __launch_bounds__(CW_THREADS) void corpus_classwise_kernel(const double *__restrict__ events,
+                                                                      const float *__restrict__ xyz,
+                                                                      const int64_t *__restrict__ items, CorpusClasswiseGeom g,
+                                                                      float *__restrict__ target, int *__restrict__ status) {
+    extern __shared__ int pick[];                // [CW_FRAMES][C][4]
+    __shared__ int lb[CW_FRAMES + 1];
+    __shared__ int cls[CW_EV_CACHE];
+    const int b = blockIdx.y, t0 = blockIdx.x * CW_FRAMES, tid = threadIdx.x;
+    const int nf = g.n_label_frames - t0 < CW_FRAMES ? g.n_label_frames - t0 : CW_FRAMES;
+    const int64_t *it = items + (size_t)b * ADYOLO_CORPUS_ITEM_WORDS;
+    const int64_t frame_off = it[1], ev_lo = it[2], ev_n = it[3], comb = it[4];
+    float *dst = target + ((size_t)b * g.n_label_frames + t0) * g.row;
+    const int n_out = nf * g.row;
+    if (ev_lo < 0 || ev_n < 0 || ev_n > g.max_events || ev_lo > g.n_events - ev_n || comb >= 16) {
+        if (blockIdx.x == 0 && tid == 0) atomicOr(status, ADYOLO_CORPUS_BAD_ITEM);
+        for (int p = tid; p < n_out; p += CW_THREADS) dst[p] = 0.f;
+        return;
+    }
+    const double *ev = events + (size_t)ev_lo * 4;
+    const int n = (int)ev_n;
+    if (tid <= nf) lb[tid] = n;
+    __syncthreads();
+    // the item's events are frame-sorted: lb[i] is written by the one event whose frame is the first to reach t0 + i (one round
+    // of independent loads, no binary search); it stays n where none does.  Unsorted input can leave lb out of order: every
+    // range below is then empty or still inside [0, n).
+    const double base = (double)(frame_off + t0);
+    for (int e = tid; e < n; e += CW_THREADS) {
+        const double fe = ev[(size_t)e * 4] - base;
+        const double fp = e > 0 ? ev[(size_t)(e - 1) * 4] - base : -1.0;
+        const double lo = fp < 0.0 ? 0.0 : floor(fp) + 1.0, hi = fe > (double)nf ? (double)nf : floor(fe);
+        if (lo <= hi)
+            for (int i = (int)lo; i <= (int)hi; ++i) lb[i] = e;
+    }
+    __syncthreads();
+    const int C = g.C, e0 = lb[0], e1 = lb[nf];
+    for (int e = e0 + tid; e < e1; e += CW_THREADS) {             // the tile's events: classes checked, the first ones cached
+        const double cd = ev[(size_t)e * 4 + 1];
+        const bool ok = cd >= 0.0 && cd < (double)C;
+        if (!ok) atomicOr(status, ADYOLO_CORPUS_BAD_CLASS);
+        if (e - e0 < CW_EV_CACHE) cls[e - e0] = ok ? (int)cd : -1;
+    }
+    __syncthreads();
+    const bool adpit = g.format == ADYOLO_CORPUS_ADPIT;
+    for (int p = tid; p < nf * C; p += CW_THREADS) {
+        const int i = p / C, c = p - i * C;
+        int cnt = 0, last = -1, first[3] = {-1, -1, -1};
+        for (int e = lb[i]; e < lb[i + 1]; ++e) {                // file order within the frame
+            int ce;
+            if (e < e1 && (unsigned)(e - e0) < (unsigned)CW_EV_CACHE) {
+                ce = cls[e - e0];
+            } else {
+                const double cd = ev[(size_t)e * 4 + 1];
+                ce = cd >= 0.0 && cd < (double)C ? (int)cd : -1;
+            }
+            if (ce == c) {
+                if (cnt < 3) first[cnt] = (int)ev_lo + e;
+                last = (int)ev_lo + e;
+                ++cnt;
+            }
+        }
+        int *q = pick + p * 4;
+        q[0] = adpit ? cnt : last;
+        q[1] = first[0];
+        q[2] = first[1];
+        q[3] = first[2];
+    }
+    __syncthreads();
+    // every position r of a frame's row is owned by one thread, its class / component / track slot worked out once (no
+    // division per element); the frames of the tile are written one after the other, each row by consecutive threads
+    const size_t slot = comb < 0 ? 0 : (size_t)comb + 1;
+    for (int r = tid; r < g.row; r += CW_THREADS) {
+        int c, k, s = 0;                       // class, component (-1: the activity 1.0, else x / y / z), ADPIT track slot
+        if (adpit) {
+            s = r / (4 * C);
+            const int rr = r - s * 4 * C;
+            k = rr / C - 1;
+            c = rr - (k + 1) * C;
+        } else {
+            const int part = r / C;
+            c = r - part * C;
+            k = g.format == ADYOLO_CORPUS_SEDDOA ? part - 1 : part;
+        }
+        // ADPIT: slot 0 takes the class's event when it has one, slots 1-2 its two, slots 3-5 the first three of three or more
+        const int lo_cnt = s == 0 ? 1 : s <= 2 ? 2 : 3, hi_cnt = s == 0 ? 1 : s <= 2 ? 2 : 0x7fffffff;
+        const int j = s == 0 ? 0 : s <= 2 ? s - 1 : s - 3;
+        for (int i = 0; i < nf; ++i) {
+            const int *q = pick + (i * C + c) * 4;
+            const int e = adpit ? (q[0] >= lo_cnt && q[0] <= hi_cnt ? q[1 + j] : -1) : q[0];
+            dst[(size_t)i * g.row + r] =
+                e < 0 ? 0.f : k < 0 ? 1.f : xyz[((size_t)e * ADYOLO_CORPUS_XYZ_SLOTS + slot) * 3 + k];
+        }
+    }
+}
+
 static int corpus_rot(const float *rot_host, CorpusRot &rot) {
     if (!rot_host) return ADYOLO_EINVAL;
     for (int c = 0; c < 16; ++c)
@@ -268,4 +380,29 @@ extern "C" int adyolo_corpus_yolo_labels(const double *events, long n_events, co
     hipLaunchKernelGGL(corpus_rows_kernel, dim3((unsigned)gx), dim3(256), 0, st, events, items, grid_bounds, rot, g, ws, count,
                        target);
     return check_launch("corpus_rows");
+}
+
+extern "C" int adyolo_corpus_classwise_labels(const double *events, const float *xyz, long n_events, const int64_t *items, int B,
+                                              int max_events, int n_label_frames, int n_classes, int format, float *target,
+                                              int *status, void *stream) {
+    ADYOLO_REQUIRE(events && xyz && items && target && status, ADYOLO_EINVAL, "corpus_classwise_labels: null pointer");
+    ADYOLO_REQUIRE(B > 0 && B < 65536 && max_events >= 0 && n_events >= 0 && n_events < (1L << 31) && n_label_frames > 0 &&
+                       n_classes > 0,
+                   ADYOLO_EINVAL, "corpus_classwise_labels: bad shape B=%d max_events=%d n_events=%ld n_label_frames=%d C=%d", B,
+                   max_events, n_events, n_label_frames, n_classes);
+    ADYOLO_REQUIRE(format == ADYOLO_CORPUS_SEDDOA || format == ADYOLO_CORPUS_ACCDOA || format == ADYOLO_CORPUS_ADPIT,
+                   ADYOLO_EINVAL, "corpus_classwise_labels: unknown format %d", format);
+    ADYOLO_REQUIRE(n_classes <= CW_MAX_CLASSES, ADYOLO_ENOSUP, "corpus_classwise_labels: %d classes (at most %d)", n_classes,
+                   CW_MAX_CLASSES);
+    ADYOLO_REQUIRE(((uintptr_t)events & 7) == 0 && ((uintptr_t)items & 7) == 0 && ((uintptr_t)xyz & 3) == 0 &&
+                       ((uintptr_t)target & 3) == 0 && ((uintptr_t)status & 3) == 0,
+                   ADYOLO_EINVAL, "corpus_classwise_labels: misaligned buffers");
+    CorpusClasswiseGeom g;
+    g.B = B; g.max_events = max_events; g.n_label_frames = n_label_frames; g.C = n_classes; g.format = format;
+    g.row = (format == ADYOLO_CORPUS_SEDDOA ? 4 : format == ADYOLO_CORPUS_ACCDOA ? 3 : 24) * n_classes;
+    g.n_events = n_events;
+    const size_t lds = (size_t)CW_FRAMES * n_classes * 4 * sizeof(int);
+    hipLaunchKernelGGL(corpus_classwise_kernel, dim3((unsigned)cdiv(n_label_frames, CW_FRAMES), (unsigned)B), dim3(CW_THREADS), lds,
+                       as_stream(stream), events, xyz, items, g, target, status);
+    return check_launch("corpus_classwise_labels");
 }

@@ -162,7 +162,9 @@ class MicFeatureExtractor:
 
     scaler: {'MEL': {'mean','std'} (1,64,4), 'GCC': {'mean','std'} (1,64,6)} or None.
     ``__call__(audio (B, n, 4))`` -> (B, T, 64, 32) channels-last float32 (features 0-9, zeros above: the 32-channel pixel the
-    Winograd stem convolution consumes) or, with ``channels_last=False``, (B, 10, T, 64).
+    Winograd stem convolution consumes) or, with ``channels_last=False``, (B, 10, T, 64).  ``channels_last8`` is accepted as an
+    alias of ``channels_last`` (the keyword ``TrainStep`` passes to every feature extractor), so the extractor plugs into
+    ``TrainStep`` directly, SpecAug tables included.
 
     ``spec_ranges`` (int32 (B, 2, 4), host or device): SpecAug as in ``FeatureExtractor``, one mask per feature family -- group 0
     the log-mel channels 0-3, group 1 the GCC-PHAT channels 4-9 (with the zero channels 10-11 of its quads).  The reference has no
@@ -183,7 +185,9 @@ class MicFeatureExtractor:
         self.gcc_mean = torch.tensor(np.asarray(mean, dtype=np.float32), device=dev).contiguous()
         self.gcc_rstd = torch.tensor(np.asarray(1.0 / std, dtype=np.float32), device=dev).contiguous()
 
-    def __call__(self, audio, channels_last=True, spec_ranges=None):
+    def __call__(self, audio, channels_last=True, spec_ranges=None, channels_last8=None):
+        if channels_last8 is not None:
+            channels_last = bool(channels_last8)
         if not audio.is_cuda or audio.dtype != torch.float32 or not audio.is_contiguous():
             raise _lib.AdyoloHipError("MicFeatureExtractor needs contiguous float32 audio (B, n_samples, 4) on the GPU")
         if spec_ranges is not None and not channels_last:

@@ -1362,7 +1362,10 @@ def pcm16_to_f32(pcm, out=None):
 
 
 CORPUS_ITEM_WORDS = 8                                     # ADYOLO_CORPUS_ITEM_WORDS / _ROT_WORDS in adyolo_hip.h
-CORPUS_STATUS = ((1, "more AD-YOLO rows than the target capacity"), (2, "an item outside the corpus"))
+CORPUS_STATUS = ((1, "more AD-YOLO rows than the target capacity"), (2, "an item outside the corpus"),
+                 (4, "an event class outside [0, nb_classes)"))
+CORPUS_XYZ_SLOTS = 17                                     # ADYOLO_CORPUS_XYZ_SLOTS: no rotation + the 16 FOA combinations
+CORPUS_FORMATS = {"seddoa": 0, "masked-seddoa": 0, "accdoa": 1, "adpit": 2}     # ADYOLO_CORPUS_SEDDOA / _ACCDOA / _ADPIT
 
 
 def corpus_rot_table(combinations):
@@ -1425,6 +1428,43 @@ def corpus_yolo_labels(events, items, max_events, n_label_frames, bounds, grid, 
     n_ev = events.shape[0]
     _c("adyolo_corpus_yolo_labels", _p(events), n_ev, _p(items), b, int(max_events), int(n_label_frames), _p(bounds), gaz, gel,
        ctypes.cast(rot, ctypes.c_void_p), _p(ws), _p(target), target.shape[0], _p(count), _p(status), _stream())
+    return target
+
+
+def corpus_classwise_shape(loss, batch, n_label_frames, nb_classes):
+    """The dense target of ``datasets.ClasswiseLabelEncoder`` stacked over a batch: (B, T', 4C) seddoa / masked-seddoa,
+    (B, T', 3C) accdoa, (B, T', 6, 4, C) adpit."""
+    if loss not in CORPUS_FORMATS:
+        raise _lib.AdyoloHipError("corpus_classwise: loss %r is not one of %s" % (loss, sorted(CORPUS_FORMATS)))
+    b, t, c = int(batch), int(n_label_frames), int(nb_classes)
+    return {0: (b, t, 4 * c), 1: (b, t, 3 * c), 2: (b, t, 6, 4, c)}[CORPUS_FORMATS[loss]]
+
+
+def corpus_classwise_labels(events, items, xyz, max_events, n_label_frames, nb_classes, loss, target, status):
+    """The dense class-wise targets of a batch on the device (adyolo_hip.h ``adyolo_corpus_classwise_labels``): events float64
+    (E, 4) {frame, class, az, el}, items int64 (B, 8), xyz float32 (E, 17, 3) (``corpus.xyz_table``) -> target float32 of
+    ``corpus_classwise_shape(loss, B, n_label_frames, nb_classes)``, every element written.  status: int32 word the call ORs its
+    bits into.  No allocation, no sync."""
+    dev = items.device
+    _corpus_i64("corpus_classwise_labels: items", items, dev)
+    if not events.is_cuda or events.dtype != torch.float64 or not events.is_contiguous() or events.dim() != 2 \
+            or events.shape[1] != 4 or events.device != dev:
+        raise _lib.AdyoloHipError("corpus_classwise_labels: events must be a contiguous float64 tensor (E, 4) on %s" % dev)
+    n_ev = events.shape[0]
+    if xyz.dtype != torch.float32 or xyz.device != dev or not xyz.is_contiguous() \
+            or tuple(xyz.shape) != (n_ev, CORPUS_XYZ_SLOTS, 3):
+        raise _lib.AdyoloHipError("corpus_classwise_labels: xyz must be a contiguous float32 tensor (%d, %d, 3) on %s"
+                                  % (n_ev, CORPUS_XYZ_SLOTS, dev))
+    b = items.shape[0]
+    want = corpus_classwise_shape(loss, b, n_label_frames, nb_classes)
+    _chk(target)
+    if tuple(target.shape) != want or target.device != dev:
+        raise _lib.AdyoloHipError("corpus_classwise_labels: target %s on %s, expected %s on %s for %s"
+                                  % (tuple(target.shape), target.device, want, dev, loss))
+    if status.dtype != torch.int32 or status.device != dev or not status.is_contiguous() or status.numel() < 1:
+        raise _lib.AdyoloHipError("corpus_classwise_labels: status must be an int32 word on %s" % dev)
+    _c("adyolo_corpus_classwise_labels", _p(events), _p(xyz), n_ev, _p(items), b, int(max_events), int(n_label_frames),
+       int(nb_classes), CORPUS_FORMATS[loss], _p(target), _p(status), _stream())
     return target
 
 

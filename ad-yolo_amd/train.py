@@ -205,19 +205,20 @@ def train_one_epoch_audio(params: dict, dataloader, trainer, stager=None, rotate
 
 
 def train_one_epoch_corpus(params: dict, corpus, trainer):
-    """``train_one_epoch_audio`` on a ``corpus.DeviceCorpus``: batches of ``batch_size`` over ``corpus.get_filelist()`` in order,
-    each made on the device (gather + rotation of the audio, AD-YOLO rows into the fixed-capacity target) and handed with its
-    SpecAug tables to ``TrainStep.step``.  With ``trainer.graphs`` the two kernels write straight into the recorded step's input
-    buffers once it exists (eager launches before the replay, no copy).  The host draws of batch k+1 (rotation, SpecAug) happen
-    while step k runs, in the order the host path draws them.  Returns the mean loss with ONE device sync at the end, where the
-    corpus' status word is read too: a batch with more rows than the capacity (or an item outside the corpus) raises."""
+    """``train_one_epoch_audio`` on a ``corpus.DeviceCorpus`` or ``corpus.ClasswiseDeviceCorpus``: batches of ``batch_size`` over
+    ``corpus.get_filelist()`` in order, each made on the device (gather + rotation of the audio; AD-YOLO rows into the
+    fixed-capacity target, or the dense class-wise target) and handed with its SpecAug tables to ``TrainStep.step``.  With
+    ``trainer.graphs`` the kernels write straight into the recorded step's input buffers (of ``corpus.target_shape``) once it
+    exists (eager launches before the replay, no copy).  The host draws of batch k+1 (rotation, SpecAug) happen while step k
+    runs, in the order the host path draws them.  Returns the mean loss with ONE device sync at the end, where the corpus' status
+    word is read too: a batch with more rows than the capacity, an item outside the corpus or a class outside the model's
+    raises."""
     bs = int(params["train_config"]["batch_size"])
     files = corpus.get_filelist()
     starts = list(range(0, len(files), bs))
     if not starts:
         return 0.0
     graphs = trainer.graphs
-    target_like = torch.empty((corpus.cap, 7), dtype=torch.float32, device="meta")
     corpus.reset_status()
     total, n = None, 0
     nxt = corpus.draw(range(starts[0], min(len(files), starts[0] + bs)))
@@ -226,6 +227,7 @@ def train_one_epoch_corpus(params: dict, corpus, trainer):
         items, spec = drawn
         bufs = None
         if graphs is not None:
+            target_like = torch.empty(corpus.target_shape(items.shape[0]), dtype=torch.float32, device="meta")
             bufs = graphs.static_inputs((items.shape[0], corpus.n_samples, 4), target_like,
                                         None if spec is None else tuple(spec.shape))
         audio, target, spec_dev = corpus.launch(drawn, *(bufs or ()))

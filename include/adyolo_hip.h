@@ -567,8 +567,9 @@ int adyolo_ln_bwd(const float *dy, const float *x, const float *gamma, float *dx
 int adyolo_foa_rotate(const float *audio, float *out, const float *cfg, int B, long n_samples, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
- * Training batches from an HBM-resident corpus (csrc/corpus.hip, ad-yolo_amd/corpus.py DeviceCorpus), opt-in: the host half of
- * FoaDataset.__getitem__ + audio_collate_fn (src/datasets.py:93-184) on the device, from one small per-batch item table.
+ * Training batches from an HBM-resident corpus (csrc/corpus.hip, ad-yolo_amd/corpus.py DeviceCorpus / ClasswiseDeviceCorpus),
+ * opt-in: the host half of FoaDataset.__getitem__ + audio_collate_fn (src/datasets.py:93-184) on the device, from one small
+ * per-batch item table.
  *   items    DEVICE int64 [B][ADYOLO_CORPUS_ITEM_WORDS] = {sample offset into pcm (frames), frame offset of the label window on
  *            its recording's frame axis, first event of the window in `events`, number of events, FOA combination (0..15, or -1:
  *            no rotation -- labels are then not wrapped either), recording, 0, 0}
@@ -586,17 +587,37 @@ int adyolo_foa_rotate(const float *audio, float *out, const float *cfg, int B, l
  *   written (at most cap; more sets ADYOLO_CORPUS_OVERFLOW, the rows past cap are dropped), b = -1 in the others (the loss
  *   skips them); ws adyolo_corpus_yolo_labels_workspace_words(B, max_events) int32 words; max_events >= every item's event
  *   count (a larger count sets ADYOLO_CORPUS_BAD_ITEM and the item gets no rows).  Gaz, Gel <= 64, else ENOSUP.
+ * adyolo_corpus_classwise_labels: the dense SEDDOA / ACCDOA / ADPIT targets of the batch (augmentations.rotate_labels, then
+ *   datasets.ClasswiseLabelEncoder, stacked over the batch), every element of target written exactly once, zeros included:
+ *     format ADYOLO_CORPUS_SEDDOA  target [B][n_label_frames][4 C]        = [se, x, y, z], the last event of a class in a frame
+ *     format ADYOLO_CORPUS_ACCDOA  target [B][n_label_frames][3 C]        = se * [x, y, z], the same event
+ *     format ADYOLO_CORPUS_ADPIT   target [B][n_label_frames][6][4][C]    = {1, x, y, z} in slot 0 (one event of the class in
+ *                                  the frame), 1-2 (two) or 3-5 (three or more: the first three in file order)
+ *   C = n_classes.  events as above (only the frame and class columns are read; file order within a frame); xyz DEVICE float
+ *   [n_events][ADYOLO_CORPUS_XYZ_SLOTS][3]: each event's direction vector built on the host (corpus.xyz_table), slot 0 without
+ *   rotation (comb < 0), slot 1 + k under combination k.  Events whose relative frame is outside [0, n_label_frames) are
+ *   dropped; an event whose class is outside [0, C) is dropped and sets ADYOLO_CORPUS_BAD_CLASS; an item outside the corpus
+ *   (as for the rows, max_events included) gets an all-zero target and sets ADYOLO_CORPUS_BAD_ITEM.  No workspace, no
+ *   atomics on the target: capturable, and the target may be a recorded step's static buffer.  C <= 256, else ENOSUP.
  * ---------------------------------------------------------------------------------------------- */
 #define ADYOLO_CORPUS_ITEM_WORDS 8
 #define ADYOLO_CORPUS_ROT_WORDS  8
 #define ADYOLO_CORPUS_OVERFLOW   1   /* more rows than the target capacity */
 #define ADYOLO_CORPUS_BAD_ITEM   2   /* an item table entry outside the corpus */
+#define ADYOLO_CORPUS_BAD_CLASS  4   /* an event class outside [0, n_classes) */
+#define ADYOLO_CORPUS_XYZ_SLOTS  17  /* no rotation + the 16 FOA combinations */
+#define ADYOLO_CORPUS_SEDDOA     0
+#define ADYOLO_CORPUS_ACCDOA     1
+#define ADYOLO_CORPUS_ADPIT      2
 int  adyolo_corpus_gather(const int16_t *pcm, long n_total, const int64_t *items, int B, long n, const float *rot_host,
                           float *audio, int *status, void *stream);
 long adyolo_corpus_yolo_labels_workspace_words(int B, int max_events);
 int  adyolo_corpus_yolo_labels(const double *events, long n_events, const int64_t *items, int B, int max_events,
                                int n_label_frames, const double *grid_bounds, int Gaz, int Gel, const float *rot_host,
                                int *ws, float *target, long cap, int *count, int *status, void *stream);
+int  adyolo_corpus_classwise_labels(const double *events, const float *xyz, long n_events, const int64_t *items, int B,
+                                    int max_events, int n_label_frames, int n_classes, int format, float *target, int *status,
+                                    void *stream);
 
 /* K11 fused Adam over one flat parameter buffer (torch.optim.Adam at src/train.py:31,55; no amsgrad) */
 int adyolo_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, long n,

@@ -6,6 +6,7 @@ batch size (16 and 64 x 20 s, hipGraph-replayed steps):
 
   load          load_chunked_split (verify="sample") + DeviceCorpus upload: seconds and bytes held on the device
   batch         gather + label kernels of one batch (DeviceCorpus.launch), device time per batch (events around --iters batches)
+  labels        (class-wise losses) the label kernel alone on an uploaded item table, device time per batch
   replay        the recorded train step alone on fixed inputs (the rate a loader has to keep up with)
   corpus        train_one_epoch_corpus
   host          train_one_epoch_audio over DataLoader(FoaDataset, num_workers=--workers, audio_collate_fn)
@@ -15,7 +16,13 @@ rate the GPU is fed at), and the host CPU seconds per step (resource.getrusage o
 on the GPU included -- and of its reaped children, i.e. the DataLoader workers).  Each path runs one warm epoch first (eager
 step, capture; page cache).
 
+--loss seddoa | accdoa | adpit trains that class-wise model from a ClasswiseDeviceCorpus instead; --mic writes the split as
+``mic_dev`` and trains on the MIC feature set (MicFeatureExtractor: BASELINE config 5 with --loss adpit); --classes sets the event
+classes of the split and the model (12 by default: the ACCDOA / ADPIT heads' GEMMs need 3C and 9C in multiples of 4);
+--labels-only stops after load, batch and labels (no model: any class count, e.g. the 13 of DCASE 2023).
+
   python tools/corpus_bench.py [--dir /tmp/adyolo_corpus] [--batches 16,64] [--steps 32,8] [--workers 16] [--json out.json]
+                               [--loss adyolo|seddoa|accdoa|adpit] [--mic] [--classes C] [--labels-only]
 """
 import argparse
 import csv
@@ -37,12 +44,12 @@ import torch  # noqa: E402
 SR, WINDOW_S, STRIDE_S, REC_S = 24000, 20, 1, 60
 
 
-def write_split(root, n_recordings, seed=0):
+def write_split(root, n_recordings, seed=0, n_classes=12, audio_dir="foa_dev"):
     """n_recordings x 60 s, chunked as the reference's preprocess.chunk_instance cuts them (60 s: no padding)."""
     from scipy.io import wavfile
     rs = np.random.RandomState(seed)
     sub = "dev-train-chunked_%ds_%ds" % (WINDOW_S, STRIDE_S)
-    wdir, cdir = os.path.join(root, "foa_dev", sub), os.path.join(root, "metadata_dev", sub)
+    wdir, cdir = os.path.join(root, audio_dir, sub), os.path.join(root, "metadata_dev", sub)
     os.makedirs(wdir, exist_ok=True)
     os.makedirs(cdir, exist_ok=True)
     win, st, wf, sf = SR * WINDOW_S, SR * STRIDE_S, WINDOW_S * 10, STRIDE_S * 10
@@ -53,7 +60,7 @@ def write_split(root, n_recordings, seed=0):
         for f in range(REC_S * 10):
             k = rs.choice(3, p=[0.35, 0.45, 0.2])
             if k:
-                label[f] = [[int(rs.randint(12)), s, round(float(rs.uniform(-180, 180)), 1), round(float(rs.uniform(-60, 60)), 1)]
+                label[f] = [[int(rs.randint(n_classes)), s, round(float(rs.uniform(-180, 180)), 1), round(float(rs.uniform(-60, 60)), 1)]
                             for s in range(k)]
         for i in range((len(audio) - win) // st + 1):
             name = "fold1_room%d_mix%03d_chunk%03d" % (r % 10, r, i + 1)
@@ -67,11 +74,14 @@ def write_split(root, n_recordings, seed=0):
     return nbytes
 
 
-def params(root, batch, steps):
+def params(root, batch, steps, loss="adyolo", mic=False, n_classes=12):
     from __graft_entry__ import _params
-    prm = _params()
+    prm = _params(nb_classes=n_classes)
+    prm["args"]["loss"] = loss
     prm["data_config"].update({"data_pth": root, "chunk_window_s": WINDOW_S, "chunk_stride_s": STRIDE_S, "sr": SR,
                                "label_hop_len_s": 0.1})
+    if mic:
+        prm["data_config"]["audio_format"] = "mic"
     prm["train_config"].update({"batch_size": batch, "nb_iters": steps})
     prm["aug_config"] = {"rotation_augment": True, "spec_augment": True, "spec_augment_thresh": 0.5,
                          "spec_augment_time_mask_param": 40, "spec_augment_freq_mask_param": 40}
@@ -79,12 +89,14 @@ def params(root, batch, steps):
 
 
 def trainer(prm):
-    from adyolo_amd.features import FeatureExtractor
+    from adyolo_amd.features import FeatureExtractor, MicFeatureExtractor
     from adyolo_amd.train import TrainStep
     from adyolo_amd.wrapper import WrapperCriterion, WrapperModel
     torch.manual_seed(0)
-    model = WrapperModel((1, 7, SR * WINDOW_S // 600, 64), (), prm).to("cuda:0")
-    tr = TrainStep(model, WrapperCriterion(prm), FeatureExtractor(None, "cuda:0"), prm, graph=True)
+    mic = prm["data_config"].get("audio_format") == "mic"
+    model = WrapperModel((1, 10 if mic else 7, SR * WINDOW_S // 600, 64), (), prm).to("cuda:0")
+    fx = MicFeatureExtractor(None, "cuda:0") if mic else FeatureExtractor(None, "cuda:0")
+    tr = TrainStep(model, WrapperCriterion(prm), fx, prm, graph=True)
     tr.stamps = []
     inner = tr.step
 
@@ -116,21 +128,28 @@ def timed_epoch(run, tr):
             "cpu_s_per_step": round((c1 - c0) / max(n, 1), 4)}
 
 
-def bench_batch(root, batch, steps, workers, iters):
-    from adyolo_amd.corpus import DeviceCorpus, load_chunked_split
+def bench_batch(root, batch, steps, workers, iters, loss="adyolo", mic=False, n_classes=12, labels_only=False):
+    from adyolo_amd import ops
+    from adyolo_amd.corpus import ClasswiseDeviceCorpus, DeviceCorpus, load_chunked_split
     from adyolo_amd.datasets import FoaDataset, audio_collate_fn
     from adyolo_amd.train import train_one_epoch_audio, train_one_epoch_corpus
-    prm = params(root, batch, steps)
+    prm = params(root, batch, steps, loss, mic, n_classes)
     out = {"batch": batch, "steps_per_epoch": steps}
+    if loss != "adyolo" or mic:
+        out.update(loss=loss, mic=mic, classes=n_classes)
     t0 = time.perf_counter()
     hc = load_chunked_split(prm, verify="sample")
     t1 = time.perf_counter()
     random.seed(0)
-    corpus = DeviceCorpus(hc, prm, "cuda:0")
+    corpus = DeviceCorpus(hc, prm, "cuda:0") if loss == "adyolo" else ClasswiseDeviceCorpus(hc, prm, "cuda:0")
     torch.cuda.synchronize()
     t2 = time.perf_counter()
     out["load"] = {"host_s": round(t1 - t0, 3), "upload_s": round(t2 - t1, 3), "device_bytes": corpus.nbytes(),
-                   "files": len(hc.total_filelist), "recordings": len(hc.rec_names), "cap_rows": corpus.cap}
+                   "files": len(hc.total_filelist), "recordings": len(hc.rec_names)}
+    if loss == "adyolo":
+        out["load"]["cap_rows"] = corpus.cap
+    else:
+        out["load"]["target_shape"] = list(corpus.target_shape(batch))
     # gather + labels of one batch
     drawn = [corpus.draw(range(i * batch % len(corpus), i * batch % len(corpus) + batch)) for i in range(4)]
     for d in drawn:
@@ -143,6 +162,34 @@ def bench_batch(root, batch, steps, workers, iters):
     e1.record()
     torch.cuda.synchronize()
     out["batch_ms"] = round(e0.elapsed_time(e1) / iters, 4)
+    if loss != "adyolo":
+        # the label kernel alone, on item tables already on the device: --iters launches recorded in one hipGraph and
+        # replayed, so that the device time is measured rather than the rate Python issues launches at
+        dev_items = [torch.from_numpy(d[0]).to("cuda:0") for d in drawn]
+        target = torch.empty(corpus.target_shape(batch), dtype=torch.float32, device="cuda:0")
+
+        def labels(i):
+            ops.corpus_classwise_labels(corpus.events, dev_items[i % 4], corpus.xyz, corpus.max_events, corpus.n_label_frames,
+                                        corpus.nb_classes, loss, target, corpus.status)
+        for i in range(4):
+            labels(i)
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            for i in range(iters):
+                labels(i)
+        graph.replay()
+        torch.cuda.synchronize()
+        e0.record()
+        graph.replay()
+        e1.record()
+        torch.cuda.synchronize()
+        out["labels_ms"] = round(e0.elapsed_time(e1) / iters, 4)
+        out["target_mb"] = round(target.numel() * 4 / 2 ** 20, 2)
+        del graph, target
+        corpus.check()
+    if labels_only:
+        return out
 
     tc = trainer(prm)
     for ep in range(2):
@@ -190,7 +237,12 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--keep", action="store_true", help="keep the split on disk afterwards")
     ap.add_argument("--json")
+    ap.add_argument("--loss", default="adyolo", choices=["adyolo", "seddoa", "accdoa", "adpit"])
+    ap.add_argument("--mic", action="store_true", help="a mic_dev split and the MIC feature set")
+    ap.add_argument("--classes", type=int, default=12, help="event classes of the split and the model")
+    ap.add_argument("--labels-only", action="store_true", help="load, batch and labels timings only (no training epochs)")
     a = ap.parse_args()
+    n_classes = a.classes
     assert torch.cuda.is_available(), "corpus_bench needs the GPU"
     import adyolo_amd  # noqa: F401
     batches = [int(b) for b in a.batches.split(",")]
@@ -200,13 +252,13 @@ def main():
     n_rec = -(-files // (REC_S - WINDOW_S + 1))
     shutil.rmtree(a.dir, ignore_errors=True)
     t0 = time.perf_counter()
-    nbytes = write_split(a.dir, n_rec)
+    nbytes = write_split(a.dir, n_rec, n_classes=n_classes, audio_dir="mic_dev" if a.mic else "foa_dev")
     res = {"split": {"recordings": n_rec, "wav_bytes": nbytes, "write_s": round(time.perf_counter() - t0, 2)},
            "cpus": len(os.sched_getaffinity(0))}
     print(json.dumps(res), flush=True)
     try:
         for b, s in zip(batches, steps):
-            r = bench_batch(a.dir, b, s, a.workers, a.iters)
+            r = bench_batch(a.dir, b, s, a.workers, a.iters, a.loss, a.mic, n_classes, a.labels_only)
             res["b%d" % b] = r
             print(json.dumps(r), flush=True)
     finally:

@@ -34,8 +34,9 @@ SIGNATURES = {
     "adyolo_wino4_pack_many": (I, [P, I, I, I, P]),
     "adyolo_wino4_tiles": (I, [I] * 3),
     "adyolo_wino4_fwd": (I, [P] * 13 + [I] * 7 + [P]),
+    "adyolo_wino4_fwd_form": (I, [I] * 3),
     "adyolo_wino4_last_form": (I, []),
-    "adyolo_reload_switches": (I, []),
+    "adyolo_set_switches": (I, [I]),
     "adyolo_wino4_wgrad_slabs": (I, [I] * 5),
     "adyolo_wino4_wgrad": (I, [P] * 7 + [I] * 6 + [P]),
     "adyolo_wino_wgrad_slabs": (I, [I] * 5),
@@ -137,6 +138,7 @@ SIGNATURES = {
 }
 
 _lib = None
+ON_LOAD = []        # called with the library right after it is loaded: ``ops`` registers the push of its switch table here
 
 
 class AdyoloHipError(RuntimeError):
@@ -163,9 +165,11 @@ def load():
         fn.restype = res
         fn.argtypes = args
     ver = lib.adyolo_abi_version()
-    if ver != 1:
-        raise AdyoloHipError("libadyolo_hip.so ABI version %d != 1" % ver)
+    if ver != 2:
+        raise AdyoloHipError("libadyolo_hip.so ABI version %d != 2" % ver)
     _lib = lib
+    for hook in ON_LOAD:
+        hook(lib)
     return lib
 
 

@@ -655,20 +655,32 @@ using namespace adyolo;
 
 static inline int wino4_tc(int W) { return W >= 32 ? 8 : 4; }
 static int g_wino4_last_form = 0;          // 1: the last adyolo_wino4_fwd launched the one-patch kernel, 2: the persistent one
+static int g_w4_switches = 3;              // bit 0: persistent kernel, bit 1: narrow patches (adyolo_set_switches; the host owns them)
 
 extern "C" int adyolo_wino4_last_form(void) { return g_wino4_last_form; }
+extern "C" int adyolo_set_switches(int bits) { return g_w4_switches = bits & 3; }
 
-// The two environment switches adyolo_wino4_fwd consults, read ONCE (first launch) and again only by adyolo_reload_switches()
-// (ops.reload_thresholds(): the host code and the library move together; round 5 ADVICE -- they used to be three getenv calls
-// in every launch).  bit 0: persistent kernel, bit 1: narrow patches; -1: not read yet.
-static int g_w4_switches = -1;
-static int w4_read_switches() {
-    const char *pe = getenv("ADYOLO_W4_PERSIST"), *ne = getenv("ADYOLO_W4_NARROW");
-    g_w4_switches = ((pe && pe[0] == '0') ? 0 : 1) | ((ne && ne[0] == '0') ? 0 : 2);
-    return g_w4_switches;
+// the launcher of one operand combination of the persistent kernel, nullptr when it is not built (wino4p_launch.hpp: the list)
+static void (*wino4p_launcher(int epi))(const w4::W4Launch &) {
+    switch (epi) {
+#define ADYOLO_W4P_CASE(E) case E: return &w4::launch_wino4p<E>;
+        ADYOLO_W4P_BUILT(ADYOLO_W4P_CASE)
+#undef ADYOLO_W4P_CASE
+        default: return nullptr;
+    }
 }
-static inline int w4_switches() { return g_w4_switches >= 0 ? g_w4_switches : w4_read_switches(); }
-extern "C" int adyolo_reload_switches(void) { return w4_read_switches(); }
+
+// THE decision which kernel adyolo_wino4_fwd launches: 2 persistent, 1 one-patch, 0 none (ADYOLO_ENOSUP).  The persistent form
+// (round 5, wino4p.hpp: one workgroup per CU walks the patches of its XCD slot) needs the XCD dealing (1, 2, 4 or 8 channel blocks),
+// masks given as bits and one of the operand combinations it is instantiated for (none has a bias); with 32-channel output blocks
+// (nb == 1) there is no other F(4x4) kernel.
+extern "C" int adyolo_wino4_fwd_form(int Cout, int operands, int mask_bits) {
+    if (Cout <= 0 || Cout % 32) return 0;
+    const int nb = Cout % 64 == 0 ? 2 : 1, ncb = Cout / (32 * nb);
+    const bool bits_ok = (!(operands & ADYOLO_W4_ADDEND_MASK) || (mask_bits & 1)) && (!(operands & ADYOLO_W4_STAT_MASK) || (mask_bits & 2));
+    if (ncb <= 8 && 8 % ncb == 0 && bits_ok && (g_w4_switches & 1) && wino4p_launcher(operands)) return 2;
+    return nb == 2 ? 1 : 0;
+}
 
 extern "C" int adyolo_wino4_tiles(int N, int H, int W) {
     if (N <= 0 || H <= 0 || W <= 0) return ADYOLO_EINVAL;
@@ -722,12 +734,12 @@ extern "C" int adyolo_wino4_fwd(const float *x, const float *u, const float *bia
                    "wino4_fwd: stat_aux needs stats, stat_mean and stat_invstd");
     ADYOLO_REQUIRE(!stat_mask || stats, ADYOLO_EINVAL, "wino4_fwd: stat_mask needs stats");
     const int ncb = Cout / (32 * nb);
+    const int operands = (stats ? ADYOLO_W4_STATS : 0) | (addend ? ADYOLO_W4_ADDEND : 0) | (addend_mask ? ADYOLO_W4_ADDEND_MASK : 0) |
+                         (stat_aux ? ADYOLO_W4_STAT_AUX : 0) | (stat_mask ? ADYOLO_W4_STAT_MASK : 0) | (bias ? ADYOLO_W4_BIAS : 0);
     // Narrow maps (W <= 8: the middle stages of the ResNet-Conformer, 800 frames x 4 or 8 bins): plain launches take patches ONE
     // or TWO tiles wide (128 x 4 / 64 x 8 pixels) on the persistent kernel instead of padding a 16-pixel-wide patch 4 or 2 times
     // over (ADYOLO_W4_NARROW=0: the 16-wide patch)
-    const int sw = w4_switches();
-    const bool narrow = W <= 8 && !stats && !addend && !addend_mask && !stat_aux && !stat_mask && !bias && !in_scale && nb == 2 &&
-                        ncb <= 8 && 8 % ncb == 0 && (sw & 3) == 3;
+    const bool narrow = W <= 8 && !operands && !in_scale && nb == 2 && ncb <= 8 && 8 % ncb == 0 && g_w4_switches == 3;
     const int tc = narrow ? (W <= 4 ? 1 : 2) : wino4_tc(W), tr = 32 / tc;
     const int patchesW = cdiv(W, 4 * tc), patchesH = cdiv(H, 4 * tr);
     const int nsp = N * patchesH * patchesW;
@@ -737,12 +749,12 @@ extern "C" int adyolo_wino4_fwd(const float *x, const float *u, const float *bia
         blocks = cdiv(nsp, xcd_div) * 8;
     }
     hipStream_t st = as_stream(stream);
-    // Persistent form (round 5, wino4p.hpp): one workgroup per CU walks the patches of its XCD slot.  Needs the XCD dealing
-    // (Cout / 64 in {1, 2, 4, 8}), no bias, masks given as bits, and one of the operand combinations it is instantiated for (the
-    // ones the SE-ResNet block launches); everything else, and ADYOLO_W4_PERSIST=0, takes the one-patch-per-workgroup kernel below.
-    const int epi = (stats ? 1 : 0) | (addend ? 2 : 0) | (addend_mask ? 4 : 0) | (stat_aux ? 8 : 0) | (stat_mask ? 16 : 0);
-    const bool bits_ok = (!addend_mask || (mask_bits & 1)) && (!stat_mask || (mask_bits & 2));
-    if (xcd_div > 0 && bits_ok && !bias && (sw & 1) && (epi == 0 || epi == 1 || epi == 2 || epi == 9 || epi == 15 || epi == 27 || epi == 31)) {
+    const int form = adyolo_wino4_fwd_form(Cout, operands, mask_bits);
+    ADYOLO_REQUIRE(form, ADYOLO_ENOSUP,
+                   "wino4_fwd: Cout=%d (a multiple of 32 but not of 64) needs the persistent kernel: no bias, masks as bits, Cout / 32 in "
+                   "{1, 2, 4, 8}, operand combination %d not built", Cout, operands);
+    g_wino4_last_form = form;
+    if (form == 2) {
         static int ncus = 0;
         if (ncus == 0) {
             int dev = 0, v = 0;
@@ -755,22 +767,9 @@ extern "C" int adyolo_wino4_fwd(const float *x, const float *u, const float *bia
         const int slots = njs < ncus / 8 ? njs : ncus / 8;
         w4::W4Launch a = {x, u, bias, addend, addend_mask, in_scale, in_shift, y, stats, stat_aux, stat_mean, stat_invstd, stat_mask,
                           H, W, Cin, Cout, patchesW, patchesH, nsp, ncb, xcd_div, relu, mask_bits, tc, slots * 8, nb, st};
-        g_wino4_last_form = 2;
-        switch (epi) {
-            case 0: w4::launch_wino4p<0>(a); break;
-            case 1: w4::launch_wino4p<1>(a); break;
-            case 2: w4::launch_wino4p<2>(a); break;
-            case 9: w4::launch_wino4p<9>(a); break;
-            case 15: w4::launch_wino4p<15>(a); break;
-            case 27: w4::launch_wino4p<27>(a); break;
-            default: w4::launch_wino4p<31>(a); break;
-        }
+        wino4p_launcher(operands)(a);
         return check_launch("wino4_fwd (persistent)");
     }
-    ADYOLO_REQUIRE(nb == 2, ADYOLO_ENOSUP,
-                   "wino4_fwd: Cout=%d (a multiple of 32 but not of 64) needs the persistent kernel: no bias, masks as bits, Cout / 32 in "
-                   "{1, 2, 4, 8}, operand combination %d not built", Cout, epi);
-    g_wino4_last_form = 1;
 #define ADYOLO_WINO4_FWD(TC_, AFF_)                                                                                    \
     hipLaunchKernelGGL((w4::wino4_fwd_kernel<TC_, AFF_>), dim3((unsigned)blocks), dim3(256), 0, st, x, u, bias, addend,    \
                        addend_mask, in_scale, in_shift, y, stats, stat_aux, stat_mean, stat_invstd, stat_mask, H, W, Cin, \

@@ -163,8 +163,9 @@ def conv_algo():
 # Dispatch switches of the 3x3 convolutions, read from the environment ONCE -- at import, and again by ``reload_thresholds()``
 # (tests and A/B tools that move one call it; README "Switches") -- into ONE table that every launch consults: the numeric
 # thresholds AND the on / off switches (round 5 ADVICE: ADYOLO_W4_PERSIST / _NARROW / ADYOLO_WINO1D used to be read per launch,
-# three getenv calls inside every adyolo_wino4_fwd, while the thresholds were frozen).  The library keeps its own copy of the two
-# switches it consults (csrc/wino4.hip, read at its first launch), refreshed by the same call.  ADYOLO_CONV_ALGO stays a
+# three getenv calls inside every adyolo_wino4_fwd, while the thresholds were frozen).  The library reads no environment: the two
+# switches it consults are pushed from this table (``_push_switches``: when the library is loaded and on every reload), so host
+# and library cannot differ (round 6 ADVICE: they used to read the environment at different moments).  ADYOLO_CONV_ALGO stays a
 # per-call read (``conv_algo``): it selects the algorithm, is validated where it is read and is part of the graph stamp on its own.
 W4_THRESHOLDS = {}
 _THRESHOLD_KEYS = ("min_k", "min_k_addend", "min_wgs", "min_wgrad_work", "min_k_32")
@@ -195,9 +196,16 @@ def reload_thresholds():
                          narrow=env("ADYOLO_W4_NARROW", "1") != "0",
                          wino1d=env("ADYOLO_WINO1D", "1") != "0",
                          wgrad_algo=(env("ADYOLO_WGRAD_ALGO") or "").lower() or None)
-    if _lib.loaded():                                  # (not loaded yet: the library reads the environment at its first launch)
-        _lib.load().adyolo_reload_switches()
+    if _lib.loaded():                                  # (not loaded yet: ``_lib.load()`` pushes them, ``_lib.ON_LOAD``)
+        _push_switches(_lib.load())
     return {k: W4_THRESHOLDS[k] for k in _THRESHOLD_KEYS}
+
+
+def _push_switches(lib):
+    lib.adyolo_set_switches((1 if W4_THRESHOLDS["persist"] else 0) | (2 if W4_THRESHOLDS["narrow"] else 0))
+
+
+_lib.ON_LOAD.append(_push_switches)
 
 
 def switch_table():
@@ -217,9 +225,6 @@ reload_thresholds()
 # When set to a dict, ``conv3x3`` counts its launches in it: key = (kernel name, Cin, Cout, operand bits) -- the table bench.py prints as
 # ``dispatch`` and tests/test_gpu_parity_scale.py asserts at the bench shape.
 DISPATCH_LOG = None
-
-
-W4P_EPIS = (0, 1, 2, 9, 15, 27, 31)            # operand combinations the persistent F(4x4) kernel is built for (csrc/wino4p_launch.hpp)
 
 
 def w4_narrow_ok(cin, cout):
@@ -289,9 +294,9 @@ class DualPack:
 
     def pick(self, n, h, w, cout, addend=False, persistent_ok=True):
         """addend: the launch adds a tensor in its epilogue (the data-gradient of a block's first convolution); until round 5 the
-        F(2x2) kernel was the faster one there below 128 channels (ADYOLO_W4_MIN_K_ADDEND, now 32: no effect by default).  persistent_ok: the launch's
-        operand combination has a persistent form (``W4P_EPIS``, no bias, masks as bits) -- with 32-channel output blocks
-        (cout % 64 != 0) there is no other F(4x4) kernel."""
+        F(2x2) kernel was the faster one there below 128 channels (ADYOLO_W4_MIN_K_ADDEND, now 32: no effect by default).  persistent_ok: the
+        library takes the persistent form for the launch's operands (``adyolo_wino4_fwd_form`` == 2, asked by ``conv3x3``) -- with
+        32-channel output blocks (cout % 64 != 0) there is no other F(4x4) kernel."""
         if cout % 64 and not (persistent_ok and W4_THRESHOLDS["persist"]):
             return self.f2
         wgs = _lib.load().adyolo_wino4_tiles(n, h, w) * ((cout + 63) // 64)
@@ -357,6 +362,13 @@ class WinoPackSet:
         return self.packs[i]
 
 
+# first axis of the pack (transform points of a Winograd form; 0: the direct pack, rank 3) -> entry point, its patch count, kernel name
+_CONV3X3_FORMS = {36: ("adyolo_wino4_fwd", "adyolo_wino4_tiles", None),                     # (named by the library's form: below)
+                  16: ("adyolo_wino_fwd", "adyolo_wino_tiles", "wino_fwd_kernel"),
+                  0: ("adyolo_conv3x3_fwd", "adyolo_conv3x3_tiles", "conv3x3_fwd_kernel")}
+_W4_KERNELS = {1: "wino4_fwd_kernel", 2: "wino4p_fwd_kernel"}                             # by ``adyolo_wino4_fwd_form``
+
+
 def conv3x3(x, wpk, cout, bias=None, addend=None, relu=False, addend_mask=None, in_affine=None, want_stats=False,
             stat_bn=None, stat_mask=None):
     """x [N][H][W][Cin] -> [N][H][W][cout];  wpk from ``pack_w3x3`` (direct [cout][9][Cin] or Winograd, rank 4).
@@ -373,39 +385,29 @@ def conv3x3(x, wpk, cout, bias=None, addend=None, relu=False, addend_mask=None, 
     if stat_mask is not None and stat_mask.dtype == torch.int64:
         mbits |= 2
     n, h, w, cin = x.shape
-    # operand combination, as the persistent F(4x4) kernel's EPI bits: 1 statistics, 2 addend, 4 addend mask, 8 stat_bn, 16 stat mask
+    # operands present, as the ADYOLO_W4_* bits of include/adyolo_hip.h: 1 statistics, 2 addend, 4 addend mask, 8 stat_bn, 16 stat mask
     epi = (1 if want_stats else 0) | (2 if addend is not None else 0) | (4 if addend_mask is not None else 0) | \
           (8 if stat_bn is not None else 0) | (16 if stat_mask is not None else 0)
-    p_ok = bias is None and epi in W4P_EPIS and (addend_mask is None or mbits & 1) and (stat_mask is None or mbits & 2)
+    lib = _lib.load()
+    # the library decides which F(4x4) kernel such a launch gets -- 2 persistent, 1 one-patch, 0 none -- and the host asks
+    w4_form = lib.adyolo_wino4_fwd_form(cout, epi | (32 if bias is not None else 0), mbits)
     if isinstance(wpk, DualPack):
-        wpk = wpk.pick(n, h, w, cout, addend is not None, p_ok)
-    elif wpk.dim() == 4 and wpk.shape[0] == 36 and cout % 64 and not p_ok:
+        wpk = wpk.pick(n, h, w, cout, addend is not None, w4_form == 2)
+    form = wpk.shape[0] if wpk.dim() == 4 else 0
+    if form == 36 and not w4_form:
         raise _lib.AdyoloHipError("conv3x3: a F(4x4) pack with %d output channels needs an operand combination the persistent kernel "
                                   "is built for (pack with ops.DualPack / WinoPackSet to fall back to F(2x2))" % cout)
+    fn, tiles_fn, name = _CONV3X3_FORMS[form]
     _chk(x, wpk, bias, addend, None if mbits & 1 else addend_mask, None if mbits & 2 else stat_mask)
-    wino = wpk.dim() == 4
-    wino4 = wino and wpk.shape[0] == 36
     y = _new(x, n, h, w, cout)
-    stats = None
-    if want_stats:
-        lib = _lib.load()
-        tiles = (lib.adyolo_wino4_tiles if wino4 else lib.adyolo_wino_tiles if wino else lib.adyolo_conv3x3_tiles)(n, h, w)
-        stats = _new(x, 2, tiles, cout)
+    stats = _new(x, 2, getattr(lib, tiles_fn)(n, h, w), cout) if want_stats else None
     sc, sh = in_affine if in_affine is not None else (None, None)
     sa, sm, si = stat_bn if stat_bn is not None else (None, None, None)
-    if wino4:
-        fn = "adyolo_wino4_fwd"
-    else:
-        fn = "adyolo_wino_fwd" if wino else "adyolo_conv3x3_fwd"
     _c(fn, _p(x), _p(wpk), _p(bias), _p(addend), _p(addend_mask),
        _p(sc), _p(sh), _p(y), _p(stats), _p(sa), _p(sm), _p(si), _p(stat_mask), n, h, w, cin, cout, int(relu), mbits,
        _stream())
     if DISPATCH_LOG is not None:
-        if wino4:
-            name = "wino4p_fwd_kernel" if _lib.load().adyolo_wino4_last_form() == 2 else "wino4_fwd_kernel"
-        else:
-            name = "wino_fwd_kernel" if wino else "conv3x3_fwd_kernel"
-        k = (name, cin, cout, epi)
+        k = (name or _W4_KERNELS[w4_form], cin, cout, epi)
         DISPATCH_LOG[k] = DISPATCH_LOG.get(k, 0) + 1
     return (y, stats) if want_stats else y
 
@@ -428,6 +430,9 @@ def wgrad_form(cin, cout, algo=None, shape=None):
     return "conv3x3_wgrad_kernel", 1.0
 
 
+_WGRAD_FORMS = {"wino4_wgrad_kernel": ("adyolo_wino4_wgrad", 36), "wino_wgrad_kernel": ("adyolo_wino_wgrad", 16)}   # entry point, points
+
+
 def conv3x3_wgrad(x, dy, cin_real, in_affine=None, algo=None, out=None):
     """x [N][H][W][Cin], dy [N][H][W][Cout] -> dw [Cout][cin_real][3][3] (x optionally seen through an affine).
 
@@ -441,20 +446,14 @@ def conv3x3_wgrad(x, dy, cin_real, in_affine=None, algo=None, out=None):
     if DISPATCH_LOG is not None:
         k = (form, cin, cout, 1 if in_affine is not None else 0)
         DISPATCH_LOG[k] = DISPATCH_LOG.get(k, 0) + 1
-    if form == "wino4_wgrad_kernel":
-        nslab = _lib.load().adyolo_wino4_wgrad_slabs(n, h, w, cin, cout)
-        slabs = _new(x, nslab, 36, cin, cout)
-        du = _new(x, 36, cin, cout)
-        _c("adyolo_wino4_wgrad", _p(x), _p(dy), _p(sc), _p(sh), _p(slabs), _p(du), _p(dw), n, h, w, cin, cin_real, cout, _stream())
-        return dw
-    if form == "wino_wgrad_kernel":
-        nslab = _lib.load().adyolo_wino_wgrad_slabs(n, h, w, cin, cout)
+    if form in _WGRAD_FORMS:
+        fn, points = _WGRAD_FORMS[form]
+        nslab = getattr(_lib.load(), fn + "_slabs")(n, h, w, cin, cout)
         if nslab <= 0:
-            raise _lib.AdyoloHipError("wino_wgrad_slabs rejected the shape")
-        slabs = _new(x, nslab, 16, cin, cout)
-        du = _new(x, 16, cin, cout)
-        _c("adyolo_wino_wgrad", _p(x), _p(dy), _p(sc), _p(sh), _p(slabs), _p(du), _p(dw), n, h, w, cin, cin_real, cout,
-           _stream())
+            raise _lib.AdyoloHipError("%s_slabs rejected the shape" % fn)
+        slabs = _new(x, nslab, points, cin, cout)
+        du = _new(x, points, cin, cout)
+        _c(fn, _p(x), _p(dy), _p(sc), _p(sh), _p(slabs), _p(du), _p(dw), n, h, w, cin, cin_real, cout, _stream())
         return dw
     nslab = _lib.load().adyolo_conv3x3_wgrad_slabs(n, h, w, cin, cout)
     if nslab <= 0:

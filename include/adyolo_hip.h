@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define ADYOLO_ABI_VERSION 1
+#define ADYOLO_ABI_VERSION 2
 #define ADYOLO_EINVAL (-1)   /* bad shape / alignment / null pointer */
 #define ADYOLO_ENOSUP (-2)   /* shape outside what the kernels are built for */
 
@@ -139,16 +139,29 @@ int adyolo_wino4_fwd(const float *x, const float *u, const float *bias, const fl
                      const float *in_scale, const float *in_shift, float *y, float *stats, const float *stat_aux,
                      const float *stat_mean, const float *stat_invstd, const float *stat_mask, int N, int H, int W, int Cin,
                      int Cout, int relu, int mask_bits, void *stream);
-/*      Round 5: adyolo_wino4_fwd launches the PERSISTENT form of the kernel (csrc/wino4p.hpp: one workgroup per CU walks the patches,
- *      the staging pipeline runs across patch boundaries, raw accumulators are exchanged and transformed on the reader side) for
- *      the operand combinations of the SE-ResNet block (no bias, masks as bits, Cout / 64 in {1, 2, 4, 8}) and the
- *      one-patch-per-workgroup kernel otherwise or with ADYOLO_W4_PERSIST=0; same results within fp32 rounding.
+/*      adyolo_wino4_fwd launches the PERSISTENT form of the kernel (csrc/wino4p.hpp: one workgroup per CU walks the patches, the
+ *      staging pipeline runs across patch boundaries, raw accumulators are exchanged and transformed on the reader side) or the
+ *      one-patch-per-workgroup kernel; same results within fp32 rounding.  adyolo_wino4_fwd_form() is the ONE place that decides
+ *      which (no device access): for Cout output channels, the operands present (the bits below) and mask_bits it returns
+ *      2 persistent: Cout / 64 when that is whole, else Cout / 32, in {1, 2, 4, 8}; every mask operand given as bits; the persistent switch
+ *        on, and an operand combination the kernel is built for (csrc/wino4p_launch.hpp: those of the SE-ResNet block; none has a bias);
+ *      1 one-patch: otherwise, when Cout is a multiple of 64;
+ *      0 none: adyolo_wino4_fwd returns ADYOLO_ENOSUP (so does a Cout that is not a positive multiple of 32).
+ *      adyolo_wino4_fwd asks the same function; N, H, W, Cin and in_scale only set the patch shape inside the form.
  *      adyolo_wino4_last_form(): which one the last call launched (1 one-patch, 2 persistent, 0 none yet) -- for reporting. */
+#define ADYOLO_W4_STATS 1        /* stats */
+#define ADYOLO_W4_ADDEND 2       /* addend */
+#define ADYOLO_W4_ADDEND_MASK 4  /* addend_mask (as bits: mask_bits & 1) */
+#define ADYOLO_W4_STAT_AUX 8     /* stat_aux, stat_mean, stat_invstd */
+#define ADYOLO_W4_STAT_MASK 16   /* stat_mask (as bits: mask_bits & 2) */
+#define ADYOLO_W4_BIAS 32        /* bias */
+int adyolo_wino4_fwd_form(int Cout, int operands, int mask_bits);
 int adyolo_wino4_last_form(void);
-/*      adyolo_reload_switches(): the library reads ADYOLO_W4_PERSIST / ADYOLO_W4_NARROW from the environment ONCE (at the first
- *      adyolo_wino4_fwd) and keeps them; this re-reads them (ops.reload_thresholds() calls it: one switch table for the host
- *      code and the library).  Returns the table as bits: 1 persistent kernel on, 2 narrow patches on. */
-int adyolo_reload_switches(void);
+/*      adyolo_set_switches(bits): the two on / off switches adyolo_wino4_fwd consults -- 1 persistent kernel, 2 patches one / two tiles
+ *      wide on maps up to 8 pixels wide (plain launches on the persistent kernel).  Both are on until it is called; the library
+ *      reads no environment variable (ops.reload_thresholds() pushes ADYOLO_W4_PERSIST / ADYOLO_W4_NARROW from the host's switch
+ *      table, at load and on every reload).  Returns the bits now in effect. */
+int adyolo_set_switches(int bits);
 /* K2w4w (round 5, csrc/wino4w.hip): the weight gradient in the Winograd F(4x4,3x3) domain,
  *      dw = G^T [ sum over 4x4 output tiles (B^T d B) (.) (A e A^T) ] G  (36 multiplies per 16 outputs and channel pair: 9/36 of the
  *      direct form's matrix FLOPs, 1.78x fewer MFMAs than adyolo_wino_wgrad; interpolation points of K2w4; error against a float64

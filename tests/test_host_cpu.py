@@ -26,7 +26,7 @@ def test_header_symbols_are_exported_and_bound():
     assert len(declared) >= 35
     assert declared == set(_lib.SIGNATURES), declared ^ set(_lib.SIGNATURES)
     lib = _lib.load()                       # raises if the library or a symbol is missing
-    assert lib.adyolo_abi_version() == 1
+    assert lib.adyolo_abi_version() == 2
     assert lib.adyolo_loss_workspace_words(4, 32, 5, 10) > 6 * 4 * 32 * 5
 
 
@@ -410,6 +410,7 @@ def test_dispatch_thresholds_and_parameter_epoch(monkeypatch):
     s0 = ops.switch_stamp()
     monkeypatch.setenv("ADYOLO_W4_PERSIST", "0")
     assert not ops.W4_THRESHOLDS["persist"] and ops.switch_stamp() != s0 and not ops.w4_narrow_ok(64, 64)
+    assert _lib.load().adyolo_wino4_fwd_form(64, 1, 0) == 1          # the library moved with the table, without any launch
     import os as _os
     _os.environ["ADYOLO_WINO1D"] = "0"                               # a direct write is NOT seen until reload_thresholds()
     assert ops.W4_THRESHOLDS["wino1d"] and ops.wino1d_ok(32, 800, 64, 64)
@@ -434,6 +435,33 @@ def test_dispatch_thresholds_and_parameter_epoch(monkeypatch):
     e1 = ops.PARAMS_EPOCH[0]
     model.load_state_dict(model.state_dict())
     assert ops.PARAMS_EPOCH[0] == e1 + 1
+
+
+def test_wino4_form_is_decided_by_the_library(monkeypatch):
+    """``adyolo_wino4_fwd_form`` (no device access) is the one place that decides which F(4x4) kernel ``adyolo_wino4_fwd`` launches:
+    2 persistent, 1 one-patch, 0 none (ENOSUP).  The decision as it stood when it moved there, written out as values; and
+    ``DualPack.pick`` where the bench shape sits on its edge (``adyolo_wino4_tiles`` is host arithmetic)."""
+    from adyolo_amd import ops
+    for k in ("ADYOLO_W4_PERSIST", "ADYOLO_W4_NARROW", "ADYOLO_W4_MIN_WGS", "ADYOLO_W4_MIN_K_ADDEND"):
+        monkeypatch.delenv(k, raising=False)
+    form = _lib.load().adyolo_wino4_fwd_form
+    BIAS = 32
+    # (Cout, operands: 1 stats | 2 addend | 4 addend mask | 8 stat_aux | 16 stat mask | 32 bias, mask_bits) -> form
+    table = [((64, 0, 0), 2), ((64, 1, 0), 2), ((64, 2, 0), 2), ((64, 9, 0), 2), ((64, 3, 0), 1), ((32, 1, 0), 2), ((32, 3, 0), 0),
+             ((96, 0, 0), 0), ((192, 0, 0), 1), ((512, 0, 0), 2), ((1024, 0, 0), 1), ((64, 6, 0), 1), ((64, 15, 1), 2),
+             ((64, 15, 0), 1), ((64, 27, 2), 2), ((64, 27, 0), 1), ((64, 31, 3), 2), ((64, 31, 1), 1), ((32, 31, 3), 2),
+             ((32, 31, 1), 0), ((64, 0 | BIAS, 0), 1), ((32, 0 | BIAS, 0), 0)]
+    got = [form(*args) for args, _ in table]
+    assert got == [want for _, want in table], [(a, g) for (a, want), g in zip(table, got) if g != want]
+    assert form(0, 0, 0) == 0 and form(48, 0, 0) == 0 and form(-64, 0, 0) == 0      # not a positive multiple of 32: no kernel
+    monkeypatch.setenv("ADYOLO_W4_PERSIST", "0")                     # (the fixture reloads, and the reload pushes to the library)
+    assert form(64, 1, 0) == 1 and form(32, 1, 0) == 0
+    monkeypatch.delenv("ADYOLO_W4_PERSIST")
+    assert form(64, 1, 0) == 2 and form(32, 1, 0) == 2
+    f4, f2 = torch.zeros(36, 2, 8, 256), torch.zeros(16, 2, 8, 256)
+    dual = ops.DualPack(f4, f2)
+    assert dual.pick(10, 600, 16, 64) is f2 and dual.pick(11, 600, 16, 64) is f4        # 190 / 209 work items against 200
+    assert dual.pick(64, 600, 16, 32, False, False) is f2 and dual.pick(64, 2400, 64, 32) is f4
 
 
 def test_float64_gru_references_match_torch_gru():

@@ -50,7 +50,7 @@ __global__ __launch_bounds__(256) void maxpool3_fwd_kernel(const float *__restri
                 const int ww = wo * 2 - 1 + kw;
                 if (ww < 0 || ww >= W) continue;
                 const float v = x[(((size_t)n * H + hh) * W + ww) * C + c];
-                if (v > best) {
+                if (v > best || v != v) {                 // a NaN is taken and then kept (nothing compares above it): nn.MaxPool2d's rule
                     best = v;
                     bi = kh * 3 + kw;
                 }

@@ -206,3 +206,120 @@ def state_dict_spec(nb_classes=12, in_ch=7, grid=(8, 4), anchors=5):
     spec.extend([("head.yolo_head.0.weight", (256, 256)), ("head.yolo_head.0.bias", (256,)),
                  ("head.yolo_head.1.weight", (k, 256)), ("head.yolo_head.1.bias", (k,))])
     return spec
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Channels-last references of the SE-block stage, one formula per function, for the kernel tests of
+# tests/test_gpu_block_stage.py (run in float64 as the yardstick and in float32 as "what plain fp32 gives").  Every function
+# follows the dtype of its tensor arguments; x is [N][H][W][C] (or [N][HW][C]) and the per-channel operands are [C].
+U32 = 2.0 ** -24          # unit roundoff of float32
+
+
+def bn_train_nhwc(x, gamma=None, beta=None, eps=BN_EPS):
+    """nn.BatchNorm2d in training mode (resnet.py:17,19): -> (y or None, mean, biased var, invstd) over every axis but the last."""
+    dims = tuple(range(x.dim() - 1))
+    mean = x.mean(dim=dims)
+    var = ((x - mean) ** 2).mean(dim=dims)
+    invstd = 1.0 / torch.sqrt(var + eps)
+    y = None if gamma is None else (x - mean) * invstd * gamma + beta
+    return y, mean, var, invstd
+
+
+def bn_running_update(running_mean, running_var, mean, var, count, momentum=BN_MOM):
+    """The buffers after one training step: the unbiased variance (count / (count - 1); the biased one when count == 1 -- the
+    guard of the kernels, nn.BatchNorm2d itself refuses a single value per channel)."""
+    unbiased = var * (count / (count - 1.0)) if count > 1 else var
+    return (1 - momentum) * running_mean + momentum * mean, (1 - momentum) * running_var + momentum * unbiased
+
+
+def xhat_nhwc(x, mean, invstd):
+    return (x - mean) * invstd
+
+
+def bn_bwd_nhwc(dy, x, gamma, mean, invstd, relu_mask=False):
+    """Backward of y = xhat(x) gamma + beta with batch statistics: -> dx, dgamma, dbeta (relu_mask: dx * (x > 0), x being a
+    ReLU output whose ReLU is folded into this pass)."""
+    dims = tuple(range(x.dim() - 1))
+    count = x.numel() // x.shape[-1]
+    xh = xhat_nhwc(x, mean, invstd)
+    dbeta = dy.sum(dim=dims)
+    dgamma = (dy * xh).sum(dim=dims)
+    dx = gamma * invstd * (dy - dbeta / count - xh * dgamma / count)
+    if relu_mask:
+        dx = dx * (x > 0)
+    return dx, dgamma, dbeta
+
+
+def se_gate(pooled, w1, b1, w2, b2):
+    """SELayer's two Linears (resnet.py:95-99, 104-105) on the squeezed [N][C]: -> hidden [N][C/r], scale [N][C]."""
+    hid = F.relu(F.linear(pooled, w1, b1))
+    return hid, torch.sigmoid(F.linear(hid, w2, b2))
+
+
+def se_tail_nhwc(c, r, scale, shift, w1, b1, w2, b2, r_affine=None, pool=False):
+    """relu(bn2(c) * s + r) with bn2(c) = c * scale + shift, s = SE gate of mean_hw(bn2(c)), the shortcut r seen through its own
+    BatchNorm affine when given; pool: followed by AvgPool2d(2, 2) (the next block's).  -> dict(pooled, hid, s, pre, e[, out])."""
+    d = c * scale + shift
+    pooled = d.mean(dim=tuple(range(1, c.dim() - 1)))
+    hid, s = se_gate(pooled, w1, b1, w2, b2)
+    if r_affine is not None:
+        r = r * r_affine[0] + r_affine[1]
+    sb = s.view(s.shape[0], *([1] * (c.dim() - 2)), s.shape[1])
+    pre = d * sb + r
+    out = {"pooled": pooled, "hid": hid, "s": s, "pre": pre, "e": F.relu(pre)}
+    if pool:
+        out["out"] = avgpool2_nhwc(out["e"])
+    return out
+
+
+def avgpool2_nhwc(x):
+    """nn.AvgPool2d(2, 2) (resnet.py:13,27-29) on [N][H][W][C]."""
+    n, h, w, c = x.shape
+    return x.view(n, h // 2, 2, w // 2, 2, c).mean(dim=(2, 4))
+
+
+def fp32_sum_bound(abs_sum, terms):
+    """A-priori bound on the error of a float32 sum of at most ``terms`` values summed in any order:
+    terms * 2^-24 * sum |values| (Higham, (n - 1) u sum|x_i|, rounded up to n)."""
+    return terms * U32 * abs_sum
+
+
+def pack_relu_bits(mask):
+    """(e > 0) of a [N]...[C] tensor as the int64 words the kernels read (csrc/common.hpp): the float4 with flat index i (four
+    consecutive channels) owns bit (i & 63) of the words [(i >> 6) * 4 + k], k = its component.  ``mask``: bool array whose size
+    is a multiple of 256."""
+    import numpy as np
+    m = np.ascontiguousarray(np.asarray(mask, dtype=bool)).reshape(-1)
+    if m.size % 256:
+        raise ValueError("pack_relu_bits: %d elements are not whole 64-float4 groups" % m.size)
+    g = m.reshape(-1, 64, 4).astype(np.uint64)                       # [group][float4 in group][component]
+    words = (g << np.arange(64, dtype=np.uint64)[None, :, None]).sum(axis=1, dtype=np.uint64)      # [group][component]
+    return words.reshape(-1).view(np.int64)
+
+
+def unpack_relu_bits(words, shape):
+    import numpy as np
+    w = np.ascontiguousarray(np.asarray(words)).view(np.uint64).reshape(-1, 1, 4)
+    bits = (w >> np.arange(64, dtype=np.uint64)[None, :, None]) & np.uint64(1)                       # [group][float4][component]
+    return bits.astype(bool).reshape(shape)
+
+
+def onepass_invstd_error(ratio, rows=76800, chunk=300, channels=32, seed=0, eps=BN_EPS):
+    """Relative error of invstd when the variance is E[x^2] - E[x]^2 from float32 sums, as the BatchNorm statistics kernels form
+    it (a thread sums ``chunk`` values of x and of the float32 x * x one after the other; the partials are combined in float64):
+    the worst of ``channels`` channels of ``rows`` Gaussian values each with |mean| / std = ``ratio``.  The float64 yardstick is
+    the two-pass value of the same float32 numbers."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    rows = rows // chunk * chunk
+    x = (ratio + rng.standard_normal((rows, channels))).astype(np.float32)
+    xc = x.reshape(-1, chunk, channels)
+    s = np.zeros((xc.shape[0], channels), np.float32)
+    q = np.zeros((xc.shape[0], channels), np.float32)
+    for j in range(chunk):
+        s = s + xc[:, j]
+        q = q + xc[:, j] * xc[:, j]
+    m = s.astype(np.float64).sum(axis=0) / rows
+    var = np.maximum(q.astype(np.float64).sum(axis=0) / rows - m * m, 0.0)
+    ref = 1.0 / np.sqrt(x.astype(np.float64).var(axis=0) + eps)
+    return float(np.max(np.abs(1.0 / np.sqrt(var + eps) - ref) / ref))

@@ -441,6 +441,7 @@ extern "C" int adyolo_attn_bwd(const float *q, const float *k, const float *v, c
     ADYOLO_REQUIRE(q && k && v && ctx && dctx && lse2 && delta && dq && dk && dv && B > 0 && T > 0 && H > 0, ADYOLO_EINVAL,
                    "attn_bwd: bad arguments");
     ADYOLO_REQUIRE(D == AD && dropout_p >= 0.f && dropout_p < 1.f, ADYOLO_ENOSUP, "attn_bwd: head dimension %d (needs 64)", D);
+    ADYOLO_REQUIRE((double)B * H * T * T < 4294967296.0, ADYOLO_ENOSUP, "attn_bwd: B*H*T*T exceeds the 32-bit dropout index");
     hipStream_t st = as_stream(stream);
     const unsigned thr = drop_threshold(dropout_p);
     const float ks = 1.0f / (1.0f - dropout_p), sl = scale * 1.4426950408889634f;
@@ -460,6 +461,7 @@ extern "C" int adyolo_attn_bwd(const float *q, const float *k, const float *v, c
 extern "C" int adyolo_attn_dropout_mask(float *mask, int B, int T, int H, float dropout_p, uint32_t seed, void *stream) {
     ADYOLO_REQUIRE(mask && B > 0 && T > 0 && H > 0 && dropout_p >= 0.f && dropout_p < 1.f, ADYOLO_EINVAL,
                    "attn_dropout_mask: bad arguments");
+    ADYOLO_REQUIRE((double)B * H * T * T < 4294967296.0, ADYOLO_ENOSUP, "attn_dropout_mask: B*H*T*T exceeds the 32-bit dropout index");
     const long n = (long)B * H * T * T;
     long g = (n + 255) / 256;
     if (g > 8192) g = 8192;

@@ -42,7 +42,7 @@ __global__ __launch_bounds__(256) void maxpool3_fwd_kernel(const float *__restri
         const int h = (int)(p % H);
         const long n = p / H;
         float best = -INFINITY;
-        int bi = 0;
+        int bi = -1;                                       // no tap yet: the first tap inside the map owns an all -inf window (nn.MaxPool2d)
         for (int kh = 0; kh < 3; ++kh) {
             const int hh = h - 1 + kh;
             if (hh < 0 || hh >= H) continue;
@@ -50,7 +50,7 @@ __global__ __launch_bounds__(256) void maxpool3_fwd_kernel(const float *__restri
                 const int ww = wo * 2 - 1 + kw;
                 if (ww < 0 || ww >= W) continue;
                 const float v = x[(((size_t)n * H + hh) * W + ww) * C + c];
-                if (v > best || v != v) {                 // a NaN is taken and then kept (nothing compares above it): nn.MaxPool2d's rule
+                if (bi < 0 || v > best || v != v) {       // a NaN is taken and then kept (nothing compares above it): nn.MaxPool2d's rule
                     best = v;
                     bi = kh * 3 + kw;
                 }

@@ -21,6 +21,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import seresnet as onet
+from oracle.checks import d64, sum_check, value_check
 
 pytestmark = pytest.mark.gpu
 
@@ -41,43 +42,6 @@ def ops():
 
 def dev(t):
     return t.to("cuda:0").contiguous()
-
-
-def d64(t):
-    return t.detach().cpu().double()
-
-
-def value_check(what, got, ref64, ref32, keep=None):
-    """err_gpu <= max(4 err_ref, 16 * 2^-24), both relative to max |ref64|.  keep (bool tensor): the elements compared."""
-    got, ref64, ref32 = d64(got), d64(ref64), d64(ref32)
-    assert got.shape == ref64.shape == ref32.shape, "%s: shapes %s %s %s" % (what, tuple(got.shape), tuple(ref64.shape), tuple(ref32.shape))
-    assert bool(torch.isfinite(got).all()), "%s: not finite" % what
-    scale = float(ref64.abs().max())
-    dg, dr = (got - ref64).abs(), (ref32 - ref64).abs()
-    if keep is not None:
-        dg, dr = dg[keep], dr[keep]
-    err_gpu = float(dg.max()) / scale if scale > 0 else float(dg.max())
-    err_ref = float(dr.max()) / scale if scale > 0 else float(dr.max())
-    bar = max(4 * err_ref, FLOOR)
-    print("%-58s err_gpu %.3e  err_ref %.3e  bar %.3e  (float64 absmax %.3e)" % (what, err_gpu, err_ref, bar, scale))
-    assert err_gpu <= bar, "%s: err_gpu %.3e > bar %.3e (err_ref %.3e, float64 absmax %.3e)" % (what, err_gpu, bar, err_ref, scale)
-    return err_gpu
-
-
-def sum_check(what, got, ref64, bound):
-    """|got - ref64| <= bound, entry by entry (bound: a tensor computed from the inputs)."""
-    got, ref64, bound = d64(got), d64(ref64), d64(bound)
-    assert got.shape == ref64.shape == bound.shape, "%s: shapes %s %s %s" % (what, tuple(got.shape), tuple(ref64.shape), tuple(bound.shape))
-    assert bool(torch.isfinite(got).all()), "%s: not finite" % what
-    err = (got - ref64).abs()
-    ok = err <= bound
-    pos = bound > 0
-    worst = float((err[pos] / bound[pos]).max()) if bool(pos.any()) else 0.0
-    scale = float(ref64.abs().max())
-    print("%-58s worst err / bound %.3e  (max err %.3e, float64 absmax %.3e)" % (what, worst, float(err.max()), scale))
-    assert bool(ok.all()), "%s: %d of %d entries over the a-priori bound, worst err / bound %.3e (max err %.3e, absmax %.3e)" % (
-        what, int((~ok).sum()), ok.numel(), worst, float(err.max()), scale)
-    return worst
 
 
 def invstd_bound(mean64, var64, b_sum, b_sq, count):

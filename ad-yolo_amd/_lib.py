@@ -135,6 +135,12 @@ SIGNATURES = {
     "adyolo_colstats": (I, [P, P, P, L, I, P]),
     "adyolo_adam_step": (I, [P] * 4 + [L, F, F, F, F, F, I, F, P]),
     "adyolo_adam_step_dev": (I, [P] * 4 + [L, F, F, F, F, F, P, P, F, P]),
+    "adyolo_grad_sumsq_parts": (L, [L]),
+    "adyolo_grad_sumsq": (I, [P, L, F, P, P]),
+    "adyolo_grad_norm_dev": (I, [P, L, F, P, F, P, P]),
+    "adyolo_adamw_step_dev": (I, [P] * 4 + [L, F, F, F, F, F, P, P, P, F, F, P]),
+    "adyolo_adam_clip_step_dev": (I, [P] * 4 + [L, F, F, F, F, F, P, P, P, F, F, P]),
+    "adyolo_sgd_step_dev": (I, [P] * 3 + [L, F, F, F, F, I, P, P, P, F, F, P]),
 }
 
 _lib = None

@@ -2,7 +2,8 @@
 result folders are interchangeable: ``model_ckpt.h5`` = {start_epoch_nb, model_state_dict, optim_state_dict,
 confidence_thresh, rng_state, best_log, train_remaining_file}, ``model_best.h5`` = {epoch_nb, model_state_dict,
 optim_state_dict, confidence_thresh}.  ``model_state_dict`` has the reference's 305 keys (WrapperModel.state_dict()),
-``optim_state_dict`` is torch.optim.Adam's layout with parameter indices in ``model.parameters()`` order.
+``optim_state_dict`` is the layout of the optimizer's torch.optim counterpart (Adam, AdamW or SGD) with parameter indices in
+``model.parameters()`` order.
 
 Unlike the reference the RNG helpers do not touch ``torch.cuda`` when the device is the CPU.
 """
@@ -39,40 +40,97 @@ def seed_resume(rng_state, device, model=None):
     os.environ["PYTHONHASHSEED"] = str(rng_state["os_hash_state"])
 
 
-def optimizer_state_dict(optimizer, model):
-    """FusedAdam state in torch.optim.Adam's layout, indices following ``model.parameters()`` (the order the reference's
-    ``optimizer.state_dict()`` uses), independent of the flat buffer's internal (reversed) order."""
+def _indexed_params(optimizer, model):
+    """-> [(index in model.parameters() order, parameter, offset in the flat buffer, numel)]: the order torch.optim's
+    ``state_dict()`` uses, independent of the flat buffer's internal (reversed) order."""
     flat = optimizer.flat
     where = {id(p): k for k, p in enumerate(flat.params)}
     params = [p for p in model.parameters() if p.requires_grad] if model is not None else flat.module_params
+    return [(i, p) + tuple(flat.offsets[where[id(p)]]) for i, p in enumerate(params)]
+
+
+def _cpu_slice(buf, off, n, p):
+    return buf[off:off + n].view(p.shape).detach().cpu().clone()
+
+
+def optimizer_state_dict(optimizer, model):
+    """The fused optimizer's state in the layout of its torch.optim counterpart (``optimizer.kind``): FusedAdam ->
+    torch.optim.Adam, FusedAdamW -> torch.optim.AdamW (Adam's state, ``decoupled_weight_decay: True`` in the group), FusedSGD ->
+    torch.optim.SGD (``momentum_buffer`` per parameter once a step with momentum was taken, no entries otherwise).  Indices
+    follow ``model.parameters()``.  ``clip_grad_norm`` is configuration, not state: it is not written."""
+    params = _indexed_params(optimizer, model)
+    kind = getattr(optimizer, "kind", "adam")
     state = {}
-    for i, p in enumerate(params):
-        off, n = flat.offsets[where[id(p)]]
+    if kind == "sgd":
+        if optimizer.momentum != 0 and optimizer.step_count > 0:
+            for i, p, off, n in params:
+                state[i] = {"momentum_buffer": _cpu_slice(optimizer.momentum_buffer, off, n, p)}
+        group = {"lr": optimizer.lr, "momentum": optimizer.momentum, "dampening": optimizer.dampening,
+                 "weight_decay": optimizer.weight_decay, "nesterov": optimizer.nesterov, "maximize": False, "foreach": None,
+                 "differentiable": False, "fused": None, "params": list(range(len(params)))}
+        return {"state": state, "param_groups": [group]}
+    for i, p, off, n in params:
         if optimizer.step_count > 0:
             state[i] = {"step": torch.tensor(float(optimizer.step_count)),
-                        "exp_avg": optimizer.exp_avg[off:off + n].view(p.shape).detach().cpu().clone(),
-                        "exp_avg_sq": optimizer.exp_avg_sq[off:off + n].view(p.shape).detach().cpu().clone()}
+                        "exp_avg": _cpu_slice(optimizer.exp_avg, off, n, p),
+                        "exp_avg_sq": _cpu_slice(optimizer.exp_avg_sq, off, n, p)}
     group = {"lr": optimizer.lr, "betas": tuple(optimizer.betas), "eps": optimizer.eps,
              "weight_decay": optimizer.weight_decay, "amsgrad": False, "maximize": False, "foreach": None,
-             "capturable": False, "differentiable": False, "fused": None, "params": list(range(len(params)))}
+             "capturable": False, "differentiable": False, "fused": None}
+    if kind == "adamw":
+        group["decoupled_weight_decay"] = True
+    group["params"] = list(range(len(params)))
     return {"state": state, "param_groups": [group]}
 
 
+def _load_sgd_state(optimizer, params, sd, g):
+    """torch.optim.SGD's state holds no step count: whether the next step is "the first" (momentum buffer := gradient) is
+    decided by the presence of buffers, and ``step_count`` -- from which the device-side flag is derived -- is set to agree."""
+    if (g.get("momentum", 0.0) != 0) != (optimizer.momentum != 0):        # (the buffer exists or not since construction)
+        raise ValueError("SGD state was written with momentum %r, this optimizer has %r"
+                         % (g.get("momentum", 0.0), optimizer.momentum))
+    optimizer.lr, optimizer.weight_decay = g["lr"], g.get("weight_decay", 0.0)
+    optimizer.momentum, optimizer.dampening = g.get("momentum", 0.0), g.get("dampening", 0.0)
+    optimizer.nesterov = bool(g.get("nesterov", False))
+    have = []
+    for i, p, off, n in params:
+        st = sd["state"].get(g["params"][i], sd["state"].get(i))
+        buf = None if st is None else st.get("momentum_buffer")
+        have.append(buf is not None)
+        if buf is None or optimizer.momentum == 0:
+            continue
+        if tuple(buf.shape) != tuple(p.shape):
+            raise ValueError("optimizer state %d has shape %s, parameter %s" % (i, tuple(buf.shape), tuple(p.shape)))
+        optimizer.momentum_buffer[off:off + n].copy_(buf.reshape(-1))
+    if optimizer.momentum != 0 and any(have) and not all(have):
+        raise ValueError("some parameters have a momentum buffer and some have none: the flat SGD keeps ONE first-step flag")
+    resumed = optimizer.momentum != 0 and bool(have) and all(have)
+    if optimizer.momentum != 0 and not resumed:
+        optimizer.momentum_buffer.zero_()
+    optimizer.step_count = 1 if resumed else 0
+
+
 def load_optimizer_state_dict(optimizer, model, sd):
-    flat = optimizer.flat
-    where = {id(p): k for k, p in enumerate(flat.params)}
-    params = [p for p in model.parameters() if p.requires_grad] if model is not None else flat.module_params
+    params = _indexed_params(optimizer, model)
     g = sd["param_groups"][0]
     if len(g["params"]) != len(params):
         raise ValueError("optimizer state has %d parameters, the model %d" % (len(g["params"]), len(params)))
+    kind = getattr(optimizer, "kind", "adam")
+    if kind == "sgd":
+        if "betas" in g:
+            raise ValueError("an Adam-family optimizer state cannot be loaded into FusedSGD")
+        return _load_sgd_state(optimizer, params, sd, g)
+    if "betas" not in g:
+        raise ValueError("an SGD optimizer state cannot be loaded into %s" % type(optimizer).__name__)
+    if kind == "adamw" and g.get("decoupled_weight_decay", True) is False:
+        raise ValueError("a torch.optim.Adam state (coupled weight decay) cannot be loaded into FusedAdamW")
     optimizer.lr, optimizer.betas, optimizer.eps = g["lr"], tuple(g["betas"]), g["eps"]
     optimizer.weight_decay = g.get("weight_decay", 0.0)
     if g.get("amsgrad", False):
         raise NotImplementedError("amsgrad Adam state is not supported by the fused gfx950 Adam")
     steps = set()
-    for i, p in enumerate(params):
+    for i, p, off, n in params:
         st = sd["state"].get(g["params"][i], sd["state"].get(i))
-        off, n = flat.offsets[where[id(p)]]
         if st is None:
             optimizer.exp_avg[off:off + n].zero_()
             optimizer.exp_avg_sq[off:off + n].zero_()

@@ -1,0 +1,282 @@
+// K11x: AdamW, SGD and gradient-norm clipping over the flat parameter buffer (the reference picks its optimizer by name,
+// src/train.py:29-37, and clips with clip_grad_norm_(max_norm), src/train.py:54).  csrc/optim.hip's Adam is left alone: the
+// clipped Adam here repeats its arithmetic operation for operation and adds the coefficient.
+//
+// One optimizer step = up to three launches whose arguments never change from step to step (hipGraph-replayable):
+//   grad_sumsq_kernel   (clipping only) partial sums of (g * grad_scale)^2 in float64, one per workgroup, fixed grid and order
+//   optim_prep_kernel   one workgroup: step counter += 1; st[0..1] = bias corrections (Adam / AdamW) or the "first step" flag
+//                       (SGD); st[2] = total_norm (fp32); st[3] = clip_coef = min(1, max_norm / (total_norm + 1e-6)) -- 1 when off
+//   *_update_kernel     the update, grad_scale * st[3] folded into the gradient
+// st is 4 floats of device scratch.  All streams move 16 bytes per lane per access (pointers 16-byte aligned, the n & 3 tail
+// elements are done by workgroup 0); grids are capped and grid-stride.  Elements that are zero in parameter, gradient and state
+// (the padding of dist.FlatParameters) stay zero in every kernel.
+#include <math.h>
+#include "common.hpp"
+
+namespace adyolo {
+
+constexpr int OX_THREADS = 256;
+constexpr int OX_MAX_BLOCKS = 2048;      // update kernels: 8 workgroups per CU, grid-stride beyond
+constexpr int OX_SUMSQ_BLOCKS = 1024;    // = the largest number of partials (8 KB of float64)
+
+static inline int update_grid(long n) {
+    long g = ((n >> 2) + OX_THREADS - 1) / OX_THREADS;
+    return (int)(g < 1 ? 1 : (g > OX_MAX_BLOCKS ? OX_MAX_BLOCKS : g));
+}
+
+static inline int sumsq_grid(long n) {
+    long g = ((n >> 2) + OX_THREADS - 1) / OX_THREADS;
+    return (int)(g < 1 ? 1 : (g > OX_SUMSQ_BLOCKS ? OX_SUMSQ_BLOCKS : g));
+}
+
+static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// ---------------------------------------------------------------------------------------------- gradient norm
+__global__ __launch_bounds__(OX_THREADS) void grad_sumsq_kernel(const float *__restrict__ g, long n, float grad_scale,
+                                                                double *__restrict__ partials) {
+    __shared__ double red[OX_THREADS / 64];
+    const long n4 = n >> 2;
+    const float4 *g4 = reinterpret_cast<const float4 *>(g);
+    double s = 0.0;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        const float4 v = g4[i];
+        const double a = (double)(v.x * grad_scale), b = (double)(v.y * grad_scale);
+        const double c = (double)(v.z * grad_scale), d = (double)(v.w * grad_scale);
+        s += (a * a + b * b) + (c * c + d * d);
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const double a = (double)(g[n4 * 4 + threadIdx.x] * grad_scale);
+        s += a * a;
+    }
+    // fixed order: butterfly inside the wave, then the four waves one after the other
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) partials[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// ---------------------------------------------------------------------------------------------- prep
+enum { PREP_ADAM = 0, PREP_SGD = 1, PREP_NORM = 2 };
+
+// one workgroup of OX_THREADS.  partials == nullptr: clipping off (st[3] = 1, st[2] untouched).  PREP_NORM: no counter, norm only.
+__global__ __launch_bounds__(OX_THREADS) void optim_prep_kernel(unsigned long long *__restrict__ step, float *__restrict__ st,
+                                                                int kind, float lr, float beta1, float beta2,
+                                                                const double *__restrict__ partials, int nparts,
+                                                                float max_norm) {
+    __shared__ double red[OX_THREADS];
+    if (threadIdx.x == 0 && kind != PREP_NORM) {
+        const unsigned long long s = *step + 1ull;
+        *step = s;
+        if (kind == PREP_ADAM) {           // as adam_prep_kernel: in double like torch's host arithmetic
+            const double bc1 = 1.0 - pow((double)beta1, (double)s);
+            const double bc2 = 1.0 - pow((double)beta2, (double)s);
+            st[0] = (float)((double)lr / bc1);
+            st[1] = (float)(1.0 / sqrt(bc2));
+        } else {                           // SGD: the momentum buffer is INITIALISED by the first step (no dampening)
+            st[0] = s == 1ull ? 1.f : 0.f;
+            st[1] = 0.f;
+        }
+    }
+    if (partials == nullptr) {             // (uniform over the workgroup)
+        if (threadIdx.x == 0) st[3] = 1.f;
+        return;
+    }
+    double s = 0.0;
+    for (int i = threadIdx.x; i < nparts; i += OX_THREADS) s += partials[i];
+    red[threadIdx.x] = s;
+    __syncthreads();
+#pragma unroll
+    for (int o = OX_THREADS / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        // torch.nn.utils.clip_grad_norm_: clip_coef = max_norm / (total_norm + 1e-6), clamped to 1; fp32; a non-finite norm is
+        // not special-cased (inf -> 0, nan -> nan)
+        const float total = (float)sqrt(red[0]);
+        const float coef = max_norm / (total + 1e-6f);
+        st[2] = total;
+        st[3] = coef > 1.f ? 1.f : coef;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- Adam / AdamW update
+// DECOUPLED = false: torch.optim.Adam (weight decay added to the gradient) -- adam_kernel<true> of optim.hip plus the coefficient.
+// DECOUPLED = true:  torch.optim.AdamW: p *= 1 - lr * wd (`decay`, formed on the host in double) before the moments.
+template <bool DECOUPLED>
+__device__ __forceinline__ void adam_one(float &p, float g, float &m, float &v, float gs, float beta1, float beta2, float eps,
+                                         float wd, float decay, float step_size, float inv_sqrt_bc2) {
+    float gi = g * gs;
+    float pi = p;
+    if (DECOUPLED) {
+        if (wd != 0.f) pi *= decay;
+    } else {
+        if (wd != 0.f) gi += wd * pi;
+    }
+    float mi = m, vi = v;
+    mi += (gi - mi) * (1.f - beta1);
+    vi = vi * beta2 + (1.f - beta2) * gi * gi;
+    const float denom = sqrtf(vi) * inv_sqrt_bc2 + eps;
+    p = pi - step_size * (mi / denom);
+    m = mi;
+    v = vi;
+}
+
+template <bool DECOUPLED>
+__global__ __launch_bounds__(OX_THREADS) void adam_update_kernel(float *__restrict__ p, const float *__restrict__ g,
+                                                                 float *__restrict__ m, float *__restrict__ v, long n,
+                                                                 float beta1, float beta2, float eps, float wd, float decay,
+                                                                 float grad_scale, const float *__restrict__ st) {
+    const float step_size = st[0], inv_sqrt_bc2 = st[1];
+    const float gs = grad_scale * st[3];
+    const long n4 = n >> 2;
+    float4 *p4 = reinterpret_cast<float4 *>(p), *m4 = reinterpret_cast<float4 *>(m), *v4 = reinterpret_cast<float4 *>(v);
+    const float4 *g4 = reinterpret_cast<const float4 *>(g);
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        float4 pv = p4[i], mv = m4[i], vv = v4[i];
+        const float4 gv = g4[i];
+        adam_one<DECOUPLED>(pv.x, gv.x, mv.x, vv.x, gs, beta1, beta2, eps, wd, decay, step_size, inv_sqrt_bc2);
+        adam_one<DECOUPLED>(pv.y, gv.y, mv.y, vv.y, gs, beta1, beta2, eps, wd, decay, step_size, inv_sqrt_bc2);
+        adam_one<DECOUPLED>(pv.z, gv.z, mv.z, vv.z, gs, beta1, beta2, eps, wd, decay, step_size, inv_sqrt_bc2);
+        adam_one<DECOUPLED>(pv.w, gv.w, mv.w, vv.w, gs, beta1, beta2, eps, wd, decay, step_size, inv_sqrt_bc2);
+        p4[i] = pv;
+        m4[i] = mv;
+        v4[i] = vv;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const long i = n4 * 4 + threadIdx.x;
+        adam_one<DECOUPLED>(p[i], g[i], m[i], v[i], gs, beta1, beta2, eps, wd, decay, step_size, inv_sqrt_bc2);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- SGD update
+// torch.optim.SGD, single-tensor path: g' = g * gs + wd * p;  MOM: buf = g' on the first step (st[0] != 0), else
+// buf = mu * buf + (1 - dampening) * g';  d = nesterov ? g' + mu * buf : buf;  p += -lr * d.  !MOM: buf is never touched.
+template <bool MOM>
+__device__ __forceinline__ void sgd_one(float &p, float g, float *buf, float gs, float lr, float wd, float mu, float keep,
+                                        bool nesterov, bool first) {
+    float gi = g * gs;
+    const float pi = p;
+    if (wd != 0.f) gi += wd * pi;
+    if (MOM) {
+        const float bi = first ? gi : *buf * mu + keep * gi;
+        *buf = bi;
+        gi = nesterov ? gi + mu * bi : bi;
+    }
+    p = pi - lr * gi;
+}
+
+template <bool MOM>
+__global__ __launch_bounds__(OX_THREADS) void sgd_update_kernel(float *__restrict__ p, const float *__restrict__ g,
+                                                                float *__restrict__ buf, long n, float lr, float wd, float mu,
+                                                                float keep, int nesterov, float grad_scale,
+                                                                const float *__restrict__ st) {
+    const bool first = st[0] != 0.f, nest = nesterov != 0;
+    const float gs = grad_scale * st[3];
+    const long n4 = n >> 2;
+    float4 *p4 = reinterpret_cast<float4 *>(p), *b4 = reinterpret_cast<float4 *>(buf);
+    const float4 *g4 = reinterpret_cast<const float4 *>(g);
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        float4 pv = p4[i];
+        const float4 gv = g4[i];
+        float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (MOM && !first) bv = b4[i];
+        sgd_one<MOM>(pv.x, gv.x, &bv.x, gs, lr, wd, mu, keep, nest, first);
+        sgd_one<MOM>(pv.y, gv.y, &bv.y, gs, lr, wd, mu, keep, nest, first);
+        sgd_one<MOM>(pv.z, gv.z, &bv.z, gs, lr, wd, mu, keep, nest, first);
+        sgd_one<MOM>(pv.w, gv.w, &bv.w, gs, lr, wd, mu, keep, nest, first);
+        p4[i] = pv;
+        if (MOM) b4[i] = bv;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const long i = n4 * 4 + threadIdx.x;
+        sgd_one<MOM>(p[i], g[i], MOM ? buf + i : nullptr, gs, lr, wd, mu, keep, nest, first);
+    }
+}
+
+static int launch_sumsq(const float *grad, long n, float grad_scale, double *partials, hipStream_t st) {
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3(sumsq_grid(n)), dim3(OX_THREADS), 0, st, grad, n, grad_scale, partials);
+    return check_launch("grad_sumsq");
+}
+
+static int launch_prep(uint64_t *step_dev, float *st_dev, int kind, float lr, float beta1, float beta2, const double *partials,
+                       long n, float max_norm, hipStream_t st) {
+    hipLaunchKernelGGL(optim_prep_kernel, dim3(1), dim3(OX_THREADS), 0, st, reinterpret_cast<unsigned long long *>(step_dev),
+                       st_dev, kind, lr, beta1, beta2, partials, partials ? sumsq_grid(n) : 0, max_norm);
+    return check_launch("optim_prep");
+}
+
+template <bool DECOUPLED>
+static int adam_ext_step(const char *what, float *param, const float *grad, float *exp_avg, float *exp_avg_sq, long n, float lr,
+                         float beta1, float beta2, float eps, float wd, uint64_t *step_dev, float *st_dev, double *partials,
+                         float max_norm, float grad_scale, void *stream) {
+    ADYOLO_REQUIRE(param && grad && exp_avg && exp_avg_sq && n > 0 && step_dev && st_dev, ADYOLO_EINVAL, "%s: bad arguments", what);
+    ADYOLO_REQUIRE(aligned16(param) && aligned16(grad) && aligned16(exp_avg) && aligned16(exp_avg_sq), ADYOLO_EINVAL,
+                   "%s: buffers not 16-byte aligned", what);
+    hipStream_t st = as_stream(stream);
+    int rc;
+    if (partials && (rc = launch_sumsq(grad, n, grad_scale, partials, st))) return rc;
+    if ((rc = launch_prep(step_dev, st_dev, PREP_ADAM, lr, beta1, beta2, partials, n, max_norm, st))) return rc;
+    const float decay = (float)(1.0 - (double)lr * (double)wd);
+    hipLaunchKernelGGL(adam_update_kernel<DECOUPLED>, dim3(update_grid(n)), dim3(OX_THREADS), 0, st, param, grad, exp_avg,
+                       exp_avg_sq, n, beta1, beta2, eps, wd, decay, grad_scale, (const float *)st_dev);
+    return check_launch(what);
+}
+
+}  // namespace adyolo
+
+using namespace adyolo;
+
+extern "C" long adyolo_grad_sumsq_parts(long n) { return n > 0 ? sumsq_grid(n) : 0; }
+
+extern "C" int adyolo_grad_sumsq(const float *grad, long n, float grad_scale, double *partials, void *stream) {
+    ADYOLO_REQUIRE(grad && partials && n > 0, ADYOLO_EINVAL, "grad_sumsq: bad arguments");
+    ADYOLO_REQUIRE(aligned16(grad) && (reinterpret_cast<uintptr_t>(partials) & 7) == 0, ADYOLO_EINVAL,
+                   "grad_sumsq: gradient not 16-byte aligned (or partials not 8-byte aligned)");
+    return launch_sumsq(grad, n, grad_scale, partials, as_stream(stream));
+}
+
+extern "C" int adyolo_grad_norm_dev(const float *grad, long n, float grad_scale, double *partials, float max_norm, float *st_dev,
+                                    void *stream) {
+    ADYOLO_REQUIRE(st_dev, ADYOLO_EINVAL, "grad_norm_dev: null scratch");
+    int rc = adyolo_grad_sumsq(grad, n, grad_scale, partials, stream);
+    if (rc) return rc;
+    return launch_prep(nullptr, st_dev, PREP_NORM, 0.f, 0.f, 0.f, partials, n, max_norm, as_stream(stream));
+}
+
+extern "C" int adyolo_adamw_step_dev(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, long n, float lr,
+                                     float beta1, float beta2, float eps, float weight_decay, uint64_t *step_dev, float *st_dev,
+                                     double *partials, float max_norm, float grad_scale, void *stream) {
+    return adam_ext_step<true>("adamw_step_dev", param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay,
+                               step_dev, st_dev, partials, max_norm, grad_scale, stream);
+}
+
+extern "C" int adyolo_adam_clip_step_dev(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, long n, float lr,
+                                         float beta1, float beta2, float eps, float weight_decay, uint64_t *step_dev,
+                                         float *st_dev, double *partials, float max_norm, float grad_scale, void *stream) {
+    ADYOLO_REQUIRE(partials, ADYOLO_EINVAL, "adam_clip_step_dev: null partials (without clipping use adam_step_dev)");
+    return adam_ext_step<false>("adam_clip_step_dev", param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay,
+                                step_dev, st_dev, partials, max_norm, grad_scale, stream);
+}
+
+extern "C" int adyolo_sgd_step_dev(float *param, const float *grad, float *momentum_buf, long n, float lr, float weight_decay,
+                                   float momentum, float dampening, int nesterov, uint64_t *step_dev, float *st_dev,
+                                   double *partials, float max_norm, float grad_scale, void *stream) {
+    ADYOLO_REQUIRE(param && grad && n > 0 && step_dev && st_dev && (momentum == 0.f || momentum_buf), ADYOLO_EINVAL,
+                   "sgd_step_dev: bad arguments");
+    ADYOLO_REQUIRE(aligned16(param) && aligned16(grad) && aligned16(momentum_buf), ADYOLO_EINVAL,
+                   "sgd_step_dev: buffers not 16-byte aligned");
+    hipStream_t st = as_stream(stream);
+    int rc;
+    if (partials && (rc = launch_sumsq(grad, n, grad_scale, partials, st))) return rc;
+    if ((rc = launch_prep(step_dev, st_dev, PREP_SGD, lr, 0.f, 0.f, partials, n, max_norm, st))) return rc;
+    const float keep = (float)(1.0 - (double)dampening);
+    if (momentum != 0.f)
+        hipLaunchKernelGGL(sgd_update_kernel<true>, dim3(update_grid(n)), dim3(OX_THREADS), 0, st, param, grad, momentum_buf, n,
+                           lr, weight_decay, momentum, keep, nesterov, grad_scale, (const float *)st_dev);
+    else
+        hipLaunchKernelGGL(sgd_update_kernel<false>, dim3(update_grid(n)), dim3(OX_THREADS), 0, st, param, grad,
+                           (float *)nullptr, n, lr, weight_decay, 0.f, keep, nesterov, grad_scale, (const float *)st_dev);
+    return check_launch("sgd_step_dev");
+}

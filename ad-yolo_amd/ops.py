@@ -1054,6 +1054,91 @@ def adam_step_dev(param, grad, exp_avg, exp_avg_sq, step_dev, bc_dev, lr=1e-3, b
        eps, weight_decay, _p(step_dev), _p(bc_dev), grad_scale, _stream())
 
 
+GRAD_SUMSQ_MAX_PARTS = 1024       # adyolo_grad_sumsq_parts(n) never exceeds this (csrc/optim_ext.hip OX_SUMSQ_BLOCKS)
+OPTIM_SCRATCH_FLOATS = 4          # st_dev of the calls below: {a, b, total_norm, clip_coef} (include/adyolo_hip.h, K11x)
+
+
+def grad_sumsq_parts(n):
+    """number of float64 partials ``grad_sumsq`` writes for a gradient of n elements (what ``clip_partials`` must hold)"""
+    return int(_lib.load().adyolo_grad_sumsq_parts(int(n)))
+
+
+def _chk_optim_dev(what, n, step_dev, st_dev, partials):
+    if step_dev is not None and (not step_dev.is_cuda or step_dev.dtype != torch.int64 or step_dev.numel() != 1):
+        raise _lib.AdyoloHipError("%s needs a one-element int64 step counter on the device" % what)
+    if st_dev is not None and st_dev.numel() < OPTIM_SCRATCH_FLOATS:
+        raise _lib.AdyoloHipError("%s needs %d floats of scratch on the device" % (what, OPTIM_SCRATCH_FLOATS))
+    if partials is not None and (not partials.is_cuda or partials.dtype != torch.float64 or not partials.is_contiguous()
+                                 or partials.numel() < grad_sumsq_parts(n)):
+        raise _lib.AdyoloHipError("%s needs %d contiguous float64 partials on the device" % (what, grad_sumsq_parts(n)))
+
+
+def _max_norm(what, partials, max_norm):
+    if (partials is None) != (max_norm is None):
+        raise _lib.AdyoloHipError("%s: partials and max_norm go together (both or neither)" % what)
+    return float(max_norm) if max_norm is not None else 0.0
+
+
+def grad_sumsq(grad, partials, grad_scale=1.0):
+    """partials[k] = float64 sum of (grad * grad_scale)^2 over workgroup k's share: fixed grid, fixed order, no atomics."""
+    _chk(grad)
+    _chk_optim_dev("grad_sumsq", grad.numel(), None, None, partials)
+    if partials is None:
+        raise _lib.AdyoloHipError("grad_sumsq needs float64 partials")
+    _c("adyolo_grad_sumsq", _p(grad), grad.numel(), grad_scale, _p(partials), _stream())
+    return partials
+
+
+def grad_norm_dev(grad, partials, st_dev, max_norm, grad_scale=1.0):
+    """st_dev[2] = ||grad * grad_scale||_2 (summed in float64, written as fp32), st_dev[3] = min(1, max_norm / (norm + 1e-6)):
+    the clipping part of an optimizer step on its own.  Returns st_dev; no host sync."""
+    _chk(grad, st_dev)
+    _chk_optim_dev("grad_norm_dev", grad.numel(), None, st_dev, partials)
+    if partials is None:
+        raise _lib.AdyoloHipError("grad_norm_dev needs float64 partials")
+    _c("adyolo_grad_norm_dev", _p(grad), grad.numel(), grad_scale, _p(partials), max_norm, _p(st_dev), _stream())
+    return st_dev
+
+
+def _adam_ext(name, param, grad, exp_avg, exp_avg_sq, step_dev, st_dev, lr, betas, eps, weight_decay, grad_scale, partials,
+              max_norm):
+    _chk(param, grad, exp_avg, exp_avg_sq, st_dev)
+    _chk_optim_dev(name, param.numel(), step_dev, st_dev, partials)
+    _c("adyolo_" + name, _p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), lr, betas[0], betas[1], eps,
+       weight_decay, _p(step_dev), _p(st_dev), _p(partials), _max_norm(name, partials, max_norm), grad_scale, _stream())
+
+
+def adamw_step_dev(param, grad, exp_avg, exp_avg_sq, step_dev, st_dev, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
+                   weight_decay=1e-2, grad_scale=1.0, partials=None, max_norm=None):
+    """torch.optim.AdamW (decoupled decay) with the step counter on the device, like ``adam_step_dev``.  st_dev:
+    ``OPTIM_SCRATCH_FLOATS`` floats.  partials (``grad_sumsq_parts(n)`` float64) + max_norm: clip the gradient norm first
+    (st_dev[2] = the pre-clip norm); partials None = no clipping."""
+    _adam_ext("adamw_step_dev", param, grad, exp_avg, exp_avg_sq, step_dev, st_dev, lr, betas, eps, weight_decay, grad_scale,
+              partials, max_norm)
+
+
+def adam_clip_step_dev(param, grad, exp_avg, exp_avg_sq, step_dev, st_dev, partials, max_norm, lr=1e-3, betas=(0.9, 0.999),
+                       eps=1e-8, weight_decay=0.0, grad_scale=1.0):
+    """``adam_step_dev`` behind ``clip_grad_norm_(max_norm)``: the same arithmetic with the coefficient folded into grad_scale."""
+    if partials is None or max_norm is None:
+        raise _lib.AdyoloHipError("adam_clip_step_dev needs partials and max_norm (without clipping: adam_step_dev)")
+    _adam_ext("adam_clip_step_dev", param, grad, exp_avg, exp_avg_sq, step_dev, st_dev, lr, betas, eps, weight_decay,
+              grad_scale, partials, max_norm)
+
+
+def sgd_step_dev(param, grad, momentum_buf, step_dev, st_dev, lr=1e-3, weight_decay=0.0, momentum=0.0, dampening=0.0,
+                 nesterov=False, grad_scale=1.0, partials=None, max_norm=None):
+    """torch.optim.SGD.  momentum_buf: None when momentum == 0 (nothing is allocated or touched); the call that takes step_dev
+    from 0 to 1 initialises it with the gradient (no dampening)."""
+    _chk(param, grad, momentum_buf, st_dev)
+    _chk_optim_dev("sgd_step_dev", param.numel(), step_dev, st_dev, partials)
+    if momentum != 0.0 and momentum_buf is None:
+        raise _lib.AdyoloHipError("sgd_step_dev with momentum needs a momentum buffer")
+    _c("adyolo_sgd_step_dev", _p(param), _p(grad), _p(momentum_buf if momentum != 0.0 else None), param.numel(), lr,
+       weight_decay, momentum, dampening, int(bool(nesterov)), _p(step_dev), _p(st_dev),
+       _p(partials), _max_norm("sgd_step_dev", partials, max_norm), grad_scale, _stream())
+
+
 def nchw_to_nhwc8(x):
     _chk(x)
     b, c, h, w = x.shape

@@ -1,5 +1,5 @@
 """Train step of the AD-YOLO hot path: features (K1) -> encoder+head forward -> AD-YOLO loss ->
-backward -> [bucketed RCCL all-reduce] -> fused Adam.  Mirror of ``get_optimizers`` / ``train_one_epoch``
+backward -> [bucketed RCCL all-reduce] -> [gradient-norm clip] -> fused Adam / AdamW / SGD.  Mirror of ``get_optimizers`` / ``train_one_epoch``
 (/root/reference/src/train.py:29-62) with the data-parallel layer the reference lacks.
 
 FusedAdam keeps torch.optim.Adam's hyper-parameters and produces a ``state_dict`` in the stock Adam
@@ -14,22 +14,38 @@ from . import ops
 from .dist import BucketedAllReduce, FlatParameters
 
 
-class FusedAdam:
-    """Adam over a FlatParameters buffer (csrc/optim.hip); lr 1e-3, betas (0.9,0.999), eps 1e-8, wd 0 by
-    default like the reference config (src/configs/hyp_train.yaml:7-9)."""
+class _FusedOptimizer:
+    """What ``graph.StepGraphs`` and ``checkpoint`` use of an optimizer over a FlatParameters buffer: ``flat``, ``step_count``
+    (settable), ``_dev_step_value``, ``step_dev``, ``sync_device_step()``, ``replayed()``, ``zero_grad()``,
+    ``step(grad_scale=1.0)``, ``state_dict()`` / ``load_state_dict()``.
 
-    def __init__(self, flat: FlatParameters, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    The step counter lives ON THE DEVICE (incremented by the optimizer launch itself), so that no kernel argument changes from
+    step to step and a whole train step can be replayed from a hipGraph; ``step_count`` is the host's mirror of it (checkpoints,
+    torch.optim's state_dict layout).
+
+    max_norm (None = off): ``torch.nn.utils.clip_grad_norm_(parameters, max_norm)`` in front of the update, on the device: one
+    pass over the gradient buffer sums (g * grad_scale)^2 in float64 (fixed order, no atomics: the same bits on every call and
+    on every rank that holds the same reduced gradients), the step's one-workgroup prep kernel turns the partials into
+    ``clip_coef = min(1, max_norm / (norm + 1e-6))`` and the update multiplies it into ``grad_scale``.  ``grad_norm`` is then a
+    device tensor of one float, the pre-clip norm of the last step (what ``clip_grad_norm_`` returns); reading it is an
+    ordinary device read, nothing in here syncs.  ``max_norm`` is a constant of a recorded step, like ``lr``."""
+
+    kind = None                     # 'adam' | 'adamw' | 'sgd': the torch.optim layout ``checkpoint`` reads and writes
+
+    def _init_common(self, flat, max_norm):
         self.flat = flat
-        self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
-        self.exp_avg = torch.zeros_like(flat.flat)
-        self.exp_avg_sq = torch.zeros_like(flat.flat)
-        # the step counter lives ON THE DEVICE (incremented by the Adam launch itself), so that no kernel argument changes
-        # from step to step and a whole train step can be replayed from a hipGraph; `step_count` is the host's mirror of
-        # it (checkpoints, torch.optim.Adam's state_dict layout)
-        self.step_dev = torch.zeros(1, dtype=torch.int64, device=flat.flat.device)
-        self.bc_dev = torch.zeros(2, dtype=torch.float32, device=flat.flat.device)
+        self.max_norm = None if max_norm is None else float(max_norm)
+        dev = flat.flat.device
+        self.step_dev = torch.zeros(1, dtype=torch.int64, device=dev)
         self._step_count = 0
         self._dev_step_value = 0
+        self.st_dev = self.clip_partials = self.grad_norm = None
+        if self.max_norm is not None:
+            self.clip_partials = torch.zeros(ops.GRAD_SUMSQ_MAX_PARTS, dtype=torch.float64, device=dev)
+        if self.max_norm is not None or self.kind != "adam":
+            self.st_dev = torch.zeros(ops.OPTIM_SCRATCH_FLOATS, dtype=torch.float32, device=dev)
+        if self.max_norm is not None:
+            self.grad_norm = self.st_dev[2:3]
 
     @property
     def step_count(self):
@@ -45,7 +61,7 @@ class FusedAdam:
             self._dev_step_value = self._step_count
 
     def replayed(self):
-        """A captured step (graph.py) was replayed: the Adam launch inside it advanced the device counter."""
+        """A captured step (graph.py) was replayed: the optimizer launch inside it advanced the device counter."""
         self._step_count += 1
         self._dev_step_value = self._step_count
         ops.params_changed()
@@ -55,14 +71,13 @@ class FusedAdam:
 
     def step(self, grad_scale=1.0):
         self.sync_device_step()
-        ops.adam_step_dev(self.flat.flat, self.flat.flat_grad, self.exp_avg, self.exp_avg_sq, self.step_dev, self.bc_dev,
-                          self.lr, self.betas, self.eps, self.weight_decay, grad_scale)
+        self._launch(grad_scale)
         self._step_count += 1
         self._dev_step_value = self._step_count
         ops.params_changed()
 
     def state_dict(self):
-        """torch.optim.Adam's layout with parameter indices in ``model.parameters()`` order -- the ONE format this build
+        """The matching torch.optim layout with parameter indices in ``model.parameters()`` order -- the format this build
         reads and writes (``checkpoint.optimizer_state_dict``), interchangeable with the reference's
         ``optimizer.state_dict()`` / ``load_state_dict`` (train.py:149, 236)."""
         from . import checkpoint
@@ -73,12 +88,92 @@ class FusedAdam:
         checkpoint.load_optimizer_state_dict(self, None, sd)
 
 
+class FusedAdam(_FusedOptimizer):
+    """Adam over a FlatParameters buffer (csrc/optim.hip); lr 1e-3, betas (0.9,0.999), eps 1e-8, wd 0 by
+    default like the reference config (src/configs/hyp_train.yaml:7-9).  Without ``max_norm`` the step is
+    ``ops.adam_step_dev``; with it, the same arithmetic behind the clip coefficient (csrc/optim_ext.hip)."""
+
+    kind = "adam"
+
+    def __init__(self, flat: FlatParameters, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_norm=None):
+        self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
+        self.exp_avg = torch.zeros_like(flat.flat)
+        self.exp_avg_sq = torch.zeros_like(flat.flat)
+        self._init_common(flat, max_norm)
+        self.bc_dev = torch.zeros(2, dtype=torch.float32, device=flat.flat.device)
+
+    def _launch(self, grad_scale):
+        if self.max_norm is None:
+            ops.adam_step_dev(self.flat.flat, self.flat.flat_grad, self.exp_avg, self.exp_avg_sq, self.step_dev, self.bc_dev,
+                              self.lr, self.betas, self.eps, self.weight_decay, grad_scale)
+        else:
+            ops.adam_clip_step_dev(self.flat.flat, self.flat.flat_grad, self.exp_avg, self.exp_avg_sq, self.step_dev,
+                                   self.st_dev, self.clip_partials, self.max_norm, self.lr, self.betas, self.eps,
+                                   self.weight_decay, grad_scale)
+
+
+class FusedAdamW(FusedAdam):
+    """torch.optim.AdamW (decoupled weight decay, default 1e-2 like torch) over a FlatParameters buffer: Adam's state and
+    checkpoint layout, the group carrying ``decoupled_weight_decay: True``."""
+
+    kind = "adamw"
+
+    def __init__(self, flat: FlatParameters, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_norm=None):
+        super().__init__(flat, lr, betas, eps, weight_decay, max_norm)
+
+    def _launch(self, grad_scale):
+        ops.adamw_step_dev(self.flat.flat, self.flat.flat_grad, self.exp_avg, self.exp_avg_sq, self.step_dev, self.st_dev,
+                           self.lr, self.betas, self.eps, self.weight_decay, grad_scale, self.clip_partials, self.max_norm)
+
+
+class FusedSGD(_FusedOptimizer):
+    """torch.optim.SGD over a FlatParameters buffer: weight_decay, momentum, dampening, nesterov.  With ``momentum == 0`` (the
+    reference's own call, ``optim.SGD(lr=..., weight_decay=...)``) no buffer is allocated or touched.  With momentum the first
+    step after construction -- or after loading a state without buffers -- sets ``momentum_buffer`` to the gradient (no
+    dampening), as torch does; "first" is ``step_count == 0``, decided on the device from the step counter.  torch's SGD state
+    holds no step count, so after loading a state WITH buffers ``step_count`` restarts at 1: it counts the steps since
+    construction or load, and only whether it is zero matters."""
+
+    kind = "sgd"
+
+    def __init__(self, flat: FlatParameters, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False,
+                 max_norm=None):
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        self._init_common(flat, max_norm)
+        self.lr, self.momentum, self.dampening, self.weight_decay = lr, momentum, dampening, weight_decay
+        self.nesterov = bool(nesterov)
+        self.momentum_buffer = torch.zeros_like(flat.flat) if momentum != 0 else None
+
+    @property
+    def first_step(self):
+        """the next step initialises the momentum buffer instead of updating it"""
+        return self._step_count == 0
+
+    def _launch(self, grad_scale):
+        ops.sgd_step_dev(self.flat.flat, self.flat.flat_grad, self.momentum_buffer, self.step_dev, self.st_dev, self.lr,
+                         self.weight_decay, self.momentum, self.dampening, self.nesterov, grad_scale, self.clip_partials,
+                         self.max_norm)
+
+
 def get_optimizers(params: dict, flat: FlatParameters):
-    """reference train.py:29-37 (only Adam is on the gfx950 path)."""
+    """reference train.py:29-37: ``optim`` 'Adam' | 'AdamW' | 'SGD' with ``lr`` / ``weight_decay``.  Optional keys of
+    ``train_config``: ``momentum``, ``dampening``, ``nesterov`` (SGD; the reference passes none of them) and ``clip_grad_norm``
+    (the max_norm of the reference's ``clip_grad_norm_`` line, train.py:54; absent or None = off)."""
     tc = params["train_config"]
-    if tc.get("optim", "Adam") == "Adam":
-        return FusedAdam(flat, lr=tc.get("lr", 1e-3), weight_decay=tc.get("weight_decay", 0.0))
-    raise NotImplementedError(tc["optim"])
+    name = tc.get("optim", "Adam")
+    clip = tc.get("clip_grad_norm")
+    if name == "Adam":
+        if clip is None:
+            return FusedAdam(flat, lr=tc.get("lr", 1e-3), weight_decay=tc.get("weight_decay", 0.0))
+        return FusedAdam(flat, lr=tc.get("lr", 1e-3), weight_decay=tc.get("weight_decay", 0.0), max_norm=clip)
+    if name == "AdamW":
+        return FusedAdamW(flat, lr=tc.get("lr", 1e-3), weight_decay=tc.get("weight_decay", 1e-2), max_norm=clip)
+    if name == "SGD":
+        return FusedSGD(flat, lr=tc.get("lr", 1e-3), weight_decay=tc.get("weight_decay", 0.0),
+                        momentum=tc.get("momentum", 0.0), dampening=tc.get("dampening", 0.0),
+                        nesterov=tc.get("nesterov", False), max_norm=clip)
+    raise NotImplementedError(name)
 
 
 class TrainStep:
@@ -94,6 +189,11 @@ class TrainStep:
     autograd path, which is what bounds the reference's own shapes (16 x 20 s chunks: the GPU work of a step is shorter than
     its launch sequence).  The first step at a new shape runs eagerly, the second is captured; results are bit-identical to
     the eager path.  Single-process only (under data parallelism the RCCL hooks stay eager).
+
+    Gradient clipping (``train_config['clip_grad_norm']``) belongs to the optimizer: it acts on the REDUCED gradients times the
+    ``grad_scale`` handed to ``optimizer.step`` (i.e. on the gradient the update uses).  Under data parallelism every rank holds
+    the same reduced buffer and the norm is summed in a fixed order, so every rank derives the same coefficient, bit for bit,
+    with no extra collective.  ``trainer.optimizer.grad_norm`` holds the pre-clip norm of the last step on the device.
     """
 
     def __init__(self, model, criterion, feature_extractor, params=None, n_buckets=4, lr=1e-3, graph=None, exact=None):
@@ -150,7 +250,8 @@ class TrainStep:
 def train_one_epoch(params: dict, dataloader, model, optimizer, criterion, device):
     """Mirror of ``train_one_epoch`` (/root/reference/src/train.py:40-62) for loaders that yield pre-computed features:
     ``for feat (B,7,T,64), label in dataloader`` -> forward, zero_grad, loss, backward, step; returns the mean loss.
-    Works with ``torch.optim.Adam`` or ``FusedAdam`` (``TrainStep`` is the faster raw-audio + flat-buffer path).
+    Works with a ``torch.optim`` optimizer or ``FusedAdam`` / ``FusedAdamW`` / ``FusedSGD`` (``TrainStep`` is the faster raw-audio +
+    flat-buffer path).
     The per-step ``loss.item()`` of the reference (a device sync every iteration, train.py:57) is replaced by one
     device-side accumulation and a single sync at the end of the epoch."""
     model.train()

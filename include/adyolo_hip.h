@@ -643,6 +643,36 @@ int adyolo_adam_step_dev(float *param, const float *grad, float *exp_avg, float 
                          float beta1, float beta2, float eps, float weight_decay, uint64_t *step_dev, float *bc_dev,
                          float grad_scale, void *stream);
 
+/* K11x AdamW, SGD and gradient-norm clipping on the same flat buffers (csrc/optim_ext.hip; the reference picks its optimizer
+ * by name, src/train.py:29-37, and clips with clip_grad_norm_, src/train.py:54).  Device-counter forms only: every call bumps
+ * step_dev itself and no argument changes from step to step (hipGraph-replayable).  All float buffers must be 16-byte aligned
+ * (ADYOLO_EINVAL otherwise); n need not be a multiple of 4.
+ *   st_dev    4 floats of scratch: {step size, 1/sqrt(bias correction 2)} (Adam / AdamW) or {first-step flag, 0} (SGD),
+ *             total_norm (the pre-clip norm of grad * grad_scale, written when clipping is on), clip_coef
+ *   partials  adyolo_grad_sumsq_parts(n) doubles of scratch, or NULL = no clipping (clip_coef = 1; max_norm ignored).
+ *             With it: clip_coef = min(1, max_norm / (total_norm + 1e-6)) (torch.nn.utils.clip_grad_norm_), multiplied into
+ *             grad_scale by the update.  The norm is summed in float64 in a fixed order: the same bits on every call. */
+long adyolo_grad_sumsq_parts(long n);
+/* partials[k] = float64 sum of (grad * grad_scale)^2 over the k-th workgroup's share */
+int  adyolo_grad_sumsq(const float *grad, long n, float grad_scale, double *partials, void *stream);
+/* grad_sumsq + the norm / coefficient part of the prep kernel alone: st_dev[2] = total_norm, st_dev[3] = clip_coef */
+int  adyolo_grad_norm_dev(const float *grad, long n, float grad_scale, double *partials, float max_norm, float *st_dev,
+                          void *stream);
+/* torch.optim.AdamW: p *= 1 - lr * weight_decay, then Adam's moments and update */
+int  adyolo_adamw_step_dev(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, long n, float lr, float beta1,
+                           float beta2, float eps, float weight_decay, uint64_t *step_dev, float *st_dev, double *partials,
+                           float max_norm, float grad_scale, void *stream);
+/* adyolo_adam_step_dev's arithmetic with the clip coefficient (partials must not be NULL) */
+int  adyolo_adam_clip_step_dev(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, long n, float lr,
+                               float beta1, float beta2, float eps, float weight_decay, uint64_t *step_dev, float *st_dev,
+                               double *partials, float max_norm, float grad_scale, void *stream);
+/* torch.optim.SGD: g' = grad * scale + wd * p; momentum != 0: buf = g' on the step that takes step_dev from 0 to 1, else
+ * buf = momentum * buf + (1 - dampening) * g'; p -= lr * (nesterov ? g' + momentum * buf : buf).  momentum == 0: p -= lr * g',
+ * momentum_buf may be NULL and is not touched. */
+int  adyolo_sgd_step_dev(float *param, const float *grad, float *momentum_buf, long n, float lr, float weight_decay,
+                         float momentum, float dampening, int nesterov, uint64_t *step_dev, float *st_dev, double *partials,
+                         float max_norm, float grad_scale, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * K9a multi-head self-attention core, flash style on the exact-fp32 matrix cores (csrc/attention.hip).
  *     replaces the energy / softmax / dropout / context products of MultiHeadAttention.forward

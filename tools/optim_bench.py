@@ -1,0 +1,147 @@
+"""Optimizers and gradient clipping in the train step: what each choice costs (device events around synchronised work, warmed
+up, repeated).
+
+  step      one hipGraph-replayed TrainStep at 16 x 20 s (the reference's batch_size / chunk) and at 64 x 60 s (the bench shape)
+            with 'Adam' (the path this build has always had: ops.adam_step_dev, the baseline), 'AdamW', 'SGD' (plain, as the
+            reference calls it) and 'Adam' with clip_grad_norm 3
+  kernels   the optimizer launches alone on buffers of the real model's flat size (6.68 M floats): adam_step_dev (baseline),
+            adamw_step_dev, sgd_step_dev without / with momentum, adam_clip_step_dev, grad_norm_dev (sum of squares + prep)
+
+At 16 x 20 s the four trainers live side by side and alternate inside each repeat; at 64 x 60 s they are built one after the
+other (activations of one recorded step at a time).  The median of the repeats is reported (ms per call).
+
+  python tools/optim_bench.py [--reps 7] [--iters 10] [--only step16] [--only step64] [--only kernels] [--json out.json]
+"""
+import argparse
+import gc
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+VARIANTS = {"adam": {"optim": "Adam"},
+            "adamw": {"optim": "AdamW", "weight_decay": 0.01},
+            "sgd": {"optim": "SGD"},
+            "adam_clip3": {"optim": "Adam", "clip_grad_norm": 3.0}}
+
+
+def timed(fns, reps, iters):
+    """fns: {name: callable}; per repeat every variant runs ``iters`` times between two events, variants alternating ->
+    {name: median ms per call}, {name: all repeats}."""
+    out = {k: [] for k in fns}
+    for _ in range(reps):
+        for name, fn in fns.items():
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(iters):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            out[name].append(e0.elapsed_time(e1) / iters)
+    return {k: round(statistics.median(v), 4) for k, v in out.items()}, {k: [round(x, 4) for x in v] for k, v in out.items()}
+
+
+def make_trainer(b, n, variant):
+    from adyolo_amd.features import FeatureExtractor
+    from adyolo_amd.train import TrainStep
+    from adyolo_amd.wrapper import WrapperCriterion, WrapperModel
+    from __graft_entry__ import _params
+    prm = _params()
+    prm["train_config"].update(VARIANTS[variant])
+    torch.manual_seed(0)
+    model = WrapperModel((1, 7, n // 600, 64), (), prm).to("cuda:0")
+    return TrainStep(model, WrapperCriterion(prm), FeatureExtractor(None, "cuda:0"), prm, graph=True)
+
+
+def warm(tr, audio, target):
+    for _ in range(4):                         # eager warm-up, capture, replays
+        tr.step(audio, target)
+    torch.cuda.synchronize()
+    assert tr.graphs is not None and tr.graphs.captures == 1 and tr.graphs.replays >= 2, "the step was not recorded"
+
+
+def bench_step(b, seconds, reps, iters, together):
+    from adyolo_amd.datasets import synthetic_audio, synthetic_targets
+    n = 24000 * seconds
+    audio = synthetic_audio(b, n, seed=2).to("cuda:0")
+    target = synthetic_targets(b, n // 2400, 12, seed=3)
+    if together:
+        trs = {v: make_trainer(b, n, v) for v in VARIANTS}
+        for tr in trs.values():
+            warm(tr, audio, target)
+        return timed({v: (lambda tr=tr: tr.step(audio, target)) for v, tr in trs.items()}, reps, iters)
+    med, runs = {}, {}
+    for v in VARIANTS:
+        tr = make_trainer(b, n, v)
+        warm(tr, audio, target)
+        m, r = timed({v: lambda: tr.step(audio, target)}, reps, iters)
+        med.update(m)
+        runs.update(r)
+        del tr
+        gc.collect()
+        torch.cuda.empty_cache()
+    return med, runs
+
+
+def bench_kernels(reps, iters):
+    from adyolo_amd import ops
+    n = 6682096                                 # the flat buffer of se-resnet34 + the AD-YOLO head (6 682 093 padded to 4)
+    g = torch.Generator().manual_seed(1)
+    p = torch.randn(n, generator=g).to("cuda:0")
+    grad = (torch.randn(n, generator=g) * 1e-2).to("cuda:0")
+    m, v, buf = torch.zeros_like(p), torch.zeros_like(p), torch.zeros_like(p)
+    step_dev = torch.zeros(1, dtype=torch.int64, device="cuda:0")
+    bc = torch.zeros(2, device="cuda:0")
+    st = torch.zeros(ops.OPTIM_SCRATCH_FLOATS, device="cuda:0")
+    parts = torch.zeros(ops.GRAD_SUMSQ_MAX_PARTS, dtype=torch.float64, device="cuda:0")
+    fns = {
+        "adam_step_dev": lambda: ops.adam_step_dev(p, grad, m, v, step_dev, bc),
+        "adamw_step_dev": lambda: ops.adamw_step_dev(p, grad, m, v, step_dev, st),
+        "sgd_step_dev": lambda: ops.sgd_step_dev(p, grad, None, step_dev, st),
+        "sgd_step_dev_momentum": lambda: ops.sgd_step_dev(p, grad, buf, step_dev, st, momentum=0.9),
+        "adam_clip_step_dev": lambda: ops.adam_clip_step_dev(p, grad, m, v, step_dev, st, parts, 3.0),
+        "grad_norm_dev": lambda: ops.grad_norm_dev(grad, parts, st, 3.0),
+    }
+    for f in fns.values():
+        for _ in range(3):
+            f()
+    return timed(fns, reps, iters)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--only", choices=["step16", "step64", "kernels"], action="append")
+    ap.add_argument("--json")
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "optim_bench needs the GPU"
+    import adyolo_amd  # noqa: F401
+    only = a.only or ["step16", "step64", "kernels"]
+    res = {}
+    if "kernels" in only:
+        res["kernels_6p68M_ms"], res["kernels_runs"] = bench_kernels(a.reps, max(20, a.iters * 5))
+    if "step16" in only:
+        res["graph_step_16x20s_ms"], res["graph_step_16x20s_runs"] = bench_step(16, 20, a.reps, a.iters, together=True)
+    if "step64" in only:
+        res["graph_step_64x60s_ms"], res["graph_step_64x60s_runs"] = bench_step(64, 60, max(3, a.reps // 2), max(2, a.iters // 3),
+                                                                              together=False)
+    for k in ("kernels_6p68M_ms", "graph_step_16x20s_ms", "graph_step_64x60s_ms"):
+        if k in res:
+            print(k, res[k])
+    line = json.dumps(res)
+    print(line)
+    if a.json:
+        with open(a.json, "w") as fh:
+            fh.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

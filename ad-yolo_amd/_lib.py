@@ -96,6 +96,8 @@ SIGNATURES = {
     "adyolo_seddoa_loss": (I, [P] * 5 + [L, I, I, I, F, F, P]),
     "adyolo_adpit_loss": (I, [P] * 5 + [L, I, P]),
     "adyolo_classwise_decode": (I, [P, P, L, I, I, P]),
+    "adyolo_classwise_select_workspace_words": (L, [L, I, I]),
+    "adyolo_classwise_select": (I, [P] * 4 + [L, I, I, F, F, P]),
     "adyolo_conv_gemm": (I, [P, P, P, P] + [I] * 13 + [P]),
     "adyolo_pack_wk": (I, [P, P, I, I, I, I, I, P]),
     "adyolo_maxpool3_fwd": (I, [P, P, P, I, I, I, I, P]),

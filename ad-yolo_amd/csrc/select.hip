@@ -17,6 +17,7 @@
 //   2. select_scan_kernel (one workgroup): exclusive scan of the slot counts, per-frame row counts and the total.
 //   3. select_compact_kernel: slot rows -> compacted [frame, class, x, y, z].
 // Angular distances use the float32 formula of postprocess._ang_dist_deg evaluated in its order without contraction.
+// The class-wise heads (seddoa / accdoa / adpit) select with adyolo_classwise_select at the end of this file.
 #include "common.hpp"
 
 namespace adyolo {
@@ -271,6 +272,88 @@ __global__ __launch_bounds__(64) void select_compact_kernel(const float *__restr
     }
 }
 
+// ---------------------------------------------------------------------------------------------- class-wise heads
+// postprocess.classwise_select (get_seddoa_output / get_accdoa_output / get_adpit_output, src/datasets.py:536-739) on the
+// records of adyolo_classwise_decode (csrc/losses.hip): up to three rows per (frame, class).  Three launches: the counts of
+// every (frame, class), select_scan_kernel above, and a pass that evaluates the slots again and stores them at the scanned
+// offsets -- the rows are a pure function of one 16- or 64-byte record, so evaluating twice is cheaper than parking them.
+// All float32, the sums in the host's operand order.
+
+// the rows of one (frame, class) in the reference's order, each handed to emit(x, y, z)
+template <int MODE, class Emit>
+__device__ __forceinline__ void classwise_slots(const float *__restrict__ dec, long slot, float conf_t, float unify_t,
+                                                Emit emit) {
+#pragma clang fp contract(off)                                   // nothing here multiplies today; kept so that it stays exact
+    const bool one_above = 1.0f > conf_t;                        // the reference's second test, on the boolean (_above)
+    if (MODE != ADYOLO_CLASSWISE_ADPIT) {
+        const f32x4 r = reinterpret_cast<const f32x4 *>(dec)[slot];
+        if (r[0] > conf_t && one_above) emit(r[1], r[2], r[3]);
+        return;
+    }
+    const f32x4 *p = reinterpret_cast<const f32x4 *>(dec) + slot * 4;
+    const f32x4 r0 = p[0], r1 = p[1], r2 = p[2], r3 = p[3];
+    const float ax = r0[3], ay = r1[0], az = r1[1], bx = r1[2], by = r1[3], bz = r2[0], dx = r2[1], dy = r2[2], dz = r2[3];
+    const bool s0 = r0[0] > conf_t, s1 = r0[1] > conf_t, s2 = r0[2] > conf_t;
+    const bool q0 = s0 && one_above, q1 = s1 && one_above, q2 = s2 && one_above;
+    const bool p01 = s0 && s1 && r3[0] < unify_t, p12 = s1 && s2 && r3[1] < unify_t, p20 = s2 && s0 && r3[2] < unify_t;
+    const int n = (int)p01 + (int)p12 + (int)p20;
+    if (n == 0) {                                                 // every active track, in track order
+        if (q0) emit(ax, ay, az);
+        if (q1) emit(bx, by, bz);
+        if (q2) emit(dx, dy, dz);
+    } else if (n >= 2) {                                          // one event: the mean of all three
+        emit(((ax + bx) + dx) / 3.f, ((ay + by) + dy) / 3.f, ((az + bz) + dz) / 3.f);
+    } else if (p01) {                                             // one pair: the third track, then the mean of the pair
+        if (q2) emit(dx, dy, dz);
+        emit((ax + bx) / 2.f, (ay + by) / 2.f, (az + bz) / 2.f);
+    } else if (p12) {
+        if (q0) emit(ax, ay, az);
+        emit((bx + dx) / 2.f, (by + dy) / 2.f, (bz + dz) / 2.f);
+    } else {
+        if (q1) emit(bx, by, bz);
+        emit((dx + ax) / 2.f, (dy + ay) / 2.f, (dz + az) / 2.f);
+    }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void classwise_count_kernel(const float *__restrict__ dec, int *__restrict__ count,
+                                                              long n_slots, float conf_t, float unify_t) {
+    const long slot = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= n_slots) return;
+    int n = 0;
+    classwise_slots<MODE>(dec, slot, conf_t, unify_t, [&](float, float, float) { ++n; });
+    count[slot] = n;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void classwise_write_kernel(const float *__restrict__ dec, const int *__restrict__ offs,
+                                                              float *__restrict__ rows, long n_slots, int C, float conf_t,
+                                                              float unify_t) {
+    const long slot = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= n_slots) return;
+    const float fr = (float)(slot / C), cl = (float)(slot % C);
+    float *dst = rows + (size_t)offs[slot] * 5;
+    classwise_slots<MODE>(dec, slot, conf_t, unify_t, [&](float x, float y, float z) {
+        dst[0] = fr, dst[1] = cl, dst[2] = x, dst[3] = y, dst[4] = z;
+        dst += 5;
+    });
+}
+
+template <int MODE>
+static int classwise_select_launch(const float *dec, int *count, int *offs, float *rows, int *frame_counts, long n_frames,
+                                   int C, float conf_t, float unify_t, hipStream_t st) {
+    const long n_slots = n_frames * C;
+    const dim3 grid(cdiv(n_slots, 256)), block(256);
+    hipLaunchKernelGGL(classwise_count_kernel<MODE>, grid, block, 0, st, dec, count, n_slots, conf_t, unify_t);
+    int rc = check_launch("classwise_select_count");
+    if (rc) return rc;
+    hipLaunchKernelGGL(select_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, st, count, offs, frame_counts, n_frames, C);
+    rc = check_launch("classwise_select_scan");
+    if (rc) return rc;
+    hipLaunchKernelGGL(classwise_write_kernel<MODE>, grid, block, 0, st, dec, offs, rows, n_slots, C, conf_t, unify_t);
+    return check_launch("classwise_select_write");
+}
+
 }  // namespace adyolo
 
 using namespace adyolo;
@@ -308,4 +391,31 @@ extern "C" int adyolo_yolo_select(const float *dec, float *ws, float *rows, int 
     hipLaunchKernelGGL(select_compact_kernel, dim3((unsigned)g), dim3(64), 0, st, slot_xyz, count, offs, rows, n_slots,
                        n_anchor, C);
     return check_launch("yolo_select_compact");
+}
+
+static inline bool classwise_mode_ok(int mode) {
+    return mode == ADYOLO_CLASSWISE_SEDDOA || mode == ADYOLO_CLASSWISE_ACCDOA || mode == ADYOLO_CLASSWISE_ADPIT;
+}
+
+extern "C" long adyolo_classwise_select_workspace_words(long n_frames, int C, int mode) {
+    if (n_frames <= 0 || C <= 0 || !classwise_mode_ok(mode)) return 0;
+    return 2 * n_frames * C;
+}
+
+extern "C" int adyolo_classwise_select(const float *dec, float *ws, float *rows, int *frame_counts, long n_frames, int C,
+                                       int mode, float conf_thresh, float unify_thresh, void *stream) {
+    ADYOLO_REQUIRE(dec && ws && rows && frame_counts, ADYOLO_EINVAL, "classwise_select: null pointer");
+    ADYOLO_REQUIRE(n_frames > 0 && C > 0, ADYOLO_EINVAL, "classwise_select: %ld frames x %d classes", n_frames, C);
+    ADYOLO_REQUIRE(((uintptr_t)dec & 15) == 0, ADYOLO_EINVAL, "classwise_select: dec is not 16-byte aligned");
+    ADYOLO_REQUIRE(classwise_mode_ok(mode), ADYOLO_ENOSUP, "classwise_select: unknown mode %d", mode);
+    ADYOLO_REQUIRE(n_frames < (1L << 31) / (3L * C), ADYOLO_ENOSUP,
+                   "classwise_select: %ld frames x %d classes x 3 rows do not fit 32-bit row counts", n_frames, C);
+    int *count = reinterpret_cast<int *>(ws);
+    int *offs = count + n_frames * C;
+    hipStream_t st = as_stream(stream);
+    if (mode == ADYOLO_CLASSWISE_ADPIT)
+        return classwise_select_launch<ADYOLO_CLASSWISE_ADPIT>(dec, count, offs, rows, frame_counts, n_frames, C, conf_thresh,
+                                                               unify_thresh, st);
+    return classwise_select_launch<ADYOLO_CLASSWISE_SEDDOA>(dec, count, offs, rows, frame_counts, n_frames, C, conf_thresh,
+                                                            unify_thresh, st);
 }

@@ -984,6 +984,36 @@ def yolo_select(decoded, nb_classes, conf, clss, unify, nms="conn-merge", trim=T
     return rows[:total], counts[:frames]
 
 
+def classwise_select(decoded, nb_classes, mode, conf, unify=None, trim=True):
+    """decoded [frames][C][rec] (``classwise_decode``) -> (rows (N, 5) [frame, class, x, y, z], counts (frames,) int32), both
+    on the device (adyolo_hip.h, ``adyolo_classwise_select``): the thresholds and, for adpit, the unification of
+    ``postprocess.classwise_select`` with the same rows in the same order, bit for bit.  mode: a loss name or its integer code;
+    unify: needed for adpit, not read otherwise.  The thresholds are compared as NumPy compares them with the host path's
+    float32 arrays (``np_f32_threshold``).  One 4-byte read of the row total synchronises the stream.  trim=False: no read and
+    no synchronisation; rows is the whole capacity buffer, of which the first counts.sum() rows are written (what
+    ``seld_score`` takes)."""
+    m = CLASSWISE_MODES[mode] if isinstance(mode, str) else int(mode)
+    if m not in CLASSWISE_REC:
+        raise _lib.AdyoloHipError("classwise_select: unknown mode %r" % (mode,))
+    if m == CLASSWISE_MODES["adpit"] and unify is None:
+        raise ValueError("classwise_select: adpit needs a unify threshold")
+    _chk(decoded)
+    c, rec = int(nb_classes), CLASSWISE_REC[m]
+    frames = decoded.shape[0] if decoded.dim() > 0 else 0
+    if frames <= 0 or c <= 0 or tuple(decoded.shape) != (frames, c, rec):
+        raise _lib.AdyoloHipError("classwise_select: decoded %s is not [frames][%d][%d]" % (tuple(decoded.shape), c, rec))
+    per_class = 3 if m == CLASSWISE_MODES["adpit"] else 1
+    ws = _new(decoded, _lib.load().adyolo_classwise_select_workspace_words(frames, c, m))
+    rows = _new(decoded, frames * c * per_class, 5)
+    counts = torch.empty(frames + 1, dtype=torch.int32, device=decoded.device)
+    _c("adyolo_classwise_select", _p(decoded), _p(ws), _p(rows), _p(counts), frames, c, m, np_f32_threshold(conf, ">"),
+       np_f32_threshold(unify, "<") if m == CLASSWISE_MODES["adpit"] else 0.0, _stream())
+    if not trim:
+        return rows, counts[:frames]
+    total = int(to_host(counts[frames:])[0])
+    return rows[:total], counts[:frames]
+
+
 SELD_STATUS = ((1, "more than 1024 predictions in one frame and class"),      # ADYOLO_SELD_* in adyolo_hip.h
                (2, "more than 8 reference events in one frame and class"),
                (4, "frame counts negative or summing past the rows given"),

@@ -12,7 +12,9 @@ rows in the same order) and copy only the selected rows to the host.
 The class-wise heads (``--loss seddoa | masked-seddoa | accdoa | adpit``, ``get_seddoa_output`` / ``get_accdoa_output`` /
 ``get_adpit_output``, datasets.py:536-739) follow the same split: a threshold-free GPU decode (csrc/losses.hip
 ``adyolo_classwise_decode``: per (frame, class) the track activities, their xyz and, for adpit, the pair distances), then a
-vectorised host ``select`` per threshold (``classwise_select``).
+vectorised host ``select`` per threshold (``classwise_select``).  Opt-in here too, ``select_device`` /
+``postprocess(on_device=True)`` run the thresholds and the ADPIT unification on the GPU (csrc/select.hip
+``adyolo_classwise_select``: the same rows, bit for bit) and copy only the selected rows to the host.
 """
 import math
 
@@ -249,15 +251,20 @@ class LabelPostProcessor:
         return nms_decoded(decoded, self.nb_classes, self.conf_thresh, self.clss_thresh, self.unify_thresh, self.nms)
 
     def select_device_rows(self, decoded_dev, n_clips=1, trim=True):
-        """``select`` on the device for the adyolo head (``ops.yolo_select``: the same rows in the same order) on a
-        ``decode_device`` result of n_clips clips -> (rows (N, 5) [frame, class, x, y, z], counts (n_clips * T',) int32, clip
-        after clip), both on the device.  trim=False: no synchronisation, rows is the capacity buffer of which the first counts.sum() are
-        written (what ``seld_metrics.DeviceSELDScorer.add_rows`` takes)."""
+        """``select`` on the device (adyolo: ``ops.yolo_select``; class-wise heads: ``ops.classwise_select`` with the current
+        conf_thresh and unify_thresh; the same rows in the same order) on a ``decode_device`` result of n_clips clips ->
+        (rows (N, 5) [frame, class, x, y, z], counts (n_clips * T',) int32, clip after clip), both on the device.
+        trim=False: no synchronisation, rows is the capacity buffer of which the first counts.sum() are written (what
+        ``seld_metrics.DeviceSELDScorer.add_rows`` takes).  There is no host implementation behind this name: a class-wise
+        decode that is not on a HIP device raises NotImplementedError (``select`` is the host path)."""
         from . import ops
-        if self.loss != "adyolo":
-            raise NotImplementedError("select_device: adyolo only (the class-wise heads select with classwise_select)")
+        if self.loss in CLASSWISE and not getattr(decoded_dev, "is_cuda", False):
+            raise NotImplementedError("select_device: the class-wise heads select on a HIP device only (the host path is "
+                                      "select / classwise_select)")
         if n_clips < 1 or decoded_dev.shape[0] % n_clips:
             raise ValueError("select_device_rows: %d frames for %d clips" % (decoded_dev.shape[0], n_clips))
+        if self.loss in CLASSWISE:
+            return ops.classwise_select(decoded_dev, self.nb_classes, self.loss, self.conf_thresh, self.unify_thresh, trim=trim)
         return ops.yolo_select(decoded_dev, self.nb_classes, self.conf_thresh, self.clss_thresh, self.unify_thresh, self.nms,
                                trim=trim)
 

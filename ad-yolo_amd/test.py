@@ -38,8 +38,9 @@ def sweep_conf_thresh(dataloader, filelist, model, criterion, postprocessor, sco
     datasets.py:532-534).  The reference re-runs the whole validation epoch for each of the nine thresholds; the network
     output does not depend on the threshold, so here the model runs ONCE per file and only the host-side selection/NMS,
     the CSV files and the metrics are redone per threshold -- same files, same scores, a ninth of the forward passes.
-    device_select: every file's decode stays on the device (~6 MB per 60 s clip) and the nine selections run there
-    (``postprocessor.select_device``); only the selected rows come back to the host.
+    device_select: every file's decode stays on the device (~6 MB per 60 s clip for adyolo, ~0.5 MB for adpit) and the nine
+    selections run there (``postprocessor.select_device``: the AD-YOLO NMS or, for the class-wise heads seddoa / masked-seddoa /
+    accdoa / adpit, the thresholds and the ADPIT unification); only the selected rows come back to the host.
     device_score: ``scorer`` is a ``seld_metrics.DeviceSELDScorer``; every threshold's rows are scored on the device (device
     rows with device_select, ``add_rows``; host rows otherwise, ``add_dict``) without CSV files, and only the last threshold's
     CSV files are written, so ``output_pth`` ends up as the host sweep leaves it.
@@ -105,8 +106,9 @@ def test_epoch_audio(dataset, model, features, criterion, postprocessor, device,
     EQUAL length may share one forward pass (batch_size > 1: same CSV files; the 60 s clips of a DCASE split all qualify) --
     3 ms per clip at B = 1 against ~1 ms at B = 8 on MI355X.  The loss stays per clip (its normalisers are per call), averaged
     over the clips like the reference's.  forward: optional ``graph.ForwardGraphs`` (K1 + model + decode replayed from a
-    hipGraph per clip length); default: eager calls.  device_select: the decoded batch is selected on the device
-    (``postprocessor.select_device``, launched after the graph replay, not recorded in it) and only the rows come back.
+    hipGraph per clip length); default: eager calls.  device_select: the decoded batch is selected on the device, whatever the
+    head (``postprocessor.select_device``: adyolo and the class-wise heads alike, with the post-processor's thresholds as they
+    are at the call; launched after the graph replay, not recorded in it) and only the rows come back.
     device_scorer: a ``seld_metrics.DeviceSELDScorer`` the selected rows of every batch are also added to (the device rows
     with device_select); the CSV files are written all the same, and the caller reads ``device_scorer.scores()``."""
     from . import ops

@@ -472,7 +472,8 @@ int adyolo_adpit_loss(const float *out, const float *tgt, float *loss, float *do
 
 /* Class-wise inference decode (LabelPostProcessor.get_seddoa_output / get_accdoa_output / get_adpit_output,
  * src/datasets.py:536-739), threshold-free: one record of ADYOLO_CLASSWISE_REC(mode) floats per (frame, class),
- * dec [n_frames][C][rec]; the conf threshold and the ADPIT unify decision stay on the host (ad-yolo_amd/postprocess.py).
+ * dec [n_frames][C][rec]; by default the conf threshold and the ADPIT unify decision stay on the host
+ * (ad-yolo_amd/postprocess.py); adyolo_classwise_select below runs them on the device.
  *   SEDDOA  out [n_frames][4C]: [act = out[c], x, y, z = out[C+c], out[2C+c], out[3C+c]]
  *   ACCDOA  out [n_frames][3C]: [act = sqrt(x*x + y*y + z*z), x, y, z = out[c], out[C+c], out[2C+c]]
  *   ADPIT   out [n_frames][9C] (track k at 3kC): [act0, act1, act2, x0, y0, z0, x1, y1, z1, x2, y2, z2, d01, d12, d20, 0],
@@ -484,6 +485,30 @@ int adyolo_adpit_loss(const float *out, const float *tgt, float *loss, float *do
 #define ADYOLO_CLASSWISE_ADPIT  2
 #define ADYOLO_CLASSWISE_REC(mode) ((mode) == ADYOLO_CLASSWISE_ADPIT ? 16 : 4)
 int adyolo_classwise_decode(const float *out, float *dec, long n_frames, int C, int mode, void *stream);
+
+/* Class-wise inference selection (csrc/select.hip), opt-in: what postprocess.classwise_select does on the host (the
+ * thresholds and, for ADPIT, the unification of get_seddoa_output / get_accdoa_output / get_adpit_output), on the decode
+ * above, bit for bit.
+ *   dec   [n_frames][C][ADYOLO_CLASSWISE_REC(mode)] from adyolo_classwise_decode, 16-byte aligned
+ *   ws    adyolo_classwise_select_workspace_words(n_frames, C, mode) = 2 * n_frames * C words (counts and offsets)
+ *   rows  capacity n_frames * C * (mode == ADYOLO_CLASSWISE_ADPIT ? 3 : 1) rows of [frame, class, x, y, z] float32; the
+ *         first total rows are written: frames ascending, classes ascending, within a class the order below
+ *   frame_counts  [n_frames + 1] int32: rows per frame, then the total at [n_frames] (as adyolo_yolo_select; what
+ *         adyolo_seld_score takes)
+ *   SEDDOA / ACCDOA: one row (xyz copied) where act > conf_thresh and 1.0f > conf_thresh (the reference tests the boolean
+ *   against the threshold a second time).  ADPIT: sed_k = act_k > conf_thresh, q_k = sed_k and 1.0f > conf_thresh; the pairs
+ *   (0,1), (1,2), (2,0) are one event when both are sed and d < unify_thresh; with n such pairs
+ *     n == 0  the tracks with q_k, in track order
+ *     n == 1  the third track if its q holds, then the mean of the pair: (a + b) / 2, (b + d) / 2 or (d + a) / 2
+ *     n >= 2  ((a + b) + d) / 3
+ *   in float32 with correctly rounded division (float32 compares: the caller rounds the thresholds the way its host
+ *   comparison would; unify_thresh is not read for the other modes).  Deterministic: positions come from an exclusive scan
+ *   of the per-(frame, class) counts, never from atomics.  No host synchronisation.
+ * EINVAL: null pointer, n_frames or C <= 0, dec not 16-byte aligned; ENOSUP: unknown mode, or n_frames * C * 3 rows do not
+ * fit 32-bit row counts. */
+long adyolo_classwise_select_workspace_words(long n_frames, int C, int mode);
+int  adyolo_classwise_select(const float *dec, float *ws, float *rows, int *frame_counts, long n_frames, int C, int mode,
+                             float conf_thresh, float unify_thresh, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Input pipeline around K1.

@@ -528,12 +528,15 @@ __global__ void mul_kernel(const float4 *__restrict__ a, const float4 *__restric
 }
 
 __global__ void scale_dev_kernel(const float4 *__restrict__ a, const float *__restrict__ s, float4 *__restrict__ y,
-                                 long n4) {
+                                 long n4, long n) {
     const float f = s[0];
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+    const long gt = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    for (long i = gt; i < n4; i += (long)gridDim.x * blockDim.x) {
         const float4 u = a[i];
         y[i] = make_float4(u.x * f, u.y * f, u.z * f, u.w * f);
     }
+    const long e = 4 * n4 + gt;                      // the up to three elements past the last float4
+    if (e < n) reinterpret_cast<float *>(y)[e] = reinterpret_cast<const float *>(a)[e] * f;
 }
 
 }  // namespace adyolo
@@ -554,11 +557,11 @@ static int gemm_fast_fetch(int M, int N, int K, int lda, int ldb, int transA, in
 }
 
 extern "C" int adyolo_scale_dev(const float *a, const float *scalar_dev, float *y, long n, void *stream) {
-    ADYOLO_REQUIRE(a && scalar_dev && y && n > 0 && n % 4 == 0, ADYOLO_EINVAL, "scale_dev: n must be a positive multiple of 4");
+    ADYOLO_REQUIRE(a && scalar_dev && y && n > 0, ADYOLO_EINVAL, "scale_dev: null pointer or n <= 0");
     const long n4 = n / 4;
     const int grid = (int)(n4 / 256 + 1 > 4096 ? 4096 : n4 / 256 + 1);
     hipLaunchKernelGGL(scale_dev_kernel, dim3(grid), dim3(256), 0, as_stream(stream), (const float4 *)a, scalar_dev,
-                       (float4 *)y, n4);
+                       (float4 *)y, n4, n);
     return check_launch("scale_dev");
 }
 

@@ -26,8 +26,9 @@ def accdoa_loss(output, target):
     return F.mse_loss(output, target)
 
 
-def adpit_loss(output, target, nb_classes):
-    """output (B,T,9C), target (B,T,6,4,C)."""
+def adpit_candidates(output, target, nb_classes):
+    """output (B,T,9C), target (B,T,6,4,C) -> losses (13,B,T,C) and candidate targets (13,B,T,9,C) of loss.py:70-153, in the
+    order the reference takes its minimum over (A0A0A0, the six B permutations, the six C permutations)."""
     b, t = output.shape[:2]
     v = target[:, :, :, 0:1, :] * target[:, :, :, 1:, :]               # (B,T,6,3,C): act * xyz
     a0, b0, b1, c0, c1, c2 = (v[:, :, i] for i in range(6))
@@ -41,7 +42,25 @@ def adpit_loss(output, target, nb_classes):
             [p + (aaa + b_perms[0]) for p in c_perms]
     out = output.reshape(b, t, 9, nb_classes)
     losses = torch.stack([((out - cand) ** 2).mean(dim=2) for cand in cands], dim=0)   # (13,B,T,C)
+    return losses, torch.stack(cands, dim=0)
+
+
+def adpit_loss(output, target, nb_classes):
+    """output (B,T,9C), target (B,T,6,4,C)."""
+    losses, _ = adpit_candidates(output, target, nb_classes)
     return losses.min(dim=0).values.mean()
+
+
+def adpit_fragile_items(losses, cands):
+    """(B,T,C) bool: items whose arg-min float32 round-off can turn -- the best candidate and the best candidate WITH A DIFFERENT
+    TARGET VECTOR differ by less than 16 * 2^-24 times the larger of the two losses (candidates with equal target vectors give
+    the same loss and gradient whichever wins).  Judge it on float64 losses."""
+    best = losses.argmin(dim=0)                                                      # (B,T,C)
+    l1 = losses.gather(0, best[None])[0]
+    idx = best[None, :, :, None, :].expand(1, *cands.shape[1:])
+    differs = (cands != cands.gather(0, idx)).any(dim=3)                             # (13,B,T,C)
+    l2 = torch.where(differs, losses, torch.full_like(losses, float("inf"))).min(dim=0).values
+    return (l2 - l1) < 16 * 2.0 ** -24 * torch.maximum(l1, l2)
 
 
 def head_activation(raw, n_sigmoid_cols):

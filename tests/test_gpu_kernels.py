@@ -279,6 +279,9 @@ def test_colsum_and_elementwise(ops):
     assert_close(ops.add(dev(a), dev(b)), a + b, 1e-6, "add")
     assert_close(ops.mul(dev(a), dev(b)), a * b, 1e-6, "mul")
     assert_close(ops.scale_dev(dev(a), dev(torch.tensor([0.25]))), a * 0.25, 1e-6, "scale_dev")
+    for n in (1, 2, 3, 5, 6, 7, 1026):                                   # every remainder past the last float4, and no float4 at all
+        v = torch.randn(n, generator=g)
+        assert torch.equal(ops.scale_dev(dev(v), dev(torch.tensor([0.25]))).cpu(), v * 0.25), "scale_dev n = %d" % n
 
 
 # ------------------------------------------------------------------------------------------------ norm

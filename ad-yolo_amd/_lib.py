@@ -135,13 +135,10 @@ SIGNATURES = {
     "adyolo_mask_ranges": (I, [P, P, I, I, I, I, P]),
     "adyolo_mask_groups": (I, [P, P, I, I, I, I, I, P, P]),
     "adyolo_colstats": (I, [P, P, P, L, I, P]),
-    "adyolo_adam_step": (I, [P] * 4 + [L, F, F, F, F, F, I, F, P]),
-    "adyolo_adam_step_dev": (I, [P] * 4 + [L, F, F, F, F, F, P, P, F, P]),
     "adyolo_grad_sumsq_parts": (L, [L]),
     "adyolo_grad_sumsq": (I, [P, L, F, P, P]),
     "adyolo_grad_norm_dev": (I, [P, L, F, P, F, P, P]),
-    "adyolo_adamw_step_dev": (I, [P] * 4 + [L, F, F, F, F, F, P, P, P, F, F, P]),
-    "adyolo_adam_clip_step_dev": (I, [P] * 4 + [L, F, F, F, F, F, P, P, P, F, F, P]),
+    "adyolo_adam_step_dev": (I, [P] * 4 + [L, F, F, F, F, F, I, P, P, P, F, F, P]),
     "adyolo_sgd_step_dev": (I, [P] * 3 + [L, F, F, F, F, I, P, P, P, F, F, P]),
 }
 
@@ -173,8 +170,8 @@ def load():
         fn.restype = res
         fn.argtypes = args
     ver = lib.adyolo_abi_version()
-    if ver != 2:
-        raise AdyoloHipError("libadyolo_hip.so ABI version %d != 2" % ver)
+    if ver != 3:
+        raise AdyoloHipError("libadyolo_hip.so ABI version %d != 3" % ver)
     _lib = lib
     for hook in ON_LOAD:
         hook(lib)

@@ -33,7 +33,7 @@ inline int check_launch(const char *what) {
 
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
-// Workspace initialisation as a KERNEL (defined in optim.hip), not hipMemsetAsync: a memset recorded into a hipGraph becomes a
+// Workspace initialisation as a KERNEL (defined in runtime.hip), not hipMemsetAsync: a memset recorded into a hipGraph becomes a
 // memset node, and on this stack a replayed memset node was seen to land out of order with the kernels around it (the
 // per-clip maxima of K1 were reset late in about half of the replays of one evaluation graph).  n32 = number of 32-bit words.
 int fill32(void *ptr, uint32_t value, size_t n32, hipStream_t st);

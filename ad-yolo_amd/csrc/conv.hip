@@ -746,3 +746,29 @@ extern "C" int adyolo_conv3x3_wgrad(const float *x, const float *dy, const float
                        Cout, CinP, Cin_real);
     return check_launch("conv3x3_wgrad_reduce");
 }
+
+// ---- entry transpose NCHW -> NHWC8: the layout the stem convolution reads (7 feature planes padded to 8 channels)
+namespace adyolo {
+__global__ __launch_bounds__(256) void nchw_to_nhwc8_kernel(const float *__restrict__ x, float *__restrict__ y, int C,
+                                                            long HW, long total) {
+    // one thread per output pixel: gathers C (<= 8) planes, writes 32 contiguous bytes
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const long n = i / HW, p = i - n * HW;
+        float v[8];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) v[c] = c < C ? x[((size_t)n * C + c) * HW + p] : 0.f;
+        float4 *o = reinterpret_cast<float4 *>(y + (size_t)i * 8);
+        o[0] = make_float4(v[0], v[1], v[2], v[3]);
+        o[1] = make_float4(v[4], v[5], v[6], v[7]);
+    }
+}
+}  // namespace adyolo
+
+extern "C" int adyolo_nchw_to_nhwc8(const float *x, float *y, int B, int C, int H, int W, void *stream) {
+    ADYOLO_REQUIRE(x && y && B > 0 && C > 0 && C <= 8 && H > 0 && W > 0, ADYOLO_EINVAL, "nchw_to_nhwc8: bad arguments");
+    const long HW = (long)H * W, total = (long)B * HW;
+    const long g = (total + 255) / 256;
+    hipLaunchKernelGGL(nchw_to_nhwc8_kernel, dim3((unsigned)(g > 8192 ? 8192 : g)), dim3(256), 0, as_stream(stream), x,
+                       y, C, HW, total);
+    return check_launch("nchw_to_nhwc8");
+}

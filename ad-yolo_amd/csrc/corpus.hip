@@ -23,7 +23,7 @@ struct CorpusRot {                     // ADYOLO_CORPUS_ROT_WORDS floats per com
 };
 
 __device__ __forceinline__ float4 pcm_rot(int lo, int hi, float sy, float sz, float sx, bool swap) {
-    // the arithmetic of pcm16_to_f32_kernel (csrc/aug.hip) then foa_rotate_kernel (csrc/optim.hip), element for element
+    // the arithmetic of pcm16_to_f32_kernel (csrc/aug.hip) then foa_rotate_kernel (csrc/aug.hip), element for element
     const float w = (float)(short)(lo & 0xffff) / 32768.0f + 1e-8f;
     const float y = (float)(short)(lo >> 16) / 32768.0f + 1e-8f;
     const float z = (float)(short)(hi & 0xffff) / 32768.0f + 1e-8f;

@@ -1,174 +1,274 @@
-// K11: fused Adam over one flat parameter buffer (all 6.68 M parameters live in one allocation, so one
-// launch updates the whole model and one RCCL all-reduce covers all gradients).  Arithmetic follows
-// torch.optim.Adam's single-tensor path (used at /root/reference/src/train.py:31,55; amsgrad off):
-//   m += (g - m)(1 - b1);  v = b2 v + (1 - b2) g^2;  p -= lr/(1 - b1^t) * m / (sqrt(v)/sqrt(1 - b2^t) + eps)
-// Also: the error string holder of the library and the NCHW -> NHWC8 entry transpose.
-#include <stdarg.h>
+// K11: Adam, AdamW, SGD and gradient-norm clipping over one flat parameter buffer (all 6.68 M parameters live in one
+// allocation, so one launch updates the whole model and one RCCL all-reduce covers all gradients).  The reference picks its
+// optimizer by name (src/train.py:29-37) and clips with clip_grad_norm_(max_norm) (src/train.py:54); the arithmetic follows
+// torch.optim's single-tensor paths.
+//
+// One optimizer step = up to three launches whose arguments never change from step to step (hipGraph-replayable):
+//   grad_sumsq_kernel   (clipping only) partial sums of (g * grad_scale)^2 in float64, one per workgroup, fixed grid and order
+//   optim_prep_kernel   one workgroup: step counter += 1; st[0..1] = bias corrections (Adam / AdamW) or the "first step" flag
+//                       (SGD); st[2] = total_norm (fp32); st[3] = clip_coef = min(1, max_norm / (total_norm + 1e-6)) -- 1 when off
+//   *_update_kernel     the update, grad_scale * st[3] folded into the gradient (exact when st[3] = 1: the unclipped step is
+//                       the same kernel)
+// st is 4 floats of device scratch.  All streams move 16 bytes per lane per access (pointers 16-byte aligned, the n & 3 tail
+// elements are done by workgroup 0); grids are capped and grid-stride.  Elements that are zero in parameter, gradient and state
+// (the padding of dist.FlatParameters) stay zero in every kernel.
+//
+// Rounding is written in the source: adam_one and sgd_one switch floating-point contraction off and spell out every fused
+// multiply-add they want, so the float4 body, the tail, and every (DECOUPLED, clipped or not) form round alike whatever the
+// vectoriser does.
 #include <math.h>
 #include "common.hpp"
 
 namespace adyolo {
 
-static thread_local char g_err[512] = "";
+constexpr int OX_THREADS = 256;
+constexpr int OX_MAX_BLOCKS = 2048;      // update kernels: 8 workgroups per CU, grid-stride beyond
+constexpr int OX_SUMSQ_BLOCKS = 1024;    // = the largest number of partials (8 KB of float64)
 
-void set_error(const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
+static inline int update_grid(long n) {
+    long g = ((n >> 2) + OX_THREADS - 1) / OX_THREADS;
+    return (int)(g < 1 ? 1 : (g > OX_MAX_BLOCKS ? OX_MAX_BLOCKS : g));
 }
 
-// DEV: step_size / inv_sqrt_bc2 come from device memory (`bc`, written by adam_prep_kernel from a device-side step
-// counter), so that a launch recorded in a hipGraph does the right bias correction at every replay
-template <bool DEV>
-__global__ __launch_bounds__(256) void adam_kernel(float *__restrict__ p, const float *__restrict__ g,
-                                                   float *__restrict__ m, float *__restrict__ v, long n, float beta1,
-                                                   float beta2, float eps, float wd, float step_size,
-                                                   float inv_sqrt_bc2, float grad_scale,
-                                                   const float *__restrict__ bc) {
-    if (DEV) {
-        step_size = bc[0];
-        inv_sqrt_bc2 = bc[1];
+static inline int sumsq_grid(long n) {
+    long g = ((n >> 2) + OX_THREADS - 1) / OX_THREADS;
+    return (int)(g < 1 ? 1 : (g > OX_SUMSQ_BLOCKS ? OX_SUMSQ_BLOCKS : g));
+}
+
+static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// ---------------------------------------------------------------------------------------------- gradient norm
+__global__ __launch_bounds__(OX_THREADS) void grad_sumsq_kernel(const float *__restrict__ g, long n, float grad_scale,
+                                                                double *__restrict__ partials) {
+    __shared__ double red[OX_THREADS / 64];
+    const long n4 = n >> 2;
+    const float4 *g4 = reinterpret_cast<const float4 *>(g);
+    double s = 0.0;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        const float4 v = g4[i];
+        const double a = (double)(v.x * grad_scale), b = (double)(v.y * grad_scale);
+        const double c = (double)(v.z * grad_scale), d = (double)(v.w * grad_scale);
+        s += (a * a + b * b) + (c * c + d * d);
     }
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        float gi = g[i] * grad_scale;
-        const float pi = p[i];
-        if (wd != 0.f) gi += wd * pi;
-        float mi = m[i], vi = v[i];
-        mi += (gi - mi) * (1.f - beta1);
-        vi = vi * beta2 + (1.f - beta2) * gi * gi;
-        const float denom = sqrtf(vi) * inv_sqrt_bc2 + eps;
-        p[i] = pi - step_size * (mi / denom);
-        m[i] = mi;
-        v[i] = vi;
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const double a = (double)(g[n4 * 4 + threadIdx.x] * grad_scale);
+        s += a * a;
     }
-}
-
-// step counter += 1 on the device; bc = {lr / (1 - beta1^t), 1 / sqrt(1 - beta2^t)} in double like the host entry point
-__global__ void adam_prep_kernel(unsigned long long *__restrict__ step, float *__restrict__ bc, float lr, float beta1,
-                                 float beta2) {
-    const unsigned long long s = *step + 1ull;
-    *step = s;
-    const double bc1 = 1.0 - pow((double)beta1, (double)s);
-    const double bc2 = 1.0 - pow((double)beta2, (double)s);
-    bc[0] = (float)((double)lr / bc1);
-    bc[1] = (float)(1.0 / sqrt(bc2));
-}
-
-__global__ __launch_bounds__(256) void fill32_kernel(uint32_t *__restrict__ p, uint32_t v, size_t n) {
-    const size_t n4 = n >> 2;
-    uint4 *p4 = reinterpret_cast<uint4 *>(p);
-    const uint4 v4 = make_uint4(v, v, v, v);
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) p4[i] = v4;
-    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) p[n4 * 4 + threadIdx.x] = v;
-}
-
-int fill32(void *ptr, uint32_t value, size_t n32, hipStream_t st) {
-    if (n32 == 0) return 0;
-    if (reinterpret_cast<uintptr_t>(ptr) & 15) {          // (never the case for the workspaces of this library)
-        set_error("fill32: pointer not 16-byte aligned");
-        return ADYOLO_EINVAL;
-    }
-    size_t g = ((n32 >> 2) + 255) / 256;
-    if (g > 4096) g = 4096;
-    if (g < 1) g = 1;
-    hipLaunchKernelGGL(fill32_kernel, dim3((unsigned)g), dim3(256), 0, st, reinterpret_cast<uint32_t *>(ptr), value, n32);
-    return check_launch("fill32");
-}
-
-__global__ void counter_add_kernel(unsigned long long *__restrict__ c, unsigned long long inc) { *c += inc; }
-
-__global__ __launch_bounds__(256) void nchw_to_nhwc8_kernel(const float *__restrict__ x, float *__restrict__ y, int C,
-                                                            long HW, long total) {
-    // one thread per output pixel: gathers C (<= 8) planes, writes 32 contiguous bytes
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const long n = i / HW, p = i - n * HW;
-        float v[8];
+    // fixed order: butterfly inside the wave, then the four waves one after the other
 #pragma unroll
-        for (int c = 0; c < 8; ++c) v[c] = c < C ? x[((size_t)n * C + c) * HW + p] : 0.f;
-        float4 *o = reinterpret_cast<float4 *>(y + (size_t)i * 8);
-        o[0] = make_float4(v[0], v[1], v[2], v[3]);
-        o[1] = make_float4(v[4], v[5], v[6], v[7]);
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) partials[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// ---------------------------------------------------------------------------------------------- prep
+enum { PREP_ADAM = 0, PREP_SGD = 1, PREP_NORM = 2 };
+
+// one workgroup of OX_THREADS.  partials == nullptr: clipping off (st[3] = 1, st[2] untouched).  PREP_NORM: no counter, norm only.
+__global__ __launch_bounds__(OX_THREADS) void optim_prep_kernel(unsigned long long *__restrict__ step, float *__restrict__ st,
+                                                                int kind, float lr, float beta1, float beta2,
+                                                                const double *__restrict__ partials, int nparts,
+                                                                float max_norm) {
+    __shared__ double red[OX_THREADS];
+    if (threadIdx.x == 0 && kind != PREP_NORM) {
+        const unsigned long long s = *step + 1ull;
+        *step = s;
+        if (kind == PREP_ADAM) {           // {lr / (1 - beta1^t), 1 / sqrt(1 - beta2^t)} in double like torch's host arithmetic
+            const double bc1 = 1.0 - pow((double)beta1, (double)s);
+            const double bc2 = 1.0 - pow((double)beta2, (double)s);
+            st[0] = (float)((double)lr / bc1);
+            st[1] = (float)(1.0 / sqrt(bc2));
+        } else {                           // SGD: the momentum buffer is INITIALISED by the first step (no dampening)
+            st[0] = s == 1ull ? 1.f : 0.f;
+            st[1] = 0.f;
+        }
     }
+    if (partials == nullptr) {             // (uniform over the workgroup)
+        if (threadIdx.x == 0) st[3] = 1.f;
+        return;
+    }
+    double s = 0.0;
+    for (int i = threadIdx.x; i < nparts; i += OX_THREADS) s += partials[i];
+    red[threadIdx.x] = s;
+    __syncthreads();
+#pragma unroll
+    for (int o = OX_THREADS / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        // torch.nn.utils.clip_grad_norm_: clip_coef = max_norm / (total_norm + 1e-6), clamped to 1; fp32; a non-finite norm is
+        // not special-cased (inf -> 0, nan -> nan)
+        const float total = (float)sqrt(red[0]);
+        const float coef = max_norm / (total + 1e-6f);
+        st[2] = total;
+        st[3] = coef > 1.f ? 1.f : coef;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- Adam / AdamW update
+// torch.optim.Adam:  m += (g - m)(1 - b1);  v = b2 v + (1 - b2) g^2;  p -= lr/(1 - b1^t) * m / (sqrt(v)/sqrt(1 - b2^t) + eps)
+// DECOUPLED = false: weight decay added to the gradient.
+// DECOUPLED = true:  torch.optim.AdamW: p *= 1 - lr * wd (`decay`, formed on the host in double) before the moments.
+// Exactly three operations are fused (m, the denominator, the parameter); gi and v round after every multiply and add.
+template <bool DECOUPLED>
+__device__ __forceinline__ void adam_one(float &p, float g, float &m, float &v, float gs, float beta1, float beta2, float eps,
+                                         float wd, float decay, float step_size, float inv_sqrt_bc2) {
+#pragma clang fp contract(off)
+    float gi = g * gs;
+    float pi = p;
+    if (wd != 0.f) {
+        if (DECOUPLED) pi = pi * decay;
+        else gi = gi + wd * pi;
+    }
+    m = __builtin_fmaf(gi - m, 1.f - beta1, m);
+    v = v * beta2 + ((1.f - beta2) * gi) * gi;
+    p = __builtin_fmaf(-step_size, m / __builtin_fmaf(sqrtf(v), inv_sqrt_bc2, eps), pi);
+}
+
+template <bool DECOUPLED>
+__global__ __launch_bounds__(OX_THREADS) void adam_update_kernel(float *__restrict__ p, const float *__restrict__ g,
+                                                                 float *__restrict__ m, float *__restrict__ v, long n,
+                                                                 float beta1, float beta2, float eps, float wd, float decay,
+                                                                 float grad_scale, const float *__restrict__ st) {
+    const float step_size = st[0], inv_sqrt_bc2 = st[1];
+    const float gs = grad_scale * st[3];
+    const long n4 = n >> 2;
+    float4 *p4 = reinterpret_cast<float4 *>(p), *m4 = reinterpret_cast<float4 *>(m), *v4 = reinterpret_cast<float4 *>(v);
+    const float4 *g4 = reinterpret_cast<const float4 *>(g);
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        float4 pv = p4[i], mv = m4[i], vv = v4[i];
+        const float4 gv = g4[i];
+        adam_one<DECOUPLED>(pv.x, gv.x, mv.x, vv.x, gs, beta1, beta2, eps, wd, decay, step_size, inv_sqrt_bc2);
+        adam_one<DECOUPLED>(pv.y, gv.y, mv.y, vv.y, gs, beta1, beta2, eps, wd, decay, step_size, inv_sqrt_bc2);
+        adam_one<DECOUPLED>(pv.z, gv.z, mv.z, vv.z, gs, beta1, beta2, eps, wd, decay, step_size, inv_sqrt_bc2);
+        adam_one<DECOUPLED>(pv.w, gv.w, mv.w, vv.w, gs, beta1, beta2, eps, wd, decay, step_size, inv_sqrt_bc2);
+        p4[i] = pv;
+        m4[i] = mv;
+        v4[i] = vv;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const long i = n4 * 4 + threadIdx.x;
+        adam_one<DECOUPLED>(p[i], g[i], m[i], v[i], gs, beta1, beta2, eps, wd, decay, step_size, inv_sqrt_bc2);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- SGD update
+// torch.optim.SGD, single-tensor path: g' = g * gs + wd * p;  MOM: buf = g' on the first step (st[0] != 0), else
+// buf = mu * buf + (1 - dampening) * g';  d = nesterov ? g' + mu * buf : buf;  p += -lr * d.  !MOM: buf is never touched.
+// Every multiply-add is fused except mu * buf, which rounds before (1 - dampening) * g' is fused onto it.
+template <bool MOM>
+__device__ __forceinline__ void sgd_one(float &p, float g, float *buf, float gs, float lr, float wd, float mu, float keep,
+                                        bool nesterov, bool first) {
+#pragma clang fp contract(off)
+    float gi = g * gs;
+    const float pi = p;
+    if (wd != 0.f) gi = __builtin_fmaf(wd, pi, gi);
+    if (MOM) {
+        const float bi = first ? gi : __builtin_fmaf(keep, gi, mu * *buf);
+        *buf = bi;
+        gi = nesterov ? __builtin_fmaf(mu, bi, gi) : bi;
+    }
+    p = __builtin_fmaf(-lr, gi, pi);
+}
+
+template <bool MOM>
+__global__ __launch_bounds__(OX_THREADS) void sgd_update_kernel(float *__restrict__ p, const float *__restrict__ g,
+                                                                float *__restrict__ buf, long n, float lr, float wd, float mu,
+                                                                float keep, int nesterov, float grad_scale,
+                                                                const float *__restrict__ st) {
+    const bool first = st[0] != 0.f, nest = nesterov != 0;
+    const float gs = grad_scale * st[3];
+    const long n4 = n >> 2;
+    float4 *p4 = reinterpret_cast<float4 *>(p), *b4 = reinterpret_cast<float4 *>(buf);
+    const float4 *g4 = reinterpret_cast<const float4 *>(g);
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        float4 pv = p4[i];
+        const float4 gv = g4[i];
+        float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (MOM && !first) bv = b4[i];
+        sgd_one<MOM>(pv.x, gv.x, &bv.x, gs, lr, wd, mu, keep, nest, first);
+        sgd_one<MOM>(pv.y, gv.y, &bv.y, gs, lr, wd, mu, keep, nest, first);
+        sgd_one<MOM>(pv.z, gv.z, &bv.z, gs, lr, wd, mu, keep, nest, first);
+        sgd_one<MOM>(pv.w, gv.w, &bv.w, gs, lr, wd, mu, keep, nest, first);
+        p4[i] = pv;
+        if (MOM) b4[i] = bv;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const long i = n4 * 4 + threadIdx.x;
+        sgd_one<MOM>(p[i], g[i], MOM ? buf + i : nullptr, gs, lr, wd, mu, keep, nest, first);
+    }
+}
+
+static int launch_sumsq(const float *grad, long n, float grad_scale, double *partials, hipStream_t st) {
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3(sumsq_grid(n)), dim3(OX_THREADS), 0, st, grad, n, grad_scale, partials);
+    return check_launch("grad_sumsq");
+}
+
+static int launch_prep(uint64_t *step_dev, float *st_dev, int kind, float lr, float beta1, float beta2, const double *partials,
+                       long n, float max_norm, hipStream_t st) {
+    hipLaunchKernelGGL(optim_prep_kernel, dim3(1), dim3(OX_THREADS), 0, st, reinterpret_cast<unsigned long long *>(step_dev),
+                       st_dev, kind, lr, beta1, beta2, partials, partials ? sumsq_grid(n) : 0, max_norm);
+    return check_launch("optim_prep");
 }
 
 }  // namespace adyolo
 
 using namespace adyolo;
 
-extern "C" int adyolo_abi_version(void) { return ADYOLO_ABI_VERSION; }
-extern "C" const char *adyolo_last_error(void) { return g_err; }
+extern "C" long adyolo_grad_sumsq_parts(long n) { return n > 0 ? sumsq_grid(n) : 0; }
 
-extern "C" int adyolo_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, long n, float lr,
-                                float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
-                                void *stream) {
-    ADYOLO_REQUIRE(param && grad && exp_avg && exp_avg_sq && n > 0 && step >= 1, ADYOLO_EINVAL, "adam_step: bad arguments");
-    const double bc1 = 1.0 - pow((double)beta1, (double)step);
-    const double bc2 = 1.0 - pow((double)beta2, (double)step);
-    const float step_size = (float)((double)lr / bc1);
-    const float inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
-    const long g = (n + 255) / 256;
-    hipLaunchKernelGGL(adam_kernel<false>, dim3((unsigned)(g > 8192 ? 8192 : g)), dim3(256), 0, as_stream(stream), param,
-                       grad, exp_avg, exp_avg_sq, n, beta1, beta2, eps, weight_decay, step_size, inv_sqrt_bc2, grad_scale,
-                       (const float *)nullptr);
-    return check_launch("adam_step");
+extern "C" int adyolo_grad_sumsq(const float *grad, long n, float grad_scale, double *partials, void *stream) {
+    ADYOLO_REQUIRE(grad && partials && n > 0, ADYOLO_EINVAL, "grad_sumsq: bad arguments");
+    ADYOLO_REQUIRE(aligned16(grad) && (reinterpret_cast<uintptr_t>(partials) & 7) == 0, ADYOLO_EINVAL,
+                   "grad_sumsq: gradient not 16-byte aligned (or partials not 8-byte aligned)");
+    return launch_sumsq(grad, n, grad_scale, partials, as_stream(stream));
+}
+
+extern "C" int adyolo_grad_norm_dev(const float *grad, long n, float grad_scale, double *partials, float max_norm, float *st_dev,
+                                    void *stream) {
+    ADYOLO_REQUIRE(st_dev, ADYOLO_EINVAL, "grad_norm_dev: null scratch");
+    int rc = adyolo_grad_sumsq(grad, n, grad_scale, partials, stream);
+    if (rc) return rc;
+    return launch_prep(nullptr, st_dev, PREP_NORM, 0.f, 0.f, 0.f, partials, n, max_norm, as_stream(stream));
 }
 
 extern "C" int adyolo_adam_step_dev(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, long n, float lr,
-                                    float beta1, float beta2, float eps, float weight_decay, uint64_t *step_dev,
-                                    float *bc_dev, float grad_scale, void *stream) {
-    ADYOLO_REQUIRE(param && grad && exp_avg && exp_avg_sq && n > 0 && step_dev && bc_dev, ADYOLO_EINVAL,
+                                    float beta1, float beta2, float eps, float weight_decay, int decoupled, uint64_t *step_dev,
+                                    float *st_dev, double *partials, float max_norm, float grad_scale, void *stream) {
+    ADYOLO_REQUIRE(param && grad && exp_avg && exp_avg_sq && n > 0 && step_dev && st_dev, ADYOLO_EINVAL,
                    "adam_step_dev: bad arguments");
+    ADYOLO_REQUIRE(aligned16(param) && aligned16(grad) && aligned16(exp_avg) && aligned16(exp_avg_sq), ADYOLO_EINVAL,
+                   "adam_step_dev: buffers not 16-byte aligned");
     hipStream_t st = as_stream(stream);
-    hipLaunchKernelGGL(adam_prep_kernel, dim3(1), dim3(1), 0, st, reinterpret_cast<unsigned long long *>(step_dev), bc_dev,
-                       lr, beta1, beta2);
-    int rc = check_launch("adam_prep");
-    if (rc) return rc;
-    const long g = (n + 255) / 256;
-    hipLaunchKernelGGL(adam_kernel<true>, dim3((unsigned)(g > 8192 ? 8192 : g)), dim3(256), 0, st, param, grad, exp_avg,
-                       exp_avg_sq, n, beta1, beta2, eps, weight_decay, 0.f, 0.f, grad_scale, (const float *)bc_dev);
+    int rc;
+    if (partials && (rc = launch_sumsq(grad, n, grad_scale, partials, st))) return rc;
+    if ((rc = launch_prep(step_dev, st_dev, PREP_ADAM, lr, beta1, beta2, partials, n, max_norm, st))) return rc;
+    const float decay = (float)(1.0 - (double)lr * (double)weight_decay);
+    auto kernel = decoupled ? adam_update_kernel<true> : adam_update_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(update_grid(n)), dim3(OX_THREADS), 0, st, param, grad, exp_avg, exp_avg_sq, n, beta1, beta2,
+                       eps, weight_decay, decay, grad_scale, (const float *)st_dev);
     return check_launch("adam_step_dev");
 }
 
-extern "C" int adyolo_counter_add(uint64_t *counter, uint64_t inc, void *stream) {
-    ADYOLO_REQUIRE(counter, ADYOLO_EINVAL, "counter_add: null pointer");
-    hipLaunchKernelGGL(counter_add_kernel, dim3(1), dim3(1), 0, as_stream(stream),
-                       reinterpret_cast<unsigned long long *>(counter), (unsigned long long)inc);
-    return check_launch("counter_add");
-}
-
-extern "C" int adyolo_nchw_to_nhwc8(const float *x, float *y, int B, int C, int H, int W, void *stream) {
-    ADYOLO_REQUIRE(x && y && B > 0 && C > 0 && C <= 8 && H > 0 && W > 0, ADYOLO_EINVAL, "nchw_to_nhwc8: bad arguments");
-    const long HW = (long)H * W, total = (long)B * HW;
-    const long g = (total + 255) / 256;
-    hipLaunchKernelGGL(nchw_to_nhwc8_kernel, dim3((unsigned)(g > 8192 ? 8192 : g)), dim3(256), 0, as_stream(stream), x,
-                       y, C, HW, total);
-    return check_launch("nchw_to_nhwc8");
-}
-
-// ---- FOA rotation augmentation on raw audio (reference src/utils/augmentations.py:81-96): per clip a sign for each of
-// the Y, Z, X channels and an optional X <-> Y swap;  audio [B][n][4] (W, Y, Z, X), cfg[b] = {sy, sz, sx, swap}
-namespace adyolo {
-__global__ __launch_bounds__(256) void foa_rotate_kernel(const float4 *__restrict__ x, float4 *__restrict__ y,
-                                                         const float *__restrict__ cfg, long n_per_clip) {
-    const int b = blockIdx.y;
-    const float sy = cfg[b * 4 + 0], sz = cfg[b * 4 + 1], sx = cfg[b * 4 + 2];
-    const bool swap = cfg[b * 4 + 3] != 0.f;
-    const float4 *src = x + (size_t)b * n_per_clip;
-    float4 *dst = y + (size_t)b * n_per_clip;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n_per_clip; i += (long)gridDim.x * blockDim.x) {
-        const float4 v = src[i];
-        const float yy = v.y * sy, zz = v.z * sz, xx = v.w * sx;
-        dst[i] = swap ? make_float4(v.x, xx, zz, yy) : make_float4(v.x, yy, zz, xx);
-    }
-}
-}  // namespace adyolo
-
-extern "C" int adyolo_foa_rotate(const float *audio, float *out, const float *cfg, int B, long n_samples, void *stream) {
-    ADYOLO_REQUIRE(audio && out && cfg && B > 0 && n_samples > 0, ADYOLO_EINVAL, "foa_rotate: bad arguments");
-    long g = (n_samples + 255) / 256;
-    if (g > 2048) g = 2048;
-    hipLaunchKernelGGL(adyolo::foa_rotate_kernel, dim3((unsigned)g, B), dim3(256), 0, adyolo::as_stream(stream),
-                       (const float4 *)audio, (float4 *)out, cfg, n_samples);
-    return adyolo::check_launch("foa_rotate");
+extern "C" int adyolo_sgd_step_dev(float *param, const float *grad, float *momentum_buf, long n, float lr, float weight_decay,
+                                   float momentum, float dampening, int nesterov, uint64_t *step_dev, float *st_dev,
+                                   double *partials, float max_norm, float grad_scale, void *stream) {
+    ADYOLO_REQUIRE(param && grad && n > 0 && step_dev && st_dev && (momentum == 0.f || momentum_buf), ADYOLO_EINVAL,
+                   "sgd_step_dev: bad arguments");
+    ADYOLO_REQUIRE(aligned16(param) && aligned16(grad) && aligned16(momentum_buf), ADYOLO_EINVAL,
+                   "sgd_step_dev: buffers not 16-byte aligned");
+    hipStream_t st = as_stream(stream);
+    int rc;
+    if (partials && (rc = launch_sumsq(grad, n, grad_scale, partials, st))) return rc;
+    if ((rc = launch_prep(step_dev, st_dev, PREP_SGD, lr, 0.f, 0.f, partials, n, max_norm, st))) return rc;
+    const float keep = (float)(1.0 - (double)dampening);
+    if (momentum != 0.f)
+        hipLaunchKernelGGL(sgd_update_kernel<true>, dim3(update_grid(n)), dim3(OX_THREADS), 0, st, param, grad, momentum_buf, n,
+                           lr, weight_decay, momentum, keep, nesterov, grad_scale, (const float *)st_dev);
+    else
+        hipLaunchKernelGGL(sgd_update_kernel<false>, dim3(update_grid(n)), dim3(OX_THREADS), 0, st, param, grad,
+                           (float *)nullptr, n, lr, weight_decay, 0.f, keep, nesterov, grad_scale, (const float *)st_dev);
+    return check_launch("sgd_step_dev");
 }

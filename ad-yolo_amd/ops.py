@@ -1066,26 +1066,8 @@ def seld_score(rows, counts, table, file_ids, t_clip, out, status=None):
     return status
 
 
-def adam_step(param, grad, exp_avg, exp_avg_sq, step, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
-              grad_scale=1.0):
-    _chk(param, grad, exp_avg, exp_avg_sq)
-    _c("adyolo_adam_step", _p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), lr, betas[0], betas[1],
-       eps, weight_decay, int(step), grad_scale, _stream())
-
-
-def adam_step_dev(param, grad, exp_avg, exp_avg_sq, step_dev, bc_dev, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
-                  weight_decay=0.0, grad_scale=1.0):
-    """``adam_step`` with the step counter on the device: step_dev (int64, one element) is incremented by the call, bc_dev
-    (2 floats) receives the bias corrections.  No argument changes from step to step (hipGraph-replayable)."""
-    _chk(param, grad, exp_avg, exp_avg_sq, bc_dev)
-    if not step_dev.is_cuda or step_dev.dtype != torch.int64 or step_dev.numel() != 1 or bc_dev.numel() < 2:
-        raise _lib.AdyoloHipError("adam_step_dev needs a one-element int64 step counter and 2 floats of scratch on the device")
-    _c("adyolo_adam_step_dev", _p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), lr, betas[0], betas[1],
-       eps, weight_decay, _p(step_dev), _p(bc_dev), grad_scale, _stream())
-
-
-GRAD_SUMSQ_MAX_PARTS = 1024       # adyolo_grad_sumsq_parts(n) never exceeds this (csrc/optim_ext.hip OX_SUMSQ_BLOCKS)
-OPTIM_SCRATCH_FLOATS = 4          # st_dev of the calls below: {a, b, total_norm, clip_coef} (include/adyolo_hip.h, K11x)
+GRAD_SUMSQ_MAX_PARTS = 1024       # adyolo_grad_sumsq_parts(n) never exceeds this (csrc/optim.hip OX_SUMSQ_BLOCKS)
+OPTIM_SCRATCH_FLOATS = 4          # st_dev of the calls below: {a, b, total_norm, clip_coef} (include/adyolo_hip.h, K11)
 
 
 def grad_sumsq_parts(n):
@@ -1130,30 +1112,24 @@ def grad_norm_dev(grad, partials, st_dev, max_norm, grad_scale=1.0):
     return st_dev
 
 
-def _adam_ext(name, param, grad, exp_avg, exp_avg_sq, step_dev, st_dev, lr, betas, eps, weight_decay, grad_scale, partials,
-              max_norm):
+def adam_step_dev(param, grad, exp_avg, exp_avg_sq, step_dev, st_dev, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
+                  weight_decay=0.0, grad_scale=1.0, partials=None, max_norm=None, decoupled=False):
+    """torch.optim.Adam (``decoupled``: torch.optim.AdamW) with the step counter on the device: step_dev (int64, one element) is
+    incremented by the call, st_dev (``OPTIM_SCRATCH_FLOATS`` floats) receives the bias corrections.  No argument changes from
+    step to step (hipGraph-replayable).  partials (``grad_sumsq_parts(n)`` float64) + max_norm: clip the gradient norm first
+    (st_dev[2] = the pre-clip norm); partials None = no clipping, the same kernel with a coefficient of exactly 1."""
     _chk(param, grad, exp_avg, exp_avg_sq, st_dev)
-    _chk_optim_dev(name, param.numel(), step_dev, st_dev, partials)
-    _c("adyolo_" + name, _p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), lr, betas[0], betas[1], eps,
-       weight_decay, _p(step_dev), _p(st_dev), _p(partials), _max_norm(name, partials, max_norm), grad_scale, _stream())
+    _chk_optim_dev("adam_step_dev", param.numel(), step_dev, st_dev, partials)
+    _c("adyolo_adam_step_dev", _p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), lr, betas[0], betas[1], eps,
+       weight_decay, int(bool(decoupled)), _p(step_dev), _p(st_dev), _p(partials),
+       _max_norm("adam_step_dev", partials, max_norm), grad_scale, _stream())
 
 
 def adamw_step_dev(param, grad, exp_avg, exp_avg_sq, step_dev, st_dev, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
                    weight_decay=1e-2, grad_scale=1.0, partials=None, max_norm=None):
-    """torch.optim.AdamW (decoupled decay) with the step counter on the device, like ``adam_step_dev``.  st_dev:
-    ``OPTIM_SCRATCH_FLOATS`` floats.  partials (``grad_sumsq_parts(n)`` float64) + max_norm: clip the gradient norm first
-    (st_dev[2] = the pre-clip norm); partials None = no clipping."""
-    _adam_ext("adamw_step_dev", param, grad, exp_avg, exp_avg_sq, step_dev, st_dev, lr, betas, eps, weight_decay, grad_scale,
-              partials, max_norm)
-
-
-def adam_clip_step_dev(param, grad, exp_avg, exp_avg_sq, step_dev, st_dev, partials, max_norm, lr=1e-3, betas=(0.9, 0.999),
-                       eps=1e-8, weight_decay=0.0, grad_scale=1.0):
-    """``adam_step_dev`` behind ``clip_grad_norm_(max_norm)``: the same arithmetic with the coefficient folded into grad_scale."""
-    if partials is None or max_norm is None:
-        raise _lib.AdyoloHipError("adam_clip_step_dev needs partials and max_norm (without clipping: adam_step_dev)")
-    _adam_ext("adam_clip_step_dev", param, grad, exp_avg, exp_avg_sq, step_dev, st_dev, lr, betas, eps, weight_decay,
-              grad_scale, partials, max_norm)
+    """``adam_step_dev`` with torch.optim.AdamW's decoupled decay and its default weight decay."""
+    adam_step_dev(param, grad, exp_avg, exp_avg_sq, step_dev, st_dev, lr, betas, eps, weight_decay, grad_scale, partials,
+                  max_norm, decoupled=True)
 
 
 def sgd_step_dev(param, grad, momentum_buf, step_dev, st_dev, lr=1e-3, weight_decay=0.0, momentum=0.0, dampening=0.0,

@@ -39,12 +39,10 @@ class _FusedOptimizer:
         self.step_dev = torch.zeros(1, dtype=torch.int64, device=dev)
         self._step_count = 0
         self._dev_step_value = 0
-        self.st_dev = self.clip_partials = self.grad_norm = None
+        self.st_dev = torch.zeros(ops.OPTIM_SCRATCH_FLOATS, dtype=torch.float32, device=dev)
+        self.clip_partials = self.grad_norm = None
         if self.max_norm is not None:
             self.clip_partials = torch.zeros(ops.GRAD_SUMSQ_MAX_PARTS, dtype=torch.float64, device=dev)
-        if self.max_norm is not None or self.kind != "adam":
-            self.st_dev = torch.zeros(ops.OPTIM_SCRATCH_FLOATS, dtype=torch.float32, device=dev)
-        if self.max_norm is not None:
             self.grad_norm = self.st_dev[2:3]
 
     @property
@@ -90,8 +88,8 @@ class _FusedOptimizer:
 
 class FusedAdam(_FusedOptimizer):
     """Adam over a FlatParameters buffer (csrc/optim.hip); lr 1e-3, betas (0.9,0.999), eps 1e-8, wd 0 by
-    default like the reference config (src/configs/hyp_train.yaml:7-9).  Without ``max_norm`` the step is
-    ``ops.adam_step_dev``; with it, the same arithmetic behind the clip coefficient (csrc/optim_ext.hip)."""
+    default like the reference config (src/configs/hyp_train.yaml:7-9).  The step is ``ops.adam_step_dev``, with or without
+    ``max_norm``: one kernel, whose clip coefficient is exactly 1 when clipping is off."""
 
     kind = "adam"
 
@@ -100,16 +98,11 @@ class FusedAdam(_FusedOptimizer):
         self.exp_avg = torch.zeros_like(flat.flat)
         self.exp_avg_sq = torch.zeros_like(flat.flat)
         self._init_common(flat, max_norm)
-        self.bc_dev = torch.zeros(2, dtype=torch.float32, device=flat.flat.device)
 
     def _launch(self, grad_scale):
-        if self.max_norm is None:
-            ops.adam_step_dev(self.flat.flat, self.flat.flat_grad, self.exp_avg, self.exp_avg_sq, self.step_dev, self.bc_dev,
-                              self.lr, self.betas, self.eps, self.weight_decay, grad_scale)
-        else:
-            ops.adam_clip_step_dev(self.flat.flat, self.flat.flat_grad, self.exp_avg, self.exp_avg_sq, self.step_dev,
-                                   self.st_dev, self.clip_partials, self.max_norm, self.lr, self.betas, self.eps,
-                                   self.weight_decay, grad_scale)
+        ops.adam_step_dev(self.flat.flat, self.flat.flat_grad, self.exp_avg, self.exp_avg_sq, self.step_dev, self.st_dev,
+                          self.lr, self.betas, self.eps, self.weight_decay, grad_scale, self.clip_partials, self.max_norm,
+                          decoupled=self.kind == "adamw")
 
 
 class FusedAdamW(FusedAdam):
@@ -120,10 +113,6 @@ class FusedAdamW(FusedAdam):
 
     def __init__(self, flat: FlatParameters, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_norm=None):
         super().__init__(flat, lr, betas, eps, weight_decay, max_norm)
-
-    def _launch(self, grad_scale):
-        ops.adamw_step_dev(self.flat.flat, self.flat.flat_grad, self.exp_avg, self.exp_avg_sq, self.step_dev, self.st_dev,
-                           self.lr, self.betas, self.eps, self.weight_decay, grad_scale, self.clip_partials, self.max_norm)
 
 
 class FusedSGD(_FusedOptimizer):
@@ -164,8 +153,6 @@ def get_optimizers(params: dict, flat: FlatParameters):
     name = tc.get("optim", "Adam")
     clip = tc.get("clip_grad_norm")
     if name == "Adam":
-        if clip is None:
-            return FusedAdam(flat, lr=tc.get("lr", 1e-3), weight_decay=tc.get("weight_decay", 0.0))
         return FusedAdam(flat, lr=tc.get("lr", 1e-3), weight_decay=tc.get("weight_decay", 0.0), max_norm=clip)
     if name == "AdamW":
         return FusedAdamW(flat, lr=tc.get("lr", 1e-3), weight_decay=tc.get("weight_decay", 1e-2), max_norm=clip)

@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define ADYOLO_ABI_VERSION 2
+#define ADYOLO_ABI_VERSION 3
 #define ADYOLO_EINVAL (-1)   /* bad shape / alignment / null pointer */
 #define ADYOLO_ENOSUP (-2)   /* shape outside what the kernels are built for */
 
@@ -657,40 +657,29 @@ int  adyolo_corpus_classwise_labels(const double *events, const float *xyz, long
                                     int max_events, int n_label_frames, int n_classes, int format, float *target, int *status,
                                     void *stream);
 
-/* K11 fused Adam over one flat parameter buffer (torch.optim.Adam at src/train.py:31,55; no amsgrad) */
-int adyolo_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, long n,
-                     float lr, float beta1, float beta2, float eps, float weight_decay, int step,
-                     float grad_scale, void *stream);
-/* same update with the step counter ON THE DEVICE (one uint64, incremented by the call itself; bc_dev = 2 floats of
- * scratch for the bias corrections): nothing in the argument list changes from step to step, so the whole train step can
- * be recorded once in a hipGraph and replayed (train.TrainStep(graph=True)). */
-int adyolo_adam_step_dev(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, long n, float lr,
-                         float beta1, float beta2, float eps, float weight_decay, uint64_t *step_dev, float *bc_dev,
-                         float grad_scale, void *stream);
-
-/* K11x AdamW, SGD and gradient-norm clipping on the same flat buffers (csrc/optim_ext.hip; the reference picks its optimizer
- * by name, src/train.py:29-37, and clips with clip_grad_norm_, src/train.py:54).  Device-counter forms only: every call bumps
- * step_dev itself and no argument changes from step to step (hipGraph-replayable).  All float buffers must be 16-byte aligned
- * (ADYOLO_EINVAL otherwise); n need not be a multiple of 4.
+/* K11 Adam, AdamW, SGD and gradient-norm clipping over one flat parameter buffer (csrc/optim.hip; the reference picks its
+ * optimizer by name, src/train.py:29-37, and clips with clip_grad_norm_, src/train.py:54; no amsgrad).  The step counter is ON
+ * THE DEVICE (one uint64): every call bumps step_dev itself and no argument changes from step to step, so the whole train step
+ * can be recorded once in a hipGraph and replayed (train.TrainStep(graph=True)).  All float buffers (parameter, gradient and
+ * state) must be 16-byte aligned (ADYOLO_EINVAL otherwise); n need not be a multiple of 4.
  *   st_dev    4 floats of scratch: {step size, 1/sqrt(bias correction 2)} (Adam / AdamW) or {first-step flag, 0} (SGD),
  *             total_norm (the pre-clip norm of grad * grad_scale, written when clipping is on), clip_coef
  *   partials  adyolo_grad_sumsq_parts(n) doubles of scratch, or NULL = no clipping (clip_coef = 1; max_norm ignored).
  *             With it: clip_coef = min(1, max_norm / (total_norm + 1e-6)) (torch.nn.utils.clip_grad_norm_), multiplied into
- *             grad_scale by the update.  The norm is summed in float64 in a fixed order: the same bits on every call. */
+ *             grad_scale by the update.  The norm is summed in float64 in a fixed order: the same bits on every call.
+ * The update kernels fix their own rounding (no compiler-chosen contraction): the n & 3 tail elements, a clip that does not
+ * bind and the plain step all give the same bits. */
 long adyolo_grad_sumsq_parts(long n);
 /* partials[k] = float64 sum of (grad * grad_scale)^2 over the k-th workgroup's share */
 int  adyolo_grad_sumsq(const float *grad, long n, float grad_scale, double *partials, void *stream);
 /* grad_sumsq + the norm / coefficient part of the prep kernel alone: st_dev[2] = total_norm, st_dev[3] = clip_coef */
 int  adyolo_grad_norm_dev(const float *grad, long n, float grad_scale, double *partials, float max_norm, float *st_dev,
                           void *stream);
-/* torch.optim.AdamW: p *= 1 - lr * weight_decay, then Adam's moments and update */
-int  adyolo_adamw_step_dev(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, long n, float lr, float beta1,
-                           float beta2, float eps, float weight_decay, uint64_t *step_dev, float *st_dev, double *partials,
-                           float max_norm, float grad_scale, void *stream);
-/* adyolo_adam_step_dev's arithmetic with the clip coefficient (partials must not be NULL) */
-int  adyolo_adam_clip_step_dev(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, long n, float lr,
-                               float beta1, float beta2, float eps, float weight_decay, uint64_t *step_dev, float *st_dev,
-                               double *partials, float max_norm, float grad_scale, void *stream);
+/* decoupled == 0: torch.optim.Adam (weight decay added to the gradient).  decoupled != 0: torch.optim.AdamW:
+ * p *= 1 - lr * weight_decay, then Adam's moments and update. */
+int  adyolo_adam_step_dev(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, long n, float lr, float beta1,
+                          float beta2, float eps, float weight_decay, int decoupled, uint64_t *step_dev, float *st_dev,
+                          double *partials, float max_norm, float grad_scale, void *stream);
 /* torch.optim.SGD: g' = grad * scale + wd * p; momentum != 0: buf = g' on the step that takes step_dev from 0 to 1, else
  * buf = momentum * buf + (1 - dampening) * g'; p -= lr * (nesterov ? g' + momentum * buf : buf).  momentum == 0: p -= lr * g',
  * momentum_buf may be NULL and is not touched. */

@@ -48,7 +48,7 @@ def test_adam_device_step_matches_torch(ops):
     pg = p0.to("cuda:0")
     m, v = torch.zeros_like(pg), torch.zeros_like(pg)
     step_dev = torch.zeros(1, dtype=torch.int64, device="cuda:0")
-    bc = torch.zeros(2, device="cuda:0")
+    bc = torch.zeros(ops.OPTIM_SCRATCH_FLOATS, device="cuda:0")
     for _ in range(7):
         grad = torch.randn(p0.numel(), generator=g)
         ref.grad = grad.clone()

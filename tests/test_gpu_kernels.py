@@ -1039,12 +1039,15 @@ def test_adam_matches_torch(ops):
     ref = p0.clone().requires_grad_(True)
     opt = torch.optim.Adam([ref], lr=1e-3)
     pg, m, v = dev(p0), torch.zeros(p0.numel(), device="cuda:0"), torch.zeros(p0.numel(), device="cuda:0")
+    step_dev = torch.zeros(1, dtype=torch.int64, device="cuda:0")
+    st = torch.zeros(ops.OPTIM_SCRATCH_FLOATS, device="cuda:0")
     for step in range(1, 6):
         grad = torch.randn(p0.numel(), generator=g)
         ref.grad = grad.clone()
         opt.step()
-        ops.adam_step(pg, dev(grad * 2.0), m, v, step, grad_scale=0.5)
+        ops.adam_step_dev(pg, dev(grad * 2.0), m, v, step_dev, st, grad_scale=0.5)
     torch.cuda.synchronize()
+    assert int(step_dev) == 5
     assert_close(pg, ref.detach(), 1e-6, "adam params")
 
 

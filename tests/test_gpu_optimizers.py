@@ -1,4 +1,4 @@
-"""GPU: AdamW, SGD and gradient-norm clipping on the flat parameter buffer (csrc/optim_ext.hip) against torch.optim /
+"""GPU: AdamW, SGD and gradient-norm clipping on the flat parameter buffer (csrc/optim.hip) against torch.optim /
 torch.nn.utils.clip_grad_norm_ on the CPU; the whole train step with them, eager vs hipGraph replay (bit for bit); checkpoint
 interchange with torch.optim.AdamW / torch.optim.SGD; two data-parallel ranks deriving the same clip coefficient.
 
@@ -47,11 +47,11 @@ def _max_err(a, b):
 
 
 # ------------------------------------------------------------------------------------------------ 3. kernels vs torch.optim
-@pytest.mark.parametrize("n", [4099, 10004])
+@pytest.mark.parametrize("n", [3, 4099, 10004])
 @pytest.mark.parametrize("wd", [0.0, 0.01])
 def test_adamw_device_step_matches_torch(ops, n, wd):
-    """adyolo_adamw_step_dev against torch.optim.AdamW: 7 steps, gradients pre-multiplied by 4 with grad_scale 0.25; n = 4099
-    has a 3-element tail behind the 16-byte accesses."""
+    """adyolo_adam_step_dev (decoupled) against torch.optim.AdamW: 7 steps, gradients pre-multiplied by 4 with grad_scale 0.25;
+    n = 4099 has a 3-element tail behind the 16-byte accesses, n = 3 is tail only (one workgroup, no float4 access)."""
     g = torch.Generator().manual_seed(3)
     p0 = torch.randn(n, generator=g)
     ref = p0.clone().requires_grad_(True)
@@ -79,7 +79,7 @@ SGD_FORMS = {"plain": {}, "wd": {"weight_decay": 0.01}, "momentum": {"momentum":
              "nesterov": {"momentum": 0.9, "nesterov": True}, "dampening": {"momentum": 0.9, "dampening": 0.1}}
 
 
-@pytest.mark.parametrize("n", [4099, 10004])
+@pytest.mark.parametrize("n", [3, 4099, 10004])
 @pytest.mark.parametrize("form", sorted(SGD_FORMS))
 def test_sgd_device_step_matches_torch(ops, n, form):
     """adyolo_sgd_step_dev against torch.optim.SGD in five forms; the first step initialises the momentum buffer with the
@@ -106,6 +106,60 @@ def test_sgd_device_step_matches_torch(ops, n, form):
     if buf is not None:
         berr = _max_err(buf, opt.state_dict()["state"][0]["momentum_buffer"])
         assert berr <= 1e-5, berr                               # (buffer values reach ~10: 1e-6 relative)
+
+
+# ------------------------------------------------------------------------------------------------ 3b. pinned rounding
+def _run_optimizer(ops, kind, p0, grads, n, clip=False):
+    """3 steps of one optimizer on the first n elements of the given data; returns (p, state..., st) on the device"""
+    pg = p0[:n].to("cuda:0")
+    state = [torch.zeros_like(pg) for _ in range(1 if kind == "sgd" else 2)]
+    step_dev = torch.zeros(1, dtype=torch.int64, device="cuda:0")
+    st = torch.zeros(ops.OPTIM_SCRATCH_FLOATS, device="cuda:0")
+    kw = {"grad_scale": 0.25}
+    if clip:
+        kw.update(partials=torch.zeros(ops.GRAD_SUMSQ_MAX_PARTS, dtype=torch.float64, device="cuda:0"), max_norm=1e30)
+    for gr in grads:
+        gd = gr[:n].to("cuda:0")
+        if kind == "sgd":
+            ops.sgd_step_dev(pg, gd, state[0], step_dev, st, lr=0.01, weight_decay=0.01, momentum=0.9, **kw)
+        else:
+            ops.adam_step_dev(pg, gd, state[0], state[1], step_dev, st, lr=1e-3, weight_decay=0.01,
+                              decoupled=kind == "adamw", **kw)
+    torch.cuda.synchronize()
+    assert int(step_dev) == len(grads)
+    return [pg] + state + [st]
+
+
+def _rounding_data(seed, n):
+    g = torch.Generator().manual_seed(seed)
+    return torch.randn(n, generator=g), [torch.randn(n, generator=g) * 4.0 for _ in range(3)]
+
+
+@pytest.mark.parametrize("kind", ["adam", "adamw", "sgd"])
+def test_body_and_tail_round_alike(ops, kind):
+    """n = 4099 puts elements 4096..4098 in the scalar tail; the same data extended by one element to n = 4100 puts them in a
+    float4.  Parameters and state of the first 4099 elements are equal bit for bit: the rounding is the source's, not the
+    vectoriser's."""
+    p0, grads = _rounding_data(31, 4100)
+    tail = _run_optimizer(ops, kind, p0, grads, 4099)
+    body = _run_optimizer(ops, kind, p0, grads, 4100)
+    for name, a, b in zip(("p", "state0", "state1"), tail[:-1], body[:-1]):
+        diff = (a != b[:4099]).nonzero().flatten().tolist()
+        print("%s %s: elements that differ between tail and body: %r" % (kind, name, diff))
+        assert torch.equal(a, b[:4099]), (kind, name, diff)
+        assert float(a.abs().sum()) > 0.0
+
+
+def test_a_clip_that_does_not_bind_changes_nothing(ops):
+    """adam_step_dev with partials and max_norm = 1e30 (coefficient exactly 1.0) against adam_step_dev without: p, m, v equal
+    bit for bit after 3 steps on n = 4099."""
+    p0, grads = _rounding_data(32, 4099)
+    plain = _run_optimizer(ops, "adam", p0, grads, 4099)
+    clipped = _run_optimizer(ops, "adam", p0, grads, 4099, clip=True)
+    assert float(clipped[-1][3]) == 1.0 and float(plain[-1][3]) == 1.0
+    assert float(clipped[-1][2]) > 0.0                           # the norm was taken
+    for name, a, b in zip("pmv", plain[:-1], clipped[:-1]):
+        assert torch.equal(a, b), name
 
 
 def test_misaligned_buffers_are_refused(ops):
@@ -245,7 +299,7 @@ def test_adam_without_clip_key_is_the_adam_step_dev_path(ops):
     assert type(te.optimizer) is FusedAdam and getattr(te.optimizer, "max_norm", None) is None
     m, v = torch.zeros_like(th.flat.flat), torch.zeros_like(th.flat.flat)
     step_dev = torch.zeros(1, dtype=torch.int64, device="cuda:0")
-    bc = torch.zeros(2, device="cuda:0")
+    bc = torch.zeros(ops.OPTIM_SCRATCH_FLOATS, device="cuda:0")
 
     def by_hand(grad_scale=1.0):
         ops.adam_step_dev(th.flat.flat, th.flat.flat_grad, m, v, step_dev, bc, 1e-3, (0.9, 0.999), 1e-8, 0.0, grad_scale)

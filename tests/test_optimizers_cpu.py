@@ -52,12 +52,13 @@ def _slice_of(flat, buf, p):
 def test_get_optimizers_dispatch():
     """'Adam' stays the same class with the same arguments; 'AdamW' / 'SGD' take lr / weight_decay as the reference passes
     them; the optional keys are honoured; anything else raises NotImplementedError."""
+    from adyolo_amd import ops
     from adyolo_amd.train import FusedAdam, FusedAdamW, FusedSGD, get_optimizers
     _, flat = _small_flat()
     o = get_optimizers(_cpu_params(lr=2e-3, weight_decay=0.1), flat)
     assert type(o) is FusedAdam and o.max_norm is None and o.grad_norm is None
     assert (o.lr, o.betas, o.eps, o.weight_decay) == (2e-3, (0.9, 0.999), 1e-8, 0.1)
-    assert tuple(o.bc_dev.shape) == (2,) and o.step_count == 0 and o.kind == "adam"
+    assert tuple(o.st_dev.shape) == (ops.OPTIM_SCRATCH_FLOATS,) and o.step_count == 0 and o.kind == "adam"
     o = get_optimizers(_cpu_params(optim="AdamW", lr=3e-3, weight_decay=0.02), flat)
     assert type(o) is FusedAdamW and (o.lr, o.weight_decay, o.max_norm) == (3e-3, 0.02, None)
     assert get_optimizers({"train_config": {"optim": "AdamW"}}, flat).weight_decay == 1e-2            # torch.optim.AdamW's default

@@ -2,10 +2,11 @@
 up, repeated).
 
   step      one hipGraph-replayed TrainStep at 16 x 20 s (the reference's batch_size / chunk) and at 64 x 60 s (the bench shape)
-            with 'Adam' (the path this build has always had: ops.adam_step_dev, the baseline), 'AdamW', 'SGD' (plain, as the
-            reference calls it) and 'Adam' with clip_grad_norm 3
+            with 'Adam' (ops.adam_step_dev, the baseline), 'AdamW', 'SGD' (plain, as the reference calls it) and 'Adam' with
+            clip_grad_norm 3
   kernels   the optimizer launches alone on buffers of the real model's flat size (6.68 M floats): adam_step_dev (baseline),
-            adamw_step_dev, sgd_step_dev without / with momentum, adam_clip_step_dev, grad_norm_dev (sum of squares + prep)
+            adamw_step_dev, sgd_step_dev without / with momentum, adam_step_dev with clipping, grad_norm_dev (sum of squares +
+            prep)
 
 At 16 x 20 s the four trainers live side by side and alternate inside each repeat; at 64 x 60 s they are built one after the
 other (activations of one recorded step at a time).  The median of the repeats is reported (ms per call).
@@ -98,15 +99,14 @@ def bench_kernels(reps, iters):
     grad = (torch.randn(n, generator=g) * 1e-2).to("cuda:0")
     m, v, buf = torch.zeros_like(p), torch.zeros_like(p), torch.zeros_like(p)
     step_dev = torch.zeros(1, dtype=torch.int64, device="cuda:0")
-    bc = torch.zeros(2, device="cuda:0")
     st = torch.zeros(ops.OPTIM_SCRATCH_FLOATS, device="cuda:0")
     parts = torch.zeros(ops.GRAD_SUMSQ_MAX_PARTS, dtype=torch.float64, device="cuda:0")
     fns = {
-        "adam_step_dev": lambda: ops.adam_step_dev(p, grad, m, v, step_dev, bc),
+        "adam_step_dev": lambda: ops.adam_step_dev(p, grad, m, v, step_dev, st),
         "adamw_step_dev": lambda: ops.adamw_step_dev(p, grad, m, v, step_dev, st),
         "sgd_step_dev": lambda: ops.sgd_step_dev(p, grad, None, step_dev, st),
         "sgd_step_dev_momentum": lambda: ops.sgd_step_dev(p, grad, buf, step_dev, st, momentum=0.9),
-        "adam_clip_step_dev": lambda: ops.adam_clip_step_dev(p, grad, m, v, step_dev, st, parts, 3.0),
+        "adam_step_dev_clip": lambda: ops.adam_step_dev(p, grad, m, v, step_dev, st, partials=parts, max_norm=3.0),
         "grad_norm_dev": lambda: ops.grad_norm_dev(grad, parts, st, 3.0),
     }
     for f in fns.values():

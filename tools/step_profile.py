@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-kernel time of ONE training step from a rocprofv3 rocpd database (steps are delimited by adam_kernel launches).
+"""Per-kernel time of ONE training step from a rocprofv3 rocpd database (steps are delimited by adam_update_kernel launches).
 usage: python tools/step_profile.py <results.db> [top]"""
 import collections
 import sqlite3
@@ -9,7 +9,7 @@ db = sqlite3.connect(sys.argv[1])
 top = int(sys.argv[2]) if len(sys.argv) > 2 else 40
 rows = list(db.execute("select s.kernel_name, d.grid_size_x, d.grid_size_y, d.grid_size_z, d.start, d.end from "
                        "rocpd_kernel_dispatch d join rocpd_info_kernel_symbol s on d.kernel_id = s.id order by d.start"))
-marks = [i for i, r in enumerate(rows) if "adam_kernel" in r[0]]
+marks = [i for i, r in enumerate(rows) if "adam_update_kernel" in r[0]]
 step = rows[marks[-2] + 1:marks[-1] + 1]
 print("kernels %d, sum %.3f ms, span %.3f ms" % (len(step), sum(r[5] - r[4] for r in step) / 1e6, (step[-1][5] - step[0][4]) / 1e6))
 agg = collections.defaultdict(lambda: [0, 0.0])

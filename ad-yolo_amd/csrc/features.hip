@@ -11,7 +11,7 @@
 // untangled into the four 601-bin spectra, turned into the 7 per-bin quantities
 // (|W|^2,|Y|^2,|Z|^2,|X|^2, Iy/E, Iz/E, Ix/E), which overwrite the transform buffer, and contracted with the sparse
 // (1165 non-zero) triangular mel filters (per-piece partial sums in LDS, combined per filter in a fixed order:
-// bit-reproducible).  34.7 KB of LDS and 122 VGPRs: four workgroups (16 waves) per CU.
+// bit-reproducible).  34.7 KB of LDS and 126 VGPRs: four workgroups (16 waves) per CU.
 // A "virtual clip" is n_samples samples starting at clip_offset[b] of the audio buffer (NULL: clip b of a [B][n][4]
 // batch): the 20 s / 1 s-stride training chunks of a recording (/root/reference/src/preprocess.py:13-84) are computed
 // from the recording in place, each with its own reflect padding and its own top_db reference.
@@ -33,7 +33,7 @@ __device__ __forceinline__ void atomic_max_float(float *addr, float val) {
     else atomicMin(reinterpret_cast<unsigned *>(addr), __float_as_uint(val));
 }
 
-constexpr int MAX_MELW = 1200, SPS8 = 8, MAX_CHUNKS = 224;     // LDS total 34.7 KB, 122 VGPRs: four workgroups per CU
+constexpr int MAX_MELW = 1200, SPS8 = 8, MAX_CHUNKS = 224;     // LDS total 34.7 KB, 126 VGPRs: four workgroups per CU
 // The transform is decimation in frequency, IN PLACE (every thread writes back to the LDS words it has just read, so one
 // barrier per pass and one 22.4 KB buffer for both signals): n = n1*120 + n2*12 + n3, pass 1 = ten-point DFTs over n1
 // (x W_1200^{(n mod 120) k1}), pass 2 = ten-point DFTs over n2 (x W_120^{n3 k2}), pass 3 = twelve-point DFTs over n3;
@@ -221,7 +221,9 @@ __global__ __launch_bounds__(256, 4) void feat_stft_mel_kernel(
                 for (int ck = mel_first[m]; ck < mel_first[m + 1]; ++ck) acc += melpart[ck * 8 + c];
             float v = 0.f;
             if (c < 4) {
-                v = 10.0f * log10f(fmaxf(acc, 1e-10f));
+                // power_to_db's amin: exactly -100 dB at and below it (the device log10f is one ulp off -10 at 1e-10f, and
+                // digital silence -- zero-padded clips -- is all floor)
+                v = acc > 1e-10f ? 10.0f * log10f(acc) : -100.0f;
                 lmax = fmaxf(lmax, v);
             } else if (c < 7) {
                 v = (acc - sc_mean[c * NMEL + m]) * sc_rstd[c * NMEL + m];

@@ -638,8 +638,10 @@ def test_features_match_oracle(ops):
     from adyolo_amd.datasets import synthetic_audio
     scaler = load_scaler_npz(os.path.join(G, "scaler_DCASE2021.npz"))
     audio = synthetic_audio(2, 24000 * 2, seed=9)                    # 2 clips x 2 s -> T = 80
-    # make the second clip quiet in one channel so the top_db clip actually bites
+    # one quiet channel (the top_db floor is per clip and channel: that alone changes nothing) and a quarter second of PCM zeros in
+    # a loud one, where the floor does bite (11 % of that channel's entries: tests/test_feature_stage_cpu.py)
     audio[1, :, 2] *= 1e-4
+    audio[1, 6000:12000, 0] = float(np.float32(1e-8))
     fx = FeatureExtractor(scaler, "cuda:0")
     out_ref_layout = fx(dev(audio), channels_last8=False).cpu()
     out_cl8 = fx(dev(audio), channels_last8=True).cpu()

@@ -9,6 +9,13 @@
 namespace adyolo {
 
 constexpr int GBM = 128, GBN = 64, GBK = 32;
+// The plain operands' 16-byte fetches promise the compiler no more than a float's alignment: parameters packed back to back
+// (dist.FlatParameters) arrive at 4- and 8-byte-aligned addresses, which global_load_dwordx4 takes as they are.
+typedef float f32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
+__device__ __forceinline__ float4 load4_a4(const float *p) {
+    const f32x4_a4 v = *reinterpret_cast<const f32x4_a4 *>(p);
+    return make_float4(v.x, v.y, v.z, v.w);
+}
 #ifndef GEMM_WHATIF
 #define GEMM_WHATIF 0        // timing-only builds (results invalid)
 #endif
@@ -275,7 +282,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN > 4 ? 1 : 2)) void gemm_kern
                 const int row = idx >> 3, q = idx & 7;
                 const int m = m0 + row, k = k0 + q * 4;
                 ra[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (m < M && k < kend) ra[i] = *reinterpret_cast<const float4 *>(A + (size_t)m * lda + k);
+                if (m < M && k < kend) ra[i] = load4_a4(A + (size_t)m * lda + k);
             }
         } else {
 #pragma unroll
@@ -284,7 +291,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN > 4 ? 1 : 2)) void gemm_kern
                 const int kk = idx / (BM / 4), q = idx % (BM / 4);
                 const int k = k0 + kk, m = m0 + q * 4;
                 ra[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (k < kend && m < M) ra[i] = *reinterpret_cast<const float4 *>(A + (size_t)k * lda + m);
+                if (k < kend && m < M) ra[i] = load4_a4(A + (size_t)k * lda + m);
             }
         }
         if (fastB) {
@@ -318,7 +325,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN > 4 ? 1 : 2)) void gemm_kern
                 const int row = idx >> 3, q = idx & 7;
                 const int nn = n0 + row, k = k0 + q * 4;
                 rb[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (nn < N && k < kend) rb[i] = *reinterpret_cast<const float4 *>(B + (size_t)nn * ldb + k);
+                if (nn < N && k < kend) rb[i] = load4_a4(B + (size_t)nn * ldb + k);
             }
         } else {
 #pragma unroll
@@ -327,7 +334,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN > 4 ? 1 : 2)) void gemm_kern
                 const int kk = idx / (BN / 4), q = idx % (BN / 4);
                 const int k = k0 + kk, nn = n0 + q * 4;
                 rb[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (k < kend && nn < N) rb[i] = *reinterpret_cast<const float4 *>(B + (size_t)k * ldb + nn);
+                if (k < kend && nn < N) rb[i] = load4_a4(B + (size_t)k * ldb + nn);
             }
         }
     };
@@ -556,6 +563,32 @@ static int gemm_fast_fetch(int M, int N, int K, int lda, int ldb, int transA, in
     return ea < lim && eb < lim ? 3 : 0;                              // bit 0: operand A, bit 1: operand B
 }
 
+// The host decisions of a launch in one place (adyolo_gemm, adyolo_conv_gemm and adyolo_gemm_plan): the K range of a split
+// in whole K tiles, the number of splits that are not empty with it, and the operands the buffer-descriptor fetch may take.
+struct GemmPlan {
+    int klen, splits, fastg;
+};
+static GemmPlan gemm_plan(int M, int N, int K, int lda, int ldb, int transA, int transB, int splits) {
+    if (splits < 1) splits = 1;
+    GemmPlan p;
+    p.klen = cdiv(cdiv(K, splits), GBK) * GBK;
+    p.splits = cdiv(K, p.klen);
+    p.fastg = gemm_fast_fetch(M, N, K, lda, ldb, transA, transB, p.klen);
+    return p;
+}
+
+// host only (no launch): what adyolo_gemm decides for these arguments.  fastg holds the eligibility bits as the kernel gets
+// them; the kernel takes the descriptor fetch for an operand only where that operand is k-major as well.
+extern "C" int adyolo_gemm_plan(int M, int N, int K, int lda, int ldb, int transA, int transB, int splits, int *klen,
+                                int *eff_splits, int *fastg) {
+    ADYOLO_REQUIRE(M > 0 && N > 0 && K > 0 && klen && eff_splits && fastg, ADYOLO_EINVAL, "gemm_plan: bad arguments");
+    const GemmPlan p = gemm_plan(M, N, K, lda, ldb, transA, transB, splits);
+    *klen = p.klen;
+    *eff_splits = p.splits;
+    *fastg = p.fastg;
+    return 0;
+}
+
 extern "C" int adyolo_scale_dev(const float *a, const float *scalar_dev, float *y, long n, void *stream) {
     ADYOLO_REQUIRE(a && scalar_dev && y && n > 0, ADYOLO_EINVAL, "scale_dev: null pointer or n <= 0");
     const long n4 = n / 4;
@@ -577,9 +610,9 @@ extern "C" int adyolo_gemm(const float *A, const float *B, const float *bias, fl
     if (splits < 1) splits = 1;
     ADYOLO_REQUIRE(splits == 1 || slabs, ADYOLO_EINVAL, "gemm: splits > 1 needs a slab workspace");
     hipStream_t st = as_stream(stream);
-    int klen = cdiv(cdiv(K, splits), GBK) * GBK;
-    splits = cdiv(K, klen);
-    const int fastg = gemm_fast_fetch(M, N, K, lda, ldb, transA, transB, klen);
+    const GemmPlan pl = gemm_plan(M, N, K, lda, ldb, transA, transB, splits);
+    const int klen = pl.klen, fastg = pl.fastg;
+    splits = pl.splits;
     dim3 grid((unsigned)cdiv(N, GBN), (unsigned)cdiv(M, GBM), (unsigned)splits);
     const size_t slab_stride = splits > 1 ? (size_t)M * N : 0;
     float *out = splits > 1 ? slabs : C;
@@ -664,12 +697,13 @@ extern "C" int adyolo_conv_gemm(const float *src, const float *other, float *out
     }
     if (mode != 2 || splits < 1) splits = mode == 2 ? (splits < 1 ? 1 : splits) : 1;
     ADYOLO_REQUIRE(splits == 1 || slabs, ADYOLO_EINVAL, "conv_gemm: splits > 1 needs a slab workspace");
-    const int klen = cdiv(cdiv(K, splits), GBK) * GBK;
-    splits = cdiv(K, klen);
     // the operand that is NOT gathered goes through the buffer-descriptor fetch: mode 2: A = dy [pixels][Cout] (transposed,
     // lda = Cout); modes 0 / 1: B = the packed filter [Nn][K] (k-major, ldb = K)
-    int fastg = mode == 2 ? (gemm_fast_fetch(M, 4, K, Cout, 4, 1, 1, klen) & 1)
-                          : (gemm_fast_fetch(4, Nn, K, 4, mode == 0 ? Kp : Kq, 0, 0, klen) & 2);
+    const GemmPlan pl = mode == 2 ? gemm_plan(M, 4, K, Cout, 4, 1, 1, splits)
+                                  : gemm_plan(4, Nn, K, 4, mode == 0 ? Kp : Kq, 0, 0, splits);
+    const int klen = pl.klen;
+    splits = pl.splits;
+    int fastg = pl.fastg & (mode == 2 ? 1 : 2);
     // bit 2: the gathered operand of a forward / unit-stride data-gradient launch through a descriptor as well (whole K tiles
     // inside one tap: source channels a multiple of the K tile; source below 2^29 floats incl. the tap bias)
     if (fastg && mode != 2 && cg.Cs % GBK == 0 && (mode == 0 || (SH == 1 && SW == 1)) &&

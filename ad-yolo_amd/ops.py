@@ -504,8 +504,32 @@ def linear_bwd(x2d, w, dy2d, need_dx=True, out_dw=None, out_db=None, need_db=Tru
     _chk(x2d, w, dy2d)
     r, k = x2d.shape
     n = w.shape[0]
+    if n % 4:
+        return _linear_bwd_padded(x2d, w, dy2d, need_dx, out_dw, out_db, need_db)
     dx = gemm(dy2d, w, r, k, n, n, k, trans_b=True) if need_dx else None
     dw = gemm(dy2d, x2d, n, k, r, n, k, trans_a=True, trans_b=True, splits=wgrad_splits(n, k, r), out=out_dw)
+    db = colsum(dy2d, out=out_db) if need_db else None
+    return dx, dw, db
+
+
+def _linear_bwd_padded(x2d, w, dy2d, need_dx, out_dw, out_db, need_db):
+    """``linear_bwd`` for an output width n that is no multiple of 4 (class-wise heads at 13 classes: 13, 39, 117).  dy is
+    operand A of both GEMMs with lda = n, which the 16-byte fetches refuse; they run on copies padded to roundup4(n) with
+    exact zeros -- dy [R][n4], w [n4][K] -- which add nothing to any sum, and dW's first n rows are copied out."""
+    r, k = x2d.shape
+    n = w.shape[0]
+    n4 = (n + 3) // 4 * 4
+    dyp = _zeros(dy2d, r, n4)
+    dyp[:, :n].copy_(dy2d)
+    dx = None
+    if need_dx:
+        wp = _zeros(w, n4, k)
+        wp[:n].copy_(w)
+        dx = gemm(dyp, wp, r, k, n4, n4, k, trans_b=True)
+    dw = gemm(dyp, x2d, n4, k, r, n4, k, trans_a=True, trans_b=True, splits=wgrad_splits(n4, k, r))[:n]
+    if out_dw is not None:
+        out_dw.view(n, k).copy_(dw)
+        dw = out_dw
     db = colsum(dy2d, out=out_db) if need_db else None
     return dx, dw, db
 

@@ -197,6 +197,11 @@ int adyolo_conv3x3_wgrad(const float *x, const float *dy, const float *in_scale,
 int adyolo_gemm(const float *A, const float *B, const float *bias, float *C, float *slabs, int M,
                 int N, int K, int lda, int ldb, int ldc, int transA, int transB, int splits,
                 int accumulate, void *stream);
+/* host only, no launch: what adyolo_gemm decides for these arguments -- klen: the K range of one split (whole K tiles of 32),
+ * eff_splits: the splits that are not empty with it, fastg: bit 0 / 1 = operand A / B may go through a buffer descriptor
+ * (taken by the kernel for k-major operands only). */
+int adyolo_gemm_plan(int M, int N, int K, int lda, int ldb, int transA, int transB, int splits, int *klen,
+                     int *eff_splits, int *fastg);
 /* batched variant (attention, resnet_conformer.py:57-85): problem (o, i), o < outer, i < inner, uses the operand
  * bases A + o*oA + i*iA etc. (strides in floats, multiples of 4);  C = alpha * product (+ C when accumulate). */
 int adyolo_gemm_batched(const float *A, const float *B, float *C, int M, int N, int K, int lda, int ldb, int ldc,

@@ -19,7 +19,7 @@ SR = 24000
 RECS = (("fold1_room1_mix001", 6.0), ("fold1_room2_mix002", 3.7), ("fold2_room1_mix003", 2.0), ("take_chunk3_mix", 4.0))
 #        5 + 3 + 1 + 3 = 12 chunks of 2 s (1 s stride): 48000 samples, 20 label frames, the test model's shape
 T_LABEL = 20
-C_TRAIN = 12     # the training tests: the heads' GEMMs need 3C and 9C in multiples of 4 (ACCDOA / ADPIT), so no model has C = 13
+C_TRAIN = 12     # the corpus-against-host training tests; any class count trains (test_train_step_at_13_classes_... below)
 
 
 @pytest.fixture(scope="module")
@@ -277,3 +277,30 @@ def test_config5_mic_adpit_specaug_epoch_equals_the_host_epoch(ops, mic_split):
     prm = _prm(mic_split, "adpit", mic=True, nb_classes=C_TRAIN)
     corpus = _epochs_agree(prm, 31, True, mic=True)
     assert corpus.host.wav_pth.split("/")[-2] == "mic_dev" and corpus.specaug.apply_augment
+
+
+@pytest.mark.parametrize("loss", ["accdoa", "adpit"])
+def test_train_step_at_13_classes_eager_equals_replayed(ops, split, loss):
+    """C = 13, the class count of the DCASE2022 data: head widths 39 and 117, no multiples of 4 (``ops.linear_bwd`` pads them).
+    Three ``TrainStep`` steps from the corpus, eagerly and with the step replayed from a captured graph: the same bits."""
+    from adyolo_amd.corpus import ClasswiseDeviceCorpus, load_chunked_split
+    from adyolo_amd.train import train_one_epoch_corpus
+    assert C == 13
+    prm = _prm(split, loss)
+    hc = load_chunked_split(prm)
+    runs = []
+    for graph in (False, True):
+        random.seed(29)
+        corpus = ClasswiseDeviceCorpus(hc, prm, "cuda:0", rank=0, world=1)
+        tr = _trainer(graph, prm)
+        train_one_epoch_corpus(prm, corpus, tr)
+        torch.cuda.synchronize()
+        runs.append(tr)
+    eager, replayed = runs
+    assert len(eager.recorded) == len(replayed.recorded) == 3
+    assert replayed.graphs.captures == 1 and replayed.graphs.replays == 2
+    for i, ((le, _, _), (lr, _, _)) in enumerate(zip(eager.recorded, replayed.recorded)):
+        assert bool(torch.isfinite(le)) and torch.equal(le, lr), (i, float(le), float(lr))
+    assert torch.equal(eager.flat.flat, replayed.flat.flat)
+    assert torch.equal(eager.optimizer.exp_avg, replayed.optimizer.exp_avg)
+    assert bool(torch.isfinite(eager.flat.flat).all())

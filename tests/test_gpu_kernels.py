@@ -606,16 +606,17 @@ def test_other_losses_and_heads_match_reference_golden(ops):
     assert_close(rg.grad, ro.grad, 1e-6, "head activation grad")
 
 
+@pytest.mark.parametrize("nb_classes", [12, 13])
 @pytest.mark.parametrize("loss_nm", ["adpit", "accdoa", "masked-seddoa"])
-def test_other_loss_plugins_train_end_to_end(ops, loss_nm):
+def test_other_loss_plugins_train_end_to_end(ops, loss_nm, nb_classes):
     from adyolo_amd.wrapper import WrapperModel, WrapperCriterion
     from adyolo_amd.datasets import ClasswiseLabelEncoder
     torch.manual_seed(100)
-    prm = _params()
+    prm = _params(nb_classes)
     prm["args"]["loss"] = loss_nm
     model = WrapperModel((1, 7, 32, 64), (), prm).to("cuda:0")
     crit = WrapperCriterion(prm)
-    enc = ClasswiseLabelEncoder(12)
+    enc = ClasswiseLabelEncoder(nb_classes)
     events = {0: [[3, 0, 10.0, 5.0]], 2: [[3, 0, 10.0, 5.0], [3, 1, -170.0, 40.0]], 5: [[1, 0, 0.0, 0.0], [2, 1, 90.0, 10.0]]}
     lab = {"adpit": enc.get_adpit_label, "accdoa": enc.get_accdoa_label, "masked-seddoa": enc.get_seddoa_label}[loss_nm]
     target = torch.stack([lab(events, 8), lab({}, 8)])

@@ -141,6 +141,10 @@ SIGNATURES = {
     "adyolo_grad_norm_dev": (I, [P, L, F, P, F, P, P]),
     "adyolo_adam_step_dev": (I, [P] * 4 + [L, F, F, F, F, F, I, P, P, P, F, F, P]),
     "adyolo_sgd_step_dev": (I, [P] * 3 + [L, F, F, F, F, I, P, P, P, F, F, P]),
+    "adyolo_sched_table_doubles": (I, []),
+    "adyolo_sched_out_floats": (I, []),
+    "adyolo_adam_step_sched_dev": (I, [P] * 4 + [L, F, F, F, F, I, P, P, P, F, F, P, P, P, P]),
+    "adyolo_sgd_step_sched_dev": (I, [P] * 3 + [L, F, F, F, I, P, P, P, F, F, P, P, P, P]),
 }
 
 _lib = None

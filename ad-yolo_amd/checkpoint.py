@@ -5,6 +5,12 @@ optim_state_dict, confidence_thresh}.  ``model_state_dict`` has the reference's 
 ``optim_state_dict`` is the layout of the optimizer's torch.optim counterpart (Adam, AdamW or SGD) with parameter indices in
 ``model.parameters()`` order.
 
+With a learning-rate schedule or an EMA on the optimizer (``train_config['lr_schedule']`` / ``['ema_decay']``), and only then,
+both files gain ``sched_state_dict`` (the optimizer's ``sched_state_dict()``: configuration, current base rate, the schedule's
+step, the EMA's update count) and, with an EMA, ``ema_state_dict``: the layout of ``model_state_dict`` with the parameters taken
+from the EMA and the buffers from the live model, so that the reference loads it as a model.  Without them the files are what
+they always were.
+
 Unlike the reference the RNG helpers do not touch ``torch.cuda`` when the device is the CPU.
 """
 import os
@@ -108,6 +114,13 @@ def _load_sgd_state(optimizer, params, sd, g):
     if optimizer.momentum != 0 and not resumed:
         optimizer.momentum_buffer.zero_()
     optimizer.step_count = 1 if resumed else 0
+    _refresh_schedule(optimizer)
+
+
+def _refresh_schedule(optimizer):
+    """the loaded group's ``lr`` is the schedule's base rate: rewrite the device table (scheduled optimizers only)"""
+    if getattr(optimizer, "sched_dev", None) is not None:
+        optimizer._write_table()
 
 
 def load_optimizer_state_dict(optimizer, model, sd):
@@ -143,6 +156,41 @@ def load_optimizer_state_dict(optimizer, model, sd):
     if len(steps) > 1:
         raise ValueError("per-parameter step counts differ (%s): not a plain Adam run" % sorted(steps))
     optimizer.step_count = steps.pop() if steps else 0
+    _refresh_schedule(optimizer)
+
+
+def _flat_slices(optimizer, model):
+    """-> [(state_dict key, parameter, offset in the flat buffer, numel)] of the parameters that live in the flat buffer"""
+    flat = optimizer.flat
+    where = {id(p): k for k, p in enumerate(flat.params)}
+    return [(name, p) + tuple(flat.offsets[where[id(p)]]) for name, p in model.named_parameters() if id(p) in where]
+
+
+def ema_state_dict(optimizer, model, model_sd=None):
+    """``model_state_dict``'s layout and keys: parameters from the optimizer's EMA (the live ones while it has had no update),
+    buffers -- BatchNorm running statistics among them -- from the live model (or from ``model_sd``, a state_dict to fill)."""
+    sd = {k: v.detach().cpu() for k, v in model.state_dict().items()} if model_sd is None else dict(model_sd)
+    if optimizer.ema_updates > 0:
+        for name, p, off, n in _flat_slices(optimizer, model):
+            sd[name] = _cpu_slice(optimizer.ema, off, n, p)
+    return sd
+
+
+def load_ema_state_dict(optimizer, model, sd):
+    for name, p, off, n in _flat_slices(optimizer, model):
+        if tuple(sd[name].shape) != tuple(p.shape):
+            raise ValueError("EMA state %s has shape %s, parameter %s" % (name, tuple(sd[name].shape), tuple(p.shape)))
+        optimizer.ema[off:off + n].copy_(sd[name].reshape(-1))
+
+
+def _schedule_entries(optimizer, model, sd):
+    """the keys a scheduled / averaging optimizer adds to a checkpoint file (none otherwise)"""
+    if getattr(optimizer, "sched_dev", None) is None:
+        return {}
+    out = {"sched_state_dict": optimizer.sched_state_dict()}
+    if optimizer.ema is not None:
+        out["ema_state_dict"] = ema_state_dict(optimizer, model, sd)
+    return out
 
 
 def _state_dict_for_save(model, group=None):
@@ -174,11 +222,13 @@ def save_checkpoint(path, model, optimizer, start_epoch_nb, conf_thresh, best_lo
     writes, sd = _state_dict_for_save(model, group)
     if not writes:
         return
-    torch.save({"start_epoch_nb": start_epoch_nb,
-                "model_state_dict": sd,
-                "optim_state_dict": optimizer_state_dict(optimizer, model),
-                "confidence_thresh": float(conf_thresh), "rng_state": get_rng_state(device, model), "best_log": best_log,
-                "train_remaining_file": train_remaining_file}, path)
+    ck = {"start_epoch_nb": start_epoch_nb,
+          "model_state_dict": sd,
+          "optim_state_dict": optimizer_state_dict(optimizer, model),
+          "confidence_thresh": float(conf_thresh), "rng_state": get_rng_state(device, model), "best_log": best_log,
+          "train_remaining_file": train_remaining_file}
+    ck.update(_schedule_entries(optimizer, model, sd))
+    torch.save(ck, path)
 
 
 def save_best(path, model, optimizer, epoch_nb, conf_thresh, group=None):
@@ -186,17 +236,28 @@ def save_best(path, model, optimizer, epoch_nb, conf_thresh, group=None):
     writes, sd = _state_dict_for_save(model, group)
     if not writes:
         return
-    torch.save({"epoch_nb": epoch_nb, "model_state_dict": sd,
-                "optim_state_dict": optimizer_state_dict(optimizer, model), "confidence_thresh": float(conf_thresh)}, path)
+    ck = {"epoch_nb": epoch_nb, "model_state_dict": sd,
+          "optim_state_dict": optimizer_state_dict(optimizer, model), "confidence_thresh": float(conf_thresh)}
+    ck.update(_schedule_entries(optimizer, model, sd))
+    torch.save(ck, path)
 
 
 def load_checkpoint(path, model, optimizer=None, device="cpu", restore_rng=True):
     """-> the checkpoint dictionary; model (strict) and optimizer are restored in place.  Parameters stay views of the
-    flat buffer: ``load_state_dict`` copies into them."""
+    flat buffer: ``load_state_dict`` copies into them.  An optimizer with a schedule / EMA continues both from
+    ``sched_state_dict`` / ``ema_state_dict``; a file without ``ema_state_dict`` starts the EMA from the loaded parameters."""
     ck = torch.load(path, map_location="cpu", weights_only=False)
     model.load_state_dict(ck["model_state_dict"], strict=True)
     if optimizer is not None and "optim_state_dict" in ck:
         load_optimizer_state_dict(optimizer, model, ck["optim_state_dict"])
+    if optimizer is not None and getattr(optimizer, "sched_dev", None) is not None:
+        if "sched_state_dict" in ck:
+            optimizer.load_sched_state_dict(ck["sched_state_dict"])
+        if optimizer.ema is not None:
+            if "ema_state_dict" in ck:
+                load_ema_state_dict(optimizer, model, ck["ema_state_dict"])
+            else:
+                optimizer.restart_ema()
     if restore_rng and ck.get("rng_state") is not None:
         seed_resume(ck["rng_state"], device, model)
     return ck

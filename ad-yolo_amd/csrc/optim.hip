@@ -9,6 +9,11 @@
 //                       (SGD); st[2] = total_norm (fp32); st[3] = clip_coef = min(1, max_norm / (total_norm + 1e-6)) -- 1 when off
 //   *_update_kernel     the update, grad_scale * st[3] folded into the gradient (exact when st[3] = 1: the unclipped step is
 //                       the same kernel)
+// The *_sched entry points take the learning rate from the device instead of from an argument: the prep kernel evaluates a
+// closed-form schedule in double from the counter and a host-written table (SCHED_* below), rounds it to float ONCE and from
+// there treats it exactly as the plain entry points treat their `lr` argument, so a constant schedule gives the plain step's
+// bits.  They can also keep an exponential moving average of the parameters in the update launch (template flag EMA: two
+// more streams, none without it).
 // st is 4 floats of device scratch.  All streams move 16 bytes per lane per access (pointers 16-byte aligned, the n & 3 tail
 // elements are done by workgroup 0); grids are capped and grid-stride.  Elements that are zero in parameter, gradient and state
 // (the padding of dist.FlatParameters) stay zero in every kernel.
@@ -24,6 +29,29 @@ namespace adyolo {
 constexpr int OX_THREADS = 256;
 constexpr int OX_MAX_BLOCKS = 2048;      // update kernels: 8 workgroups per CU, grid-stride beyond
 constexpr int OX_SUMSQ_BLOCKS = 1024;    // = the largest number of partials (8 KB of float64)
+
+// sched_dev: the schedule table, float64, written by the host only (construction, load_state_dict, set_lr)
+enum {
+    SCHED_KIND = 0,         // SCHED_CONSTANT ... SCHED_COSINE
+    SCHED_BASE = 1,         // base learning rate
+    SCHED_EVERY = 2,        // steps per schedule unit: e = floor((t - 1) / every)
+    SCHED_WARMUP = 3,       // W warm-up STEPS (0 = none)
+    SCHED_START = 4,        // s: warm(t) = s + (1 - s) * min(t - 1, W) / W
+    SCHED_GAMMA = 5,        // step / multistep / exponential
+    SCHED_STEP_SIZE = 6,    // step
+    SCHED_T_MAX = 7,        // cosine
+    SCHED_ETA_MIN = 8,      // cosine
+    SCHED_N_MILESTONES = 9, // multistep: how many of the 8 slots are used
+    SCHED_MILESTONE0 = 10,  // .. 17
+    SCHED_OFFSET = 18,      // t = device counter (after its increment) + this: the schedule's clock survives a resume
+    SCHED_EMA_DECAY = 19,
+    SCHED_EMA_WARMUP = 20,  // != 0: decay_eff = min(decay, (1 + k) / (10 + k))
+    SCHED_EMA_OFFSET = 21,  // k = device counter (after its increment) - 1 + this: EMA updates so far
+    SCHED_TABLE_DOUBLES = 24
+};
+enum { SCHED_CONSTANT = 0, SCHED_STEP = 1, SCHED_MULTISTEP = 2, SCHED_EXPONENTIAL = 3, SCHED_COSINE = 4 };
+// sched_out: what the prep kernel derives for this step, float32
+enum { SOUT_LR = 0, SOUT_DECAY = 1, SOUT_EMA_W = 2, SOUT_EMA_FIRST = 3, SCHED_OUT_FLOATS = 4 };
 
 static inline int update_grid(long n) {
     long g = ((n >> 2) + OX_THREADS - 1) / OX_THREADS;
@@ -65,15 +93,56 @@ __global__ __launch_bounds__(OX_THREADS) void grad_sumsq_kernel(const float *__r
 // ---------------------------------------------------------------------------------------------- prep
 enum { PREP_ADAM = 0, PREP_SGD = 1, PREP_NORM = 2 };
 
+// lr(t) = base * warm(t) * main(e) in double, rounded to float once; t = 1 runs at the base rate (torch's convention when
+// scheduler.step() follows optimizer.step())
+__device__ static float sched_lr(const double *__restrict__ tb, unsigned long long step) {
+    const double t = (double)step + tb[SCHED_OFFSET];
+    const double base = tb[SCHED_BASE], W = tb[SCHED_WARMUP], s0 = tb[SCHED_START];
+    const double e = floor((t - 1.0) / tb[SCHED_EVERY]);
+    const double warm = W > 0.0 ? s0 + (1.0 - s0) * fmin(t - 1.0, W) / W : 1.0;
+    double main_f = 1.0;
+    switch ((int)tb[SCHED_KIND]) {
+    case SCHED_STEP: main_f = pow(tb[SCHED_GAMMA], floor(e / tb[SCHED_STEP_SIZE])); break;
+    case SCHED_MULTISTEP: {
+        int hit = 0;
+        const int nm = (int)tb[SCHED_N_MILESTONES];
+        for (int i = 0; i < nm && i < 8; ++i) hit += tb[SCHED_MILESTONE0 + i] <= e ? 1 : 0;
+        main_f = pow(tb[SCHED_GAMMA], (double)hit);
+        break;
+    }
+    case SCHED_EXPONENTIAL: main_f = pow(tb[SCHED_GAMMA], e); break;
+    case SCHED_COSINE: {    // torch's closed form, held at eta_min after T_max
+        const double T = tb[SCHED_T_MAX], lo = tb[SCHED_ETA_MIN];
+        main_f = (lo + (base - lo) * (1.0 + cos(M_PI * fmin(e, T) / T)) / 2.0) / base;
+        break;
+    }
+    default: break;
+    }
+    return (float)(base * warm * main_f);
+}
+
 // one workgroup of OX_THREADS.  partials == nullptr: clipping off (st[3] = 1, st[2] untouched).  PREP_NORM: no counter, norm only.
+// sched != nullptr (the *_sched entry points): `lr` is ignored, the step's rate comes from the table and is written with
+// AdamW's decay and the EMA's weight to sched_out.
 __global__ __launch_bounds__(OX_THREADS) void optim_prep_kernel(unsigned long long *__restrict__ step, float *__restrict__ st,
                                                                 int kind, float lr, float beta1, float beta2,
                                                                 const double *__restrict__ partials, int nparts,
-                                                                float max_norm) {
+                                                                float max_norm, const double *__restrict__ sched,
+                                                                float *__restrict__ sched_out, float wd) {
     __shared__ double red[OX_THREADS];
     if (threadIdx.x == 0 && kind != PREP_NORM) {
         const unsigned long long s = *step + 1ull;
         *step = s;
+        if (sched != nullptr) {
+            lr = sched_lr(sched, s);
+            const double k = (double)s - 1.0 + sched[SCHED_EMA_OFFSET];       // EMA updates so far
+            double keep = sched[SCHED_EMA_DECAY];
+            if (sched[SCHED_EMA_WARMUP] != 0.0) keep = fmin(keep, (1.0 + k) / (10.0 + k));
+            sched_out[SOUT_LR] = lr;
+            sched_out[SOUT_DECAY] = (float)(1.0 - (double)lr * (double)wd);
+            sched_out[SOUT_EMA_W] = (float)(1.0 - keep);
+            sched_out[SOUT_EMA_FIRST] = k <= 0.0 ? 1.f : 0.f;
+        }
         if (kind == PREP_ADAM) {           // {lr / (1 - beta1^t), 1 / sqrt(1 - beta2^t)} in double like torch's host arithmetic
             const double bc1 = 1.0 - pow((double)beta1, (double)s);
             const double bc2 = 1.0 - pow((double)beta2, (double)s);
@@ -127,15 +196,29 @@ __device__ __forceinline__ void adam_one(float &p, float g, float &m, float &v, 
     p = __builtin_fmaf(-step_size, m / __builtin_fmaf(sqrtf(v), inv_sqrt_bc2, eps), pi);
 }
 
-template <bool DECOUPLED>
+// The moving average of the parameters, after p is formed: a copy on its first update (the old value is not read), else
+// ema += (p - ema) * w as one fused multiply-add.
+__device__ __forceinline__ void ema_one(float &a, float p, float w, bool first) {
+#pragma clang fp contract(off)
+    a = first ? p : __builtin_fmaf(p - a, w, a);
+}
+
+// SCHED: `decay` comes from so[SOUT_DECAY] (the prep kernel formed it from this step's rate) instead of the argument; the
+// rate itself is already inside st[0].  EMA (SCHED only): ema is a third read-write stream laid out like p.
+template <bool DECOUPLED, bool SCHED, bool EMA>
 __global__ __launch_bounds__(OX_THREADS) void adam_update_kernel(float *__restrict__ p, const float *__restrict__ g,
                                                                  float *__restrict__ m, float *__restrict__ v, long n,
                                                                  float beta1, float beta2, float eps, float wd, float decay,
-                                                                 float grad_scale, const float *__restrict__ st) {
+                                                                 float grad_scale, const float *__restrict__ st,
+                                                                 const float *__restrict__ so, float *__restrict__ ema) {
     const float step_size = st[0], inv_sqrt_bc2 = st[1];
     const float gs = grad_scale * st[3];
+    if (SCHED) decay = so[SOUT_DECAY];
+    const float ew = EMA ? so[SOUT_EMA_W] : 0.f;
+    const bool efirst = EMA && so[SOUT_EMA_FIRST] != 0.f;
     const long n4 = n >> 2;
     float4 *p4 = reinterpret_cast<float4 *>(p), *m4 = reinterpret_cast<float4 *>(m), *v4 = reinterpret_cast<float4 *>(v);
+    float4 *e4 = reinterpret_cast<float4 *>(ema);
     const float4 *g4 = reinterpret_cast<const float4 *>(g);
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
         float4 pv = p4[i], mv = m4[i], vv = v4[i];
@@ -147,10 +230,24 @@ __global__ __launch_bounds__(OX_THREADS) void adam_update_kernel(float *__restri
         p4[i] = pv;
         m4[i] = mv;
         v4[i] = vv;
+        if (EMA) {
+            float4 ev = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (!efirst) ev = e4[i];
+            ema_one(ev.x, pv.x, ew, efirst);
+            ema_one(ev.y, pv.y, ew, efirst);
+            ema_one(ev.z, pv.z, ew, efirst);
+            ema_one(ev.w, pv.w, ew, efirst);
+            e4[i] = ev;
+        }
     }
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
         const long i = n4 * 4 + threadIdx.x;
         adam_one<DECOUPLED>(p[i], g[i], m[i], v[i], gs, beta1, beta2, eps, wd, decay, step_size, inv_sqrt_bc2);
+        if (EMA) {
+            float ev = efirst ? 0.f : ema[i];
+            ema_one(ev, p[i], ew, efirst);
+            ema[i] = ev;
+        }
     }
 }
 
@@ -173,15 +270,21 @@ __device__ __forceinline__ void sgd_one(float &p, float g, float *buf, float gs,
     p = __builtin_fmaf(-lr, gi, pi);
 }
 
-template <bool MOM>
+// SCHED: `lr` comes from so[SOUT_LR] instead of the argument.  EMA (SCHED only): as in adam_update_kernel.
+template <bool MOM, bool SCHED, bool EMA>
 __global__ __launch_bounds__(OX_THREADS) void sgd_update_kernel(float *__restrict__ p, const float *__restrict__ g,
                                                                 float *__restrict__ buf, long n, float lr, float wd, float mu,
                                                                 float keep, int nesterov, float grad_scale,
-                                                                const float *__restrict__ st) {
+                                                                const float *__restrict__ st, const float *__restrict__ so,
+                                                                float *__restrict__ ema) {
     const bool first = st[0] != 0.f, nest = nesterov != 0;
     const float gs = grad_scale * st[3];
+    if (SCHED) lr = so[SOUT_LR];
+    const float ew = EMA ? so[SOUT_EMA_W] : 0.f;
+    const bool efirst = EMA && so[SOUT_EMA_FIRST] != 0.f;
     const long n4 = n >> 2;
     float4 *p4 = reinterpret_cast<float4 *>(p), *b4 = reinterpret_cast<float4 *>(buf);
+    float4 *e4 = reinterpret_cast<float4 *>(ema);
     const float4 *g4 = reinterpret_cast<const float4 *>(g);
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
         float4 pv = p4[i];
@@ -194,10 +297,24 @@ __global__ __launch_bounds__(OX_THREADS) void sgd_update_kernel(float *__restric
         sgd_one<MOM>(pv.w, gv.w, &bv.w, gs, lr, wd, mu, keep, nest, first);
         p4[i] = pv;
         if (MOM) b4[i] = bv;
+        if (EMA) {
+            float4 ev = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (!efirst) ev = e4[i];
+            ema_one(ev.x, pv.x, ew, efirst);
+            ema_one(ev.y, pv.y, ew, efirst);
+            ema_one(ev.z, pv.z, ew, efirst);
+            ema_one(ev.w, pv.w, ew, efirst);
+            e4[i] = ev;
+        }
     }
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
         const long i = n4 * 4 + threadIdx.x;
         sgd_one<MOM>(p[i], g[i], MOM ? buf + i : nullptr, gs, lr, wd, mu, keep, nest, first);
+        if (EMA) {
+            float ev = efirst ? 0.f : ema[i];
+            ema_one(ev, p[i], ew, efirst);
+            ema[i] = ev;
+        }
     }
 }
 
@@ -207,10 +324,48 @@ static int launch_sumsq(const float *grad, long n, float grad_scale, double *par
 }
 
 static int launch_prep(uint64_t *step_dev, float *st_dev, int kind, float lr, float beta1, float beta2, const double *partials,
-                       long n, float max_norm, hipStream_t st) {
+                       long n, float max_norm, hipStream_t st, const double *sched = nullptr, float *sched_out = nullptr,
+                       float wd = 0.f) {
     hipLaunchKernelGGL(optim_prep_kernel, dim3(1), dim3(OX_THREADS), 0, st, reinterpret_cast<unsigned long long *>(step_dev),
-                       st_dev, kind, lr, beta1, beta2, partials, partials ? sumsq_grid(n) : 0, max_norm);
+                       st_dev, kind, lr, beta1, beta2, partials, partials ? sumsq_grid(n) : 0, max_norm, sched, sched_out, wd);
     return check_launch("optim_prep");
+}
+
+// the Adam / AdamW step behind both entry points.  sched == nullptr: lr is the argument (and decay formed from it here)
+static int adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, long n, float lr, float beta1,
+                     float beta2, float eps, float weight_decay, int decoupled, uint64_t *step_dev, float *st_dev,
+                     double *partials, float max_norm, float grad_scale, const double *sched, float *sched_out, float *ema,
+                     hipStream_t st, const char *what) {
+    int rc;
+    if (partials && (rc = launch_sumsq(grad, n, grad_scale, partials, st))) return rc;
+    if ((rc = launch_prep(step_dev, st_dev, PREP_ADAM, lr, beta1, beta2, partials, n, max_norm, st, sched, sched_out,
+                          weight_decay)))
+        return rc;
+    const float decay = (float)(1.0 - (double)lr * (double)weight_decay);
+    auto kernel = decoupled ? adam_update_kernel<true, false, false> : adam_update_kernel<false, false, false>;
+    if (sched && ema) kernel = decoupled ? adam_update_kernel<true, true, true> : adam_update_kernel<false, true, true>;
+    else if (sched) kernel = decoupled ? adam_update_kernel<true, true, false> : adam_update_kernel<false, true, false>;
+    hipLaunchKernelGGL(kernel, dim3(update_grid(n)), dim3(OX_THREADS), 0, st, param, grad, exp_avg, exp_avg_sq, n, beta1, beta2,
+                       eps, weight_decay, decay, grad_scale, (const float *)st_dev, (const float *)sched_out, ema);
+    return check_launch(what);
+}
+
+static int sgd_step(float *param, const float *grad, float *momentum_buf, long n, float lr, float weight_decay, float momentum,
+                    float dampening, int nesterov, uint64_t *step_dev, float *st_dev, double *partials, float max_norm,
+                    float grad_scale, const double *sched, float *sched_out, float *ema, hipStream_t st, const char *what) {
+    int rc;
+    if (partials && (rc = launch_sumsq(grad, n, grad_scale, partials, st))) return rc;
+    if ((rc = launch_prep(step_dev, st_dev, PREP_SGD, lr, 0.f, 0.f, partials, n, max_norm, st, sched, sched_out, 0.f)))
+        return rc;
+    const float keep = (float)(1.0 - (double)dampening);
+    const bool mom = momentum != 0.f;
+    auto kernel = mom ? sgd_update_kernel<true, false, false> : sgd_update_kernel<false, false, false>;
+    if (sched && ema) kernel = mom ? sgd_update_kernel<true, true, true> : sgd_update_kernel<false, true, true>;
+    else if (sched) kernel = mom ? sgd_update_kernel<true, true, false> : sgd_update_kernel<false, true, false>;
+    hipLaunchKernelGGL(kernel, dim3(update_grid(n)), dim3(OX_THREADS), 0, st, param, grad, mom ? momentum_buf : (float *)nullptr,
+                       n, lr, weight_decay, mom ? momentum : 0.f, keep, nesterov, grad_scale, (const float *)st_dev,
+                       (const float *)sched_out, ema);
+    return check_launch(what);
 }
 
 }  // namespace adyolo
@@ -241,15 +396,8 @@ extern "C" int adyolo_adam_step_dev(float *param, const float *grad, float *exp_
                    "adam_step_dev: bad arguments");
     ADYOLO_REQUIRE(aligned16(param) && aligned16(grad) && aligned16(exp_avg) && aligned16(exp_avg_sq), ADYOLO_EINVAL,
                    "adam_step_dev: buffers not 16-byte aligned");
-    hipStream_t st = as_stream(stream);
-    int rc;
-    if (partials && (rc = launch_sumsq(grad, n, grad_scale, partials, st))) return rc;
-    if ((rc = launch_prep(step_dev, st_dev, PREP_ADAM, lr, beta1, beta2, partials, n, max_norm, st))) return rc;
-    const float decay = (float)(1.0 - (double)lr * (double)weight_decay);
-    auto kernel = decoupled ? adam_update_kernel<true> : adam_update_kernel<false>;
-    hipLaunchKernelGGL(kernel, dim3(update_grid(n)), dim3(OX_THREADS), 0, st, param, grad, exp_avg, exp_avg_sq, n, beta1, beta2,
-                       eps, weight_decay, decay, grad_scale, (const float *)st_dev);
-    return check_launch("adam_step_dev");
+    return adam_step(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, decoupled, step_dev, st_dev,
+                     partials, max_norm, grad_scale, nullptr, nullptr, nullptr, as_stream(stream), "adam_step_dev");
 }
 
 extern "C" int adyolo_sgd_step_dev(float *param, const float *grad, float *momentum_buf, long n, float lr, float weight_decay,
@@ -259,16 +407,36 @@ extern "C" int adyolo_sgd_step_dev(float *param, const float *grad, float *momen
                    "sgd_step_dev: bad arguments");
     ADYOLO_REQUIRE(aligned16(param) && aligned16(grad) && aligned16(momentum_buf), ADYOLO_EINVAL,
                    "sgd_step_dev: buffers not 16-byte aligned");
-    hipStream_t st = as_stream(stream);
-    int rc;
-    if (partials && (rc = launch_sumsq(grad, n, grad_scale, partials, st))) return rc;
-    if ((rc = launch_prep(step_dev, st_dev, PREP_SGD, lr, 0.f, 0.f, partials, n, max_norm, st))) return rc;
-    const float keep = (float)(1.0 - (double)dampening);
-    if (momentum != 0.f)
-        hipLaunchKernelGGL(sgd_update_kernel<true>, dim3(update_grid(n)), dim3(OX_THREADS), 0, st, param, grad, momentum_buf, n,
-                           lr, weight_decay, momentum, keep, nesterov, grad_scale, (const float *)st_dev);
-    else
-        hipLaunchKernelGGL(sgd_update_kernel<false>, dim3(update_grid(n)), dim3(OX_THREADS), 0, st, param, grad,
-                           (float *)nullptr, n, lr, weight_decay, 0.f, keep, nesterov, grad_scale, (const float *)st_dev);
-    return check_launch("sgd_step_dev");
+    return sgd_step(param, grad, momentum_buf, n, lr, weight_decay, momentum, dampening, nesterov, step_dev, st_dev, partials,
+                    max_norm, grad_scale, nullptr, nullptr, nullptr, as_stream(stream), "sgd_step_dev");
+}
+
+extern "C" int adyolo_sched_table_doubles(void) { return SCHED_TABLE_DOUBLES; }
+extern "C" int adyolo_sched_out_floats(void) { return SCHED_OUT_FLOATS; }
+
+extern "C" int adyolo_adam_step_sched_dev(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, long n,
+                                          float beta1, float beta2, float eps, float weight_decay, int decoupled,
+                                          uint64_t *step_dev, float *st_dev, double *partials, float max_norm,
+                                          float grad_scale, const double *sched_dev, float *sched_out, float *ema,
+                                          void *stream) {
+    ADYOLO_REQUIRE(param && grad && exp_avg && exp_avg_sq && n > 0 && step_dev && st_dev && sched_dev && sched_out,
+                   ADYOLO_EINVAL, "adam_step_sched_dev: bad arguments");
+    ADYOLO_REQUIRE(aligned16(param) && aligned16(grad) && aligned16(exp_avg) && aligned16(exp_avg_sq) && aligned16(ema) &&
+                       (reinterpret_cast<uintptr_t>(sched_dev) & 7) == 0,
+                   ADYOLO_EINVAL, "adam_step_sched_dev: buffers not 16-byte aligned (or the table not 8-byte aligned)");
+    return adam_step(param, grad, exp_avg, exp_avg_sq, n, 0.f, beta1, beta2, eps, weight_decay, decoupled, step_dev, st_dev,
+                     partials, max_norm, grad_scale, sched_dev, sched_out, ema, as_stream(stream), "adam_step_sched_dev");
+}
+
+extern "C" int adyolo_sgd_step_sched_dev(float *param, const float *grad, float *momentum_buf, long n, float weight_decay,
+                                         float momentum, float dampening, int nesterov, uint64_t *step_dev, float *st_dev,
+                                         double *partials, float max_norm, float grad_scale, const double *sched_dev,
+                                         float *sched_out, float *ema, void *stream) {
+    ADYOLO_REQUIRE(param && grad && n > 0 && step_dev && st_dev && (momentum == 0.f || momentum_buf) && sched_dev && sched_out,
+                   ADYOLO_EINVAL, "sgd_step_sched_dev: bad arguments");
+    ADYOLO_REQUIRE(aligned16(param) && aligned16(grad) && aligned16(momentum_buf) && aligned16(ema) &&
+                       (reinterpret_cast<uintptr_t>(sched_dev) & 7) == 0,
+                   ADYOLO_EINVAL, "sgd_step_sched_dev: buffers not 16-byte aligned (or the table not 8-byte aligned)");
+    return sgd_step(param, grad, momentum_buf, n, 0.f, weight_decay, momentum, dampening, nesterov, step_dev, st_dev, partials,
+                    max_norm, grad_scale, sched_dev, sched_out, ema, as_stream(stream), "sgd_step_sched_dev");
 }

@@ -11,7 +11,10 @@ the private memory pool and the capture stream).
 What had to move to the device for that: nothing in a recorded launch may change from step to step, so the Adam step
 counter (``adyolo_adam_step_dev``) and the running offset of the dropout stream (``adyolo_dropout_apply_dev`` +
 ``adyolo_counter_add``) live in device memory and are advanced by the graph itself; the AD-YOLO target list (M rows, M
-varies from batch to batch) is padded to a fixed capacity with rows the assignment kernel skips (batch index -1).
+varies from batch to batch) is padded to a fixed capacity with rows the assignment kernel skips (batch index -1).  A
+learning-rate schedule (``train_config['lr_schedule']``) is recorded like the plain step: the rate is derived by the
+optimizer's prep kernel from that counter and a table the host may rewrite between replays (``set_lr``), and the EMA of the
+parameters rides in the update launch -- nothing in either varies per step.
 
 Results are bit-identical to the eager path (tests/test_gpu_graph.py compares losses and parameters with torch.equal).
 """

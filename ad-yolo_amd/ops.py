@@ -1169,6 +1169,55 @@ def sgd_step_dev(param, grad, momentum_buf, step_dev, st_dev, lr=1e-3, weight_de
        _p(partials), _max_norm("sgd_step_dev", partials, max_norm), grad_scale, _stream())
 
 
+# The scheduled forms (include/adyolo_hip.h, "The scheduled forms"): the rate is derived on the device from the step counter
+# and ``sched_dev``; the layout of that table, by index:
+SCHED_TABLE_DOUBLES = 24          # float64 elements of sched_dev (adyolo_sched_table_doubles())
+SCHED_OUT_FLOATS = 4              # float32 elements of sched_out: {lr, AdamW decay, EMA weight, EMA first flag}
+SCHED_KINDS = {"constant": 0, "step": 1, "multistep": 2, "exponential": 3, "cosine": 4}
+(SCHED_KIND, SCHED_BASE, SCHED_EVERY, SCHED_WARMUP, SCHED_START, SCHED_GAMMA, SCHED_STEP_SIZE, SCHED_T_MAX, SCHED_ETA_MIN,
+ SCHED_N_MILESTONES, SCHED_MILESTONE0) = range(11)
+SCHED_MAX_MILESTONES = 8
+SCHED_OFFSET, SCHED_EMA_DECAY, SCHED_EMA_WARMUP, SCHED_EMA_OFFSET = 18, 19, 20, 21
+
+
+def _chk_sched(what, param, sched_dev, sched_out, ema):
+    if (not sched_dev.is_cuda or sched_dev.dtype != torch.float64 or not sched_dev.is_contiguous()
+            or sched_dev.numel() < SCHED_TABLE_DOUBLES):
+        raise _lib.AdyoloHipError("%s needs a schedule table of %d contiguous float64 on the device" % (what, SCHED_TABLE_DOUBLES))
+    _chk(sched_out, ema)
+    if sched_out.numel() < SCHED_OUT_FLOATS:
+        raise _lib.AdyoloHipError("%s needs %d floats of sched_out on the device" % (what, SCHED_OUT_FLOATS))
+    if ema is not None and ema.numel() != param.numel():
+        raise _lib.AdyoloHipError("%s: the EMA buffer has %d elements, the parameters %d" % (what, ema.numel(), param.numel()))
+
+
+def adam_step_sched_dev(param, grad, exp_avg, exp_avg_sq, step_dev, st_dev, sched_dev, sched_out, ema=None,
+                        betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_scale=1.0, partials=None, max_norm=None,
+                        decoupled=False):
+    """``adam_step_dev`` whose learning rate is computed by the step's prep kernel from step_dev and the table sched_dev
+    (``SCHED_TABLE_DOUBLES`` float64) and written to sched_out[0] (``SCHED_OUT_FLOATS`` floats); a constant schedule gives
+    ``adam_step_dev``'s bits.  ema: a buffer like param that receives the moving average of the parameters in the same launch."""
+    _chk(param, grad, exp_avg, exp_avg_sq, st_dev)
+    _chk_optim_dev("adam_step_sched_dev", param.numel(), step_dev, st_dev, partials)
+    _chk_sched("adam_step_sched_dev", param, sched_dev, sched_out, ema)
+    _c("adyolo_adam_step_sched_dev", _p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), betas[0], betas[1], eps,
+       weight_decay, int(bool(decoupled)), _p(step_dev), _p(st_dev), _p(partials),
+       _max_norm("adam_step_sched_dev", partials, max_norm), grad_scale, _p(sched_dev), _p(sched_out), _p(ema), _stream())
+
+
+def sgd_step_sched_dev(param, grad, momentum_buf, step_dev, st_dev, sched_dev, sched_out, ema=None, weight_decay=0.0,
+                       momentum=0.0, dampening=0.0, nesterov=False, grad_scale=1.0, partials=None, max_norm=None):
+    """``sgd_step_dev`` with the learning rate from the device-side schedule (see ``adam_step_sched_dev``)."""
+    _chk(param, grad, momentum_buf, st_dev)
+    _chk_optim_dev("sgd_step_sched_dev", param.numel(), step_dev, st_dev, partials)
+    _chk_sched("sgd_step_sched_dev", param, sched_dev, sched_out, ema)
+    if momentum != 0.0 and momentum_buf is None:
+        raise _lib.AdyoloHipError("sgd_step_sched_dev with momentum needs a momentum buffer")
+    _c("adyolo_sgd_step_sched_dev", _p(param), _p(grad), _p(momentum_buf if momentum != 0.0 else None), param.numel(),
+       weight_decay, momentum, dampening, int(bool(nesterov)), _p(step_dev), _p(st_dev), _p(partials),
+       _max_norm("sgd_step_sched_dev", partials, max_norm), grad_scale, _p(sched_dev), _p(sched_out), _p(ema), _stream())
+
+
 def nchw_to_nhwc8(x):
     _chk(x)
     b, c, h, w = x.shape

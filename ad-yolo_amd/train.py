@@ -5,11 +5,13 @@ backward -> [bucketed RCCL all-reduce] -> [gradient-norm clip] -> fused Adam / A
 FusedAdam keeps torch.optim.Adam's hyper-parameters and produces a ``state_dict`` in the stock Adam
 format (train.py:149,236 save/restore it) while running one HIP launch over the flat parameter buffer.
 """
+import contextlib
 import os
 
 import torch
 
 from . import functional as Fn
+from . import lr_schedule as _sched
 from . import ops
 from .dist import BucketedAllReduce, FlatParameters
 
@@ -28,7 +30,23 @@ class _FusedOptimizer:
     on every rank that holds the same reduced gradients), the step's one-workgroup prep kernel turns the partials into
     ``clip_coef = min(1, max_norm / (norm + 1e-6))`` and the update multiplies it into ``grad_scale``.  ``grad_norm`` is then a
     device tensor of one float, the pre-clip norm of the last step (what ``clip_grad_norm_`` returns); reading it is an
-    ordinary device read, nothing in here syncs.  ``max_norm`` is a constant of a recorded step, like ``lr``."""
+    ordinary device read, nothing in here syncs.  ``max_norm`` is a constant of a recorded step, and so is ``lr`` unless the
+    optimizer was built with a schedule.
+
+    lr_schedule (None = off: the plain entry points, nothing more allocated): a ``lr_schedule`` configuration
+    (``train_config['lr_schedule']``: ``{name, every, warmup_steps, warmup_start_factor, ...}``).  The rate is then computed
+    ON THE DEVICE by the step's prep kernel from the step counter and a small table (``sched_dev``, float64, written by the
+    host only), so it changes from step to step also under a replayed graph.  ``current_lr`` is a device view of one float, the
+    rate the last step used (read it like ``grad_norm``); ``lr_at(t)`` is the host mirror of the same closed form, for logging
+    without a device read; ``set_lr(x)`` writes a new base rate into the table -- it holds from the next step on, eager or
+    replayed, with no new recording (the hook for a reduce-on-plateau policy in the caller's epoch loop).  ``lr`` is the BASE
+    rate.  The schedule's clock is ``sched_step`` = ``step_count`` + an offset kept in the table, so it survives a resume
+    that restarts ``step_count`` (FusedSGD).
+
+    ema_decay (None = off): an exponential moving average of the parameters, ``ema`` (laid out like ``flat.flat``), updated by
+    the update launch itself: a copy of the parameters after its first step, then ``ema += (p - ema) * (1 - decay_eff)`` with
+    ``decay_eff = decay`` or, with ema_warmup, ``min(decay, (1 + k) / (10 + k))`` after k updates.  Without ``lr_schedule``
+    the rate is a constant schedule."""
 
     kind = None                     # 'adam' | 'adamw' | 'sgd': the torch.optim layout ``checkpoint`` reads and writes
 
@@ -64,6 +82,81 @@ class _FusedOptimizer:
         self._dev_step_value = self._step_count
         ops.params_changed()
 
+    # ------------------------------------------------------------------------------------------ schedule / EMA
+    sched_config = sched_dev = sched_out = current_lr = ema = ema_decay = None
+    ema_warmup = False
+    _sched_offset = _ema_offset = 0
+
+    def _init_sched(self, lr_schedule, ema_decay, ema_warmup):
+        if lr_schedule is None and ema_decay is None:
+            if ema_warmup:
+                raise ValueError("ema_warmup without ema_decay")
+            return
+        self.sched_config = _sched.normalise({"name": "constant"} if lr_schedule is None else lr_schedule)
+        _sched.check_base(self.sched_config, self.lr)
+        self.ema_decay = None if ema_decay is None else _sched.check_ema_decay(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
+        if self.ema_warmup and self.ema_decay is None:
+            raise ValueError("ema_warmup without ema_decay")
+        dev = self.flat.flat.device
+        self.sched_dev = torch.zeros(ops.SCHED_TABLE_DOUBLES, dtype=torch.float64, device=dev)
+        self.sched_out = torch.zeros(ops.SCHED_OUT_FLOATS, dtype=torch.float32, device=dev)
+        self.current_lr = self.sched_out[0:1]
+        if self.ema_decay is not None:
+            self.ema = torch.zeros_like(self.flat.flat)
+        self._write_table()
+
+    def _write_table(self):
+        """(re)write ``sched_dev`` from the host's values: construction, ``set_lr``, ``load_state_dict``"""
+        self._table = _sched.table(self.sched_config, self.lr, self._sched_offset, self.ema_decay, self.ema_warmup,
+                                   self._ema_offset)
+        self.sched_dev.copy_(torch.tensor(self._table, dtype=torch.float64))
+
+    @property
+    def sched_step(self):
+        """the schedule's clock: the t of the LAST step taken (0 before the first)"""
+        return self._step_count + self._sched_offset
+
+    @property
+    def ema_updates(self):
+        return self._step_count + self._ema_offset if self.ema is not None else 0
+
+    def lr_at(self, t):
+        """the rate of schedule step t (1-based) as the device computes it: the closed form in double, rounded to float32"""
+        if self.sched_dev is None:
+            return _sched.lr_at(_sched.table(_sched.normalise({"name": "constant"}), self.lr), t)
+        return _sched.lr_at(self._table, t)
+
+    def set_lr(self, lr):
+        if self.sched_dev is None:
+            raise ValueError("this optimizer was built without a schedule, its lr is a constant of the (recorded) step: "
+                             "build it with lr_schedule: {name: constant} to change the rate between steps")
+        self.lr = _sched.check_base(self.sched_config, lr)
+        self._write_table()
+
+    def sched_state_dict(self):
+        """configuration, current base rate and clocks of the schedule / EMA (``checkpoint`` writes it beside the optimizer's)"""
+        return {"config": dict(self.sched_config), "base_lr": self.lr, "step": self.sched_step,
+                "ema_decay": self.ema_decay, "ema_warmup": self.ema_warmup, "ema_updates": self.ema_updates}
+
+    def load_sched_state_dict(self, sd):
+        """After ``load_state_dict`` (it sets ``step_count``, which the offsets refer to).  The schedule continues at the saved
+        step with the saved configuration and base rate; the EMA's decay stays this run's."""
+        if self.sched_dev is None:
+            raise ValueError("this optimizer was built without a schedule")
+        self.sched_config = _sched.normalise(sd["config"])
+        self.lr = _sched.check_base(self.sched_config, sd["base_lr"])
+        self._sched_offset = int(sd["step"]) - self._step_count
+        if self.ema is not None:
+            self._ema_offset = int(sd.get("ema_updates", 0)) - self._step_count
+        self._write_table()
+
+    def restart_ema(self):
+        """the EMA becomes a copy of the parameters as they are now, counted as its first update"""
+        self.ema.copy_(self.flat.flat)
+        self._ema_offset = 1 - self._step_count
+        self._write_table()
+
     def zero_grad(self, set_to_none=False):
         self.flat.zero_grad()
 
@@ -82,6 +175,8 @@ class _FusedOptimizer:
         return checkpoint.optimizer_state_dict(self, None)
 
     def load_state_dict(self, sd):
+        """(with a schedule: the clocks keep their values relative to the loaded ``step_count``; ``load_sched_state_dict``
+        sets them)"""
         from . import checkpoint
         checkpoint.load_optimizer_state_dict(self, None, sd)
 
@@ -93,13 +188,20 @@ class FusedAdam(_FusedOptimizer):
 
     kind = "adam"
 
-    def __init__(self, flat: FlatParameters, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_norm=None):
+    def __init__(self, flat: FlatParameters, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_norm=None,
+                 lr_schedule=None, ema_decay=None, ema_warmup=False):
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         self.exp_avg = torch.zeros_like(flat.flat)
         self.exp_avg_sq = torch.zeros_like(flat.flat)
         self._init_common(flat, max_norm)
+        self._init_sched(lr_schedule, ema_decay, ema_warmup)
 
     def _launch(self, grad_scale):
+        if self.sched_dev is not None:
+            return ops.adam_step_sched_dev(self.flat.flat, self.flat.flat_grad, self.exp_avg, self.exp_avg_sq, self.step_dev,
+                                           self.st_dev, self.sched_dev, self.sched_out, self.ema, self.betas, self.eps,
+                                           self.weight_decay, grad_scale, self.clip_partials, self.max_norm,
+                                           decoupled=self.kind == "adamw")
         ops.adam_step_dev(self.flat.flat, self.flat.flat_grad, self.exp_avg, self.exp_avg_sq, self.step_dev, self.st_dev,
                           self.lr, self.betas, self.eps, self.weight_decay, grad_scale, self.clip_partials, self.max_norm,
                           decoupled=self.kind == "adamw")
@@ -111,8 +213,9 @@ class FusedAdamW(FusedAdam):
 
     kind = "adamw"
 
-    def __init__(self, flat: FlatParameters, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_norm=None):
-        super().__init__(flat, lr, betas, eps, weight_decay, max_norm)
+    def __init__(self, flat: FlatParameters, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_norm=None,
+                 lr_schedule=None, ema_decay=None, ema_warmup=False):
+        super().__init__(flat, lr, betas, eps, weight_decay, max_norm, lr_schedule, ema_decay, ema_warmup)
 
 
 class FusedSGD(_FusedOptimizer):
@@ -126,13 +229,14 @@ class FusedSGD(_FusedOptimizer):
     kind = "sgd"
 
     def __init__(self, flat: FlatParameters, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False,
-                 max_norm=None):
+                 max_norm=None, lr_schedule=None, ema_decay=None, ema_warmup=False):
         if nesterov and (momentum <= 0 or dampening != 0):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
         self._init_common(flat, max_norm)
         self.lr, self.momentum, self.dampening, self.weight_decay = lr, momentum, dampening, weight_decay
         self.nesterov = bool(nesterov)
         self.momentum_buffer = torch.zeros_like(flat.flat) if momentum != 0 else None
+        self._init_sched(lr_schedule, ema_decay, ema_warmup)
 
     @property
     def first_step(self):
@@ -140,6 +244,10 @@ class FusedSGD(_FusedOptimizer):
         return self._step_count == 0
 
     def _launch(self, grad_scale):
+        if self.sched_dev is not None:
+            return ops.sgd_step_sched_dev(self.flat.flat, self.flat.flat_grad, self.momentum_buffer, self.step_dev, self.st_dev,
+                                          self.sched_dev, self.sched_out, self.ema, self.weight_decay, self.momentum,
+                                          self.dampening, self.nesterov, grad_scale, self.clip_partials, self.max_norm)
         ops.sgd_step_dev(self.flat.flat, self.flat.flat_grad, self.momentum_buffer, self.step_dev, self.st_dev, self.lr,
                          self.weight_decay, self.momentum, self.dampening, self.nesterov, grad_scale, self.clip_partials,
                          self.max_norm)
@@ -148,18 +256,22 @@ class FusedSGD(_FusedOptimizer):
 def get_optimizers(params: dict, flat: FlatParameters):
     """reference train.py:29-37: ``optim`` 'Adam' | 'AdamW' | 'SGD' with ``lr`` / ``weight_decay``.  Optional keys of
     ``train_config``: ``momentum``, ``dampening``, ``nesterov`` (SGD; the reference passes none of them) and ``clip_grad_norm``
-    (the max_norm of the reference's ``clip_grad_norm_`` line, train.py:54; absent or None = off)."""
+    (the max_norm of the reference's ``clip_grad_norm_`` line, train.py:54; absent or None = off); ``lr_schedule`` (a dict
+    ``{name: constant | step | multistep | exponential | cosine, every, warmup_steps, warmup_start_factor, ...}``, see
+    ``lr_schedule.py``; absent = the rate is a constant of the step), ``ema_decay`` (absent = no averaged weights) and
+    ``ema_warmup`` (default false)."""
     tc = params["train_config"]
     name = tc.get("optim", "Adam")
     clip = tc.get("clip_grad_norm")
+    extra = {"lr_schedule": tc.get("lr_schedule"), "ema_decay": tc.get("ema_decay"), "ema_warmup": tc.get("ema_warmup", False)}
     if name == "Adam":
-        return FusedAdam(flat, lr=tc.get("lr", 1e-3), weight_decay=tc.get("weight_decay", 0.0), max_norm=clip)
+        return FusedAdam(flat, lr=tc.get("lr", 1e-3), weight_decay=tc.get("weight_decay", 0.0), max_norm=clip, **extra)
     if name == "AdamW":
-        return FusedAdamW(flat, lr=tc.get("lr", 1e-3), weight_decay=tc.get("weight_decay", 1e-2), max_norm=clip)
+        return FusedAdamW(flat, lr=tc.get("lr", 1e-3), weight_decay=tc.get("weight_decay", 1e-2), max_norm=clip, **extra)
     if name == "SGD":
         return FusedSGD(flat, lr=tc.get("lr", 1e-3), weight_decay=tc.get("weight_decay", 0.0),
                         momentum=tc.get("momentum", 0.0), dampening=tc.get("dampening", 0.0),
-                        nesterov=tc.get("nesterov", False), max_norm=clip)
+                        nesterov=tc.get("nesterov", False), max_norm=clip, **extra)
     raise NotImplementedError(name)
 
 
@@ -203,6 +315,31 @@ class TrainStep:
         if self.graphs is not None:
             return self.graphs.step(audio, target, spec_ranges)
         return self.step_eager(audio, target, spec_ranges)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the context the model's parameters are the optimizer's EMA (``train_config['ema_decay']``): the flat
+        parameter buffer is stashed, overwritten with the averaged weights (device copies) and put back on exit, with
+        ``ops.params_changed()`` both times so that cached weight packs and transformed filters are rebuilt.  Parameters keep
+        their addresses, so evaluation code (``test_epoch_audio``, ``graph.ForwardGraphs``) runs unchanged.  BatchNorm running
+        statistics are buffers, not parameters: inside the context they are the LIVE model's, they are not averaged.  Before
+        the first optimizer step the EMA is the live weights.  Take no train step inside the context."""
+        opt = self.optimizer
+        if getattr(opt, "ema", None) is None:
+            raise ValueError("no averaged weights: the optimizer was built without train_config['ema_decay']")
+        if opt.ema_updates <= 0:
+            yield
+            return
+        if getattr(self, "_ema_stash", None) is None:
+            self._ema_stash = torch.empty_like(self.flat.flat)
+        self._ema_stash.copy_(self.flat.flat)
+        self.flat.flat.copy_(opt.ema)
+        ops.params_changed()
+        try:
+            yield
+        finally:
+            self.flat.flat.copy_(self._ema_stash)
+            ops.params_changed()
 
     def step_eager(self, audio, target, spec_ranges=None):
         self.model.train()

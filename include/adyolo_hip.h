@@ -691,6 +691,33 @@ int  adyolo_adam_step_dev(float *param, const float *grad, float *exp_avg, float
 int  adyolo_sgd_step_dev(float *param, const float *grad, float *momentum_buf, long n, float lr, float weight_decay,
                          float momentum, float dampening, int nesterov, uint64_t *step_dev, float *st_dev, double *partials,
                          float max_norm, float grad_scale, void *stream);
+/* The scheduled forms: the learning rate is computed ON THE DEVICE by the step's prep kernel, so that it can change from step
+ * to step under a replayed hipGraph; lr is therefore no argument.  With t = *step_dev after its increment + table[18] and
+ * e = floor((t - 1) / every):  lr(t) = base * warm(t) * main(e), evaluated in double and rounded to float ONCE; from there on
+ * that float is used exactly as the plain entry points use their `lr` argument (a constant schedule gives their bits).
+ *   warm(t) = s + (1 - s) * min(t - 1, W) / W   (W = 0: 1)
+ *   main(e) = 1 | gamma^floor(e / step_size) | gamma^#{milestones <= e} | gamma^e |
+ *             (eta_min + (base - eta_min) * (1 + cos(pi * min(e, T_max) / T_max)) / 2) / base
+ *   sched_dev  adyolo_sched_table_doubles() (= 24) doubles, written by the host only, read by the prep kernel:
+ *              [0] kind 0 constant, 1 step, 2 multistep, 3 exponential, 4 cosine; [1] base lr; [2] every; [3] W; [4] s;
+ *              [5] gamma; [6] step_size; [7] T_max; [8] eta_min; [9] number of milestones (<= 8); [10..17] milestones;
+ *              [18] step offset; [19] EMA decay; [20] EMA warm-up flag; [21] EMA offset (k = *step_dev after its increment
+ *              - 1 + [21] = EMA updates so far); [22..23] reserved (0)
+ *   sched_out  adyolo_sched_out_floats() (= 4) floats written every step: {lr of this step, AdamW's 1 - lr * weight_decay,
+ *              EMA weight w of this step, EMA first-update flag}
+ *   ema        NULL, or a buffer laid out like param (16-byte aligned): after param is formed, ema = param on the first update
+ *              (k == 0; the old contents are not read), else ema = fma(param - ema, w, ema) with w = 1 - decay_eff,
+ *              decay_eff = decay or, with the warm-up flag, min(decay, (1 + k) / (10 + k)). */
+int  adyolo_sched_table_doubles(void);
+int  adyolo_sched_out_floats(void);
+int  adyolo_adam_step_sched_dev(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, long n, float beta1,
+                                float beta2, float eps, float weight_decay, int decoupled, uint64_t *step_dev, float *st_dev,
+                                double *partials, float max_norm, float grad_scale, const double *sched_dev, float *sched_out,
+                                float *ema, void *stream);
+int  adyolo_sgd_step_sched_dev(float *param, const float *grad, float *momentum_buf, long n, float weight_decay,
+                               float momentum, float dampening, int nesterov, uint64_t *step_dev, float *st_dev,
+                               double *partials, float max_norm, float grad_scale, const double *sched_dev, float *sched_out,
+                               float *ema, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * K9a multi-head self-attention core, flash style on the exact-fp32 matrix cores (csrc/attention.hip).

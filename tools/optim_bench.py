@@ -2,13 +2,14 @@
 up, repeated).
 
   step      one hipGraph-replayed TrainStep at 16 x 20 s (the reference's batch_size / chunk) and at 64 x 60 s (the bench shape)
-            with 'Adam' (ops.adam_step_dev, the baseline), 'AdamW', 'SGD' (plain, as the reference calls it) and 'Adam' with
-            clip_grad_norm 3
+            with 'Adam' (ops.adam_step_dev, the baseline), 'AdamW', 'SGD' (plain, as the reference calls it), 'Adam' with
+            clip_grad_norm 3, 'Adam' under a device-side lr_schedule (ops.adam_step_sched_dev) and the same with ema_decay
   kernels   the optimizer launches alone on buffers of the real model's flat size (6.68 M floats): adam_step_dev (baseline),
             adamw_step_dev, sgd_step_dev without / with momentum, adam_step_dev with clipping, grad_norm_dev (sum of squares +
-            prep)
+            prep); the scheduled forms adam / adamw / sgd_step_sched_dev (cosine with warm-up: the prep kernel's most expensive
+            table) and the scheduled forms with the EMA in the update launch (two more streams)
 
-At 16 x 20 s the four trainers live side by side and alternate inside each repeat; at 64 x 60 s they are built one after the
+At 16 x 20 s the trainers live side by side and alternate inside each repeat; at 64 x 60 s they are built one after the
 other (activations of one recorded step at a time).  The median of the repeats is reported (ms per call).
 
   python tools/optim_bench.py [--reps 7] [--iters 10] [--only step16] [--only step64] [--only kernels] [--json out.json]
@@ -29,7 +30,10 @@ import torch  # noqa: E402
 VARIANTS = {"adam": {"optim": "Adam"},
             "adamw": {"optim": "AdamW", "weight_decay": 0.01},
             "sgd": {"optim": "SGD"},
-            "adam_clip3": {"optim": "Adam", "clip_grad_norm": 3.0}}
+            "adam_clip3": {"optim": "Adam", "clip_grad_norm": 3.0},
+            "adam_sched": {"optim": "Adam", "lr_schedule": {"name": "cosine", "T_max": 1000, "warmup_steps": 100}},
+            "adam_sched_ema": {"optim": "Adam", "lr_schedule": {"name": "cosine", "T_max": 1000, "warmup_steps": 100},
+                               "ema_decay": 0.999}}
 
 
 def timed(fns, reps, iters):
@@ -101,6 +105,11 @@ def bench_kernels(reps, iters):
     step_dev = torch.zeros(1, dtype=torch.int64, device="cuda:0")
     st = torch.zeros(ops.OPTIM_SCRATCH_FLOATS, device="cuda:0")
     parts = torch.zeros(ops.GRAD_SUMSQ_MAX_PARTS, dtype=torch.float64, device="cuda:0")
+    from adyolo_amd import lr_schedule
+    cosine = lr_schedule.normalise({"name": "cosine", "T_max": 1000, "warmup_steps": 100})
+    sched = torch.tensor(lr_schedule.table(cosine, 1e-3), dtype=torch.float64).to("cuda:0")
+    sched_ema = torch.tensor(lr_schedule.table(cosine, 1e-3, ema_decay=0.999), dtype=torch.float64).to("cuda:0")
+    out, ema = torch.zeros(ops.SCHED_OUT_FLOATS, device="cuda:0"), torch.zeros_like(p)
     fns = {
         "adam_step_dev": lambda: ops.adam_step_dev(p, grad, m, v, step_dev, st),
         "adamw_step_dev": lambda: ops.adamw_step_dev(p, grad, m, v, step_dev, st),
@@ -108,6 +117,13 @@ def bench_kernels(reps, iters):
         "sgd_step_dev_momentum": lambda: ops.sgd_step_dev(p, grad, buf, step_dev, st, momentum=0.9),
         "adam_step_dev_clip": lambda: ops.adam_step_dev(p, grad, m, v, step_dev, st, partials=parts, max_norm=3.0),
         "grad_norm_dev": lambda: ops.grad_norm_dev(grad, parts, st, 3.0),
+        "adam_step_sched_dev": lambda: ops.adam_step_sched_dev(p, grad, m, v, step_dev, st, sched, out),
+        "adamw_step_sched_dev": lambda: ops.adam_step_sched_dev(p, grad, m, v, step_dev, st, sched, out, weight_decay=1e-2,
+                                                                decoupled=True),
+        "sgd_step_sched_dev": lambda: ops.sgd_step_sched_dev(p, grad, None, step_dev, st, sched, out),
+        "adam_step_sched_dev_ema": lambda: ops.adam_step_sched_dev(p, grad, m, v, step_dev, st, sched_ema, out, ema),
+        "sgd_step_sched_dev_momentum_ema": lambda: ops.sgd_step_sched_dev(p, grad, buf, step_dev, st, sched_ema, out, ema,
+                                                                          momentum=0.9),
     }
     for f in fns.values():
         for _ in range(3):

@@ -87,6 +87,9 @@ SIGNATURES = {
     "adyolo_loss_workspace_words": (L, [I, I, I, I]),
     "adyolo_loss_fwd_bwd": (I, [P] * 6 + [I] * 7 + [P, P, F, F, F, F, P]),
     "adyolo_loss_phase": (I, [P] * 6 + [I] * 7 + [P, P, F, F, F, F, I, L, P]),
+    "adyolo_loss_per_clip_workspace_words": (L, [I, I, I, I]),
+    "adyolo_loss_per_clip": (I, [P] * 7 + [I] * 6 + [L, P, P, F, F, F, P]),
+    "adyolo_loss_accumulate": (I, [P, P, I, P, P]),
     "adyolo_yolo_decode": (I, [P, P, L, I, I, I, I, F, F, F, P]),
     "adyolo_yolo_select_workspace_words": (L, [L, I, I]),
     "adyolo_yolo_select": (I, [P] * 4 + [L, I, I, F, F, F, F, I, P]),

@@ -21,6 +21,12 @@ rotates and encodes the labels on the host and stages every batch over PCIe.  He
 
 Parity: the same audio bit for bit and the same rows in the same order (or the same dense targets bit for bit) as the host
 path iterated in the main process (``num_workers=0``); with DataLoader workers the host path's draws happen in per-worker streams.
+
+Evaluation splits ('val' / 'valid' / 'test': whole recordings, static between epochs) have their own pair: ``load_eval_split``
+reads the split ``FoaDataset(params, set_type, is_valid=True)`` reads into the same ``HostCorpus`` layout, one recording per
+clip, and ``EvalDeviceCorpus`` uploads it once (audio, events, one item per clip) and makes each batch of
+``test.test_epoch_corpus`` from a range of clips with no host data: the gather without rotation, then the AD-YOLO rows with the
+clips' row starts or the dense class-wise target (all five losses in one class).
 """
 import copy
 import os
@@ -253,6 +259,17 @@ def xyz_table(az, el):
     return uniq.astype(np.float32)[inv.reshape(-1)]
 
 
+def xyz_unrotated(az, el):
+    """float32 (E, 3): slot 0 of ``xyz_table`` alone (no rotation), for splits that are never rotated."""
+    from .datasets import _polar_to_xyz
+    pairs = np.stack([np.asarray(az, dtype=np.float64).reshape(-1), np.asarray(el, dtype=np.float64).reshape(-1)], 1)
+    if pairs.shape[0] == 0:
+        return np.zeros((0, 3), dtype=np.float32)
+    keys, inv = np.unique(pairs.view(np.int64), axis=0, return_inverse=True)      # bit patterns: -0.0 and 0.0 differ
+    uniq = np.asarray([_polar_to_xyz(a, e) for a, e in keys.view(np.float64).tolist()], dtype=np.float64)
+    return uniq.astype(np.float32)[inv.reshape(-1)]
+
+
 class _CorpusBase:
     """What both device corpora share: the split in HBM, ``FoaDataset``'s sampling surface, the host draws of a batch, the upload
     of its item table and the audio gather.  Subclasses add the label encoding."""
@@ -278,7 +295,11 @@ class _CorpusBase:
         self.batch_size = int(params["train_config"]["batch_size"])
         self.n_samples, self.n_label_frames = hc.window, hc.window // hc.hop_label
         self.max_events = hc.max_events
-        # the corpus in HBM
+        self._to_hbm(hc)
+
+    def _to_hbm(self, hc):
+        """The split in HBM: the int16 streams, the event table {frame, class, azimuth, elevation} in float64, the status word."""
+        from .augmentations import COMBINATIONS
         self.pcm = torch.from_numpy(hc.audio).to(self.device)
         ev = hc.events[:, [0, 1, 3, 4]] if hc.events.shape[0] else np.zeros((1, 4))
         self.events = torch.from_numpy(np.ascontiguousarray(ev, dtype=np.float64)).to(self.device)
@@ -469,3 +490,220 @@ class ClasswiseDeviceCorpus(_CorpusBase):
         ops.corpus_classwise_labels(self.events, dev_items, self.xyz, self.max_events, self.n_label_frames, self.nb_classes,
                                     self.loss_nm, target, self.status)
         return audio, target, dev_spec
+
+
+# ------------------------------------------------------------------------------------------------------- evaluation splits
+def _eval_dirs(params, set_type):
+    """The directories ``FoaDataset(params, set_type, is_valid=True)`` reads for a labelled evaluation split."""
+    dc = params["data_config"]
+    if set_type == "train":
+        raise ValueError("load_eval_split: set_type='train' is the chunked training split (load_chunked_split)")
+    if set_type == "infer":
+        raise ValueError("load_eval_split: set_type='infer' has no labels; it is evaluated through test_epoch_audio")
+    adir = {"foa": "foa_dev", "mic": "mic_dev"}[str(dc.get("audio_format", "foa")).lower()]     # FoaDataset's rule
+    sub = "dev-{}".format(set_type)
+    return os.path.join(dc["data_pth"], adir, sub), os.path.join(dc["data_pth"], "metadata_dev", sub)
+
+
+def load_eval_split(params, set_type, rank=None, world=None, verify="sample"):
+    """A labelled evaluation split ('val', 'valid', 'test': what ``FoaDataset(params, set_type, is_valid=True)`` accepts) read
+    once -> ``HostCorpus``: every recording whole in one int16 stream (each on a 16-frame boundary) and one event table.
+
+    filelist    exactly ``FoaDataset``'s: ``os.listdir`` order on one rank, ``sorted(...)[rank::world]`` under data parallelism;
+                only this rank's recordings are loaded.  rec_names == filelist: recording i is clip i.
+    lengths     int64 (R,): samples per recording; rec_start / ev_start as in ``HostCorpus``; max_events: the largest event
+                count of a recording; window: the longest whole-hop length (multiple of 600 samples).
+    events      every CSV row, rows past ``len // hop_label`` label frames included (the label kernels drop them, as
+                ``FoaDataset.__getitem__`` does), frames ascending, file order within a frame.
+
+    ``ValueError`` naming the file: a file that is not int16 or not 4 channels wide, a missing CSV, a row that is not
+    [frame, class, source, azimuth, elevation], a class outside [0, nb_classes), frames that do not ascend (the host's rows
+    follow the file, the table the frames).  verify: "sample" reads the first, middle and last recording again and compares
+    them with the stream, "all" every recording, "none" nothing."""
+    from scipy.io import wavfile
+    if verify not in ("sample", "all", "none"):
+        raise ValueError("load_eval_split: verify must be 'sample', 'all' or 'none' (got %r)" % (verify,))
+    dc = params["data_config"]
+    wav_pth, csv_pth = _eval_dirs(params, set_type)
+    if not os.path.isdir(wav_pth):
+        raise ValueError("load_eval_split: %s is not a directory (set_type=%r)" % (wav_pth, set_type))
+    nb_classes = int(dc["nb_classes"])
+    hop = int(dc.get("sr", 24000) * dc.get("label_hop_len_s", 0.1))                 # FoaDataset.hop_label
+    rank, world = _rank_world(rank, world)
+    filelist = [i.replace(".wav", "") for i in os.listdir(wav_pth)]                  # FoaDataset.filelist
+    if world > 1:
+        filelist = sorted(filelist)[rank::world]
+
+    def wav_of(name):
+        path = os.path.join(wav_pth, name + ".wav")
+        _, data = wavfile.read(path, mmap=True)
+        if data.dtype != np.int16 or data.ndim != 2 or data.shape[1] != 4:
+            raise ValueError("load_eval_split: %s holds %s %s, expected int16 (n, 4)" % (path, data.dtype, tuple(data.shape)))
+        return path, data
+
+    lengths = np.zeros(len(filelist), dtype=np.int64)
+    for i, name in enumerate(filelist):                       # headers first: the stream is allocated once
+        lengths[i] = wav_of(name)[1].shape[0]
+    rec_start = np.zeros(len(filelist) + 1, dtype=np.int64)
+    pos = 0
+    for i, n in enumerate(lengths.tolist()):
+        rec_start[i] = pos
+        pos += (n + 15) // 16 * 16
+    rec_start[-1] = pos
+    audio = np.zeros((max(pos, 16), 4), dtype=np.int16)
+    ev_parts, ev_start, max_events = [], [0], 0
+    for i, name in enumerate(filelist):
+        s0, n = int(rec_start[i]), int(lengths[i])
+        audio[s0:s0 + n] = wav_of(name)[1]
+        path = os.path.join(csv_pth, name + ".csv")
+        if not os.path.exists(path):
+            raise ValueError("load_eval_split: label file %s is missing" % path)
+        rows = []
+        for frame, events in FoaDataset.load_csv2dict(path).items():
+            for ev in events:
+                if len(ev) != 4:
+                    raise ValueError("load_eval_split: %s has a row that is not [frame, class, source, azimuth, elevation]" % path)
+                if not 0 <= ev[0] < nb_classes:
+                    raise ValueError("load_eval_split: %s has an event of class %d, outside [0, %d) (nb_classes)"
+                                     % (path, ev[0], nb_classes))
+                rows.append((frame, ev[0], ev[1], ev[2], ev[3]))
+        if any(rows[k][0] > rows[k + 1][0] for k in range(len(rows) - 1)):
+            raise ValueError("load_eval_split: the frames of %s do not ascend" % path)
+        ev_parts.append(np.asarray(rows, dtype=np.float64).reshape(-1, _EV_COLS))
+        ev_start.append(ev_start[-1] + len(rows))
+        max_events = max(max_events, len(rows))
+    n_rec = len(filelist)
+    checks = range(n_rec) if verify == "all" else (sorted({0, n_rec // 2, n_rec - 1}) if verify == "sample" and n_rec else ())
+    for i in checks:
+        path, data = wav_of(filelist[i])
+        s0 = int(rec_start[i])
+        if not np.array_equal(np.asarray(data), audio[s0:s0 + int(lengths[i])]):
+            raise ValueError("load_eval_split: %s changed while the split was read" % path)
+
+    hc = HostCorpus()
+    hc.wav_pth, hc.csv_pth, hc.set_type = wav_pth, csv_pth, set_type
+    hc.rank, hc.world = rank, world
+    hc.audio = audio
+    hc.rec_names, hc.rec_start, hc.lengths = list(filelist), rec_start, lengths
+    hc.events = np.concatenate(ev_parts, 0) if ev_parts else np.zeros((0, _EV_COLS))
+    hc.ev_start = np.asarray(ev_start, dtype=np.int64)
+    hc.filelist = hc.total_filelist = list(filelist)
+    hc.hop_label, hc.max_events = hop, max_events
+    hc.window = int((lengths // 600).max() * 600) if n_rec else 0
+    hc.stride, hc.window_frames = 0, hc.window // hop
+    hc.chunks, hc.chunk_events = {}, {}
+    return hc
+
+
+class EvalDeviceCorpus(_CorpusBase):
+    """A ``load_eval_split`` split in HBM: the audio, the events and the item table of every clip are uploaded once; a batch is
+    made on the device from a range of clips with no host data at all.  All five losses: AD-YOLO rows or, for the class-wise
+    heads, the dense targets.  No sampling, no rotation, no SpecAug.
+
+        corpus = EvalDeviceCorpus(load_eval_split(params, "test"), params, "cuda:0")
+        for idx in corpus.batches(8):
+            audio, target, row_start = corpus.launch(idx)   # (B, t, 4) f32; (cap, 7) f32 + (B + 1,) int32, or dense + None
+
+    ``cap`` (AD-YOLO target rows of a batch of B clips): B x (largest event count of a clip) x (largest cell count of an
+    event), rounded up to ``graph.TARGET_QUANTUM``; ``cap_per_clip`` forces a smaller one (the status word then tells)."""
+
+    def __init__(self, host_split, params, device="cuda:0", cap_per_clip=None):
+        hc = host_split
+        if not hasattr(hc, "lengths"):
+            raise ValueError("EvalDeviceCorpus: the split of load_eval_split is needed (got the chunked training split)")
+        self.loss_nm = params["args"]["loss"]
+        if self.loss_nm != "adyolo" and self.loss_nm not in CLASSWISE_LABELS:
+            raise NotImplementedError("EvalDeviceCorpus: loss %s" % self.loss_nm)
+        self.host = hc
+        self.device = torch.device(device)
+        self.rank, self.world = hc.rank, hc.world
+        self.is_valid, self.is_infer, self.set_type = True, False, hc.set_type
+        self.wav_pth, self.csv_pth = hc.wav_pth, hc.csv_pth
+        self.hop_label = hc.hop_label
+        self.rotate = False
+        self.filelist = list(hc.filelist)
+        self.max_events = int(hc.max_events)
+        self.nb_classes = int(params["data_config"]["nb_classes"])
+        self._to_hbm(hc)
+        n = len(self.filelist)
+        self.lengths = [int(v) for v in hc.lengths.tolist()]
+        self.n_hops = [v // 600 * 600 for v in self.lengths]            # whole hops, as test_epoch_audio cuts a clip
+        self.label_frames = [v // self.hop_label for v in self.lengths]
+        items = np.zeros((max(n, 1), ops.CORPUS_ITEM_WORDS), dtype=np.int64)
+        for i in range(n):
+            items[i] = (hc.rec_start[i], 0, hc.ev_start[i], hc.ev_start[i + 1] - hc.ev_start[i], -1, i, 0, 0)
+        self.items = torch.from_numpy(items).to(self.device)
+        if self.loss_nm == "adyolo":
+            self.encoder = YoloLabelEncoder(params)
+            self.cells = max_cells_per_event(self.encoder)
+            self.cap_per_clip = int(cap_per_clip) if cap_per_clip is not None else max(1, self.max_events * self.cells)
+            enc = self.encoder
+            self.bounds = torch.from_numpy(np.concatenate([enc.az_lb, enc.az_ub, enc.el_lb, enc.el_ub])
+                                           .astype(np.float64)).to(self.device)
+            self.grid = (len(enc.az_lb), len(enc.el_lb))
+            self.xyz = None
+        else:
+            full = np.zeros((max(1, hc.events.shape[0]), ops.CORPUS_XYZ_SLOTS, 3), dtype=np.float32)
+            if hc.events.shape[0]:
+                full[:, 0] = xyz_unrotated(hc.events[:, 3], hc.events[:, 4])     # only the unrotated slot is read
+            self.xyz = torch.from_numpy(full).to(self.device)
+
+    def nbytes(self):
+        return super().nbytes() + int(self.items.numel() * 8) + (int(self.xyz.numel() * 4) if self.xyz is not None else 0)
+
+    def batches(self, batch_size):
+        """The index ranges ``test_epoch_audio(batch_size=...)`` forms on this file list: consecutive clips share a pass while
+        their whole-hop length is equal (and with it, at the usual hops, their label frames)."""
+        out, i, n, bs = [], 0, len(self.filelist), max(1, int(batch_size))
+        while i < n:
+            j = i + 1
+            while j < min(i + bs, n) and self.n_hops[j] == self.n_hops[i] and self.label_frames[j] == self.label_frames[i]:
+                j += 1
+            out.append(range(i, j))
+            i = j
+        return out
+
+    def cap(self, batch):
+        """Target rows of a batch of ``batch`` clips (AD-YOLO)."""
+        from . import graph
+        q = graph.TARGET_QUANTUM
+        return (max(1, int(batch) * self.cap_per_clip) + q - 1) // q * q
+
+    def _items_of(self, indices):
+        idx = list(indices)
+        if not idx or min(idx) < 0 or max(idx) >= len(self.filelist):
+            raise ValueError("EvalDeviceCorpus.launch: clips %s of a split of %d" % (idx, len(self.filelist)))
+        if idx == list(range(idx[0], idx[0] + len(idx))):
+            return idx, self.items[idx[0]:idx[0] + len(idx)]                     # a view: nothing crosses PCIe
+        return idx, self.items.index_select(0, torch.tensor(idx, dtype=torch.int64).to(self.device, non_blocking=True))
+
+    def launch(self, indices, audio_out=None):
+        """Clips ``indices`` of ``get_filelist()`` (equal whole-hop lengths, e.g. a range of ``batches``) -> (audio (B, t, 4) f32,
+        target, row_start) on the device with no host synchronisation.  AD-YOLO: target (cap(B), 7) rows, b = -1 past the total,
+        and row_start (B + 1,) int32, clip b's rows at [row_start[b], row_start[b + 1]); class-wise heads: the dense
+        (B, T', ...) target and None.  audio_out: write the audio into this buffer (a recorded forward graph's input)."""
+        idx, items = self._items_of(indices)
+        b, t, frames = len(idx), self.n_hops[idx[0]], self.label_frames[idx[0]]
+        if any(self.n_hops[i] != t or self.label_frames[i] != frames for i in idx):
+            raise ValueError("EvalDeviceCorpus.launch: clips %s differ in length (%s samples): one length per batch"
+                             % (idx, [self.lengths[i] for i in idx]))
+        if t <= 0 or frames <= 0:
+            raise ValueError("EvalDeviceCorpus.launch: clip %s is shorter than one hop / label frame" % self.filelist[idx[0]])
+        audio = audio_out if audio_out is not None else torch.empty((b, t, 4), dtype=torch.float32, device=self.device)
+        if tuple(audio.shape) != (b, t, 4):
+            raise ValueError("EvalDeviceCorpus.launch: audio_out %s, expected (%d, %d, 4)" % (tuple(audio.shape), b, t))
+        ops.corpus_gather(self.pcm, items, self.rot, audio, self.status)
+        if self.loss_nm != "adyolo":
+            target = torch.empty(ops.corpus_classwise_shape(self.loss_nm, b, frames, self.nb_classes), dtype=torch.float32,
+                                 device=self.device)
+            ops.corpus_classwise_labels(self.events, items, self.xyz, self.max_events, frames, self.nb_classes, self.loss_nm,
+                                        target, self.status)
+            return audio, target, None
+        me = self.max_events
+        target = torch.empty((self.cap(b), 7), dtype=torch.float32, device=self.device)
+        # the scan leaves lane (b, 0)'s exclusive offset at ws[b * me] and the total right behind the lanes: the row starts
+        ws = torch.zeros(b * max(me, 1) + 1, dtype=torch.int32, device=self.device)
+        ops.corpus_yolo_labels(self.events, items, me, frames, self.bounds, self.grid, self.rot, ws, target,
+                               ws[b * max(me, 1):], self.status)
+        row_start = ws[::max(me, 1)].contiguous()
+        return audio, target, row_start

@@ -487,3 +487,374 @@ extern "C" int adyolo_yolo_decode(const float *logit, float *out, long n_frames,
                        n_anchor, Gaz, Gel, A, C, grid_az, grid_el, 0.5f + g_overlap);
     return adyolo::check_launch("yolo_decode");
 }
+
+// ---- K8f: per-clip AD-YOLO loss, forward only (evaluation: reference src/test.py:33-60 runs batch 1, so every normaliser of
+// ADYOLOloss is per clip) ----
+// B clips of one batched forward pass in one assignment launch, one pass over the logits and one finalisation.  loss[b] carries
+// the bits adyolo_loss_fwd_bwd returns for clip b alone (its logits, its rows with b = 0, no dlogit): the grid has a clip
+// dimension, and inside a clip the rows and the anchor tiles are dealt to workgroups exactly as that call deals them (32 rows
+// per assign workgroup up to LOSS_ASSIGN_BLOCKS, LM_TILE anchors per main workgroup up to LOSS_MAIN_BLOCKS), every fp32 partial
+// sum is formed by the same expressions in the same order and combined in double in the same order.  Without a gradient nothing
+// needs the counts before the final sum: they leave as per-workgroup partials (no arrival counter, no header), and there is no
+// fixed-point gradient accumulation.
+namespace adyolo {
+
+struct ClipRows {
+    int r0, M, nang;
+};
+
+// rows [row_start[b], row_start[b + 1]) of the target, clamped to its capacity
+__device__ __forceinline__ ClipRows clip_rows(const int *__restrict__ row_start, int b, long cap) {
+    long r0 = row_start[b], r1 = row_start[b + 1];
+    r1 = r1 < 0 ? 0 : (r1 > cap ? cap : r1);
+    r0 = r0 < 0 ? 0 : (r0 > r1 ? r1 : r0);
+    ClipRows c;
+    c.r0 = (int)r0;
+    c.M = (int)(r1 - r0);
+    c.nang = (c.M + 31) / 32;
+    if (c.nang > LOSS_ASSIGN_BLOCKS) c.nang = LOSS_ASSIGN_BLOCKS;
+    return c;
+}
+
+// grid (assign workgroups of the largest clip, B); workgroup (x, b) is workgroup x of clip b's own launch of nang workgroups
+// (x >= nang: nothing to do).  A row counts only if its b column names the clip its range belongs to.
+__global__ __launch_bounds__(256) void loss_assign_clip_kernel(const float *__restrict__ logit, const float *__restrict__ target,
+                                                               const int *__restrict__ row_start, long cap, LossGeom g,
+                                                               unsigned *__restrict__ pos_bits, unsigned *__restrict__ cls_bits,
+                                                               float *__restrict__ ang_partial,
+                                                               unsigned *__restrict__ cnt_partial, long NA_all) {
+    __shared__ float red_sum[4];
+    __shared__ int red_cnt[4][4];
+    const int clip = blockIdx.y;
+    const ClipRows cr = clip_rows(row_start, clip, cap);
+    if ((int)blockIdx.x >= cr.nang) return;
+    const int a = threadIdx.x & 7;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float blk_sum = 0.f;
+    int cnt0 = 0, cnt1 = 0, cnt2 = 0, cntp = 0;
+    const long nlanes = (long)cr.M * 8;
+    for (long gt = (long)blockIdx.x * blockDim.x + threadIdx.x; gt - threadIdx.x < nlanes; gt += (long)cr.nang * blockDim.x) {
+    const int m = (int)(gt >> 3);
+    float my_sum = 0.f;
+    int my_pairs = 0;
+    float D = INFINITY;
+    long cell = 0;
+    int cl = 0;
+    bool valid = false;
+    if (m < cr.M) {
+        const float *tr = target + (size_t)(cr.r0 + m) * 7;
+        const int b = (int)tr[0], t = (int)tr[1], gi = (int)tr[2], gj = (int)tr[3];
+        cl = (int)tr[4];
+        const float U = tr[5], V = tr[6];
+        if (b == clip && t >= 0 && t < g.T && gi >= 0 && gi < g.Gaz && gj >= 0 && gj < g.Gel && cl >= 0 && cl < g.C) {
+            valid = true;
+            cell = (((long)clip * g.T + t) * g.Gaz + gi) * g.Gel + gj;
+            if (a < g.A) {
+                const int CH = g.C + 3;
+                const float off_u = gi * g.grid_az - 180.f + 0.5f * g.grid_az;
+                const float off_v = gj * g.grid_el - 90.f + 0.5f * g.grid_el;
+                const float u2 = deg2rad_(U), v2 = deg2rad_(V);
+                const float sv2 = sinf(v2), cv2 = cosf(v2);
+                const float *lp = logit + ((size_t)cell * g.A + a) * CH + g.C + 1;
+                const float tu = tanhf(lp[0]), tv = tanhf(lp[1]);
+                float ud = tu * g.span * g.grid_az + off_u;
+                const float vraw = tv * g.span * g.grid_el + off_v;
+                const float vd = fminf(fmaxf(vraw, -90.f), 90.f);
+                if (ud >= 180.f) ud -= 360.f;
+                if (ud < -180.f) ud += 360.f;
+                const float u1 = deg2rad_(ud), v1 = deg2rad_(vd);
+                const float sv1 = sinf(v1), cv1 = cosf(v1);
+                const float du = u1 - u2, adu = fabsf(du);
+                const float cs = sv1 * sv2 + cv1 * cv2 * cosf(adu);
+                const float lo = -1.f + 1e-7f, hi = 1.f - 1e-7f;
+                const float cc = fminf(fmaxf(cs, lo), hi);
+                D = rad2deg_(acosf(cc));
+            }
+        }
+    }
+    float dmin = D;
+    int amin = a;
+#pragma unroll
+    for (int o = 4; o > 0; o >>= 1) {
+        const float od = __shfl_xor(dmin, o, 64);
+        const int oa = __shfl_xor(amin, o, 64);
+        if (od < dmin || (od == dmin && oa < amin)) {
+            dmin = od;
+            amin = oa;
+        }
+    }
+    unsigned bits = 0, fresh = 0;
+    if (valid && a < g.A) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+            if (D < g.thr[i] || a == amin) bits |= 1u << i;
+    }
+    if (bits) {
+        const long anchor = cell * g.A + a;
+        const unsigned old = atomicOr(&pos_bits[anchor], bits);
+        fresh = bits & ~old;
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+            if (bits & (1u << i)) atomicOr(&cls_bits[(size_t)i * NA_all + anchor], 1u << cl);
+        if (bits & 1u) {
+            my_sum = D / 180.f;
+            my_pairs = 1;
+        }
+    }
+    cnt0 += __popcll(__ballot(fresh & 1u));
+    cnt1 += __popcll(__ballot((fresh >> 1) & 1u));
+    cnt2 += __popcll(__ballot((fresh >> 2) & 1u));
+    cntp += __popcll(__ballot(my_pairs != 0));
+    blk_sum += my_sum;
+    }
+    blk_sum = wave_sum(blk_sum);
+    if (lane == 0) {
+        red_sum[wave] = blk_sum;
+        red_cnt[wave][0] = cnt0;
+        red_cnt[wave][1] = cnt1;
+        red_cnt[wave][2] = cnt2;
+        red_cnt[wave][3] = cntp;
+    }
+    __syncthreads();
+    const size_t slot = (size_t)clip * LOSS_ASSIGN_BLOCKS + blockIdx.x;
+    if (threadIdx.x < 4)
+        cnt_partial[slot * 4 + threadIdx.x] = (unsigned)(red_cnt[0][threadIdx.x] + red_cnt[1][threadIdx.x] +
+                                                         red_cnt[2][threadIdx.x] + red_cnt[3][threadIdx.x]);
+    if (threadIdx.x == 0) ang_partial[slot] = red_sum[0] + red_sum[1] + red_sum[2] + red_sum[3];
+}
+
+// grid (main workgroups of one clip, B): loss_main_kernel's pass over clip b's logits without the gradient -- the same tile
+// staging, the same nine sums per lane, wave and workgroup.  A clip without rows is skipped (its loss is not formed).
+template <bool PAD>
+__global__ __launch_bounds__(256) void loss_main_clip_kernel(const float *__restrict__ logit_all, LossGeom g,
+                                                             const int *__restrict__ row_start, long cap,
+                                                             const unsigned *__restrict__ pos_bits_all,
+                                                             const unsigned *__restrict__ cls_bits, float *__restrict__ partial_all,
+                                                             long NA, long NA_all) {
+    extern __shared__ __attribute__((aligned(16))) float tile[];      // [LM_TILE][CHP]
+    __shared__ float red[4][9];
+    const int clip = blockIdx.y;
+    if (clip_rows(row_start, clip, cap).M == 0) return;
+    const int CH = g.C + 3;
+    const int CHP = PAD ? CH + 1 : CH;
+    const int tid = threadIdx.x;
+    const float *logit = logit_all + (size_t)clip * NA * CH;          // NA * CH * 4 bytes per clip: 16-byte aligned when
+    const unsigned *pos_bits = pos_bits_all + (size_t)clip * NA;      // NA * CH % 4 == 0 (checked by the caller)
+    float *partial = partial_all + (size_t)clip * LOSS_MAIN_BLOCKS * 9;
+    float acc[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) acc[i] = 0.f;
+    const long ntiles = (NA + LM_TILE - 1) / LM_TILE;
+    for (long tl = blockIdx.x; tl < ntiles; tl += gridDim.x) {
+        const long a0 = tl * LM_TILE;
+        const int na = (int)((NA - a0) < LM_TILE ? (NA - a0) : LM_TILE);
+        const int nel = na * CH, n4 = nel >> 2;
+        const float *src = logit + (size_t)a0 * CH;
+        for (int i = tid; i < n4; i += 256) {
+            const float4 v = reinterpret_cast<const float4 *>(src)[i];
+            if (PAD) {
+                const unsigned e = 4u * i, r = e / (unsigned)CH, c = e - r * (unsigned)CH;
+                float *d = tile + r * CHP + c;
+                const float vv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const unsigned ck = c + k;
+                    (ck < (unsigned)CH ? d + k : tile + (r + 1) * CHP + (ck - CH))[0] = vv[k];
+                }
+            } else {
+                reinterpret_cast<float4 *>(tile)[i] = v;
+            }
+        }
+        for (int e = 4 * n4 + tid; e < nel; e += 256) {
+            const int r = e / CH;
+            tile[r * CHP + (e - r * CH)] = src[e];
+        }
+        __syncthreads();
+        if (tid < na) {
+            const long anchor = a0 + tid;
+            const float *x = tile + tid * CHP;
+            const unsigned pb = pos_bits[anchor];
+            {
+                const float s = sigmoidf_(x[0]);
+                const float lp = -fmaxf(logf(s), -100.f);
+                const float lq = -fmaxf(logf(1.f - s), -100.f);
+#pragma unroll
+                for (int i = 0; i < 3; ++i) {
+                    if (pb & (1u << i))
+                        acc[i] += lp;
+                    else
+                        acc[3 + i] += lq;
+                }
+            }
+            if (pb) {
+                unsigned cb[3];
+#pragma unroll
+                for (int i = 0; i < 3; ++i)
+                    cb[i] = (pb & (1u << i)) ? cls_bits[(size_t)i * NA_all + (size_t)clip * NA + anchor] : 0u;
+                for (int ch = 1; ch <= g.C; ++ch) {
+                    const float s = sigmoidf_(x[ch]);
+                    const float lp = -fmaxf(logf(s), -100.f);
+                    const float lq = -fmaxf(logf(1.f - s), -100.f);
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) {
+                        if (pb & (1u << i)) {
+                            const unsigned yb = (cb[i] >> (ch - 1)) & 1u;
+                            acc[6 + i] += yb ? lp : lq;
+                        }
+                    }
+                }
+            }
+        }
+        __syncthreads();
+    }
+    const int lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+        const float v = wave_sum(acc[i]);
+        if (lane == 0) red[wave][i] = v;
+    }
+    __syncthreads();
+    if (tid < 9)
+        partial[(size_t)blockIdx.x * 9 + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+}
+
+// grid (B): loss_final_kernel for clip b, with the four counts summed here from the assign workgroups' partials (integers)
+__global__ __launch_bounds__(256) void loss_final_clip_kernel(const float *__restrict__ partial_all, int nblk,
+                                                              const float *__restrict__ ang_partial_all,
+                                                              const unsigned *__restrict__ cnt_partial_all,
+                                                              const int *__restrict__ row_start, long cap, LossGeom g, long NA,
+                                                              float *__restrict__ loss, int *__restrict__ valid) {
+    __shared__ double red[256];
+    __shared__ double tot[10];
+    __shared__ unsigned cred[4][4];
+    __shared__ unsigned hdr[4];
+    const int clip = blockIdx.x;
+    const ClipRows cr = clip_rows(row_start, clip, cap);
+    if (cr.M == 0) {
+        if (threadIdx.x == 0) {
+            loss[clip] = 0.f;
+            valid[clip] = 0;
+        }
+        return;
+    }
+    const float *partial = partial_all + (size_t)clip * LOSS_MAIN_BLOCKS * 9;
+    const float *ang_partial = ang_partial_all + (size_t)clip * LOSS_ASSIGN_BLOCKS;
+    const unsigned *cnt_partial = cnt_partial_all + (size_t)clip * LOSS_ASSIGN_BLOCKS * 4;
+    const int nang = cr.nang, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned t4[4] = {0u, 0u, 0u, 0u};
+    for (int bk = threadIdx.x; bk < nang; bk += 256) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) t4[i] += cnt_partial[4 * bk + i];
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        unsigned v = t4[i];
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        if (lane == 0) cred[wave][i] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < 4) hdr[threadIdx.x] = cred[0][threadIdx.x] + cred[1][threadIdx.x] + cred[2][threadIdx.x] + cred[3][threadIdx.x];
+    const double s = block_colsum32(partial, nblk, 9, 0, 9, red);        // 9 BCE sums
+    if ((threadIdx.x >> 5) == 0 && (threadIdx.x & 31) < 9) tot[threadIdx.x & 31] = s;
+    double a = 0.0;
+    for (int b = threadIdx.x; b < nang; b += 256) a += (double)ang_partial[b];
+    red[threadIdx.x] = a;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double ang = 0.0;
+        for (int k = 0; k < 256; ++k) ang += red[k];
+        double total = (double)g.gain_ang * ang / (double)hdr[3];
+        for (int i = 0; i < 3; ++i) {
+            const double np_ = (double)hdr[i], nn_ = (double)(NA - (long)hdr[i]);
+            total += ((double)g.gain_obj * tot[i] / np_ + (double)g.gain_nonobj * tot[3 + i] / nn_ +
+                      (double)g.gain_cls * tot[6 + i] / (np_ * (double)g.C)) / 3.0;
+        }
+        loss[clip] = (float)total;
+        valid[clip] = 1;
+    }
+}
+
+// one thread: acc[0] += loss[i] for the valid i in order, in float32 (the host loop's ``total + loss``); acc[1] += their count
+__global__ void loss_accumulate_kernel(const float *__restrict__ loss, const int *__restrict__ valid, int n,
+                                       float *__restrict__ acc) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    float sum = acc[0], cnt = acc[1];
+    for (int i = 0; i < n; ++i) {
+        if (valid && !valid[i]) continue;
+        sum = sum + loss[i];
+        cnt = cnt + 1.f;
+    }
+    acc[0] = sum;
+    acc[1] = cnt;
+}
+
+}  // namespace adyolo
+
+// workspace (32-bit words): [pos_bits B*NA][cls_bits 3*B*NA][ang_partial B*1024][cnt_partial B*4*1024][partial B*9*2048]
+extern "C" long adyolo_loss_per_clip_workspace_words(int B, int T, int G, int A) {
+    if (B <= 0 || T <= 0 || G <= 0 || A <= 0) return -1;
+    const long NA = (long)T * G * A;
+    return (long)B * (4 * NA + 5L * LOSS_ASSIGN_BLOCKS + 9L * LOSS_MAIN_BLOCKS) + 64;
+}
+
+extern "C" int adyolo_loss_accumulate(const float *loss, const int *valid, int n, float *acc, void *stream) {
+    ADYOLO_REQUIRE(loss && acc && n > 0, ADYOLO_EINVAL, "loss_accumulate: bad arguments");
+    hipLaunchKernelGGL(loss_accumulate_kernel, dim3(1), dim3(64), 0, as_stream(stream), loss, valid, n, acc);
+    return check_launch("loss_accumulate");
+}
+
+extern "C" int adyolo_loss_per_clip(const float *logit, const float *target, const int *row_start, float *ws, float *loss,
+                                    int *valid, float *acc, int B, int T, int Gaz, int Gel, int A, int C, long cap,
+                                    const float *thr_host, const float *gains_host, float grid_az, float grid_el,
+                                    float g_overlap, void *stream) {
+    ADYOLO_REQUIRE(logit && target && row_start && ws && loss && valid && thr_host && gains_host, ADYOLO_EINVAL,
+                   "loss_per_clip: null pointer");
+    ADYOLO_REQUIRE(B > 0 && B < 65536 && T > 0 && Gaz > 0 && Gel > 0 && A > 0 && A <= 8 && C > 0 && C <= 32, ADYOLO_ENOSUP,
+                   "loss_per_clip: unsupported geometry B=%d A=%d (<=8) C=%d (<=32)", B, A, C);
+    ADYOLO_REQUIRE(cap > 0 && cap < (1L << 31), ADYOLO_EINVAL, "loss_per_clip: bad target capacity %ld", cap);
+    const long NA = (long)T * Gaz * Gel * A, NA_all = NA * B;
+    const int CH = C + 3;
+    // every clip's logits start on a 16-byte boundary, as its own call's would (the tile loads are 16 bytes wide)
+    ADYOLO_REQUIRE(((uintptr_t)logit & 15) == 0 && (B == 1 || (NA * CH) % 4 == 0), ADYOLO_ENOSUP,
+                   "loss_per_clip: a clip of %ld x %d logits does not start on a 16-byte boundary", NA, CH);
+    hipStream_t st = as_stream(stream);
+    LossGeom g;
+    g.B = B; g.T = T; g.Gaz = Gaz; g.Gel = Gel; g.A = A; g.C = C; g.M = 0;
+    for (int i = 0; i < 3; ++i) g.thr[i] = thr_host[i];
+    g.gain_ang = gains_host[0]; g.gain_obj = gains_host[1]; g.gain_nonobj = gains_host[2]; g.gain_cls = gains_host[3];
+    g.grid_az = grid_az; g.grid_el = grid_el; g.span = 0.5f + g_overlap;
+
+    unsigned *pos_bits = reinterpret_cast<unsigned *>(ws);
+    unsigned *cls_bits = pos_bits + NA_all;
+    float *ang_partial = reinterpret_cast<float *>(cls_bits + 3 * NA_all);
+    unsigned *cnt_partial = reinterpret_cast<unsigned *>(ang_partial + (size_t)B * LOSS_ASSIGN_BLOCKS);
+    float *partial = reinterpret_cast<float *>(cnt_partial + (size_t)B * 4 * LOSS_ASSIGN_BLOCKS);
+    int rc = fill32(ws, 0u, (size_t)(4 * NA_all), st);
+    if (rc) return rc;
+    int gx = cdiv(cap, 32);
+    if (gx > LOSS_ASSIGN_BLOCKS) gx = LOSS_ASSIGN_BLOCKS;
+    hipLaunchKernelGGL(loss_assign_clip_kernel, dim3((unsigned)gx, (unsigned)B), dim3(256), 0, st, logit, target, row_start, cap,
+                       g, pos_bits, cls_bits, ang_partial, cnt_partial, NA_all);
+    rc = check_launch("loss_assign_clip");
+    if (rc) return rc;
+    long nb = (NA + LM_TILE - 1) / LM_TILE;
+    if (nb > LOSS_MAIN_BLOCKS) nb = LOSS_MAIN_BLOCKS;
+    if (CH & 1)
+        hipLaunchKernelGGL(loss_main_clip_kernel<false>, dim3((unsigned)nb, (unsigned)B), dim3(256), (size_t)LM_TILE * CH * 4, st,
+                           logit, g, row_start, cap, pos_bits, cls_bits, partial, NA, NA_all);
+    else
+        hipLaunchKernelGGL(loss_main_clip_kernel<true>, dim3((unsigned)nb, (unsigned)B), dim3(256),
+                           (size_t)(LM_TILE + 1) * (CH + 1) * 4, st, logit, g, row_start, cap, pos_bits, cls_bits, partial, NA,
+                           NA_all);
+    rc = check_launch("loss_main_clip");
+    if (rc) return rc;
+    hipLaunchKernelGGL(loss_final_clip_kernel, dim3((unsigned)B), dim3(256), 0, st, partial, (int)nb, ang_partial, cnt_partial,
+                       row_start, cap, g, NA, loss, valid);
+    rc = check_launch("loss_final_clip");
+    if (rc) return rc;
+    if (acc) {
+        hipLaunchKernelGGL(loss_accumulate_kernel, dim3(1), dim3(64), 0, st, loss, valid, B, acc);
+        rc = check_launch("loss_accumulate");
+    }
+    return rc;
+}

@@ -299,6 +299,15 @@ class ForwardGraphs:
             dec = self.post.decode_device(out)         # the post-processor owns the decode format (AD-YOLO or class-wise)
         return out, dec
 
+    def static_input(self, shape):
+        """The static input buffer of the graph recorded for ``shape`` (B, n, 4), or None when none is recorded (yet): a
+        producer that writes the audio straight into it (``corpus.EvalDeviceCorpus.launch(audio_out=...)``) and hands it to
+        ``__call__`` saves the copy.  The buffer dies with its graph (parameters written, eviction): ask again before each use."""
+        if self.epoch != self._stamp():
+            return None
+        ent = self.entries.get(tuple(shape))
+        return None if ent is None else ent[1]
+
     def __call__(self, audio):
         if self.model.training:
             raise RuntimeError("ForwardGraphs records the evaluation forward: call model.eval() first")

@@ -899,6 +899,57 @@ def adyolo_loss(logit, target, nb_classes, grid=(8, 4), anchors=5, thr=(45.0, 25
     return loss, dlogit, dist
 
 
+def loss_accumulator(device):
+    """A running device accumulator float32 (2,) {sum, count} for ``adyolo_loss_per_clip`` / ``loss_accumulate``, zeroed."""
+    return torch.zeros(2, dtype=torch.float32, device=device)
+
+
+def loss_accumulate(acc, loss, valid=None):
+    """acc {sum, count} += the losses of ``loss`` (any shape, float32) whose ``valid`` word (int32, same count; None: all) is
+    not zero, added one after the other in float32 by one device thread: an evaluation loop's ``total + loss`` without the
+    host.  No sync."""
+    _chk(acc, loss)
+    n = loss.numel()
+    if acc.numel() != 2 or n < 1:
+        raise _lib.AdyoloHipError("loss_accumulate: acc must hold 2 floats and loss at least one")
+    if valid is not None and (valid.dtype != torch.int32 or not valid.is_cuda or not valid.is_contiguous()
+                              or valid.numel() != n):
+        raise _lib.AdyoloHipError("loss_accumulate: valid must be %d contiguous int32 words on the device" % n)
+    _c("adyolo_loss_accumulate", _p(loss), _p(valid), n, _p(acc), _stream())
+    return acc
+
+
+def adyolo_loss_per_clip(logit, target, row_start, nb_classes, grid=(8, 4), anchors=5, thr=(45.0, 25.0, 10.0),
+                         gains=(5.0, 1.0, 5.0, 3.0), grid_size=(45.0, 45.0), g_overlap=0.5, acc=None):
+    """The AD-YOLO loss of every clip of a batched evaluation pass, forward only: logit [B][T][G*A*(C+3)], target (cap, 7) with
+    clip b's rows at [row_start[b], row_start[b + 1]) and b in their first column, row_start int32 (B + 1,), all on the
+    device -> loss (B,) float32, valid (B,) int32.  loss[b] carries the bits of ``adyolo_loss(logit[b:b+1], rows of clip b with
+    b = 0, need_grad=False)``; a clip without rows gets loss 0 and valid 0.  acc: a ``loss_accumulator`` the valid losses are
+    added to in clip order.  No sync."""
+    _chk(logit, target, acc)
+    if logit.dim() != 3 or target.dim() != 2 or target.shape[1] != 7 or target.shape[0] < 1:
+        raise _lib.AdyoloHipError("adyolo_loss_per_clip: logit %s / target %s are not [B][T][K] / (cap, 7)"
+                                  % (tuple(logit.shape), tuple(target.shape)))
+    b, t = logit.shape[0], logit.shape[1]
+    if logit.shape[2] != grid[0] * grid[1] * anchors * (nb_classes + 3):
+        raise _lib.AdyoloHipError("adyolo_loss_per_clip: %d logits per frame, expected %d x %d x %d x (%d + 3)"
+                                  % (logit.shape[2], grid[0], grid[1], anchors, nb_classes))
+    if row_start.dtype != torch.int32 or not row_start.is_cuda or not row_start.is_contiguous() or row_start.numel() != b + 1:
+        raise _lib.AdyoloHipError("adyolo_loss_per_clip: row_start must be %d contiguous int32 words on the device" % (b + 1))
+    if acc is not None and acc.numel() != 2:
+        raise _lib.AdyoloHipError("adyolo_loss_per_clip: acc must hold 2 floats")
+    words = _lib.load().adyolo_loss_per_clip_workspace_words(b, t, grid[0] * grid[1], anchors)
+    ws = _new(logit, words)
+    loss = _new(logit, b)
+    valid = torch.empty(b, dtype=torch.int32, device=logit.device)
+    thr_h = (ctypes.c_float * 3)(*[float(v) for v in thr])
+    gains_h = (ctypes.c_float * 4)(*[float(v) for v in gains])
+    _c("adyolo_loss_per_clip", _p(logit), _p(target), _p(row_start), _p(ws), _p(loss), _p(valid), _p(acc), b, t, grid[0],
+       grid[1], anchors, nb_classes, target.shape[0], ctypes.cast(thr_h, ctypes.c_void_p),
+       ctypes.cast(gains_h, ctypes.c_void_p), float(grid_size[0]), float(grid_size[1]), float(g_overlap), _stream())
+    return loss, valid
+
+
 def act_fwd(x2d, n_sigmoid_cols):
     """columns [0, n_sigmoid_cols) -> sigmoid, the rest -> tanh."""
     _chk(x2d)

@@ -170,6 +170,122 @@ def test_epoch_audio(dataset, model, features, criterion, postprocessor, device,
     return float(total) / max(n, 1) if total is not None else 0.0
 
 
+def _corpus_batch(corpus, idx, model, features, criterion, postprocessor, forward, acc):
+    """One batch of an HBM-resident evaluation split: ``launch`` -> forward (+ decode) -> the per-clip losses into ``acc``.
+    -> the decoded batch (a recorded graph's static output when ``forward`` replays one).  No host synchronisation."""
+    from . import ops
+    b = len(idx)
+    audio_out = None
+    if forward is not None and hasattr(forward, "static_input"):
+        audio_out = forward.static_input((b, corpus.n_hops[idx[0]], 4))      # the gather writes the graph's input itself
+    audio, target, row_start = corpus.launch(idx, audio_out)
+    dec = None
+    if forward is not None:
+        output, dec = forward(audio)
+    else:
+        output = model(features(audio, channels_last8=True), channels_last8=True)
+    if dec is None:
+        dec = postprocessor.decode_device(output)
+    if row_start is not None:                              # AD-YOLO: every clip's loss in one call, normalised per clip
+        cfg = getattr(criterion, "loss", criterion).cfg
+        ops.adyolo_loss_per_clip(output.contiguous(), target, row_start, cfg["nb_classes"], cfg["grid"], cfg["anchors"],
+                                 cfg["thr"], cfg["gains"], cfg["grid_size"], cfg["g_overlap"], acc=acc)
+    else:                                                  # class-wise heads: the existing entry point on each clip's slice
+        for k in range(b):
+            ops.loss_accumulate(acc, criterion(output[k:k + 1], target[k:k + 1]).reshape(1))
+    return dec
+
+
+def _corpus_finish(corpus, acc):
+    """The one synchronisation of a pass: the loss accumulator {sum, count} and the corpus status word -> the mean loss."""
+    from . import ops
+    acc_h, status_h = ops.to_host_many(acc, corpus.status)
+    corpus.check(int(status_h[0]))
+    total, n = acc_h[0], int(acc_h[1])
+    return float(total) / max(n, 1) if n else 0.0
+
+
+def _write_rows(output_pth, names, rows, counts):
+    """Selected device rows of ``len(names)`` clips (trimmed to their total) -> one CSV per clip."""
+    from . import ops
+    rows_h, counts_h = [t.numpy() for t in ops.to_host_many(rows, counts)]
+    for name, clip_rows in zip(names, group_rows(rows_h, counts_h, len(names))):
+        write_seld_output_file(os.path.join(output_pth, name + ".csv"), clip_rows)
+
+
+def test_epoch_corpus(corpus, model, features, criterion, postprocessor, output_pth=None, batch_size=8, forward=None,
+                      device_scorer=None):
+    """``test_epoch_audio(device_select=True)`` from an HBM-resident split (``corpus.EvalDeviceCorpus``): the same batches,
+    the same mean of per-clip losses (float32 adds in file order, clips without AD-YOLO rows left out), the same selected rows
+    into ``device_scorer`` and, with ``output_pth``, the same CSV files -- but no WAV read, no CSV parse, no host label
+    encoding and no audio or target upload: per batch ``corpus.launch`` -> ``forward(audio)`` (``graph.ForwardGraphs``; default
+    the eager forward + ``decode_device``) -> the per-clip loss on the device (``ops.adyolo_loss_per_clip``, or the class-wise
+    loss per slice) -> ``select_device_rows`` -> ``device_scorer.add_rows``.  output_pth=None: nothing is written and the
+    pass synchronises ONCE, at its end, to read the loss accumulator and the corpus status word together; with output_pth
+    every batch's rows are copied to the host (one synchronisation each).  Returns the mean loss."""
+    from . import ops
+    model.eval()
+    if output_pth is not None:
+        delete_and_create_folder(output_pth)
+    names = corpus.get_filelist()
+    corpus.reset_status()
+    acc = ops.loss_accumulator(corpus.device)
+    with torch.no_grad():
+        for idx in corpus.batches(batch_size):
+            clips = [names[i] for i in idx]
+            dec = _corpus_batch(corpus, idx, model, features, criterion, postprocessor, forward, acc)
+            rows, counts = postprocessor.select_device_rows(dec, len(clips), trim=output_pth is not None)
+            if device_scorer is not None:
+                device_scorer.add_rows(rows, counts, clips)
+            if output_pth is not None:
+                _write_rows(output_pth, clips, rows, counts)
+    return _corpus_finish(corpus, acc)
+
+
+def sweep_conf_thresh_corpus(corpus, model, features, criterion, postprocessor, scorer, thresholds=None, output_pth=None,
+                             batch_size=8, forward=None):
+    """``sweep_conf_thresh(device_select=True, device_score=True)`` from an HBM-resident split: ONE forward pass per batch,
+    every batch's decode kept on the device, then per threshold the selections and the device scores (``scorer``: a
+    ``seld_metrics.DeviceSELDScorer``); the chosen threshold is left set on the post-processor.  With ``output_pth`` the last
+    threshold's CSV files are written, as the host sweep leaves them.  Clips without AD-YOLO rows are left out of the mean
+    loss (the host sweep cannot take them at all).  -> (new_thresh, [[ER, F, LE, LR, SELD] per threshold], mean loss)"""
+    import numpy as np
+    from . import ops
+    from .seld_metrics import DeviceSELDScorer
+    if not isinstance(scorer, DeviceSELDScorer):
+        raise ValueError("sweep_conf_thresh_corpus needs a seld_metrics.DeviceSELDScorer (got %s)" % type(scorer).__name__)
+    if thresholds is None:
+        thresholds = np.arange(0.1, 1.0, 0.1)
+    model.eval()
+    names = corpus.get_filelist()
+    corpus.reset_status()
+    acc = ops.loss_accumulator(corpus.device)
+    decoded = []
+    with torch.no_grad():
+        for idx in corpus.batches(batch_size):
+            dec = _corpus_batch(corpus, idx, model, features, criterion, postprocessor, forward, acc)
+            decoded.append(([names[i] for i in idx], dec.clone() if forward is not None else dec))   # (a graph's output is reused)
+    loss = _corpus_finish(corpus, acc)
+    new_thresh, best, table = postprocessor.get_conf_thresh(), 9999.0, []
+    for k, th in enumerate(thresholds):
+        postprocessor.set_conf_thresh(th)
+        write = output_pth is not None and k == len(thresholds) - 1
+        if write:
+            delete_and_create_folder(output_pth)
+        scorer.reset()
+        for clips, dec in decoded:
+            rows, counts = postprocessor.select_device_rows(dec, len(clips), trim=write)
+            scorer.add_rows(rows, counts, clips)
+            if write:
+                _write_rows(output_pth, clips, rows, counts)
+        er, f, le, lr, seld = scorer.scores()[:5]
+        table.append([er, f, le, lr, seld])
+        if seld < best:
+            new_thresh, best = th, seld
+    postprocessor.set_conf_thresh(new_thresh)
+    return new_thresh, table, loss
+
+
 def score_output_folder(params, ref_dir, output_pth, is_jackknife=False):
     """The three score sets the reference prints for one evaluated folder (src/test.py:104-133): all frames, frames with
     overlapping events ("class-independent polyphony") and frames with overlapping events of one class

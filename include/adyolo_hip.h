@@ -397,6 +397,24 @@ int  adyolo_loss_phase(const float *logit, const float *target, float *ws, float
                        int M, const float *thr_host, const float *gains_host, float grid_az,
                        float grid_el, float g_overlap, float grad_scale, int phases, long na_total, void *stream);
 
+/* K8f per-clip AD-YOLO loss, forward only (evaluation: src/test.py:33-60 runs batch 1, every normaliser is per clip).
+ *   logit     [B][T][Gaz*Gel][A][C+3]: B clips of one batched forward pass (each clip's logits 16-byte aligned)
+ *   target    [cap][7] rows as above, the rows of clip b contiguous with b in column 0 (rows elsewhere, b = -1 padding
+ *             included, are not read); row_start [B + 1] int32: clip b owns rows [row_start[b], row_start[b + 1])
+ *   ws        adyolo_loss_per_clip_workspace_words(B, T, Gaz * Gel, A) 32-bit words (zeroed by the call itself)
+ *   loss [B]  float32: loss[b] carries the bits adyolo_loss_fwd_bwd(dlogit = NULL) returns for clip b's logits and rows alone
+ *             (0 for a clip without rows); valid [B] int32: 0 for a clip without rows, else 1
+ *   acc       NULL, or the running accumulator of adyolo_loss_accumulate the valid losses are added to
+ * Five launches whatever B is; no dlogit, no host synchronisation. */
+long adyolo_loss_per_clip_workspace_words(int B, int T, int G, int A);
+int  adyolo_loss_per_clip(const float *logit, const float *target, const int *row_start, float *ws, float *loss,
+                          int *valid, float *acc, int B, int T, int Gaz, int Gel, int A, int C, long cap,
+                          const float *thr_host, const float *gains_host, float grid_az, float grid_el,
+                          float g_overlap, void *stream);
+/* acc [2] float32 {sum, count} += the losses loss[i], i = 0 .. n - 1 with valid[i] != 0 (valid NULL: all), added one after the
+ * other in float32 by one thread: the evaluation loop's ``total + loss`` on the device. */
+int  adyolo_loss_accumulate(const float *loss, const int *valid, int n, float *acc, void *stream);
+
 /* K8b inference decode (LabelPostProcessor.get_yolo_output, src/datasets.py:752-771): per anchor
  *   out = [sigmoid(obj), sigmoid(cls_c)*sigmoid(obj) x C, U deg in [-180,180), V deg in [-90, 90-1e-7]];
  *   by default thresholding and the (tiny, data-dependent) NMS stay on the host (ad-yolo_amd/postprocess.py);

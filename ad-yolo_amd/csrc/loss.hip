@@ -9,6 +9,7 @@
 //               thresholds and dlogit written in the same pass (HBM traffic = read logits + write dlogits
 //               + 6 words per anchor of assignment state).
 //   3. final  : combines the per-workgroup partial sums in double into the (1,) loss.
+// Each kernel is a template on GRAD: <true> is this training form, <false> the forward-only per-clip form (K8f, below).
 #include "common.hpp"
 
 namespace adyolo {
@@ -35,26 +36,59 @@ __device__ __forceinline__ float from_fixed(unsigned long long q) {
     return (float)((double)(long long)q * (1.0 / 4294967296.0));
 }
 
+// The normalisation unit: what one set of counts (distinct positives per threshold, responsible pairs, anchors) covers.  The
+// three kernels below have two forms each.  GRAD, the training form (adyolo_loss_phase): the unit is the whole [B][T] batch
+// on a one-dimensional grid; the counts go through the header and the gradient is formed.  !GRAD, the per-clip form
+// (adyolo_loss_per_clip, K8f below): unit `idx` of `count` is one clip of a batched pass on a grid with a clip dimension; its
+// rows are [row_start[idx], row_start[idx + 1]) of the target, clamped to its capacity, and its logits, bit sets and partial
+// sums follow those of the clips before it.  With GRAD idx = 0 and count = 1 are constants and the offsets fold away.
+struct LossUnit {
+    int idx, count;
+    int b0, b1;            // a row counts if its b column lies in [b0, b1)
+    int r0, M, nang;       // first row, rows, assign workgroups (32 rows each per round: also the grid-stride over the rows)
+};
+
+template <bool GRAD>
+__device__ __forceinline__ LossUnit loss_unit(const LossGeom &g, const int *__restrict__ row_start, long cap, int clip, int nang) {
+    LossUnit u;
+    if constexpr (GRAD) {
+        u.idx = 0; u.count = 1; u.b0 = 0; u.b1 = g.B; u.r0 = 0; u.M = g.M; u.nang = nang;
+    } else {
+        long r0 = row_start[clip], r1 = row_start[clip + 1];
+        r1 = r1 < 0 ? 0 : (r1 > cap ? cap : r1);
+        r0 = r0 < 0 ? 0 : (r0 > r1 ? r1 : r0);
+        u.idx = clip; u.count = g.B; u.b0 = clip; u.b1 = clip + 1; u.r0 = (int)r0; u.M = (int)(r1 - r0);
+        u.nang = (u.M + 31) / 32;
+        if (u.nang > LOSS_ASSIGN_BLOCKS) u.nang = LOSS_ASSIGN_BLOCKS;
+    }
+    return u;
+}
+
 // 8 lanes per target row: lane a of the octet owns anchor a (one decode + great-circle distance per lane instead of a
 // serial loop over the anchors: 8x the parallelism of a one-lane-per-row kernel, which was latency-bound at 137 k rows);
 // the arg-min is three shuffle steps inside the octet (ties -> the lowest anchor index, like the reference's argmin);
 // distinct-positive counts are kept per wave (ballot + popcount) and leave once per workgroup.
+// GRAD: grid (nang); hdr, ang_grad and dist (optional) are written.  !GRAD: grid (assign workgroups of the largest clip, B);
+// workgroup (x, b) is workgroup x of clip b's own launch of nang workgroups (x >= nang: nothing to do); row_start and cap
+// are read.  NA: anchors of all units (the stride of the cls_bits planes).
+template <bool GRAD>
 __global__ __launch_bounds__(256) void loss_assign_kernel(const float *__restrict__ logit,
                                                           const float *__restrict__ target, LossGeom g,
                                                           unsigned *__restrict__ hdr, unsigned *__restrict__ pos_bits,
                                                           unsigned *__restrict__ cls_bits,
                                                           unsigned long long *__restrict__ ang_grad,
                                                           float *__restrict__ ang_partial, float *__restrict__ dist,
-                                                          long NA) {
+                                                          long NA, const int *__restrict__ row_start, long cap) {
     __shared__ float red_sum[4];
     __shared__ int red_cnt[4][4];
-    __shared__ bool is_last;
+    const LossUnit u = loss_unit<GRAD>(g, row_start, cap, blockIdx.y, gridDim.x);
+    if (!GRAD && (int)blockIdx.x >= u.nang) return;
     const int a = threadIdx.x & 7;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float blk_sum = 0.f;                      // this thread's share of sum(D / 180) over responsible pairs
     int cnt0 = 0, cnt1 = 0, cnt2 = 0, cntp = 0;     // wave-uniform: distinct positives per threshold, responsible pairs
-    const long nlanes = (long)g.M * 8;
-    for (long gt = (long)blockIdx.x * blockDim.x + threadIdx.x; gt - threadIdx.x < nlanes; gt += (long)gridDim.x * blockDim.x) {
+    const long nlanes = (long)u.M * 8;
+    for (long gt = (long)blockIdx.x * blockDim.x + threadIdx.x; gt - threadIdx.x < nlanes; gt += (long)u.nang * blockDim.x) {
     const int m = (int)(gt >> 3);
     float my_sum = 0.f;
     int my_pairs = 0;
@@ -62,12 +96,12 @@ __global__ __launch_bounds__(256) void loss_assign_kernel(const float *__restric
     long cell = 0;
     int cl = 0;
     bool valid = false;
-    if (m < g.M) {
-        const float *tr = target + (size_t)m * 7;
+    if (m < u.M) {
+        const float *tr = target + (size_t)(u.r0 + m) * 7;
         const int b = (int)tr[0], t = (int)tr[1], gi = (int)tr[2], gj = (int)tr[3];
         cl = (int)tr[4];
         const float U = tr[5], V = tr[6];
-        if (b >= 0 && b < g.B && t >= 0 && t < g.T && gi >= 0 && gi < g.Gaz && gj >= 0 && gj < g.Gel && cl >= 0 &&
+        if (b >= u.b0 && b < u.b1 && t >= 0 && t < g.T && gi >= 0 && gi < g.Gaz && gj >= 0 && gj < g.Gel && cl >= 0 &&
             cl < g.C) {
             valid = true;
             cell = (((long)b * g.T + t) * g.Gaz + gi) * g.Gel + gj;
@@ -91,16 +125,18 @@ __global__ __launch_bounds__(256) void loss_assign_kernel(const float *__restric
                 const float lo = -1.f + 1e-7f, hi = 1.f - 1e-7f;
                 const float cc = fminf(fmaxf(cs, lo), hi);
                 D = rad2deg_(acosf(cc));
-                float dD_dcs = 0.f;
-                if (cs >= lo && cs <= hi) dD_dcs = -57.29577951308232f / sqrtf(1.f - cc * cc);
-                const float sgn = du > 0.f ? 1.f : (du < 0.f ? -1.f : 0.f);
-                const float dcs_du1 = -cv1 * cv2 * sinf(adu) * sgn;
-                const float dcs_dv1 = cv1 * sv2 - sv1 * cv2 * cosf(adu);
-                const float dU_dl = (1.f - tu * tu) * g.span * g.grid_az;
-                const float dV_dl = (vraw >= -90.f && vraw <= 90.f) ? (1.f - tv * tv) * g.span * g.grid_el : 0.f;
-                gu = dD_dcs * dcs_du1 * 0.017453292519943295f * dU_dl;
-                gv = dD_dcs * dcs_dv1 * 0.017453292519943295f * dV_dl;
-                if (dist) dist[(size_t)m * g.A + a] = D;
+                if constexpr (GRAD) {
+                    float dD_dcs = 0.f;
+                    if (cs >= lo && cs <= hi) dD_dcs = -57.29577951308232f / sqrtf(1.f - cc * cc);
+                    const float sgn = du > 0.f ? 1.f : (du < 0.f ? -1.f : 0.f);
+                    const float dcs_du1 = -cv1 * cv2 * sinf(adu) * sgn;
+                    const float dcs_dv1 = cv1 * sv2 - sv1 * cv2 * cosf(adu);
+                    const float dU_dl = (1.f - tu * tu) * g.span * g.grid_az;
+                    const float dV_dl = (vraw >= -90.f && vraw <= 90.f) ? (1.f - tv * tv) * g.span * g.grid_el : 0.f;
+                    gu = dD_dcs * dcs_du1 * 0.017453292519943295f * dU_dl;
+                    gv = dD_dcs * dcs_dv1 * 0.017453292519943295f * dV_dl;
+                    if (dist) dist[(size_t)m * g.A + a] = D;
+                }
             }
         }
     }
@@ -132,10 +168,12 @@ __global__ __launch_bounds__(256) void loss_assign_kernel(const float *__restric
         if (bits & 1u) {          // angular term uses the first threshold only (loss.py:241-243)
             my_sum = D / 180.f;
             my_pairs = 1;
-            // several targets can share an anchor: their gradients are summed in 32.32 fixed point, so the
-            // result does not depend on the order the atomics land in (bit-reproducible training steps)
-            atomicAdd(&ang_grad[anchor * 2 + 0], to_fixed(gu / 180.f));
-            atomicAdd(&ang_grad[anchor * 2 + 1], to_fixed(gv / 180.f));
+            if constexpr (GRAD) {
+                // several targets can share an anchor: their gradients are summed in 32.32 fixed point, so the
+                // result does not depend on the order the atomics land in (bit-reproducible training steps)
+                atomicAdd(&ang_grad[anchor * 2 + 0], to_fixed(gu / 180.f));
+                atomicAdd(&ang_grad[anchor * 2 + 1], to_fixed(gv / 180.f));
+            }
         }
     }
     // distinct positives / pairs of this wave (same-address atomics are serialised by the memory system at ~12 ns each: one
@@ -155,37 +193,43 @@ __global__ __launch_bounds__(256) void loss_assign_kernel(const float *__restric
         red_cnt[wave][3] = cntp;
     }
     __syncthreads();
-    // per-workgroup results go to plain arrays; the LAST workgroup to arrive (one atomic per workgroup) adds the counts up
-    // in a fixed order and publishes them in the header
-    unsigned *cnt_partial = reinterpret_cast<unsigned *>(ang_partial + LOSS_ASSIGN_BLOCKS);
+    // per-workgroup results go to plain arrays, ang_partial [count][LOSS_ASSIGN_BLOCKS] and behind it the counts
+    // [count][LOSS_ASSIGN_BLOCKS][4].  !GRAD: the final kernel adds the counts up.  GRAD: the main kernel needs them, so the LAST
+    // workgroup to arrive (one atomic per workgroup) adds them up in a fixed order and publishes them in the header
+    unsigned *cnt_partial = reinterpret_cast<unsigned *>(ang_partial + (size_t)u.count * LOSS_ASSIGN_BLOCKS) +
+                            (size_t)u.idx * LOSS_ASSIGN_BLOCKS * 4;
+    ang_partial += (size_t)u.idx * LOSS_ASSIGN_BLOCKS;
     if (threadIdx.x < 4)
         cnt_partial[blockIdx.x * 4 + threadIdx.x] = (unsigned)(red_cnt[0][threadIdx.x] + red_cnt[1][threadIdx.x] +
                                                                 red_cnt[2][threadIdx.x] + red_cnt[3][threadIdx.x]);
     if (threadIdx.x == 0) ang_partial[blockIdx.x] = red_sum[0] + red_sum[1] + red_sum[2] + red_sum[3];
-    __syncthreads();
-    if (threadIdx.x == 0) {        // ONE device-scope fence per workgroup (a fence costs 5-20 ns per wave on this multi-XCD part;
-        __threadfence();           // release is cumulative over the barrier: it also covers the stores of threads 1-3)
-        is_last = atomicAdd(&hdr[4], 1u) == gridDim.x - 1;
-    }
-    __syncthreads();
-    if (is_last) {
-        __threadfence();
-        unsigned t4[4] = {0u, 0u, 0u, 0u};
-        for (unsigned bk = threadIdx.x; bk < gridDim.x; bk += blockDim.x) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i)        // (device-scope loads: the other workgroups' stores, not a stale L1 line)
-                t4[i] += __hip_atomic_load(cnt_partial + 4 * bk + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {                  // integer sums: any order gives the same result
-            unsigned v = t4[i];
-            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-            if (lane == 0) red_cnt[wave][i] = (int)v;
+    if constexpr (GRAD) {
+        __shared__ bool is_last;
+        __syncthreads();
+        if (threadIdx.x == 0) {        // ONE device-scope fence per workgroup (a fence costs 5-20 ns per wave on this multi-XCD part;
+            __threadfence();           // release is cumulative over the barrier: it also covers the stores of threads 1-3)
+            is_last = atomicAdd(&hdr[4], 1u) == gridDim.x - 1;
         }
         __syncthreads();
-        if (threadIdx.x < 4)
-            hdr[threadIdx.x] = (unsigned)(red_cnt[0][threadIdx.x] + red_cnt[1][threadIdx.x] + red_cnt[2][threadIdx.x] +
-                                          red_cnt[3][threadIdx.x]);
+        if (is_last) {
+            __threadfence();
+            unsigned t4[4] = {0u, 0u, 0u, 0u};
+            for (unsigned bk = threadIdx.x; bk < gridDim.x; bk += blockDim.x) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i)        // (device-scope loads: the other workgroups' stores, not a stale L1 line)
+                    t4[i] += __hip_atomic_load(cnt_partial + 4 * bk + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {                  // integer sums: any order gives the same result
+                unsigned v = t4[i];
+                for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+                if (lane == 0) red_cnt[wave][i] = (int)v;
+            }
+            __syncthreads();
+            if (threadIdx.x < 4)
+                hdr[threadIdx.x] = (unsigned)(red_cnt[0][threadIdx.x] + red_cnt[1][threadIdx.x] + red_cnt[2][threadIdx.x] +
+                                              red_cnt[3][threadIdx.x]);
+        }
     }
 }
 
@@ -199,8 +243,11 @@ __device__ __forceinline__ float bce_grad_logit(float s, float y) {
 // LDS with coalesced 16-byte loads, one lane then owns one ANCHOR (row stride odd: conflict-free) -- a negative anchor costs
 // one sigmoid / log pair (its class and angle gradients are zero), a positive one the C class terms and the angular
 // gradient -- and the gradients leave through the same LDS tile with coalesced 16-byte stores.
+// GRAD: grid (workgroups); the weights of the gradient come from the header's counts, dlogit (optional) is written.  !GRAD: grid
+// (workgroups of one clip, B): the same pass over clip b's NA anchors without the gradient; a clip without rows is skipped (its
+// loss is not formed).  Every clip's logits start on a 16-byte boundary (NA * CH % 4 == 0, checked by the caller).
 constexpr int LM_TILE = 256;
-template <bool PAD>
+template <bool PAD, bool GRAD>
 __global__ __launch_bounds__(256) void loss_main_kernel(const float *__restrict__ logit, LossGeom g,
                                                         const unsigned *__restrict__ hdr,
                                                         const unsigned *__restrict__ pos_bits,
@@ -208,28 +255,37 @@ __global__ __launch_bounds__(256) void loss_main_kernel(const float *__restrict_
                                                         const unsigned long long *__restrict__ ang_grad,
                                                         float *__restrict__ dlogit,
                                                         float *__restrict__ partial, long NA, long NA_total,
-                                                        float grad_scale) {
-    // NA_total: anchors of the whole (data-parallel) batch the header's counts refer to (== NA on one device)
+                                                        float grad_scale, const int *__restrict__ row_start, long cap) {
+    // NA: anchors of one unit.  NA_total: anchors of the whole (data-parallel) batch the header's counts refer to (== NA on one device)
     extern __shared__ __attribute__((aligned(16))) float tile[];      // [LM_TILE][CHP]
     __shared__ float red[4][9];
+    const LossUnit u = loss_unit<GRAD>(g, row_start, cap, blockIdx.y, 0);
+    if (!GRAD && u.M == 0) return;
     const int CH = g.C + 3;
     const int CHP = PAD ? CH + 1 : CH;              // PAD: CH is even -> odd row stride
     const int tid = threadIdx.x;
-    float npos[3], nneg[3];
+    const long cls_plane = NA * u.count;
+    logit += (size_t)u.idx * NA * CH;
+    pos_bits += (size_t)u.idx * NA;
+    cls_bits += (size_t)u.idx * NA;
+    partial += (size_t)u.idx * LOSS_MAIN_BLOCKS * 9;
+    float wpos[3] = {}, wneg[3] = {}, wcls[3] = {}, wang = 0.f;
+    if constexpr (GRAD) {
+        float npos[3], nneg[3];
 #pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        npos[i] = (float)hdr[i];
-        nneg[i] = (float)(NA_total - (long)hdr[i]);
-    }
-    const float npairs = (float)hdr[3];
-    float wpos[3], wneg[3], wcls[3];
+        for (int i = 0; i < 3; ++i) {
+            npos[i] = (float)hdr[i];
+            nneg[i] = (float)(NA_total - (long)hdr[i]);
+        }
+        const float npairs = (float)hdr[3];
 #pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        wpos[i] = g.gain_obj / (3.f * npos[i]);
-        wneg[i] = g.gain_nonobj / (3.f * nneg[i]);
-        wcls[i] = g.gain_cls / (3.f * npos[i] * (float)g.C);
+        for (int i = 0; i < 3; ++i) {
+            wpos[i] = g.gain_obj / (3.f * npos[i]);
+            wneg[i] = g.gain_nonobj / (3.f * nneg[i]);
+            wcls[i] = g.gain_cls / (3.f * npos[i] * (float)g.C);
+        }
+        wang = g.gain_ang / npairs;
     }
-    const float wang = g.gain_ang / npairs;
     float acc[9];
 #pragma unroll
     for (int i = 0; i < 9; ++i) acc[i] = 0.f;
@@ -267,7 +323,7 @@ __global__ __launch_bounds__(256) void loss_main_kernel(const float *__restrict_
                 const float s = sigmoidf_(x[0]);
                 const float lp = -fmaxf(logf(s), -100.f);           // -log(s), clamped like nn.BCELoss
                 const float lq = -fmaxf(logf(1.f - s), -100.f);     // -log(1-s)
-                const float g1 = bce_grad_logit(s, 1.f), g0 = bce_grad_logit(s, 0.f);
+                const float g1 = GRAD ? bce_grad_logit(s, 1.f) : 0.f, g0 = GRAD ? bce_grad_logit(s, 0.f) : 0.f;
                 float grad = 0.f;
 #pragma unroll
                 for (int i = 0; i < 3; ++i) {
@@ -279,17 +335,17 @@ __global__ __launch_bounds__(256) void loss_main_kernel(const float *__restrict_
                         grad += wneg[i] * g0;
                     }
                 }
-                x[0] = grad * grad_scale;
+                if constexpr (GRAD) x[0] = grad * grad_scale;
             }
             if (pb) {
                 unsigned cb[3];
 #pragma unroll
-                for (int i = 0; i < 3; ++i) cb[i] = (pb & (1u << i)) ? cls_bits[(size_t)i * NA + anchor] : 0u;
+                for (int i = 0; i < 3; ++i) cb[i] = (pb & (1u << i)) ? cls_bits[(size_t)i * cls_plane + anchor] : 0u;
                 for (int ch = 1; ch <= g.C; ++ch) {
                     const float s = sigmoidf_(x[ch]);
                     const float lp = -fmaxf(logf(s), -100.f);
                     const float lq = -fmaxf(logf(1.f - s), -100.f);
-                    const float g1 = bce_grad_logit(s, 1.f), g0 = bce_grad_logit(s, 0.f);
+                    const float g1 = GRAD ? bce_grad_logit(s, 1.f) : 0.f, g0 = GRAD ? bce_grad_logit(s, 0.f) : 0.f;
                     float grad = 0.f;
 #pragma unroll
                     for (int i = 0; i < 3; ++i) {
@@ -299,19 +355,21 @@ __global__ __launch_bounds__(256) void loss_main_kernel(const float *__restrict_
                             grad += wcls[i] * (yb ? g1 : g0);
                         }
                     }
-                    x[ch] = grad * grad_scale;
+                    if constexpr (GRAD) x[ch] = grad * grad_scale;
                 }
-                // (only anchors responsible at the first threshold ever received an angular gradient)
-                const ulonglong2 ag = (pb & 1u) ? *reinterpret_cast<const ulonglong2 *>(ang_grad + anchor * 2)
-                                                : make_ulonglong2(0ull, 0ull);
-                x[g.C + 1] = wang * from_fixed(ag.x) * grad_scale;
-                x[g.C + 2] = wang * from_fixed(ag.y) * grad_scale;
-            } else {
+                if constexpr (GRAD) {
+                    // (only anchors responsible at the first threshold ever received an angular gradient)
+                    const ulonglong2 ag = (pb & 1u) ? *reinterpret_cast<const ulonglong2 *>(ang_grad + anchor * 2)
+                                                    : make_ulonglong2(0ull, 0ull);
+                    x[g.C + 1] = wang * from_fixed(ag.x) * grad_scale;
+                    x[g.C + 2] = wang * from_fixed(ag.y) * grad_scale;
+                }
+            } else if constexpr (GRAD) {
                 for (int ch = 1; ch < CH; ++ch) x[ch] = 0.f;
             }
         }
         __syncthreads();
-        if (dlogit) {
+        if (GRAD && dlogit) {
             float *dst = dlogit + (size_t)a0 * CH;
             for (int i = tid; i < n4; i += 256) {
                 float4 v;
@@ -334,7 +392,7 @@ __global__ __launch_bounds__(256) void loss_main_kernel(const float *__restrict_
                 dst[e] = tile[r * CHP + (e - r * CH)];
             }
         }
-        __syncthreads();
+        if constexpr (GRAD) __syncthreads();        // (the stage-out reads other lanes' rows of the tile)
     }
     const int lane = tid & 63, wave = tid >> 6;
 #pragma unroll
@@ -347,31 +405,99 @@ __global__ __launch_bounds__(256) void loss_main_kernel(const float *__restrict_
         partial[(size_t)blockIdx.x * 9 + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
 }
 
+// One workgroup per unit combines its partial sums in double.  GRAD: grid (1); the four counts are the header's, NA is the batch
+// total and nang the assign grid.  !GRAD: grid (B); the counts of clip b are added up here from its assign workgroups' partials
+// (integers), NA is the clip's anchors, loss[b] and valid[b] are written (a clip without rows: 0 and 0).
+template <bool GRAD>
 __global__ __launch_bounds__(256) void loss_final_kernel(const float *__restrict__ partial, int nblk,
                                                          const float *__restrict__ ang_partial, int nang,
                                                          const unsigned *__restrict__ hdr, LossGeom g, long NA,
-                                                         float *__restrict__ loss) {
+                                                         float *__restrict__ loss, int *__restrict__ valid,
+                                                         const int *__restrict__ row_start, long cap) {
     __shared__ double red[256];
     __shared__ double tot[10];
+    const LossUnit u = loss_unit<GRAD>(g, row_start, cap, blockIdx.x, nang);
+    const unsigned *cnt = hdr;
+    if constexpr (!GRAD) {
+        __shared__ unsigned cred[4][4];
+        __shared__ unsigned csum[4];
+        if (u.M == 0) {
+            if (threadIdx.x == 0) {
+                loss[u.idx] = 0.f;
+                valid[u.idx] = 0;
+            }
+            return;
+        }
+        const unsigned *cnt_partial = reinterpret_cast<const unsigned *>(ang_partial + (size_t)u.count * LOSS_ASSIGN_BLOCKS) +
+                                      (size_t)u.idx * LOSS_ASSIGN_BLOCKS * 4;
+        ang_partial += (size_t)u.idx * LOSS_ASSIGN_BLOCKS;
+        partial += (size_t)u.idx * LOSS_MAIN_BLOCKS * 9;
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        unsigned t4[4] = {0u, 0u, 0u, 0u};
+        for (int bk = threadIdx.x; bk < u.nang; bk += 256) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) t4[i] += cnt_partial[4 * bk + i];
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            unsigned v = t4[i];
+            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+            if (lane == 0) cred[wave][i] = v;
+        }
+        __syncthreads();
+        if (threadIdx.x < 4) csum[threadIdx.x] = cred[0][threadIdx.x] + cred[1][threadIdx.x] + cred[2][threadIdx.x] + cred[3][threadIdx.x];
+        cnt = csum;
+    }
     const double s = block_colsum32(partial, nblk, 9, 0, 9, red);        // 9 BCE sums
     if ((threadIdx.x >> 5) == 0 && (threadIdx.x & 31) < 9) tot[threadIdx.x & 31] = s;
     double a = 0.0;
-    for (int b = threadIdx.x; b < nang; b += 256) a += (double)ang_partial[b];
+    for (int b = threadIdx.x; b < u.nang; b += 256) a += (double)ang_partial[b];
     red[threadIdx.x] = a;
     __syncthreads();
     if (threadIdx.x == 0) {
         double ang = 0.0;
         for (int k = 0; k < 256; ++k) ang += red[k];
-        double total = (double)g.gain_ang * ang / (double)hdr[3];
+        double total = (double)g.gain_ang * ang / (double)cnt[3];
         for (int i = 0; i < 3; ++i) {
-            const double np_ = (double)hdr[i], nn_ = (double)(NA - (long)hdr[i]);   // (NA here = the batch total)
+            const double np_ = (double)cnt[i], nn_ = (double)(NA - (long)cnt[i]);
             total += ((double)g.gain_obj * tot[i] / np_ + (double)g.gain_nonobj * tot[3 + i] / nn_ +
                       (double)g.gain_cls * tot[6 + i] / (np_ * (double)g.C)) / 3.0;
         }
-        loss[0] = (float)total;
+        loss[u.idx] = (float)total;
+        if constexpr (!GRAD) valid[u.idx] = 1;
     }
 }
 
+static LossGeom make_geom(int B, int T, int Gaz, int Gel, int A, int C, int M, const float *thr_host, const float *gains_host,
+                          float grid_az, float grid_el, float g_overlap) {
+    LossGeom g;
+    g.B = B; g.T = T; g.Gaz = Gaz; g.Gel = Gel; g.A = A; g.C = C; g.M = M;
+    for (int i = 0; i < 3; ++i) g.thr[i] = thr_host[i];
+    g.gain_ang = gains_host[0]; g.gain_obj = gains_host[1]; g.gain_nonobj = gains_host[2]; g.gain_cls = gains_host[3];
+    g.grid_az = grid_az; g.grid_el = grid_el; g.span = 0.5f + g_overlap;
+    return g;
+}
+
+// main workgroups of one unit of NA anchors
+static int main_blocks(long NA) {
+    const long nb = (NA + LM_TILE - 1) / LM_TILE;
+    return (int)(nb > LOSS_MAIN_BLOCKS ? LOSS_MAIN_BLOCKS : nb);
+}
+
+// loss_main_kernel<PAD, GRAD> on `grid`: an even C + 3 takes the PAD form (one more float per LDS row, one more row)
+template <bool GRAD>
+static void launch_loss_main(dim3 grid, hipStream_t st, const float *logit, const LossGeom &g, const unsigned *hdr,
+                             const unsigned *pos_bits, const unsigned *cls_bits, const unsigned long long *ang_grad,
+                             float *dlogit, float *partial, long NA, long na_total, float grad_scale, const int *row_start,
+                             long cap) {
+    const int CH = g.C + 3;
+    if (CH & 1)
+        hipLaunchKernelGGL((loss_main_kernel<false, GRAD>), grid, dim3(256), (size_t)LM_TILE * CH * 4, st, logit, g, hdr, pos_bits,
+                           cls_bits, ang_grad, dlogit, partial, NA, na_total, grad_scale, row_start, cap);
+    else
+        hipLaunchKernelGGL((loss_main_kernel<true, GRAD>), grid, dim3(256), (size_t)(LM_TILE + 1) * (CH + 1) * 4, st, logit, g, hdr,
+                           pos_bits, cls_bits, ang_grad, dlogit, partial, NA, na_total, grad_scale, row_start, cap);
+}
 
 }  // namespace adyolo
 
@@ -400,11 +526,7 @@ extern "C" int adyolo_loss_phase(const float *logit, const float *target, float 
     const long NA = (long)B * T * Gaz * Gel * A;
     ADYOLO_REQUIRE((phases & ~3) == 0 && phases != 0 && (na_total == 0 || na_total >= NA), ADYOLO_EINVAL, "loss: bad phases / na_total");
     if (na_total == 0) na_total = NA;
-    LossGeom g;
-    g.B = B; g.T = T; g.Gaz = Gaz; g.Gel = Gel; g.A = A; g.C = C; g.M = M;
-    for (int i = 0; i < 3; ++i) g.thr[i] = thr_host[i];
-    g.gain_ang = gains_host[0]; g.gain_obj = gains_host[1]; g.gain_nonobj = gains_host[2]; g.gain_cls = gains_host[3];
-    g.grid_az = grid_az; g.grid_el = grid_el; g.span = 0.5f + g_overlap;
+    const LossGeom g = make_geom(B, T, Gaz, Gel, A, C, M, thr_host, gains_host, grid_az, grid_el, g_overlap);
 
     unsigned *hdr = reinterpret_cast<unsigned *>(ws);
     unsigned *pos_bits = hdr + LOSS_HDR;
@@ -418,25 +540,19 @@ extern "C" int adyolo_loss_phase(const float *logit, const float *target, float 
     if (phases & 1) {
         rc = fill32(ws, 0u, (size_t)(LOSS_HDR + 8 * NA), st);             // (a kernel, not a memset node: see common.hpp)
         if (rc) return rc;
-        hipLaunchKernelGGL(loss_assign_kernel, dim3(nang), dim3(256), 0, st, logit, target, g, hdr, pos_bits, cls_bits,
-                           ang_grad, ang_partial, dist, NA);
+        hipLaunchKernelGGL(loss_assign_kernel<true>, dim3(nang), dim3(256), 0, st, logit, target, g, hdr, pos_bits, cls_bits,
+                           ang_grad, ang_partial, dist, NA, nullptr, 0);
         rc = check_launch("loss_assign");
         if (rc) return rc;
     }
     if (phases & 2) {
-        long nb = (NA + LM_TILE - 1) / LM_TILE;
-        if (nb > LOSS_MAIN_BLOCKS) nb = LOSS_MAIN_BLOCKS;
-        const int CH = C + 3;
-        if (CH & 1)
-            hipLaunchKernelGGL(loss_main_kernel<false>, dim3((unsigned)nb), dim3(256), (size_t)LM_TILE * CH * 4, st, logit, g,
-                               hdr, pos_bits, cls_bits, ang_grad, dlogit, partial, NA, na_total, grad_scale);
-        else
-            hipLaunchKernelGGL(loss_main_kernel<true>, dim3((unsigned)nb), dim3(256), (size_t)(LM_TILE + 1) * (CH + 1) * 4, st,
-                               logit, g, hdr, pos_bits, cls_bits, ang_grad, dlogit, partial, NA, na_total, grad_scale);
+        const int nb = main_blocks(NA);
+        launch_loss_main<true>(dim3((unsigned)nb), st, logit, g, hdr, pos_bits, cls_bits, ang_grad, dlogit, partial, NA, na_total,
+                               grad_scale, nullptr, 0);
         rc = check_launch("loss_main");
         if (rc) return rc;
-        hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(256), 0, st, partial, (int)nb, ang_partial, nang, hdr, g,
-                           na_total, loss);
+        hipLaunchKernelGGL(loss_final_kernel<true>, dim3(1), dim3(256), 0, st, partial, nb, ang_partial, nang, hdr, g, na_total,
+                           loss, nullptr, nullptr, 0);
         rc = check_launch("loss_final");
     }
     return rc;
@@ -491,288 +607,19 @@ extern "C" int adyolo_yolo_decode(const float *logit, float *out, long n_frames,
 // ---- K8f: per-clip AD-YOLO loss, forward only (evaluation: reference src/test.py:33-60 runs batch 1, so every normaliser of
 // ADYOLOloss is per clip) ----
 // B clips of one batched forward pass in one assignment launch, one pass over the logits and one finalisation.  loss[b] carries
-// the bits adyolo_loss_fwd_bwd returns for clip b alone (its logits, its rows with b = 0, no dlogit): the grid has a clip
-// dimension, and inside a clip the rows and the anchor tiles are dealt to workgroups exactly as that call deals them (32 rows
-// per assign workgroup up to LOSS_ASSIGN_BLOCKS, LM_TILE anchors per main workgroup up to LOSS_MAIN_BLOCKS), every fp32 partial
-// sum is formed by the same expressions in the same order and combined in double in the same order.  Without a gradient nothing
-// needs the counts before the final sum: they leave as per-workgroup partials (no arrival counter, no header), and there is no
-// fixed-point gradient accumulation.
+// the bits adyolo_loss_fwd_bwd returns for clip b alone (its logits, its rows with b = 0, no dlogit).  The kernels are the !GRAD
+// instantiations of the training kernels above -- loss_assign_kernel<false>, loss_main_kernel<PAD, false>,
+// loss_final_kernel<false> against that call's loss_assign_kernel<true>, loss_main_kernel<PAD, true>, loss_final_kernel<true>
+// -- so one body holds the row decode and distance, the arg-min and threshold bits, the tile staging, the nine BCE sums, the
+// workgroup reductions and the combination in double.  What the two forms do not share is the normalisation unit (LossUnit: the
+// grid has a clip dimension, and inside a clip the rows and the anchor tiles are dealt to workgroups exactly as that call deals
+// them, 32 rows per assign workgroup up to LOSS_ASSIGN_BLOCKS, LM_TILE anchors per main workgroup up to LOSS_MAIN_BLOCKS) and
+// what GRAD switches on: the derivative chain, the dist store, the fixed-point gradient atomics, the arrival counter and the
+// header in the assignment; the weights, the gradient written into the tile and its stage-out to dlogit in the main pass; the
+// header as the source of the counts in the finalisation.  Without a gradient nothing needs the counts before the final sum:
+// they leave as per-workgroup partials and are added there.  A row counts only if its b column names the clip its range
+// belongs to.
 namespace adyolo {
-
-struct ClipRows {
-    int r0, M, nang;
-};
-
-// rows [row_start[b], row_start[b + 1]) of the target, clamped to its capacity
-__device__ __forceinline__ ClipRows clip_rows(const int *__restrict__ row_start, int b, long cap) {
-    long r0 = row_start[b], r1 = row_start[b + 1];
-    r1 = r1 < 0 ? 0 : (r1 > cap ? cap : r1);
-    r0 = r0 < 0 ? 0 : (r0 > r1 ? r1 : r0);
-    ClipRows c;
-    c.r0 = (int)r0;
-    c.M = (int)(r1 - r0);
-    c.nang = (c.M + 31) / 32;
-    if (c.nang > LOSS_ASSIGN_BLOCKS) c.nang = LOSS_ASSIGN_BLOCKS;
-    return c;
-}
-
-// grid (assign workgroups of the largest clip, B); workgroup (x, b) is workgroup x of clip b's own launch of nang workgroups
-// (x >= nang: nothing to do).  A row counts only if its b column names the clip its range belongs to.
-__global__ __launch_bounds__(256) void loss_assign_clip_kernel(const float *__restrict__ logit, const float *__restrict__ target,
-                                                               const int *__restrict__ row_start, long cap, LossGeom g,
-                                                               unsigned *__restrict__ pos_bits, unsigned *__restrict__ cls_bits,
-                                                               float *__restrict__ ang_partial,
-                                                               unsigned *__restrict__ cnt_partial, long NA_all) {
-    __shared__ float red_sum[4];
-    __shared__ int red_cnt[4][4];
-    const int clip = blockIdx.y;
-    const ClipRows cr = clip_rows(row_start, clip, cap);
-    if ((int)blockIdx.x >= cr.nang) return;
-    const int a = threadIdx.x & 7;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float blk_sum = 0.f;
-    int cnt0 = 0, cnt1 = 0, cnt2 = 0, cntp = 0;
-    const long nlanes = (long)cr.M * 8;
-    for (long gt = (long)blockIdx.x * blockDim.x + threadIdx.x; gt - threadIdx.x < nlanes; gt += (long)cr.nang * blockDim.x) {
-    const int m = (int)(gt >> 3);
-    float my_sum = 0.f;
-    int my_pairs = 0;
-    float D = INFINITY;
-    long cell = 0;
-    int cl = 0;
-    bool valid = false;
-    if (m < cr.M) {
-        const float *tr = target + (size_t)(cr.r0 + m) * 7;
-        const int b = (int)tr[0], t = (int)tr[1], gi = (int)tr[2], gj = (int)tr[3];
-        cl = (int)tr[4];
-        const float U = tr[5], V = tr[6];
-        if (b == clip && t >= 0 && t < g.T && gi >= 0 && gi < g.Gaz && gj >= 0 && gj < g.Gel && cl >= 0 && cl < g.C) {
-            valid = true;
-            cell = (((long)clip * g.T + t) * g.Gaz + gi) * g.Gel + gj;
-            if (a < g.A) {
-                const int CH = g.C + 3;
-                const float off_u = gi * g.grid_az - 180.f + 0.5f * g.grid_az;
-                const float off_v = gj * g.grid_el - 90.f + 0.5f * g.grid_el;
-                const float u2 = deg2rad_(U), v2 = deg2rad_(V);
-                const float sv2 = sinf(v2), cv2 = cosf(v2);
-                const float *lp = logit + ((size_t)cell * g.A + a) * CH + g.C + 1;
-                const float tu = tanhf(lp[0]), tv = tanhf(lp[1]);
-                float ud = tu * g.span * g.grid_az + off_u;
-                const float vraw = tv * g.span * g.grid_el + off_v;
-                const float vd = fminf(fmaxf(vraw, -90.f), 90.f);
-                if (ud >= 180.f) ud -= 360.f;
-                if (ud < -180.f) ud += 360.f;
-                const float u1 = deg2rad_(ud), v1 = deg2rad_(vd);
-                const float sv1 = sinf(v1), cv1 = cosf(v1);
-                const float du = u1 - u2, adu = fabsf(du);
-                const float cs = sv1 * sv2 + cv1 * cv2 * cosf(adu);
-                const float lo = -1.f + 1e-7f, hi = 1.f - 1e-7f;
-                const float cc = fminf(fmaxf(cs, lo), hi);
-                D = rad2deg_(acosf(cc));
-            }
-        }
-    }
-    float dmin = D;
-    int amin = a;
-#pragma unroll
-    for (int o = 4; o > 0; o >>= 1) {
-        const float od = __shfl_xor(dmin, o, 64);
-        const int oa = __shfl_xor(amin, o, 64);
-        if (od < dmin || (od == dmin && oa < amin)) {
-            dmin = od;
-            amin = oa;
-        }
-    }
-    unsigned bits = 0, fresh = 0;
-    if (valid && a < g.A) {
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-            if (D < g.thr[i] || a == amin) bits |= 1u << i;
-    }
-    if (bits) {
-        const long anchor = cell * g.A + a;
-        const unsigned old = atomicOr(&pos_bits[anchor], bits);
-        fresh = bits & ~old;
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-            if (bits & (1u << i)) atomicOr(&cls_bits[(size_t)i * NA_all + anchor], 1u << cl);
-        if (bits & 1u) {
-            my_sum = D / 180.f;
-            my_pairs = 1;
-        }
-    }
-    cnt0 += __popcll(__ballot(fresh & 1u));
-    cnt1 += __popcll(__ballot((fresh >> 1) & 1u));
-    cnt2 += __popcll(__ballot((fresh >> 2) & 1u));
-    cntp += __popcll(__ballot(my_pairs != 0));
-    blk_sum += my_sum;
-    }
-    blk_sum = wave_sum(blk_sum);
-    if (lane == 0) {
-        red_sum[wave] = blk_sum;
-        red_cnt[wave][0] = cnt0;
-        red_cnt[wave][1] = cnt1;
-        red_cnt[wave][2] = cnt2;
-        red_cnt[wave][3] = cntp;
-    }
-    __syncthreads();
-    const size_t slot = (size_t)clip * LOSS_ASSIGN_BLOCKS + blockIdx.x;
-    if (threadIdx.x < 4)
-        cnt_partial[slot * 4 + threadIdx.x] = (unsigned)(red_cnt[0][threadIdx.x] + red_cnt[1][threadIdx.x] +
-                                                         red_cnt[2][threadIdx.x] + red_cnt[3][threadIdx.x]);
-    if (threadIdx.x == 0) ang_partial[slot] = red_sum[0] + red_sum[1] + red_sum[2] + red_sum[3];
-}
-
-// grid (main workgroups of one clip, B): loss_main_kernel's pass over clip b's logits without the gradient -- the same tile
-// staging, the same nine sums per lane, wave and workgroup.  A clip without rows is skipped (its loss is not formed).
-template <bool PAD>
-__global__ __launch_bounds__(256) void loss_main_clip_kernel(const float *__restrict__ logit_all, LossGeom g,
-                                                             const int *__restrict__ row_start, long cap,
-                                                             const unsigned *__restrict__ pos_bits_all,
-                                                             const unsigned *__restrict__ cls_bits, float *__restrict__ partial_all,
-                                                             long NA, long NA_all) {
-    extern __shared__ __attribute__((aligned(16))) float tile[];      // [LM_TILE][CHP]
-    __shared__ float red[4][9];
-    const int clip = blockIdx.y;
-    if (clip_rows(row_start, clip, cap).M == 0) return;
-    const int CH = g.C + 3;
-    const int CHP = PAD ? CH + 1 : CH;
-    const int tid = threadIdx.x;
-    const float *logit = logit_all + (size_t)clip * NA * CH;          // NA * CH * 4 bytes per clip: 16-byte aligned when
-    const unsigned *pos_bits = pos_bits_all + (size_t)clip * NA;      // NA * CH % 4 == 0 (checked by the caller)
-    float *partial = partial_all + (size_t)clip * LOSS_MAIN_BLOCKS * 9;
-    float acc[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) acc[i] = 0.f;
-    const long ntiles = (NA + LM_TILE - 1) / LM_TILE;
-    for (long tl = blockIdx.x; tl < ntiles; tl += gridDim.x) {
-        const long a0 = tl * LM_TILE;
-        const int na = (int)((NA - a0) < LM_TILE ? (NA - a0) : LM_TILE);
-        const int nel = na * CH, n4 = nel >> 2;
-        const float *src = logit + (size_t)a0 * CH;
-        for (int i = tid; i < n4; i += 256) {
-            const float4 v = reinterpret_cast<const float4 *>(src)[i];
-            if (PAD) {
-                const unsigned e = 4u * i, r = e / (unsigned)CH, c = e - r * (unsigned)CH;
-                float *d = tile + r * CHP + c;
-                const float vv[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const unsigned ck = c + k;
-                    (ck < (unsigned)CH ? d + k : tile + (r + 1) * CHP + (ck - CH))[0] = vv[k];
-                }
-            } else {
-                reinterpret_cast<float4 *>(tile)[i] = v;
-            }
-        }
-        for (int e = 4 * n4 + tid; e < nel; e += 256) {
-            const int r = e / CH;
-            tile[r * CHP + (e - r * CH)] = src[e];
-        }
-        __syncthreads();
-        if (tid < na) {
-            const long anchor = a0 + tid;
-            const float *x = tile + tid * CHP;
-            const unsigned pb = pos_bits[anchor];
-            {
-                const float s = sigmoidf_(x[0]);
-                const float lp = -fmaxf(logf(s), -100.f);
-                const float lq = -fmaxf(logf(1.f - s), -100.f);
-#pragma unroll
-                for (int i = 0; i < 3; ++i) {
-                    if (pb & (1u << i))
-                        acc[i] += lp;
-                    else
-                        acc[3 + i] += lq;
-                }
-            }
-            if (pb) {
-                unsigned cb[3];
-#pragma unroll
-                for (int i = 0; i < 3; ++i)
-                    cb[i] = (pb & (1u << i)) ? cls_bits[(size_t)i * NA_all + (size_t)clip * NA + anchor] : 0u;
-                for (int ch = 1; ch <= g.C; ++ch) {
-                    const float s = sigmoidf_(x[ch]);
-                    const float lp = -fmaxf(logf(s), -100.f);
-                    const float lq = -fmaxf(logf(1.f - s), -100.f);
-#pragma unroll
-                    for (int i = 0; i < 3; ++i) {
-                        if (pb & (1u << i)) {
-                            const unsigned yb = (cb[i] >> (ch - 1)) & 1u;
-                            acc[6 + i] += yb ? lp : lq;
-                        }
-                    }
-                }
-            }
-        }
-        __syncthreads();
-    }
-    const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) {
-        const float v = wave_sum(acc[i]);
-        if (lane == 0) red[wave][i] = v;
-    }
-    __syncthreads();
-    if (tid < 9)
-        partial[(size_t)blockIdx.x * 9 + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
-}
-
-// grid (B): loss_final_kernel for clip b, with the four counts summed here from the assign workgroups' partials (integers)
-__global__ __launch_bounds__(256) void loss_final_clip_kernel(const float *__restrict__ partial_all, int nblk,
-                                                              const float *__restrict__ ang_partial_all,
-                                                              const unsigned *__restrict__ cnt_partial_all,
-                                                              const int *__restrict__ row_start, long cap, LossGeom g, long NA,
-                                                              float *__restrict__ loss, int *__restrict__ valid) {
-    __shared__ double red[256];
-    __shared__ double tot[10];
-    __shared__ unsigned cred[4][4];
-    __shared__ unsigned hdr[4];
-    const int clip = blockIdx.x;
-    const ClipRows cr = clip_rows(row_start, clip, cap);
-    if (cr.M == 0) {
-        if (threadIdx.x == 0) {
-            loss[clip] = 0.f;
-            valid[clip] = 0;
-        }
-        return;
-    }
-    const float *partial = partial_all + (size_t)clip * LOSS_MAIN_BLOCKS * 9;
-    const float *ang_partial = ang_partial_all + (size_t)clip * LOSS_ASSIGN_BLOCKS;
-    const unsigned *cnt_partial = cnt_partial_all + (size_t)clip * LOSS_ASSIGN_BLOCKS * 4;
-    const int nang = cr.nang, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned t4[4] = {0u, 0u, 0u, 0u};
-    for (int bk = threadIdx.x; bk < nang; bk += 256) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) t4[i] += cnt_partial[4 * bk + i];
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        unsigned v = t4[i];
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-        if (lane == 0) cred[wave][i] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < 4) hdr[threadIdx.x] = cred[0][threadIdx.x] + cred[1][threadIdx.x] + cred[2][threadIdx.x] + cred[3][threadIdx.x];
-    const double s = block_colsum32(partial, nblk, 9, 0, 9, red);        // 9 BCE sums
-    if ((threadIdx.x >> 5) == 0 && (threadIdx.x & 31) < 9) tot[threadIdx.x & 31] = s;
-    double a = 0.0;
-    for (int b = threadIdx.x; b < nang; b += 256) a += (double)ang_partial[b];
-    red[threadIdx.x] = a;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double ang = 0.0;
-        for (int k = 0; k < 256; ++k) ang += red[k];
-        double total = (double)g.gain_ang * ang / (double)hdr[3];
-        for (int i = 0; i < 3; ++i) {
-            const double np_ = (double)hdr[i], nn_ = (double)(NA - (long)hdr[i]);
-            total += ((double)g.gain_obj * tot[i] / np_ + (double)g.gain_nonobj * tot[3 + i] / nn_ +
-                      (double)g.gain_cls * tot[6 + i] / (np_ * (double)g.C)) / 3.0;
-        }
-        loss[clip] = (float)total;
-        valid[clip] = 1;
-    }
-}
 
 // one thread: acc[0] += loss[i] for the valid i in order, in float32 (the host loop's ``total + loss``); acc[1] += their count
 __global__ void loss_accumulate_kernel(const float *__restrict__ loss, const int *__restrict__ valid, int n,
@@ -818,38 +665,27 @@ extern "C" int adyolo_loss_per_clip(const float *logit, const float *target, con
     ADYOLO_REQUIRE(((uintptr_t)logit & 15) == 0 && (B == 1 || (NA * CH) % 4 == 0), ADYOLO_ENOSUP,
                    "loss_per_clip: a clip of %ld x %d logits does not start on a 16-byte boundary", NA, CH);
     hipStream_t st = as_stream(stream);
-    LossGeom g;
-    g.B = B; g.T = T; g.Gaz = Gaz; g.Gel = Gel; g.A = A; g.C = C; g.M = 0;
-    for (int i = 0; i < 3; ++i) g.thr[i] = thr_host[i];
-    g.gain_ang = gains_host[0]; g.gain_obj = gains_host[1]; g.gain_nonobj = gains_host[2]; g.gain_cls = gains_host[3];
-    g.grid_az = grid_az; g.grid_el = grid_el; g.span = 0.5f + g_overlap;
+    const LossGeom g = make_geom(B, T, Gaz, Gel, A, C, 0, thr_host, gains_host, grid_az, grid_el, g_overlap);
 
     unsigned *pos_bits = reinterpret_cast<unsigned *>(ws);
     unsigned *cls_bits = pos_bits + NA_all;
-    float *ang_partial = reinterpret_cast<float *>(cls_bits + 3 * NA_all);
-    unsigned *cnt_partial = reinterpret_cast<unsigned *>(ang_partial + (size_t)B * LOSS_ASSIGN_BLOCKS);
-    float *partial = reinterpret_cast<float *>(cnt_partial + (size_t)B * 4 * LOSS_ASSIGN_BLOCKS);
+    float *ang_partial = reinterpret_cast<float *>(cls_bits + 3 * NA_all);        // (cnt_partial follows it: 4 B words more per slot)
+    float *partial = ang_partial + (size_t)B * 5 * LOSS_ASSIGN_BLOCKS;
     int rc = fill32(ws, 0u, (size_t)(4 * NA_all), st);
     if (rc) return rc;
     int gx = cdiv(cap, 32);
     if (gx > LOSS_ASSIGN_BLOCKS) gx = LOSS_ASSIGN_BLOCKS;
-    hipLaunchKernelGGL(loss_assign_clip_kernel, dim3((unsigned)gx, (unsigned)B), dim3(256), 0, st, logit, target, row_start, cap,
-                       g, pos_bits, cls_bits, ang_partial, cnt_partial, NA_all);
+    hipLaunchKernelGGL(loss_assign_kernel<false>, dim3((unsigned)gx, (unsigned)B), dim3(256), 0, st, logit, target, g, nullptr,
+                       pos_bits, cls_bits, nullptr, ang_partial, nullptr, NA_all, row_start, cap);
     rc = check_launch("loss_assign_clip");
     if (rc) return rc;
-    long nb = (NA + LM_TILE - 1) / LM_TILE;
-    if (nb > LOSS_MAIN_BLOCKS) nb = LOSS_MAIN_BLOCKS;
-    if (CH & 1)
-        hipLaunchKernelGGL(loss_main_clip_kernel<false>, dim3((unsigned)nb, (unsigned)B), dim3(256), (size_t)LM_TILE * CH * 4, st,
-                           logit, g, row_start, cap, pos_bits, cls_bits, partial, NA, NA_all);
-    else
-        hipLaunchKernelGGL(loss_main_clip_kernel<true>, dim3((unsigned)nb, (unsigned)B), dim3(256),
-                           (size_t)(LM_TILE + 1) * (CH + 1) * 4, st, logit, g, row_start, cap, pos_bits, cls_bits, partial, NA,
-                           NA_all);
+    const int nb = main_blocks(NA);
+    launch_loss_main<false>(dim3((unsigned)nb, (unsigned)B), st, logit, g, nullptr, pos_bits, cls_bits, nullptr, nullptr, partial,
+                            NA, 0, 0.f, row_start, cap);
     rc = check_launch("loss_main_clip");
     if (rc) return rc;
-    hipLaunchKernelGGL(loss_final_clip_kernel, dim3((unsigned)B), dim3(256), 0, st, partial, (int)nb, ang_partial, cnt_partial,
-                       row_start, cap, g, NA, loss, valid);
+    hipLaunchKernelGGL(loss_final_kernel<false>, dim3((unsigned)B), dim3(256), 0, st, partial, nb, ang_partial, 0, nullptr, g, NA,
+                       loss, valid, row_start, cap);
     rc = check_launch("loss_final_clip");
     if (rc) return rc;
     if (acc) {

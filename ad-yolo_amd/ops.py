@@ -871,6 +871,12 @@ def counter_add_(counter, inc):
 
 
 # ---------------------------------------------------------------------------------------------- loss / optim
+def _thr_gains(thr, gains):
+    """The three thresholds and the four gains of the AD-YOLO loss as host float arrays, the way the entry points take them."""
+    return (ctypes.cast((ctypes.c_float * 3)(*[float(v) for v in thr]), ctypes.c_void_p),
+            ctypes.cast((ctypes.c_float * 4)(*[float(v) for v in gains]), ctypes.c_void_p))
+
+
 def adyolo_loss(logit, target, nb_classes, grid=(8, 4), anchors=5, thr=(45.0, 25.0, 10.0),
                 gains=(5.0, 1.0, 5.0, 3.0), grid_size=(45.0, 45.0), g_overlap=0.5, need_grad=True, grad_scale=1.0,
                 want_dist=False):
@@ -883,10 +889,9 @@ def adyolo_loss(logit, target, nb_classes, grid=(8, 4), anchors=5, thr=(45.0, 25
     loss = _new(logit, 1)
     dlogit = torch.empty_like(logit) if need_grad else None
     dist = _new(logit, m, anchors) if want_dist else None
-    thr_h = (ctypes.c_float * 3)(*[float(v) for v in thr])
-    gains_h = (ctypes.c_float * 4)(*[float(v) for v in gains])
+    thr_h, gains_h = _thr_gains(thr, gains)
     args = (_p(logit), _p(target), _p(ws), _p(loss), _p(dlogit), _p(dist), b, t, grid[0], grid[1],
-            anchors, nb_classes, m, ctypes.cast(thr_h, ctypes.c_void_p), ctypes.cast(gains_h, ctypes.c_void_p),
+            anchors, nb_classes, m, thr_h, gains_h,
             float(grid_size[0]), float(grid_size[1]), float(g_overlap), float(grad_scale))
     if EXACT.on:                # counts over the batch of all ranks between the assignment and the pass over the logits
         _c("adyolo_loss_phase", *args, 1, 0, _stream())
@@ -942,11 +947,10 @@ def adyolo_loss_per_clip(logit, target, row_start, nb_classes, grid=(8, 4), anch
     ws = _new(logit, words)
     loss = _new(logit, b)
     valid = torch.empty(b, dtype=torch.int32, device=logit.device)
-    thr_h = (ctypes.c_float * 3)(*[float(v) for v in thr])
-    gains_h = (ctypes.c_float * 4)(*[float(v) for v in gains])
+    thr_h, gains_h = _thr_gains(thr, gains)
     _c("adyolo_loss_per_clip", _p(logit), _p(target), _p(row_start), _p(ws), _p(loss), _p(valid), _p(acc), b, t, grid[0],
-       grid[1], anchors, nb_classes, target.shape[0], ctypes.cast(thr_h, ctypes.c_void_p),
-       ctypes.cast(gains_h, ctypes.c_void_p), float(grid_size[0]), float(grid_size[1]), float(g_overlap), _stream())
+       grid[1], anchors, nb_classes, target.shape[0], thr_h, gains_h, float(grid_size[0]), float(grid_size[1]),
+       float(g_overlap), _stream())
     return loss, valid
 
 

@@ -55,6 +55,65 @@ def _indexed_params(optimizer, model):
     return [(i, p) + tuple(flat.offsets[where[id(p)]]) for i, p in enumerate(params)]
 
 
+def _grouping(optimizer, params):
+    """-> [(the optimizer's group or None, [positions in ``params``])] in group order, and the torch id of every position:
+    torch numbers the parameters consecutively group by group, inside a group in the order they were handed over
+    (``model.parameters()`` order here).  Without parameter groups: one group, ids = positions."""
+    groups = getattr(optimizer, "groups", None)
+    if groups is None:
+        return [(None, list(range(len(params))))], list(range(len(params)))
+    members = [(g, list(g["params"])) for g in groups]
+    ids = [None] * len(params)
+    for k, i in enumerate(i for _, mem in members for i in mem):
+        ids[i] = k
+    return members, ids
+
+
+def _shape_of(groups):
+    return [len(g["params"]) for g in groups]
+
+
+def _match_groups(optimizer, params, sd):
+    """-> (file ids by position in ``params``, the file's groups to take ``lr`` / ``weight_decay`` from or None = keep the
+    optimizer's own).  File groups of the optimizer's sizes, in order: state goes through the ids.  A one-group file into a
+    grouped optimizer (fine-tuning from an ungrouped run): by ``model.parameters()`` order.  Anything else is refused."""
+    members, ids = _grouping(optimizer, params)
+    file_groups = sd["param_groups"]
+    mine, theirs = [len(mem) for _, mem in members], _shape_of(file_groups)
+    if sum(theirs) != len(params):
+        raise ValueError("optimizer state has %d parameters, the model %d" % (sum(theirs), len(params)))
+    if theirs == mine:
+        file_ids = [None] * len(params)
+        for (_, mem), fg in zip(members, file_groups):
+            for i, fid in zip(mem, fg["params"]):
+                file_ids[i] = fid
+        return file_ids, file_groups
+    if len(theirs) == 1:
+        return list(file_groups[0]["params"]), None
+    raise ValueError("optimizer state has parameter groups of sizes %s, this optimizer %s" % (theirs, mine))
+
+
+def _shared(file_groups, keys):
+    """the hyper-parameters the flat optimizers keep ONE of must agree over the file's groups"""
+    g0 = file_groups[0]
+    for g in file_groups[1:]:
+        for k in keys:
+            if g.get(k) != g0.get(k):
+                raise ValueError("optimizer state has per-group %s (%r and %r): only lr and weight_decay may differ between "
+                                 "groups" % (k, g0.get(k), g.get(k)))
+    return g0
+
+
+def _take_group_values(optimizer, file_groups):
+    """``lr`` / ``weight_decay``: the file's, group by group (``file_groups`` None: a grouped optimizer keeps its own)"""
+    if getattr(optimizer, "groups", None) is None:
+        optimizer.lr, optimizer.weight_decay = file_groups[0]["lr"], file_groups[0].get("weight_decay", 0.0)
+    elif file_groups is not None:
+        for g, fg in zip(optimizer.groups, file_groups):
+            g["lr"], g["weight_decay"] = float(fg["lr"]), float(fg.get("weight_decay", 0.0))
+        optimizer.lr, optimizer.weight_decay = optimizer.groups[0]["lr"], optimizer.groups[0]["weight_decay"]
+
+
 def _cpu_slice(buf, off, n, p):
     return buf[off:off + n].view(p.shape).detach().cpu().clone()
 
@@ -63,44 +122,52 @@ def optimizer_state_dict(optimizer, model):
     """The fused optimizer's state in the layout of its torch.optim counterpart (``optimizer.kind``): FusedAdam ->
     torch.optim.Adam, FusedAdamW -> torch.optim.AdamW (Adam's state, ``decoupled_weight_decay: True`` in the group), FusedSGD ->
     torch.optim.SGD (``momentum_buffer`` per parameter once a step with momentum was taken, no entries otherwise).  Indices
-    follow ``model.parameters()``.  ``clip_grad_norm`` is configuration, not state: it is not written."""
+    follow ``model.parameters()``; with parameter groups there is one torch group per group, each with its own ``lr`` and
+    ``weight_decay``, and torch's numbering: consecutive group by group, ``model.parameters()`` order inside a group.
+    ``clip_grad_norm`` is configuration, not state: it is not written."""
     params = _indexed_params(optimizer, model)
+    members, ids = _grouping(optimizer, params)
     kind = getattr(optimizer, "kind", "adam")
     state = {}
     if kind == "sgd":
         if optimizer.momentum != 0 and optimizer.step_count > 0:
             for i, p, off, n in params:
-                state[i] = {"momentum_buffer": _cpu_slice(optimizer.momentum_buffer, off, n, p)}
-        group = {"lr": optimizer.lr, "momentum": optimizer.momentum, "dampening": optimizer.dampening,
-                 "weight_decay": optimizer.weight_decay, "nesterov": optimizer.nesterov, "maximize": False, "foreach": None,
-                 "differentiable": False, "fused": None, "params": list(range(len(params)))}
-        return {"state": state, "param_groups": [group]}
-    for i, p, off, n in params:
-        if optimizer.step_count > 0:
-            state[i] = {"step": torch.tensor(float(optimizer.step_count)),
-                        "exp_avg": _cpu_slice(optimizer.exp_avg, off, n, p),
-                        "exp_avg_sq": _cpu_slice(optimizer.exp_avg_sq, off, n, p)}
-    group = {"lr": optimizer.lr, "betas": tuple(optimizer.betas), "eps": optimizer.eps,
-             "weight_decay": optimizer.weight_decay, "amsgrad": False, "maximize": False, "foreach": None,
-             "capturable": False, "differentiable": False, "fused": None}
-    if kind == "adamw":
-        group["decoupled_weight_decay"] = True
-    group["params"] = list(range(len(params)))
-    return {"state": state, "param_groups": [group]}
+                state[ids[i]] = {"momentum_buffer": _cpu_slice(optimizer.momentum_buffer, off, n, p)}
+    elif optimizer.step_count > 0:
+        for i, p, off, n in params:
+            state[ids[i]] = {"step": torch.tensor(float(optimizer.step_count)),
+                             "exp_avg": _cpu_slice(optimizer.exp_avg, off, n, p),
+                             "exp_avg_sq": _cpu_slice(optimizer.exp_avg_sq, off, n, p)}
+    if getattr(optimizer, "groups", None) is not None:
+        state = {k: state[k] for k in sorted(state)}
+    out = []
+    for g, mem in members:
+        lr, wd = (optimizer.lr, optimizer.weight_decay) if g is None else (g["lr"], g["weight_decay"])
+        if kind == "sgd":
+            group = {"lr": lr, "momentum": optimizer.momentum, "dampening": optimizer.dampening, "weight_decay": wd,
+                     "nesterov": optimizer.nesterov, "maximize": False, "foreach": None, "differentiable": False, "fused": None}
+        else:
+            group = {"lr": lr, "betas": tuple(optimizer.betas), "eps": optimizer.eps, "weight_decay": wd, "amsgrad": False,
+                     "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None}
+            if kind == "adamw":
+                group["decoupled_weight_decay"] = True
+        group["params"] = [ids[i] for i in mem]
+        out.append(group)
+    return {"state": state, "param_groups": out}
 
 
-def _load_sgd_state(optimizer, params, sd, g):
+def _load_sgd_state(optimizer, params, sd, g, file_ids, file_groups):
     """torch.optim.SGD's state holds no step count: whether the next step is "the first" (momentum buffer := gradient) is
     decided by the presence of buffers, and ``step_count`` -- from which the device-side flag is derived -- is set to agree."""
     if (g.get("momentum", 0.0) != 0) != (optimizer.momentum != 0):        # (the buffer exists or not since construction)
         raise ValueError("SGD state was written with momentum %r, this optimizer has %r"
                          % (g.get("momentum", 0.0), optimizer.momentum))
-    optimizer.lr, optimizer.weight_decay = g["lr"], g.get("weight_decay", 0.0)
+    _take_group_values(optimizer, file_groups)
     optimizer.momentum, optimizer.dampening = g.get("momentum", 0.0), g.get("dampening", 0.0)
     optimizer.nesterov = bool(g.get("nesterov", False))
     have = []
     for i, p, off, n in params:
-        st = sd["state"].get(g["params"][i], sd["state"].get(i))
+        st = sd["state"].get(file_ids[i], sd["state"].get(i) if len(sd["param_groups"]) == 1 else None)
         buf = None if st is None else st.get("momentum_buffer")
         have.append(buf is not None)
         if buf is None or optimizer.momentum == 0:
@@ -124,26 +191,29 @@ def _refresh_schedule(optimizer):
 
 
 def load_optimizer_state_dict(optimizer, model, sd):
+    """A file whose groups have the sizes of the optimizer's, in order, is taken group by group (state through the ids, ``lr``
+    and ``weight_decay`` per group from the file); a one-group file into a grouped optimizer is taken by
+    ``model.parameters()`` order and the optimizer keeps its own group values; any other grouping raises ValueError."""
     params = _indexed_params(optimizer, model)
-    g = sd["param_groups"][0]
-    if len(g["params"]) != len(params):
-        raise ValueError("optimizer state has %d parameters, the model %d" % (len(g["params"]), len(params)))
+    file_ids, file_groups = _match_groups(optimizer, params, sd)
     kind = getattr(optimizer, "kind", "adam")
     if kind == "sgd":
-        if "betas" in g:
+        if any("betas" in fg for fg in sd["param_groups"]):
             raise ValueError("an Adam-family optimizer state cannot be loaded into FusedSGD")
-        return _load_sgd_state(optimizer, params, sd, g)
-    if "betas" not in g:
+        g = _shared(sd["param_groups"], ("momentum", "dampening", "nesterov"))
+        return _load_sgd_state(optimizer, params, sd, g, file_ids, file_groups)
+    if any("betas" not in fg for fg in sd["param_groups"]):
         raise ValueError("an SGD optimizer state cannot be loaded into %s" % type(optimizer).__name__)
+    g = _shared(sd["param_groups"], ("betas", "eps", "amsgrad", "decoupled_weight_decay"))
     if kind == "adamw" and g.get("decoupled_weight_decay", True) is False:
         raise ValueError("a torch.optim.Adam state (coupled weight decay) cannot be loaded into FusedAdamW")
-    optimizer.lr, optimizer.betas, optimizer.eps = g["lr"], tuple(g["betas"]), g["eps"]
-    optimizer.weight_decay = g.get("weight_decay", 0.0)
+    optimizer.betas, optimizer.eps = tuple(g["betas"]), g["eps"]
+    _take_group_values(optimizer, file_groups)
     if g.get("amsgrad", False):
         raise NotImplementedError("amsgrad Adam state is not supported by the fused gfx950 Adam")
     steps = set()
     for i, p, off, n in params:
-        st = sd["state"].get(g["params"][i], sd["state"].get(i))
+        st = sd["state"].get(file_ids[i], sd["state"].get(i) if len(sd["param_groups"]) == 1 else None)
         if st is None:
             optimizer.exp_avg[off:off + n].zero_()
             optimizer.exp_avg_sq[off:off + n].zero_()

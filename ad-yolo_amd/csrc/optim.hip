@@ -52,6 +52,11 @@ enum {
 enum { SCHED_CONSTANT = 0, SCHED_STEP = 1, SCHED_MULTISTEP = 2, SCHED_EXPONENTIAL = 3, SCHED_COSINE = 4 };
 // sched_out: what the prep kernel derives for this step, float32
 enum { SOUT_LR = 0, SOUT_DECAY = 1, SOUT_EMA_W = 2, SOUT_EMA_FIRST = 3, SCHED_OUT_FLOATS = 4 };
+// Parameter groups (the *_groups entry points).  groups_dev: float64 (G, 2) {base rate, weight_decay}, written by the host
+// only.  groups_out: float32 (G, 4), what the prep kernel derives per group for this step.  The group map holds one byte per
+// element of the buffer: the element's group.
+enum { GOUT_LR = 0, GOUT_STEP = 1, GOUT_DECAY = 2, GOUT_WD = 3, GROUP_OUT_FLOATS = 4 };
+constexpr int OX_MAX_GROUPS = 16;
 
 static inline int update_grid(long n) {
     long g = ((n >> 2) + OX_THREADS - 1) / OX_THREADS;
@@ -94,10 +99,10 @@ __global__ __launch_bounds__(OX_THREADS) void grad_sumsq_kernel(const float *__r
 enum { PREP_ADAM = 0, PREP_SGD = 1, PREP_NORM = 2 };
 
 // lr(t) = base * warm(t) * main(e) in double, rounded to float once; t = 1 runs at the base rate (torch's convention when
-// scheduler.step() follows optimizer.step())
-__device__ static float sched_lr(const double *__restrict__ tb, unsigned long long step) {
+// scheduler.step() follows optimizer.step()).  base: tb[SCHED_BASE], or a parameter group's own base rate.
+__device__ static float sched_lr(const double *__restrict__ tb, unsigned long long step, double base) {
     const double t = (double)step + tb[SCHED_OFFSET];
-    const double base = tb[SCHED_BASE], W = tb[SCHED_WARMUP], s0 = tb[SCHED_START];
+    const double W = tb[SCHED_WARMUP], s0 = tb[SCHED_START];
     const double e = floor((t - 1.0) / tb[SCHED_EVERY]);
     const double warm = W > 0.0 ? s0 + (1.0 - s0) * fmin(t - 1.0, W) / W : 1.0;
     double main_f = 1.0;
@@ -124,17 +129,36 @@ __device__ static float sched_lr(const double *__restrict__ tb, unsigned long lo
 // one workgroup of OX_THREADS.  partials == nullptr: clipping off (st[3] = 1, st[2] untouched).  PREP_NORM: no counter, norm only.
 // sched != nullptr (the *_sched entry points): `lr` is ignored, the step's rate comes from the table and is written with
 // AdamW's decay and the EMA's weight to sched_out.
+// groups != nullptr (the *_groups entry points, which are scheduled forms): the rate is derived once per group from the group's
+// own base (a base of exactly 0 gives 0 without the closed form: cosine divides by the base) and written with what the update
+// needs to groups_out; `wd` is ignored, st[0] and sched_out keep group 0's values.
 __global__ __launch_bounds__(OX_THREADS) void optim_prep_kernel(unsigned long long *__restrict__ step, float *__restrict__ st,
                                                                 int kind, float lr, float beta1, float beta2,
                                                                 const double *__restrict__ partials, int nparts,
                                                                 float max_norm, const double *__restrict__ sched,
-                                                                float *__restrict__ sched_out, float wd) {
+                                                                float *__restrict__ sched_out, float wd,
+                                                                const double *__restrict__ groups,
+                                                                float *__restrict__ groups_out, int n_groups) {
     __shared__ double red[OX_THREADS];
     if (threadIdx.x == 0 && kind != PREP_NORM) {
         const unsigned long long s = *step + 1ull;
         *step = s;
+        if (groups != nullptr) {
+            const double bc1 = kind == PREP_ADAM ? 1.0 - pow((double)beta1, (double)s) : 1.0;
+            for (int k = n_groups - 1; k >= 0; --k) {          // group 0 last: lr and wd leave the loop as group 0's
+                const double base = groups[2 * k];
+                wd = (float)groups[2 * k + 1];
+                lr = base == 0.0 ? 0.f : sched_lr(sched, s, base);
+                float *go = groups_out + GROUP_OUT_FLOATS * k;
+                go[GOUT_LR] = lr;
+                go[GOUT_STEP] = kind == PREP_ADAM ? (float)((double)lr / bc1) : lr;
+                go[GOUT_DECAY] = (float)(1.0 - (double)lr * (double)wd);
+                go[GOUT_WD] = wd;
+            }
+            if (kind != PREP_ADAM) wd = 0.f;                   // sched_out's decay is AdamW's: sgd_step passes no wd either
+        }
         if (sched != nullptr) {
-            lr = sched_lr(sched, s);
+            if (groups == nullptr) lr = sched_lr(sched, s, sched[SCHED_BASE]);
             const double k = (double)s - 1.0 + sched[SCHED_EMA_OFFSET];       // EMA updates so far
             double keep = sched[SCHED_EMA_DECAY];
             if (sched[SCHED_EMA_WARMUP] != 0.0) keep = fmin(keep, (1.0 + k) / (10.0 + k));
@@ -318,6 +342,146 @@ __global__ __launch_bounds__(OX_THREADS) void sgd_update_kernel(float *__restric
     }
 }
 
+// ---------------------------------------------------------------------------------------------- parameter groups
+// The scheduled updates with a rate and a weight decay per parameter group: the same grid, float4 streams and n & 3 tail as
+// above, the same adam_one / sgd_one / ema_one per element (so a group's elements get the bits of the ungrouped kernel run on
+// them alone with the group's constants).  groups_out goes to LDS once per workgroup; a lane reads the map as one 32-bit word
+// per float4 and, where its four bytes agree (parameters are long runs: almost always), fetches one set of constants, else
+// one per element.  Indices are masked with OX_MAX_GROUPS - 1: no map value reads outside the table.
+__device__ __forceinline__ void load_group_table(float4 *tab, const float *__restrict__ groups_out, int n_groups) {
+    if (threadIdx.x < OX_MAX_GROUPS)
+        tab[threadIdx.x] = (int)threadIdx.x < n_groups ? reinterpret_cast<const float4 *>(groups_out)[threadIdx.x]
+                                                       : make_float4(0.f, 0.f, 1.f, 0.f);
+    __syncthreads();
+}
+
+__device__ __forceinline__ bool one_group(unsigned w) { return w == (w & 0xffu) * 0x01010101u; }
+
+template <bool DECOUPLED, bool EMA>
+__global__ __launch_bounds__(OX_THREADS) void adam_update_groups_kernel(float *__restrict__ p, const float *__restrict__ g,
+                                                                        float *__restrict__ m, float *__restrict__ v, long n,
+                                                                        float beta1, float beta2, float eps, float grad_scale,
+                                                                        const float *__restrict__ st,
+                                                                        const float *__restrict__ so, float *__restrict__ ema,
+                                                                        const float *__restrict__ groups_out, int n_groups,
+                                                                        const unsigned char *__restrict__ map) {
+    __shared__ float4 tab[OX_MAX_GROUPS];          // {rate, rate / bc1, decay, wd} per group
+    load_group_table(tab, groups_out, n_groups);
+    const float inv_sqrt_bc2 = st[1];
+    const float gs = grad_scale * st[3];
+    const float ew = EMA ? so[SOUT_EMA_W] : 0.f;
+    const bool efirst = EMA && so[SOUT_EMA_FIRST] != 0.f;
+    const long n4 = n >> 2;
+    float4 *p4 = reinterpret_cast<float4 *>(p), *m4 = reinterpret_cast<float4 *>(m), *v4 = reinterpret_cast<float4 *>(v);
+    float4 *e4 = reinterpret_cast<float4 *>(ema);
+    const float4 *g4 = reinterpret_cast<const float4 *>(g);
+    const unsigned *map4 = reinterpret_cast<const unsigned *>(map);
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        const unsigned w = map4[i];
+        float4 pv = p4[i], mv = m4[i], vv = v4[i];
+        const float4 gv = g4[i];
+        if (one_group(w)) {
+            const float4 c = tab[w & (OX_MAX_GROUPS - 1)];
+            adam_one<DECOUPLED>(pv.x, gv.x, mv.x, vv.x, gs, beta1, beta2, eps, c.w, c.z, c.y, inv_sqrt_bc2);
+            adam_one<DECOUPLED>(pv.y, gv.y, mv.y, vv.y, gs, beta1, beta2, eps, c.w, c.z, c.y, inv_sqrt_bc2);
+            adam_one<DECOUPLED>(pv.z, gv.z, mv.z, vv.z, gs, beta1, beta2, eps, c.w, c.z, c.y, inv_sqrt_bc2);
+            adam_one<DECOUPLED>(pv.w, gv.w, mv.w, vv.w, gs, beta1, beta2, eps, c.w, c.z, c.y, inv_sqrt_bc2);
+        } else {
+            const float4 c0 = tab[w & (OX_MAX_GROUPS - 1)], c1 = tab[(w >> 8) & (OX_MAX_GROUPS - 1)];
+            const float4 c2 = tab[(w >> 16) & (OX_MAX_GROUPS - 1)], c3 = tab[(w >> 24) & (OX_MAX_GROUPS - 1)];
+            adam_one<DECOUPLED>(pv.x, gv.x, mv.x, vv.x, gs, beta1, beta2, eps, c0.w, c0.z, c0.y, inv_sqrt_bc2);
+            adam_one<DECOUPLED>(pv.y, gv.y, mv.y, vv.y, gs, beta1, beta2, eps, c1.w, c1.z, c1.y, inv_sqrt_bc2);
+            adam_one<DECOUPLED>(pv.z, gv.z, mv.z, vv.z, gs, beta1, beta2, eps, c2.w, c2.z, c2.y, inv_sqrt_bc2);
+            adam_one<DECOUPLED>(pv.w, gv.w, mv.w, vv.w, gs, beta1, beta2, eps, c3.w, c3.z, c3.y, inv_sqrt_bc2);
+        }
+        p4[i] = pv;
+        m4[i] = mv;
+        v4[i] = vv;
+        if (EMA) {
+            float4 ev = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (!efirst) ev = e4[i];
+            ema_one(ev.x, pv.x, ew, efirst);
+            ema_one(ev.y, pv.y, ew, efirst);
+            ema_one(ev.z, pv.z, ew, efirst);
+            ema_one(ev.w, pv.w, ew, efirst);
+            e4[i] = ev;
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const long i = n4 * 4 + threadIdx.x;
+        const float4 c = tab[map[i] & (OX_MAX_GROUPS - 1)];
+        adam_one<DECOUPLED>(p[i], g[i], m[i], v[i], gs, beta1, beta2, eps, c.w, c.z, c.y, inv_sqrt_bc2);
+        if (EMA) {
+            float ev = efirst ? 0.f : ema[i];
+            ema_one(ev, p[i], ew, efirst);
+            ema[i] = ev;
+        }
+    }
+}
+
+template <bool MOM, bool EMA>
+__global__ __launch_bounds__(OX_THREADS) void sgd_update_groups_kernel(float *__restrict__ p, const float *__restrict__ g,
+                                                                       float *__restrict__ buf, long n, float mu, float keep,
+                                                                       int nesterov, float grad_scale,
+                                                                       const float *__restrict__ st,
+                                                                       const float *__restrict__ so, float *__restrict__ ema,
+                                                                       const float *__restrict__ groups_out, int n_groups,
+                                                                       const unsigned char *__restrict__ map) {
+    __shared__ float4 tab[OX_MAX_GROUPS];          // {rate, rate, decay (unused), wd} per group
+    load_group_table(tab, groups_out, n_groups);
+    const bool first = st[0] != 0.f, nest = nesterov != 0;
+    const float gs = grad_scale * st[3];
+    const float ew = EMA ? so[SOUT_EMA_W] : 0.f;
+    const bool efirst = EMA && so[SOUT_EMA_FIRST] != 0.f;
+    const long n4 = n >> 2;
+    float4 *p4 = reinterpret_cast<float4 *>(p), *b4 = reinterpret_cast<float4 *>(buf);
+    float4 *e4 = reinterpret_cast<float4 *>(ema);
+    const float4 *g4 = reinterpret_cast<const float4 *>(g);
+    const unsigned *map4 = reinterpret_cast<const unsigned *>(map);
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        const unsigned w = map4[i];
+        float4 pv = p4[i];
+        const float4 gv = g4[i];
+        float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (MOM && !first) bv = b4[i];
+        if (one_group(w)) {
+            const float4 c = tab[w & (OX_MAX_GROUPS - 1)];
+            sgd_one<MOM>(pv.x, gv.x, &bv.x, gs, c.x, c.w, mu, keep, nest, first);
+            sgd_one<MOM>(pv.y, gv.y, &bv.y, gs, c.x, c.w, mu, keep, nest, first);
+            sgd_one<MOM>(pv.z, gv.z, &bv.z, gs, c.x, c.w, mu, keep, nest, first);
+            sgd_one<MOM>(pv.w, gv.w, &bv.w, gs, c.x, c.w, mu, keep, nest, first);
+        } else {
+            const float4 c0 = tab[w & (OX_MAX_GROUPS - 1)], c1 = tab[(w >> 8) & (OX_MAX_GROUPS - 1)];
+            const float4 c2 = tab[(w >> 16) & (OX_MAX_GROUPS - 1)], c3 = tab[(w >> 24) & (OX_MAX_GROUPS - 1)];
+            sgd_one<MOM>(pv.x, gv.x, &bv.x, gs, c0.x, c0.w, mu, keep, nest, first);
+            sgd_one<MOM>(pv.y, gv.y, &bv.y, gs, c1.x, c1.w, mu, keep, nest, first);
+            sgd_one<MOM>(pv.z, gv.z, &bv.z, gs, c2.x, c2.w, mu, keep, nest, first);
+            sgd_one<MOM>(pv.w, gv.w, &bv.w, gs, c3.x, c3.w, mu, keep, nest, first);
+        }
+        p4[i] = pv;
+        if (MOM) b4[i] = bv;
+        if (EMA) {
+            float4 ev = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (!efirst) ev = e4[i];
+            ema_one(ev.x, pv.x, ew, efirst);
+            ema_one(ev.y, pv.y, ew, efirst);
+            ema_one(ev.z, pv.z, ew, efirst);
+            ema_one(ev.w, pv.w, ew, efirst);
+            e4[i] = ev;
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const long i = n4 * 4 + threadIdx.x;
+        const float4 c = tab[map[i] & (OX_MAX_GROUPS - 1)];
+        sgd_one<MOM>(p[i], g[i], MOM ? buf + i : nullptr, gs, c.x, c.w, mu, keep, nest, first);
+        if (EMA) {
+            float ev = efirst ? 0.f : ema[i];
+            ema_one(ev, p[i], ew, efirst);
+            ema[i] = ev;
+        }
+    }
+}
+
 static int launch_sumsq(const float *grad, long n, float grad_scale, double *partials, hipStream_t st) {
     hipLaunchKernelGGL(grad_sumsq_kernel, dim3(sumsq_grid(n)), dim3(OX_THREADS), 0, st, grad, n, grad_scale, partials);
     return check_launch("grad_sumsq");
@@ -325,9 +489,10 @@ static int launch_sumsq(const float *grad, long n, float grad_scale, double *par
 
 static int launch_prep(uint64_t *step_dev, float *st_dev, int kind, float lr, float beta1, float beta2, const double *partials,
                        long n, float max_norm, hipStream_t st, const double *sched = nullptr, float *sched_out = nullptr,
-                       float wd = 0.f) {
+                       float wd = 0.f, const double *groups = nullptr, float *groups_out = nullptr, int n_groups = 0) {
     hipLaunchKernelGGL(optim_prep_kernel, dim3(1), dim3(OX_THREADS), 0, st, reinterpret_cast<unsigned long long *>(step_dev),
-                       st_dev, kind, lr, beta1, beta2, partials, partials ? sumsq_grid(n) : 0, max_norm, sched, sched_out, wd);
+                       st_dev, kind, lr, beta1, beta2, partials, partials ? sumsq_grid(n) : 0, max_norm, sched, sched_out, wd,
+                       groups, groups_out, n_groups);
     return check_launch("optim_prep");
 }
 
@@ -366,6 +531,48 @@ static int sgd_step(float *param, const float *grad, float *momentum_buf, long n
                        n, lr, weight_decay, mom ? momentum : 0.f, keep, nesterov, grad_scale, (const float *)st_dev,
                        (const float *)sched_out, ema);
     return check_launch(what);
+}
+
+static int adam_step_groups(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, long n, float beta1, float beta2,
+                            float eps, int decoupled, uint64_t *step_dev, float *st_dev, double *partials, float max_norm,
+                            float grad_scale, const double *sched, float *sched_out, float *ema, const double *groups,
+                            float *groups_out, int n_groups, const unsigned char *map, hipStream_t st, const char *what) {
+    int rc;
+    if (partials && (rc = launch_sumsq(grad, n, grad_scale, partials, st))) return rc;
+    if ((rc = launch_prep(step_dev, st_dev, PREP_ADAM, 0.f, beta1, beta2, partials, n, max_norm, st, sched, sched_out, 0.f,
+                          groups, groups_out, n_groups)))
+        return rc;
+    auto kernel = decoupled ? adam_update_groups_kernel<true, false> : adam_update_groups_kernel<false, false>;
+    if (ema) kernel = decoupled ? adam_update_groups_kernel<true, true> : adam_update_groups_kernel<false, true>;
+    hipLaunchKernelGGL(kernel, dim3(update_grid(n)), dim3(OX_THREADS), 0, st, param, grad, exp_avg, exp_avg_sq, n, beta1, beta2,
+                       eps, grad_scale, (const float *)st_dev, (const float *)sched_out, ema, (const float *)groups_out, n_groups,
+                       map);
+    return check_launch(what);
+}
+
+static int sgd_step_groups(float *param, const float *grad, float *momentum_buf, long n, float momentum, float dampening,
+                           int nesterov, uint64_t *step_dev, float *st_dev, double *partials, float max_norm, float grad_scale,
+                           const double *sched, float *sched_out, float *ema, const double *groups, float *groups_out,
+                           int n_groups, const unsigned char *map, hipStream_t st, const char *what) {
+    int rc;
+    if (partials && (rc = launch_sumsq(grad, n, grad_scale, partials, st))) return rc;
+    if ((rc = launch_prep(step_dev, st_dev, PREP_SGD, 0.f, 0.f, 0.f, partials, n, max_norm, st, sched, sched_out, 0.f, groups,
+                          groups_out, n_groups)))
+        return rc;
+    const float keep = (float)(1.0 - (double)dampening);
+    const bool mom = momentum != 0.f;
+    auto kernel = mom ? sgd_update_groups_kernel<true, false> : sgd_update_groups_kernel<false, false>;
+    if (ema) kernel = mom ? sgd_update_groups_kernel<true, true> : sgd_update_groups_kernel<false, true>;
+    hipLaunchKernelGGL(kernel, dim3(update_grid(n)), dim3(OX_THREADS), 0, st, param, grad, mom ? momentum_buf : (float *)nullptr,
+                       n, mom ? momentum : 0.f, keep, nesterov, grad_scale, (const float *)st_dev, (const float *)sched_out, ema,
+                       (const float *)groups_out, n_groups, map);
+    return check_launch(what);
+}
+
+static inline bool groups_ok(const double *groups_dev, const float *groups_out, const unsigned char *map, int n_groups) {
+    return groups_dev && groups_out && map && n_groups >= 1 && n_groups <= OX_MAX_GROUPS &&
+           (reinterpret_cast<uintptr_t>(groups_dev) & 7) == 0 && aligned16(groups_out) &&
+           (reinterpret_cast<uintptr_t>(map) & 3) == 0;
 }
 
 }  // namespace adyolo
@@ -439,4 +646,40 @@ extern "C" int adyolo_sgd_step_sched_dev(float *param, const float *grad, float 
                    ADYOLO_EINVAL, "sgd_step_sched_dev: buffers not 16-byte aligned (or the table not 8-byte aligned)");
     return sgd_step(param, grad, momentum_buf, n, 0.f, weight_decay, momentum, dampening, nesterov, step_dev, st_dev, partials,
                     max_norm, grad_scale, sched_dev, sched_out, ema, as_stream(stream), "sgd_step_sched_dev");
+}
+
+extern "C" int adyolo_optim_max_groups(void) { return OX_MAX_GROUPS; }
+
+extern "C" int adyolo_adam_step_groups_dev(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, long n,
+                                           float beta1, float beta2, float eps, int decoupled, uint64_t *step_dev,
+                                           float *st_dev, double *partials, float max_norm, float grad_scale,
+                                           const double *sched_dev, float *sched_out, float *ema, const double *groups_dev,
+                                           float *groups_out, int n_groups, const unsigned char *group_map, void *stream) {
+    ADYOLO_REQUIRE(param && grad && exp_avg && exp_avg_sq && n > 0 && step_dev && st_dev && sched_dev && sched_out,
+                   ADYOLO_EINVAL, "adam_step_groups_dev: bad arguments");
+    ADYOLO_REQUIRE(aligned16(param) && aligned16(grad) && aligned16(exp_avg) && aligned16(exp_avg_sq) && aligned16(ema) &&
+                       (reinterpret_cast<uintptr_t>(sched_dev) & 7) == 0,
+                   ADYOLO_EINVAL, "adam_step_groups_dev: buffers not 16-byte aligned (or the table not 8-byte aligned)");
+    ADYOLO_REQUIRE(groups_ok(groups_dev, groups_out, group_map, n_groups), ADYOLO_EINVAL,
+                   "adam_step_groups_dev: 1 to 16 groups, groups_dev 8-byte, groups_out 16-byte and the map 4-byte aligned");
+    return adam_step_groups(param, grad, exp_avg, exp_avg_sq, n, beta1, beta2, eps, decoupled, step_dev, st_dev, partials,
+                            max_norm, grad_scale, sched_dev, sched_out, ema, groups_dev, groups_out, n_groups, group_map,
+                            as_stream(stream), "adam_step_groups_dev");
+}
+
+extern "C" int adyolo_sgd_step_groups_dev(float *param, const float *grad, float *momentum_buf, long n, float momentum,
+                                          float dampening, int nesterov, uint64_t *step_dev, float *st_dev, double *partials,
+                                          float max_norm, float grad_scale, const double *sched_dev, float *sched_out,
+                                          float *ema, const double *groups_dev, float *groups_out, int n_groups,
+                                          const unsigned char *group_map, void *stream) {
+    ADYOLO_REQUIRE(param && grad && n > 0 && step_dev && st_dev && (momentum == 0.f || momentum_buf) && sched_dev && sched_out,
+                   ADYOLO_EINVAL, "sgd_step_groups_dev: bad arguments");
+    ADYOLO_REQUIRE(aligned16(param) && aligned16(grad) && aligned16(momentum_buf) && aligned16(ema) &&
+                       (reinterpret_cast<uintptr_t>(sched_dev) & 7) == 0,
+                   ADYOLO_EINVAL, "sgd_step_groups_dev: buffers not 16-byte aligned (or the table not 8-byte aligned)");
+    ADYOLO_REQUIRE(groups_ok(groups_dev, groups_out, group_map, n_groups), ADYOLO_EINVAL,
+                   "sgd_step_groups_dev: 1 to 16 groups, groups_dev 8-byte, groups_out 16-byte and the map 4-byte aligned");
+    return sgd_step_groups(param, grad, momentum_buf, n, momentum, dampening, nesterov, step_dev, st_dev, partials, max_norm,
+                           grad_scale, sched_dev, sched_out, ema, groups_dev, groups_out, n_groups, group_map,
+                           as_stream(stream), "sgd_step_groups_dev");
 }

@@ -47,6 +47,7 @@ class FlatParameters:
     def __init__(self, module, reverse=True):
         params = [p for p in module.parameters() if p.requires_grad]
         self.module_params = params             # module.parameters() order (= torch.optim state_dict indexing)
+        self.names = [n for n, p in module.named_parameters() if p.requires_grad]     # their names, in the same order
         self.buffers = [b for b in module.buffers() if b.is_floating_point()]      # BatchNorm running statistics
         # backward produces gradients roughly in reverse registration order: put the last layers first so
         # that bucket 0 fills first

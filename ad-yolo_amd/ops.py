@@ -1273,6 +1273,56 @@ def sgd_step_sched_dev(param, grad, momentum_buf, step_dev, st_dev, sched_dev, s
        _max_norm("sgd_step_sched_dev", partials, max_norm), grad_scale, _p(sched_dev), _p(sched_out), _p(ema), _stream())
 
 
+# The scheduled forms with parameter groups (include/adyolo_hip.h): a base rate and a weight decay per group of elements
+OPTIM_MAX_GROUPS = 16             # adyolo_optim_max_groups()
+GROUP_OUT_FLOATS = 4              # per group in groups_out: {rate, rate / bc1 (Adam) or rate (SGD), AdamW decay, weight_decay}
+
+
+def _chk_groups(what, param, groups_dev, groups_out, group_map):
+    if (not groups_dev.is_cuda or groups_dev.dtype != torch.float64 or not groups_dev.is_contiguous() or groups_dev.dim() != 2
+            or groups_dev.shape[1] != 2 or not 1 <= groups_dev.shape[0] <= OPTIM_MAX_GROUPS):
+        raise _lib.AdyoloHipError("%s needs groups_dev (G, 2) contiguous float64 on the device, 1 <= G <= %d"
+                                  % (what, OPTIM_MAX_GROUPS))
+    _chk(groups_out)
+    if tuple(groups_out.shape) != (groups_dev.shape[0], GROUP_OUT_FLOATS):
+        raise _lib.AdyoloHipError("%s needs groups_out (%d, %d)" % (what, groups_dev.shape[0], GROUP_OUT_FLOATS))
+    if (not group_map.is_cuda or group_map.dtype != torch.uint8 or not group_map.is_contiguous()
+            or group_map.numel() != param.numel() or group_map.device != param.device):
+        raise _lib.AdyoloHipError("%s needs a group map of %d contiguous uint8 on the parameters' device"
+                                  % (what, param.numel()))
+    return int(groups_dev.shape[0])
+
+
+def adam_step_groups_dev(param, grad, exp_avg, exp_avg_sq, step_dev, st_dev, sched_dev, sched_out, groups_dev, groups_out,
+                         group_map, ema=None, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, partials=None, max_norm=None,
+                         decoupled=False):
+    """``adam_step_sched_dev`` with a base rate and a weight decay per parameter group: groups_dev (G, 2) float64
+    {base rate, weight_decay}, groups_out (G, ``GROUP_OUT_FLOATS``) float32 written every step (column 0: the groups' rates),
+    group_map uint8, one entry per element of param.  The norm and the clip coefficient stay global."""
+    _chk(param, grad, exp_avg, exp_avg_sq, st_dev)
+    _chk_optim_dev("adam_step_groups_dev", param.numel(), step_dev, st_dev, partials)
+    _chk_sched("adam_step_groups_dev", param, sched_dev, sched_out, ema)
+    ng = _chk_groups("adam_step_groups_dev", param, groups_dev, groups_out, group_map)
+    _c("adyolo_adam_step_groups_dev", _p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), betas[0], betas[1], eps,
+       int(bool(decoupled)), _p(step_dev), _p(st_dev), _p(partials), _max_norm("adam_step_groups_dev", partials, max_norm),
+       grad_scale, _p(sched_dev), _p(sched_out), _p(ema), _p(groups_dev), _p(groups_out), ng, _p(group_map), _stream())
+
+
+def sgd_step_groups_dev(param, grad, momentum_buf, step_dev, st_dev, sched_dev, sched_out, groups_dev, groups_out, group_map,
+                        ema=None, momentum=0.0, dampening=0.0, nesterov=False, grad_scale=1.0, partials=None, max_norm=None):
+    """``sgd_step_sched_dev`` with a base rate and a weight decay per parameter group (see ``adam_step_groups_dev``)."""
+    _chk(param, grad, momentum_buf, st_dev)
+    _chk_optim_dev("sgd_step_groups_dev", param.numel(), step_dev, st_dev, partials)
+    _chk_sched("sgd_step_groups_dev", param, sched_dev, sched_out, ema)
+    ng = _chk_groups("sgd_step_groups_dev", param, groups_dev, groups_out, group_map)
+    if momentum != 0.0 and momentum_buf is None:
+        raise _lib.AdyoloHipError("sgd_step_groups_dev with momentum needs a momentum buffer")
+    _c("adyolo_sgd_step_groups_dev", _p(param), _p(grad), _p(momentum_buf if momentum != 0.0 else None), param.numel(),
+       momentum, dampening, int(bool(nesterov)), _p(step_dev), _p(st_dev), _p(partials),
+       _max_norm("sgd_step_groups_dev", partials, max_norm), grad_scale, _p(sched_dev), _p(sched_out), _p(ema),
+       _p(groups_dev), _p(groups_out), ng, _p(group_map), _stream())
+
+
 def nchw_to_nhwc8(x):
     _chk(x)
     b, c, h, w = x.shape

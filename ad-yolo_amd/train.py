@@ -13,6 +13,7 @@ import torch
 from . import functional as Fn
 from . import lr_schedule as _sched
 from . import ops
+from . import param_groups as _pgroups
 from .dist import BucketedAllReduce, FlatParameters
 
 
@@ -46,7 +47,21 @@ class _FusedOptimizer:
     ema_decay (None = off): an exponential moving average of the parameters, ``ema`` (laid out like ``flat.flat``), updated by
     the update launch itself: a copy of the parameters after its first step, then ``ema += (p - ema) * (1 - decay_eff)`` with
     ``decay_eff = decay`` or, with ema_warmup, ``min(decay, (1 + k) / (10 + k))`` after k updates.  Without ``lr_schedule``
-    the rate is a constant schedule."""
+    the rate is a constant schedule.
+
+    param_groups (None or empty = off: the entry points above with their arguments, nothing more allocated): resolved
+    parameter groups, ``[{name, lr, weight_decay, params}]`` with ``params`` the members' indices in ``flat.module_params``
+    (``param_groups.resolve`` makes them from ``train_config['param_groups']``).  Every group has its own base rate and weight
+    decay; the schedule (constant without ``lr_schedule``), the counter, the clip -- ONE norm over all groups, as
+    ``clip_grad_norm_(model.parameters())`` gives -- and the EMA are shared.  The step is then ``ops.*_step_groups_dev``: the
+    prep kernel derives every group's rate from ``groups_dev`` (float64 (G, 2) {base rate, weight decay}, written by the host
+    only) into ``groups_out``, and the update launch looks every element's group up in ``group_map`` (uint8, one entry per
+    element of ``flat.flat``; a function of the layout alone, so identical on every rank).  ``groups`` lists
+    ``{name, lr, weight_decay, params}``; ``current_lrs`` is a device view of the G rates the last step used; ``lr_at(t, group)``
+    mirrors them on the host; ``set_lr(x, group=)`` / ``set_weight_decay(x, group=)`` (index or name) rewrite ``groups_dev``
+    and hold from the next step on, eager or replayed -- a group built with rate 0 and decay 0 keeps its parameters bit for
+    bit (its moments still move, its gradient still counts in the norm) until ``set_lr`` releases it.  ``lr`` and
+    ``weight_decay`` mirror group 0's."""
 
     kind = None                     # 'adam' | 'adamw' | 'sgd': the torch.optim layout ``checkpoint`` reads and writes
 
@@ -86,14 +101,20 @@ class _FusedOptimizer:
     sched_config = sched_dev = sched_out = current_lr = ema = ema_decay = None
     ema_warmup = False
     _sched_offset = _ema_offset = 0
+    groups = group_map = groups_dev = groups_out = current_lrs = None
 
-    def _init_sched(self, lr_schedule, ema_decay, ema_warmup):
+    def _init_sched(self, lr_schedule, ema_decay, ema_warmup, param_groups=None):
+        if param_groups:
+            self.groups = _pgroups.check(param_groups, self.flat)
+            self.lr, self.weight_decay = self.groups[0]["lr"], self.groups[0]["weight_decay"]
+            lr_schedule = {"name": "constant"} if lr_schedule is None else lr_schedule
         if lr_schedule is None and ema_decay is None:
             if ema_warmup:
                 raise ValueError("ema_warmup without ema_decay")
             return
         self.sched_config = _sched.normalise({"name": "constant"} if lr_schedule is None else lr_schedule)
-        _sched.check_base(self.sched_config, self.lr)
+        if self.groups is None:
+            _sched.check_base(self.sched_config, self.lr)
         self.ema_decay = None if ema_decay is None else _sched.check_ema_decay(ema_decay)
         self.ema_warmup = bool(ema_warmup)
         if self.ema_warmup and self.ema_decay is None:
@@ -104,13 +125,43 @@ class _FusedOptimizer:
         self.current_lr = self.sched_out[0:1]
         if self.ema_decay is not None:
             self.ema = torch.zeros_like(self.flat.flat)
+        if self.groups is not None:
+            self.group_map = _pgroups.group_map(self.groups, self.flat)
+            self.groups_dev = torch.zeros(len(self.groups), 2, dtype=torch.float64, device=dev)
+            self.groups_out = torch.zeros(len(self.groups), ops.GROUP_OUT_FLOATS, dtype=torch.float32, device=dev)
+            self.current_lrs = self.groups_out[:, 0]
         self._write_table()
 
+    def _table_for(self, base):
+        """the schedule table with ``base`` as its rate.  A group's rate may be 0 under every schedule (the device then skips
+        the closed form, and so does ``lr_at``): its table is built around a stand-in of 1."""
+        zero = self.groups is not None and float(base) == 0.0
+        tb = _sched.table(self.sched_config, 1.0 if zero else base, self._sched_offset, self.ema_decay, self.ema_warmup,
+                          self._ema_offset)
+        if zero:
+            tb[ops.SCHED_BASE] = 0.0
+        return tb
+
     def _write_table(self):
-        """(re)write ``sched_dev`` from the host's values: construction, ``set_lr``, ``load_state_dict``"""
-        self._table = _sched.table(self.sched_config, self.lr, self._sched_offset, self.ema_decay, self.ema_warmup,
-                                   self._ema_offset)
+        """(re)write ``sched_dev`` (and ``groups_dev``) from the host's values: construction, ``set_lr``, ``load_state_dict``"""
+        if self.groups is not None:
+            for g in self.groups:
+                self._table_for(g["lr"])                                      # (refuses what the schedule cannot run)
+            self.groups[0]["lr"], self.groups[0]["weight_decay"] = float(self.lr), float(self.weight_decay)
+            self.groups_dev.copy_(torch.tensor([[g["lr"], float(torch.tensor(g["weight_decay"], dtype=torch.float32))]
+                                                for g in self.groups], dtype=torch.float64))
+        self._table = self._table_for(self.lr)
         self.sched_dev.copy_(torch.tensor(self._table, dtype=torch.float64))
+
+    def _group_index(self, group):
+        if self.groups is None:
+            raise ValueError("this optimizer was built without param_groups")
+        if isinstance(group, int) and not isinstance(group, bool) and 0 <= group < len(self.groups):
+            return group
+        for k, g in enumerate(self.groups):
+            if g["name"] == group and not isinstance(group, bool):
+                return k
+        raise ValueError("no parameter group %r (groups: %s)" % (group, [g["name"] for g in self.groups]))
 
     @property
     def sched_step(self):
@@ -121,23 +172,59 @@ class _FusedOptimizer:
     def ema_updates(self):
         return self._step_count + self._ema_offset if self.ema is not None else 0
 
-    def lr_at(self, t):
-        """the rate of schedule step t (1-based) as the device computes it: the closed form in double, rounded to float32"""
+    def lr_at(self, t, group=0):
+        """the rate of schedule step t (1-based) as the device computes it: the closed form in double, rounded to float32.
+        group (index or name; grouped optimizers only): whose rate -- a group whose base is 0 has rate 0.0 at every step"""
         if self.sched_dev is None:
             return _sched.lr_at(_sched.table(_sched.normalise({"name": "constant"}), self.lr), t)
-        return _sched.lr_at(self._table, t)
+        if self.groups is None:
+            return _sched.lr_at(self._table, t)
+        base = self.groups[self._group_index(group)]["lr"]
+        return 0.0 if base == 0.0 else _sched.lr_at(self._table_for(base), t)
 
-    def set_lr(self, lr):
+    def set_lr(self, lr, group=None):
         if self.sched_dev is None:
             raise ValueError("this optimizer was built without a schedule, its lr is a constant of the (recorded) step: "
                              "build it with lr_schedule: {name: constant} to change the rate between steps")
-        self.lr = _sched.check_base(self.sched_config, lr)
+        if self.groups is None:
+            if group is not None:
+                raise ValueError("this optimizer was built without param_groups")
+            self.lr = _sched.check_base(self.sched_config, lr)
+        else:
+            if group is None and len(self.groups) > 1:
+                raise ValueError("this optimizer has %d parameter groups: say which, set_lr(lr, group=index or name) (groups: %s)"
+                                 % (len(self.groups), [g["name"] for g in self.groups]))
+            k = self._group_index(0 if group is None else group)
+            lr = _pgroups._value(self.groups[k]["name"], "lr", lr)
+            self._table_for(lr)
+            self.groups[k]["lr"] = lr
+            if k == 0:
+                self.lr = lr
+        self._write_table()
+
+    def set_weight_decay(self, weight_decay, group=None):
+        """a new weight decay for one parameter group, from the next step on (grouped optimizers: elsewhere the decay is a
+        constant of the recorded step)"""
+        if self.groups is None:
+            raise ValueError("this optimizer was built without param_groups, its weight_decay is a constant of the (recorded) "
+                             "step")
+        if group is None and len(self.groups) > 1:
+            raise ValueError("this optimizer has %d parameter groups: say which, set_weight_decay(x, group=index or name)"
+                             % len(self.groups))
+        k = self._group_index(0 if group is None else group)
+        self.groups[k]["weight_decay"] = _pgroups._value(self.groups[k]["name"], "weight_decay", weight_decay)
+        if k == 0:
+            self.weight_decay = self.groups[k]["weight_decay"]
         self._write_table()
 
     def sched_state_dict(self):
-        """configuration, current base rate and clocks of the schedule / EMA (``checkpoint`` writes it beside the optimizer's)"""
-        return {"config": dict(self.sched_config), "base_lr": self.lr, "step": self.sched_step,
-                "ema_decay": self.ema_decay, "ema_warmup": self.ema_warmup, "ema_updates": self.ema_updates}
+        """configuration, current base rate(s) and clocks of the schedule / EMA (``checkpoint`` writes it beside the
+        optimizer's)"""
+        sd = {"config": dict(self.sched_config), "base_lr": self.lr, "step": self.sched_step,
+              "ema_decay": self.ema_decay, "ema_warmup": self.ema_warmup, "ema_updates": self.ema_updates}
+        if self.groups is not None:
+            sd["group_base_lrs"] = [g["lr"] for g in self.groups]
+        return sd
 
     def load_sched_state_dict(self, sd):
         """After ``load_state_dict`` (it sets ``step_count``, which the offsets refer to).  The schedule continues at the saved
@@ -145,7 +232,15 @@ class _FusedOptimizer:
         if self.sched_dev is None:
             raise ValueError("this optimizer was built without a schedule")
         self.sched_config = _sched.normalise(sd["config"])
-        self.lr = _sched.check_base(self.sched_config, sd["base_lr"])
+        if self.groups is None:
+            self.lr = _sched.check_base(self.sched_config, sd["base_lr"])
+        elif "group_base_lrs" in sd:
+            if len(sd["group_base_lrs"]) != len(self.groups):
+                raise ValueError("the schedule state has %d group rates, this optimizer %d groups"
+                                 % (len(sd["group_base_lrs"]), len(self.groups)))
+            for g, lr in zip(self.groups, sd["group_base_lrs"]):
+                g["lr"] = _pgroups._value(g["name"], "lr", lr)
+            self.lr = self.groups[0]["lr"]
         self._sched_offset = int(sd["step"]) - self._step_count
         if self.ema is not None:
             self._ema_offset = int(sd.get("ema_updates", 0)) - self._step_count
@@ -189,14 +284,19 @@ class FusedAdam(_FusedOptimizer):
     kind = "adam"
 
     def __init__(self, flat: FlatParameters, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_norm=None,
-                 lr_schedule=None, ema_decay=None, ema_warmup=False):
+                 lr_schedule=None, ema_decay=None, ema_warmup=False, param_groups=None):
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         self.exp_avg = torch.zeros_like(flat.flat)
         self.exp_avg_sq = torch.zeros_like(flat.flat)
         self._init_common(flat, max_norm)
-        self._init_sched(lr_schedule, ema_decay, ema_warmup)
+        self._init_sched(lr_schedule, ema_decay, ema_warmup, param_groups)
 
     def _launch(self, grad_scale):
+        if self.groups is not None:
+            return ops.adam_step_groups_dev(self.flat.flat, self.flat.flat_grad, self.exp_avg, self.exp_avg_sq, self.step_dev,
+                                            self.st_dev, self.sched_dev, self.sched_out, self.groups_dev, self.groups_out,
+                                            self.group_map, self.ema, self.betas, self.eps, grad_scale, self.clip_partials,
+                                            self.max_norm, decoupled=self.kind == "adamw")
         if self.sched_dev is not None:
             return ops.adam_step_sched_dev(self.flat.flat, self.flat.flat_grad, self.exp_avg, self.exp_avg_sq, self.step_dev,
                                            self.st_dev, self.sched_dev, self.sched_out, self.ema, self.betas, self.eps,
@@ -214,8 +314,8 @@ class FusedAdamW(FusedAdam):
     kind = "adamw"
 
     def __init__(self, flat: FlatParameters, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_norm=None,
-                 lr_schedule=None, ema_decay=None, ema_warmup=False):
-        super().__init__(flat, lr, betas, eps, weight_decay, max_norm, lr_schedule, ema_decay, ema_warmup)
+                 lr_schedule=None, ema_decay=None, ema_warmup=False, param_groups=None):
+        super().__init__(flat, lr, betas, eps, weight_decay, max_norm, lr_schedule, ema_decay, ema_warmup, param_groups)
 
 
 class FusedSGD(_FusedOptimizer):
@@ -229,14 +329,14 @@ class FusedSGD(_FusedOptimizer):
     kind = "sgd"
 
     def __init__(self, flat: FlatParameters, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False,
-                 max_norm=None, lr_schedule=None, ema_decay=None, ema_warmup=False):
+                 max_norm=None, lr_schedule=None, ema_decay=None, ema_warmup=False, param_groups=None):
         if nesterov and (momentum <= 0 or dampening != 0):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
         self._init_common(flat, max_norm)
         self.lr, self.momentum, self.dampening, self.weight_decay = lr, momentum, dampening, weight_decay
         self.nesterov = bool(nesterov)
         self.momentum_buffer = torch.zeros_like(flat.flat) if momentum != 0 else None
-        self._init_sched(lr_schedule, ema_decay, ema_warmup)
+        self._init_sched(lr_schedule, ema_decay, ema_warmup, param_groups)
 
     @property
     def first_step(self):
@@ -244,6 +344,11 @@ class FusedSGD(_FusedOptimizer):
         return self._step_count == 0
 
     def _launch(self, grad_scale):
+        if self.groups is not None:
+            return ops.sgd_step_groups_dev(self.flat.flat, self.flat.flat_grad, self.momentum_buffer, self.step_dev, self.st_dev,
+                                           self.sched_dev, self.sched_out, self.groups_dev, self.groups_out, self.group_map,
+                                           self.ema, self.momentum, self.dampening, self.nesterov, grad_scale,
+                                           self.clip_partials, self.max_norm)
         if self.sched_dev is not None:
             return ops.sgd_step_sched_dev(self.flat.flat, self.flat.flat_grad, self.momentum_buffer, self.step_dev, self.st_dev,
                                           self.sched_dev, self.sched_out, self.ema, self.weight_decay, self.momentum,
@@ -259,17 +364,24 @@ def get_optimizers(params: dict, flat: FlatParameters):
     (the max_norm of the reference's ``clip_grad_norm_`` line, train.py:54; absent or None = off); ``lr_schedule`` (a dict
     ``{name: constant | step | multistep | exponential | cosine, every, warmup_steps, warmup_start_factor, ...}``, see
     ``lr_schedule.py``; absent = the rate is a constant of the step), ``ema_decay`` (absent = no averaged weights) and
-    ``ema_warmup`` (default false)."""
+    ``ema_warmup`` (default false); ``param_groups`` (a list of at most 15 entries ``{name, match, ndim_max, lr,
+    weight_decay}``, see ``param_groups.py``; absent or empty = one rate and one decay for all parameters)."""
     tc = params["train_config"]
     name = tc.get("optim", "Adam")
+    if name not in ("Adam", "AdamW", "SGD"):
+        raise NotImplementedError(name)
     clip = tc.get("clip_grad_norm")
     extra = {"lr_schedule": tc.get("lr_schedule"), "ema_decay": tc.get("ema_decay"), "ema_warmup": tc.get("ema_warmup", False)}
+    lr, wd = tc.get("lr", 1e-3), tc.get("weight_decay", 1e-2 if name == "AdamW" else 0.0)
+    groups = _pgroups.resolve(tc.get("param_groups"), flat, lr, wd)
+    if groups is not None:
+        extra["param_groups"] = groups
     if name == "Adam":
-        return FusedAdam(flat, lr=tc.get("lr", 1e-3), weight_decay=tc.get("weight_decay", 0.0), max_norm=clip, **extra)
+        return FusedAdam(flat, lr=lr, weight_decay=wd, max_norm=clip, **extra)
     if name == "AdamW":
-        return FusedAdamW(flat, lr=tc.get("lr", 1e-3), weight_decay=tc.get("weight_decay", 1e-2), max_norm=clip, **extra)
+        return FusedAdamW(flat, lr=lr, weight_decay=wd, max_norm=clip, **extra)
     if name == "SGD":
-        return FusedSGD(flat, lr=tc.get("lr", 1e-3), weight_decay=tc.get("weight_decay", 0.0),
+        return FusedSGD(flat, lr=lr, weight_decay=wd,
                         momentum=tc.get("momentum", 0.0), dampening=tc.get("dampening", 0.0),
                         nesterov=tc.get("nesterov", False), max_norm=clip, **extra)
     raise NotImplementedError(name)

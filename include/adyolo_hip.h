@@ -736,6 +736,28 @@ int  adyolo_sgd_step_sched_dev(float *param, const float *grad, float *momentum_
                                float momentum, float dampening, int nesterov, uint64_t *step_dev, float *st_dev,
                                double *partials, float max_norm, float grad_scale, const double *sched_dev, float *sched_out,
                                float *ema, void *stream);
+/* The scheduled forms with parameter groups: a base rate and a weight decay per group of elements, everything else as above
+ * (one counter, one set of bias corrections, ONE norm over the whole buffer and one clip coefficient, one EMA).
+ *   groups_dev  n_groups x 2 doubles {base rate, weight_decay}, written by the host only (8-byte aligned); the weight decay
+ *               is rounded to float first, as the float argument of the calls above is.  sched_dev[1] is not read.
+ *   groups_out  n_groups x 4 floats written every step (16-byte aligned): {rate of this step (the closed form above with the
+ *               group's base, rounded to float once; a base of exactly 0 gives 0 under every schedule), rate / (1 - beta1^t)
+ *               (Adam / AdamW) or the rate again (SGD), AdamW's 1 - rate * weight_decay, weight_decay}
+ *   group_map   n bytes (4-byte aligned): the group of every element; values are taken modulo 16
+ *   n_groups    1 .. adyolo_optim_max_groups() (= 16)
+ * st_dev[0] and sched_out keep group 0's values.  An element is updated exactly as the calls above update it when they are
+ * given its group's base rate and weight decay: the same bits. */
+int  adyolo_optim_max_groups(void);
+int  adyolo_adam_step_groups_dev(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, long n, float beta1,
+                                 float beta2, float eps, int decoupled, uint64_t *step_dev, float *st_dev, double *partials,
+                                 float max_norm, float grad_scale, const double *sched_dev, float *sched_out, float *ema,
+                                 const double *groups_dev, float *groups_out, int n_groups, const unsigned char *group_map,
+                                 void *stream);
+int  adyolo_sgd_step_groups_dev(float *param, const float *grad, float *momentum_buf, long n, float momentum, float dampening,
+                                int nesterov, uint64_t *step_dev, float *st_dev, double *partials, float max_norm,
+                                float grad_scale, const double *sched_dev, float *sched_out, float *ema,
+                                const double *groups_dev, float *groups_out, int n_groups, const unsigned char *group_map,
+                                void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * K9a multi-head self-attention core, flash style on the exact-fp32 matrix cores (csrc/attention.hip).

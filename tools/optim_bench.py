@@ -3,11 +3,14 @@ up, repeated).
 
   step      one hipGraph-replayed TrainStep at 16 x 20 s (the reference's batch_size / chunk) and at 64 x 60 s (the bench shape)
             with 'Adam' (ops.adam_step_dev, the baseline), 'AdamW', 'SGD' (plain, as the reference calls it), 'Adam' with
-            clip_grad_norm 3, 'Adam' under a device-side lr_schedule (ops.adam_step_sched_dev) and the same with ema_decay
+            clip_grad_norm 3, 'Adam' under a device-side lr_schedule (ops.adam_step_sched_dev) and the same with ema_decay;
+            'AdamW' under the schedule without and with the no-decay parameter grouping (ops.adam_step_groups_dev)
   kernels   the optimizer launches alone on buffers of the real model's flat size (6.68 M floats): adam_step_dev (baseline),
             adamw_step_dev, sgd_step_dev without / with momentum, adam_step_dev with clipping, grad_norm_dev (sum of squares +
             prep); the scheduled forms adam / adamw / sgd_step_sched_dev (cosine with warm-up: the prep kernel's most expensive
-            table) and the scheduled forms with the EMA in the update launch (two more streams)
+            table) and the scheduled forms with the EMA in the update launch (two more streams); the grouped forms
+            adam / adamw (+ EMA) / sgd_step_groups_dev with the real model's ``ndim_max: 1`` group map (150 runs), each beside
+            its ungrouped scheduled counterpart
 
 At 16 x 20 s the trainers live side by side and alternate inside each repeat; at 64 x 60 s they are built one after the
 other (activations of one recorded step at a time).  The median of the repeats is reported (ms per call).
@@ -33,7 +36,12 @@ VARIANTS = {"adam": {"optim": "Adam"},
             "adam_clip3": {"optim": "Adam", "clip_grad_norm": 3.0},
             "adam_sched": {"optim": "Adam", "lr_schedule": {"name": "cosine", "T_max": 1000, "warmup_steps": 100}},
             "adam_sched_ema": {"optim": "Adam", "lr_schedule": {"name": "cosine", "T_max": 1000, "warmup_steps": 100},
-                               "ema_decay": 0.999}}
+                               "ema_decay": 0.999},
+            "adamw_sched": {"optim": "AdamW", "weight_decay": 0.01,
+                            "lr_schedule": {"name": "cosine", "T_max": 1000, "warmup_steps": 100}},
+            "adamw_sched_groups": {"optim": "AdamW", "weight_decay": 0.01,
+                                   "lr_schedule": {"name": "cosine", "T_max": 1000, "warmup_steps": 100},
+                                   "param_groups": [{"name": "no_decay", "ndim_max": 1, "weight_decay": 0.0}]}}
 
 
 def timed(fns, reps, iters):
@@ -95,6 +103,19 @@ def bench_step(b, seconds, reps, iters, together):
     return med, runs
 
 
+def real_group_map():
+    """the group map of the real model (se-resnet34 + BiGRU + the AD-YOLO head) under the no-decay rule ``ndim_max: 1``,
+    built on the CPU: -> (uint8 map of the padded flat buffer on the GPU, number of runs)"""
+    from adyolo_amd import param_groups
+    from adyolo_amd.dist import FlatParameters
+    from adyolo_amd.wrapper import WrapperModel
+    from __graft_entry__ import _params
+    flat = FlatParameters(WrapperModel((1, 7, 64, 64), (), _params("cpu")))
+    groups = param_groups.resolve([{"name": "no_decay", "ndim_max": 1, "weight_decay": 0.0}], flat, 1e-3, 1e-2)
+    m = param_groups.group_map(groups, flat)
+    return m.to("cuda:0"), 1 + int((m[1:] != m[:-1]).sum())
+
+
 def bench_kernels(reps, iters):
     from adyolo_amd import ops
     n = 6682096                                 # the flat buffer of se-resnet34 + the AD-YOLO head (6 682 093 padded to 4)
@@ -110,7 +131,21 @@ def bench_kernels(reps, iters):
     sched = torch.tensor(lr_schedule.table(cosine, 1e-3), dtype=torch.float64).to("cuda:0")
     sched_ema = torch.tensor(lr_schedule.table(cosine, 1e-3, ema_decay=0.999), dtype=torch.float64).to("cuda:0")
     out, ema = torch.zeros(ops.SCHED_OUT_FLOATS, device="cuda:0"), torch.zeros_like(p)
+    gmap, runs = real_group_map()
+    assert gmap.numel() == n, (gmap.numel(), n)
+    print("group map: %d runs, %d elements in group 1" % (runs, int((gmap == 1).sum())))
+    gdev = torch.tensor([[1e-3, 0.0], [1e-3, 0.0]], dtype=torch.float64).to("cuda:0")
+    gdev_w = torch.tensor([[1e-3, float(torch.tensor(1e-2, dtype=torch.float32))], [1e-3, 0.0]], dtype=torch.float64).to("cuda:0")
+    gout = torch.zeros(2, ops.GROUP_OUT_FLOATS, device="cuda:0")
     fns = {
+        "adam_step_groups_dev": lambda: ops.adam_step_groups_dev(p, grad, m, v, step_dev, st, sched, out, gdev, gout, gmap),
+        "adamw_step_groups_dev": lambda: ops.adam_step_groups_dev(p, grad, m, v, step_dev, st, sched, out, gdev_w, gout, gmap,
+                                                                  decoupled=True),
+        "adamw_step_sched_dev_ema": lambda: ops.adam_step_sched_dev(p, grad, m, v, step_dev, st, sched_ema, out, ema,
+                                                                    weight_decay=1e-2, decoupled=True),
+        "adamw_step_groups_dev_ema": lambda: ops.adam_step_groups_dev(p, grad, m, v, step_dev, st, sched_ema, out, gdev_w, gout,
+                                                                      gmap, ema, decoupled=True),
+        "sgd_step_groups_dev": lambda: ops.sgd_step_groups_dev(p, grad, None, step_dev, st, sched, out, gdev, gout, gmap),
         "adam_step_dev": lambda: ops.adam_step_dev(p, grad, m, v, step_dev, st),
         "adamw_step_dev": lambda: ops.adamw_step_dev(p, grad, m, v, step_dev, st),
         "sgd_step_dev": lambda: ops.sgd_step_dev(p, grad, None, step_dev, st),

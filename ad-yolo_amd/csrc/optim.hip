@@ -9,11 +9,17 @@
 //                       (SGD); st[2] = total_norm (fp32); st[3] = clip_coef = min(1, max_norm / (total_norm + 1e-6)) -- 1 when off
 //   *_update_kernel     the update, grad_scale * st[3] folded into the gradient (exact when st[3] = 1: the unclipped step is
 //                       the same kernel)
-// The *_sched entry points take the learning rate from the device instead of from an argument: the prep kernel evaluates a
-// closed-form schedule in double from the counter and a host-written table (SCHED_* below), rounds it to float ONCE and from
-// there treats it exactly as the plain entry points treat their `lr` argument, so a constant schedule gives the plain step's
-// bits.  They can also keep an exponential moving average of the parameters in the update launch (template flag EMA: two
-// more streams, none without it).
+// There is one update kernel per rule, adam_update_kernel<DECOUPLED, FORM, EMA> and sgd_update_kernel<MOM, FORM, EMA>.  FORM
+// says where an element's constants {rate, step size, decay, weight decay} come from, and nothing else differs between the
+// forms -- the walk, the per-element arithmetic and the EMA are one piece of source, so the forms agree bit for bit:
+//   FORM_ARG     the plain entry points: from the arguments
+//   FORM_SCHED   the *_sched entry points: the rate from the device.  The prep kernel evaluates a closed-form schedule in double
+//                from the counter and a host-written table (SCHED_* below), rounds it to float ONCE and from there treats it
+//                exactly as the plain entry points treat their `lr` argument: a constant schedule gives the plain step's bits
+//   FORM_GROUPS  the *_groups entry points: a scheduled form with a rate and a weight decay per parameter group, from a table in
+//                LDS through a byte map of the buffer; a group's elements get the bits of FORM_SCHED run on them alone
+// The scheduled forms can also keep an exponential moving average of the parameters in the update launch (template flag EMA:
+// two more streams, none without it).
 // st is 4 floats of device scratch.  All streams move 16 bytes per lane per access (pointers 16-byte aligned, the n & 3 tail
 // elements are done by workgroup 0); grids are capped and grid-stride.  Elements that are zero in parameter, gradient and state
 // (the padding of dist.FlatParameters) stay zero in every kernel.
@@ -200,6 +206,63 @@ __global__ __launch_bounds__(OX_THREADS) void optim_prep_kernel(unsigned long lo
     }
 }
 
+// ---------------------------------------------------------------------------------------------- what the update kernels share
+// An element's constants travel as one float4 in groups_out's layout {rate, step size, decay, weight decay} (GOUT_*): built
+// once per lane from arguments, st and sched_out in FORM_ARG and FORM_SCHED (wave-uniform; no LDS, no barrier), fetched per
+// vector or per element from the LDS copy of groups_out in FORM_GROUPS.
+enum { FORM_ARG = 0, FORM_SCHED = 1, FORM_GROUPS = 2 };
+
+// FORM_GROUPS: groups_out goes to LDS once per workgroup (rows past n_groups: rate 0, decay 1); the other forms have no table.
+template <int FORM>
+__device__ __forceinline__ const float4 *group_table(const float *__restrict__ groups_out, int n_groups) {
+    if constexpr (FORM == FORM_GROUPS) {
+        __shared__ float4 tab[OX_MAX_GROUPS];
+        if (threadIdx.x < OX_MAX_GROUPS)
+            tab[threadIdx.x] = (int)threadIdx.x < n_groups ? reinterpret_cast<const float4 *>(groups_out)[threadIdx.x]
+                                                           : make_float4(0.f, 0.f, 1.f, 0.f);
+        __syncthreads();
+        return tab;
+    } else {
+        return nullptr;
+    }
+}
+
+// A lane reads the map as one 32-bit word per float4 and, where its four bytes agree (parameters are long runs: almost always),
+// fetches one set of constants, else one per element.  Indices are masked: no map value reads outside the table.
+__device__ __forceinline__ bool one_group(unsigned w) { return w == (w & 0xffu) * 0x01010101u; }
+
+// the constants of the element whose map byte is the low byte of `byte`: the group's row, or the lane's own set `cu` where
+// there are no groups (and no table)
+template <int FORM>
+__device__ __forceinline__ float4 consts(const float4 *tab, unsigned byte, const float4 &cu) {
+    if constexpr (FORM == FORM_GROUPS) return tab[byte & (OX_MAX_GROUPS - 1)];
+    else return cu;
+}
+
+// The moving average of the parameters, after p is formed: a copy on its first update (the old value is not read), else
+// ema += (p - ema) * w as one fused multiply-add.
+__device__ __forceinline__ void ema_one(float &a, float p, float w, bool first) {
+#pragma clang fp contract(off)
+    a = first ? p : __builtin_fmaf(p - a, w, a);
+}
+
+// The EMA of vector i and of tail element i: a third read-write stream laid out like p.
+__device__ __forceinline__ void ema_four(float4 *__restrict__ e4, long i, const float4 &pv, float w, bool first) {
+    float4 ev = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (!first) ev = e4[i];
+    ema_one(ev.x, pv.x, w, first);
+    ema_one(ev.y, pv.y, w, first);
+    ema_one(ev.z, pv.z, w, first);
+    ema_one(ev.w, pv.w, w, first);
+    e4[i] = ev;
+}
+
+__device__ __forceinline__ void ema_tail(float *__restrict__ ema, long i, float p, float w, bool first) {
+    float ev = first ? 0.f : ema[i];
+    ema_one(ev, p, w, first);
+    ema[i] = ev;
+}
+
 // ---------------------------------------------------------------------------------------------- Adam / AdamW update
 // torch.optim.Adam:  m += (g - m)(1 - b1);  v = b2 v + (1 - b2) g^2;  p -= lr/(1 - b1^t) * m / (sqrt(v)/sqrt(1 - b2^t) + eps)
 // DECOUPLED = false: weight decay added to the gradient.
@@ -220,58 +283,65 @@ __device__ __forceinline__ void adam_one(float &p, float g, float &m, float &v, 
     p = __builtin_fmaf(-step_size, m / __builtin_fmaf(sqrtf(v), inv_sqrt_bc2, eps), pi);
 }
 
-// The moving average of the parameters, after p is formed: a copy on its first update (the old value is not read), else
-// ema += (p - ema) * w as one fused multiply-add.
-__device__ __forceinline__ void ema_one(float &a, float p, float w, bool first) {
-#pragma clang fp contract(off)
-    a = first ? p : __builtin_fmaf(p - a, w, a);
+// the four elements of a vector, each with its own constants
+template <bool DECOUPLED>
+__device__ __forceinline__ void adam_four(float4 &pv, const float4 &gv, float4 &mv, float4 &vv, float gs, float beta1,
+                                          float beta2, float eps, float inv_sqrt_bc2, const float4 &c0, const float4 &c1,
+                                          const float4 &c2, const float4 &c3) {
+    adam_one<DECOUPLED>(pv.x, gv.x, mv.x, vv.x, gs, beta1, beta2, eps, c0.w, c0.z, c0.y, inv_sqrt_bc2);
+    adam_one<DECOUPLED>(pv.y, gv.y, mv.y, vv.y, gs, beta1, beta2, eps, c1.w, c1.z, c1.y, inv_sqrt_bc2);
+    adam_one<DECOUPLED>(pv.z, gv.z, mv.z, vv.z, gs, beta1, beta2, eps, c2.w, c2.z, c2.y, inv_sqrt_bc2);
+    adam_one<DECOUPLED>(pv.w, gv.w, mv.w, vv.w, gs, beta1, beta2, eps, c3.w, c3.z, c3.y, inv_sqrt_bc2);
 }
 
-// SCHED: `decay` comes from so[SOUT_DECAY] (the prep kernel formed it from this step's rate) instead of the argument; the
-// rate itself is already inside st[0].  EMA (SCHED only): ema is a third read-write stream laid out like p.
-template <bool DECOUPLED, bool SCHED, bool EMA>
+// FORM_ARG: wd and decay are the arguments, the step size is st[0].  FORM_SCHED: decay is so[SOUT_DECAY] (the prep kernel
+// formed it from this step's rate); the rate itself is already inside st[0].  FORM_GROUPS: all three from the group's row.
+template <bool DECOUPLED, int FORM, bool EMA>
 __global__ __launch_bounds__(OX_THREADS) void adam_update_kernel(float *__restrict__ p, const float *__restrict__ g,
                                                                  float *__restrict__ m, float *__restrict__ v, long n,
                                                                  float beta1, float beta2, float eps, float wd, float decay,
                                                                  float grad_scale, const float *__restrict__ st,
-                                                                 const float *__restrict__ so, float *__restrict__ ema) {
-    const float step_size = st[0], inv_sqrt_bc2 = st[1];
+                                                                 const float *__restrict__ so, float *__restrict__ ema,
+                                                                 const float *__restrict__ groups_out, int n_groups,
+                                                                 const unsigned char *__restrict__ map) {
+    static_assert(FORM != FORM_ARG || !EMA, "the EMA belongs to the scheduled forms");
+    const float4 *tab = group_table<FORM>(groups_out, n_groups);
+    float4 cu = make_float4(0.f, 0.f, 0.f, 0.f);          // the lane's constants; FORM_GROUPS: unused
+    if constexpr (FORM == FORM_SCHED) decay = so[SOUT_DECAY];
+    if constexpr (FORM != FORM_GROUPS) cu = make_float4(0.f, st[0], decay, wd);
+    const float inv_sqrt_bc2 = st[1];
     const float gs = grad_scale * st[3];
-    if (SCHED) decay = so[SOUT_DECAY];
     const float ew = EMA ? so[SOUT_EMA_W] : 0.f;
     const bool efirst = EMA && so[SOUT_EMA_FIRST] != 0.f;
     const long n4 = n >> 2;
     float4 *p4 = reinterpret_cast<float4 *>(p), *m4 = reinterpret_cast<float4 *>(m), *v4 = reinterpret_cast<float4 *>(v);
     float4 *e4 = reinterpret_cast<float4 *>(ema);
     const float4 *g4 = reinterpret_cast<const float4 *>(g);
+    const unsigned *map4 = reinterpret_cast<const unsigned *>(map);
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        unsigned w = 0;                            // without groups: one group, and `w` is not read
+        if constexpr (FORM == FORM_GROUPS) w = map4[i];
         float4 pv = p4[i], mv = m4[i], vv = v4[i];
         const float4 gv = g4[i];
-        adam_one<DECOUPLED>(pv.x, gv.x, mv.x, vv.x, gs, beta1, beta2, eps, wd, decay, step_size, inv_sqrt_bc2);
-        adam_one<DECOUPLED>(pv.y, gv.y, mv.y, vv.y, gs, beta1, beta2, eps, wd, decay, step_size, inv_sqrt_bc2);
-        adam_one<DECOUPLED>(pv.z, gv.z, mv.z, vv.z, gs, beta1, beta2, eps, wd, decay, step_size, inv_sqrt_bc2);
-        adam_one<DECOUPLED>(pv.w, gv.w, mv.w, vv.w, gs, beta1, beta2, eps, wd, decay, step_size, inv_sqrt_bc2);
+        if (one_group(w)) {                        // always, without groups
+            const float4 c = consts<FORM>(tab, w, cu);
+            adam_four<DECOUPLED>(pv, gv, mv, vv, gs, beta1, beta2, eps, inv_sqrt_bc2, c, c, c, c);
+        } else {
+            adam_four<DECOUPLED>(pv, gv, mv, vv, gs, beta1, beta2, eps, inv_sqrt_bc2, consts<FORM>(tab, w, cu),
+                                 consts<FORM>(tab, w >> 8, cu), consts<FORM>(tab, w >> 16, cu), consts<FORM>(tab, w >> 24, cu));
+        }
         p4[i] = pv;
         m4[i] = mv;
         v4[i] = vv;
-        if (EMA) {
-            float4 ev = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (!efirst) ev = e4[i];
-            ema_one(ev.x, pv.x, ew, efirst);
-            ema_one(ev.y, pv.y, ew, efirst);
-            ema_one(ev.z, pv.z, ew, efirst);
-            ema_one(ev.w, pv.w, ew, efirst);
-            e4[i] = ev;
-        }
+        if (EMA) ema_four(e4, i, pv, ew, efirst);
     }
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
         const long i = n4 * 4 + threadIdx.x;
-        adam_one<DECOUPLED>(p[i], g[i], m[i], v[i], gs, beta1, beta2, eps, wd, decay, step_size, inv_sqrt_bc2);
-        if (EMA) {
-            float ev = efirst ? 0.f : ema[i];
-            ema_one(ev, p[i], ew, efirst);
-            ema[i] = ev;
-        }
+        unsigned w = 0;
+        if constexpr (FORM == FORM_GROUPS) w = map[i];
+        const float4 c = consts<FORM>(tab, w, cu);
+        adam_one<DECOUPLED>(p[i], g[i], m[i], v[i], gs, beta1, beta2, eps, c.w, c.z, c.y, inv_sqrt_bc2);
+        if (EMA) ema_tail(ema, i, p[i], ew, efirst);
     }
 }
 
@@ -294,141 +364,29 @@ __device__ __forceinline__ void sgd_one(float &p, float g, float *buf, float gs,
     p = __builtin_fmaf(-lr, gi, pi);
 }
 
-// SCHED: `lr` comes from so[SOUT_LR] instead of the argument.  EMA (SCHED only): as in adam_update_kernel.
-template <bool MOM, bool SCHED, bool EMA>
+// the four elements of a vector, each with its own constants
+template <bool MOM>
+__device__ __forceinline__ void sgd_four(float4 &pv, const float4 &gv, float4 &bv, float gs, float mu, float keep, bool nest,
+                                         bool first, const float4 &c0, const float4 &c1, const float4 &c2, const float4 &c3) {
+    sgd_one<MOM>(pv.x, gv.x, &bv.x, gs, c0.x, c0.w, mu, keep, nest, first);
+    sgd_one<MOM>(pv.y, gv.y, &bv.y, gs, c1.x, c1.w, mu, keep, nest, first);
+    sgd_one<MOM>(pv.z, gv.z, &bv.z, gs, c2.x, c2.w, mu, keep, nest, first);
+    sgd_one<MOM>(pv.w, gv.w, &bv.w, gs, c3.x, c3.w, mu, keep, nest, first);
+}
+
+// FORM_ARG: lr and wd are the arguments.  FORM_SCHED: lr is so[SOUT_LR].  FORM_GROUPS: both from the group's row.
+template <bool MOM, int FORM, bool EMA>
 __global__ __launch_bounds__(OX_THREADS) void sgd_update_kernel(float *__restrict__ p, const float *__restrict__ g,
                                                                 float *__restrict__ buf, long n, float lr, float wd, float mu,
                                                                 float keep, int nesterov, float grad_scale,
                                                                 const float *__restrict__ st, const float *__restrict__ so,
-                                                                float *__restrict__ ema) {
-    const bool first = st[0] != 0.f, nest = nesterov != 0;
-    const float gs = grad_scale * st[3];
-    if (SCHED) lr = so[SOUT_LR];
-    const float ew = EMA ? so[SOUT_EMA_W] : 0.f;
-    const bool efirst = EMA && so[SOUT_EMA_FIRST] != 0.f;
-    const long n4 = n >> 2;
-    float4 *p4 = reinterpret_cast<float4 *>(p), *b4 = reinterpret_cast<float4 *>(buf);
-    float4 *e4 = reinterpret_cast<float4 *>(ema);
-    const float4 *g4 = reinterpret_cast<const float4 *>(g);
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
-        float4 pv = p4[i];
-        const float4 gv = g4[i];
-        float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (MOM && !first) bv = b4[i];
-        sgd_one<MOM>(pv.x, gv.x, &bv.x, gs, lr, wd, mu, keep, nest, first);
-        sgd_one<MOM>(pv.y, gv.y, &bv.y, gs, lr, wd, mu, keep, nest, first);
-        sgd_one<MOM>(pv.z, gv.z, &bv.z, gs, lr, wd, mu, keep, nest, first);
-        sgd_one<MOM>(pv.w, gv.w, &bv.w, gs, lr, wd, mu, keep, nest, first);
-        p4[i] = pv;
-        if (MOM) b4[i] = bv;
-        if (EMA) {
-            float4 ev = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (!efirst) ev = e4[i];
-            ema_one(ev.x, pv.x, ew, efirst);
-            ema_one(ev.y, pv.y, ew, efirst);
-            ema_one(ev.z, pv.z, ew, efirst);
-            ema_one(ev.w, pv.w, ew, efirst);
-            e4[i] = ev;
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-        const long i = n4 * 4 + threadIdx.x;
-        sgd_one<MOM>(p[i], g[i], MOM ? buf + i : nullptr, gs, lr, wd, mu, keep, nest, first);
-        if (EMA) {
-            float ev = efirst ? 0.f : ema[i];
-            ema_one(ev, p[i], ew, efirst);
-            ema[i] = ev;
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------- parameter groups
-// The scheduled updates with a rate and a weight decay per parameter group: the same grid, float4 streams and n & 3 tail as
-// above, the same adam_one / sgd_one / ema_one per element (so a group's elements get the bits of the ungrouped kernel run on
-// them alone with the group's constants).  groups_out goes to LDS once per workgroup; a lane reads the map as one 32-bit word
-// per float4 and, where its four bytes agree (parameters are long runs: almost always), fetches one set of constants, else
-// one per element.  Indices are masked with OX_MAX_GROUPS - 1: no map value reads outside the table.
-__device__ __forceinline__ void load_group_table(float4 *tab, const float *__restrict__ groups_out, int n_groups) {
-    if (threadIdx.x < OX_MAX_GROUPS)
-        tab[threadIdx.x] = (int)threadIdx.x < n_groups ? reinterpret_cast<const float4 *>(groups_out)[threadIdx.x]
-                                                       : make_float4(0.f, 0.f, 1.f, 0.f);
-    __syncthreads();
-}
-
-__device__ __forceinline__ bool one_group(unsigned w) { return w == (w & 0xffu) * 0x01010101u; }
-
-template <bool DECOUPLED, bool EMA>
-__global__ __launch_bounds__(OX_THREADS) void adam_update_groups_kernel(float *__restrict__ p, const float *__restrict__ g,
-                                                                        float *__restrict__ m, float *__restrict__ v, long n,
-                                                                        float beta1, float beta2, float eps, float grad_scale,
-                                                                        const float *__restrict__ st,
-                                                                        const float *__restrict__ so, float *__restrict__ ema,
-                                                                        const float *__restrict__ groups_out, int n_groups,
-                                                                        const unsigned char *__restrict__ map) {
-    __shared__ float4 tab[OX_MAX_GROUPS];          // {rate, rate / bc1, decay, wd} per group
-    load_group_table(tab, groups_out, n_groups);
-    const float inv_sqrt_bc2 = st[1];
-    const float gs = grad_scale * st[3];
-    const float ew = EMA ? so[SOUT_EMA_W] : 0.f;
-    const bool efirst = EMA && so[SOUT_EMA_FIRST] != 0.f;
-    const long n4 = n >> 2;
-    float4 *p4 = reinterpret_cast<float4 *>(p), *m4 = reinterpret_cast<float4 *>(m), *v4 = reinterpret_cast<float4 *>(v);
-    float4 *e4 = reinterpret_cast<float4 *>(ema);
-    const float4 *g4 = reinterpret_cast<const float4 *>(g);
-    const unsigned *map4 = reinterpret_cast<const unsigned *>(map);
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
-        const unsigned w = map4[i];
-        float4 pv = p4[i], mv = m4[i], vv = v4[i];
-        const float4 gv = g4[i];
-        if (one_group(w)) {
-            const float4 c = tab[w & (OX_MAX_GROUPS - 1)];
-            adam_one<DECOUPLED>(pv.x, gv.x, mv.x, vv.x, gs, beta1, beta2, eps, c.w, c.z, c.y, inv_sqrt_bc2);
-            adam_one<DECOUPLED>(pv.y, gv.y, mv.y, vv.y, gs, beta1, beta2, eps, c.w, c.z, c.y, inv_sqrt_bc2);
-            adam_one<DECOUPLED>(pv.z, gv.z, mv.z, vv.z, gs, beta1, beta2, eps, c.w, c.z, c.y, inv_sqrt_bc2);
-            adam_one<DECOUPLED>(pv.w, gv.w, mv.w, vv.w, gs, beta1, beta2, eps, c.w, c.z, c.y, inv_sqrt_bc2);
-        } else {
-            const float4 c0 = tab[w & (OX_MAX_GROUPS - 1)], c1 = tab[(w >> 8) & (OX_MAX_GROUPS - 1)];
-            const float4 c2 = tab[(w >> 16) & (OX_MAX_GROUPS - 1)], c3 = tab[(w >> 24) & (OX_MAX_GROUPS - 1)];
-            adam_one<DECOUPLED>(pv.x, gv.x, mv.x, vv.x, gs, beta1, beta2, eps, c0.w, c0.z, c0.y, inv_sqrt_bc2);
-            adam_one<DECOUPLED>(pv.y, gv.y, mv.y, vv.y, gs, beta1, beta2, eps, c1.w, c1.z, c1.y, inv_sqrt_bc2);
-            adam_one<DECOUPLED>(pv.z, gv.z, mv.z, vv.z, gs, beta1, beta2, eps, c2.w, c2.z, c2.y, inv_sqrt_bc2);
-            adam_one<DECOUPLED>(pv.w, gv.w, mv.w, vv.w, gs, beta1, beta2, eps, c3.w, c3.z, c3.y, inv_sqrt_bc2);
-        }
-        p4[i] = pv;
-        m4[i] = mv;
-        v4[i] = vv;
-        if (EMA) {
-            float4 ev = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (!efirst) ev = e4[i];
-            ema_one(ev.x, pv.x, ew, efirst);
-            ema_one(ev.y, pv.y, ew, efirst);
-            ema_one(ev.z, pv.z, ew, efirst);
-            ema_one(ev.w, pv.w, ew, efirst);
-            e4[i] = ev;
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-        const long i = n4 * 4 + threadIdx.x;
-        const float4 c = tab[map[i] & (OX_MAX_GROUPS - 1)];
-        adam_one<DECOUPLED>(p[i], g[i], m[i], v[i], gs, beta1, beta2, eps, c.w, c.z, c.y, inv_sqrt_bc2);
-        if (EMA) {
-            float ev = efirst ? 0.f : ema[i];
-            ema_one(ev, p[i], ew, efirst);
-            ema[i] = ev;
-        }
-    }
-}
-
-template <bool MOM, bool EMA>
-__global__ __launch_bounds__(OX_THREADS) void sgd_update_groups_kernel(float *__restrict__ p, const float *__restrict__ g,
-                                                                       float *__restrict__ buf, long n, float mu, float keep,
-                                                                       int nesterov, float grad_scale,
-                                                                       const float *__restrict__ st,
-                                                                       const float *__restrict__ so, float *__restrict__ ema,
-                                                                       const float *__restrict__ groups_out, int n_groups,
-                                                                       const unsigned char *__restrict__ map) {
-    __shared__ float4 tab[OX_MAX_GROUPS];          // {rate, rate, decay (unused), wd} per group
-    load_group_table(tab, groups_out, n_groups);
+                                                                float *__restrict__ ema, const float *__restrict__ groups_out,
+                                                                int n_groups, const unsigned char *__restrict__ map) {
+    static_assert(FORM != FORM_ARG || !EMA, "the EMA belongs to the scheduled forms");
+    const float4 *tab = group_table<FORM>(groups_out, n_groups);
+    float4 cu = make_float4(0.f, 0.f, 0.f, 0.f);          // the lane's constants; FORM_GROUPS: unused
+    if constexpr (FORM == FORM_SCHED) lr = so[SOUT_LR];
+    if constexpr (FORM != FORM_GROUPS) cu = make_float4(lr, 0.f, 0.f, wd);
     const bool first = st[0] != 0.f, nest = nesterov != 0;
     const float gs = grad_scale * st[3];
     const float ew = EMA ? so[SOUT_EMA_W] : 0.f;
@@ -439,46 +397,30 @@ __global__ __launch_bounds__(OX_THREADS) void sgd_update_groups_kernel(float *__
     const float4 *g4 = reinterpret_cast<const float4 *>(g);
     const unsigned *map4 = reinterpret_cast<const unsigned *>(map);
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
-        const unsigned w = map4[i];
+        unsigned w = 0;                            // without groups: one group, and `w` is not read
+        if constexpr (FORM == FORM_GROUPS) w = map4[i];
         float4 pv = p4[i];
         const float4 gv = g4[i];
         float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
         if (MOM && !first) bv = b4[i];
-        if (one_group(w)) {
-            const float4 c = tab[w & (OX_MAX_GROUPS - 1)];
-            sgd_one<MOM>(pv.x, gv.x, &bv.x, gs, c.x, c.w, mu, keep, nest, first);
-            sgd_one<MOM>(pv.y, gv.y, &bv.y, gs, c.x, c.w, mu, keep, nest, first);
-            sgd_one<MOM>(pv.z, gv.z, &bv.z, gs, c.x, c.w, mu, keep, nest, first);
-            sgd_one<MOM>(pv.w, gv.w, &bv.w, gs, c.x, c.w, mu, keep, nest, first);
+        if (one_group(w)) {                        // always, without groups
+            const float4 c = consts<FORM>(tab, w, cu);
+            sgd_four<MOM>(pv, gv, bv, gs, mu, keep, nest, first, c, c, c, c);
         } else {
-            const float4 c0 = tab[w & (OX_MAX_GROUPS - 1)], c1 = tab[(w >> 8) & (OX_MAX_GROUPS - 1)];
-            const float4 c2 = tab[(w >> 16) & (OX_MAX_GROUPS - 1)], c3 = tab[(w >> 24) & (OX_MAX_GROUPS - 1)];
-            sgd_one<MOM>(pv.x, gv.x, &bv.x, gs, c0.x, c0.w, mu, keep, nest, first);
-            sgd_one<MOM>(pv.y, gv.y, &bv.y, gs, c1.x, c1.w, mu, keep, nest, first);
-            sgd_one<MOM>(pv.z, gv.z, &bv.z, gs, c2.x, c2.w, mu, keep, nest, first);
-            sgd_one<MOM>(pv.w, gv.w, &bv.w, gs, c3.x, c3.w, mu, keep, nest, first);
+            sgd_four<MOM>(pv, gv, bv, gs, mu, keep, nest, first, consts<FORM>(tab, w, cu), consts<FORM>(tab, w >> 8, cu),
+                          consts<FORM>(tab, w >> 16, cu), consts<FORM>(tab, w >> 24, cu));
         }
         p4[i] = pv;
         if (MOM) b4[i] = bv;
-        if (EMA) {
-            float4 ev = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (!efirst) ev = e4[i];
-            ema_one(ev.x, pv.x, ew, efirst);
-            ema_one(ev.y, pv.y, ew, efirst);
-            ema_one(ev.z, pv.z, ew, efirst);
-            ema_one(ev.w, pv.w, ew, efirst);
-            e4[i] = ev;
-        }
+        if (EMA) ema_four(e4, i, pv, ew, efirst);
     }
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
         const long i = n4 * 4 + threadIdx.x;
-        const float4 c = tab[map[i] & (OX_MAX_GROUPS - 1)];
+        unsigned w = 0;
+        if constexpr (FORM == FORM_GROUPS) w = map[i];
+        const float4 c = consts<FORM>(tab, w, cu);
         sgd_one<MOM>(p[i], g[i], MOM ? buf + i : nullptr, gs, c.x, c.w, mu, keep, nest, first);
-        if (EMA) {
-            float ev = efirst ? 0.f : ema[i];
-            ema_one(ev, p[i], ew, efirst);
-            ema[i] = ev;
-        }
+        if (EMA) ema_tail(ema, i, p[i], ew, efirst);
     }
 }
 
@@ -496,83 +438,99 @@ static int launch_prep(uint64_t *step_dev, float *st_dev, int kind, float lr, fl
     return check_launch("optim_prep");
 }
 
-// the Adam / AdamW step behind both entry points.  sched == nullptr: lr is the argument (and decay formed from it here)
+// What a step's entry point adds to the plain form: all null in FORM_ARG; the table, sched_out and (optionally) the EMA in
+// FORM_SCHED and FORM_GROUPS; the groups in FORM_GROUPS.
+struct StepForm {
+    int form;
+    const double *sched;
+    float *sched_out, *ema;
+    const double *groups;
+    float *groups_out;
+    int n_groups;
+    const unsigned char *map;
+};
+
+// a kernel's five instantiations (for one value of its first template parameter) are kept in the order of this index
+static int form_index(const StepForm &f) {
+    switch (f.form) {
+    case FORM_GROUPS: return f.ema ? 4 : 3;
+    case FORM_SCHED: return f.ema ? 2 : 1;
+    default: return 0;
+    }
+}
+
+template <bool DECOUPLED>
+static auto adam_kernel(const StepForm &f) {
+    decltype(&adam_update_kernel<DECOUPLED, FORM_ARG, false>) const five[5] = {
+        adam_update_kernel<DECOUPLED, FORM_ARG, false>, adam_update_kernel<DECOUPLED, FORM_SCHED, false>,
+        adam_update_kernel<DECOUPLED, FORM_SCHED, true>, adam_update_kernel<DECOUPLED, FORM_GROUPS, false>,
+        adam_update_kernel<DECOUPLED, FORM_GROUPS, true>};
+    return five[form_index(f)];
+}
+
+template <bool MOM>
+static auto sgd_kernel(const StepForm &f) {
+    decltype(&sgd_update_kernel<MOM, FORM_ARG, false>) const five[5] = {
+        sgd_update_kernel<MOM, FORM_ARG, false>, sgd_update_kernel<MOM, FORM_SCHED, false>,
+        sgd_update_kernel<MOM, FORM_SCHED, true>, sgd_update_kernel<MOM, FORM_GROUPS, false>,
+        sgd_update_kernel<MOM, FORM_GROUPS, true>};
+    return five[form_index(f)];
+}
+
+// The argument checks of the six step entry points; `what` is the entry point's name.  present / aligned: what the rule says
+// about its own buffers (parameters, gradient, state, counter, scratch); the form's buffers are checked here.
+static int check_step(const char *what, bool present, bool aligned, long n, const StepForm &f) {
+    const bool sched = f.form != FORM_ARG;
+    ADYOLO_REQUIRE(present && n > 0 && (!sched || (f.sched && f.sched_out)), ADYOLO_EINVAL, "%s: bad arguments", what);
+    ADYOLO_REQUIRE(aligned && aligned16(f.ema) && (reinterpret_cast<uintptr_t>(f.sched) & 7) == 0, ADYOLO_EINVAL,
+                   "%s: buffers not 16-byte aligned%s", what, sched ? " (or the table not 8-byte aligned)" : "");
+    ADYOLO_REQUIRE(f.form != FORM_GROUPS ||
+                       (f.groups && f.groups_out && f.map && f.n_groups >= 1 && f.n_groups <= OX_MAX_GROUPS &&
+                        (reinterpret_cast<uintptr_t>(f.groups) & 7) == 0 && aligned16(f.groups_out) &&
+                        (reinterpret_cast<uintptr_t>(f.map) & 3) == 0),
+                   ADYOLO_EINVAL, "%s: 1 to 16 groups, groups_dev 8-byte, groups_out 16-byte and the map 4-byte aligned", what);
+    return 0;
+}
+
+// the Adam / AdamW step behind its three entry points: check, sum of squares (clipping only), prep, update.  FORM_ARG: lr is
+// the argument (and decay formed from it here); else lr is ignored, and in FORM_GROUPS weight_decay too
 static int adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, long n, float lr, float beta1,
                      float beta2, float eps, float weight_decay, int decoupled, uint64_t *step_dev, float *st_dev,
-                     double *partials, float max_norm, float grad_scale, const double *sched, float *sched_out, float *ema,
-                     hipStream_t st, const char *what) {
+                     double *partials, float max_norm, float grad_scale, const StepForm &f, hipStream_t st, const char *what) {
     int rc;
+    if ((rc = check_step(what, param && grad && exp_avg && exp_avg_sq && step_dev && st_dev,
+                         aligned16(param) && aligned16(grad) && aligned16(exp_avg) && aligned16(exp_avg_sq), n, f)))
+        return rc;
     if (partials && (rc = launch_sumsq(grad, n, grad_scale, partials, st))) return rc;
-    if ((rc = launch_prep(step_dev, st_dev, PREP_ADAM, lr, beta1, beta2, partials, n, max_norm, st, sched, sched_out,
-                          weight_decay)))
+    if ((rc = launch_prep(step_dev, st_dev, PREP_ADAM, lr, beta1, beta2, partials, n, max_norm, st, f.sched, f.sched_out,
+                          weight_decay, f.groups, f.groups_out, f.n_groups)))
         return rc;
     const float decay = (float)(1.0 - (double)lr * (double)weight_decay);
-    auto kernel = decoupled ? adam_update_kernel<true, false, false> : adam_update_kernel<false, false, false>;
-    if (sched && ema) kernel = decoupled ? adam_update_kernel<true, true, true> : adam_update_kernel<false, true, true>;
-    else if (sched) kernel = decoupled ? adam_update_kernel<true, true, false> : adam_update_kernel<false, true, false>;
+    auto kernel = decoupled ? adam_kernel<true>(f) : adam_kernel<false>(f);
     hipLaunchKernelGGL(kernel, dim3(update_grid(n)), dim3(OX_THREADS), 0, st, param, grad, exp_avg, exp_avg_sq, n, beta1, beta2,
-                       eps, weight_decay, decay, grad_scale, (const float *)st_dev, (const float *)sched_out, ema);
+                       eps, weight_decay, decay, grad_scale, (const float *)st_dev, (const float *)f.sched_out, f.ema,
+                       (const float *)f.groups_out, f.n_groups, f.map);
     return check_launch(what);
 }
 
 static int sgd_step(float *param, const float *grad, float *momentum_buf, long n, float lr, float weight_decay, float momentum,
                     float dampening, int nesterov, uint64_t *step_dev, float *st_dev, double *partials, float max_norm,
-                    float grad_scale, const double *sched, float *sched_out, float *ema, hipStream_t st, const char *what) {
+                    float grad_scale, const StepForm &f, hipStream_t st, const char *what) {
     int rc;
+    if ((rc = check_step(what, param && grad && step_dev && st_dev && (momentum == 0.f || momentum_buf),
+                         aligned16(param) && aligned16(grad) && aligned16(momentum_buf), n, f)))
+        return rc;
     if (partials && (rc = launch_sumsq(grad, n, grad_scale, partials, st))) return rc;
-    if ((rc = launch_prep(step_dev, st_dev, PREP_SGD, lr, 0.f, 0.f, partials, n, max_norm, st, sched, sched_out, 0.f)))
+    if ((rc = launch_prep(step_dev, st_dev, PREP_SGD, lr, 0.f, 0.f, partials, n, max_norm, st, f.sched, f.sched_out, 0.f,
+                          f.groups, f.groups_out, f.n_groups)))
         return rc;
     const float keep = (float)(1.0 - (double)dampening);
     const bool mom = momentum != 0.f;
-    auto kernel = mom ? sgd_update_kernel<true, false, false> : sgd_update_kernel<false, false, false>;
-    if (sched && ema) kernel = mom ? sgd_update_kernel<true, true, true> : sgd_update_kernel<false, true, true>;
-    else if (sched) kernel = mom ? sgd_update_kernel<true, true, false> : sgd_update_kernel<false, true, false>;
+    auto kernel = mom ? sgd_kernel<true>(f) : sgd_kernel<false>(f);
     hipLaunchKernelGGL(kernel, dim3(update_grid(n)), dim3(OX_THREADS), 0, st, param, grad, mom ? momentum_buf : (float *)nullptr,
                        n, lr, weight_decay, mom ? momentum : 0.f, keep, nesterov, grad_scale, (const float *)st_dev,
-                       (const float *)sched_out, ema);
+                       (const float *)f.sched_out, f.ema, (const float *)f.groups_out, f.n_groups, f.map);
     return check_launch(what);
-}
-
-static int adam_step_groups(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, long n, float beta1, float beta2,
-                            float eps, int decoupled, uint64_t *step_dev, float *st_dev, double *partials, float max_norm,
-                            float grad_scale, const double *sched, float *sched_out, float *ema, const double *groups,
-                            float *groups_out, int n_groups, const unsigned char *map, hipStream_t st, const char *what) {
-    int rc;
-    if (partials && (rc = launch_sumsq(grad, n, grad_scale, partials, st))) return rc;
-    if ((rc = launch_prep(step_dev, st_dev, PREP_ADAM, 0.f, beta1, beta2, partials, n, max_norm, st, sched, sched_out, 0.f,
-                          groups, groups_out, n_groups)))
-        return rc;
-    auto kernel = decoupled ? adam_update_groups_kernel<true, false> : adam_update_groups_kernel<false, false>;
-    if (ema) kernel = decoupled ? adam_update_groups_kernel<true, true> : adam_update_groups_kernel<false, true>;
-    hipLaunchKernelGGL(kernel, dim3(update_grid(n)), dim3(OX_THREADS), 0, st, param, grad, exp_avg, exp_avg_sq, n, beta1, beta2,
-                       eps, grad_scale, (const float *)st_dev, (const float *)sched_out, ema, (const float *)groups_out, n_groups,
-                       map);
-    return check_launch(what);
-}
-
-static int sgd_step_groups(float *param, const float *grad, float *momentum_buf, long n, float momentum, float dampening,
-                           int nesterov, uint64_t *step_dev, float *st_dev, double *partials, float max_norm, float grad_scale,
-                           const double *sched, float *sched_out, float *ema, const double *groups, float *groups_out,
-                           int n_groups, const unsigned char *map, hipStream_t st, const char *what) {
-    int rc;
-    if (partials && (rc = launch_sumsq(grad, n, grad_scale, partials, st))) return rc;
-    if ((rc = launch_prep(step_dev, st_dev, PREP_SGD, 0.f, 0.f, 0.f, partials, n, max_norm, st, sched, sched_out, 0.f, groups,
-                          groups_out, n_groups)))
-        return rc;
-    const float keep = (float)(1.0 - (double)dampening);
-    const bool mom = momentum != 0.f;
-    auto kernel = mom ? sgd_update_groups_kernel<true, false> : sgd_update_groups_kernel<false, false>;
-    if (ema) kernel = mom ? sgd_update_groups_kernel<true, true> : sgd_update_groups_kernel<false, true>;
-    hipLaunchKernelGGL(kernel, dim3(update_grid(n)), dim3(OX_THREADS), 0, st, param, grad, mom ? momentum_buf : (float *)nullptr,
-                       n, mom ? momentum : 0.f, keep, nesterov, grad_scale, (const float *)st_dev, (const float *)sched_out, ema,
-                       (const float *)groups_out, n_groups, map);
-    return check_launch(what);
-}
-
-static inline bool groups_ok(const double *groups_dev, const float *groups_out, const unsigned char *map, int n_groups) {
-    return groups_dev && groups_out && map && n_groups >= 1 && n_groups <= OX_MAX_GROUPS &&
-           (reinterpret_cast<uintptr_t>(groups_dev) & 7) == 0 && aligned16(groups_out) &&
-           (reinterpret_cast<uintptr_t>(map) & 3) == 0;
 }
 
 }  // namespace adyolo
@@ -599,23 +557,15 @@ extern "C" int adyolo_grad_norm_dev(const float *grad, long n, float grad_scale,
 extern "C" int adyolo_adam_step_dev(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, long n, float lr,
                                     float beta1, float beta2, float eps, float weight_decay, int decoupled, uint64_t *step_dev,
                                     float *st_dev, double *partials, float max_norm, float grad_scale, void *stream) {
-    ADYOLO_REQUIRE(param && grad && exp_avg && exp_avg_sq && n > 0 && step_dev && st_dev, ADYOLO_EINVAL,
-                   "adam_step_dev: bad arguments");
-    ADYOLO_REQUIRE(aligned16(param) && aligned16(grad) && aligned16(exp_avg) && aligned16(exp_avg_sq), ADYOLO_EINVAL,
-                   "adam_step_dev: buffers not 16-byte aligned");
     return adam_step(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, decoupled, step_dev, st_dev,
-                     partials, max_norm, grad_scale, nullptr, nullptr, nullptr, as_stream(stream), "adam_step_dev");
+                     partials, max_norm, grad_scale, StepForm{FORM_ARG}, as_stream(stream), "adam_step_dev");
 }
 
 extern "C" int adyolo_sgd_step_dev(float *param, const float *grad, float *momentum_buf, long n, float lr, float weight_decay,
                                    float momentum, float dampening, int nesterov, uint64_t *step_dev, float *st_dev,
                                    double *partials, float max_norm, float grad_scale, void *stream) {
-    ADYOLO_REQUIRE(param && grad && n > 0 && step_dev && st_dev && (momentum == 0.f || momentum_buf), ADYOLO_EINVAL,
-                   "sgd_step_dev: bad arguments");
-    ADYOLO_REQUIRE(aligned16(param) && aligned16(grad) && aligned16(momentum_buf), ADYOLO_EINVAL,
-                   "sgd_step_dev: buffers not 16-byte aligned");
     return sgd_step(param, grad, momentum_buf, n, lr, weight_decay, momentum, dampening, nesterov, step_dev, st_dev, partials,
-                    max_norm, grad_scale, nullptr, nullptr, nullptr, as_stream(stream), "sgd_step_dev");
+                    max_norm, grad_scale, StepForm{FORM_ARG}, as_stream(stream), "sgd_step_dev");
 }
 
 extern "C" int adyolo_sched_table_doubles(void) { return SCHED_TABLE_DOUBLES; }
@@ -626,26 +576,18 @@ extern "C" int adyolo_adam_step_sched_dev(float *param, const float *grad, float
                                           uint64_t *step_dev, float *st_dev, double *partials, float max_norm,
                                           float grad_scale, const double *sched_dev, float *sched_out, float *ema,
                                           void *stream) {
-    ADYOLO_REQUIRE(param && grad && exp_avg && exp_avg_sq && n > 0 && step_dev && st_dev && sched_dev && sched_out,
-                   ADYOLO_EINVAL, "adam_step_sched_dev: bad arguments");
-    ADYOLO_REQUIRE(aligned16(param) && aligned16(grad) && aligned16(exp_avg) && aligned16(exp_avg_sq) && aligned16(ema) &&
-                       (reinterpret_cast<uintptr_t>(sched_dev) & 7) == 0,
-                   ADYOLO_EINVAL, "adam_step_sched_dev: buffers not 16-byte aligned (or the table not 8-byte aligned)");
     return adam_step(param, grad, exp_avg, exp_avg_sq, n, 0.f, beta1, beta2, eps, weight_decay, decoupled, step_dev, st_dev,
-                     partials, max_norm, grad_scale, sched_dev, sched_out, ema, as_stream(stream), "adam_step_sched_dev");
+                     partials, max_norm, grad_scale, StepForm{FORM_SCHED, sched_dev, sched_out, ema}, as_stream(stream),
+                     "adam_step_sched_dev");
 }
 
 extern "C" int adyolo_sgd_step_sched_dev(float *param, const float *grad, float *momentum_buf, long n, float weight_decay,
                                          float momentum, float dampening, int nesterov, uint64_t *step_dev, float *st_dev,
                                          double *partials, float max_norm, float grad_scale, const double *sched_dev,
                                          float *sched_out, float *ema, void *stream) {
-    ADYOLO_REQUIRE(param && grad && n > 0 && step_dev && st_dev && (momentum == 0.f || momentum_buf) && sched_dev && sched_out,
-                   ADYOLO_EINVAL, "sgd_step_sched_dev: bad arguments");
-    ADYOLO_REQUIRE(aligned16(param) && aligned16(grad) && aligned16(momentum_buf) && aligned16(ema) &&
-                       (reinterpret_cast<uintptr_t>(sched_dev) & 7) == 0,
-                   ADYOLO_EINVAL, "sgd_step_sched_dev: buffers not 16-byte aligned (or the table not 8-byte aligned)");
     return sgd_step(param, grad, momentum_buf, n, 0.f, weight_decay, momentum, dampening, nesterov, step_dev, st_dev, partials,
-                    max_norm, grad_scale, sched_dev, sched_out, ema, as_stream(stream), "sgd_step_sched_dev");
+                    max_norm, grad_scale, StepForm{FORM_SCHED, sched_dev, sched_out, ema}, as_stream(stream),
+                    "sgd_step_sched_dev");
 }
 
 extern "C" int adyolo_optim_max_groups(void) { return OX_MAX_GROUPS; }
@@ -655,16 +597,10 @@ extern "C" int adyolo_adam_step_groups_dev(float *param, const float *grad, floa
                                            float *st_dev, double *partials, float max_norm, float grad_scale,
                                            const double *sched_dev, float *sched_out, float *ema, const double *groups_dev,
                                            float *groups_out, int n_groups, const unsigned char *group_map, void *stream) {
-    ADYOLO_REQUIRE(param && grad && exp_avg && exp_avg_sq && n > 0 && step_dev && st_dev && sched_dev && sched_out,
-                   ADYOLO_EINVAL, "adam_step_groups_dev: bad arguments");
-    ADYOLO_REQUIRE(aligned16(param) && aligned16(grad) && aligned16(exp_avg) && aligned16(exp_avg_sq) && aligned16(ema) &&
-                       (reinterpret_cast<uintptr_t>(sched_dev) & 7) == 0,
-                   ADYOLO_EINVAL, "adam_step_groups_dev: buffers not 16-byte aligned (or the table not 8-byte aligned)");
-    ADYOLO_REQUIRE(groups_ok(groups_dev, groups_out, group_map, n_groups), ADYOLO_EINVAL,
-                   "adam_step_groups_dev: 1 to 16 groups, groups_dev 8-byte, groups_out 16-byte and the map 4-byte aligned");
-    return adam_step_groups(param, grad, exp_avg, exp_avg_sq, n, beta1, beta2, eps, decoupled, step_dev, st_dev, partials,
-                            max_norm, grad_scale, sched_dev, sched_out, ema, groups_dev, groups_out, n_groups, group_map,
-                            as_stream(stream), "adam_step_groups_dev");
+    return adam_step(param, grad, exp_avg, exp_avg_sq, n, 0.f, beta1, beta2, eps, 0.f, decoupled, step_dev, st_dev, partials,
+                     max_norm, grad_scale,
+                     StepForm{FORM_GROUPS, sched_dev, sched_out, ema, groups_dev, groups_out, n_groups, group_map},
+                     as_stream(stream), "adam_step_groups_dev");
 }
 
 extern "C" int adyolo_sgd_step_groups_dev(float *param, const float *grad, float *momentum_buf, long n, float momentum,
@@ -672,14 +608,7 @@ extern "C" int adyolo_sgd_step_groups_dev(float *param, const float *grad, float
                                           float max_norm, float grad_scale, const double *sched_dev, float *sched_out,
                                           float *ema, const double *groups_dev, float *groups_out, int n_groups,
                                           const unsigned char *group_map, void *stream) {
-    ADYOLO_REQUIRE(param && grad && n > 0 && step_dev && st_dev && (momentum == 0.f || momentum_buf) && sched_dev && sched_out,
-                   ADYOLO_EINVAL, "sgd_step_groups_dev: bad arguments");
-    ADYOLO_REQUIRE(aligned16(param) && aligned16(grad) && aligned16(momentum_buf) && aligned16(ema) &&
-                       (reinterpret_cast<uintptr_t>(sched_dev) & 7) == 0,
-                   ADYOLO_EINVAL, "sgd_step_groups_dev: buffers not 16-byte aligned (or the table not 8-byte aligned)");
-    ADYOLO_REQUIRE(groups_ok(groups_dev, groups_out, group_map, n_groups), ADYOLO_EINVAL,
-                   "sgd_step_groups_dev: 1 to 16 groups, groups_dev 8-byte, groups_out 16-byte and the map 4-byte aligned");
-    return sgd_step_groups(param, grad, momentum_buf, n, momentum, dampening, nesterov, step_dev, st_dev, partials, max_norm,
-                           grad_scale, sched_dev, sched_out, ema, groups_dev, groups_out, n_groups, group_map,
-                           as_stream(stream), "sgd_step_groups_dev");
+    return sgd_step(param, grad, momentum_buf, n, 0.f, 0.f, momentum, dampening, nesterov, step_dev, st_dev, partials, max_norm,
+                    grad_scale, StepForm{FORM_GROUPS, sched_dev, sched_out, ema, groups_dev, groups_out, n_groups, group_map},
+                    as_stream(stream), "sgd_step_groups_dev");
 }

@@ -1170,6 +1170,30 @@ def _max_norm(what, partials, max_norm):
     return float(max_norm) if max_norm is not None else 0.0
 
 
+def _optim_step(what, param, grad, states, hyper, step_dev, st_dev, grad_scale, partials, max_norm, sched=(), groups=(),
+                momentum=None):
+    """The checks and the call behind every optimizer wrapper below.  ``what``: the wrapper's name, in errors and (as
+    ``adyolo_<what>``) the entry point.  states: the rule's state buffers; hyper: its scalars, in the entry point's order;
+    sched: (sched_dev, sched_out, ema) of the scheduled forms; groups: (groups_dev, groups_out, group_map) of the grouped
+    ones; momentum: SGD's, whose one state buffer is needed, and passed on, only when it is not 0."""
+    _chk(param, grad, *states, st_dev)
+    _chk_optim_dev(what, param.numel(), step_dev, st_dev, partials)
+    form = ()                         # what the entry point takes after grad_scale: sched_dev, sched_out, ema, then
+    if sched:                         # groups_dev, groups_out, n_groups, group_map
+        _chk_sched(what, param, *sched)
+        form = tuple(map(_p, sched))
+    if groups:
+        groups_dev, groups_out, group_map = groups
+        form += (_p(groups_dev), _p(groups_out), _chk_groups(what, param, *groups), _p(group_map))
+    if momentum is not None and momentum != 0.0 and states[0] is None:
+        raise _lib.AdyoloHipError("%s with momentum needs a momentum buffer" % what)
+    if momentum == 0.0:
+        states = (None,)              # SGD without momentum: the buffer is not passed on
+    # every step entry point: param, grad, state..., n, hyper..., step_dev, st_dev, partials, max_norm, grad_scale, form..., stream
+    _c("adyolo_" + what, _p(param), _p(grad), *map(_p, states), param.numel(), *hyper, _p(step_dev), _p(st_dev), _p(partials),
+       _max_norm(what, partials, max_norm), grad_scale, *form, _stream())
+
+
 def grad_sumsq(grad, partials, grad_scale=1.0):
     """partials[k] = float64 sum of (grad * grad_scale)^2 over workgroup k's share: fixed grid, fixed order, no atomics."""
     _chk(grad)
@@ -1197,11 +1221,8 @@ def adam_step_dev(param, grad, exp_avg, exp_avg_sq, step_dev, st_dev, lr=1e-3, b
     incremented by the call, st_dev (``OPTIM_SCRATCH_FLOATS`` floats) receives the bias corrections.  No argument changes from
     step to step (hipGraph-replayable).  partials (``grad_sumsq_parts(n)`` float64) + max_norm: clip the gradient norm first
     (st_dev[2] = the pre-clip norm); partials None = no clipping, the same kernel with a coefficient of exactly 1."""
-    _chk(param, grad, exp_avg, exp_avg_sq, st_dev)
-    _chk_optim_dev("adam_step_dev", param.numel(), step_dev, st_dev, partials)
-    _c("adyolo_adam_step_dev", _p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), lr, betas[0], betas[1], eps,
-       weight_decay, int(bool(decoupled)), _p(step_dev), _p(st_dev), _p(partials),
-       _max_norm("adam_step_dev", partials, max_norm), grad_scale, _stream())
+    _optim_step("adam_step_dev", param, grad, (exp_avg, exp_avg_sq), (lr, betas[0], betas[1], eps, weight_decay,
+                int(bool(decoupled))), step_dev, st_dev, grad_scale, partials, max_norm)
 
 
 def adamw_step_dev(param, grad, exp_avg, exp_avg_sq, step_dev, st_dev, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
@@ -1215,13 +1236,8 @@ def sgd_step_dev(param, grad, momentum_buf, step_dev, st_dev, lr=1e-3, weight_de
                  nesterov=False, grad_scale=1.0, partials=None, max_norm=None):
     """torch.optim.SGD.  momentum_buf: None when momentum == 0 (nothing is allocated or touched); the call that takes step_dev
     from 0 to 1 initialises it with the gradient (no dampening)."""
-    _chk(param, grad, momentum_buf, st_dev)
-    _chk_optim_dev("sgd_step_dev", param.numel(), step_dev, st_dev, partials)
-    if momentum != 0.0 and momentum_buf is None:
-        raise _lib.AdyoloHipError("sgd_step_dev with momentum needs a momentum buffer")
-    _c("adyolo_sgd_step_dev", _p(param), _p(grad), _p(momentum_buf if momentum != 0.0 else None), param.numel(), lr,
-       weight_decay, momentum, dampening, int(bool(nesterov)), _p(step_dev), _p(st_dev),
-       _p(partials), _max_norm("sgd_step_dev", partials, max_norm), grad_scale, _stream())
+    _optim_step("sgd_step_dev", param, grad, (momentum_buf,), (lr, weight_decay, momentum, dampening, int(bool(nesterov))),
+                step_dev, st_dev, grad_scale, partials, max_norm, momentum=momentum)
 
 
 # The scheduled forms (include/adyolo_hip.h, "The scheduled forms"): the rate is derived on the device from the step counter
@@ -1252,25 +1268,15 @@ def adam_step_sched_dev(param, grad, exp_avg, exp_avg_sq, step_dev, st_dev, sche
     """``adam_step_dev`` whose learning rate is computed by the step's prep kernel from step_dev and the table sched_dev
     (``SCHED_TABLE_DOUBLES`` float64) and written to sched_out[0] (``SCHED_OUT_FLOATS`` floats); a constant schedule gives
     ``adam_step_dev``'s bits.  ema: a buffer like param that receives the moving average of the parameters in the same launch."""
-    _chk(param, grad, exp_avg, exp_avg_sq, st_dev)
-    _chk_optim_dev("adam_step_sched_dev", param.numel(), step_dev, st_dev, partials)
-    _chk_sched("adam_step_sched_dev", param, sched_dev, sched_out, ema)
-    _c("adyolo_adam_step_sched_dev", _p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), betas[0], betas[1], eps,
-       weight_decay, int(bool(decoupled)), _p(step_dev), _p(st_dev), _p(partials),
-       _max_norm("adam_step_sched_dev", partials, max_norm), grad_scale, _p(sched_dev), _p(sched_out), _p(ema), _stream())
+    _optim_step("adam_step_sched_dev", param, grad, (exp_avg, exp_avg_sq), (betas[0], betas[1], eps, weight_decay,
+                int(bool(decoupled))), step_dev, st_dev, grad_scale, partials, max_norm, (sched_dev, sched_out, ema))
 
 
 def sgd_step_sched_dev(param, grad, momentum_buf, step_dev, st_dev, sched_dev, sched_out, ema=None, weight_decay=0.0,
                        momentum=0.0, dampening=0.0, nesterov=False, grad_scale=1.0, partials=None, max_norm=None):
     """``sgd_step_dev`` with the learning rate from the device-side schedule (see ``adam_step_sched_dev``)."""
-    _chk(param, grad, momentum_buf, st_dev)
-    _chk_optim_dev("sgd_step_sched_dev", param.numel(), step_dev, st_dev, partials)
-    _chk_sched("sgd_step_sched_dev", param, sched_dev, sched_out, ema)
-    if momentum != 0.0 and momentum_buf is None:
-        raise _lib.AdyoloHipError("sgd_step_sched_dev with momentum needs a momentum buffer")
-    _c("adyolo_sgd_step_sched_dev", _p(param), _p(grad), _p(momentum_buf if momentum != 0.0 else None), param.numel(),
-       weight_decay, momentum, dampening, int(bool(nesterov)), _p(step_dev), _p(st_dev), _p(partials),
-       _max_norm("sgd_step_sched_dev", partials, max_norm), grad_scale, _p(sched_dev), _p(sched_out), _p(ema), _stream())
+    _optim_step("sgd_step_sched_dev", param, grad, (momentum_buf,), (weight_decay, momentum, dampening, int(bool(nesterov))),
+                step_dev, st_dev, grad_scale, partials, max_norm, (sched_dev, sched_out, ema), momentum=momentum)
 
 
 # The scheduled forms with parameter groups (include/adyolo_hip.h): a base rate and a weight decay per group of elements
@@ -1299,28 +1305,16 @@ def adam_step_groups_dev(param, grad, exp_avg, exp_avg_sq, step_dev, st_dev, sch
     """``adam_step_sched_dev`` with a base rate and a weight decay per parameter group: groups_dev (G, 2) float64
     {base rate, weight_decay}, groups_out (G, ``GROUP_OUT_FLOATS``) float32 written every step (column 0: the groups' rates),
     group_map uint8, one entry per element of param.  The norm and the clip coefficient stay global."""
-    _chk(param, grad, exp_avg, exp_avg_sq, st_dev)
-    _chk_optim_dev("adam_step_groups_dev", param.numel(), step_dev, st_dev, partials)
-    _chk_sched("adam_step_groups_dev", param, sched_dev, sched_out, ema)
-    ng = _chk_groups("adam_step_groups_dev", param, groups_dev, groups_out, group_map)
-    _c("adyolo_adam_step_groups_dev", _p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), betas[0], betas[1], eps,
-       int(bool(decoupled)), _p(step_dev), _p(st_dev), _p(partials), _max_norm("adam_step_groups_dev", partials, max_norm),
-       grad_scale, _p(sched_dev), _p(sched_out), _p(ema), _p(groups_dev), _p(groups_out), ng, _p(group_map), _stream())
+    _optim_step("adam_step_groups_dev", param, grad, (exp_avg, exp_avg_sq), (betas[0], betas[1], eps, int(bool(decoupled))),
+                step_dev, st_dev, grad_scale, partials, max_norm, (sched_dev, sched_out, ema), (groups_dev, groups_out, group_map))
 
 
 def sgd_step_groups_dev(param, grad, momentum_buf, step_dev, st_dev, sched_dev, sched_out, groups_dev, groups_out, group_map,
                         ema=None, momentum=0.0, dampening=0.0, nesterov=False, grad_scale=1.0, partials=None, max_norm=None):
     """``sgd_step_sched_dev`` with a base rate and a weight decay per parameter group (see ``adam_step_groups_dev``)."""
-    _chk(param, grad, momentum_buf, st_dev)
-    _chk_optim_dev("sgd_step_groups_dev", param.numel(), step_dev, st_dev, partials)
-    _chk_sched("sgd_step_groups_dev", param, sched_dev, sched_out, ema)
-    ng = _chk_groups("sgd_step_groups_dev", param, groups_dev, groups_out, group_map)
-    if momentum != 0.0 and momentum_buf is None:
-        raise _lib.AdyoloHipError("sgd_step_groups_dev with momentum needs a momentum buffer")
-    _c("adyolo_sgd_step_groups_dev", _p(param), _p(grad), _p(momentum_buf if momentum != 0.0 else None), param.numel(),
-       momentum, dampening, int(bool(nesterov)), _p(step_dev), _p(st_dev), _p(partials),
-       _max_norm("sgd_step_groups_dev", partials, max_norm), grad_scale, _p(sched_dev), _p(sched_out), _p(ema),
-       _p(groups_dev), _p(groups_out), ng, _p(group_map), _stream())
+    _optim_step("sgd_step_groups_dev", param, grad, (momentum_buf,), (momentum, dampening, int(bool(nesterov))), step_dev,
+                st_dev, grad_scale, partials, max_norm, (sched_dev, sched_out, ema), (groups_dev, groups_out, group_map),
+                momentum=momentum)
 
 
 def nchw_to_nhwc8(x):

@@ -151,6 +151,9 @@ SIGNATURES = {
     "adyolo_optim_max_groups": (I, []),
     "adyolo_adam_step_groups_dev": (I, [P] * 4 + [L, F, F, F, I, P, P, P, F, F, P, P, P, P, P, I, P, P]),
     "adyolo_sgd_step_groups_dev": (I, [P] * 3 + [L, F, F, I, P, P, P, F, F, P, P, P, P, P, I, P, P]),
+    "adyolo_optim_guard_words": (I, []),
+    "adyolo_adam_step_guard_dev": (I, [P] * 4 + [L, F, F, F, F, F, I, P, P, P, F, F, P, P, P, P, P, I, P, P, P]),
+    "adyolo_sgd_step_guard_dev": (I, [P] * 3 + [L, F, F, F, F, I, P, P, P, F, F, P, P, P, P, P, I, P, P, P]),
 }
 
 _lib = None

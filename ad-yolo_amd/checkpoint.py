@@ -8,8 +8,10 @@ optim_state_dict, confidence_thresh}.  ``model_state_dict`` has the reference's 
 With a learning-rate schedule or an EMA on the optimizer (``train_config['lr_schedule']`` / ``['ema_decay']``), and only then,
 both files gain ``sched_state_dict`` (the optimizer's ``sched_state_dict()``: configuration, current base rate, the schedule's
 step, the EMA's update count) and, with an EMA, ``ema_state_dict``: the layout of ``model_state_dict`` with the parameters taken
-from the EMA and the buffers from the live model, so that the reference loads it as a model.  Without them the files are what
-they always were.
+from the EMA and the buffers from the live model, so that the reference loads it as a model.  With the non-finite guard
+(``train_config['skip_nonfinite']``) both files gain ``guard_state_dict``: {attempts, skipped}, the counts of the optimizer's
+guard record; a file without it loads with zeros, and a file with it loads into an unguarded optimizer, which ignores it.
+Without them the files are what they always were.
 
 Unlike the reference the RNG helpers do not touch ``torch.cuda`` when the device is the CPU.
 """
@@ -124,7 +126,11 @@ def optimizer_state_dict(optimizer, model):
     torch.optim.SGD (``momentum_buffer`` per parameter once a step with momentum was taken, no entries otherwise).  Indices
     follow ``model.parameters()``; with parameter groups there is one torch group per group, each with its own ``lr`` and
     ``weight_decay``, and torch's numbering: consecutive group by group, ``model.parameters()`` order inside a group.
-    ``clip_grad_norm`` is configuration, not state: it is not written."""
+    ``clip_grad_norm`` is configuration, not state: it is not written.  Under the non-finite guard
+    (``train_config['skip_nonfinite']``) the optimizer reconciles first: ``step`` is the number of APPLIED steps, what
+    torch.optim under a ``GradScaler`` would hold."""
+    if getattr(optimizer, "guard_dev", None) is not None:
+        optimizer.reconcile()
     params = _indexed_params(optimizer, model)
     members, ids = _grouping(optimizer, params)
     kind = getattr(optimizer, "kind", "adam")
@@ -254,10 +260,13 @@ def load_ema_state_dict(optimizer, model, sd):
 
 
 def _schedule_entries(optimizer, model, sd):
-    """the keys a scheduled / averaging optimizer adds to a checkpoint file (none otherwise)"""
+    """the keys a scheduled / averaging / guarded optimizer adds to a checkpoint file (none otherwise)"""
+    out = {}
+    if getattr(optimizer, "guard_dev", None) is not None:
+        out["guard_state_dict"] = optimizer.guard_state_dict()
     if getattr(optimizer, "sched_dev", None) is None:
-        return {}
-    out = {"sched_state_dict": optimizer.sched_state_dict()}
+        return out
+    out["sched_state_dict"] = optimizer.sched_state_dict()
     if optimizer.ema is not None:
         out["ema_state_dict"] = ema_state_dict(optimizer, model, sd)
     return out
@@ -328,6 +337,8 @@ def load_checkpoint(path, model, optimizer=None, device="cpu", restore_rng=True)
                 load_ema_state_dict(optimizer, model, ck["ema_state_dict"])
             else:
                 optimizer.restart_ema()
+    if optimizer is not None and getattr(optimizer, "guard_dev", None) is not None:
+        optimizer.load_guard_state_dict(ck.get("guard_state_dict"))
     if restore_rng and ck.get("rng_state") is not None:
         seed_resume(ck["rng_state"], device, model)
     return ck

@@ -20,6 +20,10 @@
 //                LDS through a byte map of the buffer; a group's elements get the bits of FORM_SCHED run on them alone
 // The scheduled forms can also keep an exponential moving average of the parameters in the update launch (template flag EMA:
 // two more streams, none without it).
+// The guarded steps (adyolo_*_step_guard_dev) always run the sum of squares; their prep kernel takes the step only if the fp32
+// norm is finite and otherwise leaves the counter, st[0..1], sched_out and groups_out alone and says so in the guard record,
+// which makes every workgroup of the update kernel return before its first access: a skipped attempt changes nothing, and
+// since the counter did not tick, the next attempt is the step the skipped one would have been.
 // st is 4 floats of device scratch.  All streams move 16 bytes per lane per access (pointers 16-byte aligned, the n & 3 tail
 // elements are done by workgroup 0); grids are capped and grid-stride.  Elements that are zero in parameter, gradient and state
 // (the padding of dist.FlatParameters) stay zero in every kernel.
@@ -132,57 +136,74 @@ __device__ static float sched_lr(const double *__restrict__ tb, unsigned long lo
     return (float)(base * warm * main_f);
 }
 
-// one workgroup of OX_THREADS.  partials == nullptr: clipping off (st[3] = 1, st[2] untouched).  PREP_NORM: no counter, norm only.
+// The guard record (the *_guard entry points): four int64 written only by the prep kernel, by one lane.
+enum { GUARD_ATTEMPTS = 0, GUARD_SKIPPED = 1, GUARD_LAST = 2, GUARD_RUN = 3, GUARD_WORDS = 4 };
+
+// What one lane of the prep kernel does for a step that is taken: the counter += 1 and everything derived from it.
 // sched != nullptr (the *_sched entry points): `lr` is ignored, the step's rate comes from the table and is written with
 // AdamW's decay and the EMA's weight to sched_out.
 // groups != nullptr (the *_groups entry points, which are scheduled forms): the rate is derived once per group from the group's
 // own base (a base of exactly 0 gives 0 without the closed form: cosine divides by the base) and written with what the update
 // needs to groups_out; `wd` is ignored, st[0] and sched_out keep group 0's values.
+// (Inlined at both of its places in the prep kernel: as a function of its own it costs the kernel a call stack in scratch.)
+__device__ __forceinline__ void prep_tick(unsigned long long *__restrict__ step, float *__restrict__ st, int kind, float lr,
+                                          float beta1, float beta2, const double *__restrict__ sched,
+                                          float *__restrict__ sched_out, float wd, const double *__restrict__ groups,
+                                          float *__restrict__ groups_out, int n_groups) {
+    const unsigned long long s = *step + 1ull;
+    *step = s;
+    if (groups != nullptr) {
+        const double bc1 = kind == PREP_ADAM ? 1.0 - pow((double)beta1, (double)s) : 1.0;
+        for (int k = n_groups - 1; k >= 0; --k) {          // group 0 last: lr and wd leave the loop as group 0's
+            const double base = groups[2 * k];
+            wd = (float)groups[2 * k + 1];
+            lr = base == 0.0 ? 0.f : sched_lr(sched, s, base);
+            float *go = groups_out + GROUP_OUT_FLOATS * k;
+            go[GOUT_LR] = lr;
+            go[GOUT_STEP] = kind == PREP_ADAM ? (float)((double)lr / bc1) : lr;
+            go[GOUT_DECAY] = (float)(1.0 - (double)lr * (double)wd);
+            go[GOUT_WD] = wd;
+        }
+        if (kind != PREP_ADAM) wd = 0.f;                   // sched_out's decay is AdamW's: sgd_step passes no wd either
+    }
+    if (sched != nullptr) {
+        if (groups == nullptr) lr = sched_lr(sched, s, sched[SCHED_BASE]);
+        const double k = (double)s - 1.0 + sched[SCHED_EMA_OFFSET];       // EMA updates so far
+        double keep = sched[SCHED_EMA_DECAY];
+        if (sched[SCHED_EMA_WARMUP] != 0.0) keep = fmin(keep, (1.0 + k) / (10.0 + k));
+        sched_out[SOUT_LR] = lr;
+        sched_out[SOUT_DECAY] = (float)(1.0 - (double)lr * (double)wd);
+        sched_out[SOUT_EMA_W] = (float)(1.0 - keep);
+        sched_out[SOUT_EMA_FIRST] = k <= 0.0 ? 1.f : 0.f;
+    }
+    if (kind == PREP_ADAM) {           // {lr / (1 - beta1^t), 1 / sqrt(1 - beta2^t)} in double like torch's host arithmetic
+        const double bc1 = 1.0 - pow((double)beta1, (double)s);
+        const double bc2 = 1.0 - pow((double)beta2, (double)s);
+        st[0] = (float)((double)lr / bc1);
+        st[1] = (float)(1.0 / sqrt(bc2));
+    } else {                           // SGD: the momentum buffer is INITIALISED by the first step (no dampening)
+        st[0] = s == 1ull ? 1.f : 0.f;
+        st[1] = 0.f;
+    }
+}
+
+// one workgroup of OX_THREADS.  partials == nullptr: clipping off (st[3] = 1, st[2] untouched).  PREP_NORM: no counter, norm only.
+// guard != nullptr (the *_guard entry points; partials is then never null): the partials are reduced FIRST and the step is
+// taken only if the fp32 norm is finite.  A skipped step writes st[2] (the offending norm) and the record and nothing else:
+// the counter does not tick, so nothing derived from it (bias corrections, the schedule's clock, the EMA's update count and
+// first-copy flag, SGD's first-step flag) sees the attempt.  A taken step is the unguarded one, value for value; a negative
+// max_norm means clipping off there (st[3] = exactly 1, not max_norm = inf: inf / inf is nan).
 __global__ __launch_bounds__(OX_THREADS) void optim_prep_kernel(unsigned long long *__restrict__ step, float *__restrict__ st,
                                                                 int kind, float lr, float beta1, float beta2,
                                                                 const double *__restrict__ partials, int nparts,
                                                                 float max_norm, const double *__restrict__ sched,
                                                                 float *__restrict__ sched_out, float wd,
                                                                 const double *__restrict__ groups,
-                                                                float *__restrict__ groups_out, int n_groups) {
+                                                                float *__restrict__ groups_out, int n_groups,
+                                                                long long *__restrict__ guard) {
     __shared__ double red[OX_THREADS];
-    if (threadIdx.x == 0 && kind != PREP_NORM) {
-        const unsigned long long s = *step + 1ull;
-        *step = s;
-        if (groups != nullptr) {
-            const double bc1 = kind == PREP_ADAM ? 1.0 - pow((double)beta1, (double)s) : 1.0;
-            for (int k = n_groups - 1; k >= 0; --k) {          // group 0 last: lr and wd leave the loop as group 0's
-                const double base = groups[2 * k];
-                wd = (float)groups[2 * k + 1];
-                lr = base == 0.0 ? 0.f : sched_lr(sched, s, base);
-                float *go = groups_out + GROUP_OUT_FLOATS * k;
-                go[GOUT_LR] = lr;
-                go[GOUT_STEP] = kind == PREP_ADAM ? (float)((double)lr / bc1) : lr;
-                go[GOUT_DECAY] = (float)(1.0 - (double)lr * (double)wd);
-                go[GOUT_WD] = wd;
-            }
-            if (kind != PREP_ADAM) wd = 0.f;                   // sched_out's decay is AdamW's: sgd_step passes no wd either
-        }
-        if (sched != nullptr) {
-            if (groups == nullptr) lr = sched_lr(sched, s, sched[SCHED_BASE]);
-            const double k = (double)s - 1.0 + sched[SCHED_EMA_OFFSET];       // EMA updates so far
-            double keep = sched[SCHED_EMA_DECAY];
-            if (sched[SCHED_EMA_WARMUP] != 0.0) keep = fmin(keep, (1.0 + k) / (10.0 + k));
-            sched_out[SOUT_LR] = lr;
-            sched_out[SOUT_DECAY] = (float)(1.0 - (double)lr * (double)wd);
-            sched_out[SOUT_EMA_W] = (float)(1.0 - keep);
-            sched_out[SOUT_EMA_FIRST] = k <= 0.0 ? 1.f : 0.f;
-        }
-        if (kind == PREP_ADAM) {           // {lr / (1 - beta1^t), 1 / sqrt(1 - beta2^t)} in double like torch's host arithmetic
-            const double bc1 = 1.0 - pow((double)beta1, (double)s);
-            const double bc2 = 1.0 - pow((double)beta2, (double)s);
-            st[0] = (float)((double)lr / bc1);
-            st[1] = (float)(1.0 / sqrt(bc2));
-        } else {                           // SGD: the momentum buffer is INITIALISED by the first step (no dampening)
-            st[0] = s == 1ull ? 1.f : 0.f;
-            st[1] = 0.f;
-        }
-    }
+    if (threadIdx.x == 0 && kind != PREP_NORM && guard == nullptr)
+        prep_tick(step, st, kind, lr, beta1, beta2, sched, sched_out, wd, groups, groups_out, n_groups);
     if (partials == nullptr) {             // (uniform over the workgroup)
         if (threadIdx.x == 0) st[3] = 1.f;
         return;
@@ -197,10 +218,23 @@ __global__ __launch_bounds__(OX_THREADS) void optim_prep_kernel(unsigned long lo
         __syncthreads();
     }
     if (threadIdx.x == 0) {
-        // torch.nn.utils.clip_grad_norm_: clip_coef = max_norm / (total_norm + 1e-6), clamped to 1; fp32; a non-finite norm is
-        // not special-cased (inf -> 0, nan -> nan)
+        // torch.nn.utils.clip_grad_norm_: clip_coef = max_norm / (total_norm + 1e-6), clamped to 1; fp32; without the guard a
+        // non-finite norm is not special-cased (inf -> 0, nan -> nan)
         const float total = (float)sqrt(red[0]);
-        const float coef = max_norm / (total + 1e-6f);
+        float coef = max_norm / (total + 1e-6f);
+        if (guard != nullptr) {
+            const bool skip = !isfinite(total);
+            guard[GUARD_ATTEMPTS] = guard[GUARD_ATTEMPTS] + 1;
+            guard[GUARD_SKIPPED] = guard[GUARD_SKIPPED] + (skip ? 1 : 0);
+            guard[GUARD_LAST] = skip ? 1 : 0;
+            guard[GUARD_RUN] = skip ? guard[GUARD_RUN] + 1 : 0;
+            if (skip) {
+                st[2] = total;
+                return;
+            }
+            prep_tick(step, st, kind, lr, beta1, beta2, sched, sched_out, wd, groups, groups_out, n_groups);
+            if (max_norm < 0.f) coef = 1.f;
+        }
         st[2] = total;
         st[3] = coef > 1.f ? 1.f : coef;
     }
@@ -211,6 +245,12 @@ __global__ __launch_bounds__(OX_THREADS) void optim_prep_kernel(unsigned long lo
 // once per lane from arguments, st and sched_out in FORM_ARG and FORM_SCHED (wave-uniform; no LDS, no barrier), fetched per
 // vector or per element from the LDS copy of groups_out in FORM_GROUPS.
 enum { FORM_ARG = 0, FORM_SCHED = 1, FORM_GROUPS = 2 };
+
+// The guarded step (guard != nullptr): the prep kernel's verdict on this attempt.  Grid-uniform, and asked before the first
+// load, store or barrier of an update kernel: a skipped step's update launch touches nothing.
+__device__ __forceinline__ bool skipped(const long long *__restrict__ guard) {
+    return guard != nullptr && guard[GUARD_LAST] != 0;
+}
 
 // FORM_GROUPS: groups_out goes to LDS once per workgroup (rows past n_groups: rate 0, decay 1); the other forms have no table.
 template <int FORM>
@@ -303,8 +343,10 @@ __global__ __launch_bounds__(OX_THREADS) void adam_update_kernel(float *__restri
                                                                  float grad_scale, const float *__restrict__ st,
                                                                  const float *__restrict__ so, float *__restrict__ ema,
                                                                  const float *__restrict__ groups_out, int n_groups,
-                                                                 const unsigned char *__restrict__ map) {
+                                                                 const unsigned char *__restrict__ map,
+                                                                 const long long *__restrict__ guard) {
     static_assert(FORM != FORM_ARG || !EMA, "the EMA belongs to the scheduled forms");
+    if (skipped(guard)) return;
     const float4 *tab = group_table<FORM>(groups_out, n_groups);
     float4 cu = make_float4(0.f, 0.f, 0.f, 0.f);          // the lane's constants; FORM_GROUPS: unused
     if constexpr (FORM == FORM_SCHED) decay = so[SOUT_DECAY];
@@ -381,8 +423,10 @@ __global__ __launch_bounds__(OX_THREADS) void sgd_update_kernel(float *__restric
                                                                 float keep, int nesterov, float grad_scale,
                                                                 const float *__restrict__ st, const float *__restrict__ so,
                                                                 float *__restrict__ ema, const float *__restrict__ groups_out,
-                                                                int n_groups, const unsigned char *__restrict__ map) {
+                                                                int n_groups, const unsigned char *__restrict__ map,
+                                                                const long long *__restrict__ guard) {
     static_assert(FORM != FORM_ARG || !EMA, "the EMA belongs to the scheduled forms");
+    if (skipped(guard)) return;
     const float4 *tab = group_table<FORM>(groups_out, n_groups);
     float4 cu = make_float4(0.f, 0.f, 0.f, 0.f);          // the lane's constants; FORM_GROUPS: unused
     if constexpr (FORM == FORM_SCHED) lr = so[SOUT_LR];
@@ -431,15 +475,16 @@ static int launch_sumsq(const float *grad, long n, float grad_scale, double *par
 
 static int launch_prep(uint64_t *step_dev, float *st_dev, int kind, float lr, float beta1, float beta2, const double *partials,
                        long n, float max_norm, hipStream_t st, const double *sched = nullptr, float *sched_out = nullptr,
-                       float wd = 0.f, const double *groups = nullptr, float *groups_out = nullptr, int n_groups = 0) {
+                       float wd = 0.f, const double *groups = nullptr, float *groups_out = nullptr, int n_groups = 0,
+                       int64_t *guard = nullptr) {
     hipLaunchKernelGGL(optim_prep_kernel, dim3(1), dim3(OX_THREADS), 0, st, reinterpret_cast<unsigned long long *>(step_dev),
                        st_dev, kind, lr, beta1, beta2, partials, partials ? sumsq_grid(n) : 0, max_norm, sched, sched_out, wd,
-                       groups, groups_out, n_groups);
+                       groups, groups_out, n_groups, reinterpret_cast<long long *>(guard));
     return check_launch("optim_prep");
 }
 
 // What a step's entry point adds to the plain form: all null in FORM_ARG; the table, sched_out and (optionally) the EMA in
-// FORM_SCHED and FORM_GROUPS; the groups in FORM_GROUPS.
+// FORM_SCHED and FORM_GROUPS; the groups in FORM_GROUPS.  guard: the record of the *_guard entry points, null elsewhere.
 struct StepForm {
     int form;
     const double *sched;
@@ -448,6 +493,7 @@ struct StepForm {
     float *groups_out;
     int n_groups;
     const unsigned char *map;
+    int64_t *guard;
 };
 
 // a kernel's five instantiations (for one value of its first template parameter) are kept in the order of this index
@@ -477,7 +523,7 @@ static auto sgd_kernel(const StepForm &f) {
     return five[form_index(f)];
 }
 
-// The argument checks of the six step entry points; `what` is the entry point's name.  present / aligned: what the rule says
+// The argument checks of the step entry points; `what` is the entry point's name.  present / aligned: what the rule says
 // about its own buffers (parameters, gradient, state, counter, scratch); the form's buffers are checked here.
 static int check_step(const char *what, bool present, bool aligned, long n, const StepForm &f) {
     const bool sched = f.form != FORM_ARG;
@@ -489,10 +535,11 @@ static int check_step(const char *what, bool present, bool aligned, long n, cons
                         (reinterpret_cast<uintptr_t>(f.groups) & 7) == 0 && aligned16(f.groups_out) &&
                         (reinterpret_cast<uintptr_t>(f.map) & 3) == 0),
                    ADYOLO_EINVAL, "%s: 1 to 16 groups, groups_dev 8-byte, groups_out 16-byte and the map 4-byte aligned", what);
+    ADYOLO_REQUIRE((reinterpret_cast<uintptr_t>(f.guard) & 7) == 0, ADYOLO_EINVAL, "%s: the guard record not 8-byte aligned", what);
     return 0;
 }
 
-// the Adam / AdamW step behind its three entry points: check, sum of squares (clipping only), prep, update.  FORM_ARG: lr is
+// the Adam / AdamW step behind its entry points: check, sum of squares (clipping only), prep, update.  FORM_ARG: lr is
 // the argument (and decay formed from it here); else lr is ignored, and in FORM_GROUPS weight_decay too
 static int adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, long n, float lr, float beta1,
                      float beta2, float eps, float weight_decay, int decoupled, uint64_t *step_dev, float *st_dev,
@@ -503,13 +550,13 @@ static int adam_step(float *param, const float *grad, float *exp_avg, float *exp
         return rc;
     if (partials && (rc = launch_sumsq(grad, n, grad_scale, partials, st))) return rc;
     if ((rc = launch_prep(step_dev, st_dev, PREP_ADAM, lr, beta1, beta2, partials, n, max_norm, st, f.sched, f.sched_out,
-                          weight_decay, f.groups, f.groups_out, f.n_groups)))
+                          weight_decay, f.groups, f.groups_out, f.n_groups, f.guard)))
         return rc;
     const float decay = (float)(1.0 - (double)lr * (double)weight_decay);
     auto kernel = decoupled ? adam_kernel<true>(f) : adam_kernel<false>(f);
     hipLaunchKernelGGL(kernel, dim3(update_grid(n)), dim3(OX_THREADS), 0, st, param, grad, exp_avg, exp_avg_sq, n, beta1, beta2,
                        eps, weight_decay, decay, grad_scale, (const float *)st_dev, (const float *)f.sched_out, f.ema,
-                       (const float *)f.groups_out, f.n_groups, f.map);
+                       (const float *)f.groups_out, f.n_groups, f.map, (const long long *)f.guard);
     return check_launch(what);
 }
 
@@ -522,14 +569,15 @@ static int sgd_step(float *param, const float *grad, float *momentum_buf, long n
         return rc;
     if (partials && (rc = launch_sumsq(grad, n, grad_scale, partials, st))) return rc;
     if ((rc = launch_prep(step_dev, st_dev, PREP_SGD, lr, 0.f, 0.f, partials, n, max_norm, st, f.sched, f.sched_out, 0.f,
-                          f.groups, f.groups_out, f.n_groups)))
+                          f.groups, f.groups_out, f.n_groups, f.guard)))
         return rc;
     const float keep = (float)(1.0 - (double)dampening);
     const bool mom = momentum != 0.f;
     auto kernel = mom ? sgd_kernel<true>(f) : sgd_kernel<false>(f);
     hipLaunchKernelGGL(kernel, dim3(update_grid(n)), dim3(OX_THREADS), 0, st, param, grad, mom ? momentum_buf : (float *)nullptr,
                        n, lr, weight_decay, mom ? momentum : 0.f, keep, nesterov, grad_scale, (const float *)st_dev,
-                       (const float *)f.sched_out, f.ema, (const float *)f.groups_out, f.n_groups, f.map);
+                       (const float *)f.sched_out, f.ema, (const float *)f.groups_out, f.n_groups, f.map,
+                       (const long long *)f.guard);
     return check_launch(what);
 }
 
@@ -611,4 +659,51 @@ extern "C" int adyolo_sgd_step_groups_dev(float *param, const float *grad, float
     return sgd_step(param, grad, momentum_buf, n, 0.f, 0.f, momentum, dampening, nesterov, step_dev, st_dev, partials, max_norm,
                     grad_scale, StepForm{FORM_GROUPS, sched_dev, sched_out, ema, groups_dev, groups_out, n_groups, group_map},
                     as_stream(stream), "sgd_step_groups_dev");
+}
+
+// The guarded steps: one entry point per rule.  The form is read from the pointers -- groups_dev: grouped (lr and
+// weight_decay ignored); else sched_dev: scheduled (lr ignored); else plain (ema must be null) -- and handed to the same
+// adam_step / sgd_step.  The sum of squares always runs (partials is required); max_norm < 0: no clipping.
+extern "C" int adyolo_optim_guard_words(void) { return GUARD_WORDS; }
+
+static int guard_form(const char *what, const double *sched_dev, float *sched_out, float *ema, const double *groups_dev,
+                      float *groups_out, int n_groups, const unsigned char *group_map, int64_t *guard, const double *partials,
+                      StepForm *f) {
+    ADYOLO_REQUIRE(guard && partials, ADYOLO_EINVAL, "%s: needs the guard record and the partials", what);
+    ADYOLO_REQUIRE(sched_dev || (!groups_dev && !ema), ADYOLO_EINVAL, "%s: groups and the EMA need a schedule table", what);
+    const int form = groups_dev ? FORM_GROUPS : (sched_dev ? FORM_SCHED : FORM_ARG);
+    *f = StepForm{form, sched_dev, sched_out, ema};
+    if (form == FORM_GROUPS) *f = StepForm{form, sched_dev, sched_out, ema, groups_dev, groups_out, n_groups, group_map};
+    f->guard = guard;
+    return 0;
+}
+
+extern "C" int adyolo_adam_step_guard_dev(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, long n, float lr,
+                                          float beta1, float beta2, float eps, float weight_decay, int decoupled,
+                                          uint64_t *step_dev, float *st_dev, double *partials, float max_norm,
+                                          float grad_scale, const double *sched_dev, float *sched_out, float *ema,
+                                          const double *groups_dev, float *groups_out, int n_groups,
+                                          const unsigned char *group_map, int64_t *guard, void *stream) {
+    StepForm f;
+    int rc = guard_form("adam_step_guard_dev", sched_dev, sched_out, ema, groups_dev, groups_out, n_groups, group_map, guard,
+                        partials, &f);
+    if (rc) return rc;
+    return adam_step(param, grad, exp_avg, exp_avg_sq, n, f.form == FORM_ARG ? lr : 0.f, beta1, beta2, eps,
+                     f.form == FORM_GROUPS ? 0.f : weight_decay, decoupled, step_dev, st_dev, partials, max_norm, grad_scale, f,
+                     as_stream(stream), "adam_step_guard_dev");
+}
+
+extern "C" int adyolo_sgd_step_guard_dev(float *param, const float *grad, float *momentum_buf, long n, float lr,
+                                         float weight_decay, float momentum, float dampening, int nesterov, uint64_t *step_dev,
+                                         float *st_dev, double *partials, float max_norm, float grad_scale,
+                                         const double *sched_dev, float *sched_out, float *ema, const double *groups_dev,
+                                         float *groups_out, int n_groups, const unsigned char *group_map, int64_t *guard,
+                                         void *stream) {
+    StepForm f;
+    int rc = guard_form("sgd_step_guard_dev", sched_dev, sched_out, ema, groups_dev, groups_out, n_groups, group_map, guard,
+                        partials, &f);
+    if (rc) return rc;
+    return sgd_step(param, grad, momentum_buf, n, f.form == FORM_ARG ? lr : 0.f, f.form == FORM_GROUPS ? 0.f : weight_decay,
+                    momentum, dampening, nesterov, step_dev, st_dev, partials, max_norm, grad_scale, f, as_stream(stream),
+                    "sgd_step_guard_dev");
 }

@@ -138,6 +138,7 @@ class StepGraphs:
         ent.n_replays = 0
         self._load(ent, audio, target, spec)
         # host-side state the captured step advances: put back afterwards (recording runs nothing), re-applied per replay
+        tr.optimizer.reconcile()                    # (non-finite guard: skipped steps leave the mirror first)
         step0 = tr.optimizer.step_count
         tr.optimizer.sync_device_step()
         for s in self.streams:
@@ -162,6 +163,7 @@ class StepGraphs:
             raise
         finally:
             ent.deltas = [s.end_capture() for s in self.streams]
+            tr.optimizer._guard_dirty = False       # the recorded attempt was not made: the guard's record has not moved
             tr.optimizer.step_count = step0
             tr.optimizer._dev_step_value = step0
         ent.graph, ent.loss = graph, loss

@@ -1171,11 +1171,13 @@ def _max_norm(what, partials, max_norm):
 
 
 def _optim_step(what, param, grad, states, hyper, step_dev, st_dev, grad_scale, partials, max_norm, sched=(), groups=(),
-                momentum=None):
+                momentum=None, guard=None):
     """The checks and the call behind every optimizer wrapper below.  ``what``: the wrapper's name, in errors and (as
     ``adyolo_<what>``) the entry point.  states: the rule's state buffers; hyper: its scalars, in the entry point's order;
     sched: (sched_dev, sched_out, ema) of the scheduled forms; groups: (groups_dev, groups_out, group_map) of the grouped
-    ones; momentum: SGD's, whose one state buffer is needed, and passed on, only when it is not 0."""
+    ones; momentum: SGD's, whose one state buffer is needed, and passed on, only when it is not 0; guard: the record of the
+    guarded entry points, which take every form's arguments (null where the form has none) and a negative max_norm for
+    "no clipping"."""
     _chk(param, grad, *states, st_dev)
     _chk_optim_dev(what, param.numel(), step_dev, st_dev, partials)
     form = ()                         # what the entry point takes after grad_scale: sched_dev, sched_out, ema, then
@@ -1189,9 +1191,20 @@ def _optim_step(what, param, grad, states, hyper, step_dev, st_dev, grad_scale, 
         raise _lib.AdyoloHipError("%s with momentum needs a momentum buffer" % what)
     if momentum == 0.0:
         states = (None,)              # SGD without momentum: the buffer is not passed on
+    if guard is not None:             # every form's arguments, null where the form has none
+        if not sched:
+            form = (_p(None),) * 3
+        if not groups:
+            form += (_p(None), _p(None), 0, _p(None))
+        form += (_p(guard),)
+        if max_norm is not None and not float(max_norm) >= 0.0:
+            raise _lib.AdyoloHipError("%s: max_norm must not be negative (None = no clipping)" % what)
+        norm = -1.0 if max_norm is None else float(max_norm)
+    else:
+        norm = _max_norm(what, partials, max_norm)
     # every step entry point: param, grad, state..., n, hyper..., step_dev, st_dev, partials, max_norm, grad_scale, form..., stream
     _c("adyolo_" + what, _p(param), _p(grad), *map(_p, states), param.numel(), *hyper, _p(step_dev), _p(st_dev), _p(partials),
-       _max_norm(what, partials, max_norm), grad_scale, *form, _stream())
+       norm, grad_scale, *form, _stream())
 
 
 def grad_sumsq(grad, partials, grad_scale=1.0):
@@ -1315,6 +1328,56 @@ def sgd_step_groups_dev(param, grad, momentum_buf, step_dev, st_dev, sched_dev, 
     _optim_step("sgd_step_groups_dev", param, grad, (momentum_buf,), (momentum, dampening, int(bool(nesterov))), step_dev,
                 st_dev, grad_scale, partials, max_norm, (sched_dev, sched_out, ema), (groups_dev, groups_out, group_map),
                 momentum=momentum)
+
+
+# The guarded steps (include/adyolo_hip.h, "The guarded steps"): a step that does nothing when the gradient is not finite
+OPTIM_GUARD_WORDS = 4             # int64 elements of the guard record: {attempts, skipped, last skipped, run} (adyolo_optim_guard_words())
+
+
+def _chk_guard(what, param, guard, partials):
+    if (guard is None or not guard.is_cuda or guard.dtype != torch.int64 or not guard.is_contiguous()
+            or guard.numel() < OPTIM_GUARD_WORDS or guard.device != param.device):
+        raise _lib.AdyoloHipError("%s needs a guard record of %d contiguous int64 on the parameters' device"
+                                  % (what, OPTIM_GUARD_WORDS))
+    if partials is None:
+        raise _lib.AdyoloHipError("%s needs float64 partials: the guard always sums the squares" % what)
+
+
+def _guard_forms(what, sched_dev, sched_out, ema, groups_dev, groups_out, group_map):
+    """-> (sched, groups) for ``_optim_step``: what is not None decides the form, as in the entry point"""
+    if sched_dev is None and (groups_dev is not None or ema is not None or sched_out is not None):
+        raise _lib.AdyoloHipError("%s: groups, sched_out and the EMA need sched_dev" % what)
+    if (groups_dev is None) != (groups_out is None) or (groups_dev is None) != (group_map is None):
+        raise _lib.AdyoloHipError("%s: groups_dev, groups_out and group_map go together" % what)
+    sched = () if sched_dev is None else (sched_dev, sched_out, ema)
+    return sched, (() if groups_dev is None else (groups_dev, groups_out, group_map))
+
+
+def adam_step_guard_dev(param, grad, exp_avg, exp_avg_sq, step_dev, st_dev, guard, partials, lr=1e-3, betas=(0.9, 0.999),
+                        eps=1e-8, weight_decay=0.0, grad_scale=1.0, max_norm=None, decoupled=False, sched_dev=None,
+                        sched_out=None, ema=None, groups_dev=None, groups_out=None, group_map=None):
+    """``adam_step_dev`` / ``adam_step_sched_dev`` / ``adam_step_groups_dev`` (sched_dev / groups_dev given or not decide which;
+    lr is ignored with sched_dev, weight_decay with groups_dev) behind the non-finite guard: the sum of squares always runs
+    (partials is required; max_norm None = no clipping, coefficient exactly 1), st_dev[2] is the norm of every attempt, and
+    when it is not finite the call changes nothing but st_dev[2] and guard (``OPTIM_GUARD_WORDS`` int64: attempts, skipped,
+    last attempt skipped, run of consecutive skips) -- step_dev does not tick.  A finite gradient gives the unguarded bits."""
+    what = "adam_step_guard_dev"
+    _chk_guard(what, param, guard, partials)
+    sched, groups = _guard_forms(what, sched_dev, sched_out, ema, groups_dev, groups_out, group_map)
+    _optim_step(what, param, grad, (exp_avg, exp_avg_sq), (lr, betas[0], betas[1], eps, weight_decay, int(bool(decoupled))),
+                step_dev, st_dev, grad_scale, partials, max_norm, sched, groups, guard=guard)
+
+
+def sgd_step_guard_dev(param, grad, momentum_buf, step_dev, st_dev, guard, partials, lr=1e-3, weight_decay=0.0, momentum=0.0,
+                       dampening=0.0, nesterov=False, grad_scale=1.0, max_norm=None, sched_dev=None, sched_out=None, ema=None,
+                       groups_dev=None, groups_out=None, group_map=None):
+    """``sgd_step_dev`` / ``sgd_step_sched_dev`` / ``sgd_step_groups_dev`` behind the non-finite guard (see
+    ``adam_step_guard_dev``); a skipped first attempt leaves the next one the first (the momentum buffer's initialisation)."""
+    what = "sgd_step_guard_dev"
+    _chk_guard(what, param, guard, partials)
+    sched, groups = _guard_forms(what, sched_dev, sched_out, ema, groups_dev, groups_out, group_map)
+    _optim_step(what, param, grad, (momentum_buf,), (lr, weight_decay, momentum, dampening, int(bool(nesterov))), step_dev,
+                st_dev, grad_scale, partials, max_norm, sched, groups, momentum=momentum, guard=guard)
 
 
 def nchw_to_nhwc8(x):

@@ -61,22 +61,40 @@ class _FusedOptimizer:
     mirrors them on the host; ``set_lr(x, group=)`` / ``set_weight_decay(x, group=)`` (index or name) rewrite ``groups_dev``
     and hold from the next step on, eager or replayed -- a group built with rate 0 and decay 0 keeps its parameters bit for
     bit (its moments still move, its gradient still counts in the norm) until ``set_lr`` releases it.  ``lr`` and
-    ``weight_decay`` mirror group 0's."""
+    ``weight_decay`` mirror group 0's.
+
+    skip_nonfinite (False = off: the entry points above, nothing more allocated): the step is ``ops.*_step_guard_dev``, which
+    does NOTHING when the gradient is not finite -- the test is the fp32 total norm of ``grad * grad_scale``, so the sum of
+    squares always runs (``clip_partials`` is allocated and ``grad_norm`` available with or without ``max_norm``), and it is
+    made on the device inside the (recorded) step: a skipped attempt leaves parameters, state, EMA and the device counter
+    untouched, so bias corrections, the schedule's clock, the EMA's count and SGD's first-step flag continue as if the batch
+    had never been drawn.  ``guard_dev`` (int64, ``ops.OPTIM_GUARD_WORDS``) is the device's record {attempts, skipped, last
+    attempt skipped, run of consecutive skips}.  The host cannot see a skip without reading it, so ``step_count`` counts
+    ATTEMPTS until ``reconcile()`` is called: it takes the record's host copy (or reads it: one sync), subtracts the skips
+    it has not seen yet from ``step_count`` and returns ``{attempts, skipped, last_skipped, run}``; ``lr_at(step_count)``,
+    ``sched_step`` and ``ema_updates`` then agree with the device.  Everything that saves the counter or writes the device
+    counter from the mirror reconciles first (``state_dict``, ``sched_state_dict``, setting ``step_count``, the fill of
+    ``sync_device_step``, a graph capture).  Under data parallelism every rank holds the same reduced buffer and sums it in the
+    same order, so every rank takes the same decision with no collective.  The guard protects what the optimizer owns:
+    BatchNorm running statistics are written by the forward pass and are not rolled back."""
 
     kind = None                     # 'adam' | 'adamw' | 'sgd': the torch.optim layout ``checkpoint`` reads and writes
 
-    def _init_common(self, flat, max_norm):
+    def _init_common(self, flat, max_norm, skip_nonfinite=False):
         self.flat = flat
         self.max_norm = None if max_norm is None else float(max_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
         dev = flat.flat.device
         self.step_dev = torch.zeros(1, dtype=torch.int64, device=dev)
         self._step_count = 0
         self._dev_step_value = 0
         self.st_dev = torch.zeros(ops.OPTIM_SCRATCH_FLOATS, dtype=torch.float32, device=dev)
         self.clip_partials = self.grad_norm = None
-        if self.max_norm is not None:
+        if self.max_norm is not None or self.skip_nonfinite:
             self.clip_partials = torch.zeros(ops.GRAD_SUMSQ_MAX_PARTS, dtype=torch.float64, device=dev)
             self.grad_norm = self.st_dev[2:3]
+        if self.skip_nonfinite:
+            self.guard_dev = torch.zeros(ops.OPTIM_GUARD_WORDS, dtype=torch.int64, device=dev)
 
     @property
     def step_count(self):
@@ -84,18 +102,63 @@ class _FusedOptimizer:
 
     @step_count.setter
     def step_count(self, v):
+        self.reconcile()                  # (guarded: skips not seen yet belong to the old value, not to the new one)
         self._step_count = int(v)
 
     def sync_device_step(self):
         if self._dev_step_value != self._step_count:
+            self.reconcile()
             self.step_dev.fill_(self._step_count)
             self._dev_step_value = self._step_count
 
     def replayed(self):
-        """A captured step (graph.py) was replayed: the optimizer launch inside it advanced the device counter."""
+        """A captured step (graph.py) was replayed: the optimizer launch inside it advanced the device counter (guarded: unless
+        it skipped, which ``reconcile`` corrects later)."""
         self._step_count += 1
         self._dev_step_value = self._step_count
+        self._guard_dirty = True
         ops.params_changed()
+
+    # ------------------------------------------------------------------------------------------ non-finite guard
+    guard_dev = None
+    skip_nonfinite = False
+    _guard_seen = 0                 # skips of the record that ``step_count`` has been corrected for
+    _guard_dirty = False            # an attempt was made since the record was last read
+    _guard_record = (0, 0, 0, 0)    # the record as last seen
+
+    def reconcile(self, guard=None):
+        """guard: a host copy of ``guard_dev`` fetched after the last attempt (None: it is read here, one sync, and only if an
+        attempt was made since the last time).  Subtracts the skips not yet seen from ``step_count`` and from the mirror of the
+        device counter's value, once.  -> {attempts, skipped, last_skipped, run}; all zero on an unguarded optimizer."""
+        if self.guard_dev is None:
+            return {"attempts": 0, "skipped": 0, "last_skipped": False, "run": 0}
+        if guard is not None:
+            self._guard_record = tuple(int(x) for x in guard.reshape(-1)[:4].tolist())
+        elif self._guard_dirty:
+            self._guard_record = tuple(int(x) for x in self.guard_dev.tolist())
+        self._guard_dirty = False
+        attempts, skipped, last, run = self._guard_record
+        unseen = skipped - self._guard_seen
+        if unseen:
+            self._step_count -= unseen
+            self._dev_step_value -= unseen
+            self._guard_seen = skipped
+        return {"attempts": attempts, "skipped": skipped, "last_skipped": bool(last), "run": run}
+
+    def guard_state_dict(self):
+        """the counts a checkpoint carries (``checkpoint`` writes them as ``guard_state_dict``)"""
+        rec = self.reconcile()
+        return {"attempts": rec["attempts"], "skipped": rec["skipped"]}
+
+    def load_guard_state_dict(self, sd=None):
+        """the record continues from a checkpoint's counts (None or a file without them: zeros); the flag and the run start
+        clean.  ``step_count`` is not touched: the loaded optimizer state already holds the number of APPLIED steps."""
+        self.reconcile()
+        sd = sd or {}
+        rec = (int(sd.get("attempts", 0)), int(sd.get("skipped", 0)), 0, 0)
+        if self.guard_dev is not None:
+            self.guard_dev.copy_(torch.tensor(rec, dtype=torch.int64))
+            self._guard_record, self._guard_seen, self._guard_dirty = rec, rec[1], False
 
     # ------------------------------------------------------------------------------------------ schedule / EMA
     sched_config = sched_dev = sched_out = current_lr = ema = ema_decay = None
@@ -220,6 +283,7 @@ class _FusedOptimizer:
     def sched_state_dict(self):
         """configuration, current base rate(s) and clocks of the schedule / EMA (``checkpoint`` writes it beside the
         optimizer's)"""
+        self.reconcile()
         sd = {"config": dict(self.sched_config), "base_lr": self.lr, "step": self.sched_step,
               "ema_decay": self.ema_decay, "ema_warmup": self.ema_warmup, "ema_updates": self.ema_updates}
         if self.groups is not None:
@@ -260,6 +324,7 @@ class _FusedOptimizer:
         self._launch(grad_scale)
         self._step_count += 1
         self._dev_step_value = self._step_count
+        self._guard_dirty = True
         ops.params_changed()
 
     def state_dict(self):
@@ -284,14 +349,19 @@ class FusedAdam(_FusedOptimizer):
     kind = "adam"
 
     def __init__(self, flat: FlatParameters, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_norm=None,
-                 lr_schedule=None, ema_decay=None, ema_warmup=False, param_groups=None):
+                 lr_schedule=None, ema_decay=None, ema_warmup=False, param_groups=None, skip_nonfinite=False):
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         self.exp_avg = torch.zeros_like(flat.flat)
         self.exp_avg_sq = torch.zeros_like(flat.flat)
-        self._init_common(flat, max_norm)
+        self._init_common(flat, max_norm, skip_nonfinite)
         self._init_sched(lr_schedule, ema_decay, ema_warmup, param_groups)
 
     def _launch(self, grad_scale):
+        if self.guard_dev is not None:
+            return ops.adam_step_guard_dev(self.flat.flat, self.flat.flat_grad, self.exp_avg, self.exp_avg_sq, self.step_dev,
+                                           self.st_dev, self.guard_dev, self.clip_partials, self.lr, self.betas, self.eps,
+                                           self.weight_decay, grad_scale, self.max_norm, self.kind == "adamw", self.sched_dev,
+                                           self.sched_out, self.ema, self.groups_dev, self.groups_out, self.group_map)
         if self.groups is not None:
             return ops.adam_step_groups_dev(self.flat.flat, self.flat.flat_grad, self.exp_avg, self.exp_avg_sq, self.step_dev,
                                             self.st_dev, self.sched_dev, self.sched_out, self.groups_dev, self.groups_out,
@@ -314,8 +384,9 @@ class FusedAdamW(FusedAdam):
     kind = "adamw"
 
     def __init__(self, flat: FlatParameters, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_norm=None,
-                 lr_schedule=None, ema_decay=None, ema_warmup=False, param_groups=None):
-        super().__init__(flat, lr, betas, eps, weight_decay, max_norm, lr_schedule, ema_decay, ema_warmup, param_groups)
+                 lr_schedule=None, ema_decay=None, ema_warmup=False, param_groups=None, skip_nonfinite=False):
+        super().__init__(flat, lr, betas, eps, weight_decay, max_norm, lr_schedule, ema_decay, ema_warmup, param_groups,
+                         skip_nonfinite)
 
 
 class FusedSGD(_FusedOptimizer):
@@ -329,10 +400,10 @@ class FusedSGD(_FusedOptimizer):
     kind = "sgd"
 
     def __init__(self, flat: FlatParameters, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False,
-                 max_norm=None, lr_schedule=None, ema_decay=None, ema_warmup=False, param_groups=None):
+                 max_norm=None, lr_schedule=None, ema_decay=None, ema_warmup=False, param_groups=None, skip_nonfinite=False):
         if nesterov and (momentum <= 0 or dampening != 0):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
-        self._init_common(flat, max_norm)
+        self._init_common(flat, max_norm, skip_nonfinite)
         self.lr, self.momentum, self.dampening, self.weight_decay = lr, momentum, dampening, weight_decay
         self.nesterov = bool(nesterov)
         self.momentum_buffer = torch.zeros_like(flat.flat) if momentum != 0 else None
@@ -344,6 +415,11 @@ class FusedSGD(_FusedOptimizer):
         return self._step_count == 0
 
     def _launch(self, grad_scale):
+        if self.guard_dev is not None:
+            return ops.sgd_step_guard_dev(self.flat.flat, self.flat.flat_grad, self.momentum_buffer, self.step_dev, self.st_dev,
+                                          self.guard_dev, self.clip_partials, self.lr, self.weight_decay, self.momentum,
+                                          self.dampening, self.nesterov, grad_scale, self.max_norm, self.sched_dev,
+                                          self.sched_out, self.ema, self.groups_dev, self.groups_out, self.group_map)
         if self.groups is not None:
             return ops.sgd_step_groups_dev(self.flat.flat, self.flat.flat_grad, self.momentum_buffer, self.step_dev, self.st_dev,
                                            self.sched_dev, self.sched_out, self.groups_dev, self.groups_out, self.group_map,
@@ -365,7 +441,10 @@ def get_optimizers(params: dict, flat: FlatParameters):
     ``{name: constant | step | multistep | exponential | cosine, every, warmup_steps, warmup_start_factor, ...}``, see
     ``lr_schedule.py``; absent = the rate is a constant of the step), ``ema_decay`` (absent = no averaged weights) and
     ``ema_warmup`` (default false); ``param_groups`` (a list of at most 15 entries ``{name, match, ndim_max, lr,
-    weight_decay}``, see ``param_groups.py``; absent or empty = one rate and one decay for all parameters)."""
+    weight_decay}``, see ``param_groups.py``; absent or empty = one rate and one decay for all parameters);
+    ``skip_nonfinite`` (default false: today's step; true: a step whose gradient is not finite is skipped on the device, see
+    ``_FusedOptimizer``) and ``skip_nonfinite_patience`` (default 10, None = off: the epoch loops raise FloatingPointError
+    when an epoch ends in that many consecutive skipped steps)."""
     tc = params["train_config"]
     name = tc.get("optim", "Adam")
     if name not in ("Adam", "AdamW", "SGD"):
@@ -376,6 +455,8 @@ def get_optimizers(params: dict, flat: FlatParameters):
     groups = _pgroups.resolve(tc.get("param_groups"), flat, lr, wd)
     if groups is not None:
         extra["param_groups"] = groups
+    if tc.get("skip_nonfinite", False):
+        extra["skip_nonfinite"] = True
     if name == "Adam":
         return FusedAdam(flat, lr=lr, weight_decay=wd, max_norm=clip, **extra)
     if name == "AdamW":
@@ -507,15 +588,58 @@ def train_one_epoch(params: dict, dataloader, model, optimizer, criterion, devic
     return float(total) / max(n, 1) if total is not None else 0.0
 
 
+class _EpochLoss:
+    """The running loss of the raw-audio epoch loops, kept on the device and read ONCE at the end of the epoch.
+
+    Without the non-finite guard (``train_config['skip_nonfinite']``): the sum of the steps' losses over their number.  With
+    it: a step's loss counts only when the step was applied -- chosen by ``torch.where`` on the flag of the optimizer's guard
+    record (a multiply would not do: NaN * 0 is NaN) -- the applied steps are counted on the device, the mean is over them,
+    and the record comes to the host in the same read, where the optimizer reconciles its ``step_count`` with it.  An epoch
+    that ENDS in ``train_config['skip_nonfinite_patience']`` (default 10; None = never) or more consecutive skipped steps
+    raises FloatingPointError: a model whose weights are already not finite would otherwise skip for ever in silence."""
+
+    def __init__(self, params, trainer):
+        self.optimizer = getattr(trainer, "optimizer", None)
+        self.guard = getattr(self.optimizer, "guard_dev", None)
+        self.patience = params.get("train_config", {}).get("skip_nonfinite_patience", 10)
+        self.total = self.applied = None
+        self.n = 0
+
+    def add(self, loss):
+        loss = loss.detach().reshape(-1)[:1]
+        if self.guard is not None:
+            ok = self.guard[2:3] == 0
+            loss = torch.where(ok, loss, torch.zeros_like(loss))
+            self.applied = ok.to(torch.int64) if self.applied is None else self.applied + ok
+        self.total = loss.clone() if self.total is None else self.total + loss
+        self.n += 1
+
+    def mean(self, *also):
+        """-> (the mean loss, host copies of ``also``) with one device read"""
+        if self.total is None:
+            return 0.0, list(also)
+        mine = (self.total,) if self.guard is None else (self.total, self.applied, self.guard)
+        host = ops.to_host_many(*mine, *also) if self.total.is_cuda else [t.clone() for t in mine + also]
+        if self.guard is None:
+            return float(host[0][0]) / max(self.n, 1), host[1:]
+        total, applied, rec = float(host[0][0]), int(host[1][0]), self.optimizer.reconcile(host[2])
+        if self.patience is not None and rec["run"] >= int(self.patience):
+            raise FloatingPointError("the epoch ended in %d consecutive optimizer steps skipped for a non-finite gradient "
+                                     "(skip_nonfinite_patience %d): %d of this epoch's %d steps were applied; %d of %d attempts "
+                                     "skipped since the start" % (rec["run"], int(self.patience), applied, self.n,
+                                                                  rec["skipped"], rec["attempts"]))
+        return total / max(applied, 1), host[3:]
+
+
 def train_one_epoch_audio(params: dict, dataloader, trainer, stager=None, rotate=True):
     """The raw-audio epoch: ``dataloader`` yields ``audio_collate_fn`` batches (pcm int16 (B,T,4), comb_nos, target[, SpecAug
     tables (B,2,4)]); each is staged to the GPU (int16 over PCIe on a side stream, double-buffered), converted, rotated and
     handed with its tables to ``TrainStep.step`` (features [+ SpecAug masks] + forward + loss + backward [+ all-reduce] +
     Adam).  Returns the mean loss with ONE device sync at the end of the epoch (the reference syncs every iteration,
-    train.py:57)."""
+    train.py:57); with ``train_config['skip_nonfinite']`` the mean over the APPLIED steps (``_EpochLoss``)."""
     from .augmentations import rotate_audio
     from .datasets import AudioStager
-    total, n = None, 0
+    acc, n = _EpochLoss(params, trainer), 0
     it = iter(dataloader)
     try:
         pcm, combs, target, *spec = next(it)
@@ -533,12 +657,11 @@ def train_one_epoch_audio(params: dict, dataloader, trainer, stager=None, rotate
             stager.stage(pcm)
         if rotate and any(int(c) != 0 for c in cur_combs):
             audio = rotate_audio(audio, cur_combs)
-        loss = trainer.step(audio, cur_target, cur_spec)
-        total = loss.detach().reshape(-1)[:1].clone() if total is None else total + loss.detach().reshape(-1)[:1]
+        acc.add(trainer.step(audio, cur_target, cur_spec))
         n += 1
         if nxt is None or (params.get("args", {}).get("quick_test") and n == 5):
             break
-    return float(total) / max(n, 1)
+    return acc.mean()[0]
 
 
 def train_one_epoch_corpus(params: dict, corpus, trainer):
@@ -549,7 +672,8 @@ def train_one_epoch_corpus(params: dict, corpus, trainer):
     exists (eager launches before the replay, no copy).  The host draws of batch k+1 (rotation, SpecAug) happen while step k
     runs, in the order the host path draws them.  Returns the mean loss with ONE device sync at the end, where the corpus' status
     word is read too: a batch with more rows than the capacity, an item outside the corpus or a class outside the model's
-    raises."""
+    raises.  With ``train_config['skip_nonfinite']``: the mean over the APPLIED steps, the guard record in the same read
+    (``_EpochLoss``)."""
     bs = int(params["train_config"]["batch_size"])
     files = corpus.get_filelist()
     starts = list(range(0, len(files), bs))
@@ -557,7 +681,7 @@ def train_one_epoch_corpus(params: dict, corpus, trainer):
         return 0.0
     graphs = trainer.graphs
     corpus.reset_status()
-    total, n = None, 0
+    acc, n = _EpochLoss(params, trainer), 0
     nxt = corpus.draw(range(starts[0], min(len(files), starts[0] + bs)))
     for k in range(len(starts)):
         drawn = nxt
@@ -568,14 +692,13 @@ def train_one_epoch_corpus(params: dict, corpus, trainer):
             bufs = graphs.static_inputs((items.shape[0], corpus.n_samples, 4), target_like,
                                         None if spec is None else tuple(spec.shape))
         audio, target, spec_dev = corpus.launch(drawn, *(bufs or ()))
-        loss = trainer.step(audio, target, spec_dev)
-        total = loss.detach().reshape(-1)[:1].clone() if total is None else total + loss.detach().reshape(-1)[:1]
+        acc.add(trainer.step(audio, target, spec_dev))
         n += 1
         nxt = None
         if k + 1 < len(starts):                   # the next batch's host draws while this step runs
             nxt = corpus.draw(range(starts[k + 1], min(len(files), starts[k + 1] + bs)))
         if nxt is None or (params.get("args", {}).get("quick_test") and n == 5):
             break
-    loss_sum, status = ops.to_host_many(total, corpus.status)
+    mean, (status,) = acc.mean(corpus.status)
     corpus.check(int(status[0]))
-    return float(loss_sum[0]) / max(n, 1)
+    return mean

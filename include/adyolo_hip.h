@@ -758,6 +758,30 @@ int  adyolo_sgd_step_groups_dev(float *param, const float *grad, float *momentum
                                 float grad_scale, const double *sched_dev, float *sched_out, float *ema,
                                 const double *groups_dev, float *groups_out, int n_groups, const unsigned char *group_map,
                                 void *stream);
+/* The guarded steps: an optimizer step that does NOTHING when the gradient is not finite, decided on the device inside the
+ * (recorded) step.  The test: the fp32 total norm -- the float of the square root of the float64 sum of (grad * grad_scale)^2 --
+ * is not finite: a NaN or an infinity anywhere in the buffer, a product grad * grad_scale that overflows, a norm beyond fp32.
+ * The sum of squares therefore always runs: partials is required, and max_norm < 0 means no clipping (clip_coef exactly 1);
+ * st_dev[2] is written on every attempt.
+ *   guard  adyolo_optim_guard_words() (= 4) int64, 8-byte aligned, written by the prep kernel only: {attempts, skipped,
+ *          last attempt skipped (0 / 1), current run of consecutive skips}
+ * A skipped attempt leaves param, the state, ema, *step_dev, st_dev[0..1], st_dev[3], sched_out and groups_out untouched and
+ * writes st_dev[2] (the offending norm) and the record.  Because the counter does not tick, everything derived from it -- bias
+ * corrections, the schedule's clock, the EMA's update count and first-copy flag, SGD's first-step flag -- continues as if the
+ * attempt had never been made.  A taken step is the unguarded entry point's, bit for bit.
+ * One entry point per rule carries the arguments of all three forms; the form is read from the pointers: groups_dev != NULL
+ * grouped (lr and weight_decay ignored), else sched_dev != NULL scheduled (lr ignored), else plain (ema must be NULL). */
+int  adyolo_optim_guard_words(void);
+int  adyolo_adam_step_guard_dev(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, long n, float lr, float beta1,
+                                float beta2, float eps, float weight_decay, int decoupled, uint64_t *step_dev, float *st_dev,
+                                double *partials, float max_norm, float grad_scale, const double *sched_dev, float *sched_out,
+                                float *ema, const double *groups_dev, float *groups_out, int n_groups,
+                                const unsigned char *group_map, int64_t *guard, void *stream);
+int  adyolo_sgd_step_guard_dev(float *param, const float *grad, float *momentum_buf, long n, float lr, float weight_decay,
+                               float momentum, float dampening, int nesterov, uint64_t *step_dev, float *st_dev,
+                               double *partials, float max_norm, float grad_scale, const double *sched_dev, float *sched_out,
+                               float *ema, const double *groups_dev, float *groups_out, int n_groups,
+                               const unsigned char *group_map, int64_t *guard, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * K9a multi-head self-attention core, flash style on the exact-fp32 matrix cores (csrc/attention.hip).

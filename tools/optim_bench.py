@@ -4,13 +4,16 @@ up, repeated).
   step      one hipGraph-replayed TrainStep at 16 x 20 s (the reference's batch_size / chunk) and at 64 x 60 s (the bench shape)
             with 'Adam' (ops.adam_step_dev, the baseline), 'AdamW', 'SGD' (plain, as the reference calls it), 'Adam' with
             clip_grad_norm 3, 'Adam' under a device-side lr_schedule (ops.adam_step_sched_dev) and the same with ema_decay;
-            'AdamW' under the schedule without and with the no-decay parameter grouping (ops.adam_step_groups_dev)
+            'AdamW' under the schedule without and with the no-decay parameter grouping (ops.adam_step_groups_dev); 'Adam'
+            behind the non-finite guard (skip_nonfinite, ops.adam_step_guard_dev) without and with clip_grad_norm 3
   kernels   the optimizer launches alone on buffers of the real model's flat size (6.68 M floats): adam_step_dev (baseline),
             adamw_step_dev, sgd_step_dev without / with momentum, adam_step_dev with clipping, grad_norm_dev (sum of squares +
             prep); the scheduled forms adam / adamw / sgd_step_sched_dev (cosine with warm-up: the prep kernel's most expensive
             table) and the scheduled forms with the EMA in the update launch (two more streams); the grouped forms
             adam / adamw (+ EMA) / sgd_step_groups_dev with the real model's ``ndim_max: 1`` group map (150 runs), each beside
-            its ungrouped scheduled counterpart
+            its ungrouped scheduled counterpart; the guarded steps adam / adamw grouped + EMA / sgd_step_guard_dev without
+            and with clipping, each beside the unguarded step of the same form without and with clipping (a guarded
+            unclipped step should cost what the clipped one costs, a guarded clipped step the same again)
 
 At 16 x 20 s the trainers live side by side and alternate inside each repeat; at 64 x 60 s they are built one after the
 other (activations of one recorded step at a time).  The median of the repeats is reported (ms per call).
@@ -41,7 +44,9 @@ VARIANTS = {"adam": {"optim": "Adam"},
                             "lr_schedule": {"name": "cosine", "T_max": 1000, "warmup_steps": 100}},
             "adamw_sched_groups": {"optim": "AdamW", "weight_decay": 0.01,
                                    "lr_schedule": {"name": "cosine", "T_max": 1000, "warmup_steps": 100},
-                                   "param_groups": [{"name": "no_decay", "ndim_max": 1, "weight_decay": 0.0}]}}
+                                   "param_groups": [{"name": "no_decay", "ndim_max": 1, "weight_decay": 0.0}]},
+            "adam_guard": {"optim": "Adam", "skip_nonfinite": True},
+            "adam_clip3_guard": {"optim": "Adam", "clip_grad_norm": 3.0, "skip_nonfinite": True}}
 
 
 def timed(fns, reps, iters):
@@ -137,7 +142,21 @@ def bench_kernels(reps, iters):
     gdev = torch.tensor([[1e-3, 0.0], [1e-3, 0.0]], dtype=torch.float64).to("cuda:0")
     gdev_w = torch.tensor([[1e-3, float(torch.tensor(1e-2, dtype=torch.float32))], [1e-3, 0.0]], dtype=torch.float64).to("cuda:0")
     gout = torch.zeros(2, ops.GROUP_OUT_FLOATS, device="cuda:0")
+    guard = torch.zeros(ops.OPTIM_GUARD_WORDS, dtype=torch.int64, device="cuda:0")
+    form = dict(sched_dev=sched_ema, sched_out=out, ema=ema, groups_dev=gdev_w, groups_out=gout, group_map=gmap)
     fns = {
+        "adam_step_guard_dev": lambda: ops.adam_step_guard_dev(p, grad, m, v, step_dev, st, guard, parts),
+        "adam_step_guard_dev_clip": lambda: ops.adam_step_guard_dev(p, grad, m, v, step_dev, st, guard, parts, max_norm=3.0),
+        "adamw_step_groups_dev_ema_clip": lambda: ops.adam_step_groups_dev(p, grad, m, v, step_dev, st, sched_ema, out, gdev_w,
+                                                                           gout, gmap, ema, decoupled=True, partials=parts,
+                                                                           max_norm=3.0),
+        "adamw_step_guard_dev_groups_ema": lambda: ops.adam_step_guard_dev(p, grad, m, v, step_dev, st, guard, parts,
+                                                                           decoupled=True, **form),
+        "adamw_step_guard_dev_groups_ema_clip": lambda: ops.adam_step_guard_dev(p, grad, m, v, step_dev, st, guard, parts,
+                                                                                max_norm=3.0, decoupled=True, **form),
+        "sgd_step_dev_clip": lambda: ops.sgd_step_dev(p, grad, None, step_dev, st, partials=parts, max_norm=3.0),
+        "sgd_step_guard_dev": lambda: ops.sgd_step_guard_dev(p, grad, None, step_dev, st, guard, parts),
+        "sgd_step_guard_dev_clip": lambda: ops.sgd_step_guard_dev(p, grad, None, step_dev, st, guard, parts, max_norm=3.0),
         "adam_step_groups_dev": lambda: ops.adam_step_groups_dev(p, grad, m, v, step_dev, st, sched, out, gdev, gout, gmap),
         "adamw_step_groups_dev": lambda: ops.adam_step_groups_dev(p, grad, m, v, step_dev, st, sched, out, gdev_w, gout, gmap,
                                                                   decoupled=True),

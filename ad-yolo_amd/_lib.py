@@ -154,6 +154,9 @@ SIGNATURES = {
     "adyolo_optim_guard_words": (I, []),
     "adyolo_adam_step_guard_dev": (I, [P] * 4 + [L, F, F, F, F, F, I, P, P, P, F, F, P, P, P, P, P, I, P, P, P]),
     "adyolo_sgd_step_guard_dev": (I, [P] * 3 + [L, F, F, F, F, I, P, P, P, F, F, P, P, P, P, P, I, P, P, P]),
+    "adyolo_optim_accum_words": (I, []),
+    "adyolo_adam_step_accum_dev": (I, [P] * 4 + [L, F, F, F, F, F, I, P, P, P, F, F, P, P, P, P, P, I, P, P, P, P, I, P]),
+    "adyolo_sgd_step_accum_dev": (I, [P] * 3 + [L, F, F, F, F, I, P, P, P, F, F, P, P, P, P, P, I, P, P, P, P, I, P]),
 }
 
 _lib = None

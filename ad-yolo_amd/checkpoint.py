@@ -128,7 +128,10 @@ def optimizer_state_dict(optimizer, model):
     ``weight_decay``, and torch's numbering: consecutive group by group, ``model.parameters()`` order inside a group.
     ``clip_grad_norm`` is configuration, not state: it is not written.  Under the non-finite guard
     (``train_config['skip_nonfinite']``) the optimizer reconciles first: ``step`` is the number of APPLIED steps, what
-    torch.optim under a ``GradScaler`` would hold."""
+    torch.optim under a ``GradScaler`` would hold.  Under gradient accumulation (``train_config['accum_steps']``) a state in the
+    middle of a cycle is refused with ValueError: the accumulator is not part of a checkpoint."""
+    if getattr(optimizer, "micro_index", 0) != 0:
+        optimizer._refuse_mid_cycle("optimizer state_dict")
     if getattr(optimizer, "guard_dev", None) is not None:
         optimizer.reconcile()
     params = _indexed_params(optimizer, model)
@@ -199,7 +202,10 @@ def _refresh_schedule(optimizer):
 def load_optimizer_state_dict(optimizer, model, sd):
     """A file whose groups have the sizes of the optimizer's, in order, is taken group by group (state through the ids, ``lr``
     and ``weight_decay`` per group from the file); a one-group file into a grouped optimizer is taken by
-    ``model.parameters()`` order and the optimizer keeps its own group values; any other grouping raises ValueError."""
+    ``model.parameters()`` order and the optimizer keeps its own group values; any other grouping raises ValueError.  An
+    accumulating optimizer starts a new cycle."""
+    if getattr(optimizer, "accum_dev", None) is not None:
+        optimizer.reset_accumulation()
     params = _indexed_params(optimizer, model)
     file_ids, file_groups = _match_groups(optimizer, params, sd)
     kind = getattr(optimizer, "kind", "adam")

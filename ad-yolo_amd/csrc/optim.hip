@@ -24,6 +24,11 @@
 // norm is finite and otherwise leaves the counter, st[0..1], sched_out and groups_out alone and says so in the guard record,
 // which makes every workgroup of the update kernel return before its first access: a skipped attempt changes nothing, and
 // since the counter did not tick, the next attempt is the step the skipped one would have been.
+// The accumulating steps (adyolo_*_step_accum_dev; K micro-batches, one step): every call is a micro-step.  grad_accum_kernel
+// adds the gradient into an accumulator laid out like it (the cycle's first call overwrites it), the prep kernel keeps the
+// accumulation record and, on all but the cycle's last call, stops there and tells the update kernel to do the same; the last
+// call is the step above with the accumulator as its gradient and grad_scale / K as its scale.  Which call of the cycle this
+// is, is read from the record on the device: the launches and their arguments are the same for every micro-step.
 // st is 4 floats of device scratch.  All streams move 16 bytes per lane per access (pointers 16-byte aligned, the n & 3 tail
 // elements are done by workgroup 0); grids are capped and grid-stride.  Elements that are zero in parameter, gradient and state
 // (the padding of dist.FlatParameters) stay zero in every kernel.
@@ -97,6 +102,62 @@ __global__ __launch_bounds__(OX_THREADS) void grad_sumsq_kernel(const float *__r
         const double a = (double)(g[n4 * 4 + threadIdx.x] * grad_scale);
         s += a * a;
     }
+    // fixed order: butterfly inside the wave, then the four waves one after the other
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) partials[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// ---------------------------------------------------------------------------------------------- gradient accumulation
+// The accumulation record (the *_accum entry points): four int64 written only by the prep kernel, by one lane.  ACC_MICRO is
+// the index inside its cycle of the NEXT call (0 .. accum_steps - 1); ACC_HOLD says that the last call was not its cycle's last.
+enum { ACC_MICRO = 0, ACC_CALLS = 1, ACC_CYCLES = 2, ACC_HOLD = 3, ACC_WORDS = 4 };
+
+// accum = g on a cycle's first micro-step (accum is not read: whatever a discarded cycle left there is gone), else accum + g.
+// On the cycle's last micro-step, with partials != nullptr, also the partial sums of (accum * grad_scale)^2 that
+// grad_sumsq_kernel would give on the finished accumulator: it is launched on that kernel's grid, a lane walks the same
+// vectors and sums the same expressions in the same order, and the reduction is the same.  The micro index is grid-uniform
+// and read before the first load; the prep kernel, which alone writes it, runs after this kernel in the stream.
+__global__ __launch_bounds__(OX_THREADS) void grad_accum_kernel(const float *__restrict__ g, float *__restrict__ accum, long n,
+                                                                float grad_scale, double *__restrict__ partials,
+                                                                const long long *__restrict__ acc, int accum_steps) {
+    __shared__ double red[OX_THREADS / 64];
+    const long long micro = acc[ACC_MICRO];
+    const bool first = micro == 0;
+    const bool sum = partials != nullptr && micro + 1 >= accum_steps;
+    const long n4 = n >> 2;
+    const float4 *g4 = reinterpret_cast<const float4 *>(g);
+    float4 *a4 = reinterpret_cast<float4 *>(accum);
+    double s = 0.0;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        float4 v = g4[i];
+        if (!first) {
+            const float4 o = a4[i];
+            v.x = o.x + v.x;
+            v.y = o.y + v.y;
+            v.z = o.z + v.z;
+            v.w = o.w + v.w;
+        }
+        a4[i] = v;
+        if (sum) {
+            const double a = (double)(v.x * grad_scale), b = (double)(v.y * grad_scale);
+            const double c = (double)(v.z * grad_scale), d = (double)(v.w * grad_scale);
+            s += (a * a + b * b) + (c * c + d * d);
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const long i = n4 * 4 + threadIdx.x;
+        float v = g[i];
+        if (!first) v = accum[i] + v;
+        accum[i] = v;
+        if (sum) {
+            const double a = (double)(v * grad_scale);
+            s += a * a;
+        }
+    }
+    if (!sum) return;                      // (grid-uniform)
     // fixed order: butterfly inside the wave, then the four waves one after the other
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
@@ -193,6 +254,8 @@ __device__ __forceinline__ void prep_tick(unsigned long long *__restrict__ step,
 // the counter does not tick, so nothing derived from it (bias corrections, the schedule's clock, the EMA's update count and
 // first-copy flag, SGD's first-step flag) sees the attempt.  A taken step is the unguarded one, value for value; a negative
 // max_norm means clipping off there (st[3] = exactly 1, not max_norm = inf: inf / inf is nan).
+// acc != nullptr (the *_accum entry points): the accumulation record is advanced FIRST.  On a hold call -- not the last of its
+// cycle -- that is all: no tick, no guard record, no st.  The cycle's last call goes on as above, guard included.
 __global__ __launch_bounds__(OX_THREADS) void optim_prep_kernel(unsigned long long *__restrict__ step, float *__restrict__ st,
                                                                 int kind, float lr, float beta1, float beta2,
                                                                 const double *__restrict__ partials, int nparts,
@@ -200,8 +263,21 @@ __global__ __launch_bounds__(OX_THREADS) void optim_prep_kernel(unsigned long lo
                                                                 float *__restrict__ sched_out, float wd,
                                                                 const double *__restrict__ groups,
                                                                 float *__restrict__ groups_out, int n_groups,
-                                                                long long *__restrict__ guard) {
+                                                                long long *__restrict__ guard, long long *__restrict__ acc,
+                                                                int accum_steps) {
     __shared__ double red[OX_THREADS];
+    if (acc != nullptr) {                  // (uniform over the workgroup)
+        const long long micro = acc[ACC_MICRO];
+        const bool hold = micro + 1 < accum_steps;
+        __syncthreads();                   // every lane has read the index before one lane moves it
+        if (threadIdx.x == 0) {
+            acc[ACC_MICRO] = hold ? micro + 1 : 0;
+            acc[ACC_CALLS] = acc[ACC_CALLS] + 1;
+            acc[ACC_CYCLES] = acc[ACC_CYCLES] + (hold ? 0 : 1);
+            acc[ACC_HOLD] = hold ? 1 : 0;
+        }
+        if (hold) return;
+    }
     if (threadIdx.x == 0 && kind != PREP_NORM && guard == nullptr)
         prep_tick(step, st, kind, lr, beta1, beta2, sched, sched_out, wd, groups, groups_out, n_groups);
     if (partials == nullptr) {             // (uniform over the workgroup)
@@ -248,7 +324,9 @@ enum { FORM_ARG = 0, FORM_SCHED = 1, FORM_GROUPS = 2 };
 
 // The guarded step (guard != nullptr): the prep kernel's verdict on this attempt.  Grid-uniform, and asked before the first
 // load, store or barrier of an update kernel: a skipped step's update launch touches nothing.
-__device__ __forceinline__ bool skipped(const long long *__restrict__ guard) {
+// The accumulating step (acc != nullptr) asks the same way whether this call is a hold call of its cycle.
+__device__ __forceinline__ bool skipped(const long long *__restrict__ guard, const long long *__restrict__ acc) {
+    if (acc != nullptr && acc[ACC_HOLD] != 0) return true;
     return guard != nullptr && guard[GUARD_LAST] != 0;
 }
 
@@ -344,9 +422,10 @@ __global__ __launch_bounds__(OX_THREADS) void adam_update_kernel(float *__restri
                                                                  const float *__restrict__ so, float *__restrict__ ema,
                                                                  const float *__restrict__ groups_out, int n_groups,
                                                                  const unsigned char *__restrict__ map,
-                                                                 const long long *__restrict__ guard) {
+                                                                 const long long *__restrict__ guard,
+                                                                 const long long *__restrict__ acc) {
     static_assert(FORM != FORM_ARG || !EMA, "the EMA belongs to the scheduled forms");
-    if (skipped(guard)) return;
+    if (skipped(guard, acc)) return;
     const float4 *tab = group_table<FORM>(groups_out, n_groups);
     float4 cu = make_float4(0.f, 0.f, 0.f, 0.f);          // the lane's constants; FORM_GROUPS: unused
     if constexpr (FORM == FORM_SCHED) decay = so[SOUT_DECAY];
@@ -424,9 +503,10 @@ __global__ __launch_bounds__(OX_THREADS) void sgd_update_kernel(float *__restric
                                                                 const float *__restrict__ st, const float *__restrict__ so,
                                                                 float *__restrict__ ema, const float *__restrict__ groups_out,
                                                                 int n_groups, const unsigned char *__restrict__ map,
-                                                                const long long *__restrict__ guard) {
+                                                                const long long *__restrict__ guard,
+                                                                const long long *__restrict__ acc) {
     static_assert(FORM != FORM_ARG || !EMA, "the EMA belongs to the scheduled forms");
-    if (skipped(guard)) return;
+    if (skipped(guard, acc)) return;
     const float4 *tab = group_table<FORM>(groups_out, n_groups);
     float4 cu = make_float4(0.f, 0.f, 0.f, 0.f);          // the lane's constants; FORM_GROUPS: unused
     if constexpr (FORM == FORM_SCHED) lr = so[SOUT_LR];
@@ -473,18 +553,27 @@ static int launch_sumsq(const float *grad, long n, float grad_scale, double *par
     return check_launch("grad_sumsq");
 }
 
+static int launch_accum(const float *grad, float *accum, long n, float grad_scale, double *partials, const int64_t *acc,
+                        int accum_steps, hipStream_t st) {
+    hipLaunchKernelGGL(grad_accum_kernel, dim3(sumsq_grid(n)), dim3(OX_THREADS), 0, st, grad, accum, n, grad_scale, partials,
+                       reinterpret_cast<const long long *>(acc), accum_steps);
+    return check_launch("grad_accum");
+}
+
 static int launch_prep(uint64_t *step_dev, float *st_dev, int kind, float lr, float beta1, float beta2, const double *partials,
                        long n, float max_norm, hipStream_t st, const double *sched = nullptr, float *sched_out = nullptr,
                        float wd = 0.f, const double *groups = nullptr, float *groups_out = nullptr, int n_groups = 0,
-                       int64_t *guard = nullptr) {
+                       int64_t *guard = nullptr, int64_t *acc = nullptr, int accum_steps = 1) {
     hipLaunchKernelGGL(optim_prep_kernel, dim3(1), dim3(OX_THREADS), 0, st, reinterpret_cast<unsigned long long *>(step_dev),
                        st_dev, kind, lr, beta1, beta2, partials, partials ? sumsq_grid(n) : 0, max_norm, sched, sched_out, wd,
-                       groups, groups_out, n_groups, reinterpret_cast<long long *>(guard));
+                       groups, groups_out, n_groups, reinterpret_cast<long long *>(guard), reinterpret_cast<long long *>(acc),
+                       accum_steps);
     return check_launch("optim_prep");
 }
 
 // What a step's entry point adds to the plain form: all null in FORM_ARG; the table, sched_out and (optionally) the EMA in
 // FORM_SCHED and FORM_GROUPS; the groups in FORM_GROUPS.  guard: the record of the *_guard entry points, null elsewhere.
+// acc, accum, accum_steps: the record, the accumulator and K of the *_accum entry points, null elsewhere.
 struct StepForm {
     int form;
     const double *sched;
@@ -494,7 +583,21 @@ struct StepForm {
     int n_groups;
     const unsigned char *map;
     int64_t *guard;
+    int64_t *acc;
+    float *accum;
+    int accum_steps;
 };
+
+// The front of a step: the sum of squares of the gradient (clipping or the guard), or, in the accumulating step, the
+// micro-gradient into the accumulator (with the sum on the cycle's last call) -- the step then reads the accumulator under
+// grad_scale / accum_steps.
+static int step_front(const float *&grad, float &grad_scale, long n, double *partials, const StepForm &f, hipStream_t st) {
+    if (f.acc == nullptr) return partials ? launch_sumsq(grad, n, grad_scale, partials, st) : 0;
+    grad_scale = (float)((double)grad_scale / f.accum_steps);
+    const int rc = launch_accum(grad, f.accum, n, grad_scale, partials, f.acc, f.accum_steps, st);
+    grad = f.accum;
+    return rc;
+}
 
 // a kernel's five instantiations (for one value of its first template parameter) are kept in the order of this index
 static int form_index(const StepForm &f) {
@@ -536,6 +639,8 @@ static int check_step(const char *what, bool present, bool aligned, long n, cons
                         (reinterpret_cast<uintptr_t>(f.map) & 3) == 0),
                    ADYOLO_EINVAL, "%s: 1 to 16 groups, groups_dev 8-byte, groups_out 16-byte and the map 4-byte aligned", what);
     ADYOLO_REQUIRE((reinterpret_cast<uintptr_t>(f.guard) & 7) == 0, ADYOLO_EINVAL, "%s: the guard record not 8-byte aligned", what);
+    ADYOLO_REQUIRE((reinterpret_cast<uintptr_t>(f.acc) & 7) == 0 && aligned16(f.accum), ADYOLO_EINVAL,
+                   "%s: the accumulator not 16-byte aligned (or the accumulation record not 8-byte aligned)", what);
     return 0;
 }
 
@@ -548,15 +653,16 @@ static int adam_step(float *param, const float *grad, float *exp_avg, float *exp
     if ((rc = check_step(what, param && grad && exp_avg && exp_avg_sq && step_dev && st_dev,
                          aligned16(param) && aligned16(grad) && aligned16(exp_avg) && aligned16(exp_avg_sq), n, f)))
         return rc;
-    if (partials && (rc = launch_sumsq(grad, n, grad_scale, partials, st))) return rc;
+    if ((rc = step_front(grad, grad_scale, n, partials, f, st))) return rc;
     if ((rc = launch_prep(step_dev, st_dev, PREP_ADAM, lr, beta1, beta2, partials, n, max_norm, st, f.sched, f.sched_out,
-                          weight_decay, f.groups, f.groups_out, f.n_groups, f.guard)))
+                          weight_decay, f.groups, f.groups_out, f.n_groups, f.guard, f.acc, f.accum_steps)))
         return rc;
     const float decay = (float)(1.0 - (double)lr * (double)weight_decay);
     auto kernel = decoupled ? adam_kernel<true>(f) : adam_kernel<false>(f);
     hipLaunchKernelGGL(kernel, dim3(update_grid(n)), dim3(OX_THREADS), 0, st, param, grad, exp_avg, exp_avg_sq, n, beta1, beta2,
                        eps, weight_decay, decay, grad_scale, (const float *)st_dev, (const float *)f.sched_out, f.ema,
-                       (const float *)f.groups_out, f.n_groups, f.map, (const long long *)f.guard);
+                       (const float *)f.groups_out, f.n_groups, f.map, (const long long *)f.guard,
+                       (const long long *)f.acc);
     return check_launch(what);
 }
 
@@ -567,9 +673,9 @@ static int sgd_step(float *param, const float *grad, float *momentum_buf, long n
     if ((rc = check_step(what, param && grad && step_dev && st_dev && (momentum == 0.f || momentum_buf),
                          aligned16(param) && aligned16(grad) && aligned16(momentum_buf), n, f)))
         return rc;
-    if (partials && (rc = launch_sumsq(grad, n, grad_scale, partials, st))) return rc;
+    if ((rc = step_front(grad, grad_scale, n, partials, f, st))) return rc;
     if ((rc = launch_prep(step_dev, st_dev, PREP_SGD, lr, 0.f, 0.f, partials, n, max_norm, st, f.sched, f.sched_out, 0.f,
-                          f.groups, f.groups_out, f.n_groups, f.guard)))
+                          f.groups, f.groups_out, f.n_groups, f.guard, f.acc, f.accum_steps)))
         return rc;
     const float keep = (float)(1.0 - (double)dampening);
     const bool mom = momentum != 0.f;
@@ -577,7 +683,7 @@ static int sgd_step(float *param, const float *grad, float *momentum_buf, long n
     hipLaunchKernelGGL(kernel, dim3(update_grid(n)), dim3(OX_THREADS), 0, st, param, grad, mom ? momentum_buf : (float *)nullptr,
                        n, lr, weight_decay, mom ? momentum : 0.f, keep, nesterov, grad_scale, (const float *)st_dev,
                        (const float *)f.sched_out, f.ema, (const float *)f.groups_out, f.n_groups, f.map,
-                       (const long long *)f.guard);
+                       (const long long *)f.guard, (const long long *)f.acc);
     return check_launch(what);
 }
 
@@ -668,8 +774,9 @@ extern "C" int adyolo_optim_guard_words(void) { return GUARD_WORDS; }
 
 static int guard_form(const char *what, const double *sched_dev, float *sched_out, float *ema, const double *groups_dev,
                       float *groups_out, int n_groups, const unsigned char *group_map, int64_t *guard, const double *partials,
-                      StepForm *f) {
-    ADYOLO_REQUIRE(guard && partials, ADYOLO_EINVAL, "%s: needs the guard record and the partials", what);
+                      StepForm *f, bool guard_optional = false) {
+    ADYOLO_REQUIRE((guard && partials) || (guard_optional && !guard), ADYOLO_EINVAL,
+                   "%s: needs the guard record and the partials", what);
     ADYOLO_REQUIRE(sched_dev || (!groups_dev && !ema), ADYOLO_EINVAL, "%s: groups and the EMA need a schedule table", what);
     const int form = groups_dev ? FORM_GROUPS : (sched_dev ? FORM_SCHED : FORM_ARG);
     *f = StepForm{form, sched_dev, sched_out, ema};
@@ -706,4 +813,49 @@ extern "C" int adyolo_sgd_step_guard_dev(float *param, const float *grad, float 
     return sgd_step(param, grad, momentum_buf, n, f.form == FORM_ARG ? lr : 0.f, f.form == FORM_GROUPS ? 0.f : weight_decay,
                     momentum, dampening, nesterov, step_dev, st_dev, partials, max_norm, grad_scale, f, as_stream(stream),
                     "sgd_step_guard_dev");
+}
+
+// The accumulating steps: one entry point per rule, the guarded entry point's arguments with the guard optional (null:
+// unguarded, and partials null: no clipping, as in the unguarded entry points) and then the accumulator, the accumulation
+// record and K.  K = 1 makes every call a cycle of its own: the step of the form's own entry point on a copy of the gradient.
+extern "C" int adyolo_optim_accum_words(void) { return ACC_WORDS; }
+
+static int accum_form(const char *what, float *accum, int64_t *accum_dev, int accum_steps, StepForm *f) {
+    ADYOLO_REQUIRE(accum && accum_dev, ADYOLO_EINVAL, "%s: needs the accumulator and the accumulation record", what);
+    ADYOLO_REQUIRE(accum_steps >= 1, ADYOLO_EINVAL, "%s: accum_steps %d, must be at least 1", what, accum_steps);
+    f->acc = accum_dev;
+    f->accum = accum;
+    f->accum_steps = accum_steps;
+    return 0;
+}
+
+extern "C" int adyolo_adam_step_accum_dev(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, long n, float lr,
+                                          float beta1, float beta2, float eps, float weight_decay, int decoupled,
+                                          uint64_t *step_dev, float *st_dev, double *partials, float max_norm,
+                                          float grad_scale, const double *sched_dev, float *sched_out, float *ema,
+                                          const double *groups_dev, float *groups_out, int n_groups,
+                                          const unsigned char *group_map, int64_t *guard, float *accum, int64_t *accum_dev,
+                                          int accum_steps, void *stream) {
+    StepForm f;
+    int rc = guard_form("adam_step_accum_dev", sched_dev, sched_out, ema, groups_dev, groups_out, n_groups, group_map, guard,
+                        partials, &f, true);
+    if (rc || (rc = accum_form("adam_step_accum_dev", accum, accum_dev, accum_steps, &f))) return rc;
+    return adam_step(param, grad, exp_avg, exp_avg_sq, n, f.form == FORM_ARG ? lr : 0.f, beta1, beta2, eps,
+                     f.form == FORM_GROUPS ? 0.f : weight_decay, decoupled, step_dev, st_dev, partials, max_norm, grad_scale, f,
+                     as_stream(stream), "adam_step_accum_dev");
+}
+
+extern "C" int adyolo_sgd_step_accum_dev(float *param, const float *grad, float *momentum_buf, long n, float lr,
+                                         float weight_decay, float momentum, float dampening, int nesterov, uint64_t *step_dev,
+                                         float *st_dev, double *partials, float max_norm, float grad_scale,
+                                         const double *sched_dev, float *sched_out, float *ema, const double *groups_dev,
+                                         float *groups_out, int n_groups, const unsigned char *group_map, int64_t *guard,
+                                         float *accum, int64_t *accum_dev, int accum_steps, void *stream) {
+    StepForm f;
+    int rc = guard_form("sgd_step_accum_dev", sched_dev, sched_out, ema, groups_dev, groups_out, n_groups, group_map, guard,
+                        partials, &f, true);
+    if (rc || (rc = accum_form("sgd_step_accum_dev", accum, accum_dev, accum_steps, &f))) return rc;
+    return sgd_step(param, grad, momentum_buf, n, f.form == FORM_ARG ? lr : 0.f, f.form == FORM_GROUPS ? 0.f : weight_decay,
+                    momentum, dampening, nesterov, step_dev, st_dev, partials, max_norm, grad_scale, f, as_stream(stream),
+                    "sgd_step_accum_dev");
 }

@@ -14,7 +14,9 @@ counter (``adyolo_adam_step_dev``) and the running offset of the dropout stream 
 varies from batch to batch) is padded to a fixed capacity with rows the assignment kernel skips (batch index -1).  A
 learning-rate schedule (``train_config['lr_schedule']``) is recorded like the plain step: the rate is derived by the
 optimizer's prep kernel from that counter and a table the host may rewrite between replays (``set_lr``), and the EMA of the
-parameters rides in the update launch -- nothing in either varies per step.
+parameters rides in the update launch -- nothing in either varies per step.  Gradient accumulation
+(``train_config['accum_steps']``) is recorded the same way: every replay is a micro-step, and whether it only adds its gradient
+to the accumulator or also takes the step is decided by the optimizer's kernels from a record on the device.
 
 Results are bit-identical to the eager path (tests/test_gpu_graph.py compares losses and parameters with torch.equal).
 """
@@ -140,7 +142,8 @@ class StepGraphs:
         # host-side state the captured step advances: put back afterwards (recording runs nothing), re-applied per replay
         tr.optimizer.reconcile()                    # (non-finite guard: skipped steps leave the mirror first)
         step0 = tr.optimizer.step_count
-        tr.optimizer.sync_device_step()
+        micro0 = tr.optimizer.micro_index           # (gradient accumulation: the recording serves every micro-step of a cycle --
+        tr.optimizer.sync_device_step()             #  which one a replay is, its kernels read from the device's record)
         for s in self.streams:
             s.sync_device()
             s.begin_capture(dev)
@@ -166,6 +169,7 @@ class StepGraphs:
             tr.optimizer._guard_dirty = False       # the recorded attempt was not made: the guard's record has not moved
             tr.optimizer.step_count = step0
             tr.optimizer._dev_step_value = step0
+            tr.optimizer.micro_index = micro0
         ent.graph, ent.loss = graph, loss
         self.evictions += _lru_insert(self.entries, key, ent, MAX_GRAPHS)
         self.captures += 1

@@ -1171,13 +1171,14 @@ def _max_norm(what, partials, max_norm):
 
 
 def _optim_step(what, param, grad, states, hyper, step_dev, st_dev, grad_scale, partials, max_norm, sched=(), groups=(),
-                momentum=None, guard=None):
+                momentum=None, guard=None, accum=None):
     """The checks and the call behind every optimizer wrapper below.  ``what``: the wrapper's name, in errors and (as
     ``adyolo_<what>``) the entry point.  states: the rule's state buffers; hyper: its scalars, in the entry point's order;
     sched: (sched_dev, sched_out, ema) of the scheduled forms; groups: (groups_dev, groups_out, group_map) of the grouped
     ones; momentum: SGD's, whose one state buffer is needed, and passed on, only when it is not 0; guard: the record of the
     guarded entry points, which take every form's arguments (null where the form has none) and a negative max_norm for
-    "no clipping"."""
+    "no clipping"; accum: (accum, accum_dev, accum_steps) of the accumulating entry points, which take the guarded ones'
+    arguments with the guard optional."""
     _chk(param, grad, *states, st_dev)
     _chk_optim_dev(what, param.numel(), step_dev, st_dev, partials)
     form = ()                         # what the entry point takes after grad_scale: sched_dev, sched_out, ema, then
@@ -1191,12 +1192,15 @@ def _optim_step(what, param, grad, states, hyper, step_dev, st_dev, grad_scale, 
         raise _lib.AdyoloHipError("%s with momentum needs a momentum buffer" % what)
     if momentum == 0.0:
         states = (None,)              # SGD without momentum: the buffer is not passed on
-    if guard is not None:             # every form's arguments, null where the form has none
+    if guard is not None or accum is not None:        # every form's arguments, null where the form has none
         if not sched:
             form = (_p(None),) * 3
         if not groups:
             form += (_p(None), _p(None), 0, _p(None))
         form += (_p(guard),)
+    if accum is not None:
+        form += (_p(accum[0]), _p(accum[1]), int(accum[2]))
+    if guard is not None:
         if max_norm is not None and not float(max_norm) >= 0.0:
             raise _lib.AdyoloHipError("%s: max_norm must not be negative (None = no clipping)" % what)
         norm = -1.0 if max_norm is None else float(max_norm)
@@ -1378,6 +1382,56 @@ def sgd_step_guard_dev(param, grad, momentum_buf, step_dev, st_dev, guard, parti
     sched, groups = _guard_forms(what, sched_dev, sched_out, ema, groups_dev, groups_out, group_map)
     _optim_step(what, param, grad, (momentum_buf,), (lr, weight_decay, momentum, dampening, int(bool(nesterov))), step_dev,
                 st_dev, grad_scale, partials, max_norm, sched, groups, momentum=momentum, guard=guard)
+
+
+# The accumulating steps (include/adyolo_hip.h, "The accumulating steps"): K micro-batches, one optimizer step
+OPTIM_ACCUM_WORDS = 4             # int64 elements of the accumulation record: {next micro index, calls, cycles, last call held}
+#                                   (adyolo_optim_accum_words())
+
+
+def _chk_accum(what, param, accum, accum_dev, accum_steps, guard, partials):
+    _chk(accum)
+    if accum is None or accum.numel() != param.numel() or accum.device != param.device:
+        raise _lib.AdyoloHipError("%s needs an accumulator of %d floats on the parameters' device" % (what, param.numel()))
+    if (accum_dev is None or not accum_dev.is_cuda or accum_dev.dtype != torch.int64 or not accum_dev.is_contiguous()
+            or accum_dev.numel() < OPTIM_ACCUM_WORDS or accum_dev.device != param.device):
+        raise _lib.AdyoloHipError("%s needs an accumulation record of %d contiguous int64 on the parameters' device"
+                                  % (what, OPTIM_ACCUM_WORDS))
+    if isinstance(accum_steps, bool) or int(accum_steps) != accum_steps or int(accum_steps) < 1:
+        raise _lib.AdyoloHipError("%s: accum_steps must be an integer >= 1, not %r" % (what, accum_steps))
+    if guard is not None:
+        _chk_guard(what, param, guard, partials)
+    return accum, accum_dev, int(accum_steps)
+
+
+def adam_step_accum_dev(param, grad, exp_avg, exp_avg_sq, step_dev, st_dev, accum, accum_dev, accum_steps, guard=None,
+                        partials=None, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_scale=1.0, max_norm=None,
+                        decoupled=False, sched_dev=None, sched_out=None, ema=None, groups_dev=None, groups_out=None,
+                        group_map=None):
+    """One micro-step of a cycle of ``accum_steps`` calls.  Every call adds grad into accum (a buffer like grad; the cycle's
+    first call overwrites it) in fp32, left to right.  All but the cycle's last call change nothing else but accum_dev
+    (``OPTIM_ACCUM_WORDS`` int64: index of the next call in its cycle, calls, cycles, last call held).  The last call then takes
+    the step of ``adam_step_dev`` / ``adam_step_sched_dev`` / ``adam_step_groups_dev`` (sched_dev / groups_dev decide which) --
+    or, with guard, of ``adam_step_guard_dev`` -- on accum under ``float32(float64(grad_scale) / accum_steps)``, bit for bit.
+    The position in the cycle is read on the device: the call is the same every time (hipGraph-replayable).  Without guard:
+    partials and max_norm go together (both None = no clipping)."""
+    what = "adam_step_accum_dev"
+    acc = _chk_accum(what, param, accum, accum_dev, accum_steps, guard, partials)
+    sched, groups = _guard_forms(what, sched_dev, sched_out, ema, groups_dev, groups_out, group_map)
+    _optim_step(what, param, grad, (exp_avg, exp_avg_sq), (lr, betas[0], betas[1], eps, weight_decay, int(bool(decoupled))),
+                step_dev, st_dev, grad_scale, partials, max_norm, sched, groups, guard=guard, accum=acc)
+
+
+def sgd_step_accum_dev(param, grad, momentum_buf, step_dev, st_dev, accum, accum_dev, accum_steps, guard=None, partials=None,
+                       lr=1e-3, weight_decay=0.0, momentum=0.0, dampening=0.0, nesterov=False, grad_scale=1.0, max_norm=None,
+                       sched_dev=None, sched_out=None, ema=None, groups_dev=None, groups_out=None, group_map=None):
+    """``sgd_step_dev`` / ``sgd_step_sched_dev`` / ``sgd_step_groups_dev`` (with guard: ``sgd_step_guard_dev``) once per cycle of
+    ``accum_steps`` calls, on the accumulated gradient (see ``adam_step_accum_dev``)."""
+    what = "sgd_step_accum_dev"
+    acc = _chk_accum(what, param, accum, accum_dev, accum_steps, guard, partials)
+    sched, groups = _guard_forms(what, sched_dev, sched_out, ema, groups_dev, groups_out, group_map)
+    _optim_step(what, param, grad, (momentum_buf,), (lr, weight_decay, momentum, dampening, int(bool(nesterov))), step_dev,
+                st_dev, grad_scale, partials, max_norm, sched, groups, momentum=momentum, guard=guard, accum=acc)
 
 
 def nchw_to_nhwc8(x):

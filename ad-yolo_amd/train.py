@@ -76,11 +76,26 @@ class _FusedOptimizer:
     counter from the mirror reconciles first (``state_dict``, ``sched_state_dict``, setting ``step_count``, the fill of
     ``sync_device_step``, a graph capture).  Under data parallelism every rank holds the same reduced buffer and sums it in the
     same order, so every rank takes the same decision with no collective.  The guard protects what the optimizer owns:
-    BatchNorm running statistics are written by the forward pass and are not rolled back."""
+    BatchNorm running statistics are written by the forward pass and are not rolled back.
+
+    accum_steps (1 = off: the entry points above with their arguments, nothing more allocated): gradient accumulation over K
+    micro-batches.  Every ``step()`` -- every ``TrainStep.step``, eager or replayed -- is then a MICRO-STEP,
+    ``ops.*_step_accum_dev``: it adds ``flat.flat_grad`` into ``accum`` (laid out like it; fp32, left to right, as ``p.grad``
+    accumulates in torch; the cycle's first micro-step overwrites), and all but the K-th of a cycle do nothing else.  The K-th
+    takes the step the optimizer would take without accumulation on ``accum`` as its gradient under ``grad_scale / K`` (the
+    mean of the micro-gradients): the norm, the clip, the guard's verdict -- one poisoned micro-gradient makes the whole cycle
+    a skipped attempt --, the schedule's clock, the bias corrections and the EMA's count see one step per CYCLE.  Which
+    micro-step a call is, is read by the kernels from ``accum_dev`` (int64, ``ops.OPTIM_ACCUM_WORDS``: {next micro index,
+    calls, cycles, last call held}), so the call is the same every time and one recorded graph serves the whole cycle;
+    ``micro_index`` (0 .. K-1, the next call's) is the host's mirror, and ``step_count`` advances on a cycle's last call
+    only.  ``reset_accumulation()`` discards a partial cycle (the epoch loops call it when an epoch stops inside one);
+    ``state_dict()`` and the checkpoint refuse a mid-cycle state with ValueError, ``load_state_dict`` starts a new cycle.
+    BatchNorm statistics are per MICRO-batch, and the running statistics move on every micro-step, as in torch.  Under data
+    parallelism every micro-gradient is all-reduced before it is accumulated."""
 
     kind = None                     # 'adam' | 'adamw' | 'sgd': the torch.optim layout ``checkpoint`` reads and writes
 
-    def _init_common(self, flat, max_norm, skip_nonfinite=False):
+    def _init_common(self, flat, max_norm, skip_nonfinite=False, accum_steps=1):
         self.flat = flat
         self.max_norm = None if max_norm is None else float(max_norm)
         self.skip_nonfinite = bool(skip_nonfinite)
@@ -95,6 +110,10 @@ class _FusedOptimizer:
             self.grad_norm = self.st_dev[2:3]
         if self.skip_nonfinite:
             self.guard_dev = torch.zeros(ops.OPTIM_GUARD_WORDS, dtype=torch.int64, device=dev)
+        if _check_accum_steps(accum_steps) > 1:
+            self.accum_steps = int(accum_steps)
+            self.accum = torch.zeros_like(flat.flat_grad)
+            self.accum_dev = torch.zeros(ops.OPTIM_ACCUM_WORDS, dtype=torch.int64, device=dev)
 
     @property
     def step_count(self):
@@ -113,11 +132,37 @@ class _FusedOptimizer:
 
     def replayed(self):
         """A captured step (graph.py) was replayed: the optimizer launch inside it advanced the device counter (guarded: unless
-        it skipped, which ``reconcile`` corrects later)."""
+        it skipped, which ``reconcile`` corrects later; accumulating: on a cycle's last micro-step)."""
+        self._advance()
+
+    def _advance(self):
+        """the host's mirrors after one call of the step's launches, made now or replayed"""
+        if self.accum_dev is not None:
+            self.micro_index = (self.micro_index + 1) % self.accum_steps
+            if self.micro_index != 0:         # a hold call: the device moved the accumulator and its record, nothing else
+                return
         self._step_count += 1
         self._dev_step_value = self._step_count
         self._guard_dirty = True
         ops.params_changed()
+
+    # ------------------------------------------------------------------------------------------ gradient accumulation
+    accum_steps = 1
+    accum = accum_dev = None
+    micro_index = 0                 # which micro-step of its cycle the NEXT call is: the mirror of accum_dev[0]
+
+    def reset_accumulation(self):
+        """Discard a partial cycle: the next call is micro-step 0 of a new one, which overwrites the accumulator.  (A stream-
+        ordered device write, no sync; nothing to do when accumulation is off.)"""
+        if self.accum_dev is not None:
+            self.accum_dev[0:1].zero_()
+        self.micro_index = 0
+
+    def _accum_kw(self):
+        """what the accumulating entry points take beyond the guarded ones' arguments"""
+        return dict(accum=self.accum, accum_dev=self.accum_dev, accum_steps=self.accum_steps, guard=self.guard_dev,
+                    partials=self.clip_partials, max_norm=self.max_norm, sched_dev=self.sched_dev, sched_out=self.sched_out,
+                    ema=self.ema, groups_dev=self.groups_dev, groups_out=self.groups_out, group_map=self.group_map)
 
     # ------------------------------------------------------------------------------------------ non-finite guard
     guard_dev = None
@@ -322,10 +367,7 @@ class _FusedOptimizer:
     def step(self, grad_scale=1.0):
         self.sync_device_step()
         self._launch(grad_scale)
-        self._step_count += 1
-        self._dev_step_value = self._step_count
-        self._guard_dirty = True
-        ops.params_changed()
+        self._advance()
 
     def state_dict(self):
         """The matching torch.optim layout with parameter indices in ``model.parameters()`` order -- the format this build
@@ -334,11 +376,23 @@ class _FusedOptimizer:
         from . import checkpoint
         return checkpoint.optimizer_state_dict(self, None)
 
+    def _refuse_mid_cycle(self, what):
+        if self.micro_index != 0:
+            raise ValueError("%s in the middle of an accumulation cycle (micro-step %d of %d): a partial cycle is not saved; "
+                             "finish the cycle or drop it with reset_accumulation()"
+                             % (what, self.micro_index, self.accum_steps))
+
     def load_state_dict(self, sd):
         """(with a schedule: the clocks keep their values relative to the loaded ``step_count``; ``load_sched_state_dict``
         sets them)"""
         from . import checkpoint
-        checkpoint.load_optimizer_state_dict(self, None, sd)
+        checkpoint.load_optimizer_state_dict(self, None, sd)          # (starts a new accumulation cycle)
+
+
+def _check_accum_steps(k):
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise ValueError("accum_steps must be an integer >= 1 (1 = no gradient accumulation), not %r" % (k,))
+    return k
 
 
 class FusedAdam(_FusedOptimizer):
@@ -349,14 +403,19 @@ class FusedAdam(_FusedOptimizer):
     kind = "adam"
 
     def __init__(self, flat: FlatParameters, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_norm=None,
-                 lr_schedule=None, ema_decay=None, ema_warmup=False, param_groups=None, skip_nonfinite=False):
+                 lr_schedule=None, ema_decay=None, ema_warmup=False, param_groups=None, skip_nonfinite=False, accum_steps=1):
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         self.exp_avg = torch.zeros_like(flat.flat)
         self.exp_avg_sq = torch.zeros_like(flat.flat)
-        self._init_common(flat, max_norm, skip_nonfinite)
+        self._init_common(flat, max_norm, skip_nonfinite, accum_steps)
         self._init_sched(lr_schedule, ema_decay, ema_warmup, param_groups)
 
     def _launch(self, grad_scale):
+        if self.accum_dev is not None:
+            return ops.adam_step_accum_dev(self.flat.flat, self.flat.flat_grad, self.exp_avg, self.exp_avg_sq, self.step_dev,
+                                           self.st_dev, lr=self.lr, betas=self.betas, eps=self.eps,
+                                           weight_decay=self.weight_decay, grad_scale=grad_scale,
+                                           decoupled=self.kind == "adamw", **self._accum_kw())
         if self.guard_dev is not None:
             return ops.adam_step_guard_dev(self.flat.flat, self.flat.flat_grad, self.exp_avg, self.exp_avg_sq, self.step_dev,
                                            self.st_dev, self.guard_dev, self.clip_partials, self.lr, self.betas, self.eps,
@@ -384,9 +443,9 @@ class FusedAdamW(FusedAdam):
     kind = "adamw"
 
     def __init__(self, flat: FlatParameters, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_norm=None,
-                 lr_schedule=None, ema_decay=None, ema_warmup=False, param_groups=None, skip_nonfinite=False):
+                 lr_schedule=None, ema_decay=None, ema_warmup=False, param_groups=None, skip_nonfinite=False, accum_steps=1):
         super().__init__(flat, lr, betas, eps, weight_decay, max_norm, lr_schedule, ema_decay, ema_warmup, param_groups,
-                         skip_nonfinite)
+                         skip_nonfinite, accum_steps)
 
 
 class FusedSGD(_FusedOptimizer):
@@ -400,10 +459,11 @@ class FusedSGD(_FusedOptimizer):
     kind = "sgd"
 
     def __init__(self, flat: FlatParameters, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False,
-                 max_norm=None, lr_schedule=None, ema_decay=None, ema_warmup=False, param_groups=None, skip_nonfinite=False):
+                 max_norm=None, lr_schedule=None, ema_decay=None, ema_warmup=False, param_groups=None, skip_nonfinite=False,
+                 accum_steps=1):
         if nesterov and (momentum <= 0 or dampening != 0):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
-        self._init_common(flat, max_norm, skip_nonfinite)
+        self._init_common(flat, max_norm, skip_nonfinite, accum_steps)
         self.lr, self.momentum, self.dampening, self.weight_decay = lr, momentum, dampening, weight_decay
         self.nesterov = bool(nesterov)
         self.momentum_buffer = torch.zeros_like(flat.flat) if momentum != 0 else None
@@ -415,6 +475,11 @@ class FusedSGD(_FusedOptimizer):
         return self._step_count == 0
 
     def _launch(self, grad_scale):
+        if self.accum_dev is not None:
+            return ops.sgd_step_accum_dev(self.flat.flat, self.flat.flat_grad, self.momentum_buffer, self.step_dev, self.st_dev,
+                                          lr=self.lr, weight_decay=self.weight_decay, momentum=self.momentum,
+                                          dampening=self.dampening, nesterov=self.nesterov, grad_scale=grad_scale,
+                                          **self._accum_kw())
         if self.guard_dev is not None:
             return ops.sgd_step_guard_dev(self.flat.flat, self.flat.flat_grad, self.momentum_buffer, self.step_dev, self.st_dev,
                                           self.guard_dev, self.clip_partials, self.lr, self.weight_decay, self.momentum,
@@ -444,7 +509,8 @@ def get_optimizers(params: dict, flat: FlatParameters):
     weight_decay}``, see ``param_groups.py``; absent or empty = one rate and one decay for all parameters);
     ``skip_nonfinite`` (default false: today's step; true: a step whose gradient is not finite is skipped on the device, see
     ``_FusedOptimizer``) and ``skip_nonfinite_patience`` (default 10, None = off: the epoch loops raise FloatingPointError
-    when an epoch ends in that many consecutive skipped steps)."""
+    when an epoch ends in that many consecutive skipped steps); ``accum_steps`` (an integer >= 1, default 1 = off: gradient
+    accumulation, one optimizer step per that many calls of ``step``, see ``_FusedOptimizer``)."""
     tc = params["train_config"]
     name = tc.get("optim", "Adam")
     if name not in ("Adam", "AdamW", "SGD"):
@@ -457,6 +523,8 @@ def get_optimizers(params: dict, flat: FlatParameters):
         extra["param_groups"] = groups
     if tc.get("skip_nonfinite", False):
         extra["skip_nonfinite"] = True
+    if _check_accum_steps(tc.get("accum_steps", 1)) > 1:
+        extra["accum_steps"] = tc["accum_steps"]
     if name == "Adam":
         return FusedAdam(flat, lr=lr, weight_decay=wd, max_norm=clip, **extra)
     if name == "AdamW":
@@ -596,28 +664,50 @@ class _EpochLoss:
     record (a multiply would not do: NaN * 0 is NaN) -- the applied steps are counted on the device, the mean is over them,
     and the record comes to the host in the same read, where the optimizer reconciles its ``step_count`` with it.  An epoch
     that ENDS in ``train_config['skip_nonfinite_patience']`` (default 10; None = never) or more consecutive skipped steps
-    raises FloatingPointError: a model whose weights are already not finite would otherwise skip for ever in silence."""
+    raises FloatingPointError: a model whose weights are already not finite would otherwise skip for ever in silence.
+
+    Under gradient accumulation (``train_config['accum_steps']``) every call of ``add`` is a micro-step.  Without the guard
+    nothing changes: the mean over all micro-steps.  With it the guard's flag speaks for a whole cycle and only after the
+    cycle's last micro-step, so the micro losses wait in a pending sum that is folded in, by the same ``torch.where``, when the
+    cycle ends: the mean is over the micro-steps of the applied cycles.  ``drop_partial_cycle()`` ends an epoch that stops
+    inside a cycle: the optimizer's accumulation is reset and the pending losses are dropped with it."""
 
     def __init__(self, params, trainer):
         self.optimizer = getattr(trainer, "optimizer", None)
         self.guard = getattr(self.optimizer, "guard_dev", None)
+        self.cycles = self.guard is not None and getattr(self.optimizer, "accum_steps", 1) > 1
         self.patience = params.get("train_config", {}).get("skip_nonfinite_patience", 10)
-        self.total = self.applied = None
-        self.n = 0
+        self.total = self.applied = self.pending = None
+        self.n = self.n_pending = 0
 
     def add(self, loss):
         loss = loss.detach().reshape(-1)[:1]
+        self.n += 1
         if self.guard is not None:
+            count = 1
+            if self.cycles:
+                self.pending = loss.clone() if self.pending is None else self.pending + loss
+                self.n_pending += 1
+                if self.optimizer.micro_index != 0:           # the cycle goes on: the flag still speaks for the last one
+                    return
+                loss, count, self.pending, self.n_pending = self.pending, self.n_pending, None, 0
             ok = self.guard[2:3] == 0
             loss = torch.where(ok, loss, torch.zeros_like(loss))
-            self.applied = ok.to(torch.int64) if self.applied is None else self.applied + ok
+            ok_n = ok.to(torch.int64) if count == 1 else ok * count
+            self.applied = ok_n if self.applied is None else self.applied + ok_n
         self.total = loss.clone() if self.total is None else self.total + loss
-        self.n += 1
+
+    def drop_partial_cycle(self):
+        if getattr(self.optimizer, "micro_index", 0) != 0:
+            self.optimizer.reset_accumulation()
+        self.pending, self.n_pending = None, 0
 
     def mean(self, *also):
         """-> (the mean loss, host copies of ``also``) with one device read"""
-        if self.total is None:
+        if self.total is None and self.n == 0:
             return 0.0, list(also)
+        if self.total is None:                                # (guarded accumulation: no cycle of this epoch came to its end)
+            self.total, self.applied = torch.zeros_like(self.guard[:1], dtype=torch.float32), self.guard[:1] * 0
         mine = (self.total,) if self.guard is None else (self.total, self.applied, self.guard)
         host = ops.to_host_many(*mine, *also) if self.total.is_cuda else [t.clone() for t in mine + also]
         if self.guard is None:
@@ -636,7 +726,9 @@ def train_one_epoch_audio(params: dict, dataloader, trainer, stager=None, rotate
     tables (B,2,4)]); each is staged to the GPU (int16 over PCIe on a side stream, double-buffered), converted, rotated and
     handed with its tables to ``TrainStep.step`` (features [+ SpecAug masks] + forward + loss + backward [+ all-reduce] +
     Adam).  Returns the mean loss with ONE device sync at the end of the epoch (the reference syncs every iteration,
-    train.py:57); with ``train_config['skip_nonfinite']`` the mean over the APPLIED steps (``_EpochLoss``)."""
+    train.py:57); with ``train_config['skip_nonfinite']`` the mean over the APPLIED steps (``_EpochLoss``).  With
+    ``train_config['accum_steps']`` every batch is a micro-step; an epoch whose number of batches is no multiple of it (or that
+    ``quick_test`` cuts short) ends inside a cycle, and that partial cycle is DROPPED: its gradients take part in no step."""
     from .augmentations import rotate_audio
     from .datasets import AudioStager
     acc, n = _EpochLoss(params, trainer), 0
@@ -661,6 +753,7 @@ def train_one_epoch_audio(params: dict, dataloader, trainer, stager=None, rotate
         n += 1
         if nxt is None or (params.get("args", {}).get("quick_test") and n == 5):
             break
+    acc.drop_partial_cycle()
     return acc.mean()[0]
 
 
@@ -673,7 +766,8 @@ def train_one_epoch_corpus(params: dict, corpus, trainer):
     runs, in the order the host path draws them.  Returns the mean loss with ONE device sync at the end, where the corpus' status
     word is read too: a batch with more rows than the capacity, an item outside the corpus or a class outside the model's
     raises.  With ``train_config['skip_nonfinite']``: the mean over the APPLIED steps, the guard record in the same read
-    (``_EpochLoss``)."""
+    (``_EpochLoss``).  With ``train_config['accum_steps']``: micro-steps, and a partial cycle at the end of the epoch is dropped,
+    as in ``train_one_epoch_audio``."""
     bs = int(params["train_config"]["batch_size"])
     files = corpus.get_filelist()
     starts = list(range(0, len(files), bs))
@@ -699,6 +793,7 @@ def train_one_epoch_corpus(params: dict, corpus, trainer):
             nxt = corpus.draw(range(starts[k + 1], min(len(files), starts[k + 1] + bs)))
         if nxt is None or (params.get("args", {}).get("quick_test") and n == 5):
             break
+    acc.drop_partial_cycle()
     mean, (status,) = acc.mean(corpus.status)
     corpus.check(int(status[0]))
     return mean

@@ -782,6 +782,33 @@ int  adyolo_sgd_step_guard_dev(float *param, const float *grad, float *momentum_
                                double *partials, float max_norm, float grad_scale, const double *sched_dev, float *sched_out,
                                float *ema, const double *groups_dev, float *groups_out, int n_groups,
                                const unsigned char *group_map, int64_t *guard, void *stream);
+/* The accumulating steps: K micro-batches, one optimizer step, decided on the device inside the (recorded) step.  Every call
+ * is a micro-step of a cycle of accum_steps calls; which one is read from the record, so the launches and their arguments
+ * are the same for every call and one recording serves them all (accum_steps is a constant of a recorded step).
+ *   accum      n floats laid out like grad, 16-byte aligned: the fp32 sum of the cycle's gradients so far, added left to
+ *              right, ((g0 + g1) + g2) ...; the cycle's first call overwrites it without reading it
+ *   accum_dev  adyolo_optim_accum_words() (= 4) int64, 8-byte aligned, written by the prep kernel only: {index of the next
+ *              call inside its cycle, calls so far, cycles completed, the last call was a hold call (0 / 1)}.  Writing 0 to
+ *              the first word between calls discards a partial cycle.
+ * A hold call (not the last of its cycle) changes accum and the record and nothing else.  The cycle's last call adds its
+ * gradient in and then takes the step the form's own entry point would take with grad = accum and
+ * grad_scale = (float)((double)grad_scale / accum_steps), bit for bit: norm, clip coefficient, guard, counter, schedule and
+ * EMA see one step per cycle.  The arguments are the guarded entry points' with guard optional: guard == NULL is the
+ * unguarded step, and partials == NULL then means no clipping; with a guard a non-finite value in any micro-gradient of the
+ * cycle makes the cycle's last call a skipped attempt. */
+int  adyolo_optim_accum_words(void);
+int  adyolo_adam_step_accum_dev(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, long n, float lr, float beta1,
+                                float beta2, float eps, float weight_decay, int decoupled, uint64_t *step_dev, float *st_dev,
+                                double *partials, float max_norm, float grad_scale, const double *sched_dev, float *sched_out,
+                                float *ema, const double *groups_dev, float *groups_out, int n_groups,
+                                const unsigned char *group_map, int64_t *guard, float *accum, int64_t *accum_dev,
+                                int accum_steps, void *stream);
+int  adyolo_sgd_step_accum_dev(float *param, const float *grad, float *momentum_buf, long n, float lr, float weight_decay,
+                               float momentum, float dampening, int nesterov, uint64_t *step_dev, float *st_dev,
+                               double *partials, float max_norm, float grad_scale, const double *sched_dev, float *sched_out,
+                               float *ema, const double *groups_dev, float *groups_out, int n_groups,
+                               const unsigned char *group_map, int64_t *guard, float *accum, int64_t *accum_dev,
+                               int accum_steps, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * K9a multi-head self-attention core, flash style on the exact-fp32 matrix cores (csrc/attention.hip).

@@ -5,7 +5,9 @@ up, repeated).
             with 'Adam' (ops.adam_step_dev, the baseline), 'AdamW', 'SGD' (plain, as the reference calls it), 'Adam' with
             clip_grad_norm 3, 'Adam' under a device-side lr_schedule (ops.adam_step_sched_dev) and the same with ema_decay;
             'AdamW' under the schedule without and with the no-decay parameter grouping (ops.adam_step_groups_dev); 'Adam'
-            behind the non-finite guard (skip_nonfinite, ops.adam_step_guard_dev) without and with clip_grad_norm 3
+            behind the non-finite guard (skip_nonfinite, ops.adam_step_guard_dev) without and with clip_grad_norm 3; 'Adam'
+            and the guarded clipped 'Adam' with accum_steps 4 (ops.adam_step_accum_dev: the mean over a cycle's four replays,
+            three hold calls and one step)
   kernels   the optimizer launches alone on buffers of the real model's flat size (6.68 M floats): adam_step_dev (baseline),
             adamw_step_dev, sgd_step_dev without / with momentum, adam_step_dev with clipping, grad_norm_dev (sum of squares +
             prep); the scheduled forms adam / adamw / sgd_step_sched_dev (cosine with warm-up: the prep kernel's most expensive
@@ -13,7 +15,11 @@ up, repeated).
             adam / adamw (+ EMA) / sgd_step_groups_dev with the real model's ``ndim_max: 1`` group map (150 runs), each beside
             its ungrouped scheduled counterpart; the guarded steps adam / adamw grouped + EMA / sgd_step_guard_dev without
             and with clipping, each beside the unguarded step of the same form without and with clipping (a guarded
-            unclipped step should cost what the clipped one costs, a guarded clipped step the same again)
+            unclipped step should cost what the clipped one costs, a guarded clipped step the same again); the accumulating
+            steps adam / adamw grouped + EMA (guarded, clipped) / sgd_step_accum_dev as a hold call (the accumulation pass, a
+            one-workgroup prep and an update launch that returns at once; 12 bytes per element, 8 on a cycle's first call)
+            and as a cycle's last call (the pass with the sum of squares fused in, then the step) -- the record is put at the
+            wanted micro index by a 32-byte device copy in front of each call, timed alone as accum_record_preset
 
 At 16 x 20 s the trainers live side by side and alternate inside each repeat; at 64 x 60 s they are built one after the
 other (activations of one recorded step at a time).  The median of the repeats is reported (ms per call).
@@ -46,7 +52,9 @@ VARIANTS = {"adam": {"optim": "Adam"},
                                    "lr_schedule": {"name": "cosine", "T_max": 1000, "warmup_steps": 100},
                                    "param_groups": [{"name": "no_decay", "ndim_max": 1, "weight_decay": 0.0}]},
             "adam_guard": {"optim": "Adam", "skip_nonfinite": True},
-            "adam_clip3_guard": {"optim": "Adam", "clip_grad_norm": 3.0, "skip_nonfinite": True}}
+            "adam_clip3_guard": {"optim": "Adam", "clip_grad_norm": 3.0, "skip_nonfinite": True},
+            "adam_accum4": {"optim": "Adam", "accum_steps": 4},
+            "adam_clip3_guard_accum4": {"optim": "Adam", "clip_grad_norm": 3.0, "skip_nonfinite": True, "accum_steps": 4}}
 
 
 def timed(fns, reps, iters):
@@ -79,7 +87,7 @@ def make_trainer(b, n, variant):
 
 
 def warm(tr, audio, target):
-    for _ in range(4):                         # eager warm-up, capture, replays
+    for _ in range(4):                         # eager warm-up, capture, replays (accumulating: one whole cycle of 4)
         tr.step(audio, target)
     torch.cuda.synchronize()
     assert tr.graphs is not None and tr.graphs.captures == 1 and tr.graphs.replays >= 2, "the step was not recorded"
@@ -144,7 +152,31 @@ def bench_kernels(reps, iters):
     gout = torch.zeros(2, ops.GROUP_OUT_FLOATS, device="cuda:0")
     guard = torch.zeros(ops.OPTIM_GUARD_WORDS, dtype=torch.int64, device="cuda:0")
     form = dict(sched_dev=sched_ema, sched_out=out, ema=ema, groups_dev=gdev_w, groups_out=gout, group_map=gmap)
+    # the accumulating steps: K = 4; the record is copied into place before each call: index 0 (a cycle's first call, which
+    # overwrites), 1 (a hold call that adds) or 3 (the cycle's last call)
+    accum = torch.zeros_like(p)
+    acc = torch.zeros(ops.OPTIM_ACCUM_WORDS, dtype=torch.int64, device="cuda:0")
+    at = {k: torch.tensor([k, 0, 0, 0], dtype=torch.int64, device="cuda:0") for k in (0, 1, 3)}
+
+    def micro(index, fn, *args, **kw):
+        def call():
+            acc.copy_(at[index])
+            fn(*args, accum, acc, 4, **kw)
+        return call
+
+    adam_args, sgd_args = (ops.adam_step_accum_dev, p, grad, m, v, step_dev, st), (ops.sgd_step_accum_dev, p, grad, None, step_dev, st)
+    full = dict(guard=guard, partials=parts, max_norm=3.0, decoupled=True, **form)
     fns = {
+        "accum_record_preset": lambda: acc.copy_(at[1]),
+        "adam_step_accum_dev_first": micro(0, *adam_args),
+        "adam_step_accum_dev_hold": micro(1, *adam_args),
+        "adam_step_accum_dev_last": micro(3, *adam_args),
+        "adam_step_accum_dev_clip_last": micro(3, *adam_args, partials=parts, max_norm=3.0),
+        "adamw_step_accum_dev_guard_groups_ema_clip_hold": micro(1, *adam_args, **full),
+        "adamw_step_accum_dev_guard_groups_ema_clip_last": micro(3, *adam_args, **full),
+        "sgd_step_accum_dev_first": micro(0, *sgd_args),
+        "sgd_step_accum_dev_hold": micro(1, *sgd_args),
+        "sgd_step_accum_dev_last": micro(3, *sgd_args),
         "adam_step_guard_dev": lambda: ops.adam_step_guard_dev(p, grad, m, v, step_dev, st, guard, parts),
         "adam_step_guard_dev_clip": lambda: ops.adam_step_guard_dev(p, grad, m, v, step_dev, st, guard, parts, max_norm=3.0),
         "adamw_step_groups_dev_ema_clip": lambda: ops.adam_step_groups_dev(p, grad, m, v, step_dev, st, sched_ema, out, gdev_w,

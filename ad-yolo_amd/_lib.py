@@ -131,7 +131,9 @@ SIGNATURES = {
     "adyolo_seed32_dev": (I, [ctypes.c_uint64, ctypes.c_uint64, P, P, P]),
     "adyolo_attn_dropout_mask": (I, [P, I, I, I, F, ctypes.c_uint32, P]),
     "adyolo_foa_rotate": (I, [P, P, P, I, L, P]),
+    "adyolo_mic_swap": (I, [P, P, P, I, L, P]),
     "adyolo_corpus_gather": (I, [P, L, P, I, L, P, P, P, P]),
+    "adyolo_corpus_gather_mic": (I, [P, L, P, I, L, P, P, P, P]),
     "adyolo_corpus_yolo_labels_workspace_words": (L, [I, I]),
     "adyolo_corpus_yolo_labels": (I, [P, L, P, I, I, I, P, I, I, P, P, P, L, P, P, P]),
     "adyolo_corpus_classwise_labels": (I, [P, P, L, P, I, I, I, I, I, P, P, P]),

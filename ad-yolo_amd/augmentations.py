@@ -1,8 +1,10 @@
-"""FOA rotation augmentation.  Mirror of ``RotationAug`` (/root/reference/src/utils/augmentations.py:36-111): 16
+"""FOA rotation and MIC channel-swap augmentation.  Mirror of ``RotationAug`` (/root/reference/src/utils/augmentations.py:36-111): 16
 combinations of channel sign flips / X-Y swap with the matching azimuth / elevation remapping of the labels.
 ``rotate_labels`` is the host half (label dict); ``rotate_audio`` applies the channel transform to a whole batch of raw
-audio on the GPU (csrc/aug.hip ``foa_rotate_kernel``).  ``SpecAug`` (augmentations.py:6-33) masks the GPU feature
-tensor (csrc/aug.hip); its random draw restates torchaudio 0.10, which is absent here (parity of the stream unpinned)."""
+audio on the GPU (csrc/aug.hip ``foa_rotate_kernel``).  ``swap_audio`` / ``ChannelSwapAug`` are the MIC-format counterpart (no
+reference: a permutation of the four capsules by a symmetry of the array, derived below from ``rotate_labels``).  ``SpecAug``
+(augmentations.py:6-33) masks the GPU feature tensor (csrc/aug.hip); its random draw restates torchaudio 0.10, which is absent
+here (parity of the stream unpinned)."""
 import random
 
 import torch
@@ -50,6 +52,84 @@ def rotate_audio(audio, comb_nos):
     out = torch.empty_like(audio)
     _lib.call("adyolo_foa_rotate", _p(audio), _p(out), _p(cfg), b, n, _stream())
     return out
+
+
+# ---- MIC channel swap (ACS): the MIC-format counterpart of the FOA rotation.  The four capsules of the DCASE tetrahedral array
+# (channel 0..3 = M1..M4, azimuth / elevation in degrees); a label map of COMBINATIONS that sends every capsule onto a capsule
+# is a symmetry of the array, and permuting the channels the same way keeps the audio in agreement with the moved labels.
+MIC_DIRECTIONS = ((45, 35), (-45, -35), (135, -35), (-135, 35))
+
+
+def _mic_symmetries():
+    """{combination: (s0, s1, s2, s3)}, derived from ``rotate_labels``: combination k maps capsule i onto capsule pi(i) (or is
+    no symmetry); a source heard by capsule i is, after the map, heard by capsule pi(i): new[pi(i)] = old[i], s = pi^-1."""
+    out = {}
+    for k in range(len(COMBINATIONS)):
+        images = [tuple(ev[2:]) for ev in rotate_labels({0: [[0, 0, az, el] for az, el in MIC_DIRECTIONS]}, k)[0]]
+        if all(d in MIC_DIRECTIONS for d in images):
+            pi = [MIC_DIRECTIONS.index(d) for d in images]
+            out[k] = tuple(pi.index(j) for j in range(4))
+    return out
+
+
+_MIC_SWAP_SOURCE = _mic_symmetries()
+MIC_SWAP_COMBS = tuple(sorted(_MIC_SWAP_SOURCE))
+assert MIC_SWAP_COMBS == (0, 3, 4, 7, 9, 10, 13, 14), MIC_SWAP_COMBS
+assert [_MIC_SWAP_SOURCE[k] for k in MIC_SWAP_COMBS] == [(0, 1, 2, 3), (1, 0, 3, 2), (3, 2, 1, 0), (2, 3, 0, 1), (1, 3, 0, 2),
+                                                        (0, 2, 1, 3), (2, 0, 3, 1), (3, 1, 2, 0)], _MIC_SWAP_SOURCE
+
+
+def mic_swap_source(comb_no):
+    """Combination (one of ``MIC_SWAP_COMBS``) -> (s0, s1, s2, s3): output channel j is input channel s_j."""
+    src = _MIC_SWAP_SOURCE.get(int(comb_no))
+    if src is None:
+        raise ValueError("mic_swap_source: combination %r is not a symmetry of the microphone array (the symmetries are %s)"
+                         % (comb_no, list(MIC_SWAP_COMBS)))
+    return src
+
+
+def channel_swap_enabled(params):
+    """``aug_config.channel_swap_augment``, with its two refusals: MIC-format audio only, and not together with the FOA
+    rotation (``ValueError``: both would move the labels)."""
+    aug = params.get("aug_config", {})
+    if not bool(aug.get("channel_swap_augment", False)):
+        return False
+    fmt = str(params.get("data_config", {}).get("audio_format", "foa")).lower()
+    if fmt != "mic":
+        raise ValueError("aug_config.channel_swap_augment permutes microphone capsules: it needs data_config.audio_format "
+                         "'mic' (got %r; rotation_augment is the FOA augmentation)" % fmt)
+    if bool(aug.get("rotation_augment", False)):
+        raise ValueError("aug_config.channel_swap_augment and aug_config.rotation_augment are both on: rotation_augment is "
+                         "the FOA augmentation, a MIC run takes channel_swap_augment alone")
+    return True
+
+
+def swap_audio(audio, comb_nos):
+    """audio (B, n_samples, 4) float32 on the GPU, comb_nos: B combinations of ``MIC_SWAP_COMBS`` -> the audio with its channels
+    permuted (new tensor; csrc/aug.hip ``mic_swap_kernel``).  ``ValueError`` for any other combination, before any launch."""
+    src = [mic_swap_source(c) for c in comb_nos]
+    if not audio.is_cuda or audio.dtype != torch.float32 or not audio.is_contiguous():
+        raise _lib.AdyoloHipError("swap_audio needs contiguous float32 audio (B, n_samples, 4) on the GPU")
+    if audio.dim() != 3 or audio.shape[2] != 4 or audio.shape[0] != len(src):
+        raise _lib.AdyoloHipError("swap_audio: audio %s with %d combinations, expected (B, n_samples, 4) and B of them"
+                                  % (tuple(audio.shape), len(src)))
+    from . import ops
+    return ops.mic_swap(audio, torch.tensor(src, dtype=torch.int32).reshape(-1, 4).to(audio.device))
+
+
+class ChannelSwapAug:
+    """``RotationAug``'s surface for MIC-format audio: ``augment(audio (T,4) on the GPU, label)`` with one of the eight
+    symmetries of the array (``aug_config.channel_swap_augment``; never on validation data)."""
+
+    def __init__(self, params: dict, is_valid: bool):
+        self.apply_augment = channel_swap_enabled(params) and not is_valid
+
+    def augment(self, audio, label, comb_no=None):
+        if not self.apply_augment:
+            return audio, label
+        if comb_no is None:
+            comb_no = MIC_SWAP_COMBS[int(random.uniform(0, len(MIC_SWAP_COMBS)))]
+        return swap_audio(audio.view(1, -1, 4), [comb_no]).view_as(audio), rotate_labels(label, comb_no)
 
 
 class RotationAug:

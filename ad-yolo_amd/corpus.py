@@ -12,8 +12,8 @@ rotates and encodes the labels on the host and stages every batch over PCIe.  He
 * ``DeviceCorpus`` (device half, AD-YOLO): the streams as one int16 buffer and the events as one float64 table in HBM (0.69 GB
   per hour of 4-channel 24 kHz audio), ``FoaDataset``'s sampling surface (the same functions), and ``batch(indices)``: the same
   ``random`` draws as ``FoaDataset.__getitem__`` item by item, one small H2D copy of the item table, then ``adyolo_corpus_gather``
-  (audio, rotated) and ``adyolo_corpus_yolo_labels`` (the AD-YOLO rows into a fixed-capacity target, padding b = -1).  No host
-  sync.
+  (audio, rotated; with ``aug_config.channel_swap_augment`` ``adyolo_corpus_gather_mic``: MIC capsules permuted) and
+  ``adyolo_corpus_yolo_labels`` (the AD-YOLO rows into a fixed-capacity target, padding b = -1).  No host sync.
 * ``ClasswiseDeviceCorpus`` (device half, ``seddoa | masked-seddoa | accdoa | adpit``): the same split, sampling, draws and
   gather; the labels are ``adyolo_corpus_classwise_labels``, the dense ``ClasswiseLabelEncoder`` targets of the batch written
   whole, from a float32 table of every event's direction vector under no rotation and the 16 FOA combinations (``xyz_table``,
@@ -282,7 +282,7 @@ class _CorpusBase:
     __len__ = FoaDataset.__len__
 
     def _setup(self, host_corpus, params, device, rank, world):
-        from .augmentations import COMBINATIONS, SpecAug
+        from .augmentations import MIC_SWAP_COMBS, SpecAug, channel_swap_enabled, mic_swap_source
         self.host = hc = host_corpus
         self.device = torch.device(device)
         self._copy, self._os, self._random = copy, os, random
@@ -291,6 +291,9 @@ class _CorpusBase:
         self.wav_pth, self.csv_pth = hc.wav_pth, hc.csv_pth
         self.hop_label = hc.hop_label
         self.rotate = bool(params.get("aug_config", {}).get("rotation_augment", False))
+        # MIC channel swap (ValueError: audio_format is not 'mic', or rotation_augment is on as well): the gather's table
+        self.swap = channel_swap_enabled(params)
+        self.mic_src = ops.corpus_mic_table({k: mic_swap_source(k) for k in MIC_SWAP_COMBS}) if self.swap else None
         self.specaug = SpecAug(params, False)
         self.batch_size = int(params["train_config"]["batch_size"])
         self.n_samples, self.n_label_frames = hc.window, hc.window // hc.hop_label
@@ -321,8 +324,9 @@ class _CorpusBase:
 
     # ---------------------------------------------------------------------------------------------------------- batches
     def draw(self, indices):
-        """The host half of a batch: ``FoaDataset.__getitem__``'s ``random`` draws item by item (rotation, then SpecAug) and the
-        item table -> (items int64 (B, 8), spec int32 (B, 2, 4) or None), host arrays."""
+        """The host half of a batch: ``FoaDataset.__getitem__``'s ``random`` draws item by item (rotation or channel swap, then
+        SpecAug) and the item table -> (items int64 (B, 8), spec int32 (B, 2, 4) or None), host arrays."""
+        from .augmentations import MIC_SWAP_COMBS
         from .features import HOP, N_MELS
         names = [self.filelist[i] for i in indices]
         b = len(names)
@@ -334,6 +338,8 @@ class _CorpusBase:
             comb = -1
             if self.rotate:
                 comb = int(self._random.uniform(0, 16))                       # augmentations.py:76, as in __getitem__
+            elif self.swap:
+                comb = MIC_SWAP_COMBS[int(self._random.uniform(0, 8))]        # as in __getitem__: one draw
             if spec is not None:
                 spec[j] = self.specaug.draw_groups(1, self.n_samples // HOP, N_MELS, 2)[0].numpy()
             items[j] = (off, f_off, ev_lo, ev_n, comb, rec, 0, 0)
@@ -371,6 +377,12 @@ class _CorpusBase:
         """Items ``indices`` of ``get_filelist()`` -> (audio (B, n, 4) f32, target, spec (B, 2, 4) int32 or None), on the device,
         with no host synchronisation.  audio_out / target_out: write into these buffers (a recorded step's)."""
         return self.launch(self.draw(indices), audio_out, target_out)
+
+    def _gather(self, dev_items, audio):
+        """The audio of a batch: FOA-rotated, or with ``aug_config.channel_swap_augment`` the MIC capsules permuted."""
+        if self.swap:
+            return ops.corpus_gather_mic(self.pcm, dev_items, self.mic_src, audio, self.status)
+        return ops.corpus_gather(self.pcm, dev_items, self.rot, audio, self.status)
 
     def reset_status(self):
         self.status.zero_()
@@ -430,7 +442,7 @@ class DeviceCorpus(_CorpusBase):
                              % (tuple(audio.shape), tuple(target.shape), b, self.n_samples, self.cap))
         ws = torch.empty(max(1, ops.corpus_labels_workspace_words(b, self.max_events)), dtype=torch.int32, device=self.device)
         self.rows = torch.empty(1, dtype=torch.int32, device=self.device)
-        ops.corpus_gather(self.pcm, dev_items, self.rot, audio, self.status)
+        self._gather(dev_items, audio)
         ops.corpus_yolo_labels(self.events, dev_items, self.max_events, self.n_label_frames, self.bounds, self.grid, self.rot, ws,
                                target, self.rows, self.status)
         return audio, target, dev_spec
@@ -486,7 +498,7 @@ class ClasswiseDeviceCorpus(_CorpusBase):
         if tuple(audio.shape) != (b, self.n_samples, 4) or tuple(target.shape) != shape:
             raise ValueError("ClasswiseDeviceCorpus.launch: output buffers %s / %s, expected (%d, %d, 4) / %s"
                              % (tuple(audio.shape), tuple(target.shape), b, self.n_samples, shape))
-        ops.corpus_gather(self.pcm, dev_items, self.rot, audio, self.status)
+        self._gather(dev_items, audio)
         ops.corpus_classwise_labels(self.events, dev_items, self.xyz, self.max_events, self.n_label_frames, self.nb_classes,
                                     self.loss_nm, target, self.status)
         return audio, target, dev_spec

@@ -192,3 +192,41 @@ extern "C" int adyolo_foa_rotate(const float *audio, float *out, const float *cf
                        (const float4 *)audio, (float4 *)out, cfg, n_samples);
     return adyolo::check_launch("foa_rotate");
 }
+
+// ---- MIC channel-swap augmentation on raw audio (augmentations.swap_audio): per clip a permutation of the four capsules,
+// out[b][i][j] = audio[b][i][src[b][j] & 3].  One 16-byte load and one 16-byte store per frame; the clip's four selectors are
+// uniform over the workgroup (blockIdx.y = clip: scalar loads, once), so each output word is three bit selects between the
+// frame's registers.  The frame travels as four 32-bit integers: nothing is computed on the values, NaN payloads and -0.0 keep their bits.
+namespace adyolo {
+// word s of the frame through two all-ones / all-zeros masks of the selector's bits (and / or on scalar masks): no branch in the loop
+__device__ __forceinline__ int mic_pick(const int4 &v, int s) {
+    const int m0 = -(s & 1), m1 = -((s >> 1) & 1);
+    const int lo = (v.y & m0) | (v.x & ~m0), hi = (v.w & m0) | (v.z & ~m0);
+    return (hi & m1) | (lo & ~m1);
+}
+
+__global__ __launch_bounds__(256) void mic_swap_kernel(const int4 *__restrict__ x, int4 *__restrict__ y,
+                                                       const int *__restrict__ sel, long n_per_clip) {
+    const int b = blockIdx.y;
+    const int s0 = sel[b * 4 + 0] & 3, s1 = sel[b * 4 + 1] & 3, s2 = sel[b * 4 + 2] & 3, s3 = sel[b * 4 + 3] & 3;
+    const int4 *src = x + (size_t)b * n_per_clip;
+    int4 *dst = y + (size_t)b * n_per_clip;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n_per_clip; i += (long)gridDim.x * blockDim.x) {
+        const int4 v = src[i];
+        dst[i] = make_int4(mic_pick(v, s0), mic_pick(v, s1), mic_pick(v, s2), mic_pick(v, s3));
+    }
+}
+}  // namespace adyolo
+
+extern "C" int adyolo_mic_swap(const float *audio, float *out, const int *src_dev, int B, long n_samples, void *stream) {
+    ADYOLO_REQUIRE(audio && out && src_dev && B > 0 && B < 65536 && n_samples > 0, ADYOLO_EINVAL, "mic_swap: bad arguments");
+    ADYOLO_REQUIRE(((uintptr_t)audio & 15) == 0 && ((uintptr_t)out & 15) == 0 && ((uintptr_t)src_dev & 3) == 0, ADYOLO_EINVAL,
+                   "mic_swap: misaligned buffers (audio / out 16 bytes, src 4 bytes)");
+    const size_t words = (size_t)B * (size_t)n_samples * 4;
+    ADYOLO_REQUIRE(out + words <= audio || audio + words <= out, ADYOLO_EINVAL, "mic_swap: out overlaps audio (out-of-place only)");
+    long g = (n_samples + 255) / 256;
+    if (g > 2048) g = 2048;
+    hipLaunchKernelGGL(adyolo::mic_swap_kernel, dim3((unsigned)g, (unsigned)B), dim3(256), 0, adyolo::as_stream(stream),
+                       (const int4 *)audio, (int4 *)out, src_dev, n_samples);
+    return adyolo::check_launch("mic_swap");
+}

@@ -6,6 +6,7 @@
 //
 //   corpus_gather_kernel     one pass int16 window -> float32 ``x / 32768 + 1e-8``, FOA channels rotated; 16-byte loads of
 //                            two int16 frames, two 16-byte stores (8-byte loads when the window starts on an odd frame)
+//   corpus_gather_mic_kernel the same pass for MIC-format audio: the four capsules permuted (channel swap) instead of rotated
 //   corpus_count_scan_kernel one workgroup: rows per (item, event) lane, exclusive scan, the total and the overflow bit
 //   corpus_rows_kernel       the rows [b, t, gi, gj, cls, U, V] at their scanned offsets, b = -1 in the rest of the capacity
 //   corpus_classwise_kernel  the dense SEDDOA / ACCDOA / ADPIT targets (datasets.ClasswiseLabelEncoder): per tile of label
@@ -69,6 +70,69 @@ __global__ __launch_bounds__(256) void corpus_gather_kernel(const int16_t *__res
         for (long i = tid; i < n; i += nth) {
             const int2 v = s2[i];
             dst[i] = pcm_rot(v.x, v.y, sy, sz, sx, swap);
+        }
+    }
+}
+
+// ---- the MIC form: a permutation of the four capsules instead of signs (augmentations.mic_swap_source).  The permutation is
+// uniform over the workgroup (blockIdx.y = item), so the two byte selectors of v_perm_b32 are built once, in scalar registers;
+// the int16 halves of a frame are moved to their output places before the conversion: two v_perm_b32 per frame, then the
+// arithmetic of pcm16_to_f32_kernel, element for element.  Same access shapes as corpus_gather_kernel.
+struct CorpusMicSrc {                  // one word per combination (adyolo_hip.h), passed by value (capturable)
+    unsigned w[16];
+};
+
+// frame bytes 0..7 = {lo, hi}; selector byte k of v_perm_b32(hi, lo, sel) names the frame byte that lands in byte k
+__device__ __forceinline__ float4 pcm_swap(int lo, int hi, unsigned sel_lo, unsigned sel_hi) {
+    const int a = (int)__builtin_amdgcn_perm((unsigned)hi, (unsigned)lo, sel_lo);
+    const int c = (int)__builtin_amdgcn_perm((unsigned)hi, (unsigned)lo, sel_hi);
+    return make_float4((float)(short)(a & 0xffff) / 32768.0f + 1e-8f, (float)(short)(a >> 16) / 32768.0f + 1e-8f,
+                       (float)(short)(c & 0xffff) / 32768.0f + 1e-8f, (float)(short)(c >> 16) / 32768.0f + 1e-8f);
+}
+
+// grid (blocks per item, B).  An item whose offset is outside the corpus, or whose combination is >= 16 or no symmetry of the
+// array, gets zeros and sets status bit 2; comb < 0: the frame as it is.
+__global__ __launch_bounds__(256) void corpus_gather_mic_kernel(const int16_t *__restrict__ pcm, long n_total,
+                                                                const int64_t *__restrict__ items, long n, CorpusMicSrc tab,
+                                                                float4 *__restrict__ out, int *__restrict__ status) {
+    const int b = blockIdx.y;
+    const int64_t off = items[(size_t)b * ADYOLO_CORPUS_ITEM_WORDS + 0];
+    const int64_t comb = items[(size_t)b * ADYOLO_CORPUS_ITEM_WORDS + 4];
+    float4 *dst = out + (size_t)b * n;
+    const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, nth = (long)gridDim.x * blockDim.x;
+    unsigned w = 0x03020100u;                               // identity: channel j from channel j
+    bool bad = off < 0 || off > n_total - n || comb >= 16;
+    if (!bad && comb >= 0) {
+        w = tab.w[comb];
+        bad = w == ADYOLO_MIC_SWAP_NONE;
+    }
+    if (bad) {
+        if (tid == 0 && status) atomicOr(status, ADYOLO_CORPUS_BAD_ITEM);
+        for (long i = tid; i < n; i += nth) dst[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        return;
+    }
+    // channel s = frame bytes {2 s, 2 s + 1}: the byte pair s * 0x0202 + 0x0100; & 3 keeps every selector inside the frame
+    const unsigned s0 = w & 3u, s1 = (w >> 8) & 3u, s2 = (w >> 16) & 3u, s3 = (w >> 24) & 3u;
+    const unsigned sel_lo = (s0 * 0x0202u + 0x0100u) | ((s1 * 0x0202u + 0x0100u) << 16);
+    const unsigned sel_hi = (s2 * 0x0202u + 0x0100u) | ((s3 * 0x0202u + 0x0100u) << 16);
+    const int16_t *src = pcm + (size_t)off * 4;
+    if ((off & 1) == 0) {                                   // two frames per 16-byte load
+        const long n2 = n >> 1;
+        const int4 *s4 = reinterpret_cast<const int4 *>(src);
+        for (long i = tid; i < n2; i += nth) {
+            const int4 v = s4[i];
+            dst[2 * i] = pcm_swap(v.x, v.y, sel_lo, sel_hi);
+            dst[2 * i + 1] = pcm_swap(v.z, v.w, sel_lo, sel_hi);
+        }
+        if ((n & 1) && tid == 0) {
+            const int2 v = reinterpret_cast<const int2 *>(src)[n - 1];
+            dst[n - 1] = pcm_swap(v.x, v.y, sel_lo, sel_hi);
+        }
+    } else {
+        const int2 *s2v = reinterpret_cast<const int2 *>(src);
+        for (long i = tid; i < n; i += nth) {
+            const int2 v = s2v[i];
+            dst[i] = pcm_swap(v.x, v.y, sel_lo, sel_hi);
         }
     }
 }
@@ -343,6 +407,22 @@ extern "C" int adyolo_corpus_gather(const int16_t *pcm, long n_total, const int6
     hipLaunchKernelGGL(corpus_gather_kernel, dim3((unsigned)gx, (unsigned)B), dim3(256), 0, as_stream(stream), pcm, n_total,
                        items, n, rot, (float4 *)audio, status);
     return check_launch("corpus_gather");
+}
+
+extern "C" int adyolo_corpus_gather_mic(const int16_t *pcm, long n_total, const int64_t *items, int B, long n,
+                                        const unsigned int *src_host, float *audio, int *status, void *stream) {
+    ADYOLO_REQUIRE(pcm && items && audio && src_host, ADYOLO_EINVAL, "corpus_gather_mic: null pointer");
+    ADYOLO_REQUIRE(B > 0 && B < 65536 && n > 0 && n_total >= n, ADYOLO_EINVAL,
+                   "corpus_gather_mic: bad shape B=%d n=%ld n_total=%ld", B, n, n_total);
+    ADYOLO_REQUIRE(((uintptr_t)pcm & 15) == 0 && ((uintptr_t)audio & 15) == 0 && ((uintptr_t)items & 7) == 0, ADYOLO_EINVAL,
+                   "corpus_gather_mic: misaligned buffers (pcm / audio 16 bytes, items 8 bytes)");
+    CorpusMicSrc tab;
+    for (int c = 0; c < 16; ++c) tab.w[c] = src_host[c];
+    int gx = cdiv(n, 256L * 16);                            // the grid of adyolo_corpus_gather
+    gx = gx < 1 ? 1 : (gx > 4096 ? 4096 : gx);
+    hipLaunchKernelGGL(corpus_gather_mic_kernel, dim3((unsigned)gx, (unsigned)B), dim3(256), 0, as_stream(stream), pcm, n_total,
+                       items, n, tab, (float4 *)audio, status);
+    return check_launch("corpus_gather_mic");
 }
 
 extern "C" long adyolo_corpus_yolo_labels_workspace_words(int B, int max_events) {

@@ -248,7 +248,9 @@ class FoaDataset(torch.utils.data.Dataset):
     ``init_remaining_file_from_list`` for resume) and the same CSV label reader -- but ``__getitem__`` stops before the
     arithmetic: it returns ``(pcm int16 (T, 4), comb_no, label_rows)``, and with ``aug_config.spec_augment`` on a training split a
     4th element, the item's SpecAug table int32 (2, 4) (``SpecAug.draw_groups``: log-mel, then intensity vector; masked on the
-    GPU by ``FeatureExtractor(.., spec_ranges=)`` inside ``TrainStep.step``).  Normalisation, rotation of the audio and the
+    GPU by ``FeatureExtractor(.., spec_ranges=)`` inside ``TrainStep.step``).  With ``aug_config.channel_swap_augment`` (MIC-format
+    training splits only) ``comb_no`` is drawn from the eight symmetries of the array (``augmentations.MIC_SWAP_COMBS``) and the
+    audio is permuted by ``swap_audio`` instead of rotated.  Normalisation, rotation of the audio and the
     features run on the GPU (``AudioStager`` -> ``rotate_audio`` -> ``FeatureExtractor``); the label half of the rotation
     and the label encoding stay here on the host, as in the reference's DataLoader workers.  ``label_rows``: the AD-YOLO row
     list, or for ``seddoa | masked-seddoa | accdoa | adpit`` the dense ``ClasswiseLabelEncoder`` tensor (T', ...)."""
@@ -273,6 +275,8 @@ class FoaDataset(torch.utils.data.Dataset):
         self.is_valid, self.is_infer, self.set_type = is_valid, set_type == "infer", set_type
         self.loss_nm = params["args"]["loss"]
         dc = params["data_config"]
+        from .augmentations import channel_swap_enabled
+        self.swap = channel_swap_enabled(params) and not is_valid      # MIC channel swap (ValueError: not 'mic', or with rotation)
         # audio format: the reference reads ``foa_dev`` only (datasets.py:36-37,55); ``data_config.audio_format: mic`` selects the
         # DCASE ``mic_dev`` directory of the same layout (4-channel int16 WAVs; BASELINE config 5, features.MicFeatureExtractor)
         adir = {"foa": "foa_dev", "mic": "mic_dev"}[str(dc.get("audio_format", "foa")).lower()]
@@ -362,6 +366,10 @@ class FoaDataset(torch.utils.data.Dataset):
         comb_no = 0
         if self.rotate:
             comb_no = int(self._random.uniform(0, 16))                                    # augmentations.py:76
+            label = rotate_labels(label, comb_no)
+        elif self.swap:                         # one draw, like the rotation: the SpecAug draws below stay where they are
+            from .augmentations import MIC_SWAP_COMBS
+            comb_no = MIC_SWAP_COMBS[int(self._random.uniform(0, 8))]
             label = rotate_labels(label, comb_no)
         spec = None
         if self.specaug.apply_augment:          # datasets.py:158-159: MEL, then IV, each its own draw, right after the rotation

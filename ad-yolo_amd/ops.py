@@ -1760,23 +1760,73 @@ def _corpus_i64(name, t, device):
         raise _lib.AdyoloHipError("%s must be a contiguous int64 tensor on %s" % (name, device))
 
 
+def _corpus_gather_args(name, pcm, items, out, status):
+    """The argument checks both gathers share -> B."""
+    dev = pcm.device
+    if not pcm.is_cuda or pcm.dtype != torch.int16 or not pcm.is_contiguous() or pcm.dim() != 2 or pcm.shape[1] != 4:
+        raise _lib.AdyoloHipError("%s: pcm must be a contiguous int16 tensor (S, 4) on the device" % name)
+    _corpus_i64("%s: items" % name, items, dev)
+    _chk(out)
+    b = items.shape[0] if items.dim() == 2 else 0
+    if items.dim() != 2 or items.shape[1] != CORPUS_ITEM_WORDS or out.dim() != 3 or out.shape[0] != b or out.shape[2] != 4:
+        raise _lib.AdyoloHipError("%s: items %s / out %s are not (B, %d) / (B, n, 4)"
+                                  % (name, tuple(items.shape), tuple(out.shape), CORPUS_ITEM_WORDS))
+    if status.dtype != torch.int32 or status.device != dev:
+        raise _lib.AdyoloHipError("%s: status must be an int32 word on %s" % (name, dev))
+    return b
+
+
 def corpus_gather(pcm, items, rot, out, status):
     """pcm int16 (S, 4) and items int64 (B, 8) on the device -> out (B, n, 4) float32: the int16 windows at the items' sample
     offsets as ``x / 32768 + 1e-8``, FOA-rotated by their combinations (adyolo_hip.h ``adyolo_corpus_gather``).  rot:
     ``corpus_rot_table``; status: int32 word on the device the call ORs its bits into.  No allocation, no sync."""
-    dev = pcm.device
-    if not pcm.is_cuda or pcm.dtype != torch.int16 or not pcm.is_contiguous() or pcm.dim() != 2 or pcm.shape[1] != 4:
-        raise _lib.AdyoloHipError("corpus_gather: pcm must be a contiguous int16 tensor (S, 4) on the device")
-    _corpus_i64("corpus_gather: items", items, dev)
-    _chk(out)
-    b = items.shape[0] if items.dim() == 2 else 0
-    if items.dim() != 2 or items.shape[1] != CORPUS_ITEM_WORDS or out.dim() != 3 or out.shape[0] != b or out.shape[2] != 4:
-        raise _lib.AdyoloHipError("corpus_gather: items %s / out %s are not (B, %d) / (B, n, 4)"
-                                  % (tuple(items.shape), tuple(out.shape), CORPUS_ITEM_WORDS))
-    if status.dtype != torch.int32 or status.device != dev:
-        raise _lib.AdyoloHipError("corpus_gather: status must be an int32 word on %s" % dev)
+    b = _corpus_gather_args("corpus_gather", pcm, items, out, status)
     _c("adyolo_corpus_gather", _p(pcm), pcm.shape[0], _p(items), b, out.shape[1], ctypes.cast(rot, ctypes.c_void_p), _p(out),
        _p(status), _stream())
+    return out
+
+
+MIC_SWAP_NONE = 0xFFFFFFFF                                # ADYOLO_MIC_SWAP_NONE: a combination that is no symmetry of the array
+
+
+def corpus_mic_table(sources):
+    """{combination: (s0, s1, s2, s3)} (``augmentations.mic_swap_source`` of every symmetry) -> the host table uint32 [16] of
+    ``adyolo_corpus_gather_mic``: s_j in bits [8 j, 8 j + 2), ``MIC_SWAP_NONE`` for every other combination."""
+    words = [MIC_SWAP_NONE] * 16
+    for comb, src in sources.items():
+        src = tuple(int(v) for v in src)
+        if not 0 <= int(comb) < 16 or sorted(src) != [0, 1, 2, 3]:
+            raise ValueError("corpus_mic_table: combination %r -> %r is not a permutation of the four channels" % (comb, src))
+        words[int(comb)] = src[0] | src[1] << 8 | src[2] << 16 | src[3] << 24
+    return (ctypes.c_uint32 * 16)(*words)
+
+
+def corpus_gather_mic(pcm, items, src, out, status):
+    """``corpus_gather`` for MIC-format audio: the windows' four capsules permuted by the items' combinations instead of rotated
+    (adyolo_hip.h ``adyolo_corpus_gather_mic``; bit for bit ``pcm16_to_f32`` then ``mic_swap``).  src: ``corpus_mic_table``; an
+    item whose combination is no symmetry gets zeros and sets status bit 2.  No allocation, no sync."""
+    b = _corpus_gather_args("corpus_gather_mic", pcm, items, out, status)
+    _c("adyolo_corpus_gather_mic", _p(pcm), pcm.shape[0], _p(items), b, out.shape[1], ctypes.cast(src, ctypes.c_void_p), _p(out),
+       _p(status), _stream())
+    return out
+
+
+def mic_swap(audio, src, out=None):
+    """audio (B, n, 4) float32 and src int32 (B, 4) on the device -> out[b, i, j] = audio[b, i, src[b, j] & 3] (a new tensor
+    unless ``out``, which must not overlap audio, is given).  The values are moved bit for bit (adyolo_hip.h ``adyolo_mic_swap``)."""
+    _chk(audio)
+    if audio.dim() != 3 or audio.shape[2] != 4:
+        raise _lib.AdyoloHipError("mic_swap: audio %s is not (B, n, 4)" % (tuple(audio.shape),))
+    b, n, _ = audio.shape
+    if src.dtype != torch.int32 or src.device != audio.device or not src.is_contiguous() or tuple(src.shape) != (b, 4):
+        raise _lib.AdyoloHipError("mic_swap: src must be a contiguous int32 tensor (%d, 4) on %s" % (b, audio.device))
+    if out is None:
+        out = torch.empty_like(audio)
+    else:
+        _chk(out)
+        if tuple(out.shape) != tuple(audio.shape) or out.device != audio.device:
+            raise _lib.AdyoloHipError("mic_swap: out %s does not match audio %s" % (tuple(out.shape), tuple(audio.shape)))
+    _c("adyolo_mic_swap", _p(audio), _p(out), _p(src), b, n, _stream())
     return out
 
 

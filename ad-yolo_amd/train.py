@@ -723,14 +723,15 @@ class _EpochLoss:
 
 def train_one_epoch_audio(params: dict, dataloader, trainer, stager=None, rotate=True):
     """The raw-audio epoch: ``dataloader`` yields ``audio_collate_fn`` batches (pcm int16 (B,T,4), comb_nos, target[, SpecAug
-    tables (B,2,4)]); each is staged to the GPU (int16 over PCIe on a side stream, double-buffered), converted, rotated and
-    handed with its tables to ``TrainStep.step`` (features [+ SpecAug masks] + forward + loss + backward [+ all-reduce] +
-    Adam).  Returns the mean loss with ONE device sync at the end of the epoch (the reference syncs every iteration,
-    train.py:57); with ``train_config['skip_nonfinite']`` the mean over the APPLIED steps (``_EpochLoss``).  With
-    ``train_config['accum_steps']`` every batch is a micro-step; an epoch whose number of batches is no multiple of it (or that
+    tables (B,2,4)]); each is staged to the GPU (int16 over PCIe on a side stream, double-buffered), converted, rotated (with
+    ``aug_config.channel_swap_augment``: its channels permuted, ``swap_audio``) and handed with its tables to ``TrainStep.step``
+    (features [+ SpecAug masks] + forward + loss + backward [+ all-reduce] + Adam).  Returns the mean loss with ONE device sync
+    at the end of the epoch (the reference syncs every iteration, train.py:57); with ``train_config['skip_nonfinite']`` the
+    mean over the APPLIED steps (``_EpochLoss``).  With ``train_config['accum_steps']`` every batch is a micro-step; an epoch whose number of batches is no multiple of it (or that
     ``quick_test`` cuts short) ends inside a cycle, and that partial cycle is DROPPED: its gradients take part in no step."""
-    from .augmentations import rotate_audio
+    from .augmentations import channel_swap_enabled, rotate_audio, swap_audio
     from .datasets import AudioStager
+    move_audio = swap_audio if channel_swap_enabled(params) else rotate_audio     # MIC channel swap | FOA rotation
     acc, n = _EpochLoss(params, trainer), 0
     it = iter(dataloader)
     try:
@@ -748,7 +749,7 @@ def train_one_epoch_audio(params: dict, dataloader, trainer, stager=None, rotate
             pcm, combs, target, *spec = nxt
             stager.stage(pcm)
         if rotate and any(int(c) != 0 for c in cur_combs):
-            audio = rotate_audio(audio, cur_combs)
+            audio = move_audio(audio, cur_combs)
         acc.add(trainer.step(audio, cur_target, cur_spec))
         n += 1
         if nxt is None or (params.get("args", {}).get("quick_test") and n == 5):

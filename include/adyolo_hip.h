@@ -627,6 +627,13 @@ int adyolo_ln_bwd(const float *dy, const float *x, const float *gamma, float *dx
  * cfg [B][4] = {sign_y, sign_z, sign_x, swap_xy}.  Label angles are remapped on the host (augmentations.RotationAug). */
 int adyolo_foa_rotate(const float *audio, float *out, const float *cfg, int B, long n_samples, void *stream);
 
+/* MIC channel-swap augmentation on raw audio (augmentations.swap_audio; the MIC-format counterpart of adyolo_foa_rotate):
+ * audio/out [B][n_samples][4] (capsules M1..M4), 16-byte aligned, out-of-place only (out must not overlap audio);
+ * src_dev DEVICE int32 [B][4]: out[b][i][j] = audio[b][i][src_dev[b][j] & 3] -- the selectors are masked in the kernel, so no
+ * table value addresses outside the frame; the values are moved, not computed on (NaN payloads and -0.0 keep their bits).
+ * Label angles are remapped on the host by the same combination (augmentations.rotate_labels). */
+int adyolo_mic_swap(const float *audio, float *out, const int *src_dev, int B, long n_samples, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Training batches from an HBM-resident corpus (csrc/corpus.hip, ad-yolo_amd/corpus.py DeviceCorpus / ClasswiseDeviceCorpus),
  * opt-in: the host half of FoaDataset.__getitem__ + audio_collate_fn (src/datasets.py:93-184) on the device, from one small
@@ -640,6 +647,13 @@ int adyolo_foa_rotate(const float *audio, float *out, const float *cfg, int B, l
  * adyolo_corpus_gather: audio [B][n][4] float32 = the int16 frames pcm[off .. off + n) (W,Y,Z,X) as x / 32768 + 1e-8, rotated
  *   like adyolo_foa_rotate -- bit for bit adyolo_pcm16_to_f32 followed by adyolo_foa_rotate.  pcm [n_total][4] int16, 16-byte
  *   aligned; an item outside it gets zeros and sets ADYOLO_CORPUS_BAD_ITEM.
+ * adyolo_corpus_gather_mic: the MIC form of adyolo_corpus_gather over the same items: audio [B][n][4] float32 = the int16 frames
+ *   pcm[off .. off + n) (capsules M1..M4) with the channels permuted by the item's combination, then x / 32768 + 1e-8 -- bit for
+ *   bit adyolo_pcm16_to_f32 followed by adyolo_mic_swap.  src_host HOST uint32 [16], one word per combination: source channel
+ *   s_j of output channel j in bits [8 j, 8 j + 2) (augmentations.mic_swap_source; passed by value: capturable), or
+ *   ADYOLO_MIC_SWAP_NONE where the combination is no symmetry of the array.  comb < 0: no permutation (the bits of
+ *   adyolo_corpus_gather with comb < 0).  comb >= 16, a combination marked ADYOLO_MIC_SWAP_NONE or an item outside pcm: zeros
+ *   for that item and ADYOLO_CORPUS_BAD_ITEM.  The label calls below are the same for both formats.
  * adyolo_corpus_yolo_labels: the AD-YOLO rows of the batch (datasets.get_yolo_label + collate_fn): per item, per event
  *   [b, frame - frame offset, gi, gj, cls, U, V] for every responsible cell in (gi, gj) order, the rotation of
  *   augmentations.rotate_labels and the cell test of YoloLabelEncoder.encode_events in double, events whose relative frame is
@@ -672,6 +686,9 @@ int adyolo_foa_rotate(const float *audio, float *out, const float *cfg, int B, l
 #define ADYOLO_CORPUS_ADPIT      2
 int  adyolo_corpus_gather(const int16_t *pcm, long n_total, const int64_t *items, int B, long n, const float *rot_host,
                           float *audio, int *status, void *stream);
+#define ADYOLO_MIC_SWAP_NONE     0xffffffffu  /* src_host word of a combination that is no symmetry of the array */
+int  adyolo_corpus_gather_mic(const int16_t *pcm, long n_total, const int64_t *items, int B, long n,
+                              const unsigned int *src_host, float *audio, int *status, void *stream);
 long adyolo_corpus_yolo_labels_workspace_words(int B, int max_events);
 int  adyolo_corpus_yolo_labels(const double *events, long n_events, const int64_t *items, int B, int max_events,
                                int n_label_frames, const double *grid_bounds, int Gaz, int Gel, const float *rot_host,

@@ -6,6 +6,8 @@ batch size (16 and 64 x 20 s, hipGraph-replayed steps):
 
   load          load_chunked_split (verify="sample") + DeviceCorpus upload: seconds and bytes held on the device
   batch         gather + label kernels of one batch (DeviceCorpus.launch), device time per batch (events around --iters batches)
+  gather        the gather alone on uploaded item tables, device time per launch in us (--iters launches replayed from one
+                hipGraph): ``adyolo_corpus_gather`` always, and with --swap ``adyolo_corpus_gather_mic`` on the same tables
   labels        (class-wise losses) the label kernel alone on an uploaded item table, device time per batch
   replay        the recorded train step alone on fixed inputs (the rate a loader has to keep up with)
   corpus        train_one_epoch_corpus
@@ -19,10 +21,13 @@ step, capture; page cache).
 --loss seddoa | accdoa | adpit trains that class-wise model from a ClasswiseDeviceCorpus instead; --mic writes the split as
 ``mic_dev`` and trains on the MIC feature set (MicFeatureExtractor: BASELINE config 5 with --loss adpit); --classes sets the event
 classes of the split and the model (12 by default: the ACCDOA / ADPIT heads' GEMMs need 3C and 9C in multiples of 4);
---labels-only stops after load, batch and labels (no model: any class count, e.g. the 13 of DCASE 2023).
+--swap (with --mic only) turns ``aug_config.channel_swap_augment`` on instead of ``rotation_augment``: the MIC channel swap;
+--labels-only stops after load, batch, gather and labels (no model: any class count, e.g. the 13 of DCASE 2023); --corpus-only
+skips the host-loader epochs.
 
   python tools/corpus_bench.py [--dir /tmp/adyolo_corpus] [--batches 16,64] [--steps 32,8] [--workers 16] [--json out.json]
-                               [--loss adyolo|seddoa|accdoa|adpit] [--mic] [--classes C] [--labels-only]
+                               [--loss adyolo|seddoa|accdoa|adpit] [--mic] [--swap] [--classes C] [--labels-only]
+                               [--corpus-only]
 """
 import argparse
 import csv
@@ -74,7 +79,7 @@ def write_split(root, n_recordings, seed=0, n_classes=12, audio_dir="foa_dev"):
     return nbytes
 
 
-def params(root, batch, steps, loss="adyolo", mic=False, n_classes=12):
+def params(root, batch, steps, loss="adyolo", mic=False, n_classes=12, swap=False):
     from __graft_entry__ import _params
     prm = _params(nb_classes=n_classes)
     prm["args"]["loss"] = loss
@@ -85,6 +90,8 @@ def params(root, batch, steps, loss="adyolo", mic=False, n_classes=12):
     prm["train_config"].update({"batch_size": batch, "nb_iters": steps})
     prm["aug_config"] = {"rotation_augment": True, "spec_augment": True, "spec_augment_thresh": 0.5,
                          "spec_augment_time_mask_param": 40, "spec_augment_freq_mask_param": 40}
+    if swap:
+        prm["aug_config"].update({"rotation_augment": False, "channel_swap_augment": True})
     return prm
 
 
@@ -128,15 +135,41 @@ def timed_epoch(run, tr):
             "cpu_s_per_step": round((c1 - c0) / max(n, 1), 4)}
 
 
-def bench_batch(root, batch, steps, workers, iters, loss="adyolo", mic=False, n_classes=12, labels_only=False):
+def graph_us(launch, iters):
+    """launch(i) recorded ``iters`` times in one hipGraph and replayed -> device time per launch in us (the device time rather
+    than the rate Python issues launches at)."""
+    for i in range(4):
+        launch(i)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        for i in range(iters):
+            launch(i)
+    graph.replay()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    best = float("inf")
+    for _ in range(5):
+        e0.record()
+        graph.replay()
+        e1.record()
+        torch.cuda.synchronize()
+        best = min(best, e0.elapsed_time(e1))
+    return round(1e3 * best / iters, 2)
+
+
+def bench_batch(root, batch, steps, workers, iters, loss="adyolo", mic=False, n_classes=12, labels_only=False, swap=False,
+                corpus_only=False):
     from adyolo_amd import ops
     from adyolo_amd.corpus import ClasswiseDeviceCorpus, DeviceCorpus, load_chunked_split
     from adyolo_amd.datasets import FoaDataset, audio_collate_fn
     from adyolo_amd.train import train_one_epoch_audio, train_one_epoch_corpus
-    prm = params(root, batch, steps, loss, mic, n_classes)
+    prm = params(root, batch, steps, loss, mic, n_classes, swap)
     out = {"batch": batch, "steps_per_epoch": steps}
     if loss != "adyolo" or mic:
         out.update(loss=loss, mic=mic, classes=n_classes)
+    if swap:
+        out["swap"] = True
     t0 = time.perf_counter()
     hc = load_chunked_split(prm, verify="sample")
     t1 = time.perf_counter()
@@ -162,10 +195,18 @@ def bench_batch(root, batch, steps, workers, iters, loss="adyolo", mic=False, n_
     e1.record()
     torch.cuda.synchronize()
     out["batch_ms"] = round(e0.elapsed_time(e1) / iters, 4)
+    # the gather alone, on item tables already on the device (with --swap their combinations are the eight symmetries, which
+    # both kernels take: the same bytes read and written)
+    dev_items = [torch.from_numpy(d[0]).to("cuda:0") for d in drawn]
+    audio = torch.empty((batch, corpus.n_samples, 4), dtype=torch.float32, device="cuda:0")
+    out["gather_us"] = graph_us(lambda i: ops.corpus_gather(corpus.pcm, dev_items[i % 4], corpus.rot, audio, corpus.status), iters)
+    if swap:
+        out["gather_mic_us"] = graph_us(lambda i: ops.corpus_gather_mic(corpus.pcm, dev_items[i % 4], corpus.mic_src, audio,
+                                                                        corpus.status), iters)
+    del audio
     if loss != "adyolo":
         # the label kernel alone, on item tables already on the device: --iters launches recorded in one hipGraph and
         # replayed, so that the device time is measured rather than the rate Python issues launches at
-        dev_items = [torch.from_numpy(d[0]).to("cuda:0") for d in drawn]
         target = torch.empty(corpus.target_shape(batch), dtype=torch.float32, device="cuda:0")
 
         def labels(i):
@@ -211,6 +252,8 @@ def bench_batch(root, batch, steps, workers, iters, loss="adyolo", mic=False, n_
     out["replay_ms"] = round(e0.elapsed_time(e1) / iters, 3)
     del tc, corpus
     torch.cuda.empty_cache()
+    if corpus_only:
+        return out
 
     th = trainer(prm)
     random.seed(0)
@@ -241,7 +284,11 @@ def main():
     ap.add_argument("--mic", action="store_true", help="a mic_dev split and the MIC feature set")
     ap.add_argument("--classes", type=int, default=12, help="event classes of the split and the model")
     ap.add_argument("--labels-only", action="store_true", help="load, batch and labels timings only (no training epochs)")
+    ap.add_argument("--swap", action="store_true", help="MIC channel swap instead of the FOA rotation (needs --mic)")
+    ap.add_argument("--corpus-only", action="store_true", help="skip the host-loader epochs")
     a = ap.parse_args()
+    if a.swap and not a.mic:
+        ap.error("--swap permutes microphone capsules: it needs --mic")
     n_classes = a.classes
     assert torch.cuda.is_available(), "corpus_bench needs the GPU"
     import adyolo_amd  # noqa: F401
@@ -258,7 +305,7 @@ def main():
     print(json.dumps(res), flush=True)
     try:
         for b, s in zip(batches, steps):
-            r = bench_batch(a.dir, b, s, a.workers, a.iters, a.loss, a.mic, n_classes, a.labels_only)
+            r = bench_batch(a.dir, b, s, a.workers, a.iters, a.loss, a.mic, n_classes, a.labels_only, a.swap, a.corpus_only)
             res["b%d" % b] = r
             print(json.dumps(r), flush=True)
     finally:

@@ -104,6 +104,57 @@ def channel_swap_enabled(params):
     return True
 
 
+# ---- Time-domain mixing: the audio of two training chunks summed, their labels united (``aug_config.time_mix_augment``).
+def time_mix_config(params):
+    """``aug_config.time_mix_augment`` and its keys -> None (off) or (prob, gain_lo_db, gain_hi_db).  ``time_mix_prob`` (default
+    0.5) must be in [0, 1]; ``time_mix_gain_db`` (default [0.0, 0.0]) must be two finite numbers lo <= hi (``ValueError`` naming
+    the key otherwise)."""
+    import math
+    aug = params.get("aug_config", {})
+    if not bool(aug.get("time_mix_augment", False)):
+        return None
+    prob = aug.get("time_mix_prob", 0.5)
+    if isinstance(prob, bool) or not isinstance(prob, (int, float)) or not 0.0 <= prob <= 1.0:
+        raise ValueError("aug_config.time_mix_prob must be a number in [0, 1] (got %r)" % (prob,))
+    gain = aug.get("time_mix_gain_db", [0.0, 0.0])
+    if not isinstance(gain, (list, tuple)) or len(gain) != 2 \
+            or any(isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) for v in gain) \
+            or gain[0] > gain[1]:
+        raise ValueError("aug_config.time_mix_gain_db must be [lo, hi] with lo <= hi, both finite (got %r)" % (gain,))
+    return float(prob), float(gain[0]), float(gain[1])
+
+
+def time_mix_enabled(params):
+    """``aug_config.time_mix_augment``, with the refusals of ``time_mix_config``."""
+    return time_mix_config(params) is not None
+
+
+def draw_time_mix(rnd, config, total_filelist, name, comb_draw=None):
+    """The draws of one training item, after its own (rotation or swap combination, SpecAug table), from ``rnd`` (the dataset's
+    ``random`` module): mixed at all?  If so the mate chunk, the mate's combination (``comb_draw`` "rotate": one of 16, "swap": one
+    of ``MIC_SWAP_COMBS``, None: no draw) and the gain.  -> None (unmixed) or (mate name, combination or None, np.float32 gain).
+    A mate that is the item itself leaves the item unmixed, after all the draws."""
+    import numpy as np
+    prob, lo, hi = config
+    if not rnd.random() < prob:
+        return None
+    mate = total_filelist[int(rnd.uniform(0, len(total_filelist)))]
+    comb = None
+    if comb_draw == "rotate":
+        comb = int(rnd.uniform(0, 16))
+    elif comb_draw == "swap":
+        comb = MIC_SWAP_COMBS[int(rnd.uniform(0, 8))]
+    gain = np.float32(10.0 ** (rnd.uniform(lo, hi) / 20.0))
+    return None if mate == name else (mate, comb, gain)
+
+
+def merge_labels(a: dict, b: dict):
+    """Two label dicts {frame: [[cls, src, az, el], ...]} (each already moved by its own ``rotate_labels``) -> the labels of their
+    mixture: the frames of both in ascending order, each frame's list ``a``'s events followed by ``b``'s.  New dict and lists."""
+    return {frame: [list(ev) for ev in a.get(frame, [])] + [list(ev) for ev in b.get(frame, [])]
+            for frame in sorted(set(a) | set(b))}
+
+
 def swap_audio(audio, comb_nos):
     """audio (B, n_samples, 4) float32 on the GPU, comb_nos: B combinations of ``MIC_SWAP_COMBS`` -> the audio with its channels
     permuted (new tensor; csrc/aug.hip ``mic_swap_kernel``).  ``ValueError`` for any other combination, before any launch."""

@@ -13,7 +13,9 @@ rotates and encodes the labels on the host and stages every batch over PCIe.  He
   per hour of 4-channel 24 kHz audio), ``FoaDataset``'s sampling surface (the same functions), and ``batch(indices)``: the same
   ``random`` draws as ``FoaDataset.__getitem__`` item by item, one small H2D copy of the item table, then ``adyolo_corpus_gather``
   (audio, rotated; with ``aug_config.channel_swap_augment`` ``adyolo_corpus_gather_mic``: MIC capsules permuted) and
-  ``adyolo_corpus_yolo_labels`` (the AD-YOLO rows into a fixed-capacity target, padding b = -1).  No host sync.
+  ``adyolo_corpus_yolo_labels`` (the AD-YOLO rows into a fixed-capacity target, padding b = -1).  No host sync.  With
+  ``aug_config.time_mix_augment`` the draws of ``augmentations.draw_time_mix`` follow each item's, a second table of mates rides
+  in the same copy and the ``_mix`` calls sum the mate's window in and unite the labels (``augmentations.merge_labels``).
 * ``ClasswiseDeviceCorpus`` (device half, ``seddoa | masked-seddoa | accdoa | adpit``): the same split, sampling, draws and
   gather; the labels are ``adyolo_corpus_classwise_labels``, the dense ``ClasswiseLabelEncoder`` targets of the batch written
   whole, from a float32 table of every event's direction vector under no rotation and the 16 FOA combinations (``xyz_table``,
@@ -282,7 +284,7 @@ class _CorpusBase:
     __len__ = FoaDataset.__len__
 
     def _setup(self, host_corpus, params, device, rank, world):
-        from .augmentations import MIC_SWAP_COMBS, SpecAug, channel_swap_enabled, mic_swap_source
+        from .augmentations import MIC_SWAP_COMBS, SpecAug, channel_swap_enabled, mic_swap_source, time_mix_config
         self.host = hc = host_corpus
         self.device = torch.device(device)
         self._copy, self._os, self._random = copy, os, random
@@ -295,6 +297,7 @@ class _CorpusBase:
         self.swap = channel_swap_enabled(params)
         self.mic_src = ops.corpus_mic_table({k: mic_swap_source(k) for k in MIC_SWAP_COMBS}) if self.swap else None
         self.specaug = SpecAug(params, False)
+        self.mix = time_mix_config(params)    # time-domain mixing: None or (prob, gain lo, gain hi) (ValueError: a bad key)
         self.batch_size = int(params["train_config"]["batch_size"])
         self.n_samples, self.n_label_frames = hc.window, hc.window // hc.hop_label
         self.max_events = hc.max_events
@@ -325,13 +328,20 @@ class _CorpusBase:
     # ---------------------------------------------------------------------------------------------------------- batches
     def draw(self, indices):
         """The host half of a batch: ``FoaDataset.__getitem__``'s ``random`` draws item by item (rotation or channel swap, then
-        SpecAug) and the item table -> (items int64 (B, 8), spec int32 (B, 2, 4) or None), host arrays."""
-        from .augmentations import MIC_SWAP_COMBS
+        SpecAug) and the item table -> (items int64 (B, 8), spec int32 (B, 2, 4) or None), host arrays.  With
+        ``aug_config.time_mix_augment`` the item's mixing draws follow (``augmentations.draw_time_mix``) and a third element is
+        returned: mates int64 (B, 8), the mate chunk as an item row with its own combination and the float32 bits of the gain in
+        word 6, offset -1 where the item is unmixed."""
+        from .augmentations import MIC_SWAP_COMBS, draw_time_mix
         from .features import HOP, N_MELS
         names = [self.filelist[i] for i in indices]
         b = len(names)
         items = np.zeros((b, ops.CORPUS_ITEM_WORDS), dtype=np.int64)
         spec = np.zeros((b, 2, 4), dtype=np.int32) if self.specaug.apply_augment else None
+        mates = None
+        if self.mix is not None:
+            mates = np.zeros((b, ops.CORPUS_ITEM_WORDS), dtype=np.int64)
+            mates[:, 0] = mates[:, 4] = -1
         for j, name in enumerate(names):
             rec, off, f_off = self.host.chunks[name]
             ev_lo, ev_n = self.host.chunk_events[name]
@@ -343,15 +353,29 @@ class _CorpusBase:
             if spec is not None:
                 spec[j] = self.specaug.draw_groups(1, self.n_samples // HOP, N_MELS, 2)[0].numpy()
             items[j] = (off, f_off, ev_lo, ev_n, comb, rec, 0, 0)
+            if mates is not None:
+                drawn = draw_time_mix(self._random, self.mix, self.total_filelist, name,
+                                      "rotate" if self.rotate else "swap" if self.swap else None)
+                if drawn is not None:
+                    mate, m_comb, gain = drawn
+                    m_rec, m_off, m_f_off = self.host.chunks[mate]
+                    m_lo, m_n = self.host.chunk_events[mate]
+                    mates[j] = (m_off, m_f_off, m_lo, m_n, -1 if m_comb is None else m_comb, m_rec,
+                                int(np.float32(gain).view(np.uint32)), 0)
+        if mates is not None:
+            return items, spec, mates
         return items, spec
 
     def _upload(self, drawn):
         """One H2D copy of the item table (+ SpecAug tables) through a double-buffered page-locked buffer
-        -> (items int64 (B, 8), spec int32 (B, 2, 4) or None) on the device."""
-        items, spec = drawn
+        -> (items int64 (B, 8), spec int32 (B, 2, 4) or None) on the device; with mates in ``drawn`` they travel in the same
+        copy, behind the items, and come back as a third element."""
+        items, spec = drawn[0], drawn[1]
+        mates = drawn[2] if len(drawn) > 2 else None
         b = items.shape[0]
         n_i = b * ops.CORPUS_ITEM_WORDS
-        n_words = n_i + (b * 4 if spec is not None else 0)              # 8 int32 of SpecAug per item = 4 int64 words
+        n_m = n_i if mates is not None else 0
+        n_words = n_i + n_m + (b * 4 if spec is not None else 0)        # 8 int32 of SpecAug per item = 4 int64 words
         slot = self._slot
         self._slot ^= 1
         key = (slot, n_words)
@@ -362,15 +386,19 @@ class _CorpusBase:
             self._copied[slot].synchronize()          # the copy out of this page-locked buffer two batches ago has landed
         hv = host.numpy()
         hv[:n_i] = items.reshape(-1)
+        if mates is not None:
+            hv[n_i:n_i + n_m] = mates.reshape(-1)
         if spec is not None:
-            hv[n_i:].view(np.int32)[:] = spec.reshape(-1)
+            hv[n_i + n_m:].view(np.int32)[:] = spec.reshape(-1)
         dev = torch.empty(n_words, dtype=torch.int64, device=self.device)
         dev.copy_(host, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(self.device))
         self._copied[slot] = ev
         dev_items = dev[:n_i].view(b, ops.CORPUS_ITEM_WORDS)
-        dev_spec = dev[n_i:].view(torch.int32).view(b, 2, 4) if spec is not None else None
+        dev_spec = dev[n_i + n_m:].view(torch.int32).view(b, 2, 4) if spec is not None else None
+        if mates is not None:
+            return dev_items, dev_spec, dev[n_i:n_i + n_m].view(b, ops.CORPUS_ITEM_WORDS)
         return dev_items, dev_spec
 
     def batch(self, indices, audio_out=None, target_out=None):
@@ -378,8 +406,11 @@ class _CorpusBase:
         with no host synchronisation.  audio_out / target_out: write into these buffers (a recorded step's)."""
         return self.launch(self.draw(indices), audio_out, target_out)
 
-    def _gather(self, dev_items, audio):
-        """The audio of a batch: FOA-rotated, or with ``aug_config.channel_swap_augment`` the MIC capsules permuted."""
+    def _gather(self, dev_items, audio, dev_mates=None):
+        """The audio of a batch: FOA-rotated, or with ``aug_config.channel_swap_augment`` the MIC capsules permuted; with mates
+        (``aug_config.time_mix_augment``) each mate's window, under its own combination, summed in by the same pass."""
+        if dev_mates is not None:
+            return ops.corpus_gather_mix(self.pcm, dev_items, dev_mates, self.rot, self.mic_src, audio, self.status)
         if self.swap:
             return ops.corpus_gather_mic(self.pcm, dev_items, self.mic_src, audio, self.status)
         return ops.corpus_gather(self.pcm, dev_items, self.rot, audio, self.status)
@@ -401,10 +432,11 @@ class DeviceCorpus(_CorpusBase):
         corpus = DeviceCorpus(load_chunked_split(params), params, "cuda:0")
         audio, target, spec = corpus.batch(range(16))    # (16, n, 4) f32, (cap, 7) f32, (16, 2, 4) int32 or None: all on the device
 
-    ``cap`` (the target rows) is fixed here: batch_size x (largest event count of a window) x (largest cell count of an event),
-    rounded up to ``graph.TARGET_QUANTUM`` -- one input shape, one recorded graph.  More rows than that in a batch (a smaller
-    ``cap`` forced by the caller) set the status word; ``check()`` raises then.  AD-YOLO labels only: the class-wise losses
-    train from ``ClasswiseDeviceCorpus``."""
+    ``cap`` (the target rows) is fixed here: batch_size x (largest event count of a window; twice that with
+    ``aug_config.time_mix_augment``, where an item holds two windows' events) x (largest cell count of an event), rounded up to
+    ``graph.TARGET_QUANTUM`` -- one input shape, one recorded graph.  More rows than that in a batch (a smaller ``cap`` forced by
+    the caller) set the status word; ``check()`` raises then.  AD-YOLO labels only: the class-wise losses train from
+    ``ClasswiseDeviceCorpus``."""
 
     def __init__(self, host_corpus, params, device="cuda:0", rank=None, world=None, cap=None):
         from . import graph
@@ -416,7 +448,8 @@ class DeviceCorpus(_CorpusBase):
         self.encoder = YoloLabelEncoder(params)
         self.cells = max_cells_per_event(self.encoder)
         if cap is None:
-            need = max(1, self.batch_size * self.max_events * self.cells)
+            # a mixed item holds the events of two windows
+            need = max(1, self.batch_size * (2 if self.mix is not None else 1) * self.max_events * self.cells)
             cap = (need + graph.TARGET_QUANTUM - 1) // graph.TARGET_QUANTUM * graph.TARGET_QUANTUM
         self.cap = int(cap)
         enc = self.encoder
@@ -432,7 +465,7 @@ class DeviceCorpus(_CorpusBase):
     def launch(self, drawn, audio_out=None, target_out=None):
         """The device half: one H2D copy of the item table (+ SpecAug tables), the gather and the label kernels.
         -> (audio (B, n, 4) f32, target (cap, 7) f32, spec (B, 2, 4) int32 or None) on the device; no host sync."""
-        dev_items, dev_spec = self._upload(drawn)
+        dev_items, dev_spec, *dev_mates = self._upload(drawn)
         b = dev_items.shape[0]
         audio = audio_out if audio_out is not None else \
             torch.empty((b, self.n_samples, 4), dtype=torch.float32, device=self.device)
@@ -440,8 +473,15 @@ class DeviceCorpus(_CorpusBase):
         if tuple(audio.shape) != (b, self.n_samples, 4) or tuple(target.shape) != (self.cap, 7):
             raise ValueError("DeviceCorpus.launch: output buffers %s / %s, expected (%d, %d, 4) / (%d, 7)"
                              % (tuple(audio.shape), tuple(target.shape), b, self.n_samples, self.cap))
-        ws = torch.empty(max(1, ops.corpus_labels_workspace_words(b, self.max_events)), dtype=torch.int32, device=self.device)
         self.rows = torch.empty(1, dtype=torch.int32, device=self.device)
+        if dev_mates:                            # time-domain mixing: both sources' audio summed, their rows in merged order
+            ws = torch.empty(max(1, ops.corpus_labels_mix_workspace_words(b, self.max_events)), dtype=torch.int32,
+                             device=self.device)
+            self._gather(dev_items, audio, dev_mates[0])
+            ops.corpus_yolo_labels_mix(self.events, dev_items, dev_mates[0], self.max_events, self.n_label_frames, self.bounds,
+                                       self.grid, self.rot, ws, target, self.rows, self.status)
+            return audio, target, dev_spec
+        ws = torch.empty(max(1, ops.corpus_labels_workspace_words(b, self.max_events)), dtype=torch.int32, device=self.device)
         self._gather(dev_items, audio)
         ops.corpus_yolo_labels(self.events, dev_items, self.max_events, self.n_label_frames, self.bounds, self.grid, self.rot, ws,
                                target, self.rows, self.status)
@@ -489,7 +529,7 @@ class ClasswiseDeviceCorpus(_CorpusBase):
     def launch(self, drawn, audio_out=None, target_out=None):
         """The device half: one H2D copy of the item table (+ SpecAug tables), the gather and the label kernel.
         -> (audio (B, n, 4) f32, target ``target_shape(B)`` f32, spec (B, 2, 4) int32 or None) on the device; no host sync."""
-        dev_items, dev_spec = self._upload(drawn)
+        dev_items, dev_spec, *dev_mates = self._upload(drawn)
         b = dev_items.shape[0]
         shape = self.target_shape(b)
         audio = audio_out if audio_out is not None else \
@@ -498,6 +538,11 @@ class ClasswiseDeviceCorpus(_CorpusBase):
         if tuple(audio.shape) != (b, self.n_samples, 4) or tuple(target.shape) != shape:
             raise ValueError("ClasswiseDeviceCorpus.launch: output buffers %s / %s, expected (%d, %d, 4) / %s"
                              % (tuple(audio.shape), tuple(target.shape), b, self.n_samples, shape))
+        if dev_mates:                            # time-domain mixing: both sources' audio summed, the targets of the merged events
+            self._gather(dev_items, audio, dev_mates[0])
+            ops.corpus_classwise_labels_mix(self.events, dev_items, dev_mates[0], self.xyz, self.max_events, self.n_label_frames,
+                                            self.nb_classes, self.loss_nm, target, self.status)
+            return audio, target, dev_spec
         self._gather(dev_items, audio)
         ops.corpus_classwise_labels(self.events, dev_items, self.xyz, self.max_events, self.n_label_frames, self.nb_classes,
                                     self.loss_nm, target, self.status)

@@ -230,3 +230,46 @@ extern "C" int adyolo_mic_swap(const float *audio, float *out, const int *src_de
                        (const int4 *)audio, (int4 *)out, src_dev, n_samples);
     return adyolo::check_launch("mic_swap");
 }
+
+// ---- Time-domain mixing on raw audio (aug_config.time_mix_augment, the host-fed path): per clip out = audio + gain * mate where
+// the clip is mixed, the clip as it is where it is not.  One float4 per frame from each side; the clip's flag and gain are
+// uniform over the workgroup (blockIdx.y = clip).  The product is rounded before the sum (mix_add), as in the corpus gather.  An
+// unmixed clip travels as integers (its bits are kept) or, in place, is not touched at all.
+namespace adyolo {
+__global__ __launch_bounds__(256) void audio_mix_kernel(const float4 *x, const float4 *__restrict__ mate,
+                                                        const float *__restrict__ gains,
+                                                        const unsigned char *__restrict__ mixed, float4 *y, long n_per_clip) {
+    const int b = blockIdx.y;
+    const float4 *src = x + (size_t)b * n_per_clip;
+    float4 *dst = y + (size_t)b * n_per_clip;
+    const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, nth = (long)gridDim.x * blockDim.x;
+    if (!mixed[b]) {
+        if (src == dst) return;
+        const int4 *s = reinterpret_cast<const int4 *>(src);
+        int4 *d = reinterpret_cast<int4 *>(dst);
+        for (long i = tid; i < n_per_clip; i += nth) d[i] = s[i];
+        return;
+    }
+    const float g = gains[b];
+    const float4 *m = mate + (size_t)b * n_per_clip;
+    for (long i = tid; i < n_per_clip; i += nth) dst[i] = mix_add(src[i], m[i], g);      // out == audio: read, then written
+}
+}  // namespace adyolo
+
+extern "C" int adyolo_audio_mix(const float *audio, const float *mate, const float *gains, const unsigned char *mixed, float *out,
+                                int B, long n_samples, void *stream) {
+    ADYOLO_REQUIRE(audio && mate && gains && mixed && out && B > 0 && B < 65536 && n_samples > 0, ADYOLO_EINVAL,
+                   "audio_mix: bad arguments");
+    ADYOLO_REQUIRE(((uintptr_t)audio & 15) == 0 && ((uintptr_t)mate & 15) == 0 && ((uintptr_t)out & 15) == 0 &&
+                       ((uintptr_t)gains & 3) == 0,
+                   ADYOLO_EINVAL, "audio_mix: misaligned buffers (audio / mate / out 16 bytes, gains 4 bytes)");
+    const size_t words = (size_t)B * (size_t)n_samples * 4;
+    ADYOLO_REQUIRE(out == audio || out + words <= audio || audio + words <= out, ADYOLO_EINVAL,
+                   "audio_mix: out overlaps audio without being audio (in place or apart)");
+    ADYOLO_REQUIRE(out + words <= mate || mate + words <= out, ADYOLO_EINVAL, "audio_mix: out overlaps mate");
+    long g = (n_samples + 255) / 256;
+    if (g > 2048) g = 2048;
+    hipLaunchKernelGGL(adyolo::audio_mix_kernel, dim3((unsigned)g, (unsigned)B), dim3(256), 0, adyolo::as_stream(stream),
+                       (const float4 *)audio, (const float4 *)mate, gains, mixed, (float4 *)out, n_samples);
+    return adyolo::check_launch("audio_mix");
+}

@@ -75,6 +75,13 @@ __device__ __forceinline__ bool mask_bit1(const unsigned long long *__restrict__
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
+// Time-domain mixing (augmentations time_mix): a + g * m per channel, the product rounded before the sum (no FMA), which is
+// what ``a + g * m`` on float32 tensors gives.
+__device__ __forceinline__ float4 mix_add(const float4 a, const float4 m, const float g) {
+#pragma clang fp contract(off)
+    return make_float4(a.x + g * m.x, a.y + g * m.y, a.z + g * m.z, a.w + g * m.w);
+}
+
 // Sum `nparts` partial rows of a [nparts][ld] fp32 array for 32 consecutive columns starting at c0, in double.
 // Call from a 256-thread workgroup (32 columns x 8 part-groups); returns the column total in threads with
 // (threadIdx.x >> 5) == 0 (valid for c0 + (threadIdx.x & 31) < C).  `red` = 256 doubles of LDS.

@@ -12,6 +12,11 @@
 //   corpus_classwise_kernel  the dense SEDDOA / ACCDOA / ADPIT targets (datasets.ClasswiseLabelEncoder): per tile of label
 //                            frames, each frame's event range, the event each (frame, class) output takes, then every output
 //                            element written once
+// Time-domain mixing (aug_config.time_mix_augment: the audio of two chunks summed, their labels united) has its own forms, each
+// over the item table and a second table of mates; the kernels above are not touched by it:
+//   corpus_gather_mix_kernel      the gather with a second window, converted under its own combination, added as a + g * m
+//   corpus_mix_count_scan_kernel, corpus_mix_rows_kernel   the AD-YOLO rows of both sources in merged order
+//   corpus_classwise_mix_kernel   the dense targets of the merged events
 // The AD-YOLO label arithmetic is done in double, as the host does it (augmentations.rotate_labels on Python floats,
 // datasets.YoloLabelEncoder.encode_events in float64); only the written row is rounded to float32.  The class-wise kernel does
 // no arithmetic at all: the direction vectors come from a table the host builds with its own functions (corpus.xyz_table).
@@ -144,12 +149,11 @@ struct CorpusLabelGeom {
 
 // The label window of lane (b, e): event ev_lo + e of the item's range, its frame relative to the window, the rotated angles
 // and its az / el cell masks.  Returns the number of rows it produces (0: no event, or its frame is past the label frames).
-__device__ int corpus_event(const double *__restrict__ events, const int64_t *__restrict__ items,
-                            const double *__restrict__ bounds, const CorpusRot &rot, const CorpusLabelGeom &g, long lane,
-                            int &frame, int &cls, double &az, double &el, unsigned long long &az_bits,
-                            unsigned long long &el_bits, bool &bad) {
-    const int b = (int)(lane / g.max_events), e = (int)(lane % g.max_events);
-    const int64_t *it = items + (size_t)b * ADYOLO_CORPUS_ITEM_WORDS;
+// corpus_event_at: the same for event e of the item row ``it`` (the mixing labels call it with either source's row).
+__device__ int corpus_event_at(const double *__restrict__ events, const int64_t *__restrict__ it,
+                               const double *__restrict__ bounds, const CorpusRot &rot, const CorpusLabelGeom &g, int e,
+                               int &frame, int &cls, double &az, double &el, unsigned long long &az_bits,
+                               unsigned long long &el_bits, bool &bad) {
     const int64_t frame_off = it[1], ev_lo = it[2], ev_n = it[3], comb = it[4];
     bad = ev_lo < 0 || ev_n < 0 || ev_n > g.max_events || ev_lo > g.n_events - ev_n || comb >= 16;
     if (bad || e >= ev_n) return 0;
@@ -184,6 +188,15 @@ __device__ int corpus_event(const double *__restrict__ events, const int64_t *__
     az = a;
     el = v;
     return naz * nel;
+}
+
+__device__ int corpus_event(const double *__restrict__ events, const int64_t *__restrict__ items,
+                            const double *__restrict__ bounds, const CorpusRot &rot, const CorpusLabelGeom &g, long lane,
+                            int &frame, int &cls, double &az, double &el, unsigned long long &az_bits,
+                            unsigned long long &el_bits, bool &bad) {
+    const int b = (int)(lane / g.max_events), e = (int)(lane % g.max_events);
+    return corpus_event_at(events, items + (size_t)b * ADYOLO_CORPUS_ITEM_WORDS, bounds, rot, g, e, frame, cls, az, el, az_bits,
+                           el_bits, bad);
 }
 
 constexpr int CORPUS_SCAN_THREADS = 1024;
@@ -381,6 +394,390 @@ __global__ __launch_bounds__(CW_THREADS) void corpus_classwise_kernel(const doub
     }
 }
 
+// ================================================================================================ time-domain mixing
+// A mate row has the layout of an item row; offset (word 0) == -1: the item has no mate; word 6: the float32 bits of the gain.
+
+// One source's conversion, uniform over the workgroup (scalar registers): the signs and the swap of pcm_rot, or the two byte
+// selectors of pcm_swap.  mix_source returns false for a combination that is no symmetry of the array (MIC table only).
+struct CorpusMixSrc {
+    float sy, sz, sx;
+    bool swap;
+    unsigned sel_lo, sel_hi;
+};
+
+__device__ __forceinline__ bool mix_source(const CorpusRot &rot, int64_t comb, CorpusMixSrc &s) {
+    s.sy = 1.f; s.sz = 1.f; s.sx = 1.f; s.swap = false; s.sel_lo = 0u; s.sel_hi = 0u;
+    if (comb >= 0) {
+        s.sy = rot.c[comb][0]; s.sz = rot.c[comb][1]; s.sx = rot.c[comb][2]; s.swap = rot.c[comb][3] != 0.f;
+    }
+    return true;
+}
+
+__device__ __forceinline__ bool mix_source(const CorpusMicSrc &tab, int64_t comb, CorpusMixSrc &s) {
+    unsigned w = 0x03020100u;                               // identity, as in corpus_gather_mic_kernel
+    if (comb >= 0) w = tab.w[comb];
+    const unsigned s0 = w & 3u, s1 = (w >> 8) & 3u, s2 = (w >> 16) & 3u, s3 = (w >> 24) & 3u;
+    s.sy = 1.f; s.sz = 1.f; s.sx = 1.f; s.swap = false;
+    s.sel_lo = (s0 * 0x0202u + 0x0100u) | ((s1 * 0x0202u + 0x0100u) << 16);
+    s.sel_hi = (s2 * 0x0202u + 0x0100u) | ((s3 * 0x0202u + 0x0100u) << 16);
+    return w != ADYOLO_MIC_SWAP_NONE;
+}
+
+__device__ __forceinline__ float4 mix_conv(const CorpusRot &, int lo, int hi, const CorpusMixSrc &s) {
+    return pcm_rot(lo, hi, s.sy, s.sz, s.sx, s.swap);
+}
+__device__ __forceinline__ float4 mix_conv(const CorpusMicSrc &, int lo, int hi, const CorpusMixSrc &s) {
+    return pcm_swap(lo, hi, s.sel_lo, s.sel_hi);
+}
+
+// frames 2 i and 2 i + 1 of a window: one 16-byte load where the window starts on an even frame, two 8-byte loads where not
+template <bool EVEN>
+__device__ __forceinline__ int4 mix_load2(const int16_t *__restrict__ src, long i) {
+    if (EVEN) return reinterpret_cast<const int4 *>(src)[i];
+    const int2 *s2 = reinterpret_cast<const int2 *>(src);
+    const int2 a = s2[2 * i], c = s2[2 * i + 1];
+    return make_int4(a.x, a.y, c.x, c.y);
+}
+
+// the streaming loop for one parity of the item's and of the mate's offset; MIXED false: the mate is not read at all
+template <class Tab, bool A_EVEN, bool M_EVEN, bool MIXED>
+__device__ __forceinline__ void mix_loop(const Tab &tab, const int16_t *__restrict__ sa, const int16_t *__restrict__ sm, long n,
+                                         const CorpusMixSrc &ca, const CorpusMixSrc &cm, float g, float4 *__restrict__ dst,
+                                         long tid, long nth) {
+    const long n2 = n >> 1;
+    for (long i = tid; i < n2; i += nth) {
+        const int4 va = mix_load2<A_EVEN>(sa, i);
+        float4 o0 = mix_conv(tab, va.x, va.y, ca), o1 = mix_conv(tab, va.z, va.w, ca);
+        if (MIXED) {
+            const int4 vm = mix_load2<M_EVEN>(sm, i);
+            o0 = mix_add(o0, mix_conv(tab, vm.x, vm.y, cm), g);
+            o1 = mix_add(o1, mix_conv(tab, vm.z, vm.w, cm), g);
+        }
+        dst[2 * i] = o0;
+        dst[2 * i + 1] = o1;
+    }
+    if ((n & 1) && tid == 0) {
+        const int2 va = reinterpret_cast<const int2 *>(sa)[n - 1];
+        float4 o = mix_conv(tab, va.x, va.y, ca);
+        if (MIXED) {
+            const int2 vm = reinterpret_cast<const int2 *>(sm)[n - 1];
+            o = mix_add(o, mix_conv(tab, vm.x, vm.y, cm), g);
+        }
+        dst[n - 1] = o;
+    }
+}
+
+// grid (blocks per item, B), the grid of corpus_gather_kernel.  Tab = CorpusRot (FOA) or CorpusMicSrc (MIC).  A bad item or a
+// bad mate: zeros for the whole sample and status bit 2; no mate: the plain gather's bits, and nothing of the mate row but its
+// offset is read.
+template <class Tab>
+__global__ __launch_bounds__(256) void corpus_gather_mix_kernel(const int16_t *__restrict__ pcm, long n_total,
+                                                                const int64_t *__restrict__ items,
+                                                                const int64_t *__restrict__ mates, long n, Tab tab,
+                                                                float4 *__restrict__ out, int *__restrict__ status) {
+    const int b = blockIdx.y;
+    const int64_t *it = items + (size_t)b * ADYOLO_CORPUS_ITEM_WORDS, *mt = mates + (size_t)b * ADYOLO_CORPUS_ITEM_WORDS;
+    const int64_t off = it[0], comb = it[4], moff = mt[0];
+    const bool mixed = moff != -1;
+    float4 *dst = out + (size_t)b * n;
+    const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, nth = (long)gridDim.x * blockDim.x;
+    CorpusMixSrc ca, cm = {1.f, 1.f, 1.f, false, 0u, 0u};
+    float g = 0.f;
+    bool bad = off < 0 || off > n_total - n || comb >= 16 || !mix_source(tab, comb, ca);
+    if (!bad && mixed) {
+        const int64_t mcomb = mt[4];
+        bad = moff < 0 || moff > n_total - n || mcomb >= 16 || !mix_source(tab, mcomb, cm);
+        g = __int_as_float((int)mt[6]);
+    }
+    if (bad) {
+        if (tid == 0 && status) atomicOr(status, ADYOLO_CORPUS_BAD_ITEM);
+        for (long i = tid; i < n; i += nth) dst[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        return;
+    }
+    const int16_t *sa = pcm + (size_t)off * 4;
+    if (!mixed) {
+        if ((off & 1) == 0)
+            mix_loop<Tab, true, true, false>(tab, sa, sa, n, ca, cm, g, dst, tid, nth);
+        else
+            mix_loop<Tab, false, true, false>(tab, sa, sa, n, ca, cm, g, dst, tid, nth);
+        return;
+    }
+    const int16_t *sm = pcm + (size_t)moff * 4;
+    switch ((int)(off & 1) | ((int)(moff & 1) << 1)) {           // uniform over the workgroup
+    case 0: mix_loop<Tab, true, true, true>(tab, sa, sm, n, ca, cm, g, dst, tid, nth); break;
+    case 1: mix_loop<Tab, false, true, true>(tab, sa, sm, n, ca, cm, g, dst, tid, nth); break;
+    case 2: mix_loop<Tab, true, false, true>(tab, sa, sm, n, ca, cm, g, dst, tid, nth); break;
+    default: mix_loop<Tab, false, false, true>(tab, sa, sm, n, ca, cm, g, dst, tid, nth); break;
+    }
+}
+
+// ---- AD-YOLO rows of a mixed batch.  Lanes are (item, source, event): 2 max_events per item, the item's events first.  Both
+// sources' events are frame-sorted (corpus.load_chunked_split), so the place of an event in the merged order of
+// augmentations.merge_labels -- frames ascending, the item's events before the mate's within a frame -- is its own index plus
+// the number of the other source's events before it: those with a smaller window-relative frame for an item lane, a smaller or
+// equal one for a mate lane (a binary search).  The lanes without an event take the places behind the events, so that every
+// place of the item's 2 max_events is written once.  An item whose own row or whose mate row is bad has no rows at all.
+__device__ __forceinline__ bool corpus_row_bad(const int64_t *__restrict__ row, const CorpusLabelGeom &g) {
+    const int64_t ev_lo = row[2], ev_n = row[3], comb = row[4];
+    return ev_lo < 0 || ev_n < 0 || ev_n > g.max_events || ev_lo > g.n_events - ev_n || comb >= 16;
+}
+
+// -> rows of the lane (as corpus_event); place: its place among the item's 2 max_events; b: its item
+__device__ int corpus_mix_event(const double *__restrict__ events, const int64_t *__restrict__ items,
+                                const int64_t *__restrict__ mates, const double *__restrict__ bounds, const CorpusRot &rot,
+                                const CorpusLabelGeom &g, long lane, int &b, int &place, int &frame, int &cls, double &az,
+                                double &el, unsigned long long &az_bits, unsigned long long &el_bits, bool &bad) {
+    const int me = g.max_events, per = 2 * me;
+    b = (int)(lane / per);
+    const int r = (int)(lane - (long)b * per), src = r >= me ? 1 : 0, e = r - src * me;
+    const int64_t *it = items + (size_t)b * ADYOLO_CORPUS_ITEM_WORDS, *mt = mates + (size_t)b * ADYOLO_CORPUS_ITEM_WORDS;
+    const bool has_mate = mt[0] != -1;
+    bad = corpus_row_bad(it, g) || (has_mate && corpus_row_bad(mt, g));
+    const int n_a = bad ? 0 : (int)it[3], n_m = bad || !has_mate ? 0 : (int)mt[3];
+    if (e >= (src ? n_m : n_a)) {
+        place = src ? me + e : n_m + e;
+        return 0;
+    }
+    const int64_t *own = src ? mt : it, *other = src ? it : mt;
+    const int64_t f = (int64_t)events[(size_t)(own[2] + e) * 4] - own[1];
+    const double *oev = events + (size_t)other[2] * 4;
+    const int64_t ooff = other[1];
+    int lo = 0, hi = src ? n_a : n_m;
+    while (lo < hi) {                                            // the other source's events that come first
+        const int mid = (lo + hi) >> 1;
+        const int64_t fo = (int64_t)oev[(size_t)mid * 4] - ooff;
+        if (src ? fo <= f : fo < f)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    place = e + lo;
+    bool own_bad;
+    return corpus_event_at(events, own, bounds, rot, g, e, frame, cls, az, el, az_bits, el_bits, own_bad);
+}
+
+// one workgroup, as corpus_count_scan_kernel; ws[b * 2 max_events + place] = exclusive row offset of that place
+__global__ __launch_bounds__(CORPUS_SCAN_THREADS) void corpus_mix_count_scan_kernel(
+    const double *__restrict__ events, const int64_t *__restrict__ items, const int64_t *__restrict__ mates,
+    const double *__restrict__ bounds, CorpusRot rot, CorpusLabelGeom g, int *ws, int *__restrict__ count,
+    int *__restrict__ status) {
+    __shared__ int part[CORPUS_SCAN_THREADS];
+    __shared__ int any_bad;
+    const int t = threadIdx.x;
+    if (t == 0) any_bad = 0;
+    __syncthreads();
+    const long lanes = (long)g.B * 2 * g.max_events;
+    const long chunk = (lanes + CORPUS_SCAN_THREADS - 1) / CORPUS_SCAN_THREADS;
+    const long s0 = t * chunk, s1 = s0 + chunk < lanes ? s0 + chunk : lanes;
+    bool bad_here = false;
+    for (long s = s0; s < s1; ++s) {                             // every lane's row count, at its merged place
+        int b, place, frame, cls;
+        double az, el;
+        unsigned long long ab, eb;
+        bool bad;
+        const int c = corpus_mix_event(events, items, mates, bounds, rot, g, s, b, place, frame, cls, az, el, ab, eb, bad);
+        bad_here |= bad;
+        ws[(long)b * 2 * g.max_events + place] = c;
+    }
+    if (bad_here) any_bad = 1;
+    __threadfence_block();
+    __syncthreads();
+    int sum = 0;
+    for (long s = s0; s < s1; ++s) sum += ws[s];
+    part[t] = sum;
+    __syncthreads();
+    for (int o = 1; o < CORPUS_SCAN_THREADS; o <<= 1) {
+        const int v = t >= o ? part[t - o] : 0;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    int run = part[t] - sum;
+    for (long s = s0; s < s1; ++s) {
+        const int c = ws[s];
+        ws[s] = run;
+        run += c;
+    }
+    if (t == CORPUS_SCAN_THREADS - 1) {
+        const int total = part[t];
+        count[0] = total;
+        int bits = any_bad ? ADYOLO_CORPUS_BAD_ITEM : 0;
+        if ((long)total > g.cap) bits |= ADYOLO_CORPUS_OVERFLOW;
+        if (bits && status) atomicOr(status, bits);
+    }
+}
+
+// as corpus_rows_kernel; column 0 of a row is the item, whichever source the event comes from
+__global__ __launch_bounds__(256) void corpus_mix_rows_kernel(const double *__restrict__ events,
+                                                              const int64_t *__restrict__ items,
+                                                              const int64_t *__restrict__ mates,
+                                                              const double *__restrict__ bounds, CorpusRot rot, CorpusLabelGeom g,
+                                                              const int *__restrict__ ws, const int *__restrict__ count,
+                                                              float *__restrict__ target) {
+    const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, nth = (long)gridDim.x * blockDim.x;
+    const long lanes = (long)g.B * 2 * g.max_events;
+    for (long s = tid; s < lanes; s += nth) {
+        int b, place, frame, cls;
+        double az, el;
+        unsigned long long ab, eb;
+        bool bad;
+        const int c = corpus_mix_event(events, items, mates, bounds, rot, g, s, b, place, frame, cls, az, el, ab, eb, bad);
+        if (c == 0) continue;
+        long r = ws[(long)b * 2 * g.max_events + place];
+        const float fb = (float)b, ft = (float)frame, fc = (float)cls, fu = (float)az, fv = (float)el;
+        for (int i = 0; i < g.Gaz; ++i) {
+            if (!((ab >> i) & 1ull)) continue;
+            for (int j = 0; j < g.Gel; ++j) {
+                if (!((eb >> j) & 1ull)) continue;
+                if (r < g.cap) {
+                    float *row = target + (size_t)r * 7;
+                    row[0] = fb; row[1] = ft; row[2] = (float)i; row[3] = (float)j; row[4] = fc; row[5] = fu; row[6] = fv;
+                }
+                ++r;
+            }
+        }
+    }
+    const long total = count[0];
+    for (long r = total + tid; r < g.cap; r += nth) {
+        float *row = target + (size_t)r * 7;
+        row[0] = -1.f; row[1] = 0.f; row[2] = 0.f; row[3] = 0.f; row[4] = 0.f; row[5] = 0.f; row[6] = 0.f;
+    }
+}
+
+// ---- the dense class-wise targets of a mixed batch: corpus_classwise_kernel over two sources.  Each source has its own frame
+// ranges lb[s] and class cache cls[s]; a (frame, class) output picks over the item's range, then the mate's (the order of
+// merge_labels), and every picked event carries its source in bit 30 of its index (n_events < 2^30), because its direction
+// vector is read from the xyz slot of its own source's combination.  An item without a mate has one source: the bits of
+// corpus_classwise_kernel.
+constexpr int CW_SRC_BIT = 30;
+
+__global__ __launch_bounds__(CW_THREADS) void corpus_classwise_mix_kernel(const double *__restrict__ events,
+                                                                          const float *__restrict__ xyz,
+                                                                          const int64_t *__restrict__ items,
+                                                                          const int64_t *__restrict__ mates,
+                                                                          CorpusClasswiseGeom g, float *__restrict__ target,
+                                                                          int *__restrict__ status) {
+    extern __shared__ int pick[];                // [CW_FRAMES][C][4]
+    __shared__ int lb[2][CW_FRAMES + 1];
+    __shared__ int cls[2][CW_EV_CACHE];
+    const int b = blockIdx.y, t0 = blockIdx.x * CW_FRAMES, tid = threadIdx.x;
+    const int nf = g.n_label_frames - t0 < CW_FRAMES ? g.n_label_frames - t0 : CW_FRAMES;
+    const int64_t *rows[2] = {items + (size_t)b * ADYOLO_CORPUS_ITEM_WORDS, mates + (size_t)b * ADYOLO_CORPUS_ITEM_WORDS};
+    const int ns = rows[1][0] != -1 ? 2 : 1;
+    float *dst = target + ((size_t)b * g.n_label_frames + t0) * g.row;
+    const int n_out = nf * g.row;
+    int64_t frame_off[2] = {0, 0}, ev_lo[2] = {0, 0};
+    int n[2] = {0, 0};
+    size_t slot[2] = {0, 0};
+    bool bad = false;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        if (s >= ns) break;
+        const int64_t lo = rows[s][2], cnt = rows[s][3], comb = rows[s][4];
+        bad |= lo < 0 || cnt < 0 || cnt > g.max_events || lo > g.n_events - cnt || comb >= 16;
+        frame_off[s] = rows[s][1];
+        ev_lo[s] = lo;
+        n[s] = (int)cnt;
+        slot[s] = comb < 0 ? 0 : (size_t)comb + 1;
+    }
+    if (bad) {
+        if (blockIdx.x == 0 && tid == 0) atomicOr(status, ADYOLO_CORPUS_BAD_ITEM);
+        for (int p = tid; p < n_out; p += CW_THREADS) dst[p] = 0.f;
+        return;
+    }
+    if (tid <= nf) {
+        lb[0][tid] = n[0];
+        lb[1][tid] = n[1];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {                                 // as in corpus_classwise_kernel, per source
+        if (s >= ns) break;
+        const double *ev = events + (size_t)ev_lo[s] * 4;
+        const double base = (double)(frame_off[s] + t0);
+        for (int e = tid; e < n[s]; e += CW_THREADS) {
+            const double fe = ev[(size_t)e * 4] - base;
+            const double fp = e > 0 ? ev[(size_t)(e - 1) * 4] - base : -1.0;
+            const double lo = fp < 0.0 ? 0.0 : floor(fp) + 1.0, hi = fe > (double)nf ? (double)nf : floor(fe);
+            if (lo <= hi)
+                for (int i = (int)lo; i <= (int)hi; ++i) lb[s][i] = e;
+        }
+    }
+    __syncthreads();
+    const int C = g.C;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        if (s >= ns) break;
+        const double *ev = events + (size_t)ev_lo[s] * 4;
+        const int e0 = lb[s][0], e1 = lb[s][nf];
+        for (int e = e0 + tid; e < e1; e += CW_THREADS) {
+            const double cd = ev[(size_t)e * 4 + 1];
+            const bool ok = cd >= 0.0 && cd < (double)C;
+            if (!ok) atomicOr(status, ADYOLO_CORPUS_BAD_CLASS);
+            if (e - e0 < CW_EV_CACHE) cls[s][e - e0] = ok ? (int)cd : -1;
+        }
+    }
+    __syncthreads();
+    const bool adpit = g.format == ADYOLO_CORPUS_ADPIT;
+    for (int p = tid; p < nf * C; p += CW_THREADS) {
+        const int i = p / C, c = p - i * C;
+        int cnt = 0, last = -1, first[3] = {-1, -1, -1};
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {                             // the item's events of the frame, then the mate's
+            if (s >= ns) break;
+            const double *ev = events + (size_t)ev_lo[s] * 4;
+            const int e0 = lb[s][0], e1 = lb[s][nf];
+            for (int e = lb[s][i]; e < lb[s][i + 1]; ++e) {
+                int ce;
+                if (e < e1 && (unsigned)(e - e0) < (unsigned)CW_EV_CACHE) {
+                    ce = cls[s][e - e0];
+                } else {
+                    const double cd = ev[(size_t)e * 4 + 1];
+                    ce = cd >= 0.0 && cd < (double)C ? (int)cd : -1;
+                }
+                if (ce == c) {
+                    const int idx = ((int)ev_lo[s] + e) | (s << CW_SRC_BIT);
+                    if (cnt < 3) first[cnt] = idx;
+                    last = idx;
+                    ++cnt;
+                }
+            }
+        }
+        int *q = pick + p * 4;
+        q[0] = adpit ? cnt : last;
+        q[1] = first[0];
+        q[2] = first[1];
+        q[3] = first[2];
+    }
+    __syncthreads();
+    for (int r = tid; r < g.row; r += CW_THREADS) {
+        int c, k, s = 0;
+        if (adpit) {
+            s = r / (4 * C);
+            const int rr = r - s * 4 * C;
+            k = rr / C - 1;
+            c = rr - (k + 1) * C;
+        } else {
+            const int part = r / C;
+            c = r - part * C;
+            k = g.format == ADYOLO_CORPUS_SEDDOA ? part - 1 : part;
+        }
+        const int lo_cnt = s == 0 ? 1 : s <= 2 ? 2 : 3, hi_cnt = s == 0 ? 1 : s <= 2 ? 2 : 0x7fffffff;
+        const int j = s == 0 ? 0 : s <= 2 ? s - 1 : s - 3;
+        for (int i = 0; i < nf; ++i) {
+            const int *q = pick + (i * C + c) * 4;
+            const int e = adpit ? (q[0] >= lo_cnt && q[0] <= hi_cnt ? q[1 + j] : -1) : q[0];
+            float v = 0.f;
+            if (e >= 0) {
+                const size_t sl = (e >> CW_SRC_BIT) & 1 ? slot[1] : slot[0];
+                const size_t idx = (size_t)(e & ((1 << CW_SRC_BIT) - 1));
+                v = k < 0 ? 1.f : xyz[(idx * ADYOLO_CORPUS_XYZ_SLOTS + sl) * 3 + k];
+            }
+            dst[(size_t)i * g.row + r] = v;
+        }
+    }
+}
+
 static int corpus_rot(const float *rot_host, CorpusRot &rot) {
     if (!rot_host) return ADYOLO_EINVAL;
     for (int c = 0; c < 16; ++c)
@@ -485,4 +882,94 @@ extern "C" int adyolo_corpus_classwise_labels(const double *events, const float 
     hipLaunchKernelGGL(corpus_classwise_kernel, dim3((unsigned)cdiv(n_label_frames, CW_FRAMES), (unsigned)B), dim3(CW_THREADS), lds,
                        as_stream(stream), events, xyz, items, g, target, status);
     return check_launch("corpus_classwise_labels");
+}
+
+// ------------------------------------------------------------------------------------------------ time-domain mixing
+extern "C" int adyolo_corpus_gather_mix(const int16_t *pcm, long n_total, const int64_t *items, const int64_t *mates, int B,
+                                        long n, const float *rot_host, const unsigned int *mic_src_host, float *audio,
+                                        int *status, void *stream) {
+    ADYOLO_REQUIRE(pcm && items && mates && audio && (rot_host || mic_src_host), ADYOLO_EINVAL, "corpus_gather_mix: null pointer");
+    ADYOLO_REQUIRE(B > 0 && B < 65536 && n > 0 && n_total >= n, ADYOLO_EINVAL,
+                   "corpus_gather_mix: bad shape B=%d n=%ld n_total=%ld", B, n, n_total);
+    ADYOLO_REQUIRE(((uintptr_t)pcm & 15) == 0 && ((uintptr_t)audio & 15) == 0 && ((uintptr_t)items & 7) == 0 &&
+                       ((uintptr_t)mates & 7) == 0,
+                   ADYOLO_EINVAL, "corpus_gather_mix: misaligned buffers (pcm / audio 16 bytes, items / mates 8 bytes)");
+    int gx = cdiv(n, 256L * 16);                            // the grid of adyolo_corpus_gather
+    gx = gx < 1 ? 1 : (gx > 4096 ? 4096 : gx);
+    const dim3 grid((unsigned)gx, (unsigned)B);
+    if (mic_src_host) {
+        CorpusMicSrc tab;
+        for (int c = 0; c < 16; ++c) tab.w[c] = mic_src_host[c];
+        hipLaunchKernelGGL(corpus_gather_mix_kernel<CorpusMicSrc>, grid, dim3(256), 0, as_stream(stream), pcm, n_total, items,
+                           mates, n, tab, (float4 *)audio, status);
+    } else {
+        CorpusRot rot;
+        corpus_rot(rot_host, rot);
+        hipLaunchKernelGGL(corpus_gather_mix_kernel<CorpusRot>, grid, dim3(256), 0, as_stream(stream), pcm, n_total, items, mates,
+                           n, rot, (float4 *)audio, status);
+    }
+    return check_launch("corpus_gather_mix");
+}
+
+extern "C" long adyolo_corpus_yolo_labels_mix_workspace_words(int B, int max_events) {
+    if (B <= 0 || max_events < 0) return -1;
+    return (long)B * 2 * (max_events > 0 ? max_events : 1);
+}
+
+extern "C" int adyolo_corpus_yolo_labels_mix(const double *events, long n_events, const int64_t *items, const int64_t *mates,
+                                             int B, int max_events, int n_label_frames, const double *grid_bounds, int Gaz,
+                                             int Gel, const float *rot_host, int *ws, float *target, long cap, int *count,
+                                             int *status, void *stream) {
+    ADYOLO_REQUIRE(events && items && mates && grid_bounds && rot_host && ws && target && count && status, ADYOLO_EINVAL,
+                   "corpus_yolo_labels_mix: null pointer");
+    ADYOLO_REQUIRE(B > 0 && max_events >= 0 && n_events >= 0 && n_label_frames > 0 && cap > 0 && cap < (1L << 31) &&
+                       (long)B * 2 * max_events < (1L << 31),
+                   ADYOLO_EINVAL, "corpus_yolo_labels_mix: bad shape B=%d max_events=%d cap=%ld", B, max_events, cap);
+    ADYOLO_REQUIRE(Gaz > 0 && Gaz <= 64 && Gel > 0 && Gel <= 64, ADYOLO_ENOSUP,
+                   "corpus_yolo_labels_mix: grid %d x %d (at most 64 x 64 cells)", Gaz, Gel);
+    ADYOLO_REQUIRE(((uintptr_t)events & 7) == 0 && ((uintptr_t)items & 7) == 0 && ((uintptr_t)mates & 7) == 0 &&
+                       ((uintptr_t)grid_bounds & 7) == 0 && ((uintptr_t)target & 3) == 0,
+                   ADYOLO_EINVAL, "corpus_yolo_labels_mix: misaligned buffers");
+    CorpusRot rot;
+    corpus_rot(rot_host, rot);
+    CorpusLabelGeom g;
+    g.B = B; g.max_events = max_events; g.n_label_frames = n_label_frames; g.Gaz = Gaz; g.Gel = Gel;
+    g.n_events = n_events; g.cap = cap;
+    hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(corpus_mix_count_scan_kernel, dim3(1), dim3(CORPUS_SCAN_THREADS), 0, st, events, items, mates, grid_bounds,
+                       rot, g, ws, count, status);
+    int rc = check_launch("corpus_mix_count_scan");
+    if (rc) return rc;
+    long work = cap > (long)B * 2 * max_events ? cap : (long)B * 2 * max_events;
+    int gx = cdiv(work, 256L * 4);
+    gx = gx < 1 ? 1 : (gx > 1024 ? 1024 : gx);
+    hipLaunchKernelGGL(corpus_mix_rows_kernel, dim3((unsigned)gx), dim3(256), 0, st, events, items, mates, grid_bounds, rot, g,
+                       ws, count, target);
+    return check_launch("corpus_mix_rows");
+}
+
+extern "C" int adyolo_corpus_classwise_labels_mix(const double *events, const float *xyz, long n_events, const int64_t *items,
+                                                  const int64_t *mates, int B, int max_events, int n_label_frames, int n_classes,
+                                                  int format, float *target, int *status, void *stream) {
+    ADYOLO_REQUIRE(events && xyz && items && mates && target && status, ADYOLO_EINVAL,
+                   "corpus_classwise_labels_mix: null pointer");
+    ADYOLO_REQUIRE(B > 0 && B < 65536 && max_events >= 0 && n_events >= 0 && n_events < (1L << CW_SRC_BIT) &&
+                       n_label_frames > 0 && n_classes > 0,
+                   ADYOLO_EINVAL, "corpus_classwise_labels_mix: bad shape B=%d max_events=%d n_events=%ld n_label_frames=%d C=%d",
+                   B, max_events, n_events, n_label_frames, n_classes);
+    ADYOLO_REQUIRE(format == ADYOLO_CORPUS_SEDDOA || format == ADYOLO_CORPUS_ACCDOA || format == ADYOLO_CORPUS_ADPIT,
+                   ADYOLO_EINVAL, "corpus_classwise_labels_mix: unknown format %d", format);
+    ADYOLO_REQUIRE(n_classes <= CW_MAX_CLASSES, ADYOLO_ENOSUP, "corpus_classwise_labels_mix: %d classes (at most %d)", n_classes,
+                   CW_MAX_CLASSES);
+    ADYOLO_REQUIRE(((uintptr_t)events & 7) == 0 && ((uintptr_t)items & 7) == 0 && ((uintptr_t)mates & 7) == 0 &&
+                       ((uintptr_t)xyz & 3) == 0 && ((uintptr_t)target & 3) == 0 && ((uintptr_t)status & 3) == 0,
+                   ADYOLO_EINVAL, "corpus_classwise_labels_mix: misaligned buffers");
+    CorpusClasswiseGeom g;
+    g.B = B; g.max_events = max_events; g.n_label_frames = n_label_frames; g.C = n_classes; g.format = format;
+    g.row = (format == ADYOLO_CORPUS_SEDDOA ? 4 : format == ADYOLO_CORPUS_ACCDOA ? 3 : 24) * n_classes;
+    g.n_events = n_events;
+    const size_t lds = (size_t)CW_FRAMES * n_classes * 4 * sizeof(int);
+    hipLaunchKernelGGL(corpus_classwise_mix_kernel, dim3((unsigned)cdiv(n_label_frames, CW_FRAMES), (unsigned)B), dim3(CW_THREADS),
+                       lds, as_stream(stream), events, xyz, items, mates, g, target, status);
+    return check_launch("corpus_classwise_labels_mix");
 }

@@ -250,7 +250,10 @@ class FoaDataset(torch.utils.data.Dataset):
     4th element, the item's SpecAug table int32 (2, 4) (``SpecAug.draw_groups``: log-mel, then intensity vector; masked on the
     GPU by ``FeatureExtractor(.., spec_ranges=)`` inside ``TrainStep.step``).  With ``aug_config.channel_swap_augment`` (MIC-format
     training splits only) ``comb_no`` is drawn from the eight symmetries of the array (``augmentations.MIC_SWAP_COMBS``) and the
-    audio is permuted by ``swap_audio`` instead of rotated.  Normalisation, rotation of the audio and the
+    audio is permuted by ``swap_audio`` instead of rotated.  With ``aug_config.time_mix_augment`` (training splits) the item ends in
+    one more element, a dict {"mate_pcm": int16 (T, 4) or None, "mate_comb": int, "gain": float}: the chunk summed into this one
+    by ``ops.audio_mix`` (None: the item is not mixed), and ``label_rows`` encode ``augmentations.merge_labels`` of both chunks'
+    labels, each under its own combination.  Normalisation, rotation of the audio and the
     features run on the GPU (``AudioStager`` -> ``rotate_audio`` -> ``FeatureExtractor``); the label half of the rotation
     and the label encoding stay here on the host, as in the reference's DataLoader workers.  ``label_rows``: the AD-YOLO row
     list, or for ``seddoa | masked-seddoa | accdoa | adpit`` the dense ``ClasswiseLabelEncoder`` tensor (T', ...)."""
@@ -299,8 +302,10 @@ class FoaDataset(torch.utils.data.Dataset):
                 self.filelist = sorted(self.filelist)[self.rank::self.world]
         self.hop_label = int(dc.get("sr", 24000) * dc.get("label_hop_len_s", 0.1))
         self.rotate = bool(params.get("aug_config", {}).get("rotation_augment", False)) and not is_valid
-        from .augmentations import SpecAug
+        from .augmentations import SpecAug, time_mix_config
         self.specaug = SpecAug(params, is_valid)            # spec_augment on and not a validation split: a mask table per item
+        mix = time_mix_config(params)                       # ValueError: time_mix_prob / time_mix_gain_db out of range
+        self.mix = mix if set_type == "train" and not is_valid else None
         if self.loss_nm == "adyolo":
             self.encoder = YoloLabelEncoder(params)
         elif self.loss_nm in CLASSWISE_LABELS:
@@ -375,14 +380,32 @@ class FoaDataset(torch.utils.data.Dataset):
         if self.specaug.apply_augment:          # datasets.py:158-159: MEL, then IV, each its own draw, right after the rotation
             from .features import HOP, N_MELS
             spec = self.specaug.draw_groups(1, pcm.shape[0] // HOP, N_MELS, 2)[0]
+        mixed = None
+        if self.mix is not None:                # time-domain mixing: the last draws of the item; the mate's audio and labels
+            from .augmentations import draw_time_mix, merge_labels
+            mixed = {"mate_pcm": None, "mate_comb": 0, "gain": 1.0}
+            drawn = draw_time_mix(self._random, self.mix, self.total_filelist, name,
+                                  "rotate" if self.rotate else "swap" if self.swap else None)
+            if drawn is not None:
+                mate, mate_comb, gain = drawn
+                _, mate_pcm = wavfile.read(self._os.path.join(self.wav_pth, mate + ".wav"))
+                mate_label = self.load_csv2dict(self._os.path.join(self.csv_pth, mate + ".csv"))
+                if mate_comb is not None:
+                    mate_label = rotate_labels(mate_label, mate_comb)
+                label = merge_labels(label, mate_label)
+                mixed = {"mate_pcm": np.ascontiguousarray(mate_pcm, dtype=np.int16), "mate_comb": int(mate_comb or 0),
+                         "gain": float(gain)}
         nb_label_frames = pcm.shape[0] // self.hop_label
         if self.loss_nm == "adyolo":
             target = self.encoder.get_yolo_label(label, nb_label_frames)
         else:                                   # dense (T', ...) float32 tensor, datasets.py:210-219
             target = getattr(self.encoder, CLASSWISE_LABELS[self.loss_nm])(label, nb_label_frames)
+        item = (np.ascontiguousarray(pcm, dtype=np.int16), comb_no, target)
         if spec is not None:
-            return np.ascontiguousarray(pcm, dtype=np.int16), comb_no, target, spec
-        return np.ascontiguousarray(pcm, dtype=np.int16), comb_no, target
+            item += (spec,)
+        if mixed is not None:
+            item += (mixed,)
+        return item
 
 
 CLASSWISE_LABELS = {"seddoa": "get_seddoa_label", "masked-seddoa": "get_seddoa_label", "accdoa": "get_accdoa_label",
@@ -393,7 +416,12 @@ def audio_collate_fn(batch):
     """list of FoaDataset items -> (pcm int16 (B, T, 4) host tensor, comb_nos list, target).  AD-YOLO: target (M, 7) float32
     rows built exactly like ``collate_fn`` (datasets.py:164-184); class-wise losses: the dense labels stacked to (B, T', ...),
     like the default collate the reference uses for them.  Items with SpecAug tables (4-tuples) -> a 4th element, the tables
-    stacked to int32 (B, 2, 4)."""
+    stacked to int32 (B, 2, 4).  Items of a mixing dataset (``aug_config.time_mix_augment``: a trailing dict) -> one trailing dict
+    {"mate_pcm": int16 (B, T, 4), zeros where the item is unmixed, "mate_combs": list, "gains": float32 (B,), "mixed": bool (B,)}."""
+    mix = None
+    if isinstance(batch[0][-1], dict):
+        mix = [item[-1] for item in batch]
+        batch = [item[:-1] for item in batch]
     pcms, combs, labels = list(zip(*batch))[:3]
     if isinstance(labels[0], torch.Tensor):
         target = torch.stack(labels, 0)
@@ -402,4 +430,12 @@ def audio_collate_fn(batch):
     out = torch.stack([torch.from_numpy(p) for p in pcms], 0), list(combs), target
     if len(batch[0]) == 4:
         out += (torch.stack([item[3] for item in batch], 0).to(torch.int32),)
+    if mix is not None:
+        mate_pcm = torch.zeros(out[0].shape, dtype=torch.int16)
+        for b, m in enumerate(mix):
+            if m["mate_pcm"] is not None:
+                mate_pcm[b] = torch.from_numpy(m["mate_pcm"])
+        out += ({"mate_pcm": mate_pcm, "mate_combs": [m["mate_comb"] for m in mix],
+                 "gains": torch.tensor([m["gain"] for m in mix], dtype=torch.float32),
+                 "mixed": torch.tensor([m["mate_pcm"] is not None for m in mix], dtype=torch.bool)},)
     return out

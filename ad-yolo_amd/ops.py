@@ -1811,6 +1811,51 @@ def corpus_gather_mic(pcm, items, src, out, status):
     return out
 
 
+def _corpus_mates(name, items, mates):
+    _corpus_i64("%s: mates" % name, mates, items.device)
+    if tuple(mates.shape) != tuple(items.shape):
+        raise _lib.AdyoloHipError("%s: mates %s do not match items %s" % (name, tuple(mates.shape), tuple(items.shape)))
+
+
+def corpus_gather_mix(pcm, items, mates, rot, mic_src, out, status):
+    """``corpus_gather`` (``mic_src`` None; rot: ``corpus_rot_table``) or ``corpus_gather_mic`` (mic_src: ``corpus_mic_table``) with
+    a second window per item summed in: mates int64 (B, 8) on the device, rows like ``items`` with their own combinations, the
+    float32 bits of the gain in word 6, offset -1 = no mate -> out = a + g * m, bit for bit two plain gathers and that
+    expression on float32 tensors (adyolo_hip.h ``adyolo_corpus_gather_mix``).  A bad item or mate: zeros for the sample and
+    status bit 2.  No allocation, no sync."""
+    b = _corpus_gather_args("corpus_gather_mix", pcm, items, out, status)
+    _corpus_mates("corpus_gather_mix", items, mates)
+    if mic_src is None and rot is None:
+        raise _lib.AdyoloHipError("corpus_gather_mix: the FOA form needs the rotation table")
+    _c("adyolo_corpus_gather_mix", _p(pcm), pcm.shape[0], _p(items), _p(mates), b, out.shape[1],
+       NULL if rot is None else ctypes.cast(rot, ctypes.c_void_p),
+       NULL if mic_src is None else ctypes.cast(mic_src, ctypes.c_void_p), _p(out), _p(status), _stream())
+    return out
+
+
+def audio_mix(audio, mate, gains, mixed, out=None):
+    """audio, mate (B, n, 4) float32, gains float32 (B,), mixed bool (B,), all on the device ->
+    ``mixed[b] ? audio[b] + gains[b] * mate[b] : audio[b]`` (a new tensor unless ``out`` is given; ``out`` may be ``audio`` itself).
+    The product is rounded before the sum; an unmixed clip keeps its bits (adyolo_hip.h ``adyolo_audio_mix``)."""
+    _chk(audio, mate)
+    if audio.dim() != 3 or audio.shape[2] != 4 or tuple(mate.shape) != tuple(audio.shape) or mate.device != audio.device:
+        raise _lib.AdyoloHipError("audio_mix: audio %s / mate %s are not two (B, n, 4) tensors on one device"
+                                  % (tuple(audio.shape), tuple(mate.shape)))
+    b, n, _ = audio.shape
+    if gains.dtype != torch.float32 or gains.device != audio.device or not gains.is_contiguous() or tuple(gains.shape) != (b,):
+        raise _lib.AdyoloHipError("audio_mix: gains must be a contiguous float32 tensor (%d,) on %s" % (b, audio.device))
+    if mixed.dtype != torch.bool or mixed.device != audio.device or not mixed.is_contiguous() or tuple(mixed.shape) != (b,):
+        raise _lib.AdyoloHipError("audio_mix: mixed must be a contiguous bool tensor (%d,) on %s" % (b, audio.device))
+    if out is None:
+        out = torch.empty_like(audio)
+    else:
+        _chk(out)
+        if tuple(out.shape) != tuple(audio.shape) or out.device != audio.device:
+            raise _lib.AdyoloHipError("audio_mix: out %s does not match audio %s" % (tuple(out.shape), tuple(audio.shape)))
+    _c("adyolo_audio_mix", _p(audio), _p(mate), _p(gains), _p(mixed), _p(out), b, n, _stream())
+    return out
+
+
 def mic_swap(audio, src, out=None):
     """audio (B, n, 4) float32 and src int32 (B, 4) on the device -> out[b, i, j] = audio[b, i, src[b, j] & 3] (a new tensor
     unless ``out``, which must not overlap audio, is given).  The values are moved bit for bit (adyolo_hip.h ``adyolo_mic_swap``)."""
@@ -1860,6 +1905,37 @@ def corpus_yolo_labels(events, items, max_events, n_label_frames, bounds, grid, 
     return target
 
 
+def corpus_labels_mix_workspace_words(batch, max_events):
+    return int(_lib.load().adyolo_corpus_yolo_labels_mix_workspace_words(int(batch), int(max_events)))
+
+
+def corpus_yolo_labels_mix(events, items, mates, max_events, n_label_frames, bounds, grid, rot, ws, target, count, status):
+    """``corpus_yolo_labels`` for mixed items: the rows of ``augmentations.merge_labels(item, mate)`` per item, each event under
+    its own source's combination and frame offset, column 0 the item (adyolo_hip.h ``adyolo_corpus_yolo_labels_mix``).  mates
+    int64 (B, 8) as for ``corpus_gather_mix``; ws int32 of ``corpus_labels_mix_workspace_words`` words.  No allocation, no sync."""
+    dev = items.device
+    _corpus_i64("corpus_yolo_labels_mix: items", items, dev)
+    _corpus_mates("corpus_yolo_labels_mix", items, mates)
+    if not events.is_cuda or events.dtype != torch.float64 or not events.is_contiguous() or events.dim() != 2 \
+            or events.shape[1] != 4 or events.device != dev:
+        raise _lib.AdyoloHipError("corpus_yolo_labels_mix: events must be a contiguous float64 tensor (E, 4) on %s" % dev)
+    gaz, gel = int(grid[0]), int(grid[1])
+    if bounds.dtype != torch.float64 or bounds.device != dev or not bounds.is_contiguous() or bounds.numel() != 2 * (gaz + gel):
+        raise _lib.AdyoloHipError("corpus_yolo_labels_mix: bounds must be float64 (2 Gaz + 2 Gel,) on %s" % dev)
+    _chk(target)
+    if target.dim() != 2 or target.shape[1] != 7:
+        raise _lib.AdyoloHipError("corpus_yolo_labels_mix: target %s is not (cap, 7)" % (tuple(target.shape),))
+    b = items.shape[0]
+    for name, t, words in (("ws", ws, corpus_labels_mix_workspace_words(b, max_events)), ("count", count, 1),
+                           ("status", status, 1)):
+        if t.dtype != torch.int32 or t.device != dev or not t.is_contiguous() or t.numel() < words:
+            raise _lib.AdyoloHipError("corpus_yolo_labels_mix: %s must be at least %d int32 words on %s" % (name, words, dev))
+    _c("adyolo_corpus_yolo_labels_mix", _p(events), events.shape[0], _p(items), _p(mates), b, int(max_events),
+       int(n_label_frames), _p(bounds), gaz, gel, ctypes.cast(rot, ctypes.c_void_p), _p(ws), _p(target), target.shape[0],
+       _p(count), _p(status), _stream())
+    return target
+
+
 def corpus_classwise_shape(loss, batch, n_label_frames, nb_classes):
     """The dense target of ``datasets.ClasswiseLabelEncoder`` stacked over a batch: (B, T', 4C) seddoa / masked-seddoa,
     (B, T', 3C) accdoa, (B, T', 6, 4, C) adpit."""
@@ -1894,6 +1970,34 @@ def corpus_classwise_labels(events, items, xyz, max_events, n_label_frames, nb_c
         raise _lib.AdyoloHipError("corpus_classwise_labels: status must be an int32 word on %s" % dev)
     _c("adyolo_corpus_classwise_labels", _p(events), _p(xyz), n_ev, _p(items), b, int(max_events), int(n_label_frames),
        int(nb_classes), CORPUS_FORMATS[loss], _p(target), _p(status), _stream())
+    return target
+
+
+def corpus_classwise_labels_mix(events, items, mates, xyz, max_events, n_label_frames, nb_classes, loss, target, status):
+    """``corpus_classwise_labels`` for mixed items: the dense targets of the host encoders on ``augmentations.merge_labels(item,
+    mate)``, each event's direction vector from its own source's combination (adyolo_hip.h ``adyolo_corpus_classwise_labels_mix``).
+    mates int64 (B, 8) as for ``corpus_gather_mix``.  No allocation, no sync."""
+    dev = items.device
+    _corpus_i64("corpus_classwise_labels_mix: items", items, dev)
+    _corpus_mates("corpus_classwise_labels_mix", items, mates)
+    if not events.is_cuda or events.dtype != torch.float64 or not events.is_contiguous() or events.dim() != 2 \
+            or events.shape[1] != 4 or events.device != dev:
+        raise _lib.AdyoloHipError("corpus_classwise_labels_mix: events must be a contiguous float64 tensor (E, 4) on %s" % dev)
+    n_ev = events.shape[0]
+    if xyz.dtype != torch.float32 or xyz.device != dev or not xyz.is_contiguous() \
+            or tuple(xyz.shape) != (n_ev, CORPUS_XYZ_SLOTS, 3):
+        raise _lib.AdyoloHipError("corpus_classwise_labels_mix: xyz must be a contiguous float32 tensor (%d, %d, 3) on %s"
+                                  % (n_ev, CORPUS_XYZ_SLOTS, dev))
+    b = items.shape[0]
+    want = corpus_classwise_shape(loss, b, n_label_frames, nb_classes)
+    _chk(target)
+    if tuple(target.shape) != want or target.device != dev:
+        raise _lib.AdyoloHipError("corpus_classwise_labels_mix: target %s on %s, expected %s on %s for %s"
+                                  % (tuple(target.shape), target.device, want, dev, loss))
+    if status.dtype != torch.int32 or status.device != dev or not status.is_contiguous() or status.numel() < 1:
+        raise _lib.AdyoloHipError("corpus_classwise_labels_mix: status must be an int32 word on %s" % dev)
+    _c("adyolo_corpus_classwise_labels_mix", _p(events), _p(xyz), n_ev, _p(items), _p(mates), b, int(max_events),
+       int(n_label_frames), int(nb_classes), CORPUS_FORMATS[loss], _p(target), _p(status), _stream())
     return target
 
 

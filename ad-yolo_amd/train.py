@@ -724,7 +724,9 @@ class _EpochLoss:
 def train_one_epoch_audio(params: dict, dataloader, trainer, stager=None, rotate=True):
     """The raw-audio epoch: ``dataloader`` yields ``audio_collate_fn`` batches (pcm int16 (B,T,4), comb_nos, target[, SpecAug
     tables (B,2,4)]); each is staged to the GPU (int16 over PCIe on a side stream, double-buffered), converted, rotated (with
-    ``aug_config.channel_swap_augment``: its channels permuted, ``swap_audio``) and handed with its tables to ``TrainStep.step``
+    ``aug_config.channel_swap_augment``: its channels permuted, ``swap_audio``; with ``aug_config.time_mix_augment``: the batch's
+    trailing dict of mates staged, moved by their own combinations and summed in by ``ops.audio_mix``) and handed with its
+    tables to ``TrainStep.step``
     (features [+ SpecAug masks] + forward + loss + backward [+ all-reduce] + Adam).  Returns the mean loss with ONE device sync
     at the end of the epoch (the reference syncs every iteration, train.py:57); with ``train_config['skip_nonfinite']`` the
     mean over the APPLIED steps (``_EpochLoss``).  With ``train_config['accum_steps']`` every batch is a micro-step; an epoch whose number of batches is no multiple of it (or that
@@ -732,24 +734,44 @@ def train_one_epoch_audio(params: dict, dataloader, trainer, stager=None, rotate
     from .augmentations import channel_swap_enabled, rotate_audio, swap_audio
     from .datasets import AudioStager
     move_audio = swap_audio if channel_swap_enabled(params) else rotate_audio     # MIC channel swap | FOA rotation
+
+    def split(rest):
+        """The optional tail of a batch -> (SpecAug tables or None, mixing dict or None), told apart by type."""
+        spec = [r for r in rest if isinstance(r, torch.Tensor)]
+        mix = [r for r in rest if isinstance(r, dict)]
+        return (spec[0] if spec else None), (mix[0] if mix else None)
     acc, n = _EpochLoss(params, trainer), 0
     it = iter(dataloader)
     try:
-        pcm, combs, target, *spec = next(it)
+        pcm, combs, target, *rest = next(it)
     except StopIteration:
         return 0.0
+    spec, mix = split(rest)
+    device = trainer.flat.flat.device
     if stager is None:
-        stager = AudioStager(pcm.shape[0], pcm.shape[1], trainer.flat.flat.device)
+        stager = AudioStager(pcm.shape[0], pcm.shape[1], device)
     stager.stage(pcm)
+    mate_stager = None
+    if mix is not None:                           # time-domain mixing: the mates cross PCIe through a stager of their own
+        mate_stager = AudioStager(pcm.shape[0], pcm.shape[1], device)
+        mate_stager.stage(mix["mate_pcm"])
     while True:
         audio = stager.get()
-        cur_combs, cur_target, cur_spec = combs, target, (spec[0] if spec else None)
+        mate = mate_stager.get() if mate_stager is not None else None
+        cur_combs, cur_target, cur_spec, cur_mix = combs, target, spec, mix
         nxt = next(it, None)
         if nxt is not None:                       # the next batch crosses PCIe while this step runs
-            pcm, combs, target, *spec = nxt
+            pcm, combs, target, *rest = nxt
+            spec, mix = split(rest)
             stager.stage(pcm)
+            if mate_stager is not None:
+                mate_stager.stage(mix["mate_pcm"])
         if rotate and any(int(c) != 0 for c in cur_combs):
             audio = move_audio(audio, cur_combs)
+        if cur_mix is not None:                   # each side under its own combinations, then audio + gain * mate
+            if rotate and any(int(c) != 0 for c in cur_mix["mate_combs"]):
+                mate = move_audio(mate, cur_mix["mate_combs"])
+            audio = ops.audio_mix(audio, mate, cur_mix["gains"].to(device), cur_mix["mixed"].to(device), out=audio)
         acc.add(trainer.step(audio, cur_target, cur_spec))
         n += 1
         if nxt is None or (params.get("args", {}).get("quick_test") and n == 5):
@@ -780,7 +802,7 @@ def train_one_epoch_corpus(params: dict, corpus, trainer):
     nxt = corpus.draw(range(starts[0], min(len(files), starts[0] + bs)))
     for k in range(len(starts)):
         drawn = nxt
-        items, spec = drawn
+        items, spec = drawn[0], drawn[1]          # a third element (mates: time-domain mixing) goes through to launch
         bufs = None
         if graphs is not None:
             target_like = torch.empty(corpus.target_shape(items.shape[0]), dtype=torch.float32, device="meta")

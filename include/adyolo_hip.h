@@ -634,6 +634,15 @@ int adyolo_foa_rotate(const float *audio, float *out, const float *cfg, int B, l
  * Label angles are remapped on the host by the same combination (augmentations.rotate_labels). */
 int adyolo_mic_swap(const float *audio, float *out, const int *src_dev, int B, long n_samples, void *stream);
 
+/* Time-domain mixing on raw audio (aug_config.time_mix_augment, the host-fed path; the corpus paths mix inside
+ * adyolo_corpus_gather_mix): audio / mate / out [B][n_samples][4] float32, 16-byte aligned; gains DEVICE float [B]; mixed DEVICE
+ * bytes [B] (0: the clip is not mixed).  out[b] = mixed[b] ? audio[b] + gains[b] * mate[b] : audio[b], the product rounded to
+ * float32 before the sum (no FMA: the bits of ``audio + gain * mate`` on float32 tensors).  An unmixed clip is moved, not
+ * computed on (NaN payloads and -0.0 keep their bits), and its mate and gain are not read.  out may be audio itself (in place)
+ * or a buffer apart from it; it must not overlap mate. */
+int adyolo_audio_mix(const float *audio, const float *mate, const float *gains, const unsigned char *mixed, float *out, int B,
+                     long n_samples, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Training batches from an HBM-resident corpus (csrc/corpus.hip, ad-yolo_amd/corpus.py DeviceCorpus / ClasswiseDeviceCorpus),
  * opt-in: the host half of FoaDataset.__getitem__ + audio_collate_fn (src/datasets.py:93-184) on the device, from one small
@@ -674,6 +683,27 @@ int adyolo_mic_swap(const float *audio, float *out, const int *src_dev, int B, l
  *   dropped; an event whose class is outside [0, C) is dropped and sets ADYOLO_CORPUS_BAD_CLASS; an item outside the corpus
  *   (as for the rows, max_events included) gets an all-zero target and sets ADYOLO_CORPUS_BAD_ITEM.  No workspace, no
  *   atomics on the target: capturable, and the target may be a recorded step's static buffer.  C <= 256, else ENOSUP.
+ *
+ * Time-domain mixing (aug_config.time_mix_augment): the audio of two chunks summed, their labels united.  The *_mix calls take
+ * the item table and a second table of the same shape and layout:
+ *   mates    DEVICE int64 [B][ADYOLO_CORPUS_ITEM_WORDS]: the chunk mixed into item b, as an item row with its own combination;
+ *            word 0 (sample offset) exactly -1: item b has no mate and the rest of the row is not read; any other offset outside
+ *            pcm is a bad item; word 6: the bit pattern of the float32 gain g (zero-extended).
+ * adyolo_corpus_gather_mix: audio [b] = a + g * m, where a is what adyolo_corpus_gather (mic_src_host NULL; rot_host needed) or
+ *   adyolo_corpus_gather_mic (mic_src_host given; rot_host not read) writes for item b and m what it would write for the mate
+ *   row, each under its own combination; the product is rounded to float32 before the sum (no FMA): bit for bit two gathers
+ *   and ``a + g * m`` on float32 tensors.  An item without a mate has the plain gather's bits and costs its bytes.  A bad item or
+ *   a bad mate: zeros for the whole sample and ADYOLO_CORPUS_BAD_ITEM.  One pass; every parity of the two offsets is legal.
+ * adyolo_corpus_yolo_labels_mix: the rows of augmentations.merge_labels(item, mate) per item: frames ascending, the item's
+ *   events before the mate's within a frame (both sources' events must be frame-sorted, as load_chunked_split leaves them), each
+ *   event rotated by its own source's combination and counted from its own source's frame offset; column 0 is the item for
+ *   both.  ws adyolo_corpus_yolo_labels_mix_workspace_words(B, max_events) int32 words; max_events bounds each source's event
+ *   count; an item whose own row or mate row is bad gets no rows at all and sets ADYOLO_CORPUS_BAD_ITEM.  Capacity, overflow,
+ *   the b = -1 tail and the grid limit as for adyolo_corpus_yolo_labels, whose rows an all-unmixed batch equals.
+ * adyolo_corpus_classwise_labels_mix: the dense targets of the merged events: SEDDOA / ACCDOA take the last event of a class in
+ *   a frame in item-then-mate order (the mate's wins a collision), ADPIT counts over both sources and keeps the first three in
+ *   that order; each direction vector comes from the xyz slot of its own source's combination.  n_events < 2^30.  An item
+ *   without a mate has the bits of adyolo_corpus_classwise_labels; bad items (either row) and bad classes as there.
  * ---------------------------------------------------------------------------------------------- */
 #define ADYOLO_CORPUS_ITEM_WORDS 8
 #define ADYOLO_CORPUS_ROT_WORDS  8
@@ -696,6 +726,17 @@ int  adyolo_corpus_yolo_labels(const double *events, long n_events, const int64_
 int  adyolo_corpus_classwise_labels(const double *events, const float *xyz, long n_events, const int64_t *items, int B,
                                     int max_events, int n_label_frames, int n_classes, int format, float *target, int *status,
                                     void *stream);
+int  adyolo_corpus_gather_mix(const int16_t *pcm, long n_total, const int64_t *items, const int64_t *mates, int B, long n,
+                              const float *rot_host, const unsigned int *mic_src_host /* NULL = FOA */, float *audio,
+                              int *status, void *stream);
+long adyolo_corpus_yolo_labels_mix_workspace_words(int B, int max_events);
+int  adyolo_corpus_yolo_labels_mix(const double *events, long n_events, const int64_t *items, const int64_t *mates, int B,
+                                   int max_events, int n_label_frames, const double *grid_bounds, int Gaz, int Gel,
+                                   const float *rot_host, int *ws, float *target, long cap, int *count, int *status,
+                                   void *stream);
+int  adyolo_corpus_classwise_labels_mix(const double *events, const float *xyz, long n_events, const int64_t *items,
+                                        const int64_t *mates, int B, int max_events, int n_label_frames, int n_classes,
+                                        int format, float *target, int *status, void *stream);
 
 /* K11 Adam, AdamW, SGD and gradient-norm clipping over one flat parameter buffer (csrc/optim.hip; the reference picks its
  * optimizer by name, src/train.py:29-37, and clips with clip_grad_norm_, src/train.py:54; no amsgrad).  The step counter is ON

@@ -23,11 +23,14 @@ step, capture; page cache).
 classes of the split and the model (12 by default: the ACCDOA / ADPIT heads' GEMMs need 3C and 9C in multiples of 4);
 --swap (with --mic only) turns ``aug_config.channel_swap_augment`` on instead of ``rotation_augment``: the MIC channel swap;
 --labels-only stops after load, batch, gather and labels (no model: any class count, e.g. the 13 of DCASE 2023); --corpus-only
-skips the host-loader epochs.
+skips the host-loader epochs.  --mix [--prob P] runs every batch size twice, key off ("b16") and with
+``aug_config.time_mix_augment`` at probability P ("b16_mix": doubled AD-YOLO row capacity), and adds to the second the time-domain
+mixing calls on the same batch: ``adyolo_corpus_gather_mix`` with the drawn mates, with a mate for every item (prob 1.0) and with
+none (prob 0.0), and the ``_mix`` label call next to the plain one.
 
   python tools/corpus_bench.py [--dir /tmp/adyolo_corpus] [--batches 16,64] [--steps 32,8] [--workers 16] [--json out.json]
                                [--loss adyolo|seddoa|accdoa|adpit] [--mic] [--swap] [--classes C] [--labels-only]
-                               [--corpus-only]
+                               [--corpus-only] [--mix [--prob P]]
 """
 import argparse
 import csv
@@ -79,7 +82,7 @@ def write_split(root, n_recordings, seed=0, n_classes=12, audio_dir="foa_dev"):
     return nbytes
 
 
-def params(root, batch, steps, loss="adyolo", mic=False, n_classes=12, swap=False):
+def params(root, batch, steps, loss="adyolo", mic=False, n_classes=12, swap=False, mix=None):
     from __graft_entry__ import _params
     prm = _params(nb_classes=n_classes)
     prm["args"]["loss"] = loss
@@ -92,6 +95,8 @@ def params(root, batch, steps, loss="adyolo", mic=False, n_classes=12, swap=Fals
                          "spec_augment_time_mask_param": 40, "spec_augment_freq_mask_param": 40}
     if swap:
         prm["aug_config"].update({"rotation_augment": False, "channel_swap_augment": True})
+    if mix is not None:
+        prm["aug_config"].update({"time_mix_augment": True, "time_mix_prob": mix})
     return prm
 
 
@@ -159,13 +164,15 @@ def graph_us(launch, iters):
 
 
 def bench_batch(root, batch, steps, workers, iters, loss="adyolo", mic=False, n_classes=12, labels_only=False, swap=False,
-                corpus_only=False):
+                corpus_only=False, mix=None):
     from adyolo_amd import ops
     from adyolo_amd.corpus import ClasswiseDeviceCorpus, DeviceCorpus, load_chunked_split
     from adyolo_amd.datasets import FoaDataset, audio_collate_fn
     from adyolo_amd.train import train_one_epoch_audio, train_one_epoch_corpus
-    prm = params(root, batch, steps, loss, mic, n_classes, swap)
+    prm = params(root, batch, steps, loss, mic, n_classes, swap, mix)
     out = {"batch": batch, "steps_per_epoch": steps}
+    if mix is not None:
+        out["mix_prob"] = mix
     if loss != "adyolo" or mic:
         out.update(loss=loss, mic=mic, classes=n_classes)
     if swap:
@@ -203,6 +210,49 @@ def bench_batch(root, batch, steps, workers, iters, loss="adyolo", mic=False, n_
     if swap:
         out["gather_mic_us"] = graph_us(lambda i: ops.corpus_gather_mic(corpus.pcm, dev_items[i % 4], corpus.mic_src, audio,
                                                                         corpus.status), iters)
+    if mix is not None:
+        # the mixing gather on the same item tables: the drawn mates (prob P), a mate for every item (the next item of the batch,
+        # gain 1.0: prob 1.0) and none (prob 0.0)
+        one = int(np.float32(1.0).view(np.uint32))
+        every, none = [], []
+        for d in drawn:
+            m = np.roll(d[0], 1, axis=0).copy()
+            m[:, 6] = one
+            every.append(torch.from_numpy(m).to("cuda:0"))
+            m = np.zeros_like(d[0])
+            m[:, 0] = m[:, 4] = -1
+            none.append(torch.from_numpy(m).to("cuda:0"))
+        dev_mates = [torch.from_numpy(d[2]).to("cuda:0") for d in drawn]
+        out["mixed_items"] = round(float(np.mean([(d[2][:, 0] != -1).mean() for d in drawn])), 3)
+        for key, tabs in (("gather_mix_us", dev_mates), ("gather_mix_p1_us", every), ("gather_mix_p0_us", none)):
+            out[key] = graph_us(lambda i: ops.corpus_gather_mix(corpus.pcm, dev_items[i % 4], tabs[i % 4], corpus.rot,
+                                                                corpus.mic_src, audio, corpus.status), iters)
+        gb = batch * corpus.n_samples * (8 + 16) / 1e9                   # int16 frames read + float32 frames written
+        out["gather_tb_s"] = round(gb / out["gather_us"] * 1e3, 2)
+        out["gather_mix_p1_tb_s"] = round((gb + batch * corpus.n_samples * 8 / 1e9) / out["gather_mix_p1_us"] * 1e3, 2)
+        if loss == "adyolo":
+            target = torch.empty((corpus.cap, 7), dtype=torch.float32, device="cuda:0")
+            rows = torch.empty(1, dtype=torch.int32, device="cuda:0")
+            ws = torch.empty(ops.corpus_labels_mix_workspace_words(batch, corpus.max_events), dtype=torch.int32, device="cuda:0")
+            out["labels_us"] = graph_us(lambda i: ops.corpus_yolo_labels(
+                corpus.events, dev_items[i % 4], corpus.max_events, corpus.n_label_frames, corpus.bounds, corpus.grid, corpus.rot,
+                ws, target, rows, corpus.status), iters)
+            for key, tabs in (("labels_mix_us", dev_mates), ("labels_mix_p1_us", every)):
+                out[key] = graph_us(lambda i: ops.corpus_yolo_labels_mix(
+                    corpus.events, dev_items[i % 4], tabs[i % 4], corpus.max_events, corpus.n_label_frames, corpus.bounds,
+                    corpus.grid, corpus.rot, ws, target, rows, corpus.status), iters)
+            del target, rows, ws
+        else:
+            target = torch.empty(corpus.target_shape(batch), dtype=torch.float32, device="cuda:0")
+            out["labels_us"] = graph_us(lambda i: ops.corpus_classwise_labels(
+                corpus.events, dev_items[i % 4], corpus.xyz, corpus.max_events, corpus.n_label_frames, corpus.nb_classes, loss,
+                target, corpus.status), iters)
+            for key, tabs in (("labels_mix_us", dev_mates), ("labels_mix_p1_us", every)):
+                out[key] = graph_us(lambda i: ops.corpus_classwise_labels_mix(
+                    corpus.events, dev_items[i % 4], tabs[i % 4], corpus.xyz, corpus.max_events, corpus.n_label_frames,
+                    corpus.nb_classes, loss, target, corpus.status), iters)
+            del target
+        corpus.check()
     del audio
     if loss != "adyolo":
         # the label kernel alone, on item tables already on the device: --iters launches recorded in one hipGraph and
@@ -286,6 +336,8 @@ def main():
     ap.add_argument("--labels-only", action="store_true", help="load, batch and labels timings only (no training epochs)")
     ap.add_argument("--swap", action="store_true", help="MIC channel swap instead of the FOA rotation (needs --mic)")
     ap.add_argument("--corpus-only", action="store_true", help="skip the host-loader epochs")
+    ap.add_argument("--mix", action="store_true", help="each batch size with aug_config.time_mix_augment off and on")
+    ap.add_argument("--prob", type=float, default=0.5, help="time_mix_prob of the --mix runs")
     a = ap.parse_args()
     if a.swap and not a.mic:
         ap.error("--swap permutes microphone capsules: it needs --mic")
@@ -308,6 +360,11 @@ def main():
             r = bench_batch(a.dir, b, s, a.workers, a.iters, a.loss, a.mic, n_classes, a.labels_only, a.swap, a.corpus_only)
             res["b%d" % b] = r
             print(json.dumps(r), flush=True)
+            if a.mix:
+                r = bench_batch(a.dir, b, s, a.workers, a.iters, a.loss, a.mic, n_classes, a.labels_only, a.swap, a.corpus_only,
+                                mix=a.prob)
+                res["b%d_mix" % b] = r
+                print(json.dumps(r), flush=True)
     finally:
         if not a.keep:
             shutil.rmtree(a.dir, ignore_errors=True)

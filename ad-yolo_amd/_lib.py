@@ -43,6 +43,7 @@ SIGNATURES = {
     "adyolo_wino_wgrad": (I, [P] * 7 + [I] * 6 + [P]),
     "adyolo_conv3x3_wgrad_slabs": (I, [I] * 5),
     "adyolo_conv3x3_wgrad": (I, [P] * 6 + [I] * 6 + [P]),
+    "adyolo_wgrad_plan": (I, [I] * 6 + [P]),
     "adyolo_gemm": (I, [P] * 5 + [I] * 10 + [P]),
     "adyolo_gemm_plan": (I, [I] * 8 + [P, P, P]),
     "adyolo_gemm_batched": (I, [P] * 3 + [I] * 10 + [L] * 6 + [F, I, P]),

@@ -747,6 +747,47 @@ extern "C" int adyolo_conv3x3_wgrad(const float *x, const float *dy, const float
     return check_launch("conv3x3_wgrad_reduce");
 }
 
+// Host only, no launch: the work split the three weight-gradient entry points take for a shape (the geometry functions their
+// launchers call).  form 0: conv3x3_wgrad_kernel, 1: stem_wgrad_kernel, 2: wino_wgrad_kernel, 3: wino4_wgrad_kernel.
+extern "C" int adyolo_wgrad_plan(int form, int N, int H, int W, int Cin, int Cout, int *out8) {
+    ADYOLO_REQUIRE(out8 && form >= 0 && form <= 3 && N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, ADYOLO_EINVAL,
+                   "wgrad_plan: bad arguments");
+    for (int i = 0; i < 8; ++i) out8[i] = 0;
+    if (form <= 1) {
+        if (Cout % 32 || (Cin != 8 && Cin % 32)) return 0;
+        if (form == 1 && !(Cin == 8 && Cout == 32 && (long)N * H < (1L << 31))) return 0;
+        int TW;
+        const int nsplit = wgrad_splits(N, H, W, Cin, Cout, &TW);
+        out8[0] = nsplit;
+        out8[2] = 1;
+        out8[4] = 1;
+        if (form == 0) {
+            out8[1] = N * cdiv(H, 256 / TW) * cdiv(W, TW);
+            out8[3] = 256 / TW;
+            out8[5] = TW;
+        } else {
+            const int nblk = nsplit < 512 ? nsplit : 512;
+            out8[1] = N * H;
+            out8[3] = cdiv(N * H, nblk);
+            out8[5] = SW_T;
+            out8[6] = nblk;
+        }
+        out8[7] = 1;
+        return 0;
+    }
+    if (form == 2) {
+        if (adyolo_wino_wgrad_slabs(N, H, W, Cin, Cout) <= 0 ||
+            (size_t)H * W * (Cin > Cout ? Cin : Cout) * 4 >= ((size_t)1 << 31))
+            return 0;
+        wino_wgrad_plan(N, H, W, Cin, Cout, out8);
+    } else {
+        if (adyolo_wino4_wgrad_slabs(N, H, W, Cin, Cout) <= 0) return 0;
+        wino4_wgrad_plan(N, H, W, Cin, Cout, out8);
+    }
+    out8[7] = 1;
+    return 0;
+}
+
 // ---- entry transpose NCHW -> NHWC8: the layout the stem convolution reads (7 feature planes padded to 8 channels)
 namespace adyolo {
 __global__ __launch_bounds__(256) void nchw_to_nhwc8_kernel(const float *__restrict__ x, float *__restrict__ y, int C,

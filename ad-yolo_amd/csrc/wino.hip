@@ -843,6 +843,16 @@ static int wino_wgrad_geometry(int N, int H, int W, int Cin, int Cout, int *nt_o
     return best_split;
 }
 
+void wino_wgrad_plan(int N, int H, int W, int Cin, int Cout, int *out8) {
+    int nt, nseg, seg_rows, nitems;
+    out8[0] = wino_wgrad_geometry(N, H, W, Cin, Cout, &nt, &nseg, &seg_rows, &nitems);
+    out8[1] = nitems;
+    out8[2] = nseg;
+    out8[3] = seg_rows;
+    out8[4] = nt;
+    out8[5] = 16;
+}
+
 }  // namespace adyolo
 
 extern "C" int adyolo_wino_wgrad_slabs(int N, int H, int W, int Cin, int Cout) {

@@ -627,6 +627,17 @@ static int wino4_wgrad_geometry(int N, int H, int W, int Cin, int Cout, int *npa
 }
 
 }  // namespace w4
+
+void wino4_wgrad_plan(int N, int H, int W, int Cin, int Cout, int *out8) {
+    int npairs, nseg, seg_steps, nitems, nblk;
+    out8[0] = w4::wino4_wgrad_geometry(N, H, W, Cin, Cout, &npairs, &nseg, &seg_steps, &nitems, &nblk);
+    out8[1] = nitems;
+    out8[2] = nseg;
+    out8[3] = seg_steps;
+    out8[4] = Cout % 64 == 0 ? 2 : 1;
+    out8[5] = 16;
+}
+
 }  // namespace adyolo
 
 using namespace adyolo;

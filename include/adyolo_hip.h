@@ -183,6 +183,13 @@ int adyolo_conv3x3_wgrad_slabs(int N, int H, int W, int Cin, int Cout);
 int adyolo_conv3x3_wgrad(const float *x, const float *dy, const float *in_scale, const float *in_shift,
                          float *slabs, float *dw, int N, int H, int W, int Cin, int Cin_real, int Cout,
                          void *stream);
+/* host only, no launch: the work split the weight-gradient launchers compute for a shape.  form 0: conv3x3_wgrad_kernel,
+ * 1: stem_wgrad_kernel (Cin = 8, Cout = 32, no affine), 2: wino_wgrad_kernel, 3: wino4_wgrad_kernel.  out8 = {workgroups per channel
+ * block (= slabs; the stem before its cap), work items (tiles | image rows | strip segments | run-pair segments), segments per
+ * strip / pair, segment length (rows of a tile | rows per workgroup | tile rows | steps of one tile row), block width (NT | NB;
+ * 1), tile / strip width in pixels, the stem's workgroups (min(slabs, 512)), 1 when the entry point takes the shape with that
+ * kernel}; all zeros when it does not. */
+int adyolo_wgrad_plan(int form, int N, int H, int W, int Cin, int Cout, int *out8);
 
 /* ------------------------------------------------------------------------------------------------
  * K7  dense GEMM on fp32 MFMA:  C[m][n] = sum_k opA(m,k) * opB(n,k) (+ bias[n])

@@ -111,7 +111,8 @@ def test_conv3x3_without_relu_propagates_nan(ops, monkeypatch, algo, persist):
 @pytest.mark.parametrize("n,h,w,cin,cout", [
     (2, 16, 64, 32, 32), (2, 13, 32, 32, 64), (1, 18, 16, 64, 128), (1, 9, 16, 256, 256), (2, 20, 64, 7, 32),
     (3, 40, 64, 32, 32), (2, 150, 24, 32, 64), (1, 67, 37, 64, 32),
-    (6, 132, 16, 256, 256),      # Winograd wgrad: 18 work items on 16 slabs -> several items per workgroup, ragged segment
+    (6, 132, 16, 256, 256),      # several items per workgroup: F(2x2) 30 items (segments of 14, 14, 14, 14, 10 tile rows) on 16 slabs,
+                                 # direct 54 tiles on 16; F(4x4): 6 items on 6 (tests/test_gpu_wgrad_stage.py has its several-item cases)
     (2, 21, 19, 96, 32),         # odd H and W (general masking path), 3 input-channel blocks
     (3, 11, 37, 7, 32), (1, 5, 64, 7, 32), (5, 3, 6, 7, 32),    # stem weight-gradient kernel: odd W, fewer rows than waves
 ])
@@ -140,7 +141,8 @@ def test_conv3x3_dgrad_wgrad(ops, monkeypatch, n, h, w, cin, cout, algo):
     (2, 8, 16, 32, 64, 0), (1, 8, 16, 32, 64, 1),           # one pair / half a pair, a single step
     (3, 40, 16, 64, 64, 1), (5, 36, 32, 64, 128, 1),         # odd run counts: the last pair is half empty
     (2, 64, 32, 32, 64, 0), (1, 100, 48, 32, 64, 1), (2, 24, 64, 64, 64, 0),      # widths of 2, 3, 4 runs
-    (4, 300, 32, 64, 64, 1), (6, 132, 16, 256, 256, 0),      # several segments per pair, several items per workgroup
+    (4, 300, 32, 64, 64, 1), (6, 132, 16, 256, 256, 0),      # several segments per pair: 36 items on 36 splits, 6 on 6 (one item per
+                                                             # workgroup; several: oracle/wgrad_stage.py, test_gpu_wgrad_stage.py)
     (3, 28, 16, 96, 192, 1),                                 # 3 x 3 channel blocks
     (2, 64, 64, 32, 32, 1), (3, 20, 48, 64, 32, 0), (1, 12, 16, 32, 96, 1),       # 32-channel output blocks (NB = 1)
     (5, 36, 4, 64, 64, 1), (7, 64, 4, 128, 128, 0), (3, 40, 8, 64, 128, 0), (2, 24, 8, 64, 64, 1), (9, 16, 4, 32, 32, 1),   # narrow maps: runs of 4 / 2 samples

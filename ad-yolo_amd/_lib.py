@@ -146,6 +146,7 @@ SIGNATURES = {
     "adyolo_pcm16_to_f32": (I, [P, P, L, P]),
     "adyolo_mask_ranges": (I, [P, P, I, I, I, I, P]),
     "adyolo_mask_groups": (I, [P, P, I, I, I, I, I, P, P]),
+    "adyolo_feat_augment": (I, [P, P, I, I, I, I, I, P, ctypes.c_uint, P]),
     "adyolo_colstats": (I, [P, P, P, L, I, P]),
     "adyolo_grad_sumsq_parts": (L, [L]),
     "adyolo_grad_sumsq": (I, [P, L, F, P, P]),

@@ -4,7 +4,8 @@ combinations of channel sign flips / X-Y swap with the matching azimuth / elevat
 audio on the GPU (csrc/aug.hip ``foa_rotate_kernel``).  ``swap_audio`` / ``ChannelSwapAug`` are the MIC-format counterpart (no
 reference: a permutation of the four capsules by a symmetry of the array, derived below from ``rotate_labels``).  ``SpecAug``
 (augmentations.py:6-33) masks the GPU feature tensor (csrc/aug.hip); its random draw restates torchaudio 0.10, which is absent
-here (parity of the stream unpinned)."""
+here (parity of the stream unpinned).  ``feature_aug_config`` / ``draw_feature_aug`` / ``apply_feature_aug_host`` are the keys,
+draws and NumPy definition of the frequency-shift and cutout augmentation of the features (csrc/aug.hip ``feat_augment_kernel``)."""
 import random
 
 import torch
@@ -153,6 +154,121 @@ def merge_labels(a: dict, b: dict):
     mixture: the frames of both in ascending order, each frame's list ``a``'s events followed by ``b``'s.  New dict and lists."""
     return {frame: [list(ev) for ev in a.get(frame, [])] + [list(ev) for ev in b.get(frame, [])]
             for frame in sorted(set(a) | set(b))}
+
+
+# ---- Frequency shift and cutout on the normalised features (``aug_config.freq_shift_augment`` / ``cutout_augment``).  The item's
+# table grows from the SpecAug rows (G, 4) to (G + 2, 4): row G the cutout rectangle {t0, t1, f0, f1}, row G + 1 {shift, 0, 0, 0}.
+FEATURE_AUG_DEFAULTS = {"freq_shift_prob": 0.5, "freq_shift_max_bins": 5, "cutout_prob": 0.5, "cutout_time_param": 40,
+                        "cutout_freq_param": 20}
+
+
+def feature_aug_config(params):
+    """``aug_config.freq_shift_augment`` / ``cutout_augment`` and their keys -> None (both off) or
+    (shift_prob or None, shift_max_bins, cutout_prob or None, cutout_time_param, cutout_freq_param): a probability of None is an
+    augmentation that is off.  ``freq_shift_prob`` / ``cutout_prob`` (0.5) must be numbers in [0, 1], ``freq_shift_max_bins`` (5)
+    an integer in 1..63, ``cutout_time_param`` (40 frames) / ``cutout_freq_param`` (20 mel bins) finite numbers >= 0
+    (``ValueError`` naming the key otherwise).  The keys of an augmentation that is off are not read."""
+    import math
+    aug = params.get("aug_config", {})
+    shift_on, cut_on = bool(aug.get("freq_shift_augment", False)), bool(aug.get("cutout_augment", False))
+    if not shift_on and not cut_on:
+        return None
+
+    def number(key):
+        v = aug.get(key, FEATURE_AUG_DEFAULTS[key])
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+            raise ValueError("aug_config.%s must be a finite number (got %r)" % (key, v))
+        return v
+
+    def prob(key):
+        v = number(key)
+        if not 0.0 <= v <= 1.0:
+            raise ValueError("aug_config.%s must be a number in [0, 1] (got %r)" % (key, v))
+        return float(v)
+
+    shift_prob, max_bins, cut_prob, cut_t, cut_f = None, FEATURE_AUG_DEFAULTS["freq_shift_max_bins"], None, 0.0, 0.0
+    if shift_on:
+        shift_prob = prob("freq_shift_prob")
+        max_bins = aug.get("freq_shift_max_bins", max_bins)
+        if isinstance(max_bins, bool) or not isinstance(max_bins, int) or not 1 <= max_bins <= 63:
+            raise ValueError("aug_config.freq_shift_max_bins must be an integer in 1..63 (got %r)" % (max_bins,))
+    if cut_on:
+        cut_prob = prob("cutout_prob")
+        cut_t, cut_f = number("cutout_time_param"), number("cutout_freq_param")
+        for key, v in (("cutout_time_param", cut_t), ("cutout_freq_param", cut_f)):
+            if v < 0:
+                raise ValueError("aug_config.%s must be >= 0 (got %r)" % (key, v))
+    return shift_prob, int(max_bins), cut_prob, float(cut_t), float(cut_f)
+
+
+def draw_feature_aug(rnd, config, t, f):
+    """The LAST draws of one training item (after its rotation or swap, SpecAug table and mixing draws), from ``rnd`` (the
+    dataset's ``random`` module), for features of ``t`` frames and ``f`` bins -> (cutout row [t0, t1, f0, f1], shift).  The shift,
+    if enabled: ``random() < prob``, then the size 1 + min(int(random() * max_bins), max_bins - 1), then the sign (negative when
+    ``random() < 0.5``).  The cutout, if enabled: ``random() < prob``, then the frame range and the bin range by ``SpecAug._range``'s
+    formula (value = U * param, start = U * (size - value), [int(start), int(start + value))).  One helper for ``FoaDataset`` and
+    both device corpora: the same seed draws the same tables on every training path."""
+    shift_prob, max_bins, cut_prob, cut_t, cut_f = config
+    shift, row = 0, [0, 0, 0, 0]
+    if shift_prob is not None and rnd.random() < shift_prob:
+        shift = 1 + min(int(rnd.random() * max_bins), max_bins - 1)
+        if rnd.random() < 0.5:
+            shift = -shift
+    if cut_prob is not None and rnd.random() < cut_prob:
+        for k, (param, size) in enumerate(((cut_t, t), (cut_f, f))):
+            value = rnd.random() * param
+            start = rnd.random() * (size - value)
+            row[2 * k], row[2 * k + 1] = int(start), int(start + value)
+    return row, shift
+
+
+def feature_aug_table(spec, cutout, shift):
+    """One item's table int32 (G + 2, 4): ``spec`` (G, 4) (the SpecAug draw, or zeros), the cutout row, {shift, 0, 0, 0}."""
+    return torch.cat([spec.to(torch.int32).reshape(-1, 4), torch.tensor([list(cutout), [int(shift), 0, 0, 0]], dtype=torch.int32)], 0)
+
+
+def apply_feature_aug_host(feat, table, groups, shift_groups):
+    """The definition of ``adyolo_feat_augment`` in NumPy (exact: data movement and zero fill).  feat (B, T, F, C) float32, table
+    int32 (B, G + 2, 4), groups G pairs (q0, q1) of float4 quads, shift_groups one bool per group -> new array.  Per sample, in
+    this order: (1) shift: s = clamp(table[b, G + 1, 0], -(F - 1), F - 1); if s != 0 every channel of a group with
+    ``shift_groups[g]`` moves along the bin axis, out[t, f] = in[t, src(f)], u = f - s, src = -u (u < 0), 2 (F - 1) - u (u > F - 1),
+    u otherwise -- ``np.pad(mode="reflect")`` and a crop (a channel in several shifting groups moves once); (2) the SpecAug
+    stripes of rows 0..G-1 as ``adyolo_mask_groups``: frames [t0, t1) x all bins and bins [f0, f1) x all frames of the group's
+    channels, t0 = clamp(., 0, T), t1 = clamp(., t0, T), likewise the bins; (3) cutout: row G = {t0, t1, f0, f1}, clamped the same
+    way, zeroes [t0, t1) x [f0, f1) in ALL channels; an empty range in either direction masks nothing."""
+    import numpy as np
+    feat = feat.detach().cpu().numpy() if isinstance(feat, torch.Tensor) else np.asarray(feat)
+    table = table.detach().cpu().numpy() if isinstance(table, torch.Tensor) else np.asarray(table)
+    out = np.array(feat, dtype=np.float32, copy=True)
+    nb, t, f, c = out.shape
+    g = len(groups)
+    if table.shape != (nb, g + 2, 4) or len(shift_groups) != g:
+        raise ValueError("apply_feature_aug_host: table %s with %d groups, expected (%d, %d, 4)" % (table.shape, g, nb, g + 2))
+
+    def clamp(lo, hi, size):
+        lo = min(max(int(lo), 0), size)
+        return lo, min(max(int(hi), lo), size)
+
+    bins = np.arange(f)
+    for b in range(nb):
+        s = min(max(int(table[b, g + 1, 0]), -(f - 1)), f - 1)
+        if s != 0:
+            u = bins - s
+            src = np.where(u < 0, -u, np.where(u > f - 1, 2 * (f - 1) - u, u))
+            moving = np.zeros(c, dtype=bool)
+            for (q0, q1), on in zip(groups, shift_groups):
+                if on:
+                    moving[4 * q0:4 * q1] = True
+            out[b][:, :, moving] = feat[b][:, src][:, :, moving]
+        for (q0, q1), row in zip(groups, table[b, :g]):
+            t0, t1 = clamp(row[0], row[1], t)
+            f0, f1 = clamp(row[2], row[3], f)
+            out[b, t0:t1, :, 4 * q0:4 * q1] = 0.0
+            out[b, :, f0:f1, 4 * q0:4 * q1] = 0.0
+        t0, t1 = clamp(table[b, g, 0], table[b, g, 1], t)
+        f0, f1 = clamp(table[b, g, 2], table[b, g, 3], f)
+        out[b, t0:t1, f0:f1, :] = 0.0
+    return out
 
 
 def swap_audio(audio, comb_nos):

@@ -284,7 +284,8 @@ class _CorpusBase:
     __len__ = FoaDataset.__len__
 
     def _setup(self, host_corpus, params, device, rank, world):
-        from .augmentations import MIC_SWAP_COMBS, SpecAug, channel_swap_enabled, mic_swap_source, time_mix_config
+        from .augmentations import (MIC_SWAP_COMBS, SpecAug, channel_swap_enabled, feature_aug_config, mic_swap_source,
+                                    time_mix_config)
         self.host = hc = host_corpus
         self.device = torch.device(device)
         self._copy, self._os, self._random = copy, os, random
@@ -298,6 +299,7 @@ class _CorpusBase:
         self.mic_src = ops.corpus_mic_table({k: mic_swap_source(k) for k in MIC_SWAP_COMBS}) if self.swap else None
         self.specaug = SpecAug(params, False)
         self.mix = time_mix_config(params)    # time-domain mixing: None or (prob, gain lo, gain hi) (ValueError: a bad key)
+        self.feat_aug = feature_aug_config(params)        # frequency shift / cutout: None or the parsed keys (ValueError: a bad key)
         self.batch_size = int(params["train_config"]["batch_size"])
         self.n_samples, self.n_label_frames = hc.window, hc.window // hc.hop_label
         self.max_events = hc.max_events
@@ -328,16 +330,20 @@ class _CorpusBase:
     # ---------------------------------------------------------------------------------------------------------- batches
     def draw(self, indices):
         """The host half of a batch: ``FoaDataset.__getitem__``'s ``random`` draws item by item (rotation or channel swap, then
-        SpecAug) and the item table -> (items int64 (B, 8), spec int32 (B, 2, 4) or None), host arrays.  With
+        SpecAug) and the item table -> (items int64 (B, 8), spec int32 (B, 2, 4) or None), host arrays; with
+        ``aug_config.freq_shift_augment`` / ``cutout_augment`` spec is int32 (B, 4, 4): the SpecAug rows (zeros with ``spec_augment``
+        off), the cutout row, {shift, 0, 0, 0} (``augmentations.draw_feature_aug``, the last draws of every item).  With
         ``aug_config.time_mix_augment`` the item's mixing draws follow (``augmentations.draw_time_mix``) and a third element is
         returned: mates int64 (B, 8), the mate chunk as an item row with its own combination and the float32 bits of the gain in
         word 6, offset -1 where the item is unmixed."""
-        from .augmentations import MIC_SWAP_COMBS, draw_time_mix
+        from .augmentations import MIC_SWAP_COMBS, draw_feature_aug, draw_time_mix
         from .features import HOP, N_MELS
         names = [self.filelist[i] for i in indices]
         b = len(names)
         items = np.zeros((b, ops.CORPUS_ITEM_WORDS), dtype=np.int64)
-        spec = np.zeros((b, 2, 4), dtype=np.int32) if self.specaug.apply_augment else None
+        spec = None
+        if self.specaug.apply_augment or self.feat_aug is not None:
+            spec = np.zeros((b, 2 if self.feat_aug is None else 4, 4), dtype=np.int32)
         mates = None
         if self.mix is not None:
             mates = np.zeros((b, ops.CORPUS_ITEM_WORDS), dtype=np.int64)
@@ -350,8 +356,8 @@ class _CorpusBase:
                 comb = int(self._random.uniform(0, 16))                       # augmentations.py:76, as in __getitem__
             elif self.swap:
                 comb = MIC_SWAP_COMBS[int(self._random.uniform(0, 8))]        # as in __getitem__: one draw
-            if spec is not None:
-                spec[j] = self.specaug.draw_groups(1, self.n_samples // HOP, N_MELS, 2)[0].numpy()
+            if self.specaug.apply_augment:
+                spec[j, :2] = self.specaug.draw_groups(1, self.n_samples // HOP, N_MELS, 2)[0].numpy()
             items[j] = (off, f_off, ev_lo, ev_n, comb, rec, 0, 0)
             if mates is not None:
                 drawn = draw_time_mix(self._random, self.mix, self.total_filelist, name,
@@ -362,20 +368,24 @@ class _CorpusBase:
                     m_lo, m_n = self.host.chunk_events[mate]
                     mates[j] = (m_off, m_f_off, m_lo, m_n, -1 if m_comb is None else m_comb, m_rec,
                                 int(np.float32(gain).view(np.uint32)), 0)
+            if self.feat_aug is not None:
+                spec[j, 2], spec[j, 3, 0] = draw_feature_aug(self._random, self.feat_aug, self.n_samples // HOP, N_MELS)
         if mates is not None:
             return items, spec, mates
         return items, spec
 
     def _upload(self, drawn):
         """One H2D copy of the item table (+ SpecAug tables) through a double-buffered page-locked buffer
-        -> (items int64 (B, 8), spec int32 (B, 2, 4) or None) on the device; with mates in ``drawn`` they travel in the same
+        -> (items int64 (B, 8), spec int32 (B, rows, 4) or None; rows = 2, or 4 with the frequency-shift / cutout rows) on the
+        device; with mates in ``drawn`` they travel in the same
         copy, behind the items, and come back as a third element."""
         items, spec = drawn[0], drawn[1]
         mates = drawn[2] if len(drawn) > 2 else None
         b = items.shape[0]
         n_i = b * ops.CORPUS_ITEM_WORDS
         n_m = n_i if mates is not None else 0
-        n_words = n_i + n_m + (b * 4 if spec is not None else 0)        # 8 int32 of SpecAug per item = 4 int64 words
+        # 8 int32 of SpecAug per item = 4 int64 words; 16 int32 = 8 words with the frequency-shift / cutout rows
+        n_words = n_i + n_m + (spec.size // 2 if spec is not None else 0)
         slot = self._slot
         self._slot ^= 1
         key = (slot, n_words)
@@ -396,13 +406,13 @@ class _CorpusBase:
         ev.record(torch.cuda.current_stream(self.device))
         self._copied[slot] = ev
         dev_items = dev[:n_i].view(b, ops.CORPUS_ITEM_WORDS)
-        dev_spec = dev[n_i + n_m:].view(torch.int32).view(b, 2, 4) if spec is not None else None
+        dev_spec = dev[n_i + n_m:].view(torch.int32).view(b, spec.shape[1], 4) if spec is not None else None
         if mates is not None:
             return dev_items, dev_spec, dev[n_i:n_i + n_m].view(b, ops.CORPUS_ITEM_WORDS)
         return dev_items, dev_spec
 
     def batch(self, indices, audio_out=None, target_out=None):
-        """Items ``indices`` of ``get_filelist()`` -> (audio (B, n, 4) f32, target, spec (B, 2, 4) int32 or None), on the device,
+        """Items ``indices`` of ``get_filelist()`` -> (audio (B, n, 4) f32, target, spec (B, 2 | 4, 4) int32 or None), on the device,
         with no host synchronisation.  audio_out / target_out: write into these buffers (a recorded step's)."""
         return self.launch(self.draw(indices), audio_out, target_out)
 
@@ -464,7 +474,7 @@ class DeviceCorpus(_CorpusBase):
 
     def launch(self, drawn, audio_out=None, target_out=None):
         """The device half: one H2D copy of the item table (+ SpecAug tables), the gather and the label kernels.
-        -> (audio (B, n, 4) f32, target (cap, 7) f32, spec (B, 2, 4) int32 or None) on the device; no host sync."""
+        -> (audio (B, n, 4) f32, target (cap, 7) f32, spec (B, 2 | 4, 4) int32 or None) on the device; no host sync."""
         dev_items, dev_spec, *dev_mates = self._upload(drawn)
         b = dev_items.shape[0]
         audio = audio_out if audio_out is not None else \
@@ -528,7 +538,7 @@ class ClasswiseDeviceCorpus(_CorpusBase):
 
     def launch(self, drawn, audio_out=None, target_out=None):
         """The device half: one H2D copy of the item table (+ SpecAug tables), the gather and the label kernel.
-        -> (audio (B, n, 4) f32, target ``target_shape(B)`` f32, spec (B, 2, 4) int32 or None) on the device; no host sync."""
+        -> (audio (B, n, 4) f32, target ``target_shape(B)`` f32, spec (B, 2 | 4, 4) int32 or None) on the device; no host sync."""
         dev_items, dev_spec, *dev_mates = self._upload(drawn)
         b = dev_items.shape[0]
         shape = self.target_shape(b)

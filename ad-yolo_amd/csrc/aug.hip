@@ -68,6 +68,100 @@ __global__ __launch_bounds__(256) void mask_groups_kernel(float *__restrict__ fe
     }
 }
 
+// Frequency shift + SpecAug stripes + cutout on feat [B][T][64][C] in one pass, in place (adyolo_feat_augment).  table int32
+// [B][G + 2][4]: rows 0..G-1 the SpecAug ranges of mask_groups_kernel, row G the cutout rectangle {t0, t1, f0, f1} over ALL quads,
+// row G + 1 = {shift, -, -, -}.  Per sample, in this order: every quad of a group whose bit is set in shift_mask moves along the
+// bin axis by s = clamp(shift, -63, 63), out[t][f] = in[t][src(f)] with the vacated bins reflected (u = f - s; src = -u below 0,
+// 126 - u above 63); then the stripes; then the rectangle.  As all masks fill with 0 the result of an element is 0 where any mask
+// covers it and in[src(f)] elsewhere: a masked element is stored as zero and not loaded, an unshifted quad is only stored to
+// where it is masked (write-only, as mask_groups_kernel), and a sample with nothing to do costs no memory access.
+// Every range and the shift are clamped here: no table value reaches outside the tensor.
+// Work split: a row (b, t) of one quad is 64 float4, one per lane of a wave (F == 64 == the wave width).  One wave owns whole
+// rows, FA_ROWS adjacent ones per pass (their loads issued together); grid (blocks per sample, B), 4 waves per block, the rows
+// of [row_lo, row_hi) -- the frames any operation of this sample can touch -- dealt to the waves of the sample.
+constexpr int FA_ROWS = 4;
+
+__global__ __launch_bounds__(256) void feat_augment_kernel(float *feat, const int *__restrict__ table, MaskGroups groups, int G,
+                                                           unsigned shift_mask, int T, int C4) {
+    constexpr int F = 64;
+    const int b = blockIdx.y, lane = threadIdx.x & 63;
+    const int *tb = table + (size_t)b * (G + 2) * 4;
+    int gt0[ADYOLO_MASK_MAX_GROUPS], gt1[ADYOLO_MASK_MAX_GROUPS];
+    unsigned fm = 0;                                  // per lane: bit g = this lane's bin is in group g's bin stripe
+    unsigned live = 0;                                // bit g = group g has quads
+    int row_lo = T, row_hi = 0;
+#pragma unroll
+    for (int g = 0; g < ADYOLO_MASK_MAX_GROUPS; ++g) {
+        gt0[g] = gt1[g] = 0;
+        if (g < G && groups.q[g][1] > groups.q[g][0]) {
+            live |= 1u << g;
+            const int t0 = min(max(tb[g * 4 + 0], 0), T), t1 = min(max(tb[g * 4 + 1], t0), T);
+            const int f0 = min(max(tb[g * 4 + 2], 0), F), f1 = min(max(tb[g * 4 + 3], f0), F);
+            gt0[g] = t0;
+            gt1[g] = t1;
+            fm |= (unsigned)(lane >= f0 && lane < f1) << g;
+            if (f1 > f0) row_lo = 0, row_hi = T;                                  // a bin stripe crosses every frame
+            if (t1 > t0) row_lo = min(row_lo, t0), row_hi = max(row_hi, t1);
+        }
+    }
+    const int *cr = tb + G * 4;
+    int ct0 = min(max(cr[0], 0), T), ct1 = min(max(cr[1], ct0), T);
+    const int cf0 = min(max(cr[2], 0), F), cf1 = min(max(cr[3], cf0), F);
+    if (cf1 == cf0) ct1 = ct0;                                                    // empty in either direction: no rectangle
+    if (ct1 > ct0) row_lo = min(row_lo, ct0), row_hi = max(row_hi, ct1);
+    const bool fc = lane >= cf0 && lane < cf1;
+    const int s = min(max(tb[(G + 1) * 4], -(F - 1)), F - 1);
+    const unsigned shifting = s != 0 ? shift_mask & live : 0u;                    // the groups that move in this sample
+    if (shifting) row_lo = 0, row_hi = T;                                         // a moving quad: every frame of the sample
+    const int u = lane - s;
+    const int src = u < 0 ? -u : (u > F - 1 ? 2 * (F - 1) - u : u);               // in [0, 63] for |s| <= 63
+    float4 *base = reinterpret_cast<float4 *>(feat) + (size_t)b * T * F * C4;
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    const int wave = blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = gridDim.x * 4;
+    for (int t = row_lo + wave * FA_ROWS; t < row_hi; t += n_waves * FA_ROWS) {
+        unsigned tm[FA_ROWS];                                                     // bit g = row t + r is in group g's frame stripe
+        bool cut[FA_ROWS];                                                        // this lane's element of row t + r is in the rectangle
+#pragma unroll
+        for (int r = 0; r < FA_ROWS; ++r) {
+            tm[r] = 0;
+#pragma unroll
+            for (int g = 0; g < ADYOLO_MASK_MAX_GROUPS; ++g) tm[r] |= (unsigned)(t + r >= gt0[g] && t + r < gt1[g]) << g;
+            cut[r] = fc && t + r >= ct0 && t + r < ct1;
+        }
+        for (int q = 0; q < C4; ++q) {
+            unsigned gm = 0;                                                      // the groups this quad belongs to
+#pragma unroll
+            for (int g = 0; g < ADYOLO_MASK_MAX_GROUPS; ++g)
+                gm |= (unsigned)(g < G && q >= groups.q[g][0] && q < groups.q[g][1]) << g;
+            const bool in_bins = (fm & gm) != 0;
+            if (gm & shifting) {
+                // In place.  Rows t .. t + FA_ROWS - 1 belong to this wave alone (no other wave, of this or any other block,
+                // loads or stores them), and a row of one quad is 64 float4, one per lane.  All 64 lanes load in[src(f)] of a
+                // row in one wave-wide instruction BEFORE any lane stores to f: the stores take their data from the registers
+                // the loads fill, so they wait for them, and the wave barrier keeps the compiler from moving the store of one
+                // lane above the load of another.  A row is never split across waves, and the tensor is reached through this
+                // one pointer only (no __restrict__ pair over the same buffer).
+                float4 v[FA_ROWS];
+#pragma unroll
+                for (int r = 0; r < FA_ROWS; ++r) {
+                    v[r] = z;
+                    if (t + r < row_hi && !((tm[r] & gm) != 0 || in_bins || cut[r]))
+                        v[r] = base[((size_t)(t + r) * F + src) * C4 + q];
+                }
+                __builtin_amdgcn_wave_barrier();
+#pragma unroll
+                for (int r = 0; r < FA_ROWS; ++r)
+                    if (t + r < row_hi) base[((size_t)(t + r) * F + lane) * C4 + q] = v[r];
+            } else {                                                              // write-only: the masked elements
+#pragma unroll
+                for (int r = 0; r < FA_ROWS; ++r)
+                    if (t + r < row_hi && ((tm[r] & gm) != 0 || in_bins || cut[r]))
+                        base[((size_t)(t + r) * F + lane) * C4 + q] = z;
+            }
+        }
+    }
+}
+
 // per-column sum / sum of squares / max / min of a [rows][cols] matrix, stage 1: one partial row per workgroup
 // part [4][nblk][cols]
 __global__ __launch_bounds__(256) void colstats_partial_kernel(const float *__restrict__ a, float *__restrict__ part,
@@ -146,6 +240,31 @@ extern "C" int adyolo_mask_groups(float *feat, const int *ranges, int B, int G, 
     hipLaunchKernelGGL(mask_groups_kernel, dim3((unsigned)gx, (unsigned)(B * G)), dim3(256), 0, as_stream(stream), feat, ranges,
                        groups, G, T, F, C4);
     return check_launch("mask_groups");
+}
+
+// frequency shift + SpecAug stripes + cutout, in place: table [B][G + 2][4] on the device (feat_augment_kernel)
+extern "C" int adyolo_feat_augment(float *feat, const int *table, int B, int G, int T, int F, int C, const int *group_quads,
+                                   unsigned shift_mask, void *stream) {
+    ADYOLO_REQUIRE(feat && table && group_quads && B > 0 && B < 65536 && G > 0 && G <= ADYOLO_MASK_MAX_GROUPS && T > 0 && F > 0 &&
+                   C > 0 && C % 4 == 0 && (long)T * F * (C / 4) < (1L << 31), ADYOLO_EINVAL, "feat_augment: bad arguments");
+    ADYOLO_REQUIRE(((uintptr_t)feat & 15) == 0 && ((uintptr_t)table & 3) == 0, ADYOLO_EINVAL, "feat_augment: misaligned buffers");
+    ADYOLO_REQUIRE((shift_mask >> G) == 0, ADYOLO_EINVAL, "feat_augment: shift_mask 0x%x has bits above the %d groups", shift_mask, G);
+    ADYOLO_REQUIRE(F == 64, ADYOLO_ENOSUP, "feat_augment: F = %d (a row of 64 mel bins is one wave; no other width)", F);
+    const int C4 = C / 4;
+    MaskGroups groups{};
+    for (int g = 0; g < G; ++g) {
+        const int q0 = group_quads[2 * g], q1 = group_quads[2 * g + 1];
+        ADYOLO_REQUIRE(0 <= q0 && q0 <= q1 && q1 <= C4, ADYOLO_EINVAL, "feat_augment: group %d quads [%d,%d) outside [0,%d]", g, q0,
+                       q1, C4);
+        groups.q[g][0] = q0;
+        groups.q[g][1] = q1;
+    }
+    // FA_ROWS rows per wave and pass, 4 waves per block: two passes per wave (75 blocks per sample at T = 2400), at most 128 blocks
+    int gx = cdiv(T, 4L * FA_ROWS * 2);
+    gx = gx < 1 ? 1 : (gx > 128 ? 128 : gx);
+    hipLaunchKernelGGL(feat_augment_kernel, dim3((unsigned)gx, (unsigned)B), dim3(256), 0, as_stream(stream), feat, table, groups,
+                       G, shift_mask, T, C4);
+    return check_launch("feat_augment");
 }
 
 // one group over all quads: ranges [B][4] is the table [B][1][4]

@@ -253,7 +253,10 @@ class FoaDataset(torch.utils.data.Dataset):
     audio is permuted by ``swap_audio`` instead of rotated.  With ``aug_config.time_mix_augment`` (training splits) the item ends in
     one more element, a dict {"mate_pcm": int16 (T, 4) or None, "mate_comb": int, "gain": float}: the chunk summed into this one
     by ``ops.audio_mix`` (None: the item is not mixed), and ``label_rows`` encode ``augmentations.merge_labels`` of both chunks'
-    labels, each under its own combination.  Normalisation, rotation of the audio and the
+    labels, each under its own combination.  With ``aug_config.freq_shift_augment`` or ``cutout_augment`` (training splits) the
+    table is int32 (4, 4) instead, in the same tuple slot: rows 0-1 the SpecAug draw (zeros with ``spec_augment`` off), row 2 the
+    cutout rectangle, row 3 {shift, 0, 0, 0} -- ``augmentations.draw_feature_aug``, the last draws of the item; no label moves.
+    Normalisation, rotation of the audio and the
     features run on the GPU (``AudioStager`` -> ``rotate_audio`` -> ``FeatureExtractor``); the label half of the rotation
     and the label encoding stay here on the host, as in the reference's DataLoader workers.  ``label_rows``: the AD-YOLO row
     list, or for ``seddoa | masked-seddoa | accdoa | adpit`` the dense ``ClasswiseLabelEncoder`` tensor (T', ...)."""
@@ -306,6 +309,9 @@ class FoaDataset(torch.utils.data.Dataset):
         self.specaug = SpecAug(params, is_valid)            # spec_augment on and not a validation split: a mask table per item
         mix = time_mix_config(params)                       # ValueError: time_mix_prob / time_mix_gain_db out of range
         self.mix = mix if set_type == "train" and not is_valid else None
+        from .augmentations import feature_aug_config
+        feat_aug = feature_aug_config(params)               # ValueError: a freq_shift_* / cutout_* key out of range
+        self.feat_aug = feat_aug if set_type == "train" and not is_valid else None
         if self.loss_nm == "adyolo":
             self.encoder = YoloLabelEncoder(params)
         elif self.loss_nm in CLASSWISE_LABELS:
@@ -395,6 +401,11 @@ class FoaDataset(torch.utils.data.Dataset):
                 label = merge_labels(label, mate_label)
                 mixed = {"mate_pcm": np.ascontiguousarray(mate_pcm, dtype=np.int16), "mate_comb": int(mate_comb or 0),
                          "gain": float(gain)}
+        if self.feat_aug is not None:           # frequency shift / cutout: the very last draws; the table grows to (4, 4)
+            from .augmentations import draw_feature_aug, feature_aug_table
+            from .features import HOP, N_MELS
+            cutout, shift = draw_feature_aug(self._random, self.feat_aug, pcm.shape[0] // HOP, N_MELS)
+            spec = feature_aug_table(spec if spec is not None else torch.zeros(2, 4, dtype=torch.int32), cutout, shift)
         nb_label_frames = pcm.shape[0] // self.hop_label
         if self.loss_nm == "adyolo":
             target = self.encoder.get_yolo_label(label, nb_label_frames)
@@ -416,7 +427,7 @@ def audio_collate_fn(batch):
     """list of FoaDataset items -> (pcm int16 (B, T, 4) host tensor, comb_nos list, target).  AD-YOLO: target (M, 7) float32
     rows built exactly like ``collate_fn`` (datasets.py:164-184); class-wise losses: the dense labels stacked to (B, T', ...),
     like the default collate the reference uses for them.  Items with SpecAug tables (4-tuples) -> a 4th element, the tables
-    stacked to int32 (B, 2, 4).  Items of a mixing dataset (``aug_config.time_mix_augment``: a trailing dict) -> one trailing dict
+    stacked to int32 (B, 2, 4) (or (B, 4, 4): the tables of the frequency-shift / cutout augmentation).  Items of a mixing dataset (``aug_config.time_mix_augment``: a trailing dict) -> one trailing dict
     {"mate_pcm": int16 (B, T, 4), zeros where the item is unmixed, "mate_combs": list, "gains": float32 (B,), "mixed": bool (B,)}."""
     mix = None
     if isinstance(batch[0][-1], dict):

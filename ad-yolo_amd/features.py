@@ -96,6 +96,8 @@ class FeatureExtractor:
 
     # SpecAug groups of the 8-channel pixel, in float4 quads: log-mel W,Y,Z,X | intensity vector y,z,x + the zero channel 7
     SPEC_GROUPS = ((0, 1), (1, 2))
+    # frequency-shift augmentation: log-mel and intensity vector move along the mel axis together
+    SHIFT_GROUPS = (True, True)
 
     def __call__(self, audio, channels_last8=True, chunk_offsets=None, chunk_samples=None, validate_offsets=True,
                  spec_ranges=None):
@@ -106,6 +108,10 @@ class FeatureExtractor:
         the log-mel group (channels 0-3) and the intensity-vector group (4-6), e.g. ``SpecAug.draw_groups(B, T, 64, 2)``:
         the normalised features are masked with 0 in the same call (``ops.mask_groups_``, one more launch on the stream),
         as the reference masks MEL and IV each with its own draw (datasets.py:158-159).  Channels-last only.
+        An int32 (B, 4, 4) tensor is the table of the frequency-shift and cutout augmentation: rows 0-1 as above, row 2 the
+        cutout rectangle {t0, t1, f0, f1} zeroed in all channels, row 3 = {shift in mel bins, 0, 0, 0} (both groups move, the
+        vacated bins reflected); shift, stripes and rectangle in this order on the normalised features, in one launch
+        (``ops.feat_augment_``; definition: ``augmentations.apply_feature_aug_host``).
 
         chunk_offsets (int64 tensor on the device, sample offsets into the flattened (B * n_samples) audio) with
         chunk_samples: features of the CHUNKS ``audio.view(-1, 4)[off : off + chunk_samples]`` instead (one output row
@@ -145,7 +151,7 @@ class FeatureExtractor:
                   _p(self.sc_mean), _p(self.sc_rstd), _p(out), _p(chan_max), b, n, layout, st)
         _lib.call("adyolo_feat_finish", _p(out), _p(chan_max), _p(self.sc_mean), _p(self.sc_rstd), b, t, layout, st)
         if spec_ranges is not None:
-            _mask(out, spec_ranges, self.SPEC_GROUPS)
+            _mask(out, spec_ranges, self.SPEC_GROUPS, self.SHIFT_GROUPS)
         return out
 
     @staticmethod
@@ -168,10 +174,15 @@ class MicFeatureExtractor:
 
     ``spec_ranges`` (int32 (B, 2, 4), host or device): SpecAug as in ``FeatureExtractor``, one mask per feature family -- group 0
     the log-mel channels 0-3, group 1 the GCC-PHAT channels 4-9 (with the zero channels 10-11 of its quads).  The reference has no
-    MIC format; this grouping restates its one-draw-per-feature-family rule (datasets.py:158-159) for the MIC feature set."""
+    MIC format; this grouping restates its one-draw-per-feature-family rule (datasets.py:158-159) for the MIC feature set.
+    An int32 (B, 4, 4) tensor adds the cutout rectangle (row 2, all channels) and the frequency shift (row 3), as in
+    ``FeatureExtractor``; only the log-mel channels shift (``SHIFT_GROUPS``), the GCC-PHAT quads keep their bits."""
 
     N_FEATURES = 10
     SPEC_GROUPS = ((0, 1), (1, 3))
+    # frequency-shift augmentation: the log-mel quad alone.  The bin axis of the GCC-PHAT channels is a LAG axis: moving it would
+    # move the direction of arrival while the labels stay.
+    SHIFT_GROUPS = (True, False)
 
     def __init__(self, scaler=None, device="cuda:0"):
         mel_scaler = None
@@ -203,17 +214,27 @@ class MicFeatureExtractor:
         _lib.call("adyolo_feat_gcc_phat", _p(audio), _p(None), _p(self.k1.twiddle), _p(self.gcc_mean), _p(self.gcc_rstd),
                   _p(out), b, n, 32, 4, _stream())
         if spec_ranges is not None:
-            _mask(out, spec_ranges, self.SPEC_GROUPS)
+            _mask(out, spec_ranges, self.SPEC_GROUPS, self.SHIFT_GROUPS)
         if channels_last:
             return out
         return out[..., :10].permute(0, 3, 1, 2).contiguous()
 
 
-def _mask(out, spec_ranges, groups):
-    """SpecAug masks of (B, 2, 4) int32 ranges (host or device) on the channels-last features ``out``, stream-ordered."""
+def _mask(out, spec_ranges, groups, shift_groups=None):
+    """The per-item int32 table (host or device) on the channels-last features ``out``, stream-ordered.  (B, G, 4), G the number
+    of groups: SpecAug masks (``ops.mask_groups_``).  (B, G + 2, 4): frequency shift of the ``shift_groups``, SpecAug masks and
+    cutout in one launch (``ops.feat_augment_``).  Any other shape raises."""
+    g = len(groups)
     if not isinstance(spec_ranges, torch.Tensor) or spec_ranges.dtype != torch.int32:
-        raise _lib.AdyoloHipError("spec_ranges must be an int32 tensor (B, %d, 4)" % len(groups))
-    ops.mask_groups_(out, spec_ranges.to(out.device, non_blocking=True).contiguous(), groups)
+        raise _lib.AdyoloHipError("spec_ranges must be an int32 tensor (B, %d, 4) or (B, %d, 4)" % (g, g + 2))
+    shape, b = tuple(spec_ranges.shape), out.shape[0]
+    if shape == (b, g, 4):
+        ops.mask_groups_(out, spec_ranges.to(out.device, non_blocking=True).contiguous(), groups)
+    elif shape == (b, g + 2, 4) and shift_groups is not None:
+        ops.feat_augment_(out, spec_ranges.to(out.device, non_blocking=True).contiguous(), groups, shift_groups)
+    else:
+        raise _lib.AdyoloHipError("spec_ranges must be an int32 tensor (%d, %d, 4) or (%d, %d, 4) (got %s)"
+                                  % (b, g, b, g + 2, shape))
 
 
 def load_scaler_npz(path):

@@ -74,8 +74,9 @@ class StepGraphs:
     call at a new (audio shape, target capacity[, masked]) runs eagerly (lazy initialisations, allocator warm-up -- and it IS a
     real step, nothing is discarded), the second records the graph, every call from then on copies the inputs into the graph's
     static buffers (skipped when the caller already works in them: ``static_inputs``) and replays it.  A step with SpecAug
-    tables (int32 (B, 2, 4)) is recorded with a static device buffer for them, refreshed before every replay like the audio:
-    the masks change from step to step without a new capture."""
+    tables (int32 (B, 2, 4); (B, 4, 4) with the frequency-shift / cutout rows: a graph of its own, the shape is part of the key)
+    is recorded with a static device buffer for them, refreshed before every replay like the audio: the masks, shifts and
+    rectangles change from step to step without a new capture."""
 
     def __init__(self, trainer, warm_calls=1):
         self.trainer = trainer
@@ -207,7 +208,7 @@ class StepGraphs:
         tr = self.trainer
         target = target.to(torch.float32)
         if spec_ranges is not None and spec_ranges.dtype != torch.int32:
-            raise _lib.AdyoloHipError("spec_ranges must be an int32 tensor (B, 2, 4)")
+            raise _lib.AdyoloHipError("spec_ranges must be an int32 tensor (B, 2, 4) or (B, 4, 4)")
         key = self._key(audio, target, spec_ranges)
         sw = ops.switch_stamp()
         if sw != self.switches:                # ``ops.reload_thresholds()`` / ADYOLO_CONV_ALGO moved the dispatch: record again

@@ -2039,6 +2039,33 @@ def mask_groups_(feat, ranges, group_quads):
     return feat
 
 
+def feat_augment_(feat, table, group_quads, shift_groups):
+    """In-place frequency shift + SpecAug stripes + cutout of feat [B][T][64][C] in one launch (``adyolo_feat_augment``; the
+    definition is ``augmentations.apply_feature_aug_host``).  table int32 [B][G + 2][4] on the device: rows 0..G-1 the SpecAug
+    ranges of ``mask_groups_``, row G the cutout rectangle {t0, t1, f0, f1} over all channels, row G + 1 = {shift, 0, 0, 0}
+    (every value clamped by the kernel); group_quads G pairs (q0, q1) of float4 quads; shift_groups one bool per group (the
+    groups whose bin axis moves)."""
+    _chk(feat)
+    if feat.dim() != 4 or feat.shape[3] % 4 != 0:
+        raise _lib.AdyoloHipError("feat_augment_ needs feat (B, T, F, C) with C %% 4 == 0 (got %s)" % (tuple(feat.shape),))
+    b, t, f, c = feat.shape
+    gq = [(int(q0), int(q1)) for q0, q1 in group_quads]
+    g = len(gq)
+    if table.dtype != torch.int32 or not table.is_contiguous() or table.device != feat.device:
+        raise _lib.AdyoloHipError("feat_augment_ needs a contiguous int32 table on the device of feat")
+    if tuple(table.shape) != (b, g + 2, 4):
+        raise _lib.AdyoloHipError("feat_augment_: table must be (%d, %d, 4) (got %s)" % (b, g + 2, tuple(table.shape)))
+    if not 0 < g <= 8 or any(not 0 <= q0 <= q1 <= c // 4 for q0, q1 in gq):
+        raise _lib.AdyoloHipError("feat_augment_: 1..8 groups of quads within [0, %d] (got %s)" % (c // 4, gq))
+    shift = [bool(s) for s in shift_groups]
+    if len(shift) != g:
+        raise _lib.AdyoloHipError("feat_augment_: shift_groups must have one entry per group (%d; got %d)" % (g, len(shift)))
+    quads = (ctypes.c_int32 * (2 * g))(*[q for pair in gq for q in pair])
+    _c("adyolo_feat_augment", _p(feat), _p(table), b, g, t, f, c, ctypes.cast(quads, ctypes.c_void_p),
+       sum(1 << i for i, s in enumerate(shift) if s), _stream())
+    return feat
+
+
 def colstats(a2d):
     """[rows][cols] fp32 -> float64 [4][cols]: column sum, sum of squares, max, min."""
     _chk(a2d)

@@ -540,7 +540,8 @@ class TrainStep:
     """One data-parallel optimisation step on raw audio.
 
     step(audio (B, n_samples, 4) float32 on the GPU, target (M,7), spec_ranges=None) -> loss tensor (1,) on the device (no
-    host sync).  spec_ranges: SpecAug tables int32 (B, 2, 4) (``FoaDataset`` items with ``spec_augment`` on), handed to the
+    host sync).  spec_ranges: SpecAug tables int32 (B, 2, 4) (``FoaDataset`` items with ``spec_augment`` on) or the (B, 4, 4) tables
+    of the frequency-shift / cutout augmentation (``aug_config.freq_shift_augment`` / ``cutout_augment``), handed to the
     feature extractor, which masks its output in the same call; None leaves the step exactly as without SpecAug (the
     feature callable is then called without the keyword).
 
@@ -723,7 +724,7 @@ class _EpochLoss:
 
 def train_one_epoch_audio(params: dict, dataloader, trainer, stager=None, rotate=True):
     """The raw-audio epoch: ``dataloader`` yields ``audio_collate_fn`` batches (pcm int16 (B,T,4), comb_nos, target[, SpecAug
-    tables (B,2,4)]); each is staged to the GPU (int16 over PCIe on a side stream, double-buffered), converted, rotated (with
+    tables (B,2,4), or (B,4,4) with the frequency-shift / cutout rows]); each is staged to the GPU (int16 over PCIe on a side stream, double-buffered), converted, rotated (with
     ``aug_config.channel_swap_augment``: its channels permuted, ``swap_audio``; with ``aug_config.time_mix_augment``: the batch's
     trailing dict of mates staged, moved by their own combinations and summed in by ``ops.audio_mix``) and handed with its
     tables to ``TrainStep.step``

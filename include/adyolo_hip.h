@@ -552,6 +552,17 @@ int  adyolo_classwise_select(const float *dec, float *ws, float *rows, int *fram
  *                        safe); group_quads: HOST int32 [G][2] = {q0, q1}, 0 <= q0 <= q1 <= C/4, G <= ADYOLO_MASK_MAX_GROUPS
  *                        (passed by value: capturable in a hipGraph).  Writes only the masked elements; no sync, no memset.
  *                        adyolo_mask_ranges is its one-group case (group_quads {0, C/4}).
+ *   adyolo_feat_augment: frequency shift, the SpecAug stripes of adyolo_mask_groups and one cutout rectangle on feat
+ *                        [B][T][64][C] in ONE launch, in place (no second feature-sized buffer).  table: DEVICE int32
+ *                        [B][G + 2][4]; rows 0..G-1 = the ranges of adyolo_mask_groups, row G = the rectangle {t0, t1, f0, f1}
+ *                        zeroed in ALL C channels (empty in either direction: nothing), row G + 1 = {s, 0, 0, 0}.  Per sample,
+ *                        in this order: with s' = clamp(s, -63, 63) != 0 every quad of a group g with bit g of shift_mask set
+ *                        moves along the bin axis, out[t][f] = in[t][src(f)], u = f - s', src = -u (u < 0), 126 - u (u > 63),
+ *                        u otherwise (numpy.pad mode "reflect", cropped to 64 bins); then the stripes; then the rectangle.
+ *                        Fill value 0.  Every table value is clamped on the device (any value is safe); a sample with s' = 0
+ *                        is write-only (its masked elements), a masked element is never loaded.  group_quads as for
+ *                        adyolo_mask_groups (host, by value).  No allocation, no sync: capturable.  EINVAL: null / misaligned
+ *                        pointers, sizes as adyolo_mask_groups, shift_mask bits at or above G; ENOSUP: F != 64.
  *   adyolo_colstats:     per-column sum, sum of squares, max, min of a [rows][cols] fp32 matrix -> out [4][cols] float64
  *                        (train-set scaler statistics, src/preprocess.py:86-130); partial = [4][1024][cols] fp32 scratch
  * ---------------------------------------------------------------------------------------------- */
@@ -560,6 +571,8 @@ int adyolo_mask_ranges(float *feat, const int32_t *ranges, int B, int T, int F, 
 #define ADYOLO_MASK_MAX_GROUPS 8
 int adyolo_mask_groups(float *feat, const int32_t *ranges, int B, int G, int T, int F, int C, const int32_t *group_quads,
                        void *stream);
+int adyolo_feat_augment(float *feat, const int32_t *table, int B, int G, int T, int F, int C, const int32_t *group_quads,
+                        unsigned shift_mask, void *stream);
 int adyolo_colstats(const float *a, float *partial, double *out, long rows, int cols, void *stream);
 
 /* General strided convolution (channels-last) as an implicit GEMM on the fp32 MFMA, no column buffer (replaces nn.Conv2d

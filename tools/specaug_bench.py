@@ -6,10 +6,17 @@
   mask_ranges   adyolo_mask_ranges on (64, 2400, 64, 8) in each library given by --mask-lib (e.g. a build of the parent commit
                 and this one; default: the package's library), plus adyolo_mask_groups with the two FOA groups
 
+  feat_augment  (--shift and / or --cutout) adyolo_feat_augment on the FOA features (64, 2400, 64, 8) and the MIC features
+                (64, 800, 64, 32) next to adyolo_mask_groups on the same tensor: "stripes" = the worst-case SpecAug rows alone (no
+                sample shifted), "shift" = every sample shifted and nothing masked, "all" = every sample shifted under the
+                worst-case stripes and a 40 x 20 rectangle, "empty" = an all-zero table (the launch alone).  Each with its byte
+                model (read + write of the moving quads' unmasked elements, write of every masked element) as achieved GB/s.
+                The step then gets a third variant with the (B, 4, 4) tables.
+
 Tables are the worst case of the reference's configuration (hyp_augmentation.yaml: mask params 40): every sample and group
 masked with 40 frames and 40 bins.  Variants alternate inside each repeat; the median of the repeats is reported (ms per call).
 
-  python tools/specaug_bench.py [--reps 7] [--iters 20] [--mask-lib A.so --mask-lib B.so] [--json out.json]
+  python tools/specaug_bench.py [--reps 7] [--iters 20] [--shift] [--cutout] [--mask-lib A.so --mask-lib B.so] [--json out.json]
 """
 import argparse
 import ctypes
@@ -63,7 +70,75 @@ def bench_features(reps, iters):
     return timed(fns, reps, iters)
 
 
-def bench_step(reps, iters):
+def aug_tables(b, t, shift, cutout, stripes=True, seed=0, max_bins=5):
+    """(b, 4, 4) int32: the worst-case SpecAug rows (or zeros), a 40-frame x 20-bin rectangle for every sample (``cutout``) and a
+    shift of 1..max_bins bins either way for every sample (``shift``)."""
+    g = torch.Generator().manual_seed(1000 + seed)
+    tab = torch.zeros(b, 4, 4, dtype=torch.int32)
+    if stripes:
+        tab[:, :2] = worst_tables(b, t, seed=seed)
+    if cutout:
+        t0 = torch.randint(0, t - 40, (b,), generator=g)
+        f0 = torch.randint(0, 64 - 20, (b,), generator=g)
+        tab[:, 2] = torch.stack([t0, t0 + 40, f0, f0 + 20], -1).to(torch.int32)
+    if shift:
+        size = torch.randint(1, max_bins + 1, (b,), generator=g)
+        tab[:, 3, 0] = (size * (2 * torch.randint(0, 2, (b,), generator=g) - 1)).to(torch.int32)
+    return tab
+
+
+def model_bytes(tab, t, c4, groups, shift_groups):
+    """HBM bytes the table asks for: every masked element written (16 B per quad), every unmasked element of a moving quad read
+    and written."""
+    total = 0
+    for row in tab.tolist():
+        cut = torch.zeros(t, 64, dtype=torch.bool)
+        cut[row[2][0]:row[2][1], row[2][2]:row[2][3]] = True
+        in_group = [False] * c4
+        for (q0, q1), (t0, t1, f0, f1), moves in zip(groups, row[:2], shift_groups):
+            m = cut.clone()
+            m[t0:t1] = True
+            m[:, f0:f1] = True
+            masked = int(m.sum())
+            moving = moves and row[3][0] != 0
+            total += (q1 - q0) * 16 * (masked + (2 * (t * 64 - masked) if moving else 0))
+            for q in range(q0, q1):
+                in_group[q] = True
+        total += in_group.count(False) * 16 * int(cut.sum())
+    return total
+
+
+def bench_feat_augment(reps, iters, shift, cutout):
+    from adyolo_amd import ops
+    out = {}
+    for name, (b, t, c, groups, moves) in {"foa_64x60s": (64, 2400, 8, ((0, 1), (1, 2)), (True, True)),
+                                           "mic_64x20s": (64, 800, 32, ((0, 1), (1, 3)), (True, False))}.items():
+        feat = torch.randn(b, t, 64, c, device="cuda:0")
+        cases = {"empty": aug_tables(b, t, False, False, stripes=False),
+                 "stripes": aug_tables(b, t, False, False)}
+        if shift:
+            cases["shift"] = aug_tables(b, t, True, False, stripes=False)
+        if cutout:
+            cases["cutout"] = aug_tables(b, t, False, True, stripes=False)
+        cases["all"] = aug_tables(b, t, shift, cutout)
+        dev = {k: v.to("cuda:0") for k, v in cases.items()}
+        spec = dev["stripes"][:, :2].contiguous()
+        fns = {"mask_groups": lambda: ops.mask_groups_(feat, spec, groups)}
+        for k in cases:
+            fns["feat_augment[%s]" % k] = (lambda k=k: ops.feat_augment_(feat, dev[k], groups, moves))
+        for f in fns.values():
+            for _ in range(3):
+                f()
+        med, runs = timed(fns, reps, iters)
+        nbytes = {"mask_groups": model_bytes(cases["stripes"], t, c // 4, groups, (False, False))}
+        nbytes.update({"feat_augment[%s]" % k: model_bytes(v, t, c // 4, groups, moves) for k, v in cases.items()})
+        out[name] = {k: {"ms": med[k], "runs_ms": runs[k], "model_MB": round(nbytes[k] / 1e6, 1),
+                         "model_GBps": round(nbytes[k] / 1e6 / med[k], 1) if nbytes[k] else None} for k in fns}
+        del feat
+    return out
+
+
+def bench_step(reps, iters, shift=False, cutout=False):
     from adyolo_amd.datasets import synthetic_audio, synthetic_targets
     from adyolo_amd.features import FeatureExtractor
     from adyolo_amd.train import TrainStep
@@ -85,11 +160,18 @@ def bench_step(reps, iters):
         return tr.step(audio, target, spec_ranges=tables[k[0] % len(tables)])
 
     fns = {"plain": lambda: tr.step(audio, target), "masked": masked}
+    if shift or cutout:
+        tables4 = [aug_tables(b, t, shift, cutout, seed=s) for s in range(8)]
+
+        def augmented():
+            k[0] += 1
+            return tr.step(audio, target, spec_ranges=tables4[k[0] % len(tables4)])
+        fns["augmented"] = augmented
     for f in fns.values():
         for _ in range(4):                     # eager warm-up, capture, replays
             f()
     torch.cuda.synchronize()
-    assert tr.graphs is not None and tr.graphs.captures == 2, "expected one graph per variant"
+    assert tr.graphs is not None and tr.graphs.captures == len(fns), "expected one graph per variant"
     return timed(fns, reps, iters)
 
 
@@ -124,21 +206,29 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--mask-lib", action="append", default=[])
-    ap.add_argument("--only", choices=["features", "step", "mask_ranges"], action="append")
+    ap.add_argument("--only", choices=["features", "step", "mask_ranges", "feat_augment"], action="append")
+    ap.add_argument("--shift", action="store_true", help="the frequency-shift rows: feat_augment, and a third variant of the step")
+    ap.add_argument("--cutout", action="store_true", help="the cutout rows: feat_augment, and a third variant of the step")
     ap.add_argument("--json")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "specaug_bench needs the GPU"
     import adyolo_amd  # noqa: F401
     from adyolo_amd import _lib
     libs = a.mask_lib or [_lib.LIB_PATH]
-    only = a.only or ["features", "step", "mask_ranges"]
+    only = a.only or (["features", "step", "mask_ranges"] + (["feat_augment"] if a.shift or a.cutout else []))
     res = {"libs": libs}
     if "features" in only:
         res["features_64x60s_ms"], res["features_runs"] = bench_features(a.reps, a.iters)
     if "step" in only:
-        res["graph_step_16x20s_ms"], res["graph_step_runs"] = bench_step(a.reps, max(1, a.iters // 2))
+        res["graph_step_16x20s_ms"], res["graph_step_runs"] = bench_step(a.reps, max(1, a.iters // 2), a.shift, a.cutout)
     if "mask_ranges" in only:
         res["mask_64x60s_ms"], res["mask_runs"] = bench_mask_ranges(libs, a.reps, a.iters)
+    if "feat_augment" in only:
+        assert a.shift or a.cutout, "feat_augment needs --shift and / or --cutout"
+        res["feat_augment"] = bench_feat_augment(a.reps, a.iters, a.shift, a.cutout)
+        for name, rows in res["feat_augment"].items():
+            for k, v in rows.items():
+                print(name, k, v["ms"], "ms", v["model_MB"], "MB", v["model_GBps"], "GB/s")
     for k in ("features_64x60s_ms", "graph_step_16x20s_ms", "mask_64x60s_ms"):
         if k in res:
             print(k, res[k])

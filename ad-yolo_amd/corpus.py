@@ -29,6 +29,11 @@ reads the split ``FoaDataset(params, set_type, is_valid=True)`` reads into the s
 clip, and ``EvalDeviceCorpus`` uploads it once (audio, events, one item per clip) and makes each batch of
 ``test.test_epoch_corpus`` from a range of clips with no host data: the gather without rotation, then the AD-YOLO rows with the
 clips' row starts or the dense class-wise target (all five losses in one class).
+
+Inference on a folder of recordings of any length has the third pair: ``load_infer_split`` (or ``infer_split_from_arrays``)
+lays the recordings out the same way, without events, and ``InferDeviceCorpus`` cuts them into overlapping windows of one shape
+(``window_plan``) through a window table uploaded once; ``test.infer_epoch_corpus`` runs the windows in passes through one
+recorded graph, keeps each window's frames that have context on both sides and stitches them back onto the recordings' axes.
 """
 import copy
 import os
@@ -774,3 +779,219 @@ class EvalDeviceCorpus(_CorpusBase):
                                ws[b * max(me, 1):], self.status)
         row_start = ws[::max(me, 1)].contiguous()
         return audio, target, row_start
+
+
+# ------------------------------------------------------------------------------------------------------- windowed inference
+def window_plan(n_frames, window_frames, margin_frames):
+    """A recording of ``n_frames`` label frames cut into windows of ``window_frames`` that overlap so that every kept frame has
+    ``margin_frames`` of context on both sides -> [(start_frame, src_lo, dst_lo, n)] per window: the window starts at label frame
+    start_frame of the recording, and its frames [src_lo, src_lo + n) (window-local) are the recording's [dst_lo, dst_lo + n).
+
+    F <= Wf: one window (0, 0, 0, F).  Otherwise, with the stride S = Wf - 2 Mf, ceil((F - Wf) / S) + 1 windows: window k
+    starts at k S, the last one at F - Wf (tail-aligned: it ends with the recording and holds no padding); window 0 keeps
+    [0, Wf - Mf), a middle one [Mf, Wf - Mf), the last one from where the one before stopped up to F.  The kept ranges tile
+    [0, F) exactly once, in order.  ``ValueError`` unless Wf > 2 Mf >= 0."""
+    f, wf, mf = int(n_frames), int(window_frames), int(margin_frames)
+    if mf < 0 or wf <= 2 * mf:
+        raise ValueError("window_plan: a window of %d frames with a margin of %d (window_frames > 2 * margin_frames >= 0)" % (wf, mf))
+    if f < 0:
+        raise ValueError("window_plan: %d frames" % f)
+    if f <= wf:
+        return [(0, 0, 0, f)]
+    s = wf - 2 * mf
+    k_n = -(-(f - wf) // s) + 1
+    out = [(0, 0, 0, wf - mf)]
+    for k in range(1, k_n - 1):
+        out.append((k * s, mf, k * s + mf, s))
+    done = (k_n - 2) * s + wf - mf                       # where window K - 2 stopped (K = 2: window 0, at Wf - Mf)
+    start = f - wf
+    out.append((start, done - start, done, f - done))
+    return out
+
+
+def split_pass_rows(rows, counts, base_frame, frame_start):
+    """The host half of a windowed pass: rows (N, 5) [frame of the run, class, x, y, z] in frame order and counts (frames of the
+    run,) rows per frame (``select_device_rows`` on the stitched run), the run starting at ``base_frame`` on the axis of all
+    recordings laid end to end, frame_start (R + 1,) the first frame of each recording on that axis -> {recording: {frame of the
+    recording: [[class, x, y, z], ...]}}, frames ascending: ``group_rows`` split at the recording boundaries."""
+    counts = np.asarray(counts, dtype=np.int64).reshape(-1)
+    rows = np.asarray(rows, dtype=np.float32).reshape(-1, 5)
+    frame_start = np.asarray(frame_start, dtype=np.int64).reshape(-1)
+    if int(counts.sum()) != len(rows) or base_frame < 0 or base_frame + len(counts) > int(frame_start[-1]):
+        raise ValueError("split_pass_rows: %d rows, %d frame counts summing to %d, frames [%d, %d) of %d"
+                         % (len(rows), len(counts), int(counts.sum()), base_frame, base_frame + len(counts), int(frame_start[-1])))
+    ends = np.cumsum(counts)
+    frames = np.flatnonzero(counts)
+    glob = frames + int(base_frame)
+    rec = np.searchsorted(frame_start, glob, "right") - 1
+    local = glob - frame_start[rec]
+    vals = rows[:, 1:].tolist()
+    out = {}
+    for r, f, s, e in zip(rec.tolist(), local.tolist(), (ends[frames] - counts[frames]).tolist(), ends[frames].tolist()):
+        out.setdefault(r, {})[f] = vals[s:e]
+    return out
+
+
+def infer_split_from_arrays(names, arrays, params):
+    """Recordings held in memory (int16 (n, 4) each) -> the ``HostCorpus`` ``load_infer_split`` returns: every recording whole in
+    one int16 stream, each on a 16-frame boundary, ``lengths``, no events.  ``ValueError`` naming the recording for anything
+    that is not int16 (n, 4)."""
+    names = [str(n) for n in names]
+    arrays = list(arrays)
+    if len(names) != len(arrays):
+        raise ValueError("infer_split_from_arrays: %d names for %d arrays" % (len(names), len(arrays)))
+    dc = params["data_config"]
+    hop = int(dc.get("sr", 24000) * dc.get("label_hop_len_s", 0.1))                 # FoaDataset.hop_label
+    for name, a in zip(names, arrays):
+        if getattr(a, "dtype", None) != np.int16 or a.ndim != 2 or a.shape[1] != 4:
+            raise ValueError("infer_split_from_arrays: %s holds %s %s, expected int16 (n, 4)"
+                             % (name, getattr(a, "dtype", type(a).__name__), tuple(getattr(a, "shape", ()))))
+    lengths = np.asarray([a.shape[0] for a in arrays], dtype=np.int64).reshape(-1)
+    rec_start = np.zeros(len(names) + 1, dtype=np.int64)
+    pos = 0
+    for i, n in enumerate(lengths.tolist()):
+        rec_start[i] = pos
+        pos += (n + 15) // 16 * 16
+    rec_start[-1] = pos
+    audio = np.zeros((max(pos, 16), 4), dtype=np.int16)
+    for i, a in enumerate(arrays):
+        audio[int(rec_start[i]):int(rec_start[i]) + int(lengths[i])] = a
+    hc = HostCorpus()
+    hc.wav_pth, hc.csv_pth, hc.set_type = None, None, "infer"
+    hc.rank, hc.world = 0, 1
+    hc.audio = audio
+    hc.rec_names, hc.rec_start, hc.lengths = list(names), rec_start, lengths
+    hc.events = np.zeros((0, _EV_COLS))
+    hc.ev_start = np.zeros(len(names) + 1, dtype=np.int64)
+    hc.filelist = hc.total_filelist = list(names)
+    hc.hop_label, hc.max_events = hop, 0
+    hc.window = int((lengths // 600).max() * 600) if len(names) else 0
+    hc.stride, hc.window_frames = 0, hc.window // hop
+    hc.chunks, hc.chunk_events = {}, {}
+    return hc
+
+
+def load_infer_split(params, rank=None, world=None, verify="sample", files=None):
+    """The int16 4-channel WAV files under ``params['args']['infer_pth']`` read once -> ``HostCorpus`` (the layout of
+    ``load_eval_split`` without events).  The file list is ``FoaDataset(params, 'infer')``'s: ``os.listdir`` order on one rank,
+    ``sorted(...)[rank::world]`` under data parallelism.  files: names (without ``.wav``) of the recordings to load, in the
+    order of that list -- a folder that does not fit HBM is taken in parts; a name the list does not hold raises.
+    ``ValueError`` naming the file for anything that is not int16 (n, 4).  verify: as in ``load_eval_split``."""
+    from scipy.io import wavfile
+    if verify not in ("sample", "all", "none"):
+        raise ValueError("load_infer_split: verify must be 'sample', 'all' or 'none' (got %r)" % (verify,))
+    wav_pth = str(params["args"]["infer_pth"])
+    if not os.path.isdir(wav_pth):
+        raise ValueError("load_infer_split: %s is not a directory (args.infer_pth)" % wav_pth)
+    rank, world = _rank_world(rank, world)
+    filelist = [i.replace(".wav", "") for i in os.listdir(wav_pth)]                  # FoaDataset.filelist
+    if world > 1:
+        filelist = sorted(filelist)[rank::world]
+    if files is not None:
+        want = set(str(f) for f in files)
+        missing = sorted(want - set(filelist))
+        if missing:
+            raise ValueError("load_infer_split: %s is not among this rank's files of %s" % (", ".join(missing), wav_pth))
+        filelist = [f for f in filelist if f in want]
+
+    def wav_of(name):
+        path = os.path.join(wav_pth, name + ".wav")
+        _, data = wavfile.read(path, mmap=True)
+        if data.dtype != np.int16 or data.ndim != 2 or data.shape[1] != 4:
+            raise ValueError("load_infer_split: %s holds %s %s, expected int16 (n, 4)" % (path, data.dtype, tuple(data.shape)))
+        return path, data
+
+    hc = infer_split_from_arrays(filelist, [wav_of(name)[1] for name in filelist], params)
+    n_rec = len(filelist)
+    checks = range(n_rec) if verify == "all" else (sorted({0, n_rec // 2, n_rec - 1}) if verify == "sample" and n_rec else ())
+    for i in checks:
+        path, data = wav_of(filelist[i])
+        s0 = int(hc.rec_start[i])
+        if not np.array_equal(np.asarray(data), hc.audio[s0:s0 + int(hc.lengths[i])]):
+            raise ValueError("load_infer_split: %s changed while the split was read" % path)
+    hc.wav_pth, hc.rank, hc.world = wav_pth, rank, world
+    return hc
+
+
+class InferDeviceCorpus(_CorpusBase):
+    """A ``load_infer_split`` / ``infer_split_from_arrays`` split in HBM, cut into windows of ONE shape for
+    ``test.infer_epoch_corpus``: every recording's ``window_plan`` (F = length // hop_label label frames; F = 0: no window), all
+    windows in file order, cut into passes of ``batch_size`` windows, the last pass filled up with empty windows.  The window
+    table (``ops.WINDOW_WORDS`` int64 per window: stream offset, valid samples, src_lo, destination frame on the axis of all
+    recordings laid end to end, n, recording) is built here once and uploaded once: no pass copies anything to the device.
+
+        corpus = InferDeviceCorpus(load_infer_split(params), params, "cuda:0", window_s=20, margin_s=2.0, batch_size=8)
+        audio = corpus.launch(p)                 # pass p: (batch_size, n_samples, 4) f32 on the device, no host sync
+
+    window_s defaults to ``data_config.chunk_window_s`` (what the model was trained on), margin_s to 2.0 (a configuration
+    default, not a tuned value); both must be whole multiples of the label hop, the window also of the feature hop."""
+
+    def __init__(self, host_split, params, device="cuda:0", window_s=None, margin_s=None, batch_size=8):
+        from .features import HOP
+        hc = host_split
+        if not hasattr(hc, "lengths"):
+            raise ValueError("InferDeviceCorpus: the split of load_infer_split is needed (got the chunked training split)")
+        dc = params["data_config"]
+        sr = int(dc.get("sr", 24000))
+        hop = int(hc.hop_label)
+        window_s = dc["chunk_window_s"] if window_s is None else window_s
+        margin_s = 2.0 if margin_s is None else margin_s
+        n, m = int(round(sr * float(window_s))), int(round(sr * float(margin_s)))
+        if n <= 0 or m < 0 or abs(n - sr * float(window_s)) > 1e-6 or abs(m - sr * float(margin_s)) > 1e-6 or n % hop or m % hop:
+            raise ValueError("InferDeviceCorpus: window %r s / margin %r s are not whole multiples of the label hop (%d samples at "
+                             "%d Hz)" % (window_s, margin_s, hop, sr))
+        if n % HOP:
+            raise ValueError("InferDeviceCorpus: a window of %d samples is not a whole number of feature hops (%d)" % (n, HOP))
+        self.window_frames, self.margin_frames = n // hop, m // hop
+        if self.window_frames <= 2 * self.margin_frames:
+            raise ValueError("InferDeviceCorpus: a window of %r s keeps nothing between two margins of %r s" % (window_s, margin_s))
+        self.batch_size = int(batch_size)
+        if not 1 <= self.batch_size < 65536:
+            raise ValueError("InferDeviceCorpus: batch_size %r" % (batch_size,))
+        self.host = hc
+        self.device = torch.device(device)
+        self.rank, self.world = hc.rank, hc.world
+        self.is_valid, self.is_infer, self.set_type = True, True, "infer"
+        self.wav_pth, self.csv_pth = hc.wav_pth, None
+        self.hop_label, self.n_samples = hop, n
+        self.rotate = False
+        self.filelist = list(hc.filelist)
+        self.lengths = [int(v) for v in hc.lengths.tolist()]
+        self.label_frames = [v // hop for v in self.lengths]
+        self.frame_start = np.concatenate([[0], np.cumsum(self.label_frames)]).astype(np.int64)
+        rows = []
+        for r, frames in enumerate(self.label_frames):
+            if frames == 0:
+                continue
+            for start, src_lo, dst_lo, cnt in window_plan(frames, self.window_frames, self.margin_frames):
+                off = int(hc.rec_start[r]) + start * hop
+                rows.append((off, min(n, self.lengths[r] - start * hop), src_lo, int(self.frame_start[r]) + dst_lo, cnt, r, 0, 0))
+        self.n_windows = len(rows)
+        self.n_passes = (self.n_windows + self.batch_size - 1) // self.batch_size
+        total = int(self.frame_start[-1])
+        rows += [(0, 0, 0, total, 0, -1, 0, 0)] * (self.n_passes * self.batch_size - self.n_windows)      # empty windows
+        table = np.asarray(rows, dtype=np.int64).reshape(-1, ops.WINDOW_WORDS)
+        self.table_host = table
+        per = table.reshape(self.n_passes, self.batch_size, ops.WINDOW_WORDS)
+        self.pass_base = [int(v) for v in per[:, 0, 3].tolist()]
+        self.pass_frames = [int(v) for v in per[:, :, 4].sum(1).tolist()]
+        self._to_hbm(hc)
+        self.table = torch.from_numpy(table if len(rows) else np.zeros((1, ops.WINDOW_WORDS), dtype=np.int64)).to(self.device)
+
+    def nbytes(self):
+        return int(self.pcm.numel() * 2 + self.table.numel() * 8)
+
+    def pass_table(self, p):
+        """The window rows of pass ``p``: a view of the table in HBM."""
+        if not 0 <= p < self.n_passes:
+            raise ValueError("InferDeviceCorpus: pass %r of %d" % (p, self.n_passes))
+        return self.table[p * self.batch_size:(p + 1) * self.batch_size]
+
+    def launch(self, p, audio_out=None):
+        """Pass ``p`` -> audio (batch_size, n_samples, 4) f32 on the device; no host data, no host synchronisation.  audio_out:
+        write into this buffer (a recorded forward graph's input)."""
+        shape = (self.batch_size, self.n_samples, 4)
+        audio = audio_out if audio_out is not None else torch.empty(shape, dtype=torch.float32, device=self.device)
+        if tuple(audio.shape) != shape:
+            raise ValueError("InferDeviceCorpus.launch: audio_out %s, expected %s" % (tuple(audio.shape), shape))
+        return ops.corpus_gather_windows(self.pcm, self.pass_table(p), audio, self.status)

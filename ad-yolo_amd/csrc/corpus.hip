@@ -17,6 +17,9 @@
 //   corpus_gather_mix_kernel      the gather with a second window, converted under its own combination, added as a + g * m
 //   corpus_mix_count_scan_kernel, corpus_mix_rows_kernel   the AD-YOLO rows of both sources in merged order
 //   corpus_classwise_mix_kernel   the dense targets of the merged events
+// Windowed inference (corpus.py InferDeviceCorpus, test.py infer_epoch_corpus) reads the same stream through a window table:
+//   corpus_gather_windows_kernel  the gather without rotation, the frames past a window's valid count int16 zero, never read
+//   decode_stitch_kernel          each window's kept decoded frames copied into one contiguous run per pass
 // The AD-YOLO label arithmetic is done in double, as the host does it (augmentations.rotate_labels on Python floats,
 // datasets.YoloLabelEncoder.encode_events in float64); only the written row is rounded to float32.  The class-wise kernel does
 // no arithmetic at all: the direction vectors come from a table the host builds with its own functions (corpus.xyz_table).
@@ -778,6 +781,85 @@ __global__ __launch_bounds__(CW_THREADS) void corpus_classwise_mix_kernel(const 
     }
 }
 
+// ================================================================================================ windowed inference
+// A window row: {offset, valid, src_lo, dst, n, recording, 0, 0} (adyolo_hip.h).  Both kernels stream: every output element is
+// written once by the thread that read its source, in the access shapes of corpus_gather_kernel.
+
+// grid (blocks per window, W).  Frames at or past ``valid`` are the conversion of int16 zero and are not read from the stream.
+__global__ __launch_bounds__(256) void corpus_gather_windows_kernel(const int16_t *__restrict__ pcm, long n_total,
+                                                                    const int64_t *__restrict__ windows, long n,
+                                                                    float4 *__restrict__ out, int *__restrict__ status) {
+    const int w = blockIdx.y;
+    const int64_t off = windows[(size_t)w * ADYOLO_WINDOW_WORDS + 0];
+    const int64_t valid = windows[(size_t)w * ADYOLO_WINDOW_WORDS + 1];
+    float4 *dst = out + (size_t)w * n;
+    const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, nth = (long)gridDim.x * blockDim.x;
+    const float4 pad = pcm_rot(0, 0, 1.f, 1.f, 1.f, false);      // int16 zero: what the zero padding of a training chunk becomes
+    if (valid == 0) {                                             // an empty window: nothing else of the row is looked at
+        for (long i = tid; i < n; i += nth) dst[i] = pad;
+        return;
+    }
+    if (off < 0 || (off & 1) || valid < 0 || valid > n || off > n_total - valid) {
+        if (tid == 0 && status) atomicOr(status, ADYOLO_CORPUS_BAD_ITEM);
+        for (long i = tid; i < n; i += nth) dst[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        return;
+    }
+    const int16_t *src = pcm + (size_t)off * 4;                   // even offset: two frames per 16-byte load
+    const long n2 = n >> 1;
+    const int4 *s4 = reinterpret_cast<const int4 *>(src);
+    const int2 *s2 = reinterpret_cast<const int2 *>(src);
+    for (long i = tid; i < n2; i += nth) {
+        float4 o0 = pad, o1 = pad;
+        if (2 * i + 1 < valid) {
+            const int4 v = s4[i];
+            o0 = pcm_rot(v.x, v.y, 1.f, 1.f, 1.f, false);
+            o1 = pcm_rot(v.z, v.w, 1.f, 1.f, 1.f, false);
+        } else if (2 * i < valid) {                               // the last frame of an odd count
+            const int2 v = s2[2 * i];
+            o0 = pcm_rot(v.x, v.y, 1.f, 1.f, 1.f, false);
+        }
+        dst[2 * i] = o0;
+        dst[2 * i + 1] = o1;
+    }
+    if ((n & 1) && tid == 0) {
+        float4 o = pad;
+        if (n - 1 < valid) {
+            const int2 v = s2[n - 1];
+            o = pcm_rot(v.x, v.y, 1.f, 1.f, 1.f, false);
+        }
+        dst[n - 1] = o;
+    }
+}
+
+// grid (blocks per window, W).  A window's kept frames are one contiguous run of n * rec floats on both sides.  VEC: rec % 4
+// == 0, so that every run starts and ends on a 16-byte boundary of its buffer.
+template <bool VEC>
+__global__ __launch_bounds__(256) void decode_stitch_kernel(const float *__restrict__ decoded,
+                                                            const int64_t *__restrict__ windows, int Wf, long rec,
+                                                            long pass_base, float *__restrict__ out, long out_frames,
+                                                            int *__restrict__ status) {
+    const int w = blockIdx.y;
+    const int64_t *row = windows + (size_t)w * ADYOLO_WINDOW_WORDS;
+    const int64_t src_lo = row[2], n = row[4];
+    const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, nth = (long)gridDim.x * blockDim.x;
+    if (n == 0) return;
+    const int64_t d0 = row[3] - pass_base;
+    if (src_lo < 0 || n < 0 || n > Wf || src_lo > Wf - n || d0 < 0 || d0 > out_frames - n) {
+        if (tid == 0 && status) atomicOr(status, ADYOLO_CORPUS_BAD_ITEM);
+        return;
+    }
+    const float *s = decoded + ((size_t)w * Wf + (size_t)src_lo) * rec;
+    float *d = out + (size_t)d0 * rec;
+    const long len = (long)n * rec;
+    if (VEC) {
+        const float4 *s4 = reinterpret_cast<const float4 *>(s);
+        float4 *d4 = reinterpret_cast<float4 *>(d);
+        for (long i = tid; i < (len >> 2); i += nth) d4[i] = s4[i];
+    } else {
+        for (long i = tid; i < len; i += nth) d[i] = s[i];
+    }
+}
+
 static int corpus_rot(const float *rot_host, CorpusRot &rot) {
     if (!rot_host) return ADYOLO_EINVAL;
     for (int c = 0; c < 16; ++c)
@@ -972,4 +1054,41 @@ extern "C" int adyolo_corpus_classwise_labels_mix(const double *events, const fl
     hipLaunchKernelGGL(corpus_classwise_mix_kernel, dim3((unsigned)cdiv(n_label_frames, CW_FRAMES), (unsigned)B), dim3(CW_THREADS),
                        lds, as_stream(stream), events, xyz, items, mates, g, target, status);
     return check_launch("corpus_classwise_labels_mix");
+}
+
+// ------------------------------------------------------------------------------------------------ windowed inference
+extern "C" int adyolo_corpus_gather_windows(const int16_t *pcm, long n_total, const int64_t *windows, int W, long n,
+                                            float *audio, int *status, void *stream) {
+    ADYOLO_REQUIRE(pcm && windows && audio, ADYOLO_EINVAL, "corpus_gather_windows: null pointer");
+    ADYOLO_REQUIRE(W > 0 && W < 65536 && n > 0 && n_total >= 0, ADYOLO_EINVAL,
+                   "corpus_gather_windows: bad shape W=%d n=%ld n_total=%ld", W, n, n_total);
+    ADYOLO_REQUIRE(((uintptr_t)pcm & 15) == 0 && ((uintptr_t)audio & 15) == 0 && ((uintptr_t)windows & 7) == 0, ADYOLO_EINVAL,
+                   "corpus_gather_windows: misaligned buffers (pcm / audio 16 bytes, windows 8 bytes)");
+    int gx = cdiv(n, 256L * 16);                            // the grid of adyolo_corpus_gather
+    gx = gx < 1 ? 1 : (gx > 4096 ? 4096 : gx);
+    hipLaunchKernelGGL(corpus_gather_windows_kernel, dim3((unsigned)gx, (unsigned)W), dim3(256), 0, as_stream(stream), pcm,
+                       n_total, windows, n, (float4 *)audio, status);
+    return check_launch("corpus_gather_windows");
+}
+
+extern "C" int adyolo_decode_stitch(const float *decoded, const int64_t *windows, int W, int Wf, long rec, long pass_base,
+                                    float *out, long out_frames, int *status, void *stream) {
+    ADYOLO_REQUIRE(decoded && windows && out, ADYOLO_EINVAL, "decode_stitch: null pointer");
+    ADYOLO_REQUIRE(W > 0 && W < 65536 && Wf > 0 && rec > 0 && out_frames > 0, ADYOLO_EINVAL,
+                   "decode_stitch: bad shape W=%d Wf=%d rec=%ld out_frames=%ld", W, Wf, rec, out_frames);
+    const bool vec = (rec & 3) == 0;
+    ADYOLO_REQUIRE(((uintptr_t)decoded & (vec ? 15 : 3)) == 0 && ((uintptr_t)out & (vec ? 15 : 3)) == 0 &&
+                       ((uintptr_t)windows & 7) == 0,
+                   ADYOLO_EINVAL, "decode_stitch: misaligned buffers (decoded / out %d bytes, windows 8 bytes)", vec ? 16 : 4);
+    // ~16 bytes x 4 per thread over one window's frames
+    int gx = cdiv((long)Wf * rec, 256L * 16);
+    gx = gx < 1 ? 1 : (gx > 1024 ? 1024 : gx);
+    const dim3 grid((unsigned)gx, (unsigned)W);
+    if (vec)
+        hipLaunchKernelGGL(decode_stitch_kernel<true>, grid, dim3(256), 0, as_stream(stream), decoded, windows, Wf, rec, pass_base,
+                           out, out_frames, status);
+    else
+        hipLaunchKernelGGL(decode_stitch_kernel<false>, grid, dim3(256), 0, as_stream(stream), decoded, windows, Wf, rec, pass_base,
+                           out, out_frames, status);
+    return check_launch("decode_stitch");
 }

@@ -2001,6 +2001,56 @@ def corpus_classwise_labels_mix(events, items, mates, xyz, max_events, n_label_f
     return target
 
 
+WINDOW_WORDS = 8                                          # ADYOLO_WINDOW_WORDS: {offset, valid, src_lo, dst, n, recording, 0, 0}
+
+
+def _window_table(name, windows, device):
+    _corpus_i64("%s: windows" % name, windows, device)
+    if windows.dim() != 2 or windows.shape[0] < 1 or windows.shape[1] != WINDOW_WORDS:
+        raise _lib.AdyoloHipError("%s: windows %s are not (W, %d)" % (name, tuple(windows.shape), WINDOW_WORDS))
+    return int(windows.shape[0])
+
+
+def corpus_gather_windows(pcm, windows, out, status):
+    """pcm int16 (S, 4) and windows int64 (W, 8) on the device -> out (W, n, 4) float32: each window's ``valid`` int16 frames
+    from its offset as ``x / 32768 + 1e-8``, the rest of the window the conversion of int16 zero, not read from pcm
+    (adyolo_hip.h ``adyolo_corpus_gather_windows``).  An odd or negative offset, or a window past the stream: zeros for it and
+    status bit 2.  out may be a recorded graph's static input.  No allocation, no sync."""
+    dev = pcm.device
+    if not pcm.is_cuda or pcm.dtype != torch.int16 or not pcm.is_contiguous() or pcm.dim() != 2 or pcm.shape[1] != 4:
+        raise _lib.AdyoloHipError("corpus_gather_windows: pcm must be a contiguous int16 tensor (S, 4) on the device")
+    w = _window_table("corpus_gather_windows", windows, dev)
+    _chk(out)
+    if out.dim() != 3 or out.shape[0] != w or out.shape[1] < 1 or out.shape[2] != 4 or out.device != dev:
+        raise _lib.AdyoloHipError("corpus_gather_windows: out %s is not (%d, n, 4) on %s" % (tuple(out.shape), w, dev))
+    if status.dtype != torch.int32 or status.device != dev or status.numel() < 1:
+        raise _lib.AdyoloHipError("corpus_gather_windows: status must be an int32 word on %s" % dev)
+    _c("adyolo_corpus_gather_windows", _p(pcm), pcm.shape[0], _p(windows), w, out.shape[1], _p(out), _p(status), _stream())
+    return out
+
+
+def decode_stitch(decoded, windows, window_frames, pass_base, out, status):
+    """decoded (W * window_frames, ...) float32 (``LabelPostProcessor.decode_device`` of a pass of W windows) and windows int64
+    (W, 8) on the device -> out (capacity, ...) float32 with the same trailing shape: window w's frames [src_lo, src_lo + n)
+    copied to out[dst - pass_base ...], the kept frames of the pass as one run in window order (adyolo_hip.h
+    ``adyolo_decode_stitch``).  A window whose frames are outside its own window or outside out is skipped and sets status
+    bit 2.  No allocation, no sync."""
+    _chk(decoded, out)
+    dev = decoded.device
+    w = _window_table("decode_stitch", windows, dev)
+    wf = int(window_frames)
+    if wf < 1 or decoded.dim() < 2 or decoded.shape[0] != w * wf:
+        raise _lib.AdyoloHipError("decode_stitch: decoded %s is not (%d * %d, ...)" % (tuple(decoded.shape), w, wf))
+    if out.dim() != decoded.dim() or out.shape[0] < 1 or tuple(out.shape[1:]) != tuple(decoded.shape[1:]) or out.device != dev:
+        raise _lib.AdyoloHipError("decode_stitch: out %s does not hold frames of %s on %s"
+                                  % (tuple(out.shape), tuple(decoded.shape[1:]), dev))
+    if status.dtype != torch.int32 or status.device != dev or status.numel() < 1:
+        raise _lib.AdyoloHipError("decode_stitch: status must be an int32 word on %s" % dev)
+    rec = decoded.numel() // decoded.shape[0]
+    _c("adyolo_decode_stitch", _p(decoded), _p(windows), w, wf, rec, int(pass_base), _p(out), out.shape[0], _p(status), _stream())
+    return out
+
+
 def corpus_status_check(word):
     """Raise ``AdyoloHipError`` for the ADYOLO_CORPUS_* bits of a status word already read to the host."""
     word = int(word)

@@ -286,6 +286,56 @@ def sweep_conf_thresh_corpus(corpus, model, features, criterion, postprocessor, 
     return new_thresh, table, loss
 
 
+def infer_epoch_corpus(corpus, model, features, postprocessor, output_pth, forward=None):
+    """Inference on recordings of any length from an HBM-resident folder (``corpus.InferDeviceCorpus``): every recording cut
+    into overlapping windows of one shape, the windows run ``corpus.batch_size`` at a time -- so the whole folder has ONE input
+    shape and, with ``forward`` (``graph.ForwardGraphs``), one recorded graph.  Per pass: ``adyolo_corpus_gather_windows`` (into
+    the graph's static input when there is one) -> ``forward(audio)`` or the eager forward + ``decode_device`` ->
+    ``adyolo_decode_stitch`` (each window's frames that have context on both sides, compacted into one run) ->
+    ``select_device_rows`` on the run (both selections work frame by frame) -> the rows and counts to the host, where
+    ``corpus.split_pass_rows`` puts them on each recording's own frame axis.  One CSV per recording, named after the file, empty
+    for a recording without rows or without a label frame.  No audio crosses PCIe; nothing is uploaded per pass.
+    -> {'recordings', 'windows', 'passes', 'frames'}."""
+    from . import ops
+    from .corpus import split_pass_rows
+    model.eval()
+    delete_and_create_folder(output_pth)
+    names = corpus.get_filelist()
+    corpus.reset_status()
+    b, n, wf = corpus.batch_size, corpus.n_samples, corpus.window_frames
+    outs = [{} for _ in names]
+    stitched = None
+    with torch.no_grad():
+        for p in range(corpus.n_passes):
+            audio_out = None
+            if forward is not None and hasattr(forward, "static_input"):
+                audio_out = forward.static_input((b, n, 4))                  # the gather writes the graph's input itself
+            audio = corpus.launch(p, audio_out)
+            dec = None
+            if forward is not None:
+                output, dec = forward(audio)
+            else:
+                output = model(features(audio, channels_last8=True), channels_last8=True)
+            if dec is None:
+                dec = postprocessor.decode_device(output)
+            if dec.shape[0] != b * wf:
+                raise ValueError("infer_epoch_corpus: %d decoded frames from %d windows of %d label frames (the model's frame rate "
+                                 "is not the label hop's)" % (dec.shape[0], b, wf))
+            if stitched is None:
+                stitched = torch.empty_like(dec)
+            frames = corpus.pass_frames[p]
+            ops.decode_stitch(dec, corpus.pass_table(p), wf, corpus.pass_base[p], stitched, corpus.status)
+            rows, counts = postprocessor.select_device_rows(stitched[:frames], 1)
+            rows_h, counts_h = [t.numpy() for t in ops.to_host_many(rows, counts)]
+            for r, found in split_pass_rows(rows_h, counts_h, corpus.pass_base[p], corpus.frame_start).items():
+                outs[r].update(found)                                        # (a recording's passes come in frame order)
+    corpus.check()
+    for name, rows in zip(names, outs):
+        write_seld_output_file(os.path.join(output_pth, name + ".csv"), rows)
+    return {"recordings": len(names), "windows": corpus.n_windows, "passes": corpus.n_passes,
+            "frames": int(corpus.frame_start[-1])}
+
+
 def score_output_folder(params, ref_dir, output_pth, is_jackknife=False):
     """The three score sets the reference prints for one evaluated folder (src/test.py:104-133): all frames, frames with
     overlapping events ("class-independent polyphony") and frames with overlapping events of one class

@@ -758,6 +758,30 @@ int  adyolo_corpus_classwise_labels_mix(const double *events, const float *xyz, 
                                         const int64_t *mates, int B, int max_events, int n_label_frames, int n_classes,
                                         int format, float *target, int *status, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Windowed inference (corpus.InferDeviceCorpus, test.infer_epoch_corpus): recordings of any length cut into overlapping
+ * windows of ONE shape, each pass of W windows made and stitched on the device from a table uploaded once.
+ *   windows  DEVICE int64 [W][ADYOLO_WINDOW_WORDS] = {sample offset into pcm (frames), valid samples, src_lo (first kept label
+ *            frame, window-local), dst (its place on the frame axis of all recordings laid end to end), n (kept frames),
+ *            recording, 0, 0}; an empty window (the filler of the last pass) has valid = 0 and n = 0
+ * adyolo_corpus_gather_windows: audio [W][n][4] float32 = the int16 frames pcm[off .. off + valid) as x / 32768 + 1e-8 (the
+ *   arithmetic of adyolo_corpus_gather with comb < 0, element for element), then n - valid frames of int16 zero, 1e-8f, which
+ *   are not read from pcm (behind a recording lies the next one).  valid = 0: all 1e-8f, nothing else of the row is read.
+ *   Offsets are whole label hops, so even: an odd or negative offset, valid outside [0, n] or off + valid > n_total gives
+ *   zeros for that window and sets ADYOLO_CORPUS_BAD_ITEM.  pcm and audio 16-byte aligned; audio may be a recorded graph's
+ *   static input.
+ * adyolo_decode_stitch: for each window w, n frame records of rec floats from decoded[(w Wf + src_lo) ..] to
+ *   out[(dst - pass_base) ..]: the pass's kept frames compacted into one run in window order.  decoded [W Wf][rec], out
+ *   [out_frames][rec] (rec: whatever the decode writes per frame); 16-byte copies where rec % 4 == 0 (both buffers 16-byte
+ *   aligned then), 4-byte copies otherwise.  A window with src_lo < 0, n < 0, src_lo + n > Wf or a destination outside
+ *   [0, out_frames) is not copied and sets ADYOLO_CORPUS_BAD_ITEM.  The frames of out no window names are left as they are.
+ * ---------------------------------------------------------------------------------------------- */
+#define ADYOLO_WINDOW_WORDS 8
+int  adyolo_corpus_gather_windows(const int16_t *pcm, long n_total, const int64_t *windows, int W, long n, float *audio,
+                                  int *status, void *stream);
+int  adyolo_decode_stitch(const float *decoded, const int64_t *windows, int W, int Wf, long rec, long pass_base, float *out,
+                          long out_frames, int *status, void *stream);
+
 /* K11 Adam, AdamW, SGD and gradient-norm clipping over one flat parameter buffer (csrc/optim.hip; the reference picks its
  * optimizer by name, src/train.py:29-37, and clips with clip_grad_norm_, src/train.py:54; no amsgrad).  The step counter is ON
  * THE DEVICE (one uint64): every call bumps step_dev itself and no argument changes from step to step, so the whole train step

@@ -382,8 +382,7 @@ class _CorpusBase:
     def _upload(self, drawn):
         """One H2D copy of the item table (+ SpecAug tables) through a double-buffered page-locked buffer
         -> (items int64 (B, 8), spec int32 (B, rows, 4) or None; rows = 2, or 4 with the frequency-shift / cutout rows) on the
-        device; with mates in ``drawn`` they travel in the same
-        copy, behind the items, and come back as a third element."""
+        device, and the mates int64 (B, 8) or None: with mates in ``drawn`` they travel in the same copy, behind the items."""
         items, spec = drawn[0], drawn[1]
         mates = drawn[2] if len(drawn) > 2 else None
         b = items.shape[0]
@@ -412,14 +411,27 @@ class _CorpusBase:
         self._copied[slot] = ev
         dev_items = dev[:n_i].view(b, ops.CORPUS_ITEM_WORDS)
         dev_spec = dev[n_i + n_m:].view(torch.int32).view(b, spec.shape[1], 4) if spec is not None else None
-        if mates is not None:
-            return dev_items, dev_spec, dev[n_i:n_i + n_m].view(b, ops.CORPUS_ITEM_WORDS)
-        return dev_items, dev_spec
+        dev_mates = dev[n_i:n_i + n_m].view(b, ops.CORPUS_ITEM_WORDS) if mates is not None else None
+        return dev_items, dev_spec, dev_mates
 
     def batch(self, indices, audio_out=None, target_out=None):
         """Items ``indices`` of ``get_filelist()`` -> (audio (B, n, 4) f32, target, spec (B, 2 | 4, 4) int32 or None), on the device,
         with no host synchronisation.  audio_out / target_out: write into these buffers (a recorded step's)."""
         return self.launch(self.draw(indices), audio_out, target_out)
+
+    def _begin(self, drawn, audio_out, target_out):
+        """What every ``launch`` starts with: the H2D copy of the tables, then the output buffers (the caller's, checked against
+        ``target_shape``, or new ones) -> (items, mates or None, spec or None, audio, target), all on the device."""
+        dev_items, dev_spec, dev_mates = self._upload(drawn)
+        b = dev_items.shape[0]
+        shape = tuple(self.target_shape(b))
+        audio = audio_out if audio_out is not None else \
+            torch.empty((b, self.n_samples, 4), dtype=torch.float32, device=self.device)
+        target = target_out if target_out is not None else torch.empty(shape, dtype=torch.float32, device=self.device)
+        if tuple(audio.shape) != (b, self.n_samples, 4) or tuple(target.shape) != shape:
+            raise ValueError("%s.launch: output buffers %s / %s, expected (%d, %d, 4) / %s"
+                             % (type(self).__name__, tuple(audio.shape), tuple(target.shape), b, self.n_samples, shape))
+        return dev_items, dev_mates, dev_spec, audio, target
 
     def _gather(self, dev_items, audio, dev_mates=None):
         """The audio of a batch: FOA-rotated, or with ``aug_config.channel_swap_augment`` the MIC capsules permuted; with mates
@@ -480,26 +492,17 @@ class DeviceCorpus(_CorpusBase):
     def launch(self, drawn, audio_out=None, target_out=None):
         """The device half: one H2D copy of the item table (+ SpecAug tables), the gather and the label kernels.
         -> (audio (B, n, 4) f32, target (cap, 7) f32, spec (B, 2 | 4, 4) int32 or None) on the device; no host sync."""
-        dev_items, dev_spec, *dev_mates = self._upload(drawn)
+        dev_items, dev_mates, dev_spec, audio, target = self._begin(drawn, audio_out, target_out)
         b = dev_items.shape[0]
-        audio = audio_out if audio_out is not None else \
-            torch.empty((b, self.n_samples, 4), dtype=torch.float32, device=self.device)
-        target = target_out if target_out is not None else torch.empty((self.cap, 7), dtype=torch.float32, device=self.device)
-        if tuple(audio.shape) != (b, self.n_samples, 4) or tuple(target.shape) != (self.cap, 7):
-            raise ValueError("DeviceCorpus.launch: output buffers %s / %s, expected (%d, %d, 4) / (%d, 7)"
-                             % (tuple(audio.shape), tuple(target.shape), b, self.n_samples, self.cap))
         self.rows = torch.empty(1, dtype=torch.int32, device=self.device)
-        if dev_mates:                            # time-domain mixing: both sources' audio summed, their rows in merged order
-            ws = torch.empty(max(1, ops.corpus_labels_mix_workspace_words(b, self.max_events)), dtype=torch.int32,
-                             device=self.device)
-            self._gather(dev_items, audio, dev_mates[0])
-            ops.corpus_yolo_labels_mix(self.events, dev_items, dev_mates[0], self.max_events, self.n_label_frames, self.bounds,
-                                       self.grid, self.rot, ws, target, self.rows, self.status)
-            return audio, target, dev_spec
-        ws = torch.empty(max(1, ops.corpus_labels_workspace_words(b, self.max_events)), dtype=torch.int32, device=self.device)
-        self._gather(dev_items, audio)
-        ops.corpus_yolo_labels(self.events, dev_items, self.max_events, self.n_label_frames, self.bounds, self.grid, self.rot, ws,
-                               target, self.rows, self.status)
+        self._gather(dev_items, audio, dev_mates)
+        if dev_mates is None:
+            ws_words, labels, tables = ops.corpus_labels_workspace_words, ops.corpus_yolo_labels, (dev_items,)
+        else:                                    # time-domain mixing: both sources' audio summed, their rows in merged order
+            ws_words, labels, tables = ops.corpus_labels_mix_workspace_words, ops.corpus_yolo_labels_mix, (dev_items, dev_mates)
+        ws = torch.empty(max(1, ws_words(b, self.max_events)), dtype=torch.int32, device=self.device)
+        labels(self.events, *tables, self.max_events, self.n_label_frames, self.bounds, self.grid, self.rot, ws, target, self.rows,
+               self.status)
         return audio, target, dev_spec
 
 
@@ -544,23 +547,14 @@ class ClasswiseDeviceCorpus(_CorpusBase):
     def launch(self, drawn, audio_out=None, target_out=None):
         """The device half: one H2D copy of the item table (+ SpecAug tables), the gather and the label kernel.
         -> (audio (B, n, 4) f32, target ``target_shape(B)`` f32, spec (B, 2 | 4, 4) int32 or None) on the device; no host sync."""
-        dev_items, dev_spec, *dev_mates = self._upload(drawn)
-        b = dev_items.shape[0]
-        shape = self.target_shape(b)
-        audio = audio_out if audio_out is not None else \
-            torch.empty((b, self.n_samples, 4), dtype=torch.float32, device=self.device)
-        target = target_out if target_out is not None else torch.empty(shape, dtype=torch.float32, device=self.device)
-        if tuple(audio.shape) != (b, self.n_samples, 4) or tuple(target.shape) != shape:
-            raise ValueError("ClasswiseDeviceCorpus.launch: output buffers %s / %s, expected (%d, %d, 4) / %s"
-                             % (tuple(audio.shape), tuple(target.shape), b, self.n_samples, shape))
-        if dev_mates:                            # time-domain mixing: both sources' audio summed, the targets of the merged events
-            self._gather(dev_items, audio, dev_mates[0])
-            ops.corpus_classwise_labels_mix(self.events, dev_items, dev_mates[0], self.xyz, self.max_events, self.n_label_frames,
-                                            self.nb_classes, self.loss_nm, target, self.status)
-            return audio, target, dev_spec
-        self._gather(dev_items, audio)
-        ops.corpus_classwise_labels(self.events, dev_items, self.xyz, self.max_events, self.n_label_frames, self.nb_classes,
-                                    self.loss_nm, target, self.status)
+        dev_items, dev_mates, dev_spec, audio, target = self._begin(drawn, audio_out, target_out)
+        self._gather(dev_items, audio, dev_mates)
+        if dev_mates is None:
+            labels, tables = ops.corpus_classwise_labels, (dev_items,)
+        else:                                    # time-domain mixing: both sources' audio summed, the targets of the merged events
+            labels, tables = ops.corpus_classwise_labels_mix, (dev_items, dev_mates)
+        labels(self.events, *tables, self.xyz, self.max_events, self.n_label_frames, self.nb_classes, self.loss_nm, target,
+               self.status)
         return audio, target, dev_spec
 
 

@@ -4,19 +4,20 @@
 // src/datasets.py:93-184: the WAV read, ``audio / 32768 + 1e-8``, RotationAug, get_yolo_label or the class-wise encoders,
 // collate_fn) followed by AudioStager, adyolo_pcm16_to_f32 and adyolo_foa_rotate.
 //
-//   corpus_gather_kernel     one pass int16 window -> float32 ``x / 32768 + 1e-8``, FOA channels rotated; 16-byte loads of
-//                            two int16 frames, two 16-byte stores (8-byte loads when the window starts on an odd frame)
-//   corpus_gather_mic_kernel the same pass for MIC-format audio: the four capsules permuted (channel swap) instead of rotated
-//   corpus_count_scan_kernel one workgroup: rows per (item, event) lane, exclusive scan, the total and the overflow bit
-//   corpus_rows_kernel       the rows [b, t, gi, gj, cls, U, V] at their scanned offsets, b = -1 in the rest of the capacity
-//   corpus_classwise_kernel  the dense SEDDOA / ACCDOA / ADPIT targets (datasets.ClasswiseLabelEncoder): per tile of label
-//                            frames, each frame's event range, the event each (frame, class) output takes, then every output
-//                            element written once
-// Time-domain mixing (aug_config.time_mix_augment: the audio of two chunks summed, their labels united) has its own forms, each
-// over the item table and a second table of mates; the kernels above are not touched by it:
-//   corpus_gather_mix_kernel      the gather with a second window, converted under its own combination, added as a + g * m
-//   corpus_mix_count_scan_kernel, corpus_mix_rows_kernel   the AD-YOLO rows of both sources in merged order
-//   corpus_classwise_mix_kernel   the dense targets of the merged events
+// Every stage has one kernel body with a compile-time MIX parameter.  MIX false is the plain batch: the item table alone, and
+// nothing of a second source in its lanes, LDS or registers.  MIX true is time-domain mixing (aug_config.time_mix_augment: the
+// audio of two chunks summed, their labels united): a second table of mates beside the items, and an item without a mate gets
+// the plain form's bits.
+//   corpus_gather_kernel<Tab, MIX>   one pass int16 window -> float32 ``x / 32768 + 1e-8``, two frames per iteration from one
+//                                    16-byte load (two 8-byte loads when the window starts on an odd frame), two 16-byte stores.
+//                                    Tab = CorpusRot: FOA channels rotated; CorpusMicSrc: the four MIC capsules permuted
+//                                    (channel swap).  MIX: the mate's window, under its own combination, added as a + g * m
+//   corpus_count_scan_kernel<MIX>    one workgroup: rows per lane -- (item, event), or (item, source, event) in merged order --
+//                                    exclusive scan, the total and the overflow bit
+//   corpus_rows_kernel<MIX>          the rows [b, t, gi, gj, cls, U, V] at their scanned offsets, b = -1 in the rest of the capacity
+//   corpus_classwise_kernel<MIX>     the dense SEDDOA / ACCDOA / ADPIT targets (datasets.ClasswiseLabelEncoder): per tile of label
+//                                    frames, each frame's event range per source, the event each (frame, class) output takes,
+//                                    then every output element written once
 // Windowed inference (corpus.py InferDeviceCorpus, test.py infer_epoch_corpus) reads the same stream through a window table:
 //   corpus_gather_windows_kernel  the gather without rotation, the frames past a window's valid count int16 zero, never read
 //   decode_stitch_kernel          each window's kept decoded frames copied into one contiguous run per pass
@@ -31,6 +32,10 @@ struct CorpusRot {                     // ADYOLO_CORPUS_ROT_WORDS floats per com
     float c[16][ADYOLO_CORPUS_ROT_WORDS];
 };
 
+struct CorpusMicSrc {                  // one word per combination (adyolo_hip.h), passed by value (capturable)
+    unsigned w[16];
+};
+
 __device__ __forceinline__ float4 pcm_rot(int lo, int hi, float sy, float sz, float sx, bool swap) {
     // the arithmetic of pcm16_to_f32_kernel (csrc/aug.hip) then foa_rotate_kernel (csrc/aug.hip), element for element
     const float w = (float)(short)(lo & 0xffff) / 32768.0f + 1e-8f;
@@ -41,55 +46,9 @@ __device__ __forceinline__ float4 pcm_rot(int lo, int hi, float sy, float sz, fl
     return swap ? make_float4(w, xx, zz, yy) : make_float4(w, yy, zz, xx);
 }
 
-// grid (blocks per item, B).  An item whose offset or combination is outside the corpus gets zeros and sets status bit 2.
-__global__ __launch_bounds__(256) void corpus_gather_kernel(const int16_t *__restrict__ pcm, long n_total,
-                                                            const int64_t *__restrict__ items, long n, CorpusRot rot,
-                                                            float4 *__restrict__ out, int *__restrict__ status) {
-    const int b = blockIdx.y;
-    const int64_t off = items[(size_t)b * ADYOLO_CORPUS_ITEM_WORDS + 0];
-    const int64_t comb = items[(size_t)b * ADYOLO_CORPUS_ITEM_WORDS + 4];
-    float4 *dst = out + (size_t)b * n;
-    const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, nth = (long)gridDim.x * blockDim.x;
-    if (off < 0 || off > n_total - n || comb >= 16) {
-        if (tid == 0 && status) atomicOr(status, ADYOLO_CORPUS_BAD_ITEM);
-        for (long i = tid; i < n; i += nth) dst[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        return;
-    }
-    float sy = 1.f, sz = 1.f, sx = 1.f;
-    bool swap = false;
-    if (comb >= 0) {
-        sy = rot.c[comb][0]; sz = rot.c[comb][1]; sx = rot.c[comb][2]; swap = rot.c[comb][3] != 0.f;
-    }
-    const int16_t *src = pcm + (size_t)off * 4;
-    if ((off & 1) == 0) {                                   // two frames per 16-byte load
-        const long n2 = n >> 1;
-        const int4 *s4 = reinterpret_cast<const int4 *>(src);
-        for (long i = tid; i < n2; i += nth) {
-            const int4 v = s4[i];
-            dst[2 * i] = pcm_rot(v.x, v.y, sy, sz, sx, swap);
-            dst[2 * i + 1] = pcm_rot(v.z, v.w, sy, sz, sx, swap);
-        }
-        if ((n & 1) && tid == 0) {
-            const int2 v = reinterpret_cast<const int2 *>(src)[n - 1];
-            dst[n - 1] = pcm_rot(v.x, v.y, sy, sz, sx, swap);
-        }
-    } else {
-        const int2 *s2 = reinterpret_cast<const int2 *>(src);
-        for (long i = tid; i < n; i += nth) {
-            const int2 v = s2[i];
-            dst[i] = pcm_rot(v.x, v.y, sy, sz, sx, swap);
-        }
-    }
-}
-
-// ---- the MIC form: a permutation of the four capsules instead of signs (augmentations.mic_swap_source).  The permutation is
-// uniform over the workgroup (blockIdx.y = item), so the two byte selectors of v_perm_b32 are built once, in scalar registers;
-// the int16 halves of a frame are moved to their output places before the conversion: two v_perm_b32 per frame, then the
-// arithmetic of pcm16_to_f32_kernel, element for element.  Same access shapes as corpus_gather_kernel.
-struct CorpusMicSrc {                  // one word per combination (adyolo_hip.h), passed by value (capturable)
-    unsigned w[16];
-};
-
+// The MIC form: a permutation of the four capsules instead of signs (augmentations.mic_swap_source).  The int16 halves of a
+// frame are moved to their output places before the conversion: two v_perm_b32 per frame, then the arithmetic of
+// pcm16_to_f32_kernel, element for element.
 // frame bytes 0..7 = {lo, hi}; selector byte k of v_perm_b32(hi, lo, sel) names the frame byte that lands in byte k
 __device__ __forceinline__ float4 pcm_swap(int lo, int hi, unsigned sel_lo, unsigned sel_hi) {
     const int a = (int)__builtin_amdgcn_perm((unsigned)hi, (unsigned)lo, sel_lo);
@@ -98,50 +57,131 @@ __device__ __forceinline__ float4 pcm_swap(int lo, int hi, unsigned sel_lo, unsi
                        (float)(short)(c & 0xffff) / 32768.0f + 1e-8f, (float)(short)(c >> 16) / 32768.0f + 1e-8f);
 }
 
-// grid (blocks per item, B).  An item whose offset is outside the corpus, or whose combination is >= 16 or no symmetry of the
-// array, gets zeros and sets status bit 2; comb < 0: the frame as it is.
-__global__ __launch_bounds__(256) void corpus_gather_mic_kernel(const int16_t *__restrict__ pcm, long n_total,
-                                                                const int64_t *__restrict__ items, long n, CorpusMicSrc tab,
-                                                                float4 *__restrict__ out, int *__restrict__ status) {
+// One source's conversion, uniform over the workgroup (blockIdx.y = item), so held in scalar registers: the signs and the swap
+// of pcm_rot, or the two byte selectors of pcm_swap.  gather_source returns false for a combination that is no symmetry of the
+// array (MIC table only); comb < 0: the frame as it is.
+struct CorpusSrc {
+    float sy, sz, sx;
+    bool swap;
+    unsigned sel_lo, sel_hi;
+};
+
+__device__ __forceinline__ bool gather_source(const CorpusRot &rot, int64_t comb, CorpusSrc &s) {
+    s.sy = 1.f; s.sz = 1.f; s.sx = 1.f; s.swap = false; s.sel_lo = 0u; s.sel_hi = 0u;
+    if (comb >= 0) {
+        s.sy = rot.c[comb][0]; s.sz = rot.c[comb][1]; s.sx = rot.c[comb][2]; s.swap = rot.c[comb][3] != 0.f;
+    }
+    return true;
+}
+
+__device__ __forceinline__ bool gather_source(const CorpusMicSrc &tab, int64_t comb, CorpusSrc &s) {
+    unsigned w = 0x03020100u;                               // identity: channel j from channel j
+    if (comb >= 0) w = tab.w[comb];
+    // channel c = frame bytes {2 c, 2 c + 1}: the byte pair c * 0x0202 + 0x0100; & 3 keeps every selector inside the frame
+    const unsigned s0 = w & 3u, s1 = (w >> 8) & 3u, s2 = (w >> 16) & 3u, s3 = (w >> 24) & 3u;
+    s.sy = 1.f; s.sz = 1.f; s.sx = 1.f; s.swap = false;
+    s.sel_lo = (s0 * 0x0202u + 0x0100u) | ((s1 * 0x0202u + 0x0100u) << 16);
+    s.sel_hi = (s2 * 0x0202u + 0x0100u) | ((s3 * 0x0202u + 0x0100u) << 16);
+    return w != ADYOLO_MIC_SWAP_NONE;
+}
+
+__device__ __forceinline__ float4 gather_conv(const CorpusRot &, int lo, int hi, const CorpusSrc &s) {
+    return pcm_rot(lo, hi, s.sy, s.sz, s.sx, s.swap);
+}
+__device__ __forceinline__ float4 gather_conv(const CorpusMicSrc &, int lo, int hi, const CorpusSrc &s) {
+    return pcm_swap(lo, hi, s.sel_lo, s.sel_hi);
+}
+
+// an item or mate row as a window of the stream: false when its offset or combination is outside the corpus
+template <class Tab>
+__device__ __forceinline__ bool gather_window(const int64_t *__restrict__ row, long n_total, long n, const Tab &tab,
+                                              CorpusSrc &s) {
+    const int64_t off = row[0], comb = row[4];
+    return off >= 0 && off <= n_total - n && comb < 16 && gather_source(tab, comb, s);
+}
+
+// frames 2 i and 2 i + 1 of a window: one 16-byte load where the window starts on an even frame, two 8-byte loads where not
+template <bool EVEN>
+__device__ __forceinline__ int4 gather_load2(const int16_t *__restrict__ src, long i) {
+    if (EVEN) return reinterpret_cast<const int4 *>(src)[i];
+    const int2 *s2 = reinterpret_cast<const int2 *>(src);
+    const int2 a = s2[2 * i], c = s2[2 * i + 1];
+    return make_int4(a.x, a.y, c.x, c.y);
+}
+
+// the streaming loop for one parity of the item's and of the mate's offset; MIXED false: the mate is not read at all
+template <class Tab, bool A_EVEN, bool M_EVEN, bool MIXED>
+__device__ __forceinline__ void gather_loop(const Tab &tab, const int16_t *__restrict__ sa, const int16_t *__restrict__ sm,
+                                            long n, const CorpusSrc &ca, const CorpusSrc &cm, float g, float4 *__restrict__ dst,
+                                            long tid, long nth) {
+    const long n2 = n >> 1;
+    for (long i = tid; i < n2; i += nth) {
+        const int4 va = gather_load2<A_EVEN>(sa, i);
+        float4 o0 = gather_conv(tab, va.x, va.y, ca), o1 = gather_conv(tab, va.z, va.w, ca);
+        if (MIXED) {
+            const int4 vm = gather_load2<M_EVEN>(sm, i);
+            o0 = mix_add(o0, gather_conv(tab, vm.x, vm.y, cm), g);
+            o1 = mix_add(o1, gather_conv(tab, vm.z, vm.w, cm), g);
+        }
+        dst[2 * i] = o0;
+        dst[2 * i + 1] = o1;
+    }
+    if ((n & 1) && tid == 0) {
+        const int2 va = reinterpret_cast<const int2 *>(sa)[n - 1];
+        float4 o = gather_conv(tab, va.x, va.y, ca);
+        if (MIXED) {
+            const int2 vm = reinterpret_cast<const int2 *>(sm)[n - 1];
+            o = mix_add(o, gather_conv(tab, vm.x, vm.y, cm), g);
+        }
+        dst[n - 1] = o;
+    }
+}
+
+// grid (blocks per item, B).  An item whose window is outside the corpus -- with MIX, or whose mate's is -- gets zeros for the
+// whole sample and sets status bit 2.  A mate row has the layout of an item row; offset (word 0) == -1: the item has no mate,
+// and nothing else of that row is read; word 6: the float32 bits of the gain.  MIX false: ``mates`` is not read.
+template <class Tab, bool MIX>
+__global__ __launch_bounds__(256) void corpus_gather_kernel(const int16_t *__restrict__ pcm, long n_total,
+                                                            const int64_t *__restrict__ items,
+                                                            const int64_t *__restrict__ mates, long n, Tab tab,
+                                                            float4 *__restrict__ out, int *__restrict__ status) {
     const int b = blockIdx.y;
-    const int64_t off = items[(size_t)b * ADYOLO_CORPUS_ITEM_WORDS + 0];
-    const int64_t comb = items[(size_t)b * ADYOLO_CORPUS_ITEM_WORDS + 4];
+    const int64_t *it = items + (size_t)b * ADYOLO_CORPUS_ITEM_WORDS, *mt = it;
+    bool mixed = false;
+    if (MIX) {
+        mt = mates + (size_t)b * ADYOLO_CORPUS_ITEM_WORDS;
+        mixed = mt[0] != -1;
+    }
     float4 *dst = out + (size_t)b * n;
     const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, nth = (long)gridDim.x * blockDim.x;
-    unsigned w = 0x03020100u;                               // identity: channel j from channel j
-    bool bad = off < 0 || off > n_total - n || comb >= 16;
-    if (!bad && comb >= 0) {
-        w = tab.w[comb];
-        bad = w == ADYOLO_MIC_SWAP_NONE;
+    CorpusSrc ca, cm = {1.f, 1.f, 1.f, false, 0u, 0u};
+    float g = 0.f;
+    bool ok = gather_window(it, n_total, n, tab, ca);
+    if (ok && mixed) {
+        ok = gather_window(mt, n_total, n, tab, cm);
+        g = __int_as_float((int)mt[6]);
     }
-    if (bad) {
+    if (!ok) {
         if (tid == 0 && status) atomicOr(status, ADYOLO_CORPUS_BAD_ITEM);
         for (long i = tid; i < n; i += nth) dst[i] = make_float4(0.f, 0.f, 0.f, 0.f);
         return;
     }
-    // channel s = frame bytes {2 s, 2 s + 1}: the byte pair s * 0x0202 + 0x0100; & 3 keeps every selector inside the frame
-    const unsigned s0 = w & 3u, s1 = (w >> 8) & 3u, s2 = (w >> 16) & 3u, s3 = (w >> 24) & 3u;
-    const unsigned sel_lo = (s0 * 0x0202u + 0x0100u) | ((s1 * 0x0202u + 0x0100u) << 16);
-    const unsigned sel_hi = (s2 * 0x0202u + 0x0100u) | ((s3 * 0x0202u + 0x0100u) << 16);
-    const int16_t *src = pcm + (size_t)off * 4;
-    if ((off & 1) == 0) {                                   // two frames per 16-byte load
-        const long n2 = n >> 1;
-        const int4 *s4 = reinterpret_cast<const int4 *>(src);
-        for (long i = tid; i < n2; i += nth) {
-            const int4 v = s4[i];
-            dst[2 * i] = pcm_swap(v.x, v.y, sel_lo, sel_hi);
-            dst[2 * i + 1] = pcm_swap(v.z, v.w, sel_lo, sel_hi);
-        }
-        if ((n & 1) && tid == 0) {
-            const int2 v = reinterpret_cast<const int2 *>(src)[n - 1];
-            dst[n - 1] = pcm_swap(v.x, v.y, sel_lo, sel_hi);
-        }
-    } else {
-        const int2 *s2v = reinterpret_cast<const int2 *>(src);
-        for (long i = tid; i < n; i += nth) {
-            const int2 v = s2v[i];
-            dst[i] = pcm_swap(v.x, v.y, sel_lo, sel_hi);
-        }
+    const int64_t off = it[0];
+    const int16_t *sa = pcm + (size_t)off * 4;
+    if (!mixed) {
+        if ((off & 1) == 0)
+            gather_loop<Tab, true, true, false>(tab, sa, sa, n, ca, cm, g, dst, tid, nth);
+        else
+            gather_loop<Tab, false, true, false>(tab, sa, sa, n, ca, cm, g, dst, tid, nth);
+        return;
+    }
+    const int64_t moff = mt[0];
+    const int16_t *sm = pcm + (size_t)moff * 4;
+    switch ((int)(off & 1) | ((int)(moff & 1) << 1)) {           // uniform over the workgroup
+    case 0: gather_loop<Tab, true, true, true>(tab, sa, sm, n, ca, cm, g, dst, tid, nth); break;
+    case 1: gather_loop<Tab, false, true, true>(tab, sa, sm, n, ca, cm, g, dst, tid, nth); break;
+    case 2: gather_loop<Tab, true, false, true>(tab, sa, sm, n, ca, cm, g, dst, tid, nth); break;
+    default: gather_loop<Tab, false, false, true>(tab, sa, sm, n, ca, cm, g, dst, tid, nth); break;
     }
 }
 
@@ -150,15 +190,20 @@ struct CorpusLabelGeom {
     long n_events, cap;
 };
 
-// The label window of lane (b, e): event ev_lo + e of the item's range, its frame relative to the window, the rotated angles
-// and its az / el cell masks.  Returns the number of rows it produces (0: no event, or its frame is past the label frames).
-// corpus_event_at: the same for event e of the item row ``it`` (the mixing labels call it with either source's row).
+// an item or mate row as a range of the event table: true when the range or the combination is outside the corpus
+__device__ __forceinline__ bool corpus_row_bad(const int64_t *__restrict__ row, int max_events, long n_events) {
+    const int64_t ev_lo = row[2], ev_n = row[3], comb = row[4];
+    return ev_lo < 0 || ev_n < 0 || ev_n > max_events || ev_lo > n_events - ev_n || comb >= 16;
+}
+
+// Event e of the item (or mate) row ``it``: its frame relative to the row's window, the rotated angles and its az / el cell
+// masks.  Returns the number of rows it produces (0: no event, or its frame is past the label frames).
 __device__ int corpus_event_at(const double *__restrict__ events, const int64_t *__restrict__ it,
                                const double *__restrict__ bounds, const CorpusRot &rot, const CorpusLabelGeom &g, int e,
                                int &frame, int &cls, double &az, double &el, unsigned long long &az_bits,
                                unsigned long long &el_bits, bool &bad) {
     const int64_t frame_off = it[1], ev_lo = it[2], ev_n = it[3], comb = it[4];
-    bad = ev_lo < 0 || ev_n < 0 || ev_n > g.max_events || ev_lo > g.n_events - ev_n || comb >= 16;
+    bad = corpus_row_bad(it, g.max_events, g.n_events);
     if (bad || e >= ev_n) return 0;
     const double *ev = events + (size_t)(ev_lo + e) * 4;
     const int64_t fr = (int64_t)ev[0] - frame_off;
@@ -193,45 +238,92 @@ __device__ int corpus_event_at(const double *__restrict__ events, const int64_t 
     return naz * nel;
 }
 
-__device__ int corpus_event(const double *__restrict__ events, const int64_t *__restrict__ items,
-                            const double *__restrict__ bounds, const CorpusRot &rot, const CorpusLabelGeom &g, long lane,
-                            int &frame, int &cls, double &az, double &el, unsigned long long &az_bits,
-                            unsigned long long &el_bits, bool &bad) {
-    const int b = (int)(lane / g.max_events), e = (int)(lane % g.max_events);
-    return corpus_event_at(events, items + (size_t)b * ADYOLO_CORPUS_ITEM_WORDS, bounds, rot, g, e, frame, cls, az, el, az_bits,
-                           el_bits, bad);
+// The lane decoder of both AD-YOLO kernels -> rows of the lane (as corpus_event_at); b: its item; at: the word of ws that holds
+// its count, then its scanned offset: the item's first word plus the lane's place among the item's lanes.
+// Plain: lanes are (item, event), max_events per item, and a lane's place is the lane itself.
+// MIX: lanes are (item, source, event), 2 max_events per item, the item's events first.  Both sources' events are frame-sorted
+// (corpus.load_chunked_split), so the place of an event in the merged order of augmentations.merge_labels -- frames ascending,
+// the item's events before the mate's within a frame -- is its own index plus the number of the other source's events before
+// it: those with a smaller window-relative frame for an item lane, a smaller or equal one for a mate lane (a binary search).
+// The lanes without an event take the places behind the events, so that every place of the item's 2 max_events is written
+// once.  An item whose own row or whose mate row is bad has no rows at all.
+template <bool MIX>
+__device__ int corpus_lane(const double *__restrict__ events, const int64_t *__restrict__ items,
+                           const int64_t *__restrict__ mates, const double *__restrict__ bounds, const CorpusRot &rot,
+                           const CorpusLabelGeom &g, long lane, int &b, long &at, int &frame, int &cls, double &az, double &el,
+                           unsigned long long &az_bits, unsigned long long &el_bits, bool &bad) {
+    const int me = g.max_events, per = MIX ? 2 * me : me;
+    b = (int)(lane / per);
+    const int r = (int)(lane - (long)b * per);
+    const int64_t *it = items + (size_t)b * ADYOLO_CORPUS_ITEM_WORDS;
+    if (!MIX) {
+        at = lane;
+        return corpus_event_at(events, it, bounds, rot, g, r, frame, cls, az, el, az_bits, el_bits, bad);
+    }
+    const int src = r >= me ? 1 : 0, e = r - src * me;
+    const int64_t *mt = mates + (size_t)b * ADYOLO_CORPUS_ITEM_WORDS;
+    const bool has_mate = mt[0] != -1;
+    bad = corpus_row_bad(it, me, g.n_events) || (has_mate && corpus_row_bad(mt, me, g.n_events));
+    const int n_a = bad ? 0 : (int)it[3], n_m = bad || !has_mate ? 0 : (int)mt[3];
+    if (e >= (src ? n_m : n_a)) {
+        at = lane - r + (src ? me + e : n_m + e);
+        return 0;
+    }
+    const int64_t *own = src ? mt : it, *other = src ? it : mt;
+    const int64_t f = (int64_t)events[(size_t)(own[2] + e) * 4] - own[1];
+    const double *oev = events + (size_t)other[2] * 4;
+    const int64_t ooff = other[1];
+    int lo = 0, hi = src ? n_a : n_m;
+    while (lo < hi) {                                            // the other source's events that come first
+        const int mid = (lo + hi) >> 1;
+        const int64_t fo = (int64_t)oev[(size_t)mid * 4] - ooff;
+        if (src ? fo <= f : fo < f)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    at = lane - r + e + lo;
+    bool own_bad;
+    return corpus_event_at(events, own, bounds, rot, g, e, frame, cls, az, el, az_bits, el_bits, own_bad);
 }
 
 constexpr int CORPUS_SCAN_THREADS = 1024;
 
-// one workgroup: ws[lane] = exclusive offset of lane's rows; count[0] = total rows; status |= overflow / bad item
-__global__ __launch_bounds__(CORPUS_SCAN_THREADS) void corpus_count_scan_kernel(const double *__restrict__ events,
-                                                                               const int64_t *__restrict__ items,
-                                                                               const double *__restrict__ bounds, CorpusRot rot,
-                                                                               CorpusLabelGeom g, int *__restrict__ ws,
-                                                                               int *__restrict__ count,
-                                                                               int *__restrict__ status) {
+// one workgroup: ws[at] = exclusive offset of the rows of the lane decoded to ``at``; count[0] = total rows; status |= overflow /
+// bad item
+template <bool MIX>
+__global__ __launch_bounds__(CORPUS_SCAN_THREADS) void corpus_count_scan_kernel(
+    const double *__restrict__ events, const int64_t *__restrict__ items, const int64_t *__restrict__ mates,
+    const double *__restrict__ bounds, CorpusRot rot, CorpusLabelGeom g, int *ws, int *__restrict__ count,
+    int *__restrict__ status) {
     __shared__ int part[CORPUS_SCAN_THREADS];
     __shared__ int any_bad;
     const int t = threadIdx.x;
     if (t == 0) any_bad = 0;
     __syncthreads();
-    const long lanes = (long)g.B * g.max_events;
+    const long lanes = (long)g.B * (MIX ? 2 : 1) * g.max_events;
     const long chunk = (lanes + CORPUS_SCAN_THREADS - 1) / CORPUS_SCAN_THREADS;
     const long s0 = t * chunk, s1 = s0 + chunk < lanes ? s0 + chunk : lanes;
     int sum = 0;
     bool bad_here = false;
-    for (long s = s0; s < s1; ++s) {
-        int frame, cls;
+    for (long s = s0; s < s1; ++s) {                             // every lane's row count, at its word
+        int b, frame, cls;
+        long at;
         double az, el;
         unsigned long long ab, eb;
         bool bad;
-        const int c = corpus_event(events, items, bounds, rot, g, s, frame, cls, az, el, ab, eb, bad);
+        const int c = corpus_lane<MIX>(events, items, mates, bounds, rot, g, s, b, at, frame, cls, az, el, ab, eb, bad);
         bad_here |= bad;
-        ws[s] = c;
-        sum += c;
+        ws[at] = c;
+        sum += c;                                                // plain: at == s, so this is the chunk's sum
     }
     if (bad_here) any_bad = 1;
+    if (MIX) {                                                   // the chunk's words were written from other threads' lanes
+        __threadfence_block();
+        __syncthreads();
+        sum = 0;
+        for (long s = s0; s < s1; ++s) sum += ws[s];
+    }
     part[t] = sum;
     __syncthreads();
     for (int o = 1; o < CORPUS_SCAN_THREADS; o <<= 1) {          // inclusive Hillis-Steele scan of the chunk sums
@@ -255,22 +347,26 @@ __global__ __launch_bounds__(CORPUS_SCAN_THREADS) void corpus_count_scan_kernel(
     }
 }
 
-// grid-stride over the lanes (rows of each event, cells in (gi, gj) order) and over the capacity (b = -1 past the total)
+// grid-stride over the lanes (rows of each event, cells in (gi, gj) order) and over the capacity (b = -1 past the total);
+// column 0 of a row is the item, whichever source the event comes from
+template <bool MIX>
 __global__ __launch_bounds__(256) void corpus_rows_kernel(const double *__restrict__ events, const int64_t *__restrict__ items,
+                                                          const int64_t *__restrict__ mates,
                                                           const double *__restrict__ bounds, CorpusRot rot, CorpusLabelGeom g,
                                                           const int *__restrict__ ws, const int *__restrict__ count,
                                                           float *__restrict__ target) {
     const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, nth = (long)gridDim.x * blockDim.x;
-    const long lanes = (long)g.B * g.max_events;
+    const long lanes = (long)g.B * (MIX ? 2 : 1) * g.max_events;
     for (long s = tid; s < lanes; s += nth) {
-        int frame, cls;
+        int b, frame, cls;
+        long at;
         double az, el;
         unsigned long long ab, eb;
         bool bad;
-        const int c = corpus_event(events, items, bounds, rot, g, s, frame, cls, az, el, ab, eb, bad);
+        const int c = corpus_lane<MIX>(events, items, mates, bounds, rot, g, s, b, at, frame, cls, az, el, ab, eb, bad);
         if (c == 0) continue;
-        long r = ws[s];
-        const float fb = (float)(s / g.max_events), ft = (float)frame, fc = (float)cls, fu = (float)az, fv = (float)el;
+        long r = ws[at];
+        const float fb = (float)b, ft = (float)frame, fc = (float)cls, fu = (float)az, fv = (float)el;
         for (int i = 0; i < g.Gaz; ++i) {
             if (!((ab >> i) & 1ull)) continue;
             for (int j = 0; j < g.Gel; ++j) {
@@ -293,394 +389,49 @@ __global__ __launch_bounds__(256) void corpus_rows_kernel(const double *__restri
 constexpr int CW_THREADS = 256;
 constexpr int CW_FRAMES = 8;                   // label frames per workgroup
 constexpr int CW_MAX_CLASSES = 256;
-constexpr int CW_EV_CACHE = 512;               // classes of a tile's events held in LDS (the rest are read from memory)
+constexpr int CW_EV_CACHE = 512;               // classes of a tile's events held in LDS per source (the rest are read from memory)
+constexpr int CW_SRC_BIT = 30;                 // MIX: a picked event carries its source in this bit of its index (n_events < 2^30)
 
 struct CorpusClasswiseGeom {
     int B, max_events, n_label_frames, C, format, row;   // row: floats per label frame (4 C, 3 C or 24 C)
     long n_events;
 };
 
-// grid (label-frame tiles, B).  LDS: lb[i] = the first event of the item at or after frame t0 + i; cls[] = the classes of the
-// tile's events (-1: outside [0, C)); pick[i][c] = {count of class c in frame t0 + i, its first three events} (ADPIT) or {its
-// last event, ...} (SEDDOA / ACCDOA), -1 where there is none.
+// grid (label-frame tiles, B).  NS sources: the item, and with MIX its mate when it has one.  LDS: lb[s][i] = the first event
+// of source s at or after frame t0 + i; cls[s][] = the classes of the tile's events (-1: outside [0, C)); pick[i][c] = {count of
+// class c in frame t0 + i, its first three events} (ADPIT) or {its last event, ...} (SEDDOA / ACCDOA), -1 where there is none.
+// A (frame, class) output picks over the item's range, then the mate's (the order of merge_labels); every picked event carries
+// its source, because its direction vector is read from the xyz slot of its own source's combination.
+template <bool MIX>
 __global__ __launch_bounds__(CW_THREADS) void corpus_classwise_kernel(const double *__restrict__ events,
                                                                       const float *__restrict__ xyz,
-                                                                      const int64_t *__restrict__ items, CorpusClasswiseGeom g,
+                                                                      const int64_t *__restrict__ items,
+                                                                      const int64_t *__restrict__ mates, CorpusClasswiseGeom g,
                                                                       float *__restrict__ target, int *__restrict__ status) {
+    constexpr int NS = MIX ? 2 : 1;
     extern __shared__ int pick[];                // [CW_FRAMES][C][4]
-    __shared__ int lb[CW_FRAMES + 1];
-    __shared__ int cls[CW_EV_CACHE];
+    __shared__ int lb[NS][CW_FRAMES + 1];
+    __shared__ int cls[NS][CW_EV_CACHE];
     const int b = blockIdx.y, t0 = blockIdx.x * CW_FRAMES, tid = threadIdx.x;
     const int nf = g.n_label_frames - t0 < CW_FRAMES ? g.n_label_frames - t0 : CW_FRAMES;
-    const int64_t *it = items + (size_t)b * ADYOLO_CORPUS_ITEM_WORDS;
-    const int64_t frame_off = it[1], ev_lo = it[2], ev_n = it[3], comb = it[4];
+    const int64_t *rows[NS];
+    rows[0] = items + (size_t)b * ADYOLO_CORPUS_ITEM_WORDS;
+    if (MIX) rows[NS - 1] = mates + (size_t)b * ADYOLO_CORPUS_ITEM_WORDS;
+    const int ns = MIX && rows[NS - 1][0] != -1 ? 2 : 1;
     float *dst = target + ((size_t)b * g.n_label_frames + t0) * g.row;
     const int n_out = nf * g.row;
-    if (ev_lo < 0 || ev_n < 0 || ev_n > g.max_events || ev_lo > g.n_events - ev_n || comb >= 16) {
-        if (blockIdx.x == 0 && tid == 0) atomicOr(status, ADYOLO_CORPUS_BAD_ITEM);
-        for (int p = tid; p < n_out; p += CW_THREADS) dst[p] = 0.f;
-        return;
-    }
-    const double *ev = events + (size_t)ev_lo * 4;
-    const int n = (int)ev_n;
-    if (tid <= nf) lb[tid] = n;
-    __syncthreads();
-    // the item's events are frame-sorted: lb[i] is written by the one event whose frame is the first to reach t0 + i (one round
-    // of independent loads, no binary search); it stays n where none does.  Unsorted input can leave lb out of order: every
-    // range below is then empty or still inside [0, n).
-    const double base = (double)(frame_off + t0);
-    for (int e = tid; e < n; e += CW_THREADS) {
-        const double fe = ev[(size_t)e * 4] - base;
-        const double fp = e > 0 ? ev[(size_t)(e - 1) * 4] - base : -1.0;
-        const double lo = fp < 0.0 ? 0.0 : floor(fp) + 1.0, hi = fe > (double)nf ? (double)nf : floor(fe);
-        if (lo <= hi)
-            for (int i = (int)lo; i <= (int)hi; ++i) lb[i] = e;
-    }
-    __syncthreads();
-    const int C = g.C, e0 = lb[0], e1 = lb[nf];
-    for (int e = e0 + tid; e < e1; e += CW_THREADS) {             // the tile's events: classes checked, the first ones cached
-        const double cd = ev[(size_t)e * 4 + 1];
-        const bool ok = cd >= 0.0 && cd < (double)C;
-        if (!ok) atomicOr(status, ADYOLO_CORPUS_BAD_CLASS);
-        if (e - e0 < CW_EV_CACHE) cls[e - e0] = ok ? (int)cd : -1;
-    }
-    __syncthreads();
-    const bool adpit = g.format == ADYOLO_CORPUS_ADPIT;
-    for (int p = tid; p < nf * C; p += CW_THREADS) {
-        const int i = p / C, c = p - i * C;
-        int cnt = 0, last = -1, first[3] = {-1, -1, -1};
-        for (int e = lb[i]; e < lb[i + 1]; ++e) {                // file order within the frame
-            int ce;
-            if (e < e1 && (unsigned)(e - e0) < (unsigned)CW_EV_CACHE) {
-                ce = cls[e - e0];
-            } else {
-                const double cd = ev[(size_t)e * 4 + 1];
-                ce = cd >= 0.0 && cd < (double)C ? (int)cd : -1;
-            }
-            if (ce == c) {
-                if (cnt < 3) first[cnt] = (int)ev_lo + e;
-                last = (int)ev_lo + e;
-                ++cnt;
-            }
-        }
-        int *q = pick + p * 4;
-        q[0] = adpit ? cnt : last;
-        q[1] = first[0];
-        q[2] = first[1];
-        q[3] = first[2];
-    }
-    __syncthreads();
-    // every position r of a frame's row is owned by one thread, its class / component / track slot worked out once (no
-    // division per element); the frames of the tile are written one after the other, each row by consecutive threads
-    const size_t slot = comb < 0 ? 0 : (size_t)comb + 1;
-    for (int r = tid; r < g.row; r += CW_THREADS) {
-        int c, k, s = 0;                       // class, component (-1: the activity 1.0, else x / y / z), ADPIT track slot
-        if (adpit) {
-            s = r / (4 * C);
-            const int rr = r - s * 4 * C;
-            k = rr / C - 1;
-            c = rr - (k + 1) * C;
-        } else {
-            const int part = r / C;
-            c = r - part * C;
-            k = g.format == ADYOLO_CORPUS_SEDDOA ? part - 1 : part;
-        }
-        // ADPIT: slot 0 takes the class's event when it has one, slots 1-2 its two, slots 3-5 the first three of three or more
-        const int lo_cnt = s == 0 ? 1 : s <= 2 ? 2 : 3, hi_cnt = s == 0 ? 1 : s <= 2 ? 2 : 0x7fffffff;
-        const int j = s == 0 ? 0 : s <= 2 ? s - 1 : s - 3;
-        for (int i = 0; i < nf; ++i) {
-            const int *q = pick + (i * C + c) * 4;
-            const int e = adpit ? (q[0] >= lo_cnt && q[0] <= hi_cnt ? q[1 + j] : -1) : q[0];
-            dst[(size_t)i * g.row + r] =
-                e < 0 ? 0.f : k < 0 ? 1.f : xyz[((size_t)e * ADYOLO_CORPUS_XYZ_SLOTS + slot) * 3 + k];
-        }
-    }
-}
-
-// ================================================================================================ time-domain mixing
-// A mate row has the layout of an item row; offset (word 0) == -1: the item has no mate; word 6: the float32 bits of the gain.
-
-// One source's conversion, uniform over the workgroup (scalar registers): the signs and the swap of pcm_rot, or the two byte
-// selectors of pcm_swap.  mix_source returns false for a combination that is no symmetry of the array (MIC table only).
-struct CorpusMixSrc {
-    float sy, sz, sx;
-    bool swap;
-    unsigned sel_lo, sel_hi;
-};
-
-__device__ __forceinline__ bool mix_source(const CorpusRot &rot, int64_t comb, CorpusMixSrc &s) {
-    s.sy = 1.f; s.sz = 1.f; s.sx = 1.f; s.swap = false; s.sel_lo = 0u; s.sel_hi = 0u;
-    if (comb >= 0) {
-        s.sy = rot.c[comb][0]; s.sz = rot.c[comb][1]; s.sx = rot.c[comb][2]; s.swap = rot.c[comb][3] != 0.f;
-    }
-    return true;
-}
-
-__device__ __forceinline__ bool mix_source(const CorpusMicSrc &tab, int64_t comb, CorpusMixSrc &s) {
-    unsigned w = 0x03020100u;                               // identity, as in corpus_gather_mic_kernel
-    if (comb >= 0) w = tab.w[comb];
-    const unsigned s0 = w & 3u, s1 = (w >> 8) & 3u, s2 = (w >> 16) & 3u, s3 = (w >> 24) & 3u;
-    s.sy = 1.f; s.sz = 1.f; s.sx = 1.f; s.swap = false;
-    s.sel_lo = (s0 * 0x0202u + 0x0100u) | ((s1 * 0x0202u + 0x0100u) << 16);
-    s.sel_hi = (s2 * 0x0202u + 0x0100u) | ((s3 * 0x0202u + 0x0100u) << 16);
-    return w != ADYOLO_MIC_SWAP_NONE;
-}
-
-__device__ __forceinline__ float4 mix_conv(const CorpusRot &, int lo, int hi, const CorpusMixSrc &s) {
-    return pcm_rot(lo, hi, s.sy, s.sz, s.sx, s.swap);
-}
-__device__ __forceinline__ float4 mix_conv(const CorpusMicSrc &, int lo, int hi, const CorpusMixSrc &s) {
-    return pcm_swap(lo, hi, s.sel_lo, s.sel_hi);
-}
-
-// frames 2 i and 2 i + 1 of a window: one 16-byte load where the window starts on an even frame, two 8-byte loads where not
-template <bool EVEN>
-__device__ __forceinline__ int4 mix_load2(const int16_t *__restrict__ src, long i) {
-    if (EVEN) return reinterpret_cast<const int4 *>(src)[i];
-    const int2 *s2 = reinterpret_cast<const int2 *>(src);
-    const int2 a = s2[2 * i], c = s2[2 * i + 1];
-    return make_int4(a.x, a.y, c.x, c.y);
-}
-
-// the streaming loop for one parity of the item's and of the mate's offset; MIXED false: the mate is not read at all
-template <class Tab, bool A_EVEN, bool M_EVEN, bool MIXED>
-__device__ __forceinline__ void mix_loop(const Tab &tab, const int16_t *__restrict__ sa, const int16_t *__restrict__ sm, long n,
-                                         const CorpusMixSrc &ca, const CorpusMixSrc &cm, float g, float4 *__restrict__ dst,
-                                         long tid, long nth) {
-    const long n2 = n >> 1;
-    for (long i = tid; i < n2; i += nth) {
-        const int4 va = mix_load2<A_EVEN>(sa, i);
-        float4 o0 = mix_conv(tab, va.x, va.y, ca), o1 = mix_conv(tab, va.z, va.w, ca);
-        if (MIXED) {
-            const int4 vm = mix_load2<M_EVEN>(sm, i);
-            o0 = mix_add(o0, mix_conv(tab, vm.x, vm.y, cm), g);
-            o1 = mix_add(o1, mix_conv(tab, vm.z, vm.w, cm), g);
-        }
-        dst[2 * i] = o0;
-        dst[2 * i + 1] = o1;
-    }
-    if ((n & 1) && tid == 0) {
-        const int2 va = reinterpret_cast<const int2 *>(sa)[n - 1];
-        float4 o = mix_conv(tab, va.x, va.y, ca);
-        if (MIXED) {
-            const int2 vm = reinterpret_cast<const int2 *>(sm)[n - 1];
-            o = mix_add(o, mix_conv(tab, vm.x, vm.y, cm), g);
-        }
-        dst[n - 1] = o;
-    }
-}
-
-// grid (blocks per item, B), the grid of corpus_gather_kernel.  Tab = CorpusRot (FOA) or CorpusMicSrc (MIC).  A bad item or a
-// bad mate: zeros for the whole sample and status bit 2; no mate: the plain gather's bits, and nothing of the mate row but its
-// offset is read.
-template <class Tab>
-__global__ __launch_bounds__(256) void corpus_gather_mix_kernel(const int16_t *__restrict__ pcm, long n_total,
-                                                                const int64_t *__restrict__ items,
-                                                                const int64_t *__restrict__ mates, long n, Tab tab,
-                                                                float4 *__restrict__ out, int *__restrict__ status) {
-    const int b = blockIdx.y;
-    const int64_t *it = items + (size_t)b * ADYOLO_CORPUS_ITEM_WORDS, *mt = mates + (size_t)b * ADYOLO_CORPUS_ITEM_WORDS;
-    const int64_t off = it[0], comb = it[4], moff = mt[0];
-    const bool mixed = moff != -1;
-    float4 *dst = out + (size_t)b * n;
-    const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, nth = (long)gridDim.x * blockDim.x;
-    CorpusMixSrc ca, cm = {1.f, 1.f, 1.f, false, 0u, 0u};
-    float g = 0.f;
-    bool bad = off < 0 || off > n_total - n || comb >= 16 || !mix_source(tab, comb, ca);
-    if (!bad && mixed) {
-        const int64_t mcomb = mt[4];
-        bad = moff < 0 || moff > n_total - n || mcomb >= 16 || !mix_source(tab, mcomb, cm);
-        g = __int_as_float((int)mt[6]);
-    }
-    if (bad) {
-        if (tid == 0 && status) atomicOr(status, ADYOLO_CORPUS_BAD_ITEM);
-        for (long i = tid; i < n; i += nth) dst[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        return;
-    }
-    const int16_t *sa = pcm + (size_t)off * 4;
-    if (!mixed) {
-        if ((off & 1) == 0)
-            mix_loop<Tab, true, true, false>(tab, sa, sa, n, ca, cm, g, dst, tid, nth);
-        else
-            mix_loop<Tab, false, true, false>(tab, sa, sa, n, ca, cm, g, dst, tid, nth);
-        return;
-    }
-    const int16_t *sm = pcm + (size_t)moff * 4;
-    switch ((int)(off & 1) | ((int)(moff & 1) << 1)) {           // uniform over the workgroup
-    case 0: mix_loop<Tab, true, true, true>(tab, sa, sm, n, ca, cm, g, dst, tid, nth); break;
-    case 1: mix_loop<Tab, false, true, true>(tab, sa, sm, n, ca, cm, g, dst, tid, nth); break;
-    case 2: mix_loop<Tab, true, false, true>(tab, sa, sm, n, ca, cm, g, dst, tid, nth); break;
-    default: mix_loop<Tab, false, false, true>(tab, sa, sm, n, ca, cm, g, dst, tid, nth); break;
-    }
-}
-
-// ---- AD-YOLO rows of a mixed batch.  Lanes are (item, source, event): 2 max_events per item, the item's events first.  Both
-// sources' events are frame-sorted (corpus.load_chunked_split), so the place of an event in the merged order of
-// augmentations.merge_labels -- frames ascending, the item's events before the mate's within a frame -- is its own index plus
-// the number of the other source's events before it: those with a smaller window-relative frame for an item lane, a smaller or
-// equal one for a mate lane (a binary search).  The lanes without an event take the places behind the events, so that every
-// place of the item's 2 max_events is written once.  An item whose own row or whose mate row is bad has no rows at all.
-__device__ __forceinline__ bool corpus_row_bad(const int64_t *__restrict__ row, const CorpusLabelGeom &g) {
-    const int64_t ev_lo = row[2], ev_n = row[3], comb = row[4];
-    return ev_lo < 0 || ev_n < 0 || ev_n > g.max_events || ev_lo > g.n_events - ev_n || comb >= 16;
-}
-
-// -> rows of the lane (as corpus_event); place: its place among the item's 2 max_events; b: its item
-__device__ int corpus_mix_event(const double *__restrict__ events, const int64_t *__restrict__ items,
-                                const int64_t *__restrict__ mates, const double *__restrict__ bounds, const CorpusRot &rot,
-                                const CorpusLabelGeom &g, long lane, int &b, int &place, int &frame, int &cls, double &az,
-                                double &el, unsigned long long &az_bits, unsigned long long &el_bits, bool &bad) {
-    const int me = g.max_events, per = 2 * me;
-    b = (int)(lane / per);
-    const int r = (int)(lane - (long)b * per), src = r >= me ? 1 : 0, e = r - src * me;
-    const int64_t *it = items + (size_t)b * ADYOLO_CORPUS_ITEM_WORDS, *mt = mates + (size_t)b * ADYOLO_CORPUS_ITEM_WORDS;
-    const bool has_mate = mt[0] != -1;
-    bad = corpus_row_bad(it, g) || (has_mate && corpus_row_bad(mt, g));
-    const int n_a = bad ? 0 : (int)it[3], n_m = bad || !has_mate ? 0 : (int)mt[3];
-    if (e >= (src ? n_m : n_a)) {
-        place = src ? me + e : n_m + e;
-        return 0;
-    }
-    const int64_t *own = src ? mt : it, *other = src ? it : mt;
-    const int64_t f = (int64_t)events[(size_t)(own[2] + e) * 4] - own[1];
-    const double *oev = events + (size_t)other[2] * 4;
-    const int64_t ooff = other[1];
-    int lo = 0, hi = src ? n_a : n_m;
-    while (lo < hi) {                                            // the other source's events that come first
-        const int mid = (lo + hi) >> 1;
-        const int64_t fo = (int64_t)oev[(size_t)mid * 4] - ooff;
-        if (src ? fo <= f : fo < f)
-            lo = mid + 1;
-        else
-            hi = mid;
-    }
-    place = e + lo;
-    bool own_bad;
-    return corpus_event_at(events, own, bounds, rot, g, e, frame, cls, az, el, az_bits, el_bits, own_bad);
-}
-
-// one workgroup, as corpus_count_scan_kernel; ws[b * 2 max_events + place] = exclusive row offset of that place
-__global__ __launch_bounds__(CORPUS_SCAN_THREADS) void corpus_mix_count_scan_kernel(
-    const double *__restrict__ events, const int64_t *__restrict__ items, const int64_t *__restrict__ mates,
-    const double *__restrict__ bounds, CorpusRot rot, CorpusLabelGeom g, int *ws, int *__restrict__ count,
-    int *__restrict__ status) {
-    __shared__ int part[CORPUS_SCAN_THREADS];
-    __shared__ int any_bad;
-    const int t = threadIdx.x;
-    if (t == 0) any_bad = 0;
-    __syncthreads();
-    const long lanes = (long)g.B * 2 * g.max_events;
-    const long chunk = (lanes + CORPUS_SCAN_THREADS - 1) / CORPUS_SCAN_THREADS;
-    const long s0 = t * chunk, s1 = s0 + chunk < lanes ? s0 + chunk : lanes;
-    bool bad_here = false;
-    for (long s = s0; s < s1; ++s) {                             // every lane's row count, at its merged place
-        int b, place, frame, cls;
-        double az, el;
-        unsigned long long ab, eb;
-        bool bad;
-        const int c = corpus_mix_event(events, items, mates, bounds, rot, g, s, b, place, frame, cls, az, el, ab, eb, bad);
-        bad_here |= bad;
-        ws[(long)b * 2 * g.max_events + place] = c;
-    }
-    if (bad_here) any_bad = 1;
-    __threadfence_block();
-    __syncthreads();
-    int sum = 0;
-    for (long s = s0; s < s1; ++s) sum += ws[s];
-    part[t] = sum;
-    __syncthreads();
-    for (int o = 1; o < CORPUS_SCAN_THREADS; o <<= 1) {
-        const int v = t >= o ? part[t - o] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    int run = part[t] - sum;
-    for (long s = s0; s < s1; ++s) {
-        const int c = ws[s];
-        ws[s] = run;
-        run += c;
-    }
-    if (t == CORPUS_SCAN_THREADS - 1) {
-        const int total = part[t];
-        count[0] = total;
-        int bits = any_bad ? ADYOLO_CORPUS_BAD_ITEM : 0;
-        if ((long)total > g.cap) bits |= ADYOLO_CORPUS_OVERFLOW;
-        if (bits && status) atomicOr(status, bits);
-    }
-}
-
-// as corpus_rows_kernel; column 0 of a row is the item, whichever source the event comes from
-__global__ __launch_bounds__(256) void corpus_mix_rows_kernel(const double *__restrict__ events,
-                                                              const int64_t *__restrict__ items,
-                                                              const int64_t *__restrict__ mates,
-                                                              const double *__restrict__ bounds, CorpusRot rot, CorpusLabelGeom g,
-                                                              const int *__restrict__ ws, const int *__restrict__ count,
-                                                              float *__restrict__ target) {
-    const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, nth = (long)gridDim.x * blockDim.x;
-    const long lanes = (long)g.B * 2 * g.max_events;
-    for (long s = tid; s < lanes; s += nth) {
-        int b, place, frame, cls;
-        double az, el;
-        unsigned long long ab, eb;
-        bool bad;
-        const int c = corpus_mix_event(events, items, mates, bounds, rot, g, s, b, place, frame, cls, az, el, ab, eb, bad);
-        if (c == 0) continue;
-        long r = ws[(long)b * 2 * g.max_events + place];
-        const float fb = (float)b, ft = (float)frame, fc = (float)cls, fu = (float)az, fv = (float)el;
-        for (int i = 0; i < g.Gaz; ++i) {
-            if (!((ab >> i) & 1ull)) continue;
-            for (int j = 0; j < g.Gel; ++j) {
-                if (!((eb >> j) & 1ull)) continue;
-                if (r < g.cap) {
-                    float *row = target + (size_t)r * 7;
-                    row[0] = fb; row[1] = ft; row[2] = (float)i; row[3] = (float)j; row[4] = fc; row[5] = fu; row[6] = fv;
-                }
-                ++r;
-            }
-        }
-    }
-    const long total = count[0];
-    for (long r = total + tid; r < g.cap; r += nth) {
-        float *row = target + (size_t)r * 7;
-        row[0] = -1.f; row[1] = 0.f; row[2] = 0.f; row[3] = 0.f; row[4] = 0.f; row[5] = 0.f; row[6] = 0.f;
-    }
-}
-
-// ---- the dense class-wise targets of a mixed batch: corpus_classwise_kernel over two sources.  Each source has its own frame
-// ranges lb[s] and class cache cls[s]; a (frame, class) output picks over the item's range, then the mate's (the order of
-// merge_labels), and every picked event carries its source in bit 30 of its index (n_events < 2^30), because its direction
-// vector is read from the xyz slot of its own source's combination.  An item without a mate has one source: the bits of
-// corpus_classwise_kernel.
-constexpr int CW_SRC_BIT = 30;
-
-__global__ __launch_bounds__(CW_THREADS) void corpus_classwise_mix_kernel(const double *__restrict__ events,
-                                                                          const float *__restrict__ xyz,
-                                                                          const int64_t *__restrict__ items,
-                                                                          const int64_t *__restrict__ mates,
-                                                                          CorpusClasswiseGeom g, float *__restrict__ target,
-                                                                          int *__restrict__ status) {
-    extern __shared__ int pick[];                // [CW_FRAMES][C][4]
-    __shared__ int lb[2][CW_FRAMES + 1];
-    __shared__ int cls[2][CW_EV_CACHE];
-    const int b = blockIdx.y, t0 = blockIdx.x * CW_FRAMES, tid = threadIdx.x;
-    const int nf = g.n_label_frames - t0 < CW_FRAMES ? g.n_label_frames - t0 : CW_FRAMES;
-    const int64_t *rows[2] = {items + (size_t)b * ADYOLO_CORPUS_ITEM_WORDS, mates + (size_t)b * ADYOLO_CORPUS_ITEM_WORDS};
-    const int ns = rows[1][0] != -1 ? 2 : 1;
-    float *dst = target + ((size_t)b * g.n_label_frames + t0) * g.row;
-    const int n_out = nf * g.row;
-    int64_t frame_off[2] = {0, 0}, ev_lo[2] = {0, 0};
-    int n[2] = {0, 0};
-    size_t slot[2] = {0, 0};
+    int64_t frame_off[NS] = {}, ev_lo[NS] = {};
+    int n[NS] = {};
+    size_t slot[NS] = {};
     bool bad = false;
 #pragma unroll
-    for (int s = 0; s < 2; ++s) {
+    for (int s = 0; s < NS; ++s) {
         if (s >= ns) break;
-        const int64_t lo = rows[s][2], cnt = rows[s][3], comb = rows[s][4];
-        bad |= lo < 0 || cnt < 0 || cnt > g.max_events || lo > g.n_events - cnt || comb >= 16;
+        bad |= corpus_row_bad(rows[s], g.max_events, g.n_events);
+        const int64_t comb = rows[s][4];
         frame_off[s] = rows[s][1];
-        ev_lo[s] = lo;
-        n[s] = (int)cnt;
+        ev_lo[s] = rows[s][2];
+        n[s] = (int)rows[s][3];
         slot[s] = comb < 0 ? 0 : (size_t)comb + 1;
     }
     if (bad) {
@@ -689,12 +440,15 @@ __global__ __launch_bounds__(CW_THREADS) void corpus_classwise_mix_kernel(const 
         return;
     }
     if (tid <= nf) {
-        lb[0][tid] = n[0];
-        lb[1][tid] = n[1];
+#pragma unroll
+        for (int s = 0; s < NS; ++s) lb[s][tid] = n[s];
     }
     __syncthreads();
+    // a source's events are frame-sorted: lb[s][i] is written by the one event whose frame is the first to reach t0 + i (one
+    // round of independent loads, no binary search); it stays n[s] where none does.  Unsorted input can leave lb out of order:
+    // every range below is then empty or still inside [0, n[s]).
 #pragma unroll
-    for (int s = 0; s < 2; ++s) {                                 // as in corpus_classwise_kernel, per source
+    for (int s = 0; s < NS; ++s) {
         if (s >= ns) break;
         const double *ev = events + (size_t)ev_lo[s] * 4;
         const double base = (double)(frame_off[s] + t0);
@@ -708,16 +462,18 @@ __global__ __launch_bounds__(CW_THREADS) void corpus_classwise_mix_kernel(const 
     }
     __syncthreads();
     const int C = g.C;
+    int e0[NS] = {}, e1[NS] = {};                                 // the tile's events of each source
 #pragma unroll
-    for (int s = 0; s < 2; ++s) {
+    for (int s = 0; s < NS; ++s) {                                // their classes checked, the first ones cached
         if (s >= ns) break;
         const double *ev = events + (size_t)ev_lo[s] * 4;
-        const int e0 = lb[s][0], e1 = lb[s][nf];
-        for (int e = e0 + tid; e < e1; e += CW_THREADS) {
+        e0[s] = lb[s][0];
+        e1[s] = lb[s][nf];
+        for (int e = e0[s] + tid; e < e1[s]; e += CW_THREADS) {
             const double cd = ev[(size_t)e * 4 + 1];
             const bool ok = cd >= 0.0 && cd < (double)C;
             if (!ok) atomicOr(status, ADYOLO_CORPUS_BAD_CLASS);
-            if (e - e0 < CW_EV_CACHE) cls[s][e - e0] = ok ? (int)cd : -1;
+            if (e - e0[s] < CW_EV_CACHE) cls[s][e - e0[s]] = ok ? (int)cd : -1;
         }
     }
     __syncthreads();
@@ -726,14 +482,13 @@ __global__ __launch_bounds__(CW_THREADS) void corpus_classwise_mix_kernel(const 
         const int i = p / C, c = p - i * C;
         int cnt = 0, last = -1, first[3] = {-1, -1, -1};
 #pragma unroll
-        for (int s = 0; s < 2; ++s) {                             // the item's events of the frame, then the mate's
+        for (int s = 0; s < NS; ++s) {                            // the item's events of the frame, then the mate's
             if (s >= ns) break;
             const double *ev = events + (size_t)ev_lo[s] * 4;
-            const int e0 = lb[s][0], e1 = lb[s][nf];
-            for (int e = lb[s][i]; e < lb[s][i + 1]; ++e) {
+            for (int e = lb[s][i]; e < lb[s][i + 1]; ++e) {       // file order within the frame
                 int ce;
-                if (e < e1 && (unsigned)(e - e0) < (unsigned)CW_EV_CACHE) {
-                    ce = cls[s][e - e0];
+                if (e < e1[s] && (unsigned)(e - e0[s]) < (unsigned)CW_EV_CACHE) {
+                    ce = cls[s][e - e0[s]];
                 } else {
                     const double cd = ev[(size_t)e * 4 + 1];
                     ce = cd >= 0.0 && cd < (double)C ? (int)cd : -1;
@@ -753,8 +508,10 @@ __global__ __launch_bounds__(CW_THREADS) void corpus_classwise_mix_kernel(const 
         q[3] = first[2];
     }
     __syncthreads();
+    // every position r of a frame's row is owned by one thread, its class / component / track slot worked out once (no
+    // division per element); the frames of the tile are written one after the other, each row by consecutive threads
     for (int r = tid; r < g.row; r += CW_THREADS) {
-        int c, k, s = 0;
+        int c, k, s = 0;                       // class, component (-1: the activity 1.0, else x / y / z), ADPIT track slot
         if (adpit) {
             s = r / (4 * C);
             const int rr = r - s * 4 * C;
@@ -765,18 +522,15 @@ __global__ __launch_bounds__(CW_THREADS) void corpus_classwise_mix_kernel(const 
             c = r - part * C;
             k = g.format == ADYOLO_CORPUS_SEDDOA ? part - 1 : part;
         }
+        // ADPIT: slot 0 takes the class's event when it has one, slots 1-2 its two, slots 3-5 the first three of three or more
         const int lo_cnt = s == 0 ? 1 : s <= 2 ? 2 : 3, hi_cnt = s == 0 ? 1 : s <= 2 ? 2 : 0x7fffffff;
         const int j = s == 0 ? 0 : s <= 2 ? s - 1 : s - 3;
         for (int i = 0; i < nf; ++i) {
             const int *q = pick + (i * C + c) * 4;
             const int e = adpit ? (q[0] >= lo_cnt && q[0] <= hi_cnt ? q[1 + j] : -1) : q[0];
-            float v = 0.f;
-            if (e >= 0) {
-                const size_t sl = (e >> CW_SRC_BIT) & 1 ? slot[1] : slot[0];
-                const size_t idx = (size_t)(e & ((1 << CW_SRC_BIT) - 1));
-                v = k < 0 ? 1.f : xyz[(idx * ADYOLO_CORPUS_XYZ_SLOTS + sl) * 3 + k];
-            }
-            dst[(size_t)i * g.row + r] = v;
+            const size_t sl = MIX && ((e >> CW_SRC_BIT) & 1) ? slot[NS - 1] : slot[0];
+            const size_t idx = MIX ? (size_t)(e & ((1 << CW_SRC_BIT) - 1)) : (size_t)e;
+            dst[(size_t)i * g.row + r] = e < 0 ? 0.f : k < 0 ? 1.f : xyz[(idx * ADYOLO_CORPUS_XYZ_SLOTS + sl) * 3 + k];
         }
     }
 }
@@ -860,11 +614,91 @@ __global__ __launch_bounds__(256) void decode_stitch_kernel(const float *__restr
     }
 }
 
-static int corpus_rot(const float *rot_host, CorpusRot &rot) {
-    if (!rot_host) return ADYOLO_EINVAL;
+static void corpus_rot(const float *rot_host, CorpusRot &rot) {
     for (int c = 0; c < 16; ++c)
         for (int k = 0; k < ADYOLO_CORPUS_ROT_WORDS; ++k) rot.c[c][k] = rot_host[c * ADYOLO_CORPUS_ROT_WORDS + k];
-    return 0;
+}
+
+static void corpus_mic(const unsigned int *src_host, CorpusMicSrc &tab) {
+    for (int c = 0; c < 16; ++c) tab.w[c] = src_host[c];
+}
+
+// The launchers behind the entry points of each stage: ``name`` is the entry point called, for its messages; MIX false takes
+// mates == nullptr.
+template <class Tab, bool MIX>
+static int corpus_gather_launch(const char *name, const int16_t *pcm, long n_total, const int64_t *items, const int64_t *mates,
+                                int B, long n, const Tab &tab, float *audio, int *status, void *stream) {
+    ADYOLO_REQUIRE(pcm && items && (mates || !MIX) && audio, ADYOLO_EINVAL, "%s: null pointer", name);
+    ADYOLO_REQUIRE(B > 0 && B < 65536 && n > 0 && n_total >= n, ADYOLO_EINVAL, "%s: bad shape B=%d n=%ld n_total=%ld", name, B, n,
+                   n_total);
+    ADYOLO_REQUIRE(((uintptr_t)pcm & 15) == 0 && ((uintptr_t)audio & 15) == 0 && ((uintptr_t)items & 7) == 0 &&
+                       ((uintptr_t)mates & 7) == 0,
+                   ADYOLO_EINVAL, "%s: misaligned buffers (pcm / audio 16 bytes, items / mates 8 bytes)", name);
+    // ~16 frames per thread: at 20 s (480000 frames) 118 blocks per item, 1888 for a batch of 16
+    int gx = cdiv(n, 256L * 16);
+    gx = gx < 1 ? 1 : (gx > 4096 ? 4096 : gx);
+    hipLaunchKernelGGL((corpus_gather_kernel<Tab, MIX>), dim3((unsigned)gx, (unsigned)B), dim3(256), 0, as_stream(stream), pcm,
+                       n_total, items, mates, n, tab, (float4 *)audio, status);
+    return check_launch(name);
+}
+
+template <bool MIX>
+static int corpus_yolo_labels_launch(const char *name, const double *events, long n_events, const int64_t *items,
+                                     const int64_t *mates, int B, int max_events, int n_label_frames, const double *grid_bounds,
+                                     int Gaz, int Gel, const float *rot_host, int *ws, float *target, long cap, int *count,
+                                     int *status, void *stream) {
+    ADYOLO_REQUIRE(events && items && (mates || !MIX) && grid_bounds && rot_host && ws && target && count && status, ADYOLO_EINVAL,
+                   "%s: null pointer", name);
+    const long lanes = (long)B * (MIX ? 2 : 1) * max_events;
+    ADYOLO_REQUIRE(B > 0 && max_events >= 0 && n_events >= 0 && n_label_frames > 0 && cap > 0 && cap < (1L << 31) &&
+                       lanes < (1L << 31),
+                   ADYOLO_EINVAL, "%s: bad shape B=%d max_events=%d cap=%ld", name, B, max_events, cap);
+    ADYOLO_REQUIRE(Gaz > 0 && Gaz <= 64 && Gel > 0 && Gel <= 64, ADYOLO_ENOSUP, "%s: grid %d x %d (at most 64 x 64 cells)", name,
+                   Gaz, Gel);
+    ADYOLO_REQUIRE(((uintptr_t)events & 7) == 0 && ((uintptr_t)items & 7) == 0 && ((uintptr_t)mates & 7) == 0 &&
+                       ((uintptr_t)grid_bounds & 7) == 0 && ((uintptr_t)target & 3) == 0,
+                   ADYOLO_EINVAL, "%s: misaligned buffers", name);
+    CorpusRot rot;
+    corpus_rot(rot_host, rot);
+    CorpusLabelGeom g;
+    g.B = B; g.max_events = max_events; g.n_label_frames = n_label_frames; g.Gaz = Gaz; g.Gel = Gel;
+    g.n_events = n_events; g.cap = cap;
+    hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(corpus_count_scan_kernel<MIX>, dim3(1), dim3(CORPUS_SCAN_THREADS), 0, st, events, items, mates,
+                       grid_bounds, rot, g, ws, count, status);
+    int rc = check_launch(name);
+    if (rc) return rc;
+    long work = cap > lanes ? cap : lanes;
+    int gx = cdiv(work, 256L * 4);
+    gx = gx < 1 ? 1 : (gx > 1024 ? 1024 : gx);
+    hipLaunchKernelGGL(corpus_rows_kernel<MIX>, dim3((unsigned)gx), dim3(256), 0, st, events, items, mates, grid_bounds, rot, g,
+                       ws, count, target);
+    return check_launch(name);
+}
+
+template <bool MIX>
+static int corpus_classwise_launch(const char *name, const double *events, const float *xyz, long n_events, const int64_t *items,
+                                   const int64_t *mates, int B, int max_events, int n_label_frames, int n_classes, int format,
+                                   float *target, int *status, void *stream) {
+    ADYOLO_REQUIRE(events && xyz && items && (mates || !MIX) && target && status, ADYOLO_EINVAL, "%s: null pointer", name);
+    ADYOLO_REQUIRE(B > 0 && B < 65536 && max_events >= 0 && n_events >= 0 && n_events < (1L << (MIX ? CW_SRC_BIT : 31)) &&
+                       n_label_frames > 0 && n_classes > 0,
+                   ADYOLO_EINVAL, "%s: bad shape B=%d max_events=%d n_events=%ld n_label_frames=%d C=%d", name, B, max_events,
+                   n_events, n_label_frames, n_classes);
+    ADYOLO_REQUIRE(format == ADYOLO_CORPUS_SEDDOA || format == ADYOLO_CORPUS_ACCDOA || format == ADYOLO_CORPUS_ADPIT,
+                   ADYOLO_EINVAL, "%s: unknown format %d", name, format);
+    ADYOLO_REQUIRE(n_classes <= CW_MAX_CLASSES, ADYOLO_ENOSUP, "%s: %d classes (at most %d)", name, n_classes, CW_MAX_CLASSES);
+    ADYOLO_REQUIRE(((uintptr_t)events & 7) == 0 && ((uintptr_t)items & 7) == 0 && ((uintptr_t)mates & 7) == 0 &&
+                       ((uintptr_t)xyz & 3) == 0 && ((uintptr_t)target & 3) == 0 && ((uintptr_t)status & 3) == 0,
+                   ADYOLO_EINVAL, "%s: misaligned buffers", name);
+    CorpusClasswiseGeom g;
+    g.B = B; g.max_events = max_events; g.n_label_frames = n_label_frames; g.C = n_classes; g.format = format;
+    g.row = (format == ADYOLO_CORPUS_SEDDOA ? 4 : format == ADYOLO_CORPUS_ACCDOA ? 3 : 24) * n_classes;
+    g.n_events = n_events;
+    const size_t lds = (size_t)CW_FRAMES * n_classes * 4 * sizeof(int);
+    hipLaunchKernelGGL(corpus_classwise_kernel<MIX>, dim3((unsigned)cdiv(n_label_frames, CW_FRAMES), (unsigned)B),
+                       dim3(CW_THREADS), lds, as_stream(stream), events, xyz, items, mates, g, target, status);
+    return check_launch(name);
 }
 
 }  // namespace adyolo
@@ -873,35 +707,34 @@ using namespace adyolo;
 
 extern "C" int adyolo_corpus_gather(const int16_t *pcm, long n_total, const int64_t *items, int B, long n,
                                     const float *rot_host, float *audio, int *status, void *stream) {
-    ADYOLO_REQUIRE(pcm && items && audio && rot_host, ADYOLO_EINVAL, "corpus_gather: null pointer");
-    ADYOLO_REQUIRE(B > 0 && B < 65536 && n > 0 && n_total >= n, ADYOLO_EINVAL,
-                   "corpus_gather: bad shape B=%d n=%ld n_total=%ld", B, n, n_total);
-    ADYOLO_REQUIRE(((uintptr_t)pcm & 15) == 0 && ((uintptr_t)audio & 15) == 0 && ((uintptr_t)items & 7) == 0, ADYOLO_EINVAL,
-                   "corpus_gather: misaligned buffers (pcm / audio 16 bytes, items 8 bytes)");
+    ADYOLO_REQUIRE(rot_host, ADYOLO_EINVAL, "corpus_gather: null pointer");
     CorpusRot rot;
     corpus_rot(rot_host, rot);
-    // ~16 frames per thread: at 20 s (480000 frames) 118 blocks per item, 1888 for a batch of 16
-    int gx = cdiv(n, 256L * 16);
-    gx = gx < 1 ? 1 : (gx > 4096 ? 4096 : gx);
-    hipLaunchKernelGGL(corpus_gather_kernel, dim3((unsigned)gx, (unsigned)B), dim3(256), 0, as_stream(stream), pcm, n_total,
-                       items, n, rot, (float4 *)audio, status);
-    return check_launch("corpus_gather");
+    return corpus_gather_launch<CorpusRot, false>("corpus_gather", pcm, n_total, items, nullptr, B, n, rot, audio, status, stream);
 }
 
 extern "C" int adyolo_corpus_gather_mic(const int16_t *pcm, long n_total, const int64_t *items, int B, long n,
                                         const unsigned int *src_host, float *audio, int *status, void *stream) {
-    ADYOLO_REQUIRE(pcm && items && audio && src_host, ADYOLO_EINVAL, "corpus_gather_mic: null pointer");
-    ADYOLO_REQUIRE(B > 0 && B < 65536 && n > 0 && n_total >= n, ADYOLO_EINVAL,
-                   "corpus_gather_mic: bad shape B=%d n=%ld n_total=%ld", B, n, n_total);
-    ADYOLO_REQUIRE(((uintptr_t)pcm & 15) == 0 && ((uintptr_t)audio & 15) == 0 && ((uintptr_t)items & 7) == 0, ADYOLO_EINVAL,
-                   "corpus_gather_mic: misaligned buffers (pcm / audio 16 bytes, items 8 bytes)");
+    ADYOLO_REQUIRE(src_host, ADYOLO_EINVAL, "corpus_gather_mic: null pointer");
     CorpusMicSrc tab;
-    for (int c = 0; c < 16; ++c) tab.w[c] = src_host[c];
-    int gx = cdiv(n, 256L * 16);                            // the grid of adyolo_corpus_gather
-    gx = gx < 1 ? 1 : (gx > 4096 ? 4096 : gx);
-    hipLaunchKernelGGL(corpus_gather_mic_kernel, dim3((unsigned)gx, (unsigned)B), dim3(256), 0, as_stream(stream), pcm, n_total,
-                       items, n, tab, (float4 *)audio, status);
-    return check_launch("corpus_gather_mic");
+    corpus_mic(src_host, tab);
+    return corpus_gather_launch<CorpusMicSrc, false>("corpus_gather_mic", pcm, n_total, items, nullptr, B, n, tab, audio, status,
+                                                     stream);
+}
+
+extern "C" int adyolo_corpus_gather_mix(const int16_t *pcm, long n_total, const int64_t *items, const int64_t *mates, int B,
+                                        long n, const float *rot_host, const unsigned int *mic_src_host, float *audio,
+                                        int *status, void *stream) {
+    const char *name = "corpus_gather_mix";
+    ADYOLO_REQUIRE(rot_host || mic_src_host, ADYOLO_EINVAL, "%s: null pointer", name);
+    if (mic_src_host) {
+        CorpusMicSrc tab;
+        corpus_mic(mic_src_host, tab);
+        return corpus_gather_launch<CorpusMicSrc, true>(name, pcm, n_total, items, mates, B, n, tab, audio, status, stream);
+    }
+    CorpusRot rot;
+    corpus_rot(rot_host, rot);
+    return corpus_gather_launch<CorpusRot, true>(name, pcm, n_total, items, mates, B, n, rot, audio, status, stream);
 }
 
 extern "C" long adyolo_corpus_yolo_labels_workspace_words(int B, int max_events) {
@@ -909,151 +742,39 @@ extern "C" long adyolo_corpus_yolo_labels_workspace_words(int B, int max_events)
     return (long)B * (max_events > 0 ? max_events : 1);
 }
 
+extern "C" long adyolo_corpus_yolo_labels_mix_workspace_words(int B, int max_events) {
+    if (B <= 0 || max_events < 0) return -1;
+    return (long)B * 2 * (max_events > 0 ? max_events : 1);
+}
+
 extern "C" int adyolo_corpus_yolo_labels(const double *events, long n_events, const int64_t *items, int B, int max_events,
                                          int n_label_frames, const double *grid_bounds, int Gaz, int Gel,
                                          const float *rot_host, int *ws, float *target, long cap, int *count, int *status,
                                          void *stream) {
-    ADYOLO_REQUIRE(events && items && grid_bounds && rot_host && ws && target && count && status, ADYOLO_EINVAL,
-                   "corpus_yolo_labels: null pointer");
-    ADYOLO_REQUIRE(B > 0 && max_events >= 0 && n_events >= 0 && n_label_frames > 0 && cap > 0 && cap < (1L << 31) &&
-                       (long)B * max_events < (1L << 31),
-                   ADYOLO_EINVAL, "corpus_yolo_labels: bad shape B=%d max_events=%d cap=%ld", B, max_events, cap);
-    ADYOLO_REQUIRE(Gaz > 0 && Gaz <= 64 && Gel > 0 && Gel <= 64, ADYOLO_ENOSUP,
-                   "corpus_yolo_labels: grid %d x %d (at most 64 x 64 cells)", Gaz, Gel);
-    ADYOLO_REQUIRE(((uintptr_t)events & 7) == 0 && ((uintptr_t)items & 7) == 0 && ((uintptr_t)grid_bounds & 7) == 0 &&
-                       ((uintptr_t)target & 3) == 0,
-                   ADYOLO_EINVAL, "corpus_yolo_labels: misaligned buffers");
-    CorpusRot rot;
-    corpus_rot(rot_host, rot);
-    CorpusLabelGeom g;
-    g.B = B; g.max_events = max_events; g.n_label_frames = n_label_frames; g.Gaz = Gaz; g.Gel = Gel;
-    g.n_events = n_events; g.cap = cap;
-    hipStream_t st = as_stream(stream);
-    hipLaunchKernelGGL(corpus_count_scan_kernel, dim3(1), dim3(CORPUS_SCAN_THREADS), 0, st, events, items, grid_bounds, rot, g,
-                       ws, count, status);
-    int rc = check_launch("corpus_count_scan");
-    if (rc) return rc;
-    long work = cap > (long)B * max_events ? cap : (long)B * max_events;
-    int gx = cdiv(work, 256L * 4);
-    gx = gx < 1 ? 1 : (gx > 1024 ? 1024 : gx);
-    hipLaunchKernelGGL(corpus_rows_kernel, dim3((unsigned)gx), dim3(256), 0, st, events, items, grid_bounds, rot, g, ws, count,
-                       target);
-    return check_launch("corpus_rows");
-}
-
-extern "C" int adyolo_corpus_classwise_labels(const double *events, const float *xyz, long n_events, const int64_t *items, int B,
-                                              int max_events, int n_label_frames, int n_classes, int format, float *target,
-                                              int *status, void *stream) {
-    ADYOLO_REQUIRE(events && xyz && items && target && status, ADYOLO_EINVAL, "corpus_classwise_labels: null pointer");
-    ADYOLO_REQUIRE(B > 0 && B < 65536 && max_events >= 0 && n_events >= 0 && n_events < (1L << 31) && n_label_frames > 0 &&
-                       n_classes > 0,
-                   ADYOLO_EINVAL, "corpus_classwise_labels: bad shape B=%d max_events=%d n_events=%ld n_label_frames=%d C=%d", B,
-                   max_events, n_events, n_label_frames, n_classes);
-    ADYOLO_REQUIRE(format == ADYOLO_CORPUS_SEDDOA || format == ADYOLO_CORPUS_ACCDOA || format == ADYOLO_CORPUS_ADPIT,
-                   ADYOLO_EINVAL, "corpus_classwise_labels: unknown format %d", format);
-    ADYOLO_REQUIRE(n_classes <= CW_MAX_CLASSES, ADYOLO_ENOSUP, "corpus_classwise_labels: %d classes (at most %d)", n_classes,
-                   CW_MAX_CLASSES);
-    ADYOLO_REQUIRE(((uintptr_t)events & 7) == 0 && ((uintptr_t)items & 7) == 0 && ((uintptr_t)xyz & 3) == 0 &&
-                       ((uintptr_t)target & 3) == 0 && ((uintptr_t)status & 3) == 0,
-                   ADYOLO_EINVAL, "corpus_classwise_labels: misaligned buffers");
-    CorpusClasswiseGeom g;
-    g.B = B; g.max_events = max_events; g.n_label_frames = n_label_frames; g.C = n_classes; g.format = format;
-    g.row = (format == ADYOLO_CORPUS_SEDDOA ? 4 : format == ADYOLO_CORPUS_ACCDOA ? 3 : 24) * n_classes;
-    g.n_events = n_events;
-    const size_t lds = (size_t)CW_FRAMES * n_classes * 4 * sizeof(int);
-    hipLaunchKernelGGL(corpus_classwise_kernel, dim3((unsigned)cdiv(n_label_frames, CW_FRAMES), (unsigned)B), dim3(CW_THREADS), lds,
-                       as_stream(stream), events, xyz, items, g, target, status);
-    return check_launch("corpus_classwise_labels");
-}
-
-// ------------------------------------------------------------------------------------------------ time-domain mixing
-extern "C" int adyolo_corpus_gather_mix(const int16_t *pcm, long n_total, const int64_t *items, const int64_t *mates, int B,
-                                        long n, const float *rot_host, const unsigned int *mic_src_host, float *audio,
-                                        int *status, void *stream) {
-    ADYOLO_REQUIRE(pcm && items && mates && audio && (rot_host || mic_src_host), ADYOLO_EINVAL, "corpus_gather_mix: null pointer");
-    ADYOLO_REQUIRE(B > 0 && B < 65536 && n > 0 && n_total >= n, ADYOLO_EINVAL,
-                   "corpus_gather_mix: bad shape B=%d n=%ld n_total=%ld", B, n, n_total);
-    ADYOLO_REQUIRE(((uintptr_t)pcm & 15) == 0 && ((uintptr_t)audio & 15) == 0 && ((uintptr_t)items & 7) == 0 &&
-                       ((uintptr_t)mates & 7) == 0,
-                   ADYOLO_EINVAL, "corpus_gather_mix: misaligned buffers (pcm / audio 16 bytes, items / mates 8 bytes)");
-    int gx = cdiv(n, 256L * 16);                            // the grid of adyolo_corpus_gather
-    gx = gx < 1 ? 1 : (gx > 4096 ? 4096 : gx);
-    const dim3 grid((unsigned)gx, (unsigned)B);
-    if (mic_src_host) {
-        CorpusMicSrc tab;
-        for (int c = 0; c < 16; ++c) tab.w[c] = mic_src_host[c];
-        hipLaunchKernelGGL(corpus_gather_mix_kernel<CorpusMicSrc>, grid, dim3(256), 0, as_stream(stream), pcm, n_total, items,
-                           mates, n, tab, (float4 *)audio, status);
-    } else {
-        CorpusRot rot;
-        corpus_rot(rot_host, rot);
-        hipLaunchKernelGGL(corpus_gather_mix_kernel<CorpusRot>, grid, dim3(256), 0, as_stream(stream), pcm, n_total, items, mates,
-                           n, rot, (float4 *)audio, status);
-    }
-    return check_launch("corpus_gather_mix");
-}
-
-extern "C" long adyolo_corpus_yolo_labels_mix_workspace_words(int B, int max_events) {
-    if (B <= 0 || max_events < 0) return -1;
-    return (long)B * 2 * (max_events > 0 ? max_events : 1);
+    return corpus_yolo_labels_launch<false>("corpus_yolo_labels", events, n_events, items, nullptr, B, max_events, n_label_frames,
+                                            grid_bounds, Gaz, Gel, rot_host, ws, target, cap, count, status, stream);
 }
 
 extern "C" int adyolo_corpus_yolo_labels_mix(const double *events, long n_events, const int64_t *items, const int64_t *mates,
                                              int B, int max_events, int n_label_frames, const double *grid_bounds, int Gaz,
                                              int Gel, const float *rot_host, int *ws, float *target, long cap, int *count,
                                              int *status, void *stream) {
-    ADYOLO_REQUIRE(events && items && mates && grid_bounds && rot_host && ws && target && count && status, ADYOLO_EINVAL,
-                   "corpus_yolo_labels_mix: null pointer");
-    ADYOLO_REQUIRE(B > 0 && max_events >= 0 && n_events >= 0 && n_label_frames > 0 && cap > 0 && cap < (1L << 31) &&
-                       (long)B * 2 * max_events < (1L << 31),
-                   ADYOLO_EINVAL, "corpus_yolo_labels_mix: bad shape B=%d max_events=%d cap=%ld", B, max_events, cap);
-    ADYOLO_REQUIRE(Gaz > 0 && Gaz <= 64 && Gel > 0 && Gel <= 64, ADYOLO_ENOSUP,
-                   "corpus_yolo_labels_mix: grid %d x %d (at most 64 x 64 cells)", Gaz, Gel);
-    ADYOLO_REQUIRE(((uintptr_t)events & 7) == 0 && ((uintptr_t)items & 7) == 0 && ((uintptr_t)mates & 7) == 0 &&
-                       ((uintptr_t)grid_bounds & 7) == 0 && ((uintptr_t)target & 3) == 0,
-                   ADYOLO_EINVAL, "corpus_yolo_labels_mix: misaligned buffers");
-    CorpusRot rot;
-    corpus_rot(rot_host, rot);
-    CorpusLabelGeom g;
-    g.B = B; g.max_events = max_events; g.n_label_frames = n_label_frames; g.Gaz = Gaz; g.Gel = Gel;
-    g.n_events = n_events; g.cap = cap;
-    hipStream_t st = as_stream(stream);
-    hipLaunchKernelGGL(corpus_mix_count_scan_kernel, dim3(1), dim3(CORPUS_SCAN_THREADS), 0, st, events, items, mates, grid_bounds,
-                       rot, g, ws, count, status);
-    int rc = check_launch("corpus_mix_count_scan");
-    if (rc) return rc;
-    long work = cap > (long)B * 2 * max_events ? cap : (long)B * 2 * max_events;
-    int gx = cdiv(work, 256L * 4);
-    gx = gx < 1 ? 1 : (gx > 1024 ? 1024 : gx);
-    hipLaunchKernelGGL(corpus_mix_rows_kernel, dim3((unsigned)gx), dim3(256), 0, st, events, items, mates, grid_bounds, rot, g,
-                       ws, count, target);
-    return check_launch("corpus_mix_rows");
+    return corpus_yolo_labels_launch<true>("corpus_yolo_labels_mix", events, n_events, items, mates, B, max_events,
+                                           n_label_frames, grid_bounds, Gaz, Gel, rot_host, ws, target, cap, count, status, stream);
+}
+
+extern "C" int adyolo_corpus_classwise_labels(const double *events, const float *xyz, long n_events, const int64_t *items, int B,
+                                              int max_events, int n_label_frames, int n_classes, int format, float *target,
+                                              int *status, void *stream) {
+    return corpus_classwise_launch<false>("corpus_classwise_labels", events, xyz, n_events, items, nullptr, B, max_events,
+                                          n_label_frames, n_classes, format, target, status, stream);
 }
 
 extern "C" int adyolo_corpus_classwise_labels_mix(const double *events, const float *xyz, long n_events, const int64_t *items,
                                                   const int64_t *mates, int B, int max_events, int n_label_frames, int n_classes,
                                                   int format, float *target, int *status, void *stream) {
-    ADYOLO_REQUIRE(events && xyz && items && mates && target && status, ADYOLO_EINVAL,
-                   "corpus_classwise_labels_mix: null pointer");
-    ADYOLO_REQUIRE(B > 0 && B < 65536 && max_events >= 0 && n_events >= 0 && n_events < (1L << CW_SRC_BIT) &&
-                       n_label_frames > 0 && n_classes > 0,
-                   ADYOLO_EINVAL, "corpus_classwise_labels_mix: bad shape B=%d max_events=%d n_events=%ld n_label_frames=%d C=%d",
-                   B, max_events, n_events, n_label_frames, n_classes);
-    ADYOLO_REQUIRE(format == ADYOLO_CORPUS_SEDDOA || format == ADYOLO_CORPUS_ACCDOA || format == ADYOLO_CORPUS_ADPIT,
-                   ADYOLO_EINVAL, "corpus_classwise_labels_mix: unknown format %d", format);
-    ADYOLO_REQUIRE(n_classes <= CW_MAX_CLASSES, ADYOLO_ENOSUP, "corpus_classwise_labels_mix: %d classes (at most %d)", n_classes,
-                   CW_MAX_CLASSES);
-    ADYOLO_REQUIRE(((uintptr_t)events & 7) == 0 && ((uintptr_t)items & 7) == 0 && ((uintptr_t)mates & 7) == 0 &&
-                       ((uintptr_t)xyz & 3) == 0 && ((uintptr_t)target & 3) == 0 && ((uintptr_t)status & 3) == 0,
-                   ADYOLO_EINVAL, "corpus_classwise_labels_mix: misaligned buffers");
-    CorpusClasswiseGeom g;
-    g.B = B; g.max_events = max_events; g.n_label_frames = n_label_frames; g.C = n_classes; g.format = format;
-    g.row = (format == ADYOLO_CORPUS_SEDDOA ? 4 : format == ADYOLO_CORPUS_ACCDOA ? 3 : 24) * n_classes;
-    g.n_events = n_events;
-    const size_t lds = (size_t)CW_FRAMES * n_classes * 4 * sizeof(int);
-    hipLaunchKernelGGL(corpus_classwise_mix_kernel, dim3((unsigned)cdiv(n_label_frames, CW_FRAMES), (unsigned)B), dim3(CW_THREADS),
-                       lds, as_stream(stream), events, xyz, items, mates, g, target, status);
-    return check_launch("corpus_classwise_labels_mix");
+    return corpus_classwise_launch<true>("corpus_classwise_labels_mix", events, xyz, n_events, items, mates, B, max_events,
+                                         n_label_frames, n_classes, format, target, status, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ windowed inference

@@ -1760,12 +1760,21 @@ def _corpus_i64(name, t, device):
         raise _lib.AdyoloHipError("%s must be a contiguous int64 tensor on %s" % (name, device))
 
 
-def _corpus_gather_args(name, pcm, items, out, status):
-    """The argument checks both gathers share -> B."""
+def _corpus_tables(name, items, mates, device):
+    """The item table of a corpus call and, where the call has one, its table of mates: rows like the items'."""
+    _corpus_i64("%s: items" % name, items, device)
+    if mates is not None:
+        _corpus_i64("%s: mates" % name, mates, device)
+        if tuple(mates.shape) != tuple(items.shape):
+            raise _lib.AdyoloHipError("%s: mates %s do not match items %s" % (name, tuple(mates.shape), tuple(items.shape)))
+
+
+def _corpus_gather_args(name, pcm, items, out, status, mates=None):
+    """The argument checks of the gather family -> B."""
     dev = pcm.device
     if not pcm.is_cuda or pcm.dtype != torch.int16 or not pcm.is_contiguous() or pcm.dim() != 2 or pcm.shape[1] != 4:
         raise _lib.AdyoloHipError("%s: pcm must be a contiguous int16 tensor (S, 4) on the device" % name)
-    _corpus_i64("%s: items" % name, items, dev)
+    _corpus_tables(name, items, mates, dev)
     _chk(out)
     b = items.shape[0] if items.dim() == 2 else 0
     if items.dim() != 2 or items.shape[1] != CORPUS_ITEM_WORDS or out.dim() != 3 or out.shape[0] != b or out.shape[2] != 4:
@@ -1811,20 +1820,13 @@ def corpus_gather_mic(pcm, items, src, out, status):
     return out
 
 
-def _corpus_mates(name, items, mates):
-    _corpus_i64("%s: mates" % name, mates, items.device)
-    if tuple(mates.shape) != tuple(items.shape):
-        raise _lib.AdyoloHipError("%s: mates %s do not match items %s" % (name, tuple(mates.shape), tuple(items.shape)))
-
-
 def corpus_gather_mix(pcm, items, mates, rot, mic_src, out, status):
     """``corpus_gather`` (``mic_src`` None; rot: ``corpus_rot_table``) or ``corpus_gather_mic`` (mic_src: ``corpus_mic_table``) with
     a second window per item summed in: mates int64 (B, 8) on the device, rows like ``items`` with their own combinations, the
     float32 bits of the gain in word 6, offset -1 = no mate -> out = a + g * m, bit for bit two plain gathers and that
     expression on float32 tensors (adyolo_hip.h ``adyolo_corpus_gather_mix``).  A bad item or mate: zeros for the sample and
     status bit 2.  No allocation, no sync."""
-    b = _corpus_gather_args("corpus_gather_mix", pcm, items, out, status)
-    _corpus_mates("corpus_gather_mix", items, mates)
+    b = _corpus_gather_args("corpus_gather_mix", pcm, items, out, status, mates)
     if mic_src is None and rot is None:
         raise _lib.AdyoloHipError("corpus_gather_mix: the FOA form needs the rotation table")
     _c("adyolo_corpus_gather_mix", _p(pcm), pcm.shape[0], _p(items), _p(mates), b, out.shape[1],
@@ -1879,60 +1881,57 @@ def corpus_labels_workspace_words(batch, max_events):
     return int(_lib.load().adyolo_corpus_yolo_labels_workspace_words(int(batch), int(max_events)))
 
 
+def corpus_labels_mix_workspace_words(batch, max_events):
+    return int(_lib.load().adyolo_corpus_yolo_labels_mix_workspace_words(int(batch), int(max_events)))
+
+
+def _corpus_events(name, events, items, mates):
+    """The checks every label call makes of its tables and of the event table -> (B, E)."""
+    dev = items.device
+    _corpus_tables(name, items, mates, dev)
+    if not events.is_cuda or events.dtype != torch.float64 or not events.is_contiguous() or events.dim() != 2 \
+            or events.shape[1] != 4 or events.device != dev:
+        raise _lib.AdyoloHipError("%s: events must be a contiguous float64 tensor (E, 4) on %s" % (name, dev))
+    return items.shape[0], events.shape[0]
+
+
+def _corpus_yolo_args(name, events, items, max_events, bounds, grid, ws, target, count, status, mates=None):
+    """The argument checks of the AD-YOLO label family -> (B, E, Gaz, Gel)."""
+    dev = items.device
+    b, n_ev = _corpus_events(name, events, items, mates)
+    gaz, gel = int(grid[0]), int(grid[1])
+    if bounds.dtype != torch.float64 or bounds.device != dev or not bounds.is_contiguous() or bounds.numel() != 2 * (gaz + gel):
+        raise _lib.AdyoloHipError("%s: bounds must be float64 (2 Gaz + 2 Gel,) on %s" % (name, dev))
+    _chk(target)
+    if target.dim() != 2 or target.shape[1] != 7:
+        raise _lib.AdyoloHipError("%s: target %s is not (cap, 7)" % (name, tuple(target.shape)))
+    ws_words = (corpus_labels_workspace_words if mates is None else corpus_labels_mix_workspace_words)(b, max_events)
+    for what, t, words in (("ws", ws, ws_words), ("count", count, 1), ("status", status, 1)):
+        if t.dtype != torch.int32 or t.device != dev or not t.is_contiguous() or t.numel() < words:
+            raise _lib.AdyoloHipError("%s: %s must be at least %d int32 words on %s" % (name, what, words, dev))
+    return b, n_ev, gaz, gel
+
+
 def corpus_yolo_labels(events, items, max_events, n_label_frames, bounds, grid, rot, ws, target, count, status):
     """The AD-YOLO rows of a batch on the device (adyolo_hip.h ``adyolo_corpus_yolo_labels``): events float64 (E, 4) {frame,
     class, az, el}, items int64 (B, 8), bounds float64 (2 Gaz + 2 Gel,), grid (Gaz, Gel), ws int32 of
     ``corpus_labels_workspace_words`` words -> target (cap, 7) float32 (b = -1 past the total), count int32 word = total rows.
     status: int32 word the call ORs its bits into.  No allocation, no sync."""
-    dev = items.device
-    _corpus_i64("corpus_yolo_labels: items", items, dev)
-    if not events.is_cuda or events.dtype != torch.float64 or not events.is_contiguous() or events.dim() != 2 \
-            or events.shape[1] != 4 or events.device != dev:
-        raise _lib.AdyoloHipError("corpus_yolo_labels: events must be a contiguous float64 tensor (E, 4) on %s" % dev)
-    gaz, gel = int(grid[0]), int(grid[1])
-    if bounds.dtype != torch.float64 or bounds.device != dev or not bounds.is_contiguous() or bounds.numel() != 2 * (gaz + gel):
-        raise _lib.AdyoloHipError("corpus_yolo_labels: bounds must be float64 (2 Gaz + 2 Gel,) on %s" % dev)
-    _chk(target)
-    if target.dim() != 2 or target.shape[1] != 7:
-        raise _lib.AdyoloHipError("corpus_yolo_labels: target %s is not (cap, 7)" % (tuple(target.shape),))
-    b = items.shape[0]
-    for name, t, words in (("ws", ws, corpus_labels_workspace_words(b, max_events)), ("count", count, 1), ("status", status, 1)):
-        if t.dtype != torch.int32 or t.device != dev or not t.is_contiguous() or t.numel() < words:
-            raise _lib.AdyoloHipError("corpus_yolo_labels: %s must be at least %d int32 words on %s" % (name, words, dev))
-    n_ev = events.shape[0]
+    b, n_ev, gaz, gel = _corpus_yolo_args("corpus_yolo_labels", events, items, max_events, bounds, grid, ws, target, count, status)
     _c("adyolo_corpus_yolo_labels", _p(events), n_ev, _p(items), b, int(max_events), int(n_label_frames), _p(bounds), gaz, gel,
        ctypes.cast(rot, ctypes.c_void_p), _p(ws), _p(target), target.shape[0], _p(count), _p(status), _stream())
     return target
-
-
-def corpus_labels_mix_workspace_words(batch, max_events):
-    return int(_lib.load().adyolo_corpus_yolo_labels_mix_workspace_words(int(batch), int(max_events)))
 
 
 def corpus_yolo_labels_mix(events, items, mates, max_events, n_label_frames, bounds, grid, rot, ws, target, count, status):
     """``corpus_yolo_labels`` for mixed items: the rows of ``augmentations.merge_labels(item, mate)`` per item, each event under
     its own source's combination and frame offset, column 0 the item (adyolo_hip.h ``adyolo_corpus_yolo_labels_mix``).  mates
     int64 (B, 8) as for ``corpus_gather_mix``; ws int32 of ``corpus_labels_mix_workspace_words`` words.  No allocation, no sync."""
-    dev = items.device
-    _corpus_i64("corpus_yolo_labels_mix: items", items, dev)
-    _corpus_mates("corpus_yolo_labels_mix", items, mates)
-    if not events.is_cuda or events.dtype != torch.float64 or not events.is_contiguous() or events.dim() != 2 \
-            or events.shape[1] != 4 or events.device != dev:
-        raise _lib.AdyoloHipError("corpus_yolo_labels_mix: events must be a contiguous float64 tensor (E, 4) on %s" % dev)
-    gaz, gel = int(grid[0]), int(grid[1])
-    if bounds.dtype != torch.float64 or bounds.device != dev or not bounds.is_contiguous() or bounds.numel() != 2 * (gaz + gel):
-        raise _lib.AdyoloHipError("corpus_yolo_labels_mix: bounds must be float64 (2 Gaz + 2 Gel,) on %s" % dev)
-    _chk(target)
-    if target.dim() != 2 or target.shape[1] != 7:
-        raise _lib.AdyoloHipError("corpus_yolo_labels_mix: target %s is not (cap, 7)" % (tuple(target.shape),))
-    b = items.shape[0]
-    for name, t, words in (("ws", ws, corpus_labels_mix_workspace_words(b, max_events)), ("count", count, 1),
-                           ("status", status, 1)):
-        if t.dtype != torch.int32 or t.device != dev or not t.is_contiguous() or t.numel() < words:
-            raise _lib.AdyoloHipError("corpus_yolo_labels_mix: %s must be at least %d int32 words on %s" % (name, words, dev))
-    _c("adyolo_corpus_yolo_labels_mix", _p(events), events.shape[0], _p(items), _p(mates), b, int(max_events),
-       int(n_label_frames), _p(bounds), gaz, gel, ctypes.cast(rot, ctypes.c_void_p), _p(ws), _p(target), target.shape[0],
-       _p(count), _p(status), _stream())
+    b, n_ev, gaz, gel = _corpus_yolo_args("corpus_yolo_labels_mix", events, items, max_events, bounds, grid, ws, target, count,
+                                          status, mates)
+    _c("adyolo_corpus_yolo_labels_mix", _p(events), n_ev, _p(items), _p(mates), b, int(max_events), int(n_label_frames),
+       _p(bounds), gaz, gel, ctypes.cast(rot, ctypes.c_void_p), _p(ws), _p(target), target.shape[0], _p(count), _p(status),
+       _stream())
     return target
 
 
@@ -1945,29 +1944,31 @@ def corpus_classwise_shape(loss, batch, n_label_frames, nb_classes):
     return {0: (b, t, 4 * c), 1: (b, t, 3 * c), 2: (b, t, 6, 4, c)}[CORPUS_FORMATS[loss]]
 
 
+def _corpus_classwise_args(name, events, items, xyz, n_label_frames, nb_classes, loss, target, status, mates=None):
+    """The argument checks of the class-wise label family -> (B, E)."""
+    dev = items.device
+    b, n_ev = _corpus_events(name, events, items, mates)
+    if xyz.dtype != torch.float32 or xyz.device != dev or not xyz.is_contiguous() \
+            or tuple(xyz.shape) != (n_ev, CORPUS_XYZ_SLOTS, 3):
+        raise _lib.AdyoloHipError("%s: xyz must be a contiguous float32 tensor (%d, %d, 3) on %s"
+                                  % (name, n_ev, CORPUS_XYZ_SLOTS, dev))
+    want = corpus_classwise_shape(loss, b, n_label_frames, nb_classes)
+    _chk(target)
+    if tuple(target.shape) != want or target.device != dev:
+        raise _lib.AdyoloHipError("%s: target %s on %s, expected %s on %s for %s"
+                                  % (name, tuple(target.shape), target.device, want, dev, loss))
+    if status.dtype != torch.int32 or status.device != dev or not status.is_contiguous() or status.numel() < 1:
+        raise _lib.AdyoloHipError("%s: status must be an int32 word on %s" % (name, dev))
+    return b, n_ev
+
+
 def corpus_classwise_labels(events, items, xyz, max_events, n_label_frames, nb_classes, loss, target, status):
     """The dense class-wise targets of a batch on the device (adyolo_hip.h ``adyolo_corpus_classwise_labels``): events float64
     (E, 4) {frame, class, az, el}, items int64 (B, 8), xyz float32 (E, 17, 3) (``corpus.xyz_table``) -> target float32 of
     ``corpus_classwise_shape(loss, B, n_label_frames, nb_classes)``, every element written.  status: int32 word the call ORs its
     bits into.  No allocation, no sync."""
-    dev = items.device
-    _corpus_i64("corpus_classwise_labels: items", items, dev)
-    if not events.is_cuda or events.dtype != torch.float64 or not events.is_contiguous() or events.dim() != 2 \
-            or events.shape[1] != 4 or events.device != dev:
-        raise _lib.AdyoloHipError("corpus_classwise_labels: events must be a contiguous float64 tensor (E, 4) on %s" % dev)
-    n_ev = events.shape[0]
-    if xyz.dtype != torch.float32 or xyz.device != dev or not xyz.is_contiguous() \
-            or tuple(xyz.shape) != (n_ev, CORPUS_XYZ_SLOTS, 3):
-        raise _lib.AdyoloHipError("corpus_classwise_labels: xyz must be a contiguous float32 tensor (%d, %d, 3) on %s"
-                                  % (n_ev, CORPUS_XYZ_SLOTS, dev))
-    b = items.shape[0]
-    want = corpus_classwise_shape(loss, b, n_label_frames, nb_classes)
-    _chk(target)
-    if tuple(target.shape) != want or target.device != dev:
-        raise _lib.AdyoloHipError("corpus_classwise_labels: target %s on %s, expected %s on %s for %s"
-                                  % (tuple(target.shape), target.device, want, dev, loss))
-    if status.dtype != torch.int32 or status.device != dev or not status.is_contiguous() or status.numel() < 1:
-        raise _lib.AdyoloHipError("corpus_classwise_labels: status must be an int32 word on %s" % dev)
+    b, n_ev = _corpus_classwise_args("corpus_classwise_labels", events, items, xyz, n_label_frames, nb_classes, loss, target,
+                                     status)
     _c("adyolo_corpus_classwise_labels", _p(events), _p(xyz), n_ev, _p(items), b, int(max_events), int(n_label_frames),
        int(nb_classes), CORPUS_FORMATS[loss], _p(target), _p(status), _stream())
     return target
@@ -1977,25 +1978,8 @@ def corpus_classwise_labels_mix(events, items, mates, xyz, max_events, n_label_f
     """``corpus_classwise_labels`` for mixed items: the dense targets of the host encoders on ``augmentations.merge_labels(item,
     mate)``, each event's direction vector from its own source's combination (adyolo_hip.h ``adyolo_corpus_classwise_labels_mix``).
     mates int64 (B, 8) as for ``corpus_gather_mix``.  No allocation, no sync."""
-    dev = items.device
-    _corpus_i64("corpus_classwise_labels_mix: items", items, dev)
-    _corpus_mates("corpus_classwise_labels_mix", items, mates)
-    if not events.is_cuda or events.dtype != torch.float64 or not events.is_contiguous() or events.dim() != 2 \
-            or events.shape[1] != 4 or events.device != dev:
-        raise _lib.AdyoloHipError("corpus_classwise_labels_mix: events must be a contiguous float64 tensor (E, 4) on %s" % dev)
-    n_ev = events.shape[0]
-    if xyz.dtype != torch.float32 or xyz.device != dev or not xyz.is_contiguous() \
-            or tuple(xyz.shape) != (n_ev, CORPUS_XYZ_SLOTS, 3):
-        raise _lib.AdyoloHipError("corpus_classwise_labels_mix: xyz must be a contiguous float32 tensor (%d, %d, 3) on %s"
-                                  % (n_ev, CORPUS_XYZ_SLOTS, dev))
-    b = items.shape[0]
-    want = corpus_classwise_shape(loss, b, n_label_frames, nb_classes)
-    _chk(target)
-    if tuple(target.shape) != want or target.device != dev:
-        raise _lib.AdyoloHipError("corpus_classwise_labels_mix: target %s on %s, expected %s on %s for %s"
-                                  % (tuple(target.shape), target.device, want, dev, loss))
-    if status.dtype != torch.int32 or status.device != dev or not status.is_contiguous() or status.numel() < 1:
-        raise _lib.AdyoloHipError("corpus_classwise_labels_mix: status must be an int32 word on %s" % dev)
+    b, n_ev = _corpus_classwise_args("corpus_classwise_labels_mix", events, items, xyz, n_label_frames, nb_classes, loss, target,
+                                     status, mates)
     _c("adyolo_corpus_classwise_labels_mix", _p(events), _p(xyz), n_ev, _p(items), _p(mates), b, int(max_events),
        int(n_label_frames), int(nb_classes), CORPUS_FORMATS[loss], _p(target), _p(status), _stream())
     return target

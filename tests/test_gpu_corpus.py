@@ -106,13 +106,14 @@ def test_batches_equal_the_host_path(ops, split, monkeypatch):
 
 
 def test_gather_edges_odd_offsets_no_rotation_and_bad_items(ops):
-    """Direct calls: windows starting on odd frames (8-byte path), odd lengths, comb -1 (identity), an item past the end
-    (zeros + status bit 2) -- nothing is read or written outside the buffers."""
+    """Direct calls: windows starting on odd frames (8-byte path), odd lengths, one and two frames (the tail alone, one
+    iteration of the two-frame loop), comb -1 (identity), an item past the end (zeros + status bit 2) -- nothing is read or
+    written outside the buffers: for every n the last item ends exactly at the end of ``pcm``."""
     from adyolo_amd.augmentations import COMBINATIONS, rotate_audio
     g = torch.Generator().manual_seed(3)
     pcm = torch.randint(-32768, 32768, (1001, 4), generator=g, dtype=torch.int32).to(torch.int16).to("cuda:0")
     rot = ops.corpus_rot_table(COMBINATIONS)
-    for n in (257, 256):
+    for n in (1, 2, 257, 256):
         offs, combs = [0, 1, 3, 744, 1001 - n], [5, -1, 15, 8, 2]
         items = torch.zeros(5, 8, dtype=torch.int64)
         items[:, 0] = torch.tensor(offs)

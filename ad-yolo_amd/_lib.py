@@ -44,6 +44,7 @@ SIGNATURES = {
     "adyolo_conv3x3_wgrad_slabs": (I, [I] * 5),
     "adyolo_conv3x3_wgrad": (I, [P] * 6 + [I] * 6 + [P]),
     "adyolo_wgrad_plan": (I, [I] * 6 + [P]),
+    "adyolo_conv_fwd_plan": (I, [I] * 9 + [P]),
     "adyolo_gemm": (I, [P] * 5 + [I] * 10 + [P]),
     "adyolo_gemm_plan": (I, [I] * 8 + [P, P, P]),
     "adyolo_gemm_batched": (I, [P] * 3 + [I] * 10 + [L] * 6 + [F, I, P]),

@@ -42,6 +42,9 @@ int fill32(void *ptr, uint32_t value, size_t n32, hipStream_t st);
 // wino4w.hip: the geometry functions the launchers call); out8 as documented at adyolo_wgrad_plan.
 void wino_wgrad_plan(int N, int H, int W, int Cin, int Cout, int *out8);
 void wino4_wgrad_plan(int N, int H, int W, int Cin, int Cout, int *out8);
+// ... and of the forward / data-gradient launches as adyolo_conv_fwd_plan reports them (wino.hip, wino4.hip); out24 as documented there
+void wino_fwd_plan(int N, int H, int W, int Cin, int Cout, int affine, int *out24);
+void wino4_fwd_plan(int N, int H, int W, int Cin, int Cout, int operands, int mask_bits, int affine, int *out24);
 
 // v_mfma_f32_32x32x2_f32: D(32x32) += A(32x2) * B(2x32); lane l holds A[l&31][l>>5], B[l>>5][l&31];
 // D register r of lane l is D[(r&3) + 8*(r>>2) + 4*(l>>5)][l&31].

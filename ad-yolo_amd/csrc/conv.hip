@@ -628,12 +628,11 @@ template <int KC, int BN, int TW>
 static int launch_fwd(const float *x, const float *wpk, const float *bias, const float *addend,
                       const float *addend_mask, const float *in_scale, const float *in_shift, float *y, float *stats,
                       const float *stat_aux, const float *stat_mean, const float *stat_invstd, const float *stat_mask,
-                      int N, int H, int W, int Cin, int Cout, int relu, int mask_bits, hipStream_t st) {
+                      int N, int H, int W, int Cin, int Cout, int relu, int mask_bits, hipStream_t st, int tilesW, int tilesH) {
     // (a variant that walks several patches per workgroup and prefetches the next halo patch into registers under
     //  the current patch's MFMAs was measured 6-9 % SLOWER at every stage on MI355X -- 252 VGPRs, no gain over the
     //  overlap two resident workgroups per CU already give -- and was removed; see DESIGN.md "Tried and rejected")
-    constexpr int TH = 256 / TW;
-    const int tilesW = cdiv(W, TW), tilesH = cdiv(H, TH);
+    // (tilesW x tilesH tiles of 256 / TW rows x TW columns: conv3x3_fwd_variant)
     dim3 grid((unsigned)(N * tilesH * tilesW), (unsigned)(Cout / BN));
     hipLaunchKernelGGL((conv3x3_fwd_kernel<KC, BN, TW>), grid, dim3(256), 0, st, x, wpk, bias, addend, addend_mask,
                        in_scale, in_shift, y, stats, stat_aux, stat_mean, stat_invstd, stat_mask, H, W, Cin, Cout, tilesW,
@@ -672,6 +671,24 @@ extern "C" int adyolo_conv3x3_tiles(int N, int H, int W) {
     return N * cdiv(H, TH) * cdiv(W, TW);
 }
 
+// THE choice of kernel and tile of an adyolo_conv3x3_fwd launch, for the launcher and for adyolo_conv_fwd_plan.  plain: no addend,
+// input affine, stat_aux or stat_mask (what the stem kernel does not take).  The stem kernel's tile is 8 rows x 32 columns.
+struct ConvFwdVariant {
+    int stem, KC, BN, TW, TH, tilesW, tilesH;
+};
+static ConvFwdVariant conv3x3_fwd_variant(int H, int W, int Cin, int Cout, bool plain) {
+    ConvFwdVariant v = {};
+    const bool wide = W >= 32;
+    v.stem = Cin == 8 && Cout == 32 && wide && plain;
+    v.KC = Cin == 8 ? 8 : 32;
+    v.BN = Cin != 8 && Cout % 64 == 0 ? 64 : 32;
+    v.TW = wide ? 32 : 16;
+    v.TH = v.stem ? 8 : 256 / v.TW;
+    v.tilesW = cdiv(W, v.TW);
+    v.tilesH = cdiv(H, v.TH);
+    return v;
+}
+
 extern "C" int adyolo_conv3x3_fwd(const float *x, const float *wpk, const float *bias, const float *addend,
                                   const float *addend_mask, const float *in_scale, const float *in_shift, float *y,
                                   float *stats, const float *stat_aux, const float *stat_mean,
@@ -688,18 +705,18 @@ extern "C" int adyolo_conv3x3_fwd(const float *x, const float *wpk, const float 
                    "conv3x3_fwd: stat_aux needs stats, stat_mean and stat_invstd");
     ADYOLO_REQUIRE(!stat_mask || stats, ADYOLO_EINVAL, "conv3x3_fwd: stat_mask needs stats");
     hipStream_t st = as_stream(stream);
-    const bool wide = W >= 32;
+    const ConvFwdVariant v = conv3x3_fwd_variant(H, W, Cin, Cout, !addend && !in_scale && !stat_aux && !stat_mask);
 #define ADYOLO_FWD(KC_, BN_, TW_) \
     launch_fwd<KC_, BN_, TW_>(x, wpk, bias, addend, addend_mask, in_scale, in_shift, y, stats, stat_aux, stat_mean, \
-                              stat_invstd, stat_mask, N, H, W, Cin, Cout, relu, mask_bits, st)
-    if (Cin == 8 && Cout == 32 && wide && !addend && !in_scale && !stat_aux && !stat_mask) {      // the stem
-        const int tilesW = cdiv(W, 32), tilesH = cdiv(H, 8);
-        hipLaunchKernelGGL(stem_fwd_kernel, dim3((unsigned)(N * tilesH * tilesW)), dim3(256), 0, st, x, wpk, bias, y, stats, H,
-                           W, tilesW, tilesH, relu);
+                              stat_invstd, stat_mask, N, H, W, Cin, Cout, relu, mask_bits, st, v.tilesW, v.tilesH)
+    if (v.stem) {
+        hipLaunchKernelGGL(stem_fwd_kernel, dim3((unsigned)(N * v.tilesH * v.tilesW)), dim3(256), 0, st, x, wpk, bias, y, stats, H,
+                           W, v.tilesW, v.tilesH, relu);
         return check_launch("stem_fwd");
     }
-    if (Cin == 8) return wide ? ADYOLO_FWD(8, 32, 32) : ADYOLO_FWD(8, 32, 16);
-    if (Cout % 64 == 0) return wide ? ADYOLO_FWD(32, 64, 32) : ADYOLO_FWD(32, 64, 16);
+    const bool wide = v.TW == 32;
+    if (v.KC == 8) return wide ? ADYOLO_FWD(8, 32, 32) : ADYOLO_FWD(8, 32, 16);
+    if (v.BN == 64) return wide ? ADYOLO_FWD(32, 64, 32) : ADYOLO_FWD(32, 64, 16);
     return wide ? ADYOLO_FWD(32, 32, 32) : ADYOLO_FWD(32, 32, 16);
 #undef ADYOLO_FWD
 }
@@ -785,6 +802,53 @@ extern "C" int adyolo_wgrad_plan(int form, int N, int H, int W, int Cin, int Cou
         wino4_wgrad_plan(N, H, W, Cin, Cout, out8);
     }
     out8[7] = 1;
+    return 0;
+}
+
+// Host only, no launch: what adyolo_conv3x3_fwd (form 0: conv3x3_fwd_kernel, 1: stem_fwd_kernel), adyolo_wino_fwd (2) and
+// adyolo_wino4_fwd (3) would launch for a shape and operand set -- through the functions those launchers call (conv3x3_fwd_variant,
+// wino_fwd_geometry, wino4_fwd_geometry + wino4p_variant).  operands: the ADYOLO_W4_* bits; affine: an input affine is given.
+// out24 as documented in include/adyolo_hip.h; out24[0] == 0: the entry point refuses the launch (or, forms 0 / 1, takes the other
+// of its two kernels).
+extern "C" int adyolo_conv_fwd_plan(int form, int N, int H, int W, int Cin, int Cout, int operands, int mask_bits, int affine,
+                                    int *out24) {
+    ADYOLO_REQUIRE(out24 && form >= 0 && form <= 3 && N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && operands >= 0 && operands < 64,
+                   ADYOLO_EINVAL, "conv_fwd_plan: bad arguments");
+    for (int i = 0; i < 24; ++i) out24[i] = 0;
+    // what all three entry points refuse
+    if ((mask_bits & ~3) || (mask_bits && ((long)H * W * (Cout / 4)) % 64 != 0)) return 0;
+    if (((operands & ADYOLO_W4_ADDEND_MASK) && !(operands & ADYOLO_W4_ADDEND)) ||
+        ((operands & (ADYOLO_W4_STAT_AUX | ADYOLO_W4_STAT_MASK)) && !(operands & ADYOLO_W4_STATS)))
+        return 0;
+    if (form <= 1) {
+        if (Cout % 32 || (Cin != 8 && Cin % 32)) return 0;
+        const ConvFwdVariant v = conv3x3_fwd_variant(
+            H, W, Cin, Cout, !affine && !(operands & (ADYOLO_W4_ADDEND | ADYOLO_W4_STAT_AUX | ADYOLO_W4_STAT_MASK)));
+        if (v.stem != form) return 0;
+        out24[0] = v.stem ? 2 : 1;
+        out24[1] = v.TH;
+        out24[2] = v.TW;
+        out24[3] = v.tilesH;
+        out24[4] = v.tilesW;
+        out24[5] = N * v.tilesH * v.tilesW;
+        out24[6] = v.BN / 32;
+        out24[7] = Cout / v.BN;
+        out24[9] = out24[5];
+        out24[10] = v.stem ? 1 : Cout / v.BN;
+        out24[13] = !v.stem && affine;
+        out24[15] = v.KC;
+        out24[16] = v.BN;
+        out24[17] = v.TW;
+        return 0;
+    }
+    if (Cin % 32 || Cout % 32 || Cin > 512) return 0;
+    if ((size_t)(H + (form == 3 ? 2 : 0)) * W * Cin * 4 >= ((size_t)1 << 31) || (size_t)H * W * Cout * 4 >= ((size_t)1 << 31) ||
+        (long)H * W >= (1L << 23))
+        return 0;
+    if (form == 2)
+        wino_fwd_plan(N, H, W, Cin, Cout, affine, out24);
+    else
+        wino4_fwd_plan(N, H, W, Cin, Cout, operands, mask_bits, affine, out24);
     return 0;
 }
 

@@ -391,6 +391,45 @@ extern "C" int adyolo_wino_pack_many(const int64_t *table, int n, int max_cout, 
     return check_launch("wino_pack_many");
 }
 
+// THE geometry of an adyolo_wino_fwd launch (patches of 8 rows x 16 columns, NT 32-channel output blocks per workgroup, channel
+// blocks dealt to the XCDs when there are 1, 2, 4 or 8 of them), for the launcher and for adyolo_conv_fwd_plan
+struct WinoFwdGeometry {
+    int tilesW, tilesH, nsp, nt, ncb, xcd_div, blocks, one;
+};
+static WinoFwdGeometry wino_fwd_geometry(int N, int H, int W, int Cin, int Cout) {
+    WinoFwdGeometry g = {};
+    g.tilesW = cdiv(W, 16);
+    g.tilesH = cdiv(H, 8);
+    g.nsp = N * g.tilesH * g.tilesW;
+    g.nt = Cout % 64 == 0 ? 2 : 1;
+    g.ncb = Cout / (32 * g.nt);
+    g.blocks = g.nsp * g.ncb;
+    if (g.ncb <= 8 && 8 % g.ncb == 0) {
+        g.xcd_div = 8 / g.ncb;
+        g.blocks = cdiv(g.nsp, g.xcd_div) * 8;
+    }
+    g.one = Cin == WKC;                                   // the whole contraction is one chunk
+    return g;
+}
+
+// adyolo_conv_fwd_plan, form 2 (out24 as documented there); the arguments were checked as adyolo_wino_fwd checks them
+void adyolo::wino_fwd_plan(int N, int H, int W, int Cin, int Cout, int affine, int *out24) {
+    const WinoFwdGeometry g = wino_fwd_geometry(N, H, W, Cin, Cout);
+    out24[0] = 3;
+    out24[1] = 8;
+    out24[2] = 16;
+    out24[3] = g.tilesH;
+    out24[4] = g.tilesW;
+    out24[5] = g.nsp;
+    out24[6] = g.nt;
+    out24[7] = g.ncb;
+    out24[8] = g.xcd_div;
+    out24[9] = g.blocks;
+    out24[10] = 1;
+    out24[13] = affine ? 1 : 0;
+    out24[14] = g.one;
+}
+
 extern "C" int adyolo_wino_fwd(const float *x, const float *u, const float *bias, const float *addend,
                                const float *addend_mask, const float *in_scale, const float *in_shift, float *y,
                                float *stats, const float *stat_aux, const float *stat_mean, const float *stat_invstd,
@@ -411,21 +450,14 @@ extern "C" int adyolo_wino_fwd(const float *x, const float *u, const float *bias
     ADYOLO_REQUIRE(!stat_aux || (stats && stat_mean && stat_invstd), ADYOLO_EINVAL,
                    "wino_fwd: stat_aux needs stats, stat_mean and stat_invstd");
     ADYOLO_REQUIRE(!stat_mask || stats, ADYOLO_EINVAL, "wino_fwd: stat_mask needs stats");
-    const int tilesW = cdiv(W, 16), tilesH = cdiv(H, 8);
-    const int nsp = N * tilesH * tilesW;
-    const int nt = Cout % 64 == 0 ? 2 : 1;
-    const int ncb = Cout / (32 * nt);
-    int xcd_div = 0, blocks = nsp * ncb;
-    if (ncb <= 8 && 8 % ncb == 0) {
-        xcd_div = 8 / ncb;
-        blocks = cdiv(nsp, xcd_div) * 8;
-    }
+    const WinoFwdGeometry g = wino_fwd_geometry(N, H, W, Cin, Cout);
+    const int tilesW = g.tilesW, tilesH = g.tilesH, nsp = g.nsp, nt = g.nt, ncb = g.ncb, xcd_div = g.xcd_div, blocks = g.blocks;
     hipStream_t st = as_stream(stream);
 #define ADYOLO_WINO_FWD(NT_, ONE_)                                                                                  \
     hipLaunchKernelGGL((wino_fwd_kernel<NT_, ONE_>), dim3((unsigned)blocks), dim3(256), 0, st, x, u, bias, addend,       \
                        addend_mask, in_scale, in_shift, y, stats, stat_aux, stat_mean, stat_invstd, stat_mask, H, W,   \
                        Cin, Cout, tilesW, tilesH, nsp, ncb, xcd_div, relu, mask_bits)
-    if (Cin == WKC) {
+    if (g.one) {
         if (nt == 2) ADYOLO_WINO_FWD(2, true); else ADYOLO_WINO_FWD(1, true);
     } else {
         if (nt == 2) ADYOLO_WINO_FWD(2, false); else ADYOLO_WINO_FWD(1, false);

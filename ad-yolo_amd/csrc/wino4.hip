@@ -688,6 +688,78 @@ extern "C" int adyolo_wino4_tiles(int N, int H, int W) {
     return N * cdiv(H, 4 * tr) * cdiv(W, 4 * tc);
 }
 
+// the CU count of the current device (read once; 256 when it cannot be read): the persistent form launches one workgroup per CU
+static int wino4_ncus() {
+    static int ncus = 0;
+    if (ncus == 0) {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 8)
+            v = 256;
+        ncus = v;
+    }
+    return ncus;
+}
+
+// THE geometry of an adyolo_wino4_fwd launch -- which kernel, the patch, the dealing, the grid -- for the launcher and for
+// adyolo_conv_fwd_plan.  Cout: a positive multiple of 32; operands: the ADYOLO_W4_* bits.  Host arithmetic (and the CU count).
+static w4::W4Geometry wino4_fwd_geometry(int N, int H, int W, int Cout, int operands, int mask_bits, bool affine) {
+    w4::W4Geometry g = {};
+    g.nb = Cout % 64 == 0 ? 2 : 1;                     // 32-channel output blocks per workgroup (1: persistent kernel only)
+    g.ncb = Cout / (32 * g.nb);
+    // Narrow maps (W <= 8: the middle stages of the ResNet-Conformer, 800 frames x 4 or 8 bins): plain launches take patches ONE
+    // or TWO tiles wide (128 x 4 / 64 x 8 pixels) on the persistent kernel instead of padding a 16-pixel-wide patch 4 or 2 times
+    // over (ADYOLO_W4_NARROW=0: the 16-wide patch)
+    g.narrow = W <= 8 && !operands && !affine && g.nb == 2 && g.ncb <= 8 && 8 % g.ncb == 0 && g_w4_switches == 3;
+    g.tc = g.narrow ? (W <= 4 ? 1 : 2) : wino4_tc(W);
+    g.tr = 32 / g.tc;
+    g.patchesW = cdiv(W, 4 * g.tc);
+    g.patchesH = cdiv(H, 4 * g.tr);
+    g.nsp = N * g.patchesH * g.patchesW;
+    g.blocks = g.nsp * g.ncb;
+    if (g.ncb <= 8 && 8 % g.ncb == 0) {
+        g.xcd_div = 8 / g.ncb;
+        g.blocks = cdiv(g.nsp, g.xcd_div) * 8;
+    }
+    g.form = adyolo_wino4_fwd_form(Cout, operands, mask_bits);
+    if (g.form == 2) {
+        const int ncus = wino4_ncus(), njs = cdiv(g.nsp, g.xcd_div);
+        g.slots = njs < ncus / 8 ? njs : ncus / 8;
+        g.blocks = g.slots * 8;
+    }
+    return g;
+}
+
+// adyolo_conv_fwd_plan, form 3 (out24 as documented there); the arguments were checked as adyolo_wino4_fwd checks them
+void adyolo::wino4_fwd_plan(int N, int H, int W, int Cin, int Cout, int operands, int mask_bits, int affine, int *out24) {
+    const w4::W4Geometry g = wino4_fwd_geometry(N, H, W, Cout, operands, mask_bits, affine != 0);
+    if (!g.form) return;
+    out24[0] = g.form == 2 ? 5 : 4;
+    out24[1] = 4 * g.tr;
+    out24[2] = 4 * g.tc;
+    out24[3] = g.patchesH;
+    out24[4] = g.patchesW;
+    out24[5] = g.nsp;
+    out24[6] = g.nb;
+    out24[7] = g.ncb;
+    out24[8] = g.xcd_div;
+    out24[9] = g.blocks;
+    out24[10] = 1;
+    out24[11] = g.slots;
+    out24[12] = g.tc;
+    out24[13] = affine ? 1 : 0;
+    out24[21] = g.narrow;
+    if (g.form == 2) {
+        const w4::W4Variant v = w4::wino4p_variant(operands, g.tc, g.nb, W, Cin, Cout, affine != 0, mask_bits);
+        out24[6] = v.nb;
+        out24[12] = v.tc;
+        out24[13] = v.aff;
+        out24[18] = v.bres;
+        out24[19] = v.full;
+        out24[20] = v.mkm;
+    }
+}
+
 extern "C" int adyolo_wino4_pack_w(const float *w, float *u_fwd, float *u_dgrad, int Cout, int Cin_real, int Cin,
                                    void *stream) {
     ADYOLO_REQUIRE(w && (u_fwd || u_dgrad) && Cout > 0 && Cin_real > 0 && Cin >= Cin_real, ADYOLO_EINVAL,
@@ -733,40 +805,19 @@ extern "C" int adyolo_wino4_fwd(const float *x, const float *u, const float *bia
     ADYOLO_REQUIRE(!stat_aux || (stats && stat_mean && stat_invstd), ADYOLO_EINVAL,
                    "wino4_fwd: stat_aux needs stats, stat_mean and stat_invstd");
     ADYOLO_REQUIRE(!stat_mask || stats, ADYOLO_EINVAL, "wino4_fwd: stat_mask needs stats");
-    const int ncb = Cout / (32 * nb);
     const int operands = (stats ? ADYOLO_W4_STATS : 0) | (addend ? ADYOLO_W4_ADDEND : 0) | (addend_mask ? ADYOLO_W4_ADDEND_MASK : 0) |
                          (stat_aux ? ADYOLO_W4_STAT_AUX : 0) | (stat_mask ? ADYOLO_W4_STAT_MASK : 0) | (bias ? ADYOLO_W4_BIAS : 0);
-    // Narrow maps (W <= 8: the middle stages of the ResNet-Conformer, 800 frames x 4 or 8 bins): plain launches take patches ONE
-    // or TWO tiles wide (128 x 4 / 64 x 8 pixels) on the persistent kernel instead of padding a 16-pixel-wide patch 4 or 2 times
-    // over (ADYOLO_W4_NARROW=0: the 16-wide patch)
-    const bool narrow = W <= 8 && !operands && !in_scale && nb == 2 && ncb <= 8 && 8 % ncb == 0 && g_w4_switches == 3;
-    const int tc = narrow ? (W <= 4 ? 1 : 2) : wino4_tc(W), tr = 32 / tc;
-    const int patchesW = cdiv(W, 4 * tc), patchesH = cdiv(H, 4 * tr);
-    const int nsp = N * patchesH * patchesW;
-    int xcd_div = 0, blocks = nsp * ncb;
-    if (ncb <= 8 && 8 % ncb == 0) {
-        xcd_div = 8 / ncb;
-        blocks = cdiv(nsp, xcd_div) * 8;
-    }
+    const w4::W4Geometry g = wino4_fwd_geometry(N, H, W, Cout, operands, mask_bits, in_scale != nullptr);
+    const int tc = g.tc, patchesW = g.patchesW, patchesH = g.patchesH, nsp = g.nsp, ncb = g.ncb, xcd_div = g.xcd_div, blocks = g.blocks;
     hipStream_t st = as_stream(stream);
-    const int form = adyolo_wino4_fwd_form(Cout, operands, mask_bits);
+    const int form = g.form;
     ADYOLO_REQUIRE(form, ADYOLO_ENOSUP,
                    "wino4_fwd: Cout=%d (a multiple of 32 but not of 64) needs the persistent kernel: no bias, masks as bits, Cout / 32 in "
                    "{1, 2, 4, 8}, operand combination %d not built", Cout, operands);
     g_wino4_last_form = form;
     if (form == 2) {
-        static int ncus = 0;
-        if (ncus == 0) {
-            int dev = 0, v = 0;
-            if (hipGetDevice(&dev) != hipSuccess ||
-                hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 8)
-                v = 256;
-            ncus = v;
-        }
-        const int njs = cdiv(nsp, xcd_div);
-        const int slots = njs < ncus / 8 ? njs : ncus / 8;
         w4::W4Launch a = {x, u, bias, addend, addend_mask, in_scale, in_shift, y, stats, stat_aux, stat_mean, stat_invstd, stat_mask,
-                          H, W, Cin, Cout, patchesW, patchesH, nsp, ncb, xcd_div, relu, mask_bits, tc, slots * 8, nb, st};
+                          H, W, Cin, Cout, patchesW, patchesH, nsp, ncb, xcd_div, relu, mask_bits, tc, g.slots * 8, nb, st};
         wino4p_launcher(operands)(a);
         return check_launch("wino4_fwd (persistent)");
     }

@@ -49,12 +49,7 @@
 #define W4P_AFF_EXEC 1    // 1: the producer's BatchNorm affine is applied under an EXEC mask made by the range comparison (aff6_inrange),
                           // 0: compare + four selects of the shift per pixel (until round 6)
 #endif
-#ifndef W4P_BRES
-#define W4P_BRES 1        // 1: 32 -> 32 layers take the resident-U form of the kernel (BRES below), 0: the B ring as everywhere else
-#endif
-#ifndef W4P_MKDEDUP
-#define W4P_MKDEDUP 1     // 1: the epilogue's ReLU-mask bit loads shared between the pixels of a row segment where Cout allows (32 / 64 / 128)
-#endif
+// (W4P_BRES, W4P_MKDEDUP, W4P_FULL: wino4p_launch.hpp, beside wino4p_variant, which they steer)
 #ifndef W4P_REQ_FENCE
 #define W4P_REQ_FENCE 0   // 1: a compiler barrier behind the step-16 requests of the per-pair bodies (BRES, FULL), which otherwise drift down
                           // to ~step 23 -- measured neutral (+-0.5 %, profiles/r06_w4p_leftpin_ab.txt): off
@@ -64,9 +59,6 @@
 #endif
 #ifndef W4P_LEFT_PIN
 #define W4P_LEFT_PIN 1    // 1: the leftover-row data get an (empty) unconditional use in front of `if (lwave)`: see pair_body, step 22
-#endif
-#ifndef W4P_FULL
-#define W4P_FULL 1        // 1: 32 -> 32 layers with operand sets 15 / 27 / 31 request both halves of the next patch's input lines together
 #endif
 #ifndef W4P_BRES_ACC
 #define W4P_BRES_ACC 3    // channel groups (of the four) of the resident U kept in AccVGPRs
@@ -979,58 +971,52 @@ void launch_wino4p(const W4Launch &a) {
                        a.stat_invstd, a.stat_mask, a.H, a.W, a.Cin, a.Cout, a.patchesW, a.patchesH, a.nsp, a.ncb,          \
                        a.xcd_div, a.relu, a.mask_bits)
 #define ADYOLO_WINO4P_NB(NB_)                                                                                              \
-    if (a.tc == 8) {                                                                                                       \
-        if (a.in_scale) ADYOLO_WINO4P_FWD(8, true, NB_); else ADYOLO_WINO4P_FWD(8, false, NB_);                            \
+    if (v.tc == 8) {                                                                                                       \
+        if (v.aff) ADYOLO_WINO4P_FWD(8, true, NB_); else ADYOLO_WINO4P_FWD(8, false, NB_);                                 \
     } else {                                                                                                               \
-        if (a.in_scale) ADYOLO_WINO4P_FWD(4, true, NB_); else ADYOLO_WINO4P_FWD(4, false, NB_);                            \
+        if (v.aff) ADYOLO_WINO4P_FWD(4, true, NB_); else ADYOLO_WINO4P_FWD(4, false, NB_);                                 \
     }
-    // narrow maps (W <= 8: the middle stages of the ResNet-Conformer): patches one or two tiles wide, plain launches only
+    // WHICH instantiation: wino4p_variant (wino4p_launch.hpp) decides, for this launcher and for adyolo_conv_fwd_plan alike; the
+    // `if constexpr`s only keep a translation unit from instantiating what the function never returns for its EPI
+    const W4Variant v = wino4p_variant(EPI, a.tc, a.nb, a.W, a.Cin, a.Cout, a.in_scale != nullptr, a.mask_bits);
     if constexpr (EPI == 0) {
-        if (a.tc == 1 || a.tc == 2) {
-            if (a.tc == 1) ADYOLO_WINO4P_FWD(1, false, 2); else ADYOLO_WINO4P_FWD(2, false, 2);
+        if (v.tc == 1 || v.tc == 2) {
+            if (v.tc == 1) ADYOLO_WINO4P_FWD(1, false, 2); else ADYOLO_WINO4P_FWD(2, false, 2);
             return;
         }
     }
-    // shared ReLU-mask words (MKM): the three shapes the SE-ResNet's data gradients have, bits for every mask that is given
-    const bool mkshare = W4P_MKDEDUP && (EPI == 15 || EPI == 27 || EPI == 31) && (a.W & 3) == 0 && !a.in_scale &&
-                         (a.mask_bits & (((EPI & 4) ? 1 : 0) | ((EPI & 16) ? 2 : 0))) == (((EPI & 4) ? 1 : 0) | ((EPI & 16) ? 2 : 0));
     if constexpr (EPI == 15 || EPI == 27 || EPI == 31) {
-        if (mkshare && a.nb == 2 && a.tc == 8 && a.Cout == 64) {
+        if (v.mkm == 2) {
             ADYOLO_WINO4P_FWD(8, false, 2, false, false, 2);
             return;
         }
-        // (Cout = 128, two 8-byte words per component and row segment -- MKM 3 -- measured 0.5-2.9 % SLOWER than the dwords and is
-        //  not instantiated: profiles/r06_w4p_mkdedup_ab.txt)
-        if (mkshare && a.nb == 1 && a.tc == 8 && a.Cout == 32 && a.Cin == 32 && W4P_FULL) {
+        if (v.mkm == 1) {
             ADYOLO_WINO4P_FWD(8, false, 1, false, true, 1);
             return;
         }
     }
-    if (a.nb == 2) {
+    if (v.nb == 2) {
         ADYOLO_WINO4P_NB(2)
-    } else {
-        // 32 -> 32 layers: the resident-U form where the epilogue leaves it the registers (operand sets 15 / 27 / 31 do not: 20-46
-        // spilled registers and 6-14 % slower, profiles/r06_w4p_bres_ab.txt)
-        if constexpr (W4P_FULL && (EPI == 15 || EPI == 27 || EPI == 31)) {
-            // the same layers where resident U does not fit: whole input lines at once.  (Data gradients carry no producer affine;
-            //  a launch that does takes the B-ring form below, which is the one the affine variants are checked in.)
-            if (a.Cin == 32 && !a.in_scale) {
-                if (a.tc == 8) ADYOLO_WINO4P_FWD(8, false, 1, false, true); else ADYOLO_WINO4P_FWD(4, false, 1, false, true);
-                return;
-            }
-        }
-        if constexpr (W4P_BRES && (EPI == 0 || EPI == 1 || EPI == 2 || EPI == 9)) {
-            if (a.Cin == 32) {
-                if (a.tc == 8) {
-                    if (a.in_scale) ADYOLO_WINO4P_FWD(8, true, 1, true); else ADYOLO_WINO4P_FWD(8, false, 1, true);
-                } else {
-                    if (a.in_scale) ADYOLO_WINO4P_FWD(4, true, 1, true); else ADYOLO_WINO4P_FWD(4, false, 1, true);
-                }
-                return;
-            }
-        }
-        ADYOLO_WINO4P_NB(1)
+        return;
     }
+    // 32-channel output blocks: whole input lines (FULL), resident U (BRES), else the B ring
+    if constexpr (W4P_FULL && (EPI == 15 || EPI == 27 || EPI == 31)) {
+        if (v.full) {
+            if (v.tc == 8) ADYOLO_WINO4P_FWD(8, false, 1, false, true); else ADYOLO_WINO4P_FWD(4, false, 1, false, true);
+            return;
+        }
+    }
+    if constexpr (W4P_BRES && (EPI == 0 || EPI == 1 || EPI == 2 || EPI == 9)) {
+        if (v.bres) {
+            if (v.tc == 8) {
+                if (v.aff) ADYOLO_WINO4P_FWD(8, true, 1, true); else ADYOLO_WINO4P_FWD(8, false, 1, true);
+            } else {
+                if (v.aff) ADYOLO_WINO4P_FWD(4, true, 1, true); else ADYOLO_WINO4P_FWD(4, false, 1, true);
+            }
+            return;
+        }
+    }
+    ADYOLO_WINO4P_NB(1)
 #undef ADYOLO_WINO4P_NB
 #undef ADYOLO_WINO4P_FWD
 }

@@ -190,6 +190,18 @@ int adyolo_conv3x3_wgrad(const float *x, const float *dy, const float *in_scale,
  * 1), tile / strip width in pixels, the stem's workgroups (min(slabs, 512)), 1 when the entry point takes the shape with that
  * kernel}; all zeros when it does not. */
 int adyolo_wgrad_plan(int form, int N, int H, int W, int Cin, int Cout, int *out8);
+/* host only, no launch (the CU count the F(4x4) launcher caches apart): what the forward / data-gradient entry points would
+ * launch for a shape and operand set, through the functions their launchers call.  form 0: adyolo_conv3x3_fwd with
+ * conv3x3_fwd_kernel, 1: the same entry point with stem_fwd_kernel, 2: adyolo_wino_fwd, 3: adyolo_wino4_fwd.  operands: the
+ * ADYOLO_W4_* bits above; mask_bits as at the entry points; affine: in_scale / in_shift are given.  out24 =
+ *   [0] kernel: 0 refused (forms 0 / 1: or the entry point takes its other kernel), 1 conv3x3_fwd_kernel, 2 stem_fwd_kernel,
+ *       3 wino_fwd_kernel, 4 wino4_fwd_kernel, 5 wino4p_fwd_kernel (persistent)
+ *   [1] [2] rows and columns of a patch,  [3] patchesH,  [4] patchesW,  [5] nsp = N * patchesH * patchesW
+ *   [6] 32-channel output blocks per workgroup (BN / 32 | NT | NB),  [7] ncb channel blocks,  [8] xcd_div (0: no XCD dealing)
+ *   [9] grid x,  [10] grid y,  [11] slots (persistent: workgroups per XCD, grid = 8 slots; else 0)
+ *   [12] TC,  [13] AFF,  [14] ONE,  [15] KC,  [16] BN,  [17] TW,  [18] BRES,  [19] FULL,  [20] MKM,  [21] narrow,  [22] [23] 0
+ * (template arguments of the kernel launched; 0 where the kernel has no such argument).  All zeros when refused. */
+int adyolo_conv_fwd_plan(int form, int N, int H, int W, int Cin, int Cout, int operands, int mask_bits, int affine, int *out24);
 
 /* ------------------------------------------------------------------------------------------------
  * K7  dense GEMM on fp32 MFMA:  C[m][n] = sum_k opA(m,k) * opB(n,k) (+ bias[n])

@@ -62,7 +62,10 @@ SETS = (1, 9, 15, 27, 31)         # ADYOLO_W4_* bits: 1 statistics, 2 addend, 4 
 # one / two / three channel blocks, 32-channel blocks (F(4x4): the persistent kernel only)
 EPI_SMALL = [(2, 13, 16, 32, 32), (1, 5, 5, 32, 64), (2, 37, 40, 64, 64), (3, 20, 32, 64, 96), (2, 9, 64, 32, 128),
              (1, 33, 16, 64, 256), (2, 70, 48, 32, 32)]
-# a few samples at each stage geometry of the benchmark (60 s clips: 2400 x 64 x 32 ... 600 x 16 x 256)
+# a few samples at each stage geometry of the benchmark (60 s clips: 2400 x 64 x 32 ... 600 x 16 x 256).  On 256 CUs only the first
+# gives a workgroup of the persistent kernel a second patch (600 full patches on 256 workgroups, 32 -> 32 forms only); every other
+# shape of this module deals one patch per workgroup (oracle/fwd_stage.py: ``walks``).  The hand-over between patches is
+# tests/test_gpu_fwd_stage.py's.
 EPI_BENCH = [(2, 2400, 64, 32, 32), (2, 1200, 32, 64, 64), (2, 600, 16, 128, 128), (2, 600, 16, 256, 256)]
 EPI_LOG = {}                      # ops.DISPATCH_LOG of every epilogue launch of this module
 

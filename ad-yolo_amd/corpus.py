@@ -34,6 +34,9 @@ Inference on a folder of recordings of any length has the third pair: ``load_inf
 lays the recordings out the same way, without events, and ``InferDeviceCorpus`` cuts them into overlapping windows of one shape
 (``window_plan``) through a window table uploaded once; ``test.infer_epoch_corpus`` runs the windows in passes through one
 recorded graph, keeps each window's frames that have context on both sides and stitches them back onto the recordings' axes.
+With ``load_infer_split(..., resample=True)`` (``infer_split_from_arrays(..., rates=...)``) the recordings may be at any standard
+rate and in int16, 24-bit or float32: those that are not int16 at ``data_config.sr`` stay in their native form on the host, and
+the upload converts them on the device (``ops.resample_pcm``, resample.py) into the places the layout left for them.
 """
 import copy
 import os
@@ -93,7 +96,8 @@ class HostCorpus:
     """
 
     def nbytes(self):
-        return int(self.audio.nbytes + self.events.nbytes)
+        native = sum(a.nbytes for a in getattr(self, "native", None) or () if a is not None)     # a resample=True split
+        return int(self.audio.nbytes + self.events.nbytes + native)
 
 
 def load_chunked_split(params, set_type="train", verify="sample"):
@@ -826,21 +830,55 @@ def split_pass_rows(rows, counts, base_frame, frame_start):
     return out
 
 
-def infer_split_from_arrays(names, arrays, params):
+def infer_split_from_arrays(names, arrays, params, rates=None):
     """Recordings held in memory (int16 (n, 4) each) -> the ``HostCorpus`` ``load_infer_split`` returns: every recording whole in
     one int16 stream, each on a 16-frame boundary, ``lengths``, no events.  ``ValueError`` naming the recording for anything
-    that is not int16 (n, 4)."""
+    that is not int16 (n, 4).
+
+    rates: one sample rate (Hz) per recording; each array may then be int16, int32 (24-bit PCM left-justified, as scipy reads
+    it) or float32 (n, 4).  An int16 recording at ``data_config.sr`` is laid out as above.  Every other one keeps its samples on
+    the host (``native``) and has its converted length, ceil(n L / M) (``resample.n_out``), in ``lengths`` and a zeroed place
+    of that length in ``audio``, which ``InferDeviceCorpus`` fills on the device: ``rec_start``, the window plan and the frame
+    axis are those of the converted recordings.  The split then also holds ``rates``, ``kinds`` (0 int16, 1 int32, 2 float32)
+    and ``native_lengths``.  ``ValueError`` naming the recording and both rates for a ratio ``resample.plan`` refuses."""
     names = [str(n) for n in names]
     arrays = list(arrays)
     if len(names) != len(arrays):
         raise ValueError("infer_split_from_arrays: %d names for %d arrays" % (len(names), len(arrays)))
     dc = params["data_config"]
     hop = int(dc.get("sr", 24000) * dc.get("label_hop_len_s", 0.1))                 # FoaDataset.hop_label
-    for name, a in zip(names, arrays):
-        if getattr(a, "dtype", None) != np.int16 or a.ndim != 2 or a.shape[1] != 4:
-            raise ValueError("infer_split_from_arrays: %s holds %s %s, expected int16 (n, 4)"
-                             % (name, getattr(a, "dtype", type(a).__name__), tuple(getattr(a, "shape", ()))))
-    lengths = np.asarray([a.shape[0] for a in arrays], dtype=np.int64).reshape(-1)
+    native = None
+    if rates is None:
+        for name, a in zip(names, arrays):
+            if getattr(a, "dtype", None) != np.int16 or a.ndim != 2 or a.shape[1] != 4:
+                raise ValueError("infer_split_from_arrays: %s holds %s %s, expected int16 (n, 4)"
+                                 % (name, getattr(a, "dtype", type(a).__name__), tuple(getattr(a, "shape", ()))))
+        lengths = np.asarray([a.shape[0] for a in arrays], dtype=np.int64).reshape(-1)
+    else:
+        from . import resample
+        sr = int(dc.get("sr", 24000))
+        rates = [int(r) for r in rates]
+        if len(rates) != len(names):
+            raise ValueError("infer_split_from_arrays: %d rates for %d arrays" % (len(rates), len(arrays)))
+        kinds, native, lengths = [], [], []
+        for name, a, rate in zip(names, arrays, rates):
+            dtype = getattr(a, "dtype", None)
+            kind = resample.KINDS.get(dtype) if isinstance(dtype, np.dtype) else None
+            if kind is None or a.ndim != 2 or a.shape[1] != 4:
+                raise ValueError("infer_split_from_arrays: %s holds %s %s, expected int16, int32 or float32 (n, 4)"
+                                 % (name, getattr(a, "dtype", type(a).__name__), tuple(getattr(a, "shape", ()))))
+            try:
+                l, m = resample.ratio(rate, sr)
+            except ValueError as e:
+                raise ValueError("infer_split_from_arrays: %s: %s" % (name, e))
+            if max(l, m) > resample.MAX_P:                        # what resample.plan refuses, before anything is uploaded
+                raise ValueError("infer_split_from_arrays: %s: %d -> %d Hz is the ratio %d / %d, beyond resample.plan (%d)"
+                                 % (name, rate, sr, l, m, resample.MAX_P))
+            kinds.append(kind)
+            native.append(None if (l == m and kind == 0) else a)
+            lengths.append(resample.n_out(a.shape[0], l, m))
+        native_lengths = np.asarray([a.shape[0] for a in arrays], dtype=np.int64).reshape(-1)
+        lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
     rec_start = np.zeros(len(names) + 1, dtype=np.int64)
     pos = 0
     for i, n in enumerate(lengths.tolist()):
@@ -849,8 +887,12 @@ def infer_split_from_arrays(names, arrays, params):
     rec_start[-1] = pos
     audio = np.zeros((max(pos, 16), 4), dtype=np.int16)
     for i, a in enumerate(arrays):
-        audio[int(rec_start[i]):int(rec_start[i]) + int(lengths[i])] = a
+        if native is None or native[i] is None:
+            audio[int(rec_start[i]):int(rec_start[i]) + int(lengths[i])] = a
     hc = HostCorpus()
+    if native is not None:
+        hc.native, hc.rates, hc.native_lengths = native, np.asarray(rates, dtype=np.int64).reshape(-1), native_lengths
+        hc.kinds = np.asarray(kinds, dtype=np.int64).reshape(-1)
     hc.wav_pth, hc.csv_pth, hc.set_type = None, None, "infer"
     hc.rank, hc.world = 0, 1
     hc.audio = audio
@@ -865,12 +907,18 @@ def infer_split_from_arrays(names, arrays, params):
     return hc
 
 
-def load_infer_split(params, rank=None, world=None, verify="sample", files=None):
+def load_infer_split(params, rank=None, world=None, verify="sample", files=None, resample=False):
     """The int16 4-channel WAV files under ``params['args']['infer_pth']`` read once -> ``HostCorpus`` (the layout of
     ``load_eval_split`` without events).  The file list is ``FoaDataset(params, 'infer')``'s: ``os.listdir`` order on one rank,
     ``sorted(...)[rank::world]`` under data parallelism.  files: names (without ``.wav``) of the recordings to load, in the
     order of that list -- a folder that does not fit HBM is taken in parts; a name the list does not hold raises.
-    ``ValueError`` naming the file for anything that is not int16 (n, 4).  verify: as in ``load_eval_split``."""
+    ``ValueError`` naming the file for anything that is not int16 (n, 4).  verify: as in ``load_eval_split``.
+
+    resample=True: every file's rate and sample format are read.  int16, 24-bit (scipy: int32, left-justified) and float32 files
+    of four channels at any rate ``resample.plan`` takes against ``data_config.sr`` are accepted, anything else is refused by
+    path; an int16 file at ``data_config.sr`` is laid out as above and every other one keeps its samples on the host for
+    ``InferDeviceCorpus`` to convert on the device (``infer_split_from_arrays`` with ``rates``).  Without it the rate of a file
+    is not looked at: a 48 kHz recording is run as if it were at ``data_config.sr``."""
     from scipy.io import wavfile
     if verify not in ("sample", "all", "none"):
         raise ValueError("load_infer_split: verify must be 'sample', 'all' or 'none' (got %r)" % (verify,))
@@ -895,11 +943,42 @@ def load_infer_split(params, rank=None, world=None, verify="sample", files=None)
             raise ValueError("load_infer_split: %s holds %s %s, expected int16 (n, 4)" % (path, data.dtype, tuple(data.shape)))
         return path, data
 
-    hc = infer_split_from_arrays(filelist, [wav_of(name)[1] for name in filelist], params)
+    def native_wav_of(name):
+        from . import resample as rs
+        path = os.path.join(wav_pth, name + ".wav")
+        try:
+            rate, data = wavfile.read(path, mmap=True)
+        except ValueError as e:
+            if "mmap" not in str(e):                             # only scipy's "mmap=True not compatible with 24-bit" is retried
+                raise
+            rate, data = wavfile.read(path, mmap=False)          # 24-bit samples cannot be mapped: read into memory
+        if data.dtype not in rs.KINDS or data.ndim != 2 or data.shape[1] != 4:
+            raise ValueError("load_infer_split: %s holds %s %s, expected int16, 24-bit or float32 (n, 4)"
+                             % (path, data.dtype, tuple(data.shape)))
+        sr = int(params["data_config"].get("sr", 24000))
+        if max(rs.ratio(rate, sr)) > rs.MAX_P:
+            raise ValueError("load_infer_split: %s is at %d Hz; %d -> %d Hz is the ratio %d / %d, beyond resample.plan (%d)"
+                             % ((path, rate, rate, sr) + rs.ratio(rate, sr) + (rs.MAX_P,)))
+        return path, data, int(rate)
+
     n_rec = len(filelist)
     checks = range(n_rec) if verify == "all" else (sorted({0, n_rec // 2, n_rec - 1}) if verify == "sample" and n_rec else ())
+    if resample:
+        read = [native_wav_of(name) for name in filelist]
+        hc = infer_split_from_arrays(filelist, [r[1] for r in read], params, rates=[r[2] for r in read])
+    else:
+        hc = infer_split_from_arrays(filelist, [wav_of(name)[1] for name in filelist], params)
     for i in checks:
-        path, data = wav_of(filelist[i])
+        if resample:
+            path, data, rate = native_wav_of(filelist[i])
+            if hc.native[i] is not None:
+                kept = np.asarray(hc.native[i])
+                if rate != int(hc.rates[i]) or data.dtype != kept.dtype or data.shape != kept.shape or \
+                        not np.array_equal(np.ascontiguousarray(data).view(np.uint8), np.ascontiguousarray(kept).view(np.uint8)):
+                    raise ValueError("load_infer_split: %s changed while the split was read" % path)
+                continue
+        else:
+            path, data = wav_of(filelist[i])
         s0 = int(hc.rec_start[i])
         if not np.array_equal(np.asarray(data), hc.audio[s0:s0 + int(hc.lengths[i])]):
             raise ValueError("load_infer_split: %s changed while the split was read" % path)
@@ -918,7 +997,10 @@ class InferDeviceCorpus(_CorpusBase):
         audio = corpus.launch(p)                 # pass p: (batch_size, n_samples, 4) f32 on the device, no host sync
 
     window_s defaults to ``data_config.chunk_window_s`` (what the model was trained on), margin_s to 2.0 (a configuration
-    default, not a tuned value); both must be whole multiples of the label hop, the window also of the feature hop."""
+    default, not a tuned value); both must be whole multiples of the label hop, the window also of the feature hop.
+
+    A split that carries native recordings (``load_infer_split(..., resample=True)``) is converted on the device during the
+    upload (``_convert_native``); everything after the upload is the same."""
 
     def __init__(self, host_split, params, device="cuda:0", window_s=None, margin_s=None, batch_size=8):
         from .features import HOP
@@ -970,7 +1052,46 @@ class InferDeviceCorpus(_CorpusBase):
         self.pass_base = [int(v) for v in per[:, 0, 3].tolist()]
         self.pass_frames = [int(v) for v in per[:, :, 4].sum(1).tolist()]
         self._to_hbm(hc)
+        self._convert_native(hc, sr)
         self.table = torch.from_numpy(table if len(rows) else np.zeros((1, ops.WINDOW_WORDS), dtype=np.int64)).to(self.device)
+
+    def _convert_native(self, hc, sr):
+        """The recordings a ``resample=True`` / ``rates=`` split kept in their native rate or format: per (rate, kind) group the
+        native samples uploaded as one stream, one ``ops.resample_pcm`` launch into ``self.pcm`` at the recordings' places, the
+        native buffer dropped before the next group's upload (the allocator hands the block on in stream order: no sync).  The
+        alignment tails stay int16 zero.  The status word is read after each group (one host synchronisation per group, beside
+        uploads that block the host anyway): a non-finite float sample or a bad row raises ``AdyoloHipError`` naming the group,
+        here and not in a later ``check()``, because ``infer_epoch_corpus`` clears the word when a pass begins."""
+        native = getattr(hc, "native", None)
+        if native is None:
+            return
+        from . import resample
+        groups = {}
+        for i, a in enumerate(native):
+            if a is not None and a.shape[0]:
+                groups.setdefault((int(hc.rates[i]), int(hc.kinds[i])), []).append(i)
+        for (rate, kind), members in sorted(groups.items()):
+            pl = resample.plan_for(rate, sr)
+            recs, pos = [], 0
+            for i in members:
+                recs.append((pos, int(hc.native_lengths[i]), int(hc.rec_start[i]), int(hc.lengths[i])))
+                pos += int(hc.native_lengths[i])
+            stream = np.concatenate([native[i] for i in members], 0) if len(members) > 1 else np.ascontiguousarray(native[members[0]])
+            src = torch.from_numpy(stream).to(self.device)
+            del stream
+            taps = torch.from_numpy(pl["taps"]).to(self.device)
+            for r0 in range(0, len(recs), 32768):                           # rows per launch: the grid's second dimension
+                rows = torch.tensor(recs[r0:r0 + 32768], dtype=torch.int64, device=self.device)
+                ops.resample_pcm(src, rows, taps, pl["M"], pl["centre"], self.pcm, self.status)
+            del src, taps
+            # read here, once per group: a pass begins with reset_status(), so a bit left in the word would be lost unseen
+            word = int(ops.to_host(self.status)[0])
+            if word:
+                self.status.zero_()
+                shown = ", ".join(hc.rec_names[i] for i in members[:8]) + (", ..." if len(members) > 8 else "")
+                why = "; ".join(msg for bit, msg in ops.CORPUS_STATUS if word & bit)
+                raise ops._lib.AdyoloHipError("InferDeviceCorpus: converting the %d Hz %s recordings (%s) failed (status 0x%x): %s"
+                                              % (rate, ("int16", "24-bit", "float32")[kind], shown, word, why))
 
     def nbytes(self):
         return int(self.pcm.numel() * 2 + self.table.numel() * 8)

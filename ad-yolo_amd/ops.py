@@ -1742,7 +1742,7 @@ def pcm16_to_f32(pcm, out=None):
 
 CORPUS_ITEM_WORDS = 8                                     # ADYOLO_CORPUS_ITEM_WORDS / _ROT_WORDS in adyolo_hip.h
 CORPUS_STATUS = ((1, "more AD-YOLO rows than the target capacity"), (2, "an item outside the corpus"),
-                 (4, "an event class outside [0, nb_classes)"))
+                 (4, "an event class outside [0, nb_classes)"), (8, "an Inf or NaN sample in a float32 recording"))
 CORPUS_XYZ_SLOTS = 17                                     # ADYOLO_CORPUS_XYZ_SLOTS: no rotation + the 16 FOA combinations
 CORPUS_FORMATS = {"seddoa": 0, "masked-seddoa": 0, "accdoa": 1, "adpit": 2}     # ADYOLO_CORPUS_SEDDOA / _ACCDOA / _ADPIT
 
@@ -2033,6 +2033,36 @@ def decode_stitch(decoded, windows, window_frames, pass_base, out, status):
     rec = decoded.numel() // decoded.shape[0]
     _c("adyolo_decode_stitch", _p(decoded), _p(windows), w, wf, rec, int(pass_base), _p(out), out.shape[0], _p(status), _stream())
     return out
+
+
+RESAMPLE_WORDS = 4                                        # ADYOLO_RESAMPLE_WORDS: {src offset, src frames, dst offset, dst frames}
+RESAMPLE_TILE = 256                                       # ADYOLO_RESAMPLE_TILE: output frames per workgroup pass
+RESAMPLE_KINDS = {torch.int16: 0, torch.int32: 1, torch.float32: 2}     # ADYOLO_RESAMPLE_INT16 / _INT32 / _FLOAT32
+
+
+def resample_pcm(src, recs, taps, m, centre, dst, status):
+    """src int16 / int32 (24-bit PCM left-justified) / float32 (S, 4), recs int64 (R, 4) {src offset, src frames, dst offset, dst
+    frames} and taps int32 (L, K) (``resample.plan``) on the device -> dst int16 (D, 4): every row's recording converted by L / m
+    into its place, bit for bit the integer polyphase filter of adyolo_hip.h ``adyolo_resample_pcm``; nothing outside the rows'
+    destinations is written.  A row outside either stream, or whose dst frames are not (src frames * L + m - 1) // m: not
+    written, status bit 2; a non-finite float sample: taken as 0, status bit 8.  No allocation, no sync."""
+    dev = src.device
+    if not src.is_cuda or src.dtype not in RESAMPLE_KINDS or not src.is_contiguous() or src.dim() != 2 or src.shape[1] != 4:
+        raise _lib.AdyoloHipError("resample_pcm: src must be a contiguous int16, int32 or float32 tensor (S, 4) on the device")
+    _corpus_i64("resample_pcm: recs", recs, dev)
+    if recs.dim() != 2 or recs.shape[0] < 1 or recs.shape[1] != RESAMPLE_WORDS:
+        raise _lib.AdyoloHipError("resample_pcm: recs %s are not (R, %d)" % (tuple(recs.shape), RESAMPLE_WORDS))
+    if taps.dtype != torch.int32 or taps.device != dev or not taps.is_contiguous() or taps.dim() != 2 or taps.numel() < 1:
+        raise _lib.AdyoloHipError("resample_pcm: taps must be a contiguous int32 tensor (L, K) on %s" % dev)
+    if dst.dtype != torch.int16 or dst.device != dev or not dst.is_contiguous() or dst.dim() != 2 or dst.shape[1] != 4:
+        raise _lib.AdyoloHipError("resample_pcm: dst must be a contiguous int16 tensor (D, 4) on %s" % dev)
+    if status.dtype != torch.int32 or status.device != dev or status.numel() < 1:
+        raise _lib.AdyoloHipError("resample_pcm: status must be an int32 word on %s" % dev)
+    if int(m) < 1 or int(centre) < 0:
+        raise _lib.AdyoloHipError("resample_pcm: M %r, centre %r" % (m, centre))
+    _c("adyolo_resample_pcm", _p(src), RESAMPLE_KINDS[src.dtype], src.shape[0], _p(recs), recs.shape[0], _p(taps), taps.numel(),
+       taps.shape[0], int(m), taps.shape[1], int(centre), _p(dst), dst.shape[0], _p(status), _stream())
+    return dst
 
 
 def corpus_status_check(word):

@@ -794,6 +794,38 @@ int  adyolo_corpus_gather_windows(const int16_t *pcm, long n_total, const int64_
 int  adyolo_decode_stitch(const float *decoded, const int64_t *windows, int W, int Wf, long rec, long pass_base, float *out,
                           long out_frames, int *status, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Sample-rate conversion of whole recordings (csrc/resample.hip; resample.plan builds the table, corpus.InferDeviceCorpus
+ * and resample.resample_device call it): a polyphase FIR in integer arithmetic from a native four-channel stream into the
+ * int16 stream the calls above read.  The result is defined bit for bit:
+ *   source sample -> Q23 integer q    ADYOLO_RESAMPLE_INT16    q = x << 8
+ *                                     ADYOLO_RESAMPLE_INT32    q = x >> 8, arithmetic (24-bit PCM left-justified in 32 bits)
+ *                                     ADYOLO_RESAMPLE_FLOAT32  q = clamp(rint(x * 2^23), -2^23, 2^23 - 1), ties to even; Inf and
+ *                                                              NaN count as 0 and set ADYOLO_CORPUS_NONFINITE
+ *   output frame j of a recording of n frames (0 <= j < n_out = (n L + M - 1) / M), per channel:
+ *     t = j M + centre,  p = t % L,  i0 = t / L
+ *     acc = sum over k in [0, K) of q[i0 - k] * taps[p][k]        in int64; q is 0 outside [0, n)
+ *     y = clamp((acc + 2^37 - 1 + ((acc >> 38) & 1)) >> 38, -32768, 32767)      round half even (38 = 30 + 23 - 15)
+ *   taps  DEVICE int32 [L][K] in Q30 (n_taps = L K), every row summing to 2^30 and to at most 3 * 2^30 in magnitude (then acc
+ *         cannot overflow); L / M is the rate ratio in lowest terms.  L = M = K = 1, centre = 0, taps = {2^30} only converts
+ *         the sample format.
+ *   recs  DEVICE int64 [R][ADYOLO_RESAMPLE_WORDS] = {src offset, src frames, dst offset, dst frames} in frames of 4 channels:
+ *         one launch converts R recordings of one rate and kind.  A row that reaches outside src [src_frames][4] or dst
+ *         [dst_frames][4], or whose dst frames are not n_out of its src frames, writes nothing and sets ADYOLO_CORPUS_BAD_ITEM.
+ *         Only dst[dst offset .. + dst frames) of a good row is written.
+ * src and dst 16-byte aligned; R < 65536; L, M, K < 65536.  A tile of ADYOLO_RESAMPLE_TILE output frames keeps its input span
+ * (ceil((tile - 1) M / L) + K frames of 16 bytes) and its min(L, tile) phase rows in LDS: a plan that needs more than 160 KiB
+ * there is ADYOLO_ENOSUP (every plan of resample.plan with M / L <= 15 fits; 192 kHz to 24 kHz is 8).  No allocation, no synchronisation, capturable.
+ * ---------------------------------------------------------------------------------------------- */
+#define ADYOLO_RESAMPLE_WORDS 4
+#define ADYOLO_RESAMPLE_TILE 256
+#define ADYOLO_RESAMPLE_INT16   0
+#define ADYOLO_RESAMPLE_INT32   1
+#define ADYOLO_RESAMPLE_FLOAT32 2
+#define ADYOLO_CORPUS_NONFINITE 8   /* an Inf or NaN sample in a float32 recording (converted as 0) */
+int  adyolo_resample_pcm(const void *src, int kind, long src_frames, const int64_t *recs, int R, const int32_t *taps,
+                         long n_taps, int L, int M, int K, long centre, int16_t *dst, long dst_frames, int *status, void *stream);
+
 /* K11 Adam, AdamW, SGD and gradient-norm clipping over one flat parameter buffer (csrc/optim.hip; the reference picks its
  * optimizer by name, src/train.py:29-37, and clips with clip_grad_norm_, src/train.py:54; no amsgrad).  The step counter is ON
  * THE DEVICE (one uint64): every call bumps step_dev itself and no argument changes from step to step, so the whole train step

@@ -18,8 +18,14 @@ a direction more than 1 degree off).  Both shares are split into the frames next
 and the first the next one keeps) and all other frames.  The weights are random filler: the figures say how far the context a
 window lacks moves THIS network's output, and little about a trained model.
 
+Sample-rate conversion.  With --rate HZ the folder is written at that rate and loaded with ``load_infer_split(resample=True)``:
+the one ``adyolo_resample_pcm`` launch over all recordings (median of 20 by device events, GB/s over the bytes read and written)
+beside the host-to-device copy of the same native bytes in the same session, the load with the conversion in it, and the
+windowed pass over the converted folder.  --rate 24000 is the same run without a conversion.
+
   python tools/infer_bench.py [--dir DIR] [--recordings 14] [--clips 4] [--batch 8] [--window 20] [--margin 2]
                               [--loss adyolo|seddoa|accdoa|adpit] [--conf 0.5] [--repeats 3] [--json out.json] [--keep]
+                              [--rate HZ]
 """
 import argparse
 import json
@@ -44,14 +50,90 @@ SR = 24000
 LENGTHS_S = (20.0, 31.7, 44.3, 60.0, 72.5, 85.1, 97.0, 110.4, 123.9, 137.2, 150.0, 163.6, 180.0, 41.1, 60.0, 97.0)
 
 
-def write_folder(root, lengths_s, seed=0):
+def write_folder(root, lengths_s, seed=0, rate=SR):
     from scipy.io import wavfile
     rs = np.random.RandomState(seed)
     os.makedirs(root, exist_ok=True)
     for r, s in enumerate(lengths_s):
-        audio = np.clip(rs.normal(0, 3000, size=(int(round(SR * s)), 4)), -32768, 32767).astype(np.int16)
-        wavfile.write(os.path.join(root, "rec%03d.wav" % r), SR, audio)
-    return sum(int(round(SR * s)) for s in lengths_s)
+        audio = np.clip(rs.normal(0, 3000, size=(int(round(rate * s)), 4)), -32768, 32767).astype(np.int16)
+        wavfile.write(os.path.join(root, "rec%03d.wav" % r), rate, audio)
+    return sum(int(round(rate * s)) for s in lengths_s)
+
+
+def event_ms(run, repeats):
+    """Median and range of ``run`` between two device events, after one untimed call."""
+    run()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(repeats):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        run()
+        e1.record()
+        e1.synchronize()
+        out.append(e0.elapsed_time(e1))
+    return {"median_ms": round(statistics.median(out), 4), "min_ms": round(min(out), 4), "max_ms": round(max(out), 4), "n": len(out)}
+
+
+def rate_run(a, res, folder, out, lengths):
+    """--rate: the folder written at ``a.rate`` Hz, loaded with ``resample=True``.  The conversion launch (all recordings, one
+    launch) and the host-to-device copy of the same native bytes (pageable, as the corpus uploads them, and page-locked) by
+    device events in one session; the windowed pass over the converted folder as in the plain run."""
+    import adyolo_amd  # noqa: F401
+    from adyolo_amd import ops, resample, test as atest
+    from adyolo_amd.corpus import InferDeviceCorpus, load_infer_split
+    from adyolo_amd.features import FeatureExtractor
+    from adyolo_amd.graph import ForwardGraphs
+    from adyolo_amd.postprocess import LabelPostProcessor
+    from adyolo_amd.wrapper import WrapperModel
+    samples = write_folder(folder, lengths, rate=a.rate)
+    seconds = samples / a.rate
+    res["folder"] = {"recordings": len(lengths), "rate": a.rate, "seconds": round(seconds, 1), "native_bytes": samples * 8}
+    prm = params(folder, a.loss, a.classes, a.window, a.conf)
+    torch.manual_seed(0)
+    model = WrapperModel((1, 7, int(SR * a.window) // 600, 64), (), prm).to("cuda:0").eval()
+    fx, post = FeatureExtractor(None, "cuda:0"), LabelPostProcessor(prm)
+    t0 = time.perf_counter()
+    hs = load_infer_split(prm, rank=0, world=1, verify="sample", resample=True)
+    t1 = time.perf_counter()
+    corpus = InferDeviceCorpus(hs, prm, "cuda:0", window_s=a.window, margin_s=a.margin, batch_size=a.batch)
+    torch.cuda.synchronize()
+    t2 = time.perf_counter()
+    res["load"] = {"host_s": round(t1 - t0, 3), "upload_and_convert_s": round(t2 - t1, 3), "device_bytes": corpus.nbytes(),
+                   "ms_per_recorded_s": round(1e3 * (t2 - t0) / seconds, 4)}
+    if a.rate != SR:
+        pl = resample.plan(a.rate, SR)
+        stream = np.concatenate(hs.native, 0)
+        pos = np.concatenate([[0], np.cumsum(hs.native_lengths)])
+        rows = torch.tensor([(int(pos[i]), int(hs.native_lengths[i]), int(hs.rec_start[i]), int(hs.lengths[i]))
+                             for i in range(len(hs.native))], dtype=torch.int64, device="cuda:0")
+        src, taps = torch.from_numpy(stream).to("cuda:0"), torch.from_numpy(pl["taps"]).to("cuda:0")
+        dst, status = torch.zeros_like(corpus.pcm), torch.zeros(1, dtype=torch.int32, device="cuda:0")
+        conv = event_ms(lambda: ops.resample_pcm(src, rows, taps, pl["M"], pl["centre"], dst, status), 20)
+        assert int(status.item()) == 0 and torch.equal(dst, corpus.pcm), "the timed launch is not the corpus's conversion"
+        moved = stream.nbytes + int(hs.lengths.sum()) * 8
+        macs = int(hs.lengths.sum()) * 4 * pl["K"]
+        res["convert"] = dict(conv, L=pl["L"], M=pl["M"], K=pl["K"], bytes_in=stream.nbytes, bytes_out=int(hs.lengths.sum()) * 8,
+                              gb_per_s=round(moved / conv["median_ms"] / 1e6, 1), gmac_per_s=round(macs / conv["median_ms"] / 1e6, 1),
+                              ms_per_recorded_s=round(conv["median_ms"] / seconds, 6))
+        del src
+        hold = torch.empty(stream.shape, dtype=torch.int16, device="cuda:0")
+        host = torch.from_numpy(stream)
+        res["h2d_pageable"] = dict(event_ms(lambda: hold.copy_(host), 5), bytes=stream.nbytes)
+        pinned = host.pin_memory()
+        res["h2d_pinned"] = dict(event_ms(lambda: hold.copy_(pinned, non_blocking=True), 5), bytes=stream.nbytes)
+        for key in ("h2d_pageable", "h2d_pinned"):
+            res[key]["gb_per_s"] = round(stream.nbytes / res[key]["median_ms"] / 1e6, 1)
+        res["convert_over_h2d_pinned"] = round(conv["median_ms"] / res["h2d_pinned"]["median_ms"], 3)
+        del hold, host, pinned, stream, dst
+    print(json.dumps({k: res[k] for k in ("folder", "load", "convert", "h2d_pageable", "h2d_pinned") if k in res}), flush=True)
+    fg = ForwardGraphs(model, fx, post, warm_calls=0)
+    info = {}
+    walls = timed(lambda: info.update(atest.infer_epoch_corpus(corpus, model, fx, post, out, forward=fg)), a.repeats)
+    med = statistics.median(walls)
+    res["windowed"] = {"wall_s": [round(w, 4) for w in walls], "median_s": round(med, 4),
+                       "ms_per_recorded_s": round(1e3 * med / seconds, 4), **info}
+    print(json.dumps(res), flush=True)
 
 
 def params(folder, loss, n_classes, window_s, conf=0.5):
@@ -123,6 +205,8 @@ def main():
     ap.add_argument("--classes", type=int, default=12)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--conf", type=float, default=0.5, help="conf_thresh and clss_thresh (random weights: lower it until rows appear)")
+    ap.add_argument("--rate", type=int, default=0, help="write the folder at this rate (Hz) and load it with resample=True: the "
+                    "conversion launch against the upload of the same bytes, then the windowed pass (no whole pass, no agreement)")
     ap.add_argument("--keep", action="store_true", help="keep the folders on disk afterwards")
     ap.add_argument("--json")
     a = ap.parse_args()
@@ -142,6 +226,13 @@ def main():
     res = {"batch": a.batch, "window_s": a.window, "margin_s": a.margin, "loss": a.loss, "conf_thresh": a.conf, "repeats": a.repeats,
            "max_graphs": graph.MAX_GRAPHS, "cpus": len(os.sched_getaffinity(0))}
     try:
+        if a.rate:
+            rate_run(a, res, folder, out, lengths)
+            if a.json:
+                os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+                with open(a.json, "w") as f:
+                    json.dump(res, f, indent=1)
+            return
         samples = write_folder(folder, lengths)
         seconds = samples / SR
         res["folder"] = {"recordings": len(lengths), "distinct_lengths": len(set(lengths)), "seconds": round(seconds, 1)}

@@ -37,6 +37,10 @@ recorded graph, keeps each window's frames that have context on both sides and s
 With ``load_infer_split(..., resample=True)`` (``infer_split_from_arrays(..., rates=...)``) the recordings may be at any standard
 rate and in int16, 24-bit or float32: those that are not int16 at ``data_config.sr`` stay in their native form on the host, and
 the upload converts them on the device (``ops.resample_pcm``, resample.py) into the places the layout left for them.
+
+One structure under all of it: every loader returns a ``HostCorpus``, whose constructor owns the stream layout (16-frame
+alignment) and gives every field a value, with ``kind`` saying which split it is; the loaders share one WAV reader, one CSV
+reader and one verify pick (``_read_wav``, ``_csv_rows``, ``_verify_picks``); the four device corpora share ``_CorpusBase``.
 """
 import copy
 import os
@@ -69,34 +73,116 @@ def _parse_chunk(name):
     return name[:i], int(name[i + 6:])
 
 
-def _csv_rows(path):
-    """A chunk CSV as ``FoaDataset`` sees it: ``load_csv2dict`` iterated -> [(frame, cls, src, az, el)] (polar rows only)."""
+def _csv_rows(who, path, nb_classes=None):
+    """A label CSV as ``FoaDataset`` sees it: ``load_csv2dict`` iterated -> [(frame, cls, src, az, el)] (polar rows only).
+    nb_classes: also refuse a class outside [0, nb_classes).  who: the loader's name, for the messages."""
     if not os.path.exists(path):
-        raise ValueError("load_chunked_split: label file %s is missing" % path)
+        raise ValueError("%s: label file %s is missing" % (who, path))
     rows = []
     for frame, events in FoaDataset.load_csv2dict(path).items():
         for ev in events:
             if len(ev) != 4:
-                raise ValueError("load_chunked_split: %s has a row that is not [frame, class, source, azimuth, elevation]" % path)
+                raise ValueError("%s: %s has a row that is not [frame, class, source, azimuth, elevation]" % (who, path))
+            if nb_classes is not None and not 0 <= ev[0] < nb_classes:
+                raise ValueError("%s: %s has an event of class %d, outside [0, %d) (nb_classes)" % (who, path, ev[0], nb_classes))
             rows.append((frame, ev[0], ev[1], ev[2], ev[3]))
     return rows
 
 
-class HostCorpus:
-    """What ``load_chunked_split`` returns (NumPy, host memory).
+def _read_wav(who, path, window=None, native=False):
+    """One WAV file, memory-mapped -> (rate, data).  The file must hold int16 (n, 4) -- (window, 4) exactly with ``window`` --
+    or, with ``native``, any sample format of ``resample.KINDS``; ``ValueError`` naming ``who`` (the loader) and the path
+    otherwise.  Only ``native`` reads a 24-bit file, which scipy cannot map, into memory."""
+    from scipy.io import wavfile
+    try:
+        rate, data = wavfile.read(path, mmap=True)
+    except ValueError as e:
+        if not native or "mmap" not in str(e):                   # only scipy's "mmap=True not compatible with 24-bit" is retried
+            raise
+        rate, data = wavfile.read(path, mmap=False)
+    if native:
+        from .resample import KINDS
+        known = data.dtype in KINDS
+    else:
+        known = data.dtype == np.int16
+    if not known or data.ndim != 2 or data.shape != (data.shape[0] if window is None else window, 4):
+        raise ValueError("%s: %s holds %s %s, expected %s (%s, 4)"
+                         % (who, path, data.dtype, tuple(data.shape), "int16, 24-bit or float32" if native else "int16",
+                            "n" if window is None else "%d" % window))
+    return int(rate), data
 
-    audio      int16 (S, 4): the recordings' streams, each starting on a 16-frame boundary
-    rec_names  recording names; rec_start int64 (R + 1,): first frame of each stream in ``audio`` (end of the last at R)
+
+def _verify_picks(who, verify, n):
+    """The indices of ``range(n)`` a loader reads a second time: all of them for "all", the first, middle (n // 2) and last for
+    "sample", none for "none"; ``ValueError`` for any other value."""
+    if verify not in ("sample", "all", "none"):
+        raise ValueError("%s: verify must be 'sample', 'all' or 'none' (got %r)" % (who, verify))
+    if verify == "all":
+        return range(n)
+    return sorted({0, n // 2, n - 1}) if verify == "sample" and n else ()
+
+
+class HostCorpus:
+    """A split in host memory (NumPy): what ``load_chunked_split`` (kind ``CHUNKED``), ``load_eval_split`` (``EVAL``) and
+    ``load_infer_split`` / ``infer_split_from_arrays`` (``INFER``) return.  The constructor lays the recordings out and gives
+    every field its empty value; the loader fills in the audio and, if the split has labels, the events.
+
+    kind       CHUNKED | EVAL | INFER: what the device corpora ask instead of probing for fields
+    rec_names  recording names; lengths int64 (R,): samples per recording (CHUNKED: of the rebuilt stream; a recording that is
+               converted on the device: after conversion)
+    rec_start  int64 (R + 1,): first frame of each stream in ``audio`` (end of the last at R), each a multiple of 16
+    audio      int16 (max(S, 16), 4): the streams, zero between the end of one and the start of the next
     events     float64 (E, 5) [frame on the recording's axis, class, source, azimuth, elevation], recording after recording,
-               frames ascending, file order within a frame; ev_start int64 (R + 1,)
-    chunks     name -> (recording, sample offset into ``audio``, frame offset on the recording's axis)
-    chunk_events  name -> (first event, number of events) of its label window
-    total_filelist  the chunk names in ``os.listdir`` order, exactly as ``FoaDataset`` builds it
-    window, stride (samples), hop_label (samples per label frame), window_frames, max_events (largest event count of a window)
+               frames ascending, file order within a frame; ev_start int64 (R + 1,).  INFER: (0, 5) and zeros
+    max_events the largest event count of a window (CHUNKED) or of a recording (EVAL); INFER: 0
+    chunks     name -> (recording, sample offset into ``audio``, frame offset on the recording's axis); chunk_events  name ->
+               (first event, number of events) of its label window.  CHUNKED only, {} otherwise
+    total_filelist, filelist  CHUNKED: the chunk names in ``os.listdir`` order, exactly as ``FoaDataset`` builds them (the
+               device corpus draws its own ``filelist`` from them); otherwise this rank's recordings: == rec_names
+    rank, world  the shard that was loaded (CHUNKED: 0, 1 -- the device corpus shards the draw)
+    window, stride (samples; EVAL / INFER: the longest whole-hop length, a multiple of 600 samples, and 0), hop_label (samples
+               per label frame), window_frames; wav_pth, csv_pth, set_type as ``FoaDataset`` has them (None without a folder)
+    native, rates, kinds, native_lengths  None, except in an INFER split made with ``rates=`` / ``resample=True``: per
+               recording the samples kept in their own rate and format (None where ``audio`` already holds them), the rate
+               in Hz, the sample format (0 int16, 1 int32, 2 float32) and the length before conversion
     """
 
+    CHUNKED, EVAL, INFER = "chunked", "eval", "infer"
+
+    def __init__(self, kind, rec_names, lengths, hop_label, set_type, wav_pth=None, csv_pth=None, rank=0, world=1, window=None,
+                 stride=0):
+        self.kind, self.set_type, self.wav_pth, self.csv_pth = kind, set_type, wav_pth, csv_pth
+        self.rank, self.world = rank, world
+        self.rec_names = list(rec_names)
+        self.filelist = self.total_filelist = list(rec_names)
+        self.lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
+        self.rec_start = np.zeros(len(self.rec_names) + 1, dtype=np.int64)
+        pos = 0
+        for i, n in enumerate(self.lengths.tolist()):
+            self.rec_start[i] = pos
+            pos += (n + 15) // 16 * 16               # a contract with the gather kernels: their 16-byte loads are aligned
+        self.rec_start[-1] = pos
+        self.audio = np.zeros((max(pos, 16), 4), dtype=np.int16)
+        self.set_events([np.zeros((0, _EV_COLS))] * len(self.rec_names))
+        self.max_events = 0
+        self.chunks, self.chunk_events = {}, {}
+        if window is None:                                       # whole recordings: the longest whole-hop length
+            window = int((self.lengths // 600).max() * 600) if len(self.rec_names) else 0
+        self.window, self.stride, self.hop_label, self.window_frames = window, stride, hop_label, window // hop_label
+        self.native = self.rates = self.kinds = self.native_lengths = None
+
+    def set_events(self, per_recording):
+        """The event table from one float64 (n, 5) array per recording."""
+        self.events = np.concatenate(per_recording, 0) if per_recording else np.zeros((0, _EV_COLS))
+        self.ev_start = np.concatenate([[0], np.cumsum([len(e) for e in per_recording])]).astype(np.int64)
+
+    def stream(self, i):
+        """Recording ``i``'s samples: a view of ``audio``, without the alignment tail."""
+        s0 = int(self.rec_start[i])
+        return self.audio[s0:s0 + int(self.lengths[i])]
+
     def nbytes(self):
-        native = sum(a.nbytes for a in getattr(self, "native", None) or () if a is not None)     # a resample=True split
+        native = sum(a.nbytes for a in self.native or () if a is not None)
         return int(self.audio.nbytes + self.events.nbytes + native)
 
 
@@ -105,9 +191,8 @@ def load_chunked_split(params, set_type="train", verify="sample"):
     middle and last chunk of every recording in full and compares them with their rebuilt windows, "all" every chunk, "none"
     nothing; every header is checked (int16, 4 channels, ``window`` samples) and every CSV is compared with the event table.
     Anything else raises ``ValueError`` naming the file."""
-    from scipy.io import wavfile
-    if verify not in ("sample", "all", "none"):
-        raise ValueError("load_chunked_split: verify must be 'sample', 'all' or 'none' (got %r)" % (verify,))
+    who = "load_chunked_split"
+    _verify_picks(who, verify, 0)                                # a bad value is refused before anything is read
     dc = params["data_config"]
     wav_pth, csv_pth = _split_dirs(params, set_type)
     sr = int(dc.get("sr", 24000))
@@ -128,49 +213,31 @@ def load_chunked_split(params, set_type="train", verify="sample"):
         if ks != list(range(1, len(ks) + 1)):
             raise ValueError("load_chunked_split: recording %s has chunks %s (expected 1..%d without gaps)" % (rec, ks, len(ks)))
 
-    def wav_of(name):
-        path = os.path.join(wav_pth, name + ".wav")
-        _, data = wavfile.read(path, mmap=True)
-        if data.dtype != np.int16 or data.ndim != 2 or data.shape != (window, 4):
-            raise ValueError("load_chunked_split: %s holds %s %s, expected int16 (%d, 4)"
-                             % (path, data.dtype, tuple(data.shape), window))
-        return path, data
-
-    # stream layout: each recording starts on a 16-frame boundary (aligned 16-byte loads in the gather)
-    lengths = [window + (len(groups[r]) - 1) * stride for r in rec_names]
-    rec_start = np.zeros(len(rec_names) + 1, dtype=np.int64)
-    pos = 0
-    for i, n in enumerate(lengths):
-        rec_start[i] = pos
-        pos += (n + 15) // 16 * 16
-    rec_start[-1] = pos
-    audio = np.zeros((max(pos, 16), 4), dtype=np.int16)
-    ev_parts, ev_start = [], [0]
-    chunks, chunk_events = {}, {}
-    max_events = 0
+    hc = HostCorpus(HostCorpus.CHUNKED, rec_names, [window + (len(groups[r]) - 1) * stride for r in rec_names], hop, set_type,
+                    wav_pth, csv_pth, window=window, stride=stride)
+    hc.filelist = hc.total_filelist = total_filelist
+    ev_parts, ev_base = [], 0
     for r, rec in enumerate(rec_names):
         names = groups[rec]
         nk = len(names)
-        s0 = int(rec_start[r])
+        paths = {k: os.path.join(wav_pth, names[k] + ".wav") for k in names}
+        s0, stream = int(hc.rec_start[r]), hc.stream(r)
         # audio: chunk 1 whole, the last `stride` samples of every later chunk
         for k in range(1, nk + 1):
-            path, data = wav_of(names[k])
+            data = _read_wav(who, paths[k], window)[1]
             if k == 1:
-                audio[s0:s0 + window] = data
+                stream[:window] = data
             else:
-                lo = s0 + window + (k - 2) * stride
-                audio[lo:lo + stride] = data[window - stride:]
+                lo = window + (k - 2) * stride
+                stream[lo:lo + stride] = data[window - stride:]
             del data
-        checks = range(1, nk + 1) if verify == "all" else (sorted({1, (nk + 1) // 2, nk}) if verify == "sample" else ())
-        for k in checks:
-            path, data = wav_of(names[k])
-            lo = s0 + (k - 1) * stride
-            if not np.array_equal(np.asarray(data), audio[lo:lo + window]):
+        for k in sorted(nk - i for i in _verify_picks(who, verify, nk)):        # chunks 1, (nk + 1) // 2 and nk of "sample"
+            lo = (k - 1) * stride
+            if not np.array_equal(np.asarray(_read_wav(who, paths[k], window)[1]), stream[lo:lo + window]):
                 raise ValueError("load_chunked_split: %s differs from the window rebuilt from its neighbours (overlapping chunks "
-                                 "of %s disagree)" % (path, rec))
-            del data
+                                 "of %s disagree)" % (paths[k], rec))
         # labels: chunk 1's rows, then the last stride_frames frames of every later chunk, on the recording's frame axis
-        csv = {k: _csv_rows(os.path.join(csv_pth, names[k] + ".csv")) for k in range(1, nk + 1)}
+        csv = {k: _csv_rows(who, os.path.join(csv_pth, names[k] + ".csv")) for k in range(1, nk + 1)}
         rows = []
         for k in range(1, nk + 1):
             f_off = (k - 1) * stride_frames
@@ -188,22 +255,12 @@ def load_chunked_split(params, set_type="train", verify="sample"):
                 raise ValueError("load_chunked_split: %s disagrees with the event table of %s rebuilt from its chunks (rows "
                                  "outside [0, %d) frames, out of frame order, or overlaps that differ)"
                                  % (os.path.join(csv_pth, names[k] + ".csv"), rec, window_frames))
-            chunks[names[k]] = (r, s0 + (k - 1) * stride, f_off)
-            chunk_events[names[k]] = (ev_start[-1] + int(lo), int(hi - lo))
-            max_events = max(max_events, int(hi - lo))
+            hc.chunks[names[k]] = (r, s0 + (k - 1) * stride, f_off)
+            hc.chunk_events[names[k]] = (ev_base + int(lo), int(hi - lo))
+            hc.max_events = max(hc.max_events, int(hi - lo))
         ev_parts.append(ev)
-        ev_start.append(ev_start[-1] + ev.shape[0])
-
-    hc = HostCorpus()
-    hc.wav_pth, hc.csv_pth, hc.set_type = wav_pth, csv_pth, set_type
-    hc.audio = audio
-    hc.rec_names, hc.rec_start = rec_names, rec_start
-    hc.events = np.concatenate(ev_parts, 0) if ev_parts else np.zeros((0, _EV_COLS))
-    hc.ev_start = np.asarray(ev_start, dtype=np.int64)
-    hc.chunks, hc.chunk_events = chunks, chunk_events
-    hc.total_filelist = total_filelist
-    hc.window, hc.stride, hc.hop_label = window, stride, hop
-    hc.window_frames, hc.max_events = window_frames, max_events
+        ev_base += ev.shape[0]
+    hc.set_events(ev_parts)
     return hc
 
 
@@ -282,8 +339,11 @@ def xyz_unrotated(az, el):
 
 
 class _CorpusBase:
-    """What both device corpora share: the split in HBM, ``FoaDataset``'s sampling surface, the host draws of a batch, the upload
-    of its item table and the audio gather.  Subclasses add the label encoding."""
+    """What the four device corpora share.  All of them: the adopted ``HostCorpus`` in HBM with the identity fields and methods
+    of ``FoaDataset`` that the epoch loops read (``_adopt``), the status word and ``check``, and the small helpers of a
+    ``launch`` (``_out``, ``_round_cap``, ``_yolo_tables``).  The two training corpora only (``DeviceCorpus``,
+    ``ClasswiseDeviceCorpus``): the augmentation configuration and ``FoaDataset``'s sampling of files (``_train_setup``), the host
+    draws of a batch, the upload of its item table and the audio gather (``draw`` .. ``_gather``).  Subclasses add the labels."""
 
     # the same functions as the host dataset: checkpoints (remaining_file) and the rank shards interchange with it
     sample_filelist_for_train_iter = FoaDataset.sample_filelist_for_train_iter
@@ -291,17 +351,26 @@ class _CorpusBase:
     get_remaining_file = FoaDataset.get_remaining_file
     get_filelist = FoaDataset.get_filelist
     __len__ = FoaDataset.__len__
+    _copy, _random = copy, random                # the modules ``sample_filelist_for_train_iter`` and ``draw`` draw through
 
-    def _setup(self, host_corpus, params, device, rank, world):
+    def _adopt(self, hc, device, rank, world, is_valid, is_infer=False):
+        """Every corpus: the host split, the device, what ``FoaDataset`` would answer for this split, the split in HBM."""
+        self.host = hc
+        self.device = torch.device(device)
+        self.rank, self.world = rank, world
+        self.is_valid, self.is_infer, self.set_type = is_valid, is_infer, "infer" if is_infer else hc.set_type
+        self.wav_pth, self.csv_pth = hc.wav_pth, None if is_infer else hc.csv_pth
+        self.hop_label = hc.hop_label
+        self.rotate = False
+        self.filelist = list(hc.filelist)
+        self.max_events = int(hc.max_events)
+        self._to_hbm(hc)
+
+    def _train_setup(self, params):
+        """The training corpora: the augmentations, the batch shape and the first draw of files (``FoaDataset.__init__``)."""
         from .augmentations import (MIC_SWAP_COMBS, SpecAug, channel_swap_enabled, feature_aug_config, mic_swap_source,
                                     time_mix_config)
-        self.host = hc = host_corpus
-        self.device = torch.device(device)
-        self._copy, self._os, self._random = copy, os, random
-        self.rank, self.world = _rank_world(rank, world)
-        self.is_valid, self.is_infer, self.set_type = False, False, hc.set_type
-        self.wav_pth, self.csv_pth = hc.wav_pth, hc.csv_pth
-        self.hop_label = hc.hop_label
+        hc = self.host
         self.rotate = bool(params.get("aug_config", {}).get("rotation_augment", False))
         # MIC channel swap (ValueError: audio_format is not 'mic', or rotation_augment is on as well): the gather's table
         self.swap = channel_swap_enabled(params)
@@ -311,8 +380,32 @@ class _CorpusBase:
         self.feat_aug = feature_aug_config(params)        # frequency shift / cutout: None or the parsed keys (ValueError: a bad key)
         self.batch_size = int(params["train_config"]["batch_size"])
         self.n_samples, self.n_label_frames = hc.window, hc.window // hc.hop_label
-        self.max_events = hc.max_events
-        self._to_hbm(hc)
+        self.total_filelist = list(hc.total_filelist)
+        self.remaining_file = copy.deepcopy(self.total_filelist)
+        self.nb_samples = self.batch_size * params["train_config"]["nb_iters"] * self.world
+        self.sample_filelist_for_train_iter()
+
+    def _yolo_tables(self, params):
+        """The AD-YOLO label tables: the host encoder, the largest cell count of an event, the cell bounds in HBM, the grid."""
+        self.encoder = enc = YoloLabelEncoder(params)
+        self.cells = max_cells_per_event(enc)
+        self.bounds = torch.from_numpy(np.concatenate([enc.az_lb, enc.az_ub, enc.el_lb, enc.el_ub]).astype(np.float64)).to(self.device)
+        self.grid = (len(enc.az_lb), len(enc.el_lb))
+
+    @staticmethod
+    def _round_cap(rows):
+        """At least one target row, rounded up to ``graph.TARGET_QUANTUM``: one input shape per recorded graph."""
+        from . import graph
+        q = graph.TARGET_QUANTUM
+        return (max(1, int(rows)) + q - 1) // q * q
+
+    def _out(self, given, shape, what="audio_out"):
+        """An output of ``launch``: the caller's buffer, which must have this shape, or a new float32 tensor."""
+        if given is None:
+            return torch.empty(shape, dtype=torch.float32, device=self.device)
+        if tuple(given.shape) != tuple(shape):
+            raise ValueError("%s.launch: %s %s, expected %s" % (type(self).__name__, what, tuple(given.shape), tuple(shape)))
+        return given
 
     def _to_hbm(self, hc):
         """The split in HBM: the int16 streams, the event table {frame, class, azimuth, elevation} in float64, the status word."""
@@ -324,14 +417,6 @@ class _CorpusBase:
         self.rot = ops.corpus_rot_table(COMBINATIONS)
         self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._pinned, self._copied, self._slot = {}, [None, None], 0
-
-    def _start_sampling(self, params):
-        """FoaDataset.__init__ for a training split: the first draw of files."""
-        self.total_filelist = list(self.host.total_filelist)
-        self.remaining_file = copy.deepcopy(self.total_filelist)
-        self.nb_samples = self.batch_size * params["train_config"]["nb_iters"] * self.world
-        self.filelist = []
-        self.sample_filelist_for_train_iter()
 
     def nbytes(self):
         return int(self.pcm.numel() * 2 + self.events.numel() * 8)
@@ -428,13 +513,8 @@ class _CorpusBase:
         ``target_shape``, or new ones) -> (items, mates or None, spec or None, audio, target), all on the device."""
         dev_items, dev_spec, dev_mates = self._upload(drawn)
         b = dev_items.shape[0]
-        shape = tuple(self.target_shape(b))
-        audio = audio_out if audio_out is not None else \
-            torch.empty((b, self.n_samples, 4), dtype=torch.float32, device=self.device)
-        target = target_out if target_out is not None else torch.empty(shape, dtype=torch.float32, device=self.device)
-        if tuple(audio.shape) != (b, self.n_samples, 4) or tuple(target.shape) != shape:
-            raise ValueError("%s.launch: output buffers %s / %s, expected (%d, %d, 4) / %s"
-                             % (type(self).__name__, tuple(audio.shape), tuple(target.shape), b, self.n_samples, shape))
+        audio = self._out(audio_out, (b, self.n_samples, 4))
+        target = self._out(target_out, self.target_shape(b), "target_out")
         return dev_items, dev_mates, dev_spec, audio, target
 
     def _gather(self, dev_items, audio, dev_mates=None):
@@ -470,24 +550,18 @@ class DeviceCorpus(_CorpusBase):
     ``ClasswiseDeviceCorpus``."""
 
     def __init__(self, host_corpus, params, device="cuda:0", rank=None, world=None, cap=None):
-        from . import graph
         self.loss_nm = params["args"]["loss"]
         if self.loss_nm != "adyolo":
             raise NotImplementedError("DeviceCorpus: loss %s -- AD-YOLO labels only; the class-wise losses train from "
                                       "ClasswiseDeviceCorpus" % self.loss_nm)
-        self._setup(host_corpus, params, device, rank, world)
-        self.encoder = YoloLabelEncoder(params)
-        self.cells = max_cells_per_event(self.encoder)
+        self._adopt(host_corpus, device, *_rank_world(rank, world), is_valid=False)
+        self._yolo_tables(params)
+        self._train_setup(params)
         if cap is None:
             # a mixed item holds the events of two windows
-            need = max(1, self.batch_size * (2 if self.mix is not None else 1) * self.max_events * self.cells)
-            cap = (need + graph.TARGET_QUANTUM - 1) // graph.TARGET_QUANTUM * graph.TARGET_QUANTUM
+            cap = self._round_cap(self.batch_size * (2 if self.mix is not None else 1) * self.max_events * self.cells)
         self.cap = int(cap)
-        enc = self.encoder
-        self.bounds = torch.from_numpy(np.concatenate([enc.az_lb, enc.az_ub, enc.el_lb, enc.el_ub]).astype(np.float64)).to(self.device)
-        self.grid = (len(enc.az_lb), len(enc.el_lb))
         self.rows = None                 # int32 word on the device: the row count of the last batch
-        self._start_sampling(params)
 
     def target_shape(self, batch):
         """The target of every batch: (cap, 7) rows, whatever the batch size."""
@@ -535,11 +609,11 @@ class ClasswiseDeviceCorpus(_CorpusBase):
             r = int(np.searchsorted(hc.ev_start, bad[0], "right")) - 1
             raise ValueError("ClasswiseDeviceCorpus: recording %s has an event of class %g, outside [0, %d) (nb_classes)"
                              % (hc.rec_names[r], cls[bad[0]], c))
-        self._setup(host_corpus, params, device, rank, world)
+        self._adopt(hc, device, *_rank_world(rank, world), is_valid=False)
         xyz = xyz_table(hc.events[:, 3], hc.events[:, 4]) if hc.events.shape[0] else \
             np.zeros((1, ops.CORPUS_XYZ_SLOTS, 3), dtype=np.float32)
         self.xyz = torch.from_numpy(xyz).to(self.device)
-        self._start_sampling(params)
+        self._train_setup(params)
 
     def nbytes(self):
         return super().nbytes() + int(self.xyz.numel() * 4)
@@ -577,12 +651,10 @@ def _eval_dirs(params, set_type):
 
 def load_eval_split(params, set_type, rank=None, world=None, verify="sample"):
     """A labelled evaluation split ('val', 'valid', 'test': what ``FoaDataset(params, set_type, is_valid=True)`` accepts) read
-    once -> ``HostCorpus``: every recording whole in one int16 stream (each on a 16-frame boundary) and one event table.
+    once -> ``HostCorpus`` of kind ``EVAL``: every recording whole in its stream and one event table.
 
     filelist    exactly ``FoaDataset``'s: ``os.listdir`` order on one rank, ``sorted(...)[rank::world]`` under data parallelism;
                 only this rank's recordings are loaded.  rec_names == filelist: recording i is clip i.
-    lengths     int64 (R,): samples per recording; rec_start / ev_start as in ``HostCorpus``; max_events: the largest event
-                count of a recording; window: the longest whole-hop length (multiple of 600 samples).
     events      every CSV row, rows past ``len // hop_label`` label frames included (the label kernels drop them, as
                 ``FoaDataset.__getitem__`` does), frames ascending, file order within a frame.
 
@@ -590,9 +662,8 @@ def load_eval_split(params, set_type, rank=None, world=None, verify="sample"):
     [frame, class, source, azimuth, elevation], a class outside [0, nb_classes), frames that do not ascend (the host's rows
     follow the file, the table the frames).  verify: "sample" reads the first, middle and last recording again and compares
     them with the stream, "all" every recording, "none" nothing."""
-    from scipy.io import wavfile
-    if verify not in ("sample", "all", "none"):
-        raise ValueError("load_eval_split: verify must be 'sample', 'all' or 'none' (got %r)" % (verify,))
+    who = "load_eval_split"
+    _verify_picks(who, verify, 0)                                # a bad value is refused before anything is read
     dc = params["data_config"]
     wav_pth, csv_pth = _eval_dirs(params, set_type)
     if not os.path.isdir(wav_pth):
@@ -603,65 +674,23 @@ def load_eval_split(params, set_type, rank=None, world=None, verify="sample"):
     filelist = [i.replace(".wav", "") for i in os.listdir(wav_pth)]                  # FoaDataset.filelist
     if world > 1:
         filelist = sorted(filelist)[rank::world]
-
-    def wav_of(name):
-        path = os.path.join(wav_pth, name + ".wav")
-        _, data = wavfile.read(path, mmap=True)
-        if data.dtype != np.int16 or data.ndim != 2 or data.shape[1] != 4:
-            raise ValueError("load_eval_split: %s holds %s %s, expected int16 (n, 4)" % (path, data.dtype, tuple(data.shape)))
-        return path, data
-
-    lengths = np.zeros(len(filelist), dtype=np.int64)
-    for i, name in enumerate(filelist):                       # headers first: the stream is allocated once
-        lengths[i] = wav_of(name)[1].shape[0]
-    rec_start = np.zeros(len(filelist) + 1, dtype=np.int64)
-    pos = 0
-    for i, n in enumerate(lengths.tolist()):
-        rec_start[i] = pos
-        pos += (n + 15) // 16 * 16
-    rec_start[-1] = pos
-    audio = np.zeros((max(pos, 16), 4), dtype=np.int16)
-    ev_parts, ev_start, max_events = [], [0], 0
+    paths = [os.path.join(wav_pth, name + ".wav") for name in filelist]
+    # headers first: the stream is allocated once
+    hc = HostCorpus(HostCorpus.EVAL, filelist, [_read_wav(who, p)[1].shape[0] for p in paths], hop, set_type, wav_pth, csv_pth,
+                    rank, world)
+    ev_parts = []
     for i, name in enumerate(filelist):
-        s0, n = int(rec_start[i]), int(lengths[i])
-        audio[s0:s0 + n] = wav_of(name)[1]
+        hc.stream(i)[:] = _read_wav(who, paths[i])[1]
         path = os.path.join(csv_pth, name + ".csv")
-        if not os.path.exists(path):
-            raise ValueError("load_eval_split: label file %s is missing" % path)
-        rows = []
-        for frame, events in FoaDataset.load_csv2dict(path).items():
-            for ev in events:
-                if len(ev) != 4:
-                    raise ValueError("load_eval_split: %s has a row that is not [frame, class, source, azimuth, elevation]" % path)
-                if not 0 <= ev[0] < nb_classes:
-                    raise ValueError("load_eval_split: %s has an event of class %d, outside [0, %d) (nb_classes)"
-                                     % (path, ev[0], nb_classes))
-                rows.append((frame, ev[0], ev[1], ev[2], ev[3]))
+        rows = _csv_rows(who, path, nb_classes)
         if any(rows[k][0] > rows[k + 1][0] for k in range(len(rows) - 1)):
             raise ValueError("load_eval_split: the frames of %s do not ascend" % path)
         ev_parts.append(np.asarray(rows, dtype=np.float64).reshape(-1, _EV_COLS))
-        ev_start.append(ev_start[-1] + len(rows))
-        max_events = max(max_events, len(rows))
-    n_rec = len(filelist)
-    checks = range(n_rec) if verify == "all" else (sorted({0, n_rec // 2, n_rec - 1}) if verify == "sample" and n_rec else ())
-    for i in checks:
-        path, data = wav_of(filelist[i])
-        s0 = int(rec_start[i])
-        if not np.array_equal(np.asarray(data), audio[s0:s0 + int(lengths[i])]):
-            raise ValueError("load_eval_split: %s changed while the split was read" % path)
-
-    hc = HostCorpus()
-    hc.wav_pth, hc.csv_pth, hc.set_type = wav_pth, csv_pth, set_type
-    hc.rank, hc.world = rank, world
-    hc.audio = audio
-    hc.rec_names, hc.rec_start, hc.lengths = list(filelist), rec_start, lengths
-    hc.events = np.concatenate(ev_parts, 0) if ev_parts else np.zeros((0, _EV_COLS))
-    hc.ev_start = np.asarray(ev_start, dtype=np.int64)
-    hc.filelist = hc.total_filelist = list(filelist)
-    hc.hop_label, hc.max_events = hop, max_events
-    hc.window = int((lengths // 600).max() * 600) if n_rec else 0
-    hc.stride, hc.window_frames = 0, hc.window // hop
-    hc.chunks, hc.chunk_events = {}, {}
+        hc.max_events = max(hc.max_events, len(rows))
+    hc.set_events(ev_parts)
+    for i in _verify_picks(who, verify, len(filelist)):
+        if not np.array_equal(np.asarray(_read_wav(who, paths[i])[1]), hc.stream(i)):
+            raise ValueError("load_eval_split: %s changed while the split was read" % paths[i])
     return hc
 
 
@@ -679,22 +708,13 @@ class EvalDeviceCorpus(_CorpusBase):
 
     def __init__(self, host_split, params, device="cuda:0", cap_per_clip=None):
         hc = host_split
-        if not hasattr(hc, "lengths"):
+        if hc.kind == HostCorpus.CHUNKED:
             raise ValueError("EvalDeviceCorpus: the split of load_eval_split is needed (got the chunked training split)")
         self.loss_nm = params["args"]["loss"]
         if self.loss_nm != "adyolo" and self.loss_nm not in CLASSWISE_LABELS:
             raise NotImplementedError("EvalDeviceCorpus: loss %s" % self.loss_nm)
-        self.host = hc
-        self.device = torch.device(device)
-        self.rank, self.world = hc.rank, hc.world
-        self.is_valid, self.is_infer, self.set_type = True, False, hc.set_type
-        self.wav_pth, self.csv_pth = hc.wav_pth, hc.csv_pth
-        self.hop_label = hc.hop_label
-        self.rotate = False
-        self.filelist = list(hc.filelist)
-        self.max_events = int(hc.max_events)
         self.nb_classes = int(params["data_config"]["nb_classes"])
-        self._to_hbm(hc)
+        self._adopt(hc, device, hc.rank, hc.world, is_valid=True)
         n = len(self.filelist)
         self.lengths = [int(v) for v in hc.lengths.tolist()]
         self.n_hops = [v // 600 * 600 for v in self.lengths]            # whole hops, as test_epoch_audio cuts a clip
@@ -704,13 +724,8 @@ class EvalDeviceCorpus(_CorpusBase):
             items[i] = (hc.rec_start[i], 0, hc.ev_start[i], hc.ev_start[i + 1] - hc.ev_start[i], -1, i, 0, 0)
         self.items = torch.from_numpy(items).to(self.device)
         if self.loss_nm == "adyolo":
-            self.encoder = YoloLabelEncoder(params)
-            self.cells = max_cells_per_event(self.encoder)
+            self._yolo_tables(params)
             self.cap_per_clip = int(cap_per_clip) if cap_per_clip is not None else max(1, self.max_events * self.cells)
-            enc = self.encoder
-            self.bounds = torch.from_numpy(np.concatenate([enc.az_lb, enc.az_ub, enc.el_lb, enc.el_ub])
-                                           .astype(np.float64)).to(self.device)
-            self.grid = (len(enc.az_lb), len(enc.el_lb))
             self.xyz = None
         else:
             full = np.zeros((max(1, hc.events.shape[0]), ops.CORPUS_XYZ_SLOTS, 3), dtype=np.float32)
@@ -735,9 +750,7 @@ class EvalDeviceCorpus(_CorpusBase):
 
     def cap(self, batch):
         """Target rows of a batch of ``batch`` clips (AD-YOLO)."""
-        from . import graph
-        q = graph.TARGET_QUANTUM
-        return (max(1, int(batch) * self.cap_per_clip) + q - 1) // q * q
+        return self._round_cap(int(batch) * self.cap_per_clip)
 
     def _items_of(self, indices):
         idx = list(indices)
@@ -759,9 +772,7 @@ class EvalDeviceCorpus(_CorpusBase):
                              % (idx, [self.lengths[i] for i in idx]))
         if t <= 0 or frames <= 0:
             raise ValueError("EvalDeviceCorpus.launch: clip %s is shorter than one hop / label frame" % self.filelist[idx[0]])
-        audio = audio_out if audio_out is not None else torch.empty((b, t, 4), dtype=torch.float32, device=self.device)
-        if tuple(audio.shape) != (b, t, 4):
-            raise ValueError("EvalDeviceCorpus.launch: audio_out %s, expected (%d, %d, 4)" % (tuple(audio.shape), b, t))
+        audio = self._out(audio_out, (b, t, 4))
         ops.corpus_gather(self.pcm, items, self.rot, audio, self.status)
         if self.loss_nm != "adyolo":
             target = torch.empty(ops.corpus_classwise_shape(self.loss_nm, b, frames, self.nb_classes), dtype=torch.float32,
@@ -879,31 +890,13 @@ def infer_split_from_arrays(names, arrays, params, rates=None):
             lengths.append(resample.n_out(a.shape[0], l, m))
         native_lengths = np.asarray([a.shape[0] for a in arrays], dtype=np.int64).reshape(-1)
         lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
-    rec_start = np.zeros(len(names) + 1, dtype=np.int64)
-    pos = 0
-    for i, n in enumerate(lengths.tolist()):
-        rec_start[i] = pos
-        pos += (n + 15) // 16 * 16
-    rec_start[-1] = pos
-    audio = np.zeros((max(pos, 16), 4), dtype=np.int16)
+    hc = HostCorpus(HostCorpus.INFER, names, lengths, hop, "infer")
     for i, a in enumerate(arrays):
         if native is None or native[i] is None:
-            audio[int(rec_start[i]):int(rec_start[i]) + int(lengths[i])] = a
-    hc = HostCorpus()
+            hc.stream(i)[:] = a
     if native is not None:
         hc.native, hc.rates, hc.native_lengths = native, np.asarray(rates, dtype=np.int64).reshape(-1), native_lengths
         hc.kinds = np.asarray(kinds, dtype=np.int64).reshape(-1)
-    hc.wav_pth, hc.csv_pth, hc.set_type = None, None, "infer"
-    hc.rank, hc.world = 0, 1
-    hc.audio = audio
-    hc.rec_names, hc.rec_start, hc.lengths = list(names), rec_start, lengths
-    hc.events = np.zeros((0, _EV_COLS))
-    hc.ev_start = np.zeros(len(names) + 1, dtype=np.int64)
-    hc.filelist = hc.total_filelist = list(names)
-    hc.hop_label, hc.max_events = hop, 0
-    hc.window = int((lengths // 600).max() * 600) if len(names) else 0
-    hc.stride, hc.window_frames = 0, hc.window // hop
-    hc.chunks, hc.chunk_events = {}, {}
     return hc
 
 
@@ -919,9 +912,8 @@ def load_infer_split(params, rank=None, world=None, verify="sample", files=None,
     path; an int16 file at ``data_config.sr`` is laid out as above and every other one keeps its samples on the host for
     ``InferDeviceCorpus`` to convert on the device (``infer_split_from_arrays`` with ``rates``).  Without it the rate of a file
     is not looked at: a 48 kHz recording is run as if it were at ``data_config.sr``."""
-    from scipy.io import wavfile
-    if verify not in ("sample", "all", "none"):
-        raise ValueError("load_infer_split: verify must be 'sample', 'all' or 'none' (got %r)" % (verify,))
+    who = "load_infer_split"
+    _verify_picks(who, verify, 0)                                # a bad value is refused before anything is read
     wav_pth = str(params["args"]["infer_pth"])
     if not os.path.isdir(wav_pth):
         raise ValueError("load_infer_split: %s is not a directory (args.infer_pth)" % wav_pth)
@@ -936,52 +928,31 @@ def load_infer_split(params, rank=None, world=None, verify="sample", files=None,
             raise ValueError("load_infer_split: %s is not among this rank's files of %s" % (", ".join(missing), wav_pth))
         filelist = [f for f in filelist if f in want]
 
-    def wav_of(name):
-        path = os.path.join(wav_pth, name + ".wav")
-        _, data = wavfile.read(path, mmap=True)
-        if data.dtype != np.int16 or data.ndim != 2 or data.shape[1] != 4:
-            raise ValueError("load_infer_split: %s holds %s %s, expected int16 (n, 4)" % (path, data.dtype, tuple(data.shape)))
-        return path, data
+    paths = [os.path.join(wav_pth, name + ".wav") for name in filelist]
 
-    def native_wav_of(name):
-        from . import resample as rs
-        path = os.path.join(wav_pth, name + ".wav")
-        try:
-            rate, data = wavfile.read(path, mmap=True)
-        except ValueError as e:
-            if "mmap" not in str(e):                             # only scipy's "mmap=True not compatible with 24-bit" is retried
-                raise
-            rate, data = wavfile.read(path, mmap=False)          # 24-bit samples cannot be mapped: read into memory
-        if data.dtype not in rs.KINDS or data.ndim != 2 or data.shape[1] != 4:
-            raise ValueError("load_infer_split: %s holds %s %s, expected int16, 24-bit or float32 (n, 4)"
-                             % (path, data.dtype, tuple(data.shape)))
-        sr = int(params["data_config"].get("sr", 24000))
-        if max(rs.ratio(rate, sr)) > rs.MAX_P:
-            raise ValueError("load_infer_split: %s is at %d Hz; %d -> %d Hz is the ratio %d / %d, beyond resample.plan (%d)"
-                             % ((path, rate, rate, sr) + rs.ratio(rate, sr) + (rs.MAX_P,)))
-        return path, data, int(rate)
+    def read(path):
+        rate, data = _read_wav(who, path, native=resample)
+        if resample:                                             # what resample.plan refuses, by path
+            from .resample import MAX_P, ratio
+            sr = int(params["data_config"].get("sr", 24000))
+            if max(ratio(rate, sr)) > MAX_P:
+                raise ValueError("load_infer_split: %s is at %d Hz; %d -> %d Hz is the ratio %d / %d, beyond resample.plan (%d)"
+                                 % ((path, rate, rate, sr) + ratio(rate, sr) + (MAX_P,)))
+        return rate, data
 
-    n_rec = len(filelist)
-    checks = range(n_rec) if verify == "all" else (sorted({0, n_rec // 2, n_rec - 1}) if verify == "sample" and n_rec else ())
-    if resample:
-        read = [native_wav_of(name) for name in filelist]
-        hc = infer_split_from_arrays(filelist, [r[1] for r in read], params, rates=[r[2] for r in read])
-    else:
-        hc = infer_split_from_arrays(filelist, [wav_of(name)[1] for name in filelist], params)
-    for i in checks:
-        if resample:
-            path, data, rate = native_wav_of(filelist[i])
-            if hc.native[i] is not None:
-                kept = np.asarray(hc.native[i])
-                if rate != int(hc.rates[i]) or data.dtype != kept.dtype or data.shape != kept.shape or \
-                        not np.array_equal(np.ascontiguousarray(data).view(np.uint8), np.ascontiguousarray(kept).view(np.uint8)):
-                    raise ValueError("load_infer_split: %s changed while the split was read" % path)
-                continue
+    files_read = [read(p) for p in paths]
+    hc = infer_split_from_arrays(filelist, [data for _, data in files_read], params,
+                                 rates=[rate for rate, _ in files_read] if resample else None)
+    for i in _verify_picks(who, verify, len(filelist)):
+        rate, data = read(paths[i])
+        if hc.native is not None and hc.native[i] is not None:
+            kept = np.asarray(hc.native[i])
+            same = rate == int(hc.rates[i]) and data.dtype == kept.dtype and data.shape == kept.shape and \
+                np.array_equal(np.ascontiguousarray(data).view(np.uint8), np.ascontiguousarray(kept).view(np.uint8))
         else:
-            path, data = wav_of(filelist[i])
-        s0 = int(hc.rec_start[i])
-        if not np.array_equal(np.asarray(data), hc.audio[s0:s0 + int(hc.lengths[i])]):
-            raise ValueError("load_infer_split: %s changed while the split was read" % path)
+            same = np.array_equal(np.asarray(data), hc.stream(i))
+        if not same:
+            raise ValueError("load_infer_split: %s changed while the split was read" % paths[i])
     hc.wav_pth, hc.rank, hc.world = wav_pth, rank, world
     return hc
 
@@ -1005,7 +976,7 @@ class InferDeviceCorpus(_CorpusBase):
     def __init__(self, host_split, params, device="cuda:0", window_s=None, margin_s=None, batch_size=8):
         from .features import HOP
         hc = host_split
-        if not hasattr(hc, "lengths"):
+        if hc.kind == HostCorpus.CHUNKED:
             raise ValueError("InferDeviceCorpus: the split of load_infer_split is needed (got the chunked training split)")
         dc = params["data_config"]
         sr = int(dc.get("sr", 24000))
@@ -1024,14 +995,8 @@ class InferDeviceCorpus(_CorpusBase):
         self.batch_size = int(batch_size)
         if not 1 <= self.batch_size < 65536:
             raise ValueError("InferDeviceCorpus: batch_size %r" % (batch_size,))
-        self.host = hc
-        self.device = torch.device(device)
-        self.rank, self.world = hc.rank, hc.world
-        self.is_valid, self.is_infer, self.set_type = True, True, "infer"
-        self.wav_pth, self.csv_pth = hc.wav_pth, None
-        self.hop_label, self.n_samples = hop, n
-        self.rotate = False
-        self.filelist = list(hc.filelist)
+        self._adopt(hc, device, hc.rank, hc.world, is_valid=True, is_infer=True)
+        self.n_samples = n
         self.lengths = [int(v) for v in hc.lengths.tolist()]
         self.label_frames = [v // hop for v in self.lengths]
         self.frame_start = np.concatenate([[0], np.cumsum(self.label_frames)]).astype(np.int64)
@@ -1051,7 +1016,6 @@ class InferDeviceCorpus(_CorpusBase):
         per = table.reshape(self.n_passes, self.batch_size, ops.WINDOW_WORDS)
         self.pass_base = [int(v) for v in per[:, 0, 3].tolist()]
         self.pass_frames = [int(v) for v in per[:, :, 4].sum(1).tolist()]
-        self._to_hbm(hc)
         self._convert_native(hc, sr)
         self.table = torch.from_numpy(table if len(rows) else np.zeros((1, ops.WINDOW_WORDS), dtype=np.int64)).to(self.device)
 
@@ -1062,7 +1026,7 @@ class InferDeviceCorpus(_CorpusBase):
         alignment tails stay int16 zero.  The status word is read after each group (one host synchronisation per group, beside
         uploads that block the host anyway): a non-finite float sample or a bad row raises ``AdyoloHipError`` naming the group,
         here and not in a later ``check()``, because ``infer_epoch_corpus`` clears the word when a pass begins."""
-        native = getattr(hc, "native", None)
+        native = hc.native
         if native is None:
             return
         from . import resample
@@ -1105,8 +1069,5 @@ class InferDeviceCorpus(_CorpusBase):
     def launch(self, p, audio_out=None):
         """Pass ``p`` -> audio (batch_size, n_samples, 4) f32 on the device; no host data, no host synchronisation.  audio_out:
         write into this buffer (a recorded forward graph's input)."""
-        shape = (self.batch_size, self.n_samples, 4)
-        audio = audio_out if audio_out is not None else torch.empty(shape, dtype=torch.float32, device=self.device)
-        if tuple(audio.shape) != shape:
-            raise ValueError("InferDeviceCorpus.launch: audio_out %s, expected %s" % (tuple(audio.shape), shape))
+        audio = self._out(audio_out, (self.batch_size, self.n_samples, 4))
         return ops.corpus_gather_windows(self.pcm, self.pass_table(p), audio, self.status)

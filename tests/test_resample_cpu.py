@@ -240,7 +240,7 @@ def test_load_infer_split_reads_rates_and_formats(tmp_path):
     with pytest.raises(ValueError, match=r"c_float\.wav"):
         C.load_infer_split(prm, rank=0, world=1, files=["a_native", "c_float"])
     plain = C.infer_split_from_arrays(["a"], [written["a_native"][1]], prm)
-    assert not hasattr(plain, "native") and not hasattr(plain, "rates")
+    assert plain.native is None and plain.rates is None
     # refused by path: two channels, float64, a rate beyond the plan
     wavfile.write(str(tmp_path / "e_stereo.wav"), 48000, np.zeros((480, 2), dtype=np.int16))
     with pytest.raises(ValueError, match=r"e_stereo\.wav"):

@@ -105,6 +105,7 @@ SIGNATURES = {
     "adyolo_classwise_select_workspace_words": (L, [L, I, I]),
     "adyolo_classwise_select": (I, [P] * 4 + [L, I, I, F, F, P]),
     "adyolo_conv_gemm": (I, [P, P, P, P] + [I] * 13 + [P]),
+    "adyolo_conv_gemm_plan": (I, [I] * 13 + [P]),
     "adyolo_pack_wk": (I, [P, P, I, I, I, I, I, P]),
     "adyolo_maxpool3_fwd": (I, [P, P, P, I, I, I, I, P]),
     "adyolo_maxpool3_bwd": (I, [P, P, P, I, I, I, I, P]),

@@ -42,6 +42,14 @@ struct ConvGather {
     int Hs, Ws, Cs, Hm, Wm, KH, KW, SH, SW, PH, PW, dgrad, kreal;
 };
 
+// The two carried index forms of a gathered operand, as predicates of the geometry alone: gemm_kernel takes them and the host
+// reports them (adyolo_conv_gemm_plan) through these two functions.
+//   fastk (G == 1): the source's channel count is a multiple of the K tile, so a K tile lies inside one tap.
+//   fastp (G == 2): the map width divides the K tile and the map has at least GBK / Wm rows, so a K tile moves y by GBK / Wm
+//                   with at most one carry into the sample index.
+__host__ __device__ inline bool conv_gather_fastk(int Cs) { return (Cs % GBK) == 0; }
+__host__ __device__ inline bool conv_gather_fastp(int Hm, int Wm) { return Wm > 0 && (GBK % Wm) == 0 && Hm >= GBK / Wm; }
+
 // Tile shape (round 4): WM x WN waves, each SM x SN accumulator tiles of 32 x 32: BM = 32 WM SM rows x BN = 32 WN SN columns.
 //   4 x 1 x 1 x 2 = 128 x 64 on 256 threads: the form every launch uses.
 //   4 x 2 x 2 x 2 = 256 x 128 on 512 threads was measured in round 4 and is not launched (not faster: see above adyolo_gemm).
@@ -104,6 +112,9 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN > 4 ? 1 : 2)) void gemm_kern
         }
     }
     // gathered B (G == 2): the (kh, kw, c) of this thread's columns is fixed over the K loop
+    // (nn < cg.kreal here and k < cg.kreal in the gathered A fetch below are never false behind adyolo_conv_gemm: it wants the
+    //  channel counts to be multiples of 4, so the padded K of the packed filter IS kreal and N resp. K end there; they stay
+    //  for a caller with a padded K)
     int bkh = 0, bkw = 0, bc = -1;
     if (G == 2) {
         const int nn = n0 + (tid % (BN / 4)) * 4;
@@ -118,7 +129,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN > 4 ? 1 : 2)) void gemm_kern
     // gathered A: (kh, kw, c) of the K tile's first column.  With the channel count a multiple of the K tile, a tile never
     // straddles two taps and the triple is advanced with carries from tile to tile instead of two integer divisions per
     // fetch (~70 vector instructions per thread and tile beside 32 MFMAs)
-    const bool fastk = G == 1 && (cg.Cs % GBK) == 0;
+    const bool fastk = G == 1 && conv_gather_fastk(cg.Cs);
     int c_run = 0, kh_run = 0, kw_run = 0;
     if (fastk) {
         const int tap0 = kbeg / cg.Cs;
@@ -128,7 +139,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN > 4 ? 1 : 2)) void gemm_kern
     }
     // gathered B (G == 2): pixel (n, y, x) of this thread's two K rows; with the map width dividing the K tile a tile step
     // moves y by GBK / Wm with at most one carry into n (Hm >= GBK / Wm is checked), instead of three divisions per row and fetch
-    const bool fastp = G == 2 && cg.Wm > 0 && (GBK % cg.Wm) == 0 && cg.Hm >= GBK / cg.Wm;
+    const bool fastp = G == 2 && conv_gather_fastp(cg.Hm, cg.Wm);
     int px[2] = {0, 0}, py[2] = {0, 0}, pn[2] = {0, 0};
     if (fastp) {
 #pragma unroll
@@ -667,48 +678,79 @@ extern "C" int adyolo_gemm_batched(const float *A, const float *B, float *C, int
 //   mode 1 (data-gradient):  out dx [N*H*W][Cin]    = gather(dy) . wkT^T     src = dy [N][Ho][Wo][Cout], other = wkT [Cin][Kq]
 //   mode 2 (weight-gradient):out dwk[Cout][Kp]      = dy^T . gather(x)       src = x,                    other = dy
 // with Kp = roundup4(KH*KW*Cin), k = (kh*KW + kw)*Cin + ci and Kq = roundup4(KH*KW*Cout), k = (kh*KW + kw)*Cout + co.
-extern "C" int adyolo_conv_gemm(const float *src, const float *other, float *out, float *slabs, int mode, int N, int H,
-                                int W, int Cin, int Cout, int KH, int KW, int SH, int SW, int PH, int PW, int splits,
-                                void *stream) {
-    ADYOLO_REQUIRE(src && other && out && N > 0 && H > 0 && W > 0 && KH > 0 && KW > 0 && SH > 0 && SW > 0 && PH >= 0 &&
-                       PW >= 0 && mode >= 0 && mode <= 2,
+//
+// THE host decisions of such a launch, for adyolo_conv_gemm and adyolo_conv_gemm_plan: the GEMM shape, the gather, the K range
+// of a split, the splits that are not empty, the fetch bits.  Checks the geometry as the entry point always did.
+struct ConvGemmPlan {
+    int M, Nn, K, ldo, klen, splits, fastg;        // ldo: leading dimension of the packed filter (modes 0 / 1)
+    ConvGather cg;
+};
+static int conv_gemm_plan(int mode, int N, int H, int W, int Cin, int Cout, int KH, int KW, int SH, int SW, int PH, int PW,
+                          int splits, ConvGemmPlan *p) {
+    ADYOLO_REQUIRE(N > 0 && H > 0 && W > 0 && KH > 0 && KW > 0 && SH > 0 && SW > 0 && PH >= 0 && PW >= 0 && mode >= 0 && mode <= 2,
                    ADYOLO_EINVAL, "conv_gemm: bad arguments");
     ADYOLO_REQUIRE(Cin > 0 && Cout > 0 && Cin % 4 == 0 && Cout % 4 == 0, ADYOLO_ENOSUP,
                    "conv_gemm: Cin=%d and Cout=%d must be multiples of 4", Cin, Cout);
     const int Ho = (H + 2 * PH - KH) / SH + 1, Wo = (W + 2 * PW - KW) / SW + 1;
-    ADYOLO_REQUIRE(Ho > 0 && Wo > 0, ADYOLO_EINVAL, "conv_gemm: empty output");
+    ADYOLO_REQUIRE(H + 2 * PH >= KH && W + 2 * PW >= KW && Ho > 0 && Wo > 0, ADYOLO_EINVAL, "conv_gemm: empty output");
     ADYOLO_REQUIRE((size_t)N * H * W * Cin < ((size_t)1 << 31) && (size_t)N * Ho * Wo * Cout < ((size_t)1 << 31), ADYOLO_ENOSUP,
                    "conv_gemm: tensors must stay below 2^31 elements");
-    hipStream_t st = as_stream(stream);
     const int Kp = cdiv(KH * KW * Cin, 4) * 4, Kq = cdiv(KH * KW * Cout, 4) * 4;
-    GemmBatch bt{0, 0, 0, 0, 0, 0, 0, 1.0f};
-    const float *bias = nullptr;
-    int M, Nn, K;
-    ConvGather cg;
     if (mode == 0) {
-        M = N * Ho * Wo, Nn = Cout, K = Kp;
-        cg = ConvGather{H, W, Cin, Ho, Wo, KH, KW, SH, SW, PH, PW, 0, KH * KW * Cin};
+        p->M = N * Ho * Wo, p->Nn = Cout, p->K = Kp, p->ldo = Kp;
+        p->cg = ConvGather{H, W, Cin, Ho, Wo, KH, KW, SH, SW, PH, PW, 0, KH * KW * Cin};
     } else if (mode == 1) {
-        M = N * H * W, Nn = Cin, K = Kq;
-        cg = ConvGather{Ho, Wo, Cout, H, W, KH, KW, SH, SW, PH, PW, 1, KH * KW * Cout};
+        p->M = N * H * W, p->Nn = Cin, p->K = Kq, p->ldo = Kq;
+        p->cg = ConvGather{Ho, Wo, Cout, H, W, KH, KW, SH, SW, PH, PW, 1, KH * KW * Cout};
     } else {
-        M = Cout, Nn = Kp, K = N * Ho * Wo;
-        cg = ConvGather{H, W, Cin, Ho, Wo, KH, KW, SH, SW, PH, PW, 0, KH * KW * Cin};
+        p->M = Cout, p->Nn = Kp, p->K = N * Ho * Wo, p->ldo = 0;
+        p->cg = ConvGather{H, W, Cin, Ho, Wo, KH, KW, SH, SW, PH, PW, 0, KH * KW * Cin};
     }
-    if (mode != 2 || splits < 1) splits = mode == 2 ? (splits < 1 ? 1 : splits) : 1;
-    ADYOLO_REQUIRE(splits == 1 || slabs, ADYOLO_EINVAL, "conv_gemm: splits > 1 needs a slab workspace");
+    if (mode != 2 || splits < 1) splits = 1;
     // the operand that is NOT gathered goes through the buffer-descriptor fetch: mode 2: A = dy [pixels][Cout] (transposed,
     // lda = Cout); modes 0 / 1: B = the packed filter [Nn][K] (k-major, ldb = K)
-    const GemmPlan pl = mode == 2 ? gemm_plan(M, 4, K, Cout, 4, 1, 1, splits)
-                                  : gemm_plan(4, Nn, K, 4, mode == 0 ? Kp : Kq, 0, 0, splits);
-    const int klen = pl.klen;
-    splits = pl.splits;
-    int fastg = pl.fastg & (mode == 2 ? 1 : 2);
+    const GemmPlan pl = mode == 2 ? gemm_plan(p->M, 4, p->K, Cout, 4, 1, 1, splits) : gemm_plan(4, p->Nn, p->K, 4, p->ldo, 0, 0, splits);
+    p->klen = pl.klen;
+    p->splits = pl.splits;
+    p->fastg = pl.fastg & (mode == 2 ? 1 : 2);
     // bit 2: the gathered operand of a forward / unit-stride data-gradient launch through a descriptor as well (whole K tiles
     // inside one tap: source channels a multiple of the K tile; source below 2^29 floats incl. the tap bias)
-    if (fastg && mode != 2 && cg.Cs % GBK == 0 && (mode == 0 || (SH == 1 && SW == 1)) &&
+    const ConvGather &cg = p->cg;
+    if (p->fastg && mode != 2 && conv_gather_fastk(cg.Cs) && (mode == 0 || (SH == 1 && SW == 1)) &&
         (long)N * cg.Hs * cg.Ws * cg.Cs + (long)(KH * cg.Ws + KW) * cg.Cs < ((long)1 << 29))
-        fastg |= 4;
+        p->fastg |= 4;
+    return 0;
+}
+
+// host only (no launch): what adyolo_conv_gemm decides for these arguments (and refuses, with its codes).  out8 = M, Nn, K of
+// the GEMM, klen, the effective splits, fastg as the kernel gets it (bit 0 / 1: the plain operand A / B on a descriptor, bit 2:
+// the gathered A on a descriptor), fastk and fastp as the kernel evaluates them (0 where the mode's instantiation has no such form).
+extern "C" int adyolo_conv_gemm_plan(int mode, int N, int H, int W, int Cin, int Cout, int KH, int KW, int SH, int SW, int PH,
+                                     int PW, int splits, int *out8) {
+    ADYOLO_REQUIRE(out8, ADYOLO_EINVAL, "conv_gemm_plan: null pointer");
+    ConvGemmPlan p;
+    const int rc = conv_gemm_plan(mode, N, H, W, Cin, Cout, KH, KW, SH, SW, PH, PW, splits, &p);
+    if (rc) return rc;
+    out8[0] = p.M, out8[1] = p.Nn, out8[2] = p.K, out8[3] = p.klen, out8[4] = p.splits, out8[5] = p.fastg;
+    out8[6] = mode != 2 && conv_gather_fastk(p.cg.Cs);
+    out8[7] = mode == 2 && conv_gather_fastp(p.cg.Hm, p.cg.Wm);
+    return 0;
+}
+
+extern "C" int adyolo_conv_gemm(const float *src, const float *other, float *out, float *slabs, int mode, int N, int H,
+                                int W, int Cin, int Cout, int KH, int KW, int SH, int SW, int PH, int PW, int splits,
+                                void *stream) {
+    ADYOLO_REQUIRE(src && other && out, ADYOLO_EINVAL, "conv_gemm: bad arguments");
+    ConvGemmPlan pl;
+    int rc = conv_gemm_plan(mode, N, H, W, Cin, Cout, KH, KW, SH, SW, PH, PW, splits, &pl);
+    if (rc) return rc;
+    ADYOLO_REQUIRE(mode != 2 || splits <= 1 || slabs, ADYOLO_EINVAL, "conv_gemm: splits > 1 needs a slab workspace");
+    hipStream_t st = as_stream(stream);
+    GemmBatch bt{0, 0, 0, 0, 0, 0, 0, 1.0f};
+    const float *bias = nullptr;
+    const int M = pl.M, Nn = pl.Nn, K = pl.K, klen = pl.klen, fastg = pl.fastg;
+    const ConvGather cg = pl.cg;
+    splits = pl.splits;
     dim3 grid((unsigned)cdiv(Nn, GBN), (unsigned)cdiv(M, GBM), (unsigned)splits);
     const size_t slab_stride = splits > 1 ? (size_t)M * Nn : 0;
     float *dst = splits > 1 ? slabs : out;
@@ -717,8 +759,8 @@ extern "C" int adyolo_conv_gemm(const float *src, const float *other, float *out
                            Nn, klen, slab_stride, Nn, 0, bt, cg, fastg);
     else
         hipLaunchKernelGGL((gemm_kernel<false, false, 1>), grid, dim3(256), 0, st, src, other, bias, dst, M, Nn, K, 0,
-                           mode == 0 ? Kp : Kq, Nn, klen, slab_stride, Nn, 0, bt, cg, fastg);
-    int rc = check_launch("conv_gemm");
+                           pl.ldo, Nn, klen, slab_stride, Nn, 0, bt, cg, fastg);
+    rc = check_launch("conv_gemm");
     if (rc || splits == 1) return rc;
     const size_t total = (size_t)M * Nn;
     hipLaunchKernelGGL(gemm_slab_reduce_kernel, dim3(cdiv((long)total, 256)), dim3(256), 0, st, slabs, bias, out, M, Nn,

@@ -596,6 +596,16 @@ int adyolo_colstats(const float *a, float *partial, double *out, long rows, int 
  * splits (mode 2 only): split-K over the N*Ho*Wo output pixels, slabs = [splits][Cout][Kp] workspace (deterministic sum). */
 int adyolo_conv_gemm(const float *src, const float *other, float *out, float *slabs, int mode, int N, int H, int W,
                      int Cin, int Cout, int KH, int KW, int SH, int SW, int PH, int PW, int splits, void *stream);
+/* host only, no launch: what adyolo_conv_gemm decides for these arguments, refused with the same codes.  out8 =
+ *   [0] M, [1] N, [2] K of the GEMM (mode 0: pixels of y x Cout x Kp; mode 1: pixels of dx x Cin x Kq; mode 2: Cout x Kp x pixels of y)
+ *   [3] klen: the K range of one split (whole K tiles of 32),  [4] the splits that are not empty with it (1 in modes 0 / 1)
+ *   [5] fastg: bit 0 / 1 = the plain operand A (mode 2: dy) / B (modes 0 / 1: the packed filter) may go through a buffer
+ *       descriptor -- the kernel takes it for a k-major operand only, so never for mode 2's transposed dy; bit 2 = the gathered
+ *       pixel operand of modes 0 / 1 goes through a descriptor (tap in the scalar offset)
+ *   [6] fastk (modes 0 / 1): the (c, kh, kw) triple of a K tile is carried, not divided (source channels % 32 == 0)
+ *   [7] fastp (mode 2): the pixel triple of a K row is carried (32 % Wo == 0 and Ho >= 32 / Wo) */
+int adyolo_conv_gemm_plan(int mode, int N, int H, int W, int Cin, int Cout, int KH, int KW, int SH, int SW, int PH, int PW,
+                          int splits, int *out8);
 
 /* ------------------------------------------------------------------------------------------------
  * K9  ResNet-Conformer encoder pieces (src/models/backbones/resnet_conformer.py), channels-last fp32

@@ -134,6 +134,7 @@ SIGNATURES = {
     "adyolo_seed32_dev": (I, [ctypes.c_uint64, ctypes.c_uint64, P, P, P]),
     "adyolo_attn_dropout_mask": (I, [P, I, I, I, F, ctypes.c_uint32, P]),
     "adyolo_foa_rotate": (I, [P, P, P, I, L, P]),
+    "adyolo_foa_rotate_yaw": (I, [P, P, P, I, L, P]),
     "adyolo_mic_swap": (I, [P, P, P, I, L, P]),
     "adyolo_corpus_gather": (I, [P, L, P, I, L, P, P, P, P]),
     "adyolo_corpus_gather_mic": (I, [P, L, P, I, L, P, P, P, P]),
@@ -145,6 +146,12 @@ SIGNATURES = {
     "adyolo_corpus_yolo_labels_mix_workspace_words": (L, [I, I]),
     "adyolo_corpus_yolo_labels_mix": (I, [P, L, P, P, I, I, I, P, I, I, P, P, P, L, P, P, P]),
     "adyolo_corpus_classwise_labels_mix": (I, [P, P, L, P, P, I, I, I, I, I, P, P, P]),
+    "adyolo_corpus_gather_yaw": (I, [P, L, P, I, L, P, P, P, P, P]),
+    "adyolo_corpus_gather_yaw_mix": (I, [P, L, P, P, I, L, P, P, P, P, P]),
+    "adyolo_corpus_yolo_labels_yaw": (I, [P, L, P, I, I, I, P, I, I, P, P, P, L, P, P, P]),
+    "adyolo_corpus_yolo_labels_yaw_mix": (I, [P, L, P, P, I, I, I, P, I, I, P, P, P, L, P, P, P]),
+    "adyolo_corpus_classwise_labels_yaw": (I, [P, P, L, P, I, I, I, I, I, P, P, P, P, P, P]),
+    "adyolo_corpus_classwise_labels_yaw_mix": (I, [P, P, L, P, P, I, I, I, I, I, P, P, P, P, P, P]),
     "adyolo_corpus_gather_windows": (I, [P, L, P, I, L, P, P, P]),
     "adyolo_decode_stitch": (I, [P, P, I, I, L, L, P, L, P, P]),
     "adyolo_resample_pcm": (I, [P, I, L, P, I, P, L, I, I, I, L, P, L, P, P]),

@@ -1,7 +1,10 @@
 """FOA rotation and MIC channel-swap augmentation.  Mirror of ``RotationAug`` (/root/reference/src/utils/augmentations.py:36-111): 16
 combinations of channel sign flips / X-Y swap with the matching azimuth / elevation remapping of the labels.
 ``rotate_labels`` is the host half (label dict); ``rotate_audio`` applies the channel transform to a whole batch of raw
-audio on the GPU (csrc/aug.hip ``foa_rotate_kernel``).  ``swap_audio`` / ``ChannelSwapAug`` are the MIC-format counterpart (no
+audio on the GPU (csrc/aug.hip ``foa_rotate_kernel``).  ``yaw_config`` / ``draw_yaw`` / ``yaw_cos_sin`` / ``yaw_labels`` /
+``rotate_audio_yaw`` are the yaw rotation: the FOA sound field turned about the vertical axis by any whole angle after the
+combination (no reference; ``aug_config.yaw_rotation_augment``, csrc/aug.hip ``foa_rotate_yaw_kernel``).
+``swap_audio`` / ``ChannelSwapAug`` are the MIC-format counterpart (no
 reference: a permutation of the four capsules by a symmetry of the array, derived below from ``rotate_labels``).  ``SpecAug``
 (augmentations.py:6-33) masks the GPU feature tensor (csrc/aug.hip); its random draw restates torchaudio 0.10, which is absent
 here (parity of the stream unpinned).  ``feature_aug_config`` / ``draw_feature_aug`` / ``apply_feature_aug_host`` are the keys,
@@ -52,6 +55,95 @@ def rotate_audio(audio, comb_nos):
                        dtype=torch.float32).to(audio.device)
     out = torch.empty_like(audio)
     _lib.call("adyolo_foa_rotate", _p(audio), _p(out), _p(cfg), b, n, _stream())
+    return out
+
+
+# ---- Yaw rotation: the sound field turned about the vertical axis by any whole angle (``aug_config.yaw_rotation_augment``), an
+# exact symmetry of the B-format: X' = X cos - Y sin, Y' = Y cos + X sin, W and Z unchanged, every azimuth moved by the angle.
+def yaw_config(params):
+    """``aug_config.yaw_rotation_augment`` and ``yaw_step_deg`` -> None (off; ``yaw_step_deg`` is not read) or the step in
+    degrees (default 1): an integer >= 1 that divides 360 (``ValueError`` naming the key otherwise).  FOA only: with
+    ``data_config.audio_format: mic`` the key raises ``ValueError`` (a yaw is no symmetry of the microphone array;
+    ``channel_swap_augment`` is the MIC augmentation)."""
+    aug = params.get("aug_config", {})
+    if not bool(aug.get("yaw_rotation_augment", False)):
+        return None
+    fmt = str(params.get("data_config", {}).get("audio_format", "foa")).lower()
+    if fmt != "foa":
+        raise ValueError("aug_config.yaw_rotation_augment turns the B-format sound field: it needs data_config.audio_format "
+                         "'foa' (got %r; channel_swap_augment is the MIC augmentation)" % fmt)
+    step = aug.get("yaw_step_deg", 1)
+    if isinstance(step, bool) or not isinstance(step, int) or step < 1 or 360 % step:
+        raise ValueError("aug_config.yaw_step_deg must be an integer >= 1 that divides 360 (got %r)" % (step,))
+    return int(step)
+
+
+def draw_yaw(rnd, config):
+    """One yaw draw from ``rnd`` (the dataset's ``random`` module), right after a combination draw (or where it would stand):
+    phi = -180 + step * k degrees, k uniform in 0 .. 360 / step - 1 -> int in [-180, 180).  One helper for ``FoaDataset`` and both
+    device corpora (the mate's yaw is drawn inside ``draw_time_mix``): the same seed draws the same yaws on every path."""
+    n = 360 // config
+    return -180 + config * min(int(rnd.random() * n), n - 1)
+
+
+def yaw_cos_sin(phi):
+    """Yaw in degrees -> (cos, sin) as two ``np.float32``: exact at the multiples of 90 degrees, elsewhere the float32 of
+    ``math.cos`` / ``math.sin`` of ``math.radians(phi)``."""
+    import math
+    import numpy as np
+    exact = {0: (1.0, 0.0), 90: (0.0, 1.0), 180: (-1.0, 0.0), 270: (0.0, -1.0)}.get(phi % 360 if phi == int(phi) else None)
+    if exact is not None:
+        return np.float32(exact[0]), np.float32(exact[1])
+    return np.float32(math.cos(math.radians(phi))), np.float32(math.sin(math.radians(phi)))
+
+
+def yaw_labels(label: dict, phi):
+    """label {frame: [[cls, src, az, el], ...]} (already moved by ``rotate_labels``, if at all) -> copy with every azimuth moved
+    by ``phi`` degrees and wrapped as ``rotate_labels`` wraps (one wrap suffices for az in [-180, 180], phi in [-180, 180));
+    the elevation is untouched."""
+    out = {}
+    for frame, events in label.items():
+        rows = []
+        for ev in events:
+            az = ev[-2] + phi
+            if az < -180:
+                az += 360
+            elif az > 180:
+                az -= 360
+            rows.append(list(ev[:-2]) + [az, ev[-1]])
+        out[frame] = rows
+    return out
+
+
+def yaw_audio_host(audio, phi):
+    """The definition of the yaw on audio, in NumPy float32: audio (..., 4) float32 frames (W, Y, Z, X) -> new array with
+    Y' = fl(fl(Y c) + fl(X s)), X' = fl(fl(X c) - fl(Y s)), (c, s) = ``yaw_cos_sin(phi)``; every product and sum rounded."""
+    import numpy as np
+    a = np.asarray(audio, dtype=np.float32)
+    c, s = yaw_cos_sin(phi)
+    out = a.copy()
+    y, x = a[..., 1], a[..., 3]
+    out[..., 1] = (y * c).astype(np.float32) + (x * s).astype(np.float32)
+    out[..., 3] = (x * c).astype(np.float32) - (y * s).astype(np.float32)
+    return out
+
+
+def rotate_audio_yaw(audio, comb_nos, phis):
+    """audio (B, n_samples, 4) float32 on the GPU, comb_nos: B combination indices (None or negative: no combination), phis: B
+    yaws in degrees -> the audio under its combinations, then yawed (new tensor; csrc/aug.hip ``foa_rotate_yaw_kernel``)."""
+    if not audio.is_cuda or audio.dtype != torch.float32 or not audio.is_contiguous() or audio.dim() != 3 or audio.shape[2] != 4:
+        raise _lib.AdyoloHipError("rotate_audio_yaw needs contiguous float32 audio (B, n_samples, 4) on the GPU")
+    b, n, _ = audio.shape
+    if len(comb_nos) != b or len(phis) != b:
+        raise _lib.AdyoloHipError("rotate_audio_yaw: %d combinations and %d yaws for a batch of %d" % (len(comb_nos), len(phis), b))
+    rows = []
+    for c, phi in zip(comb_nos, phis):
+        signs, swap = ((1, 1, 1), False) if c is None or int(c) < 0 else COMBINATIONS[int(c)][:2]
+        cos, sin = yaw_cos_sin(phi)
+        rows.append([*signs, float(swap), float(cos), float(sin)])
+    cfg = torch.tensor(rows, dtype=torch.float32).to(audio.device)
+    out = torch.empty_like(audio)
+    _lib.call("adyolo_foa_rotate_yaw", _p(audio), _p(out), _p(cfg), b, n, _stream())
     return out
 
 
@@ -130,11 +222,12 @@ def time_mix_enabled(params):
     return time_mix_config(params) is not None
 
 
-def draw_time_mix(rnd, config, total_filelist, name, comb_draw=None):
+def draw_time_mix(rnd, config, total_filelist, name, comb_draw=None, yaw=None):
     """The draws of one training item, after its own (rotation or swap combination, SpecAug table), from ``rnd`` (the dataset's
     ``random`` module): mixed at all?  If so the mate chunk, the mate's combination (``comb_draw`` "rotate": one of 16, "swap": one
     of ``MIC_SWAP_COMBS``, None: no draw) and the gain.  -> None (unmixed) or (mate name, combination or None, np.float32 gain).
-    A mate that is the item itself leaves the item unmixed, after all the draws."""
+    A mate that is the item itself leaves the item unmixed, after all the draws.  yaw (``yaw_config``; None: no draw, and the
+    tuple as above): the mate's yaw is drawn right after its combination (``draw_yaw``) and returned as a fourth element."""
     import numpy as np
     prob, lo, hi = config
     if not rnd.random() < prob:
@@ -145,8 +238,11 @@ def draw_time_mix(rnd, config, total_filelist, name, comb_draw=None):
         comb = int(rnd.uniform(0, 16))
     elif comb_draw == "swap":
         comb = MIC_SWAP_COMBS[int(rnd.uniform(0, 8))]
+    phi = draw_yaw(rnd, yaw) if yaw is not None else None
     gain = np.float32(10.0 ** (rnd.uniform(lo, hi) / 20.0))
-    return None if mate == name else (mate, comb, gain)
+    if mate == name:
+        return None
+    return (mate, comb, gain) if yaw is None else (mate, comb, gain, phi)
 
 
 def merge_labels(a: dict, b: dict):
@@ -305,7 +401,14 @@ class RotationAug:
     def __init__(self, params: dict, is_valid: bool):
         self.apply_augment = bool(params["aug_config"]["rotation_augment"]) and not is_valid
 
-    def augment(self, audio, label, comb_no=None):
+    def augment(self, audio, label, comb_no=None, phi=None):
+        """phi (degrees, optional): the yaw applied after the combination -- on its own where the rotation is off."""
+        if phi is not None:
+            comb = None
+            if self.apply_augment:
+                comb = int(random.uniform(0, 16)) if comb_no is None else comb_no
+                label = rotate_labels(label, comb)
+            return rotate_audio_yaw(audio.view(1, -1, 4), [comb], [phi]).view_as(audio), yaw_labels(label, phi)
         if not self.apply_augment:
             return audio, label
         if comb_no is None:

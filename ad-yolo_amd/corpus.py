@@ -15,11 +15,14 @@ rotates and encodes the labels on the host and stages every batch over PCIe.  He
   (audio, rotated; with ``aug_config.channel_swap_augment`` ``adyolo_corpus_gather_mic``: MIC capsules permuted) and
   ``adyolo_corpus_yolo_labels`` (the AD-YOLO rows into a fixed-capacity target, padding b = -1).  No host sync.  With
   ``aug_config.time_mix_augment`` the draws of ``augmentations.draw_time_mix`` follow each item's, a second table of mates rides
-  in the same copy and the ``_mix`` calls sum the mate's window in and unite the labels (``augmentations.merge_labels``).
+  in the same copy and the ``_mix`` calls sum the mate's window in and unite the labels (``augmentations.merge_labels``).  With
+  ``aug_config.yaw_rotation_augment`` (FOA) every item and mate row carries its own yaw in word 7 (``augmentations.draw_yaw``,
+  right after the combination draw) and the ``_yaw`` calls turn the audio and move the azimuths after the combination.
 * ``ClasswiseDeviceCorpus`` (device half, ``seddoa | masked-seddoa | accdoa | adpit``): the same split, sampling, draws and
   gather; the labels are ``adyolo_corpus_classwise_labels``, the dense ``ClasswiseLabelEncoder`` targets of the batch written
   whole, from a float32 table of every event's direction vector under no rotation and the 16 FOA combinations (``xyz_table``,
-  built once on the host with the host's own functions: 204 bytes per event).
+  built once on the host with the host's own functions: 204 bytes per event).  With the yaw rotation x and y come from two
+  whole-degree tables instead (``ops.corpus_yaw_xyz_tables``), so the split's angles must then be whole degrees.
 
 Parity: the same audio bit for bit and the same rows in the same order (or the same dense targets bit for bit) as the host
 path iterated in the main process (``num_workers=0``); with DataLoader workers the host path's draws happen in per-worker streams.
@@ -369,13 +372,17 @@ class _CorpusBase:
     def _train_setup(self, params):
         """The training corpora: the augmentations, the batch shape and the first draw of files (``FoaDataset.__init__``)."""
         from .augmentations import (MIC_SWAP_COMBS, SpecAug, channel_swap_enabled, feature_aug_config, mic_swap_source,
-                                    time_mix_config)
+                                    time_mix_config, yaw_config)
         hc = self.host
         self.rotate = bool(params.get("aug_config", {}).get("rotation_augment", False))
+        # yaw rotation (FOA only; ValueError: MIC audio or a bad yaw_step_deg): None or the step, and the gather's table
+        self.yaw = yaw_config(params)
+        self.yaw_tab = ops.corpus_yaw_table(self.device) if self.yaw is not None else None
         # MIC channel swap (ValueError: audio_format is not 'mic', or rotation_augment is on as well): the gather's table
         self.swap = channel_swap_enabled(params)
         self.mic_src = ops.corpus_mic_table({k: mic_swap_source(k) for k in MIC_SWAP_COMBS}) if self.swap else None
         self.specaug = SpecAug(params, False)
+        self._mix_yaw = {} if self.yaw is None else {"yaw": self.yaw}     # what draw_time_mix is told of it: nothing when off
         self.mix = time_mix_config(params)    # time-domain mixing: None or (prob, gain lo, gain hi) (ValueError: a bad key)
         self.feat_aug = feature_aug_config(params)        # frequency shift / cutout: None or the parsed keys (ValueError: a bad key)
         self.batch_size = int(params["train_config"]["batch_size"])
@@ -425,12 +432,14 @@ class _CorpusBase:
     def draw(self, indices):
         """The host half of a batch: ``FoaDataset.__getitem__``'s ``random`` draws item by item (rotation or channel swap, then
         SpecAug) and the item table -> (items int64 (B, 8), spec int32 (B, 2, 4) or None), host arrays; with
+        ``aug_config.yaw_rotation_augment`` each row's yaw (``augmentations.draw_yaw``, right after its combination draw) is word 7
+        of the row, in whole degrees; with
         ``aug_config.freq_shift_augment`` / ``cutout_augment`` spec is int32 (B, 4, 4): the SpecAug rows (zeros with ``spec_augment``
         off), the cutout row, {shift, 0, 0, 0} (``augmentations.draw_feature_aug``, the last draws of every item).  With
         ``aug_config.time_mix_augment`` the item's mixing draws follow (``augmentations.draw_time_mix``) and a third element is
         returned: mates int64 (B, 8), the mate chunk as an item row with its own combination and the float32 bits of the gain in
         word 6, offset -1 where the item is unmixed."""
-        from .augmentations import MIC_SWAP_COMBS, draw_feature_aug, draw_time_mix
+        from .augmentations import MIC_SWAP_COMBS, draw_feature_aug, draw_time_mix, draw_yaw
         from .features import HOP, N_MELS
         names = [self.filelist[i] for i in indices]
         b = len(names)
@@ -450,18 +459,19 @@ class _CorpusBase:
                 comb = int(self._random.uniform(0, 16))                       # augmentations.py:76, as in __getitem__
             elif self.swap:
                 comb = MIC_SWAP_COMBS[int(self._random.uniform(0, 8))]        # as in __getitem__: one draw
+            phi = draw_yaw(self._random, self.yaw) if self.yaw is not None else 0
             if self.specaug.apply_augment:
                 spec[j, :2] = self.specaug.draw_groups(1, self.n_samples // HOP, N_MELS, 2)[0].numpy()
-            items[j] = (off, f_off, ev_lo, ev_n, comb, rec, 0, 0)
+            items[j] = (off, f_off, ev_lo, ev_n, comb, rec, 0, phi)
             if mates is not None:
                 drawn = draw_time_mix(self._random, self.mix, self.total_filelist, name,
-                                      "rotate" if self.rotate else "swap" if self.swap else None)
+                                      "rotate" if self.rotate else "swap" if self.swap else None, **self._mix_yaw)
                 if drawn is not None:
-                    mate, m_comb, gain = drawn
+                    mate, m_comb, gain = drawn[:3]
                     m_rec, m_off, m_f_off = self.host.chunks[mate]
                     m_lo, m_n = self.host.chunk_events[mate]
                     mates[j] = (m_off, m_f_off, m_lo, m_n, -1 if m_comb is None else m_comb, m_rec,
-                                int(np.float32(gain).view(np.uint32)), 0)
+                                int(np.float32(gain).view(np.uint32)), drawn[3] if self.yaw is not None else 0)
             if self.feat_aug is not None:
                 spec[j, 2], spec[j, 3, 0] = draw_feature_aug(self._random, self.feat_aug, self.n_samples // HOP, N_MELS)
         if mates is not None:
@@ -518,8 +528,13 @@ class _CorpusBase:
         return dev_items, dev_mates, dev_spec, audio, target
 
     def _gather(self, dev_items, audio, dev_mates=None):
-        """The audio of a batch: FOA-rotated, or with ``aug_config.channel_swap_augment`` the MIC capsules permuted; with mates
+        """The audio of a batch: FOA-rotated (with ``aug_config.yaw_rotation_augment``: and yawed, each row by its word 7), or with
+        ``aug_config.channel_swap_augment`` the MIC capsules permuted; with mates
         (``aug_config.time_mix_augment``) each mate's window, under its own combination, summed in by the same pass."""
+        if self.yaw is not None:
+            if dev_mates is not None:
+                return ops.corpus_gather_yaw_mix(self.pcm, dev_items, dev_mates, self.rot, self.yaw_tab, audio, self.status)
+            return ops.corpus_gather_yaw(self.pcm, dev_items, self.rot, self.yaw_tab, audio, self.status)
         if dev_mates is not None:
             return ops.corpus_gather_mix(self.pcm, dev_items, dev_mates, self.rot, self.mic_src, audio, self.status)
         if self.swap:
@@ -562,6 +577,9 @@ class DeviceCorpus(_CorpusBase):
             cap = self._round_cap(self.batch_size * (2 if self.mix is not None else 1) * self.max_events * self.cells)
         self.cap = int(cap)
         self.rows = None                 # int32 word on the device: the row count of the last batch
+        # the label calls (plain, mixed) of this corpus: with the yaw rotation the forms that move each row's azimuths by word 7
+        self._labels = (ops.corpus_yolo_labels, ops.corpus_yolo_labels_mix) if self.yaw is None else \
+            (ops.corpus_yolo_labels_yaw, ops.corpus_yolo_labels_yaw_mix)
 
     def target_shape(self, batch):
         """The target of every batch: (cap, 7) rows, whatever the batch size."""
@@ -575,9 +593,9 @@ class DeviceCorpus(_CorpusBase):
         self.rows = torch.empty(1, dtype=torch.int32, device=self.device)
         self._gather(dev_items, audio, dev_mates)
         if dev_mates is None:
-            ws_words, labels, tables = ops.corpus_labels_workspace_words, ops.corpus_yolo_labels, (dev_items,)
+            ws_words, labels, tables = ops.corpus_labels_workspace_words, self._labels[0], (dev_items,)
         else:                                    # time-domain mixing: both sources' audio summed, their rows in merged order
-            ws_words, labels, tables = ops.corpus_labels_mix_workspace_words, ops.corpus_yolo_labels_mix, (dev_items, dev_mates)
+            ws_words, labels, tables = ops.corpus_labels_mix_workspace_words, self._labels[1], (dev_items, dev_mates)
         ws = torch.empty(max(1, ws_words(b, self.max_events)), dtype=torch.int32, device=self.device)
         labels(self.events, *tables, self.max_events, self.n_label_frames, self.bounds, self.grid, self.rot, ws, target, self.rows,
                self.status)
@@ -614,6 +632,16 @@ class ClasswiseDeviceCorpus(_CorpusBase):
             np.zeros((1, ops.CORPUS_XYZ_SLOTS, 3), dtype=np.float32)
         self.xyz = torch.from_numpy(xyz).to(self.device)
         self._train_setup(params)
+        self.yaw_xyz = None
+        if self.yaw is not None:         # x and y of a yawed event come from whole-degree tables: the split must have no other angle
+            ang = hc.events[:, 3:5]
+            frac = np.flatnonzero(~((ang == np.round(ang)).all(1) & (np.abs(ang[:, 0]) <= 180) & (np.abs(ang[:, 1]) <= 90)))
+            if frac.size:
+                r = int(np.searchsorted(hc.ev_start, frac[0], "right")) - 1
+                raise ValueError("ClasswiseDeviceCorpus: aug_config.yaw_rotation_augment needs whole-degree labels, and recording "
+                                 "%s has an event at azimuth %r, elevation %r (DeviceCorpus and FoaDataset take any angles)"
+                                 % (hc.rec_names[r], float(ang[frac[0], 0]), float(ang[frac[0], 1])))
+            self.yaw_xyz = ops.corpus_yaw_xyz_tables(self.device)
 
     def nbytes(self):
         return super().nbytes() + int(self.xyz.numel() * 4)
@@ -631,6 +659,11 @@ class ClasswiseDeviceCorpus(_CorpusBase):
             labels, tables = ops.corpus_classwise_labels, (dev_items,)
         else:                                    # time-domain mixing: both sources' audio summed, the targets of the merged events
             labels, tables = ops.corpus_classwise_labels_mix, (dev_items, dev_mates)
+        if self.yaw is not None:                 # yaw rotation: x and y from the whole-degree tables, each row's yaw in word 7
+            labels = ops.corpus_classwise_labels_yaw if dev_mates is None else ops.corpus_classwise_labels_yaw_mix
+            labels(self.events, *tables, self.xyz, self.rot, self.yaw_xyz, self.max_events, self.n_label_frames, self.nb_classes,
+                   self.loss_nm, target, self.status)
+            return audio, target, dev_spec
         labels(self.events, *tables, self.xyz, self.max_events, self.n_label_frames, self.nb_classes, self.loss_nm, target,
                self.status)
         return audio, target, dev_spec

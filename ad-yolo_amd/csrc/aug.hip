@@ -312,6 +312,36 @@ extern "C" int adyolo_foa_rotate(const float *audio, float *out, const float *cf
     return adyolo::check_launch("foa_rotate");
 }
 
+// ---- FOA rotation followed by a yaw about the vertical axis (aug_config.yaw_rotation_augment, the host-fed path): the work of
+// foa_rotate_kernel, then yaw_apply, per clip from cfg[b] = {sy, sz, sx, swap, cos, sin}
+namespace adyolo {
+__global__ __launch_bounds__(256) void foa_rotate_yaw_kernel(const float4 *__restrict__ x, float4 *__restrict__ y,
+                                                             const float *__restrict__ cfg, long n_per_clip) {
+    const int b = blockIdx.y;
+    const float sy = cfg[b * 6 + 0], sz = cfg[b * 6 + 1], sx = cfg[b * 6 + 2];
+    const bool swap = cfg[b * 6 + 3] != 0.f;
+    const float c = cfg[b * 6 + 4], s = cfg[b * 6 + 5];
+    const float4 *src = x + (size_t)b * n_per_clip;
+    float4 *dst = y + (size_t)b * n_per_clip;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n_per_clip; i += (long)gridDim.x * blockDim.x) {
+        const float4 v = src[i];
+        const float yy = v.y * sy, zz = v.z * sz, xx = v.w * sx;
+        dst[i] = yaw_apply(swap ? make_float4(v.x, xx, zz, yy) : make_float4(v.x, yy, zz, xx), c, s);
+    }
+}
+}  // namespace adyolo
+
+extern "C" int adyolo_foa_rotate_yaw(const float *audio, float *out, const float *cfg, int B, long n_samples, void *stream) {
+    ADYOLO_REQUIRE(audio && out && cfg && B > 0 && B < 65536 && n_samples > 0, ADYOLO_EINVAL, "foa_rotate_yaw: bad arguments");
+    ADYOLO_REQUIRE(((uintptr_t)audio & 15) == 0 && ((uintptr_t)out & 15) == 0 && ((uintptr_t)cfg & 3) == 0, ADYOLO_EINVAL,
+                   "foa_rotate_yaw: misaligned buffers (audio / out 16 bytes, cfg 4 bytes)");
+    long g = (n_samples + 255) / 256;
+    if (g > 2048) g = 2048;
+    hipLaunchKernelGGL(adyolo::foa_rotate_yaw_kernel, dim3((unsigned)g, (unsigned)B), dim3(256), 0, adyolo::as_stream(stream),
+                       (const float4 *)audio, (float4 *)out, cfg, n_samples);
+    return adyolo::check_launch("foa_rotate_yaw");
+}
+
 // ---- MIC channel-swap augmentation on raw audio (augmentations.swap_audio): per clip a permutation of the four capsules,
 // out[b][i][j] = audio[b][i][src[b][j] & 3].  One 16-byte load and one 16-byte store per frame; the clip's four selectors are
 // uniform over the workgroup (blockIdx.y = clip: scalar loads, once), so each output word is three bit selects between the

@@ -90,6 +90,14 @@ __device__ __forceinline__ float4 mix_add(const float4 a, const float4 m, const 
     return make_float4(a.x + g * m.x, a.y + g * m.y, a.z + g * m.z, a.w + g * m.w);
 }
 
+// FOA yaw rotation (augmentations yaw_rotation_augment) of one frame (W, Y, Z, X) about the vertical axis: Y' = Y c + X s,
+// X' = X c - Y s, every product and every sum rounded to float32 (no FMA), which is what the NumPy float32 definition gives.
+__device__ __forceinline__ float4 yaw_apply(const float4 v, const float c, const float s) {
+#pragma clang fp contract(off)
+    const float yc = v.y * c, xs = v.w * s, xc = v.w * c, ys = v.y * s;
+    return make_float4(v.x, yc + xs, v.z, xc - ys);
+}
+
 // Sum `nparts` partial rows of a [nparts][ld] fp32 array for 32 consecutive columns starting at c0, in double.
 // Call from a 256-thread workgroup (32 columns x 8 part-groups); returns the column total in threads with
 // (threadIdx.x >> 5) == 0 (valid for c0 + (threadIdx.x & 31) < C).  `red` = 256 doubles of LDS.

@@ -11,19 +11,24 @@
 //   corpus_gather_kernel<Tab, MIX>   one pass int16 window -> float32 ``x / 32768 + 1e-8``, two frames per iteration from one
 //                                    16-byte load (two 8-byte loads when the window starts on an odd frame), two 16-byte stores.
 //                                    Tab = CorpusRot: FOA channels rotated; CorpusMicSrc: the four MIC capsules permuted
-//                                    (channel swap).  MIX: the mate's window, under its own combination, added as a + g * m
+//                                    (channel swap); CorpusYaw: CorpusRot, then a yaw about the vertical axis by the whole angle
+//                                    in word 7 of the row.  MIX: the mate's window, under its own combination (and yaw), added
+//                                    as a + g * m
 //   corpus_count_scan_kernel<MIX>    one workgroup: rows per lane -- (item, event), or (item, source, event) in merged order --
 //                                    exclusive scan, the total and the overflow bit
 //   corpus_rows_kernel<MIX>          the rows [b, t, gi, gj, cls, U, V] at their scanned offsets, b = -1 in the rest of the capacity
 //   corpus_classwise_kernel<MIX>     the dense SEDDOA / ACCDOA / ADPIT targets (datasets.ClasswiseLabelEncoder): per tile of label
 //                                    frames, each frame's event range per source, the event each (frame, class) output takes,
 //                                    then every output element written once
+// The label kernels have a second compile-time parameter YAW (aug_config.yaw_rotation_augment): each row's azimuths moved by its
+// word 7 after the combination (augmentations.yaw_labels); YAW false is the code without it.
 // Windowed inference (corpus.py InferDeviceCorpus, test.py infer_epoch_corpus) reads the same stream through a window table:
 //   corpus_gather_windows_kernel  the gather without rotation, the frames past a window's valid count int16 zero, never read
 //   decode_stitch_kernel          each window's kept decoded frames copied into one contiguous run per pass
 // The AD-YOLO label arithmetic is done in double, as the host does it (augmentations.rotate_labels on Python floats,
 // datasets.YoloLabelEncoder.encode_events in float64); only the written row is rounded to float32.  The class-wise kernel does
-// no arithmetic at all: the direction vectors come from a table the host builds with its own functions (corpus.xyz_table).
+// no arithmetic at all: the direction vectors come from a table the host builds with its own functions (corpus.xyz_table); with
+// YAW x and y are one double product of two host-built table entries each (CorpusYawXyz), z still the table's.
 #include "common.hpp"
 
 namespace adyolo {
@@ -35,6 +40,17 @@ struct CorpusRot {                     // ADYOLO_CORPUS_ROT_WORDS floats per com
 struct CorpusMicSrc {                  // one word per combination (adyolo_hip.h), passed by value (capturable)
     unsigned w[16];
 };
+
+// FOA rotation followed by a yaw (aug_config.yaw_rotation_augment): the combinations of CorpusRot, and the device table
+// [360][2] = {cos, sin} of the whole-degree yaws -180 .. 179 (ops.corpus_yaw_table: augmentations.yaw_cos_sin); a row's yaw is
+// its word ADYOLO_CORPUS_YAW_WORD, in whole degrees
+struct CorpusYaw {
+    CorpusRot rot;
+    const float2 *cs;
+};
+
+// a row's yaw is legal: whole degrees in [-180, 180)
+__device__ __forceinline__ bool corpus_yaw_ok(int64_t phi) { return phi >= -180 && phi < 180; }
 
 __device__ __forceinline__ float4 pcm_rot(int lo, int hi, float sy, float sz, float sx, bool swap) {
     // the arithmetic of pcm16_to_f32_kernel (csrc/aug.hip) then foa_rotate_kernel (csrc/aug.hip), element for element
@@ -64,6 +80,7 @@ struct CorpusSrc {
     float sy, sz, sx;
     bool swap;
     unsigned sel_lo, sel_hi;
+    float c, s;                        // CorpusYaw only: the cosine and sine of the row's yaw
 };
 
 __device__ __forceinline__ bool gather_source(const CorpusRot &rot, int64_t comb, CorpusSrc &s) {
@@ -85,11 +102,30 @@ __device__ __forceinline__ bool gather_source(const CorpusMicSrc &tab, int64_t c
     return w != ADYOLO_MIC_SWAP_NONE;
 }
 
+__device__ __forceinline__ bool gather_source(const CorpusYaw &tab, int64_t comb, CorpusSrc &s) {
+    return gather_source(tab.rot, comb, s);
+}
+
+// the part of a source's conversion that comes from the rest of its row: the yaw (CorpusYaw; false outside [-180, 180))
+__device__ __forceinline__ bool gather_row(const CorpusRot &, const int64_t *__restrict__, CorpusSrc &) { return true; }
+__device__ __forceinline__ bool gather_row(const CorpusMicSrc &, const int64_t *__restrict__, CorpusSrc &) { return true; }
+__device__ __forceinline__ bool gather_row(const CorpusYaw &tab, const int64_t *__restrict__ row, CorpusSrc &s) {
+    const int64_t phi = row[ADYOLO_CORPUS_YAW_WORD];
+    if (!corpus_yaw_ok(phi)) return false;
+    const float2 cs = tab.cs[phi + 180];
+    s.c = cs.x;
+    s.s = cs.y;
+    return true;
+}
+
 __device__ __forceinline__ float4 gather_conv(const CorpusRot &, int lo, int hi, const CorpusSrc &s) {
     return pcm_rot(lo, hi, s.sy, s.sz, s.sx, s.swap);
 }
 __device__ __forceinline__ float4 gather_conv(const CorpusMicSrc &, int lo, int hi, const CorpusSrc &s) {
     return pcm_swap(lo, hi, s.sel_lo, s.sel_hi);
+}
+__device__ __forceinline__ float4 gather_conv(const CorpusYaw &, int lo, int hi, const CorpusSrc &s) {
+    return yaw_apply(pcm_rot(lo, hi, s.sy, s.sz, s.sx, s.swap), s.c, s.s);
 }
 
 // an item or mate row as a window of the stream: false when its offset or combination is outside the corpus
@@ -97,7 +133,7 @@ template <class Tab>
 __device__ __forceinline__ bool gather_window(const int64_t *__restrict__ row, long n_total, long n, const Tab &tab,
                                               CorpusSrc &s) {
     const int64_t off = row[0], comb = row[4];
-    return off >= 0 && off <= n_total - n && comb < 16 && gather_source(tab, comb, s);
+    return off >= 0 && off <= n_total - n && comb < 16 && gather_source(tab, comb, s) && gather_row(tab, row, s);
 }
 
 // frames 2 i and 2 i + 1 of a window: one 16-byte load where the window starts on an even frame, two 8-byte loads where not
@@ -154,7 +190,7 @@ __global__ __launch_bounds__(256) void corpus_gather_kernel(const int16_t *__res
     }
     float4 *dst = out + (size_t)b * n;
     const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, nth = (long)gridDim.x * blockDim.x;
-    CorpusSrc ca, cm = {1.f, 1.f, 1.f, false, 0u, 0u};
+    CorpusSrc ca, cm = {1.f, 1.f, 1.f, false, 0u, 0u, 1.f, 0.f};
     float g = 0.f;
     bool ok = gather_window(it, n_total, n, tab, ca);
     if (ok && mixed) {
@@ -190,29 +226,22 @@ struct CorpusLabelGeom {
     long n_events, cap;
 };
 
-// an item or mate row as a range of the event table: true when the range or the combination is outside the corpus
+// an item or mate row as a range of the event table: true when the range or the combination -- with YAW, or the yaw -- is
+// outside the corpus
+template <bool YAW = false>
 __device__ __forceinline__ bool corpus_row_bad(const int64_t *__restrict__ row, int max_events, long n_events) {
     const int64_t ev_lo = row[2], ev_n = row[3], comb = row[4];
+    if (YAW && !corpus_yaw_ok(row[ADYOLO_CORPUS_YAW_WORD])) return true;
     return ev_lo < 0 || ev_n < 0 || ev_n > max_events || ev_lo > n_events - ev_n || comb >= 16;
 }
 
-// Event e of the item (or mate) row ``it``: its frame relative to the row's window, the rotated angles and its az / el cell
-// masks.  Returns the number of rows it produces (0: no event, or its frame is past the label frames).
-__device__ int corpus_event_at(const double *__restrict__ events, const int64_t *__restrict__ it,
-                               const double *__restrict__ bounds, const CorpusRot &rot, const CorpusLabelGeom &g, int e,
-                               int &frame, int &cls, double &az, double &el, unsigned long long &az_bits,
-                               unsigned long long &el_bits, bool &bad) {
-    const int64_t frame_off = it[1], ev_lo = it[2], ev_n = it[3], comb = it[4];
-    bad = corpus_row_bad(it, g.max_events, g.n_events);
-    if (bad || e >= ev_n) return 0;
-    const double *ev = events + (size_t)(ev_lo + e) * 4;
-    const int64_t fr = (int64_t)ev[0] - frame_off;
-    if (fr < 0 || fr >= g.n_label_frames) return 0;              // get_yolo_label: frame_idx < nb_label_frames
-    frame = (int)fr;
-    cls = (int)ev[1];
-    double a = ev[2], v = ev[3];
-    if (comb >= 0) {                                              // augmentations.rotate_labels
+// An event's angles as the host moves them: augmentations.rotate_labels under the row's combination (comb < 0: none), then
+// with YAW augmentations.yaw_labels by the row's yaw (whole degrees, legal: corpus_row_bad), all in double, nothing contracted.
+template <bool YAW>
+__device__ __forceinline__ void corpus_move_angles(const CorpusRot &rot, const int64_t *__restrict__ row, double &a, double &v) {
 #pragma clang fp contract(off)
+    const int64_t comb = row[4];
+    if (comb >= 0) {                                              // augmentations.rotate_labels
         a = a * (double)rot.c[comb][4] + (double)rot.c[comb][5];
         if (a < -180.0)
             a += 360.0;
@@ -220,6 +249,32 @@ __device__ int corpus_event_at(const double *__restrict__ events, const int64_t 
             a -= 360.0;
         v = v * (double)rot.c[comb][6];
     }
+    if (YAW) {                                                    // augmentations.yaw_labels
+        a = a + (double)row[ADYOLO_CORPUS_YAW_WORD];
+        if (a < -180.0)
+            a += 360.0;
+        else if (a > 180.0)
+            a -= 360.0;
+    }
+}
+
+// Event e of the item (or mate) row ``it``: its frame relative to the row's window, the rotated angles and its az / el cell
+// masks.  Returns the number of rows it produces (0: no event, or its frame is past the label frames).
+template <bool YAW>
+__device__ int corpus_event_at(const double *__restrict__ events, const int64_t *__restrict__ it,
+                               const double *__restrict__ bounds, const CorpusRot &rot, const CorpusLabelGeom &g, int e,
+                               int &frame, int &cls, double &az, double &el, unsigned long long &az_bits,
+                               unsigned long long &el_bits, bool &bad) {
+    const int64_t frame_off = it[1], ev_lo = it[2], ev_n = it[3];
+    bad = corpus_row_bad<YAW>(it, g.max_events, g.n_events);
+    if (bad || e >= ev_n) return 0;
+    const double *ev = events + (size_t)(ev_lo + e) * 4;
+    const int64_t fr = (int64_t)ev[0] - frame_off;
+    if (fr < 0 || fr >= g.n_label_frames) return 0;              // get_yolo_label: frame_idx < nb_label_frames
+    frame = (int)fr;
+    cls = (int)ev[1];
+    double a = ev[2], v = ev[3];
+    corpus_move_angles<YAW>(rot, it, a, v);
     if (a == 180.0) a = -180.0;                                  // YoloLabelEncoder.encode_events
     const double *az_lb = bounds, *az_ub = bounds + g.Gaz, *el_lb = bounds + 2 * g.Gaz, *el_ub = el_lb + g.Gel;
     az_bits = 0ull;
@@ -247,7 +302,7 @@ __device__ int corpus_event_at(const double *__restrict__ events, const int64_t 
 // it: those with a smaller window-relative frame for an item lane, a smaller or equal one for a mate lane (a binary search).
 // The lanes without an event take the places behind the events, so that every place of the item's 2 max_events is written
 // once.  An item whose own row or whose mate row is bad has no rows at all.
-template <bool MIX>
+template <bool MIX, bool YAW>
 __device__ int corpus_lane(const double *__restrict__ events, const int64_t *__restrict__ items,
                            const int64_t *__restrict__ mates, const double *__restrict__ bounds, const CorpusRot &rot,
                            const CorpusLabelGeom &g, long lane, int &b, long &at, int &frame, int &cls, double &az, double &el,
@@ -258,12 +313,12 @@ __device__ int corpus_lane(const double *__restrict__ events, const int64_t *__r
     const int64_t *it = items + (size_t)b * ADYOLO_CORPUS_ITEM_WORDS;
     if (!MIX) {
         at = lane;
-        return corpus_event_at(events, it, bounds, rot, g, r, frame, cls, az, el, az_bits, el_bits, bad);
+        return corpus_event_at<YAW>(events, it, bounds, rot, g, r, frame, cls, az, el, az_bits, el_bits, bad);
     }
     const int src = r >= me ? 1 : 0, e = r - src * me;
     const int64_t *mt = mates + (size_t)b * ADYOLO_CORPUS_ITEM_WORDS;
     const bool has_mate = mt[0] != -1;
-    bad = corpus_row_bad(it, me, g.n_events) || (has_mate && corpus_row_bad(mt, me, g.n_events));
+    bad = corpus_row_bad<YAW>(it, me, g.n_events) || (has_mate && corpus_row_bad<YAW>(mt, me, g.n_events));
     const int n_a = bad ? 0 : (int)it[3], n_m = bad || !has_mate ? 0 : (int)mt[3];
     if (e >= (src ? n_m : n_a)) {
         at = lane - r + (src ? me + e : n_m + e);
@@ -284,14 +339,14 @@ __device__ int corpus_lane(const double *__restrict__ events, const int64_t *__r
     }
     at = lane - r + e + lo;
     bool own_bad;
-    return corpus_event_at(events, own, bounds, rot, g, e, frame, cls, az, el, az_bits, el_bits, own_bad);
+    return corpus_event_at<YAW>(events, own, bounds, rot, g, e, frame, cls, az, el, az_bits, el_bits, own_bad);
 }
 
 constexpr int CORPUS_SCAN_THREADS = 1024;
 
 // one workgroup: ws[at] = exclusive offset of the rows of the lane decoded to ``at``; count[0] = total rows; status |= overflow /
 // bad item
-template <bool MIX>
+template <bool MIX, bool YAW>
 __global__ __launch_bounds__(CORPUS_SCAN_THREADS) void corpus_count_scan_kernel(
     const double *__restrict__ events, const int64_t *__restrict__ items, const int64_t *__restrict__ mates,
     const double *__restrict__ bounds, CorpusRot rot, CorpusLabelGeom g, int *ws, int *__restrict__ count,
@@ -312,7 +367,7 @@ __global__ __launch_bounds__(CORPUS_SCAN_THREADS) void corpus_count_scan_kernel(
         double az, el;
         unsigned long long ab, eb;
         bool bad;
-        const int c = corpus_lane<MIX>(events, items, mates, bounds, rot, g, s, b, at, frame, cls, az, el, ab, eb, bad);
+        const int c = corpus_lane<MIX, YAW>(events, items, mates, bounds, rot, g, s, b, at, frame, cls, az, el, ab, eb, bad);
         bad_here |= bad;
         ws[at] = c;
         sum += c;                                                // plain: at == s, so this is the chunk's sum
@@ -349,7 +404,7 @@ __global__ __launch_bounds__(CORPUS_SCAN_THREADS) void corpus_count_scan_kernel(
 
 // grid-stride over the lanes (rows of each event, cells in (gi, gj) order) and over the capacity (b = -1 past the total);
 // column 0 of a row is the item, whichever source the event comes from
-template <bool MIX>
+template <bool MIX, bool YAW>
 __global__ __launch_bounds__(256) void corpus_rows_kernel(const double *__restrict__ events, const int64_t *__restrict__ items,
                                                           const int64_t *__restrict__ mates,
                                                           const double *__restrict__ bounds, CorpusRot rot, CorpusLabelGeom g,
@@ -363,7 +418,7 @@ __global__ __launch_bounds__(256) void corpus_rows_kernel(const double *__restri
         double az, el;
         unsigned long long ab, eb;
         bool bad;
-        const int c = corpus_lane<MIX>(events, items, mates, bounds, rot, g, s, b, at, frame, cls, az, el, ab, eb, bad);
+        const int c = corpus_lane<MIX, YAW>(events, items, mates, bounds, rot, g, s, b, at, frame, cls, az, el, ab, eb, bad);
         if (c == 0) continue;
         long r = ws[at];
         const float fb = (float)b, ft = (float)frame, fc = (float)cls, fu = (float)az, fv = (float)el;
@@ -402,11 +457,40 @@ struct CorpusClasswiseGeom {
 // class c in frame t0 + i, its first three events} (ADPIT) or {its last event, ...} (SEDDOA / ACCDOA), -1 where there is none.
 // A (frame, class) output picks over the item's range, then the mate's (the order of merge_labels); every picked event carries
 // its source, because its direction vector is read from the xyz slot of its own source's combination.
-template <bool MIX>
+//
+// YAW (aug_config.yaw_rotation_augment): z still comes from the xyz slot (a yaw does not move it), x and y from two host-built
+// double tables indexed by the moved whole-degree angles (corpus_move_angles): yaw.az [361][2] = {cos, sin} of azimuth -180 ..
+// 180, yaw.el [181] = cos of elevation -90 .. 90; x = (float)(cos_az * cos_el), y = (float)(sin_az * cos_el), one double
+// product each, rounded once -- what the host encoder's float64 arrays give as float32.  YAW false: ``yaw`` is not read.
+struct CorpusYawXyz {
+    CorpusRot rot;
+    const double *az, *el;
+};
+struct CorpusNoYawXyz {};              // what the kernel takes in its place without YAW: nothing
+template <bool YAW> struct CorpusYawXyzArg { typedef CorpusNoYawXyz type; };
+template <> struct CorpusYawXyzArg<true> { typedef CorpusYawXyz type; };
+
+__device__ __forceinline__ float corpus_yaw_xy(const CorpusNoYawXyz &, const double *__restrict__, const int64_t *__restrict__,
+                                               int) {
+    return 0.f;
+}
+
+__device__ __forceinline__ float corpus_yaw_xy(const CorpusYawXyz &yaw, const double *__restrict__ ev,
+                                               const int64_t *__restrict__ row, int k) {
+#pragma clang fp contract(off)
+    double a = ev[2], v = ev[3];
+    corpus_move_angles<true>(yaw.rot, row, a, v);
+    // whole degrees inside the tables (the host corpus refuses a split with any other angle); anything else reads entry 0
+    const int ia = a >= -180.0 && a <= 180.0 ? (int)a + 180 : 0, ie = v >= -90.0 && v <= 90.0 ? (int)v + 90 : 0;
+    return (float)(yaw.az[2 * ia + k] * yaw.el[ie]);
+}
+
+template <bool MIX, bool YAW>
 __global__ __launch_bounds__(CW_THREADS) void corpus_classwise_kernel(const double *__restrict__ events,
                                                                       const float *__restrict__ xyz,
                                                                       const int64_t *__restrict__ items,
                                                                       const int64_t *__restrict__ mates, CorpusClasswiseGeom g,
+                                                                      typename CorpusYawXyzArg<YAW>::type yaw,
                                                                       float *__restrict__ target, int *__restrict__ status) {
     constexpr int NS = MIX ? 2 : 1;
     extern __shared__ int pick[];                // [CW_FRAMES][C][4]
@@ -427,7 +511,7 @@ __global__ __launch_bounds__(CW_THREADS) void corpus_classwise_kernel(const doub
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
         if (s >= ns) break;
-        bad |= corpus_row_bad(rows[s], g.max_events, g.n_events);
+        bad |= corpus_row_bad<YAW>(rows[s], g.max_events, g.n_events);
         const int64_t comb = rows[s][4];
         frame_off[s] = rows[s][1];
         ev_lo[s] = rows[s][2];
@@ -530,6 +614,11 @@ __global__ __launch_bounds__(CW_THREADS) void corpus_classwise_kernel(const doub
             const int e = adpit ? (q[0] >= lo_cnt && q[0] <= hi_cnt ? q[1 + j] : -1) : q[0];
             const size_t sl = MIX && ((e >> CW_SRC_BIT) & 1) ? slot[NS - 1] : slot[0];
             const size_t idx = MIX ? (size_t)(e & ((1 << CW_SRC_BIT) - 1)) : (size_t)e;
+            if (YAW && e >= 0 && (k == 0 || k == 1)) {            // x, y of a yawed event: from its moved angles
+                const bool mate = MIX && ((e >> CW_SRC_BIT) & 1);
+                dst[(size_t)i * g.row + r] = corpus_yaw_xy(yaw, events + idx * 4, mate ? rows[NS - 1] : rows[0], k);
+                continue;
+            }
             dst[(size_t)i * g.row + r] = e < 0 ? 0.f : k < 0 ? 1.f : xyz[(idx * ADYOLO_CORPUS_XYZ_SLOTS + sl) * 3 + k];
         }
     }
@@ -642,7 +731,7 @@ static int corpus_gather_launch(const char *name, const int16_t *pcm, long n_tot
     return check_launch(name);
 }
 
-template <bool MIX>
+template <bool MIX, bool YAW = false>
 static int corpus_yolo_labels_launch(const char *name, const double *events, long n_events, const int64_t *items,
                                      const int64_t *mates, int B, int max_events, int n_label_frames, const double *grid_bounds,
                                      int Gaz, int Gel, const float *rot_host, int *ws, float *target, long cap, int *count,
@@ -664,22 +753,23 @@ static int corpus_yolo_labels_launch(const char *name, const double *events, lon
     g.B = B; g.max_events = max_events; g.n_label_frames = n_label_frames; g.Gaz = Gaz; g.Gel = Gel;
     g.n_events = n_events; g.cap = cap;
     hipStream_t st = as_stream(stream);
-    hipLaunchKernelGGL(corpus_count_scan_kernel<MIX>, dim3(1), dim3(CORPUS_SCAN_THREADS), 0, st, events, items, mates,
+    hipLaunchKernelGGL((corpus_count_scan_kernel<MIX, YAW>), dim3(1), dim3(CORPUS_SCAN_THREADS), 0, st, events, items, mates,
                        grid_bounds, rot, g, ws, count, status);
     int rc = check_launch(name);
     if (rc) return rc;
     long work = cap > lanes ? cap : lanes;
     int gx = cdiv(work, 256L * 4);
     gx = gx < 1 ? 1 : (gx > 1024 ? 1024 : gx);
-    hipLaunchKernelGGL(corpus_rows_kernel<MIX>, dim3((unsigned)gx), dim3(256), 0, st, events, items, mates, grid_bounds, rot, g,
+    hipLaunchKernelGGL((corpus_rows_kernel<MIX, YAW>), dim3((unsigned)gx), dim3(256), 0, st, events, items, mates, grid_bounds, rot, g,
                        ws, count, target);
     return check_launch(name);
 }
 
-template <bool MIX>
+template <bool MIX, bool YAW = false>
 static int corpus_classwise_launch(const char *name, const double *events, const float *xyz, long n_events, const int64_t *items,
                                    const int64_t *mates, int B, int max_events, int n_label_frames, int n_classes, int format,
-                                   float *target, int *status, void *stream) {
+                                   float *target, int *status, void *stream,
+                                   typename CorpusYawXyzArg<YAW>::type yaw = typename CorpusYawXyzArg<YAW>::type()) {
     ADYOLO_REQUIRE(events && xyz && items && (mates || !MIX) && target && status, ADYOLO_EINVAL, "%s: null pointer", name);
     ADYOLO_REQUIRE(B > 0 && B < 65536 && max_events >= 0 && n_events >= 0 && n_events < (1L << (MIX ? CW_SRC_BIT : 31)) &&
                        n_label_frames > 0 && n_classes > 0,
@@ -696,8 +786,8 @@ static int corpus_classwise_launch(const char *name, const double *events, const
     g.row = (format == ADYOLO_CORPUS_SEDDOA ? 4 : format == ADYOLO_CORPUS_ACCDOA ? 3 : 24) * n_classes;
     g.n_events = n_events;
     const size_t lds = (size_t)CW_FRAMES * n_classes * 4 * sizeof(int);
-    hipLaunchKernelGGL(corpus_classwise_kernel<MIX>, dim3((unsigned)cdiv(n_label_frames, CW_FRAMES), (unsigned)B),
-                       dim3(CW_THREADS), lds, as_stream(stream), events, xyz, items, mates, g, target, status);
+    hipLaunchKernelGGL((corpus_classwise_kernel<MIX, YAW>), dim3((unsigned)cdiv(n_label_frames, CW_FRAMES), (unsigned)B),
+                       dim3(CW_THREADS), lds, as_stream(stream), events, xyz, items, mates, g, yaw, target, status);
     return check_launch(name);
 }
 
@@ -775,6 +865,82 @@ extern "C" int adyolo_corpus_classwise_labels_mix(const double *events, const fl
                                                   int format, float *target, int *status, void *stream) {
     return corpus_classwise_launch<true>("corpus_classwise_labels_mix", events, xyz, n_events, items, mates, B, max_events,
                                          n_label_frames, n_classes, format, target, status, stream);
+}
+
+// ------------------------------------------------------------------------------------------------ yaw rotation
+static int corpus_gather_yaw(const char *name, const int16_t *pcm, long n_total, const int64_t *items, const int64_t *mates,
+                             bool mix, int B, long n, const float *rot_host, const float *yaw_tab, float *audio, int *status,
+                             void *stream) {
+    ADYOLO_REQUIRE(rot_host && yaw_tab, ADYOLO_EINVAL, "%s: null pointer", name);
+    ADYOLO_REQUIRE(((uintptr_t)yaw_tab & 7) == 0, ADYOLO_EINVAL, "%s: misaligned yaw table (8 bytes)", name);
+    CorpusYaw tab;
+    corpus_rot(rot_host, tab.rot);
+    tab.cs = reinterpret_cast<const float2 *>(yaw_tab);
+    if (mix) return corpus_gather_launch<CorpusYaw, true>(name, pcm, n_total, items, mates, B, n, tab, audio, status, stream);
+    return corpus_gather_launch<CorpusYaw, false>(name, pcm, n_total, items, nullptr, B, n, tab, audio, status, stream);
+}
+
+extern "C" int adyolo_corpus_gather_yaw(const int16_t *pcm, long n_total, const int64_t *items, int B, long n,
+                                        const float *rot_host, const float *yaw_tab, float *audio, int *status, void *stream) {
+    return corpus_gather_yaw("corpus_gather_yaw", pcm, n_total, items, nullptr, false, B, n, rot_host, yaw_tab, audio, status,
+                             stream);
+}
+
+extern "C" int adyolo_corpus_gather_yaw_mix(const int16_t *pcm, long n_total, const int64_t *items, const int64_t *mates, int B,
+                                            long n, const float *rot_host, const float *yaw_tab, float *audio, int *status,
+                                            void *stream) {
+    return corpus_gather_yaw("corpus_gather_yaw_mix", pcm, n_total, items, mates, true, B, n, rot_host, yaw_tab, audio, status,
+                             stream);
+}
+
+extern "C" int adyolo_corpus_yolo_labels_yaw(const double *events, long n_events, const int64_t *items, int B, int max_events,
+                                             int n_label_frames, const double *grid_bounds, int Gaz, int Gel,
+                                             const float *rot_host, int *ws, float *target, long cap, int *count, int *status,
+                                             void *stream) {
+    return corpus_yolo_labels_launch<false, true>("corpus_yolo_labels_yaw", events, n_events, items, nullptr, B, max_events,
+                                                  n_label_frames, grid_bounds, Gaz, Gel, rot_host, ws, target, cap, count, status,
+                                                  stream);
+}
+
+extern "C" int adyolo_corpus_yolo_labels_yaw_mix(const double *events, long n_events, const int64_t *items, const int64_t *mates,
+                                                 int B, int max_events, int n_label_frames, const double *grid_bounds, int Gaz,
+                                                 int Gel, const float *rot_host, int *ws, float *target, long cap, int *count,
+                                                 int *status, void *stream) {
+    return corpus_yolo_labels_launch<true, true>("corpus_yolo_labels_yaw_mix", events, n_events, items, mates, B, max_events,
+                                                 n_label_frames, grid_bounds, Gaz, Gel, rot_host, ws, target, cap, count, status,
+                                                 stream);
+}
+
+static int corpus_yaw_xyz(const char *name, const float *rot_host, const double *yaw_az, const double *yaw_el, CorpusYawXyz &yaw) {
+    ADYOLO_REQUIRE(rot_host && yaw_az && yaw_el, ADYOLO_EINVAL, "%s: null pointer", name);
+    ADYOLO_REQUIRE(((uintptr_t)yaw_az & 7) == 0 && ((uintptr_t)yaw_el & 7) == 0, ADYOLO_EINVAL, "%s: misaligned yaw tables", name);
+    corpus_rot(rot_host, yaw.rot);
+    yaw.az = yaw_az;
+    yaw.el = yaw_el;
+    return 0;
+}
+
+extern "C" int adyolo_corpus_classwise_labels_yaw(const double *events, const float *xyz, long n_events, const int64_t *items,
+                                                  int B, int max_events, int n_label_frames, int n_classes, int format,
+                                                  const float *rot_host, const double *yaw_az, const double *yaw_el,
+                                                  float *target, int *status, void *stream) {
+    CorpusYawXyz yaw;
+    const int rc = corpus_yaw_xyz("corpus_classwise_labels_yaw", rot_host, yaw_az, yaw_el, yaw);
+    if (rc) return rc;
+    return corpus_classwise_launch<false, true>("corpus_classwise_labels_yaw", events, xyz, n_events, items, nullptr, B,
+                                                max_events, n_label_frames, n_classes, format, target, status, stream, yaw);
+}
+
+extern "C" int adyolo_corpus_classwise_labels_yaw_mix(const double *events, const float *xyz, long n_events,
+                                                      const int64_t *items, const int64_t *mates, int B, int max_events,
+                                                      int n_label_frames, int n_classes, int format, const float *rot_host,
+                                                      const double *yaw_az, const double *yaw_el, float *target, int *status,
+                                                      void *stream) {
+    CorpusYawXyz yaw;
+    const int rc = corpus_yaw_xyz("corpus_classwise_labels_yaw_mix", rot_host, yaw_az, yaw_el, yaw);
+    if (rc) return rc;
+    return corpus_classwise_launch<true, true>("corpus_classwise_labels_yaw_mix", events, xyz, n_events, items, mates, B,
+                                               max_events, n_label_frames, n_classes, format, target, status, stream, yaw);
 }
 
 // ------------------------------------------------------------------------------------------------ windowed inference

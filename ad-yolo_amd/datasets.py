@@ -256,6 +256,9 @@ class FoaDataset(torch.utils.data.Dataset):
     labels, each under its own combination.  With ``aug_config.freq_shift_augment`` or ``cutout_augment`` (training splits) the
     table is int32 (4, 4) instead, in the same tuple slot: rows 0-1 the SpecAug draw (zeros with ``spec_augment`` off), row 2 the
     cutout rectangle, row 3 {shift, 0, 0, 0} -- ``augmentations.draw_feature_aug``, the last draws of the item; no label moves.
+    With ``aug_config.yaw_rotation_augment`` (FOA training splits) the item's yaw is drawn right after its combination
+    (``augmentations.draw_yaw``), the labels are moved by ``yaw_labels`` after ``rotate_labels``, and the tuple's second element
+    is the pair ``(comb_no, yaw in degrees)``; a mixing item's dict gains "mate_yaw".
     Normalisation, rotation of the audio and the
     features run on the GPU (``AudioStager`` -> ``rotate_audio`` -> ``FeatureExtractor``); the label half of the rotation
     and the label encoding stay here on the host, as in the reference's DataLoader workers.  ``label_rows``: the AD-YOLO row
@@ -283,6 +286,9 @@ class FoaDataset(torch.utils.data.Dataset):
         dc = params["data_config"]
         from .augmentations import channel_swap_enabled
         self.swap = channel_swap_enabled(params) and not is_valid      # MIC channel swap (ValueError: not 'mic', or with rotation)
+        from .augmentations import yaw_config
+        yaw = yaw_config(params)                # yaw rotation (ValueError: MIC audio, or a yaw_step_deg that does not divide 360)
+        self.yaw = yaw if set_type == "train" and not is_valid else None      # validation, test and inference are never yawed
         # audio format: the reference reads ``foa_dev`` only (datasets.py:36-37,55); ``data_config.audio_format: mic`` selects the
         # DCASE ``mic_dev`` directory of the same layout (4-channel int16 WAVs; BASELINE config 5, features.MicFeatureExtractor)
         adir = {"foa": "foa_dev", "mic": "mic_dev"}[str(dc.get("audio_format", "foa")).lower()]
@@ -382,6 +388,11 @@ class FoaDataset(torch.utils.data.Dataset):
             from .augmentations import MIC_SWAP_COMBS
             comb_no = MIC_SWAP_COMBS[int(self._random.uniform(0, 8))]
             label = rotate_labels(label, comb_no)
+        phi = None
+        if self.yaw is not None:                # yaw rotation: drawn right after the combination, applied after it
+            from .augmentations import draw_yaw, yaw_labels
+            phi = draw_yaw(self._random, self.yaw)
+            label = yaw_labels(label, phi)
         spec = None
         if self.specaug.apply_augment:          # datasets.py:158-159: MEL, then IV, each its own draw, right after the rotation
             from .features import HOP, N_MELS
@@ -391,16 +402,23 @@ class FoaDataset(torch.utils.data.Dataset):
             from .augmentations import draw_time_mix, merge_labels
             mixed = {"mate_pcm": None, "mate_comb": 0, "gain": 1.0}
             drawn = draw_time_mix(self._random, self.mix, self.total_filelist, name,
-                                  "rotate" if self.rotate else "swap" if self.swap else None)
+                                  "rotate" if self.rotate else "swap" if self.swap else None,
+                                  **({} if self.yaw is None else {"yaw": self.yaw}))
             if drawn is not None:
-                mate, mate_comb, gain = drawn
+                mate, mate_comb, gain = drawn[:3]
                 _, mate_pcm = wavfile.read(self._os.path.join(self.wav_pth, mate + ".wav"))
                 mate_label = self.load_csv2dict(self._os.path.join(self.csv_pth, mate + ".csv"))
                 if mate_comb is not None:
                     mate_label = rotate_labels(mate_label, mate_comb)
+                if self.yaw is not None:
+                    mate_label = yaw_labels(mate_label, drawn[3])
                 label = merge_labels(label, mate_label)
                 mixed = {"mate_pcm": np.ascontiguousarray(mate_pcm, dtype=np.int16), "mate_comb": int(mate_comb or 0),
                          "gain": float(gain)}
+                if self.yaw is not None:
+                    mixed["mate_yaw"] = drawn[3]
+            if self.yaw is not None:
+                mixed.setdefault("mate_yaw", 0)
         if self.feat_aug is not None:           # frequency shift / cutout: the very last draws; the table grows to (4, 4)
             from .augmentations import draw_feature_aug, feature_aug_table
             from .features import HOP, N_MELS
@@ -411,7 +429,8 @@ class FoaDataset(torch.utils.data.Dataset):
             target = self.encoder.get_yolo_label(label, nb_label_frames)
         else:                                   # dense (T', ...) float32 tensor, datasets.py:210-219
             target = getattr(self.encoder, CLASSWISE_LABELS[self.loss_nm])(label, nb_label_frames)
-        item = (np.ascontiguousarray(pcm, dtype=np.int16), comb_no, target)
+        # with the yaw rotation the combination's slot carries the pair (combination, yaw in degrees)
+        item = (np.ascontiguousarray(pcm, dtype=np.int16), comb_no if phi is None else (comb_no, phi), target)
         if spec is not None:
             item += (spec,)
         if mixed is not None:
@@ -424,7 +443,9 @@ CLASSWISE_LABELS = {"seddoa": "get_seddoa_label", "masked-seddoa": "get_seddoa_l
 
 
 def audio_collate_fn(batch):
-    """list of FoaDataset items -> (pcm int16 (B, T, 4) host tensor, comb_nos list, target).  AD-YOLO: target (M, 7) float32
+    """list of FoaDataset items -> (pcm int16 (B, T, 4) host tensor, comb_nos list, target).  Items of a yawing dataset
+    (``aug_config.yaw_rotation_augment``) carry (combination, yaw) pairs, and so does the list; a mixing dict gains "mate_yaws".
+    AD-YOLO: target (M, 7) float32
     rows built exactly like ``collate_fn`` (datasets.py:164-184); class-wise losses: the dense labels stacked to (B, T', ...),
     like the default collate the reference uses for them.  Items with SpecAug tables (4-tuples) -> a 4th element, the tables
     stacked to int32 (B, 2, 4) (or (B, 4, 4): the tables of the frequency-shift / cutout augmentation).  Items of a mixing dataset (``aug_config.time_mix_augment``: a trailing dict) -> one trailing dict
@@ -449,4 +470,6 @@ def audio_collate_fn(batch):
         out += ({"mate_pcm": mate_pcm, "mate_combs": [m["mate_comb"] for m in mix],
                  "gains": torch.tensor([m["gain"] for m in mix], dtype=torch.float32),
                  "mixed": torch.tensor([m["mate_pcm"] is not None for m in mix], dtype=torch.bool)},)
+        if "mate_yaw" in mix[0]:                   # aug_config.yaw_rotation_augment: the mates' yaws beside their combinations
+            out[-1]["mate_yaws"] = [m["mate_yaw"] for m in mix]
     return out

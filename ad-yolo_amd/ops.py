@@ -1985,6 +1985,105 @@ def corpus_classwise_labels_mix(events, items, mates, xyz, max_events, n_label_f
     return target
 
 
+# ---- yaw rotation (aug_config.yaw_rotation_augment): the *_yaw forms read each row's yaw, whole degrees, from word 7
+CORPUS_YAW_WORD = 7                                       # ADYOLO_CORPUS_YAW_WORD
+
+
+def corpus_yaw_table(device):
+    """float32 (360, 2) on ``device``: {cos, sin} of the yaws -180 .. 179 degrees (``augmentations.yaw_cos_sin``), the table of
+    ``corpus_gather_yaw``."""
+    from .augmentations import yaw_cos_sin
+    return torch.tensor([[float(v) for v in yaw_cos_sin(phi)] for phi in range(-180, 180)], dtype=torch.float32).to(device)
+
+
+def corpus_yaw_xyz_tables(device):
+    """(az float64 (361, 2) = {cos, sin} of the azimuths -180 .. 180 degrees, el float64 (181,) = cos of the elevations -90 ..
+    90) on ``device``, each value by the expressions of ``datasets._polar_to_xyz`` on a Python float: the tables of
+    ``corpus_classwise_labels_yaw``."""
+    import numpy as np
+    az = [[float(np.cos(float(a) * np.pi / 180)), float(np.sin(float(a) * np.pi / 180))] for a in range(-180, 181)]
+    el = [float(np.cos(float(e) * np.pi / 180.0)) for e in range(-90, 91)]
+    return torch.tensor(az, dtype=torch.float64).to(device), torch.tensor(el, dtype=torch.float64).to(device)
+
+
+def _corpus_yaw_tab(name, tab, device, dtype, shape):
+    if tab.dtype != dtype or tab.device != device or not tab.is_contiguous() or tuple(tab.shape) != shape:
+        raise _lib.AdyoloHipError("%s: the yaw table must be a contiguous %s tensor %s on %s" % (name, dtype, shape, device))
+
+
+def corpus_gather_yaw(pcm, items, rot, yaw_tab, out, status):
+    """``corpus_gather`` with every item yawed after its combination by word 7 of its row, whole degrees in [-180, 180) (adyolo_hip.h
+    ``adyolo_corpus_gather_yaw``; bit for bit ``pcm16_to_f32`` then ``augmentations.rotate_audio_yaw``).  yaw_tab:
+    ``corpus_yaw_table``; a yaw outside the range: zeros for the item and status bit 2.  No allocation, no sync."""
+    b = _corpus_gather_args("corpus_gather_yaw", pcm, items, out, status)
+    _corpus_yaw_tab("corpus_gather_yaw", yaw_tab, pcm.device, torch.float32, (360, 2))
+    _c("adyolo_corpus_gather_yaw", _p(pcm), pcm.shape[0], _p(items), b, out.shape[1], ctypes.cast(rot, ctypes.c_void_p),
+       _p(yaw_tab), _p(out), _p(status), _stream())
+    return out
+
+
+def corpus_gather_yaw_mix(pcm, items, mates, rot, yaw_tab, out, status):
+    """``corpus_gather_mix`` (FOA form) with item and mate each under its own combination and its own yaw (word 7 of either row;
+    word 6 of a mate stays the gain) (adyolo_hip.h ``adyolo_corpus_gather_yaw_mix``).  No allocation, no sync."""
+    b = _corpus_gather_args("corpus_gather_yaw_mix", pcm, items, out, status, mates)
+    _corpus_yaw_tab("corpus_gather_yaw_mix", yaw_tab, pcm.device, torch.float32, (360, 2))
+    _c("adyolo_corpus_gather_yaw_mix", _p(pcm), pcm.shape[0], _p(items), _p(mates), b, out.shape[1],
+       ctypes.cast(rot, ctypes.c_void_p), _p(yaw_tab), _p(out), _p(status), _stream())
+    return out
+
+
+def corpus_yolo_labels_yaw(events, items, max_events, n_label_frames, bounds, grid, rot, ws, target, count, status):
+    """``corpus_yolo_labels`` with ``augmentations.yaw_labels`` by word 7 of each row after its combination (adyolo_hip.h
+    ``adyolo_corpus_yolo_labels_yaw``).  The same workspace.  No allocation, no sync."""
+    name = "corpus_yolo_labels_yaw"
+    b, n_ev, gaz, gel = _corpus_yolo_args(name, events, items, max_events, bounds, grid, ws, target, count, status)
+    _c("adyolo_" + name, _p(events), n_ev, _p(items), b, int(max_events), int(n_label_frames), _p(bounds), gaz, gel,
+       ctypes.cast(rot, ctypes.c_void_p), _p(ws), _p(target), target.shape[0], _p(count), _p(status), _stream())
+    return target
+
+
+def corpus_yolo_labels_yaw_mix(events, items, mates, max_events, n_label_frames, bounds, grid, rot, ws, target, count, status):
+    """``corpus_yolo_labels_mix`` with each source's events yawed by its own row's word 7 after its combination (adyolo_hip.h
+    ``adyolo_corpus_yolo_labels_yaw_mix``).  The same workspace.  No allocation, no sync."""
+    name = "corpus_yolo_labels_yaw_mix"
+    b, n_ev, gaz, gel = _corpus_yolo_args(name, events, items, max_events, bounds, grid, ws, target, count, status, mates)
+    _c("adyolo_" + name, _p(events), n_ev, _p(items), _p(mates), b, int(max_events), int(n_label_frames), _p(bounds), gaz, gel,
+       ctypes.cast(rot, ctypes.c_void_p), _p(ws), _p(target), target.shape[0], _p(count), _p(status), _stream())
+    return target
+
+
+def _corpus_yaw_xyz_args(name, yaw_xyz, device):
+    az, el = yaw_xyz
+    _corpus_yaw_tab(name, az, device, torch.float64, (361, 2))
+    _corpus_yaw_tab(name, el, device, torch.float64, (181,))
+    return az, el
+
+
+def corpus_classwise_labels_yaw(events, items, xyz, rot, yaw_xyz, max_events, n_label_frames, nb_classes, loss, target, status):
+    """``corpus_classwise_labels`` for yawed items (word 7 of each row): z from the event's xyz slot, x and y from ``yaw_xyz``
+    (``corpus_yaw_xyz_tables``) at the event's moved whole-degree angles (adyolo_hip.h ``adyolo_corpus_classwise_labels_yaw``).
+    rot: ``corpus_rot_table``.  No allocation, no sync."""
+    name = "corpus_classwise_labels_yaw"
+    b, n_ev = _corpus_classwise_args(name, events, items, xyz, n_label_frames, nb_classes, loss, target, status)
+    az, el = _corpus_yaw_xyz_args(name, yaw_xyz, items.device)
+    _c("adyolo_" + name, _p(events), _p(xyz), n_ev, _p(items), b, int(max_events), int(n_label_frames), int(nb_classes),
+       CORPUS_FORMATS[loss], ctypes.cast(rot, ctypes.c_void_p), _p(az), _p(el), _p(target), _p(status), _stream())
+    return target
+
+
+def corpus_classwise_labels_yaw_mix(events, items, mates, xyz, rot, yaw_xyz, max_events, n_label_frames, nb_classes, loss, target,
+                                    status):
+    """``corpus_classwise_labels_mix`` for yawed sources, each under its own row's combination and yaw (adyolo_hip.h
+    ``adyolo_corpus_classwise_labels_yaw_mix``).  No allocation, no sync."""
+    name = "corpus_classwise_labels_yaw_mix"
+    b, n_ev = _corpus_classwise_args(name, events, items, xyz, n_label_frames, nb_classes, loss, target, status, mates)
+    az, el = _corpus_yaw_xyz_args(name, yaw_xyz, items.device)
+    _c("adyolo_" + name, _p(events), _p(xyz), n_ev, _p(items), _p(mates), b, int(max_events), int(n_label_frames),
+       int(nb_classes), CORPUS_FORMATS[loss], ctypes.cast(rot, ctypes.c_void_p), _p(az), _p(el), _p(target), _p(status),
+       _stream())
+    return target
+
+
 WINDOW_WORDS = 8                                          # ADYOLO_WINDOW_WORDS: {offset, valid, src_lo, dst, n, recording, 0, 0}
 
 

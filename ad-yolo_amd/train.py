@@ -725,16 +725,24 @@ class _EpochLoss:
 def train_one_epoch_audio(params: dict, dataloader, trainer, stager=None, rotate=True):
     """The raw-audio epoch: ``dataloader`` yields ``audio_collate_fn`` batches (pcm int16 (B,T,4), comb_nos, target[, SpecAug
     tables (B,2,4), or (B,4,4) with the frequency-shift / cutout rows]); each is staged to the GPU (int16 over PCIe on a side stream, double-buffered), converted, rotated (with
-    ``aug_config.channel_swap_augment``: its channels permuted, ``swap_audio``; with ``aug_config.time_mix_augment``: the batch's
+    ``aug_config.channel_swap_augment``: its channels permuted, ``swap_audio``; with ``aug_config.yaw_rotation_augment``: rotated
+    and yawed by ``rotate_audio_yaw``, the batch's second element then holding (combination, yaw) pairs; with
+    ``aug_config.time_mix_augment``: the batch's
     trailing dict of mates staged, moved by their own combinations and summed in by ``ops.audio_mix``) and handed with its
     tables to ``TrainStep.step``
     (features [+ SpecAug masks] + forward + loss + backward [+ all-reduce] + Adam).  Returns the mean loss with ONE device sync
     at the end of the epoch (the reference syncs every iteration, train.py:57); with ``train_config['skip_nonfinite']`` the
     mean over the APPLIED steps (``_EpochLoss``).  With ``train_config['accum_steps']`` every batch is a micro-step; an epoch whose number of batches is no multiple of it (or that
     ``quick_test`` cuts short) ends inside a cycle, and that partial cycle is DROPPED: its gradients take part in no step."""
-    from .augmentations import channel_swap_enabled, rotate_audio, swap_audio
+    from .augmentations import channel_swap_enabled, rotate_audio, rotate_audio_yaw, swap_audio
     from .datasets import AudioStager
     move_audio = swap_audio if channel_swap_enabled(params) else rotate_audio     # MIC channel swap | FOA rotation
+
+    def yawed(combs):
+        """``aug_config.yaw_rotation_augment``: the batch carries (combination, yaw) pairs -> (combinations, yaws), else None."""
+        if len(combs) and isinstance(combs[0], tuple):
+            return [c for c, _ in combs], [p for _, p in combs]
+        return None
 
     def split(rest):
         """The optional tail of a batch -> (SpecAug tables or None, mixing dict or None), told apart by type."""
@@ -767,10 +775,17 @@ def train_one_epoch_audio(params: dict, dataloader, trainer, stager=None, rotate
             stager.stage(pcm)
             if mate_stager is not None:
                 mate_stager.stage(mix["mate_pcm"])
-        if rotate and any(int(c) != 0 for c in cur_combs):
+        pairs = yawed(cur_combs)
+        if pairs is not None:                     # FOA rotation, then the yaw, in one pass
+            if rotate:
+                audio = rotate_audio_yaw(audio, *pairs)
+        elif rotate and any(int(c) != 0 for c in cur_combs):
             audio = move_audio(audio, cur_combs)
         if cur_mix is not None:                   # each side under its own combinations, then audio + gain * mate
-            if rotate and any(int(c) != 0 for c in cur_mix["mate_combs"]):
+            if "mate_yaws" in cur_mix:
+                if rotate:
+                    mate = rotate_audio_yaw(mate, cur_mix["mate_combs"], cur_mix["mate_yaws"])
+            elif rotate and any(int(c) != 0 for c in cur_mix["mate_combs"]):
                 mate = move_audio(mate, cur_mix["mate_combs"])
             audio = ops.audio_mix(audio, mate, cur_mix["gains"].to(device), cur_mix["mixed"].to(device), out=audio)
         acc.add(trainer.step(audio, cur_target, cur_spec))

@@ -669,6 +669,13 @@ int adyolo_ln_bwd(const float *dy, const float *x, const float *gamma, float *dx
  * cfg [B][4] = {sign_y, sign_z, sign_x, swap_xy}.  Label angles are remapped on the host (augmentations.RotationAug). */
 int adyolo_foa_rotate(const float *audio, float *out, const float *cfg, int B, long n_samples, void *stream);
 
+/* FOA rotation followed by a yaw about the vertical axis (aug_config.yaw_rotation_augment, augmentations.rotate_audio_yaw; the
+ * host-fed path): audio/out [B][n_samples][4] (W,Y,Z,X), 16-byte aligned; cfg DEVICE float [B][6] = {sign_y, sign_z, sign_x,
+ * swap_xy, cos, sin} (augmentations.yaw_cos_sin).  Per frame the result (W, Y, Z, X) of adyolo_foa_rotate, then
+ * Y' = fl(fl(Y c) + fl(X s)), X' = fl(fl(X c) - fl(Y s)): every product and sum rounded to float32, no FMA.  cos = 1, sin = 0
+ * gives the bits of adyolo_foa_rotate (on frames without -0.0). */
+int adyolo_foa_rotate_yaw(const float *audio, float *out, const float *cfg, int B, long n_samples, void *stream);
+
 /* MIC channel-swap augmentation on raw audio (augmentations.swap_audio; the MIC-format counterpart of adyolo_foa_rotate):
  * audio/out [B][n_samples][4] (capsules M1..M4), 16-byte aligned, out-of-place only (out must not overlap audio);
  * src_dev DEVICE int32 [B][4]: out[b][i][j] = audio[b][i][src_dev[b][j] & 3] -- the selectors are masked in the kernel, so no
@@ -746,8 +753,27 @@ int adyolo_audio_mix(const float *audio, const float *mate, const float *gains, 
  *   a frame in item-then-mate order (the mate's wins a collision), ADPIT counts over both sources and keeps the first three in
  *   that order; each direction vector comes from the xyz slot of its own source's combination.  n_events < 2^30.  An item
  *   without a mate has the bits of adyolo_corpus_classwise_labels; bad items (either row) and bad classes as there.
+ *
+ * Yaw rotation (aug_config.yaw_rotation_augment, FOA only): after its combination every source is turned about the vertical
+ * axis by its own yaw.  The *_yaw calls read it from word ADYOLO_CORPUS_YAW_WORD (7) of the item row and of the mate row (word 6
+ * of a mate stays the gain): the yaw in WHOLE DEGREES as a signed integer, legal in [-180, 180); 0 turns nothing.  A row whose
+ * yaw is outside that range is a bad item, as a combination >= 16 is.  The other calls never read word 7.
+ * adyolo_corpus_gather_yaw / _yaw_mix: adyolo_corpus_gather / adyolo_corpus_gather_mix (FOA form) with each source's frames
+ *   yawed after its combination -- bit for bit adyolo_pcm16_to_f32 -> adyolo_foa_rotate_yaw (-> a + g * m).  yaw_tab DEVICE float
+ *   [360][2] = {cos, sin} of the yaws -180 .. 179 (augmentations.yaw_cos_sin), 8-byte aligned; entry yaw + 180 is read once
+ *   per workgroup.  comb < 0: the yaw alone.  All parities of the two offsets and an odd n are legal, as in the plain calls.
+ * adyolo_corpus_yolo_labels_yaw / _yaw_mix: adyolo_corpus_yolo_labels / _mix with augmentations.yaw_labels after the
+ *   combination's arithmetic: az = az + yaw, then < -180: += 360, > 180: -= 360, in double and uncontracted, before the
+ *   180 -> -180 rule of the encoder.  The same workspace functions; any angles.
+ * adyolo_corpus_classwise_labels_yaw / _yaw_mix: adyolo_corpus_classwise_labels / _mix for yawed sources.  z of an event is
+ *   still read from its xyz slot; x = (float)(cos_az * cos_el) and y = (float)(sin_az * cos_el), one double product each,
+ *   from yaw_az DEVICE double [361][2] = {cos, sin} of the azimuths -180 .. 180 and yaw_el DEVICE double [181] = cos of the
+ *   elevations -90 .. 90, both built on the host with the expressions of datasets._polar_to_xyz (ops.corpus_yaw_xyz_tables)
+ *   and indexed by the event's moved angles (as in the _yolo_labels_yaw calls).  The events' angles must be whole degrees
+ *   (corpus.ClasswiseDeviceCorpus refuses any other split); an angle that is not indexes entry 0.  rot_host as above.
  * ---------------------------------------------------------------------------------------------- */
 #define ADYOLO_CORPUS_ITEM_WORDS 8
+#define ADYOLO_CORPUS_YAW_WORD   7   /* the *_yaw calls: the row's yaw in whole degrees, [-180, 180) */
 #define ADYOLO_CORPUS_ROT_WORDS  8
 #define ADYOLO_CORPUS_OVERFLOW   1   /* more rows than the target capacity */
 #define ADYOLO_CORPUS_BAD_ITEM   2   /* an item table entry outside the corpus */
@@ -779,6 +805,24 @@ int  adyolo_corpus_yolo_labels_mix(const double *events, long n_events, const in
 int  adyolo_corpus_classwise_labels_mix(const double *events, const float *xyz, long n_events, const int64_t *items,
                                         const int64_t *mates, int B, int max_events, int n_label_frames, int n_classes,
                                         int format, float *target, int *status, void *stream);
+int  adyolo_corpus_gather_yaw(const int16_t *pcm, long n_total, const int64_t *items, int B, long n, const float *rot_host,
+                              const float *yaw_tab, float *audio, int *status, void *stream);
+int  adyolo_corpus_gather_yaw_mix(const int16_t *pcm, long n_total, const int64_t *items, const int64_t *mates, int B, long n,
+                                  const float *rot_host, const float *yaw_tab, float *audio, int *status, void *stream);
+int  adyolo_corpus_yolo_labels_yaw(const double *events, long n_events, const int64_t *items, int B, int max_events,
+                                   int n_label_frames, const double *grid_bounds, int Gaz, int Gel, const float *rot_host,
+                                   int *ws, float *target, long cap, int *count, int *status, void *stream);
+int  adyolo_corpus_yolo_labels_yaw_mix(const double *events, long n_events, const int64_t *items, const int64_t *mates, int B,
+                                       int max_events, int n_label_frames, const double *grid_bounds, int Gaz, int Gel,
+                                       const float *rot_host, int *ws, float *target, long cap, int *count, int *status,
+                                       void *stream);
+int  adyolo_corpus_classwise_labels_yaw(const double *events, const float *xyz, long n_events, const int64_t *items, int B,
+                                        int max_events, int n_label_frames, int n_classes, int format, const float *rot_host,
+                                        const double *yaw_az, const double *yaw_el, float *target, int *status, void *stream);
+int  adyolo_corpus_classwise_labels_yaw_mix(const double *events, const float *xyz, long n_events, const int64_t *items,
+                                            const int64_t *mates, int B, int max_events, int n_label_frames, int n_classes,
+                                            int format, const float *rot_host, const double *yaw_az, const double *yaw_el,
+                                            float *target, int *status, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Windowed inference (corpus.InferDeviceCorpus, test.infer_epoch_corpus): recordings of any length cut into overlapping

@@ -26,11 +26,14 @@ classes of the split and the model (12 by default: the ACCDOA / ADPIT heads' GEM
 skips the host-loader epochs.  --mix [--prob P] runs every batch size twice, key off ("b16") and with
 ``aug_config.time_mix_augment`` at probability P ("b16_mix": doubled AD-YOLO row capacity), and adds to the second the time-domain
 mixing calls on the same batch: ``adyolo_corpus_gather_mix`` with the drawn mates, with a mate for every item (prob 1.0) and with
-none (prob 0.0), and the ``_mix`` label call next to the plain one.
+none (prob 0.0), and the ``_mix`` label call next to the plain one.  --yaw runs every batch size (and with --mix every mixing
+run) a second time with ``aug_config.yaw_rotation_augment`` on ("b16_yaw", "b16_yaw_mix"; the split's labels are then whole
+degrees, which the class-wise corpus needs) and measures, on the same item tables, ``adyolo_corpus_gather_yaw`` against
+``adyolo_corpus_gather``, ``_yaw_mix`` against ``adyolo_corpus_gather_mix`` and the ``_yaw`` label calls against the un-yawed ones.
 
   python tools/corpus_bench.py [--dir /tmp/adyolo_corpus] [--batches 16,64] [--steps 32,8] [--workers 16] [--json out.json]
                                [--loss adyolo|seddoa|accdoa|adpit] [--mic] [--swap] [--classes C] [--labels-only]
-                               [--corpus-only] [--mix [--prob P]]
+                               [--corpus-only] [--mix [--prob P]] [--yaw]
 """
 import argparse
 import csv
@@ -52,8 +55,10 @@ import torch  # noqa: E402
 SR, WINDOW_S, STRIDE_S, REC_S = 24000, 20, 1, 60
 
 
-def write_split(root, n_recordings, seed=0, n_classes=12, audio_dir="foa_dev"):
-    """n_recordings x 60 s, chunked as the reference's preprocess.chunk_instance cuts them (60 s: no padding)."""
+def write_split(root, n_recordings, seed=0, n_classes=12, audio_dir="foa_dev", whole=False):
+    """n_recordings x 60 s, chunked as the reference's preprocess.chunk_instance cuts them (60 s: no padding).  whole: the
+    angles in whole degrees instead of tenths."""
+    nd = 0 if whole else 1
     from scipy.io import wavfile
     rs = np.random.RandomState(seed)
     sub = "dev-train-chunked_%ds_%ds" % (WINDOW_S, STRIDE_S)
@@ -68,7 +73,7 @@ def write_split(root, n_recordings, seed=0, n_classes=12, audio_dir="foa_dev"):
         for f in range(REC_S * 10):
             k = rs.choice(3, p=[0.35, 0.45, 0.2])
             if k:
-                label[f] = [[int(rs.randint(n_classes)), s, round(float(rs.uniform(-180, 180)), 1), round(float(rs.uniform(-60, 60)), 1)]
+                label[f] = [[int(rs.randint(n_classes)), s, round(float(rs.uniform(-180, 180)), nd), round(float(rs.uniform(-60, 60)), nd)]
                             for s in range(k)]
         for i in range((len(audio) - win) // st + 1):
             name = "fold1_room%d_mix%03d_chunk%03d" % (r % 10, r, i + 1)
@@ -82,7 +87,7 @@ def write_split(root, n_recordings, seed=0, n_classes=12, audio_dir="foa_dev"):
     return nbytes
 
 
-def params(root, batch, steps, loss="adyolo", mic=False, n_classes=12, swap=False, mix=None):
+def params(root, batch, steps, loss="adyolo", mic=False, n_classes=12, swap=False, mix=None, yaw=False):
     from __graft_entry__ import _params
     prm = _params(nb_classes=n_classes)
     prm["args"]["loss"] = loss
@@ -97,6 +102,8 @@ def params(root, batch, steps, loss="adyolo", mic=False, n_classes=12, swap=Fals
         prm["aug_config"].update({"rotation_augment": False, "channel_swap_augment": True})
     if mix is not None:
         prm["aug_config"].update({"time_mix_augment": True, "time_mix_prob": mix})
+    if yaw:
+        prm["aug_config"]["yaw_rotation_augment"] = True
     return prm
 
 
@@ -164,13 +171,15 @@ def graph_us(launch, iters):
 
 
 def bench_batch(root, batch, steps, workers, iters, loss="adyolo", mic=False, n_classes=12, labels_only=False, swap=False,
-                corpus_only=False, mix=None):
+                corpus_only=False, mix=None, yaw=False):
     from adyolo_amd import ops
     from adyolo_amd.corpus import ClasswiseDeviceCorpus, DeviceCorpus, load_chunked_split
     from adyolo_amd.datasets import FoaDataset, audio_collate_fn
     from adyolo_amd.train import train_one_epoch_audio, train_one_epoch_corpus
-    prm = params(root, batch, steps, loss, mic, n_classes, swap, mix)
+    prm = params(root, batch, steps, loss, mic, n_classes, swap, mix, yaw)
     out = {"batch": batch, "steps_per_epoch": steps}
+    if yaw:
+        out["yaw"] = True
     if mix is not None:
         out["mix_prob"] = mix
     if loss != "adyolo" or mic:
@@ -252,6 +261,40 @@ def bench_batch(root, batch, steps, workers, iters, loss="adyolo", mic=False, n_
                     corpus.events, dev_items[i % 4], tabs[i % 4], corpus.xyz, corpus.max_events, corpus.n_label_frames,
                     corpus.nb_classes, loss, target, corpus.status), iters)
             del target
+        corpus.check()
+    if yaw:
+        # the yaw calls on the same tables (word 7 of every row holds its drawn yaw, which the un-yawed calls do not read)
+        out["gather_yaw_us"] = graph_us(lambda i: ops.corpus_gather_yaw(corpus.pcm, dev_items[i % 4], corpus.rot, corpus.yaw_tab,
+                                                                        audio, corpus.status), iters)
+        if mix is not None:
+            for key, tabs in (("gather_yaw_mix_us", dev_mates), ("gather_yaw_mix_p1_us", every)):
+                out[key] = graph_us(lambda i: ops.corpus_gather_yaw_mix(corpus.pcm, dev_items[i % 4], tabs[i % 4], corpus.rot,
+                                                                        corpus.yaw_tab, audio, corpus.status), iters)
+        target = torch.empty(corpus.target_shape(batch), dtype=torch.float32, device="cuda:0")
+        if loss == "adyolo":
+            rows = torch.empty(1, dtype=torch.int32, device="cuda:0")
+            ws = torch.empty(ops.corpus_labels_mix_workspace_words(batch, corpus.max_events), dtype=torch.int32, device="cuda:0")
+            tail = (corpus.max_events, corpus.n_label_frames, corpus.bounds, corpus.grid, corpus.rot, ws, target, rows,
+                    corpus.status)
+            calls = [("labels_us", ops.corpus_yolo_labels, None), ("labels_yaw_us", ops.corpus_yolo_labels_yaw, None)]
+            if mix is not None:
+                calls += [("labels_mix_us", ops.corpus_yolo_labels_mix, dev_mates),
+                          ("labels_yaw_mix_us", ops.corpus_yolo_labels_yaw_mix, dev_mates)]
+            for key, call, tabs in calls:
+                out[key] = graph_us(lambda i: call(corpus.events, dev_items[i % 4], *(() if tabs is None else (tabs[i % 4],)),
+                                                   *tail), iters)
+        else:
+            tail = (corpus.max_events, corpus.n_label_frames, corpus.nb_classes, loss, target, corpus.status)
+            calls = [("labels_us", ops.corpus_classwise_labels, None, (corpus.xyz,)),
+                     ("labels_yaw_us", ops.corpus_classwise_labels_yaw, None, (corpus.xyz, corpus.rot, corpus.yaw_xyz))]
+            if mix is not None:
+                calls += [("labels_mix_us", ops.corpus_classwise_labels_mix, dev_mates, (corpus.xyz,)),
+                          ("labels_yaw_mix_us", ops.corpus_classwise_labels_yaw_mix, dev_mates,
+                           (corpus.xyz, corpus.rot, corpus.yaw_xyz))]
+            for key, call, tabs, xyz in calls:
+                out[key] = graph_us(lambda i: call(corpus.events, dev_items[i % 4], *(() if tabs is None else (tabs[i % 4],)),
+                                                   *xyz, *tail), iters)
+        del target
         corpus.check()
     del audio
     if loss != "adyolo":
@@ -338,9 +381,12 @@ def main():
     ap.add_argument("--corpus-only", action="store_true", help="skip the host-loader epochs")
     ap.add_argument("--mix", action="store_true", help="each batch size with aug_config.time_mix_augment off and on")
     ap.add_argument("--prob", type=float, default=0.5, help="time_mix_prob of the --mix runs")
+    ap.add_argument("--yaw", action="store_true", help="each run with aug_config.yaw_rotation_augment off and on (FOA only)")
     a = ap.parse_args()
     if a.swap and not a.mic:
         ap.error("--swap permutes microphone capsules: it needs --mic")
+    if a.yaw and a.mic:
+        ap.error("--yaw turns the B-format sound field: it is the FOA augmentation (no --mic)")
     n_classes = a.classes
     assert torch.cuda.is_available(), "corpus_bench needs the GPU"
     import adyolo_amd  # noqa: F401
@@ -351,7 +397,7 @@ def main():
     n_rec = -(-files // (REC_S - WINDOW_S + 1))
     shutil.rmtree(a.dir, ignore_errors=True)
     t0 = time.perf_counter()
-    nbytes = write_split(a.dir, n_rec, n_classes=n_classes, audio_dir="mic_dev" if a.mic else "foa_dev")
+    nbytes = write_split(a.dir, n_rec, n_classes=n_classes, audio_dir="mic_dev" if a.mic else "foa_dev", whole=a.yaw)
     res = {"split": {"recordings": n_rec, "wav_bytes": nbytes, "write_s": round(time.perf_counter() - t0, 2)},
            "cpus": len(os.sched_getaffinity(0))}
     print(json.dumps(res), flush=True)
@@ -360,10 +406,20 @@ def main():
             r = bench_batch(a.dir, b, s, a.workers, a.iters, a.loss, a.mic, n_classes, a.labels_only, a.swap, a.corpus_only)
             res["b%d" % b] = r
             print(json.dumps(r), flush=True)
+            if a.yaw:
+                r = bench_batch(a.dir, b, s, a.workers, a.iters, a.loss, a.mic, n_classes, a.labels_only, a.swap, a.corpus_only,
+                                yaw=True)
+                res["b%d_yaw" % b] = r
+                print(json.dumps(r), flush=True)
             if a.mix:
                 r = bench_batch(a.dir, b, s, a.workers, a.iters, a.loss, a.mic, n_classes, a.labels_only, a.swap, a.corpus_only,
                                 mix=a.prob)
                 res["b%d_mix" % b] = r
+                print(json.dumps(r), flush=True)
+            if a.mix and a.yaw:
+                r = bench_batch(a.dir, b, s, a.workers, a.iters, a.loss, a.mic, n_classes, a.labels_only, a.swap, a.corpus_only,
+                                mix=a.prob, yaw=True)
+                res["b%d_yaw_mix" % b] = r
                 print(json.dumps(r), flush=True)
     finally:
         if not a.keep:

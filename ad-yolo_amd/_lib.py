@@ -136,22 +136,11 @@ SIGNATURES = {
     "adyolo_foa_rotate": (I, [P, P, P, I, L, P]),
     "adyolo_foa_rotate_yaw": (I, [P, P, P, I, L, P]),
     "adyolo_mic_swap": (I, [P, P, P, I, L, P]),
-    "adyolo_corpus_gather": (I, [P, L, P, I, L, P, P, P, P]),
-    "adyolo_corpus_gather_mic": (I, [P, L, P, I, L, P, P, P, P]),
-    "adyolo_corpus_yolo_labels_workspace_words": (L, [I, I]),
-    "adyolo_corpus_yolo_labels": (I, [P, L, P, I, I, I, P, I, I, P, P, P, L, P, P, P]),
-    "adyolo_corpus_classwise_labels": (I, [P, P, L, P, I, I, I, I, I, P, P, P]),
+    "adyolo_corpus_gather": (I, [P, L, P, P, I, L, P, P, P, P, P, P]),
+    "adyolo_corpus_yolo_labels_workspace_words": (L, [I, I, I]),
+    "adyolo_corpus_yolo_labels": (I, [P, L, P, P, I, I, I, P, I, I, P, I, P, P, L, P, P, P]),
+    "adyolo_corpus_classwise_labels": (I, [P, P, L, P, P, I, I, I, I, I, P, P, P, P, P, P]),
     "adyolo_audio_mix": (I, [P, P, P, P, P, I, L, P]),
-    "adyolo_corpus_gather_mix": (I, [P, L, P, P, I, L, P, P, P, P, P]),
-    "adyolo_corpus_yolo_labels_mix_workspace_words": (L, [I, I]),
-    "adyolo_corpus_yolo_labels_mix": (I, [P, L, P, P, I, I, I, P, I, I, P, P, P, L, P, P, P]),
-    "adyolo_corpus_classwise_labels_mix": (I, [P, P, L, P, P, I, I, I, I, I, P, P, P]),
-    "adyolo_corpus_gather_yaw": (I, [P, L, P, I, L, P, P, P, P, P]),
-    "adyolo_corpus_gather_yaw_mix": (I, [P, L, P, P, I, L, P, P, P, P, P]),
-    "adyolo_corpus_yolo_labels_yaw": (I, [P, L, P, I, I, I, P, I, I, P, P, P, L, P, P, P]),
-    "adyolo_corpus_yolo_labels_yaw_mix": (I, [P, L, P, P, I, I, I, P, I, I, P, P, P, L, P, P, P]),
-    "adyolo_corpus_classwise_labels_yaw": (I, [P, P, L, P, I, I, I, I, I, P, P, P, P, P, P]),
-    "adyolo_corpus_classwise_labels_yaw_mix": (I, [P, P, L, P, P, I, I, I, I, I, P, P, P, P, P, P]),
     "adyolo_corpus_gather_windows": (I, [P, L, P, I, L, P, P, P]),
     "adyolo_decode_stitch": (I, [P, P, I, I, L, L, P, L, P, P]),
     "adyolo_resample_pcm": (I, [P, I, L, P, I, P, L, I, I, I, L, P, L, P, P]),
@@ -208,8 +197,8 @@ def load():
         fn.restype = res
         fn.argtypes = args
     ver = lib.adyolo_abi_version()
-    if ver != 3:
-        raise AdyoloHipError("libadyolo_hip.so ABI version %d != 3" % ver)
+    if ver != 4:
+        raise AdyoloHipError("libadyolo_hip.so ABI version %d != 4" % ver)
     _lib = lib
     for hook in ON_LOAD:
         hook(lib)

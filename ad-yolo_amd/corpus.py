@@ -12,12 +12,12 @@ rotates and encodes the labels on the host and stages every batch over PCIe.  He
 * ``DeviceCorpus`` (device half, AD-YOLO): the streams as one int16 buffer and the events as one float64 table in HBM (0.69 GB
   per hour of 4-channel 24 kHz audio), ``FoaDataset``'s sampling surface (the same functions), and ``batch(indices)``: the same
   ``random`` draws as ``FoaDataset.__getitem__`` item by item, one small H2D copy of the item table, then ``adyolo_corpus_gather``
-  (audio, rotated; with ``aug_config.channel_swap_augment`` ``adyolo_corpus_gather_mic``: MIC capsules permuted) and
+  (audio, rotated; with ``aug_config.channel_swap_augment`` its MIC form: the capsules permuted) and
   ``adyolo_corpus_yolo_labels`` (the AD-YOLO rows into a fixed-capacity target, padding b = -1).  No host sync.  With
   ``aug_config.time_mix_augment`` the draws of ``augmentations.draw_time_mix`` follow each item's, a second table of mates rides
-  in the same copy and the ``_mix`` calls sum the mate's window in and unite the labels (``augmentations.merge_labels``).  With
+  in the same copy and both calls take it: the mate's window summed in, the labels united (``augmentations.merge_labels``).  With
   ``aug_config.yaw_rotation_augment`` (FOA) every item and mate row carries its own yaw in word 7 (``augmentations.draw_yaw``,
-  right after the combination draw) and the ``_yaw`` calls turn the audio and move the azimuths after the combination.
+  right after the combination draw) and the calls, given the yaw, turn the audio and move the azimuths after the combination.
 * ``ClasswiseDeviceCorpus`` (device half, ``seddoa | masked-seddoa | accdoa | adpit``): the same split, sampling, draws and
   gather; the labels are ``adyolo_corpus_classwise_labels``, the dense ``ClasswiseLabelEncoder`` targets of the batch written
   whole, from a float32 table of every event's direction vector under no rotation and the 16 FOA combinations (``xyz_table``,
@@ -531,15 +531,8 @@ class _CorpusBase:
         """The audio of a batch: FOA-rotated (with ``aug_config.yaw_rotation_augment``: and yawed, each row by its word 7), or with
         ``aug_config.channel_swap_augment`` the MIC capsules permuted; with mates
         (``aug_config.time_mix_augment``) each mate's window, under its own combination, summed in by the same pass."""
-        if self.yaw is not None:
-            if dev_mates is not None:
-                return ops.corpus_gather_yaw_mix(self.pcm, dev_items, dev_mates, self.rot, self.yaw_tab, audio, self.status)
-            return ops.corpus_gather_yaw(self.pcm, dev_items, self.rot, self.yaw_tab, audio, self.status)
-        if dev_mates is not None:
-            return ops.corpus_gather_mix(self.pcm, dev_items, dev_mates, self.rot, self.mic_src, audio, self.status)
-        if self.swap:
-            return ops.corpus_gather_mic(self.pcm, dev_items, self.mic_src, audio, self.status)
-        return ops.corpus_gather(self.pcm, dev_items, self.rot, audio, self.status)
+        return ops.corpus_gather(self.pcm, dev_items, self.rot, audio, self.status, mates=dev_mates, mic_src=self.mic_src,
+                                 yaw_tab=self.yaw_tab)
 
     def reset_status(self):
         self.status.zero_()
@@ -577,9 +570,6 @@ class DeviceCorpus(_CorpusBase):
             cap = self._round_cap(self.batch_size * (2 if self.mix is not None else 1) * self.max_events * self.cells)
         self.cap = int(cap)
         self.rows = None                 # int32 word on the device: the row count of the last batch
-        # the label calls (plain, mixed) of this corpus: with the yaw rotation the forms that move each row's azimuths by word 7
-        self._labels = (ops.corpus_yolo_labels, ops.corpus_yolo_labels_mix) if self.yaw is None else \
-            (ops.corpus_yolo_labels_yaw, ops.corpus_yolo_labels_yaw_mix)
 
     def target_shape(self, batch):
         """The target of every batch: (cap, 7) rows, whatever the batch size."""
@@ -592,13 +582,11 @@ class DeviceCorpus(_CorpusBase):
         b = dev_items.shape[0]
         self.rows = torch.empty(1, dtype=torch.int32, device=self.device)
         self._gather(dev_items, audio, dev_mates)
-        if dev_mates is None:
-            ws_words, labels, tables = ops.corpus_labels_workspace_words, self._labels[0], (dev_items,)
-        else:                                    # time-domain mixing: both sources' audio summed, their rows in merged order
-            ws_words, labels, tables = ops.corpus_labels_mix_workspace_words, self._labels[1], (dev_items, dev_mates)
-        ws = torch.empty(max(1, ws_words(b, self.max_events)), dtype=torch.int32, device=self.device)
-        labels(self.events, *tables, self.max_events, self.n_label_frames, self.bounds, self.grid, self.rot, ws, target, self.rows,
-               self.status)
+        # with mates (time-domain mixing) both sources' rows in merged order; with the yaw rotation the azimuths moved by word 7
+        ws_words = ops.corpus_labels_workspace_words(b, self.max_events, mix=dev_mates is not None)
+        ws = torch.empty(max(1, ws_words), dtype=torch.int32, device=self.device)
+        ops.corpus_yolo_labels(self.events, dev_items, self.max_events, self.n_label_frames, self.bounds, self.grid, self.rot, ws,
+                               target, self.rows, self.status, mates=dev_mates, yaw=self.yaw is not None)
         return audio, target, dev_spec
 
 
@@ -655,17 +643,11 @@ class ClasswiseDeviceCorpus(_CorpusBase):
         -> (audio (B, n, 4) f32, target ``target_shape(B)`` f32, spec (B, 2 | 4, 4) int32 or None) on the device; no host sync."""
         dev_items, dev_mates, dev_spec, audio, target = self._begin(drawn, audio_out, target_out)
         self._gather(dev_items, audio, dev_mates)
-        if dev_mates is None:
-            labels, tables = ops.corpus_classwise_labels, (dev_items,)
-        else:                                    # time-domain mixing: both sources' audio summed, the targets of the merged events
-            labels, tables = ops.corpus_classwise_labels_mix, (dev_items, dev_mates)
-        if self.yaw is not None:                 # yaw rotation: x and y from the whole-degree tables, each row's yaw in word 7
-            labels = ops.corpus_classwise_labels_yaw if dev_mates is None else ops.corpus_classwise_labels_yaw_mix
-            labels(self.events, *tables, self.xyz, self.rot, self.yaw_xyz, self.max_events, self.n_label_frames, self.nb_classes,
-                   self.loss_nm, target, self.status)
-            return audio, target, dev_spec
-        labels(self.events, *tables, self.xyz, self.max_events, self.n_label_frames, self.nb_classes, self.loss_nm, target,
-               self.status)
+        # with mates (time-domain mixing) the targets of the merged events; with the yaw rotation x and y from the whole-degree
+        # tables, each row's yaw in word 7
+        ops.corpus_classwise_labels(self.events, dev_items, self.xyz, self.max_events, self.n_label_frames, self.nb_classes,
+                                    self.loss_nm, target, self.status, mates=dev_mates,
+                                    rot=self.rot if self.yaw_xyz is not None else None, yaw_xyz=self.yaw_xyz)
         return audio, target, dev_spec
 
 

@@ -7,19 +7,22 @@
 // Every stage has one kernel body with a compile-time MIX parameter.  MIX false is the plain batch: the item table alone, and
 // nothing of a second source in its lanes, LDS or registers.  MIX true is time-domain mixing (aug_config.time_mix_augment: the
 // audio of two chunks summed, their labels united): a second table of mates beside the items, and an item without a mate gets
-// the plain form's bits.
+// the plain form's bits.  Each stage has ONE entry point (adyolo_corpus_gather, adyolo_corpus_yolo_labels,
+// adyolo_corpus_classwise_labels): the table of mates and the yaw are optional arguments, and the entry point picks the kernel
+// instance from which of them it was given.
 //   corpus_gather_kernel<Tab, MIX>   one pass int16 window -> float32 ``x / 32768 + 1e-8``, two frames per iteration from one
 //                                    16-byte load (two 8-byte loads when the window starts on an odd frame), two 16-byte stores.
 //                                    Tab = CorpusRot: FOA channels rotated; CorpusMicSrc: the four MIC capsules permuted
 //                                    (channel swap); CorpusYaw: CorpusRot, then a yaw about the vertical axis by the whole angle
 //                                    in word 7 of the row.  MIX: the mate's window, under its own combination (and yaw), added
 //                                    as a + g * m
-//   corpus_count_scan_kernel<MIX>    one workgroup: rows per lane -- (item, event), or (item, source, event) in merged order --
-//                                    exclusive scan, the total and the overflow bit
-//   corpus_rows_kernel<MIX>          the rows [b, t, gi, gj, cls, U, V] at their scanned offsets, b = -1 in the rest of the capacity
-//   corpus_classwise_kernel<MIX>     the dense SEDDOA / ACCDOA / ADPIT targets (datasets.ClasswiseLabelEncoder): per tile of label
-//                                    frames, each frame's event range per source, the event each (frame, class) output takes,
-//                                    then every output element written once
+//   corpus_count_scan_kernel<MIX, YAW>  one workgroup: rows per lane -- (item, event), or (item, source, event) in merged order
+//                                    -- exclusive scan, the total and the overflow bit
+//   corpus_rows_kernel<MIX, YAW>     the rows [b, t, gi, gj, cls, U, V] at their scanned offsets, b = -1 in the rest of the
+//                                    capacity
+//   corpus_classwise_kernel<MIX, YAW>  the dense SEDDOA / ACCDOA / ADPIT targets (datasets.ClasswiseLabelEncoder): per tile of
+//                                    label frames, each frame's event range per source, the event each (frame, class) output
+//                                    takes, then every output element written once
 // The label kernels have a second compile-time parameter YAW (aug_config.yaw_rotation_augment): each row's azimuths moved by its
 // word 7 after the combination (augmentations.yaw_labels); YAW false is the code without it.
 // Windowed inference (corpus.py InferDeviceCorpus, test.py infer_epoch_corpus) reads the same stream through a window table:
@@ -712,8 +715,8 @@ static void corpus_mic(const unsigned int *src_host, CorpusMicSrc &tab) {
     for (int c = 0; c < 16; ++c) tab.w[c] = src_host[c];
 }
 
-// The launchers behind the entry points of each stage: ``name`` is the entry point called, for its messages; MIX false takes
-// mates == nullptr.
+// The launchers of each stage, one per kernel instance; ``name`` is the entry point, for its messages; MIX false takes mates ==
+// nullptr.  Each entry point below picks its instance in one place: mates given -> MIX, a yaw given -> CorpusYaw / YAW.
 template <class Tab, bool MIX>
 static int corpus_gather_launch(const char *name, const int16_t *pcm, long n_total, const int64_t *items, const int64_t *mates,
                                 int B, long n, const Tab &tab, float *audio, int *status, void *stream) {
@@ -731,7 +734,7 @@ static int corpus_gather_launch(const char *name, const int16_t *pcm, long n_tot
     return check_launch(name);
 }
 
-template <bool MIX, bool YAW = false>
+template <bool MIX, bool YAW>
 static int corpus_yolo_labels_launch(const char *name, const double *events, long n_events, const int64_t *items,
                                      const int64_t *mates, int B, int max_events, int n_label_frames, const double *grid_bounds,
                                      int Gaz, int Gel, const float *rot_host, int *ws, float *target, long cap, int *count,
@@ -765,11 +768,10 @@ static int corpus_yolo_labels_launch(const char *name, const double *events, lon
     return check_launch(name);
 }
 
-template <bool MIX, bool YAW = false>
+template <bool MIX, bool YAW>
 static int corpus_classwise_launch(const char *name, const double *events, const float *xyz, long n_events, const int64_t *items,
                                    const int64_t *mates, int B, int max_events, int n_label_frames, int n_classes, int format,
-                                   float *target, int *status, void *stream,
-                                   typename CorpusYawXyzArg<YAW>::type yaw = typename CorpusYawXyzArg<YAW>::type()) {
+                                   float *target, int *status, void *stream, typename CorpusYawXyzArg<YAW>::type yaw) {
     ADYOLO_REQUIRE(events && xyz && items && (mates || !MIX) && target && status, ADYOLO_EINVAL, "%s: null pointer", name);
     ADYOLO_REQUIRE(B > 0 && B < 65536 && max_events >= 0 && n_events >= 0 && n_events < (1L << (MIX ? CW_SRC_BIT : 31)) &&
                        n_label_frames > 0 && n_classes > 0,
@@ -795,152 +797,64 @@ static int corpus_classwise_launch(const char *name, const double *events, const
 
 using namespace adyolo;
 
-extern "C" int adyolo_corpus_gather(const int16_t *pcm, long n_total, const int64_t *items, int B, long n,
-                                    const float *rot_host, float *audio, int *status, void *stream) {
-    ADYOLO_REQUIRE(rot_host, ADYOLO_EINVAL, "corpus_gather: null pointer");
-    CorpusRot rot;
-    corpus_rot(rot_host, rot);
-    return corpus_gather_launch<CorpusRot, false>("corpus_gather", pcm, n_total, items, nullptr, B, n, rot, audio, status, stream);
-}
-
-extern "C" int adyolo_corpus_gather_mic(const int16_t *pcm, long n_total, const int64_t *items, int B, long n,
-                                        const unsigned int *src_host, float *audio, int *status, void *stream) {
-    ADYOLO_REQUIRE(src_host, ADYOLO_EINVAL, "corpus_gather_mic: null pointer");
-    CorpusMicSrc tab;
-    corpus_mic(src_host, tab);
-    return corpus_gather_launch<CorpusMicSrc, false>("corpus_gather_mic", pcm, n_total, items, nullptr, B, n, tab, audio, status,
-                                                     stream);
-}
-
-extern "C" int adyolo_corpus_gather_mix(const int16_t *pcm, long n_total, const int64_t *items, const int64_t *mates, int B,
-                                        long n, const float *rot_host, const unsigned int *mic_src_host, float *audio,
-                                        int *status, void *stream) {
-    const char *name = "corpus_gather_mix";
+extern "C" int adyolo_corpus_gather(const int16_t *pcm, long n_total, const int64_t *items, const int64_t *mates, int B, long n,
+                                    const float *rot_host, const unsigned int *mic_src_host, const float *yaw_tab, float *audio,
+                                    int *status, void *stream) {
+    const char *name = "corpus_gather";
     ADYOLO_REQUIRE(rot_host || mic_src_host, ADYOLO_EINVAL, "%s: null pointer", name);
     if (mic_src_host) {
+        ADYOLO_REQUIRE(!yaw_tab, ADYOLO_EINVAL, "%s: a yaw table with the MIC form (there is no MIC yaw)", name);
         CorpusMicSrc tab;
         corpus_mic(mic_src_host, tab);
-        return corpus_gather_launch<CorpusMicSrc, true>(name, pcm, n_total, items, mates, B, n, tab, audio, status, stream);
+        return (mates ? corpus_gather_launch<CorpusMicSrc, true> : corpus_gather_launch<CorpusMicSrc, false>)(
+            name, pcm, n_total, items, mates, B, n, tab, audio, status, stream);
+    }
+    if (yaw_tab) {
+        ADYOLO_REQUIRE(((uintptr_t)yaw_tab & 7) == 0, ADYOLO_EINVAL, "%s: misaligned yaw table (8 bytes)", name);
+        CorpusYaw tab;
+        corpus_rot(rot_host, tab.rot);
+        tab.cs = reinterpret_cast<const float2 *>(yaw_tab);
+        return (mates ? corpus_gather_launch<CorpusYaw, true> : corpus_gather_launch<CorpusYaw, false>)(
+            name, pcm, n_total, items, mates, B, n, tab, audio, status, stream);
     }
     CorpusRot rot;
     corpus_rot(rot_host, rot);
-    return corpus_gather_launch<CorpusRot, true>(name, pcm, n_total, items, mates, B, n, rot, audio, status, stream);
+    return (mates ? corpus_gather_launch<CorpusRot, true> : corpus_gather_launch<CorpusRot, false>)(
+        name, pcm, n_total, items, mates, B, n, rot, audio, status, stream);
 }
 
-extern "C" long adyolo_corpus_yolo_labels_workspace_words(int B, int max_events) {
+extern "C" long adyolo_corpus_yolo_labels_workspace_words(int B, int max_events, int mix) {
     if (B <= 0 || max_events < 0) return -1;
-    return (long)B * (max_events > 0 ? max_events : 1);
+    return (long)B * (mix ? 2 : 1) * (max_events > 0 ? max_events : 1);
 }
 
-extern "C" long adyolo_corpus_yolo_labels_mix_workspace_words(int B, int max_events) {
-    if (B <= 0 || max_events < 0) return -1;
-    return (long)B * 2 * (max_events > 0 ? max_events : 1);
+extern "C" int adyolo_corpus_yolo_labels(const double *events, long n_events, const int64_t *items, const int64_t *mates, int B,
+                                         int max_events, int n_label_frames, const double *grid_bounds, int Gaz, int Gel,
+                                         const float *rot_host, int yaw, int *ws, float *target, long cap, int *count,
+                                         int *status, void *stream) {
+    return (mates ? (yaw ? corpus_yolo_labels_launch<true, true> : corpus_yolo_labels_launch<true, false>)
+                  : (yaw ? corpus_yolo_labels_launch<false, true> : corpus_yolo_labels_launch<false, false>))(
+        "corpus_yolo_labels", events, n_events, items, mates, B, max_events, n_label_frames, grid_bounds, Gaz, Gel, rot_host, ws,
+        target, cap, count, status, stream);
 }
 
-extern "C" int adyolo_corpus_yolo_labels(const double *events, long n_events, const int64_t *items, int B, int max_events,
-                                         int n_label_frames, const double *grid_bounds, int Gaz, int Gel,
-                                         const float *rot_host, int *ws, float *target, long cap, int *count, int *status,
-                                         void *stream) {
-    return corpus_yolo_labels_launch<false>("corpus_yolo_labels", events, n_events, items, nullptr, B, max_events, n_label_frames,
-                                            grid_bounds, Gaz, Gel, rot_host, ws, target, cap, count, status, stream);
-}
-
-extern "C" int adyolo_corpus_yolo_labels_mix(const double *events, long n_events, const int64_t *items, const int64_t *mates,
-                                             int B, int max_events, int n_label_frames, const double *grid_bounds, int Gaz,
-                                             int Gel, const float *rot_host, int *ws, float *target, long cap, int *count,
-                                             int *status, void *stream) {
-    return corpus_yolo_labels_launch<true>("corpus_yolo_labels_mix", events, n_events, items, mates, B, max_events,
-                                           n_label_frames, grid_bounds, Gaz, Gel, rot_host, ws, target, cap, count, status, stream);
-}
-
-extern "C" int adyolo_corpus_classwise_labels(const double *events, const float *xyz, long n_events, const int64_t *items, int B,
-                                              int max_events, int n_label_frames, int n_classes, int format, float *target,
-                                              int *status, void *stream) {
-    return corpus_classwise_launch<false>("corpus_classwise_labels", events, xyz, n_events, items, nullptr, B, max_events,
-                                          n_label_frames, n_classes, format, target, status, stream);
-}
-
-extern "C" int adyolo_corpus_classwise_labels_mix(const double *events, const float *xyz, long n_events, const int64_t *items,
-                                                  const int64_t *mates, int B, int max_events, int n_label_frames, int n_classes,
-                                                  int format, float *target, int *status, void *stream) {
-    return corpus_classwise_launch<true>("corpus_classwise_labels_mix", events, xyz, n_events, items, mates, B, max_events,
-                                         n_label_frames, n_classes, format, target, status, stream);
-}
-
-// ------------------------------------------------------------------------------------------------ yaw rotation
-static int corpus_gather_yaw(const char *name, const int16_t *pcm, long n_total, const int64_t *items, const int64_t *mates,
-                             bool mix, int B, long n, const float *rot_host, const float *yaw_tab, float *audio, int *status,
-                             void *stream) {
-    ADYOLO_REQUIRE(rot_host && yaw_tab, ADYOLO_EINVAL, "%s: null pointer", name);
-    ADYOLO_REQUIRE(((uintptr_t)yaw_tab & 7) == 0, ADYOLO_EINVAL, "%s: misaligned yaw table (8 bytes)", name);
-    CorpusYaw tab;
-    corpus_rot(rot_host, tab.rot);
-    tab.cs = reinterpret_cast<const float2 *>(yaw_tab);
-    if (mix) return corpus_gather_launch<CorpusYaw, true>(name, pcm, n_total, items, mates, B, n, tab, audio, status, stream);
-    return corpus_gather_launch<CorpusYaw, false>(name, pcm, n_total, items, nullptr, B, n, tab, audio, status, stream);
-}
-
-extern "C" int adyolo_corpus_gather_yaw(const int16_t *pcm, long n_total, const int64_t *items, int B, long n,
-                                        const float *rot_host, const float *yaw_tab, float *audio, int *status, void *stream) {
-    return corpus_gather_yaw("corpus_gather_yaw", pcm, n_total, items, nullptr, false, B, n, rot_host, yaw_tab, audio, status,
-                             stream);
-}
-
-extern "C" int adyolo_corpus_gather_yaw_mix(const int16_t *pcm, long n_total, const int64_t *items, const int64_t *mates, int B,
-                                            long n, const float *rot_host, const float *yaw_tab, float *audio, int *status,
-                                            void *stream) {
-    return corpus_gather_yaw("corpus_gather_yaw_mix", pcm, n_total, items, mates, true, B, n, rot_host, yaw_tab, audio, status,
-                             stream);
-}
-
-extern "C" int adyolo_corpus_yolo_labels_yaw(const double *events, long n_events, const int64_t *items, int B, int max_events,
-                                             int n_label_frames, const double *grid_bounds, int Gaz, int Gel,
-                                             const float *rot_host, int *ws, float *target, long cap, int *count, int *status,
-                                             void *stream) {
-    return corpus_yolo_labels_launch<false, true>("corpus_yolo_labels_yaw", events, n_events, items, nullptr, B, max_events,
-                                                  n_label_frames, grid_bounds, Gaz, Gel, rot_host, ws, target, cap, count, status,
-                                                  stream);
-}
-
-extern "C" int adyolo_corpus_yolo_labels_yaw_mix(const double *events, long n_events, const int64_t *items, const int64_t *mates,
-                                                 int B, int max_events, int n_label_frames, const double *grid_bounds, int Gaz,
-                                                 int Gel, const float *rot_host, int *ws, float *target, long cap, int *count,
-                                                 int *status, void *stream) {
-    return corpus_yolo_labels_launch<true, true>("corpus_yolo_labels_yaw_mix", events, n_events, items, mates, B, max_events,
-                                                 n_label_frames, grid_bounds, Gaz, Gel, rot_host, ws, target, cap, count, status,
-                                                 stream);
-}
-
-static int corpus_yaw_xyz(const char *name, const float *rot_host, const double *yaw_az, const double *yaw_el, CorpusYawXyz &yaw) {
+extern "C" int adyolo_corpus_classwise_labels(const double *events, const float *xyz, long n_events, const int64_t *items,
+                                              const int64_t *mates, int B, int max_events, int n_label_frames, int n_classes,
+                                              int format, const float *rot_host, const double *yaw_az, const double *yaw_el,
+                                              float *target, int *status, void *stream) {
+    const char *name = "corpus_classwise_labels";
+    if (!yaw_az && !yaw_el)
+        return (mates ? corpus_classwise_launch<true, false> : corpus_classwise_launch<false, false>)(
+            name, events, xyz, n_events, items, mates, B, max_events, n_label_frames, n_classes, format, target, status, stream,
+            CorpusNoYawXyz());
     ADYOLO_REQUIRE(rot_host && yaw_az && yaw_el, ADYOLO_EINVAL, "%s: null pointer", name);
     ADYOLO_REQUIRE(((uintptr_t)yaw_az & 7) == 0 && ((uintptr_t)yaw_el & 7) == 0, ADYOLO_EINVAL, "%s: misaligned yaw tables", name);
+    CorpusYawXyz yaw;
     corpus_rot(rot_host, yaw.rot);
     yaw.az = yaw_az;
     yaw.el = yaw_el;
-    return 0;
-}
-
-extern "C" int adyolo_corpus_classwise_labels_yaw(const double *events, const float *xyz, long n_events, const int64_t *items,
-                                                  int B, int max_events, int n_label_frames, int n_classes, int format,
-                                                  const float *rot_host, const double *yaw_az, const double *yaw_el,
-                                                  float *target, int *status, void *stream) {
-    CorpusYawXyz yaw;
-    const int rc = corpus_yaw_xyz("corpus_classwise_labels_yaw", rot_host, yaw_az, yaw_el, yaw);
-    if (rc) return rc;
-    return corpus_classwise_launch<false, true>("corpus_classwise_labels_yaw", events, xyz, n_events, items, nullptr, B,
-                                                max_events, n_label_frames, n_classes, format, target, status, stream, yaw);
-}
-
-extern "C" int adyolo_corpus_classwise_labels_yaw_mix(const double *events, const float *xyz, long n_events,
-                                                      const int64_t *items, const int64_t *mates, int B, int max_events,
-                                                      int n_label_frames, int n_classes, int format, const float *rot_host,
-                                                      const double *yaw_az, const double *yaw_el, float *target, int *status,
-                                                      void *stream) {
-    CorpusYawXyz yaw;
-    const int rc = corpus_yaw_xyz("corpus_classwise_labels_yaw_mix", rot_host, yaw_az, yaw_el, yaw);
-    if (rc) return rc;
-    return corpus_classwise_launch<true, true>("corpus_classwise_labels_yaw_mix", events, xyz, n_events, items, mates, B,
-                                               max_events, n_label_frames, n_classes, format, target, status, stream, yaw);
+    return (mates ? corpus_classwise_launch<true, true> : corpus_classwise_launch<false, true>)(
+        name, events, xyz, n_events, items, mates, B, max_events, n_label_frames, n_classes, format, target, status, stream, yaw);
 }
 
 // ------------------------------------------------------------------------------------------------ windowed inference

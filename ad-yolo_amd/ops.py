@@ -1785,13 +1785,33 @@ def _corpus_gather_args(name, pcm, items, out, status, mates=None):
     return b
 
 
-def corpus_gather(pcm, items, rot, out, status):
+def _host_table(tab):
+    return NULL if tab is None else ctypes.cast(tab, ctypes.c_void_p)
+
+
+def corpus_gather(pcm, items, rot, out, status, *, mates=None, mic_src=None, yaw_tab=None):
     """pcm int16 (S, 4) and items int64 (B, 8) on the device -> out (B, n, 4) float32: the int16 windows at the items' sample
-    offsets as ``x / 32768 + 1e-8``, FOA-rotated by their combinations (adyolo_hip.h ``adyolo_corpus_gather``).  rot:
-    ``corpus_rot_table``; status: int32 word on the device the call ORs its bits into.  No allocation, no sync."""
-    b = _corpus_gather_args("corpus_gather", pcm, items, out, status)
-    _c("adyolo_corpus_gather", _p(pcm), pcm.shape[0], _p(items), b, out.shape[1], ctypes.cast(rot, ctypes.c_void_p), _p(out),
-       _p(status), _stream())
+    offsets as ``x / 32768 + 1e-8`` (adyolo_hip.h ``adyolo_corpus_gather``), then
+    * FOA-rotated by their combinations (rot: ``corpus_rot_table``), or
+    * ``mic_src`` (``corpus_mic_table``; rot may be None): MIC-format audio, the four capsules permuted by the combinations
+      instead -- bit for bit ``pcm16_to_f32`` then ``mic_swap``; a combination that is no symmetry: a bad item;
+    * ``yaw_tab`` (``corpus_yaw_table``; FOA only): every source yawed after its combination by word 7 of its row, whole degrees
+      in [-180, 180) -- bit for bit ``pcm16_to_f32`` then ``augmentations.rotate_audio_yaw``; a yaw outside the range: a bad item;
+    * ``mates`` int64 (B, 8) on the device: a second window per item summed in, rows like ``items`` with their own combinations
+      (and yaws), the float32 bits of the gain in word 6, offset -1 = no mate -> out = a + g * m, bit for bit two plain gathers
+      and that expression on float32 tensors.
+    A bad item or mate: zeros for the sample and status bit 2.  status: int32 word on the device the call ORs its bits into.  No
+    allocation, no sync."""
+    name = "corpus_gather"
+    b = _corpus_gather_args(name, pcm, items, out, status, mates)
+    if mic_src is None and rot is None:
+        raise _lib.AdyoloHipError("%s: the FOA form needs the rotation table" % name)
+    if yaw_tab is not None:
+        if mic_src is not None:
+            raise _lib.AdyoloHipError("%s: yaw_tab with mic_src (there is no MIC yaw)" % name)
+        _corpus_yaw_tab(name, yaw_tab, pcm.device, torch.float32, (360, 2))
+    _c("adyolo_corpus_gather", _p(pcm), pcm.shape[0], _p(items), _p(mates), b, out.shape[1], _host_table(rot),
+       _host_table(mic_src), _p(yaw_tab), _p(out), _p(status), _stream())
     return out
 
 
@@ -1800,7 +1820,7 @@ MIC_SWAP_NONE = 0xFFFFFFFF                                # ADYOLO_MIC_SWAP_NONE
 
 def corpus_mic_table(sources):
     """{combination: (s0, s1, s2, s3)} (``augmentations.mic_swap_source`` of every symmetry) -> the host table uint32 [16] of
-    ``adyolo_corpus_gather_mic``: s_j in bits [8 j, 8 j + 2), ``MIC_SWAP_NONE`` for every other combination."""
+    ``corpus_gather``'s ``mic_src``: s_j in bits [8 j, 8 j + 2), ``MIC_SWAP_NONE`` for every other combination."""
     words = [MIC_SWAP_NONE] * 16
     for comb, src in sources.items():
         src = tuple(int(v) for v in src)
@@ -1808,31 +1828,6 @@ def corpus_mic_table(sources):
             raise ValueError("corpus_mic_table: combination %r -> %r is not a permutation of the four channels" % (comb, src))
         words[int(comb)] = src[0] | src[1] << 8 | src[2] << 16 | src[3] << 24
     return (ctypes.c_uint32 * 16)(*words)
-
-
-def corpus_gather_mic(pcm, items, src, out, status):
-    """``corpus_gather`` for MIC-format audio: the windows' four capsules permuted by the items' combinations instead of rotated
-    (adyolo_hip.h ``adyolo_corpus_gather_mic``; bit for bit ``pcm16_to_f32`` then ``mic_swap``).  src: ``corpus_mic_table``; an
-    item whose combination is no symmetry gets zeros and sets status bit 2.  No allocation, no sync."""
-    b = _corpus_gather_args("corpus_gather_mic", pcm, items, out, status)
-    _c("adyolo_corpus_gather_mic", _p(pcm), pcm.shape[0], _p(items), b, out.shape[1], ctypes.cast(src, ctypes.c_void_p), _p(out),
-       _p(status), _stream())
-    return out
-
-
-def corpus_gather_mix(pcm, items, mates, rot, mic_src, out, status):
-    """``corpus_gather`` (``mic_src`` None; rot: ``corpus_rot_table``) or ``corpus_gather_mic`` (mic_src: ``corpus_mic_table``) with
-    a second window per item summed in: mates int64 (B, 8) on the device, rows like ``items`` with their own combinations, the
-    float32 bits of the gain in word 6, offset -1 = no mate -> out = a + g * m, bit for bit two plain gathers and that
-    expression on float32 tensors (adyolo_hip.h ``adyolo_corpus_gather_mix``).  A bad item or mate: zeros for the sample and
-    status bit 2.  No allocation, no sync."""
-    b = _corpus_gather_args("corpus_gather_mix", pcm, items, out, status, mates)
-    if mic_src is None and rot is None:
-        raise _lib.AdyoloHipError("corpus_gather_mix: the FOA form needs the rotation table")
-    _c("adyolo_corpus_gather_mix", _p(pcm), pcm.shape[0], _p(items), _p(mates), b, out.shape[1],
-       NULL if rot is None else ctypes.cast(rot, ctypes.c_void_p),
-       NULL if mic_src is None else ctypes.cast(mic_src, ctypes.c_void_p), _p(out), _p(status), _stream())
-    return out
 
 
 def audio_mix(audio, mate, gains, mixed, out=None):
@@ -1877,12 +1872,8 @@ def mic_swap(audio, src, out=None):
     return out
 
 
-def corpus_labels_workspace_words(batch, max_events):
-    return int(_lib.load().adyolo_corpus_yolo_labels_workspace_words(int(batch), int(max_events)))
-
-
-def corpus_labels_mix_workspace_words(batch, max_events):
-    return int(_lib.load().adyolo_corpus_yolo_labels_mix_workspace_words(int(batch), int(max_events)))
+def corpus_labels_workspace_words(batch, max_events, mix=False):
+    return int(_lib.load().adyolo_corpus_yolo_labels_workspace_words(int(batch), int(max_events), int(bool(mix))))
 
 
 def _corpus_events(name, events, items, mates):
@@ -1905,33 +1896,27 @@ def _corpus_yolo_args(name, events, items, max_events, bounds, grid, ws, target,
     _chk(target)
     if target.dim() != 2 or target.shape[1] != 7:
         raise _lib.AdyoloHipError("%s: target %s is not (cap, 7)" % (name, tuple(target.shape)))
-    ws_words = (corpus_labels_workspace_words if mates is None else corpus_labels_mix_workspace_words)(b, max_events)
+    ws_words = corpus_labels_workspace_words(b, max_events, mix=mates is not None)
     for what, t, words in (("ws", ws, ws_words), ("count", count, 1), ("status", status, 1)):
         if t.dtype != torch.int32 or t.device != dev or not t.is_contiguous() or t.numel() < words:
             raise _lib.AdyoloHipError("%s: %s must be at least %d int32 words on %s" % (name, what, words, dev))
     return b, n_ev, gaz, gel
 
 
-def corpus_yolo_labels(events, items, max_events, n_label_frames, bounds, grid, rot, ws, target, count, status):
+def corpus_yolo_labels(events, items, max_events, n_label_frames, bounds, grid, rot, ws, target, count, status, *, mates=None,
+                       yaw=False):
     """The AD-YOLO rows of a batch on the device (adyolo_hip.h ``adyolo_corpus_yolo_labels``): events float64 (E, 4) {frame,
     class, az, el}, items int64 (B, 8), bounds float64 (2 Gaz + 2 Gel,), grid (Gaz, Gel), ws int32 of
-    ``corpus_labels_workspace_words`` words -> target (cap, 7) float32 (b = -1 past the total), count int32 word = total rows.
-    status: int32 word the call ORs its bits into.  No allocation, no sync."""
-    b, n_ev, gaz, gel = _corpus_yolo_args("corpus_yolo_labels", events, items, max_events, bounds, grid, ws, target, count, status)
-    _c("adyolo_corpus_yolo_labels", _p(events), n_ev, _p(items), b, int(max_events), int(n_label_frames), _p(bounds), gaz, gel,
-       ctypes.cast(rot, ctypes.c_void_p), _p(ws), _p(target), target.shape[0], _p(count), _p(status), _stream())
-    return target
-
-
-def corpus_yolo_labels_mix(events, items, mates, max_events, n_label_frames, bounds, grid, rot, ws, target, count, status):
-    """``corpus_yolo_labels`` for mixed items: the rows of ``augmentations.merge_labels(item, mate)`` per item, each event under
-    its own source's combination and frame offset, column 0 the item (adyolo_hip.h ``adyolo_corpus_yolo_labels_mix``).  mates
-    int64 (B, 8) as for ``corpus_gather_mix``; ws int32 of ``corpus_labels_mix_workspace_words`` words.  No allocation, no sync."""
-    b, n_ev, gaz, gel = _corpus_yolo_args("corpus_yolo_labels_mix", events, items, max_events, bounds, grid, ws, target, count,
-                                          status, mates)
-    _c("adyolo_corpus_yolo_labels_mix", _p(events), n_ev, _p(items), _p(mates), b, int(max_events), int(n_label_frames),
-       _p(bounds), gaz, gel, ctypes.cast(rot, ctypes.c_void_p), _p(ws), _p(target), target.shape[0], _p(count), _p(status),
-       _stream())
+    ``corpus_labels_workspace_words(B, max_events, mix=mates is not None)`` words -> target (cap, 7) float32 (b = -1 past the
+    total), count int32 word = total rows.  ``mates`` (as for ``corpus_gather``): the rows of ``augmentations.merge_labels(item,
+    mate)`` per item, each event under its own source's combination and frame offset, column 0 the item.  ``yaw``:
+    ``augmentations.yaw_labels`` by word 7 of each row after its combination.  status: int32 word the call ORs its bits into.
+    No allocation, no sync."""
+    b, n_ev, gaz, gel = _corpus_yolo_args("corpus_yolo_labels", events, items, max_events, bounds, grid, ws, target, count, status,
+                                          mates)
+    _c("adyolo_corpus_yolo_labels", _p(events), n_ev, _p(items), _p(mates), b, int(max_events),
+       int(n_label_frames), _p(bounds), gaz, gel, ctypes.cast(rot, ctypes.c_void_p), int(bool(yaw)), _p(ws), _p(target),
+       target.shape[0], _p(count), _p(status), _stream())
     return target
 
 
@@ -1962,44 +1947,43 @@ def _corpus_classwise_args(name, events, items, xyz, n_label_frames, nb_classes,
     return b, n_ev
 
 
-def corpus_classwise_labels(events, items, xyz, max_events, n_label_frames, nb_classes, loss, target, status):
+def corpus_classwise_labels(events, items, xyz, max_events, n_label_frames, nb_classes, loss, target, status, *, mates=None,
+                            rot=None, yaw_xyz=None):
     """The dense class-wise targets of a batch on the device (adyolo_hip.h ``adyolo_corpus_classwise_labels``): events float64
     (E, 4) {frame, class, az, el}, items int64 (B, 8), xyz float32 (E, 17, 3) (``corpus.xyz_table``) -> target float32 of
-    ``corpus_classwise_shape(loss, B, n_label_frames, nb_classes)``, every element written.  status: int32 word the call ORs its
-    bits into.  No allocation, no sync."""
-    b, n_ev = _corpus_classwise_args("corpus_classwise_labels", events, items, xyz, n_label_frames, nb_classes, loss, target,
-                                     status)
-    _c("adyolo_corpus_classwise_labels", _p(events), _p(xyz), n_ev, _p(items), b, int(max_events), int(n_label_frames),
-       int(nb_classes), CORPUS_FORMATS[loss], _p(target), _p(status), _stream())
+    ``corpus_classwise_shape(loss, B, n_label_frames, nb_classes)``, every element written.  ``mates`` (as for
+    ``corpus_gather``): the targets of the host encoders on ``augmentations.merge_labels(item, mate)``, each event's direction
+    vector from its own source's combination.  ``yaw_xyz`` (``corpus_yaw_xyz_tables``; needs rot: ``corpus_rot_table``): yawed
+    sources (word 7 of each row), z from the event's xyz slot, x and y from the tables at the event's moved whole-degree angles.
+    status: int32 word the call ORs its bits into.  No allocation, no sync."""
+    name = "corpus_classwise_labels"
+    b, n_ev = _corpus_classwise_args(name, events, items, xyz, n_label_frames, nb_classes, loss, target, status, mates)
+    az = el = None
+    if yaw_xyz is not None:
+        if rot is None:
+            raise _lib.AdyoloHipError("%s: yaw_xyz needs the rotation table" % name)
+        az, el = _corpus_yaw_xyz_args(name, yaw_xyz, items.device)
+    _c("adyolo_corpus_classwise_labels", _p(events), _p(xyz), n_ev, _p(items), _p(mates), b,
+       int(max_events), int(n_label_frames), int(nb_classes), CORPUS_FORMATS[loss], _host_table(rot), _p(az), _p(el), _p(target),
+       _p(status), _stream())
     return target
 
 
-def corpus_classwise_labels_mix(events, items, mates, xyz, max_events, n_label_frames, nb_classes, loss, target, status):
-    """``corpus_classwise_labels`` for mixed items: the dense targets of the host encoders on ``augmentations.merge_labels(item,
-    mate)``, each event's direction vector from its own source's combination (adyolo_hip.h ``adyolo_corpus_classwise_labels_mix``).
-    mates int64 (B, 8) as for ``corpus_gather_mix``.  No allocation, no sync."""
-    b, n_ev = _corpus_classwise_args("corpus_classwise_labels_mix", events, items, xyz, n_label_frames, nb_classes, loss, target,
-                                     status, mates)
-    _c("adyolo_corpus_classwise_labels_mix", _p(events), _p(xyz), n_ev, _p(items), _p(mates), b, int(max_events),
-       int(n_label_frames), int(nb_classes), CORPUS_FORMATS[loss], _p(target), _p(status), _stream())
-    return target
-
-
-# ---- yaw rotation (aug_config.yaw_rotation_augment): the *_yaw forms read each row's yaw, whole degrees, from word 7
+# ---- yaw rotation (aug_config.yaw_rotation_augment): with a yaw table the calls read each row's yaw, whole degrees, from word 7
 CORPUS_YAW_WORD = 7                                       # ADYOLO_CORPUS_YAW_WORD
 
 
 def corpus_yaw_table(device):
-    """float32 (360, 2) on ``device``: {cos, sin} of the yaws -180 .. 179 degrees (``augmentations.yaw_cos_sin``), the table of
-    ``corpus_gather_yaw``."""
+    """float32 (360, 2) on ``device``: {cos, sin} of the yaws -180 .. 179 degrees (``augmentations.yaw_cos_sin``), the
+    ``yaw_tab`` of ``corpus_gather``."""
     from .augmentations import yaw_cos_sin
     return torch.tensor([[float(v) for v in yaw_cos_sin(phi)] for phi in range(-180, 180)], dtype=torch.float32).to(device)
 
 
 def corpus_yaw_xyz_tables(device):
     """(az float64 (361, 2) = {cos, sin} of the azimuths -180 .. 180 degrees, el float64 (181,) = cos of the elevations -90 ..
-    90) on ``device``, each value by the expressions of ``datasets._polar_to_xyz`` on a Python float: the tables of
-    ``corpus_classwise_labels_yaw``."""
+    90) on ``device``, each value by the expressions of ``datasets._polar_to_xyz`` on a Python float: the ``yaw_xyz`` of
+    ``corpus_classwise_labels``."""
     import numpy as np
     az = [[float(np.cos(float(a) * np.pi / 180)), float(np.sin(float(a) * np.pi / 180))] for a in range(-180, 181)]
     el = [float(np.cos(float(e) * np.pi / 180.0)) for e in range(-90, 91)]
@@ -2011,77 +1995,11 @@ def _corpus_yaw_tab(name, tab, device, dtype, shape):
         raise _lib.AdyoloHipError("%s: the yaw table must be a contiguous %s tensor %s on %s" % (name, dtype, shape, device))
 
 
-def corpus_gather_yaw(pcm, items, rot, yaw_tab, out, status):
-    """``corpus_gather`` with every item yawed after its combination by word 7 of its row, whole degrees in [-180, 180) (adyolo_hip.h
-    ``adyolo_corpus_gather_yaw``; bit for bit ``pcm16_to_f32`` then ``augmentations.rotate_audio_yaw``).  yaw_tab:
-    ``corpus_yaw_table``; a yaw outside the range: zeros for the item and status bit 2.  No allocation, no sync."""
-    b = _corpus_gather_args("corpus_gather_yaw", pcm, items, out, status)
-    _corpus_yaw_tab("corpus_gather_yaw", yaw_tab, pcm.device, torch.float32, (360, 2))
-    _c("adyolo_corpus_gather_yaw", _p(pcm), pcm.shape[0], _p(items), b, out.shape[1], ctypes.cast(rot, ctypes.c_void_p),
-       _p(yaw_tab), _p(out), _p(status), _stream())
-    return out
-
-
-def corpus_gather_yaw_mix(pcm, items, mates, rot, yaw_tab, out, status):
-    """``corpus_gather_mix`` (FOA form) with item and mate each under its own combination and its own yaw (word 7 of either row;
-    word 6 of a mate stays the gain) (adyolo_hip.h ``adyolo_corpus_gather_yaw_mix``).  No allocation, no sync."""
-    b = _corpus_gather_args("corpus_gather_yaw_mix", pcm, items, out, status, mates)
-    _corpus_yaw_tab("corpus_gather_yaw_mix", yaw_tab, pcm.device, torch.float32, (360, 2))
-    _c("adyolo_corpus_gather_yaw_mix", _p(pcm), pcm.shape[0], _p(items), _p(mates), b, out.shape[1],
-       ctypes.cast(rot, ctypes.c_void_p), _p(yaw_tab), _p(out), _p(status), _stream())
-    return out
-
-
-def corpus_yolo_labels_yaw(events, items, max_events, n_label_frames, bounds, grid, rot, ws, target, count, status):
-    """``corpus_yolo_labels`` with ``augmentations.yaw_labels`` by word 7 of each row after its combination (adyolo_hip.h
-    ``adyolo_corpus_yolo_labels_yaw``).  The same workspace.  No allocation, no sync."""
-    name = "corpus_yolo_labels_yaw"
-    b, n_ev, gaz, gel = _corpus_yolo_args(name, events, items, max_events, bounds, grid, ws, target, count, status)
-    _c("adyolo_" + name, _p(events), n_ev, _p(items), b, int(max_events), int(n_label_frames), _p(bounds), gaz, gel,
-       ctypes.cast(rot, ctypes.c_void_p), _p(ws), _p(target), target.shape[0], _p(count), _p(status), _stream())
-    return target
-
-
-def corpus_yolo_labels_yaw_mix(events, items, mates, max_events, n_label_frames, bounds, grid, rot, ws, target, count, status):
-    """``corpus_yolo_labels_mix`` with each source's events yawed by its own row's word 7 after its combination (adyolo_hip.h
-    ``adyolo_corpus_yolo_labels_yaw_mix``).  The same workspace.  No allocation, no sync."""
-    name = "corpus_yolo_labels_yaw_mix"
-    b, n_ev, gaz, gel = _corpus_yolo_args(name, events, items, max_events, bounds, grid, ws, target, count, status, mates)
-    _c("adyolo_" + name, _p(events), n_ev, _p(items), _p(mates), b, int(max_events), int(n_label_frames), _p(bounds), gaz, gel,
-       ctypes.cast(rot, ctypes.c_void_p), _p(ws), _p(target), target.shape[0], _p(count), _p(status), _stream())
-    return target
-
-
 def _corpus_yaw_xyz_args(name, yaw_xyz, device):
     az, el = yaw_xyz
     _corpus_yaw_tab(name, az, device, torch.float64, (361, 2))
     _corpus_yaw_tab(name, el, device, torch.float64, (181,))
     return az, el
-
-
-def corpus_classwise_labels_yaw(events, items, xyz, rot, yaw_xyz, max_events, n_label_frames, nb_classes, loss, target, status):
-    """``corpus_classwise_labels`` for yawed items (word 7 of each row): z from the event's xyz slot, x and y from ``yaw_xyz``
-    (``corpus_yaw_xyz_tables``) at the event's moved whole-degree angles (adyolo_hip.h ``adyolo_corpus_classwise_labels_yaw``).
-    rot: ``corpus_rot_table``.  No allocation, no sync."""
-    name = "corpus_classwise_labels_yaw"
-    b, n_ev = _corpus_classwise_args(name, events, items, xyz, n_label_frames, nb_classes, loss, target, status)
-    az, el = _corpus_yaw_xyz_args(name, yaw_xyz, items.device)
-    _c("adyolo_" + name, _p(events), _p(xyz), n_ev, _p(items), b, int(max_events), int(n_label_frames), int(nb_classes),
-       CORPUS_FORMATS[loss], ctypes.cast(rot, ctypes.c_void_p), _p(az), _p(el), _p(target), _p(status), _stream())
-    return target
-
-
-def corpus_classwise_labels_yaw_mix(events, items, mates, xyz, rot, yaw_xyz, max_events, n_label_frames, nb_classes, loss, target,
-                                    status):
-    """``corpus_classwise_labels_mix`` for yawed sources, each under its own row's combination and yaw (adyolo_hip.h
-    ``adyolo_corpus_classwise_labels_yaw_mix``).  No allocation, no sync."""
-    name = "corpus_classwise_labels_yaw_mix"
-    b, n_ev = _corpus_classwise_args(name, events, items, xyz, n_label_frames, nb_classes, loss, target, status, mates)
-    az, el = _corpus_yaw_xyz_args(name, yaw_xyz, items.device)
-    _c("adyolo_" + name, _p(events), _p(xyz), n_ev, _p(items), _p(mates), b, int(max_events), int(n_label_frames),
-       int(nb_classes), CORPUS_FORMATS[loss], ctypes.cast(rot, ctypes.c_void_p), _p(az), _p(el), _p(target), _p(status),
-       _stream())
-    return target
 
 
 WINDOW_WORDS = 8                                          # ADYOLO_WINDOW_WORDS: {offset, valid, src_lo, dst, n, recording, 0, 0}

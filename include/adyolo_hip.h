@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define ADYOLO_ABI_VERSION 3
+#define ADYOLO_ABI_VERSION 4
 #define ADYOLO_EINVAL (-1)   /* bad shape / alignment / null pointer */
 #define ADYOLO_ENOSUP (-2)   /* shape outside what the kernels are built for */
 
@@ -684,7 +684,7 @@ int adyolo_foa_rotate_yaw(const float *audio, float *out, const float *cfg, int 
 int adyolo_mic_swap(const float *audio, float *out, const int *src_dev, int B, long n_samples, void *stream);
 
 /* Time-domain mixing on raw audio (aug_config.time_mix_augment, the host-fed path; the corpus paths mix inside
- * adyolo_corpus_gather_mix): audio / mate / out [B][n_samples][4] float32, 16-byte aligned; gains DEVICE float [B]; mixed DEVICE
+ * adyolo_corpus_gather): audio / mate / out [B][n_samples][4] float32, 16-byte aligned; gains DEVICE float [B]; mixed DEVICE
  * bytes [B] (0: the clip is not mixed).  out[b] = mixed[b] ? audio[b] + gains[b] * mate[b] : audio[b], the product rounded to
  * float32 before the sum (no FMA: the bits of ``audio + gain * mate`` on float32 tensors).  An unmixed clip is moved, not
  * computed on (NaN payloads and -0.0 keep their bits), and its mate and gain are not read.  out may be audio itself (in place)
@@ -702,24 +702,49 @@ int adyolo_audio_mix(const float *audio, const float *mate, const float *gains, 
  *   rot_host HOST float [16][ADYOLO_CORPUS_ROT_WORDS] = {sign_y, sign_z, sign_x, swap_xy, azimuth weight, azimuth offset,
  *            elevation weight, 0} per combination (augmentations.COMBINATIONS; passed by value: capturable)
  *   status   DEVICE int32 word the calls OR their ADYOLO_CORPUS_* bits into (never cleared by them)
- * adyolo_corpus_gather: audio [B][n][4] float32 = the int16 frames pcm[off .. off + n) (W,Y,Z,X) as x / 32768 + 1e-8, rotated
- *   like adyolo_foa_rotate -- bit for bit adyolo_pcm16_to_f32 followed by adyolo_foa_rotate.  pcm [n_total][4] int16, 16-byte
- *   aligned; an item outside it gets zeros and sets ADYOLO_CORPUS_BAD_ITEM.
- * adyolo_corpus_gather_mic: the MIC form of adyolo_corpus_gather over the same items: audio [B][n][4] float32 = the int16 frames
- *   pcm[off .. off + n) (capsules M1..M4) with the channels permuted by the item's combination, then x / 32768 + 1e-8 -- bit for
- *   bit adyolo_pcm16_to_f32 followed by adyolo_mic_swap.  src_host HOST uint32 [16], one word per combination: source channel
- *   s_j of output channel j in bits [8 j, 8 j + 2) (augmentations.mic_swap_source; passed by value: capturable), or
- *   ADYOLO_MIC_SWAP_NONE where the combination is no symmetry of the array.  comb < 0: no permutation (the bits of
- *   adyolo_corpus_gather with comb < 0).  comb >= 16, a combination marked ADYOLO_MIC_SWAP_NONE or an item outside pcm: zeros
- *   for that item and ADYOLO_CORPUS_BAD_ITEM.  The label calls below are the same for both formats.
+ * Each stage has one entry point.  Two optional arguments, the same for every stage, select its form:
+ *   mates    NULL: a plain batch.  Else time-domain mixing (aug_config.time_mix_augment: the audio of two chunks summed, their
+ *            labels united): DEVICE int64 [B][ADYOLO_CORPUS_ITEM_WORDS], the chunk mixed into item b as an item row with its own
+ *            combination; word 0 (sample offset) exactly -1: item b has no mate and the rest of the row is not read; any other
+ *            offset outside pcm is a bad item; word 6: the bit pattern of the float32 gain g (zero-extended).  An item without a
+ *            mate gets the plain form's bits.
+ *   a yaw    (aug_config.yaw_rotation_augment, FOA only; gather: yaw_tab, AD-YOLO labels: the flag ``yaw``, class-wise labels:
+ *            yaw_az + yaw_el) absent: word 7 of the rows is never read.  Else every source is turned about the vertical axis
+ *            after its combination by its own yaw, word ADYOLO_CORPUS_YAW_WORD (7) of the item row and of the mate row (word 6
+ *            of a mate stays the gain): WHOLE DEGREES as a signed integer, legal in [-180, 180); 0 turns nothing.  A row whose
+ *            yaw is outside that range is a bad item, as a combination >= 16 is.
+ * adyolo_corpus_gather: audio [B][n][4] float32 = the int16 frames pcm[off .. off + n) as x / 32768 + 1e-8, then
+ *     mic_src_host NULL (the FOA form; rot_host required): channels (W,Y,Z,X) rotated like adyolo_foa_rotate -- bit for bit
+ *       adyolo_pcm16_to_f32 followed by adyolo_foa_rotate;
+ *     mic_src_host given (the MIC form; rot_host is not read): the capsules M1..M4 permuted by the item's combination -- bit for
+ *       bit adyolo_pcm16_to_f32 followed by adyolo_mic_swap.  mic_src_host HOST uint32 [16], one word per combination: source
+ *       channel s_j of output channel j in bits [8 j, 8 j + 2) (augmentations.mic_swap_source; passed by value: capturable), or
+ *       ADYOLO_MIC_SWAP_NONE where the combination is no symmetry of the array, which makes the item a bad one.  comb < 0: no
+ *       permutation (the bits of the FOA form with comb < 0).  The label calls are the same for both formats;
+ *     yaw_tab given (FOA form only: with mic_src_host EINVAL -- there is no MIC yaw): each source's frames yawed after its
+ *       combination -- bit for bit adyolo_pcm16_to_f32 -> adyolo_foa_rotate_yaw.  yaw_tab DEVICE float [360][2] = {cos, sin} of
+ *       the yaws -180 .. 179 (augmentations.yaw_cos_sin), 8-byte aligned; entry yaw + 180 is read once per workgroup.  comb < 0:
+ *       the yaw alone;
+ *     mates given: audio [b] = a + g * m, where a is what the call writes for item b without mates and m what it would write
+ *       for the mate row, each under its own combination (and yaw); the product is rounded to float32 before the sum (no FMA):
+ *       bit for bit two gathers and ``a + g * m`` on float32 tensors.  An item without a mate costs the plain gather's bytes.
+ *   pcm [n_total][4] int16, 16-byte aligned; an item (or its mate) outside it, a combination >= 16: zeros for the whole sample
+ *   and ADYOLO_CORPUS_BAD_ITEM.  One pass; every parity of the two offsets and an odd n are legal.
  * adyolo_corpus_yolo_labels: the AD-YOLO rows of the batch (datasets.get_yolo_label + collate_fn): per item, per event
  *   [b, frame - frame offset, gi, gj, cls, U, V] for every responsible cell in (gi, gj) order, the rotation of
  *   augmentations.rotate_labels and the cell test of YoloLabelEncoder.encode_events in double, events whose relative frame is
  *   >= n_label_frames dropped.  events DEVICE double [n_events][4] = {frame, class, azimuth, elevation}; grid_bounds DEVICE
  *   double [2 Gaz + 2 Gel] = az_lb, az_ub, el_lb, el_ub (YoloLabelEncoder); target [cap][7] float32: the first count[0] rows
  *   written (at most cap; more sets ADYOLO_CORPUS_OVERFLOW, the rows past cap are dropped), b = -1 in the others (the loss
- *   skips them); ws adyolo_corpus_yolo_labels_workspace_words(B, max_events) int32 words; max_events >= every item's event
- *   count (a larger count sets ADYOLO_CORPUS_BAD_ITEM and the item gets no rows).  Gaz, Gel <= 64, else ENOSUP.
+ *   skips them); ws adyolo_corpus_yolo_labels_workspace_words(B, max_events, mix) int32 words, mix = mates given: B (mix ? 2 :
+ *   1) max(max_events, 1), -1 for B <= 0 or max_events < 0; max_events >= every item's (and mate's) event count (a larger count
+ *   sets ADYOLO_CORPUS_BAD_ITEM and the item gets no rows).  Gaz, Gel <= 64, else ENOSUP.
+ *     mates given: the rows of augmentations.merge_labels(item, mate) per item: frames ascending, the item's events before the
+ *       mate's within a frame (both sources' events must be frame-sorted, as load_chunked_split leaves them), each event rotated
+ *       by its own source's combination and counted from its own source's frame offset; column 0 is the item for both.  An
+ *       item whose own row or mate row is bad gets no rows at all.  An all-unmixed batch equals the plain rows.
+ *     yaw != 0: augmentations.yaw_labels after the combination's arithmetic: az = az + yaw, then < -180: += 360, > 180: -= 360,
+ *       in double and uncontracted, before the 180 -> -180 rule of the encoder.  Any angles.
  * adyolo_corpus_classwise_labels: the dense SEDDOA / ACCDOA / ADPIT targets of the batch (augmentations.rotate_labels, then
  *   datasets.ClasswiseLabelEncoder, stacked over the batch), every element of target written exactly once, zeros included:
  *     format ADYOLO_CORPUS_SEDDOA  target [B][n_label_frames][4 C]        = [se, x, y, z], the last event of a class in a frame
@@ -732,48 +757,20 @@ int adyolo_audio_mix(const float *audio, const float *mate, const float *gains, 
  *   dropped; an event whose class is outside [0, C) is dropped and sets ADYOLO_CORPUS_BAD_CLASS; an item outside the corpus
  *   (as for the rows, max_events included) gets an all-zero target and sets ADYOLO_CORPUS_BAD_ITEM.  No workspace, no
  *   atomics on the target: capturable, and the target may be a recorded step's static buffer.  C <= 256, else ENOSUP.
- *
- * Time-domain mixing (aug_config.time_mix_augment): the audio of two chunks summed, their labels united.  The *_mix calls take
- * the item table and a second table of the same shape and layout:
- *   mates    DEVICE int64 [B][ADYOLO_CORPUS_ITEM_WORDS]: the chunk mixed into item b, as an item row with its own combination;
- *            word 0 (sample offset) exactly -1: item b has no mate and the rest of the row is not read; any other offset outside
- *            pcm is a bad item; word 6: the bit pattern of the float32 gain g (zero-extended).
- * adyolo_corpus_gather_mix: audio [b] = a + g * m, where a is what adyolo_corpus_gather (mic_src_host NULL; rot_host needed) or
- *   adyolo_corpus_gather_mic (mic_src_host given; rot_host not read) writes for item b and m what it would write for the mate
- *   row, each under its own combination; the product is rounded to float32 before the sum (no FMA): bit for bit two gathers
- *   and ``a + g * m`` on float32 tensors.  An item without a mate has the plain gather's bits and costs its bytes.  A bad item or
- *   a bad mate: zeros for the whole sample and ADYOLO_CORPUS_BAD_ITEM.  One pass; every parity of the two offsets is legal.
- * adyolo_corpus_yolo_labels_mix: the rows of augmentations.merge_labels(item, mate) per item: frames ascending, the item's
- *   events before the mate's within a frame (both sources' events must be frame-sorted, as load_chunked_split leaves them), each
- *   event rotated by its own source's combination and counted from its own source's frame offset; column 0 is the item for
- *   both.  ws adyolo_corpus_yolo_labels_mix_workspace_words(B, max_events) int32 words; max_events bounds each source's event
- *   count; an item whose own row or mate row is bad gets no rows at all and sets ADYOLO_CORPUS_BAD_ITEM.  Capacity, overflow,
- *   the b = -1 tail and the grid limit as for adyolo_corpus_yolo_labels, whose rows an all-unmixed batch equals.
- * adyolo_corpus_classwise_labels_mix: the dense targets of the merged events: SEDDOA / ACCDOA take the last event of a class in
- *   a frame in item-then-mate order (the mate's wins a collision), ADPIT counts over both sources and keeps the first three in
- *   that order; each direction vector comes from the xyz slot of its own source's combination.  n_events < 2^30.  An item
- *   without a mate has the bits of adyolo_corpus_classwise_labels; bad items (either row) and bad classes as there.
- *
- * Yaw rotation (aug_config.yaw_rotation_augment, FOA only): after its combination every source is turned about the vertical
- * axis by its own yaw.  The *_yaw calls read it from word ADYOLO_CORPUS_YAW_WORD (7) of the item row and of the mate row (word 6
- * of a mate stays the gain): the yaw in WHOLE DEGREES as a signed integer, legal in [-180, 180); 0 turns nothing.  A row whose
- * yaw is outside that range is a bad item, as a combination >= 16 is.  The other calls never read word 7.
- * adyolo_corpus_gather_yaw / _yaw_mix: adyolo_corpus_gather / adyolo_corpus_gather_mix (FOA form) with each source's frames
- *   yawed after its combination -- bit for bit adyolo_pcm16_to_f32 -> adyolo_foa_rotate_yaw (-> a + g * m).  yaw_tab DEVICE float
- *   [360][2] = {cos, sin} of the yaws -180 .. 179 (augmentations.yaw_cos_sin), 8-byte aligned; entry yaw + 180 is read once
- *   per workgroup.  comb < 0: the yaw alone.  All parities of the two offsets and an odd n are legal, as in the plain calls.
- * adyolo_corpus_yolo_labels_yaw / _yaw_mix: adyolo_corpus_yolo_labels / _mix with augmentations.yaw_labels after the
- *   combination's arithmetic: az = az + yaw, then < -180: += 360, > 180: -= 360, in double and uncontracted, before the
- *   180 -> -180 rule of the encoder.  The same workspace functions; any angles.
- * adyolo_corpus_classwise_labels_yaw / _yaw_mix: adyolo_corpus_classwise_labels / _mix for yawed sources.  z of an event is
- *   still read from its xyz slot; x = (float)(cos_az * cos_el) and y = (float)(sin_az * cos_el), one double product each,
- *   from yaw_az DEVICE double [361][2] = {cos, sin} of the azimuths -180 .. 180 and yaw_el DEVICE double [181] = cos of the
- *   elevations -90 .. 90, both built on the host with the expressions of datasets._polar_to_xyz (ops.corpus_yaw_xyz_tables)
- *   and indexed by the event's moved angles (as in the _yolo_labels_yaw calls).  The events' angles must be whole degrees
- *   (corpus.ClasswiseDeviceCorpus refuses any other split); an angle that is not indexes entry 0.  rot_host as above.
+ *     mates given: the dense targets of the merged events: SEDDOA / ACCDOA take the last event of a class in a frame in
+ *       item-then-mate order (the mate's wins a collision), ADPIT counts over both sources and keeps the first three in that
+ *       order; each direction vector comes from the xyz slot of its own source's combination.  n_events < 2^30.  Bad items
+ *       (either row) and bad classes as without mates.
+ *     yaw_az and yaw_el given (together or not at all: one without the other is EINVAL; rot_host, as above, is then required
+ *       and otherwise not read): z of an event is still read from its xyz slot; x = (float)(cos_az * cos_el) and y =
+ *       (float)(sin_az * cos_el), one double product each, from yaw_az DEVICE double [361][2] = {cos, sin} of the azimuths
+ *       -180 .. 180 and yaw_el DEVICE double [181] = cos of the elevations -90 .. 90, both 8-byte aligned, built on the host
+ *       with the expressions of datasets._polar_to_xyz (ops.corpus_yaw_xyz_tables) and indexed by the event's moved angles (as
+ *       in adyolo_corpus_yolo_labels with yaw).  The events' angles must be whole degrees (corpus.ClasswiseDeviceCorpus refuses
+ *       any other split); an angle that is not indexes entry 0.
  * ---------------------------------------------------------------------------------------------- */
 #define ADYOLO_CORPUS_ITEM_WORDS 8
-#define ADYOLO_CORPUS_YAW_WORD   7   /* the *_yaw calls: the row's yaw in whole degrees, [-180, 180) */
+#define ADYOLO_CORPUS_YAW_WORD   7   /* with a yaw: the row's yaw in whole degrees, [-180, 180) */
 #define ADYOLO_CORPUS_ROT_WORDS  8
 #define ADYOLO_CORPUS_OVERFLOW   1   /* more rows than the target capacity */
 #define ADYOLO_CORPUS_BAD_ITEM   2   /* an item table entry outside the corpus */
@@ -782,47 +779,20 @@ int adyolo_audio_mix(const float *audio, const float *mate, const float *gains, 
 #define ADYOLO_CORPUS_SEDDOA     0
 #define ADYOLO_CORPUS_ACCDOA     1
 #define ADYOLO_CORPUS_ADPIT      2
-int  adyolo_corpus_gather(const int16_t *pcm, long n_total, const int64_t *items, int B, long n, const float *rot_host,
-                          float *audio, int *status, void *stream);
-#define ADYOLO_MIC_SWAP_NONE     0xffffffffu  /* src_host word of a combination that is no symmetry of the array */
-int  adyolo_corpus_gather_mic(const int16_t *pcm, long n_total, const int64_t *items, int B, long n,
-                              const unsigned int *src_host, float *audio, int *status, void *stream);
-long adyolo_corpus_yolo_labels_workspace_words(int B, int max_events);
-int  adyolo_corpus_yolo_labels(const double *events, long n_events, const int64_t *items, int B, int max_events,
-                               int n_label_frames, const double *grid_bounds, int Gaz, int Gel, const float *rot_host,
-                               int *ws, float *target, long cap, int *count, int *status, void *stream);
-int  adyolo_corpus_classwise_labels(const double *events, const float *xyz, long n_events, const int64_t *items, int B,
-                                    int max_events, int n_label_frames, int n_classes, int format, float *target, int *status,
-                                    void *stream);
-int  adyolo_corpus_gather_mix(const int16_t *pcm, long n_total, const int64_t *items, const int64_t *mates, int B, long n,
-                              const float *rot_host, const unsigned int *mic_src_host /* NULL = FOA */, float *audio,
-                              int *status, void *stream);
-long adyolo_corpus_yolo_labels_mix_workspace_words(int B, int max_events);
-int  adyolo_corpus_yolo_labels_mix(const double *events, long n_events, const int64_t *items, const int64_t *mates, int B,
-                                   int max_events, int n_label_frames, const double *grid_bounds, int Gaz, int Gel,
-                                   const float *rot_host, int *ws, float *target, long cap, int *count, int *status,
-                                   void *stream);
-int  adyolo_corpus_classwise_labels_mix(const double *events, const float *xyz, long n_events, const int64_t *items,
-                                        const int64_t *mates, int B, int max_events, int n_label_frames, int n_classes,
-                                        int format, float *target, int *status, void *stream);
-int  adyolo_corpus_gather_yaw(const int16_t *pcm, long n_total, const int64_t *items, int B, long n, const float *rot_host,
-                              const float *yaw_tab, float *audio, int *status, void *stream);
-int  adyolo_corpus_gather_yaw_mix(const int16_t *pcm, long n_total, const int64_t *items, const int64_t *mates, int B, long n,
-                                  const float *rot_host, const float *yaw_tab, float *audio, int *status, void *stream);
-int  adyolo_corpus_yolo_labels_yaw(const double *events, long n_events, const int64_t *items, int B, int max_events,
-                                   int n_label_frames, const double *grid_bounds, int Gaz, int Gel, const float *rot_host,
-                                   int *ws, float *target, long cap, int *count, int *status, void *stream);
-int  adyolo_corpus_yolo_labels_yaw_mix(const double *events, long n_events, const int64_t *items, const int64_t *mates, int B,
-                                       int max_events, int n_label_frames, const double *grid_bounds, int Gaz, int Gel,
-                                       const float *rot_host, int *ws, float *target, long cap, int *count, int *status,
-                                       void *stream);
-int  adyolo_corpus_classwise_labels_yaw(const double *events, const float *xyz, long n_events, const int64_t *items, int B,
-                                        int max_events, int n_label_frames, int n_classes, int format, const float *rot_host,
-                                        const double *yaw_az, const double *yaw_el, float *target, int *status, void *stream);
-int  adyolo_corpus_classwise_labels_yaw_mix(const double *events, const float *xyz, long n_events, const int64_t *items,
-                                            const int64_t *mates, int B, int max_events, int n_label_frames, int n_classes,
-                                            int format, const float *rot_host, const double *yaw_az, const double *yaw_el,
-                                            float *target, int *status, void *stream);
+#define ADYOLO_MIC_SWAP_NONE     0xffffffffu  /* mic_src_host word of a combination that is no symmetry of the array */
+int  adyolo_corpus_gather(const int16_t *pcm, long n_total, const int64_t *items, const int64_t *mates /* NULL: plain */,
+                          int B, long n, const float *rot_host, const unsigned int *mic_src_host /* NULL: FOA form */,
+                          const float *yaw_tab /* NULL: no yaw */, float *audio, int *status, void *stream);
+long adyolo_corpus_yolo_labels_workspace_words(int B, int max_events, int mix);
+int  adyolo_corpus_yolo_labels(const double *events, long n_events, const int64_t *items, const int64_t *mates /* NULL: plain */,
+                               int B, int max_events, int n_label_frames, const double *grid_bounds, int Gaz, int Gel,
+                               const float *rot_host, int yaw, int *ws, float *target, long cap, int *count, int *status,
+                               void *stream);
+int  adyolo_corpus_classwise_labels(const double *events, const float *xyz, long n_events, const int64_t *items,
+                                    const int64_t *mates /* NULL: plain */, int B, int max_events, int n_label_frames,
+                                    int n_classes, int format, const float *rot_host /* read with yaw only */,
+                                    const double *yaw_az, const double *yaw_el /* both NULL: no yaw */, float *target,
+                                    int *status, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Windowed inference (corpus.InferDeviceCorpus, test.infer_epoch_corpus): recordings of any length cut into overlapping

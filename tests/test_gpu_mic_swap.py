@@ -1,5 +1,5 @@
 """GPU: the MIC channel-swap augmentation's two kernels and its training paths.  ``adyolo_mic_swap`` (csrc/aug.hip) against
-tensor indexing on raw 32-bit patterns (NaN payloads, infinities and -0.0 keep their bits); ``adyolo_corpus_gather_mic``
+tensor indexing on raw 32-bit patterns (NaN payloads, infinities and -0.0 keep their bits); ``adyolo_corpus_gather`` (MIC form)
 (csrc/corpus.hip) against ``pcm16_to_f32`` followed by ``swap_audio``, bit for bit, at even and odd offsets, the first and the
 last window of the buffer, odd lengths, comb -1 against the FOA gather's comb -1, and a bad item between good ones;
 ``DeviceCorpus`` / ``ClasswiseDeviceCorpus`` with ``aug_config.channel_swap_augment`` against the host path iterated in the main
@@ -108,7 +108,7 @@ def test_mic_swap_refusals(ops):
         swap_audio(audio, [0])
 
 
-# ----------------------------------------------------------------------------------------------- adyolo_corpus_gather_mic
+# ------------------------------------------------------------------------------------- adyolo_corpus_gather (mic_src)
 def _mic_table(ops):
     from adyolo_amd.augmentations import MIC_SWAP_COMBS, mic_swap_source
     return ops.corpus_mic_table({k: mic_swap_source(k) for k in MIC_SWAP_COMBS})
@@ -127,7 +127,7 @@ def _gather(ops, pcm, offs, combs, n, foa=False):
     if foa:
         ops.corpus_gather(pcm, items.to("cuda:0"), ops.corpus_rot_table(COMBINATIONS), out, status)
     else:
-        ops.corpus_gather_mic(pcm, items.to("cuda:0"), _mic_table(ops), out, status)
+        ops.corpus_gather(pcm, items.to("cuda:0"), None, out, status, mic_src=_mic_table(ops))
     torch.cuda.synchronize()
     assert bool((buf[b * n * 4:] == 7.0).all())
     return out, int(status.item())

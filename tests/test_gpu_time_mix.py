@@ -1,9 +1,9 @@
 """GPU: the time-domain mixing augmentation (``aug_config.time_mix_augment``), every comparison bit for bit.
-``adyolo_corpus_gather_mix`` against two plain gathers and ``a + g * m`` in torch (all parities of the two offsets, the first and
-last window on either side, a no-mate and a bad mate between mixed items, both tables); ``adyolo_audio_mix`` in and out of place;
-``adyolo_corpus_yolo_labels_mix`` against ``get_yolo_label(merge_labels(...))`` + ``collate_fn``; ``adyolo_corpus_classwise_labels_mix``
-against the three host encoders on the merged dict; both device corpora against the host-fed path through
-``train_one_epoch_audio``; and three training steps from the mixing corpus, eagerly and replayed from one hipGraph."""
+``adyolo_corpus_gather`` with mates against two plain gathers and ``a + g * m`` in torch (all parities of the two offsets, the first
+and last window on either side, a no-mate and a bad mate between mixed items, both tables); ``adyolo_audio_mix`` in and out of
+place; ``adyolo_corpus_yolo_labels`` with mates against ``get_yolo_label(merge_labels(...))`` + ``collate_fn``;
+``adyolo_corpus_classwise_labels`` with mates against the three host encoders on the merged dict; both device corpora against
+the host-fed path through ``train_one_epoch_audio``; and three training steps from the mixing corpus, eagerly and replayed from one hipGraph."""
 import random
 
 import numpy as np
@@ -80,7 +80,7 @@ def _rows(offs, combs, gains=None):
     return rows
 
 
-# ---------------------------------------------------------------------------------------------- adyolo_corpus_gather_mix
+# -------------------------------------------------------------------------------------------- adyolo_corpus_gather (mates)
 def _tables(ops, mic):
     from adyolo_amd.augmentations import COMBINATIONS, MIC_SWAP_COMBS, mic_swap_source
     rot = ops.corpus_rot_table(COMBINATIONS)
@@ -91,10 +91,7 @@ def _plain(ops, pcm, rows, n, mic):
     rot, src = _tables(ops, mic)
     out = torch.empty(rows.shape[0], n, 4, device=DEV)
     status = torch.zeros(1, dtype=torch.int32, device=DEV)
-    if mic:
-        ops.corpus_gather_mic(pcm, rows.to(DEV), src, out, status)
-    else:
-        ops.corpus_gather(pcm, rows.to(DEV), rot, out, status)
+    ops.corpus_gather(pcm, rows.to(DEV), None if mic else rot, out, status, mic_src=src)
     assert int(status.item()) == 0
     return out
 
@@ -106,7 +103,7 @@ def _mix(ops, pcm, items, mates, n, mic):
     buf = torch.full((b * n * 4 + 64,), 7.0, device=DEV)
     out = buf[:b * n * 4].view(b, n, 4)
     status = torch.zeros(1, dtype=torch.int32, device=DEV)
-    ops.corpus_gather_mix(pcm, items.to(DEV), mates.to(DEV), rot, src, out, status)
+    ops.corpus_gather(pcm, items.to(DEV), rot, out, status, mates=mates.to(DEV), mic_src=src)
     torch.cuda.synchronize()
     assert bool((buf[b * n * 4:] == 7.0).all())
     return out, int(status.item())
@@ -173,11 +170,11 @@ def test_gather_mix_refusals(ops, pcm):
     out = torch.empty(2, 16, 4, device=DEV)
     status = torch.zeros(1, dtype=torch.int32, device=DEV)
     with pytest.raises(AdyoloHipError, match="mates"):
-        ops.corpus_gather_mix(pcm, items, items[:1], rot, None, out, status)
+        ops.corpus_gather(pcm, items, rot, out, status, mates=items[:1])
     with pytest.raises(AdyoloHipError, match="mates"):
-        ops.corpus_gather_mix(pcm, items, items.to(torch.int32), rot, None, out, status)
+        ops.corpus_gather(pcm, items, rot, out, status, mates=items.to(torch.int32))
     with pytest.raises(AdyoloHipError, match="rotation table"):
-        ops.corpus_gather_mix(pcm, items, items, None, None, out, status)
+        ops.corpus_gather(pcm, items, None, out, status, mates=items)
 
 
 # ------------------------------------------------------------------------------------------------------- adyolo_audio_mix
@@ -229,7 +226,7 @@ def test_audio_mix_refusals(ops):
         ops.audio_mix(a, a.clone()[:, :8], gains, mixed)
 
 
-# ------------------------------------------------------------------------------------------ adyolo_corpus_yolo_labels_mix
+# ---------------------------------------------------------------------------------------- adyolo_corpus_yolo_labels (mates)
 def _ev(cls, az, el=0.0):
     return [cls, 0, az, el]
 
@@ -291,15 +288,15 @@ def _yolo_run(ops, events, items, mates, t, cap):
     enc = YoloLabelEncoder()
     bounds = torch.from_numpy(np.concatenate([enc.az_lb, enc.az_ub, enc.el_lb, enc.el_ub]).astype(np.float64)).to(DEV)
     b = items.shape[0]
-    words = ops.corpus_labels_mix_workspace_words(b, MAX_EVENTS)
+    words = ops.corpus_labels_workspace_words(b, MAX_EVENTS, mix=True)
     assert words == b * 2 * MAX_EVENTS
     ws = torch.full((words + 16,), -77, dtype=torch.int32, device=DEV)
     buf = torch.full((cap * 7 + 64,), 7.0, device=DEV)
     target = buf[:cap * 7].view(cap, 7)
     count = torch.zeros(1, dtype=torch.int32, device=DEV)
     status = torch.zeros(1, dtype=torch.int32, device=DEV)
-    ops.corpus_yolo_labels_mix(events.to(DEV), items.to(DEV), mates.to(DEV), MAX_EVENTS, t, bounds,
-                               (len(enc.az_lb), len(enc.el_lb)), ops.corpus_rot_table(COMBINATIONS), ws, target, count, status)
+    ops.corpus_yolo_labels(events.to(DEV), items.to(DEV), MAX_EVENTS, t, bounds, (len(enc.az_lb), len(enc.el_lb)),
+                           ops.corpus_rot_table(COMBINATIONS), ws, target, count, status, mates=mates.to(DEV))
     torch.cuda.synchronize()
     assert bool((buf[cap * 7:] == 7.0).all()) and bool((ws[words:] == -77).all())
     return target.cpu(), int(count.item()), int(status.item())
@@ -364,7 +361,7 @@ def test_yolo_labels_mix_are_the_rows_of_the_merged_labels(ops, t):
     assert status == 0 and count == int(cnt.item()) and torch.equal(_bits(target), _bits(plain.cpu()))
 
 
-# ------------------------------------------------------------------------------------- adyolo_corpus_classwise_labels_mix
+# ----------------------------------------------------------------------------------- adyolo_corpus_classwise_labels (mates)
 CW_CASES = ((1, 1), (2, 1), (2, 2), (1, 0), (0, 1), (0, 3), (3, 1), (1, 2))     # same-class events (item, mate) in one frame
 CW_MAX_EVENTS = 80
 
@@ -441,8 +438,8 @@ def test_classwise_labels_mix_are_the_encoders_on_the_merged_labels(ops, n_class
         def run(it, mt, events=events):
             buf.fill_(7.0)
             status.zero_()
-            ops.corpus_classwise_labels_mix(events.to(DEV), it.to(DEV), mt.to(DEV), xyz, CW_MAX_EVENTS, t, n_classes, loss, target,
-                                            status)
+            ops.corpus_classwise_labels(events.to(DEV), it.to(DEV), xyz, CW_MAX_EVENTS, t, n_classes, loss, target, status,
+                                        mates=mt.to(DEV))
             torch.cuda.synchronize()
             assert bool((buf[n:] == 7.0).all())
             return int(status.item())

@@ -1,7 +1,7 @@
 """GPU: the FOA yaw-rotation augmentation (``aug_config.yaw_rotation_augment``), every comparison bit for bit (as int32).
 ``rotate_audio_yaw`` against the NumPy float32 definition and against the four combinations a quarter turn reproduces;
-``adyolo_corpus_gather_yaw`` / ``_yaw_mix`` against ``pcm16_to_f32`` -> ``rotate_audio_yaw`` (-> ``a + g * m``) at both offset
-parities, odd lengths, ``comb = -1`` and bad rows; the AD-YOLO rows and the dense class-wise targets of the ``_yaw`` label calls
+``adyolo_corpus_gather`` with a yaw table (and mates) against ``pcm16_to_f32`` -> ``rotate_audio_yaw`` (-> ``a + g * m``) at both
+offset parities, odd lengths, ``comb = -1`` and bad rows; the AD-YOLO rows and the dense class-wise targets of the yawed label calls
 against the host path (``rotate_labels`` -> ``yaw_labels`` -> ``merge_labels`` -> encoder -> collate) at the wraps, at exactly +-180,
 on cell bounds, at the poles and under every combination; both device corpora against ``FoaDataset`` through
 ``train_one_epoch_audio``; and three training steps from either corpus, eagerly and replayed from ONE hipGraph, against the
@@ -123,7 +123,7 @@ def test_rotation_aug_takes_an_optional_yaw(ops, pcm):
     assert a is audio and lab is label
 
 
-# ---------------------------------------------------------------------------------------------- adyolo_corpus_gather_yaw
+# ------------------------------------------------------------------------------------------ adyolo_corpus_gather (yaw_tab)
 def _gather(ops, pcm, items, n, mates=None):
     """One call -> (out, status word); a guard band behind the output must stay."""
     from adyolo_amd.augmentations import COMBINATIONS
@@ -132,10 +132,7 @@ def _gather(ops, pcm, items, n, mates=None):
     buf = torch.full((b * n * 4 + 64,), 7.0, device=DEV)
     out = buf[:b * n * 4].view(b, n, 4)
     status = torch.zeros(1, dtype=torch.int32, device=DEV)
-    if mates is None:
-        ops.corpus_gather_yaw(pcm, items.to(DEV), rot, tab, out, status)
-    else:
-        ops.corpus_gather_yaw_mix(pcm, items.to(DEV), mates.to(DEV), rot, tab, out, status)
+    ops.corpus_gather(pcm, items.to(DEV), rot, out, status, mates=None if mates is None else mates.to(DEV), yaw_tab=tab)
     torch.cuda.synchronize()
     assert bool((buf[b * n * 4:] == 7.0).all())
     return out, int(status.item())
@@ -231,7 +228,7 @@ def test_gather_yaw_mix_is_two_yawed_gathers_and_a_sum(ops, pcm, n):
     assert status == 0 and torch.equal(_bits(got), _bits(plain))
 
 
-# ------------------------------------------------------------------------------------------ adyolo_corpus_yolo_labels_yaw
+# ------------------------------------------------------------------------------------------ adyolo_corpus_yolo_labels (yaw)
 def _ev(cls, az, el=0.0):
     return [cls, 0, az, el]
 
@@ -303,17 +300,15 @@ def _yolo_run(ops, events, items, mates, t, cap, mix, yaw=True):
     enc = YoloLabelEncoder()
     bounds = torch.from_numpy(np.concatenate([enc.az_lb, enc.az_ub, enc.el_lb, enc.el_ub]).astype(np.float64)).to(DEV)
     b = items.shape[0]
-    words = (ops.corpus_labels_mix_workspace_words if mix else ops.corpus_labels_workspace_words)(b, MAX_EVENTS)
+    words = ops.corpus_labels_workspace_words(b, MAX_EVENTS, mix=mix)
     ws = torch.full((words + 16,), -77, dtype=torch.int32, device=DEV)
     buf = torch.full((cap * 7 + 64,), 7.0, device=DEV)
     target = buf[:cap * 7].view(cap, 7)
     count = torch.zeros(1, dtype=torch.int32, device=DEV)
     status = torch.zeros(1, dtype=torch.int32, device=DEV)
-    tables = (items.to(DEV), mates.to(DEV)) if mix else (items.to(DEV),)
-    call = {(False, True): ops.corpus_yolo_labels_yaw, (True, True): ops.corpus_yolo_labels_yaw_mix,
-            (False, False): ops.corpus_yolo_labels, (True, False): ops.corpus_yolo_labels_mix}[(mix, yaw)]
-    call(events.to(DEV), *tables, MAX_EVENTS, t, bounds, (len(enc.az_lb), len(enc.el_lb)), ops.corpus_rot_table(COMBINATIONS), ws,
-         target, count, status)
+    ops.corpus_yolo_labels(events.to(DEV), items.to(DEV), MAX_EVENTS, t, bounds, (len(enc.az_lb), len(enc.el_lb)),
+                           ops.corpus_rot_table(COMBINATIONS), ws, target, count, status, mates=mates.to(DEV) if mix else None,
+                           yaw=yaw)
     torch.cuda.synchronize()
     assert bool((buf[cap * 7:] == 7.0).all()) and bool((ws[words:] == -77).all())
     return target.cpu(), int(count.item()), int(status.item())
@@ -368,7 +363,7 @@ def test_yolo_labels_yaw_are_the_rows_of_the_host_path(ops, t, mix):
         assert torch.equal(_bits(target[:count]), _bits(want)) and bool((target[count:, 0] == -1).all())
 
 
-# ------------------------------------------------------------------------------------- adyolo_corpus_classwise_labels_yaw
+# ------------------------------------------------------------------------------------- adyolo_corpus_classwise_labels (yaw)
 CW_YAWS = (0, 90, -90, -180, 37, -179, 1, 179, -1, 123)          # -180 is the half turn: the legal range is [-180, 180)
 CW_CHUNKS = (                    # whole degrees: the poles, elevation 0 (-0.0 under an elevation flip), +-180, signed zeros
     (3, {0: [_ev(0, 30.0, 90.0), _ev(1, -45.0, -90.0), _ev(2, 100.0, 0.0)],
@@ -425,12 +420,8 @@ def test_classwise_labels_yaw_are_the_host_encoders(ops, t, mix):
         def run(it, mt):
             buf.fill_(7.0)
             status.zero_()
-            if mix:
-                ops.corpus_classwise_labels_yaw_mix(events.to(DEV), it.to(DEV), mt.to(DEV), xyz, rot, yaw_xyz, CW_MAX_EVENTS, t,
-                                                    CW_C, loss, target, status)
-            else:
-                ops.corpus_classwise_labels_yaw(events.to(DEV), it.to(DEV), xyz, rot, yaw_xyz, CW_MAX_EVENTS, t, CW_C, loss,
-                                                target, status)
+            ops.corpus_classwise_labels(events.to(DEV), it.to(DEV), xyz, CW_MAX_EVENTS, t, CW_C, loss, target, status,
+                                        mates=mt.to(DEV) if mix else None, rot=rot, yaw_xyz=yaw_xyz)
             torch.cuda.synchronize()
             assert bool((buf[n:] == 7.0).all())
             return int(status.item())
@@ -450,11 +441,8 @@ def test_classwise_labels_yaw_are_the_host_encoders(ops, t, mix):
         zero_m[:, 7] = 0
         assert run(zero_i, zero_m) == 0
         plain = torch.full(shape, 7.0, device=DEV)
-        if mix:
-            ops.corpus_classwise_labels_mix(events.to(DEV), zero_i.to(DEV), zero_m.to(DEV), xyz, CW_MAX_EVENTS, t, CW_C, loss, plain,
-                                            status)
-        else:
-            ops.corpus_classwise_labels(events.to(DEV), zero_i.to(DEV), xyz, CW_MAX_EVENTS, t, CW_C, loss, plain, status)
+        ops.corpus_classwise_labels(events.to(DEV), zero_i.to(DEV), xyz, CW_MAX_EVENTS, t, CW_C, loss, plain, status,
+                                    mates=zero_m.to(DEV) if mix else None)
         # (under a combination: without one the host keeps an azimuth of -0.0 as it is, and ``yaw_labels`` makes it -0.0 + 0 = +0.0)
         same = [j for j in range(b) if cases[j][0] >= 0 and (not mix or mate_of[j] is None or mate_of[j][0] >= 0)]
         assert len(same) > b // 2 and int(status.item()) == 0 and torch.equal(_bits(target[same]), _bits(plain[same]))
@@ -467,6 +455,34 @@ def test_classwise_labels_yaw_are_the_host_encoders(ops, t, mix):
             again = target.cpu()
             assert not bool(again[1].any())
             assert torch.equal(_bits(again[0]), _bits(want[0])) and torch.equal(_bits(again[2:]), _bits(want[2:]))
+
+
+# ------------------------------------------------------------------- what the merged argument lists refuse, on the host
+def test_optional_tables_that_do_not_go_together_are_refused_before_any_launch(ops):
+    from adyolo_amd._lib import AdyoloHipError
+    from adyolo_amd.augmentations import COMBINATIONS, MIC_SWAP_COMBS, mic_swap_source
+    rot, tab = ops.corpus_rot_table(COMBINATIONS), ops.corpus_yaw_table(DEV)
+    mic = ops.corpus_mic_table({k: mic_swap_source(k) for k in MIC_SWAP_COMBS})
+    pcm = torch.zeros(16, 4, dtype=torch.int16, device=DEV)
+    items = _rows([0], [0], [0]).to(DEV)
+    status = torch.zeros(1, dtype=torch.int32, device=DEV)
+    out = torch.full((1, 2, 4), 7.0, device=DEV)
+    for r, kw in ((rot, {"yaw_tab": tab, "mic_src": mic}),         # there is no MIC yaw
+                  (None, {"yaw_tab": tab, "mic_src": mic}),
+                  (None, {}), (None, {"yaw_tab": tab})):            # neither rot nor mic_src
+        with pytest.raises(AdyoloHipError):
+            ops.corpus_gather(pcm, items, r, out, status, **kw)
+        torch.cuda.synchronize()
+        assert bool((out == 7.0).all()) and int(status.item()) == 0, (r is None, sorted(kw))
+    events = torch.tensor([[0.0, 1.0, 30.0, 10.0]], dtype=torch.float64, device=DEV)
+    xyz = torch.zeros(1, ops.CORPUS_XYZ_SLOTS, 3, device=DEV)
+    items = torch.tensor([[0, 0, 0, 1, 0, 0, 0, 37]], dtype=torch.int64, device=DEV)
+    target = torch.full(ops.corpus_classwise_shape("accdoa", 1, 2, CW_C), 7.0, device=DEV)
+    with pytest.raises(AdyoloHipError):                            # yaw_xyz needs the rotation table
+        ops.corpus_classwise_labels(events, items, xyz, CW_MAX_EVENTS, 2, CW_C, "accdoa", target, status,
+                                    yaw_xyz=ops.corpus_yaw_xyz_tables(DEV))
+    torch.cuda.synchronize()
+    assert bool((target == 7.0).all()) and int(status.item()) == 0
 
 
 # ------------------------------------------------------------------------------------------- corpus against the host path

@@ -26,7 +26,7 @@ def test_header_symbols_are_exported_and_bound():
     assert len(declared) >= 35
     assert declared == set(_lib.SIGNATURES), declared ^ set(_lib.SIGNATURES)
     lib = _lib.load()                       # raises if the library or a symbol is missing
-    assert lib.adyolo_abi_version() == 3
+    assert lib.adyolo_abi_version() == 4
     assert lib.adyolo_loss_workspace_words(4, 32, 5, 10) > 6 * 4 * 32 * 5
 
 

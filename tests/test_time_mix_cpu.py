@@ -298,13 +298,15 @@ def test_collate_makes_one_trailing_dict(splits):
 # --------------------------------------------------------------------------------------------------------------------- ABI
 def test_new_symbols_are_declared_and_bound():
     hdr = open(os.path.join(ROOT, "include", "adyolo_hip.h")).read()
-    names = ("adyolo_corpus_gather_mix", "adyolo_corpus_yolo_labels_mix", "adyolo_corpus_yolo_labels_mix_workspace_words",
-             "adyolo_corpus_classwise_labels_mix", "adyolo_audio_mix")
+    names = ("adyolo_corpus_gather", "adyolo_corpus_yolo_labels", "adyolo_corpus_yolo_labels_workspace_words",
+             "adyolo_corpus_classwise_labels", "adyolo_audio_mix")
     for name in names:
         assert name in _lib.SIGNATURES and re.search(r"\b%s\s*\(" % name, hdr), name
     lib = _lib.load()
     for name in names:
         assert getattr(lib, name) is not None
-    assert lib.adyolo_corpus_yolo_labels_mix_workspace_words(3, 5) == 30
-    assert lib.adyolo_corpus_yolo_labels_mix_workspace_words(3, 0) == 6
-    assert lib.adyolo_corpus_yolo_labels_mix_workspace_words(0, 5) < 0
+    assert lib.adyolo_corpus_yolo_labels_workspace_words(3, 5, 1) == 30
+    assert lib.adyolo_corpus_yolo_labels_workspace_words(3, 0, 1) == 6
+    assert lib.adyolo_corpus_yolo_labels_workspace_words(0, 5, 1) < 0
+    assert lib.adyolo_corpus_yolo_labels_workspace_words(3, 5, 0) == 15
+    assert lib.adyolo_corpus_yolo_labels_workspace_words(3, 0, 0) == 3

@@ -24,7 +24,7 @@ def test_select_entry_points_are_declared_exported_and_bound():
         assert name in _lib.SIGNATURES, name
     assert "#define ADYOLO_SELECT_MAX_N 1024" in open(os.path.join(ROOT, "include", "adyolo_hip.h")).read()
     lib = _lib.load()
-    assert lib.adyolo_abi_version() == 3
+    assert lib.adyolo_abi_version() == 4
     assert lib.adyolo_yolo_select_workspace_words(600, 160, 12) == 600 * 12 * (3 * 160 + 2)
     assert lib.adyolo_yolo_select_workspace_words(0, 160, 12) == 0
 

@@ -7,7 +7,7 @@ batch size (16 and 64 x 20 s, hipGraph-replayed steps):
   load          load_chunked_split (verify="sample") + DeviceCorpus upload: seconds and bytes held on the device
   batch         gather + label kernels of one batch (DeviceCorpus.launch), device time per batch (events around --iters batches)
   gather        the gather alone on uploaded item tables, device time per launch in us (--iters launches replayed from one
-                hipGraph): ``adyolo_corpus_gather`` always, and with --swap ``adyolo_corpus_gather_mic`` on the same tables
+                hipGraph): ``adyolo_corpus_gather`` always, and with --swap its MIC form (``mic_src``) on the same tables
   labels        (class-wise losses) the label kernel alone on an uploaded item table, device time per batch
   replay        the recorded train step alone on fixed inputs (the rate a loader has to keep up with)
   corpus        train_one_epoch_corpus
@@ -25,11 +25,11 @@ classes of the split and the model (12 by default: the ACCDOA / ADPIT heads' GEM
 --labels-only stops after load, batch, gather and labels (no model: any class count, e.g. the 13 of DCASE 2023); --corpus-only
 skips the host-loader epochs.  --mix [--prob P] runs every batch size twice, key off ("b16") and with
 ``aug_config.time_mix_augment`` at probability P ("b16_mix": doubled AD-YOLO row capacity), and adds to the second the time-domain
-mixing calls on the same batch: ``adyolo_corpus_gather_mix`` with the drawn mates, with a mate for every item (prob 1.0) and with
-none (prob 0.0), and the ``_mix`` label call next to the plain one.  --yaw runs every batch size (and with --mix every mixing
-run) a second time with ``aug_config.yaw_rotation_augment`` on ("b16_yaw", "b16_yaw_mix"; the split's labels are then whole
-degrees, which the class-wise corpus needs) and measures, on the same item tables, ``adyolo_corpus_gather_yaw`` against
-``adyolo_corpus_gather``, ``_yaw_mix`` against ``adyolo_corpus_gather_mix`` and the ``_yaw`` label calls against the un-yawed ones.
+mixing calls on the same batch: ``adyolo_corpus_gather`` with ``mates`` -- the drawn ones, a mate for every item (prob 1.0) and
+none (prob 0.0) -- and the label call with ``mates`` next to the plain one.  --yaw runs every batch size (and with --mix every
+mixing run) a second time with ``aug_config.yaw_rotation_augment`` on ("b16_yaw", "b16_yaw_mix"; the split's labels are then
+whole degrees, which the class-wise corpus needs) and measures, on the same item tables, the gather with ``yaw_tab`` against the
+one without (alone, and with ``mates``) and the label calls with the yaw against the un-yawed ones.
 
   python tools/corpus_bench.py [--dir /tmp/adyolo_corpus] [--batches 16,64] [--steps 32,8] [--workers 16] [--json out.json]
                                [--loss adyolo|seddoa|accdoa|adpit] [--mic] [--swap] [--classes C] [--labels-only]
@@ -217,8 +217,8 @@ def bench_batch(root, batch, steps, workers, iters, loss="adyolo", mic=False, n_
     audio = torch.empty((batch, corpus.n_samples, 4), dtype=torch.float32, device="cuda:0")
     out["gather_us"] = graph_us(lambda i: ops.corpus_gather(corpus.pcm, dev_items[i % 4], corpus.rot, audio, corpus.status), iters)
     if swap:
-        out["gather_mic_us"] = graph_us(lambda i: ops.corpus_gather_mic(corpus.pcm, dev_items[i % 4], corpus.mic_src, audio,
-                                                                        corpus.status), iters)
+        out["gather_mic_us"] = graph_us(lambda i: ops.corpus_gather(corpus.pcm, dev_items[i % 4], None, audio, corpus.status,
+                                                                    mic_src=corpus.mic_src), iters)
     if mix is not None:
         # the mixing gather on the same item tables: the drawn mates (prob P), a mate for every item (the next item of the batch,
         # gain 1.0: prob 1.0) and none (prob 0.0)
@@ -234,22 +234,23 @@ def bench_batch(root, batch, steps, workers, iters, loss="adyolo", mic=False, n_
         dev_mates = [torch.from_numpy(d[2]).to("cuda:0") for d in drawn]
         out["mixed_items"] = round(float(np.mean([(d[2][:, 0] != -1).mean() for d in drawn])), 3)
         for key, tabs in (("gather_mix_us", dev_mates), ("gather_mix_p1_us", every), ("gather_mix_p0_us", none)):
-            out[key] = graph_us(lambda i: ops.corpus_gather_mix(corpus.pcm, dev_items[i % 4], tabs[i % 4], corpus.rot,
-                                                                corpus.mic_src, audio, corpus.status), iters)
+            out[key] = graph_us(lambda i: ops.corpus_gather(corpus.pcm, dev_items[i % 4], corpus.rot, audio, corpus.status,
+                                                            mates=tabs[i % 4], mic_src=corpus.mic_src), iters)
         gb = batch * corpus.n_samples * (8 + 16) / 1e9                   # int16 frames read + float32 frames written
         out["gather_tb_s"] = round(gb / out["gather_us"] * 1e3, 2)
         out["gather_mix_p1_tb_s"] = round((gb + batch * corpus.n_samples * 8 / 1e9) / out["gather_mix_p1_us"] * 1e3, 2)
         if loss == "adyolo":
             target = torch.empty((corpus.cap, 7), dtype=torch.float32, device="cuda:0")
             rows = torch.empty(1, dtype=torch.int32, device="cuda:0")
-            ws = torch.empty(ops.corpus_labels_mix_workspace_words(batch, corpus.max_events), dtype=torch.int32, device="cuda:0")
+            ws = torch.empty(ops.corpus_labels_workspace_words(batch, corpus.max_events, mix=True), dtype=torch.int32,
+                             device="cuda:0")
             out["labels_us"] = graph_us(lambda i: ops.corpus_yolo_labels(
                 corpus.events, dev_items[i % 4], corpus.max_events, corpus.n_label_frames, corpus.bounds, corpus.grid, corpus.rot,
                 ws, target, rows, corpus.status), iters)
             for key, tabs in (("labels_mix_us", dev_mates), ("labels_mix_p1_us", every)):
-                out[key] = graph_us(lambda i: ops.corpus_yolo_labels_mix(
-                    corpus.events, dev_items[i % 4], tabs[i % 4], corpus.max_events, corpus.n_label_frames, corpus.bounds,
-                    corpus.grid, corpus.rot, ws, target, rows, corpus.status), iters)
+                out[key] = graph_us(lambda i: ops.corpus_yolo_labels(
+                    corpus.events, dev_items[i % 4], corpus.max_events, corpus.n_label_frames, corpus.bounds, corpus.grid,
+                    corpus.rot, ws, target, rows, corpus.status, mates=tabs[i % 4]), iters)
             del target, rows, ws
         else:
             target = torch.empty(corpus.target_shape(batch), dtype=torch.float32, device="cuda:0")
@@ -257,43 +258,37 @@ def bench_batch(root, batch, steps, workers, iters, loss="adyolo", mic=False, n_
                 corpus.events, dev_items[i % 4], corpus.xyz, corpus.max_events, corpus.n_label_frames, corpus.nb_classes, loss,
                 target, corpus.status), iters)
             for key, tabs in (("labels_mix_us", dev_mates), ("labels_mix_p1_us", every)):
-                out[key] = graph_us(lambda i: ops.corpus_classwise_labels_mix(
-                    corpus.events, dev_items[i % 4], tabs[i % 4], corpus.xyz, corpus.max_events, corpus.n_label_frames,
-                    corpus.nb_classes, loss, target, corpus.status), iters)
+                out[key] = graph_us(lambda i: ops.corpus_classwise_labels(
+                    corpus.events, dev_items[i % 4], corpus.xyz, corpus.max_events, corpus.n_label_frames, corpus.nb_classes,
+                    loss, target, corpus.status, mates=tabs[i % 4]), iters)
             del target
         corpus.check()
     if yaw:
         # the yaw calls on the same tables (word 7 of every row holds its drawn yaw, which the un-yawed calls do not read)
-        out["gather_yaw_us"] = graph_us(lambda i: ops.corpus_gather_yaw(corpus.pcm, dev_items[i % 4], corpus.rot, corpus.yaw_tab,
-                                                                        audio, corpus.status), iters)
+        out["gather_yaw_us"] = graph_us(lambda i: ops.corpus_gather(corpus.pcm, dev_items[i % 4], corpus.rot, audio, corpus.status,
+                                                                    yaw_tab=corpus.yaw_tab), iters)
         if mix is not None:
             for key, tabs in (("gather_yaw_mix_us", dev_mates), ("gather_yaw_mix_p1_us", every)):
-                out[key] = graph_us(lambda i: ops.corpus_gather_yaw_mix(corpus.pcm, dev_items[i % 4], tabs[i % 4], corpus.rot,
-                                                                        corpus.yaw_tab, audio, corpus.status), iters)
+                out[key] = graph_us(lambda i: ops.corpus_gather(corpus.pcm, dev_items[i % 4], corpus.rot, audio, corpus.status,
+                                                                mates=tabs[i % 4], yaw_tab=corpus.yaw_tab), iters)
         target = torch.empty(corpus.target_shape(batch), dtype=torch.float32, device="cuda:0")
+        forms = [("labels_us", None, False), ("labels_yaw_us", None, True)]          # key, mates, yaw
+        if mix is not None:
+            forms += [("labels_mix_us", dev_mates, False), ("labels_yaw_mix_us", dev_mates, True)]
         if loss == "adyolo":
             rows = torch.empty(1, dtype=torch.int32, device="cuda:0")
-            ws = torch.empty(ops.corpus_labels_mix_workspace_words(batch, corpus.max_events), dtype=torch.int32, device="cuda:0")
-            tail = (corpus.max_events, corpus.n_label_frames, corpus.bounds, corpus.grid, corpus.rot, ws, target, rows,
-                    corpus.status)
-            calls = [("labels_us", ops.corpus_yolo_labels, None), ("labels_yaw_us", ops.corpus_yolo_labels_yaw, None)]
-            if mix is not None:
-                calls += [("labels_mix_us", ops.corpus_yolo_labels_mix, dev_mates),
-                          ("labels_yaw_mix_us", ops.corpus_yolo_labels_yaw_mix, dev_mates)]
-            for key, call, tabs in calls:
-                out[key] = graph_us(lambda i: call(corpus.events, dev_items[i % 4], *(() if tabs is None else (tabs[i % 4],)),
-                                                   *tail), iters)
+            ws = torch.empty(ops.corpus_labels_workspace_words(batch, corpus.max_events, mix=True), dtype=torch.int32,
+                             device="cuda:0")
+            for key, tabs, yawed in forms:
+                out[key] = graph_us(lambda i: ops.corpus_yolo_labels(
+                    corpus.events, dev_items[i % 4], corpus.max_events, corpus.n_label_frames, corpus.bounds, corpus.grid,
+                    corpus.rot, ws, target, rows, corpus.status, mates=None if tabs is None else tabs[i % 4], yaw=yawed), iters)
         else:
-            tail = (corpus.max_events, corpus.n_label_frames, corpus.nb_classes, loss, target, corpus.status)
-            calls = [("labels_us", ops.corpus_classwise_labels, None, (corpus.xyz,)),
-                     ("labels_yaw_us", ops.corpus_classwise_labels_yaw, None, (corpus.xyz, corpus.rot, corpus.yaw_xyz))]
-            if mix is not None:
-                calls += [("labels_mix_us", ops.corpus_classwise_labels_mix, dev_mates, (corpus.xyz,)),
-                          ("labels_yaw_mix_us", ops.corpus_classwise_labels_yaw_mix, dev_mates,
-                           (corpus.xyz, corpus.rot, corpus.yaw_xyz))]
-            for key, call, tabs, xyz in calls:
-                out[key] = graph_us(lambda i: call(corpus.events, dev_items[i % 4], *(() if tabs is None else (tabs[i % 4],)),
-                                                   *xyz, *tail), iters)
+            for key, tabs, yawed in forms:
+                out[key] = graph_us(lambda i: ops.corpus_classwise_labels(
+                    corpus.events, dev_items[i % 4], corpus.xyz, corpus.max_events, corpus.n_label_frames, corpus.nb_classes,
+                    loss, target, corpus.status, mates=None if tabs is None else tabs[i % 4], rot=corpus.rot if yawed else None,
+                    yaw_xyz=corpus.yaw_xyz if yawed else None), iters)
         del target
         corpus.check()
     del audio

@@ -104,6 +104,9 @@ SIGNATURES = {
     "adyolo_classwise_decode": (I, [P, P, L, I, I, P]),
     "adyolo_classwise_select_workspace_words": (L, [L, I, I]),
     "adyolo_classwise_select": (I, [P] * 4 + [L, I, I, F, F, P]),
+    "adyolo_tta_merge_workspace_words": (L, [L, I]),
+    "adyolo_tta_collect": (I, [P, L, P, P, P, P, P, L, I, I, I, I, ctypes.c_uint, P]),
+    "adyolo_tta_merge": (I, [P, P, P, P, L, P, P, L, I, I, I, F, I, P]),
     "adyolo_conv_gemm": (I, [P, P, P, P] + [I] * 13 + [P]),
     "adyolo_conv_gemm_plan": (I, [I] * 13 + [P]),
     "adyolo_pack_wk": (I, [P, P, I, I, I, I, I, P]),

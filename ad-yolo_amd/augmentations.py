@@ -181,6 +181,107 @@ def mic_swap_source(comb_no):
     return src
 
 
+# ---- Rotation test-time augmentation: a clip evaluated under several combinations, the detections turned back and merged
+# (``postprocess.merge_view_rows``, csrc/select.hip ``adyolo_tta_collect`` / ``adyolo_tta_merge``).
+def _view_matrices():
+    """[M_k]: the 3x3 signed permutation that takes a direction vector (x, y, z) to where combination k puts it, derived from
+    ``rotate_labels`` on the three axis directions (column j of M_k is the image of axis j)."""
+    import math
+    axes = ((0, 0), (90, 0), (0, 90))                                            # (azimuth, elevation) of x, y, z
+    out = []
+    for k in range(len(COMBINATIONS)):
+        m = [[0] * 3 for _ in range(3)]
+        for j, ev in enumerate(rotate_labels({0: [[0, 0, az, el] for az, el in axes]}, k)[0]):
+            az, el = math.radians(ev[2]), math.radians(ev[3])
+            image = (math.cos(az) * math.cos(el), math.sin(az) * math.cos(el), math.sin(el))
+            for i in range(3):
+                m[i][j] = int(round(image[i]))
+        out.append(tuple(tuple(row) for row in m))
+    return tuple(out)
+
+
+_VIEW_MATRICES = _view_matrices()
+assert all(sorted(abs(v) for row in m for v in row) == [0] * 6 + [1] * 3 and all(sum(abs(v) for v in row) == 1 for row in m)
+           and all(sum(abs(m[i][j]) for i in range(3)) == 1 for j in range(3)) for m in _VIEW_MATRICES), _VIEW_MATRICES
+assert _VIEW_MATRICES[0] == ((1, 0, 0), (0, 1, 0), (0, 0, 1)), _VIEW_MATRICES[0]
+
+
+def view_matrix(comb_no):
+    """Combination -> M (3x3 ``np.float32``, entries exactly 0 or +-1, inverse = transpose): a source at direction d is, in the
+    clip under that combination, at M d; a detection there is turned back by M^T."""
+    import numpy as np
+    if isinstance(comb_no, bool) or int(comb_no) != comb_no or not 0 <= int(comb_no) < len(COMBINATIONS):
+        raise ValueError("view_matrix: combination %r is not one of 0..%d" % (comb_no, len(COMBINATIONS) - 1))
+    return np.asarray(_VIEW_MATRICES[int(comb_no)], dtype=np.float32)
+
+
+TTA_DEFAULT_UNIFY_DEG = 15.0
+TTA_DEFAULT_ROWS_PER_FRAME = 64
+
+
+def _tta_key(params, key, default=None):
+    for section in ("test_config", "train_config"):
+        if params.get(section, {}).get(key) is not None:
+            return params[section][key], "%s.%s" % (section, key)
+    return default, "test_config.%s" % key
+
+
+def tta_views(params):
+    """``test_config.tta_views`` (falling back to ``train_config.tta_views``) -> None (absent or None: off) or the list of
+    combinations a clip is evaluated under.  "all": every combination that is a symmetry of the format, 0..15 for FOA and
+    ``MIC_SWAP_COMBS`` with ``data_config.audio_format: mic``; a list of combination numbers: those.  The unrotated clip is
+    always view 0 and is not listed twice.  ``ValueError`` naming the key: anything else, or a combination that is no symmetry
+    of the format."""
+    value, where = _tta_key(params, "tta_views")
+    if value is None:
+        return None
+    fmt = str(params.get("data_config", {}).get("audio_format", "foa")).lower()
+    allowed = tuple(MIC_SWAP_COMBS) if fmt == "mic" else tuple(range(len(COMBINATIONS)))
+    if isinstance(value, str):
+        if value.lower() != "all":
+            raise ValueError("%s must be 'all' or a list of combination numbers (got %r)" % (where, value))
+        return list(allowed)
+    if not isinstance(value, (list, tuple)):
+        raise ValueError("%s must be 'all' or a list of combination numbers (got %r)" % (where, value))
+    views = [0]
+    for v in value:
+        if isinstance(v, bool) or not isinstance(v, int) or v not in allowed:
+            raise ValueError("%s: %r is no symmetry of the %s format (the symmetries are %s)" % (where, v, fmt, list(allowed)))
+        if v not in views:
+            views.append(v)
+    return views
+
+
+def tta_options(params, views=None, postprocessor=None):
+    """What ``test.test_epoch_corpus(tta=...)`` takes: None (``tta_views`` is off) or {'views', 'min_views', 'unify_thresh',
+    'max_rows_per_frame'}.  views: the list to use instead of ``tta_views(params)``.  The other keys are read like
+    ``tta_views`` (``test_config``, then ``train_config``): ``tta_min_views`` (default a majority, (V + 1) // 2; an integer in
+    [1, V]), ``tta_unify_thresh`` (degrees in (0, 180]; default the head's ``unify_thresh`` -- ``postprocessor``'s, or
+    ``train_config``'s for adyolo and adpit -- else 15) and ``tta_max_rows_per_frame`` (default 64; an integer in [1, 1024]).
+    ``ValueError`` naming the key otherwise."""
+    import math
+    views = tta_views(params) if views is None else list(views)
+    if views is None:
+        return None
+    if not views or views[0] != 0 or len(set(views)) != len(views) or any(not 0 <= int(v) < len(COMBINATIONS) for v in views):
+        raise ValueError("tta_options: views %r must start with 0 and hold distinct combinations" % (views,))
+    n = len(views)
+    min_views, where = _tta_key(params, "tta_min_views", (n + 1) // 2)
+    if isinstance(min_views, bool) or not isinstance(min_views, int) or not 1 <= min_views <= n:
+        raise ValueError("%s must be an integer in [1, %d] (got %r)" % (where, n, min_views))
+    head = getattr(postprocessor, "unify_thresh", None)
+    if postprocessor is None and params.get("args", {}).get("loss") in ("adyolo", "adpit"):
+        head = params.get("train_config", {}).get("unify_thresh")
+    unify, where = _tta_key(params, "tta_unify_thresh", TTA_DEFAULT_UNIFY_DEG if head is None else head)
+    if isinstance(unify, bool) or not isinstance(unify, (int, float)) or not math.isfinite(unify) or not 0.0 < unify <= 180.0:
+        raise ValueError("%s must be an angle in (0, 180] degrees (got %r)" % (where, unify))
+    cap, where = _tta_key(params, "tta_max_rows_per_frame", TTA_DEFAULT_ROWS_PER_FRAME)
+    if isinstance(cap, bool) or not isinstance(cap, int) or not 1 <= cap <= 1024:
+        raise ValueError("%s must be an integer in [1, 1024] (got %r)" % (where, cap))
+    return {"views": [int(v) for v in views], "min_views": int(min_views), "unify_thresh": float(unify),
+            "max_rows_per_frame": int(cap)}
+
+
 def channel_swap_enabled(params):
     """``aug_config.channel_swap_augment``, with its two refusals: MIC-format audio only, and not together with the FOA
     rotation (``ValueError``: both would move the labels)."""

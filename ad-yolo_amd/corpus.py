@@ -738,6 +738,9 @@ class EvalDeviceCorpus(_CorpusBase):
         for i in range(n):
             items[i] = (hc.rec_start[i], 0, hc.ev_start[i], hc.ev_start[i + 1] - hc.ev_start[i], -1, i, 0, 0)
         self.items = torch.from_numpy(items).to(self.device)
+        # rotation test-time augmentation (``launch_view``): the format, the item table of each view, the MIC source table
+        self.audio_format = str(params["data_config"].get("audio_format", "foa")).lower()
+        self._view_items, self.mic_src = {}, None
         if self.loss_nm == "adyolo":
             self._yolo_tables(params)
             self.cap_per_clip = int(cap_per_clip) if cap_per_clip is not None else max(1, self.max_events * self.cells)
@@ -767,13 +770,24 @@ class EvalDeviceCorpus(_CorpusBase):
         """Target rows of a batch of ``batch`` clips (AD-YOLO)."""
         return self._round_cap(int(batch) * self.cap_per_clip)
 
-    def _items_of(self, indices):
+    def _items_of(self, indices, table=None):
+        table = self.items if table is None else table
         idx = list(indices)
         if not idx or min(idx) < 0 or max(idx) >= len(self.filelist):
             raise ValueError("EvalDeviceCorpus.launch: clips %s of a split of %d" % (idx, len(self.filelist)))
         if idx == list(range(idx[0], idx[0] + len(idx))):
-            return idx, self.items[idx[0]:idx[0] + len(idx)]                     # a view: nothing crosses PCIe
-        return idx, self.items.index_select(0, torch.tensor(idx, dtype=torch.int64).to(self.device, non_blocking=True))
+            return idx, table[idx[0]:idx[0] + len(idx)]                          # a view: nothing crosses PCIe
+        return idx, table.index_select(0, torch.tensor(idx, dtype=torch.int64).to(self.device, non_blocking=True))
+
+    def _batch_shape(self, idx):
+        """(B, samples, label frames) of the clips ``idx``, which must agree in both."""
+        b, t, frames = len(idx), self.n_hops[idx[0]], self.label_frames[idx[0]]
+        if any(self.n_hops[i] != t or self.label_frames[i] != frames for i in idx):
+            raise ValueError("EvalDeviceCorpus.launch: clips %s differ in length (%s samples): one length per batch"
+                             % (idx, [self.lengths[i] for i in idx]))
+        if t <= 0 or frames <= 0:
+            raise ValueError("EvalDeviceCorpus.launch: clip %s is shorter than one hop / label frame" % self.filelist[idx[0]])
+        return b, t, frames
 
     def launch(self, indices, audio_out=None):
         """Clips ``indices`` of ``get_filelist()`` (equal whole-hop lengths, e.g. a range of ``batches``) -> (audio (B, t, 4) f32,
@@ -781,12 +795,7 @@ class EvalDeviceCorpus(_CorpusBase):
         and row_start (B + 1,) int32, clip b's rows at [row_start[b], row_start[b + 1]); class-wise heads: the dense
         (B, T', ...) target and None.  audio_out: write the audio into this buffer (a recorded forward graph's input)."""
         idx, items = self._items_of(indices)
-        b, t, frames = len(idx), self.n_hops[idx[0]], self.label_frames[idx[0]]
-        if any(self.n_hops[i] != t or self.label_frames[i] != frames for i in idx):
-            raise ValueError("EvalDeviceCorpus.launch: clips %s differ in length (%s samples): one length per batch"
-                             % (idx, [self.lengths[i] for i in idx]))
-        if t <= 0 or frames <= 0:
-            raise ValueError("EvalDeviceCorpus.launch: clip %s is shorter than one hop / label frame" % self.filelist[idx[0]])
+        b, t, frames = self._batch_shape(idx)
         audio = self._out(audio_out, (b, t, 4))
         ops.corpus_gather(self.pcm, items, self.rot, audio, self.status)
         if self.loss_nm != "adyolo":
@@ -803,6 +812,28 @@ class EvalDeviceCorpus(_CorpusBase):
                                ws[b * max(me, 1):], self.status)
         row_start = ws[::max(me, 1)].contiguous()
         return audio, target, row_start
+
+    def launch_view(self, indices, comb, audio_out=None):
+        """The audio of ``launch`` for the same clips under combination ``comb`` (rotation test-time augmentation): FOA-rotated,
+        or with ``data_config.audio_format: mic`` the capsules permuted (a combination that is no symmetry of the array:
+        ``ValueError``).  Audio only -- a view has no labels -> audio (B, t, 4) f32.  The item table of a view is a copy of the
+        split's with word 4 set, made once."""
+        from .augmentations import COMBINATIONS, MIC_SWAP_COMBS, mic_swap_source
+        comb = int(comb)
+        if not 0 <= comb < len(COMBINATIONS):
+            raise ValueError("EvalDeviceCorpus.launch_view: combination %r is not one of 0..%d" % (comb, len(COMBINATIONS) - 1))
+        if self.audio_format == "mic":
+            mic_swap_source(comb)                                # ValueError: no symmetry of the array
+            if self.mic_src is None:
+                self.mic_src = ops.corpus_mic_table({k: mic_swap_source(k) for k in MIC_SWAP_COMBS})
+        if comb not in self._view_items:
+            table = self.items.clone()
+            table[:, 4] = comb
+            self._view_items[comb] = table
+        idx, items = self._items_of(indices, self._view_items[comb])
+        b, t, _ = self._batch_shape(idx)
+        audio = self._out(audio_out, (b, t, 4))
+        return ops.corpus_gather(self.pcm, items, self.rot, audio, self.status, mic_src=self.mic_src)
 
 
 # ------------------------------------------------------------------------------------------------------- windowed inference

@@ -17,7 +17,8 @@
 //   2. select_scan_kernel (one workgroup): exclusive scan of the slot counts, per-frame row counts and the total.
 //   3. select_compact_kernel: slot rows -> compacted [frame, class, x, y, z].
 // Angular distances use the float32 formula of postprocess._ang_dist_deg evaluated in its order without contraction.
-// The class-wise heads (seddoa / accdoa / adpit) select with adyolo_classwise_select at the end of this file.
+// The class-wise heads (seddoa / accdoa / adpit) select with adyolo_classwise_select further down; behind it, the rows that
+// several views of a clip select are merged by adyolo_tta_collect / adyolo_tta_merge (rotation test-time augmentation).
 #include "common.hpp"
 
 namespace adyolo {
@@ -44,6 +45,40 @@ __device__ __forceinline__ int sel_first(uint32_t bits, int kw) {
         if (b) return k * SEL_WAVE + (int)__builtin_ctzll(b);
     }
     return -1;
+}
+
+// One connected component of the relation near(f, j), grown breadth first from `seed` (already taken out of `left`) over the
+// rows still in `left`; the rows that join leave `left`.  -> the component as lane masks.  front: two lists of K ints in LDS.
+template <class Near>
+__device__ __forceinline__ uint32_t sel_grow(int seed, uint32_t &left, int kw, int lane, int *const *front, Near near) {
+    uint32_t memb = lane == (seed & (SEL_WAVE - 1)) ? 1u << (seed / SEL_WAVE) : 0u;
+    int cur = 0, fsz = 1;
+    if (lane == 0) front[0][0] = seed;
+    __syncthreads();
+    while (fsz > 0) {
+        uint32_t fresh = 0;
+        for (int k = 0; k < kw; ++k) {
+            if (!((left >> k) & 1u)) continue;
+            const int j = lane + k * SEL_WAVE;
+            for (int q = 0; q < fsz; ++q)
+                if (near(front[cur][q], j)) {
+                    fresh |= 1u << k;
+                    break;
+                }
+        }
+        int n = 0;
+        for (int k = 0; k < kw; ++k) {
+            const unsigned long long b = __ballot((fresh >> k) & 1u);
+            if ((fresh >> k) & 1u) front[cur ^ 1][n + __popcll(b & ((1ull << lane) - 1ull))] = lane + k * SEL_WAVE;
+            n += __popcll(b);
+        }
+        left &= ~fresh;
+        memb |= fresh;
+        __syncthreads();
+        cur ^= 1;
+        fsz = n;
+    }
+    return memb;
 }
 
 struct SelRows {
@@ -161,36 +196,9 @@ __global__ __launch_bounds__(64) void yolo_select_kernel(const float *__restrict
         if (lane == (seed & (SEL_WAVE - 1))) left &= ~(1u << (seed / SEL_WAVE));
         float ox, oy, oz;
         if (mode == ADYOLO_SELECT_CONN) {
-            uint32_t memb = lane == (seed & (SEL_WAVE - 1)) ? 1u << (seed / SEL_WAVE) : 0u;
-            int cur = 0, fsz = 1;
-            if (lane == 0) s_front[0][0] = seed;
-            __syncthreads();
-            while (fsz > 0) {
-                uint32_t fresh = 0;
-                for (int k = 0; k < kw; ++k) {
-                    if (!((left >> k) & 1u)) continue;
-                    const int j = lane + k * SEL_WAVE;
-                    const float ru = r.ru[j], sv = r.sv[j], cv = r.cv[j];
-                    for (int q = 0; q < fsz; ++q) {
-                        const int f = s_front[cur][q];
-                        if (sel_dist(r.ru[f], r.sv[f], r.cv[f], ru, sv, cv) < unify_t) {
-                            fresh |= 1u << k;
-                            break;
-                        }
-                    }
-                }
-                int n = 0;
-                for (int k = 0; k < kw; ++k) {
-                    const unsigned long long b = __ballot((fresh >> k) & 1u);
-                    if ((fresh >> k) & 1u) s_front[cur ^ 1][n + __popcll(b & ((1ull << lane) - 1ull))] = lane + k * SEL_WAVE;
-                    n += __popcll(b);
-                }
-                left &= ~fresh;
-                memb |= fresh;
-                __syncthreads();
-                cur ^= 1;
-                fsz = n;
-            }
+            const uint32_t memb = sel_grow(seed, left, kw, lane, s_front, [&](int f, int j) {
+                return sel_dist(r.ru[f], r.sv[f], r.cv[f], r.ru[j], r.sv[j], r.cv[j]) < unify_t;
+            });
             sel_vote(r, memb, kw, lane, ox, oy, oz);
         } else {
             const float ru = r.ru[seed], sv = r.sv[seed], cv = r.cv[seed];
@@ -354,6 +362,169 @@ static int classwise_select_launch(const float *dec, int *count, int *offs, floa
     return check_launch("classwise_select_write");
 }
 
+// ------------------------------------------------------------------------------------ rotation test-time augmentation
+// postprocess.merge_view_rows on the device.  adyolo_tta_collect turns one view's selected rows back into the recording's frame
+// and parks them, frame by frame, in a pool [V][frames][P] of {class, x, y, z}; adyolo_tta_merge clusters the pool's rows per
+// (frame, class) -- connected components of dot > cos_t over unit vectors, seeded in candidate order (views ascending, a
+// view's rows in the order its selection wrote them) -- keeps the clusters that at least min_views DISTINCT views support and
+// writes [frame, class, s / |s|], s the sum of the members' unit vectors in candidate order.  Every operation is a correctly
+// rounded float32 one evaluated in the host's order without contraction: the rows are the host's bit for bit.
+// Merge launches: the kept clusters of every (frame, class) counted, select_scan_kernel, and a pass that forms them again and
+// stores them at the scanned offsets (as the class-wise selection: cheaper than parking up to 1024 rows per slot).
+
+// view matrix as a word: component i of the turned-back vector is sign_i * xyz[src_i]; src_i in bits [4 i, 4 i + 2), bit
+// 4 i + 2 set for a negative sign (the product with +-1 is exact, and a zero keeps the sign the host's product gives it)
+__device__ __forceinline__ float tta_pick(uint32_t m, int i, float x, float y, float z) {
+    const uint32_t f = m >> (4 * i);
+    const float v = (f & 3u) == 0 ? x : (f & 3u) == 1 ? y : z;
+    return v * ((f & 4u) ? -1.f : 1.f);
+}
+
+__device__ __forceinline__ float tta_dot(float ax, float ay, float az, float bx, float by, float bz) {
+#pragma clang fp contract(off)
+    return (ax * bx + ay * by) + az * bz;
+}
+
+// one thread per (frame, pool position); offs: exclusive scan of counts
+__global__ __launch_bounds__(256) void tta_collect_kernel(const float *__restrict__ rows, long n_rows,
+                                                          const int *__restrict__ counts, const int *__restrict__ offs,
+                                                          f32x4 *__restrict__ pool, int *__restrict__ pool_counts,
+                                                          long n_frames, int P, int C, uint32_t mat, int *__restrict__ status) {
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long f = t / P;
+    const int i = (int)(t - f * P);
+    if (f >= n_frames) return;
+    int cnt = counts[f], bits = 0;
+    const long off = offs[f];
+    if (cnt < 0 || off < 0 || off + cnt > n_rows) {
+        cnt = 0;
+        bits |= ADYOLO_TTA_BAD_ROWS;
+    }
+    if (cnt > P) {
+        cnt = P;
+        bits |= ADYOLO_TTA_ROWS_OVERFLOW;
+    }
+    if (i < cnt) {
+        const float *r = rows + (size_t)(off + i) * 5;
+        const float c = r[1], x = r[2], y = r[3], z = r[4];
+        f32x4 o;
+        o[0] = c;
+        o[1] = tta_pick(mat, 0, x, y, z);
+        o[2] = tta_pick(mat, 1, x, y, z);
+        o[3] = tta_pick(mat, 2, x, y, z);
+        pool[f * P + i] = o;
+        if (!(c >= 0.f && c < (float)C)) atomicOr(status, ADYOLO_TTA_BAD_ROWS);   // no (frame, class) would own the row
+    }
+    if (i == 0) {
+        pool_counts[f] = cnt;
+        if (bits) atomicOr(status, bits);
+    }
+}
+
+// grid: one 64-lane workgroup per (frame, class); dynamic LDS: 7 arrays of kmax words (kmax a multiple of 64).  WRITE = false:
+// count[slot] = kept clusters; WRITE = true: the rows of a slot with count[slot] > 0 at offs[slot].
+template <bool WRITE>
+__global__ __launch_bounds__(64) void tta_merge_kernel(const f32x4 *__restrict__ pool, const int *__restrict__ pool_counts,
+                                                       int *__restrict__ count, const int *__restrict__ offs,
+                                                       float *__restrict__ rows, long n_frames, int C, int V, int P, int kmax,
+                                                       float cos_t, int min_views, int *__restrict__ status) {
+#pragma clang fp contract(off)
+    extern __shared__ float sel_lds[];
+    float *ux = sel_lds, *uy = sel_lds + kmax, *uz = sel_lds + 2 * kmax;
+    int *s_view = reinterpret_cast<int *>(sel_lds + 3 * kmax), *s_cl = s_view + kmax;
+    int *s_front[2] = {s_cl + kmax, s_cl + 2 * kmax};
+    const long slot = blockIdx.x;
+    const long frame = slot / C;
+    const int cls = (int)(slot - frame * C);
+    const int lane = threadIdx.x;
+    if (WRITE && count[slot] == 0) return;
+    // 1. the candidates of this class: views ascending, a view's rows in pool order; unit vectors
+    int K = 0;
+    bool bad = false;
+    for (int v = 0; v < V; ++v) {
+        const int n = min(max(pool_counts[v * n_frames + frame], 0), P);
+        const f32x4 *src = pool + ((size_t)v * n_frames + frame) * P;
+        for (int i0 = 0; i0 < n; i0 += SEL_WAVE) {
+            const int i = i0 + lane;
+            bool good = false;
+            float x = 0.f, y = 0.f, z = 0.f, nrm = 1.f;
+            if (i < n) {
+                const f32x4 r = src[i];
+                if (r[0] == (float)cls) {
+                    x = r[1], y = r[2], z = r[3];
+                    nrm = sqrtf((x * x + y * y) + z * z);
+                    good = nrm > 0.f && nrm < INFINITY;           // a zero, infinite or NaN norm: dropped and reported
+                    bad |= !good;
+                }
+            }
+            const unsigned long long b = __ballot(good);
+            const int at = K + __popcll(b & ((1ull << lane) - 1ull));
+            if (good && at < kmax) {
+                ux[at] = x / nrm;
+                uy[at] = y / nrm;
+                uz[at] = z / nrm;
+                s_view[at] = v;
+            }
+            K += __popcll(b);
+        }
+    }
+    if (!WRITE && bad) atomicOr(status, ADYOLO_TTA_BAD_VECTOR);
+    if (K == 0 || K > ADYOLO_SELECT_MAX_N || K > kmax) {          // (kmax >= min(V * P, ADYOLO_SELECT_MAX_N): one condition)
+        if (!WRITE && lane == 0) {
+            count[slot] = 0;
+            if (K) atomicOr(status, ADYOLO_TTA_CAND_OVERFLOW);
+        }
+        return;
+    }
+    __syncthreads();
+    // 2. connected components, seeded at the lowest unassigned candidate
+    const int kw = (K + SEL_WAVE - 1) / SEL_WAVE;
+    uint32_t left = 0;
+    for (int k = 0; k < kw; ++k)
+        if (lane + k * SEL_WAVE < K) left |= 1u << k;
+    int S = 0;
+    for (int seed = sel_first(left, kw); seed >= 0; seed = sel_first(left, kw), ++S) {
+        if (lane == (seed & (SEL_WAVE - 1))) left &= ~(1u << (seed / SEL_WAVE));
+        const uint32_t memb = sel_grow(seed, left, kw, lane, s_front, [&](int f, int j) {
+            return tta_dot(ux[f], uy[f], uz[f], ux[j], uy[j], uz[j]) > cos_t;
+        });
+        for (int k = 0; k < kw; ++k)
+            if ((memb >> k) & 1u) s_cl[lane + k * SEL_WAVE] = S;
+    }
+    __syncthreads();
+    // 3. one lane per cluster: the views that support it and the sum of its members in candidate order
+    int kept = 0;
+    float *dst = WRITE ? rows + (size_t)offs[slot] * 5 : nullptr;
+    for (int c0 = 0; c0 < S; c0 += SEL_WAVE) {
+        const int c = c0 + lane;
+        float sx = 0.f, sy = 0.f, sz = 0.f;
+        uint32_t views = 0;
+        if (c < S)
+            for (int j = 0; j < K; ++j)
+                if (s_cl[j] == c) {                               // the sum starts AT the first member: a lone -0 stays -0
+                    sx = views ? sx + ux[j] : ux[j];
+                    sy = views ? sy + uy[j] : uy[j];
+                    sz = views ? sz + uz[j] : uz[j];
+                    views |= 1u << s_view[j];
+                }
+        const bool keep = c < S && __popc(views) >= min_views;
+        const unsigned long long b = __ballot(keep);
+        if (WRITE && keep) {
+            float *d = dst + (size_t)(kept + __popcll(b & ((1ull << lane) - 1ull))) * 5;
+            const float nrm = sqrtf((sx * sx + sy * sy) + sz * sz);
+            d[0] = (float)frame, d[1] = (float)cls, d[2] = sx / nrm, d[3] = sy / nrm, d[4] = sz / nrm;
+        }
+        kept += __popcll(b);
+    }
+    if (!WRITE && lane == 0) count[slot] = kept;
+}
+
+// the matrix word of adyolo_tta_collect: three sources that are a permutation of the axes
+static inline bool tta_matrix_ok(unsigned m) {
+    const unsigned a = m & 3u, b = (m >> 4) & 3u, c = (m >> 8) & 3u;
+    return (m >> 11) == 0 && !(m & 0x88u) && a < 3 && b < 3 && c < 3 && a != b && b != c && a != c;
+}
+
 }  // namespace adyolo
 
 using namespace adyolo;
@@ -418,4 +589,76 @@ extern "C" int adyolo_classwise_select(const float *dec, float *ws, float *rows,
                                                                unify_thresh, st);
     return classwise_select_launch<ADYOLO_CLASSWISE_SEDDOA>(dec, count, offs, rows, frame_counts, n_frames, C, conf_thresh,
                                                             unify_thresh, st);
+}
+
+extern "C" long adyolo_tta_merge_workspace_words(long n_frames, int C) {
+    if (n_frames <= 0 || C <= 0) return 0;
+    return 2 * n_frames * C + 2 * n_frames + 1;
+}
+
+static int tta_shape_ok(const char *who, long n_frames, int C, int n_views, int P) {
+    ADYOLO_REQUIRE(n_frames > 0 && C > 0, ADYOLO_EINVAL, "%s: %ld frames x %d classes", who, n_frames, C);
+    ADYOLO_REQUIRE(n_views >= 1 && n_views <= ADYOLO_TTA_MAX_VIEWS, ADYOLO_EINVAL, "%s: %d views, 1 to %d are taken", who,
+                   n_views, ADYOLO_TTA_MAX_VIEWS);
+    ADYOLO_REQUIRE(P >= 1 && P <= ADYOLO_SELECT_MAX_N, ADYOLO_EINVAL, "%s: %d rows per view and frame, 1 to %d are taken", who, P,
+                   ADYOLO_SELECT_MAX_N);
+    ADYOLO_REQUIRE(n_frames * C < (1L << 31) && n_frames * n_views * P < (1L << 31), ADYOLO_ENOSUP,
+                   "%s: %ld frames x %d classes, %d views x %d rows do not fit 32-bit row counts", who, n_frames, C, n_views, P);
+    return 0;
+}
+
+extern "C" int adyolo_tta_collect(const float *rows, long n_rows, const int *frame_counts, float *ws, float *pool,
+                                  int *pool_counts, int *status, long n_frames, int C, int n_views, int view, int P,
+                                  unsigned matrix, void *stream) {
+    ADYOLO_REQUIRE(rows && frame_counts && ws && pool && pool_counts && status && n_rows >= 0, ADYOLO_EINVAL,
+                   "tta_collect: null pointer");
+    int rc = tta_shape_ok("tta_collect", n_frames, C, n_views, P);
+    if (rc) return rc;
+    ADYOLO_REQUIRE(view >= 0 && view < n_views, ADYOLO_EINVAL, "tta_collect: view %d of %d", view, n_views);
+    ADYOLO_REQUIRE(tta_matrix_ok(matrix), ADYOLO_EINVAL, "tta_collect: 0x%x is no signed permutation of the axes", matrix);
+    ADYOLO_REQUIRE(((uintptr_t)pool & 15) == 0, ADYOLO_EINVAL, "tta_collect: pool is not 16-byte aligned");
+    // the tail of the merge workspace: the exclusive scan of the frame counts, and the copy of them the scan also writes
+    int *offs = reinterpret_cast<int *>(ws) + 2 * n_frames * C;
+    int *copy = offs + n_frames;
+    hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(select_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, st, frame_counts, offs, copy, n_frames, 1);
+    rc = check_launch("tta_collect_scan");
+    if (rc) return rc;
+    hipLaunchKernelGGL(tta_collect_kernel, dim3(cdiv(n_frames * P, 256)), dim3(256), 0, st, rows, n_rows, frame_counts, offs,
+                       reinterpret_cast<f32x4 *>(pool) + (size_t)view * n_frames * P, pool_counts + (size_t)view * n_frames,
+                       n_frames, P, C, (uint32_t)matrix, status);
+    return check_launch("tta_collect");
+}
+
+extern "C" int adyolo_tta_merge(const float *pool, const int *pool_counts, float *ws, float *rows, long capacity,
+                                int *frame_counts, int *status, long n_frames, int C, int n_views, int P, float cos_t,
+                                int min_views, void *stream) {
+    ADYOLO_REQUIRE(pool && pool_counts && ws && rows && frame_counts && status, ADYOLO_EINVAL, "tta_merge: null pointer");
+    int rc = tta_shape_ok("tta_merge", n_frames, C, n_views, P);
+    if (rc) return rc;
+    ADYOLO_REQUIRE(min_views >= 1 && min_views <= n_views, ADYOLO_EINVAL, "tta_merge: min_views %d with %d views", min_views,
+                   n_views);
+    ADYOLO_REQUIRE(((uintptr_t)pool & 15) == 0, ADYOLO_EINVAL, "tta_merge: pool is not 16-byte aligned");
+    // a kept cluster has rows of min_views views, so a frame gives at most V * P / min_views of them
+    const long per_frame = (long)n_views * P / min_views;
+    ADYOLO_REQUIRE(capacity >= n_frames * per_frame, ADYOLO_EINVAL, "tta_merge: %ld rows of capacity, %ld frames x %ld are needed",
+                   capacity, n_frames, per_frame);
+    const long n_slots = n_frames * C;
+    int *count = reinterpret_cast<int *>(ws);
+    int *offs = count + n_slots;
+    const long most = (long)n_views * P < ADYOLO_SELECT_MAX_N ? (long)n_views * P : ADYOLO_SELECT_MAX_N;
+    const int kmax = (int)((most + SEL_WAVE - 1) / SEL_WAVE * SEL_WAVE);
+    const size_t lds = (size_t)7 * kmax * sizeof(float);
+    const f32x4 *pl = reinterpret_cast<const f32x4 *>(pool);
+    hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(tta_merge_kernel<false>, dim3((unsigned)n_slots), dim3(SEL_WAVE), lds, st, pl, pool_counts, count, offs,
+                       rows, n_frames, C, n_views, P, kmax, cos_t, min_views, status);
+    rc = check_launch("tta_merge_count");
+    if (rc) return rc;
+    hipLaunchKernelGGL(select_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, st, count, offs, frame_counts, n_frames, C);
+    rc = check_launch("tta_merge_scan");
+    if (rc) return rc;
+    hipLaunchKernelGGL(tta_merge_kernel<true>, dim3((unsigned)n_slots), dim3(SEL_WAVE), lds, st, pl, pool_counts, count, offs,
+                       rows, n_frames, C, n_views, P, kmax, cos_t, min_views, status);
+    return check_launch("tta_merge_write");
 }

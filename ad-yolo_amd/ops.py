@@ -1093,6 +1093,121 @@ def classwise_select(decoded, nb_classes, mode, conf, unify=None, trim=True):
     return rows[:total], counts[:frames]
 
 
+TTA_STATUS = ((1, "more rows of one view in one frame than the pool holds (enlarge tta_max_rows_per_frame)"),   # ADYOLO_TTA_*
+              (2, "more than 1024 candidates in one frame and class"),
+              (4, "a selected row with a zero or non-finite vector was dropped"),
+              (8, "frame counts negative or past the rows given, or a class outside [0, nb_classes)"))
+TTA_BAD_VECTOR = 4
+TTA_MAX_VIEWS = 16                                            # ADYOLO_TTA_MAX_VIEWS
+
+
+def tta_matrix_word(matrix):
+    """A view's 3x3 signed permutation M (``augmentations.view_matrix``) -> the word ``adyolo_tta_collect`` takes: component i of
+    M^T xyz is sign_i * xyz[src_i], src_i in bits [4 i, 4 i + 2), bit 4 i + 2 set for a negative sign."""
+    m = np.asarray(matrix)
+    if m.shape != (3, 3) or not np.isin(m, (-1, 0, 1)).all() or not (np.abs(m).sum(0) == 1).all() \
+            or not (np.abs(m).sum(1) == 1).all():
+        raise ValueError("tta_matrix_word: %r is no 3x3 signed permutation" % (matrix,))
+    word = 0
+    for i in range(3):
+        j = int(np.abs(m[:, i]).argmax())
+        word |= (j | (4 if m[j, i] < 0 else 0)) << (4 * i)
+    return word
+
+
+def tta_status_check(word):
+    """Raise ``AdyoloHipError`` for the ADYOLO_TTA_* bits of a status word already read to the host; a dropped vector alone
+    (a NaN in the network's output, which the plain pass writes out as it is) only warns."""
+    word = int(word)
+    why = "; ".join(msg for bit, msg in TTA_STATUS if word & bit)
+    if word & ~TTA_BAD_VECTOR:
+        raise _lib.AdyoloHipError("adyolo test-time augmentation failed (status 0x%x): %s" % (word, why))
+    if word:
+        import warnings
+        warnings.warn("adyolo test-time augmentation (status 0x%x): %s" % (word, why))
+
+
+def tta_buffers(device, n_views, frames, nb_classes, rows_per_frame, min_views=1):
+    """The buffers one batch shape of ``tta_collect`` / ``tta_merge`` needs, allocated once: {'pool' (V, frames, P, 4) float32,
+    'pool_counts' (V, frames) int32, 'ws', 'rows' (frames * (V * P // min_views), 5) float32, 'counts' (frames + 1,) int32}."""
+    v, f, c, p = int(n_views), int(frames), int(nb_classes), int(rows_per_frame)
+    dev = torch.device(device)
+    return {"pool": torch.empty((v, f, p, 4), dtype=torch.float32, device=dev),
+            "pool_counts": torch.empty((v, f), dtype=torch.int32, device=dev),
+            "ws": torch.empty(max(1, _lib.load().adyolo_tta_merge_workspace_words(f, c)), dtype=torch.float32, device=dev),
+            "rows": torch.empty((max(1, f * (v * p // max(1, int(min_views)))), 5), dtype=torch.float32, device=dev),
+            "counts": torch.empty(f + 1, dtype=torch.int32, device=dev)}
+
+
+def _tta_pool(name, pool, pool_counts, status, ws, nb_classes):
+    """The checks both TTA calls share -> (V, frames, P)."""
+    _chk(pool, ws)
+    if pool.dim() != 4 or pool.shape[3] != 4 or not 1 <= pool.shape[0] <= TTA_MAX_VIEWS or pool.shape[1] < 1 or pool.shape[2] < 1:
+        raise _lib.AdyoloHipError("%s: pool %s is not (views <= %d, frames, rows per frame, 4)"
+                                  % (name, tuple(pool.shape), TTA_MAX_VIEWS))
+    v, frames, p, _ = pool.shape
+    for what, t, shape in (("pool_counts", pool_counts, (v, frames)), ("status", status, None)):
+        if not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous() or t.device != pool.device \
+                or (shape is not None and tuple(t.shape) != shape) or t.numel() < 1:
+            raise _lib.AdyoloHipError("%s: %s must be a contiguous int32 tensor%s on %s"
+                                      % (name, what, "" if shape is None else " %s" % (shape,), pool.device))
+    if int(nb_classes) < 1 or ws.device != pool.device \
+            or ws.numel() < _lib.load().adyolo_tta_merge_workspace_words(frames, int(nb_classes)):
+        raise _lib.AdyoloHipError("%s: the workspace needs %d words on %s (adyolo_tta_merge_workspace_words)"
+                                  % (name, _lib.load().adyolo_tta_merge_workspace_words(frames, max(1, int(nb_classes))), pool.device))
+    return v, frames, p
+
+
+def tta_collect(rows, counts, view, matrix, nb_classes, pool, pool_counts, status, ws):
+    """One view's selection -- rows (capacity, 5) and counts (frames,) int32 as ``yolo_select`` / ``classwise_select`` return them
+    with ``trim=False`` -- turned back by ``matrix`` (``augmentations.view_matrix`` of the view, or its ``tta_matrix_word``) into
+    slot ``view`` of pool (V, frames, P, 4) {class, x, y, z} / pool_counts (V, frames) (adyolo_hip.h ``adyolo_tta_collect``;
+    ``tta_buffers`` makes the buffers).  A frame with more than P rows keeps its first P and sets status bit 1.  No allocation,
+    no synchronisation."""
+    name = "tta_collect"
+    v, frames, p = _tta_pool(name, pool, pool_counts, status, ws, nb_classes)
+    _chk(rows)
+    if rows.dim() != 2 or rows.shape[1] != 5 or rows.device != pool.device:
+        raise _lib.AdyoloHipError("%s: rows %s are not (N, 5) on %s" % (name, tuple(rows.shape), pool.device))
+    if not counts.is_cuda or counts.dtype != torch.int32 or not counts.is_contiguous() or counts.device != pool.device \
+            or counts.numel() != frames:
+        raise _lib.AdyoloHipError("%s: counts must be a contiguous int32 tensor (%d,) on %s" % (name, frames, pool.device))
+    if not 0 <= int(view) < v:
+        raise _lib.AdyoloHipError("%s: view %r of %d" % (name, view, v))
+    word = int(matrix) if isinstance(matrix, int) else tta_matrix_word(matrix)
+    _c("adyolo_tta_collect", _p(rows) if rows.numel() else _p(pool), rows.shape[0], _p(counts), _p(ws), _p(pool),
+       _p(pool_counts), _p(status), frames, int(nb_classes), v, int(view), p, word, _stream())
+
+
+def tta_merge(pool, pool_counts, nb_classes, cos_t, min_views, status, ws, rows=None, counts=None, trim=True):
+    """The pool ``tta_collect`` filled for every view -> (rows (N, 5) [frame, class, x, y, z], counts (frames,) int32), both on
+    the device, in the layout of ``yolo_select`` (adyolo_hip.h ``adyolo_tta_merge``): ``postprocess.merge_view_rows`` bit for
+    bit.  cos_t: ``postprocess.tta_cos`` of the cluster distance.  rows / counts: the buffers to write, (>= frames * (V * P //
+    min_views), 5) float32 and (frames + 1,) int32 (``tta_buffers``); None: new ones.  trim as ``yolo_select``: True reads the
+    row total (one 4-byte copy, synchronises); False neither allocates (given buffers) nor synchronises."""
+    name = "tta_merge"
+    v, frames, p = _tta_pool(name, pool, pool_counts, status, ws, nb_classes)
+    if isinstance(min_views, bool) or int(min_views) != min_views or not 1 <= int(min_views) <= v:
+        raise _lib.AdyoloHipError("%s: min_views %r with %d views" % (name, min_views, v))
+    need = frames * (v * p // int(min_views))
+    if rows is None:
+        rows = _new(pool, max(1, need), 5)
+    if counts is None:
+        counts = torch.empty(frames + 1, dtype=torch.int32, device=pool.device)
+    _chk(rows)
+    if rows.dim() != 2 or rows.shape[1] != 5 or rows.shape[0] < need or rows.device != pool.device:
+        raise _lib.AdyoloHipError("%s: rows %s are not (>= %d, 5) on %s" % (name, tuple(rows.shape), need, pool.device))
+    if not counts.is_cuda or counts.dtype != torch.int32 or not counts.is_contiguous() or counts.device != pool.device \
+            or counts.numel() != frames + 1:
+        raise _lib.AdyoloHipError("%s: counts must be a contiguous int32 tensor (%d,) on %s" % (name, frames + 1, pool.device))
+    _c("adyolo_tta_merge", _p(pool), _p(pool_counts), _p(ws), _p(rows), rows.shape[0], _p(counts), _p(status), frames,
+       int(nb_classes), v, p, float(np.float32(cos_t)), int(min_views), _stream())
+    if not trim:
+        return rows, counts[:frames]
+    total = int(to_host(counts[frames:])[0])
+    return rows[:total], counts[:frames]
+
+
 SELD_STATUS = ((1, "more than 1024 predictions in one frame and class"),      # ADYOLO_SELD_* in adyolo_hip.h
                (2, "more than 8 reference events in one frame and class"),
                (4, "frame counts negative or summing past the rows given"),

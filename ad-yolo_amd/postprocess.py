@@ -193,6 +193,124 @@ def group_rows(rows, counts, n_clips=1):
     return outs
 
 
+# ---- Rotation test-time augmentation: the host definition of csrc/select.hip ``adyolo_tta_collect`` / ``adyolo_tta_merge``.
+TTA_ROWS_OVERFLOW, TTA_CAND_OVERFLOW, TTA_BAD_VECTOR, TTA_BAD_ROWS = 1, 2, 4, 8     # ADYOLO_TTA_* in adyolo_hip.h
+TTA_MAX_CANDIDATES = 1024                                                          # ADYOLO_SELECT_MAX_N
+
+
+def tta_cos(unify_thresh):
+    """The membership threshold of ``merge_view_rows``: float32(cos(radians(unify_thresh))), computed once on the host."""
+    return F32(math.cos(math.radians(float(unify_thresh))))
+
+
+def _norm3(v):
+    """sqrt((x*x + y*y) + z*z) of float32 rows (N, 3), every operation rounded."""
+    return np.sqrt((v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1]) + v[:, 2] * v[:, 2])
+
+
+def _merge_frame(cls, view, p, cos_t, min_views):
+    """The merged rows [[class, x, y, z], ...] of one frame and its status bits.  cls (N,) float32, view (N,) view index,
+    p (N, 3) float32 vectors already turned back, in candidate order."""
+    status = 0
+    with np.errstate(all="ignore"):
+        norm = _norm3(p)
+        good = np.isfinite(norm) & (norm > 0)
+        if not good.all():
+            status |= TTA_BAD_VECTOR
+        cls, view = cls[good], view[good]
+        u = (p[good] / norm[good, None]).astype(F32)
+    out = []
+    for c in np.unique(cls):
+        idx = np.flatnonzero(cls == c)
+        if len(idx) > TTA_MAX_CANDIDATES:
+            status |= TTA_CAND_OVERFLOW
+            continue
+        uc, vc = u[idx], view[idx]
+        near = ((uc[:, None, 0] * uc[None, :, 0] + uc[:, None, 1] * uc[None, :, 1]) + uc[:, None, 2] * uc[None, :, 2]) > cos_t
+        cluster = np.full(len(idx), -1)
+        n_clusters = 0
+        for seed in range(len(idx)):
+            if cluster[seed] >= 0:
+                continue
+            cluster[seed] = n_clusters
+            front = [seed]
+            while front:                                           # breadth first; the component does not depend on the order
+                reach = near[front].any(axis=0) & (cluster < 0)
+                cluster[reach] = n_clusters
+                front = np.flatnonzero(reach).tolist()
+            n_clusters += 1
+        for k in range(n_clusters):
+            memb = np.flatnonzero(cluster == k)
+            if len(set(vc[memb].tolist())) < min_views:
+                continue
+            s = np.cumsum(uc[memb], axis=0, dtype=F32)[-1:]        # a running float32 sum, in candidate order
+            with np.errstate(all="ignore"):
+                out.append([float(c)] + (s[0] / _norm3(s)[0]).astype(F32).tolist())
+    return out, status
+
+
+def merge_view_rows(per_view, views, unify_thresh, min_views=None, max_rows_per_frame=None):
+    """Rotation test-time augmentation, the host definition: the selections of the SAME clips under the combinations ``views``
+    (``augmentations.COMBINATIONS``; view 0 the unrotated clip) -> one selection and the status bits of the call.
+
+    per_view: one selection per view, either {frame: [[class, x, y, z], ...]} (what ``select`` returns; the result is such a
+    dict) or (rows (N, 5) [frame, class, x, y, z], counts (frames,)) arrays (what ``select_device_rows`` returns; the result is
+    such a pair, float32 rows and int32 counts).  Everything is float32, every operation rounded (no contraction):
+      * candidates of a (frame, class): views ascending, within a view the order its selection wrote them; a view gives at most
+        ``max_rows_per_frame`` rows per frame (None: all), its first ones (``TTA_ROWS_OVERFLOW``);
+      * a candidate's vector is p = M^T xyz, M = ``augmentations.view_matrix(view)`` (p_i = M[j][i] * xyz[j] for the one j with
+        M[j][i] != 0: exact); u = p / sqrt((px*px + py*py) + pz*pz); a zero or non-finite norm drops it (``TTA_BAD_VECTOR``);
+      * two candidates are neighbours when (ua.x*ub.x + ua.y*ub.y) + ua.z*ub.z > ``tta_cos(unify_thresh)``; the clusters are
+        the connected components, seeded at the lowest unassigned candidate and written in seed order (``nms_frame``'s
+        conn-merge discipline); more than ``TTA_MAX_CANDIDATES`` candidates leave the (frame, class) empty
+        (``TTA_CAND_OVERFLOW``);
+      * a cluster is kept when at least ``min_views`` (default a majority, (V + 1) // 2) DISTINCT views have a member in it;
+        its row is [class, s / |s|], s the members' u summed in candidate order, |s| by the expression above.
+    Frames ascend, classes ascend within a frame, clusters come in seed order within a class."""
+    from .augmentations import view_matrix
+    n_views = len(views)
+    if n_views < 1 or len(per_view) != n_views:
+        raise ValueError("merge_view_rows: %d selections for %d views" % (len(per_view), n_views))
+    min_views = (n_views + 1) // 2 if min_views is None else int(min_views)
+    if not 1 <= min_views <= n_views:
+        raise ValueError("merge_view_rows: min_views %d with %d views" % (min_views, n_views))
+    arrays = not isinstance(per_view[0], dict)
+    n_frames = None
+    if arrays:
+        n_frames = len(np.asarray(per_view[0][1]).reshape(-1))
+        per_view = [group_rows(np.asarray(r, dtype=F32).reshape(-1, 5)[:int(np.asarray(c).sum())], c)[0] for r, c in per_view]
+    turn = []                                                      # per view: the source axis and the sign of each component
+    for v in views:
+        m = view_matrix(v)
+        src = np.abs(m).argmax(axis=0)
+        turn.append((src, m[src, np.arange(3)].astype(F32)))
+    cos_t = tta_cos(unify_thresh)
+    status, out = 0, {}
+    for frame in sorted(set().union(*[set(d) for d in per_view])):
+        cls, view, vec = [], [], []
+        for k, d in enumerate(per_view):
+            rows = np.asarray(d.get(frame, []), dtype=F32).reshape(-1, 4)
+            if max_rows_per_frame is not None and len(rows) > max_rows_per_frame:
+                status |= TTA_ROWS_OVERFLOW
+                rows = rows[:max_rows_per_frame]
+            src, sign = turn[k]
+            cls.append(rows[:, 0])
+            view.append(np.full(len(rows), k))
+            vec.append(rows[:, 1:4][:, src] * sign[None, :])
+        merged, bits = _merge_frame(np.concatenate(cls), np.concatenate(view), np.concatenate(vec).astype(F32), cos_t, min_views)
+        status |= bits
+        if merged:
+            out[frame] = merged
+    if not arrays:
+        return out, status
+    counts = np.zeros(n_frames, dtype=np.int32)
+    rows = []
+    for frame in sorted(out):
+        counts[frame] = len(out[frame])
+        rows += [[float(frame)] + r for r in out[frame]]
+    return (np.asarray(rows, dtype=F32).reshape(-1, 5), counts), status
+
+
 class LabelPostProcessor:
     """``LabelPostProcessor(params).postprocess(output)`` for the adyolo head (decode + NMS) and the class-wise heads
     (``--loss seddoa | masked-seddoa | accdoa | adpit``); ``output`` (1, T', K) on the GPU."""

@@ -196,11 +196,66 @@ def _corpus_batch(corpus, idx, model, features, criterion, postprocessor, forwar
     return dec
 
 
-def _corpus_finish(corpus, acc):
-    """The one synchronisation of a pass: the loss accumulator {sum, count} and the corpus status word -> the mean loss."""
+def _corpus_view(corpus, idx, comb, model, features, postprocessor, forward):
+    """A further view of the batch ``_corpus_batch`` ran (rotation test-time augmentation): ``launch_view`` into the same graph
+    input -> forward -> the decoded batch.  No labels, no loss, no host synchronisation."""
+    audio_out = None
+    if forward is not None and hasattr(forward, "static_input"):
+        audio_out = forward.static_input((len(idx), corpus.n_hops[idx[0]], 4))
+    audio = corpus.launch_view(idx, comb, audio_out)
+    dec = None
+    if forward is not None:
+        output, dec = forward(audio)
+    else:
+        output = model(features(audio, channels_last8=True), channels_last8=True)
+    return dec if dec is not None else postprocessor.decode_device(output)
+
+
+class _ViewMerge:
+    """The device half of rotation test-time augmentation for the corpus loops: every view's selected rows collected
+    (``ops.tta_collect``), then merged (``ops.tta_merge``) into rows and counts in the selection's own layout.  tta: the list of
+    views (``augmentations.tta_views``; the other keys at their defaults) or the dict of ``augmentations.tta_options``.  The
+    buffers are made once per batch shape; ``status`` collects the ADYOLO_TTA_* bits of the pass."""
+
+    def __init__(self, tta, postprocessor, device):
+        from .augmentations import tta_options, view_matrix
+        from .postprocess import tta_cos
+        from . import ops
+        opt = tta if isinstance(tta, dict) else tta_options({}, views=tta, postprocessor=postprocessor)
+        self.views, self.min_views, self.rows_per_frame = list(opt["views"]), opt["min_views"], opt["max_rows_per_frame"]
+        self.cos_t = tta_cos(opt["unify_thresh"])
+        self.words = [ops.tta_matrix_word(view_matrix(v)) for v in self.views]
+        self.nb_classes = postprocessor.nb_classes
+        self.status = torch.zeros(1, dtype=torch.int32, device=device)
+        self._buffers = {}
+
+    def merged(self, postprocessor, decoded_views, n_clips, trim):
+        """decoded_views: an iterable of every view's decoded batch, in the order of ``views`` (each is selected before the next
+        is asked for: a recorded graph's output is reused) -> the merged (rows, counts)."""
+        from . import ops
+        buf = None
+        for k, dec in enumerate(decoded_views):
+            rows, counts = postprocessor.select_device_rows(dec, n_clips, trim=False)
+            if buf is None:
+                key = counts.numel()
+                buf = self._buffers.get(key)
+                if buf is None:
+                    buf = self._buffers[key] = ops.tta_buffers(self.status.device, len(self.views), key, self.nb_classes,
+                                                               self.rows_per_frame, self.min_views)
+            ops.tta_collect(rows, counts, k, self.words[k], self.nb_classes, buf["pool"], buf["pool_counts"], self.status,
+                            buf["ws"])
+        return ops.tta_merge(buf["pool"], buf["pool_counts"], self.nb_classes, self.cos_t, self.min_views, self.status, buf["ws"],
+                             buf["rows"], buf["counts"], trim=trim)
+
+
+def _corpus_finish(corpus, acc, tta_status=None):
+    """The one synchronisation of a pass: the loss accumulator {sum, count} and the corpus status word -> the mean loss.
+    tta_status: the status word of a pass with test-time augmentation, read in the same copy."""
     from . import ops
-    acc_h, status_h = ops.to_host_many(acc, corpus.status)
+    acc_h, status_h, *tta_h = ops.to_host_many(acc, corpus.status, *([] if tta_status is None else [tta_status]))
     corpus.check(int(status_h[0]))
+    if tta_h:
+        ops.tta_status_check(int(tta_h[0][0]))
     total, n = acc_h[0], int(acc_h[1])
     return float(total) / max(n, 1) if n else 0.0
 
@@ -214,7 +269,7 @@ def _write_rows(output_pth, names, rows, counts):
 
 
 def test_epoch_corpus(corpus, model, features, criterion, postprocessor, output_pth=None, batch_size=8, forward=None,
-                      device_scorer=None):
+                      device_scorer=None, tta=None):
     """``test_epoch_audio(device_select=True)`` from an HBM-resident split (``corpus.EvalDeviceCorpus``): the same batches,
     the same mean of per-clip losses (float32 adds in file order, clips without AD-YOLO rows left out), the same selected rows
     into ``device_scorer`` and, with ``output_pth``, the same CSV files -- but no WAV read, no CSV parse, no host label
@@ -222,7 +277,14 @@ def test_epoch_corpus(corpus, model, features, criterion, postprocessor, output_
     the eager forward + ``decode_device``) -> the per-clip loss on the device (``ops.adyolo_loss_per_clip``, or the class-wise
     loss per slice) -> ``select_device_rows`` -> ``device_scorer.add_rows``.  output_pth=None: nothing is written and the
     pass synchronises ONCE, at its end, to read the loss accumulator and the corpus status word together; with output_pth
-    every batch's rows are copied to the host (one synchronisation each).  Returns the mean loss."""
+    every batch's rows are copied to the host (one synchronisation each).  Returns the mean loss.
+
+    tta (rotation test-time augmentation): None, or the views of ``augmentations.tta_views`` (a list of combinations starting
+    with 0, or the dict of ``augmentations.tta_options`` with the other keys).  Every batch then also runs under each further
+    view -- ``corpus.launch_view`` into the same graph input, forward, decode, selection -- and the rows that go to the scorer
+    and the files are the views' rows turned back and merged on the device (``postprocess.merge_view_rows``; csrc/select.hip).
+    View 0 is the plain pass, so the loss is the plain pass's, the same float; the status word of the merge is read with the
+    loss (an overflow raises, naming the key to enlarge)."""
     from . import ops
     model.eval()
     if output_pth is not None:
@@ -230,25 +292,34 @@ def test_epoch_corpus(corpus, model, features, criterion, postprocessor, output_
     names = corpus.get_filelist()
     corpus.reset_status()
     acc = ops.loss_accumulator(corpus.device)
+    merge = _ViewMerge(tta, postprocessor, corpus.device) if tta is not None else None
     with torch.no_grad():
         for idx in corpus.batches(batch_size):
             clips = [names[i] for i in idx]
             dec = _corpus_batch(corpus, idx, model, features, criterion, postprocessor, forward, acc)
-            rows, counts = postprocessor.select_device_rows(dec, len(clips), trim=output_pth is not None)
+            if merge is None:
+                rows, counts = postprocessor.select_device_rows(dec, len(clips), trim=output_pth is not None)
+            else:
+                views = (dec if k == 0 else _corpus_view(corpus, idx, v, model, features, postprocessor, forward)
+                         for k, v in enumerate(merge.views))
+                rows, counts = merge.merged(postprocessor, views, len(clips), trim=output_pth is not None)
             if device_scorer is not None:
                 device_scorer.add_rows(rows, counts, clips)
             if output_pth is not None:
                 _write_rows(output_pth, clips, rows, counts)
-    return _corpus_finish(corpus, acc)
+    return _corpus_finish(corpus, acc, None if merge is None else merge.status)
 
 
 def sweep_conf_thresh_corpus(corpus, model, features, criterion, postprocessor, scorer, thresholds=None, output_pth=None,
-                             batch_size=8, forward=None):
+                             batch_size=8, forward=None, tta=None):
     """``sweep_conf_thresh(device_select=True, device_score=True)`` from an HBM-resident split: ONE forward pass per batch,
     every batch's decode kept on the device, then per threshold the selections and the device scores (``scorer``: a
     ``seld_metrics.DeviceSELDScorer``); the chosen threshold is left set on the post-processor.  With ``output_pth`` the last
     threshold's CSV files are written, as the host sweep leaves them.  Clips without AD-YOLO rows are left out of the mean
-    loss (the host sweep cannot take them at all).  -> (new_thresh, [[ER, F, LE, LR, SELD] per threshold], mean loss)"""
+    loss (the host sweep cannot take them at all).  -> (new_thresh, [[ER, F, LE, LR, SELD] per threshold], mean loss)
+
+    tta: as ``test_epoch_corpus``.  Every VIEW's decode of every batch is kept on the device, and each threshold selects,
+    collects and merges them again; the merge's status word is read once, after the last threshold."""
     import numpy as np
     from . import ops
     from .seld_metrics import DeviceSELDScorer
@@ -261,10 +332,15 @@ def sweep_conf_thresh_corpus(corpus, model, features, criterion, postprocessor, 
     corpus.reset_status()
     acc = ops.loss_accumulator(corpus.device)
     decoded = []
+    merge = _ViewMerge(tta, postprocessor, corpus.device) if tta is not None else None
     with torch.no_grad():
         for idx in corpus.batches(batch_size):
             dec = _corpus_batch(corpus, idx, model, features, criterion, postprocessor, forward, acc)
-            decoded.append(([names[i] for i in idx], dec.clone() if forward is not None else dec))   # (a graph's output is reused)
+            dec = dec.clone() if forward is not None else dec                                         # (a graph's output is reused)
+            if merge is not None:
+                dec = [dec] + [_corpus_view(corpus, idx, v, model, features, postprocessor, forward).clone()
+                               for v in merge.views[1:]]
+            decoded.append(([names[i] for i in idx], dec))
     loss = _corpus_finish(corpus, acc)
     new_thresh, best, table = postprocessor.get_conf_thresh(), 9999.0, []
     for k, th in enumerate(thresholds):
@@ -274,7 +350,10 @@ def sweep_conf_thresh_corpus(corpus, model, features, criterion, postprocessor, 
             delete_and_create_folder(output_pth)
         scorer.reset()
         for clips, dec in decoded:
-            rows, counts = postprocessor.select_device_rows(dec, len(clips), trim=write)
+            if merge is None:
+                rows, counts = postprocessor.select_device_rows(dec, len(clips), trim=write)
+            else:
+                rows, counts = merge.merged(postprocessor, dec, len(clips), trim=write)
             scorer.add_rows(rows, counts, clips)
             if write:
                 _write_rows(output_pth, clips, rows, counts)
@@ -283,6 +362,8 @@ def sweep_conf_thresh_corpus(corpus, model, features, criterion, postprocessor, 
         if seld < best:
             new_thresh, best = th, seld
     postprocessor.set_conf_thresh(new_thresh)
+    if merge is not None:
+        ops.tta_status_check(int(ops.to_host(merge.status)[0]))
     return new_thresh, table, loss
 
 

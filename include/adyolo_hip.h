@@ -552,6 +552,42 @@ long adyolo_classwise_select_workspace_words(long n_frames, int C, int mode);
 int  adyolo_classwise_select(const float *dec, float *ws, float *rows, int *frame_counts, long n_frames, int C, int mode,
                              float conf_thresh, float unify_thresh, void *stream);
 
+/* Rotation test-time augmentation (csrc/select.hip), opt-in: what postprocess.merge_view_rows does on the host, bit for bit.
+ * The same clips are selected under n_views symmetries of the array (augmentations.COMBINATIONS); adyolo_tta_collect parks
+ * each view's rows, turned back into the recording's frame, and adyolo_tta_merge keeps what enough views agree on.
+ *   pool         [n_views][n_frames][P][4] float32 {class, x, y, z}, 16-byte aligned; pool_counts [n_views][n_frames] int32
+ *   ws           adyolo_tta_merge_workspace_words(n_frames, C) words: ONE workspace for the collects and the merge of a batch
+ *   status       one int32 the kernels OR ADYOLO_TTA_* bits into
+ * adyolo_tta_collect: one view's selection as adyolo_yolo_select / adyolo_classwise_select leave it -- rows (capacity n_rows,
+ *   [frame, class, x, y, z]) and frame_counts [n_frames] (the total behind them is not read) -- into slot `view` of the pool.
+ *   matrix: the view's signed permutation as a word, so that the call can be captured: component i of the turned-back vector
+ *   is sign_i * xyz[src_i], src_i in bits [4 i, 4 i + 2), bit 4 i + 2 set for a negative sign (i.e. p = M^T xyz for the M that
+ *   takes a direction to where the view puts it).  A frame with more than P rows keeps its first P (ADYOLO_TTA_ROWS_OVERFLOW);
+ *   counts that are negative or run past n_rows, or a class outside [0, C): ADYOLO_TTA_BAD_ROWS.  The rows' positions come
+ *   from a scan of the counts.
+ * adyolo_tta_merge: per (frame, class) the candidates are the pool's rows of that class, views ascending and within a view in
+ *   pool order; u = p / sqrt((px*px + py*py) + pz*pz), a candidate whose norm is zero or not finite is dropped
+ *   (ADYOLO_TTA_BAD_VECTOR).  Two candidates are neighbours when (ua.x*ub.x + ua.y*ub.y) + ua.z*ub.z > cos_t; the clusters are
+ *   the connected components, seeded at the lowest unassigned candidate, in seed order.  A cluster with members of at least
+ *   min_views DISTINCT views gives the row [frame, class, s / |s|], s the sum of its members' u in candidate order, |s| by
+ *   the expression above.  All float32, correctly rounded, no contraction.  More than ADYOLO_SELECT_MAX_N candidates in one
+ *   (frame, class): that slot stays empty (ADYOLO_TTA_CAND_OVERFLOW).
+ *   rows [capacity][5] and frame_counts [n_frames + 1] (the total last): the layout adyolo_yolo_select writes; capacity >=
+ *   n_frames * (n_views * P / min_views), which no result exceeds.  Positions come from an exclusive scan, never from atomics;
+ *   no host synchronisation.
+ * EINVAL: null or misaligned pointer, n_views outside [1, ADYOLO_TTA_MAX_VIEWS], P outside [1, ADYOLO_SELECT_MAX_N], view or
+ * min_views out of range, a matrix word that is no signed permutation, too small a capacity; ENOSUP: 32-bit counts overflow. */
+#define ADYOLO_TTA_MAX_VIEWS     16
+#define ADYOLO_TTA_ROWS_OVERFLOW 1    /* more than P rows of one view in one frame: the first P were kept */
+#define ADYOLO_TTA_CAND_OVERFLOW 2    /* more than ADYOLO_SELECT_MAX_N candidates in one (frame, class): left empty */
+#define ADYOLO_TTA_BAD_VECTOR    4    /* a row whose vector has a zero or non-finite norm: dropped */
+#define ADYOLO_TTA_BAD_ROWS      8    /* frame counts negative or past the rows given, or a class outside [0, C) */
+long adyolo_tta_merge_workspace_words(long n_frames, int C);
+int  adyolo_tta_collect(const float *rows, long n_rows, const int *frame_counts, float *ws, float *pool, int *pool_counts,
+                        int *status, long n_frames, int C, int n_views, int view, int P, unsigned matrix, void *stream);
+int  adyolo_tta_merge(const float *pool, const int *pool_counts, float *ws, float *rows, long capacity, int *frame_counts,
+                      int *status, long n_frames, int C, int n_views, int P, float cos_t, int min_views, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Input pipeline around K1.
  *   adyolo_pcm16_to_f32: staged WAV samples int16 -> float, x / 32768 + 1e-8 (src/datasets.py:105, src/preprocess.py:104)

@@ -97,6 +97,8 @@ SIGNATURES = {
     "adyolo_yolo_select": (I, [P] * 4 + [L, I, I, F, F, F, F, I, P]),
     "adyolo_seld_score_workspace_words": (L, [L, I, I, I]),
     "adyolo_seld_score": (I, [P, I, L, P, L, I] + [P] * 5 + [I, I, I, I, ctypes.c_double, P, P, P, P]),
+    "adyolo_seld_score_runs_workspace_words": (L, [L, L, I, I]),
+    "adyolo_seld_score_runs": (I, [P, I, L, P, L, P, L] + [P] * 4 + [I, I, I, I, ctypes.c_double, P, P, P, P]),
     "adyolo_act_fwd": (I, [P, P, L, I, I, P]),
     "adyolo_act_bwd": (I, [P, P, P, L, I, I, P]),
     "adyolo_seddoa_loss": (I, [P] * 5 + [L, I, I, I, F, F, P]),

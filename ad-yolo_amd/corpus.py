@@ -41,9 +41,14 @@ With ``load_infer_split(..., resample=True)`` (``infer_split_from_arrays(..., ra
 rate and in int16, 24-bit or float32: those that are not int16 at ``data_config.sr`` stay in their native form on the host, and
 the upload converts them on the device (``ops.resample_pcm``, resample.py) into the places the layout left for them.
 
+Labelled evaluation of recordings of any length joins the two: ``EvalWindowCorpus`` takes the split of ``load_eval_split`` and
+cuts it into the windows of ``InferDeviceCorpus`` (``plan_windows``, ``_WindowCorpus``), with one label item row per window
+(``window_items``), for ``test.test_epoch_windows``; the device scorer then scores each pass's stitched run in segments
+(``seld_metrics.run_segments``).
+
 One structure under all of it: every loader returns a ``HostCorpus``, whose constructor owns the stream layout (16-frame
 alignment) and gives every field a value, with ``kind`` saying which split it is; the loaders share one WAV reader, one CSV
-reader and one verify pick (``_read_wav``, ``_csv_rows``, ``_verify_picks``); the four device corpora share ``_CorpusBase``.
+reader and one verify pick (``_read_wav``, ``_csv_rows``, ``_verify_picks``); the five device corpora share ``_CorpusBase``.
 """
 import copy
 import os
@@ -342,7 +347,7 @@ def xyz_unrotated(az, el):
 
 
 class _CorpusBase:
-    """What the four device corpora share.  All of them: the adopted ``HostCorpus`` in HBM with the identity fields and methods
+    """What the five device corpora share (the two windowed ones through ``_WindowCorpus``).  All of them: the adopted ``HostCorpus`` in HBM with the identity fields and methods
     of ``FoaDataset`` that the epoch loops read (``_adopt``), the status word and ``check``, and the small helpers of a
     ``launch`` (``_out``, ``_round_cap``, ``_yolo_tables``).  The two training corpora only (``DeviceCorpus``,
     ``ClasswiseDeviceCorpus``): the augmentation configuration and ``FoaDataset``'s sampling of files (``_train_setup``), the host
@@ -1003,7 +1008,91 @@ def load_infer_split(params, rank=None, world=None, verify="sample", files=None,
     return hc
 
 
-class InferDeviceCorpus(_CorpusBase):
+def plan_windows(label_frames, lengths, rec_start, hop, n_samples, window_frames, margin_frames, batch_size):
+    """The window table of a split cut into windows of one shape (pure NumPy; ``InferDeviceCorpus`` and ``EvalWindowCorpus``):
+    every recording's ``window_plan`` (no window for a recording without a label frame), all windows in file order, cut into
+    passes of ``batch_size`` windows, the last pass filled up with empty windows -> dict of
+      table        int64 (passes * batch_size, ``ops.WINDOW_WORDS``): {stream offset, valid samples, src_lo, destination frame on
+                   the axis of all recordings laid end to end, n, recording (-1: an empty window), 0, 0}
+      starts       int64 (n_windows,): each window's first label frame on its own recording's axis
+      frame_start  int64 (R + 1,): the first frame of each recording on the common axis
+      n_windows, n_passes, pass_base (the first frame of each pass's run on the common axis), pass_frames (its length)."""
+    label_frames = [int(v) for v in label_frames]
+    frame_start = np.concatenate([[0], np.cumsum(label_frames)]).astype(np.int64)
+    rows, starts = [], []
+    for r, frames in enumerate(label_frames):
+        if frames == 0:
+            continue
+        for start, src_lo, dst_lo, cnt in window_plan(frames, window_frames, margin_frames):
+            off = int(rec_start[r]) + start * hop
+            rows.append((off, min(n_samples, int(lengths[r]) - start * hop), src_lo, int(frame_start[r]) + dst_lo, cnt, r, 0, 0))
+            starts.append(start)
+    n_windows = len(rows)
+    n_passes = (n_windows + batch_size - 1) // batch_size
+    total = int(frame_start[-1])
+    rows += [(0, 0, 0, total, 0, -1, 0, 0)] * (n_passes * batch_size - n_windows)                     # empty windows
+    table = np.asarray(rows, dtype=np.int64).reshape(-1, ops.WINDOW_WORDS)
+    per = table.reshape(n_passes, batch_size, ops.WINDOW_WORDS)
+    return {"table": table, "starts": np.asarray(starts, dtype=np.int64), "frame_start": frame_start, "n_windows": n_windows,
+            "n_passes": n_passes, "pass_base": [int(v) for v in per[:, 0, 3].tolist()],
+            "pass_frames": [int(v) for v in per[:, :, 4].sum(1).tolist()]}
+
+
+class _WindowCorpus(_CorpusBase):
+    """What the two windowed corpora share: the window and margin arguments (``_window_setup``, before anything is uploaded),
+    the window table (``plan_windows``) and its upload, ``pass_table`` and the gather of a pass."""
+
+    def _window_setup(self, hc, params, window_s, margin_s, batch_size):
+        """window_s / margin_s / batch_size checked and kept as samples and label frames -> the sample rate."""
+        from .features import HOP
+        who = type(self).__name__
+        dc = params["data_config"]
+        sr = int(dc.get("sr", 24000))
+        hop = int(hc.hop_label)
+        window_s = dc["chunk_window_s"] if window_s is None else window_s
+        margin_s = 2.0 if margin_s is None else margin_s
+        n, m = int(round(sr * float(window_s))), int(round(sr * float(margin_s)))
+        if n <= 0 or m < 0 or abs(n - sr * float(window_s)) > 1e-6 or abs(m - sr * float(margin_s)) > 1e-6 or n % hop or m % hop:
+            raise ValueError("%s: window %r s / margin %r s are not whole multiples of the label hop (%d samples at "
+                             "%d Hz)" % (who, window_s, margin_s, hop, sr))
+        if n % HOP:
+            raise ValueError("%s: a window of %d samples is not a whole number of feature hops (%d)" % (who, n, HOP))
+        self.window_frames, self.margin_frames = n // hop, m // hop
+        if self.window_frames <= 2 * self.margin_frames:
+            raise ValueError("%s: a window of %r s keeps nothing between two margins of %r s" % (who, window_s, margin_s))
+        self.batch_size = int(batch_size)
+        if not 1 <= self.batch_size < 65536:
+            raise ValueError("%s: batch_size %r" % (who, batch_size))
+        self.n_samples = n
+        return sr
+
+    def _window_tables(self, hc):
+        """The split's window plan on the host (``plan_windows``)."""
+        hop = int(hc.hop_label)
+        self.lengths = [int(v) for v in hc.lengths.tolist()]
+        self.label_frames = [v // hop for v in self.lengths]
+        plan = plan_windows(self.label_frames, self.lengths, hc.rec_start, hop, self.n_samples, self.window_frames,
+                            self.margin_frames, self.batch_size)
+        self.frame_start, self.table_host, self.window_starts = plan["frame_start"], plan["table"], plan["starts"]
+        self.n_windows, self.n_passes = plan["n_windows"], plan["n_passes"]
+        self.pass_base, self.pass_frames = plan["pass_base"], plan["pass_frames"]
+
+    def _upload_table(self):
+        table = self.table_host
+        self.table = torch.from_numpy(table if len(table) else np.zeros((1, ops.WINDOW_WORDS), dtype=np.int64)).to(self.device)
+
+    def pass_table(self, p):
+        """The window rows of pass ``p``: a view of the table in HBM."""
+        if not 0 <= p < self.n_passes:
+            raise ValueError("%s: pass %r of %d" % (type(self).__name__, p, self.n_passes))
+        return self.table[p * self.batch_size:(p + 1) * self.batch_size]
+
+    def _gather_pass(self, p, audio_out):
+        audio = self._out(audio_out, (self.batch_size, self.n_samples, 4))
+        return ops.corpus_gather_windows(self.pcm, self.pass_table(p), audio, self.status)
+
+
+class InferDeviceCorpus(_WindowCorpus):
     """A ``load_infer_split`` / ``infer_split_from_arrays`` split in HBM, cut into windows of ONE shape for
     ``test.infer_epoch_corpus``: every recording's ``window_plan`` (F = length // hop_label label frames; F = 0: no window), all
     windows in file order, cut into passes of ``batch_size`` windows, the last pass filled up with empty windows.  The window
@@ -1020,50 +1109,14 @@ class InferDeviceCorpus(_CorpusBase):
     upload (``_convert_native``); everything after the upload is the same."""
 
     def __init__(self, host_split, params, device="cuda:0", window_s=None, margin_s=None, batch_size=8):
-        from .features import HOP
         hc = host_split
         if hc.kind == HostCorpus.CHUNKED:
             raise ValueError("InferDeviceCorpus: the split of load_infer_split is needed (got the chunked training split)")
-        dc = params["data_config"]
-        sr = int(dc.get("sr", 24000))
-        hop = int(hc.hop_label)
-        window_s = dc["chunk_window_s"] if window_s is None else window_s
-        margin_s = 2.0 if margin_s is None else margin_s
-        n, m = int(round(sr * float(window_s))), int(round(sr * float(margin_s)))
-        if n <= 0 or m < 0 or abs(n - sr * float(window_s)) > 1e-6 or abs(m - sr * float(margin_s)) > 1e-6 or n % hop or m % hop:
-            raise ValueError("InferDeviceCorpus: window %r s / margin %r s are not whole multiples of the label hop (%d samples at "
-                             "%d Hz)" % (window_s, margin_s, hop, sr))
-        if n % HOP:
-            raise ValueError("InferDeviceCorpus: a window of %d samples is not a whole number of feature hops (%d)" % (n, HOP))
-        self.window_frames, self.margin_frames = n // hop, m // hop
-        if self.window_frames <= 2 * self.margin_frames:
-            raise ValueError("InferDeviceCorpus: a window of %r s keeps nothing between two margins of %r s" % (window_s, margin_s))
-        self.batch_size = int(batch_size)
-        if not 1 <= self.batch_size < 65536:
-            raise ValueError("InferDeviceCorpus: batch_size %r" % (batch_size,))
+        sr = self._window_setup(hc, params, window_s, margin_s, batch_size)
         self._adopt(hc, device, hc.rank, hc.world, is_valid=True, is_infer=True)
-        self.n_samples = n
-        self.lengths = [int(v) for v in hc.lengths.tolist()]
-        self.label_frames = [v // hop for v in self.lengths]
-        self.frame_start = np.concatenate([[0], np.cumsum(self.label_frames)]).astype(np.int64)
-        rows = []
-        for r, frames in enumerate(self.label_frames):
-            if frames == 0:
-                continue
-            for start, src_lo, dst_lo, cnt in window_plan(frames, self.window_frames, self.margin_frames):
-                off = int(hc.rec_start[r]) + start * hop
-                rows.append((off, min(n, self.lengths[r] - start * hop), src_lo, int(self.frame_start[r]) + dst_lo, cnt, r, 0, 0))
-        self.n_windows = len(rows)
-        self.n_passes = (self.n_windows + self.batch_size - 1) // self.batch_size
-        total = int(self.frame_start[-1])
-        rows += [(0, 0, 0, total, 0, -1, 0, 0)] * (self.n_passes * self.batch_size - self.n_windows)      # empty windows
-        table = np.asarray(rows, dtype=np.int64).reshape(-1, ops.WINDOW_WORDS)
-        self.table_host = table
-        per = table.reshape(self.n_passes, self.batch_size, ops.WINDOW_WORDS)
-        self.pass_base = [int(v) for v in per[:, 0, 3].tolist()]
-        self.pass_frames = [int(v) for v in per[:, :, 4].sum(1).tolist()]
+        self._window_tables(hc)
         self._convert_native(hc, sr)
-        self.table = torch.from_numpy(table if len(rows) else np.zeros((1, ops.WINDOW_WORDS), dtype=np.int64)).to(self.device)
+        self._upload_table()
 
     def _convert_native(self, hc, sr):
         """The recordings a ``resample=True`` / ``rates=`` split kept in their native rate or format: per (rate, kind) group the
@@ -1106,14 +1159,122 @@ class InferDeviceCorpus(_CorpusBase):
     def nbytes(self):
         return int(self.pcm.numel() * 2 + self.table.numel() * 8)
 
-    def pass_table(self, p):
-        """The window rows of pass ``p``: a view of the table in HBM."""
-        if not 0 <= p < self.n_passes:
-            raise ValueError("InferDeviceCorpus: pass %r of %d" % (p, self.n_passes))
-        return self.table[p * self.batch_size:(p + 1) * self.batch_size]
-
     def launch(self, p, audio_out=None):
         """Pass ``p`` -> audio (batch_size, n_samples, 4) f32 on the device; no host data, no host synchronisation.  audio_out:
         write into this buffer (a recorded forward graph's input)."""
-        audio = self._out(audio_out, (self.batch_size, self.n_samples, 4))
-        return ops.corpus_gather_windows(self.pcm, self.pass_table(p), audio, self.status)
+        return self._gather_pass(p, audio_out)
+
+
+# ------------------------------------------------------------------------------------------- labelled windowed evaluation
+def window_items(plan, label_frames, window_frames, ev_start, event_frames):
+    """The label item row of every window of ``plan`` (``plan_windows``; pure NumPy) -> int64 (passes * batch_size,
+    ``ops.CORPUS_ITEM_WORDS``): {stream offset, the window's first label frame on its recording's axis, first event, events, -1
+    (no rotation), recording, 0, 0}.  The events of a window are the recording's frame-sorted events (``event_frames``: the
+    frame column of the split's event table, ``ev_start`` its recordings) whose frame lies in [start, min(start + window_frames,
+    the recording's label frames)), found by binary search; an empty window's row holds no events."""
+    table = plan["table"]
+    items = np.zeros((len(table), ops.CORPUS_ITEM_WORDS), dtype=np.int64)
+    items[:, 4] = -1
+    event_frames = np.asarray(event_frames, dtype=np.float64).reshape(-1)
+    for w in range(plan["n_windows"]):
+        r, start = int(table[w, 5]), int(plan["starts"][w])
+        end = min(start + int(window_frames), int(label_frames[r]))
+        e0, e1 = int(ev_start[r]), int(ev_start[r + 1])
+        lo, hi = (int(v) for v in np.searchsorted(event_frames[e0:e1], [start, end], "left"))
+        items[w] = (table[w, 0], start, e0 + lo, hi - lo, -1, r, 0, 0)
+    return items
+
+
+class EvalWindowCorpus(_WindowCorpus):
+    """A ``load_eval_split`` split in HBM, cut into windows of ONE shape like ``InferDeviceCorpus``, with labels: labelled
+    evaluation of recordings of any length for ``test.test_epoch_windows`` / ``test.sweep_conf_thresh_windows``.  The window
+    table, one label item row per window and (per scorer, ``segments``) the scorer's segment tables are built once and uploaded
+    once; a pass uploads nothing.
+
+        corpus = EvalWindowCorpus(load_eval_split(params, "test"), params, "cuda:0", window_s=20, margin_s=2.0, batch_size=8)
+        audio, target, row_start = corpus.launch(p)         # as EvalDeviceCorpus.launch, for the windows of pass p
+
+    window_s / margin_s: ``InferDeviceCorpus``'s rules, and both must be whole multiples of the scorer's block (``fpb = int(sr
+    / int(sr * label_hop_len_s))`` label frames, 10 at the usual rates; ``ValueError`` otherwise): kept ranges start at Wf - Mf
+    and advance by Wf - 2 Mf, the tail-aligned last window starts where its predecessor stopped, so every pass boundary inside
+    a recording falls on a block boundary (``adyolo_seld_score_runs``).  A recording without a label frame has no window; its
+    zero-frame segment rides in the pass of the next recording (``seld_metrics.run_segments``).  A split without any window:
+    ``ValueError``.  Rotation test-time augmentation and ``resample=True`` splits are not supported here."""
+
+    def __init__(self, host_split, params, device="cuda:0", window_s=None, margin_s=None, batch_size=8, cap_per_window=None):
+        hc = host_split
+        if hc.kind != HostCorpus.EVAL:
+            raise ValueError("EvalWindowCorpus: the split of load_eval_split is needed (got the %s split)" % hc.kind)
+        self.loss_nm = params["args"]["loss"]
+        if self.loss_nm != "adyolo" and self.loss_nm not in CLASSWISE_LABELS:
+            raise NotImplementedError("EvalWindowCorpus: loss %s" % self.loss_nm)
+        self.nb_classes = int(params["data_config"]["nb_classes"])
+        dc = params["data_config"]
+        sr = self._window_setup(hc, params, window_s, margin_s, batch_size)
+        self.frames_per_block = fpb = int(sr / int(sr * dc.get("label_hop_len_s", 0.1)))     # DeviceSELDScorer's block
+        if self.window_frames % fpb or self.margin_frames % fpb:
+            raise ValueError("EvalWindowCorpus: a window of %d label frames with a margin of %d: both must be whole multiples of "
+                             "the scorer's block (%d frames)" % (self.window_frames, self.margin_frames, fpb))
+        if not any(int(v) // int(hc.hop_label) for v in hc.lengths.tolist()):
+            raise ValueError("EvalWindowCorpus: no recording of the split holds a label frame: there is no window to run")
+        self._adopt(hc, device, hc.rank, hc.world, is_valid=True)
+        self._window_tables(hc)
+        plan = {"table": self.table_host, "starts": self.window_starts, "n_windows": self.n_windows}
+        items = window_items(plan, self.label_frames, self.window_frames, hc.ev_start, hc.events[:, 0])
+        self.items_host = items
+        self.max_events = int(items[:, 3].max())                     # the largest event count of a WINDOW
+        self.pass_bounds = self.pass_base + [int(self.frame_start[-1])]
+        self._upload_table()
+        self.items = torch.from_numpy(items).to(self.device)
+        self._segments = {}
+        if self.loss_nm == "adyolo":
+            self._yolo_tables(params)
+            self.cap_per_window = int(cap_per_window) if cap_per_window is not None else max(1, self.max_events * self.cells)
+            self.xyz = None
+        else:
+            full = np.zeros((max(1, hc.events.shape[0]), ops.CORPUS_XYZ_SLOTS, 3), dtype=np.float32)
+            if hc.events.shape[0]:
+                full[:, 0] = xyz_unrotated(hc.events[:, 3], hc.events[:, 4])     # only the unrotated slot is read
+            self.xyz = torch.from_numpy(full).to(self.device)
+
+    def nbytes(self):
+        return super().nbytes() + int((self.table.numel() + self.items.numel()) * 8) + \
+            (int(self.xyz.numel() * 4) if self.xyz is not None else 0)
+
+    def cap(self):
+        """Target rows of a pass (AD-YOLO)."""
+        return self._round_cap(self.batch_size * self.cap_per_window)
+
+    def windows_in_pass(self, p):
+        """The windows of pass ``p`` that belong to a recording (the others, at the end of the last pass, are empty)."""
+        return max(0, min(self.batch_size, self.n_windows - p * self.batch_size))
+
+    def segments(self, scorer):
+        """``scorer.segment_tables`` for this corpus's passes: built and uploaded on the first call, cached per scorer."""
+        hit = self._segments.get(id(scorer))
+        if hit is None or hit[0] is not scorer:
+            hit = self._segments[id(scorer)] = (scorer, scorer.segment_tables(self.get_filelist(), self.label_frames,
+                                                                              self.pass_bounds))
+        return hit[1]
+
+    def launch(self, p, audio_out=None):
+        """Pass ``p`` -> (audio (batch_size, n_samples, 4) f32, target, row_start) on the device, as ``EvalDeviceCorpus.launch``
+        with a window for a clip: the AD-YOLO rows (cap(), 7) and row_start (batch_size + 1,) int32, or the dense class-wise
+        target (batch_size, window_frames, ...) and None; an empty window has no rows / an all-zero target.  No host data, no
+        host synchronisation.  audio_out: write the audio into this buffer (a recorded forward graph's input)."""
+        b, frames = self.batch_size, self.window_frames
+        audio = self._gather_pass(p, audio_out)
+        items = self.items[p * b:(p + 1) * b]
+        if self.loss_nm != "adyolo":
+            target = torch.empty(ops.corpus_classwise_shape(self.loss_nm, b, frames, self.nb_classes), dtype=torch.float32,
+                                 device=self.device)
+            ops.corpus_classwise_labels(self.events, items, self.xyz, self.max_events, frames, self.nb_classes, self.loss_nm,
+                                        target, self.status)
+            return audio, target, None
+        me = self.max_events
+        target = torch.empty((self.cap(), 7), dtype=torch.float32, device=self.device)
+        ws = torch.zeros(b * max(me, 1) + 1, dtype=torch.int32, device=self.device)
+        ops.corpus_yolo_labels(self.events, items, me, frames, self.bounds, self.grid, self.rot, ws, target,
+                               ws[b * max(me, 1):], self.status)
+        row_start = ws[::max(me, 1)].contiguous()
+        return audio, target, row_start

@@ -12,6 +12,10 @@
 //   3. seld_clip_kernel, one workgroup per clip: the records summed in block order; S / D / I from each block's loc_fp / loc_fn.
 //   4. seld_file_kernel (one workgroup): the clip sums added to the per-file accumulators in clip order, unless the status
 //      word is set.  No float atomics anywhere: the result is the same from run to run.
+// adyolo_seld_score_runs scores the segments of one stitched run of frames (windowed evaluation) instead of whole clips: the
+// scan, then seld_run_block_kernel, one wave per (segment, block, class) -- the same body as seld_block_kernel under the
+// segment's frame mapping (seld_block_body, SeldSpan) -- then seld_run_sum_kernel (one workgroup): the segments in table order,
+// each block record added to the file's accumulators one at a time, which leaves the bits of a whole-clip call.
 // Distances are float64 in the host's order (cartesian_to_polar, then * pi / 180, then _great_circle_deg) without
 // contraction; only OCML's atan2 / sin / cos / acos may differ from the host's libm by an ulp.
 #include "common.hpp"
@@ -66,13 +70,23 @@ __device__ int seld_count_class(const T *rows, long off, int cnt, int c, int lan
     return n;
 }
 
-// grid: n_clips * max_blocks * C workgroups of one wave
+// The frames of one file that a launch holds predictions for: file frame fr, lo <= fr < hi, is frame first + (fr - lo) of
+// counts / offs.  The clip form: lo = 0, hi = t_clip, first = clip * t_clip; a segment of a run: lo = f0, hi = f0 + n, first = r0.
+struct SeldSpan {
+    long first;
+    int lo, hi;
+    __device__ bool holds(int fr) const { return fr >= lo && fr < hi; }
+    __device__ long at(int fr) const { return first + (fr - lo); }
+};
+
+// One wave: block b, class c of the file whose table frames start at base, the predictions of its frames in span -> the record
+// rec (zeroed by the caller).  Both kernels below are this body under their own frame mapping.
 template <typename T>
-__global__ __launch_bounds__(SELD_WAVE) void seld_block_kernel(
-    const T *__restrict__ rows, const int *__restrict__ counts, const int *__restrict__ offs, const int *__restrict__ file_ids,
-    const int *__restrict__ file_info, const int *__restrict__ ref_off, const double *__restrict__ ref_ev,
-    const int *__restrict__ keep, int n_files, int t_clip, int C, int fpb, int max_blocks, double doa_thresh,
-    double *__restrict__ rec_out, int *__restrict__ status) {
+__device__ __forceinline__ void seld_block_body(const T *__restrict__ rows, const int *__restrict__ counts,
+                                                const int *__restrict__ offs, const int *__restrict__ ref_off,
+                                                const double *__restrict__ ref_ev, const int *__restrict__ keep, long base,
+                                                SeldSpan span, int b, int c, int C, int fpb, double doa_thresh,
+                                                double *__restrict__ rec, int *__restrict__ status) {
 #pragma clang fp contract(off)
     __shared__ double p_az[ADYOLO_SELECT_MAX_N], p_s[ADYOLO_SELECT_MAX_N], p_c[ADYOLO_SELECT_MAX_N];
     __shared__ double l_v[ADYOLO_SELECT_MAX_N], l_spc[ADYOLO_SELECT_MAX_N];
@@ -83,22 +97,7 @@ __global__ __launch_bounds__(SELD_WAVE) void seld_block_kernel(
     __shared__ double t_sum[ADYOLO_SELD_MAX_REF];
     __shared__ int t_cnt[ADYOLO_SELD_MAX_REF], t_order[ADYOLO_SELD_MAX_REF];
     __shared__ int f_nref[64], f_npred[64];
-
     const int lane = threadIdx.x;
-    const long g = blockIdx.x;
-    const int c = (int)(g % C);
-    const int b = (int)((g / C) % max_blocks);
-    const long clip = g / ((long)C * max_blocks);
-    double *rec = rec_out + g * SELD_REC;
-    if (lane < SELD_REC) rec[lane] = 0.0;
-    if (*status != 0) return;                                   // bad rows, or an error of an earlier call: nothing is added
-    const int fid = file_ids[clip];
-    if (fid < 0 || fid >= n_files) {
-        if (lane == 0 && b == 0 && c == 0) atomicOr(status, ADYOLO_SELD_BAD_FILE);
-        return;
-    }
-    const long base = file_info[2 * fid];
-    if (b >= file_info[2 * fid + 1]) return;
 
     // per-frame event counts of class c on both sides
     int n_ref = 0, n_pred = 0;
@@ -107,8 +106,8 @@ __global__ __launch_bounds__(SELD_WAVE) void seld_block_kernel(
         const long cell = (base + fr) * C + c;
         const int nr = ref_off[cell + 1] - ref_off[cell];
         int np = 0;
-        if (fr < t_clip && (keep == nullptr || keep[base + fr])) {
-            const long f = clip * t_clip + fr;
+        if (span.holds(fr) && (keep == nullptr || keep[base + fr])) {
+            const long f = span.at(fr);
             np = seld_count_class(rows, (long)offs[f], counts[f], c, lane);
         }
         if (lane == 0) {
@@ -136,7 +135,7 @@ __global__ __launch_bounds__(SELD_WAVE) void seld_block_kernel(
             const int nr = f_nref[q], np = f_npred[q];
             if (nr == 0 || np == 0) continue;
             const int fr = b * fpb + q;
-            const long f = clip * t_clip + fr;
+            const long f = span.at(fr);
             // the reference events of this frame (CSV order) and the predictions of class c (row order)
             const long e0 = ref_off[(base + fr) * C + c];
             if (lane < nr) {
@@ -241,6 +240,116 @@ __global__ __launch_bounds__(SELD_WAVE) void seld_block_kernel(
         rec[8] = de_fn;
         rec[9] = loc_fp;
         rec[10] = loc_fn;
+    }
+}
+
+// grid: n_clips * max_blocks * C workgroups of one wave: whole clips of t_clip frames, each from frame 0 of its file
+template <typename T>
+__global__ __launch_bounds__(SELD_WAVE) void seld_block_kernel(
+    const T *__restrict__ rows, const int *__restrict__ counts, const int *__restrict__ offs, const int *__restrict__ file_ids,
+    const int *__restrict__ file_info, const int *__restrict__ ref_off, const double *__restrict__ ref_ev,
+    const int *__restrict__ keep, int n_files, int t_clip, int C, int fpb, int max_blocks, double doa_thresh,
+    double *__restrict__ rec_out, int *__restrict__ status) {
+    const int lane = threadIdx.x;
+    const long g = blockIdx.x;
+    const int c = (int)(g % C);
+    const int b = (int)((g / C) % max_blocks);
+    const long clip = g / ((long)C * max_blocks);
+    double *rec = rec_out + g * SELD_REC;
+    if (lane < SELD_REC) rec[lane] = 0.0;
+    if (*status != 0) return;                                   // bad rows, or an error of an earlier call: nothing is added
+    const int fid = file_ids[clip];
+    if (fid < 0 || fid >= n_files) {
+        if (lane == 0 && b == 0 && c == 0) atomicOr(status, ADYOLO_SELD_BAD_FILE);
+        return;
+    }
+    if (b >= file_info[2 * fid + 1]) return;
+    const SeldSpan span{clip * t_clip, 0, t_clip};
+    seld_block_body(rows, counts, offs, ref_off, ref_ev, keep, (long)file_info[2 * fid], span, b, c, C, fpb, doa_thresh, rec,
+                    status);
+}
+
+// A segment row {file, f0, r0, n, last, 0, 0, 0} -> the file's blocks [b0, b1) it covers; false for a row that breaks the
+// contract of adyolo_seld_score_runs (the caller has checked the file id).
+__device__ __forceinline__ bool seld_segment_blocks(const int *__restrict__ sg, int file_blocks, int fpb, int run_frames,
+                                                    int seg_blocks, int &b0, int &b1) {
+    const int f0 = sg[1], r0 = sg[2], n = sg[3], last = sg[4];
+    b0 = b1 = 0;
+    if (f0 < 0 || r0 < 0 || n < 0 || f0 % fpb != 0 || n > run_frames || r0 > run_frames - n || f0 > INT_MAX - n) return false;
+    if (!last && (f0 + n) % fpb != 0) return false;
+    b0 = f0 / fpb;
+    b1 = last ? file_blocks : min((f0 + n) / fpb, file_blocks);
+    if (b1 < b0) b1 = b0;
+    return b1 - b0 <= seg_blocks;
+}
+
+// grid: n_segments * seg_blocks * C workgroups of one wave: the segments of one stitched run
+template <typename T>
+__global__ __launch_bounds__(SELD_WAVE) void seld_run_block_kernel(
+    const T *__restrict__ rows, const int *__restrict__ counts, const int *__restrict__ offs, const int *__restrict__ segments,
+    const int *__restrict__ file_info, const int *__restrict__ ref_off, const double *__restrict__ ref_ev,
+    const int *__restrict__ keep, int n_files, int run_frames, int C, int fpb, int seg_blocks, double doa_thresh,
+    double *__restrict__ rec_out, int *__restrict__ status) {
+    const int lane = threadIdx.x;
+    const long g = blockIdx.x;
+    const int c = (int)(g % C);
+    const int k = (int)((g / C) % seg_blocks);
+    const long seg = g / ((long)C * seg_blocks);
+    double *rec = rec_out + g * SELD_REC;
+    if (lane < SELD_REC) rec[lane] = 0.0;
+    if (*status != 0) return;
+    const int *sg = segments + seg * ADYOLO_SELD_RUN_WORDS;
+    const int fid = sg[0];
+    if (fid < 0 || fid >= n_files) {
+        if (lane == 0 && k == 0 && c == 0) atomicOr(status, ADYOLO_SELD_BAD_FILE);
+        return;
+    }
+    int b0, b1;
+    if (!seld_segment_blocks(sg, file_info[2 * fid + 1], fpb, run_frames, seg_blocks, b0, b1)) {
+        if (lane == 0 && k == 0 && c == 0) atomicOr(status, ADYOLO_SELD_BAD_RUN);
+        return;
+    }
+    if (b0 + k >= b1) return;
+    const SeldSpan span{(long)sg[2], sg[1], sg[1] + sg[3]};
+    seld_block_body(rows, counts, offs, ref_off, ref_ev, keep, (long)file_info[2 * fid], span, b0 + k, c, C, fpb, doa_thresh, rec,
+                    status);
+}
+
+// One workgroup, a thread per accumulator column: the segments in table order, each one's block records added to acc[file]
+// one at a time from left to right (S / D / I per block from its loc_fp / loc_fn, as seld_clip_kernel forms them).  A file
+// scored in ordered segments into a zeroed row therefore ends with the bits of one whole-clip call: 0 + r0 + r1 + ...
+__global__ __launch_bounds__(128) void seld_run_sum_kernel(const double *__restrict__ rec, const int *__restrict__ segments,
+                                                           const int *__restrict__ file_info, int n_segments, int run_frames,
+                                                           int C, int fpb, int seg_blocks, double *__restrict__ acc,
+                                                           const int *__restrict__ status) {
+    if (*status != 0) return;
+    const int ncol = SELD_FIELDS * C + 3;
+    for (int col = threadIdx.x; col < ncol; col += blockDim.x) {
+        for (int seg = 0; seg < n_segments; ++seg) {
+            const int *sg = segments + (long)seg * ADYOLO_SELD_RUN_WORDS;
+            const int fid = sg[0];
+            int b0, b1;
+            seld_segment_blocks(sg, file_info[2 * fid + 1], fpb, run_frames, seg_blocks, b0, b1);   // (status is 0: legal)
+            const int nb = b1 - b0;
+            if (nb <= 0) continue;
+            const double *r0 = rec + (long)seg * seg_blocks * C * SELD_REC;
+            double s = acc[(long)fid * ncol + col];
+            if (col < SELD_FIELDS * C) {
+                const int f = col / C, c = col % C;
+                for (int b = 0; b < nb; ++b) s += r0[((long)b * C + c) * SELD_REC + f];
+            } else {
+                const int which = col - SELD_FIELDS * C;         // 0 S, 1 D, 2 I
+                for (int b = 0; b < nb; ++b) {
+                    double lfp = 0.0, lfn = 0.0;
+                    for (int c = 0; c < C; ++c) {
+                        lfp += r0[((long)b * C + c) * SELD_REC + 9];
+                        lfn += r0[((long)b * C + c) * SELD_REC + 10];
+                    }
+                    s += which == 0 ? fmin(lfp, lfn) : which == 1 ? fmax(0.0, lfn - lfp) : fmax(0.0, lfp - lfn);
+                }
+            }
+            acc[(long)fid * ncol + col] = s;
+        }
     }
 }
 
@@ -361,4 +470,42 @@ extern "C" int adyolo_seld_score(const void *rows, int rows_f64, long n_rows, co
     hipLaunchKernelGGL(seld_file_kernel, dim3(1), dim3(256), 0, st, clip_sum, file_ids, n_clips, SELD_FIELDS * C + 3, acc,
                        status);
     return check_launch("seld_score_file");
+}
+
+extern "C" long adyolo_seld_score_runs_workspace_words(long n_segments, long run_frames, int seg_blocks, int C) {
+    if (n_segments <= 0 || run_frames <= 0 || seg_blocks <= 0 || C <= 0) return 0;
+    return 2 * seld_rec_doubles(n_segments, seg_blocks, C) + run_frames;
+}
+
+extern "C" int adyolo_seld_score_runs(const void *rows, int rows_f64, long n_rows, const int *counts, long run_frames,
+                                      const int *segments, long n_segments, const int *file_info, const int *ref_off,
+                                      const double *ref_ev, const int *keep, int n_files, int C, int fpb, int seg_blocks,
+                                      double doa_thresh, float *ws, double *acc, int *status, void *stream) {
+    ADYOLO_REQUIRE(counts && segments && file_info && ref_off && ref_ev && ws && acc && status && (rows || n_rows == 0) &&
+                       n_rows >= 0 && run_frames > 0 && n_segments > 0 && n_files > 0 && C > 0 && fpb > 0 && fpb <= 64 &&
+                       seg_blocks > 0 && (rows_f64 == 0 || rows_f64 == 1) && doa_thresh == doa_thresh,
+                   ADYOLO_EINVAL, "seld_score_runs: bad arguments");
+    ADYOLO_REQUIRE(n_segments * seg_blocks * C < (1L << 31) && run_frames < (1L << 31) && n_rows < (1L << 31), ADYOLO_ENOSUP,
+                   "seld_score_runs: %ld segments x %d blocks x %d classes, %ld frames, %ld rows do not fit 32-bit indices",
+                   n_segments, seg_blocks, C, run_frames, n_rows);
+    double *rec = reinterpret_cast<double *>(ws);
+    int *offs = reinterpret_cast<int *>(rec + seld_rec_doubles(n_segments, seg_blocks, C));
+    hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(seld_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, st, counts, offs, run_frames, n_rows, status);
+    int rc = check_launch("seld_score_runs_scan");
+    if (rc) return rc;
+    const dim3 grid((unsigned)(n_segments * seg_blocks * C));
+    if (rows_f64)
+        hipLaunchKernelGGL(seld_run_block_kernel<double>, grid, dim3(SELD_WAVE), 0, st, static_cast<const double *>(rows),
+                           counts, offs, segments, file_info, ref_off, ref_ev, keep, n_files, (int)run_frames, C, fpb, seg_blocks,
+                           doa_thresh, rec, status);
+    else
+        hipLaunchKernelGGL(seld_run_block_kernel<float>, grid, dim3(SELD_WAVE), 0, st, static_cast<const float *>(rows), counts,
+                           offs, segments, file_info, ref_off, ref_ev, keep, n_files, (int)run_frames, C, fpb, seg_blocks,
+                           doa_thresh, rec, status);
+    rc = check_launch("seld_score_runs_block");
+    if (rc) return rc;
+    hipLaunchKernelGGL(seld_run_sum_kernel, dim3(1), dim3(128), 0, st, rec, segments, file_info, (int)n_segments,
+                       (int)run_frames, C, fpb, seg_blocks, acc, status);
+    return check_launch("seld_score_runs_sum");
 }

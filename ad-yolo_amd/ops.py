@@ -1212,7 +1212,8 @@ SELD_STATUS = ((1, "more than 1024 predictions in one frame and class"),      # 
                (2, "more than 8 reference events in one frame and class"),
                (4, "frame counts negative or summing past the rows given"),
                (8, "a file index outside the reference table"),
-               (16, "no finite assignment (NaN coordinates)"))
+               (16, "no finite assignment (NaN coordinates)"),
+               (32, "a run segment off the block grid, outside the run or beyond seg_blocks"))
 SELD_ENOSUP_BITS = 1 | 2                                      # ADYOLO_SELD_PRED_OVERFLOW | ADYOLO_SELD_REF_OVERFLOW
 
 
@@ -1255,6 +1256,45 @@ def seld_score(rows, counts, table, file_ids, t_clip, out, status=None):
        _p(counts), n_clips, t_clip, _p(file_ids), _p(table.file_info), _p(table.ref_off), _p(table.ref_ev),
        _p(table.keep), table.n_files, table.nb_classes, table.frames_per_block, table.max_blocks, float(table.doa_threshold),
        _p(ws), _p(out), _p(status), _stream())
+    if own:
+        seld_status_check(status)
+    return status
+
+
+SELD_RUN_WORDS = 8                                            # ADYOLO_SELD_RUN_WORDS: {file, f0, r0, n, last, 0, 0, 0}
+SELD_BAD_RUN = 32                                             # ADYOLO_SELD_BAD_RUN
+
+
+def seld_score_runs(rows, counts, table, segments, seg_blocks, out, status=None):
+    """Adds the SELD accumulators of the segments of ONE stitched run of frames into out [files][9 C + 3] float64 (adyolo_hip.h,
+    ``adyolo_seld_score_runs``).  rows, table, out, status as for ``seld_score``; counts (run frames,) int32: rows per frame of
+    the run (``select_device_rows(run, 1, trim=False)``); segments int32 (S, 8) on the device: {file id, f0, r0, n, last, 0, 0,
+    0} per row (``seld_metrics.run_segments``); seg_blocks: at least the blocks any segment covers.  A file scored in ordered
+    segments into a zeroed row ends with the bits of one ``seld_score`` call on the whole recording.  No sync with a status."""
+    if not rows.is_cuda or rows.dtype not in (torch.float32, torch.float64) or not rows.is_contiguous():
+        raise _lib.AdyoloHipError("seld_score_runs: rows must be a contiguous float32 or float64 tensor on the device")
+    if rows.numel() % 5 or (rows.dim() == 2 and rows.shape[1] != 5):
+        raise _lib.AdyoloHipError("seld_score_runs: rows %s are not (N, 5)" % (tuple(rows.shape),))
+    for name, t, dt in (("counts", counts, torch.int32), ("segments", segments, torch.int32), ("out", out, torch.float64)):
+        if not t.is_cuda or t.dtype != dt or not t.is_contiguous() or t.device != rows.device:
+            raise _lib.AdyoloHipError("seld_score_runs: %s must be a contiguous %s tensor on %s" % (name, dt, rows.device))
+    if segments.dim() != 2 or segments.shape[0] < 1 or segments.shape[1] != SELD_RUN_WORDS:
+        raise _lib.AdyoloHipError("seld_score_runs: segments %s are not (S, %d)" % (tuple(segments.shape), SELD_RUN_WORDS))
+    run_frames, n_seg, seg_blocks = counts.numel(), segments.shape[0], int(seg_blocks)
+    if run_frames < 1 or seg_blocks < 1:
+        raise _lib.AdyoloHipError("seld_score_runs: a run of %d frames, %d blocks per segment" % (run_frames, seg_blocks))
+    if out.shape != (table.n_files, 9 * table.nb_classes + 3):
+        raise _lib.AdyoloHipError("seld_score_runs: out %s is not [%d][%d]" % (tuple(out.shape), table.n_files,
+                                                                               9 * table.nb_classes + 3))
+    own = status is None
+    if own:
+        status = torch.zeros(1, dtype=torch.int32, device=rows.device)
+    words = _lib.load().adyolo_seld_score_runs_workspace_words(n_seg, run_frames, seg_blocks, table.nb_classes)
+    ws = torch.empty(max(1, words), dtype=torch.float32, device=rows.device)
+    _c("adyolo_seld_score_runs", _p(rows) if rows.numel() else NULL, int(rows.dtype == torch.float64), rows.numel() // 5,
+       _p(counts), run_frames, _p(segments), n_seg, _p(table.file_info), _p(table.ref_off), _p(table.ref_ev), _p(table.keep),
+       table.n_files, table.nb_classes, table.frames_per_block, seg_blocks, float(table.doa_threshold), _p(ws), _p(out),
+       _p(status), _stream())
     if own:
         seld_status_check(status)
     return status

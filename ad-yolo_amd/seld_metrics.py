@@ -344,6 +344,39 @@ def pack_reference(refs, nb_classes, frames_per_block, keep_frames=None):
             "ref_ev": np.ascontiguousarray(ev, dtype=np.float64), "keep": keep if keep_frames is not None else None}
 
 
+def run_segments(label_frames, bounds):
+    """Recordings of ``label_frames`` frames each, laid end to end on one frame axis, scored in runs: run p holds the frames
+    [bounds[p], bounds[p + 1]) of that axis (bounds ascending from 0 to the total: the pass boundaries of a windowed
+    evaluation) -> per run an int64 array (S, 5) of {recording, f0, r0, n, last}: the recordings the run holds frames of, in
+    order -- f0 the first of them on the recording's own axis, r0 its place in the run, n their number, last = 1 when the run
+    holds the recording's final frame.  A recording without any frame gets one row {r, 0, r0, 0, 1} in the run that holds the
+    next recording's first frame, or in the last run when no frame follows.  Every recording has exactly one last row."""
+    frames = np.asarray(label_frames, dtype=np.int64).reshape(-1)
+    bounds = np.asarray(bounds, dtype=np.int64).reshape(-1)
+    start = np.concatenate([[0], np.cumsum(frames)]).astype(np.int64)
+    if len(bounds) < 2 or bounds[0] != 0 or bounds[-1] != start[-1] or (np.diff(bounds) <= 0).any() or (frames < 0).any():
+        raise ValueError("run_segments: bounds %s do not cut the %d frames of the recordings into runs"
+                         % (bounds.tolist(), int(start[-1])))
+    out = []
+    for p in range(len(bounds) - 1):
+        lo, hi = int(bounds[p]), int(bounds[p + 1])
+        final = p == len(bounds) - 2
+        rows = []
+        # the recordings that start before the run's end and end after its start, and the empty ones that start inside it
+        for r in range(int(np.searchsorted(start[1:], lo, "left")), len(frames)):
+            s, e = int(start[r]), int(start[r + 1])
+            if s >= hi and not (final and s == e == hi):
+                break
+            if s == e:
+                if lo <= s < hi or (final and s == hi):
+                    rows.append((r, 0, s - lo, 0, 1))
+            elif e > lo:
+                a, b = max(s, lo), min(e, hi)
+                rows.append((r, a - s, a - lo, b - a, int(b == e)))
+        out.append(np.asarray(rows, dtype=np.int64).reshape(-1, 5))
+    return out
+
+
 class SELDRefTable:
     """A packed reference table (``pack_reference``) on a device, the ``table`` argument of ``ops.seld_score``."""
 
@@ -444,6 +477,43 @@ class DeviceSELDScorer:
         if not names or counts.numel() % len(names):
             raise ValueError("add_rows: %d frame counts for %d clips" % (counts.numel(), len(names)))
         self._score(rows, counts.reshape(-1), ids, counts.numel() // len(names))
+
+    def segment_tables(self, names, label_frames, bounds):
+        """The segment tables of a windowed evaluation (``run_segments``) for THIS scorer's reference table: recordings
+        ``names`` (as ``get_filelist()`` gives them) of ``label_frames`` frames each, scored in runs cut at ``bounds`` -> one
+        table per run for ``add_run``, uploaded here, once.  Names go through ``_lookup``: one without a reference raises
+        KeyError (overlap=None) or maps to the empty entry (the overlap variants), as in ``add_rows``."""
+        import torch
+        ids = [self._lookup(n) for n in names]
+        if len(ids) != len(label_frames):
+            raise ValueError("segment_tables: %d names for %d recordings" % (len(ids), len(label_frames)))
+        fpb, tables = self._fpb, []
+        for seg in run_segments(label_frames, bounds):
+            rows = np.zeros((len(seg), 8), dtype=np.int32)                 # ADYOLO_SELD_RUN_WORDS
+            rows[:, 0] = [ids[r] for r in seg[:, 0].tolist()]
+            rows[:, 1:5] = seg[:, 1:5]
+            blocks = np.asarray([self._frames[k] // fpb for k in rows[:, 0].tolist()], dtype=np.int64)
+            b1 = np.where(seg[:, 4] != 0, blocks, np.minimum((seg[:, 1] + seg[:, 3]) // fpb, blocks))
+            seg_blocks = max(1, int((b1 - seg[:, 1] // fpb).max())) if len(seg) else 1
+            dev = torch.from_numpy(rows).to(self.device) if len(seg) else None
+            tables.append((dev, seg_blocks, rows[:, 0].tolist()))
+        return tables
+
+    def add_run(self, rows, counts, segments):
+        """rows (N, 5) and counts (run frames,) int32 on the device for ONE stitched run of frames (``select_device_rows(run, 1,
+        trim=False)``) and the run's entry of ``segment_tables``: every segment's blocks are added to its file's accumulators
+        (``ops.seld_score_runs``); a file whose ordered segments have all been added holds the bits ``add_rows`` on the whole
+        recording leaves.  No synchronisation."""
+        from . import ops
+        dev, seg_blocks, ids = segments
+        if dev is None:
+            return
+        ops.seld_score_runs(rows, counts.reshape(-1), self.table, dev, seg_blocks, self._acc, self._status)
+        seen = set(self._order)
+        for k in ids:
+            if k != self._skip and k not in seen:
+                self._order.append(k)
+                seen.add(k)
 
     def add_dict(self, name, labels):
         """Host rows {frame: [[class, x, y, z], ...]} of one file (what ``LabelPostProcessor.select`` returns); uploaded in

@@ -417,6 +417,139 @@ def infer_epoch_corpus(corpus, model, features, postprocessor, output_pth, forwa
             "frames": int(corpus.frame_start[-1])}
 
 
+def _window_pass(corpus, p, model, features, criterion, postprocessor, forward, acc, stitched):
+    """One pass of a labelled windowed evaluation: ``launch`` -> forward (+ decode) -> the window losses into ``acc`` ->
+    ``decode_stitch`` -> the pass's run of decoded frames (a view of ``stitched``, which is made on the first pass and handed
+    back).  No host synchronisation."""
+    from . import ops
+    b, n, wf = corpus.batch_size, corpus.n_samples, corpus.window_frames
+    audio_out = None
+    if forward is not None and hasattr(forward, "static_input"):
+        audio_out = forward.static_input((b, n, 4))                          # the gather writes the graph's input itself
+    audio, target, row_start = corpus.launch(p, audio_out)
+    dec = None
+    if forward is not None:
+        output, dec = forward(audio)
+    else:
+        output = model(features(audio, channels_last8=True), channels_last8=True)
+    if dec is None:
+        dec = postprocessor.decode_device(output)
+    if dec.shape[0] != b * wf:
+        raise ValueError("test_epoch_windows: %d decoded frames from %d windows of %d label frames (the model's frame rate is "
+                         "not the label hop's)" % (dec.shape[0], b, wf))
+    if row_start is not None:                              # AD-YOLO: every window's loss in one call; an empty window has no rows
+        cfg = getattr(criterion, "loss", criterion).cfg
+        ops.adyolo_loss_per_clip(output.contiguous(), target, row_start, cfg["nb_classes"], cfg["grid"], cfg["anchors"],
+                                 cfg["thr"], cfg["gains"], cfg["grid_size"], cfg["g_overlap"], acc=acc)
+    else:                                                  # class-wise heads: the criterion on each window's slice, empty ones left out
+        for k in range(corpus.windows_in_pass(p)):
+            ops.loss_accumulate(acc, criterion(output[k:k + 1], target[k:k + 1]).reshape(1))
+    if stitched is None:
+        stitched = torch.empty_like(dec)
+    ops.decode_stitch(dec, corpus.pass_table(p), wf, corpus.pass_base[p], stitched, corpus.status)
+    return stitched, stitched[:corpus.pass_frames[p]]
+
+
+def _write_pass_rows(corpus, p, rows, counts, outs):
+    """The selected rows of pass ``p``'s run (trimmed) -> the host, onto each recording's own frame axis in ``outs``."""
+    from . import ops
+    from .corpus import split_pass_rows
+    rows_h, counts_h = [t.numpy() for t in ops.to_host_many(rows, counts)]
+    for r, found in split_pass_rows(rows_h, counts_h, corpus.pass_base[p], corpus.frame_start).items():
+        outs[r].update(found)                                                # (a recording's passes come in frame order)
+
+
+def test_epoch_windows(corpus, model, features, criterion, postprocessor, output_pth=None, forward=None, device_scorer=None):
+    """Labelled evaluation of recordings of ANY length from an HBM-resident split (``corpus.EvalWindowCorpus``): every recording
+    cut into overlapping windows of one shape, ``corpus.batch_size`` windows per pass -- one input shape for the whole split
+    and, with ``forward`` (``graph.ForwardGraphs``), one recorded graph.  Per pass: ``corpus.launch`` (audio into the graph's
+    static input when there is one, the windows' labels) -> forward + decode -> the window losses into a device accumulator
+    -> ``adyolo_decode_stitch`` (the kept frames of the pass as one run) -> ``select_device_rows`` on the run ->
+    ``device_scorer.add_run`` (``adyolo_seld_score_runs``: the run scored in segments, one per recording it touches; a
+    recording whose segments have all been added holds the accumulator bits of one whole-recording ``add_rows``).
+
+    THE LOSS is the training chunks' definition, not the reference's per-recording one: the mean over the windows, in window
+    order in float32, of the loss of each window's full ``window_frames`` frames, margins included (AD-YOLO:
+    ``adyolo_loss_per_clip`` with a window for a clip -- a window without AD-YOLO rows is left out, as a clip without rows is
+    in ``test_epoch_corpus``; class-wise heads: the criterion on each window's slice).  A frame that two windows overlap on
+    counts in both, a short recording's window is padded with silence and no events.  It equals the reference's loss only
+    where every recording is exactly one window long.
+
+    output_pth=None: nothing is written and the pass synchronises ONCE, at its end: one ``to_host_many`` of the loss
+    accumulator and the corpus status word (the scorer's status is read by its ``scores()``).  With output_pth the rows of
+    every pass go to the host (one synchronisation each) and one CSV is written per recording (``corpus.split_pass_rows``),
+    empty for a recording without rows or without a label frame.  Returns the mean loss."""
+    from . import ops
+    model.eval()
+    if output_pth is not None:
+        delete_and_create_folder(output_pth)
+    names = corpus.get_filelist()
+    corpus.reset_status()
+    acc = ops.loss_accumulator(corpus.device)
+    segments = corpus.segments(device_scorer) if device_scorer is not None else None
+    outs = [{} for _ in names]
+    stitched = None
+    with torch.no_grad():
+        for p in range(corpus.n_passes):
+            stitched, run = _window_pass(corpus, p, model, features, criterion, postprocessor, forward, acc, stitched)
+            rows, counts = postprocessor.select_device_rows(run, 1, trim=output_pth is not None)
+            if device_scorer is not None:
+                device_scorer.add_run(rows, counts, segments[p])
+            if output_pth is not None:
+                _write_pass_rows(corpus, p, rows, counts, outs)
+    if output_pth is not None:
+        for name, rows in zip(names, outs):
+            write_seld_output_file(os.path.join(output_pth, name + ".csv"), rows)
+    return _corpus_finish(corpus, acc)
+
+
+def sweep_conf_thresh_windows(corpus, model, features, criterion, postprocessor, scorer, thresholds=None, output_pth=None,
+                              forward=None):
+    """``sweep_conf_thresh_corpus`` through windows (``corpus.EvalWindowCorpus``): ONE forward pass per window pass, every
+    pass's stitched run kept (cloned) on the device, then per threshold ``scorer.reset()``, the selection of every run and
+    ``scorer.add_run``; the chosen threshold is left set on the post-processor.  With ``output_pth`` the last threshold's CSV
+    files are written.  The loss is ``test_epoch_windows``'s.  -> (new_thresh, [[ER, F, LE, LR, SELD] per threshold], mean loss)"""
+    import numpy as np
+    from . import ops
+    from .seld_metrics import DeviceSELDScorer
+    if not isinstance(scorer, DeviceSELDScorer):
+        raise ValueError("sweep_conf_thresh_windows needs a seld_metrics.DeviceSELDScorer (got %s)" % type(scorer).__name__)
+    if thresholds is None:
+        thresholds = np.arange(0.1, 1.0, 0.1)
+    model.eval()
+    names = corpus.get_filelist()
+    corpus.reset_status()
+    acc = ops.loss_accumulator(corpus.device)
+    segments = corpus.segments(scorer)
+    runs, stitched = [], None
+    with torch.no_grad():
+        for p in range(corpus.n_passes):
+            stitched, run = _window_pass(corpus, p, model, features, criterion, postprocessor, forward, acc, stitched)
+            runs.append(run.clone())                                         # (the stitch buffer is reused)
+    loss = _corpus_finish(corpus, acc)
+    new_thresh, best, table = postprocessor.get_conf_thresh(), 9999.0, []
+    for k, th in enumerate(thresholds):
+        postprocessor.set_conf_thresh(th)
+        write = output_pth is not None and k == len(thresholds) - 1
+        outs = [{} for _ in names]
+        scorer.reset()
+        for p, run in enumerate(runs):
+            rows, counts = postprocessor.select_device_rows(run, 1, trim=write)
+            scorer.add_run(rows, counts, segments[p])
+            if write:
+                _write_pass_rows(corpus, p, rows, counts, outs)
+        if write:
+            delete_and_create_folder(output_pth)
+            for name, rows in zip(names, outs):
+                write_seld_output_file(os.path.join(output_pth, name + ".csv"), rows)
+        er, f, le, lr, seld = scorer.scores()[:5]
+        table.append([er, f, le, lr, seld])
+        if seld < best:
+            new_thresh, best = th, seld
+    postprocessor.set_conf_thresh(new_thresh)
+    return new_thresh, table, loss
+
+
 def score_output_folder(params, ref_dir, output_pth, is_jackknife=False):
     """The three score sets the reference prints for one evaluated folder (src/test.py:104-133): all frames, frames with
     overlapping events ("class-independent polyphony") and frames with overlapping events of one class

@@ -494,6 +494,33 @@ int  adyolo_seld_score(const void *rows, int rows_f64, long n_rows, const int *c
                        const int *file_ids, const int *file_info, const int *ref_off, const double *ref_ev, const int *keep,
                        int n_files, int C, int fpb, int max_blocks, double doa_thresh, float *ws, double *acc, int *status,
                        void *stream);
+/* adyolo_seld_score_runs, opt-in: the same scores for the segments of ONE stitched run of frames (labelled evaluation through
+ * windows: a pass begins in the middle of one recording and ends in the middle of another), against the same reference table.
+ *   rows, rows_f64, n_rows  as above
+ *   counts   [run_frames] int32: rows per frame of the run (what the selection writes for the run as one clip)
+ *   segments DEVICE int32 [n_segments][ADYOLO_SELD_RUN_WORDS] = {file id, f0 = the segment's first frame on the file's own frame
+ *            axis, r0 = its first frame in counts, n >= 0 = the frames of the run that belong to it, last = 1 for the file's
+ *            final segment, 0, 0, 0}
+ *   a segment covers the file's blocks [f0 / fpb, b1): b1 = min((f0 + n) / fpb, blocks) for a segment that is not the last,
+ *   b1 = blocks of file_info for the last one, which so also accounts for the blocks past the audio that still hold reference
+ *   events (FN); nothing at or past blocks * fpb is scored.  A prediction of file frame fr is read from counts[r0 + fr - f0],
+ *   and only for f0 <= fr < f0 + n (and keep, where given).  A last segment with n = 0 is legal (a recording shorter than one
+ *   frame that has a reference).
+ *   acc      for every column the kernel reads acc[file][col], adds the segment's block records one at a time, left to right in
+ *            float64 (S, D, I per block from its loc_fp / loc_fn), and writes it back; segments in table order; no float
+ *            atomics.  A file scored in ordered segments into a zeroed row ends, in every column, with the bits one
+ *            adyolo_seld_score call on the whole recording leaves (that call forms 0 + (r0 + r1 + ...) in the same order).
+ *   seg_blocks >= the blocks every segment covers (it sizes the grid: one wave per (segment, block, class));
+ *   ws       adyolo_seld_score_runs_workspace_words(n_segments, run_frames, seg_blocks, C) words
+ *   status   as above, and ADYOLO_SELD_BAD_RUN for a segment with f0 % fpb != 0, (f0 + n) % fpb != 0 unless last, a negative
+ *            f0, r0 or n, r0 + n > run_frames, or more blocks than seg_blocks; while the word is nonzero acc is left as it is. */
+#define ADYOLO_SELD_RUN_WORDS 8
+#define ADYOLO_SELD_BAD_RUN   32  /* a segment that breaks the contract above */
+long adyolo_seld_score_runs_workspace_words(long n_segments, long run_frames, int seg_blocks, int C);
+int  adyolo_seld_score_runs(const void *rows, int rows_f64, long n_rows, const int *counts, long run_frames,
+                            const int *segments, long n_segments, const int *file_info, const int *ref_off,
+                            const double *ref_ev, const int *keep, int n_files, int C, int fpb, int seg_blocks,
+                            double doa_thresh, float *ws, double *acc, int *status, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * K10 the other heads / losses behind the reference's --loss switch (src/main.py:43)

@@ -109,6 +109,8 @@ SIGNATURES = {
     "adyolo_tta_merge_workspace_words": (L, [L, I]),
     "adyolo_tta_collect": (I, [P, L, P, P, P, P, P, L, I, I, I, I, ctypes.c_uint, P]),
     "adyolo_tta_merge": (I, [P, P, P, P, L, P, P, L, I, I, I, F, I, P]),
+    "adyolo_track_workspace_words": (L, [L, I]),
+    "adyolo_track_rows": (I, [P, L, P, L, I, I, F, I, I, F, F, P, P, P, L, P, P, P]),
     "adyolo_conv_gemm": (I, [P, P, P, P] + [I] * 13 + [P]),
     "adyolo_conv_gemm_plan": (I, [I] * 13 + [P]),
     "adyolo_pack_wk": (I, [P, P, I, I, I, I, I, P]),

@@ -282,6 +282,43 @@ def tta_options(params, views=None, postprocessor=None):
             "max_rows_per_frame": int(cap)}
 
 
+TRACK_DEFAULT_GATE_DEG = 20.0                                 # the scorer's DOA threshold
+TRACK_DEFAULT_MAX_GAP = 2
+TRACK_DEFAULT_MIN_LEN = 3
+TRACK_DEFAULT_SMOOTH = 0.5
+
+
+def track_options(params):
+    """What ``test.test_epoch_corpus(track=...)`` takes: None (tracking is off) or {'gate_deg', 'max_gap', 'min_len',
+    'smooth'}, the parameters of ``postprocess.track_rows``.  The keys are read from ``test_config``, then ``train_config``.
+    Only ``track: true`` switches tracking on (absent or false: None).  ``track_gate_deg``: the association gate, an angle in
+    (0, 90) degrees, default 20 (the scorer's DOA threshold); ``track_max_gap``: the longest gap in frames that is bridged and
+    filled, an integer >= 0, default 2; ``track_min_len``: the fewest hits a track needs to be kept, an integer >= 1, default
+    3; ``track_smooth``: the weight of a new detection in the track's direction, in (0, 1], default 0.5 (1: no smoothing).
+    None of the defaults is tuned on data.  ``ValueError`` naming the key otherwise."""
+    import math
+    import numpy as np
+    on, where = _tta_key(params, "track", False)
+    if not isinstance(on, bool):
+        raise ValueError("%s must be true or false (got %r)" % (where, on))
+    if not on:
+        return None
+    gate, where = _tta_key(params, "track_gate_deg", TRACK_DEFAULT_GATE_DEG)
+    if isinstance(gate, bool) or not isinstance(gate, (int, float)) or not math.isfinite(gate) or not 0.0 < gate < 90.0 \
+            or not 0.0 < np.float32(math.cos(math.radians(gate))) < 1.0:       # (the float32 cosine is what the gate compares)
+        raise ValueError("%s must be an angle in (0, 90) degrees (got %r)" % (where, gate))
+    max_gap, where = _tta_key(params, "track_max_gap", TRACK_DEFAULT_MAX_GAP)
+    if isinstance(max_gap, bool) or not isinstance(max_gap, int) or max_gap < 0:
+        raise ValueError("%s must be an integer >= 0 (got %r)" % (where, max_gap))
+    min_len, where = _tta_key(params, "track_min_len", TRACK_DEFAULT_MIN_LEN)
+    if isinstance(min_len, bool) or not isinstance(min_len, int) or min_len < 1:
+        raise ValueError("%s must be an integer >= 1 (got %r)" % (where, min_len))
+    smooth, where = _tta_key(params, "track_smooth", TRACK_DEFAULT_SMOOTH)
+    if isinstance(smooth, bool) or not isinstance(smooth, (int, float)) or not math.isfinite(smooth) or not 0.0 < smooth <= 1.0:
+        raise ValueError("%s must lie in (0, 1] (got %r)" % (where, smooth))
+    return {"gate_deg": float(gate), "max_gap": int(max_gap), "min_len": int(min_len), "smooth": float(smooth)}
+
+
 def channel_swap_enabled(params):
     """``aug_config.channel_swap_augment``, with its two refusals: MIC-format audio only, and not together with the FOA
     rotation (``ValueError``: both would move the labels)."""

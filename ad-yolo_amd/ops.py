@@ -1208,6 +1208,86 @@ def tta_merge(pool, pool_counts, nb_classes, cos_t, min_views, status, ws, rows=
     return rows[:total], counts[:frames]
 
 
+TRACK_STATUS = ((1, "more than 64 rows in one frame and class: the first 64 were linked"),                       # ADYOLO_TRACK_*
+                (2, "more than 8 concurrent tracks of one class: a detection was dropped"),
+                (4, "a selected row with a zero or non-finite vector was dropped"),
+                (8, "frame counts negative or past the rows given, or a class outside [0, nb_classes)"))
+TRACK_BAD_ROWS = 8
+TRACK_SLOTS = 8                                               # ADYOLO_TRACK_SLOTS
+
+
+def track_status_check(word):
+    """Raise ``AdyoloHipError`` for ADYOLO_TRACK_BAD_ROWS in a status word already read to the host.  The two overflows and a
+    dropped vector are defined behaviour (caps of ``postprocess.track_rows``; an untrained model's twenty rows per class and
+    frame pass through) and only warn."""
+    word = int(word)
+    why = "; ".join(msg for bit, msg in TRACK_STATUS if word & bit)
+    if word & TRACK_BAD_ROWS:
+        raise _lib.AdyoloHipError("adyolo tracking failed (status 0x%x): %s" % (word, why))
+    if word:
+        import warnings
+        warnings.warn("adyolo tracking (status 0x%x): %s" % (word, why))
+
+
+def track_buffers(device, frames, nb_classes):
+    """The buffers one batch shape of ``track_rows`` needs, allocated once: {'ws', 'rows' (frames * C * 8, 5) float32, 'ids'
+    (frames * C * 8,) int32, 'counts' (frames + 1,) int32}."""
+    f, c = int(frames), int(nb_classes)
+    dev = torch.device(device)
+    return {"ws": torch.empty(max(4, _lib.load().adyolo_track_workspace_words(f, c)), dtype=torch.float32, device=dev),
+            "rows": torch.empty((max(1, f * c * TRACK_SLOTS), 5), dtype=torch.float32, device=dev),
+            "ids": torch.empty(max(1, f * c * TRACK_SLOTS), dtype=torch.int32, device=dev),
+            "counts": torch.empty(f + 1, dtype=torch.int32, device=dev)}
+
+
+def track_rows(rows, counts, n_clips, nb_classes, opts, buf=None, status=None, trim=True):
+    """A selection -- rows (capacity, 5) [frame, class, x, y, z] and counts (n_clips * T',) int32 on the device, as
+    ``yolo_select`` / ``classwise_select`` / ``tta_merge`` return them, trimmed or not -- linked into tracks (adyolo_hip.h
+    ``adyolo_track_rows``): ``postprocess.track_rows`` bit for bit -> (rows' (N', 5), counts' (n_clips * T',) int32, ids (N',)
+    int32), all on the device.  opts: the dict of ``augmentations.track_options`` {'gate_deg', 'max_gap', 'min_len', 'smooth'}.
+    buf: ``track_buffers`` of this shape (None: new ones); status: one int32 on the device the ADYOLO_TRACK_* bits are ORed into
+    (None: a new word, read and passed to ``track_status_check`` here when trim is True).  trim as ``yolo_select``: True reads
+    the row total (one 4-byte copy, synchronises); False with given buffers neither allocates nor synchronises, and rows' / ids
+    are the capacity buffers of which the first counts'.sum() are written."""
+    from .postprocess import track_cos
+    name = "track_rows"
+    _chk(rows)
+    frames, c, n_clips = int(counts.numel()), int(nb_classes), int(n_clips)
+    if rows.dim() != 2 or rows.shape[1] != 5:
+        raise _lib.AdyoloHipError("%s: rows %s are not (N, 5)" % (name, tuple(rows.shape)))
+    if not counts.is_cuda or counts.dtype != torch.int32 or not counts.is_contiguous() or counts.device != rows.device:
+        raise _lib.AdyoloHipError("%s: counts must be a contiguous int32 tensor on %s" % (name, rows.device))
+    if n_clips < 1 or frames < 1 or frames % n_clips or c < 1:
+        raise _lib.AdyoloHipError("%s: %d frame counts, %d clips, %d classes" % (name, frames, n_clips, c))
+    if buf is None:
+        buf = track_buffers(rows.device, frames, c)
+    own_status = status is None
+    if own_status:
+        status = torch.zeros(1, dtype=torch.int32, device=rows.device)
+    need = frames * c * TRACK_SLOTS
+    ws, out, ids, out_counts = buf["ws"], buf["rows"], buf["ids"], buf["counts"]
+    _chk(ws, out)
+    if ws.numel() < _lib.load().adyolo_track_workspace_words(frames, c) or out.dim() != 2 or out.shape[1] != 5 \
+            or out.shape[0] < need or ids.numel() < need or out_counts.numel() != frames + 1 \
+            or any(t.device != rows.device for t in (ws, out, ids, out_counts, status)) \
+            or any(t.dtype != torch.int32 or not t.is_contiguous() for t in (ids, out_counts, status)) or status.numel() < 1:
+        raise _lib.AdyoloHipError("%s: the buffers are not track_buffers(%s, %d, %d) / status no int32 word there"
+                                  % (name, rows.device, frames, c))
+    a = np.float32(opts["smooth"])
+    _c("adyolo_track_rows", _p(rows) if rows.numel() else _p(out), rows.shape[0], _p(counts), n_clips, frames // n_clips, c,
+       float(track_cos(opts["gate_deg"])), int(opts["max_gap"]), int(opts["min_len"]), float(a),
+       float(np.float32(np.float32(1) - a)), _p(ws), _p(out), _p(ids), out.shape[0], _p(out_counts), _p(status), _stream())
+    if not trim:
+        return out, out_counts[:frames], ids
+    if own_status:
+        total_h, status_h = to_host_many(out_counts[frames:], status)
+        track_status_check(int(status_h[0]))
+        total = int(total_h[0])
+    else:
+        total = int(to_host(out_counts[frames:])[0])
+    return out[:total], out_counts[:frames], ids[:total]
+
+
 SELD_STATUS = ((1, "more than 1024 predictions in one frame and class"),      # ADYOLO_SELD_* in adyolo_hip.h
                (2, "more than 8 reference events in one frame and class"),
                (4, "frame counts negative or summing past the rows given"),

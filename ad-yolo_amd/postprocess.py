@@ -311,6 +311,187 @@ def merge_view_rows(per_view, views, unify_thresh, min_views=None, max_rows_per_
     return (np.asarray(rows, dtype=F32).reshape(-1, 5), counts), status
 
 
+# ---- Tracks: the host definition of csrc/track.hip ``adyolo_track_rows``.
+TRACK_DET_OVERFLOW, TRACK_SLOT_OVERFLOW, TRACK_BAD_VECTOR, TRACK_BAD_ROWS = 1, 2, 4, 8     # ADYOLO_TRACK_* in adyolo_hip.h
+TRACK_SLOTS = 8                                                    # ADYOLO_TRACK_SLOTS: concurrent tracks per clip and class
+TRACK_MAX_DET = 64                                                 # ADYOLO_TRACK_MAX_DET: detections per frame and class
+
+
+def track_cos(gate_deg):
+    """The association gate of ``track_rows``: float32(cos(radians(gate_deg))), computed once on the host."""
+    return F32(math.cos(math.radians(float(gate_deg))))
+
+
+def _unit3(v):
+    """v / sqrt((x*x + y*y) + z*z) of one float32 vector, every operation rounded."""
+    return v / np.sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2])
+
+
+def track_candidates(rows, counts, nb_classes):
+    """Step 1 of ``track_rows``: {(frame, class): unit vectors (n <= TRACK_MAX_DET, 3) in row order} and the status bits.
+    frame is the index on the counts axis; the rows' own frame column is not read."""
+    rows = np.asarray(rows, dtype=F32).reshape(-1, 5)
+    counts = np.asarray(counts).astype(np.int64).reshape(-1)
+    offs = np.cumsum(counts) - counts
+    bad = (counts < 0) | (offs < 0) | (offs + counts > len(rows))  # such a frame has no rows
+    status = TRACK_BAD_ROWS if bad.any() else 0
+    cand = {}
+    for f in np.flatnonzero(~bad & (counts > 0)).tolist():
+        r = rows[offs[f]:offs[f] + counts[f]]
+        cls = r[:, 1]
+        with np.errstate(all="ignore"):
+            ok = (cls >= 0) & (cls < nb_classes) & (cls == np.floor(cls))
+        if not ok.all():                                           # no (frame, class) owns such a row
+            status |= TRACK_BAD_ROWS
+        for c in np.unique(cls[ok]).tolist():
+            p = r[cls == c][:, 2:5]
+            if len(p) > TRACK_MAX_DET:
+                status |= TRACK_DET_OVERFLOW
+                p = p[:TRACK_MAX_DET]
+            with np.errstate(all="ignore"):
+                norm = _norm3(p)
+                good = np.isfinite(norm) & (norm > 0)
+                if not good.all():
+                    status |= TRACK_BAD_VECTOR
+                u = (p[good] / norm[good, None]).astype(F32)
+            if len(u):
+                cand[(f, int(c))] = u
+    return cand, status
+
+
+def track_rows(rows, counts, n_clips, nb_classes, gate_deg, max_gap, min_len, smooth, trace=None):
+    """Link selected rows into tracks across frames, the host definition (csrc/track.hip matches it bit for bit): rows (N, 5)
+    [frame, class, x, y, z] and counts (n_clips * T',) rows per frame, clip after clip (``select_device_rows`` /
+    ``merge_view_rows``) -> ((rows', counts'), track_ids (N',) int32, status) in the same layout, the frame column the index on
+    the counts axis.  Everything is float32, every operation rounded (no contraction).  cos_g = ``track_cos(gate_deg)``,
+    a = float32(smooth), b = float32(1) - a.  Every (clip, class) on its own, ``TRACK_SLOTS`` slots that are empty or hold a
+    track {id, s (unit vector), first, last, hits}, next_id = 0; for frame t = 0 .. T' - 1:
+      1. candidates: the rows of the class in the frame in row order, the first ``TRACK_MAX_DET`` of them
+         (``TRACK_DET_OVERFLOW``); u = p / sqrt((px*px + py*py) + pz*pz), a zero or non-finite norm drops it
+         (``TRACK_BAD_VECTOR``);
+      2. expire: every occupied slot with t - last - 1 > max_gap is closed; closing a track with hits < min_len erases its
+         cells in frames first .. last of the slot;
+      3. associate: dot(k, j) = (s.x*u.x + s.y*u.y) + s.z*u.z, eligible when dot > cos_g; greedy rounds over the unmatched
+         slots and candidates take the eligible pair with the largest dot (ties: the lowest slot, then the lowest candidate);
+      4. update each matched (k, j): m = unit((s * b) + (u * a)); with gap = t - last - 1, for g = 1 .. gap, w = float32(g) /
+         float32(gap + 1), cell (last + g, class, k) = unit((s * (float32(1) - w)) + (m * w)) with the track's id; then cell
+         (t, class, k) = m, s = m, last = t, hits += 1 (filled frames are no hits);
+      5. open: the unmatched candidates in candidate order take the lowest empty slot each (one closed in step 2 of this frame
+         included): s = u, first = last = t, hits = 1, id = next_id++, cell (t, class, k) = u; without an empty slot the
+         candidate is dropped (``TRACK_SLOT_OVERFLOW``).
+    After the last frame every slot is closed (short tracks are pruned there too).  Output: frames ascend, classes ascend within
+    a frame, slots ascend within a class; a track's id is the order in which it was opened within its (clip, class), pruned
+    tracks included.  ``TRACK_BAD_ROWS``: counts negative or running past the rows (such a frame has no rows), or a class that
+    is no integer in [0, nb_classes) (such a row is skipped).  trace: a dict that receives what happened on the way, for tests:
+    {'opened', 'pruned', 'pruned_fills' (filled cells erased with their track), 'filled', 'reused' (slots closed in step 2 and
+    opened again in step 5 of the same frame)}."""
+    n_clips, nb_classes, max_gap, min_len = int(n_clips), int(nb_classes), int(max_gap), int(min_len)
+    n_frames = len(np.asarray(counts).reshape(-1))
+    if n_clips < 1 or n_frames < 1 or n_frames % n_clips or nb_classes < 1:
+        raise ValueError("track_rows: %d frame counts, %d clips, %d classes" % (n_frames, n_clips, nb_classes))
+    cos_g, a = track_cos(gate_deg), F32(smooth)
+    if max_gap < 0 or min_len < 1 or not 0 < float(gate_deg) < 90 or not 0 < cos_g < 1 or not 0 < a <= 1:
+        raise ValueError("track_rows: gate_deg %r, max_gap %r, min_len %r, smooth %r" % (gate_deg, max_gap, min_len, smooth))
+    b = F32(F32(1) - a)
+    t_clip = n_frames // n_clips
+    cand, status = track_candidates(rows, counts, nb_classes)
+    active = {}                                                    # (clip, class) -> its frames with candidates
+    for f, c in sorted(cand):
+        active.setdefault((f // t_clip, c), []).append(f)
+    cells = {}                                                     # (frame, class, slot) -> (unit vector, id)
+    seen = {"opened": 0, "pruned": 0, "pruned_fills": 0, "filled": 0, "reused": 0}
+    for (clip, c), frames in active.items():
+        f0 = clip * t_clip
+        slots = [None] * TRACK_SLOTS                               # None or [id, s, first, last, hits]
+        next_id = 0
+
+        def close(k):
+            _, _, first, last, hits = slots[k]
+            if hits < min_len:
+                gone = sum(cells.pop((f0 + t, c, k), None) is not None for t in range(first, last + 1))
+                seen["pruned"] += 1
+                seen["pruned_fills"] += gone - hits
+            slots[k] = None
+
+        for t in range(frames[0] - f0, t_clip):
+            u = cand.get((f0 + t, c))
+            if u is None and not any(slots):
+                if f0 + t > frames[-1]:
+                    break
+                continue
+            expired = set()
+            for k in range(TRACK_SLOTS):                           # 2. expire
+                if slots[k] is not None and t - slots[k][3] - 1 > max_gap:
+                    close(k)
+                    expired.add(k)
+            if u is None:
+                continue
+            occ = [k for k in range(TRACK_SLOTS) if slots[k] is not None]
+            cand_free = np.ones(len(u), dtype=bool)
+            if occ:                                                # 3. associate
+                s = np.stack([slots[k][1] for k in occ])
+                dot = (s[:, None, 0] * u[None, :, 0] + s[:, None, 1] * u[None, :, 1]) + s[:, None, 2] * u[None, :, 2]
+                val = np.where(dot > cos_g, dot, F32(-np.inf))
+                while True:
+                    at = int(np.argmax(val))                       # row-major: the lowest slot, then the lowest candidate
+                    i, j = divmod(at, len(u))
+                    if not val[i, j] > -np.inf:
+                        break
+                    val[i, :] = -np.inf
+                    val[:, j] = -np.inf
+                    cand_free[j] = False
+                    trk = slots[occ[i]]                            # 4. update
+                    k, sk, last = occ[i], trk[1], trk[3]
+                    m = _unit3((sk * b) + (u[j] * a))
+                    gap = t - last - 1
+                    for g in range(1, gap + 1):
+                        w = F32(g) / F32(gap + 1)
+                        cells[(f0 + last + g, c, k)] = (_unit3((sk * (F32(1) - w)) + (m * w)), trk[0])
+                    seen["filled"] += gap
+                    cells[(f0 + t, c, k)] = (m, trk[0])
+                    trk[1], trk[3], trk[4] = m, t, trk[4] + 1
+            for j in np.flatnonzero(cand_free).tolist():           # 5. open
+                k = next((k for k in range(TRACK_SLOTS) if slots[k] is None), None)
+                if k is None:
+                    status |= TRACK_SLOT_OVERFLOW
+                    break
+                slots[k] = [next_id, u[j], t, t, 1]
+                cells[(f0 + t, c, k)] = (u[j], next_id)
+                next_id += 1
+                seen["opened"] += 1
+                seen["reused"] += k in expired
+        for k in range(TRACK_SLOTS):
+            if slots[k] is not None:
+                close(k)
+    keys = sorted(cells)
+    out = np.zeros((len(keys), 5), dtype=F32)
+    ids = np.zeros(len(keys), dtype=np.int32)
+    out_counts = np.zeros(n_frames, dtype=np.int32)
+    for n, key in enumerate(keys):
+        vec, tid = cells[key]
+        out[n, 0], out[n, 1], out[n, 2:5], ids[n] = key[0], key[1], vec, tid
+        out_counts[key[0]] += 1
+    if trace is not None:
+        trace.update(seen)
+    return (out, out_counts), ids, status
+
+
+def track_groups(ids, counts, n_clips=1):
+    """The ids of ``track_rows`` grouped like ``group_rows`` groups its rows: one {frame of the clip: [id, ...]} per clip, what
+    ``write_seld_output_file(tracks=...)`` takes."""
+    ids = np.asarray(ids).reshape(-1).tolist()
+    counts = np.asarray(counts, dtype=np.int64).reshape(-1)
+    if n_clips < 1 or len(counts) % n_clips or int(counts.sum()) != len(ids):
+        raise ValueError("track_groups: %d ids, %d frame counts summing to %d, %d clips"
+                         % (len(ids), len(counts), int(counts.sum()), n_clips))
+    t = len(counts) // n_clips
+    ends = np.cumsum(counts)
+    outs = [{} for _ in range(n_clips)]
+    for f in np.flatnonzero(counts).tolist():
+        outs[f // t][f % t] = ids[ends[f] - counts[f]:ends[f]]
+    return outs
+
+
 class LabelPostProcessor:
     """``LabelPostProcessor(params).postprocess(output)`` for the adyolo head (decode + NMS) and the class-wise heads
     (``--loss seddoa | masked-seddoa | accdoa | adpit``); ``output`` (1, T', K) on the GPU."""
@@ -386,6 +567,13 @@ class LabelPostProcessor:
         return ops.yolo_select(decoded_dev, self.nb_classes, self.conf_thresh, self.clss_thresh, self.unify_thresh, self.nms,
                                trim=trim)
 
+    def track_device_rows(self, rows, counts, n_clips, opts, buf=None, status=None, trim=True):
+        """``track_rows`` on the device (``ops.track_rows``; the same rows, counts and ids bit for bit) on what
+        ``select_device_rows`` or the test-time-augmentation merge returns for n_clips clips -> (rows', counts', ids), all on
+        the device.  opts: ``augmentations.track_options``; buf / status / trim as ``ops.track_rows``."""
+        from . import ops
+        return ops.track_rows(rows, counts, n_clips, self.nb_classes, opts, buf=buf, status=status, trim=trim)
+
     def select_device(self, decoded_dev, n_clips=1):
         """``select_device_rows`` -> one {frame: [[class, x, y, z], ...]} per clip.  Only the selected rows and the per-frame
         counts are copied to the host."""
@@ -403,9 +591,16 @@ class LabelPostProcessor:
         return self.select(self.decode(output, borrow=True))       # consumed at once: no second host copy
 
 
-def write_seld_output_file(file_pth, output: dict):
-    """reference test.py:26-30: rows ``frame,class,0,x,y,z``."""
+def write_seld_output_file(file_pth, output: dict, tracks=None):
+    """reference test.py:26-30: rows ``frame,class,0,x,y,z``.  tracks: {frame: [id, ...]} parallel to ``output``
+    (``track_groups`` of the ids ``track_rows`` returns): the third column, the DCASE track index, is the row's id instead
+    of 0."""
     with open(file_pth, "w") as f:
         for frame_idx in output.keys():
-            for [class_idx, x, y, z] in output[frame_idx]:
-                f.write("{},{},{},{},{},{}\n".format(int(frame_idx), int(class_idx), 0, float(x), float(y), float(z)))
+            ids = None if tracks is None else tracks[frame_idx]
+            if ids is not None and len(ids) != len(output[frame_idx]):
+                raise ValueError("write_seld_output_file: frame %r has %d rows and %d track ids"
+                                 % (frame_idx, len(output[frame_idx]), len(ids)))
+            for n, [class_idx, x, y, z] in enumerate(output[frame_idx]):
+                f.write("{},{},{},{},{},{}\n".format(int(frame_idx), int(class_idx), 0 if ids is None else int(ids[n]),
+                                                     float(x), float(y), float(z)))

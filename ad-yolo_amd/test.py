@@ -110,7 +110,10 @@ def test_epoch_audio(dataset, model, features, criterion, postprocessor, device,
     head (``postprocessor.select_device``: adyolo and the class-wise heads alike, with the post-processor's thresholds as they
     are at the call; launched after the graph replay, not recorded in it) and only the rows come back.
     device_scorer: a ``seld_metrics.DeviceSELDScorer`` the selected rows of every batch are also added to (the device rows
-    with device_select); the CSV files are written all the same, and the caller reads ``device_scorer.scores()``."""
+    with device_select); the CSV files are written all the same, and the caller reads ``device_scorer.scores()``.
+
+    Tracking (``test_epoch_corpus(track=...)``) is not taken here: the stage runs on rows that stay on the device, which only
+    the corpus passes keep there."""
     from . import ops
     from .datasets import audio_collate_fn
 
@@ -248,28 +251,62 @@ class _ViewMerge:
                              buf["rows"], buf["counts"], trim=trim)
 
 
-def _corpus_finish(corpus, acc, tta_status=None):
+class _Tracker:
+    """The device half of tracking for the corpus loops: a batch's selected (or merged) rows linked into tracks
+    (``LabelPostProcessor.track_device_rows``).  track: the dict of ``augmentations.track_options``.  The buffers are made once
+    per batch shape; ``status`` collects the ADYOLO_TRACK_* bits of the pass."""
+
+    def __init__(self, track, device):
+        missing = [k for k in ("gate_deg", "max_gap", "min_len", "smooth") if k not in track]
+        if missing:
+            raise ValueError("track: %r lacks %s (augmentations.track_options makes the dict)" % (track, missing))
+        self.opts = dict(track)
+        self.status = torch.zeros(1, dtype=torch.int32, device=device)
+        self._buffers = {}
+
+    def tracked(self, postprocessor, rows, counts, n_clips, trim):
+        """-> (rows', counts', ids) of the batch."""
+        from . import ops
+        key = counts.numel()
+        buf = self._buffers.get(key)
+        if buf is None:
+            buf = self._buffers[key] = ops.track_buffers(self.status.device, key, postprocessor.nb_classes)
+        return postprocessor.track_device_rows(rows, counts, n_clips, self.opts, buf=buf, status=self.status, trim=trim)
+
+
+def _corpus_finish(corpus, acc, tta_status=None, track_status=None):
     """The one synchronisation of a pass: the loss accumulator {sum, count} and the corpus status word -> the mean loss.
-    tta_status: the status word of a pass with test-time augmentation, read in the same copy."""
+    tta_status / track_status: the status words of a pass with test-time augmentation / tracking, read in the same copy."""
     from . import ops
-    acc_h, status_h, *tta_h = ops.to_host_many(acc, corpus.status, *([] if tta_status is None else [tta_status]))
+    more = [s for s in (tta_status, track_status) if s is not None]
+    acc_h, status_h, *more_h = ops.to_host_many(acc, corpus.status, *more)
     corpus.check(int(status_h[0]))
-    if tta_h:
-        ops.tta_status_check(int(tta_h[0][0]))
+    if tta_status is not None:
+        ops.tta_status_check(int(more_h[0][0]))
+    if track_status is not None:
+        ops.track_status_check(int(more_h[-1][0]))
     total, n = acc_h[0], int(acc_h[1])
     return float(total) / max(n, 1) if n else 0.0
 
 
-def _write_rows(output_pth, names, rows, counts):
-    """Selected device rows of ``len(names)`` clips (trimmed to their total) -> one CSV per clip."""
+def _write_rows(output_pth, names, rows, counts, ids=None):
+    """Selected device rows of ``len(names)`` clips (trimmed to their total) -> one CSV per clip.  ids: the rows' track ids
+    (tracking is on), written into the track column."""
     from . import ops
-    rows_h, counts_h = [t.numpy() for t in ops.to_host_many(rows, counts)]
-    for name, clip_rows in zip(names, group_rows(rows_h, counts_h, len(names))):
-        write_seld_output_file(os.path.join(output_pth, name + ".csv"), clip_rows)
+    if ids is None:
+        rows_h, counts_h = [t.numpy() for t in ops.to_host_many(rows, counts)]
+        for name, clip_rows in zip(names, group_rows(rows_h, counts_h, len(names))):
+            write_seld_output_file(os.path.join(output_pth, name + ".csv"), clip_rows)
+        return
+    from .postprocess import track_groups
+    rows_h, counts_h, ids_h = [t.numpy() for t in ops.to_host_many(rows, counts, ids)]
+    for name, clip_rows, clip_ids in zip(names, group_rows(rows_h, counts_h, len(names)),
+                                         track_groups(ids_h, counts_h, len(names))):
+        write_seld_output_file(os.path.join(output_pth, name + ".csv"), clip_rows, clip_ids)
 
 
 def test_epoch_corpus(corpus, model, features, criterion, postprocessor, output_pth=None, batch_size=8, forward=None,
-                      device_scorer=None, tta=None):
+                      device_scorer=None, tta=None, track=None):
     """``test_epoch_audio(device_select=True)`` from an HBM-resident split (``corpus.EvalDeviceCorpus``): the same batches,
     the same mean of per-clip losses (float32 adds in file order, clips without AD-YOLO rows left out), the same selected rows
     into ``device_scorer`` and, with ``output_pth``, the same CSV files -- but no WAV read, no CSV parse, no host label
@@ -284,7 +321,13 @@ def test_epoch_corpus(corpus, model, features, criterion, postprocessor, output_
     view -- ``corpus.launch_view`` into the same graph input, forward, decode, selection -- and the rows that go to the scorer
     and the files are the views' rows turned back and merged on the device (``postprocess.merge_view_rows``; csrc/select.hip).
     View 0 is the plain pass, so the loss is the plain pass's, the same float; the status word of the merge is read with the
-    loss (an overflow raises, naming the key to enlarge)."""
+    loss (an overflow raises, naming the key to enlarge).
+
+    track (tracks across frames): None, or the dict of ``augmentations.track_options``.  Every batch's rows -- the merged ones
+    with ``tta`` -- are then linked per (clip, class) into tracks on the device (``postprocess.track_rows``; csrc/track.hip):
+    directions smoothed, short gaps filled, short tracks dropped.  The tracked rows go to the scorer and the files, whose
+    third column carries the track ids; the loss is the plain pass's.  The status word is read with the loss (the caps of the
+    definition only warn).  None leaves the pass exactly as it is."""
     from . import ops
     model.eval()
     if output_pth is not None:
@@ -293,25 +336,30 @@ def test_epoch_corpus(corpus, model, features, criterion, postprocessor, output_
     corpus.reset_status()
     acc = ops.loss_accumulator(corpus.device)
     merge = _ViewMerge(tta, postprocessor, corpus.device) if tta is not None else None
+    tracker = _Tracker(track, corpus.device) if track is not None else None
+    trim = output_pth is not None
     with torch.no_grad():
         for idx in corpus.batches(batch_size):
             clips = [names[i] for i in idx]
             dec = _corpus_batch(corpus, idx, model, features, criterion, postprocessor, forward, acc)
             if merge is None:
-                rows, counts = postprocessor.select_device_rows(dec, len(clips), trim=output_pth is not None)
+                rows, counts = postprocessor.select_device_rows(dec, len(clips), trim=trim and tracker is None)
             else:
                 views = (dec if k == 0 else _corpus_view(corpus, idx, v, model, features, postprocessor, forward)
                          for k, v in enumerate(merge.views))
-                rows, counts = merge.merged(postprocessor, views, len(clips), trim=output_pth is not None)
+                rows, counts = merge.merged(postprocessor, views, len(clips), trim=trim and tracker is None)
+            ids = None
+            if tracker is not None:
+                rows, counts, ids = tracker.tracked(postprocessor, rows, counts, len(clips), trim=trim)
             if device_scorer is not None:
                 device_scorer.add_rows(rows, counts, clips)
             if output_pth is not None:
-                _write_rows(output_pth, clips, rows, counts)
-    return _corpus_finish(corpus, acc, None if merge is None else merge.status)
+                _write_rows(output_pth, clips, rows, counts, ids)
+    return _corpus_finish(corpus, acc, None if merge is None else merge.status, None if tracker is None else tracker.status)
 
 
 def sweep_conf_thresh_corpus(corpus, model, features, criterion, postprocessor, scorer, thresholds=None, output_pth=None,
-                             batch_size=8, forward=None, tta=None):
+                             batch_size=8, forward=None, tta=None, track=None):
     """``sweep_conf_thresh(device_select=True, device_score=True)`` from an HBM-resident split: ONE forward pass per batch,
     every batch's decode kept on the device, then per threshold the selections and the device scores (``scorer``: a
     ``seld_metrics.DeviceSELDScorer``); the chosen threshold is left set on the post-processor.  With ``output_pth`` the last
@@ -319,7 +367,10 @@ def sweep_conf_thresh_corpus(corpus, model, features, criterion, postprocessor, 
     loss (the host sweep cannot take them at all).  -> (new_thresh, [[ER, F, LE, LR, SELD] per threshold], mean loss)
 
     tta: as ``test_epoch_corpus``.  Every VIEW's decode of every batch is kept on the device, and each threshold selects,
-    collects and merges them again; the merge's status word is read once, after the last threshold."""
+    collects and merges them again; the merge's status word is read once, after the last threshold.
+
+    track: as ``test_epoch_corpus``.  Each threshold's rows (merged ones with ``tta``) are linked into tracks before they are
+    scored and written; the status word is read once, after the last threshold, in the copy that reads the merge's."""
     import numpy as np
     from . import ops
     from .seld_metrics import DeviceSELDScorer
@@ -333,6 +384,7 @@ def sweep_conf_thresh_corpus(corpus, model, features, criterion, postprocessor, 
     acc = ops.loss_accumulator(corpus.device)
     decoded = []
     merge = _ViewMerge(tta, postprocessor, corpus.device) if tta is not None else None
+    tracker = _Tracker(track, corpus.device) if track is not None else None
     with torch.no_grad():
         for idx in corpus.batches(batch_size):
             dec = _corpus_batch(corpus, idx, model, features, criterion, postprocessor, forward, acc)
@@ -351,19 +403,27 @@ def sweep_conf_thresh_corpus(corpus, model, features, criterion, postprocessor, 
         scorer.reset()
         for clips, dec in decoded:
             if merge is None:
-                rows, counts = postprocessor.select_device_rows(dec, len(clips), trim=write)
+                rows, counts = postprocessor.select_device_rows(dec, len(clips), trim=write and tracker is None)
             else:
-                rows, counts = merge.merged(postprocessor, dec, len(clips), trim=write)
+                rows, counts = merge.merged(postprocessor, dec, len(clips), trim=write and tracker is None)
+            ids = None
+            if tracker is not None:
+                rows, counts, ids = tracker.tracked(postprocessor, rows, counts, len(clips), trim=write)
             scorer.add_rows(rows, counts, clips)
             if write:
-                _write_rows(output_pth, clips, rows, counts)
+                _write_rows(output_pth, clips, rows, counts, ids)
         er, f, le, lr, seld = scorer.scores()[:5]
         table.append([er, f, le, lr, seld])
         if seld < best:
             new_thresh, best = th, seld
     postprocessor.set_conf_thresh(new_thresh)
-    if merge is not None:
+    if merge is not None and tracker is None:
         ops.tta_status_check(int(ops.to_host(merge.status)[0]))
+    elif tracker is not None:
+        words = [int(w[0]) for w in ops.to_host_many(*([merge.status] if merge is not None else []), tracker.status)]
+        if merge is not None:
+            ops.tta_status_check(words[0])
+        ops.track_status_check(words[-1])
     return new_thresh, table, loss
 
 
@@ -376,7 +436,10 @@ def infer_epoch_corpus(corpus, model, features, postprocessor, output_pth, forwa
     ``select_device_rows`` on the run (both selections work frame by frame) -> the rows and counts to the host, where
     ``corpus.split_pass_rows`` puts them on each recording's own frame axis.  One CSV per recording, named after the file, empty
     for a recording without rows or without a label frame.  No audio crosses PCIe; nothing is uploaded per pass.
-    -> {'recordings', 'windows', 'passes', 'frames'}."""
+    -> {'recordings', 'windows', 'passes', 'frames'}.
+
+    Tracking (``test_epoch_corpus(track=...)``) is not taken here: a run cuts recordings mid-way, and a track's pruning or
+    gap fill would have to reach back into rows already scored (carried state; a later change)."""
     from . import ops
     from .corpus import split_pass_rows
     model.eval()
@@ -478,7 +541,10 @@ def test_epoch_windows(corpus, model, features, criterion, postprocessor, output
     output_pth=None: nothing is written and the pass synchronises ONCE, at its end: one ``to_host_many`` of the loss
     accumulator and the corpus status word (the scorer's status is read by its ``scores()``).  With output_pth the rows of
     every pass go to the host (one synchronisation each) and one CSV is written per recording (``corpus.split_pass_rows``),
-    empty for a recording without rows or without a label frame.  Returns the mean loss."""
+    empty for a recording without rows or without a label frame.  Returns the mean loss.
+
+    Tracking (``test_epoch_corpus(track=...)``) is not taken here: a run cuts recordings mid-way, and a track's pruning or
+    gap fill would have to reach back into rows already scored (carried state; a later change)."""
     from . import ops
     model.eval()
     if output_pth is not None:
@@ -508,7 +574,10 @@ def sweep_conf_thresh_windows(corpus, model, features, criterion, postprocessor,
     """``sweep_conf_thresh_corpus`` through windows (``corpus.EvalWindowCorpus``): ONE forward pass per window pass, every
     pass's stitched run kept (cloned) on the device, then per threshold ``scorer.reset()``, the selection of every run and
     ``scorer.add_run``; the chosen threshold is left set on the post-processor.  With ``output_pth`` the last threshold's CSV
-    files are written.  The loss is ``test_epoch_windows``'s.  -> (new_thresh, [[ER, F, LE, LR, SELD] per threshold], mean loss)"""
+    files are written.  The loss is ``test_epoch_windows``'s.  -> (new_thresh, [[ER, F, LE, LR, SELD] per threshold], mean loss)
+
+    Tracking (``test_epoch_corpus(track=...)``) is not taken here: a run cuts recordings mid-way, and a track's pruning or
+    gap fill would have to reach back into rows already scored (carried state; a later change)."""
     import numpy as np
     from . import ops
     from .seld_metrics import DeviceSELDScorer

@@ -615,6 +615,43 @@ int  adyolo_tta_collect(const float *rows, long n_rows, const int *frame_counts,
 int  adyolo_tta_merge(const float *pool, const int *pool_counts, float *ws, float *rows, long capacity, int *frame_counts,
                       int *status, long n_frames, int C, int n_views, int P, float cos_t, int min_views, void *stream);
 
+/* Tracks (csrc/track.hip), opt-in: what postprocess.track_rows does on the host, bit for bit.  The rows a selection or
+ * adyolo_tta_merge left are linked per (clip, class) into tracks across frames: directions smoothed, gaps of up to max_gap
+ * frames filled, tracks of fewer than min_len hits dropped, tracks numbered; the result has the selection's layout.
+ *   rows / frame_counts  a selection as adyolo_yolo_select / adyolo_classwise_select / adyolo_tta_merge leave it: rows (capacity
+ *                n_rows, [frame, class, x, y, z]; the frame column is not read) and frame_counts [n_clips * t_clip], clip after
+ *                clip (the total behind them is not read)
+ *   ws           adyolo_track_workspace_words(n_clips * t_clip, C) words, 16-byte aligned; the caller initialises nothing
+ *   out_rows [capacity][5], out_ids [capacity] int32, out_counts [n_clips * t_clip + 1] int32 (the total last): the layout
+ *                adyolo_yolo_select writes, the frame column the index on the counts axis, and each row's track id;
+ *                capacity >= n_clips * t_clip * C * ADYOLO_TRACK_SLOTS, which no result exceeds
+ *   status       one int32 the kernels OR ADYOLO_TRACK_* bits into
+ * Every (clip, class) on its own; ADYOLO_TRACK_SLOTS slots, each empty or a track {id, s, first, last, hits}; next_id = 0.
+ * Per frame t of the clip: (1) the candidates are the class's rows of the frame in row order, the first ADYOLO_TRACK_MAX_DET of
+ * them (ADYOLO_TRACK_DET_OVERFLOW), u = p / sqrt((px*px + py*py) + pz*pz), a zero or non-finite norm dropped
+ * (ADYOLO_TRACK_BAD_VECTOR); (2) a slot with t - last - 1 > max_gap is closed, and closing a track with hits < min_len erases
+ * its cells of frames first .. last; (3) greedy rounds match the unmatched slot and candidate with the largest
+ * (s.x*u.x + s.y*u.y) + s.z*u.z > cos_gate (ties: the lowest slot, then the lowest candidate); (4) a matched slot gets
+ * m = unit((s * b) + (u * a)), the frames of the gap behind it unit((s * (1 - w)) + (m * w)), w = g / (gap + 1), then s = m,
+ * last = t, hits += 1; (5) the unmatched candidates in order open the lowest empty slots (s = u, id = next_id++), and one that
+ * finds none is dropped (ADYOLO_TRACK_SLOT_OVERFLOW).  The clip's end closes every slot.  Rows: frames ascending, classes
+ * ascending, slots ascending.  All float32, correctly rounded, no contraction.  cos_gate = cos of the gate angle, a the weight
+ * of the new direction, b = 1 - a, all rounded by the caller.  A frame whose count is negative or runs past n_rows has no rows,
+ * a row whose class is no integer in [0, C) is skipped: ADYOLO_TRACK_BAD_ROWS; nothing is read out of range.  Positions come
+ * from exclusive scans, never from atomics; no host synchronisation.
+ * EINVAL, before any launch: null or misaligned pointer, n_clips * t_clip < 1, C < 1, max_gap < 0, min_len < 1, cos_gate
+ * outside (0, 1), a outside (0, 1], too small a capacity; ENOSUP: 32-bit counts overflow. */
+#define ADYOLO_TRACK_SLOTS         8    /* concurrent tracks per clip and class */
+#define ADYOLO_TRACK_MAX_DET       64   /* detections considered per frame and class */
+#define ADYOLO_TRACK_DET_OVERFLOW  1    /* more than ADYOLO_TRACK_MAX_DET rows in one (frame, class): the first were taken */
+#define ADYOLO_TRACK_SLOT_OVERFLOW 2    /* a detection found no empty slot: dropped */
+#define ADYOLO_TRACK_BAD_VECTOR    4    /* a row whose vector has a zero or non-finite norm: dropped */
+#define ADYOLO_TRACK_BAD_ROWS      8    /* frame counts negative or past the rows given, or a class outside [0, C) */
+long adyolo_track_workspace_words(long n_frames, int C);
+int  adyolo_track_rows(const float *rows, long n_rows, const int *frame_counts, long n_clips, int t_clip, int C,
+                       float cos_gate, int max_gap, int min_len, float a, float b, float *ws, float *out_rows, int *out_ids,
+                       long capacity, int *out_counts, int *status, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Input pipeline around K1.
  *   adyolo_pcm16_to_f32: staged WAV samples int16 -> float, x / 32768 + 1e-8 (src/datasets.py:105, src/preprocess.py:104)

@@ -111,6 +111,9 @@ SIGNATURES = {
     "adyolo_tta_merge": (I, [P, P, P, P, L, P, P, L, I, I, I, F, I, P]),
     "adyolo_track_workspace_words": (L, [L, I]),
     "adyolo_track_rows": (I, [P, L, P, L, I, I, F, I, I, F, F, P, P, P, L, P, P, P]),
+    "adyolo_track_carry_words": (L, [I, I]),
+    "adyolo_track_run_workspace_words": (L, [L, I, I]),
+    "adyolo_track_run": (I, [P, L, P, L, P, L, I, F, I, I, F, F, I, P, P, P, P, L, P, P, P]),
     "adyolo_conv_gemm": (I, [P, P, P, P] + [I] * 13 + [P]),
     "adyolo_conv_gemm_plan": (I, [I] * 13 + [P]),
     "adyolo_pack_wk": (I, [P, P, I, I, I, I, I, P]),

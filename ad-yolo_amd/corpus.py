@@ -1038,6 +1038,35 @@ def plan_windows(label_frames, lengths, rec_start, hop, n_samples, window_frames
             "pass_frames": [int(v) for v in per[:, :, 4].sum(1).tolist()]}
 
 
+def plan_track(frame_start, pass_bounds, hold):
+    """``_WindowCorpus.track_plan`` in NumPy: frame_start (R + 1,) the recordings' first frames on the common axis,
+    pass_bounds (passes + 1,) the passes' bounds on it, hold D -> {'hold', 'bounds', 'pass_base', 'pass_frames',
+    'segments_host'}."""
+    start = np.asarray(frame_start, dtype=np.int64).reshape(-1)
+    b = np.asarray(pass_bounds, dtype=np.int64).reshape(-1)
+    hold = int(hold)
+    if hold < 0 or len(b) < 2 or b[0] != 0 or b[-1] != start[-1] or (np.diff(b) <= 0).any():
+        raise ValueError("plan_track: hold %d, pass bounds %s on %d frames" % (hold, b.tolist(), int(start[-1])))
+    rec = np.searchsorted(start, b, "right") - 1                     # the recording a bound lies in (the last one starting there)
+    rec = np.minimum(rec, len(start) - 2)
+    inside = (b != start[rec]) & (b != start[-1])
+    e = np.where(inside, np.maximum(b - hold, start[rec]), b)
+    tables = []
+    for p in range(len(b) - 1):
+        lo, hi = int(b[p]), int(b[p + 1])
+        rows = []
+        for r in range(int(np.searchsorted(start[1:], lo, "right")), len(start) - 1):
+            s, t = int(start[r]), int(start[r + 1])
+            if s >= hi:
+                break
+            if t > s:
+                a, z = max(s, lo), min(t, hi)
+                rows.append((a - lo, z - a, int(a > s), int(z < t)))
+        tables.append(np.asarray(rows, dtype=np.int32).reshape(-1, 4))
+    return {"hold": hold, "bounds": e, "pass_base": [int(v) for v in e[:-1].tolist()],
+            "pass_frames": [int(v) for v in np.diff(e).tolist()], "segments_host": tables}
+
+
 class _WindowCorpus(_CorpusBase):
     """What the two windowed corpora share: the window and margin arguments (``_window_setup``, before anything is uploaded),
     the window table (``plan_windows``) and its upload, ``pass_table`` and the gather of a pass."""
@@ -1090,6 +1119,29 @@ class _WindowCorpus(_CorpusBase):
     def _gather_pass(self, p, audio_out):
         audio = self._out(audio_out, (self.batch_size, self.n_samples, 4))
         return ops.corpus_gather_windows(self.pcm, self.pass_table(p), audio, self.status)
+
+    hold_block = 1                                       # the hold of ``track_plan`` is a whole multiple of this many frames
+
+    def track_plan(self, opts):
+        """Tracking through the passes (``postprocess.track_run``; ``test.test_epoch_windows(tracking=opts)``): built once per
+        (max_gap, min_len), its tables uploaded once; a pass uploads nothing.  The hold D is ``track_hold(max_gap, min_len)``
+        rounded up to ``hold_block`` frames.  Pass p walks the frames [b[p], b[p + 1]) of the common axis and EMITS [e[p], e[p
+        + 1]): a bound that is a recording's start or end stays, one inside a recording moves back by D, not past that
+        recording's start.  -> dict of
+          hold         D
+          bounds       e, int64 (passes + 1,), ascending (repeats: a pass that emits nothing)
+          pass_base, pass_frames   e[p] and e[p + 1] - e[p] per pass
+          segments_host            per pass the int32 (S, 4) table of ``track_run``: one row per recording with frames in the pass
+          segments                 the same tables on the device."""
+        from .postprocess import track_hold
+        key = (int(opts["max_gap"]), int(opts["min_len"]))
+        cache = self.__dict__.setdefault("_track_plans", {})
+        if key not in cache:
+            plan = plan_track(self.frame_start, self.pass_base + [int(self.frame_start[-1])],
+                              -(-track_hold(*key) // self.hold_block) * self.hold_block)
+            plan["segments"] = [torch.from_numpy(s).to(self.device) for s in plan["segments_host"]]
+            cache[key] = plan
+        return cache[key]
 
 
 class InferDeviceCorpus(_WindowCorpus):
@@ -1212,6 +1264,7 @@ class EvalWindowCorpus(_WindowCorpus):
         dc = params["data_config"]
         sr = self._window_setup(hc, params, window_s, margin_s, batch_size)
         self.frames_per_block = fpb = int(sr / int(sr * dc.get("label_hop_len_s", 0.1)))     # DeviceSELDScorer's block
+        self.hold_block = fpb                                        # emitted run bounds stay on block boundaries
         if self.window_frames % fpb or self.margin_frames % fpb:
             raise ValueError("EvalWindowCorpus: a window of %d label frames with a margin of %d: both must be whole multiples of "
                              "the scorer's block (%d frames)" % (self.window_frames, self.margin_frames, fpb))
@@ -1249,12 +1302,22 @@ class EvalWindowCorpus(_WindowCorpus):
         """The windows of pass ``p`` that belong to a recording (the others, at the end of the last pass, are empty)."""
         return max(0, min(self.batch_size, self.n_windows - p * self.batch_size))
 
-    def segments(self, scorer):
-        """``scorer.segment_tables`` for this corpus's passes: built and uploaded on the first call, cached per scorer."""
-        hit = self._segments.get(id(scorer))
+    def segments(self, scorer, bounds=None):
+        """``scorer.segment_tables`` for this corpus's passes: built and uploaded on the first call, cached per scorer.
+        bounds: other run bounds than the passes' (the emitted bounds of ``track_plan``; repeated ones, runs without a frame,
+        are dropped) -> one entry per pass, None for a pass whose run is empty."""
+        if bounds is None:
+            hit = self._segments.get(id(scorer))
+            if hit is None or hit[0] is not scorer:
+                hit = self._segments[id(scorer)] = (scorer, scorer.segment_tables(self.get_filelist(), self.label_frames,
+                                                                                  self.pass_bounds))
+            return hit[1]
+        bounds = [int(v) for v in np.asarray(bounds).reshape(-1).tolist()]
+        key = (id(scorer), tuple(bounds))
+        hit = self._segments.get(key)
         if hit is None or hit[0] is not scorer:
-            hit = self._segments[id(scorer)] = (scorer, scorer.segment_tables(self.get_filelist(), self.label_frames,
-                                                                              self.pass_bounds))
+            tables = iter(scorer.segment_tables(self.get_filelist(), self.label_frames, sorted(set(bounds))))
+            hit = self._segments[key] = (scorer, [next(tables) if hi > lo else None for lo, hi in zip(bounds, bounds[1:])])
         return hit[1]
 
     def launch(self, p, audio_out=None):

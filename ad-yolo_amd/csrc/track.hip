@@ -17,6 +17,12 @@
 //         program order, and the caller initialises nothing.
 //   emit  track_emit_kernel<false> counts the valid cells per frame, track_scan_kernel turns the counts into offsets, and
 //         track_emit_kernel<true> compacts the cells into rows [frame, class, x, y, z] and ids; grid order is output order.
+// The carried form, adyolo_track_run (postprocess.track_run on the device), links one run of a stream of recordings -- a pass of
+// a windowed evaluation -- and carries the state to the next call: track_run_plan_kernel first (the carry copied, the segment
+// table checked, the emitted window), then the same bin, the link as track_link_run_kernel with one wave per (segment, class),
+// and the emit over the emitted frames only.  Both link kernels are one text, track_link.hpp, compiled twice.  What makes it
+// exact: a fill reaches max_gap frames back and an erasure (min_len - 1) * (max_gap + 1) + 1, so a recording's frames further
+// back than the hold are final and can be emitted.
 // Every float operation is a correctly rounded float32 one in the host's order without contraction (the division and the
 // square root as adyolo_tta_merge writes them): rows, counts, ids and status are the host's bit for bit.
 #include "common.hpp"
@@ -156,147 +162,66 @@ __device__ __forceinline__ f32x4 trk_cell(float x, float y, float z, int id) {
     return v;
 }
 
-// grid: one wave per (clip, class)
-__global__ __launch_bounds__(TRK_WAVE) void track_link_kernel(const float *__restrict__ cand, const int *__restrict__ ncand,
-                                                             f32x4 *__restrict__ grid, long n_frames, int t_clip, int C,
-                                                             float cos_g, int max_gap, int min_len, float a, float b,
-                                                             int *__restrict__ status) {
-#pragma clang fp contract(off)
-    const int lane = threadIdx.x;
-    const long clip = blockIdx.x / C;
-    const int c = (int)(blockIdx.x - clip * C);
-    const long f0 = clip * t_clip;
-    const int *nc = ncand + (size_t)c * n_frames + f0;
-    const float *cd = cand + ((size_t)f0 * C + c) * TRK_CAND_WORDS;           // frame t: + t * C * TRK_CAND_WORDS
-    f32x4 *cells = grid + ((size_t)f0 * C + c) * TRK_SLOTS + (lane & (TRK_SLOTS - 1));   // frame t: + t * C * TRK_SLOTS
-    const size_t cand_step = (size_t)C * TRK_CAND_WORDS, cell_step = (size_t)C * TRK_SLOTS;
-    const f32x4 empty = trk_cell(0.f, 0.f, 0.f, -1);
-    // slot k's track, in lane k
-    bool occ = false;
-    int id = 0, first = 0, last = 0, hits = 0;
-    float sx = 0.f, sy = 0.f, sz = 0.f;
-    int next_id = 0, bits = 0;
-    // the candidates fetched ahead: the lengths of this block of 64 frames and of the next, the vectors of the next frame
-    int len_blk = 0, len_nxt = lane < t_clip ? nc[lane] : 0;
-    float px = 0.f, py = 0.f, pz = 0.f;
-    if (lane < trk_lane(len_nxt, 0)) px = cd[lane], py = cd[TRK_DET + lane], pz = cd[2 * TRK_DET + lane];
-    for (int t = 0; t < t_clip; ++t) {
-        if ((t & (TRK_WAVE - 1)) == 0) {
-            len_blk = len_nxt;
-            len_nxt = t + TRK_WAVE + lane < t_clip ? nc[t + TRK_WAVE + lane] : 0;
-            if (__ballot(len_blk != 0) == 0 && __ballot(occ) == 0) {
-                // silence: nothing arrives in these 64 frames and nothing is open.  All lanes clear the block's cells (no
-                // later write reaches back into it) and the walk goes on behind it, the first frame there fetched
-#pragma unroll
-                for (int i = 0; i < TRK_WAVE / TRK_SLOTS; ++i) {
-                    const int f = t + (lane >> 3) + TRK_SLOTS * i;
-                    if (f < t_clip) cells[(size_t)f * cell_step] = empty;
-                }
-                const int t1 = t + TRK_WAVE;
-                if (t1 < t_clip && lane < trk_lane(len_nxt, 0)) {
-                    const float *p = cd + (size_t)t1 * cand_step;
-                    px = p[lane], py = p[TRK_DET + lane], pz = p[2 * TRK_DET + lane];
-                }
-                t += TRK_WAVE - 1;
-                continue;
-            }
-        }
-        const int n = trk_lane(len_blk, t & (TRK_WAVE - 1));
-        const float ux = px, uy = py, uz = pz;
-        const int t1 = t + 1;
-        const int n1 = t1 >= t_clip ? 0 : (t1 & (TRK_WAVE - 1)) ? trk_lane(len_blk, t1 & (TRK_WAVE - 1)) : trk_lane(len_nxt, 0);
-        if (lane < n1) {
-            const float *p = cd + (size_t)t1 * cand_step;
-            px = p[lane], py = p[TRK_DET + lane], pz = p[2 * TRK_DET + lane];
-        }
-        f32x4 *cell = cells + (size_t)t * cell_step;
-        if (n == 0 && __ballot(occ) == 0) {                      // nothing arrives and nothing is open
-            if (lane < TRK_SLOTS) *cell = empty;
-            continue;
-        }
-        // 2. expire
-        if (occ && t - last - 1 > max_gap) {
-            if (hits < min_len)
-                for (int f = first; f <= last; ++f) cells[(size_t)f * cell_step] = empty;
-            occ = false;
-        }
-        bool hit = false;
-        unsigned long long cand_free = n >= TRK_WAVE ? ~0ull : trk_below(n);
-        const unsigned occ_mask = (unsigned)__ballot(occ);
-        if (n > 0 && occ_mask) {
-            // 3. associate: the eligible dots of candidate `lane` with every slot, as ordered keys (dot > cos_g > 0)
-            unsigned key[TRK_SLOTS];
-#pragma unroll
-            for (int k = 0; k < TRK_SLOTS; ++k) {
-                const float kx = trk_lane(sx, k), ky = trk_lane(sy, k), kz = trk_lane(sz, k);
-                const float d = (kx * ux + ky * uy) + kz * uz;
-                key[k] = (lane < n && ((occ_mask >> k) & 1u) && d > cos_g) ? __float_as_uint(d) : 0u;
-            }
-            for (;;) {
-                unsigned bv = 0;
-                int bk = 0;
-#pragma unroll
-                for (int k = 0; k < TRK_SLOTS; ++k)
-                    if (key[k] > bv) bv = key[k], bk = k;        // strictly larger: the lowest slot keeps a tie
-                const unsigned m = trk_wave_max(bv);
-                if (m == 0) break;
-                const unsigned who = trk_wave_max(bv == m ? (((unsigned)(TRK_SLOTS - 1 - bk) << 6) | (unsigned)(63 - lane)) + 1u : 0u) - 1u;
-                const int ks = TRK_SLOTS - 1 - (int)(who >> 6), js = 63 - (int)(who & 63u);
-#pragma unroll
-                for (int k = 0; k < TRK_SLOTS; ++k)
-                    if (k == ks || lane == js) key[k] = 0u;
-                cand_free &= ~(1ull << js);
-                // 4. update slot ks with candidate js (every lane forms m; lane ks keeps it)
-                const float kx = trk_lane(sx, ks), ky = trk_lane(sy, ks), kz = trk_lane(sz, ks);
-                const float vx = trk_lane(ux, js), vy = trk_lane(uy, js), vz = trk_lane(uz, js);
-                float mx = (kx * b) + (vx * a), my = (ky * b) + (vy * a), mz = (kz * b) + (vz * a);
-                const float nrm = sqrtf((mx * mx + my * my) + mz * mz);
-                mx = mx / nrm, my = my / nrm, mz = mz / nrm;
-                if (lane == ks) {
-                    const int gap = t - last - 1;
-                    for (int g = 1; g <= gap; ++g) {
-                        const float w = (float)g / (float)(gap + 1);
-                        const float w1 = 1.f - w;
-                        const float gx = (sx * w1) + (mx * w), gy = (sy * w1) + (my * w), gz = (sz * w1) + (mz * w);
-                        const float gn = sqrtf((gx * gx + gy * gy) + gz * gz);
-                        cells[(size_t)(last + g) * cell_step] = trk_cell(gx / gn, gy / gn, gz / gn, id);
-                    }
-                    sx = mx, sy = my, sz = mz;
-                    last = t;
-                    ++hits;
-                    hit = true;
-                }
-            }
-        }
-        // 5. open: the r-th unmatched candidate takes the r-th empty slot
-        if (cand_free) {
-            const unsigned free_slots = ~(unsigned)__ballot(occ) & ((1u << TRK_SLOTS) - 1u);
-            const int n_new = __popcll(cand_free), n_free = __popc(free_slots);
-            if (n_new > n_free) bits |= ADYOLO_TRACK_SLOT_OVERFLOW;
-            const int n_open = n_new < n_free ? n_new : n_free;
-            const int r = __popc(free_slots & ((1u << (lane & 31)) - 1u));
-            const bool opens = lane < TRK_SLOTS && !occ && r < n_open;
-            unsigned long long rest = cand_free;
-            for (int i = 0; i < TRK_SLOTS - 1; ++i)
-                if (i < r && opens) rest &= rest - 1ull;
-            const int j = opens ? (int)__builtin_ctzll(rest) : 0;
-            const float vx = __shfl(ux, j), vy = __shfl(uy, j), vz = __shfl(uz, j);
-            if (opens) {
-                occ = true;
-                id = next_id + r;
-                sx = vx, sy = vy, sz = vz;
-                first = last = t;
-                hits = 1;
-                hit = true;
-            }
-            next_id += n_open;
-        }
-        if (lane < TRK_SLOTS) *cell = hit ? trk_cell(sx, sy, sz, id) : empty;
+// The carry of the carried form (adyolo_track_run), all of one recording that goes on in the next run, per class so that a
+// class's wave reads and writes words of its own only:
+//   head  [C][4] int        {next_id, walked: the recording's frames walked so far, held = min(hold, walked), 0}
+//   slot  [C][8][8]         {occupied, id, first, last (on the recording's own frame axis), hits, s.x, s.y, s.z}
+//   cells [hold][C][8] f32x4  the held frames' cells, the last frame walked at hold - 1 (the first hold - held are not read)
+constexpr int TRK_HEAD_WORDS = 4, TRK_SLOT_WORDS = 8, TRK_WIN_WORDS = 4;
+__host__ __device__ inline long trk_carry_words(int C, int hold) {
+    return (long)C * (TRK_HEAD_WORDS + TRK_SLOTS * TRK_SLOT_WORDS) + (long)hold * C * TRK_SLOTS * 4;
+}
+
+#define TRK_CARRY 0
+#include "track_link.hpp"
+#undef TRK_CARRY
+#define TRK_CARRY 1
+#include "track_link.hpp"
+#undef TRK_CARRY
+
+// The carried form's first kernel, one block: the carry is copied to `snap` (the link kernel reads the copy and writes the
+// carry, so a run whose first segment continues and whose last is open needs no second buffer), the segment table and -- when
+// row 0 continues -- the carry's heads are checked, and win = {the grid frame the emitted frames start at, their number, 1 (0:
+// refused, ADYOLO_TRACK_BAD_ROWS, nothing is linked or emitted), 0}; the number also goes to n_emit [0].
+__global__ __launch_bounds__(TRK_SCAN_THREADS) void track_run_plan_kernel(const int *__restrict__ segs, int S, long run_frames,
+                                                                          int C, int hold, const float *__restrict__ carry,
+                                                                          float *__restrict__ snap, int *__restrict__ win,
+                                                                          int *__restrict__ n_emit, int *__restrict__ status) {
+    __shared__ int bad;
+    const int t = threadIdx.x;
+    if (t == 0) bad = 0;
+    const long words = trk_carry_words(C, hold);
+    for (long i = t; i < words; i += TRK_SCAN_THREADS) snap[i] = carry[i];
+    __syncthreads();
+    bool b = false;
+    for (int s = t; s < S; s += TRK_SCAN_THREADS) {
+        const long r0 = segs[4 * s], n = segs[4 * s + 1], cont = segs[4 * s + 2], open = segs[4 * s + 3];
+        const long before = s ? (long)segs[4 * s - 4] + segs[4 * s - 3] : 0;
+        b |= r0 != before || n < 1 || r0 < 0 || r0 + n > run_frames || (s == S - 1 && r0 + n != run_frames) ||
+             (cont != 0 && (cont != 1 || s != 0)) || (open != 0 && (open != 1 || s != S - 1));
     }
-    // the clip's end closes every slot
-    if (occ && hits < min_len)
-        for (int f = first; f <= last; ++f) cells[(size_t)f * cell_step] = empty;
-    if (__ballot(bits != 0) && lane == 0) atomicOr(status, ADYOLO_TRACK_SLOT_OVERFLOW);
+    const int *head = reinterpret_cast<const int *>(snap);
+    const bool cont = segs[2] == 1;
+    if (cont)
+        for (int c = t; c < C; c += TRK_SCAN_THREADS) {
+            const int next_id = head[4 * c], walked = head[4 * c + 1], held = head[4 * c + 2];
+            b |= next_id < 0 || walked < 0 || walked > (1 << 30) || held != (walked < hold ? walked : hold) || walked != head[1];
+        }
+    if (b) atomicOr(&bad, 1);
+    __syncthreads();
+    if (t == 0) {
+        if (bad) {
+            win[0] = hold, win[1] = 0, win[2] = 0, win[3] = 0;
+            n_emit[0] = 0;
+            atomicOr(status, ADYOLO_TRACK_BAD_ROWS);
+        } else {
+            const int held_in = cont ? head[2] : 0;
+            const long walked = (S == 1 && cont ? (long)head[1] : 0L) + segs[4 * (S - 1) + 1];
+            const int held_out = segs[4 * (S - 1) + 3] ? (int)(walked < hold ? walked : hold) : 0;
+            win[0] = hold - held_in, win[1] = (int)(held_in + run_frames - held_out), win[2] = 1, win[3] = 0;
+            n_emit[0] = win[1];
+        }
+    }
 }
 
 // grid: one wave per frame.  WRITE = false: cell_count[frame] = its valid cells; WRITE = true: they go to rows / ids at
@@ -329,6 +254,50 @@ __global__ __launch_bounds__(TRK_WAVE) void track_emit_kernel(const f32x4 *__res
             run += __popcll(bm);
         }
         if (!WRITE && lane == 0) cell_count[frame] = run;
+    }
+}
+
+// The carried form's emit (track_emit_kernel's frame loop with the frame's place and number given): one frame's cells `src`
+// [C][8], by one wave.  WRITE = false: -> the number of valid ones; WRITE = true: they go to rows / ids
+// from row at0 on, classes ascending, slots ascending, with `frame` in the frame column.
+template <bool WRITE>
+__device__ __forceinline__ int trk_emit_frame(const f32x4 *__restrict__ src, long at0, long frame, int n_cells,
+                                              float *__restrict__ rows, int *__restrict__ ids) {
+    const int lane = threadIdx.x;
+    int run = 0;
+    for (int i0 = 0; i0 < n_cells; i0 += TRK_WAVE) {
+        const int i = i0 + lane;
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        bool valid = false;
+        if (i < n_cells) {
+            v = src[i];
+            valid = __float_as_int(v[3]) >= 0;
+        }
+        const unsigned long long bm = __ballot(valid);
+        if (WRITE && valid) {
+            const long at = at0 + run + __popcll(bm & trk_below(lane));
+            float *d = rows + (size_t)at * 5;
+            d[0] = (float)frame, d[1] = (float)(i / TRK_SLOTS), d[2] = v[0], d[3] = v[1], d[4] = v[2];
+            ids[at] = __float_as_int(v[3]);
+        }
+        run += __popcll(bm);
+    }
+    return run;
+}
+
+// The carried form: emitted frame e is grid frame win[0] + e for e < win[1]; the frames behind them (n_out = hold + run_frames
+// in all) count no cell.
+template <bool WRITE>
+__global__ __launch_bounds__(TRK_WAVE) void track_emit_run_kernel(const f32x4 *__restrict__ grid, int *__restrict__ cell_count,
+                                                                 const int *__restrict__ cell_offs, float *__restrict__ rows,
+                                                                 int *__restrict__ ids, long n_out, int C,
+                                                                 const int *__restrict__ win) {
+    const int n_cells = C * TRK_SLOTS;
+    const long lo = win[0], n_emit = win[1];
+    for (long e = blockIdx.x; e < n_out; e += gridDim.x) {
+        int run = 0;
+        if (e < n_emit) run = trk_emit_frame<WRITE>(grid + (size_t)(lo + e) * n_cells, WRITE ? cell_offs[e] : 0, e, n_cells, rows, ids);
+        if (!WRITE && threadIdx.x == 0) cell_count[e] = run;
     }
 }
 
@@ -392,5 +361,81 @@ extern "C" int adyolo_track_rows(const float *rows, long n_rows, const int *fram
     if (rc) return rc;
     hipLaunchKernelGGL(track_emit_kernel<true>, eg, dim3(TRK_WAVE), 0, st, grid, cell_count, cell_offs, out_rows, out_ids,
                        n_frames, C);
+    return check_launch("track_emit_write");
+}
+
+extern "C" long adyolo_track_carry_words(int C, int hold) {
+    if (C <= 0 || hold < 0) return 0;
+    return trk_carry_words(C, hold);
+}
+
+extern "C" long adyolo_track_run_workspace_words(long run_frames, int C, int hold) {
+    if (run_frames <= 0 || C <= 0 || hold < 0) return 0;
+    const long n_out = run_frames + hold;
+    return n_out * C * 4L * TRK_SLOTS + trk_carry_words(C, hold) + run_frames * C * (TRK_CAND_WORDS + 1) + run_frames + 2 * n_out +
+           TRK_WIN_WORDS;
+}
+
+extern "C" int adyolo_track_run(const float *rows, long n_rows, const int *frame_counts, long run_frames, const int *segments,
+                                long n_segments, int C, float cos_gate, int max_gap, int min_len, float a, float b, int hold,
+                                float *carry, float *ws, float *out_rows, int *out_ids, long capacity, int *out_counts,
+                                int *status, void *stream) {
+    ADYOLO_REQUIRE(rows && frame_counts && segments && carry && ws && out_rows && out_ids && out_counts && status, ADYOLO_EINVAL,
+                   "track_run: null pointer");
+    ADYOLO_REQUIRE((((uintptr_t)rows | (uintptr_t)frame_counts | (uintptr_t)segments | (uintptr_t)out_rows | (uintptr_t)out_ids |
+                     (uintptr_t)out_counts | (uintptr_t)status) & 3) == 0 && (((uintptr_t)ws | (uintptr_t)carry) & 15) == 0,
+                   ADYOLO_EINVAL, "track_run: a pointer is not 4-byte aligned, or ws or carry not 16-byte aligned");
+    ADYOLO_REQUIRE(n_rows >= 0 && run_frames >= 1 && C >= 1 && n_segments >= 1 && n_segments <= run_frames, ADYOLO_EINVAL,
+                   "track_run: %ld rows, %ld frames x %d classes in %ld segments", n_rows, run_frames, C, n_segments);
+    ADYOLO_REQUIRE(max_gap >= 0 && min_len >= 1, ADYOLO_EINVAL, "track_run: max_gap %d, min_len %d", max_gap, min_len);
+    ADYOLO_REQUIRE(cos_gate > 0.f && cos_gate < 1.f, ADYOLO_EINVAL, "track_run: cos_gate %g outside (0, 1)", (double)cos_gate);
+    ADYOLO_REQUIRE(a > 0.f && a <= 1.f, ADYOLO_EINVAL, "track_run: smoothing weight %g outside (0, 1]", (double)a);
+    // what a write can reach back: a fill max_gap frames, the erasure of a track of min_len - 1 hits (postprocess.track_hold)
+    const long reach = min_len == 1 ? (long)max_gap : ((long)min_len - 1) * ((long)max_gap + 1) + 1;
+    ADYOLO_REQUIRE(hold >= reach, ADYOLO_EINVAL, "track_run: a hold of %d frames, max_gap %d and min_len %d reach back %ld", hold,
+                   max_gap, min_len, reach);
+    const long n_out = run_frames + hold;
+    ADYOLO_REQUIRE(n_out < (1L << 31) / ((long)C * TRK_SLOTS) && n_rows < (1L << 31) && n_segments < (1L << 31) / C, ADYOLO_ENOSUP,
+                   "track_run: %ld frames x %d classes x %d tracks or %ld rows do not fit 32-bit row counts", n_out, C, TRK_SLOTS,
+                   n_rows);
+    ADYOLO_REQUIRE(capacity >= n_out * C * TRK_SLOTS, ADYOLO_EINVAL, "track_run: %ld rows of capacity, %ld are needed", capacity,
+                   n_out * C * TRK_SLOTS);
+    const long n_slots = run_frames * C;
+    f32x4 *grid = reinterpret_cast<f32x4 *>(ws);
+    float *snap = ws + (size_t)n_out * C * 4 * TRK_SLOTS;
+    float *cand = snap + trk_carry_words(C, hold);
+    int *ncand = reinterpret_cast<int *>(cand + (size_t)n_slots * TRK_CAND_WORDS);
+    int *in_offs = ncand + n_slots;
+    int *cell_count = in_offs + run_frames;
+    int *cell_offs = cell_count + n_out;
+    int *win = cell_offs + n_out;
+    hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(track_run_plan_kernel, dim3(1), dim3(TRK_SCAN_THREADS), 0, st, segments, (int)n_segments, run_frames, C, hold,
+                       carry, snap, win, out_counts + n_out + 1, status);
+    int rc = check_launch("track_run_plan");
+    if (rc) return rc;
+    hipLaunchKernelGGL(track_scan_kernel<true>, dim3(1), dim3(TRK_SCAN_THREADS), 0, st, frame_counts, in_offs,
+                       static_cast<int *>(nullptr), run_frames, n_rows, status);
+    rc = check_launch("track_scan_rows");
+    if (rc) return rc;
+    hipLaunchKernelGGL(track_bin_kernel, dim3((unsigned)n_slots), dim3(TRK_WAVE), 0, st, rows, frame_counts, in_offs, cand, ncand,
+                       run_frames, C, status);
+    rc = check_launch("track_bin");
+    if (rc) return rc;
+    hipLaunchKernelGGL(track_link_run_kernel, dim3((unsigned)(n_segments * C)), dim3(TRK_WAVE), 0, st, cand, ncand, grid, run_frames,
+                       C, cos_gate, max_gap, min_len, a, b, status, segments, win, snap, carry, hold);
+    rc = check_launch("track_link_run");
+    if (rc) return rc;
+    const dim3 eg((unsigned)(n_out < 65536 ? n_out : 65536));
+    hipLaunchKernelGGL(track_emit_run_kernel<false>, eg, dim3(TRK_WAVE), 0, st, grid, cell_count, cell_offs, out_rows, out_ids,
+                       n_out, C, win);
+    rc = check_launch("track_emit_count");
+    if (rc) return rc;
+    hipLaunchKernelGGL(track_scan_kernel<false>, dim3(1), dim3(TRK_SCAN_THREADS), 0, st, cell_count, cell_offs, out_counts, n_out,
+                       0L, status);
+    rc = check_launch("track_emit_scan");
+    if (rc) return rc;
+    hipLaunchKernelGGL(track_emit_run_kernel<true>, eg, dim3(TRK_WAVE), 0, st, grid, cell_count, cell_offs, out_rows, out_ids,
+                       n_out, C, win);
     return check_launch("track_emit_write");
 }

@@ -1288,7 +1288,81 @@ def track_rows(rows, counts, n_clips, nb_classes, opts, buf=None, status=None, t
     return out[:total], out_counts[:frames], ids[:total]
 
 
-SELD_STATUS = ((1, "more than 1024 predictions in one frame and class"),      # ADYOLO_SELD_* in adyolo_hip.h
+def track_carry(device, nb_classes, hold):
+    """An empty carry for ``track_run``: the state of one stream of recordings between two runs (the open recording's slots,
+    next ids and held frames' cells), adyolo_hip.h ``adyolo_track_carry_words`` float32 words, all zero.  ``zero_()`` empties
+    it again."""
+    return torch.zeros(max(4, _lib.load().adyolo_track_carry_words(int(nb_classes), int(hold))), dtype=torch.float32,
+                       device=torch.device(device))
+
+
+def track_run_buffers(device, run_frames, nb_classes, hold):
+    """The buffers one run length of ``track_run`` needs, allocated once: {'ws', 'rows' ((hold + run_frames) * C * 8, 5)
+    float32, 'ids' int32, 'counts' (hold + run_frames + 2,) int32}."""
+    f, c, d = int(run_frames), int(nb_classes), int(hold)
+    dev = torch.device(device)
+    n = max(1, (f + d) * c * TRACK_SLOTS)
+    return {"ws": torch.empty(max(4, _lib.load().adyolo_track_run_workspace_words(f, c, d)), dtype=torch.float32, device=dev),
+            "rows": torch.empty((n, 5), dtype=torch.float32, device=dev), "ids": torch.empty(n, dtype=torch.int32, device=dev),
+            "counts": torch.empty(f + d + 2, dtype=torch.int32, device=dev)}
+
+
+def track_run(rows, counts, segments, nb_classes, opts, hold, carry, buf=None, status=None, trim=True, emitted=None):
+    """``track_rows`` on one run of a stream of recordings, the state carried in ``carry`` from call to call (adyolo_hip.h
+    ``adyolo_track_run``): ``postprocess.track_run`` bit for bit -> (rows' (N', 5), counts' (emitted frames,) int32, ids (N',)
+    int32) on the device.  rows / counts (run frames,) / opts / status / trim as ``track_rows``.  segments: (S, 4) int32 on the
+    device, {first frame in the run, frames, continues, open} per recording of the run (``corpus.track_plan`` uploads them
+    once).  hold: D >= ``postprocess.track_hold``.  carry: ``track_carry(device, nb_classes, hold)``, read and rewritten here.
+    buf: ``track_run_buffers`` of this run length.  emitted: the number of emitted frames when the caller knows it (the plan
+    does); None with trim=False returns all hold + run frames counts, zeros behind the emitted ones; trim=True reads the row
+    total and the emitted frames in one 8-byte copy."""
+    from .postprocess import track_cos
+    name = "track_run"
+    _chk(rows)
+    frames, c, d = int(counts.numel()), int(nb_classes), int(hold)
+    if rows.dim() != 2 or rows.shape[1] != 5:
+        raise _lib.AdyoloHipError("%s: rows %s are not (N, 5)" % (name, tuple(rows.shape)))
+    if not counts.is_cuda or counts.dtype != torch.int32 or not counts.is_contiguous() or counts.device != rows.device:
+        raise _lib.AdyoloHipError("%s: counts must be a contiguous int32 tensor on %s" % (name, rows.device))
+    if not torch.is_tensor(segments) or segments.dtype != torch.int32 or segments.dim() != 2 or segments.shape[1] != 4 \
+            or segments.shape[0] < 1 or not segments.is_contiguous() or segments.device != rows.device:
+        raise _lib.AdyoloHipError("%s: segments must be a contiguous (S >= 1, 4) int32 tensor on %s" % (name, rows.device))
+    if frames < 1 or c < 1 or d < 0:
+        raise _lib.AdyoloHipError("%s: %d frame counts, %d classes, hold %d" % (name, frames, c, d))
+    if buf is None:
+        buf = track_run_buffers(rows.device, frames, c, d)
+    own_status = status is None
+    if own_status:
+        status = torch.zeros(1, dtype=torch.int32, device=rows.device)
+    n_out = frames + d
+    need = n_out * c * TRACK_SLOTS
+    ws, out, ids, out_counts = buf["ws"], buf["rows"], buf["ids"], buf["counts"]
+    _chk(ws, out)
+    lib = _lib.load()
+    if ws.numel() < lib.adyolo_track_run_workspace_words(frames, c, d) or out.dim() != 2 or out.shape[1] != 5 \
+            or out.shape[0] < need or ids.numel() < need or out_counts.numel() != n_out + 2 \
+            or any(t.device != rows.device for t in (ws, out, ids, out_counts, status, carry)) \
+            or any(t.dtype != torch.int32 or not t.is_contiguous() for t in (ids, out_counts, status)) or status.numel() < 1 \
+            or carry.dtype != torch.float32 or not carry.is_contiguous() or carry.numel() < lib.adyolo_track_carry_words(c, d):
+        raise _lib.AdyoloHipError("%s: the buffers are not track_run_buffers(%s, %d, %d, %d) / carry not track_carry of that "
+                                  "shape / status no int32 word there" % (name, rows.device, frames, c, d))
+    a = np.float32(opts["smooth"])
+    _c("adyolo_track_run", _p(rows) if rows.numel() else _p(out), rows.shape[0], _p(counts), frames, _p(segments),
+       segments.shape[0], c, float(track_cos(opts["gate_deg"])), int(opts["max_gap"]), int(opts["min_len"]), float(a),
+       float(np.float32(np.float32(1) - a)), d, _p(carry), _p(ws), _p(out), _p(ids), out.shape[0], _p(out_counts), _p(status),
+       _stream())
+    if not trim:
+        return out, out_counts[:n_out if emitted is None else int(emitted)], ids
+    if own_status:
+        tail_h, status_h = to_host_many(out_counts[n_out:], status)
+        track_status_check(int(status_h[0]))
+    else:
+        tail_h = to_host(out_counts[n_out:])
+    total = int(tail_h[0])
+    return out[:total], out_counts[:int(tail_h[1]) if emitted is None else int(emitted)], ids[:total]
+
+
+SELD_STATUS =((1, "more than 1024 predictions in one frame and class"),      # ADYOLO_SELD_* in adyolo_hip.h
                (2, "more than 8 reference events in one frame and class"),
                (4, "frame counts negative or summing past the rows given"),
                (8, "a file index outside the reference table"),

@@ -492,6 +492,165 @@ def track_groups(ids, counts, n_clips=1):
     return outs
 
 
+# ---- Tracks through windows: the host definition of csrc/track.hip ``adyolo_track_run``.
+def track_hold(max_gap, min_len):
+    """H: how many frames behind the frame being walked ``track_rows`` can still write.  Step 4 fills at most max_gap frames
+    back.  A track that can still be erased has at most min_len - 1 hits, at most max_gap + 1 frames apart, and is closed in
+    frame last + max_gap + 2: t - first <= (min_len - 1) * (max_gap + 1) + 1.  With min_len 1 nothing is erased and H is max_gap.
+    Once the frames [0, e) of a recording are walked, every cell of a frame < e - H is final."""
+    max_gap, min_len = int(max_gap), int(min_len)
+    if max_gap < 0 or min_len < 1:
+        raise ValueError("track_hold: max_gap %r, min_len %r" % (max_gap, min_len))
+    return max_gap if min_len == 1 else (min_len - 1) * (max_gap + 1) + 1
+
+
+def track_run(rows, counts, segments, nb_classes, gate_deg, max_gap, min_len, smooth, hold, carry, trace=None):
+    """``track_rows`` on one run of frames of a stream of recordings, the state carried from run to run: a recording linked
+    through any number of runs gives, concatenated, the rows, counts and ids of ``track_rows(n_clips=1)`` on it whole, bit for
+    bit.  rows (N, 5) / counts (run frames,) as ``track_rows`` takes them.  segments: int (S, 4), one row per recording the run
+    holds frames of, {first frame in the run, frames (>= 1), continues, open}: the rows tile the run in order; ``continues``
+    (row 0 only): the recording's earlier frames were walked by the call that returned ``carry``; ``open`` (the last row
+    only): the recording goes on in the next run.  hold: D >= ``track_hold(max_gap, min_len)`` frames (not checked here: every
+    write is, see below).  carry: None (nothing to continue) or what the previous call returned.
+      * A continuing segment starts from the carried slots and next_id, its time running on from the carried frames; every other
+        segment starts empty at its first frame.  Per frame: steps 1 to 5 of ``track_rows``.
+      * A segment that is not open closes every slot at its end, as a clip's end does.  An open one keeps its slots, next_id and
+        the cells of its last min(D, frames walked so far in the recording) frames -- the held frames -- for the carry.
+      * Emitted: the carried held frames first (they are final now or held again), then the run's frames without the newly held
+        ones.  counts' runs over the emitted frames and rows' frame column is the index on that axis.
+    A write -- a gap fill or an erasure -- made while frame t is walked (t = the end for the closing there) that lands before
+    frame t - D raises AssertionError: D was smaller than the reach of these parameters.
+    -> ((rows', counts'), ids, status, carry').  carry' is empty when the last segment is not open; continuing from an empty
+    carry is starting fresh.  trace: as ``track_rows``, and {'carried_fills': gap fills written into held frames of an earlier
+    call, 'carried_prunes': erased cells that were held frames of an earlier call}."""
+    nb_classes, max_gap, min_len, hold = int(nb_classes), int(max_gap), int(min_len), int(hold)
+    counts = np.asarray(counts).reshape(-1)
+    run_frames = len(counts)
+    seg = np.asarray(segments, dtype=np.int64).reshape(-1, 4)
+    cos_g, a = track_cos(gate_deg), F32(smooth)
+    if max_gap < 0 or min_len < 1 or not 0 < float(gate_deg) < 90 or not 0 < cos_g < 1 or not 0 < a <= 1 or hold < 0:
+        raise ValueError("track_run: gate_deg %r, max_gap %r, min_len %r, smooth %r, hold %r"
+                         % (gate_deg, max_gap, min_len, smooth, hold))
+    ends = seg[:, 0] + seg[:, 1]
+    if run_frames < 1 or nb_classes < 1 or len(seg) < 1 or seg[0, 0] != 0 or (seg[:, 1] < 1).any() or ends[-1] != run_frames \
+            or (seg[1:, 0] != ends[:-1]).any() or not np.isin(seg[:, 2:], (0, 1)).all() or seg[1:, 2].any() or seg[:-1, 3].any():
+        raise ValueError("track_run: segments %s do not tile %d frames (continues on row 0, open on the last row only)"
+                         % (seg.tolist(), run_frames))
+    if carry is not None and (carry["hold"] != hold or carry["nb_classes"] != nb_classes):
+        raise ValueError("track_run: the carry was made with hold %d and %d classes" % (carry["hold"], carry["nb_classes"]))
+    b = F32(F32(1) - a)
+    cand, status = track_candidates(rows, counts, nb_classes)
+    seen = {"opened": 0, "pruned": 0, "pruned_fills": 0, "filled": 0, "reused": 0, "carried_fills": 0, "carried_prunes": 0}
+    empty = {"hold": hold, "nb_classes": nb_classes, "walked": 0, "held": 0, "slots": {}, "next_id": {}, "cells": {}}
+    carry = empty if carry is None else carry
+    cells = {}                                                     # (frame of the run, class, slot) -> (unit vector, id)
+    held_in = carry["held"] if seg[0, 2] else 0
+    out_carry = empty
+    for r0, n, cont, is_open in seg.tolist():
+        walked = carry["walked"] if cont else 0                    # the recording's frames before local frame 0
+        if cont:                                                   # (r0 == 0: the held frames sit at run frames -held .. -1)
+            cells.update(carry["cells"])
+        keep = {"hold": hold, "nb_classes": nb_classes, "walked": walked + n, "held": min(hold, walked + n), "slots": {},
+                "next_id": {}, "cells": {}}
+        for c in range(nb_classes):
+            slots = [None] * TRACK_SLOTS
+            next_id = 0
+            if cont:
+                slots = [None if s is None else [s[0], s[1], s[2] - walked, s[3] - walked, s[4]]
+                         for s in carry["slots"].get(c, slots)]
+                next_id = carry["next_id"].get(c, 0)
+
+            def held_line(f, t):
+                if f < t - hold:
+                    raise AssertionError("track_run: a write at frame %d while frame %d is walked reaches past the hold of %d "
+                                         "frames (track_hold(%d, %d) = %d)" % (f, t, hold, max_gap, min_len,
+                                                                                track_hold(max_gap, min_len)))
+
+            def close(k, t):
+                _, _, first, last, hits = slots[k]
+                if hits < min_len:
+                    gone = 0
+                    held_line(first, t)                            # (the track's first hit: the farthest cell it owns)
+                    for f in range(first, last + 1):
+                        if cells.pop((r0 + f, c, k), None) is not None:
+                            gone += 1
+                            seen["carried_prunes"] += f < 0
+                    seen["pruned"] += 1
+                    seen["pruned_fills"] += gone - hits
+                slots[k] = None
+
+            for t in range(n):
+                u = cand.get((r0 + t, c))
+                if u is None and not any(slots):
+                    continue
+                expired = set()
+                for k in range(TRACK_SLOTS):                       # 2. expire
+                    if slots[k] is not None and t - slots[k][3] - 1 > max_gap:
+                        close(k, t)
+                        expired.add(k)
+                if u is None:
+                    continue
+                occ = [k for k in range(TRACK_SLOTS) if slots[k] is not None]
+                cand_free = np.ones(len(u), dtype=bool)
+                if occ:                                            # 3. associate
+                    s = np.stack([slots[k][1] for k in occ])
+                    dot = (s[:, None, 0] * u[None, :, 0] + s[:, None, 1] * u[None, :, 1]) + s[:, None, 2] * u[None, :, 2]
+                    val = np.where(dot > cos_g, dot, F32(-np.inf))
+                    while True:
+                        at = int(np.argmax(val))
+                        i, j = divmod(at, len(u))
+                        if not val[i, j] > -np.inf:
+                            break
+                        val[i, :] = -np.inf
+                        val[:, j] = -np.inf
+                        cand_free[j] = False
+                        trk = slots[occ[i]]                        # 4. update
+                        k, sk, last = occ[i], trk[1], trk[3]
+                        m = _unit3((sk * b) + (u[j] * a))
+                        gap = t - last - 1
+                        for g in range(1, gap + 1):
+                            w = F32(g) / F32(gap + 1)
+                            held_line(last + g, t)
+                            cells[(r0 + last + g, c, k)] = (_unit3((sk * (F32(1) - w)) + (m * w)), trk[0])
+                            seen["carried_fills"] += last + g < 0
+                        seen["filled"] += gap
+                        cells[(r0 + t, c, k)] = (m, trk[0])
+                        trk[1], trk[3], trk[4] = m, t, trk[4] + 1
+                for j in np.flatnonzero(cand_free).tolist():       # 5. open
+                    k = next((k for k in range(TRACK_SLOTS) if slots[k] is None), None)
+                    if k is None:
+                        status |= TRACK_SLOT_OVERFLOW
+                        break
+                    slots[k] = [next_id, u[j], t, t, 1]
+                    cells[(r0 + t, c, k)] = (u[j], next_id)
+                    next_id += 1
+                    seen["opened"] += 1
+                    seen["reused"] += k in expired
+            if is_open:
+                keep["slots"][c] = [None if s is None else [s[0], s[1], s[2] + walked, s[3] + walked, s[4]] for s in slots]
+                keep["next_id"][c] = next_id
+            else:
+                for k in range(TRACK_SLOTS):
+                    if slots[k] is not None:
+                        close(k, n)
+        if is_open:                                                # the newly held frames leave the run for the carry
+            for key in [key for key in cells if key[0] >= run_frames - keep["held"]]:
+                keep["cells"][(key[0] - run_frames, key[1], key[2])] = cells.pop(key)
+            out_carry = keep
+    n_emit = held_in + run_frames - out_carry["held"]
+    keys = sorted(cells)
+    out = np.zeros((len(keys), 5), dtype=F32)
+    ids = np.zeros(len(keys), dtype=np.int32)
+    out_counts = np.zeros(n_emit, dtype=np.int32)
+    for i, key in enumerate(keys):
+        vec, tid = cells[key]
+        out[i, 0], out[i, 1], out[i, 2:5], ids[i] = key[0] + held_in, key[1], vec, tid
+        out_counts[key[0] + held_in] += 1
+    if trace is not None:
+        trace.update(seen)
+    return (out, out_counts), ids, status, out_carry
+
+
 class LabelPostProcessor:
     """``LabelPostProcessor(params).postprocess(output)`` for the adyolo head (decode + NMS) and the class-wise heads
     (``--loss seddoa | masked-seddoa | accdoa | adpit``); ``output`` (1, T', K) on the GPU."""
@@ -573,6 +732,14 @@ class LabelPostProcessor:
         the device.  opts: ``augmentations.track_options``; buf / status / trim as ``ops.track_rows``."""
         from . import ops
         return ops.track_rows(rows, counts, n_clips, self.nb_classes, opts, buf=buf, status=status, trim=trim)
+
+    def track_device_run(self, rows, counts, segments, opts, hold, carry, buf=None, status=None, trim=True, emitted=None):
+        """``track_run`` on the device (``ops.track_run``; the same rows, counts and ids bit for bit) on what
+        ``select_device_rows`` returns for one stitched run of a windowed pass -> (rows', counts', ids) of the emitted frames,
+        all on the device.  segments / hold: ``corpus.track_plan``; carry: ``ops.track_carry``; the rest as ``ops.track_run``."""
+        from . import ops
+        return ops.track_run(rows, counts, segments, self.nb_classes, opts, hold, carry, buf=buf, status=status, trim=trim,
+                             emitted=emitted)
 
     def select_device(self, decoded_dev, n_clips=1):
         """``select_device_rows`` -> one {frame: [[class, x, y, z], ...]} per clip.  Only the selected rows and the per-frame

@@ -274,6 +274,41 @@ class _Tracker:
         return postprocessor.track_device_rows(rows, counts, n_clips, self.opts, buf=buf, status=self.status, trim=trim)
 
 
+class _RunTracker:
+    """The device half of tracking through windows: every pass's selected rows linked into tracks with the state carried from
+    pass to pass (``LabelPostProcessor.track_device_run``), after ``corpus.track_plan(tracking)``.  tracking: the dict of
+    ``augmentations.track_options``.  The buffers are made once per run length, the carry once; ``status`` collects the
+    ADYOLO_TRACK_* bits.  ``reset()`` empties the carry: before a split is walked again from its first pass."""
+
+    def __init__(self, tracking, corpus):
+        missing = [k for k in ("gate_deg", "max_gap", "min_len", "smooth") if k not in tracking]
+        if missing:
+            raise ValueError("tracking: %r lacks %s (augmentations.track_options makes the dict)" % (tracking, missing))
+        self.opts = dict(tracking)
+        self.plan = corpus.track_plan(self.opts)
+        self.hold = self.plan["hold"]
+        self.status = torch.zeros(1, dtype=torch.int32, device=corpus.device)
+        self.carry = None
+        self._buffers = {}
+
+    def reset(self):
+        if self.carry is not None:
+            self.carry.zero_()
+
+    def tracked(self, postprocessor, p, rows, counts, trim):
+        """Pass ``p``'s selected (rows, counts) -> (rows', counts', ids) of the frames the pass emits (``plan['pass_frames'][p]``
+        of them, from ``plan['pass_base'][p]`` on the common axis)."""
+        from . import ops
+        if self.carry is None:
+            self.carry = ops.track_carry(self.status.device, postprocessor.nb_classes, self.hold)
+        key = counts.numel()
+        buf = self._buffers.get(key)
+        if buf is None:
+            buf = self._buffers[key] = ops.track_run_buffers(self.status.device, key, postprocessor.nb_classes, self.hold)
+        return postprocessor.track_device_run(rows, counts, self.plan["segments"][p], self.opts, self.hold, self.carry, buf=buf,
+                                              status=self.status, trim=trim, emitted=self.plan["pass_frames"][p])
+
+
 def _corpus_finish(corpus, acc, tta_status=None, track_status=None):
     """The one synchronisation of a pass: the loss accumulator {sum, count} and the corpus status word -> the mean loss.
     tta_status / track_status: the status words of a pass with test-time augmentation / tracking, read in the same copy."""
@@ -427,7 +462,7 @@ def sweep_conf_thresh_corpus(corpus, model, features, criterion, postprocessor, 
     return new_thresh, table, loss
 
 
-def infer_epoch_corpus(corpus, model, features, postprocessor, output_pth, forward=None):
+def infer_epoch_corpus(corpus, model, features, postprocessor, output_pth, forward=None, tracking=None):
     """Inference on recordings of any length from an HBM-resident folder (``corpus.InferDeviceCorpus``): every recording cut
     into overlapping windows of one shape, the windows run ``corpus.batch_size`` at a time -- so the whole folder has ONE input
     shape and, with ``forward`` (``graph.ForwardGraphs``), one recorded graph.  Per pass: ``adyolo_corpus_gather_windows`` (into
@@ -438,8 +473,14 @@ def infer_epoch_corpus(corpus, model, features, postprocessor, output_pth, forwa
     for a recording without rows or without a label frame.  No audio crosses PCIe; nothing is uploaded per pass.
     -> {'recordings', 'windows', 'passes', 'frames'}.
 
-    Tracking (``test_epoch_corpus(track=...)``) is not taken here: a run cuts recordings mid-way, and a track's pruning or
-    gap fill would have to reach back into rows already scored (carried state; a later change)."""
+    Tracking (``tracking``: None, or the dict of ``augmentations.track_options``): every pass's selected rows are linked into
+    tracks on the device with the state carried from pass to pass (``postprocess.track_run``; csrc/track.hip
+    ``adyolo_track_run``), so a recording cut by any number of passes gets the rows and ids ``postprocess.track_rows`` gives on
+    it whole, bit for bit.  A pass then emits its frames without the last D of a recording that goes on in the next pass -- a
+    gap fill or the erasure of a short track can still reach them -- and with the D it held back before
+    (``corpus.track_plan``, D = ``postprocess.track_hold``).  The emitted rows go to the files, whose third column carries the
+    track ids; the status word is read with the corpus's at the end (the caps of the definition only warn).  None leaves
+    every call, allocation and bit as it is."""
     from . import ops
     from .corpus import split_pass_rows
     model.eval()
@@ -448,6 +489,8 @@ def infer_epoch_corpus(corpus, model, features, postprocessor, output_pth, forwa
     corpus.reset_status()
     b, n, wf = corpus.batch_size, corpus.n_samples, corpus.window_frames
     outs = [{} for _ in names]
+    tracker = _RunTracker(tracking, corpus) if tracking is not None else None
+    out_ids = [{} for _ in names] if tracker is not None else None
     stitched = None
     with torch.no_grad():
         for p in range(corpus.n_passes):
@@ -469,13 +512,23 @@ def infer_epoch_corpus(corpus, model, features, postprocessor, output_pth, forwa
                 stitched = torch.empty_like(dec)
             frames = corpus.pass_frames[p]
             ops.decode_stitch(dec, corpus.pass_table(p), wf, corpus.pass_base[p], stitched, corpus.status)
+            if tracker is not None:
+                rows, counts = postprocessor.select_device_rows(stitched[:frames], 1, trim=False)
+                rows, counts, ids = tracker.tracked(postprocessor, p, rows, counts, trim=True)
+                if counts.numel():
+                    _write_pass_tracks(corpus, tracker.plan["pass_base"][p], rows, counts, ids, outs, out_ids)
+                continue
             rows, counts = postprocessor.select_device_rows(stitched[:frames], 1)
             rows_h, counts_h = [t.numpy() for t in ops.to_host_many(rows, counts)]
             for r, found in split_pass_rows(rows_h, counts_h, corpus.pass_base[p], corpus.frame_start).items():
                 outs[r].update(found)                                        # (a recording's passes come in frame order)
-    corpus.check()
-    for name, rows in zip(names, outs):
-        write_seld_output_file(os.path.join(output_pth, name + ".csv"), rows)
+    if tracker is None:
+        corpus.check()
+    else:
+        status_h, track_h = ops.to_host_many(corpus.status, tracker.status)
+        corpus.check(int(status_h[0]))
+        ops.track_status_check(int(track_h[0]))
+    _write_recordings(output_pth, names, outs, out_ids)
     return {"recordings": len(names), "windows": corpus.n_windows, "passes": corpus.n_passes,
             "frames": int(corpus.frame_start[-1])}
 
@@ -522,7 +575,29 @@ def _write_pass_rows(corpus, p, rows, counts, outs):
         outs[r].update(found)                                                # (a recording's passes come in frame order)
 
 
-def test_epoch_windows(corpus, model, features, criterion, postprocessor, output_pth=None, forward=None, device_scorer=None):
+def _write_pass_tracks(corpus, base, rows, counts, ids, outs, out_ids):
+    """``_write_pass_rows`` for a tracked pass: the emitted run starts at ``base`` on the common axis, and the rows' track ids go
+    to ``out_ids`` {frame of the recording: [id, ...]} per recording, parallel to ``outs``."""
+    import numpy as np
+    from . import ops
+    from .corpus import split_pass_rows
+    rows_h, counts_h, ids_h = [t.numpy() for t in ops.to_host_many(rows, counts, ids)]
+    for r, found in split_pass_rows(rows_h, counts_h, base, corpus.frame_start).items():
+        outs[r].update(found)
+    ends = np.cumsum(counts_h.astype(np.int64))
+    ids_h = ids_h.tolist()
+    for f in np.flatnonzero(counts_h).tolist():
+        r = int(np.searchsorted(corpus.frame_start, base + f, "right")) - 1
+        out_ids[r][base + f - int(corpus.frame_start[r])] = ids_h[int(ends[f]) - int(counts_h[f]):int(ends[f])]
+
+
+def _write_recordings(output_pth, names, outs, out_ids=None):
+    for k, (name, rows) in enumerate(zip(names, outs)):
+        write_seld_output_file(os.path.join(output_pth, name + ".csv"), rows, None if out_ids is None else out_ids[k])
+
+
+def test_epoch_windows(corpus, model, features, criterion, postprocessor, output_pth=None, forward=None, device_scorer=None,
+                       tracking=None):
     """Labelled evaluation of recordings of ANY length from an HBM-resident split (``corpus.EvalWindowCorpus``): every recording
     cut into overlapping windows of one shape, ``corpus.batch_size`` windows per pass -- one input shape for the whole split
     and, with ``forward`` (``graph.ForwardGraphs``), one recorded graph.  Per pass: ``corpus.launch`` (audio into the graph's
@@ -543,8 +618,14 @@ def test_epoch_windows(corpus, model, features, criterion, postprocessor, output
     every pass go to the host (one synchronisation each) and one CSV is written per recording (``corpus.split_pass_rows``),
     empty for a recording without rows or without a label frame.  Returns the mean loss.
 
-    Tracking (``test_epoch_corpus(track=...)``) is not taken here: a run cuts recordings mid-way, and a track's pruning or
-    gap fill would have to reach back into rows already scored (carried state; a later change)."""
+    Tracking (``tracking``: None, or the dict of ``augmentations.track_options``): every pass's selected rows are linked into
+    tracks on the device with the state carried from pass to pass (``postprocess.track_run``; csrc/track.hip
+    ``adyolo_track_run``), so a recording cut by any number of passes gets the rows and ids ``postprocess.track_rows`` gives on
+    it whole, bit for bit.  A pass then emits its frames without the last D of a recording that goes on in the next pass -- a
+    gap fill or the erasure of a short track can still reach them -- and with the D it held back before
+    (``corpus.track_plan``).  The emitted rows go to the scorer (its segment tables on the emitted bounds) and to the files,
+    whose third column carries the track ids; the status word is read in the one end-of-pass copy (the caps of the definition
+    only warn).  None leaves every call, allocation and bit as it is.  Test-time augmentation is not taken here."""
     from . import ops
     model.eval()
     if output_pth is not None:
@@ -552,32 +633,47 @@ def test_epoch_windows(corpus, model, features, criterion, postprocessor, output
     names = corpus.get_filelist()
     corpus.reset_status()
     acc = ops.loss_accumulator(corpus.device)
-    segments = corpus.segments(device_scorer) if device_scorer is not None else None
+    tracker = _RunTracker(tracking, corpus) if tracking is not None else None
+    bounds = None if tracker is None else tracker.plan["bounds"]
+    segments = corpus.segments(device_scorer, bounds=bounds) if device_scorer is not None else None
     outs = [{} for _ in names]
+    out_ids = [{} for _ in names] if tracker is not None else None
     stitched = None
     with torch.no_grad():
         for p in range(corpus.n_passes):
             stitched, run = _window_pass(corpus, p, model, features, criterion, postprocessor, forward, acc, stitched)
-            rows, counts = postprocessor.select_device_rows(run, 1, trim=output_pth is not None)
+            rows, counts = postprocessor.select_device_rows(run, 1, trim=output_pth is not None and tracker is None)
+            if tracker is not None:
+                rows, counts, ids = tracker.tracked(postprocessor, p, rows, counts, trim=output_pth is not None)
+                if not counts.numel():                                       # the pass holds all its frames back
+                    continue
             if device_scorer is not None:
                 device_scorer.add_run(rows, counts, segments[p])
-            if output_pth is not None:
+            if output_pth is not None and tracker is None:
                 _write_pass_rows(corpus, p, rows, counts, outs)
+            elif output_pth is not None:
+                _write_pass_tracks(corpus, tracker.plan["pass_base"][p], rows, counts, ids, outs, out_ids)
     if output_pth is not None:
-        for name, rows in zip(names, outs):
-            write_seld_output_file(os.path.join(output_pth, name + ".csv"), rows)
-    return _corpus_finish(corpus, acc)
+        _write_recordings(output_pth, names, outs, out_ids)
+    return _corpus_finish(corpus, acc, track_status=None if tracker is None else tracker.status)
 
 
 def sweep_conf_thresh_windows(corpus, model, features, criterion, postprocessor, scorer, thresholds=None, output_pth=None,
-                              forward=None):
+                              forward=None, tracking=None):
     """``sweep_conf_thresh_corpus`` through windows (``corpus.EvalWindowCorpus``): ONE forward pass per window pass, every
     pass's stitched run kept (cloned) on the device, then per threshold ``scorer.reset()``, the selection of every run and
     ``scorer.add_run``; the chosen threshold is left set on the post-processor.  With ``output_pth`` the last threshold's CSV
     files are written.  The loss is ``test_epoch_windows``'s.  -> (new_thresh, [[ER, F, LE, LR, SELD] per threshold], mean loss)
 
-    Tracking (``test_epoch_corpus(track=...)``) is not taken here: a run cuts recordings mid-way, and a track's pruning or
-    gap fill would have to reach back into rows already scored (carried state; a later change)."""
+    Tracking (``tracking``: None, or the dict of ``augmentations.track_options``): every pass's selected rows are linked into
+    tracks on the device with the state carried from pass to pass (``postprocess.track_run``; csrc/track.hip
+    ``adyolo_track_run``), so a recording cut by any number of passes gets the rows and ids ``postprocess.track_rows`` gives on
+    it whole, bit for bit.  A pass then emits its frames without the last D of a recording that goes on in the next pass -- a
+    gap fill or the erasure of a short track can still reach them -- and with the D it held back before
+    (``corpus.track_plan``).  Per threshold the carry is emptied with the scorer; the emitted rows go to the scorer (its segment
+    tables on the emitted bounds) and, for the last threshold, to the files, whose third column carries the track ids; the
+    status word is read once, after the last threshold (the caps of the definition only warn).  None leaves every call,
+    allocation and bit as it is.  Test-time augmentation is not taken here."""
     import numpy as np
     from . import ops
     from .seld_metrics import DeviceSELDScorer
@@ -589,7 +685,8 @@ def sweep_conf_thresh_windows(corpus, model, features, criterion, postprocessor,
     names = corpus.get_filelist()
     corpus.reset_status()
     acc = ops.loss_accumulator(corpus.device)
-    segments = corpus.segments(scorer)
+    tracker = _RunTracker(tracking, corpus) if tracking is not None else None
+    segments = corpus.segments(scorer, bounds=None if tracker is None else tracker.plan["bounds"])
     runs, stitched = [], None
     with torch.no_grad():
         for p in range(corpus.n_passes):
@@ -601,21 +698,31 @@ def sweep_conf_thresh_windows(corpus, model, features, criterion, postprocessor,
         postprocessor.set_conf_thresh(th)
         write = output_pth is not None and k == len(thresholds) - 1
         outs = [{} for _ in names]
+        out_ids = [{} for _ in names] if tracker is not None else None
         scorer.reset()
+        if tracker is not None:
+            tracker.reset()
         for p, run in enumerate(runs):
-            rows, counts = postprocessor.select_device_rows(run, 1, trim=write)
+            rows, counts = postprocessor.select_device_rows(run, 1, trim=write and tracker is None)
+            if tracker is not None:
+                rows, counts, ids = tracker.tracked(postprocessor, p, rows, counts, trim=write)
+                if not counts.numel():
+                    continue
             scorer.add_run(rows, counts, segments[p])
-            if write:
+            if write and tracker is None:
                 _write_pass_rows(corpus, p, rows, counts, outs)
+            elif write:
+                _write_pass_tracks(corpus, tracker.plan["pass_base"][p], rows, counts, ids, outs, out_ids)
         if write:
             delete_and_create_folder(output_pth)
-            for name, rows in zip(names, outs):
-                write_seld_output_file(os.path.join(output_pth, name + ".csv"), rows)
+            _write_recordings(output_pth, names, outs, out_ids)
         er, f, le, lr, seld = scorer.scores()[:5]
         table.append([er, f, le, lr, seld])
         if seld < best:
             new_thresh, best = th, seld
     postprocessor.set_conf_thresh(new_thresh)
+    if tracker is not None:
+        ops.track_status_check(int(ops.to_host(tracker.status)[0]))
     return new_thresh, table, loss
 
 

@@ -652,6 +652,35 @@ int  adyolo_track_rows(const float *rows, long n_rows, const int *frame_counts, 
                        float cos_gate, int max_gap, int min_len, float a, float b, float *ws, float *out_rows, int *out_ids,
                        long capacity, int *out_counts, int *status, void *stream);
 
+/* Tracks through runs (csrc/track.hip), opt-in: what postprocess.track_run does on the host, bit for bit -- adyolo_track_rows
+ * on a stream of recordings that arrives in runs of frames (the passes of a windowed evaluation), the state carried from one
+ * call to the next.  A recording linked through any number of runs gives, concatenated, what adyolo_track_rows gives on it
+ * whole (n_clips = 1): rows, counts, ids, status bits.
+ *   rows / frame_counts [run_frames]  as adyolo_track_rows
+ *   segments     [n_segments][4] int32 ON THE DEVICE, one row per recording the run holds frames of: {first frame in the run,
+ *                frames (>= 1), continues, open}.  The rows tile the run in order.  continues (row 0 only): the recording's
+ *                earlier frames were walked by the call that left `carry`; open (the last row only): it goes on in the next run
+ *   hold         D >= H frames, H = max_gap for min_len 1, else (min_len - 1) * (max_gap + 1) + 1: how far behind the frame
+ *                being walked a gap fill or the erasure of a short track can write (postprocess.track_hold)
+ *   carry        adyolo_track_carry_words(C, hold) words, 16-byte aligned, all zero before a stream's first call, otherwise
+ *                untouched by the caller: read when row 0 continues, written by every call (emptied when the last row is not open)
+ *   ws           adyolo_track_run_workspace_words(run_frames, C, hold) words, 16-byte aligned; the caller initialises nothing
+ *   out_rows [capacity][5], out_ids [capacity], capacity >= (hold + run_frames) * C * ADYOLO_TRACK_SLOTS
+ *   out_counts   [hold + run_frames + 2] int32: the EMITTED frames' counts, zeros behind them, at [hold + run_frames] the row
+ *                total, at [hold + run_frames + 1] the number of emitted frames
+ * One wave per (segment, class).  A continuing segment starts from the carried slots and next_id, every other one empty.  A
+ * segment that is not open closes every slot at its end, as a clip's end does.  An open one keeps its slots, next_id and the
+ * cells of its last min(D, frames walked so far in the recording) frames -- the held frames -- in the carry.  Emitted: the
+ * carried held frames first, then the run's frames without the newly held ones; the frame column is the index among them.
+ * On the device, ADYOLO_TRACK_BAD_ROWS and nothing linked or emitted: a segment table that does not tile the run or carries a
+ * flag on another row than stated, or (row 0 continuing) a carry no call leaves behind; nothing is read out of range.
+ * EINVAL, before any launch: as adyolo_track_rows, and n_segments outside [1, run_frames], hold < H; ENOSUP: 32-bit counts. */
+long adyolo_track_carry_words(int C, int hold);
+long adyolo_track_run_workspace_words(long run_frames, int C, int hold);
+int  adyolo_track_run(const float *rows, long n_rows, const int *frame_counts, long run_frames, const int *segments,
+                      long n_segments, int C, float cos_gate, int max_gap, int min_len, float a, float b, int hold, float *carry,
+                      float *ws, float *out_rows, int *out_ids, long capacity, int *out_counts, int *status, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Input pipeline around K1.
  *   adyolo_pcm16_to_f32: staged WAV samples int16 -> float, x / 32768 + 1e-8 (src/datasets.py:105, src/preprocess.py:104)

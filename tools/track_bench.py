@@ -19,7 +19,17 @@ each.
            default keys, against the generator's clean cells.  An illustration on synthetic flicker: it says nothing about a
            trained model and sets no threshold.
 
-  python tools/track_bench.py [--part stages|epoch|value|all] [--dir /tmp/adyolo_track_bench] [--clips 16] [--batch 8]
+  windows  (--windows, or --part windows; not part of ``all``) tracks carried through windows.  (a) ``ops.track_run`` over ONE
+           recording of --recording-s seconds cut into the passes of the window plan (--window / --margin seconds, --batch windows
+           a pass; ``corpus.window_plan`` and ``corpus.plan_track`` with the scorer's block of 10), all passes between the events
+           (given buffers, trim=False, the emitted frames known: no allocation, no synchronisation), against ``ops.track_rows``
+           on the same recording whole: ms per recording, the difference per pass, and the link stage's share per frame step
+           as the whole figure over the frames.  (b) ``test_epoch_windows`` on the 14-recording split of
+           tools/eval_windows_bench.py with ``ForwardGraphs`` and a ``DeviceSELDScorer``, ``tracking`` off and at its defaults,
+           alternately, at the configured threshold (an untrained model selects nothing) and at --dense-conf; ms per recorded
+           second.  With --root (a checkout that does not know ``tracking``) only the plain figure.
+
+  python tools/track_bench.py [--part stages|epoch|value|windows|all] [--windows] [--dir /tmp/adyolo_track_bench] [--clips 16] [--batch 8]
                               [--reps 7] [--calls 20] [--classes 13] [--dense-conf 0.3] [--root PATH] [--json out.json]
 """
 import argparse
@@ -39,9 +49,95 @@ def spread(values, per=1.0):
             "max": round(max(values) / per, 4)}
 
 
+def windows_part(a, res, alternately, opts, dev):
+    """The ``windows`` part (see the module's text)."""
+    import numpy as np
+    import torch
+    import warnings
+    from adyolo_amd import ops, test as atest
+    from adyolo_amd.corpus import EvalWindowCorpus, load_eval_split, window_plan
+    from adyolo_amd.features import FeatureExtractor
+    from adyolo_amd.graph import ForwardGraphs
+    from adyolo_amd.postprocess import LabelPostProcessor
+    from adyolo_amd.seld_metrics import DeviceSELDScorer
+    from adyolo_amd.wrapper import WrapperCriterion, WrapperModel
+    from eval_windows_bench import LENGTHS_S, SR, params, write_split
+    import inspect
+    has_run = hasattr(ops, "track_run") and "tracking" in inspect.signature(atest.test_epoch_windows).parameters
+    C = a.classes
+    res["windows"] = {"track_run": has_run}
+    if has_run:
+        from adyolo_amd.corpus import plan_track
+        from adyolo_amd.postprocess import track_hold
+        from test_track_cpu import random_tracks
+        frames, wf, mf = int(round(a.recording_s * 10)), int(round(a.window * 10)), int(round(a.margin * 10))
+        kept = [w[3] for w in window_plan(frames, wf, mf)]
+        bounds = [0] + np.cumsum([sum(kept[k:k + a.batch]) for k in range(0, len(kept), a.batch)]).tolist()
+        hold = -(-track_hold(opts["max_gap"], opts["min_len"]) // 10) * 10
+        plan = plan_track([0, frames], bounds, hold)
+        case = random_tracks(7, 1, frames, C)
+        offs = np.concatenate([[0], np.cumsum(case["counts"])])
+        rows, counts = torch.from_numpy(case["rows"]).to(dev), torch.from_numpy(case["counts"]).to(dev)
+        passes = [(rows[offs[lo]:offs[hi]].contiguous(), counts[lo:hi].contiguous(), torch.from_numpy(seg).to(dev),
+                   ops.track_run_buffers(dev, hi - lo, C, hold), n)
+                  for lo, hi, seg, n in zip(bounds, bounds[1:], plan["segments_host"], plan["pass_frames"])]
+        carry, status = ops.track_carry(dev, C, hold), torch.zeros(1, dtype=torch.int32, device=dev)
+        buf = ops.track_buffers(dev, frames, C)
+
+        def carried():
+            for _ in range(a.calls):
+                for r, c, seg, b, n in passes:
+                    ops.track_run(r, c, seg, C, opts, hold, carry, buf=b, status=status, trim=False, emitted=n)
+
+        def whole():
+            for _ in range(a.calls):
+                ops.track_rows(rows, counts, 1, C, opts, buf=buf, status=status, trim=False)
+        t = alternately({"whole": whole, "carried": carried}, a.calls)
+        out_whole = int(buf["counts"][frames])
+        out_run = sum(int(b["counts"][b["counts"].numel() - 2]) for _, _, _, b, _ in passes)
+        res["windows"]["recording"] = {
+            "frames": frames, "passes": len(passes), "pass_frames": [int(c.numel()) for _, c, _, _, _ in passes], "hold": hold,
+            "rows_in": int(case["counts"].sum()), "rows_out": out_whole, "same_rows_out": out_run == out_whole,
+            "ms_per_recording": t, "carry_ms_per_pass": round((t["carried"]["median"] - t["whole"]["median"]) / len(passes), 4),
+            "whole_us_per_frame_step": round(1e3 * t["whole"]["median"] / frames, 4),
+            "carried_us_per_frame_step": round(1e3 * t["carried"]["median"] / frames, 4)}
+        print(json.dumps(res["windows"]["recording"]), flush=True)
+    lengths = [LENGTHS_S[i % len(LENGTHS_S)] for i in range(14)]
+    seconds = write_split(a.dir, lengths, C) / SR
+    prm = params(a.dir, "adyolo", C, a.window, 0.5)
+    ref = os.path.join(a.dir, "metadata_dev", "dev-test")
+    torch.manual_seed(0)
+    model = WrapperModel((1, 7, int(SR * a.window) // 600, 64), (), prm).to(dev).eval()
+    fx, post, crit = FeatureExtractor(None, dev), LabelPostProcessor(prm), WrapperCriterion(prm)
+    corpus = EvalWindowCorpus(load_eval_split(prm, "test", rank=0, world=1, verify="sample"), prm, dev, window_s=a.window,
+                              margin_s=a.margin, batch_size=a.batch)
+    fg, scorer = ForwardGraphs(model, fx, post, warm_calls=0), DeviceSELDScorer(prm, ref, dev)
+
+    def epoch(**kw):
+        def run():
+            scorer.reset()
+            return atest.test_epoch_windows(corpus, model, fx, crit, post, None, forward=fg, device_scorer=scorer, **kw)
+        return run
+    runs = {"plain": epoch()}
+    if has_run:
+        warnings.simplefilter("ignore")                                        # (the caps of the definition only warn)
+        runs["tracked"] = epoch(tracking=opts)
+    res["windows"]["split"] = {"recordings": len(lengths), "seconds": round(seconds, 1), "passes": corpus.n_passes}
+    res["windows"]["epoch_ms_per_recorded_s"] = alternately(runs, seconds)
+    post.set_conf_thresh(a.dense_conf)
+    res["windows"]["epoch_dense_ms_per_recorded_s"] = alternately(runs, seconds)
+    if has_run:
+        res["windows"]["same_loss"] = runs["plain"]() == runs["tracked"]()
+    print(json.dumps({k: v for k, v in res["windows"].items() if k != "recording"}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--part", default="all", choices=["stages", "epoch", "value", "all"])
+    ap.add_argument("--part", default="all", choices=["stages", "epoch", "value", "windows", "all"])
+    ap.add_argument("--windows", action="store_true", help="the same as --part windows")
+    ap.add_argument("--recording-s", type=float, default=180.0)
+    ap.add_argument("--window", type=float, default=20.0)
+    ap.add_argument("--margin", type=float, default=2.0)
     ap.add_argument("--dir", default=os.path.join("/tmp", "adyolo_track_bench"))
     ap.add_argument("--clips", type=int, default=16)
     ap.add_argument("--batch", type=int, default=8)
@@ -52,6 +148,8 @@ def main():
     ap.add_argument("--root", default=os.path.dirname(HERE), help="the checkout whose package is measured")
     ap.add_argument("--json")
     a = ap.parse_args()
+    if a.windows:
+        a.part = "windows"
     root = os.path.abspath(a.root)
     sys.path.insert(0, root)
     sys.path.insert(1, HERE)
@@ -177,6 +275,8 @@ def main():
                 sc.add_rows(r, c, names)
                 res["value"][key] = dict(zip(("ER", "F", "LE", "LR", "SELD"), (round(float(v), 4) for v in sc.scores()[:5])))
             print(json.dumps(res["value"]), flush=True)
+        if a.part == "windows":
+            windows_part(a, res, alternately, opts, dev)
     finally:
         shutil.rmtree(a.dir, ignore_errors=True)
     if a.json:

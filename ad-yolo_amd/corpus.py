@@ -1093,6 +1093,9 @@ class _WindowCorpus(_CorpusBase):
         if not 1 <= self.batch_size < 65536:
             raise ValueError("%s: batch_size %r" % (who, batch_size))
         self.n_samples = n
+        # rotation test-time augmentation (``launch_view``): the format, the MIC source table (made by the first MIC view)
+        self.audio_format = str(dc.get("audio_format", "foa")).lower()
+        self.mic_src = None
         return sr
 
     def _window_tables(self, hc):
@@ -1120,7 +1123,26 @@ class _WindowCorpus(_CorpusBase):
         audio = self._out(audio_out, (self.batch_size, self.n_samples, 4))
         return ops.corpus_gather_windows(self.pcm, self.pass_table(p), audio, self.status)
 
-    hold_block = 1                                       # the hold of ``track_plan`` is a whole multiple of this many frames
+    def launch_view(self, p, comb, audio_out=None):
+        """The audio of ``launch`` for pass ``p`` under combination ``comb`` (rotation test-time augmentation): FOA-rotated, or
+        with ``data_config.audio_format: mic`` the capsules permuted (a combination that is no symmetry of the array:
+        ``ValueError``), the padding of a short window turned with the rest.  Audio only -- a view has no labels -> audio
+        (batch_size, n_samples, 4) f32.  The combination travels by value: nothing is uploaded, no host synchronisation.  A
+        ``resample=True`` split is read as every pass reads it: the converted int16 stream."""
+        from .augmentations import COMBINATIONS, MIC_SWAP_COMBS, mic_swap_source
+        who = type(self).__name__
+        comb = int(comb)
+        if not 0 <= comb < len(COMBINATIONS):
+            raise ValueError("%s.launch_view: combination %r is not one of 0..%d" % (who, comb, len(COMBINATIONS) - 1))
+        if self.audio_format == "mic":
+            mic_swap_source(comb)                                # ValueError: no symmetry of the array
+            if self.mic_src is None:
+                self.mic_src = ops.corpus_mic_table({k: mic_swap_source(k) for k in MIC_SWAP_COMBS})
+        audio = self._out(audio_out, (self.batch_size, self.n_samples, 4))
+        return ops.corpus_gather_windows_view(self.pcm, self.pass_table(p), comb, self.rot, audio, self.status,
+                                              mic_src=self.mic_src)
+
+    hold_block = 1                                      # the hold of ``track_plan`` is a whole multiple of this many frames
 
     def track_plan(self, opts):
         """Tracking through the passes (``postprocess.track_run``; ``test.test_epoch_windows(tracking=opts)``): built once per
@@ -1251,7 +1273,8 @@ class EvalWindowCorpus(_WindowCorpus):
     and advance by Wf - 2 Mf, the tail-aligned last window starts where its predecessor stopped, so every pass boundary inside
     a recording falls on a block boundary (``adyolo_seld_score_runs``).  A recording without a label frame has no window; its
     zero-frame segment rides in the pass of the next recording (``seld_metrics.run_segments``).  A split without any window:
-    ``ValueError``.  Rotation test-time augmentation and ``resample=True`` splits are not supported here."""
+    ``ValueError``.  ``launch_view`` gives a pass's audio under a combination (rotation test-time augmentation).
+    ``resample=True`` splits are not supported here."""
 
     def __init__(self, host_split, params, device="cuda:0", window_s=None, margin_s=None, batch_size=8, cap_per_window=None):
         hc = host_split

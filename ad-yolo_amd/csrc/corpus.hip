@@ -26,7 +26,8 @@
 // The label kernels have a second compile-time parameter YAW (aug_config.yaw_rotation_augment): each row's azimuths moved by its
 // word 7 after the combination (augmentations.yaw_labels); YAW false is the code without it.
 // Windowed inference (corpus.py InferDeviceCorpus, test.py infer_epoch_corpus) reads the same stream through a window table:
-//   corpus_gather_windows_kernel  the gather without rotation, the frames past a window's valid count int16 zero, never read
+//   corpus_gather_windows_kernel<FORM>  the gather without rotation, the frames past a window's valid count int16 zero, never
+//                                 read; or (rotation test-time augmentation) under one combination for the whole launch
 //   decode_stitch_kernel          each window's kept decoded frames copied into one contiguous run per pass
 // The AD-YOLO label arithmetic is done in double, as the host does it (augmentations.rotate_labels on Python floats,
 // datasets.YoloLabelEncoder.encode_events in float64); only the written row is rounded to float32.  The class-wise kernel does
@@ -78,7 +79,8 @@ __device__ __forceinline__ float4 pcm_swap(int lo, int hi, unsigned sel_lo, unsi
 
 // One source's conversion, uniform over the workgroup (blockIdx.y = item), so held in scalar registers: the signs and the swap
 // of pcm_rot, or the two byte selectors of pcm_swap.  gather_source returns false for a combination that is no symmetry of the
-// array (MIC table only); comb < 0: the frame as it is.
+// array (MIC table only); comb < 0: the frame as it is.  The two table forms also run on the host: a window gather under one
+// combination for the whole launch takes its CorpusSrc as a kernel argument.
 struct CorpusSrc {
     float sy, sz, sx;
     bool swap;
@@ -86,7 +88,7 @@ struct CorpusSrc {
     float c, s;                        // CorpusYaw only: the cosine and sine of the row's yaw
 };
 
-__device__ __forceinline__ bool gather_source(const CorpusRot &rot, int64_t comb, CorpusSrc &s) {
+__host__ __device__ __forceinline__ bool gather_source(const CorpusRot &rot, int64_t comb, CorpusSrc &s) {
     s.sy = 1.f; s.sz = 1.f; s.sx = 1.f; s.swap = false; s.sel_lo = 0u; s.sel_hi = 0u;
     if (comb >= 0) {
         s.sy = rot.c[comb][0]; s.sz = rot.c[comb][1]; s.sx = rot.c[comb][2]; s.swap = rot.c[comb][3] != 0.f;
@@ -94,7 +96,7 @@ __device__ __forceinline__ bool gather_source(const CorpusRot &rot, int64_t comb
     return true;
 }
 
-__device__ __forceinline__ bool gather_source(const CorpusMicSrc &tab, int64_t comb, CorpusSrc &s) {
+__host__ __device__ __forceinline__ bool gather_source(const CorpusMicSrc &tab, int64_t comb, CorpusSrc &s) {
     unsigned w = 0x03020100u;                               // identity: channel j from channel j
     if (comb >= 0) w = tab.w[comb];
     // channel c = frame bytes {2 c, 2 c + 1}: the byte pair c * 0x0202 + 0x0100; & 3 keeps every selector inside the frame
@@ -631,21 +633,38 @@ __global__ __launch_bounds__(CW_THREADS) void corpus_classwise_kernel(const doub
 // A window row: {offset, valid, src_lo, dst, n, recording, 0, 0} (adyolo_hip.h).  Both kernels stream: every output element is
 // written once by the thread that read its source, in the access shapes of corpus_gather_kernel.
 
-// grid (blocks per window, W).  Frames at or past ``valid`` are the conversion of int16 zero and are not read from the stream.
+// The conversion of a window gather, one kernel instance each: the frame as it is (adyolo_corpus_gather_windows), or one
+// combination for the whole launch (adyolo_corpus_gather_windows_view: rotation test-time augmentation), FOA signs and swap or
+// the MIC byte selectors.  The combination's CorpusSrc is worked out on the host and passed by value, so the signs, the swap
+// and the selectors are kernel arguments: scalar registers, no table read at all.
+enum { WINDOW_PLAIN, WINDOW_FOA, WINDOW_MIC };
+
+template <int FORM>
+__device__ __forceinline__ float4 window_conv(int lo, int hi, const CorpusSrc &s) {
+    if (FORM == WINDOW_MIC) return pcm_swap(lo, hi, s.sel_lo, s.sel_hi);
+    if (FORM == WINDOW_FOA) return pcm_rot(lo, hi, s.sy, s.sz, s.sx, s.swap);
+    return pcm_rot(lo, hi, 1.f, 1.f, 1.f, false);
+}
+
+// grid (blocks per window, W).  Frames at or past ``valid`` are the conversion of int16 zero and are not read from the stream:
+// under a view the padding is turned like every other frame (1e-8f under the signs and the swap).  comb_ok false (a MIC
+// combination that is no symmetry of the array): every window is a bad item.
+template <int FORM>
 __global__ __launch_bounds__(256) void corpus_gather_windows_kernel(const int16_t *__restrict__ pcm, long n_total,
-                                                                    const int64_t *__restrict__ windows, long n,
-                                                                    float4 *__restrict__ out, int *__restrict__ status) {
+                                                                    const int64_t *__restrict__ windows, long n, CorpusSrc cs,
+                                                                    int comb_ok, float4 *__restrict__ out,
+                                                                    int *__restrict__ status) {
     const int w = blockIdx.y;
     const int64_t off = windows[(size_t)w * ADYOLO_WINDOW_WORDS + 0];
     const int64_t valid = windows[(size_t)w * ADYOLO_WINDOW_WORDS + 1];
     float4 *dst = out + (size_t)w * n;
     const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, nth = (long)gridDim.x * blockDim.x;
-    const float4 pad = pcm_rot(0, 0, 1.f, 1.f, 1.f, false);      // int16 zero: what the zero padding of a training chunk becomes
-    if (valid == 0) {                                             // an empty window: nothing else of the row is looked at
+    const float4 pad = window_conv<FORM>(0, 0, cs);               // int16 zero: what the zero padding of a training chunk becomes
+    if (valid == 0 && comb_ok) {                                  // an empty window: nothing else of the row is looked at
         for (long i = tid; i < n; i += nth) dst[i] = pad;
         return;
     }
-    if (off < 0 || (off & 1) || valid < 0 || valid > n || off > n_total - valid) {
+    if (!comb_ok || off < 0 || (off & 1) || valid < 0 || valid > n || off > n_total - valid) {
         if (tid == 0 && status) atomicOr(status, ADYOLO_CORPUS_BAD_ITEM);
         for (long i = tid; i < n; i += nth) dst[i] = make_float4(0.f, 0.f, 0.f, 0.f);
         return;
@@ -658,11 +677,11 @@ __global__ __launch_bounds__(256) void corpus_gather_windows_kernel(const int16_
         float4 o0 = pad, o1 = pad;
         if (2 * i + 1 < valid) {
             const int4 v = s4[i];
-            o0 = pcm_rot(v.x, v.y, 1.f, 1.f, 1.f, false);
-            o1 = pcm_rot(v.z, v.w, 1.f, 1.f, 1.f, false);
+            o0 = window_conv<FORM>(v.x, v.y, cs);
+            o1 = window_conv<FORM>(v.z, v.w, cs);
         } else if (2 * i < valid) {                               // the last frame of an odd count
             const int2 v = s2[2 * i];
-            o0 = pcm_rot(v.x, v.y, 1.f, 1.f, 1.f, false);
+            o0 = window_conv<FORM>(v.x, v.y, cs);
         }
         dst[2 * i] = o0;
         dst[2 * i + 1] = o1;
@@ -671,7 +690,7 @@ __global__ __launch_bounds__(256) void corpus_gather_windows_kernel(const int16_
         float4 o = pad;
         if (n - 1 < valid) {
             const int2 v = s2[n - 1];
-            o = pcm_rot(v.x, v.y, 1.f, 1.f, 1.f, false);
+            o = window_conv<FORM>(v.x, v.y, cs);
         }
         dst[n - 1] = o;
     }
@@ -858,18 +877,50 @@ extern "C" int adyolo_corpus_classwise_labels(const double *events, const float 
 }
 
 // ------------------------------------------------------------------------------------------------ windowed inference
-extern "C" int adyolo_corpus_gather_windows(const int16_t *pcm, long n_total, const int64_t *windows, int W, long n,
-                                            float *audio, int *status, void *stream) {
-    ADYOLO_REQUIRE(pcm && windows && audio, ADYOLO_EINVAL, "corpus_gather_windows: null pointer");
-    ADYOLO_REQUIRE(W > 0 && W < 65536 && n > 0 && n_total >= 0, ADYOLO_EINVAL,
-                   "corpus_gather_windows: bad shape W=%d n=%ld n_total=%ld", W, n, n_total);
+namespace adyolo {
+// both window gathers: the checks, the grid of adyolo_corpus_gather and the instance of the form
+template <int FORM>
+static int corpus_gather_windows_launch(const char *name, const int16_t *pcm, long n_total, const int64_t *windows, int W, long n,
+                                        const CorpusSrc &cs, bool comb_ok, float *audio, int *status, void *stream) {
+    ADYOLO_REQUIRE(pcm && windows && audio, ADYOLO_EINVAL, "%s: null pointer", name);
+    ADYOLO_REQUIRE(W > 0 && W < 65536 && n > 0 && n_total >= 0, ADYOLO_EINVAL, "%s: bad shape W=%d n=%ld n_total=%ld", name, W, n,
+                   n_total);
     ADYOLO_REQUIRE(((uintptr_t)pcm & 15) == 0 && ((uintptr_t)audio & 15) == 0 && ((uintptr_t)windows & 7) == 0, ADYOLO_EINVAL,
-                   "corpus_gather_windows: misaligned buffers (pcm / audio 16 bytes, windows 8 bytes)");
+                   "%s: misaligned buffers (pcm / audio 16 bytes, windows 8 bytes)", name);
     int gx = cdiv(n, 256L * 16);                            // the grid of adyolo_corpus_gather
     gx = gx < 1 ? 1 : (gx > 4096 ? 4096 : gx);
-    hipLaunchKernelGGL(corpus_gather_windows_kernel, dim3((unsigned)gx, (unsigned)W), dim3(256), 0, as_stream(stream), pcm,
-                       n_total, windows, n, (float4 *)audio, status);
-    return check_launch("corpus_gather_windows");
+    hipLaunchKernelGGL(corpus_gather_windows_kernel<FORM>, dim3((unsigned)gx, (unsigned)W), dim3(256), 0, as_stream(stream), pcm,
+                       n_total, windows, n, cs, comb_ok ? 1 : 0, (float4 *)audio, status);
+    return check_launch(name);
+}
+}  // namespace adyolo
+
+extern "C" int adyolo_corpus_gather_windows(const int16_t *pcm, long n_total, const int64_t *windows, int W, long n,
+                                            float *audio, int *status, void *stream) {
+    const CorpusSrc cs = {1.f, 1.f, 1.f, false, 0u, 0u, 1.f, 0.f};
+    return corpus_gather_windows_launch<WINDOW_PLAIN>("corpus_gather_windows", pcm, n_total, windows, W, n, cs, true, audio,
+                                                      status, stream);
+}
+
+extern "C" int adyolo_corpus_gather_windows_view(const int16_t *pcm, long n_total, const int64_t *windows, int W, long n,
+                                                 int comb, const float *rot_host, const unsigned int *mic_src_host,
+                                                 float *audio, int *status, void *stream) {
+    const char *name = "corpus_gather_windows_view";
+    ADYOLO_REQUIRE(rot_host || mic_src_host, ADYOLO_EINVAL, "%s: null pointer", name);
+    ADYOLO_REQUIRE(comb < 16, ADYOLO_EINVAL, "%s: combination %d (at most 15)", name, comb);
+    CorpusSrc cs = {1.f, 1.f, 1.f, false, 0u, 0u, 1.f, 0.f};
+    if (comb <= 0)                                          // no view, or the identity: the plain gather's instance and bits
+        return corpus_gather_windows_launch<WINDOW_PLAIN>(name, pcm, n_total, windows, W, n, cs, true, audio, status, stream);
+    if (mic_src_host) {
+        CorpusMicSrc tab;
+        corpus_mic(mic_src_host, tab);
+        const bool ok = gather_source(tab, comb, cs);
+        return corpus_gather_windows_launch<WINDOW_MIC>(name, pcm, n_total, windows, W, n, cs, ok, audio, status, stream);
+    }
+    CorpusRot rot;
+    corpus_rot(rot_host, rot);
+    gather_source(rot, comb, cs);
+    return corpus_gather_windows_launch<WINDOW_FOA>(name, pcm, n_total, windows, W, n, cs, true, audio, status, stream);
 }
 
 extern "C" int adyolo_decode_stitch(const float *decoded, const int64_t *windows, int W, int Wf, long rec, long pass_base,

@@ -2321,21 +2321,43 @@ def _window_table(name, windows, device):
     return int(windows.shape[0])
 
 
+def _gather_windows_args(name, pcm, windows, out, status):
+    """The argument checks of both window gathers -> W."""
+    dev = pcm.device
+    if not pcm.is_cuda or pcm.dtype != torch.int16 or not pcm.is_contiguous() or pcm.dim() != 2 or pcm.shape[1] != 4:
+        raise _lib.AdyoloHipError("%s: pcm must be a contiguous int16 tensor (S, 4) on the device" % name)
+    w = _window_table(name, windows, dev)
+    _chk(out)
+    if out.dim() != 3 or out.shape[0] != w or out.shape[1] < 1 or out.shape[2] != 4 or out.device != dev:
+        raise _lib.AdyoloHipError("%s: out %s is not (%d, n, 4) on %s" % (name, tuple(out.shape), w, dev))
+    if status.dtype != torch.int32 or status.device != dev or status.numel() < 1:
+        raise _lib.AdyoloHipError("%s: status must be an int32 word on %s" % (name, dev))
+    return w
+
+
 def corpus_gather_windows(pcm, windows, out, status):
     """pcm int16 (S, 4) and windows int64 (W, 8) on the device -> out (W, n, 4) float32: each window's ``valid`` int16 frames
     from its offset as ``x / 32768 + 1e-8``, the rest of the window the conversion of int16 zero, not read from pcm
     (adyolo_hip.h ``adyolo_corpus_gather_windows``).  An odd or negative offset, or a window past the stream: zeros for it and
     status bit 2.  out may be a recorded graph's static input.  No allocation, no sync."""
-    dev = pcm.device
-    if not pcm.is_cuda or pcm.dtype != torch.int16 or not pcm.is_contiguous() or pcm.dim() != 2 or pcm.shape[1] != 4:
-        raise _lib.AdyoloHipError("corpus_gather_windows: pcm must be a contiguous int16 tensor (S, 4) on the device")
-    w = _window_table("corpus_gather_windows", windows, dev)
-    _chk(out)
-    if out.dim() != 3 or out.shape[0] != w or out.shape[1] < 1 or out.shape[2] != 4 or out.device != dev:
-        raise _lib.AdyoloHipError("corpus_gather_windows: out %s is not (%d, n, 4) on %s" % (tuple(out.shape), w, dev))
-    if status.dtype != torch.int32 or status.device != dev or status.numel() < 1:
-        raise _lib.AdyoloHipError("corpus_gather_windows: status must be an int32 word on %s" % dev)
+    w = _gather_windows_args("corpus_gather_windows", pcm, windows, out, status)
     _c("adyolo_corpus_gather_windows", _p(pcm), pcm.shape[0], _p(windows), w, out.shape[1], _p(out), _p(status), _stream())
+    return out
+
+
+def corpus_gather_windows_view(pcm, windows, comb, rot, out, status, *, mic_src=None):
+    """``corpus_gather_windows`` under ONE combination ``comb`` for all windows (rotation test-time augmentation through
+    windows; adyolo_hip.h ``adyolo_corpus_gather_windows_view``): FOA-rotated (rot: ``corpus_rot_table``) -- bit for bit the
+    plain window gather then ``augmentations.rotate_audio``, the padding past ``valid`` turned too -- or with ``mic_src``
+    (``corpus_mic_table``; rot may be None) the four capsules permuted -- bit for bit the plain gather then ``swap_audio``; a
+    combination that is no symmetry: zeros and status bit 2.  comb <= 0: the bits of ``corpus_gather_windows``; comb >= 16
+    raises.  Bad windows as in the plain gather.  No allocation, no sync."""
+    name = "corpus_gather_windows_view"
+    w = _gather_windows_args(name, pcm, windows, out, status)
+    if mic_src is None and rot is None:
+        raise _lib.AdyoloHipError("%s: the FOA form needs the rotation table" % name)
+    _c("adyolo_corpus_gather_windows_view", _p(pcm), pcm.shape[0], _p(windows), w, out.shape[1], int(comb), _host_table(rot),
+       _host_table(mic_src), _p(out), _p(status), _stream())
     return out
 
 

@@ -218,9 +218,11 @@ class _ViewMerge:
     """The device half of rotation test-time augmentation for the corpus loops: every view's selected rows collected
     (``ops.tta_collect``), then merged (``ops.tta_merge``) into rows and counts in the selection's own layout.  tta: the list of
     views (``augmentations.tta_views``; the other keys at their defaults) or the dict of ``augmentations.tta_options``.  The
-    buffers are made once per batch shape; ``status`` collects the ADYOLO_TTA_* bits of the pass."""
+    buffers are made once per batch shape; ``status`` collects the ADYOLO_TTA_* bits of the pass.  max_frames (the windowed
+    loops, whose runs differ in length from pass to pass): ONE set of buffers for a run of that many frames, made by the
+    first merge; a shorter run works in views of it."""
 
-    def __init__(self, tta, postprocessor, device):
+    def __init__(self, tta, postprocessor, device, max_frames=None):
         from .augmentations import tta_options, view_matrix
         from .postprocess import tta_cos
         from . import ops
@@ -231,6 +233,29 @@ class _ViewMerge:
         self.nb_classes = postprocessor.nb_classes
         self.status = torch.zeros(1, dtype=torch.int32, device=device)
         self._buffers = {}
+        self.max_frames, self._longest = None if max_frames is None else int(max_frames), None
+
+    def _buffers_for(self, frames):
+        """The buffers of a batch of ``frames`` frames: their own allocation, or with ``max_frames`` views of the one made for
+        the longest run (the same layouts over fewer frames; the workspace and the rows as they are)."""
+        from . import ops
+        buf = self._buffers.get(frames)
+        if buf is not None:
+            return buf
+        v, p = len(self.views), self.rows_per_frame
+        if self.max_frames is None:
+            buf = ops.tta_buffers(self.status.device, v, frames, self.nb_classes, p, self.min_views)
+        else:
+            if not 0 < frames <= self.max_frames:
+                raise ValueError("_ViewMerge: a run of %d frames with buffers for %d" % (frames, self.max_frames))
+            if self._longest is None:
+                self._longest = ops.tta_buffers(self.status.device, v, self.max_frames, self.nb_classes, p, self.min_views)
+            big = self._longest
+            buf = {"pool": big["pool"].view(-1)[:v * frames * p * 4].view(v, frames, p, 4),
+                   "pool_counts": big["pool_counts"].view(-1)[:v * frames].view(v, frames),
+                   "ws": big["ws"], "rows": big["rows"], "counts": big["counts"][:frames + 1]}
+        self._buffers[frames] = buf
+        return buf
 
     def merged(self, postprocessor, decoded_views, n_clips, trim):
         """decoded_views: an iterable of every view's decoded batch, in the order of ``views`` (each is selected before the next
@@ -240,11 +265,7 @@ class _ViewMerge:
         for k, dec in enumerate(decoded_views):
             rows, counts = postprocessor.select_device_rows(dec, n_clips, trim=False)
             if buf is None:
-                key = counts.numel()
-                buf = self._buffers.get(key)
-                if buf is None:
-                    buf = self._buffers[key] = ops.tta_buffers(self.status.device, len(self.views), key, self.nb_classes,
-                                                               self.rows_per_frame, self.min_views)
+                buf = self._buffers_for(counts.numel())
             ops.tta_collect(rows, counts, k, self.words[k], self.nb_classes, buf["pool"], buf["pool_counts"], self.status,
                             buf["ws"])
         return ops.tta_merge(buf["pool"], buf["pool_counts"], self.nb_classes, self.cos_t, self.min_views, self.status, buf["ws"],
@@ -462,7 +483,7 @@ def sweep_conf_thresh_corpus(corpus, model, features, criterion, postprocessor, 
     return new_thresh, table, loss
 
 
-def infer_epoch_corpus(corpus, model, features, postprocessor, output_pth, forward=None, tracking=None):
+def infer_epoch_corpus(corpus, model, features, postprocessor, output_pth, forward=None, tracking=None, tta=None):
     """Inference on recordings of any length from an HBM-resident folder (``corpus.InferDeviceCorpus``): every recording cut
     into overlapping windows of one shape, the windows run ``corpus.batch_size`` at a time -- so the whole folder has ONE input
     shape and, with ``forward`` (``graph.ForwardGraphs``), one recorded graph.  Per pass: ``adyolo_corpus_gather_windows`` (into
@@ -480,7 +501,14 @@ def infer_epoch_corpus(corpus, model, features, postprocessor, output_pth, forwa
     gap fill or the erasure of a short track can still reach them -- and with the D it held back before
     (``corpus.track_plan``, D = ``postprocess.track_hold``).  The emitted rows go to the files, whose third column carries the
     track ids; the status word is read with the corpus's at the end (the caps of the definition only warn).  None leaves
-    every call, allocation and bit as it is."""
+    every call, allocation and bit as it is.
+
+    tta (rotation test-time augmentation): None, or what ``test_epoch_windows`` takes, with the same meaning: the pass above
+    is view 0, every further view is ``corpus.launch_view`` into the same input, forward, decode and stitch with the same
+    pass table, each run selected and parked before the next is made, then ``ops.tta_merge``; the merged rows are what is
+    written and, with ``tracking``, what is linked.  The pool and the workspace are allocated once, for the longest run; the
+    merge's status word joins the one copy at the end (an overflow raises, naming ``tta_max_rows_per_frame``).  None
+    leaves every call, allocation, synchronisation and bit as it is."""
     from . import ops
     from .corpus import split_pass_rows
     model.eval()
@@ -489,6 +517,7 @@ def infer_epoch_corpus(corpus, model, features, postprocessor, output_pth, forwa
     corpus.reset_status()
     b, n, wf = corpus.batch_size, corpus.n_samples, corpus.window_frames
     outs = [{} for _ in names]
+    merge = _window_merge(tta, postprocessor, corpus) if tta is not None and corpus.n_passes else None
     tracker = _RunTracker(tracking, corpus) if tracking is not None else None
     out_ids = [{} for _ in names] if tracker is not None else None
     stitched = None
@@ -512,22 +541,33 @@ def infer_epoch_corpus(corpus, model, features, postprocessor, output_pth, forwa
                 stitched = torch.empty_like(dec)
             frames = corpus.pass_frames[p]
             ops.decode_stitch(dec, corpus.pass_table(p), wf, corpus.pass_base[p], stitched, corpus.status)
+            if merge is not None:                                            # this body is view 0; merge, then link
+                views = (stitched[:frames] if k == 0 else
+                         _window_view(corpus, p, v, model, features, postprocessor, forward, stitched)
+                         for k, v in enumerate(merge.views))
+                rows, counts = merge.merged(postprocessor, views, 1, trim=tracker is None)
             if tracker is not None:
-                rows, counts = postprocessor.select_device_rows(stitched[:frames], 1, trim=False)
+                if merge is None:
+                    rows, counts = postprocessor.select_device_rows(stitched[:frames], 1, trim=False)
                 rows, counts, ids = tracker.tracked(postprocessor, p, rows, counts, trim=True)
                 if counts.numel():
                     _write_pass_tracks(corpus, tracker.plan["pass_base"][p], rows, counts, ids, outs, out_ids)
                 continue
-            rows, counts = postprocessor.select_device_rows(stitched[:frames], 1)
+            if merge is None:
+                rows, counts = postprocessor.select_device_rows(stitched[:frames], 1)
             rows_h, counts_h = [t.numpy() for t in ops.to_host_many(rows, counts)]
             for r, found in split_pass_rows(rows_h, counts_h, corpus.pass_base[p], corpus.frame_start).items():
                 outs[r].update(found)                                        # (a recording's passes come in frame order)
-    if tracker is None:
+    if tracker is None and merge is None:
         corpus.check()
     else:
-        status_h, track_h = ops.to_host_many(corpus.status, tracker.status)
+        more = [m.status for m in (merge, tracker) if m is not None]
+        status_h, *more_h = ops.to_host_many(corpus.status, *more)
         corpus.check(int(status_h[0]))
-        ops.track_status_check(int(track_h[0]))
+        if merge is not None:
+            ops.tta_status_check(int(more_h[0][0]))
+        if tracker is not None:
+            ops.track_status_check(int(more_h[-1][0]))
     _write_recordings(output_pth, names, outs, out_ids)
     return {"recordings": len(names), "windows": corpus.n_windows, "passes": corpus.n_passes,
             "frames": int(corpus.frame_start[-1])}
@@ -566,6 +606,32 @@ def _window_pass(corpus, p, model, features, criterion, postprocessor, forward, 
     return stitched, stitched[:corpus.pass_frames[p]]
 
 
+def _window_view(corpus, p, comb, model, features, postprocessor, forward, stitched):
+    """A further view of the pass ``_window_pass`` (or the inference loop's body) ran (rotation test-time augmentation):
+    ``launch_view`` into the same graph input -> forward -> decode -> ``decode_stitch`` with the same pass table into the same
+    ``stitched`` -> the pass's run under the view.  The caller has selected the previous view's run before this one is made.  No
+    labels, no loss, no host synchronisation."""
+    from . import ops
+    audio_out = None
+    if forward is not None and hasattr(forward, "static_input"):
+        audio_out = forward.static_input((corpus.batch_size, corpus.n_samples, 4))
+    audio = corpus.launch_view(p, comb, audio_out)
+    dec = None
+    if forward is not None:
+        output, dec = forward(audio)
+    else:
+        output = model(features(audio, channels_last8=True), channels_last8=True)
+    if dec is None:
+        dec = postprocessor.decode_device(output)
+    ops.decode_stitch(dec, corpus.pass_table(p), corpus.window_frames, corpus.pass_base[p], stitched, corpus.status)
+    return stitched[:corpus.pass_frames[p]]
+
+
+def _window_merge(tta, postprocessor, corpus):
+    """The ``_ViewMerge`` of a windowed loop: its pool and workspace made once, for the longest run of the split."""
+    return _ViewMerge(tta, postprocessor, corpus.device, max_frames=max(corpus.pass_frames))
+
+
 def _write_pass_rows(corpus, p, rows, counts, outs):
     """The selected rows of pass ``p``'s run (trimmed) -> the host, onto each recording's own frame axis in ``outs``."""
     from . import ops
@@ -597,7 +663,7 @@ def _write_recordings(output_pth, names, outs, out_ids=None):
 
 
 def test_epoch_windows(corpus, model, features, criterion, postprocessor, output_pth=None, forward=None, device_scorer=None,
-                       tracking=None):
+                       tracking=None, tta=None):
     """Labelled evaluation of recordings of ANY length from an HBM-resident split (``corpus.EvalWindowCorpus``): every recording
     cut into overlapping windows of one shape, ``corpus.batch_size`` windows per pass -- one input shape for the whole split
     and, with ``forward`` (``graph.ForwardGraphs``), one recorded graph.  Per pass: ``corpus.launch`` (audio into the graph's
@@ -625,7 +691,18 @@ def test_epoch_windows(corpus, model, features, criterion, postprocessor, output
     gap fill or the erasure of a short track can still reach them -- and with the D it held back before
     (``corpus.track_plan``).  The emitted rows go to the scorer (its segment tables on the emitted bounds) and to the files,
     whose third column carries the track ids; the status word is read in the one end-of-pass copy (the caps of the definition
-    only warn).  None leaves every call, allocation and bit as it is.  Test-time augmentation is not taken here."""
+    only warn).  None leaves every call, allocation and bit as it is.
+
+    tta (rotation test-time augmentation): None, or what ``test_epoch_corpus`` takes (a list of views starting with 0, or the
+    dict of ``augmentations.tta_options``).  View 0 is the plain pass: labels, loss -- the same float as without views --
+    and stitch.  Every further view of a pass is ``corpus.launch_view`` into the same static input, the forward pass, the
+    decode and ``adyolo_decode_stitch`` with the same pass table; each view's run is selected and parked
+    (``ops.tta_collect``) before the next one overwrites the graph's output and the stitch buffer, and after the last the
+    views are merged per frame (``ops.tta_merge``; ``postprocess.merge_view_rows`` bit for bit -- per frame, so it does not
+    matter where the passes cut the axis).  The merged rows take the selection's place everywhere: the scorer, the files
+    and, with ``tracking``, the link (merge, then link, as on whole clips).  The pool and the workspace are allocated once,
+    for the longest run of the split; the merge's status word is read in the one end-of-pass copy (an overflow raises,
+    naming ``tta_max_rows_per_frame``).  None leaves every call, allocation, synchronisation and bit as it is."""
     from . import ops
     model.eval()
     if output_pth is not None:
@@ -633,6 +710,7 @@ def test_epoch_windows(corpus, model, features, criterion, postprocessor, output
     names = corpus.get_filelist()
     corpus.reset_status()
     acc = ops.loss_accumulator(corpus.device)
+    merge = _window_merge(tta, postprocessor, corpus) if tta is not None else None
     tracker = _RunTracker(tracking, corpus) if tracking is not None else None
     bounds = None if tracker is None else tracker.plan["bounds"]
     segments = corpus.segments(device_scorer, bounds=bounds) if device_scorer is not None else None
@@ -642,7 +720,12 @@ def test_epoch_windows(corpus, model, features, criterion, postprocessor, output
     with torch.no_grad():
         for p in range(corpus.n_passes):
             stitched, run = _window_pass(corpus, p, model, features, criterion, postprocessor, forward, acc, stitched)
-            rows, counts = postprocessor.select_device_rows(run, 1, trim=output_pth is not None and tracker is None)
+            if merge is None:
+                rows, counts = postprocessor.select_device_rows(run, 1, trim=output_pth is not None and tracker is None)
+            else:
+                views = (run if k == 0 else _window_view(corpus, p, v, model, features, postprocessor, forward, stitched)
+                         for k, v in enumerate(merge.views))
+                rows, counts = merge.merged(postprocessor, views, 1, trim=output_pth is not None and tracker is None)
             if tracker is not None:
                 rows, counts, ids = tracker.tracked(postprocessor, p, rows, counts, trim=output_pth is not None)
                 if not counts.numel():                                       # the pass holds all its frames back
@@ -655,11 +738,11 @@ def test_epoch_windows(corpus, model, features, criterion, postprocessor, output
                 _write_pass_tracks(corpus, tracker.plan["pass_base"][p], rows, counts, ids, outs, out_ids)
     if output_pth is not None:
         _write_recordings(output_pth, names, outs, out_ids)
-    return _corpus_finish(corpus, acc, track_status=None if tracker is None else tracker.status)
+    return _corpus_finish(corpus, acc, None if merge is None else merge.status, None if tracker is None else tracker.status)
 
 
 def sweep_conf_thresh_windows(corpus, model, features, criterion, postprocessor, scorer, thresholds=None, output_pth=None,
-                              forward=None, tracking=None):
+                              forward=None, tracking=None, tta=None):
     """``sweep_conf_thresh_corpus`` through windows (``corpus.EvalWindowCorpus``): ONE forward pass per window pass, every
     pass's stitched run kept (cloned) on the device, then per threshold ``scorer.reset()``, the selection of every run and
     ``scorer.add_run``; the chosen threshold is left set on the post-processor.  With ``output_pth`` the last threshold's CSV
@@ -673,7 +756,12 @@ def sweep_conf_thresh_windows(corpus, model, features, criterion, postprocessor,
     (``corpus.track_plan``).  Per threshold the carry is emptied with the scorer; the emitted rows go to the scorer (its segment
     tables on the emitted bounds) and, for the last threshold, to the files, whose third column carries the track ids; the
     status word is read once, after the last threshold (the caps of the definition only warn).  None leaves every call,
-    allocation and bit as it is.  Test-time augmentation is not taken here."""
+    allocation and bit as it is.
+
+    tta: as ``test_epoch_windows``.  Every VIEW's stitched run of every pass is kept (cloned) on the device -- passes x views x
+    run frames x the decode's record, i.e. views x (the split's label frames) x record x 4 bytes, against one such axis
+    without views -- and each threshold selects, collects and merges them again (then links, with ``tracking``); the
+    merge's status word is read once, after the last threshold, in the copy that reads the tracker's."""
     import numpy as np
     from . import ops
     from .seld_metrics import DeviceSELDScorer
@@ -685,13 +773,18 @@ def sweep_conf_thresh_windows(corpus, model, features, criterion, postprocessor,
     names = corpus.get_filelist()
     corpus.reset_status()
     acc = ops.loss_accumulator(corpus.device)
+    merge = _window_merge(tta, postprocessor, corpus) if tta is not None else None
     tracker = _RunTracker(tracking, corpus) if tracking is not None else None
     segments = corpus.segments(scorer, bounds=None if tracker is None else tracker.plan["bounds"])
     runs, stitched = [], None
     with torch.no_grad():
         for p in range(corpus.n_passes):
             stitched, run = _window_pass(corpus, p, model, features, criterion, postprocessor, forward, acc, stitched)
-            runs.append(run.clone())                                         # (the stitch buffer is reused)
+            run = run.clone()                                                # (the stitch buffer is reused)
+            if merge is not None:
+                run = [run] + [_window_view(corpus, p, v, model, features, postprocessor, forward, stitched).clone()
+                               for v in merge.views[1:]]
+            runs.append(run)
     loss = _corpus_finish(corpus, acc)
     new_thresh, best, table = postprocessor.get_conf_thresh(), 9999.0, []
     for k, th in enumerate(thresholds):
@@ -703,7 +796,10 @@ def sweep_conf_thresh_windows(corpus, model, features, criterion, postprocessor,
         if tracker is not None:
             tracker.reset()
         for p, run in enumerate(runs):
-            rows, counts = postprocessor.select_device_rows(run, 1, trim=write and tracker is None)
+            if merge is None:
+                rows, counts = postprocessor.select_device_rows(run, 1, trim=write and tracker is None)
+            else:
+                rows, counts = merge.merged(postprocessor, run, 1, trim=write and tracker is None)
             if tracker is not None:
                 rows, counts, ids = tracker.tracked(postprocessor, p, rows, counts, trim=write)
                 if not counts.numel():
@@ -721,8 +817,13 @@ def sweep_conf_thresh_windows(corpus, model, features, criterion, postprocessor,
         if seld < best:
             new_thresh, best = th, seld
     postprocessor.set_conf_thresh(new_thresh)
-    if tracker is not None:
+    if merge is None and tracker is not None:
         ops.track_status_check(int(ops.to_host(tracker.status)[0]))
+    elif merge is not None:
+        words = [int(w[0]) for w in ops.to_host_many(merge.status, *([tracker.status] if tracker is not None else []))]
+        ops.tta_status_check(words[0])
+        if tracker is not None:
+            ops.track_status_check(words[-1])
     return new_thresh, table, loss
 
 

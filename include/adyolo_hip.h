@@ -935,6 +935,18 @@ int  adyolo_corpus_classwise_labels(const double *events, const float *xyz, long
  *   Offsets are whole label hops, so even: an odd or negative offset, valid outside [0, n] or off + valid > n_total gives
  *   zeros for that window and sets ADYOLO_CORPUS_BAD_ITEM.  pcm and audio 16-byte aligned; audio may be a recorded graph's
  *   static input.
+ * adyolo_corpus_gather_windows_view: the same gather under ONE combination comb for the whole launch, passed by value (rotation
+ *   test-time augmentation through windows: a further view of a pass, written into the same static input).  The two forms of
+ *   adyolo_corpus_gather:
+ *     mic_src_host NULL (rot_host, as above, required): FOA, bit for bit adyolo_corpus_gather_windows then adyolo_foa_rotate
+ *       under comb -- the frames past valid included: the padding is the conversion of int16 zero under the same signs and
+ *       swap (+-1e-8f), not a constant;
+ *     mic_src_host given: MIC, bit for bit adyolo_corpus_gather_windows then adyolo_mic_swap; a combination whose word is
+ *       ADYOLO_MIC_SWAP_NONE is what it is to adyolo_corpus_gather: zeros for every window and ADYOLO_CORPUS_BAD_ITEM.
+ *   comb <= 0 (no view, or the identity): the bits of adyolo_corpus_gather_windows; comb >= 16: EINVAL.  Bad window rows and
+ *   valid = 0 as above (the zeros of a bad window are +0).  The signs, the swap and the byte selectors are kernel arguments,
+ *   worked out on the host: nothing is read per element but the stream.  Not for capture into a graph that is replayed under
+ *   another combination: the call stays outside the recorded graph and writes its input.
  * adyolo_decode_stitch: for each window w, n frame records of rec floats from decoded[(w Wf + src_lo) ..] to
  *   out[(dst - pass_base) ..]: the pass's kept frames compacted into one run in window order.  decoded [W Wf][rec], out
  *   [out_frames][rec] (rec: whatever the decode writes per frame); 16-byte copies where rec % 4 == 0 (both buffers 16-byte
@@ -944,6 +956,9 @@ int  adyolo_corpus_classwise_labels(const double *events, const float *xyz, long
 #define ADYOLO_WINDOW_WORDS 8
 int  adyolo_corpus_gather_windows(const int16_t *pcm, long n_total, const int64_t *windows, int W, long n, float *audio,
                                   int *status, void *stream);
+int  adyolo_corpus_gather_windows_view(const int16_t *pcm, long n_total, const int64_t *windows, int W, long n, int comb,
+                                       const float *rot_host, const unsigned int *mic_src_host /* NULL: FOA form */,
+                                       float *audio, int *status, void *stream);
 int  adyolo_decode_stitch(const float *decoded, const int64_t *windows, int W, int Wf, long rec, long pass_base, float *out,
                           long out_frames, int *status, void *stream);
 

@@ -3,6 +3,7 @@ per file (one full clip, batch 1): eval-mode forward, loss, post-processing (GPU
 file under ``output_pth``.  The SELD scores come from ``seld_metrics.ComputeSELDResults(ref_dir).get_SELD_Results(output_pth)``."""
 import os
 import shutil
+from itertools import chain
 
 import torch
 
@@ -31,6 +32,24 @@ def test_epoch(dataloader, filelist, model, criterion, postprocessor, device, ou
     return float(total) / max(n, 1) if total is not None else 0.0
 
 
+def _sweep_thresholds(postprocessor, thresholds, score):
+    """The threshold loop of every sweep: each threshold (default 0.1 .. 0.9) set on the post-processor and scored by
+    ``score(k, th, is_last) -> (ER, F, LE, LR, SELD)``; the FIRST one with the lowest SELD score is kept and left set.
+    -> (new_thresh, [[ER, F, LE, LR, SELD] per threshold])"""
+    if thresholds is None:
+        import numpy as np
+        thresholds = np.arange(0.1, 1.0, 0.1)
+    new_thresh, best, table = postprocessor.get_conf_thresh(), 9999.0, []
+    for k, th in enumerate(thresholds):
+        postprocessor.set_conf_thresh(th)
+        er, f, le, lr, seld = score(k, th, k == len(thresholds) - 1)[:5]
+        table.append([er, f, le, lr, seld])
+        if seld < best:
+            new_thresh, best = th, seld
+    postprocessor.set_conf_thresh(new_thresh)
+    return new_thresh, table
+
+
 def sweep_conf_thresh(dataloader, filelist, model, criterion, postprocessor, scorer, device, output_pth,
                       thresholds=None, device_select=False, device_score=False):
     """The reference's periodic threshold reset (src/train.py:178-203): try conf_thresh 0.1 .. 0.9, keep the first one
@@ -45,14 +64,11 @@ def sweep_conf_thresh(dataloader, filelist, model, criterion, postprocessor, sco
     rows with device_select, ``add_rows``; host rows otherwise, ``add_dict``) without CSV files, and only the last threshold's
     CSV files are written, so ``output_pth`` ends up as the host sweep leaves it.
     -> (new_thresh, [[ER, F, LE, LR, SELD] per threshold], mean validation loss)"""
-    import numpy as np
     from . import ops
     from .seld_metrics import DeviceSELDScorer
     if device_score and not isinstance(scorer, DeviceSELDScorer):
         raise ValueError("sweep_conf_thresh: device_score=True needs a seld_metrics.DeviceSELDScorer (got %s)"
                          % type(scorer).__name__)
-    if thresholds is None:
-        thresholds = np.arange(0.1, 1.0, 0.1)
     model.eval()
     decoded, total, n = [], None, 0
     with torch.no_grad():
@@ -67,10 +83,9 @@ def sweep_conf_thresh(dataloader, filelist, model, criterion, postprocessor, sco
             else:
                 decoded.append(postprocessor.decode(output))
             n = i + 1
-    new_thresh, best, table = postprocessor.get_conf_thresh(), 9999.0, []
-    for k, th in enumerate(thresholds):
-        postprocessor.set_conf_thresh(th)
-        write = not device_score or k == len(thresholds) - 1
+
+    def score(k, th, is_last):
+        write = not device_score or is_last
         if write:
             delete_and_create_folder(output_pth)
         if device_score:
@@ -87,11 +102,9 @@ def sweep_conf_thresh(dataloader, filelist, model, criterion, postprocessor, sco
                     scorer.add_dict(filelist[i], rows)
             if write:
                 write_seld_output_file(os.path.join(output_pth, filelist[i] + ".csv"), rows)
-        er, f, le, lr, seld = (scorer.scores() if device_score else scorer.get_SELD_Results(output_pth))[:5]
-        table.append([er, f, le, lr, seld])
-        if seld < best:
-            new_thresh, best = th, seld
-    postprocessor.set_conf_thresh(new_thresh)
+        return scorer.scores() if device_score else scorer.get_SELD_Results(output_pth)
+
+    new_thresh, table = _sweep_thresholds(postprocessor, thresholds, score)
     return new_thresh, table, (float(total) / max(n, 1) if total is not None else 0.0)
 
 
@@ -173,15 +186,17 @@ def test_epoch_audio(dataset, model, features, criterion, postprocessor, device,
     return float(total) / max(n, 1) if total is not None else 0.0
 
 
-def _corpus_batch(corpus, idx, model, features, criterion, postprocessor, forward, acc):
-    """One batch of an HBM-resident evaluation split: ``launch`` -> forward (+ decode) -> the per-clip losses into ``acc``.
-    -> the decoded batch (a recorded graph's static output when ``forward`` replays one).  No host synchronisation."""
-    from . import ops
-    b = len(idx)
+# ------------------------------------------------------------------------------------- the device loops' shared stages
+def _forward_decode(launch, shape, model, features, postprocessor, forward):
+    """``launch(audio_out)`` (audio_out: the recorded graph's static input of ``shape`` when ``forward`` has one, so the gather
+    writes the graph's input itself; else None) -> the audio, or (audio, target, row_start); then ``forward(audio)`` or the
+    eager forward, and ``decode_device`` if nothing decoded yet.  -> (what ``launch`` returned, output, decoded batch: a
+    recorded graph's static output when ``forward`` replays one).  No host synchronisation."""
     audio_out = None
     if forward is not None and hasattr(forward, "static_input"):
-        audio_out = forward.static_input((b, corpus.n_hops[idx[0]], 4))      # the gather writes the graph's input itself
-    audio, target, row_start = corpus.launch(idx, audio_out)
+        audio_out = forward.static_input(shape)
+    launched = launch(audio_out)
+    audio = launched[0] if isinstance(launched, tuple) else launched
     dec = None
     if forward is not None:
         output, dec = forward(audio)
@@ -189,29 +204,61 @@ def _corpus_batch(corpus, idx, model, features, criterion, postprocessor, forwar
         output = model(features(audio, channels_last8=True), channels_last8=True)
     if dec is None:
         dec = postprocessor.decode_device(output)
-    if row_start is not None:                              # AD-YOLO: every clip's loss in one call, normalised per clip
-        cfg = getattr(criterion, "loss", criterion).cfg
+    return launched, output, dec
+
+
+def _accumulate_loss(acc, criterion, output, target, row_start, n):
+    """The losses of the batch's first ``n`` items (clips, or windows of a pass) into the device accumulator ``acc``."""
+    from . import ops
+    if row_start is not None:                              # AD-YOLO: every item's loss in one call, normalised per item; one
+        cfg = getattr(criterion, "loss", criterion).cfg    # without rows is left out
         ops.adyolo_loss_per_clip(output.contiguous(), target, row_start, cfg["nb_classes"], cfg["grid"], cfg["anchors"],
                                  cfg["thr"], cfg["gains"], cfg["grid_size"], cfg["g_overlap"], acc=acc)
-    else:                                                  # class-wise heads: the existing entry point on each clip's slice
-        for k in range(b):
+    else:                                                  # class-wise heads: the existing entry point on each item's slice
+        for k in range(n):
             ops.loss_accumulate(acc, criterion(output[k:k + 1], target[k:k + 1]).reshape(1))
+
+
+def _corpus_batch(corpus, idx, model, features, criterion, postprocessor, forward, acc, comb=None):
+    """One batch of an HBM-resident evaluation split: ``launch`` -> forward (+ decode) -> the per-clip losses into ``acc``.
+    comb: a further view of the batch instead (rotation test-time augmentation): ``launch_view`` into the same graph input, no
+    labels, no loss.  -> the decoded batch.  No host synchronisation."""
+    launch = (lambda out: corpus.launch(idx, out)) if comb is None else (lambda out: corpus.launch_view(idx, comb, out))
+    launched, output, dec = _forward_decode(launch, (len(idx), corpus.n_hops[idx[0]], 4), model, features, postprocessor, forward)
+    if comb is None:
+        _accumulate_loss(acc, criterion, output, launched[1], launched[2], len(idx))
     return dec
 
 
 def _corpus_view(corpus, idx, comb, model, features, postprocessor, forward):
-    """A further view of the batch ``_corpus_batch`` ran (rotation test-time augmentation): ``launch_view`` into the same graph
-    input -> forward -> the decoded batch.  No labels, no loss, no host synchronisation."""
-    audio_out = None
-    if forward is not None and hasattr(forward, "static_input"):
-        audio_out = forward.static_input((len(idx), corpus.n_hops[idx[0]], 4))
-    audio = corpus.launch_view(idx, comb, audio_out)
-    dec = None
-    if forward is not None:
-        output, dec = forward(audio)
-    else:
-        output = model(features(audio, channels_last8=True), channels_last8=True)
-    return dec if dec is not None else postprocessor.decode_device(output)
+    """View ``comb`` of the batch ``_corpus_batch`` ran -> the decoded batch."""
+    return _corpus_batch(corpus, idx, model, features, None, postprocessor, forward, None, comb)
+
+
+def _window_pass(corpus, p, model, features, criterion, postprocessor, forward, acc, stitched, comb=None):
+    """One pass of a windowed loop: ``launch`` -> forward (+ decode) -> the window losses into ``acc`` (criterion=None, the
+    inference corpus: audio only, no loss) -> ``decode_stitch`` -> (``stitched``, which is made on the first pass and handed
+    back; the pass's run of decoded frames, a view of it).  comb: a further view of the pass instead (rotation test-time
+    augmentation): ``launch_view`` into the same graph input, no labels, no loss, the same pass table into the same
+    ``stitched`` -- the caller has selected the previous view's run before this one is made.  No host synchronisation."""
+    from . import ops
+    b, wf = corpus.batch_size, corpus.window_frames
+    launch = (lambda out: corpus.launch(p, out)) if comb is None else (lambda out: corpus.launch_view(p, comb, out))
+    launched, output, dec = _forward_decode(launch, (b, corpus.n_samples, 4), model, features, postprocessor, forward)
+    if dec.shape[0] != b * wf:
+        raise ValueError("%s: %d decoded frames from %d windows of %d label frames (the model's frame rate is not the label "
+                         "hop's)" % (type(corpus).__name__, dec.shape[0], b, wf))
+    if comb is None and criterion is not None:
+        _accumulate_loss(acc, criterion, output, launched[1], launched[2], corpus.windows_in_pass(p))
+    if stitched is None:
+        stitched = torch.empty_like(dec)
+    ops.decode_stitch(dec, corpus.pass_table(p), wf, corpus.pass_base[p], stitched, corpus.status)
+    return stitched, stitched[:corpus.pass_frames[p]]
+
+
+def _window_view(corpus, p, comb, model, features, postprocessor, forward, stitched):
+    """View ``comb`` of the pass ``_window_pass`` ran -> the pass's run under the view."""
+    return _window_pass(corpus, p, model, features, None, postprocessor, forward, None, stitched, comb)[1]
 
 
 class _ViewMerge:
@@ -272,20 +319,29 @@ class _ViewMerge:
                              buf["rows"], buf["counts"], trim=trim)
 
 
+def _window_merge(tta, postprocessor, corpus):
+    """The ``_ViewMerge`` of a windowed loop: its pool and workspace made once, for the longest run of the split."""
+    return _ViewMerge(tta, postprocessor, corpus.device, max_frames=max(corpus.pass_frames))
+
+
+def _track_opts(track, name):
+    missing = [k for k in ("gate_deg", "max_gap", "min_len", "smooth") if k not in track]
+    if missing:
+        raise ValueError("%s: %r lacks %s (augmentations.track_options makes the dict)" % (name, track, missing))
+    return dict(track)
+
+
 class _Tracker:
     """The device half of tracking for the corpus loops: a batch's selected (or merged) rows linked into tracks
     (``LabelPostProcessor.track_device_rows``).  track: the dict of ``augmentations.track_options``.  The buffers are made once
     per batch shape; ``status`` collects the ADYOLO_TRACK_* bits of the pass."""
 
     def __init__(self, track, device):
-        missing = [k for k in ("gate_deg", "max_gap", "min_len", "smooth") if k not in track]
-        if missing:
-            raise ValueError("track: %r lacks %s (augmentations.track_options makes the dict)" % (track, missing))
-        self.opts = dict(track)
+        self.opts = _track_opts(track, "track")
         self.status = torch.zeros(1, dtype=torch.int32, device=device)
         self._buffers = {}
 
-    def tracked(self, postprocessor, rows, counts, n_clips, trim):
+    def tracked(self, postprocessor, rows, counts, n_clips, trim, p=None):
         """-> (rows', counts', ids) of the batch."""
         from . import ops
         key = counts.numel()
@@ -302,10 +358,7 @@ class _RunTracker:
     ADYOLO_TRACK_* bits.  ``reset()`` empties the carry: before a split is walked again from its first pass."""
 
     def __init__(self, tracking, corpus):
-        missing = [k for k in ("gate_deg", "max_gap", "min_len", "smooth") if k not in tracking]
-        if missing:
-            raise ValueError("tracking: %r lacks %s (augmentations.track_options makes the dict)" % (tracking, missing))
-        self.opts = dict(tracking)
+        self.opts = _track_opts(tracking, "tracking")
         self.plan = corpus.track_plan(self.opts)
         self.hold = self.plan["hold"]
         self.status = torch.zeros(1, dtype=torch.int32, device=corpus.device)
@@ -316,9 +369,10 @@ class _RunTracker:
         if self.carry is not None:
             self.carry.zero_()
 
-    def tracked(self, postprocessor, p, rows, counts, trim):
-        """Pass ``p``'s selected (rows, counts) -> (rows', counts', ids) of the frames the pass emits (``plan['pass_frames'][p]``
-        of them, from ``plan['pass_base'][p]`` on the common axis)."""
+    def tracked(self, postprocessor, rows, counts, n_clips, trim, p):
+        """Pass ``p``'s selected (rows, counts) of its one run -> (rows', counts', ids) of the frames the pass emits
+        (``plan['pass_frames'][p]`` of them, none for a pass that holds all its frames back, from ``plan['pass_base'][p]`` on
+        the common axis)."""
         from . import ops
         if self.carry is None:
             self.carry = ops.track_carry(self.status.device, postprocessor.nb_classes, self.hold)
@@ -330,18 +384,42 @@ class _RunTracker:
                                               status=self.status, trim=trim, emitted=self.plan["pass_frames"][p])
 
 
-def _corpus_finish(corpus, acc, tta_status=None, track_status=None):
-    """The one synchronisation of a pass: the loss accumulator {sum, count} and the corpus status word -> the mean loss.
-    tta_status / track_status: the status words of a pass with test-time augmentation / tracking, read in the same copy."""
+def _further_views(merge):
+    return () if merge is None else merge.views[1:]
+
+
+def _select_rows(postprocessor, dec, more, merge, tracker, n_clips, trim, p=None):
+    """The rows of a batch of ``n_clips`` clips, or of pass ``p``'s one run: ``dec`` (view 0's decoded frames) selected -- or,
+    with ``merge``, selected, parked and merged with the further views' that the iterable ``more`` yields ONE AT A TIME (a
+    recorded graph's output and the stitch buffer are reused, so a view is made only when the one before it is parked) --
+    then, with ``tracker``, linked into tracks.  Only the last stage that runs trims (reads the row total: a
+    synchronisation); the others hand their capacity buffers on.  -> (rows, counts, ids: None without a tracker)"""
+    if merge is None:
+        rows, counts = postprocessor.select_device_rows(dec, n_clips, trim=trim and tracker is None)
+    else:
+        rows, counts = merge.merged(postprocessor, chain((dec,), more), n_clips, trim=trim and tracker is None)
+    if tracker is None:
+        return rows, counts, None
+    return tracker.tracked(postprocessor, rows, counts, n_clips, trim, p)
+
+
+def _read_status(corpus, acc=None, merge=None, tracker=None):
+    """The one synchronisation that ends a walk over the split: the corpus status word and, when they are there, the loss
+    accumulator {sum, count} and the status words of the view merge and the tracker, in ONE copy; every word checked.
+    -> the mean loss (with ``acc``)."""
     from . import ops
-    more = [s for s in (tta_status, track_status) if s is not None]
-    acc_h, status_h, *more_h = ops.to_host_many(acc, corpus.status, *more)
-    corpus.check(int(status_h[0]))
-    if tta_status is not None:
-        ops.tta_status_check(int(more_h[0][0]))
-    if track_status is not None:
-        ops.track_status_check(int(more_h[-1][0]))
-    total, n = acc_h[0], int(acc_h[1])
+    parts = {"loss": acc, "corpus": corpus.status, "tta": None if merge is None else merge.status,
+             "track": None if tracker is None else tracker.status}
+    parts = {k: t for k, t in parts.items() if t is not None}
+    host = dict(zip(parts, ops.to_host_many(*parts.values())))
+    corpus.check(int(host["corpus"][0]))
+    if merge is not None:
+        ops.tta_status_check(int(host["tta"][0]))
+    if tracker is not None:
+        ops.track_status_check(int(host["track"][0]))
+    if acc is None:
+        return None
+    total, n = host["loss"][0], int(host["loss"][1])
     return float(total) / max(n, 1) if n else 0.0
 
 
@@ -361,6 +439,31 @@ def _write_rows(output_pth, names, rows, counts, ids=None):
         write_seld_output_file(os.path.join(output_pth, name + ".csv"), clip_rows, clip_ids)
 
 
+def _write_pass(corpus, base, rows, counts, ids, outs, out_ids):
+    """The rows (trimmed) of a pass's run, which starts at ``base`` on the common axis -> the host in one copy, onto each
+    recording's own frame axis in ``outs``.  ids: the rows' track ids (tracking is on), which go to ``out_ids`` {frame of the
+    recording: [id, ...]} per recording, parallel to ``outs``."""
+    import numpy as np
+    from . import ops
+    from .corpus import split_pass_rows
+    rows_h, counts_h, *ids_h = [t.numpy() for t in ops.to_host_many(*(t for t in (rows, counts, ids) if t is not None))]
+    for r, found in split_pass_rows(rows_h, counts_h, base, corpus.frame_start).items():
+        outs[r].update(found)                                                # (a recording's passes come in frame order)
+    if ids is None:
+        return
+    ends = np.cumsum(counts_h.astype(np.int64))
+    ids_h = ids_h[0].tolist()
+    for f in np.flatnonzero(counts_h).tolist():
+        r = int(np.searchsorted(corpus.frame_start, base + f, "right")) - 1
+        out_ids[r][base + f - int(corpus.frame_start[r])] = ids_h[int(ends[f]) - int(counts_h[f]):int(ends[f])]
+
+
+def _write_recordings(output_pth, names, outs, out_ids=None):
+    for k, (name, rows) in enumerate(zip(names, outs)):
+        write_seld_output_file(os.path.join(output_pth, name + ".csv"), rows, None if out_ids is None else out_ids[k])
+
+
+# ------------------------------------------------------------------------------------------------ whole clips from HBM
 def test_epoch_corpus(corpus, model, features, criterion, postprocessor, output_pth=None, batch_size=8, forward=None,
                       device_scorer=None, tta=None, track=None):
     """``test_epoch_audio(device_select=True)`` from an HBM-resident split (``corpus.EvalDeviceCorpus``): the same batches,
@@ -393,25 +496,17 @@ def test_epoch_corpus(corpus, model, features, criterion, postprocessor, output_
     acc = ops.loss_accumulator(corpus.device)
     merge = _ViewMerge(tta, postprocessor, corpus.device) if tta is not None else None
     tracker = _Tracker(track, corpus.device) if track is not None else None
-    trim = output_pth is not None
     with torch.no_grad():
         for idx in corpus.batches(batch_size):
             clips = [names[i] for i in idx]
             dec = _corpus_batch(corpus, idx, model, features, criterion, postprocessor, forward, acc)
-            if merge is None:
-                rows, counts = postprocessor.select_device_rows(dec, len(clips), trim=trim and tracker is None)
-            else:
-                views = (dec if k == 0 else _corpus_view(corpus, idx, v, model, features, postprocessor, forward)
-                         for k, v in enumerate(merge.views))
-                rows, counts = merge.merged(postprocessor, views, len(clips), trim=trim and tracker is None)
-            ids = None
-            if tracker is not None:
-                rows, counts, ids = tracker.tracked(postprocessor, rows, counts, len(clips), trim=trim)
+            more = (_corpus_view(corpus, idx, v, model, features, postprocessor, forward) for v in _further_views(merge))
+            rows, counts, ids = _select_rows(postprocessor, dec, more, merge, tracker, len(clips), output_pth is not None)
             if device_scorer is not None:
                 device_scorer.add_rows(rows, counts, clips)
             if output_pth is not None:
                 _write_rows(output_pth, clips, rows, counts, ids)
-    return _corpus_finish(corpus, acc, None if merge is None else merge.status, None if tracker is None else tracker.status)
+    return _read_status(corpus, acc, merge, tracker)
 
 
 def sweep_conf_thresh_corpus(corpus, model, features, criterion, postprocessor, scorer, thresholds=None, output_pth=None,
@@ -422,18 +517,14 @@ def sweep_conf_thresh_corpus(corpus, model, features, criterion, postprocessor, 
     threshold's CSV files are written, as the host sweep leaves them.  Clips without AD-YOLO rows are left out of the mean
     loss (the host sweep cannot take them at all).  -> (new_thresh, [[ER, F, LE, LR, SELD] per threshold], mean loss)
 
-    tta: as ``test_epoch_corpus``.  Every VIEW's decode of every batch is kept on the device, and each threshold selects,
-    collects and merges them again; the merge's status word is read once, after the last threshold.
-
-    track: as ``test_epoch_corpus``.  Each threshold's rows (merged ones with ``tta``) are linked into tracks before they are
-    scored and written; the status word is read once, after the last threshold, in the copy that reads the merge's."""
-    import numpy as np
-    from . import ops
+    tta, track: as ``test_epoch_corpus``, redone per threshold: every VIEW's decode of every batch is kept on the device, and
+    each threshold selects, collects and merges them again and links the rows before they are scored and written.  The loss
+    and the corpus status word are read after the forward phase; the status words of the merge and the tracker once, in one
+    copy, after the last threshold."""
     from .seld_metrics import DeviceSELDScorer
     if not isinstance(scorer, DeviceSELDScorer):
         raise ValueError("sweep_conf_thresh_corpus needs a seld_metrics.DeviceSELDScorer (got %s)" % type(scorer).__name__)
-    if thresholds is None:
-        thresholds = np.arange(0.1, 1.0, 0.1)
+    from . import ops
     model.eval()
     names = corpus.get_filelist()
     corpus.reset_status()
@@ -444,45 +535,30 @@ def sweep_conf_thresh_corpus(corpus, model, features, criterion, postprocessor, 
     with torch.no_grad():
         for idx in corpus.batches(batch_size):
             dec = _corpus_batch(corpus, idx, model, features, criterion, postprocessor, forward, acc)
-            dec = dec.clone() if forward is not None else dec                                         # (a graph's output is reused)
-            if merge is not None:
-                dec = [dec] + [_corpus_view(corpus, idx, v, model, features, postprocessor, forward).clone()
-                               for v in merge.views[1:]]
-            decoded.append(([names[i] for i in idx], dec))
-    loss = _corpus_finish(corpus, acc)
-    new_thresh, best, table = postprocessor.get_conf_thresh(), 9999.0, []
-    for k, th in enumerate(thresholds):
-        postprocessor.set_conf_thresh(th)
-        write = output_pth is not None and k == len(thresholds) - 1
+            views = [dec.clone() if forward is not None else dec]                                     # (a graph's output is reused)
+            views += [_corpus_view(corpus, idx, v, model, features, postprocessor, forward).clone() for v in _further_views(merge)]
+            decoded.append(([names[i] for i in idx], views))
+    loss = _read_status(corpus, acc)
+
+    def score(k, th, is_last):
+        write = is_last and output_pth is not None
         if write:
             delete_and_create_folder(output_pth)
         scorer.reset()
-        for clips, dec in decoded:
-            if merge is None:
-                rows, counts = postprocessor.select_device_rows(dec, len(clips), trim=write and tracker is None)
-            else:
-                rows, counts = merge.merged(postprocessor, dec, len(clips), trim=write and tracker is None)
-            ids = None
-            if tracker is not None:
-                rows, counts, ids = tracker.tracked(postprocessor, rows, counts, len(clips), trim=write)
+        for clips, views in decoded:
+            rows, counts, ids = _select_rows(postprocessor, views[0], views[1:], merge, tracker, len(clips), write)
             scorer.add_rows(rows, counts, clips)
             if write:
                 _write_rows(output_pth, clips, rows, counts, ids)
-        er, f, le, lr, seld = scorer.scores()[:5]
-        table.append([er, f, le, lr, seld])
-        if seld < best:
-            new_thresh, best = th, seld
-    postprocessor.set_conf_thresh(new_thresh)
-    if merge is not None and tracker is None:
-        ops.tta_status_check(int(ops.to_host(merge.status)[0]))
-    elif tracker is not None:
-        words = [int(w[0]) for w in ops.to_host_many(*([merge.status] if merge is not None else []), tracker.status)]
-        if merge is not None:
-            ops.tta_status_check(words[0])
-        ops.track_status_check(words[-1])
+        return scorer.scores()
+
+    new_thresh, table = _sweep_thresholds(postprocessor, thresholds, score)
+    if merge is not None or tracker is not None:
+        _read_status(corpus, None, merge, tracker)
     return new_thresh, table, loss
 
 
+# ------------------------------------------------------------------------------------- recordings of any length, in windows
 def infer_epoch_corpus(corpus, model, features, postprocessor, output_pth, forward=None, tracking=None, tta=None):
     """Inference on recordings of any length from an HBM-resident folder (``corpus.InferDeviceCorpus``): every recording cut
     into overlapping windows of one shape, the windows run ``corpus.batch_size`` at a time -- so the whole folder has ONE input
@@ -494,172 +570,31 @@ def infer_epoch_corpus(corpus, model, features, postprocessor, output_pth, forwa
     for a recording without rows or without a label frame.  No audio crosses PCIe; nothing is uploaded per pass.
     -> {'recordings', 'windows', 'passes', 'frames'}.
 
-    Tracking (``tracking``: None, or the dict of ``augmentations.track_options``): every pass's selected rows are linked into
-    tracks on the device with the state carried from pass to pass (``postprocess.track_run``; csrc/track.hip
-    ``adyolo_track_run``), so a recording cut by any number of passes gets the rows and ids ``postprocess.track_rows`` gives on
-    it whole, bit for bit.  A pass then emits its frames without the last D of a recording that goes on in the next pass -- a
-    gap fill or the erasure of a short track can still reach them -- and with the D it held back before
-    (``corpus.track_plan``, D = ``postprocess.track_hold``).  The emitted rows go to the files, whose third column carries the
-    track ids; the status word is read with the corpus's at the end (the caps of the definition only warn).  None leaves
-    every call, allocation and bit as it is.
-
-    tta (rotation test-time augmentation): None, or what ``test_epoch_windows`` takes, with the same meaning: the pass above
-    is view 0, every further view is ``corpus.launch_view`` into the same input, forward, decode and stitch with the same
-    pass table, each run selected and parked before the next is made, then ``ops.tta_merge``; the merged rows are what is
-    written and, with ``tracking``, what is linked.  The pool and the workspace are allocated once, for the longest run; the
-    merge's status word joins the one copy at the end (an overflow raises, naming ``tta_max_rows_per_frame``).  None
-    leaves every call, allocation, synchronisation and bit as it is."""
-    from . import ops
-    from .corpus import split_pass_rows
+    Tracking (``tracking``) and tta: as ``test_epoch_windows`` (``postprocess.track_run`` with the state carried from pass to
+    pass; the views merged, then linked), without labels, loss and scorer: the emitted rows go to the files only, with one
+    synchronisation per pass as without them, and the status words of the merge and the tracker are read with the corpus's in
+    the one copy at the end.  None leaves every call, allocation, synchronisation and bit as it is."""
     model.eval()
     delete_and_create_folder(output_pth)
     names = corpus.get_filelist()
     corpus.reset_status()
-    b, n, wf = corpus.batch_size, corpus.n_samples, corpus.window_frames
     outs = [{} for _ in names]
     merge = _window_merge(tta, postprocessor, corpus) if tta is not None and corpus.n_passes else None
     tracker = _RunTracker(tracking, corpus) if tracking is not None else None
     out_ids = [{} for _ in names] if tracker is not None else None
+    base = corpus.pass_base if tracker is None else tracker.plan["pass_base"]
     stitched = None
     with torch.no_grad():
         for p in range(corpus.n_passes):
-            audio_out = None
-            if forward is not None and hasattr(forward, "static_input"):
-                audio_out = forward.static_input((b, n, 4))                  # the gather writes the graph's input itself
-            audio = corpus.launch(p, audio_out)
-            dec = None
-            if forward is not None:
-                output, dec = forward(audio)
-            else:
-                output = model(features(audio, channels_last8=True), channels_last8=True)
-            if dec is None:
-                dec = postprocessor.decode_device(output)
-            if dec.shape[0] != b * wf:
-                raise ValueError("infer_epoch_corpus: %d decoded frames from %d windows of %d label frames (the model's frame rate "
-                                 "is not the label hop's)" % (dec.shape[0], b, wf))
-            if stitched is None:
-                stitched = torch.empty_like(dec)
-            frames = corpus.pass_frames[p]
-            ops.decode_stitch(dec, corpus.pass_table(p), wf, corpus.pass_base[p], stitched, corpus.status)
-            if merge is not None:                                            # this body is view 0; merge, then link
-                views = (stitched[:frames] if k == 0 else
-                         _window_view(corpus, p, v, model, features, postprocessor, forward, stitched)
-                         for k, v in enumerate(merge.views))
-                rows, counts = merge.merged(postprocessor, views, 1, trim=tracker is None)
-            if tracker is not None:
-                if merge is None:
-                    rows, counts = postprocessor.select_device_rows(stitched[:frames], 1, trim=False)
-                rows, counts, ids = tracker.tracked(postprocessor, p, rows, counts, trim=True)
-                if counts.numel():
-                    _write_pass_tracks(corpus, tracker.plan["pass_base"][p], rows, counts, ids, outs, out_ids)
-                continue
-            if merge is None:
-                rows, counts = postprocessor.select_device_rows(stitched[:frames], 1)
-            rows_h, counts_h = [t.numpy() for t in ops.to_host_many(rows, counts)]
-            for r, found in split_pass_rows(rows_h, counts_h, corpus.pass_base[p], corpus.frame_start).items():
-                outs[r].update(found)                                        # (a recording's passes come in frame order)
-    if tracker is None and merge is None:
-        corpus.check()
-    else:
-        more = [m.status for m in (merge, tracker) if m is not None]
-        status_h, *more_h = ops.to_host_many(corpus.status, *more)
-        corpus.check(int(status_h[0]))
-        if merge is not None:
-            ops.tta_status_check(int(more_h[0][0]))
-        if tracker is not None:
-            ops.track_status_check(int(more_h[-1][0]))
+            stitched, run = _window_pass(corpus, p, model, features, None, postprocessor, forward, None, stitched)
+            more = (_window_view(corpus, p, v, model, features, postprocessor, forward, stitched) for v in _further_views(merge))
+            rows, counts, ids = _select_rows(postprocessor, run, more, merge, tracker, 1, True, p)
+            if counts.numel():                                               # (a tracked pass may hold all its frames back)
+                _write_pass(corpus, base[p], rows, counts, ids, outs, out_ids)
+    _read_status(corpus, None, merge, tracker)
     _write_recordings(output_pth, names, outs, out_ids)
     return {"recordings": len(names), "windows": corpus.n_windows, "passes": corpus.n_passes,
             "frames": int(corpus.frame_start[-1])}
-
-
-def _window_pass(corpus, p, model, features, criterion, postprocessor, forward, acc, stitched):
-    """One pass of a labelled windowed evaluation: ``launch`` -> forward (+ decode) -> the window losses into ``acc`` ->
-    ``decode_stitch`` -> the pass's run of decoded frames (a view of ``stitched``, which is made on the first pass and handed
-    back).  No host synchronisation."""
-    from . import ops
-    b, n, wf = corpus.batch_size, corpus.n_samples, corpus.window_frames
-    audio_out = None
-    if forward is not None and hasattr(forward, "static_input"):
-        audio_out = forward.static_input((b, n, 4))                          # the gather writes the graph's input itself
-    audio, target, row_start = corpus.launch(p, audio_out)
-    dec = None
-    if forward is not None:
-        output, dec = forward(audio)
-    else:
-        output = model(features(audio, channels_last8=True), channels_last8=True)
-    if dec is None:
-        dec = postprocessor.decode_device(output)
-    if dec.shape[0] != b * wf:
-        raise ValueError("test_epoch_windows: %d decoded frames from %d windows of %d label frames (the model's frame rate is "
-                         "not the label hop's)" % (dec.shape[0], b, wf))
-    if row_start is not None:                              # AD-YOLO: every window's loss in one call; an empty window has no rows
-        cfg = getattr(criterion, "loss", criterion).cfg
-        ops.adyolo_loss_per_clip(output.contiguous(), target, row_start, cfg["nb_classes"], cfg["grid"], cfg["anchors"],
-                                 cfg["thr"], cfg["gains"], cfg["grid_size"], cfg["g_overlap"], acc=acc)
-    else:                                                  # class-wise heads: the criterion on each window's slice, empty ones left out
-        for k in range(corpus.windows_in_pass(p)):
-            ops.loss_accumulate(acc, criterion(output[k:k + 1], target[k:k + 1]).reshape(1))
-    if stitched is None:
-        stitched = torch.empty_like(dec)
-    ops.decode_stitch(dec, corpus.pass_table(p), wf, corpus.pass_base[p], stitched, corpus.status)
-    return stitched, stitched[:corpus.pass_frames[p]]
-
-
-def _window_view(corpus, p, comb, model, features, postprocessor, forward, stitched):
-    """A further view of the pass ``_window_pass`` (or the inference loop's body) ran (rotation test-time augmentation):
-    ``launch_view`` into the same graph input -> forward -> decode -> ``decode_stitch`` with the same pass table into the same
-    ``stitched`` -> the pass's run under the view.  The caller has selected the previous view's run before this one is made.  No
-    labels, no loss, no host synchronisation."""
-    from . import ops
-    audio_out = None
-    if forward is not None and hasattr(forward, "static_input"):
-        audio_out = forward.static_input((corpus.batch_size, corpus.n_samples, 4))
-    audio = corpus.launch_view(p, comb, audio_out)
-    dec = None
-    if forward is not None:
-        output, dec = forward(audio)
-    else:
-        output = model(features(audio, channels_last8=True), channels_last8=True)
-    if dec is None:
-        dec = postprocessor.decode_device(output)
-    ops.decode_stitch(dec, corpus.pass_table(p), corpus.window_frames, corpus.pass_base[p], stitched, corpus.status)
-    return stitched[:corpus.pass_frames[p]]
-
-
-def _window_merge(tta, postprocessor, corpus):
-    """The ``_ViewMerge`` of a windowed loop: its pool and workspace made once, for the longest run of the split."""
-    return _ViewMerge(tta, postprocessor, corpus.device, max_frames=max(corpus.pass_frames))
-
-
-def _write_pass_rows(corpus, p, rows, counts, outs):
-    """The selected rows of pass ``p``'s run (trimmed) -> the host, onto each recording's own frame axis in ``outs``."""
-    from . import ops
-    from .corpus import split_pass_rows
-    rows_h, counts_h = [t.numpy() for t in ops.to_host_many(rows, counts)]
-    for r, found in split_pass_rows(rows_h, counts_h, corpus.pass_base[p], corpus.frame_start).items():
-        outs[r].update(found)                                                # (a recording's passes come in frame order)
-
-
-def _write_pass_tracks(corpus, base, rows, counts, ids, outs, out_ids):
-    """``_write_pass_rows`` for a tracked pass: the emitted run starts at ``base`` on the common axis, and the rows' track ids go
-    to ``out_ids`` {frame of the recording: [id, ...]} per recording, parallel to ``outs``."""
-    import numpy as np
-    from . import ops
-    from .corpus import split_pass_rows
-    rows_h, counts_h, ids_h = [t.numpy() for t in ops.to_host_many(rows, counts, ids)]
-    for r, found in split_pass_rows(rows_h, counts_h, base, corpus.frame_start).items():
-        outs[r].update(found)
-    ends = np.cumsum(counts_h.astype(np.int64))
-    ids_h = ids_h.tolist()
-    for f in np.flatnonzero(counts_h).tolist():
-        r = int(np.searchsorted(corpus.frame_start, base + f, "right")) - 1
-        out_ids[r][base + f - int(corpus.frame_start[r])] = ids_h[int(ends[f]) - int(counts_h[f]):int(ends[f])]
-
-
-def _write_recordings(output_pth, names, outs, out_ids=None):
-    for k, (name, rows) in enumerate(zip(names, outs)):
-        write_seld_output_file(os.path.join(output_pth, name + ".csv"), rows, None if out_ids is None else out_ids[k])
 
 
 def test_epoch_windows(corpus, model, features, criterion, postprocessor, output_pth=None, forward=None, device_scorer=None,
@@ -689,9 +624,9 @@ def test_epoch_windows(corpus, model, features, criterion, postprocessor, output
     ``adyolo_track_run``), so a recording cut by any number of passes gets the rows and ids ``postprocess.track_rows`` gives on
     it whole, bit for bit.  A pass then emits its frames without the last D of a recording that goes on in the next pass -- a
     gap fill or the erasure of a short track can still reach them -- and with the D it held back before
-    (``corpus.track_plan``).  The emitted rows go to the scorer (its segment tables on the emitted bounds) and to the files,
-    whose third column carries the track ids; the status word is read in the one end-of-pass copy (the caps of the definition
-    only warn).  None leaves every call, allocation and bit as it is.
+    (``corpus.track_plan``, D = ``postprocess.track_hold``).  The emitted rows go to the scorer (its segment tables on the
+    emitted bounds) and to the files, whose third column carries the track ids; the status word is read in the one
+    end-of-pass copy (the caps of the definition only warn).  None leaves every call, allocation and bit as it is.
 
     tta (rotation test-time augmentation): None, or what ``test_epoch_corpus`` takes (a list of views starting with 0, or the
     dict of ``augmentations.tta_options``).  View 0 is the plain pass: labels, loss -- the same float as without views --
@@ -716,29 +651,22 @@ def test_epoch_windows(corpus, model, features, criterion, postprocessor, output
     segments = corpus.segments(device_scorer, bounds=bounds) if device_scorer is not None else None
     outs = [{} for _ in names]
     out_ids = [{} for _ in names] if tracker is not None else None
+    base = corpus.pass_base if tracker is None else tracker.plan["pass_base"]
     stitched = None
     with torch.no_grad():
         for p in range(corpus.n_passes):
             stitched, run = _window_pass(corpus, p, model, features, criterion, postprocessor, forward, acc, stitched)
-            if merge is None:
-                rows, counts = postprocessor.select_device_rows(run, 1, trim=output_pth is not None and tracker is None)
-            else:
-                views = (run if k == 0 else _window_view(corpus, p, v, model, features, postprocessor, forward, stitched)
-                         for k, v in enumerate(merge.views))
-                rows, counts = merge.merged(postprocessor, views, 1, trim=output_pth is not None and tracker is None)
-            if tracker is not None:
-                rows, counts, ids = tracker.tracked(postprocessor, p, rows, counts, trim=output_pth is not None)
-                if not counts.numel():                                       # the pass holds all its frames back
-                    continue
+            more = (_window_view(corpus, p, v, model, features, postprocessor, forward, stitched) for v in _further_views(merge))
+            rows, counts, ids = _select_rows(postprocessor, run, more, merge, tracker, 1, output_pth is not None, p)
+            if not counts.numel():                                           # a tracked pass that holds all its frames back
+                continue
             if device_scorer is not None:
                 device_scorer.add_run(rows, counts, segments[p])
-            if output_pth is not None and tracker is None:
-                _write_pass_rows(corpus, p, rows, counts, outs)
-            elif output_pth is not None:
-                _write_pass_tracks(corpus, tracker.plan["pass_base"][p], rows, counts, ids, outs, out_ids)
+            if output_pth is not None:
+                _write_pass(corpus, base[p], rows, counts, ids, outs, out_ids)
     if output_pth is not None:
         _write_recordings(output_pth, names, outs, out_ids)
-    return _corpus_finish(corpus, acc, None if merge is None else merge.status, None if tracker is None else tracker.status)
+    return _read_status(corpus, acc, merge, tracker)
 
 
 def sweep_conf_thresh_windows(corpus, model, features, criterion, postprocessor, scorer, thresholds=None, output_pth=None,
@@ -748,27 +676,17 @@ def sweep_conf_thresh_windows(corpus, model, features, criterion, postprocessor,
     ``scorer.add_run``; the chosen threshold is left set on the post-processor.  With ``output_pth`` the last threshold's CSV
     files are written.  The loss is ``test_epoch_windows``'s.  -> (new_thresh, [[ER, F, LE, LR, SELD] per threshold], mean loss)
 
-    Tracking (``tracking``: None, or the dict of ``augmentations.track_options``): every pass's selected rows are linked into
-    tracks on the device with the state carried from pass to pass (``postprocess.track_run``; csrc/track.hip
-    ``adyolo_track_run``), so a recording cut by any number of passes gets the rows and ids ``postprocess.track_rows`` gives on
-    it whole, bit for bit.  A pass then emits its frames without the last D of a recording that goes on in the next pass -- a
-    gap fill or the erasure of a short track can still reach them -- and with the D it held back before
-    (``corpus.track_plan``).  Per threshold the carry is emptied with the scorer; the emitted rows go to the scorer (its segment
-    tables on the emitted bounds) and, for the last threshold, to the files, whose third column carries the track ids; the
-    status word is read once, after the last threshold (the caps of the definition only warn).  None leaves every call,
-    allocation and bit as it is.
-
-    tta: as ``test_epoch_windows``.  Every VIEW's stitched run of every pass is kept (cloned) on the device -- passes x views x
-    run frames x the decode's record, i.e. views x (the split's label frames) x record x 4 bytes, against one such axis
-    without views -- and each threshold selects, collects and merges them again (then links, with ``tracking``); the
-    merge's status word is read once, after the last threshold, in the copy that reads the tracker's."""
-    import numpy as np
-    from . import ops
+    Tracking (``tracking``) and tta: as ``test_epoch_windows`` (``postprocess.track_run``), redone per threshold.  Every VIEW's
+    stitched run of every pass is kept (cloned) on the device -- passes x views x run frames x the decode's record, i.e.
+    views x (the split's label frames) x record x 4 bytes, against one such axis without views -- and each threshold empties
+    the tracker's carry with the scorer, then selects, collects, merges and links the runs again; the last threshold's
+    emitted rows also go to the files.  The loss and the corpus status word are read after the forward phase; the status
+    words of the merge and the tracker once, in one copy, after the last threshold.  None leaves every call, allocation and
+    bit as it is."""
     from .seld_metrics import DeviceSELDScorer
     if not isinstance(scorer, DeviceSELDScorer):
         raise ValueError("sweep_conf_thresh_windows needs a seld_metrics.DeviceSELDScorer (got %s)" % type(scorer).__name__)
-    if thresholds is None:
-        thresholds = np.arange(0.1, 1.0, 0.1)
+    from . import ops
     model.eval()
     names = corpus.get_filelist()
     corpus.reset_status()
@@ -776,54 +694,39 @@ def sweep_conf_thresh_windows(corpus, model, features, criterion, postprocessor,
     merge = _window_merge(tta, postprocessor, corpus) if tta is not None else None
     tracker = _RunTracker(tracking, corpus) if tracking is not None else None
     segments = corpus.segments(scorer, bounds=None if tracker is None else tracker.plan["bounds"])
+    base = corpus.pass_base if tracker is None else tracker.plan["pass_base"]
     runs, stitched = [], None
     with torch.no_grad():
         for p in range(corpus.n_passes):
             stitched, run = _window_pass(corpus, p, model, features, criterion, postprocessor, forward, acc, stitched)
-            run = run.clone()                                                # (the stitch buffer is reused)
-            if merge is not None:
-                run = [run] + [_window_view(corpus, p, v, model, features, postprocessor, forward, stitched).clone()
-                               for v in merge.views[1:]]
-            runs.append(run)
-    loss = _corpus_finish(corpus, acc)
-    new_thresh, best, table = postprocessor.get_conf_thresh(), 9999.0, []
-    for k, th in enumerate(thresholds):
-        postprocessor.set_conf_thresh(th)
-        write = output_pth is not None and k == len(thresholds) - 1
-        outs = [{} for _ in names]
+            views = [run.clone()]                                            # (the stitch buffer is reused)
+            views += [_window_view(corpus, p, v, model, features, postprocessor, forward, stitched).clone()
+                      for v in _further_views(merge)]
+            runs.append(views)
+    loss = _read_status(corpus, acc)
+
+    def score(k, th, is_last):
+        write = is_last and output_pth is not None
+        outs =[{} for _ in names]
         out_ids = [{} for _ in names] if tracker is not None else None
         scorer.reset()
         if tracker is not None:
             tracker.reset()
-        for p, run in enumerate(runs):
-            if merge is None:
-                rows, counts = postprocessor.select_device_rows(run, 1, trim=write and tracker is None)
-            else:
-                rows, counts = merge.merged(postprocessor, run, 1, trim=write and tracker is None)
-            if tracker is not None:
-                rows, counts, ids = tracker.tracked(postprocessor, p, rows, counts, trim=write)
-                if not counts.numel():
-                    continue
+        for p, views in enumerate(runs):
+            rows, counts, ids = _select_rows(postprocessor, views[0], views[1:], merge, tracker, 1, write, p)
+            if not counts.numel():
+                continue
             scorer.add_run(rows, counts, segments[p])
-            if write and tracker is None:
-                _write_pass_rows(corpus, p, rows, counts, outs)
-            elif write:
-                _write_pass_tracks(corpus, tracker.plan["pass_base"][p], rows, counts, ids, outs, out_ids)
+            if write:
+                _write_pass(corpus, base[p], rows, counts, ids, outs, out_ids)
         if write:
             delete_and_create_folder(output_pth)
             _write_recordings(output_pth, names, outs, out_ids)
-        er, f, le, lr, seld = scorer.scores()[:5]
-        table.append([er, f, le, lr, seld])
-        if seld < best:
-            new_thresh, best = th, seld
-    postprocessor.set_conf_thresh(new_thresh)
-    if merge is None and tracker is not None:
-        ops.track_status_check(int(ops.to_host(tracker.status)[0]))
-    elif merge is not None:
-        words = [int(w[0]) for w in ops.to_host_many(merge.status, *([tracker.status] if tracker is not None else []))]
-        ops.tta_status_check(words[0])
-        if tracker is not None:
-            ops.track_status_check(words[-1])
+        return scorer.scores()
+
+    new_thresh, table = _sweep_thresholds(postprocessor, thresholds, score)
+    if merge is not None or tracker is not None:
+        _read_status(corpus, None, merge, tracker)
     return new_thresh, table, loss
 
 

@@ -114,6 +114,7 @@ SIGNATURES = {
     "adyolo_track_carry_words": (L, [I, I]),
     "adyolo_track_run_workspace_words": (L, [L, I, I]),
     "adyolo_track_run": (I, [P, L, P, L, P, L, I, F, I, I, F, F, I, P, P, P, P, L, P, P, P]),
+    "adyolo_csv_format": (I, [P, L, P, L, P, P, L, P, P, L, P, P, P]),
     "adyolo_conv_gemm": (I, [P, P, P, P] + [I] * 13 + [P]),
     "adyolo_conv_gemm_plan": (I, [I] * 13 + [P]),
     "adyolo_pack_wk": (I, [P, P, I, I, I, I, I, P]),

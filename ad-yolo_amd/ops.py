@@ -1288,6 +1288,75 @@ def track_rows(rows, counts, n_clips, nb_classes, opts, buf=None, status=None, t
     return out[:total], out_counts[:frames], ids[:total]
 
 
+CSV_STATUS = ((1, "more bytes than the buffer holds: nothing was written (seg_bytes[-1] is the capacity needed)"),   # ADYOLO_CSV_*
+              (2, "frame counts negative or past the rows given"),
+              (4, "a class that is not finite or not within int32, or a negative track id"),
+              (8, "a segment table that does not ascend from frame 0 within the frames"))
+from .postprocess import CSV_LINE_MAX, CSV_OVERFLOW          # noqa: E402  (defined once, beside format_rows; a test holds them to the headers)
+
+
+def csv_status_check(word):
+    """Raise ``AdyoloHipError`` for any ADYOLO_CSV_* bit in a status word already read to the host: every one of them means
+    the bytes are not the files'."""
+    word = int(word)
+    if word:
+        raise _lib.AdyoloHipError("adyolo csv_format failed (status 0x%x): %s"
+                                  % (word, "; ".join(msg for bit, msg in CSV_STATUS if word & bit)))
+
+
+def csv_workspace_words(frames, n_rows):
+    """ADYOLO_CSV_WORKSPACE_WORDS in adyolo_hip.h."""
+    return 2 * ((int(n_rows) + 255) // 256) + 4 + int(frames)
+
+
+def csv_buffers(device, frames, n_rows, n_segments, n_bytes):
+    """The buffers one shape of ``csv_format`` needs, allocated once: {'ws' int32, 'out' (n_bytes rounded up to 16,) uint8,
+    'seg_bytes' (n_segments + 1,) int64}.  n_rows * CSV_LINE_MAX bytes always suffice; fewer may (``csv_format`` reports it)."""
+    dev = torch.device(device)
+    return {"ws": torch.empty(csv_workspace_words(frames, n_rows), dtype=torch.int32, device=dev),
+            "out": torch.empty(max(16, (int(n_bytes) + 15) // 16 * 16), dtype=torch.uint8, device=dev),
+            "seg_bytes": torch.empty(int(n_segments) + 1, dtype=torch.int64, device=dev)}
+
+
+def csv_format(rows, counts, segments, ids=None, buf=None, status=None):
+    """A selection -- rows (capacity, 5) [frame, class, x, y, z] and counts (frames,) int32 on the device, as ``yolo_select`` /
+    ``classwise_select`` / ``tta_merge`` / ``track_rows`` / ``track_run`` return them, trimmed or not -- as the bytes of its CSV
+    files (adyolo_hip.h ``adyolo_csv_format``): ``postprocess.format_rows`` byte for byte -> (out (capacity,) uint8, seg_bytes
+    (K + 1,) int64), both on the device: segment k's file is out[seg_bytes[k]:seg_bytes[k + 1]].  segments: (K, 2) int32 on the
+    device (``postprocess.csv_segments_clips`` / ``csv_segments_run``, uploaded by the caller once).  ids: (>= capacity,) int32
+    track ids or None.  buf: ``csv_buffers`` (None: new ones for rows.shape[0] * CSV_LINE_MAX bytes, which always suffice).
+    status: one int32 on the device the ADYOLO_CSV_* bits are ORed into (None: a new word).  Neither allocates (given buffers)
+    nor synchronises; the caller reads seg_bytes and status (``csv_status_check``) before it trusts a byte.
+    -> (out, seg_bytes, status)"""
+    name = "csv_format"
+    _chk(rows)
+    if rows.dim() != 2 or rows.shape[1] != 5:
+        raise _lib.AdyoloHipError("%s: rows %s are not (N, 5)" % (name, tuple(rows.shape)))
+    dev, frames = rows.device, int(counts.numel())
+    if not counts.is_cuda or counts.dtype != torch.int32 or not counts.is_contiguous() or counts.device != dev or frames < 1:
+        raise _lib.AdyoloHipError("%s: counts must be a contiguous int32 tensor of at least one frame on %s" % (name, dev))
+    if not torch.is_tensor(segments) or segments.dtype != torch.int32 or segments.dim() != 2 or segments.shape[1] != 2 \
+            or segments.shape[0] < 1 or not segments.is_contiguous() or segments.device != dev:
+        raise _lib.AdyoloHipError("%s: segments must be a contiguous (K >= 1, 2) int32 tensor on %s" % (name, dev))
+    if ids is not None and (not torch.is_tensor(ids) or ids.dtype != torch.int32 or not ids.is_contiguous() or ids.device != dev
+                            or ids.numel() < rows.shape[0]):
+        raise _lib.AdyoloHipError("%s: ids must be a contiguous int32 tensor of at least %d on %s" % (name, rows.shape[0], dev))
+    k = int(segments.shape[0])
+    if buf is None:
+        buf = csv_buffers(dev, frames, rows.shape[0], k, rows.shape[0] * CSV_LINE_MAX)
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    ws, out, seg_bytes = buf["ws"], buf["out"], buf["seg_bytes"]
+    if ws.dtype != torch.int32 or ws.numel() < csv_workspace_words(frames, rows.shape[0]) or out.dtype != torch.uint8 \
+            or seg_bytes.dtype != torch.int64 or seg_bytes.numel() < k + 1 or status.dtype != torch.int32 or status.numel() < 1 \
+            or any(t.device != dev or not t.is_contiguous() for t in (ws, out, seg_bytes, status)):
+        raise _lib.AdyoloHipError("%s: the buffers are not csv_buffers(%s, %d, %d, %d, ...) / status no int32 word there"
+                                  % (name, dev, frames, rows.shape[0], k))
+    _c("adyolo_csv_format", _p(rows) if rows.numel() else _p(ws), rows.shape[0], _p(counts), frames, _p(ids), _p(segments), k,
+       _p(ws), _p(out) if out.numel() else _p(ws), out.numel(), _p(seg_bytes), _p(status), _stream())   # (no bytes: not written)
+    return out, seg_bytes[:k + 1], status
+
+
 def track_carry(device, nb_classes, hold):
     """An empty carry for ``track_run``: the state of one stream of recordings between two runs (the open recording's slots,
     next ids and held frames' cells), adyolo_hip.h ``adyolo_track_carry_words`` float32 words, all zero.  ``zero_()`` empties

@@ -771,3 +771,74 @@ def write_seld_output_file(file_pth, output: dict, tracks=None):
             for n, [class_idx, x, y, z] in enumerate(output[frame_idx]):
                 f.write("{},{},{},{},{},{}\n".format(int(frame_idx), int(class_idx), 0 if ids is None else int(ids[n]),
                                                      float(x), float(y), float(z)))
+
+
+# ---- The CSV files as bytes: the host definition of csrc/csv.hip ``adyolo_csv_format``.
+CSV_OVERFLOW, CSV_BAD_COUNTS, CSV_BAD_VALUE, CSV_BAD_TABLE = 1, 2, 4, 8                         # ADYOLO_CSV_* in adyolo_hip.h
+CSV_LINE_MAX = 110                                                                 # CSVF_LINE_MAX in csrc/csv_format.hpp
+
+
+def csv_segments_clips(n_clips, t_clip):
+    """The segment table of ``format_rows`` for a batch of whole clips, clip after clip on the counts axis: [(k * T', 0)]."""
+    n_clips, t_clip = int(n_clips), int(t_clip)
+    if n_clips < 1 or t_clip < 0:
+        raise ValueError("csv_segments_clips: %d clips of %d frames" % (n_clips, t_clip))
+    return np.stack([np.arange(n_clips, dtype=np.int64) * t_clip, np.zeros(n_clips, dtype=np.int64)], 1).astype(np.int32)
+
+
+def csv_segments_run(base_frame, n_frames, frame_start):
+    """The segment table of ``format_rows`` for a run of ``n_frames`` frames that starts at ``base_frame`` on the axis of all
+    recordings laid end to end (frame_start (R + 1,): each recording's first frame there): one row per recording from the one
+    that holds ``base_frame`` to the one that holds the run's last frame -- a recording without frames between them has an
+    empty segment -- the split ``corpus.split_pass_rows`` makes.  -> (the first recording's index, table (K, 2) int32)"""
+    frame_start = np.asarray(frame_start, dtype=np.int64).reshape(-1)
+    base_frame, n_frames = int(base_frame), int(n_frames)
+    if n_frames < 1 or base_frame < 0 or base_frame + n_frames > int(frame_start[-1]):
+        raise ValueError("csv_segments_run: frames [%d, %d) of %d" % (base_frame, base_frame + n_frames, int(frame_start[-1])))
+    r0 = int(np.searchsorted(frame_start, base_frame, "right")) - 1
+    r1 = int(np.searchsorted(frame_start, base_frame + n_frames - 1, "right")) - 1
+    first = frame_start[r0:r1 + 1]
+    table = np.stack([np.maximum(first - base_frame, 0), np.maximum(base_frame - first, 0)], 1)
+    return r0, table.astype(np.int32)
+
+
+def format_rows(rows, counts, segments, ids=None):
+    """The bytes ``write_seld_output_file`` writes for one call's rows, all files of the call in one string: rows (N, 5)
+    [frame, class, x, y, z] in frame order, counts (frames,) rows per frame, ids (N,) track ids or None (0).  segments (K, 2)
+    int: {first frame of the segment on the counts axis, the number that frame has in its file}, ascending, the first at
+    frame 0 (``csv_segments_clips`` / ``csv_segments_run``); a segment is one file's span.  A line is
+    ``frame,class,id,x,y,z\\n`` by the writer's own format expression: the frame number from the frame's POSITION on the
+    counts axis and its segment (``rows[:, 0]`` is not read), int(class), int(id), repr(float(float32)) thrice.
+    -> (bytes, seg_bytes (K + 1,) int64: where each segment's bytes start, the total last)
+    ``ValueError``: counts that are negative or do not sum to the rows, a table that is not as above, a class that is not
+    finite or not within int32, a negative id (csrc/csv.hip reports the same with a status bit)."""
+    counts = np.asarray(counts, dtype=np.int64).reshape(-1)
+    rows = np.asarray(rows, dtype=F32).reshape(-1, 5)
+    seg = np.asarray(segments, dtype=np.int64)
+    if (counts < 0).any() or int(counts.sum()) != len(rows):
+        raise ValueError("format_rows: %d rows, %d frame counts summing to %d" % (len(rows), len(counts), int(counts.sum())))
+    if seg.ndim != 2 or seg.shape[1] != 2 or len(seg) < 1 or seg[0, 0] != 0 or (np.diff(seg[:, 0]) < 0).any() \
+            or (seg[:, 1] < 0).any() or seg[-1, 0] > len(counts) or (seg[:, 1] + len(counts) - seg[:, 0] - 1 >= 2 ** 31).any():
+        raise ValueError("format_rows: segments %r are not (K, 2) {first frame, its number}, ascending from frame 0, numbers within int32" % (seg,))
+    if ids is not None:
+        ids = np.asarray(ids).reshape(-1)
+        if len(ids) != len(rows) or (ids < 0).any():
+            raise ValueError("format_rows: %d ids for %d rows, or a negative id" % (len(ids), len(rows)))
+        ids = ids.tolist()
+    cls = rows[:, 1]
+    if not (np.isfinite(cls).all() and (np.abs(cls) < 2.0 ** 31).all()):
+        raise ValueError("format_rows: a class that is not finite or not within int32")
+    frame_of = np.repeat(np.arange(len(counts), dtype=np.int64), counts)
+    k_of = np.searchsorted(seg[:, 0], frame_of, "right") - 1
+    number = (seg[k_of, 1] + frame_of - seg[k_of, 0]).tolist()
+    ends = np.concatenate([[0], np.cumsum(counts)])
+    first_row = ends[np.minimum(seg[:, 0], len(counts))]              # the first row at or behind each segment's start
+    lines, at, total = [], np.zeros(len(rows) + 1, dtype=np.int64), 0
+    for n, (_, class_idx, x, y, z) in enumerate(rows.tolist()):
+        line = "{},{},{},{},{},{}\n".format(int(number[n]), int(class_idx), 0 if ids is None else int(ids[n]),
+                                            float(x), float(y), float(z))
+        lines.append(line)
+        at[n] = total
+        total += len(line)
+    at[len(rows)] = total
+    return "".join(lines).encode("ascii"), np.concatenate([at[first_row], [total]]).astype(np.int64)

@@ -423,10 +423,99 @@ def _read_status(corpus, acc=None, merge=None, tracker=None):
     return float(total) / max(n, 1) if n else 0.0
 
 
-def _write_rows(output_pth, names, rows, counts, ids=None):
+def _csv_flag(device_csv, name):
+    if not isinstance(device_csv, bool):
+        raise ValueError("%s: device_csv must be True or False (got %r)" % (name, device_csv))
+    return device_csv
+
+
+class _CsvWriter:
+    """The device half of ``device_csv=True``: a batch's or pass's rows formatted into the bytes of their CSV files on the
+    device (``ops.csv_format``: ``postprocess.format_rows`` byte for byte), then two copies -- the segment offsets with the
+    status word, then exactly the bytes -- where the host writer reads the row total and then copies the rows.  The rows come
+    UNTRIMMED (nothing reads their total).  The workspaces are made once per shape; every segment table is uploaded once,
+    from page-locked memory without a synchronisation -- the windowed loops' all together before the first pass; the byte buffer holds a call's row capacity at the longest line, which no call outgrows, or 64 MiB (256 bytes per frame
+    if that is more) where that is less: it then grows to the largest total seen, and the call that outgrows it is
+    formatted again -- one more read, which a walk over a split pays a handful of times at most."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._ws, self._tables, self._out, self._pinned = {}, {}, None, []
+
+    def _bytes(self, n):
+        return torch.empty(max(16, (n + 15) // 16 * 16), dtype=torch.uint8, device=self.device)
+
+    def start(self, output_pth, names):
+        """Every file of the split, empty: a windowed loop appends to them pass by pass, and a recording without rows keeps
+        its empty file."""
+        for name in names:
+            open(os.path.join(output_pth, name + ".csv"), "wb").close()
+
+    def _upload(self, pinned):
+        """The one host-to-device copy of the writer: page-locked and ``non_blocking``, so it never synchronises the stream
+        (a blocking copy from pageable memory would, behind the whole pass)."""
+        return pinned.to(self.device, non_blocking=True)
+
+    def tables(self, tables):
+        """The segment tables (K, 2) int32 that are not on the device yet -> there, all in ONE page-locked upload.  The windowed
+        loops call it with every pass's table before their first pass (``_csv_run_tables``)."""
+        import numpy as np
+        new = {}
+        for t in tables:
+            t = np.ascontiguousarray(t, dtype=np.int32)
+            if t.tobytes() not in self._tables:
+                new.setdefault(t.tobytes(), t)
+        if not new:
+            return
+        pinned = torch.from_numpy(np.concatenate(list(new.values()))).pin_memory()
+        self._pinned.append(pinned)                              # (alive until the copy has run: as long as the writer)
+        dev, at = self._upload(pinned), 0
+        for key, t in new.items():
+            self._tables[key] = dev[at:at + len(t)]
+            at += len(t)
+
+    def fetch(self, rows, counts, table, ids=None):
+        """-> (the bytes of the call on the host, a uint8 array valid until the next fetch; seg_bytes as a list)"""
+        from . import ops
+        key = table.tobytes()
+        if key not in self._tables:                              # (the clip loops: once per batch shape)
+            self.tables([table])
+        seg = self._tables[key]
+        frames, n_rows, k = counts.numel(), rows.shape[0], len(table)
+        ws = self._ws.get((frames, n_rows, k))
+        if ws is None:
+            ws = self._ws[(frames, n_rows, k)] = ops.csv_buffers(self.device, frames, n_rows, k, 0)
+        floor = min(n_rows * ops.CSV_LINE_MAX, max(64 << 20, 256 * frames))
+        if self._out is None or self._out.numel() < floor:
+            self._out = self._bytes(floor)
+        while True:
+            buf = {"ws": ws["ws"], "seg_bytes": ws["seg_bytes"], "out": self._out}
+            out, seg_bytes, _ = ops.csv_format(rows, counts, seg, ids, buf=buf, status=self.status)
+            seg_h, status_h = ops.to_host_many(seg_bytes, self.status)
+            word, seg_h = int(status_h[0]), seg_h.tolist()
+            if word != ops.CSV_OVERFLOW:
+                break
+            self._out = self._bytes(1 << (seg_h[-1] - 1).bit_length())
+            self.status.zero_()
+        ops.csv_status_check(word)
+        if not seg_h[-1]:
+            return b"", seg_h
+        return ops.to_host_many(out[:seg_h[-1]])[0].numpy(), seg_h
+
+
+def _write_rows(output_pth, names, rows, counts, ids=None, csv=None):
     """Selected device rows of ``len(names)`` clips (trimmed to their total) -> one CSV per clip.  ids: the rows' track ids
-    (tracking is on), written into the track column."""
+    (tracking is on), written into the track column.  csv: the ``_CsvWriter`` of ``device_csv=True`` (the rows untrimmed): the
+    files' bytes come formatted from the device."""
     from . import ops
+    if csv is not None:
+        from .postprocess import csv_segments_clips
+        data, at = csv.fetch(rows, counts, csv_segments_clips(len(names), counts.numel() // len(names)), ids)
+        for k, name in enumerate(names):
+            with open(os.path.join(output_pth, name + ".csv"), "wb") as f:
+                f.write(data[at[k]:at[k + 1]])
+        return
     if ids is None:
         rows_h, counts_h = [t.numpy() for t in ops.to_host_many(rows, counts)]
         for name, clip_rows in zip(names, group_rows(rows_h, counts_h, len(names))):
@@ -439,13 +528,24 @@ def _write_rows(output_pth, names, rows, counts, ids=None):
         write_seld_output_file(os.path.join(output_pth, name + ".csv"), clip_rows, clip_ids)
 
 
-def _write_pass(corpus, base, rows, counts, ids, outs, out_ids):
+def _write_pass(corpus, base, rows, counts, ids, outs, out_ids, csv=None, output_pth=None, names=None):
     """The rows (trimmed) of a pass's run, which starts at ``base`` on the common axis -> the host in one copy, onto each
     recording's own frame axis in ``outs``.  ids: the rows' track ids (tracking is on), which go to ``out_ids`` {frame of the
-    recording: [id, ...]} per recording, parallel to ``outs``."""
+    recording: [id, ...]} per recording, parallel to ``outs``.  csv: the ``_CsvWriter`` of ``device_csv=True`` (the rows
+    untrimmed): the run's bytes come formatted from the device and each recording's span is appended to its file under
+    ``output_pth`` (a recording's passes come in frame order); ``outs`` / ``out_ids`` are not touched."""
     import numpy as np
     from . import ops
     from .corpus import split_pass_rows
+    if csv is not None:
+        from .postprocess import csv_segments_run
+        r0, table = csv_segments_run(base, counts.numel(), corpus.frame_start)
+        data, at = csv.fetch(rows, counts, table, ids)
+        for k in range(len(table)):
+            if at[k + 1] > at[k]:
+                with open(os.path.join(output_pth, names[r0 + k] + ".csv"), "ab") as f:
+                    f.write(data[at[k]:at[k + 1]])
+        return
     rows_h, counts_h, *ids_h = [t.numpy() for t in ops.to_host_many(*(t for t in (rows, counts, ids) if t is not None))]
     for r, found in split_pass_rows(rows_h, counts_h, base, corpus.frame_start).items():
         outs[r].update(found)                                                # (a recording's passes come in frame order)
@@ -458,14 +558,27 @@ def _write_pass(corpus, base, rows, counts, ids, outs, out_ids):
         out_ids[r][base + f - int(corpus.frame_start[r])] = ids_h[int(ends[f]) - int(counts_h[f]):int(ends[f])]
 
 
-def _write_recordings(output_pth, names, outs, out_ids=None):
+def _csv_run_tables(csv, corpus, tracker, base):
+    """Before a windowed loop's first pass: the segment table of every pass that emits frames (``_write_pass`` asks for the
+    same ones), uploaded together, so that no pass uploads anything."""
+    if csv is None:
+        return
+    from .postprocess import csv_segments_run
+    frames = corpus.pass_frames if tracker is None else tracker.plan["pass_frames"]
+    csv.tables([csv_segments_run(int(base[p]), int(frames[p]), corpus.frame_start)[1]
+                for p in range(corpus.n_passes) if int(frames[p]) > 0])
+
+
+def _write_recordings(output_pth, names, outs, out_ids=None, csv=None):
+    if csv is not None:                                          # (``_CsvWriter.start`` made the files, the passes filled them)
+        return
     for k, (name, rows) in enumerate(zip(names, outs)):
         write_seld_output_file(os.path.join(output_pth, name + ".csv"), rows, None if out_ids is None else out_ids[k])
 
 
 # ------------------------------------------------------------------------------------------------ whole clips from HBM
 def test_epoch_corpus(corpus, model, features, criterion, postprocessor, output_pth=None, batch_size=8, forward=None,
-                      device_scorer=None, tta=None, track=None):
+                      device_scorer=None, tta=None, track=None, device_csv=False):
     """``test_epoch_audio(device_select=True)`` from an HBM-resident split (``corpus.EvalDeviceCorpus``): the same batches,
     the same mean of per-clip losses (float32 adds in file order, clips without AD-YOLO rows left out), the same selected rows
     into ``device_scorer`` and, with ``output_pth``, the same CSV files -- but no WAV read, no CSV parse, no host label
@@ -486,8 +599,15 @@ def test_epoch_corpus(corpus, model, features, criterion, postprocessor, output_
     with ``tta`` -- are then linked per (clip, class) into tracks on the device (``postprocess.track_rows``; csrc/track.hip):
     directions smoothed, short gaps filled, short tracks dropped.  The tracked rows go to the scorer and the files, whose
     third column carries the track ids; the loss is the plain pass's.  The status word is read with the loss (the caps of the
-    definition only warn).  None leaves the pass exactly as it is."""
+    definition only warn).  None leaves the pass exactly as it is.
+
+    device_csv (with output_pth): True formats every batch's rows into the bytes of their files ON THE DEVICE
+    (``ops.csv_format``, csrc/csv.hip: ``postprocess.format_rows``, the bytes ``write_seld_output_file`` writes) -- no row is
+    copied, grouped or formatted on the host; per batch the segment offsets and then the bytes are copied (two
+    synchronisations, as the host writer's row total and rows) and each file's span is written.  The same files, byte for
+    byte, with ``tta``, ``track`` and ``device_scorer`` alike.  False leaves every call, copy and byte as it is."""
     from . import ops
+    csv = _CsvWriter(corpus.device) if _csv_flag(device_csv, "test_epoch_corpus") and output_pth is not None else None
     model.eval()
     if output_pth is not None:
         delete_and_create_folder(output_pth)
@@ -501,16 +621,17 @@ def test_epoch_corpus(corpus, model, features, criterion, postprocessor, output_
             clips = [names[i] for i in idx]
             dec = _corpus_batch(corpus, idx, model, features, criterion, postprocessor, forward, acc)
             more = (_corpus_view(corpus, idx, v, model, features, postprocessor, forward) for v in _further_views(merge))
-            rows, counts, ids = _select_rows(postprocessor, dec, more, merge, tracker, len(clips), output_pth is not None)
+            rows, counts, ids = _select_rows(postprocessor, dec, more, merge, tracker, len(clips),
+                                             output_pth is not None and csv is None)
             if device_scorer is not None:
                 device_scorer.add_rows(rows, counts, clips)
             if output_pth is not None:
-                _write_rows(output_pth, clips, rows, counts, ids)
+                _write_rows(output_pth, clips, rows, counts, ids, csv)
     return _read_status(corpus, acc, merge, tracker)
 
 
 def sweep_conf_thresh_corpus(corpus, model, features, criterion, postprocessor, scorer, thresholds=None, output_pth=None,
-                             batch_size=8, forward=None, tta=None, track=None):
+                             batch_size=8, forward=None, tta=None, track=None, device_csv=False):
     """``sweep_conf_thresh(device_select=True, device_score=True)`` from an HBM-resident split: ONE forward pass per batch,
     every batch's decode kept on the device, then per threshold the selections and the device scores (``scorer``: a
     ``seld_metrics.DeviceSELDScorer``); the chosen threshold is left set on the post-processor.  With ``output_pth`` the last
@@ -520,8 +641,9 @@ def sweep_conf_thresh_corpus(corpus, model, features, criterion, postprocessor, 
     tta, track: as ``test_epoch_corpus``, redone per threshold: every VIEW's decode of every batch is kept on the device, and
     each threshold selects, collects and merges them again and links the rows before they are scored and written.  The loss
     and the corpus status word are read after the forward phase; the status words of the merge and the tracker once, in one
-    copy, after the last threshold."""
+    copy, after the last threshold.  device_csv: as ``test_epoch_corpus``, for the last threshold's files."""
     from .seld_metrics import DeviceSELDScorer
+    _csv_flag(device_csv, "sweep_conf_thresh_corpus")
     if not isinstance(scorer, DeviceSELDScorer):
         raise ValueError("sweep_conf_thresh_corpus needs a seld_metrics.DeviceSELDScorer (got %s)" % type(scorer).__name__)
     from . import ops
@@ -530,6 +652,7 @@ def sweep_conf_thresh_corpus(corpus, model, features, criterion, postprocessor, 
     corpus.reset_status()
     acc = ops.loss_accumulator(corpus.device)
     decoded = []
+    csv = _CsvWriter(corpus.device) if device_csv and output_pth is not None else None
     merge = _ViewMerge(tta, postprocessor, corpus.device) if tta is not None else None
     tracker = _Tracker(track, corpus.device) if track is not None else None
     with torch.no_grad():
@@ -546,10 +669,11 @@ def sweep_conf_thresh_corpus(corpus, model, features, criterion, postprocessor, 
             delete_and_create_folder(output_pth)
         scorer.reset()
         for clips, views in decoded:
-            rows, counts, ids = _select_rows(postprocessor, views[0], views[1:], merge, tracker, len(clips), write)
+            rows, counts, ids = _select_rows(postprocessor, views[0], views[1:], merge, tracker, len(clips),
+                                             write and csv is None)
             scorer.add_rows(rows, counts, clips)
             if write:
-                _write_rows(output_pth, clips, rows, counts, ids)
+                _write_rows(output_pth, clips, rows, counts, ids, csv)
         return scorer.scores()
 
     new_thresh, table = _sweep_thresholds(postprocessor, thresholds, score)
@@ -559,7 +683,8 @@ def sweep_conf_thresh_corpus(corpus, model, features, criterion, postprocessor, 
 
 
 # ------------------------------------------------------------------------------------- recordings of any length, in windows
-def infer_epoch_corpus(corpus, model, features, postprocessor, output_pth, forward=None, tracking=None, tta=None):
+def infer_epoch_corpus(corpus, model, features, postprocessor, output_pth, forward=None, tracking=None, tta=None,
+                       device_csv=False):
     """Inference on recordings of any length from an HBM-resident folder (``corpus.InferDeviceCorpus``): every recording cut
     into overlapping windows of one shape, the windows run ``corpus.batch_size`` at a time -- so the whole folder has ONE input
     shape and, with ``forward`` (``graph.ForwardGraphs``), one recorded graph.  Per pass: ``adyolo_corpus_gather_windows`` (into
@@ -573,32 +698,38 @@ def infer_epoch_corpus(corpus, model, features, postprocessor, output_pth, forwa
     Tracking (``tracking``) and tta: as ``test_epoch_windows`` (``postprocess.track_run`` with the state carried from pass to
     pass; the views merged, then linked), without labels, loss and scorer: the emitted rows go to the files only, with one
     synchronisation per pass as without them, and the status words of the merge and the tracker are read with the corpus's in
-    the one copy at the end.  None leaves every call, allocation, synchronisation and bit as it is."""
+    the one copy at the end.  None leaves every call, allocation, synchronisation and bit as it is.
+
+    device_csv: as ``test_epoch_windows``."""
+    csv = _CsvWriter(corpus.device) if _csv_flag(device_csv, "infer_epoch_corpus") else None
     model.eval()
     delete_and_create_folder(output_pth)
     names = corpus.get_filelist()
+    if csv is not None:
+        csv.start(output_pth, names)
     corpus.reset_status()
     outs = [{} for _ in names]
     merge = _window_merge(tta, postprocessor, corpus) if tta is not None and corpus.n_passes else None
     tracker = _RunTracker(tracking, corpus) if tracking is not None else None
     out_ids = [{} for _ in names] if tracker is not None else None
     base = corpus.pass_base if tracker is None else tracker.plan["pass_base"]
+    _csv_run_tables(csv, corpus, tracker, base)
     stitched = None
     with torch.no_grad():
         for p in range(corpus.n_passes):
             stitched, run = _window_pass(corpus, p, model, features, None, postprocessor, forward, None, stitched)
             more = (_window_view(corpus, p, v, model, features, postprocessor, forward, stitched) for v in _further_views(merge))
-            rows, counts, ids = _select_rows(postprocessor, run, more, merge, tracker, 1, True, p)
+            rows, counts, ids = _select_rows(postprocessor, run, more, merge, tracker, 1, csv is None, p)
             if counts.numel():                                               # (a tracked pass may hold all its frames back)
-                _write_pass(corpus, base[p], rows, counts, ids, outs, out_ids)
+                _write_pass(corpus, base[p], rows, counts, ids, outs, out_ids, csv, output_pth, names)
     _read_status(corpus, None, merge, tracker)
-    _write_recordings(output_pth, names, outs, out_ids)
+    _write_recordings(output_pth, names, outs, out_ids, csv)
     return {"recordings": len(names), "windows": corpus.n_windows, "passes": corpus.n_passes,
             "frames": int(corpus.frame_start[-1])}
 
 
 def test_epoch_windows(corpus, model, features, criterion, postprocessor, output_pth=None, forward=None, device_scorer=None,
-                       tracking=None, tta=None):
+                       tracking=None, tta=None, device_csv=False):
     """Labelled evaluation of recordings of ANY length from an HBM-resident split (``corpus.EvalWindowCorpus``): every recording
     cut into overlapping windows of one shape, ``corpus.batch_size`` windows per pass -- one input shape for the whole split
     and, with ``forward`` (``graph.ForwardGraphs``), one recorded graph.  Per pass: ``corpus.launch`` (audio into the graph's
@@ -637,12 +768,23 @@ def test_epoch_windows(corpus, model, features, criterion, postprocessor, output
     matter where the passes cut the axis).  The merged rows take the selection's place everywhere: the scorer, the files
     and, with ``tracking``, the link (merge, then link, as on whole clips).  The pool and the workspace are allocated once,
     for the longest run of the split; the merge's status word is read in the one end-of-pass copy (an overflow raises,
-    naming ``tta_max_rows_per_frame``).  None leaves every call, allocation, synchronisation and bit as it is."""
+    naming ``tta_max_rows_per_frame``).  None leaves every call, allocation, synchronisation and bit as it is.
+
+    device_csv (with output_pth): True formats every pass's emitted rows into the bytes of their files ON THE DEVICE
+    (``ops.csv_format``, csrc/csv.hip: ``postprocess.format_rows``, the bytes ``write_seld_output_file`` writes; the run split
+    at the recording boundaries by ``postprocess.csv_segments_run``).  Every recording's file is made empty first and each
+    pass appends its spans (a recording's passes come in frame order): no row is copied, split or formatted on the host,
+    and per pass the segment offsets and then the bytes are copied (two synchronisations, as the host writer's row total and
+    rows).  The same files, byte for byte, with ``tta``, ``tracking`` and ``device_scorer`` alike.  False leaves every call,
+    copy and byte as it is."""
     from . import ops
+    csv = _CsvWriter(corpus.device) if _csv_flag(device_csv, "test_epoch_windows") and output_pth is not None else None
     model.eval()
     if output_pth is not None:
         delete_and_create_folder(output_pth)
     names = corpus.get_filelist()
+    if csv is not None:
+        csv.start(output_pth, names)
     corpus.reset_status()
     acc = ops.loss_accumulator(corpus.device)
     merge = _window_merge(tta, postprocessor, corpus) if tta is not None else None
@@ -652,25 +794,27 @@ def test_epoch_windows(corpus, model, features, criterion, postprocessor, output
     outs = [{} for _ in names]
     out_ids = [{} for _ in names] if tracker is not None else None
     base = corpus.pass_base if tracker is None else tracker.plan["pass_base"]
+    _csv_run_tables(csv, corpus, tracker, base)
     stitched = None
     with torch.no_grad():
         for p in range(corpus.n_passes):
             stitched, run = _window_pass(corpus, p, model, features, criterion, postprocessor, forward, acc, stitched)
             more = (_window_view(corpus, p, v, model, features, postprocessor, forward, stitched) for v in _further_views(merge))
-            rows, counts, ids = _select_rows(postprocessor, run, more, merge, tracker, 1, output_pth is not None, p)
+            rows, counts, ids = _select_rows(postprocessor, run, more, merge, tracker, 1,
+                                             output_pth is not None and csv is None, p)
             if not counts.numel():                                           # a tracked pass that holds all its frames back
                 continue
             if device_scorer is not None:
                 device_scorer.add_run(rows, counts, segments[p])
             if output_pth is not None:
-                _write_pass(corpus, base[p], rows, counts, ids, outs, out_ids)
+                _write_pass(corpus, base[p], rows, counts, ids, outs, out_ids, csv, output_pth, names)
     if output_pth is not None:
-        _write_recordings(output_pth, names, outs, out_ids)
+        _write_recordings(output_pth, names, outs, out_ids, csv)
     return _read_status(corpus, acc, merge, tracker)
 
 
 def sweep_conf_thresh_windows(corpus, model, features, criterion, postprocessor, scorer, thresholds=None, output_pth=None,
-                              forward=None, tracking=None, tta=None):
+                              forward=None, tracking=None, tta=None, device_csv=False):
     """``sweep_conf_thresh_corpus`` through windows (``corpus.EvalWindowCorpus``): ONE forward pass per window pass, every
     pass's stitched run kept (cloned) on the device, then per threshold ``scorer.reset()``, the selection of every run and
     ``scorer.add_run``; the chosen threshold is left set on the post-processor.  With ``output_pth`` the last threshold's CSV
@@ -682,8 +826,10 @@ def sweep_conf_thresh_windows(corpus, model, features, criterion, postprocessor,
     the tracker's carry with the scorer, then selects, collects, merges and links the runs again; the last threshold's
     emitted rows also go to the files.  The loss and the corpus status word are read after the forward phase; the status
     words of the merge and the tracker once, in one copy, after the last threshold.  None leaves every call, allocation and
-    bit as it is."""
+    bit as it is.  device_csv: as ``test_epoch_windows``, for the last threshold's files (the folder is then emptied before
+    the last threshold's passes, not after them)."""
     from .seld_metrics import DeviceSELDScorer
+    _csv_flag(device_csv, "sweep_conf_thresh_windows")
     if not isinstance(scorer, DeviceSELDScorer):
         raise ValueError("sweep_conf_thresh_windows needs a seld_metrics.DeviceSELDScorer (got %s)" % type(scorer).__name__)
     from . import ops
@@ -696,6 +842,8 @@ def sweep_conf_thresh_windows(corpus, model, features, criterion, postprocessor,
     segments = corpus.segments(scorer, bounds=None if tracker is None else tracker.plan["bounds"])
     base = corpus.pass_base if tracker is None else tracker.plan["pass_base"]
     runs, stitched = [], None
+    csv = _CsvWriter(corpus.device) if device_csv and output_pth is not None else None
+    _csv_run_tables(csv, corpus, tracker, base)
     with torch.no_grad():
         for p in range(corpus.n_passes):
             stitched, run = _window_pass(corpus, p, model, features, criterion, postprocessor, forward, acc, stitched)
@@ -712,14 +860,17 @@ def sweep_conf_thresh_windows(corpus, model, features, criterion, postprocessor,
         scorer.reset()
         if tracker is not None:
             tracker.reset()
+        if write and csv is not None:
+            delete_and_create_folder(output_pth)
+            csv.start(output_pth, names)
         for p, views in enumerate(runs):
-            rows, counts, ids = _select_rows(postprocessor, views[0], views[1:], merge, tracker, 1, write, p)
+            rows, counts, ids = _select_rows(postprocessor, views[0], views[1:], merge, tracker, 1, write and csv is None, p)
             if not counts.numel():
                 continue
             scorer.add_run(rows, counts, segments[p])
             if write:
-                _write_pass(corpus, base[p], rows, counts, ids, outs, out_ids)
-        if write:
+                _write_pass(corpus, base[p], rows, counts, ids, outs, out_ids, csv, output_pth, names)
+        if write and csv is None:
             delete_and_create_folder(output_pth)
             _write_recordings(output_pth, names, outs, out_ids)
         return scorer.scores()

@@ -681,6 +681,36 @@ int  adyolo_track_run(const float *rows, long n_rows, const int *frame_counts, l
                       long n_segments, int C, float cos_gate, int max_gap, int min_len, float a, float b, int hold, float *carry,
                       float *ws, float *out_rows, int *out_ids, long capacity, int *out_counts, int *status, void *stream);
 
+/* The detection CSV files as bytes (csrc/csv.hip, csrc/csv_format.hpp), opt-in: what postprocess.format_rows does on the
+ * host, byte for byte -- the lines write_seld_output_file writes, "frame,class,id,x,y,z\n" with repr(float(float32)) floats, for
+ * rows already on the device; all files of the call in one buffer.
+ *   rows / frame_counts [n_frames]  a selection as adyolo_yolo_select / adyolo_classwise_select / adyolo_tta_merge /
+ *                adyolo_track_rows / adyolo_track_run leave it (capacity n_rows; the frame column is not read; nothing behind
+ *                the first sum(frame_counts) rows is read)
+ *   ids          [n_rows] int32 track ids for the third column, or NULL: 0
+ *   segments     [n_segments][2] int32 ON THE DEVICE: {first frame of the segment on the counts axis, the number that frame has
+ *                in its file}; ascending, the first at frame 0.  A segment is one file's span.
+ *   ws           ADYOLO_CSV_WORKSPACE_WORDS(n_frames, n_rows) 32-bit words, 16-byte aligned; the caller initialises nothing
+ *   out          [capacity] bytes, 16-byte aligned: the lines, segment after segment
+ *   seg_bytes    [n_segments + 1] int64: where each segment's bytes start in out, the total last
+ *   status       one int32 the kernels OR ADYOLO_CSV_* bits into
+ * A frame's number is seg.number + (frame - seg.first) of the last segment that starts at or before it.  class is the float
+ * truncated; a class that is not finite or not within int32, or a negative id, is written as 0 and reported
+ * (ADYOLO_CSV_BAD_VALUE).  A total above the capacity: ADYOLO_CSV_OVERFLOW, seg_bytes are the true offsets (the last is the
+ * capacity to come back with) and NOTHING is written to out.  Frame counts that are negative or sum to more than n_rows
+ * (ADYOLO_CSV_BAD_COUNTS), a table that is not as above (ADYOLO_CSV_BAD_TABLE): nothing is formatted, seg_bytes are zero.
+ * Positions come from scans, never from atomics; nothing is written behind the total; no host synchronisation.
+ * EINVAL, before any launch: null or misaligned pointer, n_frames < 1, n_segments < 1; ENOSUP: 32-bit counts overflow. */
+#define ADYOLO_CSV_OVERFLOW    1    /* more bytes than the capacity: nothing was written, seg_bytes hold the need */
+#define ADYOLO_CSV_BAD_COUNTS  2    /* frame counts negative or past the rows given */
+#define ADYOLO_CSV_BAD_VALUE   4    /* a class not finite or outside int32, or a negative id: written as 0 */
+#define ADYOLO_CSV_BAD_TABLE   8    /* a segment table not ascending from frame 0 within the frames */
+#define ADYOLO_CSV_LINE_MAX    110  /* no line is longer */
+#define ADYOLO_CSV_WORKSPACE_WORDS(n_frames, n_rows) (2 * (((n_rows) + 255) / 256) + 4 + (n_frames))
+int  adyolo_csv_format(const float *rows, long n_rows, const int *frame_counts, long n_frames, const int *ids,
+                       const int *segments, long n_segments, void *ws, unsigned char *out, long capacity, long long *seg_bytes,
+                       int *status, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Input pipeline around K1.
  *   adyolo_pcm16_to_f32: staged WAV samples int16 -> float, x / 32768 + 1e-8 (src/datasets.py:105, src/preprocess.py:104)

@@ -155,6 +155,7 @@ SIGNATURES = {
     "adyolo_corpus_gather_windows": (I, [P, L, P, I, L, P, P, P]),
     "adyolo_corpus_gather_windows_view": (I, [P, L, P, I, L, I, P, P, P, P, P]),
     "adyolo_decode_stitch": (I, [P, P, I, I, L, L, P, L, P, P]),
+    "adyolo_stream_gather_windows": (I, [P, L, L, P, I, L, I, P, P, P, P, P]),
     "adyolo_resample_pcm": (I, [P, I, L, P, I, P, L, I, I, I, L, P, L, P, P]),
     "adyolo_pcm16_to_f32": (I, [P, P, L, P]),
     "adyolo_mask_ranges": (I, [P, P, I, I, I, I, P]),

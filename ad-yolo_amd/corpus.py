@@ -46,6 +46,10 @@ cuts it into the windows of ``InferDeviceCorpus`` (``plan_windows``, ``_WindowCo
 (``window_items``), for ``test.test_epoch_windows``; the device scorer then scores each pass's stitched run in segments
 (``seld_metrics.run_segments``).
 
+A live stream has no length to plan from: ``stream_plan`` is the window plan that does not need the recording's end, and
+``StreamDeviceCorpus`` holds ONE such stream in a ring in HBM (``ops.stream_gather_windows`` reads the windows out of it) for
+``test.StreamInference``, which returns each frame's detections once it is final.
+
 One structure under all of it: every loader returns a ``HostCorpus``, whose constructor owns the stream layout (16-frame
 alignment) and gives every field a value, with ``kind`` saying which split it is; the loaders share one WAV reader, one CSV
 reader and one verify pick (``_read_wav``, ``_csv_rows``, ``_verify_picks``); the five device corpora share ``_CorpusBase``.
@@ -1364,3 +1368,246 @@ class EvalWindowCorpus(_WindowCorpus):
                                ws[b * max(me, 1):], self.status)
         row_start = ws[::max(me, 1)].contiguous()
         return audio, target, row_start
+
+
+# ----------------------------------------------------------------------------------------------------- streaming inference
+def stream_plan(window_frames, margin_frames, hop_frames, hop_label, planned, pushed, closing=False):
+    """The window plan of a LIVE stream, whose end is not known: the definition (pure Python) of what
+    ``StreamDeviceCorpus`` runs.  Wf = window_frames, Mf = margin_frames, Hf = hop_frames, all in label frames of ``hop_label``
+    samples; ``ValueError`` unless Mf >= 1 and 1 <= Hf <= Wf - 2 Mf.  F = pushed // hop_label label frames are there.
+
+    While the stream is open, step k = 0, 1, ... is runnable as soon as k Hf + Wf <= F.  Its window starts at frame k Hf; step 0
+    keeps the window-local frames [0, Wf - Mf), step k >= 1 keeps [Wf - Mf - Hf, Wf - Mf): the stream's frames [k Hf + Wf - Mf
+    - Hf, k Hf + Wf - Mf).  On close at F frames: F == 0 nothing; F <= Wf and no step ran: one window (0, 0, 0, F) whose valid
+    samples are all pushed samples, capped at the window (the rule of ``plan_windows``: the sub-frame remainder is fed);
+    otherwise one tail-aligned window starting at F - Wf that keeps from where the last step stopped up to F.  Mf >= 1 makes
+    that closing window keep at least one frame, so an open tracker carry can always be flushed by a call that has frames.
+
+    The kept ranges tile [0, F) exactly once, in order; every kept frame of a window that is not the first has at least Mf
+    frames of context on its left, every kept frame of a window that is not the closing one Mf on its right.  With Hf = Wf - 2
+    Mf every frame is kept from a window that starts where the window keeping it in ``window_plan(F, Wf, Mf)`` starts: the two
+    plans are the same unless (F - Wf) % Hf == 0, when the stream has already run the last start as a step and runs it once
+    more as the closing window.
+
+    The form is incremental: ``planned`` is the number of frames the rows returned so far keep (0 at the start; each call's
+    rows end at its own new value, the dst + n of the last row), ``pushed`` the samples pushed so far, ``closing`` whether the
+    stream ends here -> the NEW rows, in the layout of ``ops.WINDOW_WORDS`` that ``adyolo_decode_stitch`` takes unchanged:
+    (absolute sample offset since the stream began, valid samples, src_lo, dst frame on the stream's axis, n, 0, 0, 0).  The
+    calls over any partition of a stream, concatenated, are the one call (0, total, closing=True).
+
+    Latency: frame f is final once a window that ends at or after f + Mf has run, at most Mf + Hf frames after f was pushed
+    (the frames of step 0 wait for the first whole window, Wf frames; the closing window makes the rest final at once).  With tracking a frame is held back a further ``hold`` frames
+    (``postprocess.track_hold``)."""
+    wf, mf, hf, hop = int(window_frames), int(margin_frames), int(hop_frames), int(hop_label)
+    planned, pushed = int(planned), int(pushed)
+    if mf < 1 or hf < 1 or hf > wf - 2 * mf:
+        raise ValueError("stream_plan: a window of %d frames, a margin of %d, a hop of %d (margin >= 1, 1 <= hop <= window - "
+                         "2 * margin)" % (wf, mf, hf))
+    if hop < 1 or pushed < 0:
+        raise ValueError("stream_plan: %d samples pushed, a label hop of %d" % (pushed, hop))
+    f = pushed // hop
+    # ``planned`` is 0 or where a step stopped, k Hf + Wf - Mf (or F of a closed stream: nothing is left to plan)
+    if planned < 0 or planned > f or (planned and planned != f and (planned < wf - mf or (planned - (wf - mf)) % hf)):
+        raise ValueError("stream_plan: %d frames planned of %d (not where a step stops)" % (planned, f))
+    if planned == f:
+        return []
+    n, rows = wf * hop, []
+    k = 0 if planned == 0 else (planned - (wf - mf)) // hf + 1
+    while k * hf + wf <= f:
+        lo = 0 if k == 0 else wf - mf - hf
+        rows.append((k * hf * hop, n, lo, k * hf + lo, wf - mf - lo, 0, 0, 0))
+        planned = k * hf + wf - mf
+        k += 1
+    if closing:
+        if planned == 0:                                              # F <= Wf and no step ran
+            rows.append((0, min(pushed, n), 0, 0, f, 0, 0, 0))
+        else:
+            start = f - wf
+            rows.append((start * hop, n, planned - start, planned, f - planned, 0, 0, 0))
+    return rows
+
+
+class StreamDeviceCorpus(_WindowCorpus):
+    """ONE live stream of int16 4-channel audio at ``data_config.sr`` on the device, for ``test.StreamInference``: a ring in HBM
+    that takes samples as they come (absolute sample s at ``ring[s % capacity]``), the windows of ``stream_plan`` gathered out
+    of it (``ops.stream_gather_windows``) in passes of ONE shape, (batch_size, n_samples, 4), so one recorded graph serves the
+    whole stream.
+
+        corpus = StreamDeviceCorpus(params, "cuda:0", window_s=20, margin_s=2.0, hop_s=1.0)
+        taken = corpus.append(pcm)               # int16 (n, 4), any n: -> how many samples the ring took
+        for _ in range(corpus.runnable()):
+            audio = corpus.launch()              # (batch_size, n_samples, 4) f32, no host sync
+
+    window_s / margin_s: as ``InferDeviceCorpus``, the margin at least one label frame.  hop_s: the step from window to window,
+    a whole number of label hops between 1 and window - 2 margin (the default: the plan of ``window_plan``).  A pass is up to
+    batch_size consecutive runnable windows of the stream (catch-up after a large push), then empty filler windows.
+
+    capacity_s: the ring.  A sample must stay until no later window reads it.  The last launched step starts at k Hf; the
+    closing window starts at F - Wf >= k' Hf for the last runnable step k' >= k, and every later step starts later still: so
+    everything from the start of the last launched window (0 before the first) is kept, and nothing older is needed.  Step k +
+    1 ends Hf + Wf frames after that point, so the smallest ring that always lets the next step become runnable holds (Wf +
+    Hf) label frames = n_samples + hop samples; less is refused.  The default, n_samples + batch_size hops, lets a catch-up
+    pass fill its batch.  ``append`` takes what fits (never overwriting a kept sample) and returns the count; the rest is
+    appended after the runnable passes have been launched -- ``StreamInference.push`` does that, so any push size works.
+
+    Per push: one copy into a page-locked staging buffer (two of them, alternating: a buffer is written again only when the
+    copy out of it has landed) and at most two asynchronous copies into the ring (two when the piece crosses the seam); per
+    pass one asynchronous copy of the pass's window table from page-locked memory.  No kernel, no blocking copy.  The views of
+    a pass (``launch_view``) are gathered before the next ``append``: a window that has been overwritten is a bad item."""
+
+    def __init__(self, params, device="cuda:0", window_s=None, margin_s=None, hop_s=None, batch_size=1, capacity_s=None):
+        from types import SimpleNamespace
+        from .augmentations import COMBINATIONS
+        who = "StreamDeviceCorpus"
+        dc = params["data_config"]
+        hop = int(dc.get("sr", 24000) * dc.get("label_hop_len_s", 0.1))                 # FoaDataset.hop_label
+        sr = self._window_setup(SimpleNamespace(hop_label=hop), params, window_s, margin_s, batch_size)
+        wf, mf = self.window_frames, self.margin_frames
+        if mf < 1:
+            raise ValueError("%s: a margin of at least one label frame is needed (the closing window must keep a frame)" % who)
+        if hop_s is None:
+            h = (wf - 2 * mf) * hop
+        else:
+            h = int(round(sr * float(hop_s)))
+            if h <= 0 or abs(h - sr * float(hop_s)) > 1e-6 or h % hop:
+                raise ValueError("%s: hop %r s is not a whole multiple of the label hop (%d samples at %d Hz)" % (who, hop_s, hop, sr))
+        self.hop_frames = h // hop
+        if not 1 <= self.hop_frames <= wf - 2 * mf:
+            raise ValueError("%s: a hop of %d label frames with a window of %d and a margin of %d (1 <= hop <= window - 2 * "
+                             "margin)" % (who, self.hop_frames, wf, mf))
+        self.hop_label = hop
+        self.min_capacity = self.n_samples + h
+        if capacity_s is None:
+            cap = self.n_samples + self.batch_size * h
+        else:
+            cap = int(round(sr * float(capacity_s)))
+            if abs(cap - sr * float(capacity_s)) > 1e-6:
+                raise ValueError("%s: capacity %r s is not a whole number of samples at %d Hz" % (who, capacity_s, sr))
+        if cap < self.min_capacity or cap & 1:
+            raise ValueError("%s: a ring of %d samples; it must be even and hold a window and a hop, %d samples (%g s)"
+                             % (who, cap, self.min_capacity, self.min_capacity / sr))
+        self.capacity = cap
+        self.device = torch.device(device)
+        self.ring = torch.zeros((cap, 4), dtype=torch.int16, device=self.device)
+        self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.rot = ops.corpus_rot_table(COMBINATIONS)
+        self._stage = [torch.empty((cap, 4), dtype=torch.int16).pin_memory() for _ in range(2)]
+        self._table_host = [torch.empty((self.batch_size, ops.WINDOW_WORDS), dtype=torch.int64).pin_memory() for _ in range(2)]
+        self._table = torch.zeros((self.batch_size, ops.WINDOW_WORDS), dtype=torch.int64, device=self.device)
+        self._stage_ev, self._table_ev, self._stage_slot, self._table_slot = [None, None], [None, None], 0, 0
+        self.reset()
+
+    def reset(self):
+        """A new stream in the same buffers: nothing pushed, nothing planned, the status word cleared.  No allocation."""
+        self.head, self.planned, self.closed = 0, 0, False
+        self._pending, self._low = [], 0
+        self.n_windows = self.n_passes = 0
+        # the CURRENT pass (a stream has no pass p to ask for: ``pass_table`` is the table itself, not ``_WindowCorpus``'s lookup)
+        self.pass_table, self.pass_base, self.pass_frames, self.pass_windows, self.pass_closing = None, 0, 0, 0, False
+        self.pass_rows = []
+        self.status.zero_()
+
+    def nbytes(self):
+        return int(self.ring.numel() * 2 + self._table.numel() * 8)
+
+    @property
+    def frames(self):
+        """Label frames pushed so far."""
+        return self.head // self.hop_label
+
+    @property
+    def free(self):
+        """Samples ``append`` can take now."""
+        return self._low + self.capacity - self.head
+
+    def append(self, pcm):
+        """pcm int16 (n, 4), any n >= 0 -> the number of samples taken, min(n, ``free``): the rest does not fit until the
+        runnable passes have been launched.  No host synchronisation beyond the staging buffer's own event."""
+        if self.closed:
+            raise ValueError("StreamDeviceCorpus.append: the stream is closed (reset() starts a new one)")
+        if torch.is_tensor(pcm):
+            pcm = pcm.numpy()
+        if getattr(pcm, "dtype", None) != np.int16 or pcm.ndim != 2 or pcm.shape[1] != 4:
+            raise ValueError("StreamDeviceCorpus.append: %s %s, expected int16 (n, 4)"
+                             % (getattr(pcm, "dtype", type(pcm).__name__), tuple(getattr(pcm, "shape", ()))))
+        take = min(int(pcm.shape[0]), self.free)
+        if take <= 0:
+            return 0
+        slot = self._stage_slot
+        self._stage_slot ^= 1
+        if self._stage_ev[slot] is not None:
+            self._stage_ev[slot].synchronize()            # the copies out of this buffer two pushes ago have landed
+        stage = self._stage[slot]
+        stage.numpy()[:take] = pcm[:take]
+        at = self.head % self.capacity
+        first = min(take, self.capacity - at)
+        self.ring[at:at + first].copy_(stage[:first], non_blocking=True)
+        if first < take:                                  # across the seam
+            self.ring[:take - first].copy_(stage[first:take], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.device))
+        self._stage_ev[slot] = ev
+        self.head += take
+        return take
+
+    def runnable(self, closing=False):
+        """The number of passes that can be launched now.  closing: the stream ends here -- the closing window is planned with
+        the steps still runnable, and ``append`` is refused from now on."""
+        if not self.closed:
+            rows = stream_plan(self.window_frames, self.margin_frames, self.hop_frames, self.hop_label, self.planned, self.head,
+                               closing)
+            if rows:
+                self._pending += rows
+                self.planned = rows[-1][3] + rows[-1][4]
+            self.closed = bool(closing)
+        return -(-len(self._pending) // self.batch_size)
+
+    def _next_pass(self):
+        rows = self._pending[:self.batch_size]
+        if not rows:
+            raise ValueError("StreamDeviceCorpus.launch: no window is runnable (runnable() says how many passes are)")
+        del self._pending[:len(rows)]
+        end = rows[-1][3] + rows[-1][4]
+        self.pass_rows = rows + [(0, 0, 0, end, 0, -1, 0, 0)] * (self.batch_size - len(rows))       # empty windows
+        self.pass_base, self.pass_frames, self.pass_windows = rows[0][3], end - rows[0][3], len(rows)
+        self.pass_closing = self.closed and not self._pending
+        self._low = rows[-1][0]
+        self.n_windows += len(rows)
+        self.n_passes += 1
+        slot = self._table_slot
+        self._table_slot ^= 1
+        if self._table_ev[slot] is not None:
+            self._table_ev[slot].synchronize()            # the copy out of this page-locked table two passes ago has landed
+        host = self._table_host[slot]
+        host.numpy()[:] = np.asarray(self.pass_rows, dtype=np.int64)
+        self._table.copy_(host, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.device))
+        self._table_ev[slot] = ev
+        self.pass_table = self._table
+
+    def launch(self, audio_out=None):
+        """The next pass -> audio (batch_size, n_samples, 4) f32 on the device; ``pass_table`` (the rows in HBM), ``pass_rows``
+        (on the host), ``pass_base``, ``pass_frames``, ``pass_windows`` and ``pass_closing`` (the pass holds the closing
+        window) then describe it.  The table goes up from page-locked memory; no host synchronisation.  audio_out: write into
+        this buffer (a recorded forward graph's input)."""
+        audio = self._out(audio_out, (self.batch_size, self.n_samples, 4))
+        self._next_pass()
+        return ops.stream_gather_windows(self.ring, self.head, self.pass_table, audio, self.status)
+
+    def launch_view(self, comb, audio_out=None):
+        """The audio of the CURRENT pass (the last ``launch``) under combination ``comb``: as ``_WindowCorpus.launch_view``."""
+        from .augmentations import COMBINATIONS, MIC_SWAP_COMBS, mic_swap_source
+        who = "StreamDeviceCorpus"
+        comb = int(comb)
+        if self.pass_table is None:
+            raise ValueError("%s.launch_view: no pass has been launched" % who)
+        if not 0 <= comb < len(COMBINATIONS):
+            raise ValueError("%s.launch_view: combination %r is not one of 0..%d" % (who, comb, len(COMBINATIONS) - 1))
+        if self.audio_format == "mic":
+            mic_swap_source(comb)                                # ValueError: no symmetry of the array
+            if self.mic_src is None:
+                self.mic_src = ops.corpus_mic_table({k: mic_swap_source(k) for k in MIC_SWAP_COMBS})
+        audio = self._out(audio_out, (self.batch_size, self.n_samples, 4))
+        return ops.stream_gather_windows(self.ring, self.head, self.pass_table, audio, self.status, comb=comb, rot=self.rot,
+                                         mic_src=self.mic_src)

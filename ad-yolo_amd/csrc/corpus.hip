@@ -29,6 +29,8 @@
 //   corpus_gather_windows_kernel<FORM>  the gather without rotation, the frames past a window's valid count int16 zero, never
 //                                 read; or (rotation test-time augmentation) under one combination for the whole launch
 //   decode_stitch_kernel          each window's kept decoded frames copied into one contiguous run per pass
+// Streaming inference (corpus.py StreamDeviceCorpus, test.py StreamInference) reads windows out of a ring of the live stream:
+//   corpus_gather_windows_kernel<FORM, WindowRing>  the same kernel body with every index taken modulo the ring's capacity
 // The AD-YOLO label arithmetic is done in double, as the host does it (augmentations.rotate_labels on Python floats,
 // datasets.YoloLabelEncoder.encode_events in float64); only the written row is rounded to float32.  The class-wise kernel does
 // no arithmetic at all: the direction vectors come from a table the host builds with its own functions (corpus.xyz_table); with
@@ -646,14 +648,53 @@ __device__ __forceinline__ float4 window_conv(int lo, int hi, const CorpusSrc &s
     return pcm_rot(lo, hi, 1.f, 1.f, 1.f, false);
 }
 
-// grid (blocks per window, W).  Frames at or past ``valid`` are the conversion of int16 zero and are not read from the stream:
-// under a view the padding is turned like every other frame (1e-8f under the signs and the swap).  comb_ok false (a MIC
-// combination that is no symmetry of the array): every window is a bad item.
-template <int FORM>
+// Where a window's frames lie.  WindowLinear: a linear stream of n_total frames, window frame f at pcm[off + f] (nothing to
+// carry: no kernel argument).  WindowRing: ``pcm`` is a ring of ``capacity`` frames that holds the last ones of a live stream
+// of n_total (the head) frames so far, absolute frame s at pcm[s % capacity] (adyolo_stream_gather_windows).  Capacity and
+// offsets are even, so a two-frame 16-byte load never straddles the seam; a window is at most ``capacity`` long, so one
+// conditional subtraction wraps an index.  head % capacity comes from the host (head_mod): no division on the device.
+struct WindowLinear {
+    __device__ __forceinline__ bool bad(int64_t off, int64_t valid, long n_total) const { return off > n_total - valid; }
+    __device__ __forceinline__ int64_t seek(int64_t off, long) { return off; }      // -> the frame the reads are counted from
+    __device__ __forceinline__ long pair(long i) const { return i; }
+    __device__ __forceinline__ long frame(long f) const { return f; }
+};
+
+struct WindowRing {
+    long capacity, head_mod;
+    long pos;                                                     // the window's first frame in the ring (after seek)
+    __device__ __forceinline__ bool bad(int64_t off, int64_t valid, long head) const {
+        return off > head - valid || off < head - capacity;      // not pushed yet, or already overwritten
+    }
+    __device__ __forceinline__ int64_t seek(int64_t off, long head) {               // 0 <= head - off <= capacity
+        pos = head_mod - (long)(head - off);
+        if (pos < 0) pos += capacity;
+        return 0;
+    }
+    __device__ __forceinline__ long pair(long i) const {
+        const long j = (pos >> 1) + i;
+        return j >= (capacity >> 1) ? j - (capacity >> 1) : j;
+    }
+    __device__ __forceinline__ long frame(long f) const {
+        const long j = pos + f;
+        return j >= capacity ? j - capacity : j;
+    }
+};
+
+template <class... Ring> struct WindowOf { typedef WindowLinear type; };
+template <> struct WindowOf<WindowRing> { typedef WindowRing type; };
+
+// Both window gathers, grid (blocks per window, W).  Ring: nothing (the linear gathers: the kernel has the arguments it always
+// had), or one WindowRing (the streaming gather: the same body with every index taken through the ring).  Frames at or past
+// ``valid`` are the conversion of int16 zero and are not read from the stream: under a view the padding is turned like every
+// other frame (1e-8f under the signs and the swap).  comb_ok false (a MIC combination that is no symmetry of the array): every
+// window is a bad item.
+template <int FORM, class... Ring>
 __global__ __launch_bounds__(256) void corpus_gather_windows_kernel(const int16_t *__restrict__ pcm, long n_total,
                                                                     const int64_t *__restrict__ windows, long n, CorpusSrc cs,
                                                                     int comb_ok, float4 *__restrict__ out,
-                                                                    int *__restrict__ status) {
+                                                                    int *__restrict__ status, Ring... ring) {
+    typename WindowOf<Ring...>::type geom{ring...};
     const int w = blockIdx.y;
     const int64_t off = windows[(size_t)w * ADYOLO_WINDOW_WORDS + 0];
     const int64_t valid = windows[(size_t)w * ADYOLO_WINDOW_WORDS + 1];
@@ -664,23 +705,23 @@ __global__ __launch_bounds__(256) void corpus_gather_windows_kernel(const int16_
         for (long i = tid; i < n; i += nth) dst[i] = pad;
         return;
     }
-    if (!comb_ok || off < 0 || (off & 1) || valid < 0 || valid > n || off > n_total - valid) {
+    if (!comb_ok || off < 0 || (off & 1) || valid < 0 || valid > n || geom.bad(off, valid, n_total)) {
         if (tid == 0 && status) atomicOr(status, ADYOLO_CORPUS_BAD_ITEM);
         for (long i = tid; i < n; i += nth) dst[i] = make_float4(0.f, 0.f, 0.f, 0.f);
         return;
     }
-    const int16_t *src = pcm + (size_t)off * 4;                   // even offset: two frames per 16-byte load
+    const int16_t *src = pcm + (size_t)geom.seek(off, n_total) * 4;       // even offset: two frames per 16-byte load
     const long n2 = n >> 1;
     const int4 *s4 = reinterpret_cast<const int4 *>(src);
     const int2 *s2 = reinterpret_cast<const int2 *>(src);
     for (long i = tid; i < n2; i += nth) {
         float4 o0 = pad, o1 = pad;
         if (2 * i + 1 < valid) {
-            const int4 v = s4[i];
+            const int4 v = s4[geom.pair(i)];
             o0 = window_conv<FORM>(v.x, v.y, cs);
             o1 = window_conv<FORM>(v.z, v.w, cs);
         } else if (2 * i < valid) {                               // the last frame of an odd count
-            const int2 v = s2[2 * i];
+            const int2 v = s2[geom.frame(2 * i)];
             o0 = window_conv<FORM>(v.x, v.y, cs);
         }
         dst[2 * i] = o0;
@@ -689,7 +730,7 @@ __global__ __launch_bounds__(256) void corpus_gather_windows_kernel(const int16_
     if ((n & 1) && tid == 0) {
         float4 o = pad;
         if (n - 1 < valid) {
-            const int2 v = s2[n - 1];
+            const int2 v = s2[geom.frame(n - 1)];
             o = window_conv<FORM>(v.x, v.y, cs);
         }
         dst[n - 1] = o;
@@ -878,10 +919,12 @@ extern "C" int adyolo_corpus_classwise_labels(const double *events, const float 
 
 // ------------------------------------------------------------------------------------------------ windowed inference
 namespace adyolo {
-// both window gathers: the checks, the grid of adyolo_corpus_gather and the instance of the form
-template <int FORM>
+// the window gathers: the checks, the grid of adyolo_corpus_gather and the instance of the form.  RING: ``pcm`` is the ring of
+// adyolo_stream_gather_windows, n_total its head, capacity its length
+template <int FORM, bool RING = false>
 static int corpus_gather_windows_launch(const char *name, const int16_t *pcm, long n_total, const int64_t *windows, int W, long n,
-                                        const CorpusSrc &cs, bool comb_ok, float *audio, int *status, void *stream) {
+                                        const CorpusSrc &cs, bool comb_ok, float *audio, int *status, void *stream,
+                                        long capacity = 0) {
     ADYOLO_REQUIRE(pcm && windows && audio, ADYOLO_EINVAL, "%s: null pointer", name);
     ADYOLO_REQUIRE(W > 0 && W < 65536 && n > 0 && n_total >= 0, ADYOLO_EINVAL, "%s: bad shape W=%d n=%ld n_total=%ld", name, W, n,
                    n_total);
@@ -889,6 +932,14 @@ static int corpus_gather_windows_launch(const char *name, const int16_t *pcm, lo
                    "%s: misaligned buffers (pcm / audio 16 bytes, windows 8 bytes)", name);
     int gx = cdiv(n, 256L * 16);                            // the grid of adyolo_corpus_gather
     gx = gx < 1 ? 1 : (gx > 4096 ? 4096 : gx);
+    if constexpr (RING) {
+        ADYOLO_REQUIRE(capacity >= n && !(capacity & 1), ADYOLO_EINVAL, "%s: a ring of %ld frames for windows of %ld (even, >= n)",
+                       name, capacity, n);
+        hipLaunchKernelGGL((corpus_gather_windows_kernel<FORM, WindowRing>), dim3((unsigned)gx, (unsigned)W), dim3(256), 0,
+                           as_stream(stream), pcm, n_total, windows, n, cs, comb_ok ? 1 : 0, (float4 *)audio, status,
+                           WindowRing{capacity, n_total % capacity, 0});
+        return check_launch(name);
+    }
     hipLaunchKernelGGL(corpus_gather_windows_kernel<FORM>, dim3((unsigned)gx, (unsigned)W), dim3(256), 0, as_stream(stream), pcm,
                        n_total, windows, n, cs, comb_ok ? 1 : 0, (float4 *)audio, status);
     return check_launch(name);
@@ -921,6 +972,29 @@ extern "C" int adyolo_corpus_gather_windows_view(const int16_t *pcm, long n_tota
     corpus_rot(rot_host, rot);
     gather_source(rot, comb, cs);
     return corpus_gather_windows_launch<WINDOW_FOA>(name, pcm, n_total, windows, W, n, cs, true, audio, status, stream);
+}
+
+extern "C" int adyolo_stream_gather_windows(const int16_t *ring, long capacity, long head, const int64_t *windows, int W, long n,
+                                            int comb, const float *rot_host, const unsigned int *mic_src_host, float *audio,
+                                            int *status, void *stream) {
+    const char *name = "stream_gather_windows";
+    ADYOLO_REQUIRE(comb < 16, ADYOLO_EINVAL, "%s: combination %d (at most 15)", name, comb);
+    ADYOLO_REQUIRE(comb <= 0 || rot_host || mic_src_host, ADYOLO_EINVAL, "%s: null pointer", name);
+    CorpusSrc cs = {1.f, 1.f, 1.f, false, 0u, 0u, 1.f, 0.f};
+    if (comb <= 0)                                          // no view, or the identity
+        return corpus_gather_windows_launch<WINDOW_PLAIN, true>(name, ring, head, windows, W, n, cs, true, audio, status, stream,
+                                                                capacity);
+    if (mic_src_host) {
+        CorpusMicSrc tab;
+        corpus_mic(mic_src_host, tab);
+        const bool ok = gather_source(tab, comb, cs);
+        return corpus_gather_windows_launch<WINDOW_MIC, true>(name, ring, head, windows, W, n, cs, ok, audio, status, stream,
+                                                              capacity);
+    }
+    CorpusRot rot;
+    corpus_rot(rot_host, rot);
+    gather_source(rot, comb, cs);
+    return corpus_gather_windows_launch<WINDOW_FOA, true>(name, ring, head, windows, W, n, cs, true, audio, status, stream, capacity);
 }
 
 extern "C" int adyolo_decode_stitch(const float *decoded, const int64_t *windows, int W, int Wf, long rec, long pass_base,

@@ -2430,6 +2430,22 @@ def corpus_gather_windows_view(pcm, windows, comb, rot, out, status, *, mic_src=
     return out
 
 
+def stream_gather_windows(ring, head, windows, out, status, *, comb=0, rot=None, mic_src=None):
+    """ring int16 (capacity, 4) on the device, absolute sample s of a live stream at ``ring[s % capacity]``, ``head`` samples
+    pushed so far; windows int64 (W, 8) with ABSOLUTE sample offsets -> out (W, n, 4) float32: the bits of
+    ``corpus_gather_windows`` (comb <= 0) or ``corpus_gather_windows_view`` (comb > 0: rot / mic_src as there) on the stream
+    laid out linearly (adyolo_hip.h ``adyolo_stream_gather_windows``).  A window that is odd, not pushed yet (offset + valid >
+    head) or already overwritten (offset < head - capacity): zeros and status bit 2.  capacity odd or < n, comb >= 16: raises.
+    No allocation, no sync."""
+    name = "stream_gather_windows"
+    w = _gather_windows_args(name, ring, windows, out, status)
+    if int(comb) > 0 and mic_src is None and rot is None:
+        raise _lib.AdyoloHipError("%s: the FOA form needs the rotation table" % name)
+    _c("adyolo_stream_gather_windows", _p(ring), ring.shape[0], int(head), _p(windows), w, out.shape[1], int(comb),
+       _host_table(rot), _host_table(mic_src), _p(out), _p(status), _stream())
+    return out
+
+
 def decode_stitch(decoded, windows, window_frames, pass_base, out, status):
     """decoded (W * window_frames, ...) float32 (``LabelPostProcessor.decode_device`` of a pass of W windows) and windows int64
     (W, 8) on the device -> out (capacity, ...) float32 with the same trailing shape: window w's frames [src_lo, src_lo + n)

@@ -758,11 +758,11 @@ class LabelPostProcessor:
         return self.select(self.decode(output, borrow=True))       # consumed at once: no second host copy
 
 
-def write_seld_output_file(file_pth, output: dict, tracks=None):
+def write_seld_output_file(file_pth, output: dict, tracks=None, mode="w"):
     """reference test.py:26-30: rows ``frame,class,0,x,y,z``.  tracks: {frame: [id, ...]} parallel to ``output``
     (``track_groups`` of the ids ``track_rows`` returns): the third column, the DCASE track index, is the row's id instead
-    of 0."""
-    with open(file_pth, "w") as f:
+    of 0.  mode: "a" appends the rows to the file (a live stream's frames as they become final)."""
+    with open(file_pth, mode) as f:
         for frame_idx in output.keys():
             ids = None if tracks is None else tracks[frame_idx]
             if ids is not None and len(ids) != len(output[frame_idx]):

@@ -475,6 +475,12 @@ class _CsvWriter:
             self._tables[key] = dev[at:at + len(t)]
             at += len(t)
 
+    def forget(self):
+        """Drop the uploaded segment tables: a live stream has a new one per pass, used once.  After a ``fetch``, which has
+        synchronised behind the upload and the kernel that read the table."""
+        self._tables.clear()
+        del self._pinned[:]
+
     def fetch(self, rows, counts, table, ids=None):
         """-> (the bytes of the call on the host, a uint8 array valid until the next fetch; seg_bytes as a list)"""
         from . import ops
@@ -892,3 +898,183 @@ def score_output_folder(params, ref_dir, output_pth, is_jackknife=False):
         "homogenous": ComputeSELDResultsFromEventOverlap(params, ref_dir, classwise_overlap_test=True)
         .get_SELD_Results(output_pth, is_jackknife),
     }
+
+
+# ------------------------------------------------------------------------------------------------------ a live stream
+class _StreamTracker:
+    """The device half of tracking through a live stream: ``_RunTracker`` without a plan made in advance.  Every pass is ONE
+    segment {0, n, continues = not the first pass, open = the stream goes on}; the hold is ``track_hold`` itself, one carry.
+    The emitted frames follow from the frames walked so far: the carried held frames, then the pass's without the newly held
+    ones.  ``open`` is set by the session before each pass; ``base`` is then the first emitted frame on the stream's axis."""
+
+    def __init__(self, tracking, device):
+        from .postprocess import track_hold
+        self.opts = _track_opts(tracking, "tracking")
+        self.hold = track_hold(self.opts["max_gap"], self.opts["min_len"])
+        self.device = torch.device(device)
+        self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.carry, self._buffers, self._segments = None, {}, {}
+        self.walked, self.open, self.base = 0, True, 0
+
+    def reset(self):
+        if self.carry is not None:
+            self.carry.zero_()
+        self.walked, self.open, self.base = 0, True, 0
+        self.status.zero_()
+
+    def _segment(self, key):
+        """The one-row segment table on the device: uploaded once per (frames, continues, open), from page-locked memory."""
+        seg = self._segments.get(key)
+        if seg is None:
+            pinned = torch.tensor([[0, key[0], key[1], key[2]]], dtype=torch.int32).pin_memory()
+            seg = self._segments[key] = (pinned.to(self.device, non_blocking=True), pinned)
+        return seg[0]
+
+    def tracked(self, postprocessor, rows, counts, n_clips, trim, p=None):
+        from . import ops
+        if self.carry is None:
+            self.carry = ops.track_carry(self.device, postprocessor.nb_classes, self.hold)
+        n = counts.numel()
+        buf = self._buffers.get(n)
+        if buf is None:
+            buf = self._buffers[n] = ops.track_run_buffers(self.device, n, postprocessor.nb_classes, self.hold)
+        held = min(self.hold, self.walked)
+        emitted = held + n - (min(self.hold, self.walked + n) if self.open else 0)
+        self.base = self.walked - held
+        seg = self._segment((n, int(self.walked > 0), int(self.open)))
+        self.walked += n
+        return postprocessor.track_device_run(rows, counts, seg, self.opts, self.hold, self.carry, buf=buf, status=self.status,
+                                              trim=trim, emitted=emitted)
+
+
+class StreamInference:
+    """Inference on ONE live stream (``corpus.StreamDeviceCorpus``): push audio as it comes, get the detections of the frames
+    that have become final.  A recording pushed in any pieces and closed gives, byte for byte, the CSV file
+    ``infer_epoch_corpus`` writes for it (with the default hop, at ``batch_size`` 1: the same windows; tracking, tta and
+    device_csv alike).
+
+        session = StreamInference(corpus, model, features, postprocessor, forward=ForwardGraphs(...), output_file="live.csv")
+        rows, ids = session.push(pcm)            # int16 (n, 4), any n
+        rows, ids = session.close()
+
+    ``push`` appends the samples and runs every runnable pass -> ({frame: [[class, x, y, z], ...]}, {frame: [id, ...]} or None
+    without tracking) of the frames that became final: frames on the stream's own axis, ascending, never revised later.  A push
+    larger than the ring's free space is taken in slices between the passes.  A push that completes no window copies the
+    samples and returns empties, with no synchronisation.  ``close`` runs the closing window (the tracker's segment not open,
+    so its carry is flushed), returns the rest and checks the status words of the corpus, the merge and the tracker in one
+    copy.  ``frames_final``: the frames final so far.  ``reset()``: a new stream -- the corpus, the tracker's carry and ids,
+    the output file -- in the same buffers and graphs.
+
+    Per pass: ``_forward_decode`` (the ring gather into the graph's static input when ``forward`` has one) ->
+    ``ops.decode_stitch`` -> ``_select_rows`` (tta: the further views through ``_ViewMerge``; tracking: ``track_device_run``
+    with one segment and one carry), then ONE host synchronisation, the copy of the rows, as in ``infer_epoch_corpus``.  All
+    passes of a stream have one shape: ``forward`` records one graph.
+
+    Latency (``corpus.stream_plan``): a frame is final at most margin + hop after it was pushed, with tracking a further
+    ``postprocess.track_hold`` frames later; the rest on ``close``.
+
+    output_file: every pass appends its lines (the format of ``write_seld_output_file``).  device_csv=True (needs
+    output_file): the lines are formatted on the device (``_CsvWriter``) and go to the file only -- ``push`` and ``close``
+    then return empty dicts, nothing else is copied."""
+
+    def __init__(self, corpus, model, features, postprocessor, forward=None, tracking=None, tta=None, device_csv=False,
+                 output_file=None):
+        if _csv_flag(device_csv, "StreamInference") and output_file is None:
+            raise ValueError("StreamInference: device_csv=True formats the lines of output_file; none was given")
+        self.corpus, self.model, self.features, self.postprocessor, self.forward = corpus, model, features, postprocessor, forward
+        self.output_file = output_file
+        self.csv = _CsvWriter(corpus.device) if device_csv else None
+        self.merge = None
+        if tta is not None:
+            self.merge = _ViewMerge(tta, postprocessor, corpus.device, max_frames=corpus.batch_size * corpus.window_frames)
+        self.tracker = _StreamTracker(tracking, corpus.device) if tracking is not None else None
+        self._stitched = None
+        model.eval()
+        self.reset()
+
+    def reset(self):
+        self.corpus.reset()
+        if self.tracker is not None:
+            self.tracker.reset()
+        if self.merge is not None:
+            self.merge.status.zero_()
+        self.frames_final, self.passes = 0, 0
+        if self.output_file is not None:
+            open(self.output_file, "wb").close()
+
+    def _view(self, comb):
+        """One view of the pass (None: ``launch``, the next pass itself) -> the pass's run of decoded frames, stitched."""
+        from . import ops
+        c = self.corpus
+        b, wf = c.batch_size, c.window_frames
+        launch = c.launch if comb is None else (lambda out: c.launch_view(comb, out))
+        _, _, dec = _forward_decode(launch, (b, c.n_samples, 4), self.model, self.features, self.postprocessor, self.forward)
+        if dec.shape[0] != b * wf:
+            raise ValueError("StreamInference: %d decoded frames from %d windows of %d label frames (the model's frame rate is "
+                             "not the label hop's)" % (dec.shape[0], b, wf))
+        if self._stitched is None:
+            self._stitched = torch.empty_like(dec)
+        ops.decode_stitch(dec, c.pass_table, wf, c.pass_base, self._stitched, c.status)
+        return self._stitched[:c.pass_frames]
+
+    def _pass(self, rows_out, ids_out):
+        from . import ops
+        c, tracker = self.corpus, self.tracker
+        run = self._view(None)
+        if tracker is not None:
+            tracker.open = not c.pass_closing
+        more = (self._view(v) for v in _further_views(self.merge))
+        rows, counts, ids = _select_rows(self.postprocessor, run, more, self.merge, tracker, 1, self.csv is None)
+        self.passes += 1
+        base = c.pass_base if tracker is None else tracker.base
+        n = counts.numel()
+        if not n:                                                            # (a tracked pass may hold all its frames back)
+            return
+        self.frames_final = base + n
+        if self.csv is not None:
+            import numpy as np
+            data, at = self.csv.fetch(rows, counts, np.asarray([[0, base]], dtype=np.int32), ids)
+            self.csv.forget()                            # (one table per pass, used once: a stream has no end to plan for)
+            if at[1] > at[0]:
+                with open(self.output_file, "ab") as f:
+                    f.write(data[at[0]:at[1]])
+            return
+        rows_h, counts_h, *ids_h = [t.numpy() for t in ops.to_host_many(*(t for t in (rows, counts, ids) if t is not None))]
+        found = {base + f: v for f, v in group_rows(rows_h, counts_h, 1)[0].items()}
+        found_ids = None
+        if ids is not None:
+            from .postprocess import track_groups
+            found_ids = {base + f: v for f, v in track_groups(ids_h[0], counts_h, 1)[0].items()}
+            ids_out.update(found_ids)
+        rows_out.update(found)
+        if self.output_file is not None and found:
+            write_seld_output_file(self.output_file, found, found_ids, mode="a")
+
+    def _run(self, closing, rows_out, ids_out):
+        n = self.corpus.runnable(closing)
+        with torch.no_grad():
+            for _ in range(n):
+                self._pass(rows_out, ids_out)
+        return n
+
+    def push(self, pcm):
+        import numpy as np
+        if torch.is_tensor(pcm):
+            pcm = pcm.numpy()
+        rows_out, ids_out = {}, ({} if self.tracker is not None else None)
+        at, total = 0, int(np.shape(pcm)[0])
+        while True:
+            took = self.corpus.append(pcm[at:])
+            at += took
+            ran = self._run(False, rows_out, ids_out)
+            if at >= total:
+                return rows_out, ids_out
+            if not took and not ran:                                         # (the ring's smallest size rules this out)
+                raise RuntimeError("StreamInference.push: the ring is full and no window is runnable")
+
+    def close(self):
+        rows_out, ids_out = {}, ({} if self.tracker is not None else None)
+        self._run(True, rows_out, ids_out)
+        self.frames_final = self.corpus.frames
+        _read_status(self.corpus, None, self.merge, self.tracker)
+        return rows_out, ids_out

@@ -993,6 +993,25 @@ int  adyolo_decode_stitch(const float *decoded, const int64_t *windows, int W, i
                           long out_frames, int *status, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Streaming inference (corpus.StreamDeviceCorpus, test.StreamInference): windows gathered out of a ring that holds the last
+ * samples of ONE live stream.
+ *   ring     DEVICE int16 [capacity][4]: absolute sample s of the stream (counted from its start) lives at ring[s % capacity];
+ *            the caller copies pushed samples there (at most two copies per push, split at the seam)
+ *   head     samples pushed so far, by value
+ *   windows  as above, word 0 an ABSOLUTE sample offset of the stream
+ * adyolo_stream_gather_windows: the bits of adyolo_corpus_gather_windows (comb <= 0) or adyolo_corpus_gather_windows_view
+ *   (comb > 0; rot_host / mic_src_host as there, both may be NULL with comb <= 0) on the same stream laid out linearly with
+ *   n_total = head: the conversion, the padding past valid, valid = 0 and both forms under a view.  One kernel body with the
+ *   linear gathers, every index taken modulo the capacity; capacity and offsets are even, so the 16-byte two-frame loads never
+ *   straddle the seam.  A bad window -- an odd or negative offset, valid outside [0, n], offset + valid > head (not pushed
+ *   yet) or offset < head - capacity (already overwritten) -- gives zeros and ADYOLO_CORPUS_BAD_ITEM.  EINVAL before any
+ *   launch: a null or misaligned pointer (ring / audio 16 bytes, windows 8), capacity odd or < n, comb >= 16.
+ * ---------------------------------------------------------------------------------------------- */
+int  adyolo_stream_gather_windows(const int16_t *ring, long capacity, long head, const int64_t *windows, int W, long n, int comb,
+                                  const float *rot_host, const unsigned int *mic_src_host, float *audio, int *status,
+                                  void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Sample-rate conversion of whole recordings (csrc/resample.hip; resample.plan builds the table, corpus.InferDeviceCorpus
  * and resample.resample_device call it): a polyphase FIR in integer arithmetic from a native four-channel stream into the
  * int16 stream the calls above read.  The result is defined bit for bit:
